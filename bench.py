@@ -11,10 +11,14 @@ torch or loaded any library that touches the GPU, relays the ranks' output and e
 JSON line with n_gpus == N came back).  Started by torch.distributed.run itself (the driver's N>1 form) it is one of the ranks.
 It never prints an n_gpus: 1 line for --gpus N > 1.
 
-Three configurations of the same solve are timed in the same run (N=1; on several GPUs only the first):
+A plain run (`--gpus N --steps K --warmup W`) times only the headline configuration and prints its line:
   headline          -ksp_type cghipmi355x (the plug-in's registered CG, fused sweeps), the matrix's VALUE ARRAY STREAMED
                     (-mat_hipmi355x_value_patterns 0): what every matrix gets, constant coefficients or not.  value,
                     ms_per_step, roofline, spmv_gbps, ksp_* describe THIS leg.
+--dump-outputs DIR writes what the timed solve hands its caller after its last step (a seeded sample of the iterate x, the residual
+norm) as float64 .npy files; the inputs are the same in every run with the same arguments.
+
+--full adds everything else, in the same run.  Two more configurations of the same solve are timed (N=1):
   value_patterns    the same solver with the library's default for this matrix: P7 has constant coefficients, its rows come
                     from a 27-entry dictionary and the product does not read the value array (the product carries the same bits).
   op_by_op          -ksp_type cg: the plain restatement of PETSc's own KSPSolve_CG -- what an UNCHANGED PETSc program drives over
@@ -22,19 +26,20 @@ Three configurations of the same solve are timed in the same run (N=1; on severa
                     them as one fused sweep (same bits); ksp_its_per_sec_every_call_its_own_kernel: with that switched off.
 After the timed legs, outside any timed region, the run CHECKS ITSELF (N=1): one headline SpMV against the value-pattern SpMV bit
 for bit and against the row sums the operator has by construction, and the headline solve's x against the op_by_op solve's x
-(`checks` in the line; a failed check exits non-zero and prints no line).
+(`checks` in the line; a failed check exits non-zero and prints no line).  Then the STREAM-style legs (`stream`) and cpu_baseline.
 
-Two series.  `value` is WEAK scaling (n^3 rows per GPU).  `strong` in the same line is the STRONG-scaling point of SURVEY 8(d)
+Two series.  `value` is WEAK scaling (n^3 rows per GPU).  `strong` (--full) is the STRONG-scaling point of SURVEY 8(d)
 config 3: the cube P7(2n) (= P7(512) at the default n) split into N z-slabs, headline solver only; on 8 GPUs the two coincide.
 
 N > 1 additionally reports `multi_gpu`: bytes per halo message, busy time of the halo stream per SpMV, how much of it lies inside
-the diagonal-block SpMV (overlap), what the compute stream still waits for, halo GB/s per link, microseconds per scalar all-reduce.
+the diagonal-block SpMV (overlap), what the compute stream still waits for, halo GB/s per link; with --full also microseconds per
+scalar all-reduce and the N-rank self-checks (`checks`).
 
 Every fraction in the line is BYTES MOVED / time / 8 TB/s: PMC-measured bytes per launch (profiles/bench_pmc_summary.csv,
 quoted only while its stamp matches the kernel sources) or, failing that, the kernel's own byte model.  What the same time
 would be worth in the reference's algorithmic bytes (CSR 12 B/nnz + ..., 17 vector passes) is reported
 separately as effective_gbps_vs_reference_bytes and never as a fraction of the roof.
-cpu_baseline: the oracle's C restatement of the same solve on the host cores, bounded sample (rank 0, N=1 only).
+cpu_baseline (--full): the oracle's C restatement of the same solve on the host cores, bounded sample (rank 0, N=1 only).
 """
 import argparse
 import ctypes as C
@@ -69,7 +74,15 @@ def parse_args(argv=None):
                          "strong = the cube P7(2n) split over the GPUs, nothing else")
     ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling point")
     ap.add_argument("--no-stream", action="store_true", help="skip the STREAM-style legs (what the memory system gives the library's own copy / triad / read-only kernels)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the value_patterns and op_by_op legs, the self-checks, the STREAM-style legs, cpu_baseline, "
+                         "the strong-scaling point and (N > 1) the all-reduce latency; the --no-* and --headline-only options trim this")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed solve returns (seeded sample of x, residual norm) as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def launch_ranks(args):
@@ -353,6 +366,20 @@ def main():
                     "spmv_products_timed": int(nprod),
                     "halo_ms_per_rank": [round(r_[0], 5) for r_ in rows], "halo_exposed_ms_per_rank": [round(r_[2], 5) for r_ in rows]}
 
+    def dump_outputs(case, ksp):
+        """--dump-outputs DIR: what the timed solve returns to its caller after its last step, as float64 .npy files -- the iterate x
+        (a fixed, seeded sample of 2^21 / N of this rank's entries when it has more; x_index = their positions) and the residual norm
+        the solver reports.  The inputs (P7, b = A 1, x0 = 0, exactly K steps) are the same in every run with the same arguments."""
+        d = args.dump_outputs
+        os.makedirs(d, exist_ok=True)
+        sfx = "" if world == 1 else "_rank%d" % rank
+        x = case.x.array()
+        m = (1 << 21) // world
+        idx = np.arange(x.size) if x.size <= m else np.sort(np.random.default_rng(20240607).choice(x.size, size=m, replace=False))
+        np.save(os.path.join(d, "x%s.npy" % sfx), x[idx])
+        np.save(os.path.join(d, "x_index%s.npy" % sfx), idx.astype(np.float64))
+        np.save(os.path.join(d, "residual_norm%s.npy" % sfx), np.array([ksp.rnorm], dtype=np.float64))
+
     n = args.n
     fused_dot = world == 1
     # the registered CG (-ksp_cg_fused 4, its default): on one GPU p'w comes out of the SpMV pass -> AYPX 3 + fused update 8 = 11 vector
@@ -395,7 +422,9 @@ def main():
         if not strong_possible:
             raise SystemExit("--scaling strong: %d planes do not split over %d ranks" % (2 * n, world))
         case = Case(*strong_dims(), use_pmc=False)
-        _, head, th = headline_of(case)
+        ksp_strong, head, th = headline_of(case)
+        if args.dump_outputs:
+            dump_outputs(case, ksp_strong)
         out = {"metric": "KSP CG+Jacobi iterations/s x unknowns (3-D 7-pt Poisson P7(%d), STRONG scaling: the same cube on every N); ksp_its_per_sec and spmv_gbps are BASELINE.json's two quantities" % (2 * n),
                "value": head["value"], "unit": "Mdof-it/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": head["ms_per_step"],
                "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -415,6 +444,8 @@ def main():
     case = Case(*weak_dims(), use_pmc=True)
     mloc, unknowns = case.mloc, case.mloc * world
     ksp_fused, head, th = headline_of(case)
+    if args.dump_outputs:
+        dump_outputs(case, ksp_fused)                  # before the --full legs reuse case.x
     if os.environ.get("BENCH_NO_SPMV_EVENTS"):
         print("no-events run: %.5f ms/step" % head["ms_per_step"], flush=True)
         return
@@ -452,13 +483,14 @@ def main():
         out["roofline_cg_update"] = upd
     out["legs"] = {"headline": {kk: vv for kk, vv in head.items() if kk not in ("spmv", "cg_update")}}
     if world > 1:
-        mg = case.multi_gpu(th, head["spmv"]["avg_launch_ms"])
+        out["multi_gpu"] = case.multi_gpu(th, head["spmv"]["avg_launch_ms"])
+    if world > 1 and args.full:
+        mg = out["multi_gpu"]
         sync_us, b2b_us = C.c_double(), C.c_double()
         L.PetscCommDeviceAllreduceLatency(comm, 50, C.byref(sync_us), C.byref(b2b_us))       # collective: every rank calls it
         mg["allreduce_us_per_reduction"] = {"host_sync_after_each": round(sync_us.value, 2), "queued_back_to_back": round(b2b_us.value, 2),
                                             "what": "one-double ncclAllReduce on the compute stream's communicator, 50 repetitions; the fused CG makes 2 per iteration "
                                                     "(p'w; the update's three sums in one), KSPSolve_CG op by op 3" if not staged else "host-staged transport: not measured"}
-        out["multi_gpu"] = mg
         # ---- self-checks of the N-rank line (every rank asserts; outside the timed region): the parallel product with its halo
         # exchange applied to 1 must give the operator's row sums on this rank's rows -- a halo that brought the wrong planes, or none,
         # cannot pass --, and the solve must have reduced the true residual b - A x, recomputed with separate calls
@@ -477,7 +509,7 @@ def main():
         out["checks"] = {"mpiaij_spmv_times_ones_equals_row_sums_on_every_rank": True, "true_residual_after_K_steps": nr_.value / nb_.value}
         del ychk
 
-    if world == 1 and not args.headline_only:
+    if args.full and world == 1 and not args.headline_only:
         nvpat = case.nvpat
         timed = case.timed
         # ---- leg 2: the library's default for THIS matrix (constant coefficients: rows from a dictionary) ----
@@ -550,7 +582,7 @@ def main():
         L.MatHIPMI355XSetValuePatterns(timed, 1)
         del xs, ys, rv
 
-    if world == 1 and not args.no_stream and not args.headline_only:
+    if args.full and world == 1 and not args.no_stream and not args.headline_only:
         # ---- what the memory system gives plain streams in THIS run (SURVEY 8d "Roofline": achievable copy / triad rate next to the peak):
         # the library's own VecCopy (1 read, 1 write), VecWAXPY (2 reads, 1 write) and VecDot (2 reads) on vectors of the workload's
         # size (134 MB each at 256^3: they partly live in the 256 MB Infinity Cache, as the solve's do) and of 1 GiB (nothing cached);
@@ -585,7 +617,7 @@ def main():
                 out[key]["frac_of_achievable_stream"] = round(out[key]["achieved"] / ach, 4)
                 out[key]["achievable_stream_gbps"] = ach
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import orc
         ai, aj, aa = case.csr
         # the same workload, bounded sample: the first cpu_its iterations of the same solve on one host core
@@ -616,7 +648,7 @@ def main():
         del bref
 
     # ------------------------------------------------------------------ strong series: the cube P7(2n) on these N GPUs ------------------------------------------------------------------
-    if not args.no_strong and not args.headline_only and strong_possible:
+    if args.full and not args.no_strong and not args.headline_only and strong_possible:
         if (case.nx, case.ny, case.nz) == strong_dims():
             out["strong"] = strong_point(case, head, th)     # 8 GPUs at the default n: the weak case IS the cube
             out["strong"]["what"] += " (the weak-scaling case of this run: the two series meet here)"

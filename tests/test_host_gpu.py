@@ -2726,3 +2726,39 @@ def test_noting_follows_the_options_database(P):
     assert res["-vec_hipmi355x_defer 0"][3] == 0 and res["-vec_hipmi355x_defer 1"][3] >= res["-vec_hipmi355x_defer 1"][2] - 1 and res[""][3] == res["-vec_hipmi355x_defer 1"][3]
     for k in ("-vec_hipmi355x_defer 1", ""):
         assert np.array_equal(res[k][0], res["-vec_hipmi355x_defer 0"][0]) and np.array_equal(res[k][1], res["-vec_hipmi355x_defer 0"][1])
+
+
+def test_bench_plain_line_and_dumped_outputs(P, tmp_path):
+    """bench.py --gpus 1 --steps K --warmup W prints the headline line alone (the other legs, the checks, the stream legs, the CPU
+    baseline and the strong point are --full's); --dump-outputs DIR writes what the timed solve returns after exactly K steps as
+    float64 .npy: x (all of it at this size) equals the oracle's CG+Jacobi iterate after K steps from x0 = 0 to 1e-10 relative, the
+    residual norm its last history entry, and a second run writes the same bits."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, steps = 24, 7
+
+    def run(d):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+                            "--grid-n", str(n), "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = {k: np.load(os.path.join(d, k + ".npy")) for k in ("x", "x_index", "residual_norm")}
+        assert all(a.dtype == np.float64 for a in out.values())
+        return json.loads(lines[0]), out
+
+    line, a = run(tmp_path / "a")
+    assert line["n_gpus"] == 1 and line["steps"] == steps and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "Mdof-it/s" and line["higher_is_better"] is True and line["dtype"] == "f64" and "metric" in line
+    assert list(line["legs"]) == ["headline"] and not {"checks", "stream", "cpu_baseline", "strong"} & set(line)
+    ai, aj, aa = P.gen_poisson7(n, n, n)
+    b = orc.spmv(ai, aj, aa, np.ones(n ** 3))
+    xr, hist, its, _ = orc.ksp_solve(ai, aj, aa, b, ksp="cg", pc="jacobi", rtol=0.0, abstol=1e-300, dtol=1e300, max_it=steps)
+    assert its == steps and np.array_equal(a["x_index"], np.arange(n ** 3, dtype=np.float64))
+    assert np.max(np.abs(a["x"] - xr)) <= 1e-10 * np.max(np.abs(xr))
+    assert abs(a["residual_norm"][0] - hist[-1]) <= 1e-10 * hist[-1]
+    _, b2 = run(tmp_path / "b")
+    for k in a:
+        assert np.array_equal(bits(a[k]), bits(b2[k])), k

@@ -2,9 +2,10 @@
 bench.py reads for roofline.traffic.
 
 Run on the GPU box (from the repo root; rocprofv3 wants `cd /tmp && export TMPDIR=/tmp` first):
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_f -o f -- python3 bench.py --steps 10 --warmup 2
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_w -o w -- python3 bench.py --steps 10 --warmup 2
-  python3 tests/tools/pmc_summary.py gpurun_out/pmc_f gpurun_out/pmc_w > gpurun_out/pmc_summary.csv
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT/pmc_f -o f -- python3 bench.py --full --steps 10 --warmup 2
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d OUT/pmc_w -o w -- python3 bench.py --full --steps 10 --warmup 2
+  python3 tests/tools/pmc_summary.py OUT/pmc_f OUT/pmc_w > OUT/pmc_summary.csv
+(OUT: any scratch directory.)
 FETCH_SIZE / WRITE_SIZE are in KB; on gfx950 FETCH_SIZE reads 1/2 of the fetched bytes (profiles/r01_fetch_calibration.md) --
 the factor is applied by the reader (bench.py), not here."""
 import csv

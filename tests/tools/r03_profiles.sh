@@ -25,8 +25,8 @@ pmc() {    # name, counters (space separated), [--stamp], command...
 }
 set -x
 # the contract line: JSON, kernel summary of the same command, the two PMC passes behind roofline.traffic (stamped with the kernel sources)
-stats bench python3 $R/bench.py --steps 20 --warmup 3 || exit 1
-pmc bench "FETCH_SIZE WRITE_SIZE" --stamp python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline
+stats bench python3 $R/bench.py --full --steps 20 --warmup 3 || exit 1
+pmc bench "FETCH_SIZE WRITE_SIZE" --stamp python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline
 # ILU(0) application on the FEM stand-in: node-blocked sync-free solves
 python3 $T/fem_ilu_apply.py > $O/ilu_fem.log 2>&1 || exit 1
 stats ilu_fem python3 $T/fem_ilu_apply.py || exit 1
@@ -47,5 +47,5 @@ python3 $T/solver_bench.py 256 120 > $O/solver_bench_value_patterns.log 2>&1 || 
 stats gmres python3 $T/solver_bench.py 256 120 "-mat_hipmi355x_value_patterns 0" gmres:jacobi || exit 1
 # last, so that the JSON reads the freshly stamped counters
 cp $O/bench_pmc_summary.csv $R/profiles/bench_pmc_summary.csv
-python3 $R/bench.py > $O/bench_n1.json 2> $O/bench_n1.err || exit 1
+python3 $R/bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err || exit 1
 tail -c 1500 $O/bench_n1.json

@@ -28,10 +28,10 @@ has() { case " $PARTS " in *" $1 "*) return 0;; esac; return 1; }
 set -x
 if has bench; then
   # the contract line: kernel summary of the same command, the two PMC passes behind roofline.traffic (stamped with the kernel sources), then the JSON
-  stats bench python3 $R/bench.py --steps 20 --warmup 3 --no-strong || exit 1
-  pmc bench "FETCH_SIZE WRITE_SIZE" --stamp python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-strong
+  stats bench python3 $R/bench.py --full --steps 20 --warmup 3 --no-strong || exit 1
+  pmc bench "FETCH_SIZE WRITE_SIZE" --stamp python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-strong
   cp $O/bench_pmc_summary.csv $R/profiles/bench_pmc_summary.csv
-  python3 $R/bench.py > $O/bench_n1.json 2> $O/bench_n1.err || exit 1
+  python3 $R/bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err || exit 1
   tail -c 1200 $O/bench_n1.json
   # the strong-scaling point alone (P7(512) on this one GPU): kernel summary and traffic
   stats bench_p7_512 python3 $R/bench.py --scaling strong --steps 20 --warmup 3 --no-cpu-baseline || exit 1
