@@ -87,7 +87,7 @@ PetscErrorCode MatCreate_SeqAIJHIPMI355X(Mat B) {
   seqaij_parent.assemblyend = B->ops->assemblyend;
   seqaij_parent.destroy = B->ops->destroy;
   ierr = PetscNewLog(B, Mat_SeqAIJHIP, &d);CHKERRQ(ierr);
-  d->uploaded_state = -1; d->t_state = -1; d->pattern_nz = -1;
+  mirror_reset(d);
   B->spptr = d;
   B->ops->mult             = MatMult_SeqAIJHIP;
   B->ops->multadd          = MatMultAdd_SeqAIJHIP;

@@ -96,7 +96,7 @@ PetscErrorCode MatCreate_SeqBAIJHIPMI355X(Mat B) {
   seqbaij_parent.destroy = B->ops->destroy;
   ierr = PetscObjectQueryFunction((PetscObject)B, "MatSeqBAIJSetPreallocation_C", (void (**)(void))&seqbaij_parent_prealloc);CHKERRQ(ierr);
   ierr = PetscNewLog(B, Mat_SeqAIJHIP, &d);CHKERRQ(ierr);
-  d->uploaded_state = -1; d->t_state = -1; d->pattern_nz = -1;
+  mirror_reset(d);
   d->baij_parent = PETSC_TRUE;
   B->spptr = d;
   B->ops->mult        = MatMult_SeqAIJHIP;            /* bs > 1: mi355x_spmv_bsr_planned / mi355x_spmv_bsr4_mfma (-mat_hipmi355x_baij4) */

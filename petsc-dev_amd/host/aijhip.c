@@ -12,6 +12,8 @@
 PetscErrorCode MatSeqAIJGetArrays(Mat A, PetscInt *m, const PetscInt **i, const PetscInt **j, const PetscScalar **a);
 static PetscErrorCode device_free(Mat A);
 static PetscBool device_values_current(Mat A);
+/* the device copy is to be built again from the host at its next use */
+static void mirror_reset(Mat_SeqAIJHIP *d) { d->uploaded_state = -1; d->pattern_nz = -1; }
 
 #if !defined(PETSCHIPMI355X_WITH_PETSC)   /* inside a PETSc tree the parent type MATSEQAIJ owns the container and its assembly (aij.c) */
 /* ---------------------------------------------------------------- host container */
@@ -173,59 +175,150 @@ static PetscErrorCode MatSetFromOptions_SeqAIJHIP(Mat A) {
     ierr = PetscOptionsGetInt(HipObjPrefix(A), hopt_name[k], &v, &set);CHKERRQ(ierr);
     if (set && (!d->opt_set[k] || d->opt[k] != v)) {
       d->opt[k] = v; d->opt_set[k] = PETSC_TRUE;
-      d->uploaded_state = -1; d->pattern_nz = -1;            /* the analyses run again with the new choice */
+      mirror_reset(d);                                       /* the analyses run again with the new choice */
     }
   }
   return 0;
 }
 
 /* ---------------------------------------------------------------- device mirror */
+static void form_free(HipDevForm *f) {
+  if (f->i) mi355x_free(f->i);
+  if (f->j) mi355x_free(f->j);
+  if (f->a) mi355x_free(f->a);
+  if (f->perm) mi355x_free(f->perm);
+  if (f->plan) mi355x_spmv_plan_destroy(f->plan);
+  if (f->tiled) mi355x_spmv_tiled_destroy(f->tiled);
+  memset(f, 0, sizeof(*f));
+}
+static void batch_map_free(Mat_SeqAIJHIP *d) {
+  if (d->bm_order) mi355x_free(d->bm_order);
+  if (d->bm_segptr) mi355x_free(d->bm_segptr);
+  if (d->bm_segslot) mi355x_free(d->bm_segslot);
+  d->bm_order = d->bm_segptr = d->bm_segslot = NULL;
+}
+/* the arrays of the old pattern go; counts, requests, options, timing and (harness) the triangular factors outlive them */
 static PetscErrorCode device_free(Mat A) {
   Mat_SeqAIJHIP *d = SD(A);
   if (!d) return 0;
   { PetscErrorCode ierr = VecHIPProductMatrixChanges(A);CHKERRQ(ierr); }   /* a noted product of this matrix runs while its arrays exist */
-  if (d->d_i) mi355x_free(d->d_i);
-  if (d->d_j) mi355x_free(d->d_j);
-  if (d->d_a) mi355x_free(d->d_a);
-  if (d->plan) mi355x_spmv_plan_destroy(d->plan);
-  if (d->t_i) mi355x_free(d->t_i);
-  if (d->t_j) mi355x_free(d->t_j);
-  if (d->t_a) mi355x_free(d->t_a);
-  if (d->t_plan) mi355x_spmv_plan_destroy(d->t_plan);
-  if (d->t_tiled) { mi355x_spmv_tiled_destroy(d->t_tiled); d->t_tiled = NULL; }
-  if (d->t_perm) mi355x_free(d->t_perm);
-  if (d->tiled) mi355x_spmv_tiled_destroy(d->tiled);
-  if (d->b_i) mi355x_free(d->b_i);
-  if (d->b_j) mi355x_free(d->b_j);
-  if (d->b_a) mi355x_free(d->b_a);
-  if (d->b_perm) mi355x_free(d->b_perm);
-  if (d->b_plan) mi355x_spmv_plan_destroy(d->b_plan);
-  if (d->tb_i) mi355x_free(d->tb_i);
-  if (d->tb_j) mi355x_free(d->tb_j);
-  if (d->tb_a) mi355x_free(d->tb_a);
-  if (d->tb_perm) mi355x_free(d->tb_perm);
-  if (d->tb_plan) mi355x_spmv_plan_destroy(d->tb_plan);
-  if (d->bm_order) mi355x_free(d->bm_order);
-  if (d->bm_segptr) mi355x_free(d->bm_segptr);
-  if (d->bm_segslot) mi355x_free(d->bm_segslot);
+  form_free(&d->mat); form_free(&d->t); form_free(&d->b); form_free(&d->tb);
+  batch_map_free(d);
   if (d->bm_v) mi355x_free(d->bm_v);
-  const PetscInt nup = d->n_uploads, tb = d->t_builds, tr = d->t_refreshes;
-#if !defined(PETSCHIPMI355X_WITH_PETSC)
-  HipTriFactors *tri = d->tri;
-#endif
-  const PetscBool cprow = d->cprow, timing = d->timing;
-  const PetscInt tn = d->time_n, tcap = d->time_cap; mi355x_event_t *tev = d->time_ev;
-  PetscInt opt[8]; PetscBool opt_set[8];
-  memcpy(opt, d->opt, sizeof(opt)); memcpy(opt_set, d->opt_set, sizeof(opt_set));
-  memset(d, 0, sizeof(*d));
-  memcpy(d->opt, opt, sizeof(opt)); memcpy(d->opt_set, opt_set, sizeof(opt_set));   /* what MatSetFromOptions was told outlives the arrays */
-  d->uploaded_state = -1; d->t_state = -1; d->pattern_nz = -1;
-  d->n_uploads = nup; d->cprow = cprow;   /* a count and a request: they outlive the arrays */
-  d->t_builds = tb; d->t_refreshes = tr;
-#if !defined(PETSCHIPMI355X_WITH_PETSC)
-  d->tri = tri;
-#endif
-  d->timing = timing; d->time_n = tn; d->time_cap = tcap; d->time_ev = tev;
+  d->bm_v = NULL; d->bm_vcap = 0;
+  d->baij4_mfma = PETSC_FALSE;
+  mirror_reset(d);
+  return 0;
+}
+
+/* a form's device arrays from host ones: i (nrows + 1), j (nblocks), perm (nblocks bs^2; optional) and a (optional: else left to the gather
+ * through perm).  +16 B past j and a: the SpMV kernels read aligned pairs and the pair holding the last element may extend past it
+ * (mi355x_kernels.h).  The row-block plan partitions the VALUE stream, i.e. the row pointer scaled by bs*bs. */
+static PetscErrorCode form_upload(PetscDeviceCtx *dc, HipDevForm *f, PetscInt nrows, PetscInt bs, const PetscInt *i, const PetscInt *j,
+                                  const PetscInt *perm, const PetscScalar *a) {
+  PetscErrorCode ierr;
+  const PetscInt nblocks = i[nrows], bs2 = bs * bs;
+  const size_t nvals = (size_t)nblocks * (size_t)bs2, cap = (size_t)PetscMax(nblocks, 1) * (size_t)bs2;
+  PetscInt *sc;
+  CHKHIP(mi355x_malloc((void **)&f->i, sizeof(PetscInt) * (size_t)(nrows + 1)));
+  CHKHIP(mi355x_malloc((void **)&f->j, sizeof(PetscInt) * (size_t)PetscMax(nblocks, 1) + 16));
+  CHKHIP(mi355x_malloc((void **)&f->a, sizeof(PetscScalar) * cap + 16));
+  CHKHIP(mi355x_memcpy_h2d(dc->h, f->i, i, sizeof(PetscInt) * (size_t)(nrows + 1)));
+  CHKHIP(mi355x_memcpy_h2d(dc->h, f->j, j, sizeof(PetscInt) * (size_t)nblocks));
+  if (perm) {
+    CHKHIP(mi355x_malloc((void **)&f->perm, sizeof(PetscInt) * cap));
+    CHKHIP(mi355x_memcpy_h2d(dc->h, f->perm, perm, sizeof(PetscInt) * nvals));
+  }
+  if (a) CHKHIP(mi355x_memcpy_h2d(dc->h, f->a, a, sizeof(PetscScalar) * nvals));
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nrows + 1), &sc);CHKERRQ(ierr);
+  for (PetscInt r = 0; r <= nrows; r++) sc[r] = i[r] * bs2;
+  CHKHIP(mi355x_spmv_plan_create(dc->h, nrows, sc, NULL, &f->plan));
+  CHKHIP(mi355x_handle_synchronize(dc->h));       /* the host arrays are pageable and the caller's to free */
+  HipFree(sc);
+  f->bs = bs; f->nblocks = nblocks; f->fresh = (PetscBool)(a != NULL);
+  return 0;
+}
+/* after a change of the device values d_a: a derived form's values by one gather through its perm, a tiled layout's copy by its refresh */
+static PetscErrorCode form_current(PetscDeviceCtx *dc, HipDevForm *f, const PetscScalar *d_a) {
+  if (!f->plan || f->fresh) return 0;
+  if (f->perm) CHKHIP(mi355x_pack(dc->h, (size_t)f->nblocks * (size_t)(f->bs * f->bs), f->perm, d_a, f->a));
+  if (f->tiled) CHKHIP(mi355x_spmv_tiled_refresh_values(dc->h, f->tiled, f->a));
+  f->fresh = PETSC_TRUE;
+  return 0;
+}
+static void forms_stale(Mat_SeqAIJHIP *d) { d->mat.fresh = d->t.fresh = d->b.fresh = d->tb.fresh = PETSC_FALSE; }
+/* called just before the device values change in place (MatScale, MatZeroEntries, MatDiagonalScale, MatSetValuesBatch): a noted product
+ * of the old values runs first, the derived forms follow by a gather when next used, the value-pattern dictionary no longer describes the
+ * values, and the device copy is stamped with the state the wrapper's bump after the op gives the matrix */
+static PetscErrorCode device_values_changed(Mat A) {
+  PetscErrorCode ierr;
+  Mat_SeqAIJHIP *d = SD(A);
+  ierr = VecHIPProductMatrixChanges(A);CHKERRQ(ierr);
+  forms_stale(d);
+  CHKHIP(mi355x_spmv_plan_drop_value_patterns(d->mat.plan));
+  d->uploaded_state = HipObjState(A) + 1;
+  return 0;
+}
+
+/* the transpose of a BCSR pattern (bs = 1: CSR) of nbrows x nbcols blocks by a stable counting sort: each row of the transpose lists its
+ * entries in increasing original (block) row, the order MatMultTransposeAdd_SeqAIJ's scatter loop adds them in (aij.c:1100-1112; baij2.c:1740),
+ * every bs x bs block transposed (column-major, baij.h:13-30).  map: for each stored value of the pattern, its position in the matrix's value
+ * array (NULL: the identity); tperm: the same for each value of the transpose. */
+static PetscErrorCode transpose_pattern(PetscInt nbrows, PetscInt nbcols, const PetscInt *bi, const PetscInt *bj, PetscInt bs, const PetscInt *map,
+                                        PetscInt **ti_, PetscInt **tj_, PetscInt **tperm_) {
+  PetscErrorCode ierr;
+  const PetscInt nb = bi[nbrows], bs2 = bs * bs;
+  PetscInt *ti, *tj, *tperm, *next;
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nbcols + 1), &ti);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nb, 1), &tj);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nb, 1) * (size_t)bs2, &tperm);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nbcols, 1), &next);CHKERRQ(ierr);
+  memset(ti, 0, sizeof(PetscInt) * (size_t)(nbcols + 1));
+  for (PetscInt k = 0; k < nb; k++) ti[bj[k] + 1]++;
+  for (PetscInt c = 0; c < nbcols; c++) ti[c + 1] += ti[c];
+  for (PetscInt c = 0; c < nbcols; c++) next[c] = ti[c];
+  for (PetscInt r = 0; r < nbrows; r++)
+    for (PetscInt k = bi[r]; k < bi[r + 1]; k++) {
+      const PetscInt p = next[bj[k]]++;
+      tj[p] = r;
+      /* entry (row q, column c) of the transposed block is entry (row c, column q) of the block */
+      for (PetscInt c = 0; c < bs; c++) for (PetscInt q = 0; q < bs; q++) {
+        const size_t src = (size_t)k * bs2 + q * bs + c;
+        tperm[(size_t)p * bs2 + c * bs + q] = map ? map[src] : (PetscInt)src;
+      }
+    }
+  HipFree(next);
+  *ti_ = ti; *tj_ = tj; *tperm_ = tperm;
+  return 0;
+}
+
+/* -mat_hipmi355x_tiled <-1|0|1> (default -1 = decide), tl: the column-tiled product (csrc/spmv_tiled.hip) of an m x n pattern, or NULL.
+ * Built when asked for, or when `probe` is set and a sample of its 32-row groups shows the gathers landing on lines of x of their own
+ * (> 0.5 line per nonzero: rows that share no columns with their neighbours -- the irregular matrices of BASELINE configs[3]) on a matrix
+ * large enough for x to leave the L2 (>= 2^17 columns); the transpose (probe not set) builds it whenever the matrix took it.  Kept when asked
+ * for, or if at least half of the nonzeros fall into pairs worth staging.  A failed build is an error when the matrix asked for it, else the
+ * row-block kernels serve (e.g. no host memory for the layout).  -mat_hipmi355x_tiled_stage_min <n> (default 1024): entries a (panel, tile)
+ * pair needs to be staged. */
+static PetscErrorCode tiled_decide(Mat A, PetscInt tl, PetscBool probe, PetscInt m, PetscInt n, const PetscInt *ai, const PetscInt *aj,
+                                   mi355x_spmv_tiled_t *tiled) {
+  PetscErrorCode ierr;
+  PetscInt smin = 0; long staged = 0, rest = 0;
+  *tiled = NULL;
+  ierr = hip_mat_option(A, HOPT_TILED_SMIN, &smin);CHKERRQ(ierr);
+  if (probe && tl < 0) {
+    double lpn = 0.0;
+    if (n < (1 << 17) || ai[m] < (1 << 22)) return 0;
+    CHKHIP(mi355x_spmv_tiled_probe(m, ai, aj, &lpn));
+    if (!(lpn > 0.5)) return 0;
+  }
+  const int rc = mi355x_spmv_tiled_build(m, n, ai, aj, (int)smin, tiled);
+  if (rc) {
+    *tiled = NULL;
+    if (probe && tl > 0) CHKHIP(rc);
+    return 0;
+  }
+  CHKHIP(mi355x_spmv_tiled_info(*tiled, &staged, &rest, NULL, NULL, NULL));
+  if (tl < 0 && 2 * staged < (long)ai[m]) { mi355x_spmv_tiled_destroy(*tiled); *tiled = NULL; }
   return 0;
 }
 
@@ -234,12 +327,11 @@ static PetscErrorCode device_free(Mat A) {
 #if defined(PETSCHIPMI355X_WITH_PETSC)
 static PetscErrorCode hipaij_refresh_view_if_stale(Mat A);   /* integration/petsc-3.3/aijhipmi355x_ctor.h */
 #endif
-/* the blocked companion (see MatSeqAIJHIPUpload): BCSR arrays of an AIJ matrix whose nodes are complete bs x bs blocks; leaves d->b_plan
- * NULL when the matrix is not of that shape */
-static PetscErrorCode blocked_companion_build(Mat A, PetscDeviceCtx *dc) {
-  PetscErrorCode ierr;
-  HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
+/* the blocked companion (see upload_pattern): an AIJ matrix whose nodes are complete bs x bs blocks.  Its block size (0: not of that shape)
+ * and number of blocks */
+static PetscInt companion_shape(const HipAIJ *a, PetscInt *nblocks) {
   const PetscInt m = a->m, n = a->n, nn = a->inode_count;
+  *nblocks = 0;
   if (nn <= 0 || !a->inode_size) return 0;
   const PetscInt bs = a->inode_size[0];
   if (bs < 2 || bs > 5 || nn * bs != m || n % bs) return 0;
@@ -258,12 +350,17 @@ static PetscErrorCode blocked_companion_build(Mat A, PetscDeviceCtx *dc) {
     nblk += len / bs;
   }
   if ((double)nblk * bs * bs > 2147483000.0) return 0;
-  PetscInt *bi, *bj, *perm, *sc;
-  const PetscInt bs2 = bs * bs;
+  *nblocks = nblk;
+  return bs;
+}
+/* the companion's BCSR pattern on the host: bi, bj and perm, the position in the CSR value array of every block value (column-major) */
+static PetscErrorCode companion_pattern(const HipAIJ *a, PetscInt bs, PetscInt nblk, PetscInt **bi_, PetscInt **bj_, PetscInt **perm_) {
+  PetscErrorCode ierr;
+  const PetscInt nn = a->m / bs, bs2 = bs * bs;
+  PetscInt *bi, *bj, *perm;
   ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nn + 1), &bi);CHKERRQ(ierr);
   ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nblk, 1), &bj);CHKERRQ(ierr);
   ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nblk, 1) * (size_t)bs2, &perm);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nn + 1), &sc);CHKERRQ(ierr);
   bi[0] = 0;
   for (PetscInt i = 0, b = 0; i < nn; i++) {
     const PetscInt r = i * bs, len = a->i[r + 1] - a->i[r];
@@ -273,23 +370,161 @@ static PetscErrorCode blocked_companion_build(Mat A, PetscDeviceCtx *dc) {
     }
     bi[i + 1] = bi[i] + len / bs;
   }
-  for (PetscInt i = 0; i <= nn; i++) sc[i] = bi[i] * bs2;
-  CHKHIP(mi355x_malloc((void **)&d->b_i, sizeof(PetscInt) * (size_t)(nn + 1)));
-  CHKHIP(mi355x_malloc((void **)&d->b_j, sizeof(PetscInt) * (size_t)PetscMax(nblk, 1) + 16));
-  CHKHIP(mi355x_malloc((void **)&d->b_perm, sizeof(PetscInt) * (size_t)PetscMax(nblk, 1) * (size_t)bs2));
-  CHKHIP(mi355x_malloc((void **)&d->b_a, sizeof(PetscScalar) * (size_t)PetscMax(nblk, 1) * (size_t)bs2 + 16));
-  CHKHIP(mi355x_memcpy_h2d(dc->h, d->b_i, bi, sizeof(PetscInt) * (size_t)(nn + 1)));
-  CHKHIP(mi355x_memcpy_h2d(dc->h, d->b_j, bj, sizeof(PetscInt) * (size_t)nblk));
-  CHKHIP(mi355x_memcpy_h2d(dc->h, d->b_perm, perm, sizeof(PetscInt) * (size_t)nblk * (size_t)bs2));
-  CHKHIP(mi355x_spmv_plan_create(dc->h, nn, sc, NULL, &d->b_plan));
-  CHKHIP(mi355x_handle_synchronize(dc->h));
-  HipFree(bi); HipFree(bj); HipFree(perm); HipFree(sc);
-  d->b_bs = bs; d->b_nblocks = nblk; d->b_fresh = PETSC_FALSE;
+  *bi_ = bi; *bj_ = bj; *perm_ = perm;
   return 0;
 }
-static PetscErrorCode blocked_values_current(Mat A, PetscDeviceCtx *dc) {      /* after a device-side change of d_a: one gather, when next used */
+static PetscErrorCode blocked_companion_build(Mat A, PetscDeviceCtx *dc) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
+  PetscInt nblk, *bi, *bj, *perm;
+  const PetscInt bs = companion_shape(a, &nblk);
+  if (!bs) return 0;
+  ierr = companion_pattern(a, bs, nblk, &bi, &bj, &perm);CHKERRQ(ierr);
+  ierr = form_upload(dc, &d->b, a->m / bs, bs, bi, bj, perm, NULL);CHKERRQ(ierr);
+  HipFree(bi); HipFree(bj); HipFree(perm);
+  return 0;
+}
+
+/* PETSC_HIPMI355X_SETUP_TIMING=1: the upload's phases on stderr */
+typedef struct { int on; double t0; } UpTick;
+static void up_tick(UpTick *tk, PetscDeviceCtx *dc, const char *what) {
+  struct timespec ts;
+  if (!tk->on) return;
+  (void)mi355x_handle_synchronize(dc->h);
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  const double t = (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+  if (tk->t0 > 0.0) fprintf(stderr, "[hipmi355x]   upload: %-30s %.3f s\n", what, t - tk->t0);
+  tk->t0 = t;
+}
+/* the device forms for the matrix's pattern: the arrays, the plan and the analyses on it */
+static PetscErrorCode upload_pattern(Mat A, PetscDeviceCtx *dc, UpTick *tk) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A);
   Mat_SeqAIJHIP *d = SD(A);
-  if (d->b_plan && !d->b_fresh) { CHKHIP(mi355x_pack(dc->h, (size_t)SA(A)->nz, d->b_perm, d->d_a, d->b_a)); d->b_fresh = PETSC_TRUE; }
+  device_free(A);
+  if (a->bs > 1) {   /* BAIJ */
+    if (a->bs == 4) {   /* -mat_hipmi355x_baij4 <mfma|fma>: the matrix cores (v_mfma_f64_4x4x4, 16-byte loads: 1.22-1.28 ms at 128^3 nodes, 27
+                         * blocks per row; the default -- BASELINE configs[4]'s "MFMA 4x4 tile path") or the row-block FMA kernel with x staged
+                         * in LDS (1.25-1.32 ms in the same processes, three boxes: profiles/r03_cfg5.log) */
+      char kind[16] = "mfma"; PetscBool set;
+      ierr = PetscOptionsGetString(NULL, "-mat_hipmi355x_baij4", kind, sizeof(kind), &set);CHKERRQ(ierr);
+      if (strcmp(kind, "mfma") && strcmp(kind, "fma")) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "-mat_hipmi355x_baij4 <mfma|fma>, got %s", kind);
+      d->baij4_mfma = (PetscBool)!strcmp(kind, "mfma");
+    }
+    if ((double)a->nz * a->bs * a->bs > 2147483000.0) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_OUTOFRANGE, "BAIJ matrix too large for 32-bit value offsets");
+    ierr = form_upload(dc, &d->mat, a->m, a->bs, a->i, a->j, NULL, NULL);CHKERRQ(ierr);
+    up_tick(tk, dc, "row pointer and columns up");
+    d->pattern_nz = a->nz; d->cprow = PETSC_FALSE;
+    return 0;
+  }
+  PetscInt m = a->m, nrows = m;
+  const PetscInt *ip = a->i; PetscInt *ci = NULL, *ridx = NULL;
+  /* compressed rows when >= 60% of the rows are empty (Mat_CheckCompressedRow ratio, compressedrow.c:28;
+   * the reference forces it off for B, mpiaij.c:705, because its CPU loop gains little -- on the GPU the
+   * off-diagonal block is >99% empty rows and visiting them costs a full pass over y) */
+  PetscBool use_cprow = PETSC_FALSE;
+  if (d->cprow && m > 0 && (double)(m - a->nonzerorows) > 0.6 * m) {
+    use_cprow = PETSC_TRUE;
+    nrows = a->nonzerorows;
+    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nrows + 1), &ci);CHKERRQ(ierr);
+    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nrows, 1), &ridx);CHKERRQ(ierr);
+    PetscInt k = 0; ci[0] = 0;
+    for (PetscInt r = 0; r < m; r++) if (a->i[r + 1] > a->i[r]) { ridx[k] = r; ci[++k] = a->i[r + 1]; }
+    ip = ci;
+  }
+  CHKHIP(mi355x_malloc((void **)&d->mat.i, sizeof(PetscInt) * (size_t)(nrows + 1)));
+  /* +16 B: the SpMV kernels read aligned pairs and the pair holding the last element may extend past it (mi355x_kernels.h) */
+  CHKHIP(mi355x_malloc((void **)&d->mat.j, sizeof(PetscInt) * (size_t)PetscMax(a->nz, 1) + 16));
+  CHKHIP(mi355x_malloc((void **)&d->mat.a, sizeof(PetscScalar) * (size_t)PetscMax(a->nz, 1) + 16));
+  CHKHIP(mi355x_memcpy_h2d(dc->h, d->mat.i, ip, sizeof(PetscInt) * (size_t)(nrows + 1)));
+  CHKHIP(mi355x_memcpy_h2d(dc->h, d->mat.j, a->j, sizeof(PetscInt) * (size_t)a->nz));
+  d->mat.bs = 1; d->mat.nblocks = a->nz;
+  up_tick(tk, dc, "row pointer and columns up");
+  PetscInt ic = 1;
+  CHKHIP(mi355x_spmv_plan_create(dc->h, nrows, ip, use_cprow ? ridx : NULL, &d->mat.plan));
+  up_tick(tk, dc, "row-block plan");
+  /* -mat_hipmi355x_index_compression <0|1> (default 1): one byte per nonzero instead of a 4-byte column index
+   * when the matrix uses <= 256 distinct (col - row) offsets; plain CSR otherwise */
+  ierr = hip_mat_option(A, HOPT_IC, &ic);CHKERRQ(ierr);
+  if (ic && !use_cprow) {
+    PetscInt rp = 1;
+    CHKHIP(mi355x_spmv_plan_compress_indices(dc->h, d->mat.plan, a->i, a->j));
+    /* -mat_hipmi355x_row_patterns <0|1> (default 1): stencil matrices whose rows' offset lists come from a small dictionary
+     * stream 4 bytes per ROW instead of 1 byte per nonzero + the row pointer (spmv_csr_rowblock_pat_kernel); same bits */
+    ierr = hip_mat_option(A, HOPT_RP, &rp);CHKERRQ(ierr);
+    CHKHIP(mi355x_spmv_plan_use_patterns(d->mat.plan, rp ? 1 : 0, NULL));
+    up_tick(tk, dc, "offset / row-pattern dictionaries");
+  }
+  /* inodes: when the reference's Mat_CheckInode would switch this matrix to MatMult_SeqAIJ_Inode, the row sums take
+   * that routine's two-at-a-time order (same bits), and -- unless the 1-byte index dictionary already applies --
+   * the rows of a node share one stored column list (mi355x_spmv_plan_group_rows) */
+  ierr = seqaij_check_inode(A);CHKERRQ(ierr);
+  up_tick(tk, dc, "inode check");
+  if (a->inode_count) {
+    int ntab = 0;
+    CHKHIP(mi355x_spmv_plan_set_pairsum(d->mat.plan, 1));
+    CHKHIP(mi355x_spmv_plan_is_compressed(d->mat.plan, &ntab));
+    if (!ntab && !use_cprow) CHKHIP(mi355x_spmv_plan_group_rows(dc->h, d->mat.plan, a->i, a->j, a->inode_count, a->inode_size));
+  }
+  /* -mat_hipmi355x_blocked <-1|0|1> (default -1 = decide): the blocked companion.  When every node Mat_CheckInode found has the same
+   * size bs (2..5) and its shared column list is made of whole aligned groups of bs columns -- the 3-dof matrices of FEM codes
+   * assembled into AIJ: every coupling a complete bs x bs block -- the matrix IS a BAIJ matrix, and MatMult_SeqBAIJ_bs's kernel
+   * reads 8 bs^2 + 4 bytes per block where the grouped-row kernel reads 8 bs^2 + 4 bs: BCSR arrays are laid out beside the CSR ones
+   * (block values column-major, baij.h:13-30, as a permutation of d_a kept on the device) and the products take the BCSR row-block
+   * kernel: FEM stand-in 0.245 -> 0.197 ms, the same sums bit for bit (profiles/r04_fem_as_baij.log).  Decided here only for rows
+   * long enough that the grouped-row kernel does not carry the reference's bits anyway (more than 16 nonzeros per row). */
+  if (a->inode_count && !use_cprow) {
+    PetscInt bl = -1;
+    ierr = hip_mat_option(A, HOPT_BLOCKED, &bl);CHKERRQ(ierr);
+    if (bl != 0 && (bl > 0 || (double)a->nz > 16.0 * (double)a->m)) { ierr = blocked_companion_build(A, dc);CHKERRQ(ierr); }
+    up_tick(tk, dc, "blocked companion");
+  }
+  /* the column-tiled product for a matrix that got neither an offset dictionary nor grouped rows: it gathers x once per nonzero */
+  {
+    PetscInt tl = -1; int ntab = 0, ng = 0; long ngj = 0;
+    ierr = hip_mat_option(A, HOPT_TILED, &tl);CHKERRQ(ierr);
+    CHKHIP(mi355x_spmv_plan_is_compressed(d->mat.plan, &ntab));
+    CHKHIP(mi355x_spmv_plan_group_info(d->mat.plan, &ng, &ngj, NULL));
+    if (tl != 0 && !use_cprow && !ntab && !ng && a->nz > 0) {
+      ierr = tiled_decide(A, tl, PETSC_TRUE, a->m, a->n, a->i, a->j, &d->mat.tiled);CHKERRQ(ierr);
+      up_tick(tk, dc, "column-tiled layout");
+    }
+  }
+  CHKHIP(mi355x_handle_synchronize(dc->h));
+  HipFree(ci); HipFree(ridx);
+  d->pattern_nz = a->nz;
+  if (!use_cprow) d->cprow = PETSC_FALSE;
+  return 0;
+}
+/* the values, into the device copy and the forms that carry them */
+static PetscErrorCode upload_values(Mat A, PetscDeviceCtx *dc, PetscBool new_pattern, UpTick *tk) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A);
+  Mat_SeqAIJHIP *d = SD(A);
+  up_tick(tk, dc, "(grouped rows, bookkeeping)");
+  CHKHIP(mi355x_memcpy_h2d(dc->h, d->mat.a, a->a, sizeof(PetscScalar) * (size_t)a->nz * (size_t)(d->mat.bs * d->mat.bs)));
+  up_tick(tk, dc, "values up");
+  forms_stale(d);
+  if (d->b.plan) {
+    ierr = form_current(dc, &d->b, d->mat.a);CHKERRQ(ierr);
+    up_tick(tk, dc, "blocked companion's values");
+  }
+  if (d->mat.tiled) {
+    if (new_pattern) { CHKHIP(mi355x_spmv_tiled_upload(dc->h, d->mat.tiled, d->mat.a)); CHKHIP(mi355x_spmv_tiled_drop_host(d->mat.tiled)); d->mat.fresh = PETSC_TRUE; }
+    else { ierr = form_current(dc, &d->mat, d->mat.a);CHKERRQ(ierr); }
+    up_tick(tk, dc, "column-tiled values");
+  }
+  if (a->bs <= 1 && d->mat.plan) {
+    /* -mat_hipmi355x_value_patterns <0|1> (default 1): constant-coefficient operators -- whole rows, offsets and values,
+     * from a dictionary of <= 512 entries -- run a kernel that reads 2 bytes per row and no values (spmv_csr_valpat_kernel);
+     * same bits.  The dictionary belongs to THESE values: derived again on every upload, dropped by every device-side change. */
+    PetscInt vp = 1;
+    ierr = hip_mat_option(A, HOPT_VP, &vp);CHKERRQ(ierr);
+    CHKHIP(mi355x_spmv_plan_use_value_patterns(d->mat.plan, vp ? 1 : 0, NULL));
+    if (vp) CHKHIP(mi355x_spmv_plan_value_patterns(dc->h, d->mat.plan, a->i, a->j, a->a, NULL));
+  }
+  CHKHIP(mi355x_handle_synchronize(dc->h));
+  up_tick(tk, dc, "value-pattern analysis");
   return 0;
 }
 PetscErrorCode MatSeqAIJHIPUpload(Mat A) {
@@ -302,283 +537,82 @@ PetscErrorCode MatSeqAIJHIPUpload(Mat A) {
    * MatCopy, MatConvert set assembled = TRUE themselves): the view of them is checked before every use */
   ierr = hipaij_refresh_view_if_stale(A);CHKERRQ(ierr);
 #endif
-  if (d->uploaded_state == HipObjState(A) && d->d_a) return 0;
+  if (d->uploaded_state == HipObjState(A) && d->mat.a) return 0;
   ierr = VecHIPProductMatrixChanges(A);CHKERRQ(ierr);      /* (the device copy still holds the values the noted product was asked with) */
   ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-  const int up_timing = getenv("PETSC_HIPMI355X_SETUP_TIMING") != NULL;
-  double up_t0 = 0.0;
-#define UP_TICK(what) do { if (up_timing) { struct timespec ts__; (void)mi355x_handle_synchronize(dc->h); clock_gettime(CLOCK_MONOTONIC, &ts__); const double t__ = (double)ts__.tv_sec + 1e-9 * (double)ts__.tv_nsec; \
-    if (up_t0 > 0.0) { fprintf(stderr, "[hipmi355x]   upload: %-30s %.3f s\n", what, t__ - up_t0); } \
-    up_t0 = t__; } } while (0)
-  UP_TICK("");
+  UpTick tk = {getenv("PETSC_HIPMI355X_SETUP_TIMING") != NULL, 0.0};
+  up_tick(&tk, dc, "");
   if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled before it is sent to the GPU");
-  PetscBool same_pattern = (PetscBool)(d->d_a && d->plan && d->pattern_nz == a->nz);   /* entries are never removed: same nz == same pattern */
-  if (!same_pattern) {
-    device_free(A);
-    PetscInt m = a->m, nrows = m;
-    const PetscInt *ip = a->i; PetscInt *ci = NULL, *ridx = NULL;
-    /* compressed rows when >= 60% of the rows are empty (Mat_CheckCompressedRow ratio, compressedrow.c:28;
-     * the reference forces it off for B, mpiaij.c:705, because its CPU loop gains little -- on the GPU the
-     * off-diagonal block is >99% empty rows and visiting them costs a full pass over y) */
-    PetscBool use_cprow = PETSC_FALSE;
-    if (d->cprow && m > 0 && (double)(m - a->nonzerorows) > 0.6 * m) {
-      use_cprow = PETSC_TRUE;
-      nrows = a->nonzerorows;
-      ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nrows + 1), &ci);CHKERRQ(ierr);
-      ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nrows, 1), &ridx);CHKERRQ(ierr);
-      PetscInt k = 0; ci[0] = 0;
-      for (PetscInt r = 0; r < m; r++) if (a->i[r + 1] > a->i[r]) { ridx[k] = r; ci[++k] = a->i[r + 1]; }
-      ip = ci;
-    }
-    CHKHIP(mi355x_malloc((void **)&d->d_i, sizeof(PetscInt) * (size_t)(nrows + 1)));
-    /* +16 B: the SpMV kernels read aligned pairs and the pair holding the last element may extend past it (mi355x_kernels.h) */
-    CHKHIP(mi355x_malloc((void **)&d->d_j, sizeof(PetscInt) * (size_t)PetscMax(a->nz, 1) + 16));
-    CHKHIP(mi355x_malloc((void **)&d->d_a, sizeof(PetscScalar) * (size_t)PetscMax(a->nz, 1) + 16));
-    CHKHIP(mi355x_memcpy_h2d(dc->h, d->d_i, ip, sizeof(PetscInt) * (size_t)(nrows + 1)));
-    CHKHIP(mi355x_memcpy_h2d(dc->h, d->d_j, a->j, sizeof(PetscInt) * (size_t)a->nz));
-    UP_TICK("row pointer and columns up");
-    if (a->bs <= 1) {
-      PetscInt ic = 1;
-      CHKHIP(mi355x_spmv_plan_create(dc->h, nrows, ip, use_cprow ? ridx : NULL, &d->plan));
-      UP_TICK("row-block plan");
-      /* -mat_hipmi355x_index_compression <0|1> (default 1): one byte per nonzero instead of a 4-byte column index
-       * when the matrix uses <= 256 distinct (col - row) offsets; plain CSR otherwise */
-      ierr = hip_mat_option(A, HOPT_IC, &ic);CHKERRQ(ierr);
-      if (ic && !use_cprow) {
-        PetscInt rp = 1;
-        CHKHIP(mi355x_spmv_plan_compress_indices(dc->h, d->plan, a->i, a->j));
-        /* -mat_hipmi355x_row_patterns <0|1> (default 1): stencil matrices whose rows' offset lists come from a small dictionary
-         * stream 4 bytes per ROW instead of 1 byte per nonzero + the row pointer (spmv_csr_rowblock_pat_kernel); same bits */
-        ierr = hip_mat_option(A, HOPT_RP, &rp);CHKERRQ(ierr);
-        CHKHIP(mi355x_spmv_plan_use_patterns(d->plan, rp ? 1 : 0, NULL));
-        UP_TICK("offset / row-pattern dictionaries");
-      }
-      /* inodes: when the reference's Mat_CheckInode would switch this matrix to MatMult_SeqAIJ_Inode, the row sums take
-       * that routine's two-at-a-time order (same bits), and -- unless the 1-byte index dictionary already applies --
-       * the rows of a node share one stored column list (mi355x_spmv_plan_group_rows) */
-      ierr = seqaij_check_inode(A);CHKERRQ(ierr);
-      UP_TICK("inode check");
-      if (a->inode_count) {
-        int ntab = 0;
-        CHKHIP(mi355x_spmv_plan_set_pairsum(d->plan, 1));
-        CHKHIP(mi355x_spmv_plan_is_compressed(d->plan, &ntab));
-        if (!ntab && !use_cprow) CHKHIP(mi355x_spmv_plan_group_rows(dc->h, d->plan, a->i, a->j, a->inode_count, a->inode_size));
-      }
-      /* -mat_hipmi355x_blocked <-1|0|1> (default -1 = decide): the blocked companion.  When every node Mat_CheckInode found has the same
-       * size bs (2..5) and its shared column list is made of whole aligned groups of bs columns -- the 3-dof matrices of FEM codes
-       * assembled into AIJ: every coupling a complete bs x bs block -- the matrix IS a BAIJ matrix, and MatMult_SeqBAIJ_bs's kernel
-       * reads 8 bs^2 + 4 bytes per block where the grouped-row kernel reads 8 bs^2 + 4 bs: BCSR arrays are laid out beside the CSR ones
-       * (block values column-major, baij.h:13-30, as a permutation of d_a kept on the device) and the products take the BCSR row-block
-       * kernel: FEM stand-in 0.245 -> 0.197 ms, the same sums bit for bit (profiles/r04_fem_as_baij.log).  Decided here only for rows
-       * long enough that the grouped-row kernel does not carry the reference's bits anyway (more than 16 nonzeros per row). */
-      if (a->inode_count && !use_cprow) {
-        PetscInt bl = -1;
-        ierr = hip_mat_option(A, HOPT_BLOCKED, &bl);CHKERRQ(ierr);
-        if (bl != 0 && (bl > 0 || (double)a->nz > 16.0 * (double)a->m)) { ierr = blocked_companion_build(A, dc);CHKERRQ(ierr); }
-        UP_TICK("blocked companion");
-      }
-      /* -mat_hipmi355x_tiled <-1|0|1> (default -1 = decide): the column-tiled product (csrc/spmv_tiled.hip).  A matrix that got neither
-       * an offset dictionary nor grouped rows gathers x once per nonzero; when a sample of its 32-row groups shows those gathers
-       * landing on lines of x of their own (> 0.5 line per nonzero: rows that share no columns with their neighbours -- the
-       * irregular matrices of BASELINE configs[3]) and it is large enough for x to leave the L2 (>= 2^17 columns), the product is
-       * re-cut into row panels x column tiles with the tiles of x staged in LDS; kept only if at least half of the nonzeros fall into
-       * pairs worth staging.  -mat_hipmi355x_tiled_stage_min <n> (default 1024): entries a (panel, tile) pair needs to be staged. */
-      {
-        PetscInt tl = -1, smin = 0; int ntab = 0, ng = 0; long ngj = 0;
-        ierr = hip_mat_option(A, HOPT_TILED, &tl);CHKERRQ(ierr);
-        ierr = hip_mat_option(A, HOPT_TILED_SMIN, &smin);CHKERRQ(ierr);
-        CHKHIP(mi355x_spmv_plan_is_compressed(d->plan, &ntab));
-        CHKHIP(mi355x_spmv_plan_group_info(d->plan, &ng, &ngj, NULL));
-        if (tl != 0 && !use_cprow && !ntab && !ng && a->nz > 0) {
-          PetscBool want = (PetscBool)(tl > 0);
-          if (tl < 0 && a->n >= (1 << 17) && a->nz >= (1 << 22)) {
-            double lpn = 0.0;
-            CHKHIP(mi355x_spmv_tiled_probe(a->m, a->i, a->j, &lpn));
-            want = (PetscBool)(lpn > 0.5);
-          }
-          if (want) {
-            long staged = 0, rest = 0;
-            int rcb = mi355x_spmv_tiled_build(a->m, a->n, a->i, a->j, (int)smin, &d->tiled);
-            if (rcb && tl > 0) CHKHIP(rcb);                                  /* asked for: report; decided here: the row-block kernels serve (e.g. no host memory for the layout) */
-            if (rcb) d->tiled = NULL;
-            else {
-              CHKHIP(mi355x_spmv_tiled_info(d->tiled, &staged, &rest, NULL, NULL, NULL));
-              if (tl < 0 && 2 * staged < (long)a->nz) { mi355x_spmv_tiled_destroy(d->tiled); d->tiled = NULL; }
-            }
-          }
-          UP_TICK("column-tiled layout");
-        }
-      }
-    }
-    else {   /* BAIJ: the plan partitions the VALUE stream, i.e. the block-row pointer scaled by bs*bs */
-      PetscInt *sc, bs2 = a->bs * a->bs;
-      if (a->bs == 4) {   /* -mat_hipmi355x_baij4 <mfma|fma>: the matrix cores (v_mfma_f64_4x4x4, 16-byte loads: 1.22-1.28 ms at 128^3 nodes, 27
-                           * blocks per row; the default -- BASELINE configs[4]'s "MFMA 4x4 tile path") or the row-block FMA kernel with x staged
-                           * in LDS (1.25-1.32 ms in the same processes, three boxes: profiles/r03_cfg5.log) */
-        char kind[16] = "mfma"; PetscBool set;
-        ierr = PetscOptionsGetString(NULL, "-mat_hipmi355x_baij4", kind, sizeof(kind), &set);CHKERRQ(ierr);
-        if (strcmp(kind, "mfma") && strcmp(kind, "fma")) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "-mat_hipmi355x_baij4 <mfma|fma>, got %s", kind);
-        d->baij4_mfma = (PetscBool)!strcmp(kind, "mfma");
-      }
-      if ((double)a->nz * bs2 > 2147483000.0) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_OUTOFRANGE, "BAIJ matrix too large for 32-bit value offsets");
-      ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nrows + 1), &sc);CHKERRQ(ierr);
-      for (PetscInt r = 0; r <= nrows; r++) sc[r] = a->i[r] * bs2;
-      CHKHIP(mi355x_spmv_plan_create(dc->h, nrows, sc, NULL, &d->plan));
-      HipFree(sc);
-    }
-    CHKHIP(mi355x_handle_synchronize(dc->h));
-    HipFree(ci); HipFree(ridx);
-    d->pattern_nz = a->nz;
-    if (!use_cprow) d->cprow = PETSC_FALSE;
-  }
-  size_t vals = (size_t)a->nz * (size_t)(a->bs > 1 ? a->bs * a->bs : 1);
-  if (a->bs > 1 && !same_pattern) { mi355x_free(d->d_a); CHKHIP(mi355x_malloc((void **)&d->d_a, sizeof(PetscScalar) * PetscMax(vals, 1) + 16)); }
-  UP_TICK("(grouped rows, bookkeeping)");
-  CHKHIP(mi355x_memcpy_h2d(dc->h, d->d_a, a->a, sizeof(PetscScalar) * vals));
-  UP_TICK("values up");
-  if (d->b_plan) {
-    CHKHIP(mi355x_pack(dc->h, (size_t)a->nz, d->b_perm, d->d_a, d->b_a));
-    d->b_fresh = PETSC_TRUE; d->tb_fresh = PETSC_FALSE;
-    UP_TICK("blocked companion's values");
-  }
-  if (d->tiled) {
-    if (!same_pattern) { CHKHIP(mi355x_spmv_tiled_upload(dc->h, d->tiled, d->d_a)); CHKHIP(mi355x_spmv_tiled_drop_host(d->tiled)); }
-    else CHKHIP(mi355x_spmv_tiled_refresh_values(dc->h, d->tiled, d->d_a));
-    d->tiled_fresh = PETSC_TRUE;
-    UP_TICK("column-tiled values");
-  }
-  if (a->bs <= 1 && d->plan) {
-    /* -mat_hipmi355x_value_patterns <0|1> (default 1): constant-coefficient operators -- whole rows, offsets and values,
-     * from a dictionary of <= 512 entries -- run a kernel that reads 2 bytes per row and no values (spmv_csr_valpat_kernel);
-     * same bits.  The dictionary belongs to THESE values: derived again on every upload, dropped by every device-side change. */
-    PetscInt vp = 1;
-    ierr = hip_mat_option(A, HOPT_VP, &vp);CHKERRQ(ierr);
-    CHKHIP(mi355x_spmv_plan_use_value_patterns(d->plan, vp ? 1 : 0, NULL));
-    if (vp) CHKHIP(mi355x_spmv_plan_value_patterns(dc->h, d->plan, a->i, a->j, a->a, NULL));
-  }
-  CHKHIP(mi355x_handle_synchronize(dc->h));
-  UP_TICK("value-pattern analysis");
-#undef UP_TICK
+  const PetscBool new_pattern = (PetscBool)!(d->mat.a && d->mat.plan && d->pattern_nz == a->nz);   /* entries are never removed: same nz == same pattern */
+  if (new_pattern) { ierr = upload_pattern(A, dc, &tk);CHKERRQ(ierr); }
+  ierr = upload_values(A, dc, new_pattern, &tk);CHKERRQ(ierr);
   d->n_uploads++;
   d->uploaded_state = HipObjState(A);
   return 0;
 }
 
-PetscErrorCode MatSeqAIJHIPSetCompressedRow(Mat A, PetscBool flg) { SD(A)->cprow = flg; SD(A)->uploaded_state = -1; SD(A)->pattern_nz = -1; return 0; }
+PetscErrorCode MatSeqAIJHIPSetCompressedRow(Mat A, PetscBool flg) { SD(A)->cprow = flg; mirror_reset(SD(A)); return 0; }
 
-/* explicit transpose, contributions of each output row in increasing original-row order (the order
- * MatMultTransposeAdd_SeqAIJ's scatter loop adds them in, aij.c:1100-1112) */
-static PetscErrorCode upload_transpose(Mat A) {
+/* the transpose products' form, built when missing and with its values current: the blocked companion's block transpose (its values a
+ * gather of d_a like the companion's own), else the explicit transpose, built on the host once per pattern -- for BAIJ whenever the
+ * matrix moved -- and refreshed on the device when only the values changed */
+static PetscErrorCode transpose_current(Mat A, PetscDeviceCtx *dc) {
   PetscErrorCode ierr;
   HipAIJ *a = SA(A);
   Mat_SeqAIJHIP *d = SD(A);
-  PetscDeviceCtx *dc;
-  if (d->t_state == HipObjState(A) && d->t_a) return 0;
-  ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-  /* the device copy of A first: building it discards everything that belonged to an older pattern, a cached transpose included
-   * (device_free), so it must not happen between the check below and the use of the cached arrays */
+  PetscInt *ti, *tj, *tperm;
+  /* the device copy of A first: building it discards everything that belonged to an older pattern, the transposes included (device_free) */
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
-  if (a->bs > 1) {
-    /* BAIJ (MatMultTranspose_SeqBAIJ / MatMultTransposeAdd_SeqBAIJ, baij2.c:1579, 1740): the block transpose -- block rows and columns
-     * exchanged by the same stable counting sort (an output row's contributions in increasing original block row, the order the
-     * reference's scatter loop adds them in), every bs x bs block (column-major, baij.h:13-30) transposed -- built on the host whenever
-     * the matrix moved, then A^T x is the row-block BCSR kernel over it. */
-    PetscInt mbs = a->m, bs = a->bs, bs2 = bs * bs, nbs = a->n / bs, nzb = a->nz;      /* (a->m counts block rows, a->n scalar columns) */
-    PetscInt *ti, *tj, *next, *sc; PetscScalar *ta;
-    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nbs + 1), &ti);CHKERRQ(ierr);
-    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nzb, 1), &tj);CHKERRQ(ierr);
-    ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(nzb, 1) * (size_t)bs2, &ta);CHKERRQ(ierr);
-    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nbs, 1), &next);CHKERRQ(ierr);
-    memset(ti, 0, sizeof(PetscInt) * (size_t)(nbs + 1));
-    for (PetscInt k = 0; k < nzb; k++) ti[a->j[k] + 1]++;
-    for (PetscInt c = 0; c < nbs; c++) ti[c + 1] += ti[c];
-    for (PetscInt c = 0; c < nbs; c++) next[c] = ti[c];
-    for (PetscInt r = 0; r < mbs; r++)
-      for (PetscInt k = a->i[r]; k < a->i[r + 1]; k++) {
-        PetscInt p = next[a->j[k]]++;
-        const PetscScalar *blk = a->a + (size_t)k * bs2; PetscScalar *tb = ta + (size_t)p * bs2;
-        tj[p] = r;
-        for (PetscInt c = 0; c < bs; c++) for (PetscInt q = 0; q < bs; q++) tb[c * bs + q] = blk[q * bs + c];
-      }
-    if (d->t_i) { mi355x_free(d->t_i); mi355x_free(d->t_j); mi355x_free(d->t_a); mi355x_spmv_plan_destroy(d->t_plan); d->t_plan = NULL; d->t_i = NULL; }
-    CHKHIP(mi355x_malloc((void **)&d->t_i, sizeof(PetscInt) * (size_t)(nbs + 1)));
-    CHKHIP(mi355x_malloc((void **)&d->t_j, sizeof(PetscInt) * (size_t)PetscMax(nzb, 1) + 16));
-    CHKHIP(mi355x_malloc((void **)&d->t_a, sizeof(PetscScalar) * (size_t)PetscMax(nzb, 1) * (size_t)bs2 + 16));
-    CHKHIP(mi355x_memcpy_h2d(dc->h, d->t_i, ti, sizeof(PetscInt) * (size_t)(nbs + 1)));
-    CHKHIP(mi355x_memcpy_h2d(dc->h, d->t_j, tj, sizeof(PetscInt) * (size_t)nzb));
-    CHKHIP(mi355x_memcpy_h2d(dc->h, d->t_a, ta, sizeof(PetscScalar) * (size_t)nzb * (size_t)bs2));
-    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nbs + 1), &sc);CHKERRQ(ierr);
-    for (PetscInt c = 0; c <= nbs; c++) sc[c] = ti[c] * bs2;            /* the plan partitions the VALUE stream (as the matrix's own) */
-    CHKHIP(mi355x_spmv_plan_create(dc->h, nbs, sc, NULL, &d->t_plan));
-    CHKHIP(mi355x_handle_synchronize(dc->h));
-    HipFree(ti); HipFree(tj); HipFree(ta); HipFree(next); HipFree(sc);
-    d->t_state = HipObjState(A);
-    d->t_pattern_nz = nzb;
-    d->t_builds++;
-    return 0;
+  if (d->b.plan) {
+    if (!d->tb.plan) {
+      const PetscInt bs = d->b.bs;
+      PetscInt *bi, *bj, *perm;
+      ierr = companion_pattern(a, bs, d->b.nblocks, &bi, &bj, &perm);CHKERRQ(ierr);
+      ierr = transpose_pattern(a->m / bs, a->n / bs, bi, bj, bs, perm, &ti, &tj, &tperm);CHKERRQ(ierr);
+      ierr = form_upload(dc, &d->tb, a->n / bs, bs, ti, tj, tperm, NULL);CHKERRQ(ierr);
+      HipFree(bi); HipFree(bj); HipFree(perm); HipFree(ti); HipFree(tj); HipFree(tperm);
+    }
+    return form_current(dc, &d->tb, d->mat.a);
   }
-  if (d->t_a && d->t_perm && d->t_pattern_nz == a->nz && d->pattern_nz == a->nz) {
+  if (d->t.plan && d->t.fresh) return 0;
+  if (d->t.plan && d->t.perm) {
     /* only the VALUES changed since the transpose was built (a time step, a Newton iteration, MatScale / MatDiagonalScale /
-     * MatSetValuesBatch on the device copy): A^T's values are the matrix's values in another order, and that order -- the
-     * permutation of the counting sort below -- is on the device.  One gather kernel over the current device values; nothing
-     * is rebuilt on the host, nothing crosses PCIe beyond what MatSeqAIJHIPUpload needed for the matrix itself. */
-    CHKHIP(mi355x_pack(dc->h, (size_t)a->nz, d->t_perm, d->d_a, d->t_a));
-    if (d->t_tiled) CHKHIP(mi355x_spmv_tiled_refresh_values(dc->h, d->t_tiled, d->t_a));
-    d->t_state = HipObjState(A);
+     * MatSetValuesBatch on the device copy): A^T's values are the matrix's values in another order, and that order is on the device.
+     * One gather kernel over the current device values; nothing is rebuilt on the host, nothing crosses PCIe beyond what
+     * MatSeqAIJHIPUpload needed for the matrix itself. */
     d->t_refreshes++;
-    return 0;
+    return form_current(dc, &d->t, d->mat.a);
   }
-  PetscInt m = a->m, n = a->n, nz = a->nz;
-  PetscInt *ti, *tj, *next, *perm; PetscScalar *ta;
-  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(n + 1), &ti);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nz, 1), &tj);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(nz, 1), &ta);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(n, 1), &next);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nz, 1), &perm);CHKERRQ(ierr);
-  memset(ti, 0, sizeof(PetscInt) * (size_t)(n + 1));
-  for (PetscInt k = 0; k < nz; k++) ti[a->j[k] + 1]++;
-  for (PetscInt c = 0; c < n; c++) ti[c + 1] += ti[c];
-  for (PetscInt c = 0; c < n; c++) next[c] = ti[c];
-  for (PetscInt r = 0; r < m; r++)
-    for (PetscInt k = a->i[r]; k < a->i[r + 1]; k++) { PetscInt p = next[a->j[k]]++; tj[p] = r; ta[p] = a->a[k]; perm[p] = k; }
-  if (d->t_i) { mi355x_free(d->t_i); mi355x_free(d->t_j); mi355x_free(d->t_a); mi355x_spmv_plan_destroy(d->t_plan); d->t_plan = NULL; }
-  if (d->t_tiled) { mi355x_spmv_tiled_destroy(d->t_tiled); d->t_tiled = NULL; }
-  if (d->t_perm) { mi355x_free(d->t_perm); d->t_perm = NULL; }
-  CHKHIP(mi355x_malloc((void **)&d->t_perm, sizeof(PetscInt) * (size_t)PetscMax(nz, 1)));
-  CHKHIP(mi355x_memcpy_h2d(dc->h, d->t_perm, perm, sizeof(PetscInt) * (size_t)nz));
-  CHKHIP(mi355x_malloc((void **)&d->t_i, sizeof(PetscInt) * (size_t)(n + 1)));
-  CHKHIP(mi355x_malloc((void **)&d->t_j, sizeof(PetscInt) * (size_t)PetscMax(nz, 1) + 16));
-  CHKHIP(mi355x_malloc((void **)&d->t_a, sizeof(PetscScalar) * (size_t)PetscMax(nz, 1) + 16));
-  CHKHIP(mi355x_memcpy_h2d(dc->h, d->t_i, ti, sizeof(PetscInt) * (size_t)(n + 1)));
-  CHKHIP(mi355x_memcpy_h2d(dc->h, d->t_j, tj, sizeof(PetscInt) * (size_t)nz));
-  CHKHIP(mi355x_memcpy_h2d(dc->h, d->t_a, ta, sizeof(PetscScalar) * (size_t)nz));
-  CHKHIP(mi355x_spmv_plan_create(dc->h, n, ti, NULL, &d->t_plan));
-  { /* the transpose of a stencil matrix is a stencil matrix: same index compression / row patterns as the matrix itself */
+  /* BAIJ (MatMultTranspose_SeqBAIJ / MatMultTransposeAdd_SeqBAIJ, baij2.c:1579, 1740): the block transpose, its values placed on the host
+   * (a->m counts block rows, a->n scalar columns) */
+  const PetscInt bs = a->bs > 1 ? a->bs : 1, nbc = a->n / bs;
+  const size_t nvals = (size_t)a->nz * (size_t)(bs * bs);
+  PetscScalar *ta;
+  form_free(&d->t);
+  ierr = transpose_pattern(a->m, nbc, a->i, a->j, bs, NULL, &ti, &tj, &tperm);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscScalar) * PetscMax(nvals, 1), &ta);CHKERRQ(ierr);
+  for (size_t k = 0; k < nvals; k++) ta[k] = a->a[tperm[k]];
+  ierr = form_upload(dc, &d->t, nbc, bs, ti, tj, bs > 1 ? NULL : tperm, ta);CHKERRQ(ierr);
+  if (bs == 1) {
+    /* the transpose of a stencil matrix is a stencil matrix: same index compression / row patterns as the matrix itself */
     PetscInt ic = 1, rp = 1;
     ierr = hip_mat_option(A, HOPT_IC, &ic);CHKERRQ(ierr);
     ierr = hip_mat_option(A, HOPT_RP, &rp);CHKERRQ(ierr);
     if (ic) {
-      CHKHIP(mi355x_spmv_plan_compress_indices(dc->h, d->t_plan, ti, tj));
-      CHKHIP(mi355x_spmv_plan_use_patterns(d->t_plan, rp ? 1 : 0, NULL));
+      CHKHIP(mi355x_spmv_plan_compress_indices(dc->h, d->t.plan, ti, tj));
+      CHKHIP(mi355x_spmv_plan_use_patterns(d->t.plan, rp ? 1 : 0, NULL));
     }
+    CHKHIP(mi355x_handle_synchronize(dc->h));
   }
-  CHKHIP(mi355x_handle_synchronize(dc->h));
-  if (d->tiled) {
+  if (d->mat.tiled) {
     /* the matrix took the column-tiled product (its gathers miss the caches): so do its transpose's, whose rows pick their columns
-     * from the same wide windows.  Same rule: kept if at least half of the nonzeros fall into pairs worth staging. */
-    PetscInt tl = -1, smin = 0; long staged = 0, rest = 0;
+     * from the same wide windows */
+    PetscInt tl = -1;
     ierr = hip_mat_option(A, HOPT_TILED, &tl);CHKERRQ(ierr);
-    ierr = hip_mat_option(A, HOPT_TILED_SMIN, &smin);CHKERRQ(ierr);
-    if (mi355x_spmv_tiled_build(n, m, ti, tj, (int)smin, &d->t_tiled)) d->t_tiled = NULL;   /* (the row-block kernel over the cached transpose serves) */
-    else {
-      CHKHIP(mi355x_spmv_tiled_info(d->t_tiled, &staged, &rest, NULL, NULL, NULL));
-      if (tl < 0 && 2 * staged < (long)nz) { mi355x_spmv_tiled_destroy(d->t_tiled); d->t_tiled = NULL; }
-      else { CHKHIP(mi355x_spmv_tiled_upload(dc->h, d->t_tiled, d->t_a)); CHKHIP(mi355x_spmv_tiled_drop_host(d->t_tiled)); }
-    }
+    ierr = tiled_decide(A, tl, PETSC_FALSE, nbc, a->m, ti, tj, &d->t.tiled);CHKERRQ(ierr);
+    if (d->t.tiled) { CHKHIP(mi355x_spmv_tiled_upload(dc->h, d->t.tiled, d->t.a)); CHKHIP(mi355x_spmv_tiled_drop_host(d->t.tiled)); }
   }
-  HipFree(ti); HipFree(tj); HipFree(ta); HipFree(next); HipFree(perm);
-  d->t_state = HipObjState(A);
-  d->t_pattern_nz = nz;
+  HipFree(ti); HipFree(tj); HipFree(tperm); HipFree(ta);
   d->t_builds++;
   return 0;
 }
@@ -660,10 +694,7 @@ static PetscErrorCode batch_map_build(Mat A, PetscInt nb, PetscInt bs, const Pet
     segptr[nseg] = run; }
   for (size_t t = 0; t < T; t++) if (slot[t] >= 0) order[count[slot[t] + 1]++] = (PetscInt)t;
   ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-  if (d->bm_order) mi355x_free(d->bm_order);
-  if (d->bm_segptr) mi355x_free(d->bm_segptr);
-  if (d->bm_segslot) mi355x_free(d->bm_segslot);
-  d->bm_order = d->bm_segptr = d->bm_segslot = NULL;
+  batch_map_free(d);
   CHKHIP(mi355x_malloc((void **)&d->bm_order, sizeof(PetscInt) * PetscMax(used, 1)));
   CHKHIP(mi355x_malloc((void **)&d->bm_segptr, sizeof(PetscInt) * (size_t)(nseg + 1)));
   CHKHIP(mi355x_malloc((void **)&d->bm_segslot, sizeof(PetscInt) * (size_t)PetscMax(nseg, 1)));
@@ -700,15 +731,12 @@ static PetscErrorCode MatSetValuesBatch_SeqAIJHIP(Mat A, PetscInt nb, PetscInt b
     d->bm_vcap = d->bm_T;
   }
   CHKHIP(mi355x_memcpy_h2d(dc->h, d->bm_v, v, sizeof(PetscScalar) * d->bm_T));
-  { PetscErrorCode e__ = VecHIPProductMatrixChanges(A);CHKERRQ(e__); }
-  CHKHIP(mi355x_csr_assemble(dc->h, d->bm_nseg, d->bm_segptr, d->bm_segslot, d->bm_order, d->bm_v, d->d_a));
-  CHKHIP(mi355x_memcpy_d2h(dc->h, a->a, d->d_a, sizeof(PetscScalar) * (size_t)a->nz));   /* host mirror follows */
-  CHKHIP(mi355x_handle_synchronize(dc->h));                    /* v and a->a are pageable host memory */
   /* MatSetValuesBatch's wrapper leaves the state alone and the MatAssemblyEnd that has to follow bumps it once: the
    * device copy is stamped with that state, so the assembly does not trigger an upload */
-  d->uploaded_state = HipObjState(A) + 1;
-  d->t_state = -1; d->tiled_fresh = PETSC_FALSE; d->b_fresh = PETSC_FALSE; d->tb_fresh = PETSC_FALSE;
-  CHKHIP(mi355x_spmv_plan_drop_value_patterns(d->plan));
+  ierr = device_values_changed(A);CHKERRQ(ierr);
+  CHKHIP(mi355x_csr_assemble(dc->h, d->bm_nseg, d->bm_segptr, d->bm_segslot, d->bm_order, d->bm_v, d->mat.a));
+  CHKHIP(mi355x_memcpy_d2h(dc->h, a->a, d->mat.a, sizeof(PetscScalar) * (size_t)a->nz));   /* host mirror follows */
+  CHKHIP(mi355x_handle_synchronize(dc->h));                    /* v and a->a are pageable host memory */
   ierr = PetscLogFlops((PetscLogDouble)d->bm_T);CHKERRQ(ierr);
   return 0;
 }
@@ -724,12 +752,56 @@ static PetscErrorCode MatAssemblyEnd_SeqAIJHIP(Mat A, MatAssemblyType mode) {
 #endif
 static PetscErrorCode MatMult_SeqAIJHIP_device(Mat A, Vec xx, Vec yy);
 PetscErrorCode MatMultDiagonalScale_HIPMI355X(Mat A, Vec dd, Vec xx, Vec yy, PetscBool *ok);
-/* the column-tiled form keeps its own copy of the values in its own order: after a device-side change of d_a (MatScale,
- * MatDiagonalScale, MatZeroEntries, MatSetValuesBatch on the device copy) one gather brings it up to date, when it is next used */
-static PetscErrorCode tiled_values_current(Mat A, PetscDeviceCtx *dc) {
+/* what the product of A (transpose: of A^T) runs on: the blocked companion or the device copy itself, their transposes for A^T.  The
+ * transpose forms are built here when missing and brought up to date; a forward product takes the device copy as it is (its caller
+ * uploads) and the forward forms' values are brought up to date in product()'s timed window */
+static PetscErrorCode product_form(Mat A, PetscBool transpose, PetscDeviceCtx *dc, HipDevForm **f) {
   Mat_SeqAIJHIP *d = SD(A);
-  if (d->tiled && !d->tiled_fresh) { CHKHIP(mi355x_spmv_tiled_refresh_values(dc->h, d->tiled, d->d_a)); d->tiled_fresh = PETSC_TRUE; }
+  if (transpose) { PetscErrorCode ierr = transpose_current(A, dc);CHKERRQ(ierr); }
+  if (d->b.plan) *f = transpose ? &d->tb : &d->b;
+  else *f = transpose ? &d->t : &d->mat;
   return 0;
+}
+/* z = op(A) x (yy NULL) or z = y + op(A) x (zz may be yy), op(A) = A or A^T (MatMultTranspose: 0 + p1 + p2 ... == p1 + p2 ... bit for bit,
+ * so the plain product kernel serves).  The one place that picks the kernel: MatMult_SeqBAIJ_4 on the matrix cores (16-byte stores of y;
+ * a vector borrowing storage at an odd offset takes the FMA kernel), the BCSR row-block kernel (BAIJ, the blocked companion and their
+ * block transposes), the column-tiled kernel (with the row-block CSR kernel for an x it cannot take), the row-block CSR kernel.  The
+ * forward products are timed (MatTimingBegin/End). */
+static PetscErrorCode product(Mat A, PetscBool transpose, Vec xx, Vec yy, Vec zz) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
+  const PetscScalar *x, *y = NULL; PetscScalar *z; PetscDeviceCtx *dc; HipDevForm *f = NULL;
+  ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+  ierr = product_form(A, transpose, dc, &f);CHKERRQ(ierr);
+  const PetscBool cprow = (PetscBool)(f == &d->mat && f->bs == 1 && d->cprow);   /* rows without entries are not visited */
+  ierr = VecHIPGetRead(xx, &x);CHKERRQ(ierr);
+  if (!yy) { ierr = VecHIPGetWrite(zz, &z);CHKERRQ(ierr); }
+  else if (zz == yy) { ierr = VecHIPGetReadWrite(zz, &z);CHKERRQ(ierr); y = z; }
+  else {
+    ierr = VecHIPGetRead(yy, &y);CHKERRQ(ierr);
+    ierr = VecHIPGetWrite(zz, &z);CHKERRQ(ierr);
+    if (cprow) { CHKHIP(mi355x_vec_copy(dc->h, (size_t)a->m, y, z)); y = z; }   /* aij.c:1314-1316 */
+  }
+  if (!transpose) { ierr = MatTimingBegin(A, dc->h);CHKERRQ(ierr); }
+  ierr = form_current(dc, f, d->mat.a);CHKERRQ(ierr);
+  if (f == &d->mat && f->bs == 4 && d->baij4_mfma && !y && !(((size_t)z) & 15)) CHKHIP(mi355x_spmv_bsr4_mfma(dc->h, a->m, 0, f->i, f->j, f->a, x, z));
+  else if (f->bs > 1 && y) CHKHIP(mi355x_spmv_bsr_planned_add(dc->h, f->plan, (int)f->bs, f->i, f->j, f->a, x, y, z));
+  else if (f->bs > 1) CHKHIP(mi355x_spmv_bsr_planned(dc->h, f->plan, (int)f->bs, f->i, f->j, f->a, x, z));
+  else {
+    int rc = 801;
+    if (f->tiled) { rc = mi355x_spmv_tiled(dc->h, f->tiled, x, y, z); if (rc && rc != 801) CHKHIP(rc); }
+    if (rc && y) CHKHIP(mi355x_spmv_csr_add(dc->h, f->plan, f->i, f->j, f->a, x, y, z));
+    else if (rc) {                                                       /* no tiled form, or an x it cannot take (storage borrowed at an odd offset) */
+      if (cprow) CHKHIP(mi355x_vec_set(dc->h, (size_t)a->m, 0.0, z));
+      CHKHIP(mi355x_spmv_csr(dc->h, f->plan, f->i, f->j, f->a, x, z));
+    }
+  }
+  if (!transpose) { ierr = MatTimingEnd(A, dc->h);CHKERRQ(ierr); }
+  ierr = VecHIPRestoreWrite(zz);CHKERRQ(ierr);
+  const PetscInt bs = a->bs > 1 ? a->bs : 1;                           /* aij.c:1281, 1324; baij2.c: 2 bs^2 nz (- bs nonzero block rows) */
+  if (transpose) return PetscLogFlops(2.0 * a->nz);
+  if (yy) return PetscLogFlops(2.0 * bs * bs * a->nz);
+  return PetscLogFlops(2.0 * bs * bs * a->nz - (double)bs * a->nonzerorows);
 }
 static PetscErrorCode MatMult_SeqAIJHIP(Mat A, Vec xx, Vec yy) {   /* MatMult_SeqAIJCUSP aijcusp.cu:349 */
   PetscErrorCode ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);       /* from here on the device copy holds the values of THIS call */
@@ -744,31 +816,13 @@ static PetscErrorCode MatMult_SeqAIJHIP(Mat A, Vec xx, Vec yy) {   /* MatMult_Se
   }
   return MatMult_SeqAIJHIP_device(A, xx, yy);
 }
-static PetscErrorCode MatMult_SeqAIJHIP_device(Mat A, Vec xx, Vec yy) {   /* y = A x with the device copy as it is */
-  PetscErrorCode ierr;
-  HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
-  const PetscScalar *x; PetscScalar *y; PetscDeviceCtx *dc;
-  ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(xx, &x);CHKERRQ(ierr);
-  ierr = VecHIPGetWrite(yy, &y);CHKERRQ(ierr);
-  ierr = MatTimingBegin(A, dc->h);CHKERRQ(ierr);
-  if (a->bs == 4 && d->baij4_mfma && !(((size_t)y) & 15)) CHKHIP(mi355x_spmv_bsr4_mfma(dc->h, a->m, 0, d->d_i, d->d_j, d->d_a, x, y));   /* matrix cores: MatMult_SeqBAIJ_4 (16-byte stores of y; a vector borrowing storage at an odd offset takes the FMA kernel) */
-  else if (a->bs > 1) CHKHIP(mi355x_spmv_bsr_planned(dc->h, d->plan, a->bs, d->d_i, d->d_j, d->d_a, x, y));
-  else if (d->b_plan) { ierr = blocked_values_current(A, dc);CHKERRQ(ierr); CHKHIP(mi355x_spmv_bsr_planned(dc->h, d->b_plan, (int)d->b_bs, d->b_i, d->b_j, d->b_a, x, y)); }   /* the blocked companion */
-  else {
-    int rc = 801;
-    if (d->tiled) { ierr = tiled_values_current(A, dc);CHKERRQ(ierr); rc = mi355x_spmv_tiled(dc->h, d->tiled, x, NULL, y); if (rc && rc != 801) CHKHIP(rc); }
-    if (rc) {                                                            /* no tiled form, or an x it cannot take (storage borrowed at an odd offset) */
-      if (d->cprow) CHKHIP(mi355x_vec_set(dc->h, (size_t)a->m, 0.0, y));   /* rows without entries */
-      CHKHIP(mi355x_spmv_csr(dc->h, d->plan, d->d_i, d->d_j, d->d_a, x, y));
-    }
-  }
-  ierr = MatTimingEnd(A, dc->h);CHKERRQ(ierr);
-  ierr = VecHIPRestoreWrite(yy);CHKERRQ(ierr);
-  if (a->bs > 1) { ierr = PetscLogFlops(2.0 * a->bs * a->bs * a->nz - (double)a->bs * a->nonzerorows);CHKERRQ(ierr); }
-  else { ierr = PetscLogFlops(2.0 * a->nz - a->nonzerorows);CHKERRQ(ierr); }   /* aij.c:1281 */
-  return 0;
+static PetscErrorCode MatMult_SeqAIJHIP_device(Mat A, Vec xx, Vec yy) { return product(A, PETSC_FALSE, xx, NULL, yy); }   /* y = A x with the device copy as it is */
+static PetscErrorCode MatMultAdd_SeqAIJHIP(Mat A, Vec xx, Vec yy, Vec zz) {   /* MatMultAdd_SeqAIJCUSP aijcusp.cu:405; MatMultAdd_SeqBAIJ_N baij2.c:1168-1480 */
+  PetscErrorCode ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
+  return product(A, PETSC_FALSE, xx, yy, zz);
 }
+static PetscErrorCode MatMultTranspose_SeqAIJHIP(Mat A, Vec xx, Vec yy) { return product(A, PETSC_TRUE, xx, NULL, yy); }   /* aij.c:1124: VecSet(yy,0); Add */
+static PetscErrorCode MatMultTransposeAdd_SeqAIJHIP(Mat A, Vec xx, Vec zz, Vec yy) { return product(A, PETSC_TRUE, xx, zz, yy); }   /* aij.c:1078: yy = zz + A^T xx */
 
 /* how many times the values of a sequential matrix of this type have crossed to the device (tests: value updates with an
  * unchanged pattern must not add to it) */
@@ -778,74 +832,35 @@ PetscErrorCode MatHIPMI355XGetUploadCount(Mat A, PetscInt *n) {
   *n = SD(A)->n_uploads;
   return 0;
 }
+/* the sequential matrix of this type an info call answers for: A itself, or the diagonal block of an MPIAIJ matrix of this type; else NULL */
+static PetscErrorCode seq_block(Mat A, Mat *S) {
+  PetscErrorCode ierr;
+  Mat Ad = NULL;
+  *S = NULL;
+  if (A->ops->mult == MatMult_SeqAIJHIP) { *S = A; return 0; }
+  if (!strcmp(HipObjTypeName(A), MATMPIAIJHIPMI355X)) { ierr = MatMPIAIJGetSeqAIJ(A, &Ad, NULL, NULL);CHKERRQ(ierr); }
+  if (Ad && Ad->ops->mult == MatMult_SeqAIJHIP) *S = Ad;
+  return 0;
+}
 /* number of distinct (col - row) offsets of the index-compressed SpMV plan, 0 when the matrix streams plain 4-byte
  * column indices (bench.py labels its roofline kernel with it; an MPIAIJ matrix answers for its diagonal block) */
 PetscErrorCode MatHIPMI355XGetIndexCompression(Mat A, PetscInt *noffsets) {
   PetscErrorCode ierr; int ntab = 0;
   *noffsets = 0;
   if (!A) return 0;
-  if (A->ops->mult != MatMult_SeqAIJHIP) {
-    Mat Ad = NULL;
-    if (!strcmp(HipObjTypeName(A), MATMPIAIJHIPMI355X)) { ierr = MatMPIAIJGetSeqAIJ(A, &Ad, NULL, NULL);CHKERRQ(ierr); }
-    if (!Ad || Ad->ops->mult != MatMult_SeqAIJHIP) return 0;
-    A = Ad;
-  }
+  ierr = seq_block(A, &A);CHKERRQ(ierr);
+  if (!A) return 0;
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
-  if (SD(A)->plan && SA(A)->bs <= 1) CHKHIP(mi355x_spmv_plan_is_compressed(SD(A)->plan, &ntab));
+  if (SD(A)->mat.plan && SA(A)->bs <= 1) CHKHIP(mi355x_spmv_plan_is_compressed(SD(A)->mat.plan, &ntab));
   *noffsets = ntab;
   return 0;
 }
 
-/* the block transpose of the blocked companion (MatMultTranspose / MatMultTransposeAdd of such a matrix): built from the host CSR arrays
- * at the first transpose product after the pattern changed -- block rows and columns exchanged by a stable counting sort (an output
- * row's contributions in increasing original block row, the order aij.c:1100-1112 adds them in), every block transposed --, its
- * values a permutation gather of d_a like the companion's own */
-static PetscErrorCode blocked_transpose_current(Mat A, PetscDeviceCtx *dc) {
-  PetscErrorCode ierr;
-  HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
-  if (!d->b_plan) return 0;
-  if (!d->tb_plan) {
-    const PetscInt bs = d->b_bs, bs2 = bs * bs, nn = a->m / bs, nbs = a->n / bs, nblk = d->b_nblocks;
-    PetscInt *ti, *tj, *next, *perm, *sc;
-    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nbs + 1), &ti);CHKERRQ(ierr);
-    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nblk, 1), &tj);CHKERRQ(ierr);
-    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nbs, 1), &next);CHKERRQ(ierr);
-    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nblk, 1) * (size_t)bs2, &perm);CHKERRQ(ierr);
-    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nbs + 1), &sc);CHKERRQ(ierr);
-    memset(ti, 0, sizeof(PetscInt) * (size_t)(nbs + 1));
-    for (PetscInt i = 0; i < nn; i++) { const PetscInt r = i * bs; for (PetscInt g = 0; g < a->i[r + 1] - a->i[r]; g += bs) ti[a->j[a->i[r] + g] / bs + 1]++; }
-    for (PetscInt c = 0; c < nbs; c++) ti[c + 1] += ti[c];
-    for (PetscInt c = 0; c < nbs; c++) next[c] = ti[c];
-    for (PetscInt i = 0; i < nn; i++) {
-      const PetscInt r = i * bs, len = a->i[r + 1] - a->i[r];
-      for (PetscInt g = 0; g < len; g += bs) {
-        const PetscInt p = next[a->j[a->i[r] + g] / bs]++;
-        tj[p] = i;
-        /* transposed block, column-major: entry (row qq, column cc) of it is entry (row cc, column qq) of the block */
-        for (PetscInt cc = 0; cc < bs; cc++) for (PetscInt qq = 0; qq < bs; qq++) perm[(size_t)p * bs2 + cc * bs + qq] = a->i[r + cc] + g + qq;
-      }
-    }
-    for (PetscInt c = 0; c <= nbs; c++) sc[c] = ti[c] * bs2;
-    CHKHIP(mi355x_malloc((void **)&d->tb_i, sizeof(PetscInt) * (size_t)(nbs + 1)));
-    CHKHIP(mi355x_malloc((void **)&d->tb_j, sizeof(PetscInt) * (size_t)PetscMax(nblk, 1) + 16));
-    CHKHIP(mi355x_malloc((void **)&d->tb_perm, sizeof(PetscInt) * (size_t)PetscMax(nblk, 1) * (size_t)bs2));
-    CHKHIP(mi355x_malloc((void **)&d->tb_a, sizeof(PetscScalar) * (size_t)PetscMax(nblk, 1) * (size_t)bs2 + 16));
-    CHKHIP(mi355x_memcpy_h2d(dc->h, d->tb_i, ti, sizeof(PetscInt) * (size_t)(nbs + 1)));
-    CHKHIP(mi355x_memcpy_h2d(dc->h, d->tb_j, tj, sizeof(PetscInt) * (size_t)nblk));
-    CHKHIP(mi355x_memcpy_h2d(dc->h, d->tb_perm, perm, sizeof(PetscInt) * (size_t)nblk * (size_t)bs2));
-    CHKHIP(mi355x_spmv_plan_create(dc->h, nbs, sc, NULL, &d->tb_plan));
-    CHKHIP(mi355x_handle_synchronize(dc->h));
-    HipFree(ti); HipFree(tj); HipFree(next); HipFree(perm); HipFree(sc);
-    d->tb_fresh = PETSC_FALSE;
-  }
-  if (!d->tb_fresh) { CHKHIP(mi355x_pack(dc->h, (size_t)a->nz, d->tb_perm, d->d_a, d->tb_a)); d->tb_fresh = PETSC_TRUE; }
-  return 0;
-}
 /* the blocked companion of a sequential matrix, if the analysis chose it: block size and number of blocks (0, 0: none) */
 PetscErrorCode MatHIPMI355XGetBlockedInfo(Mat A, PetscInt *bs, PetscInt *nblocks) {
   *bs = 0; *nblocks = 0;
   if (!A || A->ops->mult != MatMult_SeqAIJHIP) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "not a sequential HIPMI355X AIJ matrix");
-  if (SD(A)->b_plan) { *bs = SD(A)->b_bs; *nblocks = SD(A)->b_nblocks; }
+  if (SD(A)->b.plan) { *bs = SD(A)->b.bs; *nblocks = SD(A)->b.nblocks; }
   return 0;
 }
 
@@ -856,7 +871,7 @@ PetscErrorCode MatHIPMI355XGetTiledInfo(Mat A, PetscInt *staged, PetscInt *remai
   *staged = 0; *remainder = 0;
   if (!A || A->ops->mult != MatMult_SeqAIJHIP) return 0;
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
-  if (SD(A)->tiled) CHKHIP(mi355x_spmv_tiled_info(SD(A)->tiled, &s_, &r_, NULL, NULL, NULL));
+  if (SD(A)->mat.tiled) CHKHIP(mi355x_spmv_tiled_info(SD(A)->mat.tiled, &s_, &r_, NULL, NULL, NULL));
   *staged = (PetscInt)s_; *remainder = (PetscInt)r_;
   return 0;
 }
@@ -866,16 +881,12 @@ PetscErrorCode MatHIPMI355XGetRowPatterns(Mat A, PetscInt *npat) {
   PetscErrorCode ierr; int np_ = 0;
   *npat = 0;
   if (!A) return 0;
-  if (A->ops->mult != MatMult_SeqAIJHIP) {
-    Mat Ad = NULL;
-    if (!strcmp(HipObjTypeName(A), MATMPIAIJHIPMI355X)) { ierr = MatMPIAIJGetSeqAIJ(A, &Ad, NULL, NULL);CHKERRQ(ierr); }
-    if (!Ad || Ad->ops->mult != MatMult_SeqAIJHIP) return 0;
-    A = Ad;
-  }
+  ierr = seq_block(A, &A);CHKERRQ(ierr);
+  if (!A) return 0;
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
-  if (SD(A)->plan && SA(A)->bs <= 1) {
+  if (SD(A)->mat.plan && SA(A)->bs <= 1) {
     PetscInt rp = 1;
-    CHKHIP(mi355x_spmv_plan_use_patterns(SD(A)->plan, -1, &np_));
+    CHKHIP(mi355x_spmv_plan_use_patterns(SD(A)->mat.plan, -1, &np_));
     ierr = hip_mat_option(A, HOPT_RP, &rp);CHKERRQ(ierr);
     if (!rp) np_ = 0;
   }
@@ -889,14 +900,10 @@ PetscErrorCode MatHIPMI355XGetValuePatterns(Mat A, PetscInt *nvpat) {
   PetscErrorCode ierr; int nv = 0;
   *nvpat = 0;
   if (!A) return 0;
-  if (A->ops->mult != MatMult_SeqAIJHIP) {
-    Mat Ad = NULL;
-    if (!strcmp(HipObjTypeName(A), MATMPIAIJHIPMI355X)) { ierr = MatMPIAIJGetSeqAIJ(A, &Ad, NULL, NULL);CHKERRQ(ierr); }
-    if (!Ad || Ad->ops->mult != MatMult_SeqAIJHIP) return 0;
-    A = Ad;
-  }
+  ierr = seq_block(A, &A);CHKERRQ(ierr);
+  if (!A) return 0;
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
-  if (SD(A)->plan && SA(A)->bs <= 1) CHKHIP(mi355x_spmv_plan_use_value_patterns(SD(A)->plan, -1, &nv));
+  if (SD(A)->mat.plan && SA(A)->bs <= 1) CHKHIP(mi355x_spmv_plan_use_value_patterns(SD(A)->mat.plan, -1, &nv));
   *nvpat = nv;
   return 0;
 }
@@ -904,19 +911,16 @@ PetscErrorCode MatHIPMI355XGetValuePatterns(Mat A, PetscInt *nvpat) {
 /* A/B switch for one matrix (the option -mat_hipmi355x_value_patterns is read at every upload; this overrides it until
  * the next upload): off -> the SpMV streams the value array again; on -> the dictionary is derived from the host copy now */
 PetscErrorCode MatHIPMI355XSetValuePatterns(Mat A, PetscBool on) {
-  PetscErrorCode ierr; PetscDeviceCtx *dc;
+  PetscErrorCode ierr; PetscDeviceCtx *dc; Mat S;
   if (!A) return 0;
-  if (A->ops->mult != MatMult_SeqAIJHIP) {
-    Mat Ad = NULL;
-    if (!strcmp(HipObjTypeName(A), MATMPIAIJHIPMI355X)) { ierr = MatMPIAIJGetSeqAIJ(A, &Ad, NULL, NULL);CHKERRQ(ierr); }
-    if (!Ad || Ad->ops->mult != MatMult_SeqAIJHIP) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "HIPMI355X AIJ matrix expected");
-    A = Ad;
-  }
+  ierr = seq_block(A, &S);CHKERRQ(ierr);
+  if (!S) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "HIPMI355X AIJ matrix expected");
+  A = S;
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
-  if (!SD(A)->plan || SA(A)->bs > 1) return 0;
+  if (!SD(A)->mat.plan || SA(A)->bs > 1) return 0;
   ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-  CHKHIP(mi355x_spmv_plan_use_value_patterns(SD(A)->plan, on ? 1 : 0, NULL));
-  if (on && device_values_current(A)) CHKHIP(mi355x_spmv_plan_value_patterns(dc->h, SD(A)->plan, SA(A)->i, SA(A)->j, SA(A)->a, NULL));
+  CHKHIP(mi355x_spmv_plan_use_value_patterns(SD(A)->mat.plan, on ? 1 : 0, NULL));
+  if (on && device_values_current(A)) CHKHIP(mi355x_spmv_plan_value_patterns(dc->h, SD(A)->mat.plan, SA(A)->i, SA(A)->j, SA(A)->a, NULL));
   return 0;
 }
 
@@ -948,14 +952,10 @@ PetscErrorCode MatHIPMI355XGetInodeInfo(Mat A, PetscInt *nodes, PetscInt *groups
   if (groups) *groups = 0;
   if (shared_indices) *shared_indices = 0;
   if (!A) return 0;
-  if (A->ops->mult != MatMult_SeqAIJHIP) {
-    Mat Ad = NULL;
-    if (!strcmp(HipObjTypeName(A), MATMPIAIJHIPMI355X)) { ierr = MatMPIAIJGetSeqAIJ(A, &Ad, NULL, NULL);CHKERRQ(ierr); }
-    if (!Ad || Ad->ops->mult != MatMult_SeqAIJHIP) return 0;
-    A = Ad;
-  }
+  ierr = seq_block(A, &A);CHKERRQ(ierr);
+  if (!A) return 0;
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
-  if (SD(A)->plan && SA(A)->bs <= 1) CHKHIP(mi355x_spmv_plan_group_info(SD(A)->plan, &ng, &ngj, NULL));
+  if (SD(A)->mat.plan && SA(A)->bs <= 1) CHKHIP(mi355x_spmv_plan_group_info(SD(A)->mat.plan, &ng, &ngj, NULL));
   if (nodes) *nodes = SA(A)->inode_count;
   if (groups) *groups = ng;
   if (shared_indices) *shared_indices = (PetscInt)ngj;
@@ -976,16 +976,16 @@ PetscErrorCode MatMultTDotBegin_HIPMI355X(Mat A, Vec xx, Vec yy, PetscBool *ok) 
   if (xx->map->n != a->n || yy->map->n != a->m || (HipCommSize(HipObjComm(xx)) > 1 && !HipCommDevice(HipObjComm(xx)))) return 0;
   ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
-  if (!d->plan) return 0;
-  CHKHIP(mi355x_spmv_plan_dot_available(d->plan, d->d_a, &ntab));   /* a plan whose kernel also leaves the per-block sums: patterns or 8-bit offsets */
+  if (!d->mat.plan) return 0;
+  CHKHIP(mi355x_spmv_plan_dot_available(d->mat.plan, d->mat.a, &ntab));   /* a plan whose kernel also leaves the per-block sums: patterns or 8-bit offsets */
   if (!ntab) return 0;
   ierr = VecHIPGetRead(xx, &x);CHKERRQ(ierr);
   ierr = VecHIPGetWrite(yy, &y);CHKERRQ(ierr);
   ierr = MatTimingBegin(A, dc->h);CHKERRQ(ierr);
-  CHKHIP(mi355x_spmv_csr_dot(dc->h, d->plan, d->d_i, d->d_j, d->d_a, x, y));
+  CHKHIP(mi355x_spmv_csr_dot(dc->h, d->mat.plan, d->mat.i, d->mat.j, d->mat.a, x, y));
   ierr = MatTimingEnd(A, dc->h);CHKERRQ(ierr);
   double *slot = mi355x_handle_device_scratch(dc->h) + PETSC_HIP_DPI_SLOT;
-  CHKHIP(mi355x_spmv_dot_finish(dc->h, d->plan, slot));
+  CHKHIP(mi355x_spmv_dot_finish(dc->h, d->mat.plan, slot));
   if (HipCommDevice(HipObjComm(xx))) CHKHIP(mi355x_comm_allreduce_sum(HipCommDevice(HipObjComm(xx)), dc->h, slot, 1));
   ierr = VecHIPRestoreWrite(yy);CHKERRQ(ierr);
   HipStateIncrease(yy);
@@ -1005,109 +1005,17 @@ PetscErrorCode MatMultDiagonalScale_HIPMI355X(Mat A, Vec dd, Vec xx, Vec yy, Pet
   if (a->bs > 1 || xx == yy || dd == yy || xx->map->n != a->n || yy->map->n != a->m || dd->map->n != a->m) return 0;
   ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
-  if (!d->plan || d->cprow || d->tiled || d->b_plan) return 0;         /* (the column-tiled and the blocked product have no scaling epilogue: the two calls stay two) */
+  if (!d->mat.plan || d->cprow || d->mat.tiled || d->b.plan) return 0;         /* (the column-tiled and the blocked product have no scaling epilogue: the two calls stay two) */
   ierr = VecHIPGetRead(xx, &x);CHKERRQ(ierr);
   ierr = VecHIPGetRead(dd, &dg);CHKERRQ(ierr);
   ierr = VecHIPGetWrite(yy, &y);CHKERRQ(ierr);
   ierr = MatTimingBegin(A, dc->h);CHKERRQ(ierr);
-  CHKHIP(mi355x_spmv_csr_scaled(dc->h, d->plan, d->d_i, d->d_j, d->d_a, x, dg, y));
+  CHKHIP(mi355x_spmv_csr_scaled(dc->h, d->mat.plan, d->mat.i, d->mat.j, d->mat.a, x, dg, y));
   ierr = MatTimingEnd(A, dc->h);CHKERRQ(ierr);
   ierr = VecHIPRestoreWrite(yy);CHKERRQ(ierr);
   HipStateIncrease(yy);
   ierr = PetscLogFlops(2.0 * a->nz - a->nonzerorows + a->m);CHKERRQ(ierr);
   *ok = PETSC_TRUE;
-  return 0;
-}
-
-static PetscErrorCode MatMultAdd_SeqAIJHIP(Mat A, Vec xx, Vec yy, Vec zz) {   /* MatMultAdd_SeqAIJCUSP aijcusp.cu:405 */
-  PetscErrorCode ierr;
-  HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
-  const PetscScalar *x, *y; PetscScalar *z; PetscDeviceCtx *dc;
-  ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-  ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
-  if (a->bs > 1) {   /* MatMultAdd_SeqBAIJ_3/_4/_N (baij2.c:1168-1480): the row-block kernel with y as the sums' start */
-    ierr = VecHIPGetRead(xx, &x);CHKERRQ(ierr);
-    if (zz == yy) { ierr = VecHIPGetReadWrite(zz, &z);CHKERRQ(ierr); y = z; }
-    else { ierr = VecHIPGetRead(yy, &y);CHKERRQ(ierr); ierr = VecHIPGetWrite(zz, &z);CHKERRQ(ierr); }
-    ierr = MatTimingBegin(A, dc->h);CHKERRQ(ierr);
-    CHKHIP(mi355x_spmv_bsr_planned_add(dc->h, d->plan, a->bs, d->d_i, d->d_j, d->d_a, x, y, z));
-    ierr = MatTimingEnd(A, dc->h);CHKERRQ(ierr);
-    ierr = VecHIPRestoreWrite(zz);CHKERRQ(ierr);
-    return PetscLogFlops(2.0 * a->bs * a->bs * a->nz);                   /* baij2.c: 2 bs^2 nz */
-  }
-  ierr = VecHIPGetRead(xx, &x);CHKERRQ(ierr);
-  if (zz == yy) { ierr = VecHIPGetReadWrite(zz, &z);CHKERRQ(ierr); y = z; }
-  else {
-    ierr = VecHIPGetRead(yy, &y);CHKERRQ(ierr);
-    ierr = VecHIPGetWrite(zz, &z);CHKERRQ(ierr);
-    if (d->cprow) { CHKHIP(mi355x_vec_copy(dc->h, (size_t)a->m, y, z)); y = z; }   /* aij.c:1314-1316 */
-  }
-  ierr = MatTimingBegin(A, dc->h);CHKERRQ(ierr);
-  if (d->b_plan && !d->cprow) { ierr = blocked_values_current(A, dc);CHKERRQ(ierr); CHKHIP(mi355x_spmv_bsr_planned_add(dc->h, d->b_plan, (int)d->b_bs, d->b_i, d->b_j, d->b_a, x, y, z)); }
-  else { int rc = 801;
-    if (d->tiled) { ierr = tiled_values_current(A, dc);CHKERRQ(ierr); rc = mi355x_spmv_tiled(dc->h, d->tiled, x, y, z); if (rc && rc != 801) CHKHIP(rc); }
-    if (rc) CHKHIP(mi355x_spmv_csr_add(dc->h, d->plan, d->d_i, d->d_j, d->d_a, x, y, z)); }
-  ierr = MatTimingEnd(A, dc->h);CHKERRQ(ierr);
-  ierr = VecHIPRestoreWrite(zz);CHKERRQ(ierr);
-  ierr = PetscLogFlops(2.0 * a->nz);CHKERRQ(ierr);
-  return 0;
-}
-
-static PetscErrorCode MatMultTransposeAdd_SeqAIJHIP(Mat A, Vec xx, Vec zz, Vec yy) {   /* aij.c:1078: yy = zz + A^T xx */
-  PetscErrorCode ierr;
-  HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
-  const PetscScalar *x, *z; PetscScalar *y; PetscDeviceCtx *dc;
-  ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-  if (a->bs <= 1) { ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr); }
-  if (a->bs <= 1 && d->b_plan) {                                      /* the blocked companion's block transpose: no scalar transpose is built */
-    ierr = blocked_transpose_current(A, dc);CHKERRQ(ierr);
-    ierr = VecHIPGetRead(xx, &x);CHKERRQ(ierr);
-    if (zz == yy) { ierr = VecHIPGetReadWrite(yy, &y);CHKERRQ(ierr); z = y; }
-    else { ierr = VecHIPGetRead(zz, &z);CHKERRQ(ierr); ierr = VecHIPGetWrite(yy, &y);CHKERRQ(ierr); }
-    CHKHIP(mi355x_spmv_bsr_planned_add(dc->h, d->tb_plan, (int)d->b_bs, d->tb_i, d->tb_j, d->tb_a, x, z, y));
-    ierr = VecHIPRestoreWrite(yy);CHKERRQ(ierr);
-    return PetscLogFlops(2.0 * a->nz);
-  }
-  ierr = upload_transpose(A);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(xx, &x);CHKERRQ(ierr);
-  if (zz == yy) { ierr = VecHIPGetReadWrite(yy, &y);CHKERRQ(ierr); z = y; }
-  else { ierr = VecHIPGetRead(zz, &z);CHKERRQ(ierr); ierr = VecHIPGetWrite(yy, &y);CHKERRQ(ierr); }
-  if (a->bs > 1) CHKHIP(mi355x_spmv_bsr_planned_add(dc->h, d->t_plan, a->bs, d->t_i, d->t_j, d->t_a, x, z, y));   /* MatMultTransposeAdd_SeqBAIJ, baij2.c:1740 */
-  else {
-    int rc = 801;
-    if (d->t_tiled) { rc = mi355x_spmv_tiled(dc->h, d->t_tiled, x, z, y); if (rc && rc != 801) CHKHIP(rc); }
-    if (rc) CHKHIP(mi355x_spmv_csr_add(dc->h, d->t_plan, d->t_i, d->t_j, d->t_a, x, z, y));
-  }
-  ierr = VecHIPRestoreWrite(yy);CHKERRQ(ierr);
-  ierr = PetscLogFlops(2.0 * a->nz);CHKERRQ(ierr);
-  return 0;
-}
-static PetscErrorCode MatMultTranspose_SeqAIJHIP(Mat A, Vec xx, Vec yy) {   /* aij.c:1124: VecSet(yy,0); Add */
-  PetscErrorCode ierr;
-  HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
-  const PetscScalar *x; PetscScalar *y; PetscDeviceCtx *dc;
-  ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-  if (a->bs <= 1) { ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr); }
-  if (a->bs <= 1 && d->b_plan) {
-    ierr = blocked_transpose_current(A, dc);CHKERRQ(ierr);
-    ierr = VecHIPGetRead(xx, &x);CHKERRQ(ierr);
-    ierr = VecHIPGetWrite(yy, &y);CHKERRQ(ierr);
-    CHKHIP(mi355x_spmv_bsr_planned(dc->h, d->tb_plan, (int)d->b_bs, d->tb_i, d->tb_j, d->tb_a, x, y));
-    ierr = VecHIPRestoreWrite(yy);CHKERRQ(ierr);
-    return PetscLogFlops(2.0 * a->nz);
-  }
-  ierr = upload_transpose(A);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(xx, &x);CHKERRQ(ierr);
-  ierr = VecHIPGetWrite(yy, &y);CHKERRQ(ierr);
-  /* 0 + p1 + p2 ... == p1 + p2 ... bit for bit, so the plain product kernel serves */
-  if (a->bs > 1) CHKHIP(mi355x_spmv_bsr_planned(dc->h, d->t_plan, a->bs, d->t_i, d->t_j, d->t_a, x, y));          /* MatMultTranspose_SeqBAIJ, baij2.c:1579 */
-  else {
-    int rc = 801;
-    if (d->t_tiled) { rc = mi355x_spmv_tiled(dc->h, d->t_tiled, x, NULL, y); if (rc && rc != 801) CHKHIP(rc); }
-    if (rc) CHKHIP(mi355x_spmv_csr(dc->h, d->t_plan, d->t_i, d->t_j, d->t_a, x, y));
-  }
-  ierr = VecHIPRestoreWrite(yy);CHKERRQ(ierr);
-  ierr = PetscLogFlops(2.0 * a->nz);CHKERRQ(ierr);
   return 0;
 }
 
@@ -1132,17 +1040,17 @@ static PetscErrorCode MatGetDiagonal_SeqAIJHIP(Mat A, Vec v) {   /* aij.c:1040 *
   ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
   ierr = VecHIPGetWrite(v, &dv);CHKERRQ(ierr);
-  CHKHIP(mi355x_csr_get_diagonal(dc->h, a->m, d->d_i, d->d_j, d->d_a, dv));
+  CHKHIP(mi355x_csr_get_diagonal(dc->h, a->m, d->mat.i, d->mat.j, d->mat.a, dv));
   return VecHIPRestoreWrite(v);
 }
 
 /* Value updates with an unchanged pattern: the host copy and the device copy are updated side by side, so
  * the next MatMult finds the device values current and nothing crosses PCIe (the reference's GPU back end re-sent the
  * whole matrix after every such call, aijcusp.cu:138-152).  The wrappers in mat.c bump the object state AFTER the op:
- * the device copy is stamped with that future state.  The cached transpose is dropped. */
+ * the device copy is stamped with that future state (device_values_changed); the derived forms follow by a gather. */
 static PetscBool device_values_current(Mat A) {
   Mat_SeqAIJHIP *d = SD(A);
-  return (PetscBool)(d->d_a && d->uploaded_state == HipObjState(A) && SA(A)->bs <= 1);
+  return (PetscBool)(d->mat.a && d->uploaded_state == HipObjState(A) && SA(A)->bs <= 1);
 }
 static PetscErrorCode MatScale_SeqAIJHIP(Mat A, PetscScalar alpha) {   /* MatScale_SeqAIJ: dscal on a->a */
   PetscErrorCode ierr;
@@ -1153,11 +1061,8 @@ static PetscErrorCode MatScale_SeqAIJHIP(Mat A, PetscScalar alpha) {   /* MatSca
   if (on_device) {
     PetscDeviceCtx *dc;
     ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-    { PetscErrorCode e__ = VecHIPProductMatrixChanges(A);CHKERRQ(e__); }
-    CHKHIP(mi355x_vec_scale(dc->h, vals, alpha, d->d_a));
-    d->uploaded_state = HipObjState(A) + 1;
-    d->t_state = -1; d->tiled_fresh = PETSC_FALSE; d->b_fresh = PETSC_FALSE; d->tb_fresh = PETSC_FALSE;
-    CHKHIP(mi355x_spmv_plan_drop_value_patterns(d->plan));
+    ierr = device_values_changed(A);CHKERRQ(ierr);
+    CHKHIP(mi355x_vec_scale(dc->h, vals, alpha, d->mat.a));
   }
   return PetscLogFlops((PetscLogDouble)vals);
 }
@@ -1170,11 +1075,8 @@ static PetscErrorCode MatZeroEntries_SeqAIJHIP(Mat A) {
   if (on_device) {
     PetscDeviceCtx *dc;
     ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-    { PetscErrorCode e__ = VecHIPProductMatrixChanges(A);CHKERRQ(e__); }
-    CHKHIP(mi355x_memset(dc->h, d->d_a, 0, sizeof(PetscScalar) * vals));
-    d->uploaded_state = HipObjState(A) + 1;
-    d->t_state = -1; d->tiled_fresh = PETSC_FALSE; d->b_fresh = PETSC_FALSE; d->tb_fresh = PETSC_FALSE;
-    CHKHIP(mi355x_spmv_plan_drop_value_patterns(d->plan));
+    ierr = device_values_changed(A);CHKERRQ(ierr);
+    CHKHIP(mi355x_memset(dc->h, d->mat.a, 0, sizeof(PetscScalar) * vals));
   }
   return 0;
 }
@@ -1222,11 +1124,8 @@ static PetscErrorCode MatDiagonalScale_SeqAIJHIP(Mat A, Vec ll, Vec rr) {
     ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
     if (ll) { ierr = VecHIPGetRead(ll, &dl);CHKERRQ(ierr); }
     if (rr) { ierr = VecHIPGetRead(rr, &dr);CHKERRQ(ierr); }
-    { PetscErrorCode e__ = VecHIPProductMatrixChanges(A);CHKERRQ(e__); }
-    CHKHIP(mi355x_csr_diagonal_scale(dc->h, a->m, d->d_i, d->d_j, d->d_a, dl, dr));
-    d->uploaded_state = HipObjState(A) + 1;
-    d->t_state = -1; d->tiled_fresh = PETSC_FALSE; d->b_fresh = PETSC_FALSE; d->tb_fresh = PETSC_FALSE;
-    CHKHIP(mi355x_spmv_plan_drop_value_patterns(d->plan));
+    ierr = device_values_changed(A);CHKERRQ(ierr);
+    CHKHIP(mi355x_csr_diagonal_scale(dc->h, a->m, d->mat.i, d->mat.j, d->mat.a, dl, dr));
   }
   if (ll) {
     ierr = VecGetArrayRead(ll, &l);CHKERRQ(ierr);
@@ -1294,7 +1193,7 @@ static PetscErrorCode create_common(Mat B, const char *tname, PetscInt bs) {
   memset(a, 0, sizeof(*a));
   ierr = PetscMalloc(sizeof(*d), &d);CHKERRQ(ierr);
   memset(d, 0, sizeof(*d));
-  d->uploaded_state = -1; d->t_state = -1; d->pattern_nz = -1;
+  mirror_reset(d);
   a->m = B->rmap->n; a->n = B->cmap->n; a->bs = bs;
   B->data = a; B->spptr = d;
   ierr = PetscObjectChangeTypeName((PetscObject)B, tname);CHKERRQ(ierr);

@@ -178,33 +178,37 @@ PetscErrorCode MatICCFactorSymbolic_SeqAIJHIP(Mat F, Mat A, IS perm, const MatFa
 PetscErrorCode MatGetFactor_seqaijhipmi355x_petsc(Mat A, MatFactorType ftype, Mat *B);
 PetscErrorCode MatGetFactorAvailable_seqaijhipmi355x_petsc(Mat A, MatFactorType ftype, PetscBool *flg);
 
+/* one device form of the product: (B)CSR arrays (bs = 1: CSR) with the row-block plan over their value stream, and the column-tiled layout
+ * when one was chosen for it.  The device copy of the matrix is one; the forms derived from it (the cached transpose, the blocked companion
+ * and its block transpose) hold the matrix's values in another order, a = d_a[perm], refreshed by one gather (host/aijhip.c) */
+typedef struct {
+  PetscInt *i, *j, *perm;           /* device; perm NULL: the matrix's own arrays, or values placed from the host (the BAIJ transpose) */
+  PetscScalar *a;
+  mi355x_spmv_plan_t plan;
+  PetscInt bs, nblocks;             /* block size (1: CSR), stored blocks */
+  mi355x_spmv_tiled_t tiled;        /* column-tiled layout (csrc/spmv_tiled.hip: x staged in LDS) for gathers that miss the caches; NULL: the row-block kernels */
+  PetscBool fresh;                  /* a (and the tiled layout's copy of it) hold the matrix's current device values */
+} HipDevForm;
+
 /* device mirror */
 typedef struct {
-  PetscInt *d_i, *d_j;
-  PetscScalar *d_a;
-  mi355x_spmv_plan_t plan;
+  HipDevForm mat;            /* the device copy of the matrix (compressed rows: the rows with entries only) */
   int uploaded_state;        /* Mat state at last upload (compare state instead of valid_GPU_matrix) */
   /* compressed-row form for mostly-empty blocks (src/mat/utils/compressedrow.c:28) */
   PetscBool cprow;            /* compressed-row form requested (off-diagonal block) */
   PetscBool baij4_mfma;       /* BAIJ bs = 4: MatMult on the matrix cores (mi355x_spmv_bsr4_mfma) */
   PetscInt pattern_nz;        /* nz of the pattern the mirror was built for (-1: none) */
-  /* cached explicit transpose for MatMultTranspose */
-  PetscInt *t_i, *t_j; PetscScalar *t_a; mi355x_spmv_plan_t t_plan; int t_state;
-  PetscInt *t_perm, t_pattern_nz;   /* device: position in A^T -> position in A (values follow by one gather when only values change) */
+  HipDevForm t;               /* cached explicit transpose for MatMultTranspose (perm: position in A^T -> position in A); its column-tiled
+                               * layout is built when the matrix itself took that form */
   PetscInt t_builds, t_refreshes;   /* host builds / device refreshes so far */
   PetscInt n_uploads;        /* value uploads so far */
   /* MatSetValuesBatch map for one connectivity (rows array): contributions grouped by nonzero, in call order */
   PetscInt bm_nb, bm_bs, bm_nseg; unsigned long long bm_hash; size_t bm_T, bm_vcap;
   PetscInt *bm_order, *bm_segptr, *bm_segslot;   /* device */
   PetscScalar *bm_v;                             /* device staging of the element values */
-  /* column-tiled form of the product (csrc/spmv_tiled.hip: x staged in LDS) for matrices whose gathers miss the caches; NULL: the
-   * row-block kernels.  tiled_fresh: its values are those of d_a */
-  mi355x_spmv_tiled_t tiled; PetscBool tiled_fresh;
-  mi355x_spmv_tiled_t t_tiled;        /* the column-tiled form of the cached transpose (built when the matrix itself took that form) */
-  /* the blocked companion of an AIJ matrix whose nodes are complete bs x bs blocks (3-dof FEM matrices): BCSR arrays on the device, values
-   * a permutation gather of d_a, multiplied by the BAIJ row-block kernel (host/aijhip.c, "blocked companion") */
-  PetscInt *b_i, *b_j, *b_perm, b_bs, b_nblocks; PetscScalar *b_a; mi355x_spmv_plan_t b_plan; PetscBool b_fresh;
-  PetscInt *tb_i, *tb_j, *tb_perm; PetscScalar *tb_a; mi355x_spmv_plan_t tb_plan; PetscBool tb_fresh;   /* ... and its block transpose, for the transpose products */
+  /* the blocked companion of an AIJ matrix whose nodes are complete bs x bs blocks (3-dof FEM matrices): BCSR arrays multiplied by the
+   * BAIJ row-block kernel (host/aijhip.c, "blocked companion"), and its block transpose, for the transpose products */
+  HipDevForm b, tb;
   PetscInt opt[8]; PetscBool opt_set[8];   /* the type's options as MatSetFromOptions read them under the matrix's prefix (host/aijhip.c) */
   /* per-launch device timing for bench.py (hipEvent pairs on the compute stream) */
   PetscBool timing; PetscInt time_n, time_cap; mi355x_event_t *time_ev;
