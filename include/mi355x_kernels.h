@@ -144,6 +144,15 @@ int mi355x_vec_cg_update(mi355x_handle_t h, size_t n, double a, const double *p,
 int mi355x_vec_cg_update_dev(mi355x_handle_t h, size_t n, double beta, const double *dpi_dev, double dpiold, int check_sign,
                              const double *p, const double *w, const double *d, double *x, double *r, double *z, double *out,
                              int also_to_host);
+/* The same sweep without x += a p (the AYPX that reads p next does it: mi355x_vec_aypx_dev_x): reads r, w, d, writes r, z
+ * -- 5 vector passes instead of 8.  Same a, same break-down tests, same r, z and out[0..3] bits. */
+int mi355x_vec_cg_update_dev_nox(mi355x_handle_t h, size_t n, double beta, const double *dpi_dev, double dpiold, int check_sign,
+                                 const double *w, const double *d, double *r, double *z, double *out, int also_to_host);
+/* mi355x_vec_aypx_dev that first applies the CG step the x-less update left out, with the y it is about to overwrite:
+ * a = beta / *dpi_dev with the tests of mi355x_vec_cg_update_dev; a != 0: sol = sol + a y; then y = x + (*num_dev / den) y.
+ * Bits of mi355x_vec_cg_update_dev's x followed by mi355x_vec_aypx_dev's y. */
+int mi355x_vec_aypx_dev_x(mi355x_handle_t h, size_t n, const double *num_dev, double den, const double *x, double *y,
+                          double beta, const double *dpi_dev, double dpiold, int check_sign, double *sol);
 /* Fused forms for KSPSolve_BCGS (src/ksp/ksp/impls/bcgs/bcgs.c:43-160); same bits as the calls they replace.
  * pmult_dot:      w = x .* d (PCApply_Jacobi jacobi.c:266; d == NULL: identity), out[0] = sum w*y       (bcgs.c:108-109)
  * pmult_dotnorm2: w = x .* d,                       out[0] = sum s*w, out[1] = sum w*w               (bcgs.c:116-117)

@@ -25,6 +25,11 @@ typedef struct {
   /* KSPGMRESClassicalGramSchmidtOrthogonalization without refinement (borthog2.c:60-66) and the VecNormalize that follows it
    * (gmres.c:146): dots[j] = <w, V[j]>, w -= sum_j dots[j] V[j], *nrm = |w|, w /= |w|; one host wait instead of three */
   PetscErrorCode (*gmres_orthog_normalize)(Vec w, PetscInt nv, const Vec V[], PetscScalar *dots, PetscReal *nrm, PetscBool *done);
+  /* cg_update_dev_begin without x += a p (r -= a w, z = B r and the sums only), and aypx_dev that applies that x += a p with
+   * the p it is about to overwrite (a = beta / p'w with the same device-side tests; a refused step leaves x alone): the pair
+   * computes what cg_update_dev_begin followed by aypx_dev computes, with one pass over p fewer */
+  PetscErrorCode (*cg_update_dev_begin_nox)(Vec r, Vec z, Vec w, Vec d, PetscScalar beta, PetscScalar dpiold, PetscBool check_sign);
+  PetscErrorCode (*aypx_dev_x)(Vec p, PetscScalar den, Vec z, Vec x, PetscScalar beta, PetscScalar dpiold, PetscBool check_sign);
 } VecKrylovFusedOps;
 typedef const VecKrylovFusedOps *(*VecKrylovFusedOpsGetFn)(void);
 typedef PetscErrorCode (*MatMultTDotBeginFn)(Mat A, Vec x, Vec y, PetscBool *ok);

@@ -251,35 +251,74 @@ __device__ __forceinline__ void publish_to_host(unsigned long long *host_seq, un
   }
 }
 
+// KSPSolve_CG's step length a = beta / dpi with dpi = p'w still in device memory, and the reference's break-down tests on dpi
+// (cg.c:196-199).  When one fires a = 0 and nothing may be modified; the host, which receives dpi with the sums, takes the exit.
+struct CGStepLen {
+  double beta, dpiold;
+  int check_sign;
+  const double *dpi_ptr;
+  __device__ __forceinline__ bool operator()(double &a) const {
+    const double dpi = *dpi_ptr;
+    const bool bad = !(dpi == dpi) || fabs(dpi) == __builtin_huge_val() || dpi == 0.0 || (check_sign && dpi * dpiold <= 0.0);
+    a = bad ? 0.0 : beta / dpi;
+    return !bad;
+  }
+};
+
 // y = x + (num/den) y with the scalar's numerator still in device memory (KSPSolve_CG: b = beta_new/beta_old, beta_new
 // being the z'r the previous kernel on the stream has just reduced).  VecAYPX_Seq's special case alpha == 0 -> copy
 // (dvec2.c:980) is kept; alpha == +-1 need no special form (x + 1*y and x + (-1)*y are the bits of x + y and x - y).
-template <bool NT>
-__global__ __launch_bounds__(MI355X_BLOCK) void aypx_dev_kernel(const double *num, double den, const double *x, double *y, size_t n, int vec_ok) {
+// WX: the same pass also does KSPSolve_CG's sol += a y (cg.c:206) with the y it is about to overwrite, so the update sweep
+// before it (CGUpdateDevF with x == NULL) reads neither p nor x: 12 vector passes per CG iteration instead of 13.  a is
+// formed as the update forms it (CGStepLen); for a == 0 (a refused step) sol is left alone, as VecAXPY leaves y alone
+// (bvec1.c:253).  x (= z) and sol have their last reader of the iteration here: streamed (see nt_load2).
+template <bool NT, bool WX>
+__global__ __launch_bounds__(MI355X_BLOCK) void aypx_dev_kernel(const double *num, double den, const double *x, double *y, size_t n, int vec_ok,
+                                                              CGStepLen sl, double *sol) {
   const double alpha = *num / den;
   const bool copy = (alpha == 0.0);
+  double a = 0.0;
+  if (WX) sl(a);
+  const bool ax = WX && a != 0.0;
   const size_t tid = (size_t)blockIdx.x * MI355X_BLOCK + threadIdx.x;
   if (vec_ok) {                                    // one tile of MI355X_MAP_TILE2 double2's per workgroup (see map_kernel)
     const size_t n2 = n >> 1;
     const double2 *x2 = reinterpret_cast<const double2 *>(x);
-    double2 *y2 = reinterpret_cast<double2 *>(y);
+    double2 *y2 = reinterpret_cast<double2 *>(y), *s2 = reinterpret_cast<double2 *>(sol);
     const size_t stride = MI355X_BLOCK;
     const size_t i = (size_t)blockIdx.x * MI355X_MAP_TILE2 + threadIdx.x;
     if (i + stride < n2) {
       double2 xv0 = nt_load2(x2 + i), xv1 = nt_load2(x2 + i + stride), yv0 = ld2<NT>(y2 + i), yv1 = ld2<NT>(y2 + i + stride), r0, r1;   // x = z: its last reader (see nt_load2)
+      if (ax) {
+        double2 sv0 = nt_load2(s2 + i), sv1 = nt_load2(s2 + i + stride);
+        sv0.x = sv0.x + a * yv0.x; sv0.y = sv0.y + a * yv0.y;
+        sv1.x = sv1.x + a * yv1.x; sv1.y = sv1.y + a * yv1.y;
+        nt_store2(s2 + i, sv0); nt_store2(s2 + i + stride, sv1);
+      }
       r0.x = copy ? xv0.x : xv0.x + alpha * yv0.x; r0.y = copy ? xv0.y : xv0.y + alpha * yv0.y;
       r1.x = copy ? xv1.x : xv1.x + alpha * yv1.x; r1.y = copy ? xv1.y : xv1.y + alpha * yv1.y;
       st2<NT>(y2 + i, r0);
       st2<NT>(y2 + i + stride, r1);
     } else if (i < n2) {
       double2 xv = nt_load2(x2 + i), yv = y2[i], r;
+      if (ax) {
+        double2 sv = nt_load2(s2 + i);
+        sv.x = sv.x + a * yv.x; sv.y = sv.y + a * yv.y;
+        nt_store2(s2 + i, sv);
+      }
       r.x = copy ? xv.x : xv.x + alpha * yv.x; r.y = copy ? xv.y : xv.y + alpha * yv.y;
       y2[i] = r;
     }
-    if ((n & 1) && tid == 0) y[n - 1] = copy ? x[n - 1] : x[n - 1] + alpha * y[n - 1];
+    if ((n & 1) && tid == 0) {
+      if (ax) sol[n - 1] = sol[n - 1] + a * y[n - 1];
+      y[n - 1] = copy ? x[n - 1] : x[n - 1] + alpha * y[n - 1];
+    }
   } else {
     const size_t stride = (size_t)gridDim.x * MI355X_BLOCK;
-    for (size_t i = tid; i < n; i += stride) y[i] = copy ? x[i] : x[i] + alpha * y[i];
+    for (size_t i = tid; i < n; i += stride) {
+      if (ax) sol[i] = sol[i] + a * y[i];
+      y[i] = copy ? x[i] : x[i] + alpha * y[i];
+    }
   }
 }
 
@@ -561,28 +600,23 @@ struct CGUpdateF {
 // The same sweep with the step length computed on the device: a = beta / dpi where dpi = p'w is still in device memory
 // (the VecTDot kernel, all-reduced in place over RCCL on several ranks, wrote it there), so the host does not have to
 // wait for the dot before it can launch the update -- one host synchronisation per CG iteration instead of two.
-// KSPSolve_CG's break-down tests on dpi (cg.c:196-199) are evaluated here too: when one fires nothing is modified, and
-// the host, which receives dpi in out[3], takes the reference's exit with x, r, z untouched.  out[3] carries dpi
-// through the reduction tree unchanged (lane 0 of workgroup 0 contributes it, every other lane +0.0).
+// KSPSolve_CG's break-down tests on dpi (cg.c:196-199) are evaluated here too (CGStepLen): when one fires nothing is
+// modified, and the host, which receives dpi in out[3], takes the reference's exit with x, r, z untouched.  out[3] carries
+// dpi through the reduction tree unchanged (lane 0 of workgroup 0 contributes it, every other lane +0.0).
+// x == NULL: x += a p is left to the AYPX that follows (aypx_dev_kernel<NT, true>), and neither p nor x is read here:
+// 5 vector passes instead of 8; same lanes, same order, same sums.
 struct CGUpdateDevF {
-  double beta, dpiold;
-  int check_sign;
-  const double *dpi_ptr;
+  CGStepLen sl;
   const double *p, *w, *d;
   double *x, *r, *z;
   int big = 0;                 // see CGUpdateF
-  __device__ __forceinline__ bool scalars(double &a) const {
-    const double dpi = *dpi_ptr;
-    const bool bad = !(dpi == dpi) || fabs(dpi) == __builtin_huge_val() || dpi == 0.0 || (check_sign && dpi * dpiold <= 0.0);
-    a = bad ? 0.0 : beta / dpi;
-    return !bad;
-  }
   __device__ __forceinline__ void prologue(size_t tid, double (&acc)[4]) const {
-    if (tid == 0) acc[3] = *dpi_ptr;
+    if (tid == 0) acc[3] = *sl.dpi_ptr;
   }
+  template <bool WX>
   __device__ __forceinline__ void step(double a, double pv, double wv, double dv, double &xv, double &rv, double &zv, double (&acc)[4]) const {
     if (a != 0.0) {            // VecAXPY leaves y alone for alpha == 0 (bvec1.c:253)
-      xv = xv + a * pv;
+      if (WX) xv = xv + a * pv;
       rv = rv + (-a) * wv;
     }
     zv = rv * dv;
@@ -593,32 +627,47 @@ struct CGUpdateDevF {
   template <int NOUT_>
   __device__ __forceinline__ void sweep(size_t tid, size_t stride, size_t n2, double (&acc)[NOUT_]) const {
     double a;
-    if (!scalars(a)) return;
+    if (!sl(a)) return;
+    if (x) sweep_as<true>(a, tid, stride, n2, acc);
+    else sweep_as<false>(a, tid, stride, n2, acc);
+  }
+  template <bool WX>
+  __device__ __forceinline__ void sweep_as(double a, size_t tid, size_t stride, size_t n2, double (&acc)[4]) const {
     const double2 *p2 = reinterpret_cast<const double2 *>(p), *w2 = reinterpret_cast<const double2 *>(w);
     const double2 *d2 = reinterpret_cast<const double2 *>(d);
-    const double2 one2 = {1.0, 1.0};
+    const double2 one2 = {1.0, 1.0}, zero2 = {0.0, 0.0};
     double2 *x2 = reinterpret_cast<double2 *>(x), *r2 = reinterpret_cast<double2 *>(r), *z2 = reinterpret_cast<double2 *>(z);
     size_t i = tid;
     for (; i + stride < n2; i += 2 * stride) {
-      double2 pv0 = ldq(p2 + i, big), pv1 = ldq(p2 + i + stride, big), wv0 = ldq(w2 + i, big), wv1 = ldq(w2 + i + stride, big), dv0 = d ? nt_load2(d2 + i) : one2, dv1 = d ? nt_load2(d2 + i + stride) : one2;
-      double2 xv0 = nt_load2(x2 + i), xv1 = nt_load2(x2 + i + stride), rv0 = nt_load2(r2 + i), rv1 = nt_load2(r2 + i + stride), zv0, zv1;
-      step(a, pv0.x, wv0.x, dv0.x, xv0.x, rv0.x, zv0.x, acc); step(a, pv0.y, wv0.y, dv0.y, xv0.y, rv0.y, zv0.y, acc);
-      step(a, pv1.x, wv1.x, dv1.x, xv1.x, rv1.x, zv1.x, acc); step(a, pv1.y, wv1.y, dv1.y, xv1.y, rv1.y, zv1.y, acc);
-      nt_store2(x2 + i, xv0); nt_store2(r2 + i, rv0); stq(z2 + i, zv0, big);
-      nt_store2(x2 + i + stride, xv1); nt_store2(r2 + i + stride, rv1); stq(z2 + i + stride, zv1, big);
+      double2 pv0 = WX ? ldq(p2 + i, big) : zero2, pv1 = WX ? ldq(p2 + i + stride, big) : zero2, wv0 = ldq(w2 + i, big), wv1 = ldq(w2 + i + stride, big), dv0 = d ? nt_load2(d2 + i) : one2, dv1 = d ? nt_load2(d2 + i + stride) : one2;
+      double2 xv0 = WX ? nt_load2(x2 + i) : zero2, xv1 = WX ? nt_load2(x2 + i + stride) : zero2, rv0 = nt_load2(r2 + i), rv1 = nt_load2(r2 + i + stride), zv0, zv1;
+      step<WX>(a, pv0.x, wv0.x, dv0.x, xv0.x, rv0.x, zv0.x, acc); step<WX>(a, pv0.y, wv0.y, dv0.y, xv0.y, rv0.y, zv0.y, acc);
+      step<WX>(a, pv1.x, wv1.x, dv1.x, xv1.x, rv1.x, zv1.x, acc); step<WX>(a, pv1.y, wv1.y, dv1.y, xv1.y, rv1.y, zv1.y, acc);
+      if (WX) nt_store2(x2 + i, xv0);
+      nt_store2(r2 + i, rv0); stq(z2 + i, zv0, big);
+      if (WX) nt_store2(x2 + i + stride, xv1);
+      nt_store2(r2 + i + stride, rv1); stq(z2 + i + stride, zv1, big);
     }
     for (; i < n2; i += stride) {
-      double2 pv = p2[i], wv = w2[i], dv = d ? nt_load2(d2 + i) : one2, xv = nt_load2(x2 + i), rv = nt_load2(r2 + i), zv;
-      step(a, pv.x, wv.x, dv.x, xv.x, rv.x, zv.x, acc); step(a, pv.y, wv.y, dv.y, xv.y, rv.y, zv.y, acc);
-      nt_store2(x2 + i, xv); nt_store2(r2 + i, rv); z2[i] = zv;
+      double2 pv = WX ? p2[i] : zero2, wv = w2[i], dv = d ? nt_load2(d2 + i) : one2, xv = WX ? nt_load2(x2 + i) : zero2, rv = nt_load2(r2 + i), zv;
+      step<WX>(a, pv.x, wv.x, dv.x, xv.x, rv.x, zv.x, acc); step<WX>(a, pv.y, wv.y, dv.y, xv.y, rv.y, zv.y, acc);
+      if (WX) nt_store2(x2 + i, xv);
+      nt_store2(r2 + i, rv); z2[i] = zv;
     }
   }
   __device__ void accum1(size_t i, double (&acc)[4]) const {
     double a;
-    if (!scalars(a)) return;
-    double xv = x[i], rv = r[i], zv;
-    step(a, p[i], w[i], d ? d[i] : 1.0, xv, rv, zv, acc);
-    x[i] = xv; r[i] = rv; z[i] = zv;
+    if (!sl(a)) return;
+    double rv = r[i], zv;
+    if (x) {
+      double xv = x[i];
+      step<true>(a, p[i], w[i], d ? d[i] : 1.0, xv, rv, zv, acc);
+      x[i] = xv;
+    } else {
+      double xv = 0.0;
+      step<false>(a, 0.0, w[i], d ? d[i] : 1.0, xv, rv, zv, acc);
+    }
+    r[i] = rv; z[i] = zv;
   }
 };
 template <> struct has_prologue<CGUpdateDevF> { static constexpr bool value = true; };
@@ -869,8 +918,19 @@ int mi355x_vec_aypx(mi355x_handle_t h, size_t n, double alpha, const double *x, 
 int mi355x_vec_aypx_dev(mi355x_handle_t h, size_t n, const double *num_dev, double den, const double *x, double *y) {
   if (n == 0) return 0;
   int vec_ok = mi355x_aligned16(x) && mi355x_aligned16(y);
-  if (vec_streams(n)) hipLaunchKernelGGL(aypx_dev_kernel<true>, dim3(map_grid(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, num_dev, den, x, y, n, vec_ok);
-  else hipLaunchKernelGGL(aypx_dev_kernel<false>, dim3(map_grid(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, num_dev, den, x, y, n, vec_ok);
+  const CGStepLen none{0.0, 0.0, 0, nullptr};
+  if (vec_streams(n)) hipLaunchKernelGGL((aypx_dev_kernel<true, false>), dim3(map_grid(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, num_dev, den, x, y, n, vec_ok, none, (double *)nullptr);
+  else hipLaunchKernelGGL((aypx_dev_kernel<false, false>), dim3(map_grid(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, num_dev, den, x, y, n, vec_ok, none, (double *)nullptr);
+  MI355X_LAUNCH_CHECK();
+  return 0;
+}
+int mi355x_vec_aypx_dev_x(mi355x_handle_t h, size_t n, const double *num_dev, double den, const double *x, double *y,
+                          double beta, const double *dpi_dev, double dpiold, int check_sign, double *sol) {
+  if (n == 0) return 0;
+  int vec_ok = mi355x_aligned16(x) && mi355x_aligned16(y) && mi355x_aligned16(sol);
+  const CGStepLen sl{beta, dpiold, check_sign, dpi_dev};
+  if (vec_streams(n)) hipLaunchKernelGGL((aypx_dev_kernel<true, true>), dim3(map_grid(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, num_dev, den, x, y, n, vec_ok, sl, sol);
+  else hipLaunchKernelGGL((aypx_dev_kernel<false, true>), dim3(map_grid(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, num_dev, den, x, y, n, vec_ok, sl, sol);
   MI355X_LAUNCH_CHECK();
   return 0;
 }
@@ -987,11 +1047,15 @@ int mi355x_vec_cg_update(mi355x_handle_t h, size_t n, double a, const double *p,
 int mi355x_vec_cg_update_dev(mi355x_handle_t h, size_t n, double beta, const double *dpi_dev, double dpiold, int check_sign,
                              const double *p, const double *w, const double *d, double *x, double *r, double *z, double *out,
                              int also_to_host) {
-  CGUpdateDevF f{beta, dpiold, check_sign, dpi_dev, p, w, d, x, r, z};
+  CGUpdateDevF f{{beta, dpiold, check_sign, dpi_dev}, p, w, d, x, r, z};
   f.big = vec_streams(n);
   int v = mi355x_aligned16(p) && mi355x_aligned16(w) && mi355x_aligned16(d) && mi355x_aligned16(x) && mi355x_aligned16(r) &&
-          mi355x_aligned16(z);   /* d == NULL (identity preconditioner) counts as aligned */
+          mi355x_aligned16(z);   /* d == NULL (identity preconditioner) and p, x == NULL (the x-less form) count as aligned */
   return launch_reduce<4, RED_SUM>(h, f, n, v, out, also_to_host != 0);
+}
+int mi355x_vec_cg_update_dev_nox(mi355x_handle_t h, size_t n, double beta, const double *dpi_dev, double dpiold, int check_sign,
+                                 const double *w, const double *d, double *r, double *z, double *out, int also_to_host) {
+  return mi355x_vec_cg_update_dev(h, n, beta, dpi_dev, dpiold, check_sign, nullptr, w, d, nullptr, r, z, out, also_to_host);
 }
 int mi355x_vec_pmult_dot(mi355x_handle_t h, size_t n, const double *x, const double *d, const double *y, double *w, double *out) {
   PMultDotF f{x, d, y, w};

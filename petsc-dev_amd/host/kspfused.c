@@ -92,11 +92,21 @@ static PetscErrorCode report(KSP ksp, PetscInt it, PetscReal rn) {   /* what eve
  *     w = A p and p'w of iteration i+1.  If the convergence test ends the solve only work vectors have been touched.  Not done
  *     for the last permitted iteration nor within 10x of the target;
  *  4  as 3 with p'w produced by the SpMV pass itself (another summation tree: agrees with the other levels to rounding, not bit for
- *     bit; deterministic).  Sequential AIJ matrices whose product kernel leaves per-block sums ("MatMultTDotBegin_C"); level 3 otherwise. */
-typedef struct { PetscInt level; Vec dinv; } KSP_CGHIP;
+ *     bit; deterministic).  Sequential AIJ matrices whose product kernel leaves per-block sums ("MatMultTDotBegin_C"); level 3 otherwise.
+ * -ksp_cg_x_with_p <bool> (default true), levels 3 and 4: when the front half of iteration i+1 is queued, x += a p of iteration i
+ * moves from the update sweep into the AYPX that reads p anyway (the same a, the same x + a*p): 12 vector passes per iteration
+ * instead of 13, same bits.  Iterations that queue nothing keep x in the update sweep. */
+typedef struct { PetscInt level; PetscBool x_with_p; Vec dinv; } KSP_CGHIP;
 
 static PetscErrorCode KSPSetUp_CGHIP(KSP ksp) { return KSPDefaultGetWork(ksp, 3); }
-static PetscErrorCode KSPSetFromOptions_CGHIP(KSP ksp) { return option_level(ksp, "-ksp_cg_fused", 0, 4, &((KSP_CGHIP *)ksp->data)->level); }
+static PetscErrorCode KSPSetFromOptions_CGHIP(KSP ksp) {
+  KSP_CGHIP *cg = (KSP_CGHIP *)ksp->data;
+  PetscInt iv = cg->x_with_p;
+  PetscErrorCode ierr = option_level(ksp, "-ksp_cg_fused", 0, 4, &cg->level);CHKERRQ(ierr);
+  ierr = option_level(ksp, "-ksp_cg_x_with_p", 0, 1, &iv);CHKERRQ(ierr);
+  cg->x_with_p = (PetscBool)iv;
+  return 0;
+}
 static PetscErrorCode KSPDestroy_CGHIP(KSP ksp) {
   KSP_CGHIP *cg = (KSP_CGHIP *)ksp->data;
   if (cg) { PetscErrorCode ierr = VecDestroy(&cg->dinv);CHKERRQ(ierr); HipFree(cg); ksp->data = NULL; }
@@ -174,10 +184,14 @@ static PetscErrorCode KSPSolve_CGHIP(KSP ksp) {
     }
     rz_prev = rz;
     if (pw_on_device) {
-      ierr = F->cg_update_dev_begin(x, r, z, p, w, d, rz, pw_prev, (PetscBool)(it > 0));CHKERRQ(ierr);
-      if (level > 2 && it + 1 < ksp->max_it && (nt == KSP_NORM_NONE || rn > 10.0 * ksp->ttol)) {
+      const PetscBool queue = (PetscBool)(level > 2 && it + 1 < ksp->max_it && (nt == KSP_NORM_NONE || rn > 10.0 * ksp->ttol));
+      const PetscBool x_in_aypx = (PetscBool)(queue && cg->x_with_p && F->cg_update_dev_begin_nox && F->aypx_dev_x);
+      if (x_in_aypx) { ierr = F->cg_update_dev_begin_nox(r, z, w, d, rz, pw_prev, (PetscBool)(it > 0));CHKERRQ(ierr); }
+      else { ierr = F->cg_update_dev_begin(x, r, z, p, w, d, rz, pw_prev, (PetscBool)(it > 0));CHKERRQ(ierr); }
+      if (queue) {
         PetscBool ok = PETSC_FALSE;                                        /* front half of iteration it+1 */
-        ierr = F->aypx_dev(p, rz, z);CHKERRQ(ierr);
+        if (x_in_aypx) { ierr = F->aypx_dev_x(p, rz, z, x, rz, pw_prev, (PetscBool)(it > 0));CHKERRQ(ierr); }   /* x += a p, then p <- z + b p */
+        else { ierr = F->aypx_dev(p, rz, z);CHKERRQ(ierr); }
         if (level > 3) { ierr = mat_mult_with_dot(A, p, w, &ok);CHKERRQ(ierr); }
         if (!ok) {
           ierr = KSP_MatMult(ksp, A, p, w);CHKERRQ(ierr);
@@ -229,7 +243,7 @@ static PetscErrorCode KSPSolve_CGHIP(KSP ksp) {
 PetscErrorCode KSPCreate_CGHIPMI355X(KSP ksp) {
   KSP_CGHIP *cg;
   PetscErrorCode ierr = PetscMalloc(sizeof(*cg), &cg);CHKERRQ(ierr);
-  cg->level = 4; cg->dinv = NULL;
+  cg->level = 4; cg->x_with_p = PETSC_TRUE; cg->dinv = NULL;
   ksp->data = cg;
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);    /* the four of KSPCG, cg.c:439-442 */
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_LEFT, 1);CHKERRQ(ierr);

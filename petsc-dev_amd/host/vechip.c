@@ -799,30 +799,39 @@ PetscErrorCode VecTDotBegin_HIPMI355X(Vec x, Vec y, PetscBool *ok) {
 /* Begin queues the sweep (results go to device scratch slots 0..2, all-reduced there when the communicator has an
  * RCCL communicator, then published to pinned memory); End waits for exactly that point of the stream, so the caller
  * may queue more work in between (KSPSolve_CG queues the next iteration's AYPX, MatMult and dot there). */
-PetscErrorCode VecCGUpdateDevBegin_HIPMI355X(Vec x, Vec r, Vec z, Vec p, Vec w, Vec d, PetscScalar beta, PetscScalar dpiold, PetscBool check_sign) {
-  PetscErrorCode ierr; const PetscScalar *dp_, *dw, *dd; PetscScalar *dx, *dr, *dz; double *ds; DEVCTX;
-  ierr = VecHIPGetRead(p, &dp_);CHKERRQ(ierr);
+/* x == NULL (and p unused): the x-less sweep of VecCGUpdateDevBeginNoX_HIPMI355X */
+static PetscErrorCode cg_update_dev_begin(Vec x, Vec r, Vec z, Vec p, Vec w, Vec d, PetscScalar beta, PetscScalar dpiold, PetscBool check_sign) {
+  PetscErrorCode ierr; const PetscScalar *dp_ = NULL, *dw, *dd; PetscScalar *dx = NULL, *dr, *dz; double *ds; DEVCTX;
+  if (x) { ierr = VecHIPGetRead(p, &dp_);CHKERRQ(ierr); }
   ierr = VecHIPGetRead(w, &dw);CHKERRQ(ierr);
   dd = NULL;
   if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
-  ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr);
+  if (x) { ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr); }
   ierr = VecHIPGetReadWrite(r, &dr);CHKERRQ(ierr);
   if (z == w) { ierr = VecHIPGetReadWrite(z, &dz);CHKERRQ(ierr); }   /* left as it is when the update is refused */
   else { ierr = VecHIPGetWrite(z, &dz);CHKERRQ(ierr); }
   ds = mi355x_handle_device_scratch(dc->h);
   /* one rank: the finishing workgroup hands the sums to the host itself; several: all-reduce first, then publish */
   CGU_TIME_BEGIN(dc->h);
-  CHKHIP(mi355x_vec_cg_update_dev(dc->h, N_(x), beta, ds + DPI_SLOT, dpiold, (int)check_sign, dp_, dw, dd, dx, dr, dz, ds,
-                                  DEVICE_COLLECTIVES(x) ? 0 : 1));
+  CHKHIP(mi355x_vec_cg_update_dev(dc->h, N_(r), beta, ds + DPI_SLOT, dpiold, (int)check_sign, dp_, dw, dd, dx, dr, dz, ds,
+                                  DEVICE_COLLECTIVES(r) ? 0 : 1));
   CGU_TIME_END(dc->h);
-  VecHIPRestoreWrite(x); VecHIPRestoreWrite(r); VecHIPRestoreWrite(z);
-  HipStateIncrease(x); HipStateIncrease(r); HipStateIncrease(z);
-  if (DEVICE_COLLECTIVES(x)) {
-    CHKHIP(mi355x_comm_allreduce_sum(HipCommDevice(HipObjComm(x)), dc->h, ds, 3));
+  if (x) { VecHIPRestoreWrite(x); HipStateIncrease(x); }
+  VecHIPRestoreWrite(r); VecHIPRestoreWrite(z);
+  HipStateIncrease(r); HipStateIncrease(z);
+  if (DEVICE_COLLECTIVES(r)) {
+    CHKHIP(mi355x_comm_allreduce_sum(HipCommDevice(HipObjComm(r)), dc->h, ds, 3));
     CHKHIP(mi355x_handle_publish(dc->h, ds, 4));
   }
-  ierr = PetscLogFlops(9.0 * x->map->n);CHKERRQ(ierr);
+  ierr = PetscLogFlops((x ? 9.0 : 7.0) * r->map->n);CHKERRQ(ierr);
   return 0;
+}
+PetscErrorCode VecCGUpdateDevBegin_HIPMI355X(Vec x, Vec r, Vec z, Vec p, Vec w, Vec d, PetscScalar beta, PetscScalar dpiold, PetscBool check_sign) {
+  return cg_update_dev_begin(x, r, z, p, w, d, beta, dpiold, check_sign);
+}
+/* the same without x += a p: VecAYPXDevX_HIPMI355X, queued right after, applies it with the p it overwrites */
+PetscErrorCode VecCGUpdateDevBeginNoX_HIPMI355X(Vec r, Vec z, Vec w, Vec d, PetscScalar beta, PetscScalar dpiold, PetscBool check_sign) {
+  return cg_update_dev_begin(NULL, r, z, NULL, w, d, beta, dpiold, check_sign);
 }
 PetscErrorCode VecCGUpdateDevEnd_HIPMI355X(Vec x, PetscScalar *zz, PetscScalar *zr, PetscScalar *rr, PetscScalar *dpi) {
   PetscErrorCode ierr; DEVCTX;
@@ -842,6 +851,20 @@ PetscErrorCode VecAYPXDev_HIPMI355X(Vec p, PetscScalar den, Vec z) {
   VecHIPRestoreWrite(p);
   HipStateIncrease(p);
   ierr = PetscLogFlops(2.0 * p->map->n);CHKERRQ(ierr);
+  return 0;
+}
+/* x += a p (a = beta / p'w formed and tested as VecCGUpdateDevBegin does, p'w still in slot DPI_SLOT; a refused step leaves x
+ * alone), then p = z + (zr/den) p as VecAYPXDev: the second half of VecCGUpdateDevBeginNoX's iteration in the AYPX pass */
+PetscErrorCode VecAYPXDevX_HIPMI355X(Vec p, PetscScalar den, Vec z, Vec x, PetscScalar beta, PetscScalar dpiold, PetscBool check_sign) {
+  PetscErrorCode ierr; const PetscScalar *dz; PetscScalar *dp_, *dx; double *ds; DEVCTX;
+  ierr = VecHIPGetRead(z, &dz);CHKERRQ(ierr);
+  ierr = VecHIPGetReadWrite(p, &dp_);CHKERRQ(ierr);
+  ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr);
+  ds = mi355x_handle_device_scratch(dc->h);
+  CHKHIP(mi355x_vec_aypx_dev_x(dc->h, N_(p), ds + 1, den, dz, dp_, beta, ds + DPI_SLOT, dpiold, (int)check_sign, dx));
+  VecHIPRestoreWrite(p); VecHIPRestoreWrite(x);
+  HipStateIncrease(p); HipStateIncrease(x);
+  ierr = PetscLogFlops(4.0 * p->map->n);CHKERRQ(ierr);
   return 0;
 }
 /* can the six vectors of a CG iteration take the fused update at all (types, sizes, aliasing)? */
@@ -1131,7 +1154,8 @@ PetscErrorCode VecGMRESOrthogNormalize_HIPMI355X(Vec w, PetscInt nv, const Vec V
 static const VecKrylovFusedOps *VecKrylovFusedOps_HIP(void) {
   static const VecKrylovFusedOps ops = {
     VecCGUpdate_HIPMI355X, VecCGUpdateCheck_HIPMI355X, VecTDotBegin_HIPMI355X, VecCGUpdateDevBegin_HIPMI355X, VecCGUpdateDevEnd_HIPMI355X,
-    VecAYPXDev_HIPMI355X, VecPMultDot_HIPMI355X, VecPMultDotNorm2_HIPMI355X, VecBCGSUpdate_HIPMI355X, VecGMRESOrthogNormalize_HIPMI355X};
+    VecAYPXDev_HIPMI355X, VecPMultDot_HIPMI355X, VecPMultDotNorm2_HIPMI355X, VecBCGSUpdate_HIPMI355X, VecGMRESOrthogNormalize_HIPMI355X,
+    VecCGUpdateDevBeginNoX_HIPMI355X, VecAYPXDevX_HIPMI355X};
   return &ops;
 }
 /* "VecSplitReductionOps_C": VecDotBegin/End, VecNormBegin/End, PetscCommSplitReductionBegin (comb.c:402-721) with the
