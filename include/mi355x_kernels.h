@@ -39,8 +39,12 @@ int  mi355x_device_synchronize(void);
 int  mi355x_mem_info(size_t *free_bytes, size_t *total_bytes);   /* hipMemGetInfo of the current device */
 /* host threads THIS process may use for the set-up passes (pattern analyses, factorisation, plan construction), at most cap:
  * the CPUs of its affinity mask, cut to the cgroup's CPU quota, shared among the ranks torchrun started on this node
- * (LOCAL_WORLD_SIZE); MI355X_HOST_THREADS=<n> in the environment overrides.  Never less than 1. */
+ * (LOCAL_WORLD_SIZE).  MI355X_HOST_THREADS=<n> in the environment overrides the count, cap included, up to 64.  Never less than 1. */
 int  mi355x_host_threads(int cap);
+/* fn(ctx, lo, hi) over [0, n) in nth contiguous chunks (lo = n k / nth, hi = n (k + 1) / nth, k = 0 .. nth - 1), chunk 0 on the
+ * calling thread, the others on host threads of their own (on the caller, after the others, where a thread cannot be started).
+ * Returns after every chunk has run: 0, or the first nonzero status a chunk returned. */
+int  mi355x_host_parallel_ranges(long n, int nth, int (*fn)(void *ctx, long lo, long hi), void *ctx);
 
 int  mi355x_handle_create(mi355x_handle_t *h);
 int  mi355x_handle_destroy(mi355x_handle_t h);

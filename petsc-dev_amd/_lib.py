@@ -11,6 +11,7 @@ dbl = C.c_double
 i32 = C.c_int
 pi32 = C.POINTER(C.c_int)
 pdbl = C.POINTER(C.c_double)
+HOST_RANGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_long, C.c_long)   # mi355x_host_parallel_ranges' chunk
 
 # name -> argtypes (every function returns int unless listed in _RESTYPES)
 KERNEL_API = {
@@ -115,6 +116,7 @@ KERNEL_API = {
     "mi355x_spmv_tiled_drop_host": [vp],
     "mi355x_spmv_tiled_destroy": [vp],
     "mi355x_host_threads": [i32],
+    "mi355x_host_parallel_ranges": [C.c_long, i32, HOST_RANGE_FN, vp],
     "mi355x_csr_get_diagonal": [vp, i32, vp, vp, vp, vp],
     "mi355x_csr_diagonal_scale": [vp, i32, vp, vp, vp, vp, vp],
     "mi355x_csr_assemble": [vp, i32, vp, vp, vp, vp, vp],

@@ -37,13 +37,15 @@ int mi355x_comm_get_unique_id(char id[MI355X_UNIQUE_ID_BYTES]) {
 int mi355x_comm_init_rank(mi355x_comm_t *out, int nranks, int rank, const char id[MI355X_UNIQUE_ID_BYTES]) {
   ncclUniqueId uid;
   memcpy(&uid, id, sizeof(uid));
-  mi355x_comm_s *c = new mi355x_comm_s();
-  c->rank = rank;
-  c->nranks = nranks;
-  ncclResult_t r = ncclCommInitRank(&c->comm, nranks, uid, rank);
-  if (r != ncclSuccess) { delete c; *out = nullptr; return 100000 + (int)r; }
-  *out = c;
-  return 0;
+  *out = nullptr;
+  return mi355x_guard([&] {
+    std::unique_ptr<mi355x_comm_s> c(new mi355x_comm_s());
+    c->rank = rank;
+    c->nranks = nranks;
+    NCCL_TRY(ncclCommInitRank(&c->comm, nranks, uid, rank));
+    *out = c.release();
+    return 0;
+  });
 }
 
 int mi355x_comm_destroy(mi355x_comm_t c) {

@@ -3,6 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <atomic>
+#include <exception>
+#include <memory>
+#include <new>
+#include <thread>
 #include "mi355x_kernels.h"
 
 #define MI355X_WAVE 64            // CDNA wavefront width
@@ -51,6 +56,39 @@ static inline int mi355x_grid_for(size_t n, int per_thread) {
 }
 
 static inline bool mi355x_aligned16(const void *p) { return (((uintptr_t)p) & 15u) == 0; }
+
+// ---- host side of the set-up passes ------------------------------------
+// The C ABI's one exception boundary: an entry that allocates with new / std containers or starts threads runs its body
+// through this, so that what the body throws comes back as an error code (the body's owners free what it had allocated).
+template <class F> static int mi355x_guard(F f) {
+  try { return f(); }
+  catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+  catch (...) { return (int)hipErrorUnknown; }
+}
+
+// f(k) for k = 0 .. nth - 1 on nth host threads, chunk 0 on the calling thread.  A chunk whose thread cannot be started
+// runs on the caller after the others.  An exception of a chunk is caught on its thread (and sets *failed, if given: an
+// early stop for the other chunks); every thread is joined, then the first exception caught is rethrown on the caller.
+template <class F> static void mi355x_parallel_chunks(int nth, F f, std::atomic<int> *failed = nullptr) {
+  if (nth <= 1) { f(0); return; }
+  std::exception_ptr first;
+  std::atomic<int> caught(0);
+  auto run = [&](int k) {
+    try { f(k); }
+    catch (...) { if (!caught.exchange(1)) first = std::current_exception(); if (failed) failed->store(1); }
+  };
+  std::unique_ptr<std::thread[]> th(new (std::nothrow) std::thread[nth]);
+  for (int k = 1; k < nth && th; ++k) try { th[k] = std::thread(run, k); } catch (...) {}
+  run(0);
+  for (int k = 1; k < nth; ++k) { if (th && th[k].joinable()) th[k].join(); else run(k); }
+  if (first) std::rethrow_exception(first);
+}
+
+// the same over [0, n): chunk k is f(lo, hi) with lo = n k / nth, hi = n (k + 1) / nth
+template <class F> static void mi355x_parallel_ranges(long n, int nth, F f) {
+  if (nth < 1) nth = 1;
+  mi355x_parallel_chunks(nth, [&](int k) { f(n * k / nth, n * (k + 1) / nth); });
+}
 
 // ---- device helpers ----------------------------------------------------
 __device__ __forceinline__ double wave_sum(double v) {

@@ -47,23 +47,33 @@ int mi355x_host_threads(int cap) {
   return n < 1 ? 1 : (int)n;
 }
 
+int mi355x_host_parallel_ranges(long n, int nth, int (*fn)(void *ctx, long lo, long hi), void *ctx) {
+  std::atomic<int> rc(0);       // the first nonzero status
+  return mi355x_guard([&] {
+    mi355x_parallel_ranges(n, nth, [&](long lo, long hi) { int none = 0; if (const int r = fn(ctx, lo, hi)) rc.compare_exchange_strong(none, r); });
+    return rc.load();
+  });
+}
+
 int mi355x_handle_create(mi355x_handle_t *out) {
-  mi355x_handle_s *h = new mi355x_handle_s();
-  memset(h, 0, sizeof(*h));
-  MI355X_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  MI355X_TRY(hipMalloc((void **)&h->partials, sizeof(double) * MI355X_REDUCE_GRID_CAP_BIG * MI355X_MAX_RED));
-  MI355X_TRY(hipMalloc((void **)&h->ticket, 256));
-  MI355X_TRY(hipMemset(h->ticket, 0, 256));
-  // +1 slot: the completion sequence word that lets the host poll instead of synchronising the stream
-  MI355X_TRY(hipHostMalloc((void **)&h->host_scratch, sizeof(double) * (MI355X_SCRATCH_DOUBLES + 8), hipHostMallocMapped | hipHostMallocCoherent));
-  MI355X_TRY(hipMalloc((void **)&h->dev_scratch, sizeof(double) * MI355X_SCRATCH_DOUBLES));
-  MI355X_TRY(hipMemset(h->dev_scratch, 0, sizeof(double) * MI355X_SCRATCH_DOUBLES));
-  memset(h->host_scratch, 0, sizeof(double) * (MI355X_SCRATCH_DOUBLES + 8));
-  h->host_seq = reinterpret_cast<volatile unsigned long long *>(h->host_scratch + MI355X_SCRATCH_DOUBLES);
-  h->seq = 0;
-  MI355X_TRY(hipDeviceSynchronize());
-  *out = h;
-  return 0;
+  *out = nullptr;
+  return mi355x_guard([&] {
+    // (zeroed) one cleanup path: a failure frees what was allocated so far
+    std::unique_ptr<mi355x_handle_s, decltype(&mi355x_handle_destroy)> h(new mi355x_handle_s(), mi355x_handle_destroy);
+    MI355X_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    MI355X_TRY(hipMalloc((void **)&h->partials, sizeof(double) * MI355X_REDUCE_GRID_CAP_BIG * MI355X_MAX_RED));
+    MI355X_TRY(hipMalloc((void **)&h->ticket, 256));
+    MI355X_TRY(hipMemset(h->ticket, 0, 256));
+    // +1 slot: the completion sequence word that lets the host poll instead of synchronising the stream
+    MI355X_TRY(hipHostMalloc((void **)&h->host_scratch, sizeof(double) * (MI355X_SCRATCH_DOUBLES + 8), hipHostMallocMapped | hipHostMallocCoherent));
+    MI355X_TRY(hipMalloc((void **)&h->dev_scratch, sizeof(double) * MI355X_SCRATCH_DOUBLES));
+    MI355X_TRY(hipMemset(h->dev_scratch, 0, sizeof(double) * MI355X_SCRATCH_DOUBLES));
+    memset(h->host_scratch, 0, sizeof(double) * (MI355X_SCRATCH_DOUBLES + 8));
+    h->host_seq = reinterpret_cast<volatile unsigned long long *>(h->host_scratch + MI355X_SCRATCH_DOUBLES);
+    MI355X_TRY(hipDeviceSynchronize());
+    *out = h.release();
+    return 0;
+  });
 }
 int mi355x_handle_destroy(mi355x_handle_t h) {
   if (!h) return 0;
@@ -128,10 +138,13 @@ int mi355x_memset(mi355x_handle_t h, void *dst, int byte, size_t bytes) {
 }
 
 int mi355x_event_create(mi355x_event_t *e) {
-  mi355x_event_s *ev = new mi355x_event_s();
-  MI355X_TRY(hipEventCreate(&ev->ev));
-  *e = ev;
-  return 0;
+  *e = nullptr;
+  return mi355x_guard([&] {
+    std::unique_ptr<mi355x_event_s> ev(new mi355x_event_s());
+    MI355X_TRY(hipEventCreate(&ev->ev));
+    *e = ev.release();
+    return 0;
+  });
 }
 int mi355x_event_destroy(mi355x_event_t e) {
   if (!e) return 0;

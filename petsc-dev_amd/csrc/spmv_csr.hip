@@ -23,8 +23,6 @@
 #include <array>
 #include <memory>
 #include <vector>
-#include <thread>
-#include <functional>
 #include <stdlib.h>
 #include <string.h>
 
@@ -1000,25 +998,11 @@ static int launch_spmv(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai, c
 
 extern "C" {
 
-int mi355x_spmv_plan_create(mi355x_handle_t h, int nrows, const int *ai_host, const int *rows_host,
-                            mi355x_spmv_plan_t *plan) {
-  mi355x_spmv_plan_s *p = new mi355x_spmv_plan_s();
+static int spmv_plan_create(mi355x_handle_t h, int nrows, const int *ai_host, const int *rows_host, mi355x_spmv_plan_t *plan) {
+  // one cleanup path: a failure frees what was allocated so far
+  std::unique_ptr<mi355x_spmv_plan_s, decltype(&mi355x_spmv_plan_destroy)> p(new mi355x_spmv_plan_s(), mi355x_spmv_plan_destroy);   // (zeroed)
   p->nrows = nrows;
-  p->d_rowblk = nullptr;
-  p->d_rows = nullptr;
-  p->d_idx8 = nullptr;
-  p->d_offtab = nullptr;
-  p->ntab = 0;
-  p->d_prow = nullptr; p->d_pattab = nullptr; p->npat = 0; p->use_pat = 1; p->ch = SPMV_CH;
-  p->d_vrow = nullptr; p->d_vpattab = nullptr; p->d_vpatval = nullptr; p->nvpat = 0; p->vtablen = 0; p->vpat_valid = 0; p->use_vpat = 1;
-  p->nlong = 0;
-  p->d_dotpart = nullptr;
-  p->pairsum = 0;
-  p->d_rowblk4 = nullptr;
-  p->d_goff = nullptr;
-  p->d_gj = nullptr;
-  p->ngroups = 0;
-  p->ngj = 0;
+  p->use_pat = 1; p->ch = SPMV_CH; p->use_vpat = 1;
   std::vector<int2> rb;
   rb.reserve((size_t)nrows / 128 + 2);
   rb.push_back(make_int2(0, ai_host[0]));
@@ -1047,8 +1031,12 @@ int mi355x_spmv_plan_create(mi355x_handle_t h, int nrows, const int *ai_host, co
     MI355X_TRY(hipMemcpyAsync(p->d_rows, rows_host, sizeof(int) * (size_t)nrows, hipMemcpyHostToDevice, h->stream));
   }
   MI355X_TRY(hipStreamSynchronize(h->stream));  // rb is a local
-  *plan = p;
+  *plan = p.release();
   return 0;
+}
+int mi355x_spmv_plan_create(mi355x_handle_t h, int nrows, const int *ai_host, const int *rows_host, mi355x_spmv_plan_t *plan) {
+  *plan = nullptr;
+  return mi355x_guard([&] { return spmv_plan_create(h, nrows, ai_host, rows_host, plan); });
 }
 
 // host threads of the pattern analyses: up to `cap`, one below 400 000 rows; MI355X_ANALYSIS_THREADS=<n> in the environment
@@ -1064,7 +1052,7 @@ static int analysis_threads(int m, int cap) {
 
 // Offset-dictionary analysis: idx8[k] = position of (aj[k] - row) in a table of <= 256 distinct offsets.
 // Returns 0 and leaves the plan uncompressed when the matrix has more distinct offsets.
-int mi355x_spmv_plan_compress_indices(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai_host, const int *aj_host) {
+static int spmv_compress_indices(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai_host, const int *aj_host) {
   if (!p || p->d_rows || p->d_idx8 || p->nrows == 0) return 0;
   if (SPMV_BLOCK_ROWS > 256) return 0;   // row markers are bytes
   const int m = p->nrows;
@@ -1074,17 +1062,10 @@ int mi355x_spmv_plan_compress_indices(mi355x_handle_t h, mi355x_spmv_plan_t p, c
   // tables are merged in chunk order -- which gives the table of a single pass over all rows -- and the chunks renumber their part.
   int nth = analysis_threads(m, 16);
   auto chunk_lo = [&](int k) { return (int)((long)m * k / nth); };
-  auto run_chunks = [&](auto fn) {
-    if (nth == 1) { fn(0); return; }
-    std::vector<std::thread> th;
-    for (int k = 1; k < nth; ++k) th.emplace_back(fn, k);
-    fn(0);
-    for (auto &t : th) t.join();
-  };
   std::unique_ptr<unsigned char[]> idx(new unsigned char[(size_t)(nnz > 0 ? nnz : 1)]);
   struct OffTab { int tab[256]; int n = 0; bool ok = true; };
   std::vector<OffTab> lt((size_t)nth);
-  run_chunks([&](int k) {
+  mi355x_parallel_chunks(nth, [&](int k) {
     OffTab &t = lt[(size_t)k];
     int last = 0;      // (offsets of a stencil matrix repeat row after row, so the slot after the previous one is tried first)
     for (int r = chunk_lo(k); r < chunk_lo(k + 1); ++r) {
@@ -1117,11 +1098,12 @@ int mi355x_spmv_plan_compress_indices(mi355x_handle_t h, mi355x_spmv_plan_t p, c
       if (g != e) identity[(size_t)k] = 0;
     }
   }
-  run_chunks([&](int k) {
+  mi355x_parallel_chunks(nth, [&](int k) {
     if (identity[(size_t)k]) return;
     const unsigned char *mp = remap[(size_t)k].data();
     for (long q = ai_host[chunk_lo(k)]; q < ai_host[chunk_lo(k + 1)]; ++q) idx[(size_t)q] = mp[idx[(size_t)q]];
   });
+  std::vector<int2> blk((size_t)p->nblocks + 1);       // (row patterns below; allocated here: a throw must not leave copies out of idx, tab in flight)
   MI355X_TRY(hipMalloc((void **)&p->d_idx8, (size_t)(nnz > 0 ? nnz : 1) + 16));
   MI355X_TRY(hipMalloc((void **)&p->d_offtab, sizeof(int) * 256));
   MI355X_TRY(hipMemsetAsync(p->d_offtab, 0, sizeof(int) * 256, h->stream));
@@ -1148,13 +1130,12 @@ int mi355x_spmv_plan_compress_indices(mi355x_handle_t h, mi355x_spmv_plan_t p, c
   // table that would not fit leave the plan at the per-nonzero bytes
   {
     // first nonzero of every row block (the rows carry their offset from it in 16 bits: a block holds <= 2046 nonzeros)
-    std::vector<int2> blk((size_t)p->nblocks + 1);
     MI355X_TRY(hipMemcpyAsync(blk.data(), p->d_rowblk, sizeof(int2) * ((size_t)p->nblocks + 1), hipMemcpyDeviceToHost, h->stream));
     MI355X_TRY(hipStreamSynchronize(h->stream));          // (also: idx and tab have left the host)
     std::unique_ptr<unsigned int[]> prow(new unsigned int[(size_t)m]);
     struct PatDict { std::vector<int> ptab; std::vector<int> starts; std::vector<std::vector<unsigned char>> keys; bool ok = true; };
     std::vector<PatDict> pd((size_t)nth);
-    run_chunks([&](int k) {
+    mi355x_parallel_chunks(nth, [&](int k) {
       PatDict &d = pd[(size_t)k];
       std::map<std::vector<unsigned char>, int> dict;
       std::vector<unsigned char> cur, prev;
@@ -1213,7 +1194,7 @@ int mi355x_spmv_plan_compress_indices(mi355x_handle_t h, mi355x_spmv_plan_t p, c
       }
     }
     if (ok) {
-      run_chunks([&](int k) {
+      mi355x_parallel_chunks(nth, [&](int k) {
         if (same[(size_t)k]) return;
         const int *t = to[(size_t)k].data();
         for (int r = chunk_lo(k); r < chunk_lo(k + 1); ++r) prow[(size_t)r] = (prow[(size_t)r] & 0xffff0000u) | (unsigned int)t[prow[(size_t)r] & 0xffffu];
@@ -1229,6 +1210,9 @@ int mi355x_spmv_plan_compress_indices(mi355x_handle_t h, mi355x_spmv_plan_t p, c
   }
   return 0;
 }
+int mi355x_spmv_plan_compress_indices(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai_host, const int *aj_host) {
+  return mi355x_guard([&] { return spmv_compress_indices(h, p, ai_host, aj_host); });
+}
 
 // A/B switch for the row-pattern kernel (on by default when the analysis found a dictionary); *npat: its size, 0 if none
 int mi355x_spmv_plan_use_patterns(mi355x_spmv_plan_t p, int on, int *npat) {
@@ -1242,8 +1226,7 @@ int mi355x_spmv_plan_use_patterns(mi355x_spmv_plan_t p, int on, int *npat) {
 // values compared bit for bit.  Gives up as soon as the table would exceed SPMV_PAT_CAP entries -- after a few dozen
 // rows for a matrix with varying coefficients -- and then leaves the plan as it was.  To be called with the values that
 // are (about to be) on the device, after every change of them.  *nvpat: distinct rows found, 0 when not applicable.
-int mi355x_spmv_plan_value_patterns(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai_host, const int *aj_host,
-                                    const double *aa_host, int *nvpat) {
+static int spmv_value_patterns(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai_host, const int *aj_host, const double *aa_host, int *nvpat) {
   if (nvpat) *nvpat = 0;
   if (!p) return (int)hipErrorInvalidValue;
   p->vpat_valid = 0;
@@ -1290,12 +1273,7 @@ int mi355x_spmv_plan_value_patterns(mi355x_handle_t h, mi355x_spmv_plan_t p, con
   };
   const int nth = analysis_threads(m, 8);
   std::vector<Dict> dicts((size_t)nth);
-  if (nth == 1) analyse(0, m, dicts[0]);
-  else {
-    std::vector<std::thread> th;
-    for (int k = 0; k < nth; ++k) th.emplace_back(analyse, (int)((long)m * k / nth), (int)((long)m * (k + 1) / nth), std::ref(dicts[(size_t)k]));
-    for (auto &t : th) t.join();
-  }
+  mi355x_parallel_chunks(nth, [&](int k) { analyse((int)((long)m * k / nth), (int)((long)m * (k + 1) / nth), dicts[(size_t)k]); });
   for (auto &d : dicts) if (!d.ok) return 0;
   std::vector<int> ptab(std::move(dicts[0].ptab)), starts(std::move(dicts[0].starts));
   std::vector<double> pval(std::move(dicts[0].pval));
@@ -1337,6 +1315,10 @@ int mi355x_spmv_plan_value_patterns(mi355x_handle_t h, mi355x_spmv_plan_t p, con
   if (nvpat) *nvpat = p->nvpat;
   return 0;
 }
+int mi355x_spmv_plan_value_patterns(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai_host, const int *aj_host,
+                                    const double *aa_host, int *nvpat) {
+  return mi355x_guard([&] { return spmv_value_patterns(h, p, ai_host, aj_host, aa_host, nvpat); });
+}
 
 // the values on the device no longer are the ones the table was derived from
 int mi355x_spmv_plan_drop_value_patterns(mi355x_spmv_plan_t p) {
@@ -1358,8 +1340,7 @@ int mi355x_spmv_plan_use_value_patterns(mi355x_spmv_plan_t p, int on, int *nvpat
 // with it.  This routine stores one column list per group and rebuilds the row blocks from whole groups.  It leaves
 // the plan as it is (returns 0) when grouping would not pay (shared indices > 2/3 of the nonzeros), when a row has
 // more than SPMV_GJ_CAP entries, or for compressed-row / index-compressed plans.
-int mi355x_spmv_plan_group_rows(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai_host, const int *aj_host, int nnodes,
-                                const int *ns) {
+static int spmv_group_rows(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai_host, const int *aj_host, int nnodes, const int *ns) {
   if (!p || p->d_rows || p->d_idx8 || p->d_gj || p->nrows == 0 || nnodes <= 0) return 0;
   const int m = p->nrows;
   const long nnz = ai_host[m];
@@ -1420,6 +1401,10 @@ int mi355x_spmv_plan_group_rows(mi355x_handle_t h, mi355x_spmv_plan_t p, const i
   p->ngroups = ngroups;
   p->ngj = ngj;
   return 0;
+}
+int mi355x_spmv_plan_group_rows(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai_host, const int *aj_host, int nnodes,
+                                const int *ns) {
+  return mi355x_guard([&] { return spmv_group_rows(h, p, ai_host, aj_host, nnodes, ns); });
 }
 
 int mi355x_spmv_plan_set_pairsum(mi355x_spmv_plan_t p, int on) {

@@ -48,8 +48,6 @@
 #include <algorithm>
 #include <atomic>
 #include <memory>
-#include <new>
-#include <thread>
 #include <vector>
 #include <string.h>
 #include <stdlib.h>
@@ -230,31 +228,25 @@ extern "C" {
 int mi355x_spmv_tiled_probe(int m, const int *ai, const int *aj, double *lines_per_nonzero) {
   *lines_per_nonzero = 0.0;
   if (m <= 0 || ai[m] <= 0) return 0;
-  const int G = 32, ngroups = (m + G - 1) / G, nsample = std::min(ngroups, 4096);
-  long lines = 0, nz = 0;
-  std::vector<int> buf;
-  for (int s = 0; s < nsample; ++s) {
-    const int g = (int)((long)s * ngroups / nsample);
-    const int r0 = g * G, r1 = std::min(m, r0 + G);
-    buf.clear();
-    for (int k = ai[r0]; k < ai[r1]; ++k) buf.push_back(aj[k] >> 4);
-    nz += (long)buf.size();
-    std::sort(buf.begin(), buf.end());
-    lines += (long)(std::unique(buf.begin(), buf.end()) - buf.begin());
-  }
-  *lines_per_nonzero = nz ? (double)lines / (double)nz : 0.0;
-  return 0;
+  return mi355x_guard([&] {
+    const int G = 32, ngroups = (m + G - 1) / G, nsample = std::min(ngroups, 4096);
+    long lines = 0, nz = 0;
+    std::vector<int> buf;
+    for (int s = 0; s < nsample; ++s) {
+      const int g = (int)((long)s * ngroups / nsample);
+      const int r0 = g * G, r1 = std::min(m, r0 + G);
+      buf.clear();
+      for (int k = ai[r0]; k < ai[r1]; ++k) buf.push_back(aj[k] >> 4);
+      nz += (long)buf.size();
+      std::sort(buf.begin(), buf.end());
+      lines += (long)(std::unique(buf.begin(), buf.end()) - buf.begin());
+    }
+    *lines_per_nonzero = nz ? (double)lines / (double)nz : 0.0;
+    return 0;
+  });
 }
 
 // Host part: cut the CSR matrix into staged (panel, tile) streams + remainder.  No device call.  stage_min <= 0: the default (1024).
-static int tl_build_impl(int m, int n, const int *ai, const int *aj, int stage_min, mi355x_spmv_tiled_t *out);
-int mi355x_spmv_tiled_build(int m, int n, const int *ai, const int *aj, int stage_min, mi355x_spmv_tiled_t *out) {
-  *out = nullptr;
-  if (m < 0 || n < 0) return (int)hipErrorInvalidValue;
-  try { return tl_build_impl(m, n, ai, aj, stage_min, out); }       // (the layout is a few times the CSR arrays in host memory: an allocation that fails must come back as an error code)
-  catch (const std::bad_alloc &) { *out = nullptr; return (int)hipErrorOutOfMemory; }
-  catch (...) { *out = nullptr; return (int)hipErrorUnknown; }
-}
 static int tl_build_impl(int m, int n, const int *ai, const int *aj, int stage_min, mi355x_spmv_tiled_t *out) {
   if (stage_min <= 0) stage_min = 1024;
   std::unique_ptr<tl_host> Hown(new tl_host());
@@ -306,19 +298,12 @@ static int tl_build_impl(int m, int n, const int *ai, const int *aj, int stage_m
     if (H->nnz < 2000000) nth = 1;
     if (nth > H->npanels) nth = H->npanels > 0 ? H->npanels : 1;
     std::atomic<int> next(0), failed(0);
-    auto work = [&]() {
-      try {
-        std::vector<int> cnt((size_t)ntiles + 1, 0), touched, cur((size_t)TL_PANEL, 0);
-        std::vector<char> stagedflag((size_t)ntiles + 1, 0);
-        for (int p = next.fetch_add(1); p < H->npanels && !failed.load(); p = next.fetch_add(1))
-          build_panel(H->prow[(size_t)p], H->prow[(size_t)p + 1], ai, aj, stage_min, cnt, touched, cur, stagedflag, po[(size_t)p]);
-      } catch (...) { failed.store(1); }                  // (an exception must not leave a thread)
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nth; ++t) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
-    if (failed.load()) return (int)hipErrorOutOfMemory;
+    mi355x_parallel_chunks(nth, [&](int) {
+      std::vector<int> cnt((size_t)ntiles + 1, 0), touched, cur((size_t)TL_PANEL, 0);
+      std::vector<char> stagedflag((size_t)ntiles + 1, 0);
+      for (int p = next.fetch_add(1); p < H->npanels && !failed.load(); p = next.fetch_add(1))
+        build_panel(H->prow[(size_t)p], H->prow[(size_t)p + 1], ai, aj, stage_min, cnt, touched, cur, stagedflag, po[(size_t)p]);
+    }, &failed);
   }
   // concatenate: panel after panel, inside a panel wavefront after wavefront
   size_t npt = 0, nst = 0;
@@ -358,6 +343,11 @@ static int tl_build_impl(int m, int n, const int *ai, const int *aj, int stage_m
   P->nnz_near = H->nnz_near; P->nnz_far = H->nnz_far; P->nstore = H->nstore;
   *out = P;
   return 0;
+}
+int mi355x_spmv_tiled_build(int m, int n, const int *ai, const int *aj, int stage_min, mi355x_spmv_tiled_t *out) {
+  *out = nullptr;
+  if (m < 0 || n < 0) return (int)hipErrorInvalidValue;
+  return mi355x_guard([&] { return tl_build_impl(m, n, ai, aj, stage_min, out); });   // (the layout is a few times the CSR arrays in host memory)
 }
 
 // nblocks: 128-entry blocks over all wavefronts (nnz_staged / (128 nblocks) = the share of the stored entries that are not padding)

@@ -6,7 +6,6 @@
 #include "common.hpp"
 #include <vector>
 #include <algorithm>
-#include <thread>
 #include <atomic>
 #include <chrono>
 #include <memory>
@@ -822,6 +821,7 @@ __global__ __launch_bounds__(MI355X_BLOCK) void trisolve_node_level_kernel(int p
 }
 
 extern "C" int mi355x_trisolve_plan_destroy(mi355x_trisolve_plan_t p);
+using tri_plan_ptr = std::unique_ptr<mi355x_trisolve_plan_s, decltype(&mi355x_trisolve_plan_destroy)>;   // a plan under construction
 
 // The same rows, one dependency level per launch, no polling: what an application falls back to after a sync-free solve gave
 // up (bounded spins), and the reference point the sync-free kernels are measured against.  Same layout, same per-row
@@ -862,11 +862,7 @@ template <class T> struct HostBuf {
 template <class F> static void host_parallel_for(long n, long grain, F f) {
   long nth = mi355x_host_threads(8);
   if (nth > n / (grain > 0 ? grain : 1)) nth = n / (grain > 0 ? grain : 1);
-  if (nth <= 1) { f(0L, n); return; }
-  std::vector<std::thread> th;
-  for (long k = 1; k < nth; ++k) th.emplace_back(f, n * k / nth, n * (k + 1) / nth);
-  f(0L, n / nth);
-  for (auto &t : th) t.join();
+  mi355x_parallel_ranges(n, (int)nth, f);
 }
 
 __global__ __launch_bounds__(MI355X_BLOCK) void tri_arm_kernel(size_t n, double *w) {
@@ -910,6 +906,27 @@ int trisolve_plan_finish(mi355x_handle_t h, mi355x_trisolve_plan_s *p, int nlev,
   // workgroups: cap 1 2.66 ms, 2 2.67, 4 2.76, 8 2.83 per application (polled one after the other: 8.1 ms at cap 2, 2.9 at cap 8:
   // the polls flooded the L2); P7(128), 88 workgroups: cap 2 1.04 ms, cap 8 1.14
   { const char *e = getenv("MI355X_TRISOLVE_SLEEP"); p->sleep_cap = e ? atoi(e) : 2; if (p->sleep_cap < 1) p->sleep_cap = 1; }
+  return 0;
+}
+
+// the plans of a factor's two halves built side by side (mi355x_trisolve_plan_create_pair / _nodes_pair): the lower one on a second
+// host thread, which selects the caller's device, the upper one on this thread.  Both come back, or neither.
+template <class MakeLo, class MakeUp>
+static int trisolve_plan_pair(MakeLo make_lo, MakeUp make_up, mi355x_trisolve_plan_t *lower, mi355x_trisolve_plan_t *upper) {
+  int dev = 0;
+  MI355X_TRY(hipGetDevice(&dev));
+  mi355x_trisolve_plan_t lo = nullptr, up = nullptr;
+  int rc_lo = 0, rc_up = 0;
+  mi355x_parallel_chunks(2, [&](int k) {
+    if (k == 1) { (void)hipSetDevice(dev); rc_lo = make_lo(&lo); }
+    else rc_up = make_up(&up);
+  });
+  if (rc_lo || rc_up) {
+    mi355x_trisolve_plan_destroy(lo);
+    mi355x_trisolve_plan_destroy(up);
+    return rc_lo ? rc_lo : rc_up;
+  }
+  *lower = lo; *upper = up;
   return 0;
 }
 
@@ -1043,14 +1060,7 @@ static int trisolve_plan_fill(mi355x_handle_t h, mi355x_trisolve_plan_s *p, int 
         }
       }
     };
-    int nth = mi355x_host_threads(8);
-    if (n < 200000) nth = 1;
-    if (nth == 1) fill(0, n);
-    else {
-      std::vector<std::thread> th;
-      for (int k = 0; k < nth; ++k) th.emplace_back(fill, (int)((long)n * k / nth), (int)((long)n * (k + 1) / nth));
-      for (auto &t : th) t.join();
-    }
+    mi355x_parallel_ranges(n, n < 200000 ? 1 : mi355x_host_threads(8), fill);
     if (bad.load()) TRI_FAIL(); }
   tick("fill");
 #define TRI_UP(dst, vec, T) do { TRI_TRY(hipMalloc((void **)&(dst), sizeof(T) * (vec).size())); \
@@ -1075,8 +1085,6 @@ static int trisolve_plan_fill_nodes(mi355x_handle_t h, mi355x_trisolve_plan_s *p
 static int trisolve_plan_create_impl(mi355x_handle_t h, int n, int nlev, const int *lev, const int *rp, const int *rl, const int *cj,
                                      const double *cv, const double *dinv_host, const double *rscale_host, int by_level,
                                      mi355x_trisolve_plan_t *out, bool singles = false) {
-  mi355x_trisolve_plan_s *p = new mi355x_trisolve_plan_s();
-  memset(p, 0, sizeof(*p));
   *out = nullptr;
   // Deep, narrow dependency graphs (the factor of an unstructured matrix: hundreds of rows per level, thousands of levels) are a
   // chain of hand-offs: they run through the split-role kernels of the node plans with every row a node of its own (a loader and a
@@ -1088,12 +1096,15 @@ static int trisolve_plan_create_impl(mi355x_handle_t h, int n, int nlev, const i
   // serves the orders the device route does not build (dependencies oldest first, node plans).  Same plan either way, bit for bit.
   const char *bm = getenv("MI355X_TRISOLVE_BUILD");
   const bool on_device = !singles && !by_level && n > 0 && !(bm && !strcmp(bm, "host"));
-  const int rc = singles ? trisolve_plan_fill_nodes(h, p, n, n, nullptr, nlev, lev, rp, rl, cj, cv, dinv_host, by_level, 0, rscale_host, 1)
-                 : on_device ? trisolve_plan_fill_device(h, p, n, nlev, lev, rp, rl, cj, cv, dinv_host, rscale_host, by_level)
-                             : trisolve_plan_fill(h, p, n, nlev, lev, rp, rl, cj, cv, dinv_host, rscale_host, by_level);
-  if (rc) { mi355x_trisolve_plan_destroy(p); return rc; }     // one cleanup path: nothing allocated so far survives a failure
-  *out = p;
-  return 0;
+  return mi355x_guard([&] {
+    tri_plan_ptr p(new mi355x_trisolve_plan_s(), mi355x_trisolve_plan_destroy);   // (zeroed) one cleanup path: nothing allocated so far survives a failure
+    const int rc = singles ? trisolve_plan_fill_nodes(h, p.get(), n, n, nullptr, nlev, lev, rp, rl, cj, cv, dinv_host, by_level, 0, rscale_host, 1)
+                   : on_device ? trisolve_plan_fill_device(h, p.get(), n, nlev, lev, rp, rl, cj, cv, dinv_host, rscale_host, by_level)
+                               : trisolve_plan_fill(h, p.get(), n, nlev, lev, rp, rl, cj, cv, dinv_host, rscale_host, by_level);
+    if (rc) return rc;
+    *out = p.release();
+    return 0;
+  });
 }
 
 
@@ -1162,14 +1173,7 @@ static int trisolve_plan_fill_nodes(mi355x_handle_t h, mi355x_trisolve_plan_s *p
         }
       }
     };
-    int nth = mi355x_host_threads(8);
-    if (nnodes < 100000) nth = 1;
-    if (nth == 1) check(0, nnodes);
-    else {
-      std::vector<std::thread> th;
-      for (int k = 0; k < nth; ++k) th.emplace_back(check, (int)((long)nnodes * k / nth), (int)((long)nnodes * (k + 1) / nth));
-      for (auto &t : th) t.join();
-    }
+    mi355x_parallel_ranges(nnodes, nnodes < 100000 ? 1 : mi355x_host_threads(8), check);
     if (bad.load()) TRI_FAIL(); }
   tick("shape check");
   // positions: nodes by level, more shared columns first inside a level (stable)
@@ -1279,16 +1283,14 @@ static int trisolve_plan_fill_nodes(mi355x_handle_t h, mi355x_trisolve_plan_s *p
         }
       }
     };
-    int nth = mi355x_host_threads(8);
-    if (nnodes < 100000) nth = 1;
-    if (nth == 1) fill(0, nnodes);
-    else {
-      std::vector<std::thread> th;
-      for (int k = 0; k < nth; ++k) th.emplace_back(fill, (int)((long)nnodes * k / nth), (int)((long)nnodes * (k + 1) / nth));
-      for (auto &t : th) t.join();
-    }
+    mi355x_parallel_ranges(nnodes, nnodes < 100000 ? 1 : mi355x_host_threads(8), fill);
     if (bad.load()) TRI_FAIL(); }
   tick("fill");
+  std::vector<double> rsc;        // (built before the copies out of the local vectors start: an exception must not leave them in flight)
+  if (rscale_host && singles && upper) {
+    rsc.assign(np > 0 ? np : 1, 1.0);
+    for (size_t P = 0; P < np; ++P) if (rowof[P] >= 0) rsc[P] = rscale_host[rowof[P]];
+  }
 #define TRI_UP(dst, vec, T) do { TRI_TRY(hipMalloc((void **)&(dst), sizeof(T) * (vec).size())); \
     TRI_TRY(hipMemcpyAsync((dst), (vec).data(), sizeof(T) * (vec).size(), hipMemcpyHostToDevice, h->stream)); } while (0)
   TRI_UP(p->d_ptr, ptr, int); TRI_UP(p->d_info, info, int); TRI_UP(p->d_row, rowof, int); TRI_UP(p->d_col, col, int);
@@ -1296,12 +1298,7 @@ static int trisolve_plan_fill_nodes(mi355x_handle_t h, mi355x_trisolve_plan_s *p
   TRI_TRY(hipMemcpyAsync(p->d_val, val, sizeof(double) * nval, hipMemcpyHostToDevice, h->stream));
   TRI_UP(p->d_nsub, nsub, unsigned char); TRI_UP(p->d_pos, slot, int);
   TRI_UP(p->d_nsz, nszv, unsigned char); TRI_UP(p->d_din, din, double);
-  std::vector<double> rsc;
-  if (rscale_host && singles && upper) {
-    rsc.assign(np > 0 ? np : 1, 1.0);
-    for (size_t P = 0; P < np; ++P) if (rowof[P] >= 0) rsc[P] = rscale_host[rowof[P]];
-    TRI_UP(p->d_rscale, rsc, double);
-  }
+  if (!rsc.empty()) TRI_UP(p->d_rscale, rsc, double);
 #undef TRI_UP
   const size_t nw = (np > 0 ? np : 1) * (size_t)NB;
   TRI_TRY(hipStreamSynchronize(h->stream));
@@ -1338,13 +1335,14 @@ static int trisolve_plan_fill_nodes(mi355x_handle_t h, mi355x_trisolve_plan_s *p
 
 int mi355x_trisolve_plan_create_nodes(mi355x_handle_t h, int n, int nnodes, const int *nstart, int nlev, const int *nodelev, const int *rp, const int *rl,
                                       const int *cj, const double *cv, const double *dinv_host, int by_level, int block_columns, mi355x_trisolve_plan_t *out) {
-  mi355x_trisolve_plan_s *p = new mi355x_trisolve_plan_s();
-  memset(p, 0, sizeof(*p));
   *out = nullptr;
-  const int rc = trisolve_plan_fill_nodes(h, p, n, nnodes, nstart, nlev, nodelev, rp, rl, cj, cv, dinv_host, by_level, block_columns, nullptr, 0);
-  if (rc) { mi355x_trisolve_plan_destroy(p); return rc; }
-  *out = p;
-  return 0;
+  return mi355x_guard([&] {
+    tri_plan_ptr p(new mi355x_trisolve_plan_s(), mi355x_trisolve_plan_destroy);
+    const int rc = trisolve_plan_fill_nodes(h, p.get(), n, nnodes, nstart, nlev, nodelev, rp, rl, cj, cv, dinv_host, by_level, block_columns, nullptr, 0);
+    if (rc) return rc;
+    *out = p.release();
+    return 0;
+  });
 }
 
 int mi355x_trisolve_plan_create_pair(mi355x_handle_t h, int n, int by_level,
@@ -1353,10 +1351,6 @@ int mi355x_trisolve_plan_create_pair(mi355x_handle_t h, int n, int by_level,
                                      const double *dinv_up, const double *rscale_up, mi355x_trisolve_plan_t *lower, mi355x_trisolve_plan_t *upper) {
   *lower = *upper = nullptr;
   if (!dinv_up) return (int)hipErrorInvalidValue;
-  int dev = 0;
-  MI355X_TRY(hipGetDevice(&dev));
-  mi355x_trisolve_plan_t lo = nullptr, up = nullptr;
-  int rc_lo = 0, rc_up = 0;
   // MI355X_TRISOLVE_SPLIT=0 / MI355X_TRISOLVE_SPLIT_ROWS=<rows per level> move the switch between the two kernel families (default:
   // fewer than 4096 rows per dependency level -> split-role kernels, every row a node of its own)
   bool singles = false;
@@ -1364,16 +1358,9 @@ int mi355x_trisolve_plan_create_pair(mi355x_handle_t h, int n, int by_level,
     const long width = w ? atol(w) : 4096;
     const int nl = nlev_lo > nlev_up ? nlev_lo : nlev_up;
     singles = !(e && atoi(e) == 0) && nl > 0 && n >= 64 && (long)n / nl < width; }
-  std::thread tl([&] { (void)hipSetDevice(dev); rc_lo = trisolve_plan_create_impl(h, n, nlev_lo, lev_lo, rp_lo, rl_lo, cj_lo, cv_lo, nullptr, nullptr, by_level, &lo, singles); });
-  rc_up = trisolve_plan_create_impl(h, n, nlev_up, lev_up, rp_up, rl_up, cj_up, cv_up, dinv_up, rscale_up, rscale_up ? 0 : by_level, &up, singles);
-  tl.join();
-  if (rc_lo || rc_up) {
-    if (lo) mi355x_trisolve_plan_destroy(lo);
-    if (up) mi355x_trisolve_plan_destroy(up);
-    return rc_lo ? rc_lo : rc_up;
-  }
-  *lower = lo; *upper = up;
-  return 0;
+  auto lo = [&](mi355x_trisolve_plan_t *o) { return trisolve_plan_create_impl(h, n, nlev_lo, lev_lo, rp_lo, rl_lo, cj_lo, cv_lo, nullptr, nullptr, by_level, o, singles); };
+  auto up = [&](mi355x_trisolve_plan_t *o) { return trisolve_plan_create_impl(h, n, nlev_up, lev_up, rp_up, rl_up, cj_up, cv_up, dinv_up, rscale_up, rscale_up ? 0 : by_level, o, singles); };
+  return mi355x_guard([&] { return trisolve_plan_pair(lo, up, lower, upper); });
 }
 
 int mi355x_trisolve_plan_create_nodes_pair(mi355x_handle_t h, int n, int nnodes, const int *nstart, int by_level, int block_columns,
@@ -1382,20 +1369,9 @@ int mi355x_trisolve_plan_create_nodes_pair(mi355x_handle_t h, int n, int nnodes,
                                            const int *cj, const double *cv, const double *dinv, mi355x_trisolve_plan_t *lower, mi355x_trisolve_plan_t *upper) {
   *lower = *upper = nullptr;
   if (!dinv) return (int)hipErrorInvalidValue;
-  int dev = 0;
-  MI355X_TRY(hipGetDevice(&dev));
-  mi355x_trisolve_plan_t lo = nullptr, up = nullptr;
-  int rc_lo = 0, rc_up = 0;
-  std::thread tl([&] { (void)hipSetDevice(dev); rc_lo = mi355x_trisolve_plan_create_nodes(h, n, nnodes, nstart, nlev_lo, nodelev_lo, rp_lo, rl_lo, cj, cv, nullptr, by_level, block_columns, &lo); });
-  rc_up = mi355x_trisolve_plan_create_nodes(h, n, nnodes, nstart, nlev_up, nodelev_up, rp_up, rl_up, cj, cv, dinv, by_level, block_columns, &up);
-  tl.join();
-  if (rc_lo || rc_up) {
-    if (lo) mi355x_trisolve_plan_destroy(lo);
-    if (up) mi355x_trisolve_plan_destroy(up);
-    return rc_lo ? rc_lo : rc_up;
-  }
-  *lower = lo; *upper = up;
-  return 0;
+  auto lo = [&](mi355x_trisolve_plan_t *o) { return mi355x_trisolve_plan_create_nodes(h, n, nnodes, nstart, nlev_lo, nodelev_lo, rp_lo, rl_lo, cj, cv, nullptr, by_level, block_columns, o); };
+  auto up = [&](mi355x_trisolve_plan_t *o) { return mi355x_trisolve_plan_create_nodes(h, n, nnodes, nstart, nlev_up, nodelev_up, rp_up, rl_up, cj, cv, dinv, by_level, block_columns, o); };
+  return mi355x_guard([&] { return trisolve_plan_pair(lo, up, lower, upper); });
 }
 
 }  // extern "C"

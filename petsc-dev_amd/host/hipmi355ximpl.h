@@ -163,7 +163,7 @@ typedef struct {
 PetscErrorCode HipTriFactorsDestroy(HipTriFactors **f);
 PetscErrorCode HipTriFactorsApply(Mat F, HipTriFactors *f, Vec b, Vec x, PetscLogDouble flops);
 typedef void (*HipRangeFn)(void *ctx, PetscInt lo, PetscInt hi);
-void HipParallelRanges(PetscInt n, HipRangeFn fn, void *ctx);   /* fn over contiguous parts of [0, n) on up to 16 host threads (hipsys.c); one thread below 200 000 */
+void HipParallelRanges(PetscInt n, HipRangeFn fn, void *ctx);   /* fn over contiguous parts of [0, n) on HipHostThreads(16) host threads (hipsys.c); one thread below 200 000 */
 int HipHostThreads(int cap);                                    /* host threads this RANK may use for set-up passes: affinity mask, cgroup quota, ranks on the node (hipsys.c) */
 typedef PetscErrorCode (*HipProductNowFn)(Mat A, Vec x, Vec t);                           /* t = A x, launched now */
 typedef PetscErrorCode (*HipProductScaledFn)(Mat A, Vec d, Vec x, Vec w, PetscBool *ok);   /* w = d .* (A x) in one kernel */

@@ -30,22 +30,15 @@ PetscErrorCode PetscDeviceGet(PetscDeviceCtx **ctx) {
 }
 
 /* ---------------------------------------------------------------- host threads for the set-up passes */
-#include <pthread.h>
-#include <unistd.h>
-/* the set-up's bulk loops over rows (16.7 M of them for P7(256)) on host threads: contiguous ranges, nothing shared */
-typedef struct { HipRangeFn fn; void *ctx; PetscInt lo, hi; } HipRangeArg;
-static void *hip_range_thread(void *a_) { HipRangeArg *a = (HipRangeArg *)a_; a->fn(a->ctx, a->lo, a->hi); return NULL; }
 /* the affinity mask's CPUs, cut to the cgroup quota and shared among the ranks of this node (mi355x_host_threads): eight ranks of a
  * node do not start 8 x 16 spinning threads */
 int HipHostThreads(int cap) { return mi355x_host_threads(cap); }
+/* the set-up's bulk loops over rows (16.7 M of them for P7(256)) on host threads: contiguous ranges, nothing shared */
+typedef struct { HipRangeFn fn; void *ctx; } HipRangeCall;
+static int hip_range_call(void *c_, long lo, long hi) { HipRangeCall *c = (HipRangeCall *)c_; c->fn(c->ctx, (PetscInt)lo, (PetscInt)hi); return 0; }
 void HipParallelRanges(PetscInt n, HipRangeFn fn, void *ctx) {
-  HipRangeArg args[16]; pthread_t th[16]; int started[16];
-  int nth = HipHostThreads(16);
-  if (n < 200000) nth = 1;
-  for (int t = 0; t < nth; t++) { args[t].fn = fn; args[t].ctx = ctx; args[t].lo = (PetscInt)((long)n * t / nth); args[t].hi = (PetscInt)((long)n * (t + 1) / nth); }
-  for (int t = 1; t < nth; t++) started[t] = !pthread_create(&th[t], NULL, hip_range_thread, &args[t]);
-  fn(ctx, args[0].lo, args[0].hi);
-  for (int t = 1; t < nth; t++) { if (started[t]) pthread_join(th[t], NULL); else fn(ctx, args[t].lo, args[t].hi); }
+  HipRangeCall c = {fn, ctx};
+  (void)mi355x_host_parallel_ranges(n, n < 200000 ? 1 : HipHostThreads(16), hip_range_call, &c);   /* (a status comes back only from a chunk: these return 0) */
 }
 
 

@@ -80,6 +80,54 @@ def test_no_cpu_fallback(built):
     assert e.value.code == 76 and "no gfx950 device" in str(e.value)
 
 
+def test_host_parallel_ranges_runs_every_chunk_once(built):
+    """mi355x_host_parallel_ranges, the set-up passes' thread helper: chunk k is [n k / nth, n (k + 1) / nth), every chunk runs
+    exactly once whatever n and nth, and a chunk's nonzero status comes back once all chunks have finished"""
+    import time
+    from petsc_dev_amd._lib import HOST_RANGE_FN
+    k = built.load_kernels()
+    for n in (0, 1, 7, 300000):
+        for nth in (1, 3, 16, 64):
+            seen = []
+            fn = HOST_RANGE_FN(lambda ctx, lo, hi: seen.append((lo, hi)) or 0)
+            assert k.mi355x_host_parallel_ranges(n, nth, fn, None) == 0
+            assert sorted(seen) == [(n * c // nth, n * (c + 1) // nth) for c in range(nth)], (n, nth)
+    seen = []
+    bad_lo = 300000 * 5 // 16
+
+    def chunk(ctx, lo, hi):
+        if lo == bad_lo:
+            return 7
+        time.sleep(0.02)
+        seen.append(lo)
+        return 0
+    fn = HOST_RANGE_FN(chunk)
+    assert k.mi355x_host_parallel_ranges(300000, 16, fn, None) == 7
+    assert len(seen) == 15
+
+
+def test_hip_parallel_ranges_with_64_host_threads(built):
+    """HipParallelRanges (host/hipsys.c) with MI355X_HOST_THREADS=64, the documented override's largest count: 64 disjoint ranges
+    that cover [0, 300 000), in a child process (its former per-thread arrays of 16 slots overflowed here)"""
+    import subprocess
+    import sys
+    code = "\n".join([
+        "import ctypes as C, sys",
+        "C.CDLL(sys.argv[1], mode=C.RTLD_GLOBAL); C.CDLL(sys.argv[2], mode=C.RTLD_GLOBAL); plugin = C.CDLL(sys.argv[3])",
+        "FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int)",
+        "seen = []",
+        "fn = FN(lambda ctx, lo, hi: seen.append((lo, hi)))",
+        "plugin.HipParallelRanges.argtypes = [C.c_int, FN, C.c_void_p]",
+        "plugin.HipParallelRanges(300000, fn, None)",
+        "seen.sort()",
+        "assert len(seen) == 64, seen",
+        "assert seen[0][0] == 0 and seen[-1][1] == 300000 and all(a[0] < a[1] == b[0] for a, b in zip(seen, seen[1:])), seen",
+    ])
+    r = subprocess.run([sys.executable, "-c", code, built.harness_lib_path(), built.kernels_lib_path(), built.host_lib_path()],
+                       env=dict(os.environ, MI355X_HOST_THREADS="64"), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
 def lap2d(m, n):
     import scipy.sparse as sp
     N = m * n
