@@ -111,7 +111,9 @@ int mi355x_vec_pointwise_mult(mi355x_handle_t h, size_t n, const double *x, cons
 int mi355x_vec_pointwise_divide(mi355x_handle_t h, size_t n, const double *x, const double *y, double *w);
 /* VecReciprocal_Default  src/vec/vec/utils/vinv.c            x[i] = 1/x[i] where x[i] != 0 */
 int mi355x_vec_reciprocal(mi355x_handle_t h, size_t n, double *x);
-/* PCSetUp_Jacobi host loop  src/ksp/pc/impls/jacobi/jacobi.c:182-190  d = (d==0) ? 1 : 1/d, done on device */
+/* PCSetUp_Jacobi host loop  src/ksp/pc/impls/jacobi/jacobi.c:182-190  d = (d==0) ? 1 : 1/d, done on device (-0.0 counts as zero;
+ * 1/inf = 0).  The zero entries are not counted (the reference only uses the count for a PetscInfo line): nzero_dev must be NULL,
+ * anything else returns hipErrorInvalidValue and leaves d alone. */
 int mi355x_vec_jacobi_invert(mi355x_handle_t h, size_t n, double *d, int *nzero_dev);
 /* VecMAXPY_Seq        src/vec/vec/impls/seq/dvec2.c:836      x += sum_j alpha[j] y_j ; grouping
  * (nv%4 first, then fours) and left-to-right product sums follow petscaxpy.h:101-110.

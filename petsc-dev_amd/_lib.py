@@ -82,8 +82,13 @@ KERNEL_API = {
     "mi355x_trisolve_plan_create": [vp, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp)],
     "mi355x_trisolve_plan_create_ordered": [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp)],
     "mi355x_trisolve_plan_create_scaled": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)],
+    "mi355x_trisolve_plan_create_nodes": [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(vp)],
+    "mi355x_trisolve_plan_create_nodes_pair": [vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp)],
+    "mi355x_trisolve_debug_set_aborted": [vp, i32],
     "mi355x_trisolve_plan_destroy": [vp],
+    "mi355x_trisolve_plan_create_pair": [vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp)],
     "mi355x_trisolve_apply": [vp, vp, vp, vp, vp],
+    "mi355x_trisolve_apply_levels": [vp, vp, vp, vp, vp],
     "mi355x_trisolve_aborted": [vp, pi32],
     "mi355x_trisolve_debug_get": [vp, i32, vp, sz, C.POINTER(sz)],
     "mi355x_spmv_plan_create": [vp, i32, vp, vp, C.POINTER(vp)],

@@ -780,8 +780,8 @@ __global__ __launch_bounds__(SPMV_THREADS) void bsr_rowblock_kernel(const int2 *
     if (tid < BS) { double t = part[0][tid]; for (int w = 1; w < SPMV_THREADS / MI355X_WAVE; ++w) t += part[w][tid]; y[(long)r0 * BS + tid] = yin ? yin[(long)r0 * BS + tid] + t : t; }
     return;
   }
-  if (k1 == k0) {   // only empty block rows
-    if (tid < nv) y[(long)r0 * BS + tid] = yin ? yin[(long)r0 * BS + tid] : 0.0;
+  if (k1 == k0) {   // only empty block rows: up to SPMV_BLOCK_ROWS of them, i.e. up to BS times as many point rows as lanes
+    for (int v = tid; v < nv; v += SPMV_THREADS) y[(long)r0 * BS + v] = yin ? yin[(long)r0 * BS + v] : 0.0;
     return;
   }
   int tpr = 1;

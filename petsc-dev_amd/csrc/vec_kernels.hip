@@ -975,7 +975,7 @@ int mi355x_vec_reciprocal(mi355x_handle_t h, size_t n, double *x) {
   return launch_map<1>(h, OpRecip{}, x, nullptr, nullptr, x, n);
 }
 int mi355x_vec_jacobi_invert(mi355x_handle_t h, size_t n, double *d, int *nzero_dev) {
-  (void)nzero_dev;
+  if (nzero_dev) return (int)hipErrorInvalidValue;   // no count of the zero entries is kept (the header says so): refuse rather than leave it unwritten
   return launch_map<1>(h, OpJacInv{}, d, nullptr, nullptr, d, n);
 }
 int mi355x_stream_triad(mi355x_handle_t h, size_t n, double alpha, const double *b, const double *c, double *a) {

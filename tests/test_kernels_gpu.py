@@ -1,4 +1,6 @@
-"""Parity of every HIP kernel against the oracle, through the C ABI (include/mi355x_kernels.h).
+"""Parity of the HIP kernels against the oracle, through the C ABI (include/mi355x_kernels.h); test_abi_kernels_gpu.py holds the
+entry points this module does not call.  Which exported function is named by which test file is not claimed here but checked:
+test_host_cpu.py::test_every_exported_kernel_entry_point_is_named_by_a_test is the ledger.
 
 Element-wise kernels, MAXPY and the row-sequential SpMV paths must be BIT-EXACT; reductions use a
 fixed tree and are checked to |err| <= 1e-13 * sum|terms| (stated tolerance, fp64)."""
@@ -8,6 +10,7 @@ import numpy as np
 import pytest
 
 import orc
+from tri import TRI_SHAPES, tri_arrays, tri_levels as _tri_levels, tri_structure
 
 pytestmark = pytest.mark.gpu
 
@@ -781,6 +784,49 @@ def test_get_diagonal(dev):
     assert_bitexact(dev.get(dd, 2000), orc.get_diagonal(ai, aj, aa))
 
 
+def bsr_reference(bs, ai, aj, aa, x, y0=None):
+    """(ref, bound, gamma(t) S) of y = [y0 +] A x for BSR storage (blocks column-major): the row sums in np.longdouble and, per point row, the
+    worst-case distance of ANY float64 evaluation of that sum from it -- t products (rounded or fused), any order of additions:
+    |got - ref| <= gamma(t) S + t 2^-63 S, S = sum |a_ij x_j| (+ |y0_r|, t + 1 terms with y0), gamma(t) = t u / (1 - t u),
+    u = 2^-53 (Higham, Accuracy and Stability of Numerical Algorithms, 2nd ed., section 3.1 and 4.2); the second term is the
+    long-double reference's own error (64-bit significand: every product and every addition rounds to 2^-64 relative).
+    Rows without blocks: ref is exactly +0.0 (or y0_r) and the bound is 0."""
+    assert np.finfo(np.longdouble).nmant >= 63, "np.longdouble is not wider than float64 here"
+    ld = np.longdouble
+    mbs = ai.size - 1
+    nb = aj.size
+    blk_row = np.repeat(np.arange(mbs), np.diff(ai))
+    a = aa[:nb * bs * bs].reshape(nb, bs, bs).astype(ld)                     # [blk][col][row]
+    xb = x.astype(ld).reshape(-1, bs)[aj]                                    # [blk][col]
+    prod = a * xb[:, :, None]
+    ref = np.zeros((mbs, bs), dtype=ld); S = np.zeros((mbs, bs), dtype=ld)
+    np.add.at(ref, blk_row, prod.sum(axis=1))
+    np.add.at(S, blk_row, np.abs(prod).sum(axis=1))
+    t = np.repeat(np.diff(ai).astype(np.float64) * bs, bs).reshape(mbs, bs)
+    if y0 is not None:
+        ref = ref + y0.astype(ld).reshape(mbs, bs); S = S + np.abs(y0).astype(ld).reshape(mbs, bs)
+        t = np.where(t > 0, t + 1, 0.0)                                      # a row without blocks: y0_r itself, no rounding
+    u = 2.0 ** -53
+    gam = (t * u / (1 - t * u)).astype(ld)
+    bound = gam * S + t.astype(ld) * ld(2.0) ** -63 * S
+    return ref.ravel(), bound.ravel(), (gam * S).ravel()
+
+
+def assert_bsr_within_rounding(got, bs, ai, aj, aa, x, y0=None, what=""):
+    """every point row within the worst-case rounding bound of bsr_reference (no margin: it is a worst-case bound); rows without
+    blocks exactly +0.0 / y0_r.  Returns (and prints, for -s) the largest |got - ref| / (gamma(t) S) over the rows."""
+    ref, bound, gs = bsr_reference(bs, ai, aj, aa, x, y0)
+    err = np.abs(got.astype(np.longdouble) - ref)
+    worst = int(np.argmax(err - bound))
+    assert np.all(err <= bound), "%s point row %d: |got - ref| = %g > bound %g" % (what, worst, float(err[worst]), float(bound[worst]))
+    empty = np.repeat(np.diff(ai) == 0, bs)
+    expect = np.zeros(empty.sum()) if y0 is None else y0[empty]
+    assert np.array_equal(bits(got[empty]), bits(expect)), "%s: rows without blocks are not exactly +0.0 / y0" % what
+    ratio = float(np.max(err[gs > 0] / gs[gs > 0])) if np.any(gs > 0) else 0.0
+    print("%s bs=%d: max |got - ref| / (gamma(t) S) = %.3g" % (what, bs, ratio))
+    return ratio
+
+
 @pytest.mark.parametrize("bs", [1, 2, 3, 4, 5])
 def test_spmv_bsr(dev, bs):
     mbs, nbs = 400, 500
@@ -792,14 +838,13 @@ def test_spmv_bsr(dev, bs):
     dy = dev.alloc(8 * mbs * bs)
     dev.chk(dev.k.mi355x_spmv_bsr(dev.h, mbs, bs, dai, daj, daa, dx, dy))
     got = dev.get(dy, mbs * bs)
-    ref = orc.spmv_bsr(bs, ai, aj, aa, x)
-    assert np.allclose(got, ref, rtol=0, atol=1e-12 * 30 * bs * 10)
+    assert_bsr_within_rounding(got, bs, ai, aj, aa, x, what="spmv_bsr")
     if bs > 1:   # row-block streaming variant, plan over the value stream
         sc = (ai.astype(np.int64) * bs * bs).astype(np.int32)
         plan = make_plan(dev, sc)
         dev.chk(dev.k.mi355x_vec_set(dev.h, mbs * bs, 7.0, dy))
         dev.chk(dev.k.mi355x_spmv_bsr_planned(dev.h, plan, bs, dai, daj, daa, dx, dy))
-        assert np.allclose(dev.get(dy, mbs * bs), ref, rtol=0, atol=1e-12 * 30 * bs * 10)
+        assert_bsr_within_rounding(dev.get(dy, mbs * bs), bs, ai, aj, aa, x, what="spmv_bsr_planned")
 
 
 @pytest.mark.parametrize("variant", [0, 1])
@@ -850,7 +895,7 @@ def test_spmv_bsr_wide_block_row(dev):
     dx = dev.put(x); dy = dev.alloc(8 * mbs * bs)
     plan = make_plan(dev, (ai.astype(np.int64) * bs * bs).astype(np.int32))
     dev.chk(dev.k.mi355x_spmv_bsr_planned(dev.h, plan, bs, dai, daj, daa, dx, dy))
-    assert np.allclose(dev.get(dy, mbs * bs), orc.spmv_bsr(bs, ai, aj, aa, x), rtol=0, atol=1e-10)
+    assert_bsr_within_rounding(dev.get(dy, mbs * bs), bs, ai, aj, aa, x, what="spmv_bsr_planned wide")
 
 
 @pytest.mark.parametrize("bs", [2, 3, 5, 8])
@@ -868,9 +913,8 @@ def test_spmv_bsr_few_blocks_per_row(dev, bs):
     dx = dev.put(x); dy = dev.put(np.full(mbs * bs, 7.0))
     plan = make_plan(dev, (ai.astype(np.int64) * bs * bs).astype(np.int32))
     dev.chk(dev.k.mi355x_spmv_bsr_planned(dev.h, plan, bs, dai, daj, daa, dx, dy))
-    ref = orc.spmv_bsr(bs, ai, aj, aa, x)
     got = dev.get(dy, mbs * bs)
-    assert np.allclose(got, ref, rtol=0, atol=1e-12 * 2 * bs * 10)   # baij2.c groups a block's products before adding
+    assert_bsr_within_rounding(got, bs, ai, aj, aa, x, what="spmv_bsr_planned few")
     assert not np.any(got == 7.0)                        # every point row written
     dev.chk(dev.k.mi355x_spmv_plan_destroy(plan))
     for q in (dai, daj, daa, dx, dy):
@@ -1031,14 +1075,6 @@ def test_bcgs_fused_kernels_match_separate_kernels_bitwise(dev, n):
         dev.free(q)
 
 
-def _tri_levels(n, rp, rl, cj):
-    lev = np.zeros(n, dtype=np.int32)
-    for i in range(n):
-        d = cj[rp[i]:rp[i] + rl[i]]
-        lev[i] = (lev[d].max() + 1) if d.size else 0
-    return lev
-
-
 def _tri_plan_arrays(dev, plan):
     out = []
     for which, dt in ((0, np.int32), (1, np.int32), (2, np.int32), (3, np.int32), (4, np.uint64), (5, np.uint64), (6, np.uint64), (7, np.uint8), (8, np.int32), (9, np.int32)):
@@ -1051,7 +1087,7 @@ def _tri_plan_arrays(dev, plan):
     return out
 
 
-@pytest.mark.parametrize("shape", ["wide", "ragged", "chain", "tiny", "empty_rows", "n1", "n64", "n65", "longrow", "deepchain"])
+@pytest.mark.parametrize("shape", TRI_SHAPES)
 @pytest.mark.parametrize("kind", ["lower", "upper", "upper_scaled"])
 def test_trisolve_row_plans_built_on_the_device_equal_the_host_built_plans(dev, shape, kind, monkeypatch):
     """csrc/trisolve_build.hip lays a row plan out on the device (radix sort of the rows by (level, longer first), positions,
@@ -1061,35 +1097,11 @@ def test_trisolve_row_plans_built_on_the_device_equal_the_host_built_plans(dev, 
     column / value arrays (the device route uploads only the range the rows name)."""
     k = dev.k
     rng = np.random.default_rng(hash((shape, kind)) % (1 << 31))
-    n = {"wide": 40000, "ragged": 9000, "chain": 700, "tiny": 5, "empty_rows": 3000, "n1": 1, "n64": 64, "n65": 65, "longrow": 4000, "deepchain": 70000}[shape]
-    # strictly lower-triangular dependency structure (for an upper solve the caller hands over reversed roles; the plan only needs
-    # "dependencies come earlier in level order", so a lower structure serves both kinds here)
-    rl = np.zeros(n, dtype=np.int32)
-    cols = []
-    for i in range(n):
-        if shape == "wide":
-            cand = sorted(c for c in (i - 7000, i - 200, i - 1) if c >= 0 and not (c == i - 1 and i % 200 == 0))   # a 3-D stencil's lower part
-        elif shape == "ragged":
-            m = int(rng.integers(0, 40)) if i % 11 else 0
-            cand = sorted(set(int(c) for c in rng.integers(max(0, i - 3000), max(i, 1), size=m) if c < i)) if i else []
-        elif shape in ("chain", "deepchain"):
-            cand = [i - 1] if i and i % 3 else ([i - 2] if i > 1 else [])
-        elif shape in ("n1", "n64", "n65"):
-            cand = [c for c in (i - 1, i - 9) if c >= 0 and i % 4]
-        elif shape == "longrow":                            # a few rows with thousands of entries among short ones
-            cand = list(range(0, i, 1 if i in (1500, 3999) else max(i, 1))) if i in (1500, 3999) else ([i - 1] if i % 2 else [])
-        elif shape == "tiny":
-            cand = list(range(i))
-        else:
-            cand = [] if i % 2 else sorted(set(int(c) for c in rng.integers(0, max(i, 1), size=3) if c < i))
-        rl[i] = len(cand); cols.append(cand)
-    pad = 17                                                  # the rows' entries do not start at the arrays' first element
-    rp = (pad + np.concatenate(([0], np.cumsum(rl)[:-1]))).astype(np.int32)
-    nz = int(rl.sum())
-    cj = np.full(pad + nz + 5, -7, dtype=np.int32)            # entries no row names hold an invalid column: never looked at
-    cv = np.full(pad + nz + 5, np.nan)
-    for i in range(n):
-        cj[rp[i]:rp[i] + rl[i]] = cols[i]
+    n, rl, cols = tri_structure(shape, rng)                  # strictly lower-triangular dependency structure (for an upper solve the
+    # caller hands over reversed roles; the plan only needs "dependencies come earlier in level order", so it serves both kinds here)
+    rp, cj, nz = tri_arrays(n, rl, cols)                      # the rows' entries do not start at the arrays' first element; entries no
+    cv = np.full(cj.size, np.nan)                             # row names hold an invalid column / NaN: never looked at
+    pad = rp[0] if n else 0
     cv[pad:pad + nz] = rng.standard_normal(nz)
     lev = _tri_levels(n, rp, rl, cj)
     nlev = int(lev.max()) + 1
