@@ -240,6 +240,13 @@ int mi355x_spmv_csr_scaled(mi355x_handle_t h, mi355x_spmv_plan_t plan, const int
                            const double *x, const double *d, double *y);
 int mi355x_spmv_csr_add(mi355x_handle_t h, mi355x_spmv_plan_t plan, const int *ai, const int *aj,
                         const double *aa, const double *x, const double *y, double *z);
+/* z = d .* (y + A x): one step of a Jacobi-sweep triangular solve with inverted pivots, x^j = dinv .* (y - Us x^(j-1)) with A = -Us
+ * (host/ilu.c, -pc_factor_hipmi355x_trisolve sweeps:<k>; mi355x_spmv_csr_add is the step of the unit triangle).  Always the plain
+ * row-block kernel.  Short rows: one lane per row, s = y_r, s += a_j x_j in column order, d_r * s, no contraction -- with enough
+ * sweeps the bits of MatSolve_SeqAIJ_NaturalOrdering; long rows: the family's lane tree.  z may alias y, x must not alias z;
+ * z is stored non-temporally from 256 MiB. */
+int mi355x_spmv_csr_add_scaled(mi355x_handle_t h, mi355x_spmv_plan_t plan, const int *ai, const int *aj, const double *aa,
+                               const double *x, const double *y, const double *d, double *z);
 /* MatMultTranspose[Add]_SeqAIJ  src/mat/impls/aij/seq/aij.c:1078-1135 is served by the same two
  * kernels applied to an explicit transpose whose rows list contributions in increasing
  * original-row order (the order the reference's scatter loop adds them in). */

@@ -126,17 +126,22 @@ __device__ __forceinline__ double row_sum_lds(const double *prod, int rs, int re
 
 // How a row's sum reaches y.  ADD == 0: y = A x.  ADD == 1: y = yin + A x (MatMultAdd).  ADD == 2: y = yin .* (A x), yin being a
 // diagonal scaling (PCApply_Jacobi's VecPointwiseMult fused into the product: same bits as the two separate sweeps).
-template <int ADD> __device__ __forceinline__ double spmv_out(double yv, double t) { return ADD == 1 ? yv + t : (ADD == 2 ? yv * t : t); }
-template <int ADD> __device__ __forceinline__ double spmv_empty(double yv) { return ADD == 1 ? yv : (ADD == 2 ? yv * 0.0 : 0.0); }
-// same, for a sum that was started from yv when ADD == 1
-template <int ADD> __device__ __forceinline__ double spmv_fin(double yv, double s) { return ADD == 2 ? yv * s : s; }
+// ADD == 3: y = dv .* (yin + A x), one step of a Jacobi-sweep upper triangular solve (A the negated strict triangle, dv the
+// inverted pivots; host/ilu.c); the plain row-block kernel only.  The sum starts from yin as for ADD == 1, so a one-lane row
+// carries the bits of s = yin; s = s + a_j x_j ...; dv * s.
+template <int ADD> __device__ __forceinline__ double spmv_out(double yv, double t, double dv = 1.0) { return ADD == 3 ? dv * (yv + t) : (ADD == 1 ? yv + t : (ADD == 2 ? yv * t : t)); }
+template <int ADD> __device__ __forceinline__ double spmv_empty(double yv, double dv = 1.0) { return ADD == 3 ? dv * yv : (ADD == 1 ? yv : (ADD == 2 ? yv * 0.0 : 0.0)); }
+// same, for a sum that was started from yv when ADD == 1 or 3
+template <int ADD> __device__ __forceinline__ double spmv_fin(double yv, double s, double dv = 1.0) { return ADD == 3 ? dv * s : (ADD == 2 ? yv * s : s); }
 static inline int spmv_y_streams(long nrows) { return (size_t)nrows * sizeof(double) >= ((size_t)256 << 20); }   // (vec_kernels.hip: vec_streams)
 
 template <int ADD, bool CPROW, bool VEC>
 __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock_kernel(
     const int2 *__restrict__ rowblk, int nblocks, int chunk, const int *__restrict__ ai, const int *__restrict__ aj,
     const double *__restrict__ aa, const double *__restrict__ x, const double *yin, double *yout,
-    const int *__restrict__ rows, int pairsum) {
+    const int *__restrict__ rows, int pairsum, const double *__restrict__ dsc, int nty) {
+  // ADD == 3 only: dsc scales the row's result; nty: y is a stream of 256 MiB or more, stored past the caches
+  auto put = [&](int orow, double v) { if (ADD == 3 && nty) __builtin_nontemporal_store(v, yout + orow); else yout[orow] = v; };
   __shared__ double prod[SPMV_BLOCK_NNZ];
   __shared__ double wsum[SPMV_THREADS / MI355X_WAVE];
 
@@ -182,14 +187,14 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
 #pragma unroll
       for (int w = 1; w < SPMV_THREADS / MI355X_WAVE; ++w) t += wsum[w];
       const int orow = CPROW ? rows[r0] : r0;
-      yout[orow] = spmv_out<ADD>(ADD ? yin[orow] : 0.0, t);
+      put(orow, spmv_out<ADD>(ADD ? yin[orow] : 0.0, t, ADD == 3 ? dsc[orow] : 1.0));
     }
     return;
   }
   if (nnz == 0) {   // only empty rows
     if (tid < nrows) {
       const int orow = CPROW ? rows[r0 + tid] : r0 + tid;
-      yout[orow] = spmv_empty<ADD>(ADD ? yin[orow] : 0.0);
+      put(orow, spmv_empty<ADD>(ADD ? yin[orow] : 0.0, ADD == 3 ? dsc[orow] : 1.0));
     }
     return;
   }
@@ -208,6 +213,7 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
   const int orow = CPROW ? rows[r0 + rc] : r0 + rc;
   double ysum = 0.0;
   if (ADD) ysum = yin[orow];
+  const double dv = ADD == 3 ? dsc[orow] : 1.0;
 
   // ---- stream the block's nonzeros: product -> LDS -----------------------
   if (VEC) {
@@ -252,12 +258,12 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
   // ---- per-row sums out of LDS -------------------------------------------
   const int rs = r < nrows ? a0 - k0 : 0, re = r < nrows ? a1 - k0 : 0;
   if (tpr == 1) {
-    if (r < nrows) yout[orow] = spmv_fin<ADD>(ysum, row_sum_lds(prod, rs, re, ADD == 1 ? ysum : 0.0, pairsum));
+    if (r < nrows) put(orow, spmv_fin<ADD>(ysum, row_sum_lds(prod, rs, re, (ADD & 1) ? ysum : 0.0, pairsum), dv));
   } else {
     double sum = 0.0;
     if (r < nrows) for (int k = rs + sub; k < re; k += tpr) sum += prod[k];
     for (int off = tpr >> 1; off > 0; off >>= 1) sum += __shfl_down(sum, off, MI355X_WAVE);
-    if (r < nrows && sub == 0) yout[orow] = spmv_out<ADD>(ysum, sum);
+    if (r < nrows && sub == 0) put(orow, spmv_out<ADD>(ysum, sum, dv));
   }
 }
 
@@ -933,54 +939,56 @@ __global__ __launch_bounds__(MI355X_BLOCK) void csr_diag_kernel(int m, const int
 
 template <int ADD>
 static int launch_spmv(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai, const int *aj, const double *aa,
-                       const double *x, const double *yin, double *yout) {
+                       const double *x, const double *yin, double *yout, const double *dsc = nullptr) {
   if (p->nblocks == 0) return 0;
   const bool vec = mi355x_aligned16(aa) && ((((uintptr_t)aj) & 7u) == 0);
   const bool cprow = p->d_rows != nullptr;
-  if (p->vpat_valid && p->use_vpat && !cprow) {
-    const int nb = (p->nrows + SPMV_VPAT_ROWS - 1) / SPMV_VPAT_ROWS;
-    hipLaunchKernelGGL((spmv_csr_valpat_kernel<ADD, false>), dim3(nb), dim3(SPMV_THREADS), 0, h->stream, p->nrows, p->d_vrow, p->d_vpattab,
-                       p->d_vpatval, p->vtablen, x, yin, yout, (double *)nullptr, p->pairsum);
-    MI355X_LAUNCH_CHECK();
-    return 0;
-  }
-  if (p->d_gj && !cprow && mi355x_aligned16(aa)) {
+  if constexpr (ADD != 3) {   // (ADD == 3 exists in the plain row-block kernel only)
+    if (p->vpat_valid && p->use_vpat && !cprow) {
+      const int nb = (p->nrows + SPMV_VPAT_ROWS - 1) / SPMV_VPAT_ROWS;
+      hipLaunchKernelGGL((spmv_csr_valpat_kernel<ADD, false>), dim3(nb), dim3(SPMV_THREADS), 0, h->stream, p->nrows, p->d_vrow, p->d_vpattab,
+                         p->d_vpatval, p->vtablen, x, yin, yout, (double *)nullptr, p->pairsum);
+      MI355X_LAUNCH_CHECK();
+      return 0;
+    }
+    if (p->d_gj && !cprow && mi355x_aligned16(aa)) {
 #if SPMV_REMAP == 2
-    const int perg = MI355X_NXCD * SPMV_CH;
-    const int gg = ((p->nblocks + perg - 1) / perg) * perg;
+      const int perg = MI355X_NXCD * SPMV_CH;
+      const int gg = ((p->nblocks + perg - 1) / perg) * perg;
 #else
-    const int gg = p->nblocks;
+      const int gg = p->nblocks;
 #endif
-    hipLaunchKernelGGL((spmv_csr_rowblock_inode_kernel<ADD>), dim3(gg), dim3(SPMV_THREADS), 0, h->stream, p->d_rowblk4, p->nblocks,
-                       ai, p->d_goff, p->d_gj, aa, x, yin, yout, p->pairsum);
-    MI355X_LAUNCH_CHECK();
-    return 0;
-  }
-  if (p->d_prow && p->use_pat && !cprow && mi355x_aligned16(aa)) {
+      hipLaunchKernelGGL((spmv_csr_rowblock_inode_kernel<ADD>), dim3(gg), dim3(SPMV_THREADS), 0, h->stream, p->d_rowblk4, p->nblocks,
+                         ai, p->d_goff, p->d_gj, aa, x, yin, yout, p->pairsum);
+      MI355X_LAUNCH_CHECK();
+      return 0;
+    }
+    if (p->d_prow && p->use_pat && !cprow && mi355x_aligned16(aa)) {
 #if SPMV_REMAP == 2
-    const int perp = MI355X_NXCD * p->ch;
-    const int gp = ((p->nblocks + perp - 1) / perp) * perp;
+      const int perp = MI355X_NXCD * p->ch;
+      const int gp = ((p->nblocks + perp - 1) / perp) * perp;
 #else
-    const int gp = p->nblocks;
+      const int gp = p->nblocks;
 #endif
-    hipLaunchKernelGGL((spmv_csr_rowblock_pat_kernel<ADD, false>), dim3(gp), dim3(SPMV_THREADS), 0, h->stream, p->d_rowblk, p->nblocks,
-                       p->d_prow, p->d_pattab, aa, x, yin, yout, (double *)nullptr, p->pairsum, p->ch, spmv_y_streams(p->nrows));
-    MI355X_LAUNCH_CHECK();
-    return 0;
-  }
-  if (p->d_idx8 && !cprow && mi355x_aligned16(aa)) {
+      hipLaunchKernelGGL((spmv_csr_rowblock_pat_kernel<ADD, false>), dim3(gp), dim3(SPMV_THREADS), 0, h->stream, p->d_rowblk, p->nblocks,
+                         p->d_prow, p->d_pattab, aa, x, yin, yout, (double *)nullptr, p->pairsum, p->ch, spmv_y_streams(p->nrows));
+      MI355X_LAUNCH_CHECK();
+      return 0;
+    }
+    if (p->d_idx8 && !cprow && mi355x_aligned16(aa)) {
 #if SPMV_REMAP == 2
-    const int per8 = MI355X_NXCD * SPMV_CH;
-    const int g8 = ((p->nblocks + per8 - 1) / per8) * per8;
+      const int per8 = MI355X_NXCD * SPMV_CH;
+      const int g8 = ((p->nblocks + per8 - 1) / per8) * per8;
 #else
-    const int g8 = p->nblocks;
+      const int g8 = p->nblocks;
 #endif
-    hipLaunchKernelGGL((spmv_csr_rowblock_idx8_kernel<ADD, false>), dim3(g8), dim3(SPMV_THREADS), 0, h->stream, p->d_rowblk,
-                       p->nblocks, ai, p->d_idx8, p->d_offtab, p->ntab, aa, x, yin, yout, (double *)nullptr, p->pairsum);
-    MI355X_LAUNCH_CHECK();
-    return 0;
+      hipLaunchKernelGGL((spmv_csr_rowblock_idx8_kernel<ADD, false>), dim3(g8), dim3(SPMV_THREADS), 0, h->stream, p->d_rowblk,
+                         p->nblocks, ai, p->d_idx8, p->d_offtab, p->ntab, aa, x, yin, yout, (double *)nullptr, p->pairsum);
+      MI355X_LAUNCH_CHECK();
+      return 0;
+    }
   }
-  #if SPMV_REMAP == 2
+#if SPMV_REMAP == 2
   const int per = MI355X_NXCD * SPMV_CH;
   dim3 grid(((p->nblocks + per - 1) / per) * per), block(SPMV_THREADS);
 #else
@@ -988,7 +996,7 @@ static int launch_spmv(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai, c
 #endif
 #define SPMV_GO(C, V)                                                                                               \
   hipLaunchKernelGGL((spmv_csr_rowblock_kernel<ADD, C, V>), grid, block, 0, h->stream, p->d_rowblk, p->nblocks,    \
-                     p->chunk, ai, aj, aa, x, yin, yout, p->d_rows, p->pairsum)
+                     p->chunk, ai, aj, aa, x, yin, yout, p->d_rows, p->pairsum, dsc, spmv_y_streams(p->nrows))
   if (cprow) { if (vec) SPMV_GO(true, true); else SPMV_GO(true, false); }
   else       { if (vec) SPMV_GO(false, true); else SPMV_GO(false, false); }
 #undef SPMV_GO
@@ -1518,6 +1526,16 @@ int mi355x_spmv_dot_finish(mi355x_handle_t h, mi355x_spmv_plan_t p, double *out)
 int mi355x_spmv_csr_add(mi355x_handle_t h, mi355x_spmv_plan_t plan, const int *ai, const int *aj, const double *aa,
                         const double *x, const double *y, double *z) {
   return launch_spmv<1>(h, plan, ai, aj, aa, x, y, z);
+}
+
+// z = d .* (y + A x): one step of a Jacobi-sweep triangular solve with inverted pivots (x^j = dinv .* (y^k - Us x^(j-1)), A = -Us),
+// where mi355x_spmv_csr_add is the step of the unit triangle.  The plan's plain row-block kernel whatever else the plan holds:
+// rows of a block with <= SPMV_SEQ_AVG nonzeros per row on average are summed by one lane, s = y_r; s += a_j x_j in column order,
+// then d_r * s; longer rows by the family's lane tree.  z may alias y; x must not alias z.
+int mi355x_spmv_csr_add_scaled(mi355x_handle_t h, mi355x_spmv_plan_t plan, const int *ai, const int *aj, const double *aa,
+                               const double *x, const double *y, const double *d, double *z) {
+  if (!d || !y) return (int)hipErrorInvalidValue;
+  return launch_spmv<3>(h, plan, ai, aj, aa, x, y, z, d);
 }
 
 static int spmv_bsr_planned_impl(mi355x_handle_t h, mi355x_spmv_plan_t p, int bs, const int *ai, const int *aj,

@@ -279,9 +279,14 @@ static PetscErrorCode PCSetUp_BJacobi(PC pc) {
   for (PetscInt i = 0; i < nsolvers; i++) {
     if (nloc == 1) bj->block[0] = diag;
     else {
-      if (bj->block[i]) { ierr = MatDestroy(&bj->block[i]);CHKERRQ(ierr); }     /* values may have changed: extract again */
+      PetscInt carried = 0;
+      if (bj->block[i]) { carried = bj->block[i]->state + 1; ierr = MatDestroy(&bj->block[i]);CHKERRQ(ierr); }     /* values may have changed: extract again */
       if (bj->merged) { ierr = extract_block_diagonal(diag, nloc, bj->starts, &bj->block[0]);CHKERRQ(ierr); }
       else { ierr = extract_diagonal_block(diag, bj->starts[i], bj->starts[i + 1], &bj->block[i]);CHKERRQ(ierr); }
+      /* the reference extracts into the SAME matrix (MatGetSubMatrices, MAT_REUSE_MATRIX; bjacobi.c:1040) and its state moves on.  Here the block
+       * is a new object that may sit at the old one's address: its state continues the old one's, so that whoever remembers
+       * (matrix, state) -- the factored matrix, to skip a numeric factorisation of unchanged values -- sees the new values */
+      bj->block[i]->state += carried;
     }
     if (!bj->ksp[i]) {
       ierr = KSPCreate(PETSC_COMM_SELF, &bj->ksp[i]);CHKERRQ(ierr);

@@ -154,6 +154,12 @@ typedef struct {
   int by_level;                                            /* rows summed in dependency-level order (inode matrices) instead of column order */
   int block_columns;                                       /* node plans whose columns are whole dependency nodes */
   PetscInt nodes, nlevL_nodes, nlevU_nodes;                /* node-blocked plans (the factor of a matrix with inodes): nodes and their levels; 0: row-granular */
+  /* -pc_factor_hipmi355x_trisolve sweeps:<k>: k Jacobi sweeps per triangle instead of the exact solves (0: exact).  The negated
+   * strict triangles as CSR with their SpMV plans, the inverted pivots, two work vectors; sw_bi / sw_bj / sw_bdiag: the pattern they
+   * were built from (a numeric factorisation with the same pattern re-sends values only) */
+  PetscInt sweeps, sw_n, sw_nz, *sw_bi, *sw_bj, *sw_bdiag;
+  mi355x_spmv_plan_t sw_planL, sw_planU;
+  PetscInt *sw_iL, *sw_jL, *sw_iU, *sw_jU; PetscScalar *sw_aL, *sw_aU, *sw_dinv, *sw_work[2];
   int use_levels, aborted;                                 /* a sync-free application gave up: the same plans run level by level from now on */
   PetscInt nshift;                                         /* restarts / shifts the factorisation took (largest count over the blocks) */
   int factored_state; void *factored_of;                   /* operator and operator state of the last numeric factorisation */

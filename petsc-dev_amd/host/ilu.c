@@ -16,7 +16,9 @@
  *   solve   : MatSolve_SeqAIJ_NaturalOrdering (aijfact.c:3126) on the device, one lane per row in column order (same bits): by
  *             default two launches, one per triangular solve, with point-to-point hand-off of the solution values between
  *             wavefronts (mi355x_trisolve_*, csrc/trisolve.hip); -pc_factor_hipmi355x_trisolve level selects the level-scheduled
- *             kernels, one launch per dependency level (replayed from a hipGraph), which also serve systems with few levels. */
+ *             kernels, one launch per dependency level (replayed from a hipGraph), which also serve systems with few levels.
+ *             -pc_factor_hipmi355x_trisolve sweeps:<k> (opt-in, an APPROXIMATE application): k Jacobi sweeps per triangle, each one
+ *             SpMV-shaped product with the negated strict triangle (ilu0_sweeps_* below). */
 #include "hipmi355ximpl.h"
 #if defined(PETSCHIPMI355X_WITH_PETSC)
 #include <../src/mat/impls/aij/seq/aij.h>
@@ -62,10 +64,24 @@ PetscErrorCode HipTriWatchCheck(void) {
   return 0;
 }
 
+/* the device form of -pc_factor_hipmi355x_trisolve sweeps:<k> (it outlives a numeric factorisation: tri_reset_numeric leaves it) */
+static void ilu0_sweeps_free(HipTriFactors *f) {
+  void *dev[] = {f->sw_iL, f->sw_jL, f->sw_iU, f->sw_jU, f->sw_aL, f->sw_aU, f->sw_dinv, f->sw_work[0], f->sw_work[1]};
+  for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); i++) if (dev[i]) mi355x_free(dev[i]);
+  if (f->sw_planL) mi355x_spmv_plan_destroy(f->sw_planL);
+  if (f->sw_planU) mi355x_spmv_plan_destroy(f->sw_planU);
+  HipFree(f->sw_bi); HipFree(f->sw_bj); HipFree(f->sw_bdiag);
+  f->sw_iL = f->sw_jL = f->sw_iU = f->sw_jU = f->sw_bi = f->sw_bj = f->sw_bdiag = NULL;
+  f->sw_aL = f->sw_aU = f->sw_dinv = f->sw_work[0] = f->sw_work[1] = NULL;
+  f->sw_planL = f->sw_planU = NULL;
+  f->sweeps = 0;
+}
+
 PetscErrorCode HipTriFactorsDestroy(HipTriFactors **pf) {
   HipTriFactors *f = *pf;
   if (!f) return 0;
   tri_watch_remove(f);
+  ilu0_sweeps_free(f);
   if (f->owns_host) { HipFree(f->bi); HipFree(f->bj); HipFree(f->bdiag); HipFree(f->ba); }
   HipFree(f->levptrL); HipFree(f->levptrU); HipFree(f->blk); HipFree(f->rlevL); HipFree(f->rlevU);
   if (f->d_bi) mi355x_free(f->d_bi);
@@ -101,6 +117,7 @@ static void tri_reset_numeric(HipTriFactors *f) {
   f->d_bi = f->d_bj = f->d_bdiag = f->d_rowsL = f->d_rowsU = NULL; f->d_ba = f->d_work = NULL;
   f->graph = NULL; f->graph_tried = 0; f->tri_lo = f->tri_up = NULL;
   f->use_levels = 0; f->nshift = 0; f->nlevL = f->nlevU = 0;
+  f->sweeps = 0;                     /* (the sweep form's device arrays stay: the next factorisation may only have new values) */
   f->factored_state = -1;
 }
 
@@ -429,6 +446,112 @@ static void ilu0_row_arrays(void *c_, PetscInt lo, PetscInt hi) {
     c->rpU[i] = c->bdiag[i + 1] + 1; c->rlU[i] = c->bdiag[i] - c->bdiag[i + 1] - 1; c->dinv[i] = c->ba[c->bdiag[i]];
   }
 }
+/* -pc_factor_hipmi355x_trisolve sweeps:<k>.  With L = I + Ls and U = D + Us (dinv = D^-1 as the factor stores it),
+ *     lower:  y^0 = b             y^j = b - Ls y^(j-1)               j = 1..k
+ *     upper:  x^0 = dinv .* y^k   x^j = dinv .* (y^k - Us x^(j-1))   j = 1..k
+ * every step a product with a strict triangle that reads the previous iterate and writes the next one (two buffers, never in
+ * place: the same bits whatever the scheduling).  A row of dependency level l is final from sweep l on, so k >= levels - 1 IS the
+ * solve -- bit for bit where a row is summed by one lane, because s = b_i; s = s + (-l_ij) y_j in column order is the loop of
+ * MatSolve_SeqAIJ_NaturalOrdering.  Fewer sweeps: an approximate application, 2k SpMV-shaped passes instead of a chain of levels.
+ * Here: the negated strict triangles as CSR (the upper one taken out of the reference's backwards layout), their row-block
+ * plans, dinv and the two work vectors.  A factorisation with the pattern of the last one sends the values only. */
+typedef struct { const RowArr *ra; const PetscInt *bi, *bj, *iU; const PetscScalar *ba; PetscInt *jU; PetscScalar *aL, *aU; } SweepArr;
+static void ilu0_sweeps_rows(void *c_, PetscInt lo, PetscInt hi) {
+  SweepArr *c = (SweepArr *)c_;
+  for (PetscInt i = lo; i < hi; i++) {
+    for (PetscInt q = c->bi[i]; q < c->bi[i + 1]; q++) c->aL[q] = -c->ba[q];
+    for (PetscInt q = 0; q < c->ra->rlU[i]; q++) { c->jU[c->iU[i] + q] = c->bj[c->ra->rpU[i] + q]; c->aU[c->iU[i] + q] = -c->ba[c->ra->rpU[i] + q]; }
+  }
+}
+static PetscErrorCode ilu0_sweeps_upload(HipTriFactors *f, PetscDeviceCtx *dc) {
+  PetscErrorCode ierr;
+  const PetscInt n = f->n, nz = f->nz, *bi = f->bi, *bj = f->bj, *bdiag = f->bdiag;
+  const PetscInt nzL = bi[n], nzU = nz - nzL - n;
+  const size_t ni = sizeof(PetscInt) * (size_t)(n + 1), nj = sizeof(PetscInt) * (size_t)(nz + 1);
+  PetscInt *rlL, *rpU, *rlU, *iU, *jU; PetscScalar *dinv, *aL, *aU;
+  if (f->sw_planL && (f->sw_n != n || f->sw_nz != nz || memcmp(f->sw_bi, bi, ni) || memcmp(f->sw_bdiag, bdiag, ni) || memcmp(f->sw_bj, bj, nj))) ilu0_sweeps_free(f);
+  const int fresh = !f->sw_planL;
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(n, 1), &rlL);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(n, 1), &rpU);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(n, 1), &rlU);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(n, 1), &dinv);CHKERRQ(ierr);
+  ierr = PetscMalloc(ni, &iU);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nzU, 1), &jU);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(nzL, 1), &aL);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(nzU, 1), &aU);CHKERRQ(ierr);
+  RowArr ra = {bi, bdiag, f->ba, rlL, rpU, rlU, dinv};
+  HipParallelRanges(n, ilu0_row_arrays, &ra);
+  iU[0] = 0;
+  for (PetscInt i = 0; i < n; i++) iU[i + 1] = iU[i] + rlU[i];
+  { SweepArr sa = {&ra, bi, bj, iU, f->ba, jU, aL, aU};
+    HipParallelRanges(n, ilu0_sweeps_rows, &sa); }
+  int rc = 0;
+  if (fresh) {   /* (value and index arrays carry the 16 bytes of slack past their end that the row-block kernels' paired loads ask for) */
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_iL, ni);
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_iU, ni);
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_jL, sizeof(PetscInt) * (size_t)nzL + 16);
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_jU, sizeof(PetscInt) * (size_t)nzU + 16);
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_aL, sizeof(PetscScalar) * (size_t)nzL + 16);
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_aU, sizeof(PetscScalar) * (size_t)nzU + 16);
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_dinv, sizeof(PetscScalar) * (size_t)PetscMax(n, 1));
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_work[0], sizeof(PetscScalar) * (size_t)PetscMax(n, 1));
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_work[1], sizeof(PetscScalar) * (size_t)PetscMax(n, 1));
+    if (!rc) rc = mi355x_memcpy_h2d(dc->h, f->sw_iL, bi, ni);
+    if (!rc) rc = mi355x_memcpy_h2d(dc->h, f->sw_iU, iU, ni);
+    if (!rc && nzL) rc = mi355x_memcpy_h2d(dc->h, f->sw_jL, bj, sizeof(PetscInt) * (size_t)nzL);
+    if (!rc && nzU) rc = mi355x_memcpy_h2d(dc->h, f->sw_jU, jU, sizeof(PetscInt) * (size_t)nzU);
+    if (!rc) rc = mi355x_spmv_plan_create(dc->h, n, bi, NULL, &f->sw_planL);
+    if (!rc) rc = mi355x_spmv_plan_create(dc->h, n, iU, NULL, &f->sw_planU);
+  }
+  if (!rc && nzL) rc = mi355x_memcpy_h2d(dc->h, f->sw_aL, aL, sizeof(PetscScalar) * (size_t)nzL);
+  if (!rc && nzU) rc = mi355x_memcpy_h2d(dc->h, f->sw_aU, aU, sizeof(PetscScalar) * (size_t)nzU);
+  if (!rc && n) rc = mi355x_memcpy_h2d(dc->h, f->sw_dinv, dinv, sizeof(PetscScalar) * (size_t)n);
+  if (!rc) rc = mi355x_handle_synchronize(dc->h);      /* the host arrays go away below */
+  ierr = 0;
+  if (!rc && fresh) {
+    f->sw_n = n; f->sw_nz = nz;
+    ierr = PetscMalloc(ni, &f->sw_bi); if (!ierr) ierr = PetscMalloc(ni, &f->sw_bdiag); if (!ierr) ierr = PetscMalloc(nj, &f->sw_bj);
+    if (!ierr) { memcpy(f->sw_bi, bi, ni); memcpy(f->sw_bdiag, bdiag, ni); memcpy(f->sw_bj, bj, nj); }
+  }
+  HipFree(rlL); HipFree(rpU); HipFree(rlU); HipFree(dinv); HipFree(iU); HipFree(jU); HipFree(aL); HipFree(aU);
+  if (rc || ierr) ilu0_sweeps_free(f);
+  CHKHIP(rc);
+  CHKERRQ(ierr);
+  return 0;
+}
+
+/* x = (approximately) U^-1 L^-1 b: 2k products and one pointwise multiply on the compute stream, no host wait.  b is read by the
+ * lower sweeps only and x is first written after them, so b and x may be the same vector; the last upper step lands in x. */
+static PetscErrorCode ilu0_sweeps_apply(HipTriFactors *f, Vec b, Vec x) {
+  PetscErrorCode ierr;
+  const PetscScalar *db; PetscScalar *dx; PetscDeviceCtx *dc;
+  const PetscInt k = f->sweeps;
+  int rc = 0;
+  if (!f->n) return 0;
+  ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+  ierr = VecHIPGetRead(b, &db);CHKERRQ(ierr);
+  ierr = VecHIPGetWrite(x, &dx);CHKERRQ(ierr);
+  const PetscScalar *prev = db;
+  for (PetscInt j = 0; j < k && !rc; j++) {
+    PetscScalar *out = f->sw_work[j & 1];
+    rc = mi355x_spmv_csr_add(dc->h, f->sw_planL, f->sw_iL, f->sw_jL, f->sw_aL, prev, db, out);
+    prev = out;
+  }
+  const PetscScalar *yk = prev;
+  PetscScalar *spare = f->sw_work[k & 1], *cur = (k & 1) ? spare : dx;   /* x^0 where k steps of alternation end in dx */
+  if (!rc) rc = mi355x_vec_pointwise_mult(dc->h, (size_t)f->n, f->sw_dinv, yk, cur);
+  for (PetscInt j = 0; j < k && !rc; j++) {
+    PetscScalar *out = (cur == dx) ? spare : dx;
+    rc = mi355x_spmv_csr_add_scaled(dc->h, f->sw_planU, f->sw_iU, f->sw_jU, f->sw_aU, cur, yk, f->sw_dinv, out);
+    cur = out;
+  }
+  ierr = VecHIPRestoreWrite(x);CHKERRQ(ierr);
+  HipStateIncrease(x);
+  CHKHIP(rc);
+  ierr = PetscLogFlops((PetscLogDouble)k * (2.0 * f->nz - f->n));CHKERRQ(ierr);
+  return 0;
+}
+
 /* dependency levels of the two triangular factors, the sync-free plans, the level lists: everything MatSolve needs, from the
  * host factor in f->bi / bj / bdiag / ba (the reference's layout, whoever computed it) */
 static PetscErrorCode ilu0_analyse_and_upload(Mat F, Mat A) {
@@ -445,7 +568,21 @@ static PetscErrorCode ilu0_analyse_and_upload(Mat F, Mat A) {
   {   /* sync-free solves: worth it as soon as the level launches would be a launch-bound chain */
     char mode[32] = "syncfree"; PetscBool set;
     ierr = PetscOptionsGetString(HipObjPrefix(F), "-pc_factor_hipmi355x_trisolve", mode, sizeof(mode), &set);CHKERRQ(ierr);
-    if (strcmp(mode, "syncfree") && strcmp(mode, "level")) SETERRQ(HipObjComm(F), PETSC_ERR_ARG_WRONG, "-pc_factor_hipmi355x_trisolve <syncfree|level>, got %s", mode);
+    PetscInt sweeps = 0;
+    if (!strncmp(mode, "sweeps", 6)) {   /* sweeps:<k>, k >= 1; there is no default count */
+      char *end = mode + 7; long k = 0;
+      if (mode[6] == ':' && mode[7] >= '0' && mode[7] <= '9') k = strtol(mode + 7, &end, 10);
+      if (k < 1 || k > 1000000 || *end) SETERRQ(HipObjComm(F), PETSC_ERR_ARG_WRONG, "-pc_factor_hipmi355x_trisolve sweeps:<k> needs an integer k >= 1, got %s", mode);
+      sweeps = (PetscInt)k;
+    } else if (strcmp(mode, "syncfree") && strcmp(mode, "level")) SETERRQ(HipObjComm(F), PETSC_ERR_ARG_WRONG, "-pc_factor_hipmi355x_trisolve <syncfree|level|sweeps:<k>>, got %s", mode);
+    if (!sweeps) ilu0_sweeps_free(f);
+    else {   /* no sync-free plans, no level lists, not on the watch list: the level counts above are all the analysis this mode keeps */
+      ierr = ilu0_sweeps_upload(f, dc);
+      HipFree(lev); HipFree(levU);
+      CHKERRQ(ierr);
+      f->sweeps = sweeps;
+      return 0;
+    }
     if (!strcmp(mode, "syncfree") && n > 0 && (f->nlevL + f->nlevU > 16 || set)) {
       PetscInt *rpU, *rlU, *rlL; PetscScalar *dinv;
       ierr = PetscMalloc(sizeof(PetscInt) * (size_t)n, &rpU);CHKERRQ(ierr);
@@ -550,7 +687,7 @@ static PetscErrorCode MatLUFactorNumeric_SeqAIJHIP(Mat F, Mat A, const MatFactor
   HipTriFactors *f = HipTriGet(F);
   const double t0 = wall_s();
   if (A->rmap->n != A->cmap->n) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "Must be square matrix, rows %d columns %d", A->rmap->n, A->cmap->n);
-  if (f->factored_state == HipObjState(A) && f->factored_of == (void *)A && (f->tri_lo || f->d_ba)) return 0;   /* same operator, same values: nothing to redo */
+  if (f->factored_state == HipObjState(A) && f->factored_of == (void *)A && (f->tri_lo || f->d_ba || f->sweeps)) return 0;   /* same operator, same values: nothing to redo */
   tri_reset_numeric(f);
 #if defined(PETSCHIPMI355X_WITH_PETSC)
   ierr = MatLUFactorNumeric_SeqAIJ(F, A, info);CHKERRQ(ierr);            /* the parent's factorisation into F's own Mat_SeqAIJ */
@@ -612,6 +749,7 @@ static PetscErrorCode MatSolve_SeqAIJHIP_ILU(Mat F, Vec b, Vec x) {   /* MatSolv
   PetscErrorCode ierr;
   HipTriFactors *f = HipTriGet(F);
   const PetscScalar *db; PetscScalar *dx; PetscDeviceCtx *dc;
+  if (f->sweeps) return ilu0_sweeps_apply(f, b, x);
   if (f->tri_lo) return HipTriFactorsApply(F, f, b, x, 2.0 * f->nz - f->n);
   ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
   ierr = VecHIPGetRead(b, &db);CHKERRQ(ierr);
@@ -715,6 +853,23 @@ PetscErrorCode PCILUGetSolver_HIPMI355X(PC pc, PetscInt *syncfree, PetscInt *abo
     mi355x_trisolve_aborted(f->tri_lo, &a); mi355x_trisolve_aborted(f->tri_up, &b);
   }
   if (aborted) *aborted = a || b || f->aborted;
+  return 0;
+}
+/* Jacobi sweeps per triangular solve (-pc_factor_hipmi355x_trisolve sweeps:<k>); 0: the factor solves exactly */
+PetscErrorCode PCILUGetSweeps_HIPMI355X(PC pc, PetscInt *k) {
+  HipTriFactors *f;
+  PetscErrorCode ierr = pc_factors(pc, MAT_FACTOR_ILU, &f);CHKERRQ(ierr);
+  *k = f->sweeps;
+  return 0;
+}
+/* v <- the factor's application to v, input and result in ONE vector.  PCApply and MatSolve refuse identical vectors as the
+ * reference's do (precon.c:380, matrix.c:3205); the sweep form is written to work in place (its iterates live in work vectors)
+ * and this is the way to it.  The exact solves are not offered in place. */
+PetscErrorCode PCILUApplyInPlace_HIPMI355X(PC pc, Vec v) {
+  HipTriFactors *f;
+  PetscErrorCode ierr = pc_factors(pc, MAT_FACTOR_ILU, &f);CHKERRQ(ierr);
+  if (!f->sweeps) SETERRQ(HipObjComm(pc), PETSC_ERR_SUP, "in place only with -pc_factor_hipmi355x_trisolve sweeps:<k>");
+  ierr = ilu0_sweeps_apply(f, v, v);CHKERRQ(ierr);
   return 0;
 }
 /* restarts of the factorisation with a larger diagonal shift (MAT_SHIFT_NONZERO); 0 for every matrix whose pivots pass */
