@@ -325,6 +325,32 @@ int mi355x_ilu0_lower_level(mi355x_handle_t h, int nrows, const int *rows, const
 int mi355x_ilu0_upper_level(mi355x_handle_t h, int nrows, const int *rows, const int *bj, const double *ba,
                             const int *bdiag, double *x);
 
+/* ---- ILU(0) numeric factorisation, level by level (csrc/ilu_factor.hip) ------------------------------------------------------
+ * MatLUFactorNumeric_SeqAIJ  src/mat/impls/aij/seq/aijfact.c:505-570 with the restarts of MatPivotCheck_nz (matimpl.h:512-528), on
+ * the layout of MatILUFactorSymbolic_SeqAIJ_ilu0 (:1628-1700): one launch per dependency level of L, a power-of-two number of lanes
+ * per row (chosen from the widest row), every row's arithmetic the sequential loop's -- ba carries the reference's bits.
+ *   _create   once per pattern, from HOST arrays: the factor's bi / bj / bdiag, the rows sorted by dependency level of L (levptr[nlev + 1],
+ *             rows[n]), the independent blocks (blk[nblk + 1] row ranges; nblk <= 1: one block).  The layout is checked
+ *             (hipErrorInvalidValue); a creator that fails frees what it allocated.
+ *   _reset    a new numeric factorisation starts: every block is pending again
+ *   _run      one pass over the blocks still pending.  ai / aj / aa: A's CSR on the device (the pattern the factor's was taken from),
+ *             ba: the factor's nz + 1 values on the device, shift_per_block[nblk] (host) the diagonal shifts.  Returns after one host
+ *             wait with failed_row[b] (host; -1: the block passed and is no longer pending) and failed_abs[b] = |pivot| of that row.
+ *   _arrays   the context's device copies (bi, bj, bdiag, rows in level order), borrowed: they live as long as the context
+ *   _to_sweeps  the sweep form of the factor (mi355x_spmv_csr_add / _add_scaled above): aL = -ba over the L part, aU / dinv through
+ *             the row pointers iU (device) of the strict upper triangle as CSR
+ *   _info     lanes per row, levels */
+typedef struct mi355x_ilu0_factor_s *mi355x_ilu0_factor_t;
+int mi355x_ilu0_factor_create(mi355x_handle_t h, int n, const int *bi, const int *bj, const int *bdiag, int nlev, const int *levptr,
+                              const int *rows, int nblk, const int *blk, mi355x_ilu0_factor_t *ctx);
+int mi355x_ilu0_factor_destroy(mi355x_ilu0_factor_t ctx);
+int mi355x_ilu0_factor_reset(mi355x_ilu0_factor_t ctx);
+int mi355x_ilu0_factor_run(mi355x_handle_t h, mi355x_ilu0_factor_t ctx, const int *ai, const int *aj, const double *aa, double zeropivot,
+                           const double *shift_per_block, double *ba, int *failed_row, double *failed_abs);
+int mi355x_ilu0_factor_arrays(mi355x_ilu0_factor_t ctx, const int **bi, const int **bj, const int **bdiag, const int **rows);
+int mi355x_ilu0_factor_to_sweeps(mi355x_handle_t h, mi355x_ilu0_factor_t ctx, const int *iU, const double *ba, double *aL, double *aU, double *dinv);
+int mi355x_ilu0_factor_info(mi355x_ilu0_factor_t ctx, int *lanes, int *nlev);
+
 /* The same two solves WITHOUT a kernel boundary per level: one launch per triangular solve, rows sorted by level and
  * stored as sliced ELL (one wavefront per 64 rows), dependencies handed over through the solution values themselves
  * (a sentinel bit pattern means "not computed yet"; write-through stores, polling loads).  Same one-lane-per-row,

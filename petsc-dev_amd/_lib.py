@@ -132,6 +132,13 @@ KERNEL_API = {
     "mi355x_spmv_bsr_planned_form": [vp, vp, i32, i32, vp, vp, vp, vp, vp],
     "mi355x_ilu0_lower_level": [vp, i32, vp, vp, vp, vp, vp, vp],
     "mi355x_ilu0_upper_level": [vp, i32, vp, vp, vp, vp, vp],
+    "mi355x_ilu0_factor_create": [vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, C.POINTER(vp)],
+    "mi355x_ilu0_factor_destroy": [vp],
+    "mi355x_ilu0_factor_reset": [vp],
+    "mi355x_ilu0_factor_run": [vp, vp, vp, vp, vp, dbl, vp, vp, vp, vp],
+    "mi355x_ilu0_factor_arrays": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
+    "mi355x_ilu0_factor_to_sweeps": [vp, vp, vp, vp, vp, vp, vp],
+    "mi355x_ilu0_factor_info": [vp, pi32, pi32],
     "mi355x_pack": [vp, sz, vp, vp, vp],
     "mi355x_unpack_insert": [vp, sz, vp, vp, vp],
     "mi355x_unpack_add": [vp, sz, vp, vp, vp],

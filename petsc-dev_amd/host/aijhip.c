@@ -13,7 +13,8 @@ PetscErrorCode MatSeqAIJGetArrays(Mat A, PetscInt *m, const PetscInt **i, const 
 static PetscErrorCode device_free(Mat A);
 static PetscBool device_values_current(Mat A);
 /* the device copy is to be built again from the host at its next use */
-static void mirror_reset(Mat_SeqAIJHIP *d) { d->uploaded_state = -1; d->pattern_nz = -1; }
+static unsigned long long pattern_serial = 0;   /* pattern uploads so far, over all matrices */
+static void mirror_reset(Mat_SeqAIJHIP *d) { d->uploaded_state = -1; d->pattern_nz = -1; d->pattern_gen = 0; }
 
 #if !defined(PETSCHIPMI355X_WITH_PETSC)   /* inside a PETSc tree the parent type MATSEQAIJ owns the container and its assembly (aij.c) */
 /* ---------------------------------------------------------------- host container */
@@ -414,7 +415,7 @@ static PetscErrorCode upload_pattern(Mat A, PetscDeviceCtx *dc, UpTick *tk) {
     if ((double)a->nz * a->bs * a->bs > 2147483000.0) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_OUTOFRANGE, "BAIJ matrix too large for 32-bit value offsets");
     ierr = form_upload(dc, &d->mat, a->m, a->bs, a->i, a->j, NULL, NULL);CHKERRQ(ierr);
     up_tick(tk, dc, "row pointer and columns up");
-    d->pattern_nz = a->nz; d->cprow = PETSC_FALSE;
+    d->pattern_nz = a->nz; d->pattern_gen = ++pattern_serial; d->cprow = PETSC_FALSE;
     return 0;
   }
   PetscInt m = a->m, nrows = m;
@@ -492,7 +493,7 @@ static PetscErrorCode upload_pattern(Mat A, PetscDeviceCtx *dc, UpTick *tk) {
   }
   CHKHIP(mi355x_handle_synchronize(dc->h));
   HipFree(ci); HipFree(ridx);
-  d->pattern_nz = a->nz;
+  d->pattern_nz = a->nz; d->pattern_gen = ++pattern_serial;
   if (!use_cprow) d->cprow = PETSC_FALSE;
   return 0;
 }

@@ -160,6 +160,14 @@ typedef struct {
   PetscInt sweeps, sw_n, sw_nz, *sw_bi, *sw_bj, *sw_bdiag;
   mi355x_spmv_plan_t sw_planL, sw_planU;
   PetscInt *sw_iL, *sw_jL, *sw_iU, *sw_jU; PetscScalar *sw_aL, *sw_aU, *sw_dinv, *sw_work[2];
+  /* -pc_factor_hipmi355x_numeric device: the numeric factorisation runs on the device (mi355x_ilu0_factor_*), level by level, into d_ba.
+   * The context is built once per pattern; with it stay the host pattern (bi / bj / bdiag), the row levels (rlevL / rlevU) and, borrowed
+   * from it for the level-launch solves, d_bi / d_bj / d_bdiag / d_rowsL (d_borrowed: not ours to free).  dfac_gen / dfac_n / dfac_nz:
+   * the serial number of the operator's pattern upload (Mat_SeqAIJHIP.pattern_gen) and its sizes at the time -- what "the pattern of the
+   * last factorisation" is told by */
+  mi355x_ilu0_factor_t dfac; int d_borrowed, dfac_stale;
+  unsigned long long dfac_gen; PetscInt dfac_n, dfac_nz, dfac_nblk, *dfac_blk;
+  PetscInt symbolic_builds, numeric_runs;                  /* host symbolic passes / numeric factorisations so far (both routes) */
   int use_levels, aborted;                                 /* a sync-free application gave up: the same plans run level by level from now on */
   PetscInt nshift;                                         /* restarts / shifts the factorisation took (largest count over the blocks) */
   int factored_state; void *factored_of;                   /* operator and operator state of the last numeric factorisation */
@@ -204,6 +212,8 @@ typedef struct {
   PetscBool cprow;            /* compressed-row form requested (off-diagonal block) */
   PetscBool baij4_mfma;       /* BAIJ bs = 4: MatMult on the matrix cores (mi355x_spmv_bsr4_mfma) */
   PetscInt pattern_nz;        /* nz of the pattern the mirror was built for (-1: none) */
+  unsigned long long pattern_gen;   /* serial number of that pattern upload, unique in the process over all matrices (0: none): what a
+                                     * consumer that keeps pattern-derived state compares, never addresses (host/ilu.c, the device route) */
   HipDevForm t;               /* cached explicit transpose for MatMultTranspose (perm: position in A^T -> position in A); its column-tiled
                                * layout is built when the matrix itself took that form */
   PetscInt t_builds, t_refreshes;   /* host builds / device refreshes so far */

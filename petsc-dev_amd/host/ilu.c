@@ -77,11 +77,21 @@ static void ilu0_sweeps_free(HipTriFactors *f) {
   f->sweeps = 0;
 }
 
+/* the device route's state (-pc_factor_hipmi355x_numeric device): the context of one pattern and what the level-launch solves borrow from it */
+static void ilu0_device_free(HipTriFactors *f) {
+  if (f->d_borrowed) { f->d_bi = f->d_bj = f->d_bdiag = f->d_rowsL = NULL; f->d_borrowed = 0; }
+  if (f->dfac) mi355x_ilu0_factor_destroy(f->dfac);
+  HipFree(f->dfac_blk);
+  f->dfac = NULL; f->dfac_blk = NULL; f->dfac_gen = 0; f->dfac_stale = 0;
+}
+
 PetscErrorCode HipTriFactorsDestroy(HipTriFactors **pf) {
   HipTriFactors *f = *pf;
   if (!f) return 0;
   tri_watch_remove(f);
   ilu0_sweeps_free(f);
+  if (f->graph) { mi355x_graph_destroy(f->graph); f->graph = NULL; }   /* (it names the arrays the context owns) */
+  ilu0_device_free(f);
   if (f->owns_host) { HipFree(f->bi); HipFree(f->bj); HipFree(f->bdiag); HipFree(f->ba); }
   HipFree(f->levptrL); HipFree(f->levptrU); HipFree(f->blk); HipFree(f->rlevL); HipFree(f->rlevU);
   if (f->d_bi) mi355x_free(f->d_bi);
@@ -91,7 +101,6 @@ PetscErrorCode HipTriFactorsDestroy(HipTriFactors **pf) {
   if (f->d_rowsL) mi355x_free(f->d_rowsL);
   if (f->d_rowsU) mi355x_free(f->d_rowsU);
   if (f->d_work) mi355x_free(f->d_work);
-  if (f->graph) mi355x_graph_destroy(f->graph);
   if (f->tri_lo) mi355x_trisolve_plan_destroy(f->tri_lo);
   if (f->tri_up) mi355x_trisolve_plan_destroy(f->tri_up);
   HipFree(f);
@@ -100,6 +109,8 @@ PetscErrorCode HipTriFactorsDestroy(HipTriFactors **pf) {
 }
 /* forget one numeric factorisation (the symbolic choices, the block list and the watch slot stay) */
 static void tri_reset_numeric(HipTriFactors *f) {
+  if (f->graph) { mi355x_graph_destroy(f->graph); f->graph = NULL; }
+  ilu0_device_free(f);
   if (f->owns_host) { HipFree(f->bi); HipFree(f->bj); HipFree(f->bdiag); HipFree(f->ba); }
   f->bi = f->bj = f->bdiag = NULL; f->ba = NULL;
   HipFree(f->levptrL); HipFree(f->levptrU); f->levptrL = f->levptrU = NULL;
@@ -111,7 +122,6 @@ static void tri_reset_numeric(HipTriFactors *f) {
   if (f->d_rowsL) mi355x_free(f->d_rowsL);
   if (f->d_rowsU) mi355x_free(f->d_rowsU);
   if (f->d_work) mi355x_free(f->d_work);
-  if (f->graph) mi355x_graph_destroy(f->graph);
   if (f->tri_lo) mi355x_trisolve_plan_destroy(f->tri_lo);
   if (f->tri_up) mi355x_trisolve_plan_destroy(f->tri_up);
   f->d_bi = f->d_bj = f->d_bdiag = f->d_rowsL = f->d_rowsU = NULL; f->d_ba = f->d_work = NULL;
@@ -169,7 +179,7 @@ static PetscErrorCode natural_ordering_only(Mat A, IS row, IS col, const MatFact
 
 #include <time.h>
 static double wall_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
-#define SETUP_TICK(what) do { if (getenv("PETSC_HIPMI355X_SETUP_TIMING")) { const double t__ = wall_s(); fprintf(stderr, "[hipmi355x]   %-34s %.3f s\n", what, t__ - tick0); tick0 = t__; } } while (0)
+#define SETUP_TICK(what) do { if (getenv("PETSC_HIPMI355X_SETUP_TIMING")) { const double t__ = wall_s(); fprintf(stderr, "[hipmi355x]   %-34s %.6f s\n", what, t__ - tick0); tick0 = t__; } } while (0)
 
 #include <pthread.h>
 #include <unistd.h>
@@ -469,7 +479,7 @@ static PetscErrorCode ilu0_sweeps_upload(HipTriFactors *f, PetscDeviceCtx *dc) {
   const PetscInt nzL = bi[n], nzU = nz - nzL - n;
   const size_t ni = sizeof(PetscInt) * (size_t)(n + 1), nj = sizeof(PetscInt) * (size_t)(nz + 1);
   PetscInt *rlL, *rpU, *rlU, *iU, *jU; PetscScalar *dinv, *aL, *aU;
-  if (f->sw_planL && (f->sw_n != n || f->sw_nz != nz || memcmp(f->sw_bi, bi, ni) || memcmp(f->sw_bdiag, bdiag, ni) || memcmp(f->sw_bj, bj, nj))) ilu0_sweeps_free(f);
+  if (f->sw_planL && (!f->sw_bi || f->sw_n != n || f->sw_nz != nz || memcmp(f->sw_bi, bi, ni) || memcmp(f->sw_bdiag, bdiag, ni) || memcmp(f->sw_bj, bj, nj))) ilu0_sweeps_free(f);
   const int fresh = !f->sw_planL;
   ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(n, 1), &rlL);CHKERRQ(ierr);
   ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(n, 1), &rpU);CHKERRQ(ierr);
@@ -552,6 +562,58 @@ static PetscErrorCode ilu0_sweeps_apply(HipTriFactors *f, Vec b, Vec x) {
   return 0;
 }
 
+/* the device factor's values on the host (the sync-free plans' creators read them there; inside PETSc the parent's b->a) */
+static PetscErrorCode ilu0_fetch_host_ba(HipTriFactors *f, PetscDeviceCtx *dc) {
+  PetscErrorCode ierr;
+  if (!f->ba) { ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)(f->nz + 1), &f->ba);CHKERRQ(ierr); }
+  CHKHIP(mi355x_memcpy_d2h(dc->h, f->ba, f->d_ba, sizeof(PetscScalar) * (size_t)(f->nz + 1)));
+  CHKHIP(mi355x_handle_synchronize(dc->h));
+  return 0;
+}
+/* the sweep form from a factor whose values are on the device: pattern arrays and plans once per pattern (the device route forgets
+ * them when the pattern changes), the values by two small kernels from d_ba */
+static PetscErrorCode ilu0_sweeps_from_device(HipTriFactors *f, PetscDeviceCtx *dc) {
+  PetscErrorCode ierr;
+  const PetscInt n = f->n, nz = f->nz, *bi = f->bi, *bj = f->bj, *bdiag = f->bdiag;
+  const PetscInt nzL = bi[n], nzU = nz - nzL - n;
+  const size_t ni = sizeof(PetscInt) * (size_t)(n + 1);
+  int rc = 0;
+  if (f->sw_planL && (f->sw_bi || f->sw_n != n || f->sw_nz != nz)) ilu0_sweeps_free(f);   /* (left by the host route, or by another pattern) */
+  if (!f->sw_planL) {
+    PetscInt *iU, *jU;
+    ierr = PetscMalloc(ni, &iU);CHKERRQ(ierr);
+    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nzU, 1), &jU);CHKERRQ(ierr);
+    iU[0] = 0;
+    for (PetscInt i = 0; i < n; i++) {
+      const PetscInt nu = bdiag[i] - bdiag[i + 1] - 1;
+      memcpy(jU + iU[i], bj + bdiag[i + 1] + 1, sizeof(PetscInt) * (size_t)nu);
+      iU[i + 1] = iU[i] + nu;
+    }
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_iL, ni);
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_iU, ni);
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_jL, sizeof(PetscInt) * (size_t)nzL + 16);
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_jU, sizeof(PetscInt) * (size_t)nzU + 16);
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_aL, sizeof(PetscScalar) * (size_t)nzL + 16);
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_aU, sizeof(PetscScalar) * (size_t)nzU + 16);
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_dinv, sizeof(PetscScalar) * (size_t)PetscMax(n, 1));
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_work[0], sizeof(PetscScalar) * (size_t)PetscMax(n, 1));
+    if (!rc) rc = mi355x_malloc((void **)&f->sw_work[1], sizeof(PetscScalar) * (size_t)PetscMax(n, 1));
+    if (!rc) rc = mi355x_memcpy_h2d(dc->h, f->sw_iL, bi, ni);
+    if (!rc) rc = mi355x_memcpy_h2d(dc->h, f->sw_iU, iU, ni);
+    if (!rc && nzL) rc = mi355x_memcpy_h2d(dc->h, f->sw_jL, bj, sizeof(PetscInt) * (size_t)nzL);
+    if (!rc && nzU) rc = mi355x_memcpy_h2d(dc->h, f->sw_jU, jU, sizeof(PetscInt) * (size_t)nzU);
+    if (!rc) rc = mi355x_spmv_plan_create(dc->h, n, bi, NULL, &f->sw_planL);
+    if (!rc) rc = mi355x_spmv_plan_create(dc->h, n, iU, NULL, &f->sw_planU);
+    if (!rc) rc = mi355x_handle_synchronize(dc->h);
+    HipFree(iU); HipFree(jU);
+    f->sw_n = n; f->sw_nz = nz;
+  }
+  if (!rc) rc = mi355x_ilu0_factor_to_sweeps(dc->h, f->dfac, f->sw_iU, f->d_ba, f->sw_aL, f->sw_aU, f->sw_dinv);
+  if (rc) ilu0_sweeps_free(f);
+  CHKHIP(rc);
+  return 0;
+}
+
 /* dependency levels of the two triangular factors, the sync-free plans, the level lists: everything MatSolve needs, from the
  * host factor in f->bi / bj / bdiag / ba (the reference's layout, whoever computed it) */
 static PetscErrorCode ilu0_analyse_and_upload(Mat F, Mat A) {
@@ -561,7 +623,9 @@ static PetscErrorCode ilu0_analyse_and_upload(Mat F, Mat A) {
   PetscDeviceCtx *dc;
   PetscInt *lev, *levU, *rowsL = NULL, *rowsU = NULL;
   const double ta0 = wall_s();
-  if (f->rlevL && f->rlevU) { lev = f->rlevL; levU = f->rlevU; f->rlevL = f->rlevU = NULL; }   /* the host factorisation's own analysis */
+  const int from_device = f->dfac != NULL;   /* the factor's values are in d_ba; the row levels stay with the factor (the next factorisation of this pattern analyses nothing) */
+  if (from_device) { lev = f->rlevL; levU = f->rlevU; }
+  else if (f->rlevL && f->rlevU) { lev = f->rlevL; levU = f->rlevU; f->rlevL = f->rlevU = NULL; }   /* the host factorisation's own analysis */
   else { ierr = ilu0_row_levels(n, bi, bj, bdiag, &lev, &f->nlevL, &levU, &f->nlevU);CHKERRQ(ierr); }
   if (getenv("PETSC_HIPMI355X_SETUP_TIMING")) fprintf(stderr, "[hipmi355x] ILU(0): row levels %.3f s\n", wall_s() - ta0);
   ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
@@ -577,6 +641,7 @@ static PetscErrorCode ilu0_analyse_and_upload(Mat F, Mat A) {
     } else if (strcmp(mode, "syncfree") && strcmp(mode, "level")) SETERRQ(HipObjComm(F), PETSC_ERR_ARG_WRONG, "-pc_factor_hipmi355x_trisolve <syncfree|level|sweeps:<k>>, got %s", mode);
     if (!sweeps) ilu0_sweeps_free(f);
     else {   /* no sync-free plans, no level lists, not on the watch list: the level counts above are all the analysis this mode keeps */
+      if (from_device) { ierr = ilu0_sweeps_from_device(f, dc);CHKERRQ(ierr); f->sweeps = sweeps; return 0; }
       ierr = ilu0_sweeps_upload(f, dc);
       HipFree(lev); HipFree(levU);
       CHKERRQ(ierr);
@@ -585,6 +650,12 @@ static PetscErrorCode ilu0_analyse_and_upload(Mat F, Mat A) {
     }
     if (!strcmp(mode, "syncfree") && n > 0 && (f->nlevL + f->nlevU > 16 || set)) {
       PetscInt *rpU, *rlU, *rlL; PetscScalar *dinv;
+      if (from_device) {   /* the plans' creators take the values from the host: the factor's one copy back */
+        const double tf0 = wall_s();
+        if (f->owns_host) { ierr = ilu0_fetch_host_ba(f, dc);CHKERRQ(ierr); }   /* (inside PETSc the parent's array already holds it) */
+        ba = f->ba;
+        if (getenv("PETSC_HIPMI355X_SETUP_TIMING")) fprintf(stderr, "[hipmi355x] ILU(0): ... factor values back on the host %.3f s\n", wall_s() - tf0);
+      }
       ierr = PetscMalloc(sizeof(PetscInt) * (size_t)n, &rpU);CHKERRQ(ierr);
       ierr = PetscMalloc(sizeof(PetscInt) * (size_t)n, &rlU);CHKERRQ(ierr);
       ierr = PetscMalloc(sizeof(PetscInt) * (size_t)n, &rlL);CHKERRQ(ierr);
@@ -659,7 +730,19 @@ static PetscErrorCode ilu0_analyse_and_upload(Mat F, Mat A) {
       } else HipTriWatchAdd(f);
     }
   }
-  if (!f->tri_lo) {   /* the level-scheduled kernels work on the reference's layout itself, rows listed level by level */
+  if (!f->tri_lo && from_device) {   /* the level launches read d_ba itself; the index arrays and the rows of L by level are the context's */
+    if (!f->d_rowsU) {               /* (a factorisation with the pattern of the last one finds all of it in place, the captured graph included) */
+      const int *cbi, *cbj, *cbd, *crows;
+      HipFree(f->levptrL); HipFree(f->levptrU); f->levptrL = f->levptrU = NULL;
+      ierr = level_order(n, lev, f->nlevL, &f->levptrL, &rowsL);CHKERRQ(ierr);
+      ierr = level_order(n, levU, f->nlevU, &f->levptrU, &rowsU);CHKERRQ(ierr);
+      CHKHIP(mi355x_ilu0_factor_arrays(f->dfac, &cbi, &cbj, &cbd, &crows));
+      f->d_bi = (PetscInt *)cbi; f->d_bj = (PetscInt *)cbj; f->d_bdiag = (PetscInt *)cbd; f->d_rowsL = (PetscInt *)crows; f->d_borrowed = 1;
+      CHKHIP(mi355x_malloc((void **)&f->d_rowsU, sizeof(PetscInt) * (size_t)PetscMax(n, 1)));
+      CHKHIP(mi355x_memcpy_h2d(dc->h, f->d_rowsU, rowsU, sizeof(PetscInt) * (size_t)n));
+      CHKHIP(mi355x_handle_synchronize(dc->h));
+    }
+  } else if (!f->tri_lo) {   /* the level-scheduled kernels work on the reference's layout itself, rows listed level by level */
     ierr = level_order(n, lev, f->nlevL, &f->levptrL, &rowsL);CHKERRQ(ierr);
     ierr = level_order(n, levU, f->nlevU, &f->levptrU, &rowsU);CHKERRQ(ierr);
     CHKHIP(mi355x_malloc((void **)&f->d_bi, sizeof(PetscInt) * (size_t)(n + 1)));
@@ -676,7 +759,126 @@ static PetscErrorCode ilu0_analyse_and_upload(Mat F, Mat A) {
     CHKHIP(mi355x_memcpy_h2d(dc->h, f->d_rowsU, rowsU, sizeof(PetscInt) * (size_t)n));
     CHKHIP(mi355x_handle_synchronize(dc->h));
   }
-  HipFree(rowsL); HipFree(rowsU); HipFree(lev); HipFree(levU);
+  HipFree(rowsL); HipFree(rowsU);
+  if (!from_device) { HipFree(lev); HipFree(levU); }
+  return 0;
+}
+
+/* -pc_factor_hipmi355x_numeric device: the numeric ILU(0) on the device, one launch per dependency level of L
+ * (mi355x_ilu0_factor_*, csrc/ilu_factor.hip), reading A's device copy in place and writing the factor's values to d_ba.  The
+ * symbolic work -- diagonal positions, pattern of L and U, row levels -- stays on the host and is kept with the factor: a
+ * factorisation whose A has the pattern of the last one (the same upload of the operator's pattern, Mat_SeqAIJHIP.pattern_gen -- a serial number no other matrix or
+ * later pattern shares -- with the same sizes and the same independent blocks) runs the numeric kernels only.  The shift loop is
+ * ilu0_factor_host's, per independent block: a block whose pass reports a failing pivot runs again with shiftamount, then twice
+ * that, ... (MatPivotCheck_nz, matimpl.h:512-528); the other blocks' rows skip their work in those passes. */
+static PetscErrorCode ilu0_factor_device(Mat F, Mat A, const MatFactorInfo *info) {
+  PetscErrorCode ierr;
+  HipTriFactors *f = HipTriGet(F);
+  Mat_SeqAIJHIP *d = (Mat_SeqAIJHIP *)A->spptr;
+  PetscDeviceCtx *dc;
+  PetscInt n; const PetscInt *ai, *aj; const PetscScalar *aa;
+  double tick0 = wall_s();
+  ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+  ierr = MatSeqAIJGetArrays(A, &n, &ai, &aj, &aa);CHKERRQ(ierr);
+  (void)aa;                                                               /* (the values are read on the device) */
+  ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
+  if (d->cprow || d->mat.bs != 1 || (n > 0 && !d->mat.a)) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "-pc_factor_hipmi355x_numeric device needs the operator's plain CSR copy on the device");
+  SETUP_TICK("factor (device): operator current");
+  const PetscInt whole[2] = {0, n};
+  const int blocked = f->nblk > 0 && f->blk[f->nblk] == n;
+  const PetscInt nblk = blocked ? f->nblk : 1, *blk = blocked ? f->blk : whole;
+  const int same = f->dfac && !f->dfac_stale && d->pattern_gen && f->dfac_gen == d->pattern_gen && f->dfac_n == n && f->dfac_nz == ai[n] &&
+                   f->dfac_nblk == nblk && !memcmp(f->dfac_blk, blk, sizeof(PetscInt) * (size_t)(nblk + 1));
+  f->factored_state = -1;
+  if (same) {   /* values only: the plans that carry values go, everything built from the pattern stays */
+    if (f->tri_lo) mi355x_trisolve_plan_destroy(f->tri_lo);
+    if (f->tri_up) mi355x_trisolve_plan_destroy(f->tri_up);
+    f->tri_lo = f->tri_up = NULL; f->use_levels = 0; f->nshift = 0; f->sweeps = 0;
+  } else {
+    PetscInt *levptr = NULL, *rows = NULL;
+    tri_reset_numeric(f);
+    ilu0_sweeps_free(f);
+    f->n = n; f->nz = ai[n];
+#if defined(PETSCHIPMI355X_WITH_PETSC)
+    { Mat_SeqAIJ *b = (Mat_SeqAIJ *)F->data;   /* the parent's symbolic arrays (MatILUFactorSymbolic_SeqAIJ_ilu0) */
+      f->nz = b->nz; f->bi = b->i; f->bj = b->j; f->bdiag = b->diag; f->ba = b->a; f->owns_host = PETSC_FALSE; }
+#else
+    { PetscInt *adiag;
+      f->owns_host = PETSC_TRUE;
+      ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(n, 1), &adiag);CHKERRQ(ierr);
+      IluSym sy = {ai, aj, adiag, NULL, NULL, NULL, -1};
+      HipParallelRanges(n, ilu0_sym_diag, &sy);
+      if (sy.missing >= 0) {
+        PetscInt first = 0;
+        while (first < n && adiag[first] >= 0) first++;
+        HipFree(adiag);
+        SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "Matrix is missing diagonal entry %d", first);
+      }
+      ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(n + 1), &f->bi);CHKERRQ(ierr);
+      ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(f->nz + 1), &f->bj);CHKERRQ(ierr);
+      ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(n + 1), &f->bdiag);CHKERRQ(ierr);
+      f->bi[0] = 0;
+      for (PetscInt i = 0; i < n; i++) f->bi[i + 1] = f->bi[i] + (adiag[i] - ai[i]);
+      f->bdiag[n] = f->bi[n] - 1;
+      for (PetscInt i = n - 1; i >= 0; i--) f->bdiag[i] = f->bdiag[i + 1] + (ai[i + 1] - adiag[i] - 1) + 1;
+      sy.bi = f->bi; sy.bj = f->bj; sy.bdiag = f->bdiag;
+      HipParallelRanges(n, ilu0_sym_pattern, &sy);
+      HipFree(adiag); }
+#endif
+    SETUP_TICK("factor (device): pattern of L and U");
+    for (PetscInt bb = 0; bb < nblk; bb++)
+      for (PetscInt i = blk[bb]; i < blk[bb + 1]; i++)
+        if (ai[i] < ai[i + 1] && (aj[ai[i]] < blk[bb] || aj[ai[i + 1] - 1] >= blk[bb + 1])) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "row %d couples to a column outside its independent block", i);
+    ierr = ilu0_row_levels(n, f->bi, f->bj, f->bdiag, &f->rlevL, &f->nlevL, &f->rlevU, &f->nlevU);CHKERRQ(ierr);
+    ierr = level_order(n, f->rlevL, f->nlevL, &levptr, &rows);CHKERRQ(ierr);
+    SETUP_TICK("factor (device): levels of L and U");
+    int rc = mi355x_ilu0_factor_create(dc->h, n, f->bi, f->bj, f->bdiag, f->nlevL, levptr, rows, nblk, blk, &f->dfac);
+    HipFree(levptr); HipFree(rows);
+    if (!rc) rc = mi355x_malloc((void **)&f->d_ba, sizeof(PetscScalar) * (size_t)(f->nz + 1));
+    if (!rc) rc = mi355x_memset(dc->h, f->d_ba, 0, sizeof(PetscScalar) * (size_t)(f->nz + 1));   /* (the slot past the last value is never written) */
+    CHKHIP(rc);
+    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nblk + 1), &f->dfac_blk);CHKERRQ(ierr);
+    memcpy(f->dfac_blk, blk, sizeof(PetscInt) * (size_t)(nblk + 1));
+    f->dfac_gen = d->pattern_gen; f->dfac_n = n; f->dfac_nz = ai[n]; f->dfac_nblk = nblk; f->dfac_stale = 0;
+    f->symbolic_builds++;
+    SETUP_TICK("factor (device): context and index upload");
+  }
+  const PetscReal shiftamount = info->shiftamount;
+  const PetscBool shift_nz = (PetscBool)(info->shifttype == (PetscReal)MAT_SHIFT_NONZERO);
+  PetscScalar *shifts, *fabsv; PetscInt *nsh, *frow, badrow = -1; PetscReal badval = 0.0; int rc = 0;
+  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)nblk, &shifts);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)nblk, &fabsv);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)nblk, &nsh);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)nblk, &frow);CHKERRQ(ierr);
+  for (PetscInt bb = 0; bb < nblk; bb++) { shifts[bb] = 0.0; nsh[bb] = 0; }
+  mi355x_ilu0_factor_reset(f->dfac);
+  ierr = 0;
+  for (;;) {
+    int any = 0;
+    rc = mi355x_ilu0_factor_run(dc->h, f->dfac, d->mat.i, d->mat.j, d->mat.a, info->zeropivot, shifts, f->d_ba, frow, fabsv);
+    if (rc) break;
+    for (PetscInt bb = 0; bb < nblk && !ierr; bb++) {
+      if (frow[bb] < 0) continue;
+      if (!any) { badrow = frow[bb]; badval = fabsv[bb]; }
+      any = 1;
+      if (!shift_nz) { ierr = PETSC_ERR_ARG_WRONG; break; }
+      shifts[bb] = nsh[bb] ? shifts[bb] * 2.0 : shiftamount;
+      if (++nsh[bb] > 80) ierr = PETSC_ERR_ARG_WRONG;
+    }
+    if (ierr || !any) break;
+  }
+  f->nshift = 0;
+  for (PetscInt bb = 0; bb < nblk; bb++) f->nshift = PetscMax(f->nshift, nsh[bb]);
+  HipFree(shifts); HipFree(fabsv); HipFree(nsh); HipFree(frow);
+  SETUP_TICK("factor (device): numeric passes");
+  CHKHIP(rc);
+  if (ierr) SETERRQ(HipObjComm(A), 71 /* PETSC_ERR_MAT_LU_ZRPVT */, "Zero pivot row %d value %g%s", badrow, badval, shift_nz ? ": still there after 80 diagonal shifts" : "");
+  f->numeric_runs++;
+#if defined(PETSCHIPMI355X_WITH_PETSC)
+  ierr = ilu0_fetch_host_ba(f, dc);CHKERRQ(ierr);                        /* the parent's b->a holds the factor, as after its own routine */
+  F->assembled = PETSC_TRUE; F->preallocated = PETSC_TRUE;
+  SETUP_TICK("factor (device): values to the parent's array");
+#endif
   return 0;
 }
 
@@ -686,19 +888,28 @@ static PetscErrorCode MatLUFactorNumeric_SeqAIJHIP(Mat F, Mat A, const MatFactor
   PetscErrorCode ierr;
   HipTriFactors *f = HipTriGet(F);
   const double t0 = wall_s();
+  int on_device = 0;
   if (A->rmap->n != A->cmap->n) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "Must be square matrix, rows %d columns %d", A->rmap->n, A->cmap->n);
   if (f->factored_state == HipObjState(A) && f->factored_of == (void *)A && (f->tri_lo || f->d_ba || f->sweeps)) return 0;   /* same operator, same values: nothing to redo */
-  tri_reset_numeric(f);
+  { char where[16] = "host"; PetscBool set;   /* -pc_factor_hipmi355x_numeric <host|device>, an opt-in */
+    ierr = PetscOptionsGetString(HipObjPrefix(F), "-pc_factor_hipmi355x_numeric", where, sizeof(where), &set);CHKERRQ(ierr);
+    if (strcmp(where, "host") && strcmp(where, "device")) SETERRQ(HipObjComm(F), PETSC_ERR_ARG_WRONG, "-pc_factor_hipmi355x_numeric <host|device>, got %s", where);
+    on_device = !strcmp(where, "device"); }
+  if (on_device) { ierr = ilu0_factor_device(F, A, info);CHKERRQ(ierr); }
+  else {
+    tri_reset_numeric(f);
 #if defined(PETSCHIPMI355X_WITH_PETSC)
-  ierr = MatLUFactorNumeric_SeqAIJ(F, A, info);CHKERRQ(ierr);            /* the parent's factorisation into F's own Mat_SeqAIJ */
-  { Mat_SeqAIJ *b = (Mat_SeqAIJ *)F->data;
-    f->n = A->rmap->n; f->nz = b->nz; f->bi = b->i; f->bj = b->j; f->bdiag = b->diag; f->ba = b->a; f->owns_host = PETSC_FALSE; }
+    ierr = MatLUFactorNumeric_SeqAIJ(F, A, info);CHKERRQ(ierr);            /* the parent's factorisation into F's own Mat_SeqAIJ */
+    { Mat_SeqAIJ *b = (Mat_SeqAIJ *)F->data;
+      f->n = A->rmap->n; f->nz = b->nz; f->bi = b->i; f->bj = b->j; f->bdiag = b->diag; f->ba = b->a; f->owns_host = PETSC_FALSE; }
 #else
-  ierr = ilu0_factor_host(F, A, info);CHKERRQ(ierr);
+    ierr = ilu0_factor_host(F, A, info);CHKERRQ(ierr);
 #endif
+    f->symbolic_builds++; f->numeric_runs++;
+  }
   const double t1 = wall_s();
   ierr = ilu0_analyse_and_upload(F, A);CHKERRQ(ierr);
-  if (getenv("PETSC_HIPMI355X_SETUP_TIMING")) fprintf(stderr, "[hipmi355x] ILU(0) n=%d: host factorisation %.3f s, level analysis + plans + upload %.3f s\n", (int)f->n, t1 - t0, wall_s() - t1);
+  if (getenv("PETSC_HIPMI355X_SETUP_TIMING")) fprintf(stderr, "[hipmi355x] ILU(0) n=%d: %s factorisation %.3f s, level analysis + plans + upload %.3f s\n", (int)f->n, on_device ? "device" : "host", t1 - t0, wall_s() - t1);
   F->ops->solve = MatSolve_SeqAIJHIP_ILU;                                 /* aijcusparse.cu:372-373 */
   f->factored_state = HipObjState(A); f->factored_of = (void *)A;
   return 0;
@@ -711,6 +922,7 @@ static PetscErrorCode MatILUFactorSymbolic_SeqAIJHIP(Mat F, Mat A, IS row, IS co
   ierr = MatILUFactorSymbolic_SeqAIJ(F, A, row, col, info);CHKERRQ(ierr);
 #endif
   HipTriGet(F)->factored_state = -1;
+  HipTriGet(F)->dfac_stale = 1;                                            /* a new symbolic phase: the device route's context is of the old pattern */
   F->ops->lufactornumeric = MatLUFactorNumeric_SeqAIJHIP;
   return 0;
 }
@@ -860,6 +1072,16 @@ PetscErrorCode PCILUGetSweeps_HIPMI355X(PC pc, PetscInt *k) {
   HipTriFactors *f;
   PetscErrorCode ierr = pc_factors(pc, MAT_FACTOR_ILU, &f);CHKERRQ(ierr);
   *k = f->sweeps;
+  return 0;
+}
+/* on_device: the last numeric factorisation ran on the device (-pc_factor_hipmi355x_numeric device); host symbolic passes (pattern,
+ * levels, context) and numeric factorisations of this factor so far */
+PetscErrorCode PCILUGetNumeric_HIPMI355X(PC pc, PetscInt *on_device, PetscInt *symbolic_builds, PetscInt *numeric_runs) {
+  HipTriFactors *f;
+  PetscErrorCode ierr = pc_factors(pc, MAT_FACTOR_ILU, &f);CHKERRQ(ierr);
+  if (on_device) *on_device = f->dfac ? 1 : 0;
+  if (symbolic_builds) *symbolic_builds = f->symbolic_builds;
+  if (numeric_runs) *numeric_runs = f->numeric_runs;
   return 0;
 }
 /* v <- the factor's application to v, input and result in ONE vector.  PCApply and MatSolve refuse identical vectors as the
