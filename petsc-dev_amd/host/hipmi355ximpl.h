@@ -143,38 +143,53 @@ typedef struct {
 typedef struct {
   MatFactorType kind;                                      /* MAT_FACTOR_ILU or MAT_FACTOR_ICC */
   PetscInt n, nz;
-  PetscInt *bi, *bj, *bdiag; PetscScalar *ba;              /* ILU(0): host factor in the reference's L / reversed-U layout (aijfact.c:1628-1700) */
-  PetscBool owns_host;                                     /* harness: ours; inside PETSc: the arrays of F's own Mat_SeqAIJ */
-  PetscInt *d_bi, *d_bj, *d_bdiag; PetscScalar *d_ba;      /* device copies for the level-scheduled ILU kernels */
-  PetscInt nlevL, nlevU, *levptrL, *levptrU;               /* dependency levels (host) */
-  PetscInt *rlevL, *rlevU;                                 /* level of every row of L / U, left by the host factorisation for the solves' analysis (else NULL) */
-  PetscInt *d_rowsL, *d_rowsU;                             /* rows ordered by level (device) */
-  PetscScalar *d_work; void *graph; int graph_tried;       /* hipGraph of the level launches working in place on d_work */
-  mi355x_trisolve_plan_t tri_lo, tri_up;                   /* sync-free solves (NULL: level launches) */
-  int by_level;                                            /* rows summed in dependency-level order (inode matrices) instead of column order */
-  int block_columns;                                       /* node plans whose columns are whole dependency nodes */
-  PetscInt nodes, nlevL_nodes, nlevU_nodes;                /* node-blocked plans (the factor of a matrix with inodes): nodes and their levels; 0: row-granular */
-  /* -pc_factor_hipmi355x_trisolve sweeps:<k>: k Jacobi sweeps per triangle instead of the exact solves (0: exact).  The negated
-   * strict triangles as CSR with their SpMV plans, the inverted pivots, two work vectors; sw_bi / sw_bj / sw_bdiag: the pattern they
-   * were built from (a numeric factorisation with the same pattern re-sends values only) */
-  PetscInt sweeps, sw_n, sw_nz, *sw_bi, *sw_bj, *sw_bdiag;
-  mi355x_spmv_plan_t sw_planL, sw_planU;
-  PetscInt *sw_iL, *sw_jL, *sw_iU, *sw_jU; PetscScalar *sw_aL, *sw_aU, *sw_dinv, *sw_work[2];
-  /* -pc_factor_hipmi355x_numeric device: the numeric factorisation runs on the device (mi355x_ilu0_factor_*), level by level, into d_ba.
-   * The context is built once per pattern; with it stay the host pattern (bi / bj / bdiag), the row levels (rlevL / rlevU) and, borrowed
-   * from it for the level-launch solves, d_bi / d_bj / d_bdiag / d_rowsL (d_borrowed: not ours to free).  dfac_gen / dfac_n / dfac_nz:
-   * the serial number of the operator's pattern upload (Mat_SeqAIJHIP.pattern_gen) and its sizes at the time -- what "the pattern of the
-   * last factorisation" is told by */
-  mi355x_ilu0_factor_t dfac; int d_borrowed, dfac_stale;
-  unsigned long long dfac_gen; PetscInt dfac_n, dfac_nz, dfac_nblk, *dfac_blk;
+  /* one member per form of the factor; releasing a form frees its members and zeroes it (host/ilu.c, "releasing a factor") */
+  /* ILU(0): host factor in the reference's L / reversed-U layout (aijfact.c:1628-1700); owns: ours (harness), or the arrays of F's own Mat_SeqAIJ (inside PETSc) */
+  struct { PetscInt *bi, *bj, *bdiag; PetscScalar *ba; PetscBool owns; } host;
+  /* dependency levels of L / U, and the level of every row: for the time of the solves' analysis; the device route keeps them with its context (else NULL) */
+  struct { PetscInt nlevL, nlevU, *rlevL, *rlevU; } lev;
+  struct {                                                 /* the level-scheduled ILU kernels, one launch per level */
+    PetscInt *d_bi, *d_bj, *d_bdiag; PetscScalar *d_ba;    /* device copies of the factor (d_ba: the device route's factor itself) */
+    PetscInt *levptrL, *levptrU;                           /* where each level's rows start (host) */
+    PetscInt *d_rowsL, *d_rowsU;                           /* rows ordered by level (device) */
+    PetscScalar *d_work; void *graph; int graph_tried;     /* hipGraph of the level launches working in place on d_work */
+    int borrowed;                                          /* d_bi / d_bj / d_bdiag / d_rowsL are the device route's context's: not ours to free */
+  } launch;
+  struct {
+    mi355x_trisolve_plan_t tri_lo, tri_up;                 /* sync-free solves (NULL: level launches) */
+    int by_level;                                          /* rows summed in dependency-level order (inode matrices) instead of column order */
+    int block_columns;                                     /* node plans whose columns are whole dependency nodes */
+    PetscInt nodes, nlevL_nodes, nlevU_nodes;              /* node-blocked plans (the factor of a matrix with inodes): nodes and their levels; 0: row-granular */
+    int use_levels;                                        /* a sync-free application gave up: the same plans run level by level from now on */
+  } syncfree;
+  /* -pc_factor_hipmi355x_trisolve sweeps:<k>: k Jacobi sweeps per triangle instead of the exact solves (sweeps 0: exact).  The negated
+   * strict triangles as CSR with their SpMV plans, the inverted pivots, two work vectors.  A numeric factorisation with the pattern
+   * they were built for re-sends values only: the host route keeps that pattern (bi / bj / bdiag) and compares; the device route's
+   * (from_device) is the pattern of its context, which forgets this form when it is rebuilt */
+  struct {
+    PetscInt sweeps, n, nz, *bi, *bj, *bdiag; int from_device;
+    mi355x_spmv_plan_t planL, planU;
+    PetscInt *iL, *jL, *iU, *jU; PetscScalar *aL, *aU, *dinv, *work[2];
+  } sw;
+  /* -pc_factor_hipmi355x_numeric device: the numeric factorisation runs on the device (mi355x_ilu0_factor_*), level by level, into
+   * launch.d_ba.  The context is built once per pattern; with it stay the host pattern (host.bi / bj / bdiag), the row levels
+   * (lev.rlevL / rlevU) and what the level-launch solves borrow from it (launch.borrowed).  gen / n / nz: the serial number of the
+   * operator's pattern upload (Mat_SeqAIJHIP.pattern_gen) and its sizes at the time -- what "the pattern of the last factorisation" is told by */
+  struct { mi355x_ilu0_factor_t dfac; int stale; unsigned long long gen; PetscInt n, nz, nblk, *blk; } dev;
   PetscInt symbolic_builds, numeric_runs;                  /* host symbolic passes / numeric factorisations so far (both routes) */
-  int use_levels, aborted;                                 /* a sync-free application gave up: the same plans run level by level from now on */
+  int aborted;                                             /* a sync-free application of this factor gave up at some time (kept over re-factorisations) */
   PetscInt nshift;                                         /* restarts / shifts the factorisation took (largest count over the blocks) */
   int factored_state; void *factored_of;                   /* operator and operator state of the last numeric factorisation */
   PetscInt nblk, *blk;                                     /* "MatFactorSetIndependentBlocks_C": the matrix stands for that many separate matrices (row ranges) */
   PetscErrorCode (*parent_destroy)(Mat);                   /* inside PETSc: the parent factor matrix's destroy */
 } HipTriFactors;
 PetscErrorCode HipTriFactorsDestroy(HipTriFactors **f);
+void HipTriFactorsResetNumeric(HipTriFactors *f);                /* forget one numeric factorisation (host/ilu.c) */
+PetscInt HipTriFactorsBlocks(const HipTriFactors *f, PetscInt n, PetscInt whole[2], const PetscInt **blk);   /* the independent blocks a factorisation of n rows runs over */
+/* where the set-up time goes, on stderr under PETSC_HIPMI355X_SETUP_TIMING: a line; the line of the phase that began at clock (moved on) */
+double HipWallSeconds(void);
+#define HipSetupNote(...) do { if (getenv("PETSC_HIPMI355X_SETUP_TIMING")) fprintf(stderr, "[hipmi355x] " __VA_ARGS__); } while (0)
+#define HipSetupTick(clock, what) do { const double t__ = HipWallSeconds(); HipSetupNote("  %-34s %.6f s\n", what, t__ - (clock)); (clock) = t__; } while (0)
 PetscErrorCode HipTriFactorsApply(Mat F, HipTriFactors *f, Vec b, Vec x, PetscLogDouble flops);
 typedef void (*HipRangeFn)(void *ctx, PetscInt lo, PetscInt hi);
 void HipParallelRanges(PetscInt n, HipRangeFn fn, void *ctx);   /* fn over contiguous parts of [0, n) on HipHostThreads(16) host threads (hipsys.c); one thread below 200 000 */

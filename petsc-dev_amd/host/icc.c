@@ -14,6 +14,7 @@
  *             1/D(i) between the two sweeps is the upper solve's right-hand-side factor; its rows are stored last entry first, as the
  *             reference's backward loop reads them.  Same bits as the host loop. */
 #include "hipmi355ximpl.h"
+#include <pthread.h>
 #if defined(PETSCHIPMI355X_WITH_PETSC)
 #include <../src/mat/impls/aij/seq/aij.h>
 #include <../src/mat/impls/sbaij/seq/sbaij.h>
@@ -25,9 +26,6 @@ static PetscErrorCode MatSolve_SeqAIJHIP_ICC(Mat F, Vec b, Vec x) {   /* PCApply
 }
 
 static PetscErrorCode icc0_plans(Mat F, PetscInt n, const PetscInt *ui, const PetscInt *uj, const PetscScalar *ua);
-#include <time.h>
-static double icc_wall_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
-#define ICC_TICK(what) do { if (getenv("PETSC_HIPMI355X_SETUP_TIMING")) { const double t__ = icc_wall_s(); fprintf(stderr, "[hipmi355x]   %-34s %.3f s\n", what, t__ - tick0); tick0 = t__; } } while (0)
 
 #if !defined(PETSCHIPMI355X_WITH_PETSC)
 typedef struct { const PetscInt *ai, *aj; PetscInt *ui, *uj; volatile PetscInt missing; } IccSym;
@@ -54,7 +52,7 @@ static PetscErrorCode icc0_factor_host(Mat F, Mat A, const MatFactorInfo *info) 
   PetscErrorCode ierr;
   HipTriFactors *f = HipTriGet(F);
   PetscInt n; const PetscInt *ai, *aj; const PetscScalar *aa;
-  double tick0 = icc_wall_s();
+  double tick0 = HipWallSeconds();
   ierr = MatSeqAIJGetArrays(A, &n, &ai, &aj, &aa);CHKERRQ(ierr);
   f->n = n;
   if (!n) return 0;
@@ -79,7 +77,7 @@ static PetscErrorCode icc0_factor_host(Mat F, Mat A, const MatFactorInfo *info) 
     sy.uj = uj;
     HipParallelRanges(n, icc0_sym_fill, &sy); }
 
-  ICC_TICK("icc: pattern of U");
+  HipSetupTick(tick0, "icc: pattern of U");
   /* ---- numeric, left-looking over the rows; the shift of MatPivotCheck_pd (matimpl.h:532-553) restarts it.  One pass per
    * independent block (one block = the whole matrix unless "PCFactorSetIndependentBlocks_C" said otherwise) ---- */
   const PetscReal zeropivot = info->zeropivot;
@@ -89,8 +87,8 @@ static PetscErrorCode icc0_factor_host(Mat F, Mat A, const MatFactorInfo *info) 
   ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)n, &work);CHKERRQ(ierr);
   ierr = PetscMalloc(sizeof(PetscInt) * (size_t)n, &first);CHKERRQ(ierr);   /* first[i]: first entry of row i not yet folded into a later row */
   ierr = PetscMalloc(sizeof(PetscInt) * (size_t)n, &list);CHKERRQ(ierr);    /* list[c]: chain of the earlier rows whose next entry is in column c */
-  const PetscInt whole[2] = {0, n};
-  const PetscInt nblk = (f->nblk > 0 && f->blk[f->nblk] == n) ? f->nblk : 1, *blk = (f->nblk > 0 && f->blk[f->nblk] == n) ? f->blk : whole;
+  PetscInt whole[2]; const PetscInt *blk;
+  const PetscInt nblk = HipTriFactorsBlocks(f, n, whole, &blk);
   for (PetscInt bb = 0; bb < nblk; bb++) {
     const PetscInt r0 = blk[bb], r1 = blk[bb + 1];
     for (PetscInt k = r0; k < r1; k++)
@@ -151,16 +149,15 @@ static PetscErrorCode icc0_factor_host(Mat F, Mat A, const MatFactorInfo *info) 
     f->nshift = PetscMax(f->nshift, nshift);
   }
   HipFree(work); HipFree(first); HipFree(list);
-  ICC_TICK("icc: numeric");
+  HipSetupTick(tick0, "icc: numeric");
   ierr = icc0_plans(F, n, ui, uj, ua);
-  ICC_TICK("icc: plans");
+  HipSetupTick(tick0, "icc: plans");
   HipFree(ui); HipFree(uj); HipFree(ua);
   CHKERRQ(ierr);
   return 0;
 }
 #endif
 
-#include <pthread.h>
 typedef struct { PetscInt n; const PetscInt *ui, *uj; const PetscScalar *ua; PetscInt *lp, *ll, *lj; PetscScalar *lv; PetscInt *up, *ul, *uc; PetscScalar *uv, *ones, *dinv; PetscInt *levU, nlevU; } IccT;
 static void icc0_count_columns(void *c_, PetscInt lo, PetscInt hi) {          /* lp[c + 1] = entries in column c, for the columns [lo, hi) */
   IccT *t = (IccT *)c_;
@@ -230,17 +227,17 @@ static PetscErrorCode icc0_plans(Mat F, PetscInt n, const PetscInt *ui, const Pe
   HipParallelRanges(n, icc0_count_columns, &tr);
   for (PetscInt c = 0; c < n; c++) { ll[c] = 0; lp[c + 1] += lp[c]; }
   HipParallelRanges(n, icc0_fill_columns, &tr);
-  f->nlevL = 0;
+  f->lev.nlevL = 0;
   for (PetscInt c = 0; c < n; c++) {
     PetscInt l = 0;
     for (PetscInt q = lp[c]; q < lp[c] + ll[c]; q++) l = PetscMax(l, levL[lj[q]] + 1);
-    levL[c] = l; f->nlevL = PetscMax(f->nlevL, l + 1);
+    levL[c] = l; f->lev.nlevL = PetscMax(f->lev.nlevL, l + 1);
   }
   HipParallelRanges(n, icc0_upper_rows, &tr);             /* the backward loop reads a row from its last off-diagonal entry to its first */
   if (sideU) pthread_join(thU, NULL); else icc0_levels_U(&tr);
-  f->nlevU = tr.nlevU;
+  f->lev.nlevU = tr.nlevU;
   ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-  int rc = mi355x_trisolve_plan_create_pair(dc->h, n, 0, f->nlevL, levL, lp, ll, lj, lv, f->nlevU, levU, up, ul, uc, uv, ones, dinv, &f->tri_lo, &f->tri_up);
+  int rc = mi355x_trisolve_plan_create_pair(dc->h, n, 0, f->lev.nlevL, levL, lp, ll, lj, lv, f->lev.nlevU, levU, up, ul, uc, uv, ones, dinv, &f->syncfree.tri_lo, &f->syncfree.tri_up);
   HipFree(lp); HipFree(ll); HipFree(lj); HipFree(lv); HipFree(up); HipFree(ul); HipFree(uc); HipFree(uv);
   HipFree(levL); HipFree(levU); HipFree(ones); HipFree(dinv);
   CHKHIP(rc);
@@ -251,10 +248,8 @@ static PetscErrorCode MatCholeskyFactorNumeric_SeqAIJHIP(Mat F, Mat A, const Mat
   PetscErrorCode ierr;
   HipTriFactors *f = HipTriGet(F);
   if (A->rmap->n != A->cmap->n) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "Must be square matrix, rows %d columns %d", A->rmap->n, A->cmap->n);
-  if (f->factored_state == HipObjState(A) && f->factored_of == (void *)A && (f->tri_lo || !A->rmap->n)) return 0;
-  if (f->tri_lo) mi355x_trisolve_plan_destroy(f->tri_lo);
-  if (f->tri_up) mi355x_trisolve_plan_destroy(f->tri_up);
-  f->tri_lo = f->tri_up = NULL; f->use_levels = 0; f->nshift = 0; f->nlevL = f->nlevU = 0; f->factored_state = -1;
+  if (f->factored_state == HipObjState(A) && f->factored_of == (void *)A && (f->syncfree.tri_lo || !A->rmap->n)) return 0;
+  HipTriFactorsResetNumeric(f);
 #if defined(PETSCHIPMI355X_WITH_PETSC)
   ierr = MatCholeskyFactorNumeric_SeqAIJ(F, A, info);CHKERRQ(ierr);     /* the parent's factorisation into F's own Mat_SeqSBAIJ (aijfact.c:2076) */
   { Mat_SeqSBAIJ *b = (Mat_SeqSBAIJ *)F->data;
@@ -263,7 +258,7 @@ static PetscErrorCode MatCholeskyFactorNumeric_SeqAIJHIP(Mat F, Mat A, const Mat
 #else
   ierr = icc0_factor_host(F, A, info);CHKERRQ(ierr);
 #endif
-  if (f->tri_lo) HipTriWatchAdd(f);
+  if (f->syncfree.tri_lo) HipTriWatchAdd(f);
   F->ops->solve = MatSolve_SeqAIJHIP_ICC;
   f->factored_state = HipObjState(A); f->factored_of = (void *)A;
   return 0;

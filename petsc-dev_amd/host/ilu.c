@@ -20,6 +20,10 @@
  *             -pc_factor_hipmi355x_trisolve sweeps:<k> (opt-in, an APPROXIMATE application): k Jacobi sweeps per triangle, each one
  *             SpMV-shaped product with the negated strict triangle (ilu0_sweeps_* below). */
 #include "hipmi355ximpl.h"
+#include <pthread.h>
+#include <sched.h>
+#include <time.h>
+#include <unistd.h>
 #if defined(PETSCHIPMI355X_WITH_PETSC)
 #include <../src/mat/impls/aij/seq/aij.h>
 EXTERN_C_BEGIN
@@ -43,7 +47,7 @@ void HipTriWatchAdd(HipTriFactors *f) {
   for (int i = 0; i < tri_watch_cap; i++) if (!tri_watch[i]) { tri_watch[i] = f; return; }
   const int ncap = tri_watch_cap ? 2 * tri_watch_cap : 64;
   HipTriFactors **nw = (HipTriFactors **)realloc(tri_watch, sizeof(*nw) * (size_t)ncap);
-  if (!nw) { f->use_levels = 1; return; }
+  if (!nw) { f->syncfree.use_levels = 1; return; }
   memset(nw + tri_watch_cap, 0, sizeof(*nw) * (size_t)(ncap - tri_watch_cap));
   nw[tri_watch_cap] = f;
   tri_watch = nw; tri_watch_cap = ncap;
@@ -53,10 +57,10 @@ PetscErrorCode HipTriWatchCheck(void) {
   for (int i = 0; i < tri_watch_cap; i++) {
     HipTriFactors *f = tri_watch[i];
     int a = 0, b = 0;
-    if (!f || !f->tri_lo || f->use_levels) continue;
-    mi355x_trisolve_aborted(f->tri_lo, &a); mi355x_trisolve_aborted(f->tri_up, &b);
+    if (!f || !f->syncfree.tri_lo || f->syncfree.use_levels) continue;
+    mi355x_trisolve_aborted(f->syncfree.tri_lo, &a); mi355x_trisolve_aborted(f->syncfree.tri_up, &b);
     if (a || b) {
-      f->use_levels = 1; f->aborted = 1;
+      f->syncfree.use_levels = 1; f->aborted = 1;
       SETERRQ(PETSC_COMM_SELF, PETSC_ERR_LIB, "a sync-free triangular solve gave up waiting for a dependency: results computed since that MatSolve are invalid; "
                                               "later applications of this factor use one launch per dependency level");
     }
@@ -64,71 +68,70 @@ PetscErrorCode HipTriWatchCheck(void) {
   return 0;
 }
 
-/* the device form of -pc_factor_hipmi355x_trisolve sweeps:<k> (it outlives a numeric factorisation: tri_reset_numeric leaves it) */
-static void ilu0_sweeps_free(HipTriFactors *f) {
-  void *dev[] = {f->sw_iL, f->sw_jL, f->sw_iU, f->sw_jU, f->sw_aL, f->sw_aU, f->sw_dinv, f->sw_work[0], f->sw_work[1]};
+/* ---------------------------------------------------------------- releasing a factor: one function per form (hipmi355ximpl.h) */
+static void tri_free_host(HipTriFactors *f) {
+  if (f->host.owns) { HipFree(f->host.bi); HipFree(f->host.bj); HipFree(f->host.bdiag); HipFree(f->host.ba); }
+  memset(&f->host, 0, sizeof(f->host));
+}
+static void tri_free_lev(HipTriFactors *f) {
+  HipFree(f->lev.rlevL); HipFree(f->lev.rlevU);
+  memset(&f->lev, 0, sizeof(f->lev));
+}
+static void tri_free_launch(HipTriFactors *f) {
+  if (f->launch.graph) mi355x_graph_destroy(f->launch.graph);
+  if (f->launch.borrowed) f->launch.d_bi = f->launch.d_bj = f->launch.d_bdiag = f->launch.d_rowsL = NULL;   /* the context's: forgotten, not freed */
+  void *dev[] = {f->launch.d_bi, f->launch.d_bj, f->launch.d_bdiag, f->launch.d_ba, f->launch.d_rowsL, f->launch.d_rowsU, f->launch.d_work};
   for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); i++) if (dev[i]) mi355x_free(dev[i]);
-  if (f->sw_planL) mi355x_spmv_plan_destroy(f->sw_planL);
-  if (f->sw_planU) mi355x_spmv_plan_destroy(f->sw_planU);
-  HipFree(f->sw_bi); HipFree(f->sw_bj); HipFree(f->sw_bdiag);
-  f->sw_iL = f->sw_jL = f->sw_iU = f->sw_jU = f->sw_bi = f->sw_bj = f->sw_bdiag = NULL;
-  f->sw_aL = f->sw_aU = f->sw_dinv = f->sw_work[0] = f->sw_work[1] = NULL;
-  f->sw_planL = f->sw_planU = NULL;
-  f->sweeps = 0;
+  HipFree(f->launch.levptrL); HipFree(f->launch.levptrU);
+  memset(&f->launch, 0, sizeof(f->launch));
 }
-
-/* the device route's state (-pc_factor_hipmi355x_numeric device): the context of one pattern and what the level-launch solves borrow from it */
-static void ilu0_device_free(HipTriFactors *f) {
-  if (f->d_borrowed) { f->d_bi = f->d_bj = f->d_bdiag = f->d_rowsL = NULL; f->d_borrowed = 0; }
-  if (f->dfac) mi355x_ilu0_factor_destroy(f->dfac);
-  HipFree(f->dfac_blk);
-  f->dfac = NULL; f->dfac_blk = NULL; f->dfac_gen = 0; f->dfac_stale = 0;
+static void tri_free_syncfree(HipTriFactors *f) {
+  if (f->syncfree.tri_lo) mi355x_trisolve_plan_destroy(f->syncfree.tri_lo);
+  if (f->syncfree.tri_up) mi355x_trisolve_plan_destroy(f->syncfree.tri_up);
+  memset(&f->syncfree, 0, sizeof(f->syncfree));
 }
-
+/* the device form of -pc_factor_hipmi355x_trisolve sweeps:<k> */
+static void tri_free_sweeps(HipTriFactors *f) {
+  void *dev[] = {f->sw.iL, f->sw.jL, f->sw.iU, f->sw.jU, f->sw.aL, f->sw.aU, f->sw.dinv, f->sw.work[0], f->sw.work[1]};
+  for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); i++) if (dev[i]) mi355x_free(dev[i]);
+  if (f->sw.planL) mi355x_spmv_plan_destroy(f->sw.planL);
+  if (f->sw.planU) mi355x_spmv_plan_destroy(f->sw.planU);
+  HipFree(f->sw.bi); HipFree(f->sw.bj); HipFree(f->sw.bdiag);
+  memset(&f->sw, 0, sizeof(f->sw));
+}
+/* the device route's context of one pattern (-pc_factor_hipmi355x_numeric device) */
+static void tri_free_dev(HipTriFactors *f) {
+  if (f->dev.dfac) mi355x_ilu0_factor_destroy(f->dev.dfac);
+  HipFree(f->dev.blk);
+  memset(&f->dev, 0, sizeof(f->dev));
+}
+/* forget one numeric factorisation (ILU(0) and ICC(0) alike); the symbolic choices, the block list and the watch slot stay, and so
+ * do the sweep form's device arrays: the next factorisation may only have new values.  The one order that matters: the level-launch
+ * form goes BEFORE the device route's context -- its captured graph names the context's arrays, and the pointers it borrowed from the
+ * context are forgotten (tri_free_launch) while the context still owns them, never freed twice. */
+void HipTriFactorsResetNumeric(HipTriFactors *f) {
+  tri_free_launch(f); tri_free_dev(f);
+  tri_free_host(f); tri_free_lev(f); tri_free_syncfree(f);
+  f->sw.sweeps = 0; f->nshift = 0;
+  f->factored_state = -1;
+}
 PetscErrorCode HipTriFactorsDestroy(HipTriFactors **pf) {
   HipTriFactors *f = *pf;
   if (!f) return 0;
   tri_watch_remove(f);
-  ilu0_sweeps_free(f);
-  if (f->graph) { mi355x_graph_destroy(f->graph); f->graph = NULL; }   /* (it names the arrays the context owns) */
-  ilu0_device_free(f);
-  if (f->owns_host) { HipFree(f->bi); HipFree(f->bj); HipFree(f->bdiag); HipFree(f->ba); }
-  HipFree(f->levptrL); HipFree(f->levptrU); HipFree(f->blk); HipFree(f->rlevL); HipFree(f->rlevU);
-  if (f->d_bi) mi355x_free(f->d_bi);
-  if (f->d_bj) mi355x_free(f->d_bj);
-  if (f->d_bdiag) mi355x_free(f->d_bdiag);
-  if (f->d_ba) mi355x_free(f->d_ba);
-  if (f->d_rowsL) mi355x_free(f->d_rowsL);
-  if (f->d_rowsU) mi355x_free(f->d_rowsU);
-  if (f->d_work) mi355x_free(f->d_work);
-  if (f->tri_lo) mi355x_trisolve_plan_destroy(f->tri_lo);
-  if (f->tri_up) mi355x_trisolve_plan_destroy(f->tri_up);
+  HipTriFactorsResetNumeric(f);
+  tri_free_sweeps(f);
+  HipFree(f->blk);
   HipFree(f);
   *pf = NULL;
   return 0;
 }
-/* forget one numeric factorisation (the symbolic choices, the block list and the watch slot stay) */
-static void tri_reset_numeric(HipTriFactors *f) {
-  if (f->graph) { mi355x_graph_destroy(f->graph); f->graph = NULL; }
-  ilu0_device_free(f);
-  if (f->owns_host) { HipFree(f->bi); HipFree(f->bj); HipFree(f->bdiag); HipFree(f->ba); }
-  f->bi = f->bj = f->bdiag = NULL; f->ba = NULL;
-  HipFree(f->levptrL); HipFree(f->levptrU); f->levptrL = f->levptrU = NULL;
-  HipFree(f->rlevL); HipFree(f->rlevU); f->rlevL = f->rlevU = NULL;
-  if (f->d_bi) mi355x_free(f->d_bi);
-  if (f->d_bj) mi355x_free(f->d_bj);
-  if (f->d_bdiag) mi355x_free(f->d_bdiag);
-  if (f->d_ba) mi355x_free(f->d_ba);
-  if (f->d_rowsL) mi355x_free(f->d_rowsL);
-  if (f->d_rowsU) mi355x_free(f->d_rowsU);
-  if (f->d_work) mi355x_free(f->d_work);
-  if (f->tri_lo) mi355x_trisolve_plan_destroy(f->tri_lo);
-  if (f->tri_up) mi355x_trisolve_plan_destroy(f->tri_up);
-  f->d_bi = f->d_bj = f->d_bdiag = f->d_rowsL = f->d_rowsU = NULL; f->d_ba = f->d_work = NULL;
-  f->graph = NULL; f->graph_tried = 0; f->tri_lo = f->tri_up = NULL;
-  f->use_levels = 0; f->nshift = 0; f->nlevL = f->nlevU = 0;
-  f->sweeps = 0;                     /* (the sweep form's device arrays stay: the next factorisation may only have new values) */
-  f->factored_state = -1;
+
+/* the list "MatFactorSetIndependentBlocks_C" left when it covers the matrix, else the whole matrix as one block (kept in whole) */
+PetscInt HipTriFactorsBlocks(const HipTriFactors *f, PetscInt n, PetscInt whole[2], const PetscInt **blk) {
+  if (f->nblk > 0 && f->blk[f->nblk] == n) { *blk = f->blk; return f->nblk; }
+  whole[0] = 0; whole[1] = n; *blk = whole;
+  return 1;
 }
 
 /* block Jacobi solving all its ILU(0) / ICC(0) blocks as one block-diagonal system ("MatFactorSetIndependentBlocks_C", asked for
@@ -177,12 +180,8 @@ static PetscErrorCode natural_ordering_only(Mat A, IS row, IS col, const MatFact
   return 0;
 }
 
-#include <time.h>
-static double wall_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
-#define SETUP_TICK(what) do { if (getenv("PETSC_HIPMI355X_SETUP_TIMING")) { const double t__ = wall_s(); fprintf(stderr, "[hipmi355x]   %-34s %.6f s\n", what, t__ - tick0); tick0 = t__; } } while (0)
+double HipWallSeconds(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 
-#include <pthread.h>
-#include <unistd.h>
 /* the host factorisation hands its work arrays to a thread that returns them to the system; at most one such thread: it is joined before the next one starts and by PetscHIPMI355XFinalize (never left running behind the library) */
 static pthread_t release_th; static int release_running = 0;
 void HipFactorJoinHelpers(void) { if (release_running) { pthread_join(release_th, NULL); release_running = 0; } }
@@ -269,7 +268,6 @@ static int ilu0_factor_row(const IluPass *p, PetscScalar *rtmp, PetscInt i, Pets
   ba[bdiag[i]] = 1.0 / rtmp[i];
   return 0;
 }
-#include <sched.h>
 static void ilu0_barrier(IluPass *p, int *sense) {
   *sense = !*sense;
   if (__sync_add_and_fetch(&p->bar_count, 1) == p->nth) { p->bar_count = 0; __sync_synchronize(); p->bar_sense = *sense; }
@@ -328,6 +326,25 @@ static PetscErrorCode ilu0_run_pass(IluPass *p) {
 }
 #endif
 
+/* every block of an independent-blocks factorisation is a matrix of its own: no row may name a column outside its block */
+static PetscErrorCode ilu0_check_blocks(Mat A, const PetscInt *ai, const PetscInt *aj, PetscInt nblk, const PetscInt *blk) {
+  for (PetscInt bb = 0; bb < nblk; bb++)
+    for (PetscInt i = blk[bb]; i < blk[bb + 1]; i++)
+      if (ai[i] < ai[i + 1] && (aj[ai[i]] < blk[bb] || aj[ai[i + 1] - 1] >= blk[bb + 1])) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "row %d couples to a column outside its independent block", i);
+  return 0;
+}
+/* MAT_SHIFT_NONZERO, PCILU's default on a SeqAIJ matrix (ilu.c:387): a pivot that fails MatPivotCheck_nz (matimpl.h:512-528) restarts the
+ * factorisation with the diagonal shifted by shiftamount, then by twice that, ... at most 80 times (aijfact.c:507-592).  The next
+ * shift after a failed pass; non-zero: give up */
+static PetscErrorCode ilu0_next_shift(const MatFactorInfo *info, PetscReal *shift, PetscInt *nshift) {
+  if (info->shifttype != (PetscReal)MAT_SHIFT_NONZERO) return PETSC_ERR_ARG_WRONG;
+  *shift = *nshift ? *shift * 2.0 : info->shiftamount;
+  return ++*nshift > 80 ? PETSC_ERR_ARG_WRONG : 0;
+}
+static PetscErrorCode ilu0_zero_pivot(Mat A, const MatFactorInfo *info, PetscInt row, PetscReal value) {
+  SETERRQ(HipObjComm(A), 71 /* PETSC_ERR_MAT_LU_ZRPVT */, "Zero pivot row %d value %g%s", row, value, info->shifttype == (PetscReal)MAT_SHIFT_NONZERO ? ": still there after 80 diagonal shifts" : "");
+}
+
 #if !defined(PETSCHIPMI355X_WITH_PETSC)
 static void *ilu0_release_thread(void *a_) { void **a = (void **)a_; for (int i = 0; a[i]; i++) free(a[i]); free(a); return NULL; }
 typedef struct { const PetscInt *ai, *aj; PetscInt *adiag, *bi, *bj, *bdiag; volatile PetscInt missing; } IluSym;
@@ -351,55 +368,62 @@ static void ilu0_sym_pattern(void *c_, PetscInt lo, PetscInt hi) {
     u[nzu] = i;
   }
 }
-/* MatILUFactorSymbolic_SeqAIJ_ilu0 + MatLUFactorNumeric_SeqAIJ restated for the harness (inside a PETSc tree the parent's
- * routines run instead): the pattern of A, L part forward, U part from the last row backwards (aijfact.c:1660-1685); row by row
- * with a dense work row, pivots stored inverted (aijfact.c:505-570); MatPivotCheck_nz's restarts (matimpl.h:512-528) */
-static PetscErrorCode ilu0_factor_host(Mat F, Mat A, const MatFactorInfo *info) {
+/* MatILUFactorSymbolic_SeqAIJ_ilu0 restated for the harness: f->host.bi / bj / bdiag (ours) from the pattern of A.  adiag_out: for a caller
+ * with a use for the diagonal positions in A (NULL: freed here); diag_phase: the set-up clock's label for the first half (NULL: none) */
+static PetscErrorCode ilu0_symbolic_host(Mat A, PetscInt n, const PetscInt *ai, const PetscInt *aj, HipTriFactors *f, PetscInt **adiag_out, const char *diag_phase, double *clock) {
   PetscErrorCode ierr;
-  HipTriFactors *f = HipTriGet(F);
-  PetscInt n; const PetscInt *ai, *aj; const PetscScalar *aa;
-  double tick0 = wall_s();
-  ierr = MatSeqAIJGetArrays(A, &n, &ai, &aj, &aa);CHKERRQ(ierr);
-  f->n = n; f->nz = ai[n]; f->owns_host = PETSC_TRUE;
-  PetscInt *adiag;
+  PetscInt *adiag, *bi, *bdiag;
+  f->host.owns = PETSC_TRUE;
   ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(n, 1), &adiag);CHKERRQ(ierr);
-  { IluSym sy = {ai, aj, adiag, NULL, NULL, NULL, -1};
-    HipParallelRanges(n, ilu0_sym_diag, &sy);
-    if (sy.missing >= 0) {
-      PetscInt first = 0;
-      while (first < n && adiag[first] >= 0) first++;
-      HipFree(adiag);
-      SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "Matrix is missing diagonal entry %d", first);
-    } }
-  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(n + 1), &f->bi);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(f->nz + 1), &f->bj);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(n + 1), &f->bdiag);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)(f->nz + 1), &f->ba);CHKERRQ(ierr);
-  SETUP_TICK("factor: diagonal positions");
-  f->ba[f->nz] = 0.0;                      /* (every other entry is written by the numeric pass) */
-  PetscInt *bi = f->bi, *bj = f->bj, *bdiag = f->bdiag; PetscScalar *ba = f->ba;
+  IluSym sy = {ai, aj, adiag, NULL, NULL, NULL, -1};
+  HipParallelRanges(n, ilu0_sym_diag, &sy);
+  if (sy.missing >= 0) {
+    PetscInt first = 0;
+    while (first < n && adiag[first] >= 0) first++;
+    HipFree(adiag);
+    SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "Matrix is missing diagonal entry %d", first);
+  }
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(n + 1), &f->host.bi);
+  if (!ierr) ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(ai[n] + 1), &f->host.bj);
+  if (!ierr) ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(n + 1), &f->host.bdiag);
+  if (ierr) { HipFree(adiag); CHKERRQ(ierr); }
+  if (diag_phase) HipSetupTick(*clock, diag_phase);
   /* the two pointer arrays are running sums (one light sequential pass each); the column copies are per row, on host threads */
+  bi = f->host.bi; bdiag = f->host.bdiag;
   bi[0] = 0;
   for (PetscInt i = 0; i < n; i++) bi[i + 1] = bi[i] + (adiag[i] - ai[i]);
   bdiag[n] = bi[n] - 1;
   for (PetscInt i = n - 1; i >= 0; i--) bdiag[i] = bdiag[i + 1] + (ai[i + 1] - adiag[i] - 1) + 1;
-  { IluSym sy = {ai, aj, adiag, bi, bj, bdiag, -1};
-    HipParallelRanges(n, ilu0_sym_pattern, &sy); }
-  SETUP_TICK("factor: pattern of L and U");
-  const PetscReal zeropivot = info->zeropivot, shiftamount = info->shiftamount;
-  const PetscBool shift_nz = (PetscBool)(info->shifttype == (PetscReal)MAT_SHIFT_NONZERO);
+  sy.bi = bi; sy.bj = f->host.bj; sy.bdiag = bdiag;
+  HipParallelRanges(n, ilu0_sym_pattern, &sy);
+  if (adiag_out) *adiag_out = adiag; else HipFree(adiag);
+  return 0;
+}
+/* MatILUFactorSymbolic_SeqAIJ_ilu0 + MatLUFactorNumeric_SeqAIJ restated for the harness (inside a PETSc tree the parent's
+ * routines run instead): the pattern (ilu0_symbolic_host); row by row with a dense work row, pivots stored inverted
+ * (aijfact.c:505-570); MatPivotCheck_nz's restarts (ilu0_next_shift) */
+static PetscErrorCode ilu0_factor_host(Mat F, Mat A, const MatFactorInfo *info) {
+  PetscErrorCode ierr;
+  HipTriFactors *f = HipTriGet(F);
+  PetscInt n, *adiag, whole[2]; const PetscInt *ai, *aj, *blk; const PetscScalar *aa;
+  double tick0 = HipWallSeconds();
+  ierr = MatSeqAIJGetArrays(A, &n, &ai, &aj, &aa);CHKERRQ(ierr);
+  f->n = n; f->nz = ai[n];
+  ierr = ilu0_symbolic_host(A, n, ai, aj, f, &adiag, "factor: diagonal positions", &tick0);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)(f->nz + 1), &f->host.ba);
+  if (ierr) { HipFree(adiag); CHKERRQ(ierr); }
+  f->host.ba[f->nz] = 0.0;                 /* (every other entry is written by the numeric pass) */
+  HipSetupTick(tick0, "factor: pattern of L and U");
   f->nshift = 0;
-  const PetscInt whole[2] = {0, n};
-  const PetscInt nblk = (f->nblk > 0 && f->blk[f->nblk] == n) ? f->nblk : 1, *blk = (f->nblk > 0 && f->blk[f->nblk] == n) ? f->blk : whole;
-  for (PetscInt bb = 0; bb < nblk; bb++)
-    for (PetscInt i = blk[bb]; i < blk[bb + 1]; i++)
-      if (ai[i] < ai[i + 1] && (aj[ai[i]] < blk[bb] || aj[ai[i + 1] - 1] >= blk[bb + 1])) { HipFree(adiag); SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "row %d couples to a column outside its independent block", i); }
+  const PetscInt nblk = HipTriFactorsBlocks(f, n, whole, &blk);
+  ierr = ilu0_check_blocks(A, ai, aj, nblk, blk);
+  if (ierr) { HipFree(adiag); return ierr; }
   /* Rows of one dependency level of L do not read each other: a level's rows are factored by several host threads, one barrier per
    * level.  Every row's own arithmetic is the sequential loop's (ilu0_factor_row), so the factor carries the same bits whatever
    * the thread count; a pivot that fails MatPivotCheck_nz anywhere ends the pass for everybody and the block restarts shifted. */
   IluPass ps;
   memset(&ps, 0, sizeof(ps));
-  ps.ai = ai; ps.aj = aj; ps.aa = aa; ps.bi = bi; ps.bj = bj; ps.bdiag = bdiag; ps.ba = ba; ps.zeropivot = zeropivot; ps.n = n;
+  ps.ai = ai; ps.aj = aj; ps.aa = aa; ps.bi = f->host.bi; ps.bj = f->host.bj; ps.bdiag = f->host.bdiag; ps.ba = f->host.ba; ps.zeropivot = info->zeropivot; ps.n = n;
   { PetscInt nth = 1; PetscBool set;
     if (n >= 200000) nth = (PetscInt)HipHostThreads(16);
     ierr = PetscOptionsGetInt(NULL, "-mat_factor_hipmi355x_threads", &nth, &set);CHKERRQ(ierr);
@@ -407,31 +431,26 @@ static PetscErrorCode ilu0_factor_host(Mat F, Mat A, const MatFactorInfo *info) 
     if (nth > 64) nth = 64;
     ps.nth = (int)nth; ps.oversubscribed = nth > (PetscInt)HipHostThreads(64); }
   /* levels of L (the threaded passes below take a level's rows together) and of U, kept for the solves' analysis */
-  HipFree(f->rlevL); HipFree(f->rlevU); f->rlevL = f->rlevU = NULL;
-  ierr = ilu0_row_levels(n, bi, bj, bdiag, &f->rlevL, &f->nlevL, &f->rlevU, &f->nlevU);
-  if (!ierr) { ps.nlev = f->nlevL; ierr = level_order(n, f->rlevL, f->nlevL, &ps.levptr, &ps.rows); }
+  tri_free_lev(f);
+  ierr = ilu0_row_levels(n, ps.bi, ps.bj, ps.bdiag, &f->lev.rlevL, &f->lev.nlevL, &f->lev.rlevU, &f->lev.nlevU);
+  if (!ierr) { ps.nlev = f->lev.nlevL; ierr = level_order(n, f->lev.rlevL, f->lev.nlevL, &ps.levptr, &ps.rows); }
   if (ierr) { HipFree(adiag); CHKERRQ(ierr); }
-  SETUP_TICK("factor: levels of L and U");
+  HipSetupTick(tick0, "factor: levels of L and U");
   ierr = PetscMalloc(sizeof(PetscScalar *) * (size_t)ps.nth, &ps.rtmp);CHKERRQ(ierr);
   for (int t = 0; t < ps.nth; t++) { ps.rtmp[t] = (PetscScalar *)calloc((size_t)n + 1, sizeof(PetscScalar)); if (!ps.rtmp[t]) SETERRQ(HipObjComm(A), PETSC_ERR_MEM, "out of memory"); }
-  for (PetscInt bb = 0; bb < nblk; bb++) {
+  for (PetscInt bb = 0; bb < nblk && !ierr; bb++) {   /* every block is a matrix of its own: its own sequence of shifts */
     PetscInt nshift = 0;
     ps.r0 = blk[bb]; ps.r1 = blk[bb + 1]; ps.shift_amount = 0.0;
-    for (;;) {   /* MAT_SHIFT_NONZERO, PCILU's default on a SeqAIJ matrix (ilu.c:387): a pivot that fails MatPivotCheck_nz restarts the
-                  * factorisation with the diagonal shifted by shiftamount, then by twice that, ... (aijfact.c:507-592) */
+    for (;;) {
       ps.fail_row = -1; ps.fail_level = -1;
       ierr = ilu0_run_pass(&ps);
+      if (ierr || ps.fail_row < 0) break;
+      ierr = ilu0_next_shift(info, &ps.shift_amount, &nshift);
       if (ierr) break;
-      if (ps.fail_row < 0) break;
-      if (!shift_nz) { ierr = PETSC_ERR_ARG_WRONG; break; }
-      ps.shift_amount = nshift ? ps.shift_amount * 2.0 : shiftamount;
-      nshift++;
-      if (nshift > 80) { ierr = PETSC_ERR_ARG_WRONG; break; }
     }
-    if (ierr) break;
-    f->nshift = PetscMax(f->nshift, nshift);
+    if (!ierr) f->nshift = PetscMax(f->nshift, nshift);
   }
-  SETUP_TICK("factor: numeric passes");
+  HipSetupTick(tick0, "factor: numeric passes");
   /* returning 16 dense work rows (2 GB of touched pages at 16.7 M rows) to the system takes 0.12 s: off the caller's path */
   { void **junk = (void **)malloc(sizeof(void *) * (size_t)(ps.nth + 4)); int k = 0;
     if (junk) {
@@ -442,8 +461,8 @@ static PetscErrorCode ilu0_factor_host(Mat F, Mat A, const MatFactorInfo *info) 
       else release_running = 1;
     } else { for (int t = 0; t < ps.nth; t++) free(ps.rtmp[t]); HipFree(ps.levptr); HipFree(ps.rows); HipFree(adiag); }
     HipFree(ps.rtmp); }
-  SETUP_TICK("factor: work arrays released");
-  if (ierr) SETERRQ(HipObjComm(A), 71 /* PETSC_ERR_MAT_LU_ZRPVT */, "Zero pivot row %d value %g%s", ps.fail_row, ps.fail_value, shift_nz ? ": still there after 80 diagonal shifts" : "");
+  HipSetupTick(tick0, "factor: work arrays released");
+  if (ierr) return ilu0_zero_pivot(A, info, ps.fail_row, ps.fail_value);
   return 0;
 }
 #endif
@@ -465,68 +484,89 @@ static void ilu0_row_arrays(void *c_, PetscInt lo, PetscInt hi) {
  * MatSolve_SeqAIJ_NaturalOrdering.  Fewer sweeps: an approximate application, 2k SpMV-shaped passes instead of a chain of levels.
  * Here: the negated strict triangles as CSR (the upper one taken out of the reference's backwards layout), their row-block
  * plans, dinv and the two work vectors.  A factorisation with the pattern of the last one sends the values only. */
-typedef struct { const RowArr *ra; const PetscInt *bi, *bj, *iU; const PetscScalar *ba; PetscInt *jU; PetscScalar *aL, *aU; } SweepArr;
-static void ilu0_sweeps_rows(void *c_, PetscInt lo, PetscInt hi) {
+typedef struct { const PetscInt *bi, *bj, *bdiag, *iU; const PetscScalar *ba; PetscInt *jU; PetscScalar *aL, *aU, *dinv; } SweepArr;
+static void ilu0_sweeps_rows(void *c_, PetscInt lo, PetscInt hi) {   /* the columns of the upper triangle's CSR (jU set) or the host factor's values for both triangles (aL set) */
   SweepArr *c = (SweepArr *)c_;
   for (PetscInt i = lo; i < hi; i++) {
+    const PetscInt u0 = c->bdiag[i + 1] + 1, nu = c->iU[i + 1] - c->iU[i];
+    if (c->jU) memcpy(c->jU + c->iU[i], c->bj + u0, sizeof(PetscInt) * (size_t)nu);
+    if (!c->aL) continue;
     for (PetscInt q = c->bi[i]; q < c->bi[i + 1]; q++) c->aL[q] = -c->ba[q];
-    for (PetscInt q = 0; q < c->ra->rlU[i]; q++) { c->jU[c->iU[i] + q] = c->bj[c->ra->rpU[i] + q]; c->aU[c->iU[i] + q] = -c->ba[c->ra->rpU[i] + q]; }
+    for (PetscInt q = 0; q < nu; q++) c->aU[c->iU[i] + q] = -c->ba[u0 + q];
+    c->dinv[i] = c->ba[c->bdiag[i]];
   }
 }
-static PetscErrorCode ilu0_sweeps_upload(HipTriFactors *f, PetscDeviceCtx *dc) {
-  PetscErrorCode ierr;
-  const PetscInt n = f->n, nz = f->nz, *bi = f->bi, *bj = f->bj, *bdiag = f->bdiag;
+/* the pattern side, once per pattern: index arrays and plans of the two triangles (iU: the upper one's row pointer, host), the
+ * device arrays the values go to, and what the form was built for */
+static PetscErrorCode ilu0_sweeps_pattern(HipTriFactors *f, PetscDeviceCtx *dc, const PetscInt *iU, int from_device) {
+  PetscErrorCode ierr = 0;
+  const PetscInt n = f->n, nz = f->nz, *bi = f->host.bi, *bj = f->host.bj, *bdiag = f->host.bdiag;
   const PetscInt nzL = bi[n], nzU = nz - nzL - n;
-  const size_t ni = sizeof(PetscInt) * (size_t)(n + 1), nj = sizeof(PetscInt) * (size_t)(nz + 1);
-  PetscInt *rlL, *rpU, *rlU, *iU, *jU; PetscScalar *dinv, *aL, *aU;
-  if (f->sw_planL && (!f->sw_bi || f->sw_n != n || f->sw_nz != nz || memcmp(f->sw_bi, bi, ni) || memcmp(f->sw_bdiag, bdiag, ni) || memcmp(f->sw_bj, bj, nj))) ilu0_sweeps_free(f);
-  const int fresh = !f->sw_planL;
-  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(n, 1), &rlL);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(n, 1), &rpU);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(n, 1), &rlU);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(n, 1), &dinv);CHKERRQ(ierr);
-  ierr = PetscMalloc(ni, &iU);CHKERRQ(ierr);
+  const size_t ni = sizeof(PetscInt) * (size_t)(n + 1), nj = sizeof(PetscInt) * (size_t)(nz + 1), nv = sizeof(PetscScalar) * (size_t)PetscMax(n, 1);
+  /* (value and index arrays carry the 16 bytes of slack past their end that the row-block kernels' paired loads ask for) */
+  struct { void *p; size_t bytes; } dev[] = {{&f->sw.iL, ni}, {&f->sw.iU, ni}, {&f->sw.jL, sizeof(PetscInt) * (size_t)nzL + 16}, {&f->sw.jU, sizeof(PetscInt) * (size_t)nzU + 16},
+    {&f->sw.aL, sizeof(PetscScalar) * (size_t)nzL + 16}, {&f->sw.aU, sizeof(PetscScalar) * (size_t)nzU + 16}, {&f->sw.dinv, nv}, {&f->sw.work[0], nv}, {&f->sw.work[1], nv}};
+  PetscInt *jU; int rc = 0;
   ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nzU, 1), &jU);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(nzL, 1), &aL);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(nzU, 1), &aU);CHKERRQ(ierr);
-  RowArr ra = {bi, bdiag, f->ba, rlL, rpU, rlU, dinv};
-  HipParallelRanges(n, ilu0_row_arrays, &ra);
-  iU[0] = 0;
-  for (PetscInt i = 0; i < n; i++) iU[i + 1] = iU[i] + rlU[i];
-  { SweepArr sa = {&ra, bi, bj, iU, f->ba, jU, aL, aU};
+  { SweepArr sa = {bi, bj, bdiag, iU, NULL, jU, NULL, NULL, NULL};
     HipParallelRanges(n, ilu0_sweeps_rows, &sa); }
-  int rc = 0;
-  if (fresh) {   /* (value and index arrays carry the 16 bytes of slack past their end that the row-block kernels' paired loads ask for) */
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_iL, ni);
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_iU, ni);
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_jL, sizeof(PetscInt) * (size_t)nzL + 16);
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_jU, sizeof(PetscInt) * (size_t)nzU + 16);
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_aL, sizeof(PetscScalar) * (size_t)nzL + 16);
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_aU, sizeof(PetscScalar) * (size_t)nzU + 16);
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_dinv, sizeof(PetscScalar) * (size_t)PetscMax(n, 1));
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_work[0], sizeof(PetscScalar) * (size_t)PetscMax(n, 1));
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_work[1], sizeof(PetscScalar) * (size_t)PetscMax(n, 1));
-    if (!rc) rc = mi355x_memcpy_h2d(dc->h, f->sw_iL, bi, ni);
-    if (!rc) rc = mi355x_memcpy_h2d(dc->h, f->sw_iU, iU, ni);
-    if (!rc && nzL) rc = mi355x_memcpy_h2d(dc->h, f->sw_jL, bj, sizeof(PetscInt) * (size_t)nzL);
-    if (!rc && nzU) rc = mi355x_memcpy_h2d(dc->h, f->sw_jU, jU, sizeof(PetscInt) * (size_t)nzU);
-    if (!rc) rc = mi355x_spmv_plan_create(dc->h, n, bi, NULL, &f->sw_planL);
-    if (!rc) rc = mi355x_spmv_plan_create(dc->h, n, iU, NULL, &f->sw_planU);
-  }
-  if (!rc && nzL) rc = mi355x_memcpy_h2d(dc->h, f->sw_aL, aL, sizeof(PetscScalar) * (size_t)nzL);
-  if (!rc && nzU) rc = mi355x_memcpy_h2d(dc->h, f->sw_aU, aU, sizeof(PetscScalar) * (size_t)nzU);
-  if (!rc && n) rc = mi355x_memcpy_h2d(dc->h, f->sw_dinv, dinv, sizeof(PetscScalar) * (size_t)n);
-  if (!rc) rc = mi355x_handle_synchronize(dc->h);      /* the host arrays go away below */
-  ierr = 0;
-  if (!rc && fresh) {
-    f->sw_n = n; f->sw_nz = nz;
-    ierr = PetscMalloc(ni, &f->sw_bi); if (!ierr) ierr = PetscMalloc(ni, &f->sw_bdiag); if (!ierr) ierr = PetscMalloc(nj, &f->sw_bj);
-    if (!ierr) { memcpy(f->sw_bi, bi, ni); memcpy(f->sw_bdiag, bdiag, ni); memcpy(f->sw_bj, bj, nj); }
-  }
-  HipFree(rlL); HipFree(rpU); HipFree(rlU); HipFree(dinv); HipFree(iU); HipFree(jU); HipFree(aL); HipFree(aU);
-  if (rc || ierr) ilu0_sweeps_free(f);
+  for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]) && !rc; i++) rc = mi355x_malloc((void **)dev[i].p, dev[i].bytes);
+  if (!rc) rc = mi355x_memcpy_h2d(dc->h, f->sw.iL, bi, ni);
+  if (!rc) rc = mi355x_memcpy_h2d(dc->h, f->sw.iU, iU, ni);
+  if (!rc && nzL) rc = mi355x_memcpy_h2d(dc->h, f->sw.jL, bj, sizeof(PetscInt) * (size_t)nzL);
+  if (!rc && nzU) rc = mi355x_memcpy_h2d(dc->h, f->sw.jU, jU, sizeof(PetscInt) * (size_t)nzU);
+  if (!rc) rc = mi355x_spmv_plan_create(dc->h, n, bi, NULL, &f->sw.planL);
+  if (!rc) rc = mi355x_spmv_plan_create(dc->h, n, iU, NULL, &f->sw.planU);
+  if (!rc) rc = mi355x_handle_synchronize(dc->h);      /* jU goes away below */
+  HipFree(jU);
   CHKHIP(rc);
+  f->sw.n = n; f->sw.nz = nz; f->sw.from_device = from_device;
+  if (!from_device) {   /* the host route recognises its pattern by comparing */
+    ierr = PetscMalloc(ni, &f->sw.bi); if (!ierr) ierr = PetscMalloc(ni, &f->sw.bdiag); if (!ierr) ierr = PetscMalloc(nj, &f->sw.bj);CHKERRQ(ierr);
+    memcpy(f->sw.bi, bi, ni); memcpy(f->sw.bdiag, bdiag, ni); memcpy(f->sw.bj, bj, nj);
+  }
+  return 0;
+}
+/* the values of a factor that is on the host: negated, copied, with the inverted pivots */
+static PetscErrorCode ilu0_sweeps_values_host(HipTriFactors *f, PetscDeviceCtx *dc, const PetscInt *iU) {
+  PetscErrorCode ierr;
+  const PetscInt n = f->n, nzL = f->host.bi[n], nzU = f->nz - nzL - n;
+  PetscScalar *aL; int rc = 0;
+  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)(nzL + nzU + n + 1), &aL);CHKERRQ(ierr);   /* one array for the three */
+  PetscScalar *aU = aL + nzL, *dinv = aU + nzU;
+  { SweepArr sa = {f->host.bi, f->host.bj, f->host.bdiag, iU, f->host.ba, NULL, aL, aU, dinv};
+    HipParallelRanges(n, ilu0_sweeps_rows, &sa);
+    if (nzL) rc = mi355x_memcpy_h2d(dc->h, f->sw.aL, aL, sizeof(PetscScalar) * (size_t)nzL);
+    if (!rc && nzU) rc = mi355x_memcpy_h2d(dc->h, f->sw.aU, aU, sizeof(PetscScalar) * (size_t)nzU);
+    if (!rc && n) rc = mi355x_memcpy_h2d(dc->h, f->sw.dinv, dinv, sizeof(PetscScalar) * (size_t)n);
+    if (!rc) rc = mi355x_handle_synchronize(dc->h);      /* the host arrays go away below */
+  }
+  HipFree(aL);
+  CHKHIP(rc);
+  return 0;
+}
+/* the sweep form of the factor just computed: the one an earlier factorisation of this route and this pattern left (hipmi355ximpl.h on
+ * how each route tells), or a new one; then the values, from the host factor or by two small kernels from launch.d_ba */
+static PetscErrorCode ilu0_sweeps_setup(HipTriFactors *f, PetscDeviceCtx *dc, int from_device) {
+  PetscErrorCode ierr = 0;
+  const PetscInt n = f->n, nz = f->nz, *bi = f->host.bi, *bj = f->host.bj, *bdiag = f->host.bdiag;
+  const size_t ni = sizeof(PetscInt) * (size_t)(n + 1), nj = sizeof(PetscInt) * (size_t)(nz + 1);
+  PetscInt *iU = NULL; int rc = 0;
+  if (f->sw.planL && (f->sw.from_device != from_device || f->sw.n != n || f->sw.nz != nz ||
+                      (!from_device && (memcmp(f->sw.bi, bi, ni) || memcmp(f->sw.bdiag, bdiag, ni) || memcmp(f->sw.bj, bj, nj))))) tri_free_sweeps(f);
+  const int fresh = !f->sw.planL;
+  if (fresh || !from_device) {   /* the upper triangle's row pointer, out of the reference's backwards layout */
+    ierr = PetscMalloc(ni, &iU);CHKERRQ(ierr);
+    iU[0] = 0;
+    for (PetscInt i = 0; i < n; i++) iU[i + 1] = iU[i] + (bdiag[i] - bdiag[i + 1] - 1);
+  }
+  if (fresh) ierr = ilu0_sweeps_pattern(f, dc, iU, from_device);
+  if (!ierr && !from_device) ierr = ilu0_sweeps_values_host(f, dc, iU);
+  if (!ierr && from_device) rc = mi355x_ilu0_factor_to_sweeps(dc->h, f->dev.dfac, f->sw.iU, f->launch.d_ba, f->sw.aL, f->sw.aU, f->sw.dinv);
+  HipFree(iU);
+  if (ierr || rc) tri_free_sweeps(f);
   CHKERRQ(ierr);
+  CHKHIP(rc);
   return 0;
 }
 
@@ -535,7 +575,7 @@ static PetscErrorCode ilu0_sweeps_upload(HipTriFactors *f, PetscDeviceCtx *dc) {
 static PetscErrorCode ilu0_sweeps_apply(HipTriFactors *f, Vec b, Vec x) {
   PetscErrorCode ierr;
   const PetscScalar *db; PetscScalar *dx; PetscDeviceCtx *dc;
-  const PetscInt k = f->sweeps;
+  const PetscInt k = f->sw.sweeps;
   int rc = 0;
   if (!f->n) return 0;
   ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
@@ -543,16 +583,16 @@ static PetscErrorCode ilu0_sweeps_apply(HipTriFactors *f, Vec b, Vec x) {
   ierr = VecHIPGetWrite(x, &dx);CHKERRQ(ierr);
   const PetscScalar *prev = db;
   for (PetscInt j = 0; j < k && !rc; j++) {
-    PetscScalar *out = f->sw_work[j & 1];
-    rc = mi355x_spmv_csr_add(dc->h, f->sw_planL, f->sw_iL, f->sw_jL, f->sw_aL, prev, db, out);
+    PetscScalar *out = f->sw.work[j & 1];
+    rc = mi355x_spmv_csr_add(dc->h, f->sw.planL, f->sw.iL, f->sw.jL, f->sw.aL, prev, db, out);
     prev = out;
   }
   const PetscScalar *yk = prev;
-  PetscScalar *spare = f->sw_work[k & 1], *cur = (k & 1) ? spare : dx;   /* x^0 where k steps of alternation end in dx */
-  if (!rc) rc = mi355x_vec_pointwise_mult(dc->h, (size_t)f->n, f->sw_dinv, yk, cur);
+  PetscScalar *spare = f->sw.work[k & 1], *cur = (k & 1) ? spare : dx;   /* x^0 where k steps of alternation end in dx */
+  if (!rc) rc = mi355x_vec_pointwise_mult(dc->h, (size_t)f->n, f->sw.dinv, yk, cur);
   for (PetscInt j = 0; j < k && !rc; j++) {
     PetscScalar *out = (cur == dx) ? spare : dx;
-    rc = mi355x_spmv_csr_add_scaled(dc->h, f->sw_planU, f->sw_iU, f->sw_jU, f->sw_aU, cur, yk, f->sw_dinv, out);
+    rc = mi355x_spmv_csr_add_scaled(dc->h, f->sw.planU, f->sw.iU, f->sw.jU, f->sw.aU, cur, yk, f->sw.dinv, out);
     cur = out;
   }
   ierr = VecHIPRestoreWrite(x);CHKERRQ(ierr);
@@ -565,351 +605,299 @@ static PetscErrorCode ilu0_sweeps_apply(HipTriFactors *f, Vec b, Vec x) {
 /* the device factor's values on the host (the sync-free plans' creators read them there; inside PETSc the parent's b->a) */
 static PetscErrorCode ilu0_fetch_host_ba(HipTriFactors *f, PetscDeviceCtx *dc) {
   PetscErrorCode ierr;
-  if (!f->ba) { ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)(f->nz + 1), &f->ba);CHKERRQ(ierr); }
-  CHKHIP(mi355x_memcpy_d2h(dc->h, f->ba, f->d_ba, sizeof(PetscScalar) * (size_t)(f->nz + 1)));
+  if (!f->host.ba) { ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)(f->nz + 1), &f->host.ba);CHKERRQ(ierr); }
+  CHKHIP(mi355x_memcpy_d2h(dc->h, f->host.ba, f->launch.d_ba, sizeof(PetscScalar) * (size_t)(f->nz + 1)));
   CHKHIP(mi355x_handle_synchronize(dc->h));
   return 0;
 }
-/* the sweep form from a factor whose values are on the device: pattern arrays and plans once per pattern (the device route forgets
- * them when the pattern changes), the values by two small kernels from d_ba */
-static PetscErrorCode ilu0_sweeps_from_device(HipTriFactors *f, PetscDeviceCtx *dc) {
+
+/* -pc_factor_hipmi355x_trisolve <syncfree|level|sweeps:<k>>: how MatSolve applies the factor.  sweeps: k >= 1 (there is no default
+ * count), 0 for the exact solves; syncfree: the sync-free solves are wanted (set: by the user, not by default) */
+static PetscErrorCode ilu0_trisolve_mode(Mat F, PetscInt *sweeps, int *syncfree, PetscBool *set) {
   PetscErrorCode ierr;
-  const PetscInt n = f->n, nz = f->nz, *bi = f->bi, *bj = f->bj, *bdiag = f->bdiag;
-  const PetscInt nzL = bi[n], nzU = nz - nzL - n;
-  const size_t ni = sizeof(PetscInt) * (size_t)(n + 1);
-  int rc = 0;
-  if (f->sw_planL && (f->sw_bi || f->sw_n != n || f->sw_nz != nz)) ilu0_sweeps_free(f);   /* (left by the host route, or by another pattern) */
-  if (!f->sw_planL) {
-    PetscInt *iU, *jU;
-    ierr = PetscMalloc(ni, &iU);CHKERRQ(ierr);
-    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nzU, 1), &jU);CHKERRQ(ierr);
-    iU[0] = 0;
-    for (PetscInt i = 0; i < n; i++) {
-      const PetscInt nu = bdiag[i] - bdiag[i + 1] - 1;
-      memcpy(jU + iU[i], bj + bdiag[i + 1] + 1, sizeof(PetscInt) * (size_t)nu);
-      iU[i + 1] = iU[i] + nu;
+  char mode[32] = "syncfree";
+  ierr = PetscOptionsGetString(HipObjPrefix(F), "-pc_factor_hipmi355x_trisolve", mode, sizeof(mode), set);CHKERRQ(ierr);
+  *sweeps = 0; *syncfree = !strcmp(mode, "syncfree");
+  if (!strncmp(mode, "sweeps", 6)) {
+    char *end = mode + 7; long k = 0;
+    if (mode[6] == ':' && mode[7] >= '0' && mode[7] <= '9') k = strtol(mode + 7, &end, 10);
+    if (k < 1 || k > 1000000 || *end) SETERRQ(HipObjComm(F), PETSC_ERR_ARG_WRONG, "-pc_factor_hipmi355x_trisolve sweeps:<k> needs an integer k >= 1, got %s", mode);
+    *sweeps = (PetscInt)k;
+  } else if (!*syncfree && strcmp(mode, "level")) SETERRQ(HipObjComm(F), PETSC_ERR_ARG_WRONG, "-pc_factor_hipmi355x_trisolve <syncfree|level|sweeps:<k>>, got %s", mode);
+  return 0;
+}
+
+/* The factor of a matrix with inodes: the reference solves it node by node (MatSolve_SeqAIJ_Inode, inode.c:2327-2760;
+ * MatLUFactorNumeric_SeqAIJ_Inode installs it), and so does the device: one lane per NODE, dependency levels over nodes
+ * (a node's rows were consecutive levels of the row-granular analysis), the shared column list walked once per node, two
+ * columns at a time as the reference routine does.  -pc_factor_hipmi355x_trisolve_order column: in column order -- the
+ * reference routine's bits; level (the default for such factors, as for the row-granular plans): oldest dependency
+ * first -- agreement to rounding, 1.6x faster on the FEM stand-in (profiles/r03_ilu_fem_nodes.log).
+ * On request first with whole dependency nodes as columns (a fixed number of dofs per node: one gather per dependency node;
+ * measured no faster, so not the default), then the general node plans.  *made: 0 when the factor is of neither shape (the
+ * caller goes on row by row). */
+static PetscErrorCode ilu0_node_plans(Mat F, HipTriFactors *f, PetscDeviceCtx *dc, PetscInt nodes, const PetscInt *nsizes, int by_level, const RowArr *ra, double ta0, int *made) {
+  PetscErrorCode ierr;
+  const PetscInt n = f->n, *bi = f->host.bi, *bj = f->host.bj;
+  PetscInt *nstart, nlL = 0, nlU = 0, bc = 0; PetscBool bset;
+  *made = 0;
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(3 * nodes + 1 + n), &nstart);CHKERRQ(ierr);   /* one work array: node starts, node of a row, node levels */
+  PetscInt *nodeof = nstart + nodes + 1, *nlevL = nodeof + n, *nlevU = nlevL + nodes;
+  nstart[0] = 0;
+  for (PetscInt u = 0; u < nodes; u++) { nstart[u + 1] = nstart[u] + nsizes[u]; for (PetscInt r = nstart[u]; r < nstart[u + 1] && r < n; r++) nodeof[r] = u; }
+  if (nstart[nodes] == n) {
+    for (PetscInt u = 0; u < nodes; u++) {                     /* a node may start once the nodes its FIRST row references are done */
+      PetscInt l = 0; const PetscInt r0 = nstart[u];
+      for (PetscInt q = bi[r0]; q < bi[r0 + 1]; q++) l = PetscMax(l, nlevL[nodeof[bj[q]]] + 1);
+      nlevL[u] = l; nlL = PetscMax(nlL, l + 1);
     }
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_iL, ni);
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_iU, ni);
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_jL, sizeof(PetscInt) * (size_t)nzL + 16);
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_jU, sizeof(PetscInt) * (size_t)nzU + 16);
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_aL, sizeof(PetscScalar) * (size_t)nzL + 16);
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_aU, sizeof(PetscScalar) * (size_t)nzU + 16);
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_dinv, sizeof(PetscScalar) * (size_t)PetscMax(n, 1));
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_work[0], sizeof(PetscScalar) * (size_t)PetscMax(n, 1));
-    if (!rc) rc = mi355x_malloc((void **)&f->sw_work[1], sizeof(PetscScalar) * (size_t)PetscMax(n, 1));
-    if (!rc) rc = mi355x_memcpy_h2d(dc->h, f->sw_iL, bi, ni);
-    if (!rc) rc = mi355x_memcpy_h2d(dc->h, f->sw_iU, iU, ni);
-    if (!rc && nzL) rc = mi355x_memcpy_h2d(dc->h, f->sw_jL, bj, sizeof(PetscInt) * (size_t)nzL);
-    if (!rc && nzU) rc = mi355x_memcpy_h2d(dc->h, f->sw_jU, jU, sizeof(PetscInt) * (size_t)nzU);
-    if (!rc) rc = mi355x_spmv_plan_create(dc->h, n, bi, NULL, &f->sw_planL);
-    if (!rc) rc = mi355x_spmv_plan_create(dc->h, n, iU, NULL, &f->sw_planU);
-    if (!rc) rc = mi355x_handle_synchronize(dc->h);
-    HipFree(iU); HipFree(jU);
-    f->sw_n = n; f->sw_nz = nz;
+    for (PetscInt u = nodes - 1; u >= 0; u--) {                /* upper: the columns of the node's LAST row */
+      PetscInt l = 0; const PetscInt rL = nstart[u + 1] - 1;
+      for (PetscInt q = 0; q < ra->rlU[rL]; q++) l = PetscMax(l, nlevU[nodeof[bj[ra->rpU[rL] + q]]] + 1);
+      nlevU[u] = l; nlU = PetscMax(nlU, l + 1);
+    }
+    HipSetupNote("ILU(0): ... node levels at %.3f s\n", HipWallSeconds() - ta0);
+    ierr = PetscOptionsGetInt(HipObjPrefix(F), "-pc_factor_hipmi355x_trisolve_block_columns", &bc, &bset);
+    for (int blk = bc ? 1 : 0; blk >= 0 && !ierr && !*made; blk--) {
+      if (!mi355x_trisolve_plan_create_nodes_pair(dc->h, n, nodes, nstart, by_level, blk, nlL, nlevL, bi, ra->rlL, nlU, nlevU, ra->rpU, ra->rlU, bj, ra->ba, ra->dinv, &f->syncfree.tri_lo, &f->syncfree.tri_up)) {
+        f->syncfree.nodes = nodes; f->syncfree.nlevL_nodes = nlL; f->syncfree.nlevU_nodes = nlU; f->syncfree.by_level = by_level; f->syncfree.block_columns = blk;
+        *made = 1;
+      } else tri_free_syncfree(f);                             /* not of that shape: the next, more general form */
+    }
   }
-  if (!rc) rc = mi355x_ilu0_factor_to_sweeps(dc->h, f->dfac, f->sw_iU, f->d_ba, f->sw_aL, f->sw_aU, f->sw_dinv);
-  if (rc) ilu0_sweeps_free(f);
+  HipFree(nstart);
+  CHKERRQ(ierr);
+  return 0;
+}
+
+/* the sync-free plans: node by node for the factor of a matrix with inodes, else row by row.  A factor they cannot hold (e.g. one
+ * too large for 32-bit sliced-ELL offsets) is left without plans: the level kernels serve */
+static PetscErrorCode ilu0_syncfree_plans(Mat F, Mat A, HipTriFactors *f, PetscDeviceCtx *dc, double ta0) {
+  PetscErrorCode ierr;
+  const PetscInt n = f->n;
+  /* -pc_factor_hipmi355x_trisolve_order <column|level>.  column: every row is summed in column order, the bits of
+   * MatSolve_SeqAIJ_NaturalOrdering.  level: in the order of its dependencies' levels (a row then waits on its last
+   * entries only) -- the default where the reference does not run the natural-ordering routine either: a matrix with
+   * inodes, whose factor it solves with MatSolve_SeqAIJ_Inode (inode.c; MatLUFactorNumeric_SeqAIJ_Inode installs it),
+   * in yet another order.  There the two agree to rounding.
+   * -pc_factor_hipmi355x_trisolve_nodes 0 keeps the row-granular plans for such a factor. */
+  char ord[32] = "", nodeopt[16] = ""; PetscInt nodes = 0; const PetscInt *nsizes = NULL; int made = 0, rc = 0; PetscBool set, nset;
+  RowArr ra = {f->host.bi, f->host.bdiag, NULL, NULL, NULL, NULL, NULL};
+  if (f->dev.dfac) {   /* the plans' creators take the values from the host: the factor's one copy back */
+    const double tf0 = HipWallSeconds();
+    if (f->host.owns) { ierr = ilu0_fetch_host_ba(f, dc);CHKERRQ(ierr); }   /* (inside PETSc the parent's array already holds it) */
+    HipSetupNote("ILU(0): ... factor values back on the host %.3f s\n", HipWallSeconds() - tf0);
+  }
+  ra.ba = f->host.ba;
+  ierr = PetscOptionsGetString(HipObjPrefix(F), "-pc_factor_hipmi355x_trisolve_order", ord, sizeof(ord), &set);CHKERRQ(ierr);
+  if (set && strcmp(ord, "column") && strcmp(ord, "level")) SETERRQ(HipObjComm(F), PETSC_ERR_ARG_WRONG, "-pc_factor_hipmi355x_trisolve_order <column|level>, got %s", ord);
+  ierr = MatSeqAIJHIPGetInodes(A, &nodes, &nsizes);CHKERRQ(ierr);
+  ierr = PetscOptionsGetString(HipObjPrefix(F), "-pc_factor_hipmi355x_trisolve_nodes", nodeopt, sizeof(nodeopt), &nset);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscInt) * 3 * (size_t)n, &ra.rlL);            /* (one array for the three per-row index arrays) */
+  if (!ierr) ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)n, &ra.dinv);
+  if (!ierr) {
+    ra.rpU = ra.rlL + n; ra.rlU = ra.rpU + n;
+    HipParallelRanges(n, ilu0_row_arrays, &ra);
+    HipSetupNote("ILU(0): ... row arrays + inode query at %.3f s\n", HipWallSeconds() - ta0);
+    if (nodes > 0 && !(nset && (!strcmp(nodeopt, "0") || !strcmp(nodeopt, "false")))) ierr = ilu0_node_plans(F, f, dc, nodes, nsizes, set ? !strcmp(ord, "level") : 1, &ra, ta0, &made);
+  }
+  if (!ierr && !made) {
+    f->syncfree.by_level = set ? !strcmp(ord, "level") : (nodes > 0);
+    rc = mi355x_trisolve_plan_create_pair(dc->h, n, f->syncfree.by_level, f->lev.nlevL, f->lev.rlevL, ra.bi, ra.rlL, f->host.bj, ra.ba, f->lev.nlevU, f->lev.rlevU, ra.rpU, ra.rlU, f->host.bj, ra.ba, ra.dinv, NULL, &f->syncfree.tri_lo, &f->syncfree.tri_up);
+  }
+  HipFree(ra.rlL); HipFree(ra.dinv);
+  CHKERRQ(ierr);
+  HipSetupNote("ILU(0): ... plans made at %.3f s\n", HipWallSeconds() - ta0);
+  if (rc) tri_free_syncfree(f);
+  else HipTriWatchAdd(f);
+  return 0;
+}
+
+/* the level-scheduled kernels work on the reference's layout itself, rows listed level by level.  The host routes upload all of it.
+ * On the device route the launches read launch.d_ba itself, the index arrays and the rows of L are borrowed from the context, the rows
+ * of U uploaded -- and a factorisation with the pattern of the last one finds all of it in place, the captured graph included */
+static PetscErrorCode ilu0_level_form(HipTriFactors *f, PetscDeviceCtx *dc) {
+  PetscErrorCode ierr;
+  const PetscInt n = f->n;
+  const size_t ni = sizeof(PetscInt) * (size_t)(n + 1), nj = sizeof(PetscInt) * (size_t)(f->nz + 1), na = sizeof(PetscScalar) * (size_t)(f->nz + 1), nr = sizeof(PetscInt) * (size_t)n;
+  PetscInt *rowsL = NULL, *rowsU = NULL; int rc = 0;
+  if (f->dev.dfac && f->launch.d_rowsU) return 0;
+  HipFree(f->launch.levptrL); HipFree(f->launch.levptrU); f->launch.levptrL = f->launch.levptrU = NULL;
+  ierr = level_order(n, f->lev.rlevL, f->lev.nlevL, &f->launch.levptrL, &rowsL);   /* where each level starts: kept; its rows: uploaded */
+  if (!ierr) ierr = level_order(n, f->lev.rlevU, f->lev.nlevU, &f->launch.levptrU, &rowsU);
+  if (!ierr && f->dev.dfac) {
+    const int *cbi, *cbj, *cbd, *crows;
+    rc = mi355x_ilu0_factor_arrays(f->dev.dfac, &cbi, &cbj, &cbd, &crows);
+    if (!rc) { f->launch.d_bi = (PetscInt *)cbi; f->launch.d_bj = (PetscInt *)cbj; f->launch.d_bdiag = (PetscInt *)cbd; f->launch.d_rowsL = (PetscInt *)crows; f->launch.borrowed = 1; }
+  } else if (!ierr) {
+    struct { void *p; const void *from; size_t bytes; } up[] = {{&f->launch.d_bi, f->host.bi, ni}, {&f->launch.d_bj, f->host.bj, nj}, {&f->launch.d_bdiag, f->host.bdiag, ni}, {&f->launch.d_ba, f->host.ba, na}, {&f->launch.d_rowsL, rowsL, nr}};
+    for (size_t i = 0; i < sizeof(up) / sizeof(up[0]) && !rc; i++) {
+      rc = mi355x_malloc((void **)up[i].p, PetscMax(up[i].bytes, sizeof(PetscInt)));
+      if (!rc) rc = mi355x_memcpy_h2d(dc->h, *(void **)up[i].p, up[i].from, up[i].bytes);
+    }
+  }
+  if (!ierr && !rc) rc = mi355x_malloc((void **)&f->launch.d_rowsU, PetscMax(nr, sizeof(PetscInt)));
+  if (!ierr && !rc) rc = mi355x_memcpy_h2d(dc->h, f->launch.d_rowsU, rowsU, nr);
+  if (!ierr && !rc) rc = mi355x_handle_synchronize(dc->h);   /* the rows' host copies go away below */
+  HipFree(rowsL); HipFree(rowsU);
+  CHKERRQ(ierr);
   CHKHIP(rc);
   return 0;
 }
 
-/* dependency levels of the two triangular factors, the sync-free plans, the level lists: everything MatSolve needs, from the
- * host factor in f->bi / bj / bdiag / ba (the reference's layout, whoever computed it) */
+/* everything MatSolve needs, in the form -pc_factor_hipmi355x_trisolve asks for, from the host factor in f->host (the reference's
+ * layout, whoever computed it) or, on the device route, the values in launch.d_ba.  The row levels are the factor's (lev.rlevL / rlevU)
+ * for the time of the analysis: the harness's host factorisation left them, the device route kept them from the last factorisation of
+ * this pattern (which then analyses nothing), else they are computed here; only the device route keeps them afterwards */
 static PetscErrorCode ilu0_analyse_and_upload(Mat F, Mat A) {
   PetscErrorCode ierr;
   HipTriFactors *f = HipTriGet(F);
-  const PetscInt n = f->n, *bi = f->bi, *bj = f->bj, *bdiag = f->bdiag; const PetscScalar *ba = f->ba;
   PetscDeviceCtx *dc;
-  PetscInt *lev, *levU, *rowsL = NULL, *rowsU = NULL;
-  const double ta0 = wall_s();
-  const int from_device = f->dfac != NULL;   /* the factor's values are in d_ba; the row levels stay with the factor (the next factorisation of this pattern analyses nothing) */
-  if (from_device) { lev = f->rlevL; levU = f->rlevU; }
-  else if (f->rlevL && f->rlevU) { lev = f->rlevL; levU = f->rlevU; f->rlevL = f->rlevU = NULL; }   /* the host factorisation's own analysis */
-  else { ierr = ilu0_row_levels(n, bi, bj, bdiag, &lev, &f->nlevL, &levU, &f->nlevU);CHKERRQ(ierr); }
-  if (getenv("PETSC_HIPMI355X_SETUP_TIMING")) fprintf(stderr, "[hipmi355x] ILU(0): row levels %.3f s\n", wall_s() - ta0);
-  ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-  {   /* sync-free solves: worth it as soon as the level launches would be a launch-bound chain */
-    char mode[32] = "syncfree"; PetscBool set;
-    ierr = PetscOptionsGetString(HipObjPrefix(F), "-pc_factor_hipmi355x_trisolve", mode, sizeof(mode), &set);CHKERRQ(ierr);
-    PetscInt sweeps = 0;
-    if (!strncmp(mode, "sweeps", 6)) {   /* sweeps:<k>, k >= 1; there is no default count */
-      char *end = mode + 7; long k = 0;
-      if (mode[6] == ':' && mode[7] >= '0' && mode[7] <= '9') k = strtol(mode + 7, &end, 10);
-      if (k < 1 || k > 1000000 || *end) SETERRQ(HipObjComm(F), PETSC_ERR_ARG_WRONG, "-pc_factor_hipmi355x_trisolve sweeps:<k> needs an integer k >= 1, got %s", mode);
-      sweeps = (PetscInt)k;
-    } else if (strcmp(mode, "syncfree") && strcmp(mode, "level")) SETERRQ(HipObjComm(F), PETSC_ERR_ARG_WRONG, "-pc_factor_hipmi355x_trisolve <syncfree|level|sweeps:<k>>, got %s", mode);
-    if (!sweeps) ilu0_sweeps_free(f);
-    else {   /* no sync-free plans, no level lists, not on the watch list: the level counts above are all the analysis this mode keeps */
-      if (from_device) { ierr = ilu0_sweeps_from_device(f, dc);CHKERRQ(ierr); f->sweeps = sweeps; return 0; }
-      ierr = ilu0_sweeps_upload(f, dc);
-      HipFree(lev); HipFree(levU);
-      CHKERRQ(ierr);
-      f->sweeps = sweeps;
-      return 0;
-    }
-    if (!strcmp(mode, "syncfree") && n > 0 && (f->nlevL + f->nlevU > 16 || set)) {
-      PetscInt *rpU, *rlU, *rlL; PetscScalar *dinv;
-      if (from_device) {   /* the plans' creators take the values from the host: the factor's one copy back */
-        const double tf0 = wall_s();
-        if (f->owns_host) { ierr = ilu0_fetch_host_ba(f, dc);CHKERRQ(ierr); }   /* (inside PETSc the parent's array already holds it) */
-        ba = f->ba;
-        if (getenv("PETSC_HIPMI355X_SETUP_TIMING")) fprintf(stderr, "[hipmi355x] ILU(0): ... factor values back on the host %.3f s\n", wall_s() - tf0);
-      }
-      ierr = PetscMalloc(sizeof(PetscInt) * (size_t)n, &rpU);CHKERRQ(ierr);
-      ierr = PetscMalloc(sizeof(PetscInt) * (size_t)n, &rlU);CHKERRQ(ierr);
-      ierr = PetscMalloc(sizeof(PetscInt) * (size_t)n, &rlL);CHKERRQ(ierr);
-      ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)n, &dinv);CHKERRQ(ierr);
-      { RowArr ra = {bi, bdiag, ba, rlL, rpU, rlU, dinv};
-        HipParallelRanges(n, ilu0_row_arrays, &ra); }
-      /* -pc_factor_hipmi355x_trisolve_order <column|level>.  column: every row is summed in column order, the bits of
-       * MatSolve_SeqAIJ_NaturalOrdering.  level: in the order of its dependencies' levels (a row then waits on its last
-       * entries only) -- the default where the reference does not run the natural-ordering routine either: a matrix with
-       * inodes, whose factor it solves with MatSolve_SeqAIJ_Inode (inode.c; MatLUFactorNumeric_SeqAIJ_Inode installs it),
-       * in yet another order.  There the two agree to rounding. */
-      char ord[32] = "", nodeopt[16] = ""; PetscInt nodes = 0; const PetscInt *nsizes = NULL; int by_level, rc = 1; PetscBool nset;
-      ierr = PetscOptionsGetString(HipObjPrefix(F), "-pc_factor_hipmi355x_trisolve_order", ord, sizeof(ord), &set);CHKERRQ(ierr);
-      if (set && strcmp(ord, "column") && strcmp(ord, "level")) SETERRQ(HipObjComm(F), PETSC_ERR_ARG_WRONG, "-pc_factor_hipmi355x_trisolve_order <column|level>, got %s", ord);
-      ierr = MatSeqAIJHIPGetInodes(A, &nodes, &nsizes);CHKERRQ(ierr);
-      if (getenv("PETSC_HIPMI355X_SETUP_TIMING")) fprintf(stderr, "[hipmi355x] ILU(0): ... row arrays + inode query at %.3f s\n", wall_s() - ta0);
-      ierr = PetscOptionsGetString(HipObjPrefix(F), "-pc_factor_hipmi355x_trisolve_nodes", nodeopt, sizeof(nodeopt), &nset);CHKERRQ(ierr);
-      f->nodes = 0;
-      if (nodes > 0 && !(nset && (!strcmp(nodeopt, "0") || !strcmp(nodeopt, "false")))) {
-        /* The factor of a matrix with inodes: the reference solves it node by node (MatSolve_SeqAIJ_Inode, inode.c:2327-2760;
-         * MatLUFactorNumeric_SeqAIJ_Inode installs it), and so does the device: one lane per NODE, dependency levels over nodes
-         * (a node's rows were consecutive levels of the row-granular analysis), the shared column list walked once per node, two
-         * columns at a time as the reference routine does.  -pc_factor_hipmi355x_trisolve_order column: in column order -- the
-         * reference routine's bits; level (the default for such factors, as for the row-granular plans): oldest dependency
-         * first -- agreement to rounding, 1.6x faster on the FEM stand-in (profiles/r03_ilu_fem_nodes.log).
-         * -pc_factor_hipmi355x_trisolve_nodes 0 keeps the row-granular plans. */
-        PetscInt *nstart, *nodeof, *nlevL, *nlevU, nlL = 0, nlU = 0;
-        ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nodes + 1), &nstart);CHKERRQ(ierr);
-        ierr = PetscMalloc(sizeof(PetscInt) * (size_t)n, &nodeof);CHKERRQ(ierr);
-        ierr = PetscMalloc(sizeof(PetscInt) * (size_t)nodes, &nlevL);CHKERRQ(ierr);
-        ierr = PetscMalloc(sizeof(PetscInt) * (size_t)nodes, &nlevU);CHKERRQ(ierr);
-        nstart[0] = 0;
-        for (PetscInt u = 0; u < nodes; u++) { nstart[u + 1] = nstart[u] + nsizes[u]; for (PetscInt r = nstart[u]; r < nstart[u + 1] && r < n; r++) nodeof[r] = u; }
-        if (nstart[nodes] == n) {
-          for (PetscInt u = 0; u < nodes; u++) {                     /* a node may start once the nodes its FIRST row references are done */
-            PetscInt l = 0; const PetscInt r0 = nstart[u];
-            for (PetscInt q = bi[r0]; q < bi[r0 + 1]; q++) l = PetscMax(l, nlevL[nodeof[bj[q]]] + 1);
-            nlevL[u] = l; nlL = PetscMax(nlL, l + 1);
-          }
-          for (PetscInt u = nodes - 1; u >= 0; u--) {                /* upper: the columns of the node's LAST row */
-            PetscInt l = 0; const PetscInt rL = nstart[u + 1] - 1;
-            for (PetscInt q = 0; q < rlU[rL]; q++) l = PetscMax(l, nlevU[nodeof[bj[rpU[rL] + q]]] + 1);
-            nlevU[u] = l; nlU = PetscMax(nlU, l + 1);
-          }
-          by_level = set ? !strcmp(ord, "level") : 1;
-          if (getenv("PETSC_HIPMI355X_SETUP_TIMING")) fprintf(stderr, "[hipmi355x] ILU(0): ... node levels at %.3f s\n", wall_s() - ta0);
-          /* on request first with whole dependency nodes as columns (a fixed number of dofs per node: one gather per dependency
-           * node; measured no faster, so not the default), then the general node plans, then (below) row by row */
-          PetscInt bc = 0; PetscBool bset;
-          ierr = PetscOptionsGetInt(HipObjPrefix(F), "-pc_factor_hipmi355x_trisolve_block_columns", &bc, &bset);CHKERRQ(ierr);
-          for (int blk = bc ? 1 : 0; blk >= 0; blk--) {
-            rc = mi355x_trisolve_plan_create_nodes_pair(dc->h, n, nodes, nstart, by_level, blk, nlL, nlevL, bi, rlL, nlU, nlevU, rpU, rlU, bj, ba, dinv, &f->tri_lo, &f->tri_up);
-            if (!rc) { f->nodes = nodes; f->nlevL_nodes = nlL; f->nlevU_nodes = nlU; f->by_level = by_level; f->block_columns = blk; break; }
-            if (f->tri_lo) mi355x_trisolve_plan_destroy(f->tri_lo);      /* not of that shape: the next, more general form */
-            if (f->tri_up) mi355x_trisolve_plan_destroy(f->tri_up);
-            f->tri_lo = f->tri_up = NULL;
-          }
-        }
-        HipFree(nstart); HipFree(nodeof); HipFree(nlevL); HipFree(nlevU);
-      }
-      if (rc) {
-        by_level = set ? !strcmp(ord, "level") : (nodes > 0);
-        f->by_level = by_level;
-        rc = mi355x_trisolve_plan_create_pair(dc->h, n, by_level, f->nlevL, lev, bi, rlL, bj, ba, f->nlevU, levU, rpU, rlU, bj, ba, dinv, NULL, &f->tri_lo, &f->tri_up);
-      }
-      HipFree(rpU); HipFree(rlU); HipFree(rlL); HipFree(dinv);
-      if (getenv("PETSC_HIPMI355X_SETUP_TIMING")) fprintf(stderr, "[hipmi355x] ILU(0): ... plans made at %.3f s\n", wall_s() - ta0);
-      if (rc) {   /* e.g. a factor too large for 32-bit sliced-ELL offsets: the level kernels serve */
-        if (f->tri_lo) mi355x_trisolve_plan_destroy(f->tri_lo);
-        if (f->tri_up) mi355x_trisolve_plan_destroy(f->tri_up);
-        f->tri_lo = f->tri_up = NULL;
-      } else HipTriWatchAdd(f);
-    }
+  PetscInt sweeps = 0; int syncfree = 0; PetscBool set;
+  const double ta0 = HipWallSeconds();
+  const int from_device = f->dev.dfac != NULL;
+  if (!f->lev.rlevL || !f->lev.rlevU) { ierr = ilu0_row_levels(f->n, f->host.bi, f->host.bj, f->host.bdiag, &f->lev.rlevL, &f->lev.nlevL, &f->lev.rlevU, &f->lev.nlevU);CHKERRQ(ierr); }
+  HipSetupNote("ILU(0): row levels %.3f s\n", HipWallSeconds() - ta0);
+  ierr = PetscDeviceGet(&dc);
+  if (!ierr) ierr = ilu0_trisolve_mode(F, &sweeps, &syncfree, &set);
+  if (!ierr && sweeps) {   /* no sync-free plans, no level lists, not on the watch list: the level counts are all the analysis this mode keeps */
+    ierr = ilu0_sweeps_setup(f, dc, from_device);
+    if (!ierr) f->sw.sweeps = sweeps;
+  } else if (!ierr) {
+    tri_free_sweeps(f);
+    /* sync-free solves: worth it as soon as the level launches would be a launch-bound chain */
+    if (syncfree && f->n > 0 && (f->lev.nlevL + f->lev.nlevU > 16 || set)) ierr = ilu0_syncfree_plans(F, A, f, dc, ta0);
+    if (!ierr && !f->syncfree.tri_lo) ierr = ilu0_level_form(f, dc);
   }
-  if (!f->tri_lo && from_device) {   /* the level launches read d_ba itself; the index arrays and the rows of L by level are the context's */
-    if (!f->d_rowsU) {               /* (a factorisation with the pattern of the last one finds all of it in place, the captured graph included) */
-      const int *cbi, *cbj, *cbd, *crows;
-      HipFree(f->levptrL); HipFree(f->levptrU); f->levptrL = f->levptrU = NULL;
-      ierr = level_order(n, lev, f->nlevL, &f->levptrL, &rowsL);CHKERRQ(ierr);
-      ierr = level_order(n, levU, f->nlevU, &f->levptrU, &rowsU);CHKERRQ(ierr);
-      CHKHIP(mi355x_ilu0_factor_arrays(f->dfac, &cbi, &cbj, &cbd, &crows));
-      f->d_bi = (PetscInt *)cbi; f->d_bj = (PetscInt *)cbj; f->d_bdiag = (PetscInt *)cbd; f->d_rowsL = (PetscInt *)crows; f->d_borrowed = 1;
-      CHKHIP(mi355x_malloc((void **)&f->d_rowsU, sizeof(PetscInt) * (size_t)PetscMax(n, 1)));
-      CHKHIP(mi355x_memcpy_h2d(dc->h, f->d_rowsU, rowsU, sizeof(PetscInt) * (size_t)n));
-      CHKHIP(mi355x_handle_synchronize(dc->h));
-    }
-  } else if (!f->tri_lo) {   /* the level-scheduled kernels work on the reference's layout itself, rows listed level by level */
-    ierr = level_order(n, lev, f->nlevL, &f->levptrL, &rowsL);CHKERRQ(ierr);
-    ierr = level_order(n, levU, f->nlevU, &f->levptrU, &rowsU);CHKERRQ(ierr);
-    CHKHIP(mi355x_malloc((void **)&f->d_bi, sizeof(PetscInt) * (size_t)(n + 1)));
-    CHKHIP(mi355x_malloc((void **)&f->d_bj, sizeof(PetscInt) * (size_t)(f->nz + 1)));
-    CHKHIP(mi355x_malloc((void **)&f->d_bdiag, sizeof(PetscInt) * (size_t)(n + 1)));
-    CHKHIP(mi355x_malloc((void **)&f->d_ba, sizeof(PetscScalar) * (size_t)(f->nz + 1)));
-    CHKHIP(mi355x_malloc((void **)&f->d_rowsL, sizeof(PetscInt) * (size_t)PetscMax(n, 1)));
-    CHKHIP(mi355x_malloc((void **)&f->d_rowsU, sizeof(PetscInt) * (size_t)PetscMax(n, 1)));
-    CHKHIP(mi355x_memcpy_h2d(dc->h, f->d_bi, bi, sizeof(PetscInt) * (size_t)(n + 1)));
-    CHKHIP(mi355x_memcpy_h2d(dc->h, f->d_bj, bj, sizeof(PetscInt) * (size_t)(f->nz + 1)));
-    CHKHIP(mi355x_memcpy_h2d(dc->h, f->d_bdiag, bdiag, sizeof(PetscInt) * (size_t)(n + 1)));
-    CHKHIP(mi355x_memcpy_h2d(dc->h, f->d_ba, ba, sizeof(PetscScalar) * (size_t)(f->nz + 1)));
-    CHKHIP(mi355x_memcpy_h2d(dc->h, f->d_rowsL, rowsL, sizeof(PetscInt) * (size_t)n));
-    CHKHIP(mi355x_memcpy_h2d(dc->h, f->d_rowsU, rowsU, sizeof(PetscInt) * (size_t)n));
-    CHKHIP(mi355x_handle_synchronize(dc->h));
-  }
-  HipFree(rowsL); HipFree(rowsU);
-  if (!from_device) { HipFree(lev); HipFree(levU); }
+  if (!from_device) { HipFree(f->lev.rlevL); HipFree(f->lev.rlevU); f->lev.rlevL = f->lev.rlevU = NULL; }
+  CHKERRQ(ierr);
   return 0;
 }
 
+/* the device route's symbolic side, once per pattern: pattern and row levels on the host (kept), the context, the array of the values */
+static PetscErrorCode ilu0_device_symbolic(Mat F, Mat A, PetscDeviceCtx *dc, PetscInt nblk, const PetscInt *blk, double *clock) {
+  PetscErrorCode ierr;
+  HipTriFactors *f = HipTriGet(F);
+  PetscInt n, *levptr = NULL, *rows = NULL; const PetscInt *ai, *aj;
+  ierr = MatSeqAIJGetArrays(A, &n, &ai, &aj, NULL);CHKERRQ(ierr);
+  HipTriFactorsResetNumeric(f);
+  tri_free_sweeps(f);
+  f->n = n; f->nz = ai[n];
+#if defined(PETSCHIPMI355X_WITH_PETSC)
+  { Mat_SeqAIJ *b = (Mat_SeqAIJ *)F->data;   /* the parent's symbolic arrays (MatILUFactorSymbolic_SeqAIJ_ilu0) */
+    f->nz = b->nz; f->host.bi = b->i; f->host.bj = b->j; f->host.bdiag = b->diag; f->host.ba = b->a; f->host.owns = PETSC_FALSE; }
+#else
+  ierr = ilu0_symbolic_host(A, n, ai, aj, f, NULL, NULL, NULL);CHKERRQ(ierr);
+#endif
+  HipSetupTick(*clock, "factor (device): pattern of L and U");
+  ierr = ilu0_check_blocks(A, ai, aj, nblk, blk);CHKERRQ(ierr);
+  ierr = ilu0_row_levels(n, f->host.bi, f->host.bj, f->host.bdiag, &f->lev.rlevL, &f->lev.nlevL, &f->lev.rlevU, &f->lev.nlevU);CHKERRQ(ierr);
+  ierr = level_order(n, f->lev.rlevL, f->lev.nlevL, &levptr, &rows);CHKERRQ(ierr);
+  HipSetupTick(*clock, "factor (device): levels of L and U");
+  int rc = mi355x_ilu0_factor_create(dc->h, n, f->host.bi, f->host.bj, f->host.bdiag, f->lev.nlevL, levptr, rows, nblk, blk, &f->dev.dfac);
+  HipFree(levptr); HipFree(rows);
+  if (!rc) rc = mi355x_malloc((void **)&f->launch.d_ba, sizeof(PetscScalar) * (size_t)(f->nz + 1));
+  if (!rc) rc = mi355x_memset(dc->h, f->launch.d_ba, 0, sizeof(PetscScalar) * (size_t)(f->nz + 1));   /* (the slot past the last value is never written) */
+  CHKHIP(rc);
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nblk + 1), &f->dev.blk);CHKERRQ(ierr);
+  memcpy(f->dev.blk, blk, sizeof(PetscInt) * (size_t)(nblk + 1));
+  f->dev.gen = ((Mat_SeqAIJHIP *)A->spptr)->pattern_gen; f->dev.n = n; f->dev.nz = ai[n]; f->dev.nblk = nblk; f->dev.stale = 0;
+  f->symbolic_builds++;
+  HipSetupTick(*clock, "factor (device): context and index upload");
+  return 0;
+}
+/* the numeric passes on the device.  The shift rule is ilu0_factor_host's (ilu0_next_shift), per independent block, all blocks in
+ * one pass: a block whose pass reports a failing pivot runs again shifted, the other blocks' rows skip their work in those passes */
+static PetscErrorCode ilu0_device_numeric(Mat A, HipTriFactors *f, PetscDeviceCtx *dc, PetscInt nblk, const MatFactorInfo *info, double *clock) {
+  PetscErrorCode ierr;
+  Mat_SeqAIJHIP *d = (Mat_SeqAIJHIP *)A->spptr;
+  PetscReal *shifts = NULL, badval = 0.0; PetscInt *nsh = NULL, badrow = -1; int rc = 0, any = 1;
+  ierr = PetscMalloc(sizeof(PetscReal) * 2 * (size_t)nblk, &shifts);       /* per block: the shift and the failing pivot's size; */
+  if (!ierr) ierr = PetscMalloc(sizeof(PetscInt) * 2 * (size_t)nblk, &nsh);   /* the shifts taken and the failing row */
+  if (ierr) { HipFree(shifts); CHKERRQ(ierr); }
+  PetscReal *fabsv = shifts + nblk; PetscInt *frow = nsh + nblk;
+  for (PetscInt bb = 0; bb < nblk; bb++) { shifts[bb] = 0.0; nsh[bb] = 0; }
+  mi355x_ilu0_factor_reset(f->dev.dfac);
+  while (any && !ierr && !rc) {
+    any = 0;
+    rc = mi355x_ilu0_factor_run(dc->h, f->dev.dfac, d->mat.i, d->mat.j, d->mat.a, info->zeropivot, shifts, f->launch.d_ba, frow, fabsv);
+    for (PetscInt bb = 0; bb < nblk && !ierr && !rc; bb++) {
+      if (frow[bb] < 0) continue;
+      if (!any) { badrow = frow[bb]; badval = fabsv[bb]; }
+      any = 1;
+      ierr = ilu0_next_shift(info, &shifts[bb], &nsh[bb]);
+    }
+  }
+  f->nshift = 0;
+  for (PetscInt bb = 0; bb < nblk; bb++) f->nshift = PetscMax(f->nshift, nsh[bb]);
+  HipFree(shifts); HipFree(nsh);
+  HipSetupTick(*clock, "factor (device): numeric passes");
+  CHKHIP(rc);
+  if (ierr) return ilu0_zero_pivot(A, info, badrow, badval);
+  f->numeric_runs++;
+  return 0;
+}
 /* -pc_factor_hipmi355x_numeric device: the numeric ILU(0) on the device, one launch per dependency level of L
- * (mi355x_ilu0_factor_*, csrc/ilu_factor.hip), reading A's device copy in place and writing the factor's values to d_ba.  The
+ * (mi355x_ilu0_factor_*, csrc/ilu_factor.hip), reading A's device copy in place and writing the factor's values to launch.d_ba.  The
  * symbolic work -- diagonal positions, pattern of L and U, row levels -- stays on the host and is kept with the factor: a
  * factorisation whose A has the pattern of the last one (the same upload of the operator's pattern, Mat_SeqAIJHIP.pattern_gen -- a serial number no other matrix or
- * later pattern shares -- with the same sizes and the same independent blocks) runs the numeric kernels only.  The shift loop is
- * ilu0_factor_host's, per independent block: a block whose pass reports a failing pivot runs again with shiftamount, then twice
- * that, ... (MatPivotCheck_nz, matimpl.h:512-528); the other blocks' rows skip their work in those passes. */
+ * later pattern shares -- with the same sizes and the same independent blocks) runs the numeric kernels only. */
 static PetscErrorCode ilu0_factor_device(Mat F, Mat A, const MatFactorInfo *info) {
   PetscErrorCode ierr;
   HipTriFactors *f = HipTriGet(F);
   Mat_SeqAIJHIP *d = (Mat_SeqAIJHIP *)A->spptr;
   PetscDeviceCtx *dc;
-  PetscInt n; const PetscInt *ai, *aj; const PetscScalar *aa;
-  double tick0 = wall_s();
+  PetscInt n, whole[2]; const PetscInt *ai, *aj, *blk;
+  double tick0 = HipWallSeconds();
   ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-  ierr = MatSeqAIJGetArrays(A, &n, &ai, &aj, &aa);CHKERRQ(ierr);
-  (void)aa;                                                               /* (the values are read on the device) */
+  ierr = MatSeqAIJGetArrays(A, &n, &ai, &aj, NULL);CHKERRQ(ierr);          /* (the values are read on the device) */
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
   if (d->cprow || d->mat.bs != 1 || (n > 0 && !d->mat.a)) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "-pc_factor_hipmi355x_numeric device needs the operator's plain CSR copy on the device");
-  SETUP_TICK("factor (device): operator current");
-  const PetscInt whole[2] = {0, n};
-  const int blocked = f->nblk > 0 && f->blk[f->nblk] == n;
-  const PetscInt nblk = blocked ? f->nblk : 1, *blk = blocked ? f->blk : whole;
-  const int same = f->dfac && !f->dfac_stale && d->pattern_gen && f->dfac_gen == d->pattern_gen && f->dfac_n == n && f->dfac_nz == ai[n] &&
-                   f->dfac_nblk == nblk && !memcmp(f->dfac_blk, blk, sizeof(PetscInt) * (size_t)(nblk + 1));
+  HipSetupTick(tick0, "factor (device): operator current");
+  const PetscInt nblk = HipTriFactorsBlocks(f, n, whole, &blk);
+  const int same = f->dev.dfac && !f->dev.stale && d->pattern_gen && f->dev.gen == d->pattern_gen && f->dev.n == n && f->dev.nz == ai[n] &&
+                   f->dev.nblk == nblk && !memcmp(f->dev.blk, blk, sizeof(PetscInt) * (size_t)(nblk + 1));
   f->factored_state = -1;
   if (same) {   /* values only: the plans that carry values go, everything built from the pattern stays */
-    if (f->tri_lo) mi355x_trisolve_plan_destroy(f->tri_lo);
-    if (f->tri_up) mi355x_trisolve_plan_destroy(f->tri_up);
-    f->tri_lo = f->tri_up = NULL; f->use_levels = 0; f->nshift = 0; f->sweeps = 0;
-  } else {
-    PetscInt *levptr = NULL, *rows = NULL;
-    tri_reset_numeric(f);
-    ilu0_sweeps_free(f);
-    f->n = n; f->nz = ai[n];
-#if defined(PETSCHIPMI355X_WITH_PETSC)
-    { Mat_SeqAIJ *b = (Mat_SeqAIJ *)F->data;   /* the parent's symbolic arrays (MatILUFactorSymbolic_SeqAIJ_ilu0) */
-      f->nz = b->nz; f->bi = b->i; f->bj = b->j; f->bdiag = b->diag; f->ba = b->a; f->owns_host = PETSC_FALSE; }
-#else
-    { PetscInt *adiag;
-      f->owns_host = PETSC_TRUE;
-      ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(n, 1), &adiag);CHKERRQ(ierr);
-      IluSym sy = {ai, aj, adiag, NULL, NULL, NULL, -1};
-      HipParallelRanges(n, ilu0_sym_diag, &sy);
-      if (sy.missing >= 0) {
-        PetscInt first = 0;
-        while (first < n && adiag[first] >= 0) first++;
-        HipFree(adiag);
-        SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "Matrix is missing diagonal entry %d", first);
-      }
-      ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(n + 1), &f->bi);CHKERRQ(ierr);
-      ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(f->nz + 1), &f->bj);CHKERRQ(ierr);
-      ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(n + 1), &f->bdiag);CHKERRQ(ierr);
-      f->bi[0] = 0;
-      for (PetscInt i = 0; i < n; i++) f->bi[i + 1] = f->bi[i] + (adiag[i] - ai[i]);
-      f->bdiag[n] = f->bi[n] - 1;
-      for (PetscInt i = n - 1; i >= 0; i--) f->bdiag[i] = f->bdiag[i + 1] + (ai[i + 1] - adiag[i] - 1) + 1;
-      sy.bi = f->bi; sy.bj = f->bj; sy.bdiag = f->bdiag;
-      HipParallelRanges(n, ilu0_sym_pattern, &sy);
-      HipFree(adiag); }
-#endif
-    SETUP_TICK("factor (device): pattern of L and U");
-    for (PetscInt bb = 0; bb < nblk; bb++)
-      for (PetscInt i = blk[bb]; i < blk[bb + 1]; i++)
-        if (ai[i] < ai[i + 1] && (aj[ai[i]] < blk[bb] || aj[ai[i + 1] - 1] >= blk[bb + 1])) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "row %d couples to a column outside its independent block", i);
-    ierr = ilu0_row_levels(n, f->bi, f->bj, f->bdiag, &f->rlevL, &f->nlevL, &f->rlevU, &f->nlevU);CHKERRQ(ierr);
-    ierr = level_order(n, f->rlevL, f->nlevL, &levptr, &rows);CHKERRQ(ierr);
-    SETUP_TICK("factor (device): levels of L and U");
-    int rc = mi355x_ilu0_factor_create(dc->h, n, f->bi, f->bj, f->bdiag, f->nlevL, levptr, rows, nblk, blk, &f->dfac);
-    HipFree(levptr); HipFree(rows);
-    if (!rc) rc = mi355x_malloc((void **)&f->d_ba, sizeof(PetscScalar) * (size_t)(f->nz + 1));
-    if (!rc) rc = mi355x_memset(dc->h, f->d_ba, 0, sizeof(PetscScalar) * (size_t)(f->nz + 1));   /* (the slot past the last value is never written) */
-    CHKHIP(rc);
-    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nblk + 1), &f->dfac_blk);CHKERRQ(ierr);
-    memcpy(f->dfac_blk, blk, sizeof(PetscInt) * (size_t)(nblk + 1));
-    f->dfac_gen = d->pattern_gen; f->dfac_n = n; f->dfac_nz = ai[n]; f->dfac_nblk = nblk; f->dfac_stale = 0;
-    f->symbolic_builds++;
-    SETUP_TICK("factor (device): context and index upload");
-  }
-  const PetscReal shiftamount = info->shiftamount;
-  const PetscBool shift_nz = (PetscBool)(info->shifttype == (PetscReal)MAT_SHIFT_NONZERO);
-  PetscScalar *shifts, *fabsv; PetscInt *nsh, *frow, badrow = -1; PetscReal badval = 0.0; int rc = 0;
-  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)nblk, &shifts);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)nblk, &fabsv);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)nblk, &nsh);CHKERRQ(ierr);
-  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)nblk, &frow);CHKERRQ(ierr);
-  for (PetscInt bb = 0; bb < nblk; bb++) { shifts[bb] = 0.0; nsh[bb] = 0; }
-  mi355x_ilu0_factor_reset(f->dfac);
-  ierr = 0;
-  for (;;) {
-    int any = 0;
-    rc = mi355x_ilu0_factor_run(dc->h, f->dfac, d->mat.i, d->mat.j, d->mat.a, info->zeropivot, shifts, f->d_ba, frow, fabsv);
-    if (rc) break;
-    for (PetscInt bb = 0; bb < nblk && !ierr; bb++) {
-      if (frow[bb] < 0) continue;
-      if (!any) { badrow = frow[bb]; badval = fabsv[bb]; }
-      any = 1;
-      if (!shift_nz) { ierr = PETSC_ERR_ARG_WRONG; break; }
-      shifts[bb] = nsh[bb] ? shifts[bb] * 2.0 : shiftamount;
-      if (++nsh[bb] > 80) ierr = PETSC_ERR_ARG_WRONG;
-    }
-    if (ierr || !any) break;
-  }
-  f->nshift = 0;
-  for (PetscInt bb = 0; bb < nblk; bb++) f->nshift = PetscMax(f->nshift, nsh[bb]);
-  HipFree(shifts); HipFree(fabsv); HipFree(nsh); HipFree(frow);
-  SETUP_TICK("factor (device): numeric passes");
-  CHKHIP(rc);
-  if (ierr) SETERRQ(HipObjComm(A), 71 /* PETSC_ERR_MAT_LU_ZRPVT */, "Zero pivot row %d value %g%s", badrow, badval, shift_nz ? ": still there after 80 diagonal shifts" : "");
-  f->numeric_runs++;
+    tri_free_syncfree(f);
+    f->nshift = 0; f->sw.sweeps = 0;
+  } else { ierr = ilu0_device_symbolic(F, A, dc, nblk, blk, &tick0);CHKERRQ(ierr); }
+  ierr = ilu0_device_numeric(A, f, dc, nblk, info, &tick0);CHKERRQ(ierr);
 #if defined(PETSCHIPMI355X_WITH_PETSC)
   ierr = ilu0_fetch_host_ba(f, dc);CHKERRQ(ierr);                        /* the parent's b->a holds the factor, as after its own routine */
   F->assembled = PETSC_TRUE; F->preallocated = PETSC_TRUE;
-  SETUP_TICK("factor (device): values to the parent's array");
+  HipSetupTick(tick0, "factor (device): values to the parent's array");
 #endif
   return 0;
 }
 
 static PetscErrorCode MatSolve_SeqAIJHIP_ILU(Mat F, Vec b, Vec x);
-
 static PetscErrorCode MatLUFactorNumeric_SeqAIJHIP(Mat F, Mat A, const MatFactorInfo *info) {   /* MatLUFactorNumeric_SeqAIJCUSPARSE, aijcusparse.cu:358-376 */
   PetscErrorCode ierr;
   HipTriFactors *f = HipTriGet(F);
-  const double t0 = wall_s();
+  const double t0 = HipWallSeconds();
   int on_device = 0;
   if (A->rmap->n != A->cmap->n) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "Must be square matrix, rows %d columns %d", A->rmap->n, A->cmap->n);
-  if (f->factored_state == HipObjState(A) && f->factored_of == (void *)A && (f->tri_lo || f->d_ba || f->sweeps)) return 0;   /* same operator, same values: nothing to redo */
+  if (f->factored_state == HipObjState(A) && f->factored_of == (void *)A && (f->syncfree.tri_lo || f->launch.d_ba || f->sw.sweeps)) return 0;   /* same operator, same values: nothing to redo */
   { char where[16] = "host"; PetscBool set;   /* -pc_factor_hipmi355x_numeric <host|device>, an opt-in */
     ierr = PetscOptionsGetString(HipObjPrefix(F), "-pc_factor_hipmi355x_numeric", where, sizeof(where), &set);CHKERRQ(ierr);
     if (strcmp(where, "host") && strcmp(where, "device")) SETERRQ(HipObjComm(F), PETSC_ERR_ARG_WRONG, "-pc_factor_hipmi355x_numeric <host|device>, got %s", where);
     on_device = !strcmp(where, "device"); }
   if (on_device) { ierr = ilu0_factor_device(F, A, info);CHKERRQ(ierr); }
   else {
-    tri_reset_numeric(f);
+    HipTriFactorsResetNumeric(f);
 #if defined(PETSCHIPMI355X_WITH_PETSC)
     ierr = MatLUFactorNumeric_SeqAIJ(F, A, info);CHKERRQ(ierr);            /* the parent's factorisation into F's own Mat_SeqAIJ */
     { Mat_SeqAIJ *b = (Mat_SeqAIJ *)F->data;
-      f->n = A->rmap->n; f->nz = b->nz; f->bi = b->i; f->bj = b->j; f->bdiag = b->diag; f->ba = b->a; f->owns_host = PETSC_FALSE; }
+      f->n = A->rmap->n; f->nz = b->nz; f->host.bi = b->i; f->host.bj = b->j; f->host.bdiag = b->diag; f->host.ba = b->a; f->host.owns = PETSC_FALSE; }
 #else
     ierr = ilu0_factor_host(F, A, info);CHKERRQ(ierr);
 #endif
     f->symbolic_builds++; f->numeric_runs++;
   }
-  const double t1 = wall_s();
+  const double t1 = HipWallSeconds();
   ierr = ilu0_analyse_and_upload(F, A);CHKERRQ(ierr);
-  if (getenv("PETSC_HIPMI355X_SETUP_TIMING")) fprintf(stderr, "[hipmi355x] ILU(0) n=%d: %s factorisation %.3f s, level analysis + plans + upload %.3f s\n", (int)f->n, on_device ? "device" : "host", t1 - t0, wall_s() - t1);
+  HipSetupNote("ILU(0) n=%d: %s factorisation %.3f s, level analysis + plans + upload %.3f s\n", (int)f->n, on_device ? "device" : "host", t1 - t0, HipWallSeconds() - t1);
   F->ops->solve = MatSolve_SeqAIJHIP_ILU;                                 /* aijcusparse.cu:372-373 */
   f->factored_state = HipObjState(A); f->factored_of = (void *)A;
   return 0;
@@ -922,7 +910,7 @@ static PetscErrorCode MatILUFactorSymbolic_SeqAIJHIP(Mat F, Mat A, IS row, IS co
   ierr = MatILUFactorSymbolic_SeqAIJ(F, A, row, col, info);CHKERRQ(ierr);
 #endif
   HipTriGet(F)->factored_state = -1;
-  HipTriGet(F)->dfac_stale = 1;                                            /* a new symbolic phase: the device route's context is of the old pattern */
+  HipTriGet(F)->dev.stale = 1;                                            /* a new symbolic phase: the device route's context is of the old pattern */
   F->ops->lufactornumeric = MatLUFactorNumeric_SeqAIJHIP;
   return 0;
 }
@@ -937,16 +925,16 @@ PetscErrorCode HipTriFactorsApply(Mat F, HipTriFactors *f, Vec b, Vec x, PetscLo
   ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
   ierr = VecHIPGetRead(b, &db);CHKERRQ(ierr);
   ierr = VecHIPGetWrite(x, &dx);CHKERRQ(ierr);
-  if (f->use_levels) rc = mi355x_trisolve_apply_levels(dc->h, f->tri_lo, f->tri_up, db, dx);
+  if (f->syncfree.use_levels) rc = mi355x_trisolve_apply_levels(dc->h, f->syncfree.tri_lo, f->syncfree.tri_up, db, dx);
   else {
-    rc = mi355x_trisolve_apply(dc->h, f->tri_lo, f->tri_up, db, dx);
+    rc = mi355x_trisolve_apply(dc->h, f->syncfree.tri_lo, f->syncfree.tri_up, db, dx);
     if (rc == 719) {   /* hipErrorLaunchFailure: an earlier application gave up and no host wait has noticed yet: this one runs level by level */
-      f->use_levels = 1; f->aborted = 1;
-      rc = mi355x_trisolve_apply_levels(dc->h, f->tri_lo, f->tri_up, db, dx);
+      f->syncfree.use_levels = 1; f->aborted = 1;
+      rc = mi355x_trisolve_apply_levels(dc->h, f->syncfree.tri_lo, f->syncfree.tri_up, db, dx);
     } else if (rc == 1 || rc == 701 || rc == 720) {   /* hipErrorInvalidValue / LaunchOutOfResources / cooperative too large: the sync-free kernels could not be launched on this
                                                         * device (LDS, registers): nothing ran, so the same plans serve one launch per level from now on */
-      f->use_levels = 1;
-      rc = mi355x_trisolve_apply_levels(dc->h, f->tri_lo, f->tri_up, db, dx);
+      f->syncfree.use_levels = 1;
+      rc = mi355x_trisolve_apply_levels(dc->h, f->syncfree.tri_lo, f->syncfree.tri_up, db, dx);
     }
   }
   ierr = VecHIPRestoreWrite(x);CHKERRQ(ierr);      /* also on the error path: x is not left in write state */
@@ -957,42 +945,42 @@ PetscErrorCode HipTriFactorsApply(Mat F, HipTriFactors *f, Vec b, Vec x, PetscLo
   return 0;
 }
 
+/* the level launches: L's levels forward from in to out, then U's backwards in place on out (in == out: in place throughout) */
+static int ilu0_launch_levels(PetscDeviceCtx *dc, const HipTriFactors *f, const PetscScalar *in, PetscScalar *out) {
+  int rc = 0;
+  for (PetscInt l = 0; l < f->lev.nlevL && !rc; l++)
+    rc = mi355x_ilu0_lower_level(dc->h, f->launch.levptrL[l + 1] - f->launch.levptrL[l], f->launch.d_rowsL + f->launch.levptrL[l], f->launch.d_bi, f->launch.d_bj, f->launch.d_ba, in, out);
+  for (PetscInt l = 0; l < f->lev.nlevU && !rc; l++)
+    rc = mi355x_ilu0_upper_level(dc->h, f->launch.levptrU[l + 1] - f->launch.levptrU[l], f->launch.d_rowsU + f->launch.levptrU[l], f->launch.d_bj, f->launch.d_ba, f->launch.d_bdiag, out);
+  return rc;
+}
 static PetscErrorCode MatSolve_SeqAIJHIP_ILU(Mat F, Vec b, Vec x) {   /* MatSolve_SeqAIJCUSPARSE_NaturalOrdering, aijcusparse.cu:419-445 */
   PetscErrorCode ierr;
   HipTriFactors *f = HipTriGet(F);
   const PetscScalar *db; PetscScalar *dx; PetscDeviceCtx *dc;
-  if (f->sweeps) return ilu0_sweeps_apply(f, b, x);
-  if (f->tri_lo) return HipTriFactorsApply(F, f, b, x, 2.0 * f->nz - f->n);
+  if (f->sw.sweeps) return ilu0_sweeps_apply(f, b, x);
+  if (f->syncfree.tri_lo) return HipTriFactorsApply(F, f, b, x, 2.0 * f->nz - f->n);
   ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
   ierr = VecHIPGetRead(b, &db);CHKERRQ(ierr);
   ierr = VecHIPGetWrite(x, &dx);CHKERRQ(ierr);
   /* The level launches are a launch-bound inner loop (766 + 766 kernels for P7(256)): with more than a handful of levels they
    * are captured once into a hipGraph that works in place on a fixed buffer and replayed per application (copy in, one graph
    * launch, copy out).  Same kernels, same order, same bits. */
-  if (!f->graph_tried && f->nlevL + f->nlevU > 16) {
-    f->graph_tried = 1;
-    if (!mi355x_malloc((void **)&f->d_work, sizeof(PetscScalar) * (size_t)PetscMax(f->n, 1)) && !mi355x_graph_capture_begin(dc->h)) {
-      int bad = 0;
-      for (PetscInt l = 0; l < f->nlevL && !bad; l++)
-        bad = mi355x_ilu0_lower_level(dc->h, f->levptrL[l + 1] - f->levptrL[l], f->d_rowsL + f->levptrL[l], f->d_bi, f->d_bj, f->d_ba, f->d_work, f->d_work);
-      for (PetscInt l = 0; l < f->nlevU && !bad; l++)
-        bad = mi355x_ilu0_upper_level(dc->h, f->levptrU[l + 1] - f->levptrU[l], f->d_rowsU + f->levptrU[l], f->d_bj, f->d_ba, f->d_bdiag, f->d_work);
+  if (!f->launch.graph_tried && f->lev.nlevL + f->lev.nlevU > 16) {
+    f->launch.graph_tried = 1;
+    if (!mi355x_malloc((void **)&f->launch.d_work, sizeof(PetscScalar) * (size_t)PetscMax(f->n, 1)) && !mi355x_graph_capture_begin(dc->h)) {
+      const int bad = ilu0_launch_levels(dc, f, f->launch.d_work, f->launch.d_work);
       void *g = NULL;
       if (mi355x_graph_capture_end(dc->h, &g) || bad) g = NULL;   /* capture failed: stay with plain launches */
-      f->graph = g;
+      f->launch.graph = g;
     }
   }
   int rc = 0;
-  if (f->graph) {
-    rc = mi355x_vec_copy(dc->h, (size_t)f->n, db, f->d_work);
-    if (!rc) rc = mi355x_graph_launch(dc->h, f->graph);
-    if (!rc) rc = mi355x_vec_copy(dc->h, (size_t)f->n, f->d_work, dx);
-  } else {
-    for (PetscInt l = 0; l < f->nlevL && !rc; l++)
-      rc = mi355x_ilu0_lower_level(dc->h, f->levptrL[l + 1] - f->levptrL[l], f->d_rowsL + f->levptrL[l], f->d_bi, f->d_bj, f->d_ba, db, dx);
-    for (PetscInt l = 0; l < f->nlevU && !rc; l++)
-      rc = mi355x_ilu0_upper_level(dc->h, f->levptrU[l + 1] - f->levptrU[l], f->d_rowsU + f->levptrU[l], f->d_bj, f->d_ba, f->d_bdiag, dx);
-  }
+  if (f->launch.graph) {
+    rc = mi355x_vec_copy(dc->h, (size_t)f->n, db, f->launch.d_work);
+    if (!rc) rc = mi355x_graph_launch(dc->h, f->launch.graph);
+    if (!rc) rc = mi355x_vec_copy(dc->h, (size_t)f->n, f->launch.d_work, dx);
+  } else rc = ilu0_launch_levels(dc, f, db, dx);
   ierr = VecHIPRestoreWrite(x);CHKERRQ(ierr);
   HipStateIncrease(x);
   CHKHIP(rc);
@@ -1057,12 +1045,12 @@ PetscErrorCode PCILUGetSolver_HIPMI355X(PC pc, PetscInt *syncfree, PetscInt *abo
   HipTriFactors *f;
   PetscErrorCode ierr = pc_factors(pc, MAT_FACTOR_ILU, &f);CHKERRQ(ierr);
   int a = 0, b = 0;
-  if (syncfree) *syncfree = (f->tri_lo && !f->use_levels) ? 1 : 0;
-  if (f->tri_lo) {
+  if (syncfree) *syncfree = (f->syncfree.tri_lo && !f->syncfree.use_levels) ? 1 : 0;
+  if (f->syncfree.tri_lo) {
     PetscDeviceCtx *dc;
     ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
     CHKHIP(mi355x_handle_synchronize(dc->h));      /* the flag of everything queued so far */
-    mi355x_trisolve_aborted(f->tri_lo, &a); mi355x_trisolve_aborted(f->tri_up, &b);
+    mi355x_trisolve_aborted(f->syncfree.tri_lo, &a); mi355x_trisolve_aborted(f->syncfree.tri_up, &b);
   }
   if (aborted) *aborted = a || b || f->aborted;
   return 0;
@@ -1071,7 +1059,7 @@ PetscErrorCode PCILUGetSolver_HIPMI355X(PC pc, PetscInt *syncfree, PetscInt *abo
 PetscErrorCode PCILUGetSweeps_HIPMI355X(PC pc, PetscInt *k) {
   HipTriFactors *f;
   PetscErrorCode ierr = pc_factors(pc, MAT_FACTOR_ILU, &f);CHKERRQ(ierr);
-  *k = f->sweeps;
+  *k = f->sw.sweeps;
   return 0;
 }
 /* on_device: the last numeric factorisation ran on the device (-pc_factor_hipmi355x_numeric device); host symbolic passes (pattern,
@@ -1079,7 +1067,7 @@ PetscErrorCode PCILUGetSweeps_HIPMI355X(PC pc, PetscInt *k) {
 PetscErrorCode PCILUGetNumeric_HIPMI355X(PC pc, PetscInt *on_device, PetscInt *symbolic_builds, PetscInt *numeric_runs) {
   HipTriFactors *f;
   PetscErrorCode ierr = pc_factors(pc, MAT_FACTOR_ILU, &f);CHKERRQ(ierr);
-  if (on_device) *on_device = f->dfac ? 1 : 0;
+  if (on_device) *on_device = f->dev.dfac ? 1 : 0;
   if (symbolic_builds) *symbolic_builds = f->symbolic_builds;
   if (numeric_runs) *numeric_runs = f->numeric_runs;
   return 0;
@@ -1090,7 +1078,7 @@ PetscErrorCode PCILUGetNumeric_HIPMI355X(PC pc, PetscInt *on_device, PetscInt *s
 PetscErrorCode PCILUApplyInPlace_HIPMI355X(PC pc, Vec v) {
   HipTriFactors *f;
   PetscErrorCode ierr = pc_factors(pc, MAT_FACTOR_ILU, &f);CHKERRQ(ierr);
-  if (!f->sweeps) SETERRQ(HipObjComm(pc), PETSC_ERR_SUP, "in place only with -pc_factor_hipmi355x_trisolve sweeps:<k>");
+  if (!f->sw.sweeps) SETERRQ(HipObjComm(pc), PETSC_ERR_SUP, "in place only with -pc_factor_hipmi355x_trisolve sweeps:<k>");
   ierr = ilu0_sweeps_apply(f, v, v);CHKERRQ(ierr);
   return 0;
 }
@@ -1105,25 +1093,25 @@ PetscErrorCode PCILUGetShiftCount_HIPMI355X(PC pc, PetscInt *nshift) {
 PetscErrorCode PCILUGetNodeInfo_HIPMI355X(PC pc, PetscInt *nodes, PetscInt *nlevL, PetscInt *nlevU) {
   HipTriFactors *f;
   PetscErrorCode ierr = pc_factors(pc, MAT_FACTOR_ILU, &f);CHKERRQ(ierr);
-  if (nodes) *nodes = f->nodes ? (f->block_columns ? -f->nodes : f->nodes) : 0;   /* negative: block-column plans */
-  if (nlevL) *nlevL = f->nlevL_nodes;
-  if (nlevU) *nlevU = f->nlevU_nodes;
+  if (nodes) *nodes = f->syncfree.nodes ? (f->syncfree.block_columns ? -f->syncfree.nodes : f->syncfree.nodes) : 0;   /* negative: block-column plans */
+  if (nlevL) *nlevL = f->syncfree.nlevL_nodes;
+  if (nlevU) *nlevU = f->syncfree.nlevU_nodes;
   return 0;
 }
 /* levels of the two triangular solves */
 PetscErrorCode PCILUGetLevels_HIPMI355X(PC pc, PetscInt *nlevL, PetscInt *nlevU) {
   HipTriFactors *f;
   PetscErrorCode ierr = pc_factors(pc, MAT_FACTOR_ILU, &f);CHKERRQ(ierr);
-  if (nlevL) *nlevL = f->nlevL;
-  if (nlevU) *nlevU = f->nlevU;
+  if (nlevL) *nlevL = f->lev.nlevL;
+  if (nlevU) *nlevU = f->lev.nlevU;
   return 0;
 }
 /* dependency levels of the two sweeps and the number of positive-definite shifts the factorisation took */
 PetscErrorCode PCICCGetInfo_HIPMI355X(PC pc, PetscInt *nlevL, PetscInt *nlevU, PetscInt *nshift) {
   HipTriFactors *f;
   PetscErrorCode ierr = pc_factors(pc, MAT_FACTOR_ICC, &f);CHKERRQ(ierr);
-  if (nlevL) *nlevL = f->nlevL;
-  if (nlevU) *nlevU = f->nlevU;
+  if (nlevL) *nlevL = f->lev.nlevL;
+  if (nlevU) *nlevU = f->lev.nlevU;
   if (nshift) *nshift = f->nshift;
   return 0;
 }
@@ -1132,7 +1120,7 @@ PetscErrorCode PCFactorDebugSetAborted_HIPMI355X(PC pc) {
   PetscErrorCode ierr;
   Mat F = NULL;
   ierr = PCFactorGetMatrix(pc, &F);CHKERRQ(ierr);
-  if (!F || !HipTriGet(F) || !HipTriGet(F)->tri_lo) SETERRQ(HipObjComm(pc), PETSC_ERR_ARG_WRONGSTATE, "no sync-free plans");
-  CHKHIP(mi355x_trisolve_debug_set_aborted(HipTriGet(F)->tri_lo, 1));
+  if (!F || !HipTriGet(F) || !HipTriGet(F)->syncfree.tri_lo) SETERRQ(HipObjComm(pc), PETSC_ERR_ARG_WRONGSTATE, "no sync-free plans");
+  CHKHIP(mi355x_trisolve_debug_set_aborted(HipTriGet(F)->syncfree.tri_lo, 1));
   return 0;
 }
