@@ -1,23 +1,14 @@
 // CSR SpMV for gfx950: y = A x and z = y + A x  (MatMult_SeqAIJ / MatMultAdd_SeqAIJ,
 // reference src/mat/impls/aij/seq/aij.c:1225-1358).
 //
-// "Row-block streaming" layout of the work (HBM-bound, AI = 0.125 flop/B):
-//   * host analysis cuts the rows into row blocks of <= 256 rows and <= 2046 nonzeros;
-//   * one 256-thread workgroup per row block streams that block's val/col_idx slice with
-//     fully coalesced 16-byte (val) / 8-byte (col) non-temporal loads, gathers x through
-//     L1/L2 (x is the only reused operand, so val/col are kept out of the cache with `nt`),
-//     multiplies, and parks the products in LDS.  All loads are issued unconditionally and
-//     ahead of their use (clamped addresses instead of predication, see the idx8 kernel);
-//   * after one barrier each row is summed from LDS: one lane per row, products added in
-//     column order starting from 0.0 (or y[r]) -- the exact order of PetscSparseDensePlusDot
-//     (aij.h:383-386), so the result is bit-identical to the reference's non-FMA C loop.
-//     Row blocks with few, long rows use 2..64 lanes per row and a shuffle tree instead;
-//   * a row longer than 2046 nonzeros gets a whole workgroup (strided partial sums + tree);
-//   * blockIdx is remapped so that runs of SPMV_CH consecutive row blocks are dealt round-robin
-//     to the 8 XCDs: all XCDs stream one window of the matrix while the x entries a 7-point
-//     row needs (r, r+-1, r+-N, r+-N^2) are re-used out of one XCD's own 4 MiB L2;
-//   * variants: offset-dictionary index compression (1 byte per nonzero instead of 4), an
-//     x'y by-product for CG, and the BCSR form of the same structure.
+// "Row-block streaming" (HBM-bound, AI = 0.125 flop/B): host analysis cuts the rows into row blocks of <= 256 rows and
+// <= 2046 nonzeros; one 256-thread workgroup per row block streams the block's slice of the matrix with coalesced,
+// unconditional, non-temporal pair loads (x is the only reused operand), parks the products in LDS and, after one
+// barrier, sums each row out of LDS -- one lane per row in the reference's order (bit-identical to its non-FMA C loop),
+// or 2..64 lanes and a shuffle tree for blocks of few, long rows.  A row longer than the stage gets a whole workgroup.
+// The family -- plain, 8-bit offsets, row patterns, value patterns, grouped rows, BCSR -- differs in where the column of
+// a nonzero comes from; the steps they share (block -> XCD map, lanes per row, pair loads, pair sources, LDS parking, row
+// result, 8-wide accumulate, ordered workgroup sum) are the helpers below, written once.
 #include "common.hpp"
 #include <map>
 #include <array>
@@ -34,7 +25,7 @@
 #define SPMV_NT 1            // non-temporal loads for the val/col streams
 #endif
 #ifndef SPMV_REMAP
-#define SPMV_REMAP 2         // 0 = dispatch order; 1 = each XCD walks a contiguous eighth; 2 = runs of SPMV_CH row blocks dealt round-robin to the XCDs (same speed as 0, 18 % less fabric traffic: x lines stay in one XCD's L2)
+#define SPMV_REMAP 2         // 0 = dispatch order; 2 = runs of SPMV_CH row blocks dealt round-robin to the XCDs (same speed as 0, 18 % less fabric traffic: x lines stay in one XCD's L2)
 #endif
 #ifndef SPMV_CH
 #define SPMV_CH 32
@@ -49,11 +40,15 @@
 #define SPMV_BLOCK_NNZ (8 * SPMV_THREADS)   // LDS stage (doubles): 4 pairs per lane
 #define SPMV_BLOCK_CAP (SPMV_BLOCK_NNZ - 2)   // nonzeros per row block: any alignment of the first pair still fits
 #define SPMV_BLOCK_ROWS SPMV_THREADS
+#define SPMV_PAIRS (SPMV_BLOCK_NNZ / (2 * SPMV_THREADS))   // pairs of the stream per lane
+#define SPMV_WAVES (SPMV_THREADS / MI355X_WAVE)
 #if SPMV_NT
 #define SPMV_LOAD(p) __builtin_nontemporal_load(p)
 #else
 #define SPMV_LOAD(p) (*(p))
 #endif
+static_assert(SPMV_THREADS == 256 && MI355X_WAVE == 64, "one lane per row of a block with byte row markers, 256-entry offset table and 512-entry pattern tables staged one / two per lane");
+static_assert(SPMV_REMAP == 0 || SPMV_REMAP == 2, "SPMV_REMAP == 1 (each XCD walks a contiguous eighth of the row blocks) was removed: only the plain kernel ever had it; use 0 or 2");
 
 typedef double v2d __attribute__((ext_vector_type(2)));
 typedef int v2i __attribute__((ext_vector_type(2)));
@@ -62,7 +57,6 @@ struct mi355x_spmv_plan_s {
   int nrows;       // rows of the (possibly compressed) row pointer
   int nblocks;     // row blocks
   int nlong;       // of which single long rows
-  int chunk;       // ceil(nblocks / NXCD)
   int2 *d_rowblk;  // nblocks+1 entries {first row, first nonzero}
   int *d_rows;     // compressed-row output indices or NULL
   // offset-dictionary index compression (col = row + table[idx8]); NULL when the matrix has > 256 distinct offsets
@@ -95,32 +89,87 @@ struct mi355x_spmv_plan_s {
   long ngj;
 };
 
-// One lane's row sum out of the LDS product stage, 8 reads in flight.  pairsum == 0: products added one at a time in
-// column order (PetscSparseDensePlusDot, aij.h:383-386).  pairsum != 0: two at a time, sum += p[n] + p[n+1], odd
-// tail alone (MatMult_SeqAIJ_Inode / MatMultAdd_SeqAIJ_Inode, inode.c:430-440,619-631).
-__device__ __forceinline__ double row_sum_lds(const double *prod, int rs, int re, double sum, int pairsum) {
+// ---- the steps the row-block kernels share ----------------------------------------------------
+
+// Block -> XCD map and the grid it needs.  Workgroups b, b+8, b+16.. share an XCD.  SPMV_REMAP == 2: XCD x owns runs of `ch`
+// consecutive row blocks, runs dealt round-robin over the XCDs, so all XCDs stream one window of 8*ch blocks while each
+// re-uses its own x lines; the grid is rounded up to whole rounds and a workgroup whose block is >= nblocks leaves.
+static inline int rowblock_grid(int nblocks, int ch) {
+  const int per = SPMV_REMAP == 2 ? MI355X_NXCD * ch : 1;
+  return ((nblocks + per - 1) / per) * per;
+}
+__device__ __forceinline__ int rowblock_of_workgroup(int ch) {
+  if (SPMV_REMAP != 2) return blockIdx.x;
+  const int xcd = blockIdx.x % MI355X_NXCD, slot = blockIdx.x / MI355X_NXCD;
+  return ((slot / ch) * MI355X_NXCD + xcd) * ch + (slot % ch);
+}
+
+// Lanes per row: tpr, the largest power of two with nrows * tpr <= 256, at most one wavefront; lane tid is lane `sub` of row `r`
+// of the block (r >= nrows: no row).  short_rows_one_lane: a block with <= SPMV_SEQ_AVG nonzeros per row on average (the
+// stencil case) gets one lane per row and the reference's summation order.
+struct row_lanes { int tpr, r, sub; };
+__device__ __forceinline__ row_lanes lanes_per_row(int nrows, int nnz, int tid, bool short_rows_one_lane = true) {
+  int lg = 0;                                          // (log2 of tpr: the row of a lane is a shift, not a division)
+  while (lg < 6 && ((nrows * 2) << lg) <= SPMV_THREADS) ++lg;
+  if (short_rows_one_lane && nnz <= SPMV_SEQ_AVG * nrows) lg = 0;
+  return {1 << lg, tid >> lg, tid & ((1 << lg) - 1)};
+}
+
+// The stream [k0, k1) of a block is read in aligned pairs (16 bytes of values), SPMV_PAIRS per lane: pair_k is the element
+// at which pair p of lane tid starts.  The first pair may start one element before k0, the last end one after k1.
+// Every load is unconditional and there is no control flow between the loads, so the compiler keeps all of them in flight
+// behind one wait (the earlier predicated form serialised them pair by pair): a lane whose pair lies past the block
+// re-reads the block's first pair (lane 0's address: merged by the coalescer), a pair cut by the block boundary is loaded
+// whole (an aligned 16-byte access cannot leave the page its first half lies in).
+__device__ __forceinline__ int pair_k(int k0, int tid, int p) { return (k0 & ~1) + 2 * tid + p * 2 * SPMV_THREADS; }
+template <typename PAIR, typename T> __device__ __forceinline__ PAIR load_pair(const T *a, int k0, int k1, int k) {
+  return SPMV_LOAD(reinterpret_cast<const PAIR *>(a + (k < k1 ? k : (k0 & ~1))));
+}
+// Which element addresses x for each half of the pair at k: kk is the pair that load_pair read, s0 / s1 (0 or 1) the element of
+// it whose column the first / second half gathers with.  A half outside the block takes the pair's other element, an idle
+// lane (it holds the block's first pair) element k0: always a column of this block, so no gather is predicated either.
+struct pair_src { int kk, s0, s1; };
+__device__ __forceinline__ pair_src pair_source(int k, int k0, int k1) {
+  const bool in = k < k1;                       // the pair touches the block
+  const bool v0 = in && k >= k0, v1 = in && (k + 1 < k1);
+  return {in ? k : (k0 & ~1), v0 ? 0 : (in ? 1 : (k0 & 1)), v1 ? 1 : (in ? 0 : (k0 & 1))};
+}
+// The pair's two values (or products) into the LDS stage at their place in the block; halves outside the block go to
+// the stage's last slot, which no block uses (nnz <= SPMV_BLOCK_CAP).
+__device__ __forceinline__ void park_pair(double *stage, int k, int k0, int k1, double a, double b) {
+  stage[(k >= k0 && k < k1) ? k - k0 : SPMV_BLOCK_NNZ - 1] = a;
+  stage[(k + 1 < k1) ? k + 1 - k0 : SPMV_BLOCK_NNZ - 1] = b;
+}
+
+// sum + the products prod(j), j < 8 with k + j < end, in order.  pairsum == 0: one at a time (PetscSparseDensePlusDot, aij.h:383-386).
+// pairsum != 0: two at a time, sum += p[j] + p[j+1], odd tail alone (MatMult_SeqAIJ_Inode / MatMultAdd_SeqAIJ_Inode,
+// inode.c:430-440,619-631); k advances in eights from the row's start, so the pairs stay aligned with it.
+template <class PROD> __device__ __forceinline__ double accumulate8(double sum, int k, int end, int pairsum, PROD prod) {
   if (!pairsum) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { const double u = sum + prod(j); sum = (k + j < end) ? u : sum; }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; j += 2) {
+      const double pa = prod(j), pb = prod(j + 1);
+      const double inc = (k + j + 1 < end) ? pa + pb : pa;
+      const double u = sum + inc;
+      sum = (k + j < end) ? u : sum;
+    }
+  }
+  return sum;
+}
+// one lane's row sum out of the LDS product stage, 8 reads in flight (the order is chosen outside the loop)
+__device__ __forceinline__ double row_sum_lds(const double *prod, int rs, int re, double sum, int pairsum) {
+  auto run = [&](int pairs) {
     for (int k = rs; k < re; k += 8) {
       double t[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) t[j] = prod[(k + j < re) ? k + j : re - 1];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { const double u = sum + t[j]; sum = (k + j < re) ? u : sum; }
+      sum = accumulate8(sum, k, re, pairs, [&](int j) { return t[j]; });
     }
-  } else {
-    for (int k = rs; k < re; k += 8) {       // rs + multiples of 8: pairs stay aligned with the row start
-      double t[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) t[j] = prod[(k + j < re) ? k + j : re - 1];
-#pragma unroll
-      for (int j = 0; j < 8; j += 2) {
-        const double pr = t[j] + t[j + 1];
-        const double inc = (k + j + 1 < re) ? pr : t[j];
-        const double u = sum + inc;
-        sum = (k + j < re) ? u : sum;
-      }
-    }
-  }
+  };
+  if (!pairsum) run(0); else run(1);
   return sum;
 }
 
@@ -134,34 +183,59 @@ template <int ADD> __device__ __forceinline__ double spmv_empty(double yv, doubl
 // same, for a sum that was started from yv when ADD == 1 or 3
 template <int ADD> __device__ __forceinline__ double spmv_fin(double yv, double s, double dv = 1.0) { return ADD == 3 ? dv * s : (ADD == 2 ? yv * s : s); }
 static inline int spmv_y_streams(long nrows) { return (size_t)nrows * sizeof(double) >= ((size_t)256 << 20); }   // (vec_kernels.hip: vec_streams)
+// nt: y beyond the Infinity Cache (vectors of >= 256 MiB) is written once and read by another kernel much later: a non-temporal store
+// there (+3 % on P7(512), three of three alternations on one box: profiles/r04_spmv_p7_512_ab.log; nothing either way at P7(256))
+__device__ __forceinline__ void spmv_store(double *p, double v, bool nt) { if (nt) __builtin_nontemporal_store(v, p); else *p = v; }
 
+// A row's result out of the LDS product stage [rs, re) to *dst, by the row's tpr lanes (this one is lane `sub` of them; has_row:
+// it has a row at all).  One lane: products added in column order starting from yv (ADD 1, 3) or 0.0 -- the reference's bits.
+// Several: strided partial sums and a shuffle tree.  Returns what was stored, 0.0 on lanes that stored nothing.
+template <int ADD>
+__device__ __forceinline__ double row_result_lds(const double *prod, int tpr, int sub, bool has_row, int rs, int re, double yv, double dv,
+                                                 int pairsum, double *dst, bool nt) {
+  double res = 0.0;
+  if (tpr == 1) {
+    if (has_row) { res = spmv_fin<ADD>(yv, row_sum_lds(prod, rs, re, (ADD & 1) ? yv : 0.0, pairsum), dv); spmv_store(dst, res, nt); }
+  } else {
+    double sum = 0.0;
+    if (has_row) for (int k = rs + sub; k < re; k += tpr) sum += prod[k];
+    for (int off = tpr >> 1; off > 0; off >>= 1) sum += __shfl_down(sum, off, MI355X_WAVE);
+    if (has_row && sub == 0) { res = spmv_out<ADD>(yv, sum, dv); spmv_store(dst, res, nt); }
+  }
+  return res;
+}
+
+// Sum of v over a workgroup of NW wavefronts in a fixed order: lanes -> wavefront tree -> lane 0 adds the wavefronts' values
+// 0, 1, 2 ... in order.  The result is valid on lane 0 only.  Every lane of the workgroup must arrive (one barrier); the LDS
+// slots are the helper's own and are not re-armed, so a kernel calls this at most once on any path.
+template <int NW> __device__ __forceinline__ double workgroup_sum_ordered(double v) {
+  __shared__ double wave_slot[NW];
+  const int tid = threadIdx.x;
+  v = wave_sum(v);
+  if ((tid & (MI355X_WAVE - 1)) == 0) wave_slot[tid / MI355X_WAVE] = v;
+  __syncthreads();
+  double t = 0.0;
+  if (tid == 0) {
+    t = wave_slot[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) t += wave_slot[w];
+  }
+  return t;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Plain kernel: the column of a nonzero is aj[k], streamed in pairs next to the values (VEC: aa 16-byte and aj 8-byte
+// aligned; otherwise a scalar stream).  CPROW: compressed rows, row r of the plan is row rows[r] of y.
 template <int ADD, bool CPROW, bool VEC>
 __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock_kernel(
-    const int2 *__restrict__ rowblk, int nblocks, int chunk, const int *__restrict__ ai, const int *__restrict__ aj,
+    const int2 *__restrict__ rowblk, int nblocks, const int *__restrict__ ai, const int *__restrict__ aj,
     const double *__restrict__ aa, const double *__restrict__ x, const double *yin, double *yout,
     const int *__restrict__ rows, int pairsum, const double *__restrict__ dsc, int nty) {
   // ADD == 3 only: dsc scales the row's result; nty: y is a stream of 256 MiB or more, stored past the caches
-  auto put = [&](int orow, double v) { if (ADD == 3 && nty) __builtin_nontemporal_store(v, yout + orow); else yout[orow] = v; };
+  const bool nt = ADD == 3 && nty;
   __shared__ double prod[SPMV_BLOCK_NNZ];
-  __shared__ double wsum[SPMV_THREADS / MI355X_WAVE];
-
-  // XCD-aware remap: workgroups b, b+8, b+16.. share an XCD; give them consecutive row blocks
-#if SPMV_REMAP == 1
-  const int xcd = blockIdx.x % MI355X_NXCD;
-  const int slot = blockIdx.x / MI355X_NXCD;
-  const int lb = xcd * chunk + slot;
-  if (slot >= chunk || lb >= nblocks) return;
-#elif SPMV_REMAP == 2
-  // interleaved: XCD x owns runs of SPMV_CH consecutive row blocks, runs dealt round-robin over the XCDs, so all
-  // XCDs stream one window of 8*SPMV_CH blocks while each re-uses its own x lines
-  const int xcd = blockIdx.x % MI355X_NXCD;
-  const int slot = blockIdx.x / MI355X_NXCD;
-  const int lb = ((slot / SPMV_CH) * MI355X_NXCD + xcd) * SPMV_CH + (slot % SPMV_CH);
+  const int lb = rowblock_of_workgroup(SPMV_CH);
   if (lb >= nblocks) return;
-#else
-  const int lb = blockIdx.x;
-  if (lb >= nblocks) return;
-#endif
 
   // {first row, first nonzero} of this row block and of the next: one round trip, no dependent chain
   const int2 b0 = rowblk[lb];
@@ -179,35 +253,24 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
       int c = SPMV_LOAD(aj + k);
       s += v * x[c];
     }
-    s = wave_sum(s);
-    if ((tid & (MI355X_WAVE - 1)) == 0) wsum[tid / MI355X_WAVE] = s;
-    __syncthreads();
+    const double t = workgroup_sum_ordered<SPMV_WAVES>(s);
     if (tid == 0) {
-      double t = wsum[0];
-#pragma unroll
-      for (int w = 1; w < SPMV_THREADS / MI355X_WAVE; ++w) t += wsum[w];
       const int orow = CPROW ? rows[r0] : r0;
-      put(orow, spmv_out<ADD>(ADD ? yin[orow] : 0.0, t, ADD == 3 ? dsc[orow] : 1.0));
+      spmv_store(yout + orow, spmv_out<ADD>(ADD ? yin[orow] : 0.0, t, ADD == 3 ? dsc[orow] : 1.0), nt);
     }
     return;
   }
   if (nnz == 0) {   // only empty rows
     if (tid < nrows) {
       const int orow = CPROW ? rows[r0 + tid] : r0 + tid;
-      put(orow, spmv_empty<ADD>(ADD ? yin[orow] : 0.0, ADD == 3 ? dsc[orow] : 1.0));
+      spmv_store(yout + orow, spmv_empty<ADD>(ADD ? yin[orow] : 0.0, ADD == 3 ? dsc[orow] : 1.0), nt);
     }
     return;
   }
 
-  // lanes per row: largest power of two with nrows*tpr <= 256, at most one wavefront; short rows
-  // (the stencil case) get one lane per row and the reference's summation order
-  int tpr = 1;
-  while (tpr < MI355X_WAVE && nrows * (tpr * 2) <= SPMV_THREADS) tpr *= 2;
-  if (nnz <= SPMV_SEQ_AVG * nrows) tpr = 1;
-
-  // Every load below is unconditional (see the idx8 kernel further down for why): lanes past the last row re-read
-  // the last row's extent, lanes past the last pair re-read the block's first pair.
-  const int r = tid / tpr, sub = tid & (tpr - 1);
+  // lanes past the last row re-read the last row's extent: these loads are unconditional too
+  const row_lanes rl = lanes_per_row(nrows, nnz, tid);
+  const int tpr = rl.tpr, r = rl.r, sub = rl.sub;
   const int rc = r < nrows ? r : nrows - 1;
   const int a0 = ai[r0 + rc], a1 = ai[r0 + rc + 1];
   const int orow = CPROW ? rows[r0 + rc] : r0 + rc;
@@ -217,38 +280,22 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
 
   // ---- stream the block's nonzeros: product -> LDS -----------------------
   if (VEC) {
-    constexpr int PAIRS = SPMV_BLOCK_NNZ / (2 * SPMV_THREADS);
-    const int ka = k0 & ~1;  // 16-byte aligned start for val, 8-byte for col
-    v2d v[PAIRS];
-    v2i c[PAIRS];
+    v2d v[SPMV_PAIRS];
+    v2i c[SPMV_PAIRS];
 #pragma unroll
-    for (int p = 0; p < PAIRS; ++p) {
-      const int k = ka + 2 * tid + p * 2 * SPMV_THREADS;
-      const int kk = (k < k1) ? k : ka;
-      v[p] = SPMV_LOAD(reinterpret_cast<const v2d *>(aa + kk));
-      c[p] = SPMV_LOAD(reinterpret_cast<const v2i *>(aj + kk));
+    for (int p = 0; p < SPMV_PAIRS; ++p) {
+      v[p] = load_pair<v2d>(aa, k0, k1, pair_k(k0, tid, p));
+      c[p] = load_pair<v2i>(aj, k0, k1, pair_k(k0, tid, p));
     }
-    double xa[PAIRS], xb[PAIRS];
+    double xa[SPMV_PAIRS], xb[SPMV_PAIRS];
 #pragma unroll
-    for (int p = 0; p < PAIRS; ++p) {
-      const int k = ka + 2 * tid + p * 2 * SPMV_THREADS;
-      const bool in = k < k1;
-      const bool v0 = in && k >= k0, v1 = in && (k + 1 < k1);
-      // a slot whose own element lies outside the block gathers with the column of the pair's other element, an
-      // idle lane (it holds the block's first pair) with that of element k0: always a column of this block
-      const int s0 = v0 ? 0 : (in ? 1 : (k0 & 1));
-      const int s1 = v1 ? 1 : (in ? 0 : (k0 & 1));
-      xa[p] = x[s0 ? c[p].y : c[p].x];
-      xb[p] = x[s1 ? c[p].y : c[p].x];
+    for (int p = 0; p < SPMV_PAIRS; ++p) {
+      const pair_src s = pair_source(pair_k(k0, tid, p), k0, k1);
+      xa[p] = x[s.s0 ? c[p].y : c[p].x];
+      xb[p] = x[s.s1 ? c[p].y : c[p].x];
     }
 #pragma unroll
-    for (int p = 0; p < PAIRS; ++p) {
-      const int k = ka + 2 * tid + p * 2 * SPMV_THREADS;
-      const double pa = v[p].x * xa[p], pb = v[p].y * xb[p];
-      // products of elements outside the block go to the stage's last slot, which no block uses (nnz <= CAP)
-      prod[(k >= k0 && k < k1) ? k - k0 : SPMV_BLOCK_NNZ - 1] = pa;
-      prod[(k + 1 < k1) ? k + 1 - k0 : SPMV_BLOCK_NNZ - 1] = pb;
-    }
+    for (int p = 0; p < SPMV_PAIRS; ++p) park_pair(prod, pair_k(k0, tid, p), k0, k1, v[p].x * xa[p], v[p].y * xb[p]);
   } else {
     for (int k = k0 + tid; k < k1; k += SPMV_THREADS)
       prod[k - k0] = SPMV_LOAD(aa + k) * x[SPMV_LOAD(aj + k)];
@@ -257,14 +304,7 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
 
   // ---- per-row sums out of LDS -------------------------------------------
   const int rs = r < nrows ? a0 - k0 : 0, re = r < nrows ? a1 - k0 : 0;
-  if (tpr == 1) {
-    if (r < nrows) put(orow, spmv_fin<ADD>(ysum, row_sum_lds(prod, rs, re, (ADD & 1) ? ysum : 0.0, pairsum), dv));
-  } else {
-    double sum = 0.0;
-    if (r < nrows) for (int k = rs + sub; k < re; k += tpr) sum += prod[k];
-    for (int off = tpr >> 1; off > 0; off >>= 1) sum += __shfl_down(sum, off, MI355X_WAVE);
-    if (r < nrows && sub == 0) put(orow, spmv_out<ADD>(ysum, sum, dv));
-  }
+  row_result_lds<ADD>(prod, tpr, sub, r < nrows, rs, re, ysum, dv, pairsum, yout + orow, nt);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -274,11 +314,8 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
 // streams val (8 B) + idx8 (1 B) instead of val + col (12 B): 25 % fewer matrix bytes.  The row of each nonzero,
 // which the offset needs, comes from an LDS marker array written by the lanes that own the rows (they hold the
 // row extents anyway).  Arithmetic and summation order are those of the plain kernel: same bits.
-// Branch-free addressing: every lane issues all of its loads unconditionally -- a lane whose pair lies outside the
-// block re-reads the block's first pair (same address as lane 0: merged by the coalescer), a pair cut by the block
-// boundary is loaded whole (an aligned 16-byte access cannot leave the page its first half lies in) and the element
-// outside the block is simply not written to LDS.  With no control flow between the loads the compiler keeps all of
-// them in flight behind a single s_waitcnt; the earlier predicated form serialised them pair by pair.
+// DOT: the block also leaves the sum of x_r y_r over its rows in dotpart[block] (square matrix; KSPSolve_CG's p'w from the pass that
+// makes w = A p), in a fixed order; mi355x_spmv_dot_finish adds the blocks' values in block order.
 template <int ADD, bool DOT>
 __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock_idx8_kernel(
     const int2 *__restrict__ rowblk, int nblocks, const int *__restrict__ ai, const unsigned char *__restrict__ idx8,
@@ -287,16 +324,8 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
   __shared__ double prod[SPMV_BLOCK_NNZ];
   __shared__ unsigned char rowof[SPMV_BLOCK_NNZ];
   __shared__ int offtab[256];
-  __shared__ double wsum[SPMV_THREADS / MI355X_WAVE];
-  static_assert(SPMV_THREADS == 256 || SPMV_THREADS == 128 || SPMV_THREADS == 512, "the offset table is staged 256 / SPMV_THREADS entries per lane");
   static_assert(!(DOT && ADD != 0), "the x'y by-product is provided for y = A x only");
-#if SPMV_REMAP == 2
-  const int xcd = blockIdx.x % MI355X_NXCD;
-  const int slot = blockIdx.x / MI355X_NXCD;
-  const int lb = ((slot / SPMV_CH) * MI355X_NXCD + xcd) * SPMV_CH + (slot % SPMV_CH);
-#else
-  const int lb = blockIdx.x;
-#endif
+  const int lb = rowblock_of_workgroup(SPMV_CH);
   if (lb >= nblocks) return;
   const int2 b0 = rowblk[lb];
   const int2 b1 = rowblk[lb + 1];
@@ -304,39 +333,18 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
   const int nnz = k1 - k0;
   const int nrows = r1 - r0;
   const int tid = threadIdx.x;
-  const int tabv = offtab_g[tid & 255];   // 256 initialised entries (zeros past ntab)
-  const int tabv2 = (SPMV_THREADS < 256) ? offtab_g[(tid + SPMV_THREADS) & 255] : 0;
+  const int tabv = offtab_g[tid];   // 256 initialised entries (zeros past ntab)
   (void)ntab;
-
-  if (nnz > SPMV_BLOCK_CAP) {   // one long row: every entry belongs to row r0
-    if (tid < 256) offtab[tid] = tabv;
-    if (SPMV_THREADS < 256) offtab[tid + SPMV_THREADS] = tabv2;
-    __syncthreads();
-    double s = 0.0;
-    for (int k = k0 + tid; k < k1; k += SPMV_THREADS) s += SPMV_LOAD(aa + k) * x[r0 + offtab[SPMV_LOAD(idx8 + k)]];
-    s = wave_sum(s);
-    if ((tid & (MI355X_WAVE - 1)) == 0) wsum[tid / MI355X_WAVE] = s;
-    __syncthreads();
-    if (tid == 0) {
-      double t = wsum[0];
-#pragma unroll
-      for (int w = 1; w < SPMV_THREADS / MI355X_WAVE; ++w) t += wsum[w];
-      const double yv = spmv_out<ADD>(ADD ? yin[r0] : 0.0, t);
-      yout[r0] = yv;
-      if (DOT) dotpart[lb] = yv * x[r0];
-    }
-    return;
-  }
+  // No block of this kernel exceeds the stage: a row of more than SPMV_BLOCK_CAP nonzeros makes the analysis decline
+  // (spmv_compress_indices: nlong), and such a plan runs the plain kernel.
   if (nnz == 0) {               // only empty rows
     if (tid < nrows) yout[r0 + tid] = spmv_empty<ADD>(ADD ? yin[r0 + tid] : 0.0);
     if (DOT && tid == 0) dotpart[lb] = 0.0;
     return;
   }
 
-  int tpr = 1;
-  while (tpr < MI355X_WAVE && nrows * (tpr * 2) <= SPMV_THREADS) tpr *= 2;
-  if (nnz <= SPMV_SEQ_AVG * nrows) tpr = 1;
-  const int r = tid / tpr, sub = tid & (tpr - 1);
+  const row_lanes rl = lanes_per_row(nrows, nnz, tid);
+  const int tpr = rl.tpr, r = rl.r, sub = rl.sub;
   const int rc = r < nrows ? r : nrows - 1;
   const int a0 = ai[r0 + rc], a1 = ai[r0 + rc + 1];
   double ysum = 0.0;
@@ -344,72 +352,33 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
   double xrow = 0.0;
   if (DOT) xrow = x[r0 + rc];   // square matrix: x entry of this lane's row, for the x'y by-product
   // this lane's slice of the value / index streams
-  constexpr int PAIRS = SPMV_BLOCK_NNZ / (2 * SPMV_THREADS);
-  const int ka = k0 & ~1;
-  v2d v[PAIRS];
-  unsigned int ix[PAIRS];
+  v2d v[SPMV_PAIRS];
+  unsigned int ix[SPMV_PAIRS];
 #pragma unroll
-  for (int p = 0; p < PAIRS; ++p) {
-    const int k = ka + 2 * tid + p * 2 * SPMV_THREADS;
-    const int kk = (k < k1) ? k : ka;
-    v[p] = SPMV_LOAD(reinterpret_cast<const v2d *>(aa + kk));
-    ix[p] = SPMV_LOAD(reinterpret_cast<const unsigned short *>(idx8 + kk));
+  for (int p = 0; p < SPMV_PAIRS; ++p) {
+    v[p] = load_pair<v2d>(aa, k0, k1, pair_k(k0, tid, p));
+    ix[p] = load_pair<unsigned short>(idx8, k0, k1, pair_k(k0, tid, p));
   }
   const int rs = r < nrows ? a0 - k0 : 0, re = r < nrows ? a1 - k0 : 0;
   // row markers: the lanes of row r tag its nonzeros
   for (int k = rs + sub; k < re; k += tpr) rowof[k] = (unsigned char)r;
-  if (tid < 256) offtab[tid] = tabv;
-  if (SPMV_THREADS < 256) offtab[tid + SPMV_THREADS] = tabv2;
+  offtab[tid] = tabv;
   __syncthreads();
-  double xa[PAIRS], xb[PAIRS];
+  double xa[SPMV_PAIRS], xb[SPMV_PAIRS];
 #pragma unroll
-  for (int p = 0; p < PAIRS; ++p) {
-    const int k = ka + 2 * tid + p * 2 * SPMV_THREADS;
-    const bool in = k < k1;                       // the pair touches the block
-    const bool v0 = in && k >= k0, v1 = in && (k + 1 < k1);
-    const int kk = in ? k : ka;
-    // element to address x with when the slot's own element lies outside the block: the pair's other element,
-    // or (idle lane, pair = the block's first) element k0
-    const int s0 = v0 ? 0 : (in ? 1 : (k0 & 1));
-    const int s1 = v1 ? 1 : (in ? 0 : (k0 & 1));
-    xa[p] = x[r0 + rowof[kk + s0 - k0] + offtab[(ix[p] >> (8 * s0)) & 0xff]];
-    xb[p] = x[r0 + rowof[kk + s1 - k0] + offtab[(ix[p] >> (8 * s1)) & 0xff]];
+  for (int p = 0; p < SPMV_PAIRS; ++p) {
+    const pair_src s = pair_source(pair_k(k0, tid, p), k0, k1);
+    xa[p] = x[r0 + rowof[s.kk + s.s0 - k0] + offtab[(ix[p] >> (8 * s.s0)) & 0xff]];
+    xb[p] = x[r0 + rowof[s.kk + s.s1 - k0] + offtab[(ix[p] >> (8 * s.s1)) & 0xff]];
   }
 #pragma unroll
-  for (int p = 0; p < PAIRS; ++p) {
-    const int k = ka + 2 * tid + p * 2 * SPMV_THREADS;
-    const double pa = v[p].x * xa[p], pb = v[p].y * xb[p];
-    // products of elements outside the block go to the stage's last slot, which no block uses (nnz <= CAP)
-    prod[(k >= k0 && k < k1) ? k - k0 : SPMV_BLOCK_NNZ - 1] = pa;
-    prod[(k + 1 < k1) ? k + 1 - k0 : SPMV_BLOCK_NNZ - 1] = pb;
-  }
+  for (int p = 0; p < SPMV_PAIRS; ++p) park_pair(prod, pair_k(k0, tid, p), k0, k1, v[p].x * xa[p], v[p].y * xb[p]);
   __syncthreads();
-  double yval = 0.0;             // this lane's row result (lanes without a row: 0)
-  if (tpr == 1) {
-    if (r < nrows) {
-      const double sum = spmv_fin<ADD>(ysum, row_sum_lds(prod, rs, re, ADD == 1 ? ysum : 0.0, pairsum));
-      yout[r0 + r] = sum;
-      yval = sum;
-    }
-  } else {
-    double sum = 0.0;
-    if (r < nrows) for (int k = rs + sub; k < re; k += tpr) sum += prod[k];
-    for (int off = tpr >> 1; off > 0; off >>= 1) sum += __shfl_down(sum, off, MI355X_WAVE);
-    if (r < nrows && sub == 0) { yval = spmv_out<ADD>(ysum, sum); yout[r0 + r] = yval; }
-  }
+  // this lane's row result (lanes without a row: 0)
+  const double yval = row_result_lds<ADD>(prod, tpr, sub, r < nrows, rs, re, ysum, 1.0, pairsum, yout + r0 + rc, false);
   if (DOT) {
-    // x'y by-product: this block's sum of x_r y_r in a fixed order (lanes -> wavefront tree -> 4 wavefronts in order);
-    // mi355x_spmv_csr_dot sums the per-block values in block order afterwards
-    const bool mine = (r < nrows) && (sub == 0);
-    double c = wave_sum(mine ? yval * xrow : 0.0);
-    if ((tid & (MI355X_WAVE - 1)) == 0) wsum[tid / MI355X_WAVE] = c;
-    __syncthreads();
-    if (tid == 0) {
-      double t = wsum[0];
-#pragma unroll
-      for (int w = 1; w < SPMV_THREADS / MI355X_WAVE; ++w) t += wsum[w];
-      dotpart[lb] = t;
-    }
+    const double t = workgroup_sum_ordered<SPMV_WAVES>((r < nrows && sub == 0) ? yval * xrow : 0.0);
+    if (tid == 0) dotpart[lb] = t;
   }
 }
 
@@ -423,9 +392,8 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
 // consecutive x entries (the rows are consecutive, the offsets equal), so the gathers are coalesced, which the per-nonzero
 // layouts above cannot offer -- multiplies with the staged values and adds in column order (or two at a time, pairsum):
 // the arithmetic and order of the other kernels, same bits.  No row markers, no per-nonzero index stream, one barrier less.
+// DOT as in the idx8 kernel; ch: run length of the block -> XCD map (mi355x_spmv_plan_compress_indices).
 #define SPMV_PAT_CAP 512
-// DOT: the block also leaves the sum of x_r y_r over its rows in dotpart[block] (square matrix; KSPSolve_CG's p'w from the pass that
-// makes w = A p): lanes in row order, a fixed tree -- deterministic; mi355x_spmv_dot_finish adds the blocks' values in block order.
 template <int ADD, bool DOT>
 __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock_pat_kernel(
     const int2 *__restrict__ rowblk, int nblocks, const unsigned int *__restrict__ prow,
@@ -433,15 +401,7 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
     double *__restrict__ dotpart, int pairsum, int ch, int nty) {
   __shared__ double vs[SPMV_BLOCK_NNZ];
   __shared__ int pattab[SPMV_PAT_CAP];
-  __shared__ double wdot[DOT ? SPMV_THREADS / MI355X_WAVE : 1];
-  static_assert(SPMV_THREADS == 256 && SPMV_BLOCK_ROWS <= SPMV_THREADS, "one lane per row of the block");
-#if SPMV_REMAP == 2
-  const int xcd = blockIdx.x % MI355X_NXCD;
-  const int slot = blockIdx.x / MI355X_NXCD;
-  const int lb = ((slot / ch) * MI355X_NXCD + xcd) * ch + (slot % ch);     // runs of ch row blocks, see mi355x_spmv_plan_compress_indices
-#else
-  const int lb = blockIdx.x;
-#endif
+  const int lb = rowblock_of_workgroup(ch);
   if (lb >= nblocks) return;
   const int2 b0 = rowblk[lb];
   const int2 b1 = rowblk[lb + 1];
@@ -459,23 +419,13 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
   const int pst = (int)(pw & 0xffffu), rs = (int)(pw >> 16);
   double ysum = 0.0;
   if (ADD) ysum = yin[r0 + rc];
-  constexpr int PAIRS = SPMV_BLOCK_NNZ / (2 * SPMV_THREADS);
-  const int ka = k0 & ~1;
-  v2d v[PAIRS];
+  v2d v[SPMV_PAIRS];
 #pragma unroll
-  for (int p = 0; p < PAIRS; ++p) {      // every load unconditional, see the idx8 kernel
-    const int k = ka + 2 * tid + p * 2 * SPMV_THREADS;
-    const int kk = (k < k1) ? k : ka;
-    v[p] = SPMV_LOAD(reinterpret_cast<const v2d *>(aa + kk));
-  }
+  for (int p = 0; p < SPMV_PAIRS; ++p) v[p] = load_pair<v2d>(aa, k0, k1, pair_k(k0, tid, p));
   pattab[tid] = t0;
   pattab[tid + SPMV_THREADS] = t1;
 #pragma unroll
-  for (int p = 0; p < PAIRS; ++p) {
-    const int k = ka + 2 * tid + p * 2 * SPMV_THREADS;
-    vs[(k >= k0 && k < k1) ? k - k0 : SPMV_BLOCK_NNZ - 1] = v[p].x;     // elements outside the block: the spare last slot
-    vs[(k + 1 < k1) ? k + 1 - k0 : SPMV_BLOCK_NNZ - 1] = v[p].y;
-  }
+  for (int p = 0; p < SPMV_PAIRS; ++p) park_pair(vs, pair_k(k0, tid, p), k0, k1, v[p].x, v[p].y);
   __syncthreads();
   if (!DOT && tid >= nrows) return;
   const int len = tid < nrows ? pattab[pst] : 0;   // table entry: {length, offsets ...}
@@ -489,33 +439,13 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
       xv[j] = x[xbase + pattab[pst + 1 + qq]];
       av[j] = vs[rs + qq];
     }
-    if (!pairsum) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { const double u = sum + av[j] * xv[j]; sum = (q0 + j < len) ? u : sum; }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; j += 2) {
-        const double pa = av[j] * xv[j], pb = av[j + 1] * xv[j + 1];
-        const double inc = (q0 + j + 1 < len) ? pa + pb : pa;
-        const double u = sum + inc;
-        sum = (q0 + j < len) ? u : sum;
-      }
-    }
+    sum = accumulate8(sum, q0, len, pairsum, [&](int j) { return av[j] * xv[j]; });
   }
   const double yv = spmv_fin<ADD>(ysum, sum);
-  // y beyond the Infinity Cache (vectors of >= 256 MiB) is written once and read by another kernel much later: a non-temporal store
-  // there (+3 % on P7(512), three of three alternations on one box: profiles/r04_spmv_p7_512_ab.log; nothing either way at P7(256))
-  if (tid < nrows) { if (nty) __builtin_nontemporal_store(yv, yout + r0 + tid); else yout[r0 + tid] = yv; }
+  if (tid < nrows) spmv_store(yout + r0 + tid, yv, nty);
   if (DOT) {
-    const double c = wave_sum(tid < nrows ? yv * x[xbase] : 0.0);
-    if ((tid & (MI355X_WAVE - 1)) == 0) wdot[tid / MI355X_WAVE] = c;
-    __syncthreads();
-    if (tid == 0) {
-      double t = wdot[0];
-#pragma unroll
-      for (int w = 1; w < SPMV_THREADS / MI355X_WAVE; ++w) t += wdot[w];
-      dotpart[lb] = t;
-    }
+    const double t = workgroup_sum_ordered<SPMV_WAVES>(tid < nrows ? yv * x[xbase] : 0.0);
+    if (tid == 0) dotpart[lb] = t;
   }
 }
 
@@ -555,18 +485,7 @@ __device__ __forceinline__ double vpat_row(const int *pattab, const double *patv
       if (q0 + i < len) xv[i] = *reinterpret_cast<const double *>(xb + (unsigned int)(rb8 + (unsigned int)pattab[ps + 1 + q0 + i]));
       av[i] = patval[ps + 1 + q0 + i];
     }
-    if (!pairsum) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) { const double u = sum + av[i] * xv[i]; sum = (q0 + i < len) ? u : sum; }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; i += 2) {
-        const double pa = av[i] * xv[i], pb = av[i + 1] * xv[i + 1];
-        const double inc = (q0 + i + 1 < len) ? pa + pb : pa;
-        const double u = sum + inc;
-        sum = (q0 + i < len) ? u : sum;
-      }
-    }
+    sum = accumulate8(sum, q0, len, pairsum, [&](int i) { return av[i] * xv[i]; });   // (each product where it is added: nothing waits between the guarded gathers)
   }
   return sum;
 }
@@ -577,7 +496,6 @@ __global__ __launch_bounds__(SPMV_THREADS) void spmv_csr_valpat_kernel(
     const double *__restrict__ x, const double *yin, double *yout, double *__restrict__ dotpart, int pairsum) {
   __shared__ int pattab[SPMV_PAT_CAP];
   __shared__ double patval[SPMV_PAT_CAP];
-  __shared__ double wdot[DOT ? SPMV_THREADS / MI355X_WAVE : 1];
   const int tid = threadIdx.x;
   for (int t = tid; t < tablen; t += SPMV_THREADS) { pattab[t] = pattab_g[t]; patval[t] = patval_g[t]; }
   const long rbase = (long)blockIdx.x * SPMV_VPAT_ROWS + tid;          // the grid covers the rows exactly: no block without one
@@ -613,15 +531,8 @@ __global__ __launch_bounds__(SPMV_THREADS) void spmv_csr_valpat_kernel(
       const long row = rbase + (long)j * SPMV_THREADS;
       if (row < nrows) c += res[j] * x[row];
     }
-    c = wave_sum(c);
-    if ((tid & (MI355X_WAVE - 1)) == 0) wdot[tid / MI355X_WAVE] = c;
-    __syncthreads();
-    if (tid == 0) {
-      double t = wdot[0];
-#pragma unroll
-      for (int w = 1; w < SPMV_THREADS / MI355X_WAVE; ++w) t += wdot[w];
-      dotpart[blockIdx.x] = t;
-    }
+    const double t = workgroup_sum_ordered<SPMV_WAVES>(c);
+    if (tid == 0) dotpart[blockIdx.x] = t;
   }
 }
 
@@ -644,15 +555,8 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
   __shared__ int gjs[SPMV_GJ_CAP + 2];               // +2: parking slots for the halves of a pair outside the block
   __shared__ int rbase[SPMV_BLOCK_ROWS];             // per row: its nonzero e of the block has column gjs[rbase + e]
   __shared__ unsigned char rowof[SPMV_BLOCK_NNZ];    // per nonzero of the block: its row (written by the lanes that own the row)
-  static_assert(SPMV_THREADS == 256, "two index pairs per lane cover SPMV_GJ_CAP entries for 256 lanes");
   static_assert(SPMV_GJ_CAP + 2 <= 4 * SPMV_THREADS, "index staging: two int2 loads per lane");
-#if SPMV_REMAP == 2
-  const int xcd = blockIdx.x % MI355X_NXCD;
-  const int slot = blockIdx.x / MI355X_NXCD;
-  const int lb = ((slot / SPMV_CH) * MI355X_NXCD + xcd) * SPMV_CH + (slot % SPMV_CH);
-#else
-  const int lb = blockIdx.x;
-#endif
+  const int lb = rowblock_of_workgroup(SPMV_CH);
   if (lb >= nblocks) return;
   const int4 b0 = rowblk[lb];
   const int4 b1 = rowblk[lb + 1];
@@ -664,70 +568,42 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
     if (tid < nrows) yout[r0 + tid] = spmv_empty<ADD>(ADD ? yin[r0 + tid] : 0.0);
     return;
   }
-  int tpr = 1;
-  while (tpr < MI355X_WAVE && nrows * (tpr * 2) <= SPMV_THREADS) tpr *= 2;
-  if (nnz <= SPMV_SEQ_AVG * nrows) tpr = 1;
-  const int r = tid / tpr, sub = tid & (tpr - 1);
+  const row_lanes rl = lanes_per_row(nrows, nnz, tid);
+  const int tpr = rl.tpr, r = rl.r, sub = rl.sub;
   const int rc = r < nrows ? r : nrows - 1;
   const int a0 = ai[r0 + rc], a1 = ai[r0 + rc + 1];
   const int go = goff[r0 + rc];
   double ysum = 0.0;
   if (ADD) ysum = yin[r0 + rc];
-  // this lane's slices of the value stream and of the block's shared column lists; every load unconditional
-  constexpr int PAIRS = SPMV_BLOCK_NNZ / (2 * SPMV_THREADS);
-  const int ka = k0 & ~1, ga = g0 & ~1;
-  v2d v[PAIRS];
+  // this lane's slices of the value stream and of the block's shared column lists [g0, g1)
+  v2d v[SPMV_PAIRS];
   v2i gv[2];
 #pragma unroll
-  for (int p = 0; p < PAIRS; ++p) {
-    const int k = ka + 2 * tid + p * 2 * SPMV_THREADS;
-    const int kk = (k < k1) ? k : ka;
-    v[p] = SPMV_LOAD(reinterpret_cast<const v2d *>(aa + kk));
-  }
+  for (int p = 0; p < SPMV_PAIRS; ++p) v[p] = load_pair<v2d>(aa, k0, k1, pair_k(k0, tid, p));
 #pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int g = ga + 2 * tid + q * 2 * SPMV_THREADS;
-    const int gg = (g < g1) ? g : ga;
-    gv[q] = SPMV_LOAD(reinterpret_cast<const v2i *>(gj + gg));
-  }
+  for (int q = 0; q < 2; ++q) gv[q] = load_pair<v2i>(gj, g0, g1, pair_k(g0, tid, q));
   const int rs = r < nrows ? a0 - k0 : 0, re = r < nrows ? a1 - k0 : 0;
   for (int k = rs + sub; k < re; k += tpr) rowof[k] = (unsigned char)r;
   if (r < nrows && sub == 0) rbase[r] = (go - g0) - rs;
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
-    const int g = ga + 2 * tid + q * 2 * SPMV_THREADS;
+    const int g = pair_k(g0, tid, q);
     gjs[(g >= g0 && g < g1) ? g - g0 : SPMV_GJ_CAP] = gv[q].x;
     gjs[(g + 1 < g1) ? g + 1 - g0 : SPMV_GJ_CAP + 1] = gv[q].y;
   }
   __syncthreads();
-  double xa[PAIRS], xb[PAIRS];
+  double xa[SPMV_PAIRS], xb[SPMV_PAIRS];
 #pragma unroll
-  for (int p = 0; p < PAIRS; ++p) {
-    const int k = ka + 2 * tid + p * 2 * SPMV_THREADS;
-    const bool in = k < k1;
-    const bool v0 = in && k >= k0, v1 = in && (k + 1 < k1);
-    const int kk = in ? k : ka;
-    const int e0 = kk + (v0 ? 0 : (in ? 1 : (k0 & 1))) - k0;   // an element of this block to take the column from
-    const int e1 = kk + (v1 ? 1 : (in ? 0 : (k0 & 1))) - k0;
+  for (int p = 0; p < SPMV_PAIRS; ++p) {
+    const pair_src s = pair_source(pair_k(k0, tid, p), k0, k1);
+    const int e0 = s.kk + s.s0 - k0, e1 = s.kk + s.s1 - k0;   // elements of this block to take the columns from
     xa[p] = x[gjs[rbase[rowof[e0]] + e0]];
     xb[p] = x[gjs[rbase[rowof[e1]] + e1]];
   }
 #pragma unroll
-  for (int p = 0; p < PAIRS; ++p) {
-    const int k = ka + 2 * tid + p * 2 * SPMV_THREADS;
-    const double pa = v[p].x * xa[p], pb = v[p].y * xb[p];
-    prod[(k >= k0 && k < k1) ? k - k0 : SPMV_BLOCK_NNZ - 1] = pa;
-    prod[(k + 1 < k1) ? k + 1 - k0 : SPMV_BLOCK_NNZ - 1] = pb;
-  }
+  for (int p = 0; p < SPMV_PAIRS; ++p) park_pair(prod, pair_k(k0, tid, p), k0, k1, v[p].x * xa[p], v[p].y * xb[p]);
   __syncthreads();
-  if (tpr == 1) {
-    if (r < nrows) yout[r0 + r] = spmv_fin<ADD>(ysum, row_sum_lds(prod, rs, re, ADD == 1 ? ysum : 0.0, pairsum));
-  } else {
-    double sum = 0.0;
-    if (r < nrows) for (int k = rs + sub; k < re; k += tpr) sum += prod[k];
-    for (int off = tpr >> 1; off > 0; off >>= 1) sum += __shfl_down(sum, off, MI355X_WAVE);
-    if (r < nrows && sub == 0) yout[r0 + r] = spmv_out<ADD>(ysum, sum);
-  }
+  row_result_lds<ADD>(prod, tpr, sub, r < nrows, rs, re, ysum, 1.0, pairsum, yout + r0 + rc, false);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -753,15 +629,9 @@ __global__ __launch_bounds__(SPMV_THREADS) void bsr_rowblock_kernel(const int2 *
   __shared__ int ajs[XLDS ? 1 : SPMV_BLOCK_NNZ / 4 + 1];   // block columns of the row block (bs >= 2: at most NNZ/4 blocks)
   __shared__ double xs[XLDS ? (SPMV_BLOCK_NNZ / (BS * BS) + 1) * BS : 1];   // XLDS: x[bs * col .. + bs) of every stored block
   constexpr int BS2 = BS * BS;
-  // interleaved block -> XCD map of the CSR kernels: each XCD walks runs of consecutive row blocks, so a block column's x
-  // entries are pulled into ONE XCD's L2 instead of all eight (PMC at 128^3 nodes: 4.75 GB fetched for 4.35 GB without it)
-#if SPMV_REMAP == 2
-  const int xcd = blockIdx.x % MI355X_NXCD;
-  const int slot = blockIdx.x / MI355X_NXCD;
-  const int lb = ((slot / SPMV_CH) * MI355X_NXCD + xcd) * SPMV_CH + (slot % SPMV_CH);
-#else
-  const int lb = blockIdx.x;
-#endif
+  // the CSR kernels' block -> XCD map: a block column's x entries are pulled into ONE XCD's L2 instead of all eight (PMC at
+  // 128^3 nodes: 4.75 GB fetched for 4.35 GB without it)
+  const int lb = rowblock_of_workgroup(SPMV_CH);
   if (lb >= nblocks) return;
   const int2 b0 = rowblk[lb];
   const int2 b1 = rowblk[lb + 1];
@@ -779,21 +649,20 @@ __global__ __launch_bounds__(SPMV_THREADS) void bsr_rowblock_kernel(const int2 *
 #pragma unroll
       for (int rr = 0; rr < BS; ++rr) acc[rr] += (rr == r) ? p : 0.0;
     }
-    __shared__ double part[SPMV_THREADS / MI355X_WAVE][BS];
+    __shared__ double part[SPMV_WAVES][BS];
 #pragma unroll
     for (int r = 0; r < BS; ++r) { double v = wave_sum(acc[r]); if ((tid & 63) == 0) part[tid / 64][r] = v; }
     __syncthreads();
-    if (tid < BS) { double t = part[0][tid]; for (int w = 1; w < SPMV_THREADS / MI355X_WAVE; ++w) t += part[w][tid]; y[(long)r0 * BS + tid] = yin ? yin[(long)r0 * BS + tid] + t : t; }
+    if (tid < BS) { double t = part[0][tid]; for (int w = 1; w < SPMV_WAVES; ++w) t += part[w][tid]; y[(long)r0 * BS + tid] = yin ? yin[(long)r0 * BS + tid] + t : t; }
     return;
   }
   if (k1 == k0) {   // only empty block rows: up to SPMV_BLOCK_ROWS of them, i.e. up to BS times as many point rows as lanes
     for (int v = tid; v < nv; v += SPMV_THREADS) y[(long)r0 * BS + v] = yin ? yin[(long)r0 * BS + v] : 0.0;
     return;
   }
-  int tpr = 1;
-  while (tpr < MI355X_WAVE && nv * (tpr * 2) <= SPMV_THREADS) tpr *= 2;
-  // extents of this lane's point row, requested before the stream; all loads unconditional (see the idx8 kernel)
-  const int v = tid / tpr, sub = tid & (tpr - 1);
+  const row_lanes rl = lanes_per_row(nv, 0, tid, false);   // (no one-lane rule: point rows are summed with stride bs whatever their length)
+  // extents of this lane's point row, requested before the stream
+  const int tpr = rl.tpr, v = rl.r, sub = rl.sub;
   const int vc = v < nv ? v : nv - 1;
   const int br = r0 + vc / BS;
   const int rr_ = vc - (vc / BS) * BS;
@@ -801,17 +670,11 @@ __global__ __launch_bounds__(SPMV_THREADS) void bsr_rowblock_kernel(const int2 *
   // block columns of this row block: one coalesced load into LDS instead of a global gather per value (a block's bs^2
   // values share one entry); k0 is a multiple of bs^2 because row blocks start at block-row boundaries
   const int kb0 = k0 / BS2, nblk = (k1 - k0) / BS2;
-  constexpr int PAIRS = SPMV_BLOCK_NNZ / (2 * SPMV_THREADS);
-  const int ka = k0 & ~1;
-  v2d vv[PAIRS];
+  v2d vv[SPMV_PAIRS];
   if (XLDS) {
     // the value stream first (it is the long pole), then one block column per lane and its bs x entries
 #pragma unroll
-    for (int p = 0; p < PAIRS; ++p) {
-      const int k = ka + 2 * tid + p * 2 * SPMV_THREADS;
-      const int kk = (k < k1) ? k : ka;
-      vv[p] = SPMV_LOAD(reinterpret_cast<const v2d *>(aa + kk));
-    }
+    for (int p = 0; p < SPMV_PAIRS; ++p) vv[p] = load_pair<v2d>(aa, k0, k1, pair_k(k0, tid, p));
     for (int b = tid; b < nblk; b += SPMV_THREADS) {
       const long c = (long)aj[kb0 + b] * BS;
 #pragma unroll
@@ -820,23 +683,14 @@ __global__ __launch_bounds__(SPMV_THREADS) void bsr_rowblock_kernel(const int2 *
   } else {
     for (int b = tid; b < nblk; b += SPMV_THREADS) ajs[b] = aj[kb0 + b];
 #pragma unroll
-    for (int p = 0; p < PAIRS; ++p) {
-      const int k = ka + 2 * tid + p * 2 * SPMV_THREADS;
-      const int kk = (k < k1) ? k : ka;
-      vv[p] = SPMV_LOAD(reinterpret_cast<const v2d *>(aa + kk));
-    }
+    for (int p = 0; p < SPMV_PAIRS; ++p) vv[p] = load_pair<v2d>(aa, k0, k1, pair_k(k0, tid, p));
   }
   __syncthreads();
-  double xa[PAIRS], xb[PAIRS];
+  double xa[SPMV_PAIRS], xb[SPMV_PAIRS];
 #pragma unroll
-  for (int p = 0; p < PAIRS; ++p) {
-    const int k = ka + 2 * tid + p * 2 * SPMV_THREADS;
-    const bool in = k < k1;
-    const bool v0 = in && k >= k0, v1 = in && (k + 1 < k1);
-    const int kk = in ? k : ka;
-    // value index each slot takes its block column from: its own, or a neighbour inside the block
-    const int f0 = kk + (v0 ? 0 : (in ? 1 : (k0 & 1))) - k0;
-    const int f1 = kk + (v1 ? 1 : (in ? 0 : (k0 & 1))) - k0;
+  for (int p = 0; p < SPMV_PAIRS; ++p) {
+    const pair_src s = pair_source(pair_k(k0, tid, p), k0, k1);
+    const int f0 = s.kk + s.s0 - k0, f1 = s.kk + s.s1 - k0;   // value index each half takes its block column from
     const int blk0 = f0 / BS2, blk1 = f1 / BS2;
     if (XLDS) {
       xa[p] = xs[blk0 * BS + (f0 - blk0 * BS2) / BS];
@@ -847,12 +701,7 @@ __global__ __launch_bounds__(SPMV_THREADS) void bsr_rowblock_kernel(const int2 *
     }
   }
 #pragma unroll
-  for (int p = 0; p < PAIRS; ++p) {
-    const int k = ka + 2 * tid + p * 2 * SPMV_THREADS;
-    const double pa = vv[p].x * xa[p], pb = vv[p].y * xb[p];
-    prod[(k >= k0 && k < k1) ? k - k0 : SPMV_BLOCK_NNZ - 1] = pa;
-    prod[(k + 1 < k1) ? k + 1 - k0 : SPMV_BLOCK_NNZ - 1] = pb;
-  }
+  for (int p = 0; p < SPMV_PAIRS; ++p) park_pair(prod, pair_k(k0, tid, p), k0, k1, vv[p].x * xa[p], vv[p].y * xb[p]);
   __syncthreads();
   const int s = a0 * BS2 - k0;
   const int cnt = v < nv ? (a1 - a0) * BS : 0;
@@ -874,7 +723,6 @@ __global__ __launch_bounds__(SPMV_THREADS) void bsr_rowblock_kernel(const int2 *
 
 // sum of the per-row-block x'y values in block order: 1024 lanes stride over them, fixed tree
 __global__ __launch_bounds__(1024) void dot_partials_kernel(const double *__restrict__ part, int n, double *out) {
-  __shared__ double lds[1024 / MI355X_WAVE];
   // eight loads in flight per lane (one dependent load per step took 22 us for the 57 K values of P7(256)); a fixed order of
   // additions whatever n is: lane t owns values t, t + 1024, ..., added eight accumulators wide, the accumulators in a fixed tree
   double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0, a5 = 0.0, a6 = 0.0, a7 = 0.0;
@@ -885,16 +733,8 @@ __global__ __launch_bounds__(1024) void dot_partials_kernel(const double *__rest
     a0 += v0; a1 += v1; a2 += v2; a3 += v3; a4 += v4; a5 += v5; a6 += v6; a7 += v7;
   }
   for (; i < n; i += 1024) a0 += part[i];
-  double s = ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7));
-  s = wave_sum(s);
-  if ((threadIdx.x & (MI355X_WAVE - 1)) == 0) lds[threadIdx.x / MI355X_WAVE] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = lds[0];
-#pragma unroll
-    for (int w = 1; w < 1024 / MI355X_WAVE; ++w) t += lds[w];
-    out[0] = t;
-  }
+  const double t = workgroup_sum_ordered<1024 / MI355X_WAVE>(((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)));
+  if (threadIdx.x == 0) out[0] = t;
 }
 
 // Value assembly through a precomputed map (MatSetValuesBatch with an unchanged pattern): nonzero `segslot[s]` receives
@@ -937,68 +777,51 @@ __global__ __launch_bounds__(MI355X_BLOCK) void csr_diag_kernel(int m, const int
   d[r] = v;
 }
 
+// Which kernel a plan runs with these arrays: the one decision behind mi355x_spmv_csr / _add / _scaled, mi355x_spmv_csr_dot
+// and mi355x_spmv_plan_dot_available (CG relies on y carrying the same bits from the first two).  In order of precedence;
+// the compressed forms need whole rows (no compressed-row plan) and, all but the value patterns, 16-byte aligned values.
+enum spmv_form_t { SPMV_PLAIN_SCALAR, SPMV_PLAIN, SPMV_IDX8, SPMV_ROWPAT, SPMV_GROUPED, SPMV_VALPAT };
+static spmv_form_t spmv_form(const mi355x_spmv_plan_s *p, const double *aa, const int *aj, bool plain_only = false) {
+  const bool a16 = mi355x_aligned16(aa);
+  if (!p->d_rows && !plain_only) {
+    if (p->vpat_valid && p->use_vpat) return SPMV_VALPAT;
+    if (p->d_gj && a16) return SPMV_GROUPED;
+    if (p->d_prow && p->use_pat && a16) return SPMV_ROWPAT;
+    if (p->d_idx8 && a16) return SPMV_IDX8;
+  }
+  return (a16 && (((uintptr_t)aj) & 7u) == 0) ? SPMV_PLAIN : SPMV_PLAIN_SCALAR;   // pair loads of aa and aj, or the scalar stream
+}
+
 template <int ADD>
 static int launch_spmv(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai, const int *aj, const double *aa,
                        const double *x, const double *yin, double *yout, const double *dsc = nullptr) {
   if (p->nblocks == 0) return 0;
-  const bool vec = mi355x_aligned16(aa) && ((((uintptr_t)aj) & 7u) == 0);
-  const bool cprow = p->d_rows != nullptr;
-  if constexpr (ADD != 3) {   // (ADD == 3 exists in the plain row-block kernel only)
-    if (p->vpat_valid && p->use_vpat && !cprow) {
-      const int nb = (p->nrows + SPMV_VPAT_ROWS - 1) / SPMV_VPAT_ROWS;
-      hipLaunchKernelGGL((spmv_csr_valpat_kernel<ADD, false>), dim3(nb), dim3(SPMV_THREADS), 0, h->stream, p->nrows, p->d_vrow, p->d_vpattab,
-                         p->d_vpatval, p->vtablen, x, yin, yout, (double *)nullptr, p->pairsum);
-      MI355X_LAUNCH_CHECK();
-      return 0;
-    }
-    if (p->d_gj && !cprow && mi355x_aligned16(aa)) {
-#if SPMV_REMAP == 2
-      const int perg = MI355X_NXCD * SPMV_CH;
-      const int gg = ((p->nblocks + perg - 1) / perg) * perg;
-#else
-      const int gg = p->nblocks;
-#endif
-      hipLaunchKernelGGL((spmv_csr_rowblock_inode_kernel<ADD>), dim3(gg), dim3(SPMV_THREADS), 0, h->stream, p->d_rowblk4, p->nblocks,
+  const dim3 grid(rowblock_grid(p->nblocks, SPMV_CH)), block(SPMV_THREADS);
+  const spmv_form_t form = spmv_form(p, aa, aj, ADD == 3);   // (ADD == 3 exists in the plain row-block kernel only)
+  if constexpr (ADD != 3) switch (form) {
+    case SPMV_VALPAT:
+      hipLaunchKernelGGL((spmv_csr_valpat_kernel<ADD, false>), dim3((p->nrows + SPMV_VPAT_ROWS - 1) / SPMV_VPAT_ROWS), block, 0, h->stream,
+                         p->nrows, p->d_vrow, p->d_vpattab, p->d_vpatval, p->vtablen, x, yin, yout, (double *)nullptr, p->pairsum);
+      break;
+    case SPMV_GROUPED:
+      hipLaunchKernelGGL((spmv_csr_rowblock_inode_kernel<ADD>), grid, block, 0, h->stream, p->d_rowblk4, p->nblocks,
                          ai, p->d_goff, p->d_gj, aa, x, yin, yout, p->pairsum);
-      MI355X_LAUNCH_CHECK();
-      return 0;
-    }
-    if (p->d_prow && p->use_pat && !cprow && mi355x_aligned16(aa)) {
-#if SPMV_REMAP == 2
-      const int perp = MI355X_NXCD * p->ch;
-      const int gp = ((p->nblocks + perp - 1) / perp) * perp;
-#else
-      const int gp = p->nblocks;
-#endif
-      hipLaunchKernelGGL((spmv_csr_rowblock_pat_kernel<ADD, false>), dim3(gp), dim3(SPMV_THREADS), 0, h->stream, p->d_rowblk, p->nblocks,
-                         p->d_prow, p->d_pattab, aa, x, yin, yout, (double *)nullptr, p->pairsum, p->ch, spmv_y_streams(p->nrows));
-      MI355X_LAUNCH_CHECK();
-      return 0;
-    }
-    if (p->d_idx8 && !cprow && mi355x_aligned16(aa)) {
-#if SPMV_REMAP == 2
-      const int per8 = MI355X_NXCD * SPMV_CH;
-      const int g8 = ((p->nblocks + per8 - 1) / per8) * per8;
-#else
-      const int g8 = p->nblocks;
-#endif
-      hipLaunchKernelGGL((spmv_csr_rowblock_idx8_kernel<ADD, false>), dim3(g8), dim3(SPMV_THREADS), 0, h->stream, p->d_rowblk,
+      break;
+    case SPMV_ROWPAT:
+      hipLaunchKernelGGL((spmv_csr_rowblock_pat_kernel<ADD, false>), dim3(rowblock_grid(p->nblocks, p->ch)), block, 0, h->stream, p->d_rowblk,
+                         p->nblocks, p->d_prow, p->d_pattab, aa, x, yin, yout, (double *)nullptr, p->pairsum, p->ch, spmv_y_streams(p->nrows));
+      break;
+    case SPMV_IDX8:
+      hipLaunchKernelGGL((spmv_csr_rowblock_idx8_kernel<ADD, false>), grid, block, 0, h->stream, p->d_rowblk,
                          p->nblocks, ai, p->d_idx8, p->d_offtab, p->ntab, aa, x, yin, yout, (double *)nullptr, p->pairsum);
-      MI355X_LAUNCH_CHECK();
-      return 0;
-    }
+      break;
+    default: break;
   }
-#if SPMV_REMAP == 2
-  const int per = MI355X_NXCD * SPMV_CH;
-  dim3 grid(((p->nblocks + per - 1) / per) * per), block(SPMV_THREADS);
-#else
-  dim3 grid(p->chunk * MI355X_NXCD), block(SPMV_THREADS);
-#endif
-#define SPMV_GO(C, V)                                                                                               \
-  hipLaunchKernelGGL((spmv_csr_rowblock_kernel<ADD, C, V>), grid, block, 0, h->stream, p->d_rowblk, p->nblocks,    \
-                     p->chunk, ai, aj, aa, x, yin, yout, p->d_rows, p->pairsum, dsc, spmv_y_streams(p->nrows))
-  if (cprow) { if (vec) SPMV_GO(true, true); else SPMV_GO(true, false); }
-  else       { if (vec) SPMV_GO(false, true); else SPMV_GO(false, false); }
+#define SPMV_GO(C, V)                                                                                                  \
+  hipLaunchKernelGGL((spmv_csr_rowblock_kernel<ADD, C, V>), grid, block, 0, h->stream, p->d_rowblk, p->nblocks, ai, aj, \
+                     aa, x, yin, yout, p->d_rows, p->pairsum, dsc, spmv_y_streams(p->nrows))
+  if (form == SPMV_PLAIN)             { if (p->d_rows) SPMV_GO(true, true); else SPMV_GO(false, true); }
+  else if (form == SPMV_PLAIN_SCALAR) { if (p->d_rows) SPMV_GO(true, false); else SPMV_GO(false, false); }
 #undef SPMV_GO
   MI355X_LAUNCH_CHECK();
   return 0;
@@ -1031,7 +854,6 @@ static int spmv_plan_create(mi355x_handle_t h, int nrows, const int *ai_host, co
     rb.push_back(make_int2(r, ai_host[r]));
   }
   p->nblocks = (int)rb.size() - 1;
-  p->chunk = (p->nblocks + MI355X_NXCD - 1) / MI355X_NXCD;
   MI355X_TRY(hipMalloc((void **)&p->d_rowblk, sizeof(int2) * rb.size()));
   MI355X_TRY(hipMemcpyAsync(p->d_rowblk, rb.data(), sizeof(int2) * rb.size(), hipMemcpyHostToDevice, h->stream));
   if (rows_host) {
@@ -1062,7 +884,7 @@ static int analysis_threads(int m, int cap) {
 // Returns 0 and leaves the plan uncompressed when the matrix has more distinct offsets.
 static int spmv_compress_indices(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai_host, const int *aj_host) {
   if (!p || p->d_rows || p->d_idx8 || p->nrows == 0) return 0;
-  if (SPMV_BLOCK_ROWS > 256) return 0;   // row markers are bytes
+  if (p->nlong) return 0;   // a row longer than the LDS stage: the plain kernel's whole-workgroup path (distinct columns would need > 256 offsets anyway)
   const int m = p->nrows;
   const long nnz = ai_host[m];
   // The rows are analysed in contiguous chunks by host threads (one pass over the column indices of P7(256) on one thread: 0.3 s
@@ -1404,7 +1226,6 @@ static int spmv_group_rows(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *a
   MI355X_TRY(hipMemcpyAsync(p->d_gj, gjh.data(), sizeof(int) * (size_t)ngj, hipMemcpyHostToDevice, h->stream));
   MI355X_TRY(hipStreamSynchronize(h->stream));
   p->nblocks = (int)rb.size() - 1;
-  p->chunk = (p->nblocks + MI355X_NXCD - 1) / MI355X_NXCD;
   p->nlong = 0;
   p->ngroups = ngroups;
   p->ngj = ngj;
@@ -1429,19 +1250,20 @@ int mi355x_spmv_plan_group_info(mi355x_spmv_plan_t p, int *ngroups, long *nshare
 
 int mi355x_spmv_plan_destroy(mi355x_spmv_plan_t p) {
   if (!p) return 0;
+  // (hipFree(nullptr) is a no-op)
   hipFree(p->d_rowblk);
-  if (p->d_idx8) hipFree(p->d_idx8);
-  if (p->d_offtab) hipFree(p->d_offtab);
-  if (p->d_prow) hipFree(p->d_prow);
-  if (p->d_pattab) hipFree(p->d_pattab);
-  if (p->d_vrow) hipFree(p->d_vrow);
-  if (p->d_vpattab) hipFree(p->d_vpattab);
-  if (p->d_vpatval) hipFree(p->d_vpatval);
-  if (p->d_rows) hipFree(p->d_rows);
-  if (p->d_dotpart) hipFree(p->d_dotpart);
-  if (p->d_rowblk4) hipFree(p->d_rowblk4);
-  if (p->d_goff) hipFree(p->d_goff);
-  if (p->d_gj) hipFree(p->d_gj);
+  hipFree(p->d_idx8);
+  hipFree(p->d_offtab);
+  hipFree(p->d_prow);
+  hipFree(p->d_pattab);
+  hipFree(p->d_vrow);
+  hipFree(p->d_vpattab);
+  hipFree(p->d_vpatval);
+  hipFree(p->d_rows);
+  hipFree(p->d_dotpart);
+  hipFree(p->d_rowblk4);
+  hipFree(p->d_goff);
+  hipFree(p->d_gj);
   delete p;
   return 0;
 }
@@ -1453,9 +1275,8 @@ int mi355x_spmv_plan_is_compressed(mi355x_spmv_plan_t p, int *ntab) {
 
 // would mi355x_spmv_csr_dot run on this plan with this value array?
 int mi355x_spmv_plan_dot_available(mi355x_spmv_plan_t p, const double *aa, int *yes) {
-  const bool vpat = p->vpat_valid && p->use_vpat && !p->d_rows;
-  const bool pat = p->d_prow && p->use_pat && !p->d_rows && mi355x_aligned16(aa);
-  if (yes) *yes = (vpat || pat || (p->d_idx8 && !p->d_rows && mi355x_aligned16(aa))) ? 1 : 0;
+  const spmv_form_t form = spmv_form(p, aa, nullptr);
+  if (yes) *yes = (form == SPMV_VALPAT || form == SPMV_ROWPAT || form == SPMV_IDX8) ? 1 : 0;
   return 0;
 }
 
@@ -1483,36 +1304,30 @@ int mi355x_spmv_csr_scaled(mi355x_handle_t h, mi355x_spmv_plan_t plan, const int
 // mi355x_vec_dot).
 int mi355x_spmv_csr_dot(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai, const int *aj, const double *aa,
                         const double *x, double *y) {
-  (void)aj;
-  // the same choice of kernel as mi355x_spmv_csr makes (value patterns, row patterns, 8-bit offsets), each with the per-block sums
-  const bool vpat = p->vpat_valid && p->use_vpat && !p->d_rows;
-  const bool pat = p->d_prow && p->use_pat && !p->d_rows && mi355x_aligned16(aa);
-  if (!vpat && !pat && (!p->d_idx8 || p->d_rows || !mi355x_aligned16(aa))) return (int)hipErrorNotSupported;
+  // the kernel mi355x_spmv_csr runs on these arrays (spmv_form), with the per-block sums where that kernel has them
+  const spmv_form_t form = spmv_form(p, aa, aj);
+  if (form != SPMV_VALPAT && form != SPMV_ROWPAT && form != SPMV_IDX8) return (int)hipErrorNotSupported;
   if (p->nblocks == 0) return 0;
   const int nvb = (p->nrows + SPMV_VPAT_ROWS - 1) / SPMV_VPAT_ROWS;
   { const size_t need = (size_t)(p->nblocks > nvb ? p->nblocks : nvb);
     if (!p->d_dotpart) MI355X_TRY(hipMalloc((void **)&p->d_dotpart, sizeof(double) * need)); }
-#if SPMV_REMAP == 2
-  const int per8 = MI355X_NXCD * SPMV_CH;
-  const int g8 = ((p->nblocks + per8 - 1) / per8) * per8;
-#else
-  const int g8 = p->nblocks;
-#endif
-  if (vpat) {
-    hipLaunchKernelGGL((spmv_csr_valpat_kernel<0, true>), dim3(nvb), dim3(SPMV_THREADS), 0, h->stream, p->nrows, p->d_vrow, p->d_vpattab,
-                       p->d_vpatval, p->vtablen, x, (const double *)nullptr, y, p->d_dotpart, p->pairsum);
-    p->ndotpart = nvb;
-  } else if (pat) {
-    const int perp = MI355X_NXCD * p->ch;
-    const int gp = SPMV_REMAP == 2 ? ((p->nblocks + perp - 1) / perp) * perp : p->nblocks;
-    hipLaunchKernelGGL((spmv_csr_rowblock_pat_kernel<0, true>), dim3(gp), dim3(SPMV_THREADS), 0, h->stream, p->d_rowblk, p->nblocks,
-                       p->d_prow, p->d_pattab, aa, x, (const double *)nullptr, y, p->d_dotpart, p->pairsum, p->ch, spmv_y_streams(p->nrows));
-    p->ndotpart = p->nblocks;
-  } else {
-    hipLaunchKernelGGL((spmv_csr_rowblock_idx8_kernel<0, true>), dim3(g8), dim3(SPMV_THREADS), 0, h->stream, p->d_rowblk,
-                       p->nblocks, ai, p->d_idx8, p->d_offtab, p->ntab, aa, x, (const double *)nullptr, y, p->d_dotpart, p->pairsum);
-    p->ndotpart = p->nblocks;
+  const dim3 block(SPMV_THREADS);
+  const double *const no_yin = nullptr;
+  switch (form) {
+    case SPMV_VALPAT:
+      hipLaunchKernelGGL((spmv_csr_valpat_kernel<0, true>), dim3(nvb), block, 0, h->stream, p->nrows, p->d_vrow, p->d_vpattab,
+                         p->d_vpatval, p->vtablen, x, no_yin, y, p->d_dotpart, p->pairsum);
+      break;
+    case SPMV_ROWPAT:
+      hipLaunchKernelGGL((spmv_csr_rowblock_pat_kernel<0, true>), dim3(rowblock_grid(p->nblocks, p->ch)), block, 0, h->stream, p->d_rowblk,
+                         p->nblocks, p->d_prow, p->d_pattab, aa, x, no_yin, y, p->d_dotpart, p->pairsum, p->ch, spmv_y_streams(p->nrows));
+      break;
+    default:   // SPMV_IDX8
+      hipLaunchKernelGGL((spmv_csr_rowblock_idx8_kernel<0, true>), dim3(rowblock_grid(p->nblocks, SPMV_CH)), block, 0, h->stream, p->d_rowblk,
+                         p->nblocks, ai, p->d_idx8, p->d_offtab, p->ntab, aa, x, no_yin, y, p->d_dotpart, p->pairsum);
+      break;
   }
+  p->ndotpart = form == SPMV_VALPAT ? nvb : p->nblocks;
   MI355X_LAUNCH_CHECK();
   return 0;
 }
@@ -1541,12 +1356,7 @@ int mi355x_spmv_csr_add_scaled(mi355x_handle_t h, mi355x_spmv_plan_t plan, const
 static int spmv_bsr_planned_impl(mi355x_handle_t h, mi355x_spmv_plan_t p, int bs, const int *ai, const int *aj,
                                  const double *aa, const double *x, const double *yin, double *y, bool xlds) {
   if (p->nblocks == 0) return 0;
-#if SPMV_REMAP == 2
-  const int perb = MI355X_NXCD * SPMV_CH;
-  dim3 grid(((p->nblocks + perb - 1) / perb) * perb), block(SPMV_THREADS);
-#else
-  dim3 grid(p->nblocks), block(SPMV_THREADS);
-#endif
+  const dim3 grid(rowblock_grid(p->nblocks, SPMV_CH)), block(SPMV_THREADS);
 #define BSR_GO(B) do { if (xlds) hipLaunchKernelGGL((bsr_rowblock_kernel<B, true>), grid, block, 0, h->stream, p->d_rowblk, p->nblocks, ai, aj, aa, x, yin, y); \
                        else hipLaunchKernelGGL((bsr_rowblock_kernel<B, false>), grid, block, 0, h->stream, p->d_rowblk, p->nblocks, ai, aj, aa, x, yin, y); } while (0)
   switch (bs) {

@@ -1,6 +1,9 @@
 #!/bin/bash
-# build a variant of the kernel library that differs in trisolve.hip only: build_tri.sh NAME -DFOO=1 ...  (development aid for A/B runs on one box)
+# build a variant of the kernel library that differs in trisolve.hip only: build_tri.sh NAME -DFOO=1 ...   (development aid for A/B runs on one box)
+# every other object of the Makefile's SRCS is linked as `make` left it, so the list cannot go stale
 cd "$(dirname "$0")/.." || exit 1
 name=$1; shift
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -I../../include "$@" -c trisolve.hip -o variants/trisolve_$name.o 2>/dev/null || exit 1
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/libmi355x_kernels_$name.so runtime.o vec_kernels.o spmv_csr.o scatter_bsr.o variants/trisolve_$name.o trisolve_build.o comm_rccl.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+vary=trisolve
+others=$(sed -n 's/^SRCS *:= *//p' Makefile | tr ' ' '\n' | sed -n 's/\.hip$/.o/p' | grep -v "^$vary\.o$")
+/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -I../../include "$@" -c $vary.hip -o variants/${vary}_$name.o 2>/dev/null || exit 1
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/libmi355x_kernels_$name.so $others variants/${vary}_$name.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib

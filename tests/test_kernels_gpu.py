@@ -546,8 +546,9 @@ def test_spmv_index_compression_other_shapes(dev):
     assert run_spmv.last_ntab == 0
     sc2 = np.zeros(n); np.add.at(sc2, np.repeat(np.arange(n), np.diff(ai2)), np.abs(aa2 * x[aj2]))
     assert np.all(np.abs(got - orc.spmv(ai2, aj2, aa2, x)) <= 1e-12 * sc2)
-    # Toeplitz-like long row: row 0 holds columns 0..2499 and every row r holds r..r+199 (200 offsets <= 256), so the
-    # compressed kernel's whole-workgroup path runs for row 0
+    # Toeplitz-like long row: row 0 holds columns 0..2499 and every row r holds r..r+199.  The analysis declines (a row
+    # longer than the LDS stage; its 2500 offsets would not fit the table either), so the plain kernel runs and its
+    # whole-workgroup path sums row 0
     n3 = 2600
     cols3 = [np.arange(0, 2500)] + [np.arange(r, min(n3, r + 200)) for r in range(1, n3)]
     ai3 = np.concatenate(([0], np.cumsum([c.size for c in cols3]))).astype(np.int32)
@@ -557,6 +558,64 @@ def test_spmv_index_compression_other_shapes(dev):
     assert run_spmv.last_ntab == 0    # 2500 offsets in row 0
     sc3 = np.zeros(n3); np.add.at(sc3, np.repeat(np.arange(n3), np.diff(ai3)), np.abs(aa3 * x3[aj3]))
     assert np.all(np.abs(got - orc.spmv(ai3, aj3, aa3, x3)) <= 1e-12 * sc3)
+
+
+def test_spmv_unaligned_arrays_take_the_scalar_stream(dev):
+    """value array 8 bytes off a 16-byte boundary and / or column array 4 bytes off an 8-byte boundary: the plain kernel's
+    scalar stream, which is also what every compressed form falls back to.  One lane per row (P7, rows of 0..16 entries over
+    three row blocks with empty rows): the oracle's bits for MatMult, MatMultAdd and the scaled product; a row longer than
+    the LDS stage and 81-entry rows (several lanes per row): 1e-12 * sum|a_ij x_j| (+ |y_r| for MatMultAdd as in test_spmv_irregular;
+    times |d_r| for the scaled product, which multiplies the sum and its error by d_r).  An index-compressed plan whose value
+    array is off by 8 bytes has no x'y by-product (dot_available 0, csr_dot 801) and its product still carries the oracle's bits."""
+    k = dev.k
+
+    def long_row(rng, m):
+        l = rng.integers(1, 9, m); l[7] = 2500
+        return l
+    nb = 300
+    band = [np.arange(max(0, r - 40), min(nb, r + 41)) for r in range(nb)]
+    shapes = [(orc.gen_p7(5, 4, 3), True),
+              (random_csr(600, 500, lambda rng, m: rng.integers(0, 17, m), 66), True),
+              (random_csr(40, 3000, long_row, 67), False),
+              ((np.concatenate(([0], np.cumsum([c.size for c in band]))).astype(np.int32), np.concatenate(band).astype(np.int32), None), False)]
+    for si, ((ai, aj, aa), exact) in enumerate(shapes):
+        if aa is None:
+            aa = rnd(aj.size, 68)
+        m = ai.size - 1
+        x = rnd(int(aj.max()) + 1, 69 + si); y0 = rnd(m, 75); d = rnd(m, 76)
+        scale = np.zeros(m); np.add.at(scale, np.repeat(np.arange(m), np.diff(ai)), np.abs(aa * x[aj]))
+        refs = (orc.spmv(ai, aj, aa, x), orc.spmv_add(ai, aj, aa, x, y0), orc.spmv(ai, aj, aa, x) * d)
+        bounds = (scale, scale + np.abs(y0), np.abs(d) * scale)
+        dai = dev.put(ai); dx = dev.put(x); dy0 = dev.put(y0); dd = dev.put(d); dy = dev.alloc(8 * m)
+        daj = dev.put(np.concatenate(([0], aj)).astype(np.int32))      # one leading pad element each
+        daa = dev.put(np.concatenate(([0.0], aa)))
+        daj0, daa0 = dev.put(aj), dev.put(aa)
+        oaj, oaa = C.c_void_p(daj.value + 4), C.c_void_p(daa.value + 8)
+        plan = make_plan(dev, ai)
+        for paj, paa in ((daj0, oaa), (oaj, daa0), (oaj, oaa)):
+            got = []
+            dev.chk(k.mi355x_spmv_csr(dev.h, plan, dai, paj, paa, dx, dy)); got.append(dev.get(dy, m))
+            dev.chk(k.mi355x_spmv_csr_add(dev.h, plan, dai, paj, paa, dx, dy0, dy)); got.append(dev.get(dy, m))
+            dev.chk(k.mi355x_spmv_csr_scaled(dev.h, plan, dai, paj, paa, dx, dd, dy)); got.append(dev.get(dy, m))
+            for g, ref, bound in zip(got, refs, bounds):
+                if exact:
+                    assert_bitexact(g, ref)
+                else:
+                    assert np.all(np.abs(g - ref) <= 1e-12 * np.maximum(bound, 1e-300)), si
+        if si == 0:     # the compressed plan: by-product and compressed kernels only with an aligned value array
+            dev.chk(k.mi355x_spmv_plan_compress_indices(dev.h, plan, ai.ctypes.data, aj.ctypes.data))
+            nt = C.c_int(); k.mi355x_spmv_plan_is_compressed(plan, C.byref(nt)); assert nt.value == 7
+            yes = C.c_int()
+            dev.chk(k.mi355x_spmv_plan_dot_available(plan, oaa, C.byref(yes))); assert yes.value == 0
+            assert k.mi355x_spmv_csr_dot(dev.h, plan, dai, daj0, oaa, dx, dy) == 801
+            dev.chk(k.mi355x_spmv_csr(dev.h, plan, dai, daj0, oaa, dx, dy))
+            assert_bitexact(dev.get(dy, m), refs[0])
+            dev.chk(k.mi355x_spmv_plan_dot_available(plan, daa0, C.byref(yes))); assert yes.value == 1
+            dev.chk(k.mi355x_spmv_csr_dot(dev.h, plan, dai, daj0, daa0, dx, dy))
+            assert_bitexact(dev.get(dy, m), refs[0])
+        dev.chk(k.mi355x_spmv_plan_destroy(plan))
+        for q in (dai, dx, dy0, dd, dy, daj, daa, daj0, daa0):
+            dev.free(q)
 
 
 def test_spmv_with_dot_byproduct(dev):
