@@ -200,7 +200,8 @@ __device__ __forceinline__ double row_result_lds(const double *prod, int tpr, in
     double sum = 0.0;
     if (has_row) for (int k = rs + sub; k < re; k += tpr) sum += prod[k];
     for (int off = tpr >> 1; off > 0; off >>= 1) sum += __shfl_down(sum, off, MI355X_WAVE);
-    if (has_row && sub == 0) { res = spmv_out<ADD>(yv, sum, dv); spmv_store(dst, res, nt); }
+    // (a row without entries is yv itself, as on the one-lane path: yv + 0.0 would turn yv = -0.0 into +0.0)
+    if (has_row && sub == 0) { res = re == rs ? spmv_empty<ADD>(yv, dv) : spmv_out<ADD>(yv, sum, dv); spmv_store(dst, res, nt); }
   }
   return res;
 }
@@ -708,7 +709,8 @@ __global__ __launch_bounds__(SPMV_THREADS) void bsr_rowblock_kernel(const int2 *
   double sum = 0.0;
   for (int j = sub; j < cnt; j += tpr) sum += prod[s + BS * j + rr_];
   for (int off = tpr >> 1; off > 0; off >>= 1) sum += __shfl_down(sum, off, MI355X_WAVE);
-  if (v < nv && sub == 0) y[(long)br * BS + rr_] = yin ? yin[(long)br * BS + rr_] + sum : sum;
+  // (a block row without blocks is yin itself, as in the only-empty block above: yin + 0.0 would turn yin = -0.0 into +0.0)
+  if (v < nv && sub == 0) y[(long)br * BS + rr_] = yin ? (cnt ? yin[(long)br * BS + rr_] + sum : yin[(long)br * BS + rr_]) : sum;
   // block rows with very few blocks: the row block can hold more point rows than the workgroup has lanes
   // (<= 256 block rows x bs); the remaining ones are summed the same way, one lane per point row (tpr is 1 here)
   for (int v2 = tid + SPMV_THREADS; v2 < nv; v2 += SPMV_THREADS) {
@@ -717,7 +719,7 @@ __global__ __launch_bounds__(SPMV_THREADS) void bsr_rowblock_kernel(const int2 *
     const int s2 = b0_ * BS2 - k0, cnt2 = (b1_ - b0_) * BS;
     double sum2 = 0.0;
     for (int j = 0; j < cnt2; ++j) sum2 += prod[s2 + BS * j + rr2];
-    y[(long)br2 * BS + rr2] = yin ? yin[(long)br2 * BS + rr2] + sum2 : sum2;
+    y[(long)br2 * BS + rr2] = yin ? (cnt2 ? yin[(long)br2 * BS + rr2] + sum2 : yin[(long)br2 * BS + rr2]) : sum2;
   }
 }
 
