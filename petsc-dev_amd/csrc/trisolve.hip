@@ -7,7 +7,6 @@
 #include <vector>
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <memory>
 #include <string.h>
 #include <stdlib.h>
@@ -82,43 +81,171 @@ int mi355x_ilu0_upper_level(mi355x_handle_t h, int nrows, const int *rows, const
 // Every spin is bounded: a lane that gives up raises *abort_flag (pinned host memory) and all spinners drain.
 #include "trisolve_plan.hpp"
 
-__device__ __forceinline__ double tri_poll(const double *p, int *abort_flag, int sleep_cap) {
-  double v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  int spins = 0;
-  while (__double_as_longlong(v) == (long long)TRI_SENTINEL) {
-    // back off: a wavefront far ahead of the solve's front must not flood the L2 with polls (thousands of spinning
-    // wavefronts slowed the producers 3x); the wait grows from 128 clocks by 128 per poll up to sleep_cap x 128
-    { const int k = spins < sleep_cap ? spins + 1 : sleep_cap;
-      for (int z = 0; z < k; ++z) __builtin_amdgcn_s_sleep(2); }
-    if ((++spins & 255) == 0) {
-      if (spins > TRI_SPIN_LIMIT || __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) {
-        __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        break;
+#define TRI_ARM(p) (*(p) = __longlong_as_double((long long)TRI_SENTINEL))
+__device__ __forceinline__ bool tri_unset(const double v) { return __double_as_longlong(v) == (long long)TRI_SENTINEL; }
+__device__ __forceinline__ double tri_peek(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// One bounded back-off step of a wait for a solution value; false: the wait is given up.
+// Back off: a wavefront far ahead of the solve's front must not flood the L2 with polls (thousands of spinning wavefronts slowed
+// the producers 3x); the wait grows from 128 clocks by 128 per poll up to sleep_cap x 128.  Every 256 spins the limit and the
+// abort flag are looked at: a lane that gives up raises the flag, and every other spinner that sees it leaves as well.
+__device__ __forceinline__ bool tri_backoff(int &spins, int *abort_flag, const int sleep_cap) {
+  { const int k = spins < sleep_cap ? spins + 1 : sleep_cap;
+    for (int z = 0; z < k; ++z) __builtin_amdgcn_s_sleep(2); }
+  if ((++spins & 255) == 0) {
+    if (spins > TRI_SPIN_LIMIT || __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) {
+      __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      return false;
+    }
+  }
+  return true;
+}
+
+__device__ __forceinline__ double tri_poll(const double *p, int *abort_flag, const int sleep_cap) {
+  double v = tri_peek(p);
+  for (int spins = 0; tri_unset(v) && tri_backoff(spins, abort_flag, sleep_cap);) v = tri_peek(p);
+  return v;
+}
+
+// The values of a batch that were not there yet (live(j): entry j belongs to this lane's list): ALL pending values are requested
+// again together, round after round -- one memory round trip per round however many are pending.  A row's dependencies of the
+// previous level complete at about the same time: polled one after the other, each of them cost a round trip of its own ON the
+// dependency chain (P7(256), 3 entries per row: 2.83 ms per application that way, 2.67 so).  Two probes in flight half a round
+// trip apart were measured too: 3.1-3.5 ms -- more poll traffic slows the producers down.
+template <int B, class Addr, class Live>
+__device__ __forceinline__ void tri_poll_batch(double (&v)[B], Addr addr, Live live, int *abort_flag, const int sleep_cap) {
+  auto pending = [&]() __attribute__((always_inline)) {
+    bool pend = false;
+#pragma unroll
+    for (int j = 0; j < B; ++j) pend = pend || (live(j) && tri_unset(v[j]));
+    return pend;
+  };
+  for (int spins = 0; pending() && tri_backoff(spins, abort_flag, sleep_cap);) {
+#pragma unroll
+    for (int j = 0; j < B; ++j)
+      if (live(j) && tri_unset(v[j])) v[j] = tri_peek(addr(j));
+  }
+}
+
+// A solved value becomes visible to the polling wavefronts: agent scope always -- a solution value is polled by OTHER workgroups,
+// and only an agent-scope store (written through to the memory side) is visible to them by the memory model.  (Round 3 stored with
+// workgroup scope in the one-XCD form of the split-role kernels -- the line then stays in the XCD's L2, 13.4 instead of 14.0 ms on
+// the FEM stand-in -- which is correct only as long as L1 writes through and every poller shares that L2: not kept.)
+__device__ __forceinline__ void tri_publish(double *p, const double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// The workgroup's next chunk: thread 0 takes a ticket of queue q (chunk c belongs to queue c % TRI_QUEUES) and hands it to the
+// others through a double-buffered LDS word -- the slot written two iterations ago is free again: one barrier per iteration.
+__device__ __forceinline__ int tri_next_chunk(int *chunk_s, const int it, unsigned int *queue, const int q) {
+  if (threadIdx.x == 0) {
+    const unsigned int k = __hip_atomic_fetch_add(queue + q * TRI_QSTRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    chunk_s[it & 1] = (int)(k * TRI_QUEUES + q);
+  }
+  __syncthreads();
+  return chunk_s[it & 1];
+}
+// ... and one wavefront's next slice (the loader of the split-role kernels): lane 0's ticket, broadcast
+__device__ __forceinline__ long tri_next_slice(const int lane, unsigned int *queue, const int q) {
+  unsigned int k = 0;
+  if (lane == 0) k = __hip_atomic_fetch_add(queue + q * TRI_QSTRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  k = (unsigned int)__builtin_amdgcn_readfirstlane((int)k);
+  return (long)k * TRI_QUEUES + q;
+}
+
+// What every sync-free kernel does before its first chunk.  Workgroup 0 zeroes the OTHER solve's queue counters (XCD: and the words
+// of its one-XCD election).  The lower solve re-arms the tail of the other solve's vector: `reset` is the upper solve's w, complete
+// since the previous application, and may be longer than this plan's own `own` slots (its own level padding); the slots below
+// `own` are re-armed position by position (tri_rearm_position).  The upper solve re-arms the lower solve's slots as it reads them.
+template <bool UPPER, bool XCD>
+__device__ __forceinline__ void tri_prologue(unsigned int *other_queue, double *reset, const long own, const long reset_n, const int nthreads) {
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 0 && tid < TRI_QUEUES) other_queue[tid * TRI_QSTRIDE] = 0u;
+  if (XCD && blockIdx.x == 0 && tid == 0) { other_queue[TRI_XCD_WORD] = 0xffffffffu; other_queue[TRI_XCD_WORD + 1] = 0u; }
+  if (!UPPER) {
+    for (long i = own + (long)blockIdx.x * nthreads + tid; i < reset_n; i += (long)gridDim.x * nthreads) TRI_ARM(reset + i);
+  }
+}
+// (lower solve) the other solve's slots of position t: row k of the node at k * np + t, with block columns at t * NB + k
+template <int NB, bool BLK>
+__device__ __forceinline__ void tri_rearm_position(double *reset, const int t, const int np, const int reset_n) {
+#pragma unroll
+  for (int k = 0; k < NB; ++k) { const long i = BLK ? (long)t * NB + k : (long)k * np + t; if (i < reset_n) TRI_ARM(reset + i); }
+}
+
+// Right-hand side of the nsz rows of the node at position t (first row row0; nsz = 0: a padding position, nothing is read).
+// Lower: b in natural order.  Upper: the lower solve's result, src[spos[row]], times rscale[t] where the plan has one
+// (single-row plans of an incomplete Cholesky factor, MatSolve_SeqSBAIJ_1_NaturalOrdering: x[i] = xi * (1/D(i)) between the two
+// sweeps); sum[k] belongs to the node's row nsz - 1 - k (k = distance from the LAST row, as the reference counts).  REARM: the slot
+// read goes back to the sentinel right away -- only this lane reads it.
+template <int NB, bool UPPER, bool REARM>
+__device__ __forceinline__ void tri_node_rhs(double (&sum)[NB], const int t, const int row0, const int nsz, const double *src, const int *__restrict__ spos,
+                                             const double *__restrict__ rscale, double *reset) {
+#pragma unroll
+  for (int k = 0; k < NB; ++k) {
+    sum[k] = 0.0;
+    if (k < nsz) {
+      if (UPPER) {
+        const int p = spos[row0 + nsz - 1 - k];
+        sum[k] = src[p];
+        if (rscale) sum[k] = sum[k] * rscale[t];
+        if (REARM) TRI_ARM(reset + p);
+      } else sum[k] = src[row0 + k];
+    }
+  }
+}
+
+// End of a node: the couplings inside the node (dn[k (k - 1) / 2 + l], row after row), upper: times the inverted diagonals
+// (dn[NT + k]), nearest row last (inode.c:2604-2610); the results to w (POLL: published to the polling wavefronts) and, upper, to y.
+template <int NB, bool UPPER, bool BLK, bool POLL>
+__device__ __forceinline__ void tri_node_finish(double (&sum)[NB], const double *dn, const int t, const int np, const int row0, const int nsz, double *w, double *y) {
+  constexpr int NT = NB * (NB - 1) / 2;
+  auto put = [&](const int k, const double v) __attribute__((always_inline)) {
+    double *dst = BLK ? w + (size_t)t * NB + k : w + (size_t)k * np + t;
+    if (POLL) tri_publish(dst, v);
+    else *dst = v;
+  };
+  if (!UPPER) {
+#pragma unroll
+    for (int k = 1; k < NB; ++k) {
+      if (k < nsz) {
+#pragma unroll
+        for (int l = 0; l < k; ++l) sum[k] -= dn[k * (k - 1) / 2 + l] * sum[l];
       }
     }
-    v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int k = 0; k < NB; ++k)
+      if (k < nsz) put(k, sum[k]);
+  } else {
+    double xr[NB];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+      xr[k] = 0.0;
+      if (k < nsz) {
+#pragma unroll
+        for (int l = 0; l < k; ++l) sum[k] -= dn[k * (k - 1) / 2 + (k - 1 - l)] * xr[l];
+        xr[k] = sum[k] * dn[NT + k];
+        const int kk = nsz - 1 - k;            // the row's slot counts from the node's FIRST row
+        put(kk, xr[k]);
+        y[row0 + kk] = xr[k];
+      }
+    }
   }
-  return v;
 }
 
 // UPPER == false: w[t] = b[row] - L(row,:) w          (b in natural order)
 // UPPER == true : w[t] = (src[spos[row]] - U(row,:) w) * dinv[t] ;  y[row] = w[t]   (src = the lower solve's w)
-// `reset`: the OTHER solve's w, returned to the sentinel for its next run -- lower: reset[t] (coalesced; the upper
-// solve of the previous application is complete), upper: src[spos[row]] right after it has been read (only this lane
-// reads that entry).  other_queue: the other solve's queue counters, zeroed by workgroup 0.
+// `reset`: the OTHER solve's w, returned to the sentinel for its next run (tri_prologue, tri_rearm_position, tri_node_rhs).
+// other_queue: the other solve's queue counters.
 #ifdef MI355X_TRI_TRACE
-// development build (csrc/variants/build_tri_trace.sh): lane 0 of every wavefront leaves four timestamps per slice (100 MHz
-// wall clock): slice start, last batch's entries looked at, last dependency arrived, result stored
+// development build (csrc/variants/build_tri_trace.sh): lane 0 of every wavefront leaves `stride` timestamps per slice (100 MHz wall
+// clock).  Row kernel, 4: slice start, last batch's entries looked at, last dependency arrived, result stored.  Node kernels, 8:
+// start, after each of the first five batches, last dependency consumed, results stored.
 __device__ long long *tri_trace_buf = nullptr;
 extern "C" int mi355x_trisolve_debug_trace(long long *dev_buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(tri_trace_buf), &dev_buf, sizeof(dev_buf)); }
-#define TRI_STAMP(k) do { if (tri_trace_buf && lane == 0) tri_trace_buf[(UPPER ? 8000000L : 0L) + (long)s * 4 + (k)] = wall_clock64(); } while (0)
+#define TRI_STAMP(on, slice, stride, k) do { if ((on) && tri_trace_buf && lane == 0) tri_trace_buf[(UPPER ? 8000000L : 0L) + (long)(slice) * (stride) + (k)] = wall_clock64(); } while (0)
 #else
-#define TRI_STAMP(k) do { } while (0)
+#define TRI_STAMP(on, slice, stride, k) do { } while (0)
 #endif
 
-#ifndef TRI_POLL_TOGETHER
-#define TRI_POLL_TOGETHER 1
-#endif
 template <bool UPPER>
 __global__ __launch_bounds__(MI355X_BLOCK) void trisolve_syncfree_kernel(
     int nslices, int nchunks, const int *__restrict__ ptr, const int *__restrict__ info, const int *__restrict__ rowof,
@@ -128,40 +255,23 @@ __global__ __launch_bounds__(MI355X_BLOCK) void trisolve_syncfree_kernel(
     const double *__restrict__ rscale) {
   __shared__ int chunk_s[2];
   const int tid = threadIdx.x, lane = tid & (MI355X_WAVE - 1), wave = tid / MI355X_WAVE;
-  if (blockIdx.x == 0 && tid < TRI_QUEUES) other_queue[tid * TRI_QSTRIDE] = 0u;
-  if (!UPPER) {   // the other solve's vector may be longer than this one's (its own level padding): the tail is re-armed here
-    for (long i = (long)nslices * MI355X_WAVE + (long)blockIdx.x * MI355X_BLOCK + tid; i < reset_n; i += (long)gridDim.x * MI355X_BLOCK)
-      reset[i] = __longlong_as_double((long long)TRI_SENTINEL);
-  }
+  tri_prologue<UPPER, false>(other_queue, reset, (long)nslices * MI355X_WAVE, reset_n, MI355X_BLOCK);
   const int q = blockIdx.x % TRI_QUEUES;
   for (int it = 0;; ++it) {
-    if (tid == 0) {
-      const unsigned int k = __hip_atomic_fetch_add(queue + q * TRI_QSTRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      chunk_s[it & 1] = (int)(k * TRI_QUEUES + q);
-    }
-    __syncthreads();                       // (the slot written two iterations ago is free again: one barrier per iteration)
-    const int chunk = chunk_s[it & 1];
+    const int chunk = tri_next_chunk(chunk_s, it, queue, q);
     if (chunk >= nchunks || chunk < 0) break;
     const int s = chunk * (MI355X_BLOCK / MI355X_WAVE) + wave;
     if (s >= nslices) continue;
     const int t = s * MI355X_WAVE + lane;
-    const int base = ptr[s], slen = (ptr[s + 1] - base) / MI355X_WAVE;
+    const int base = ptr[s];
     const int inf = info[t], row = rowof[t];
     const int mylen = inf >> 8, mysub = inf & 255;
     const int ns = nsub[s];
-    double sum = 0.0;
-    if (row >= 0) {
-      if (UPPER) {
-        const int p = spos[row];
-        sum = src[p];
-        if (rscale) sum = sum * rscale[t];          // MatSolve_SeqSBAIJ_1_NaturalOrdering: x[i] = xi * (1/D(i)) between the two sweeps
-        reset[p] = __longlong_as_double((long long)TRI_SENTINEL);
-      }
-      else sum = src[row];
-    }
-    if (!UPPER && t < reset_n) reset[t] = __longlong_as_double((long long)TRI_SENTINEL);
-    const double di = UPPER ? dinv[t] : 1.0;
-    TRI_STAMP(0);
+    double sum[1];
+    tri_node_rhs<1, UPPER, true>(sum, t, row, row >= 0 ? 1 : 0, src, spos, rscale, reset);
+    if (!UPPER) tri_rearm_position<1, false>(reset, t, 0, reset_n);
+    const double di[1] = {UPPER ? dinv[t] : 1.0};
+    TRI_STAMP(true, s, 4, 0);
     for (int step = 0; step < ns; ++step) {
       if (row >= 0 && mysub == step) {
         // entries in batches of 8: the loads of a batch are issued together, consumed in stored order
@@ -176,56 +286,20 @@ __global__ __launch_bounds__(MI355X_BLOCK) void trisolve_syncfree_kernel(
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
             v[j] = 0.0;
-            if (q0 + j < mylen) v[j] = __hip_atomic_load(w + c[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (q0 + j < mylen) v[j] = tri_peek(w + c[j]);
           }
-          if (q0 + 8 >= mylen) TRI_STAMP(1);
-#if TRI_POLL_TOGETHER
-          // values that were not there yet: ALL of the batch's pending values are requested again together, round after round -- one
-          // memory round trip per round however many are pending (a row's dependencies of the previous level complete at about the
-          // same time: polled one after the other, each of them cost a round trip of its own ON the dependency chain: P7(256),
-          // 3 entries per row, 2.83 ms per application that way, 2.67 so); backed off and bounded as tri_poll is.  Two probes in
-          // flight half a round trip apart were measured too: 3.1-3.5 ms -- more poll traffic slows the producers down
-          { bool pend = false;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pend = pend || (q0 + j < mylen && __double_as_longlong(v[j]) == (long long)TRI_SENTINEL);
-            for (int spins = 0; pend;) {
-              { const int kz = spins < sleep_cap ? spins + 1 : sleep_cap;
-                for (int z = 0; z < kz; ++z) __builtin_amdgcn_s_sleep(2); }
-              if ((++spins & 255) == 0) {
-                if (spins > TRI_SPIN_LIMIT || __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) {
-                  __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                  break;
-                }
-              }
-#pragma unroll
-              for (int j = 0; j < 8; ++j)
-                if (q0 + j < mylen && __double_as_longlong(v[j]) == (long long)TRI_SENTINEL) v[j] = __hip_atomic_load(w + c[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              pend = false;
-#pragma unroll
-              for (int j = 0; j < 8; ++j) pend = pend || (q0 + j < mylen && __double_as_longlong(v[j]) == (long long)TRI_SENTINEL);
-            } }
+          if (q0 + 8 >= mylen) TRI_STAMP(true, s, 4, 1);
+          tri_poll_batch<8>(v, [&](const int j) __attribute__((always_inline)) { return w + c[j]; },
+                            [&](const int j) __attribute__((always_inline)) { return q0 + j < mylen; }, abort_flag, sleep_cap);
 #pragma unroll
           for (int j = 0; j < 8; ++j)
-            if (q0 + j < mylen) sum -= a[j] * v[j];
-#else
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            if (q0 + j < mylen) {
-              double xv = v[j];
-              if (__double_as_longlong(xv) == (long long)TRI_SENTINEL) xv = tri_poll(w + c[j], abort_flag, sleep_cap);
-              sum -= a[j] * xv;
-            }
-          }
-#endif
+            if (q0 + j < mylen) sum[0] -= a[j] * v[j];
         }
-        TRI_STAMP(2);
-        const double r = UPPER ? sum * di : sum;
-        __hip_atomic_store(w + t, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        TRI_STAMP(3);
-        if (UPPER) y[row] = r;
+        TRI_STAMP(true, s, 4, 2);
+        tri_node_finish<1, UPPER, false, true>(sum, di, t, 0, row, 1, w, y);
+        TRI_STAMP(true, s, 4, 3);
       }
     }
-    (void)slen;
   }
 }
 
@@ -242,13 +316,6 @@ __global__ __launch_bounds__(MI355X_BLOCK) void trisolve_syncfree_kernel(
 // node row after row -- bit for bit MatSolve_SeqAIJ_Inode while the columns are stored in column order (by_level = 0).
 // The index / value loads of the NEXT batch of columns are issued before the current batch's polls: they do not depend on any
 // solution value, and behind the polls they would add a memory round trip per batch to the dependency chain.
-#ifdef MI355X_TRI_TRACE
-// trace build: lane 0 of every wavefront leaves eight timestamps per slice: start, after each of the first five batches, last
-// dependency consumed, results stored
-#define TRI_NSTAMP(k) do { if (POLL && tri_trace_buf && lane == 0) tri_trace_buf[(UPPER ? 8000000L : 0L) + (long)(t / MI355X_WAVE) * 8 + (k)] = wall_clock64(); } while (0)
-#else
-#define TRI_NSTAMP(k) do { } while (0)
-#endif
 template <int NB, bool UPPER, bool POLL, bool BLK>
 __device__ __forceinline__ void tri_node_solve(const int t, const int lane, const int np, const int base, const int off, const int ncol, const int row0, const int nsz,
                                                const int *__restrict__ col, const double *__restrict__ val, const double *__restrict__ din,
@@ -266,29 +333,19 @@ __device__ __forceinline__ void tri_node_solve(const int t, const int lane, cons
   constexpr int CB = BLK ? B / NB : B;         // list entries per batch
   constexpr int NT = NB * (NB - 1) / 2;
   double sum[NB];
-#pragma unroll
-  for (int k = 0; k < NB; ++k) {
-    sum[k] = 0.0;
-    if (k < nsz) {
-      if (UPPER) {                             // sum[k] belongs to the node's row nsz - 1 - k (k = distance from the LAST row, as the reference counts)
-        const int p = spos[row0 + nsz - 1 - k];
-        sum[k] = src[p];
-        if (rscale) sum[k] = sum[k] * rscale[t];      // single-row plans of an incomplete Cholesky factor: D^-1 between the two sweeps
-        if (POLL) reset[p] = __longlong_as_double((long long)TRI_SENTINEL);
-      } else sum[k] = src[row0 + k];
-    }
-  }
+  tri_node_rhs<NB, UPPER, POLL>(sum, t, row0, nsz, src, spos, rscale, reset);
   // (without block columns a lane's list sits at the END of the slice's slots, trisolve_plan_fill_nodes: `off` slots of padding first)
   const double *vbase = val + ((size_t)base + (size_t)off * MI355X_WAVE) * NB + lane;
   const int *cbase = col + (BLK ? base / NB : base + off * MI355X_WAVE) + lane;
-#define TRI_XADDR(cX, j) (BLK ? w + (size_t)cX[(j) / NB] * NB + ((j) % NB) : w + cX[(j)])
-  TRI_NSTAMP(0);
+  TRI_STAMP(POLL, t / MI355X_WAVE, 8, 0);
   // the node's own triangle (and inverted diagonals): requested now, needed after the last dependency has arrived
   double dn[NT + (UPPER ? NB : 0) + 1];
 #pragma unroll
   for (int e = 0; e < NT + (UPPER ? NB : 0); ++e) dn[e] = din[(size_t)e * np + t];
   constexpr int qstart = 0;
   int cA[CB]; double aA[B * NB];
+  // where column j of the current batch lives in w
+  auto xaddr = [&](const int j) __attribute__((always_inline)) { return BLK ? w + (size_t)cA[j / NB] * NB + (j % NB) : w + cA[j]; };
 #pragma unroll
   for (int j = 0; j < CB; ++j) {
     const int q = BLK ? j * NB : qstart + j, qq = (q >= 0 && q < ncol) ? q : 0;
@@ -305,7 +362,7 @@ __device__ __forceinline__ void tri_node_solve(const int t, const int lane, cons
 #pragma unroll
     for (int j = 0; j < B; ++j) {
       v[j] = 0.0;
-      if (q0 + j >= 0 && q0 + j < ncol) v[j] = POLL ? __hip_atomic_load(TRI_XADDR(cA, j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *TRI_XADDR(cA, j);
+      if (q0 + j >= 0 && q0 + j < ncol) v[j] = POLL ? tri_peek(xaddr(j)) : *xaddr(j);
     }
     // the next batch's indices and values go out BEHIND this batch's gathers (loads return in issue order: the gathers must not
     // queue behind a round trip to HBM) and are in flight while this batch waits for its dependencies
@@ -324,21 +381,21 @@ __device__ __forceinline__ void tri_node_solve(const int t, const int lane, cons
     }
     // A value that was not there yet is polled for; when it arrives, the batch's other pending values are requested again
     // TOGETHER (one round trip): the rows of a node are stored by one lane at one time, and a poll per value would put a
-    // memory round trip per value on the dependency chain
-#define TRI_REFRESH(from)                                                                                              \
-  do {                                                                                                                 \
-    _Pragma("unroll") for (int jj = (from); jj < B; ++jj)                                                              \
-      if (q0 + jj >= 0 && q0 + jj < ncol && __double_as_longlong(v[jj]) == (long long)TRI_SENTINEL)                    \
-        v[jj] = __hip_atomic_load(TRI_XADDR(cA, jj), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                      \
-  } while (0)
+    // memory round trip per value on the dependency chain.  (Another schedule than tri_poll_batch's, and the one the node kernels
+    // were measured with.)
+    auto refresh = [&](const int from) __attribute__((always_inline)) {
+#pragma unroll
+      for (int jj = from; jj < B; ++jj)
+        if (q0 + jj >= 0 && q0 + jj < ncol && tri_unset(v[jj])) v[jj] = tri_peek(xaddr(jj));
+    };
 #pragma unroll
     for (int j = 0; j < B; j += 2) {
       if (q0 + j >= 0 && q0 + j < ncol) {
         double x0 = v[j];
-        if (POLL && __double_as_longlong(x0) == (long long)TRI_SENTINEL) { x0 = tri_poll(TRI_XADDR(cA, j), abort_flag, sleep_cap); TRI_REFRESH(j + 1); }
+        if (POLL && tri_unset(x0)) { x0 = tri_poll(xaddr(j), abort_flag, sleep_cap); refresh(j + 1); }
         if (q0 + j + 1 < ncol) {
           double x1 = v[j + 1];
-          if (POLL && __double_as_longlong(x1) == (long long)TRI_SENTINEL) { x1 = tri_poll(TRI_XADDR(cA, j + 1), abort_flag, sleep_cap); TRI_REFRESH(j + 2); }
+          if (POLL && tri_unset(x1)) { x1 = tri_poll(xaddr(j + 1), abort_flag, sleep_cap); refresh(j + 2); }
           if (NB == 1) { sum[0] -= aA[j] * x0; sum[0] -= aA[j + 1] * x1; }     // single rows: one product after the other (aijfact.c:3126)
           else {
 #pragma unroll
@@ -350,7 +407,6 @@ __device__ __forceinline__ void tri_node_solve(const int t, const int lane, cons
         }
       }
     }
-#undef TRI_REFRESH
 #pragma unroll
     for (int j = 0; j < CB; ++j) cA[j] = cN[j];
 #pragma unroll
@@ -358,44 +414,11 @@ __device__ __forceinline__ void tri_node_solve(const int t, const int lane, cons
 #pragma unroll
       for (int k = 0; k < NB; ++k) aA[j * NB + k] = aN[j * NB + k];
     }
-    if ((q0 - qstart) / B < 5) TRI_NSTAMP(1 + (q0 - qstart) / B);
+    if ((q0 - qstart) / B < 5) TRI_STAMP(POLL, t / MI355X_WAVE, 8, 1 + (q0 - qstart) / B);
   }
-  TRI_NSTAMP(6);
-  // the couplings inside the node
-  if (!UPPER) {
-#pragma unroll
-    for (int k = 1; k < NB; ++k) {
-      if (k < nsz) {
-#pragma unroll
-        for (int l = 0; l < k; ++l) sum[k] -= dn[k * (k - 1) / 2 + l] * sum[l];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < NB; ++k)
-      if (k < nsz) {
-        double *dst = BLK ? w + (size_t)t * NB + k : w + (size_t)k * np + t;
-        if (POLL) __hip_atomic_store(dst, sum[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else *dst = sum[k];
-      }
-  } else {
-    double xr[NB];
-#pragma unroll
-    for (int k = 0; k < NB; ++k) {
-      xr[k] = 0.0;
-      if (k < nsz) {
-#pragma unroll
-        for (int l = 0; l < k; ++l) sum[k] -= dn[k * (k - 1) / 2 + (k - 1 - l)] * xr[l];   // nearest row last (inode.c:2604-2610)
-        xr[k] = sum[k] * dn[NT + k];
-        const int kk = nsz - 1 - k;            // the row's slot counts from the node's FIRST row
-        double *dst = BLK ? w + (size_t)t * NB + kk : w + (size_t)kk * np + t;
-        if (POLL) __hip_atomic_store(dst, xr[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else *dst = xr[k];
-        y[row0 + kk] = xr[k];
-      }
-    }
-  }
-  TRI_NSTAMP(7);
-#undef TRI_XADDR
+  TRI_STAMP(POLL, t / MI355X_WAVE, 8, 6);
+  tri_node_finish<NB, UPPER, BLK, POLL>(sum, dn, t, np, row0, nsz, w, y);
+  TRI_STAMP(POLL, t / MI355X_WAVE, 8, 7);
 }
 
 template <int NB, bool UPPER, bool BLK>
@@ -406,19 +429,10 @@ __global__ __launch_bounds__(MI355X_BLOCK) void trisolve_node_kernel(
     double *reset, int reset_n, unsigned int *queue, unsigned int *other_queue, int *abort_flag, int sleep_cap, const double *__restrict__ rscale) {
   __shared__ int chunk_s[2];
   const int tid = threadIdx.x, lane = tid & (MI355X_WAVE - 1), wave = tid / MI355X_WAVE;
-  if (blockIdx.x == 0 && tid < TRI_QUEUES) other_queue[tid * TRI_QSTRIDE] = 0u;
-  if (!UPPER) {   // the upper solve's slots beyond this plan's own positions are re-armed here
-    for (long i = (long)NB * np + (long)blockIdx.x * blockDim.x + tid; i < reset_n; i += (long)gridDim.x * blockDim.x)
-      reset[i] = __longlong_as_double((long long)TRI_SENTINEL);
-  }
+  tri_prologue<UPPER, false>(other_queue, reset, (long)NB * np, reset_n, blockDim.x);
   const int q = blockIdx.x % TRI_QUEUES;
   for (int it = 0;; ++it) {
-    if (tid == 0) {
-      const unsigned int k = __hip_atomic_fetch_add(queue + q * TRI_QSTRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      chunk_s[it & 1] = (int)(k * TRI_QUEUES + q);
-    }
-    __syncthreads();
-    const int chunk = chunk_s[it & 1];
+    const int chunk = tri_next_chunk(chunk_s, it, queue, q);
     if (chunk >= nchunks || chunk < 0) break;
     const int s = chunk * (int)(blockDim.x / MI355X_WAVE) + wave;
     if (s >= nslices) continue;
@@ -426,10 +440,7 @@ __global__ __launch_bounds__(MI355X_BLOCK) void trisolve_node_kernel(
     const int inf = info[t], row0 = rowof[t], nsz = nszof[t];
     const int ncol = inf >> 8, mysub = inf & 255;
     const int ns = nsub[s];
-    if (!UPPER) {   // re-arm the other (upper) solve's slots of this position: its previous application is complete
-#pragma unroll
-      for (int k = 0; k < NB; ++k) { const long i = BLK ? (long)t * NB + k : (long)k * np + t; if (i < reset_n) reset[i] = __longlong_as_double((long long)TRI_SENTINEL); }
-    }
+    if (!UPPER) tri_rearm_position<NB, BLK>(reset, t, np, reset_n);
     for (int step = 0; step < ns; ++step)
       if (row0 >= 0 && mysub == step)
         tri_node_solve<NB, UPPER, true, BLK>(t, lane, np, ptr[s], BLK ? 0 : (((ptr[s + 1] - ptr[s]) / MI355X_WAVE - ncol) & ~1), ncol, row0, nsz, col, val, din, src, spos, w, y,
@@ -445,21 +456,16 @@ __global__ __launch_bounds__(MI355X_BLOCK) void trisolve_node_kernel(
 // wavefronts: the LOADER dequeues slices and streams their headers, indices and values from HBM into a ring of batches in LDS,
 // running ahead; the SOLVER's only vector-memory operations are the gathers / polls of solution values and its result stores, so
 // a poll costs one L2 / fabric round trip (0.3-0.6 us, tests/tools/probe/handoff_probe.hip).  Same plan arrays, same column
-// sequence, same pairs, same triangle: same bits as tri_node_solve.  Slices with dependent sub-steps (small levels packed into one
-// slice) are solved by the solver with tri_node_solve itself.
+// sequence, same pairs, same triangle (tri_node_rhs, tri_node_finish): same bits as tri_node_solve.  Slices with dependent sub-steps
+// (small levels packed into one slice) are solved by the solver with tri_node_solve itself.
+// A batch's values are requested when the batch is due: a value requested early is mostly a stale sentinel that costs a poll round
+// later.  (Schedules with the gathers 1 and 3 batches ahead of the products were measured and removed: FEM stand-in 13.9 ms as
+// here, 19.3 at 1, 22.7 at 3; in the inode routine's column order 30.0 / 35.5 / 44.7 -- profiles/r03_tri_variants.log.)
 // LDS: [64 B counters][2 headers][R batch stages]; counters: 0 headers produced, 1 headers consumed, 2 batches produced,
 // 3 batches consumed (monotonic; each has one writer).  LDS operations of a wavefront execute in order: data, s_waitcnt, counter.
-// A solved value becomes visible to the polling wavefronts.  All XCDs: an agent-scope store (written through to the memory side,
-// 0.54 us to a poller on another XCD).  One XCD (every participating workgroup runs on the same XCD, see the kernel): the XCD's L2 is
-// the point of coherence for all of them, a workgroup-scope store reaches it and an agent-scope load reads it there: 0.27 us
+// A solved value reaches the polling wavefronts through tri_publish: 0.54 us to a poller on another XCD; in the one-XCD form (every
+// participating workgroup runs on the same XCD, see the kernel) that XCD's L2 is where the agent-scope loads find it
 // (tests/tools/probe/handoff_probe.hip, profiles/r03_tri_variants.log).
-__device__ __forceinline__ void tri_publish(double *p, const double v, const int one_xcd) {
-  // agent scope always: a solution value is polled by OTHER workgroups, and only an agent-scope store is visible to them by the memory
-  // model.  (Round 3 stored with workgroup scope in the one-XCD form -- the line then stays in the XCD's L2, 13.4 instead of 14.0 ms on
-  // the FEM stand-in -- which is correct only as long as L1 writes through and every poller shares that L2: not kept.)
-  (void)one_xcd;
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 template <int NB> struct TriSplitGeom {
 #ifndef TRI_SPLIT_B3
 #define TRI_SPLIT_B3 16
@@ -475,24 +481,19 @@ template <int NB> struct TriSplitGeom {
   static constexpr int HB = 64 + 3 * 256 + (NB + ND) * 512;     // header bytes: meta, info / first row / rows per lane, right-hand sides, triangle
   static constexpr int SB = B * 256 + B * NB * 512;             // stage bytes: B index rows, B * NB value rows
   // legal ranges of the build knobs (csrc/variants/build_tri.sh passes arbitrary -D options: a variant outside them must not build):
-  // pairs of the inode summation stay pairs (even batches), and the smallest ring -- look-ahead + 3 batches -- fits the LDS asked for
+  // pairs of the inode summation stay pairs (even batches), and the smallest ring -- 3 batches -- fits the LDS asked for
   static_assert(B >= 2 && B % 2 == 0 && B <= 32, "TRI_SPLIT_B*: an even number of columns per batch, at most 32");
+  static __device__ __forceinline__ unsigned char *header(unsigned char *lds, const int h) { return lds + 64 + (h & 1) * HB; }
+  static __device__ __forceinline__ unsigned char *stage(unsigned char *lds, const int b, const int R) { return lds + 64 + 2 * HB + (size_t)(b % R) * SB; }
 };
 #define TRI_SPLIT_LDS_BYTES (150 * 1024)
 #define TRI_LDS_FENCE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#ifndef TRI_LOOKAHEAD
-// batches the solver's gathers run ahead of its products.  0: a batch's values are requested when the batch is due -- a value
-// requested early is mostly a stale sentinel that costs a poll round later (FEM stand-in, profiles/r03_tri_variants.log: 13.9 ms
-// at 0, 19.3 at 1, 22.7 at 3; in the inode routine's column order 30.0 / 35.5 / 44.7)
-#define TRI_LOOKAHEAD 0
-#endif
-static_assert(TRI_LOOKAHEAD >= 0 && TRI_LOOKAHEAD <= 8, "TRI_LOOKAHEAD: 0..8 batches");
-static_assert(64 + 2 * TriSplitGeom<1>::HB + (TRI_LOOKAHEAD + 3) * TriSplitGeom<1>::SB <= TRI_SPLIT_LDS_BYTES &&
-              64 + 2 * TriSplitGeom<2>::HB + (TRI_LOOKAHEAD + 3) * TriSplitGeom<2>::SB <= TRI_SPLIT_LDS_BYTES &&
-              64 + 2 * TriSplitGeom<3>::HB + (TRI_LOOKAHEAD + 3) * TriSplitGeom<3>::SB <= TRI_SPLIT_LDS_BYTES &&
-              64 + 2 * TriSplitGeom<4>::HB + (TRI_LOOKAHEAD + 3) * TriSplitGeom<4>::SB <= TRI_SPLIT_LDS_BYTES &&
-              64 + 2 * TriSplitGeom<5>::HB + (TRI_LOOKAHEAD + 3) * TriSplitGeom<5>::SB <= TRI_SPLIT_LDS_BYTES,
-              "the smallest batch ring of the split-role kernels (look-ahead + 3 batches) must fit the LDS they ask for");
+static_assert(64 + 2 * TriSplitGeom<1>::HB + 3 * TriSplitGeom<1>::SB <= TRI_SPLIT_LDS_BYTES &&
+              64 + 2 * TriSplitGeom<2>::HB + 3 * TriSplitGeom<2>::SB <= TRI_SPLIT_LDS_BYTES &&
+              64 + 2 * TriSplitGeom<3>::HB + 3 * TriSplitGeom<3>::SB <= TRI_SPLIT_LDS_BYTES &&
+              64 + 2 * TriSplitGeom<4>::HB + 3 * TriSplitGeom<4>::SB <= TRI_SPLIT_LDS_BYTES &&
+              64 + 2 * TriSplitGeom<5>::HB + 3 * TriSplitGeom<5>::SB <= TRI_SPLIT_LDS_BYTES,
+              "the smallest batch ring of the split-role kernels (3 batches) must fit the LDS they ask for");
 // wait until the LDS counter reaches `need`; bounded like every other wait of these kernels: a wavefront that gives up raises the
 // abort flag and leaves, its partner's waits then run out the same way, and the application falls back to the level-by-level kernels
 __device__ __forceinline__ bool tri_lds_wait(volatile int *c, const int need, int *abort_flag) {
@@ -517,13 +518,10 @@ __device__ __forceinline__ void tri_split_loader(unsigned char *lds, const int l
   volatile int *ctl = (volatile int *)lds;
   int hp = 0, bp = 0;
   for (;;) {
-    unsigned int k = 0;
-    if (lane == 0) k = __hip_atomic_fetch_add(queue + q * TRI_QSTRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    k = (unsigned int)__builtin_amdgcn_readfirstlane((int)k);
-    long sl = (long)k * TRI_QUEUES + q;
+    const long sl = tri_next_slice(lane, queue, q);
     const int s = sl < nslices ? (int)sl : -1;
     if (!tri_lds_wait(ctl + 1, hp - 1, abort_flag)) return;
-    unsigned char *H = lds + 64 + (hp & 1) * G::HB;
+    unsigned char *H = G::header(lds, hp);
     int *Hm = (int *)H, *Hi = (int *)(H + 64);
     double *Hd = (double *)(H + 64 + 3 * 256);
     if (s < 0) {
@@ -535,25 +533,11 @@ __device__ __forceinline__ void tri_split_loader(unsigned char *lds, const int l
     const int t = s * MI355X_WAVE + lane;
     const int base = ptr[s], maxcol = (ptr[s + 1] - base) / MI355X_WAVE, ns = nsub[s];
     const int nbatch = ns == 1 ? (maxcol + B - 1) / B : 0;
-    if (!UPPER) {   // re-arm the other (upper) solve's slots of this position: its previous application is complete
-#pragma unroll
-      for (int kk = 0; kk < NB; ++kk) { const long i = (long)kk * np + t; if (i < reset_n) reset[i] = __longlong_as_double((long long)TRI_SENTINEL); }
-    }
+    if (!UPPER) tri_rearm_position<NB, false>(reset, t, np, reset_n);
     if (ns == 1) {
       const int inf = info[t], row0 = rowof[t], nsz = nszof[t];
       double sum[NB], dn[NT + NB];
-#pragma unroll
-      for (int kk = 0; kk < NB; ++kk) {
-        sum[kk] = 0.0;
-        if (row0 >= 0 && kk < nsz) {
-          if (UPPER) {
-            const int p = spos[row0 + nsz - 1 - kk];
-            sum[kk] = src[p];
-            if (rscale) sum[kk] = sum[kk] * rscale[t];
-            reset[p] = __longlong_as_double((long long)TRI_SENTINEL);
-          } else sum[kk] = src[row0 + kk];
-        }
-      }
+      tri_node_rhs<NB, UPPER, true>(sum, t, row0, row0 >= 0 ? nsz : 0, src, spos, rscale, reset);
 #pragma unroll
       for (int e = 0; e < NT + (UPPER ? NB : 0); ++e) dn[e] = din[(size_t)e * np + t];
       Hi[lane] = inf; Hi[64 + lane] = row0; Hi[128 + lane] = nsz;
@@ -571,35 +555,36 @@ __device__ __forceinline__ void tri_split_loader(unsigned char *lds, const int l
     const int *cbase = col + base + lane;
     const double *vbase = val + (size_t)base * NB + lane;
     int cA[B], cB[B]; double aA[B * NB], aB[B * NB];
-#define TRI_LD_BATCH(i, cX, aX)                                                                                          \
-  do {                                                                                                                   \
-    _Pragma("unroll") for (int j = 0; j < B; ++j) {                                                                      \
-      const int qq = (i) * B + j - pad;               /* the slot: batches are aligned to the END of the slice's slots */  \
-      cX[j] = qq >= 0 ? cbase[(size_t)qq * MI355X_WAVE] : 0;                                                             \
-      _Pragma("unroll") for (int kk = 0; kk < NB; ++kk) aX[j * NB + kk] = qq >= 0 ? vbase[(size_t)(qq * NB + kk) * MI355X_WAVE] : 0.0; \
-    }                                                                                                                    \
-  } while (0)
-#define TRI_PUT_BATCH(cX, aX)                                                                                            \
-  do {                                                                                                                   \
-    if (!tri_lds_wait(ctl + 3, bp - R + 1, abort_flag)) return;                                                          \
-    unsigned char *S = lds + 64 + 2 * G::HB + (size_t)(bp % R) * G::SB;                                                  \
-    int *Si = (int *)S; double *Sv = (double *)(S + B * 256);                                                            \
-    _Pragma("unroll") for (int j = 0; j < B; ++j) Si[j * 64 + lane] = cX[j];                                             \
-    _Pragma("unroll") for (int j = 0; j < B * NB; ++j) Sv[j * 64 + lane] = aX[j];                                        \
-    TRI_LDS_FENCE();                                                                                                     \
-    ctl[2] = ++bp;                                                                                                       \
-  } while (0)
-    TRI_LD_BATCH(0, cA, aA);
+    auto load = [&](const int i, int (&cX)[B], double (&aX)[B * NB]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int j = 0; j < B; ++j) {
+        const int qq = i * B + j - pad;               // the slot: batches are aligned to the END of the slice's slots
+        cX[j] = qq >= 0 ? cbase[(size_t)qq * MI355X_WAVE] : 0;
+#pragma unroll
+        for (int kk = 0; kk < NB; ++kk) aX[j * NB + kk] = qq >= 0 ? vbase[(size_t)(qq * NB + kk) * MI355X_WAVE] : 0.0;
+      }
+    };
+    auto put = [&](const int (&cX)[B], const double (&aX)[B * NB]) __attribute__((always_inline)) {   // false: the wait for a free stage was given up
+      if (!tri_lds_wait(ctl + 3, bp - R + 1, abort_flag)) return false;
+      unsigned char *S = G::stage(lds, bp, R);
+      int *Si = (int *)S; double *Sv = (double *)(S + B * 256);
+#pragma unroll
+      for (int j = 0; j < B; ++j) Si[j * 64 + lane] = cX[j];
+#pragma unroll
+      for (int j = 0; j < B * NB; ++j) Sv[j * 64 + lane] = aX[j];
+      TRI_LDS_FENCE();
+      ctl[2] = ++bp;
+      return true;
+    };
+    load(0, cA, aA);
     for (int i = 0; i < nbatch; i += 2) {
-      if (i + 1 < nbatch) TRI_LD_BATCH(i + 1, cB, aB);
-      TRI_PUT_BATCH(cA, aA);
+      if (i + 1 < nbatch) load(i + 1, cB, aB);
+      if (!put(cA, aA)) return;
       if (i + 1 < nbatch) {
-        if (i + 2 < nbatch) TRI_LD_BATCH(i + 2, cA, aA);
-        TRI_PUT_BATCH(cB, aB);
+        if (i + 2 < nbatch) load(i + 2, cA, aA);
+        if (!put(cB, aB)) return;
       }
     }
-#undef TRI_LD_BATCH
-#undef TRI_PUT_BATCH
   }
 }
 
@@ -608,14 +593,14 @@ __device__ __forceinline__ void tri_split_solver(unsigned char *lds, const int l
                                                  const int *__restrict__ info, const int *__restrict__ rowof, const unsigned char *__restrict__ nszof,
                                                  const int *__restrict__ col, const double *__restrict__ val, const double *__restrict__ din,
                                                  const double *src, const int *__restrict__ spos, double *w, double *y, double *reset,
-                                                 int *abort_flag, const int sleep_cap, const double *__restrict__ rscale, const int one_xcd) {
+                                                 int *abort_flag, const int sleep_cap, const double *__restrict__ rscale) {
   using G = TriSplitGeom<NB>;
   constexpr int B = G::B, NT = G::NT;
   volatile int *ctl = (volatile int *)lds;
   int hb = 0, bb = 0;
   for (;;) {
     if (!tri_lds_wait(ctl + 0, hb + 1, abort_flag)) return;
-    const unsigned char *H = lds + 64 + (hb & 1) * G::HB;
+    const unsigned char *H = G::header(lds, hb);
     const int *Hm = (const int *)H, *Hi = (const int *)(H + 64);
     const double *Hd = (const double *)(H + 64 + 3 * 256);
     const int s = Hm[0];
@@ -645,122 +630,44 @@ __device__ __forceinline__ void tri_split_solver(unsigned char *lds, const int l
     // this lane's column q sits in slot q + (width - ncol & ~1); batch i, entry j is slot i B + j - (nbatch B - width): the last
     // batch holds the newest dependencies of every lane
     const int shift = nbatch * B - width + ((width - ncol) & ~1);
-    int cA[B], cB[B]; double vA[B], vB[B];
-#if TRI_LOOKAHEAD == 3
-    int cC[B], cD[B]; double vC[B], vD[B];
-#endif
-#ifdef MI355X_TRI_TRACE
-#define TRI_SSTAMP(k) do { if (tri_trace_buf && lane == 0) tri_trace_buf[(UPPER ? 8000000L : 0L) + (long)s * 8 + (k)] = wall_clock64(); } while (0)
-#else
-#define TRI_SSTAMP(k) do { } while (0)
-#endif
-    TRI_SSTAMP(0);
-    // gathers of batch i: its indices out of LDS, one request per column of this lane
-#define TRI_GATHER(i, cX, vX)                                                                                            \
-  do {                                                                                                                   \
-    if (!tri_lds_wait(ctl + 2, bb + (i) + 1, abort_flag)) return;                                                        \
-    const int *Si = (const int *)(lds + 64 + 2 * G::HB + (size_t)((bb + (i)) % R) * G::SB);                              \
-    _Pragma("unroll") for (int j = 0; j < B; ++j) {                                                                      \
-      cX[j] = Si[j * 64 + lane];                                                                                         \
-      vX[j] = 0.0;                                                                                                       \
-      if ((i) * B + j >= shift && (i) * B + j - shift < ncol) vX[j] = __hip_atomic_load(w + cX[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          \
-    }                                                                                                                    \
-  } while (0)
-    // batch i into the sums, two columns at a time
-#define TRI_CONSUME(i, cX, vX)                                                                                           \
-  do {                                                                                                                   \
-    const double *Sv = (const double *)(lds + 64 + 2 * G::HB + (size_t)((bb + (i)) % R) * G::SB + B * 256);              \
-    const int q0 = (i) * B - shift;                                                                                              \
-    /* values that were not there yet: ALL of the batch's pending values are requested again together, round after round   \
-     * (one memory round trip per round, however many of them are pending; bounded as tri_poll is) */                      \
-    bool pend = false;                                                                                                   \
-    _Pragma("unroll") for (int j = 0; j < B; ++j) pend = pend || (q0 + j >= 0 && q0 + j < ncol && __double_as_longlong(vX[j]) == (long long)TRI_SENTINEL); \
-    for (int spins = 0; pend;) {                                                                                         \
-      { const int kz = spins < sleep_cap ? spins + 1 : sleep_cap;                                                        \
-        for (int z = 0; z < kz; ++z) __builtin_amdgcn_s_sleep(2); }                                                      \
-      if ((++spins & 255) == 0) {                                                                                        \
-        if (spins > TRI_SPIN_LIMIT || __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) {      \
-          __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);                                \
-          break;                                                                                                         \
-        }                                                                                                                \
-      }                                                                                                                  \
-      _Pragma("unroll") for (int j = 0; j < B; ++j)                                                                      \
-        if (q0 + j >= 0 && q0 + j < ncol && __double_as_longlong(vX[j]) == (long long)TRI_SENTINEL)                                     \
-          vX[j] = __hip_atomic_load(w + cX[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                              \
-      pend = false;                                                                                                      \
-      _Pragma("unroll") for (int j = 0; j < B; ++j) pend = pend || (q0 + j >= 0 && q0 + j < ncol && __double_as_longlong(vX[j]) == (long long)TRI_SENTINEL); \
-    }                                                                                                                    \
-    _Pragma("unroll") for (int j = 0; j < B; j += 2) {                                                                   \
-      if (q0 + j >= 0 && q0 + j + 1 < ncol) {                                                                                           \
-        if (NB == 1) { sum[0] -= Sv[j * 64 + lane] * vX[j]; sum[0] -= Sv[(j + 1) * 64 + lane] * vX[j + 1]; }                             \
-        else { _Pragma("unroll") for (int k = 0; k < NB; ++k) sum[k] -= Sv[(j * NB + k) * 64 + lane] * vX[j] + Sv[((j + 1) * NB + k) * 64 + lane] * vX[j + 1]; } \
-      } else if (q0 + j >= 0 && q0 + j < ncol) {                                                                                        \
-        _Pragma("unroll") for (int k = 0; k < NB; ++k) sum[k] -= Sv[(j * NB + k) * 64 + lane] * vX[j];                   \
-      }                                                                                                                  \
-    }                                                                                                                    \
-    TRI_LDS_FENCE();                                                                                                     \
-    ctl[3] = bb + (i) + 1;                                                                                               \
-    if ((i) < 5) TRI_SSTAMP(1 + (i));                                                                                    \
-  } while (0)
-#if TRI_LOOKAHEAD == 3
-    // the gathers run three batches ahead of the products: behind a wait for a dependency the following batches' values (older
-    // dependencies in column order) are then already in registers
-    if (nbatch > 0) TRI_GATHER(0, cA, vA);
-    if (nbatch > 1) TRI_GATHER(1, cB, vB);
-    if (nbatch > 2) TRI_GATHER(2, cC, vC);
-    for (int i = 0; i < nbatch; i += 4) {
-      if (i + 3 < nbatch) TRI_GATHER(i + 3, cD, vD);
-      TRI_CONSUME(i, cA, vA);
-      if (i + 1 < nbatch) { if (i + 4 < nbatch) TRI_GATHER(i + 4, cA, vA); TRI_CONSUME(i + 1, cB, vB); }
-      if (i + 2 < nbatch) { if (i + 5 < nbatch) TRI_GATHER(i + 5, cB, vB); TRI_CONSUME(i + 2, cC, vC); }
-      if (i + 3 < nbatch) { if (i + 6 < nbatch) TRI_GATHER(i + 6, cC, vC); TRI_CONSUME(i + 3, cD, vD); }
-    }
-#elif TRI_LOOKAHEAD == 0
-    for (int i = 0; i < nbatch; ++i) { TRI_GATHER(i, cA, vA); TRI_CONSUME(i, cA, vA); }
-#else
-    if (nbatch > 0) TRI_GATHER(0, cA, vA);
-    for (int i = 0; i < nbatch; i += 2) {
-      if (i + 1 < nbatch) TRI_GATHER(i + 1, cB, vB);
-      TRI_CONSUME(i, cA, vA);
-      if (i + 1 < nbatch) {
-        if (i + 2 < nbatch) TRI_GATHER(i + 2, cA, vA);
-        TRI_CONSUME(i + 1, cB, vB);
+    TRI_STAMP(true, s, 8, 0);
+    for (int i = 0; i < nbatch; ++i) {
+      // gathers of batch i: its indices out of LDS, one request per column of this lane
+      if (!tri_lds_wait(ctl + 2, bb + i + 1, abort_flag)) return;
+      const unsigned char *S = G::stage(lds, bb + i, R);
+      const int *Si = (const int *)S; const double *Sv = (const double *)(S + B * 256);
+      const int q0 = i * B - shift;
+      auto live = [&](const int j) __attribute__((always_inline)) { return q0 + j >= 0 && q0 + j < ncol; };
+      int c[B]; double v[B];
+#pragma unroll
+      for (int j = 0; j < B; ++j) {
+        c[j] = Si[j * 64 + lane];
+        v[j] = 0.0;
+        if (i * B + j >= shift && i * B + j - shift < ncol) v[j] = tri_peek(w + c[j]);      // (= live(j); written on the slot, live(j) here costs the 3-row upper kernel a stack frame)
       }
+      tri_poll_batch<B>(v, [&](const int j) __attribute__((always_inline)) { return w + c[j]; }, live, abort_flag, sleep_cap);
+      // batch i into the sums, two columns at a time
+#pragma unroll
+      for (int j = 0; j < B; j += 2) {
+        if (q0 + j >= 0 && q0 + j + 1 < ncol) {
+          if (NB == 1) { sum[0] -= Sv[j * 64 + lane] * v[j]; sum[0] -= Sv[(j + 1) * 64 + lane] * v[j + 1]; }
+          else {
+#pragma unroll
+            for (int k = 0; k < NB; ++k) sum[k] -= Sv[(j * NB + k) * 64 + lane] * v[j] + Sv[((j + 1) * NB + k) * 64 + lane] * v[j + 1];
+          }
+        } else if (live(j)) {
+#pragma unroll
+          for (int k = 0; k < NB; ++k) sum[k] -= Sv[(j * NB + k) * 64 + lane] * v[j];
+        }
+      }
+      TRI_LDS_FENCE();
+      ctl[3] = bb + i + 1;
+      if (i < 5) TRI_STAMP(true, s, 8, 1 + i);
     }
-#endif
-#undef TRI_GATHER
-#undef TRI_CONSUME
     bb += nbatch;
-    TRI_SSTAMP(6);
-    // the couplings inside the node (as tri_node_solve)
-    if (row0 < 0) {
-    } else if (!UPPER) {
-#pragma unroll
-      for (int k = 1; k < NB; ++k) {
-        if (k < nsz) {
-#pragma unroll
-          for (int l = 0; l < k; ++l) sum[k] -= dn[k * (k - 1) / 2 + l] * sum[l];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < NB; ++k)
-        if (k < nsz) tri_publish(w + (size_t)k * np + t, sum[k], one_xcd);
-    } else {
-      double xr[NB];
-#pragma unroll
-      for (int k = 0; k < NB; ++k) {
-        xr[k] = 0.0;
-        if (k < nsz) {
-#pragma unroll
-          for (int l = 0; l < k; ++l) sum[k] -= dn[k * (k - 1) / 2 + (k - 1 - l)] * xr[l];
-          xr[k] = sum[k] * dn[NT + k];
-          const int kk = nsz - 1 - k;
-          tri_publish(w + (size_t)kk * np + t, xr[k], one_xcd);
-          y[row0 + kk] = xr[k];
-        }
-      }
-    }
-    TRI_SSTAMP(7);
+    TRI_STAMP(true, s, 8, 6);
+    if (row0 >= 0) tri_node_finish<NB, UPPER, false, true>(sum, dn, t, np, row0, nsz, w, y);
+    TRI_STAMP(true, s, 8, 7);
   }
 }
 
@@ -774,12 +681,7 @@ __global__ __launch_bounds__(2 * MI355X_WAVE) void trisolve_node_split_kernel(
   extern __shared__ __align__(16) unsigned char tri_split_lds[];
   const int tid = threadIdx.x, lane = tid & (MI355X_WAVE - 1), wave = tid / MI355X_WAVE;
   if (tid < 16) ((int *)tri_split_lds)[tid] = 0;
-  if (blockIdx.x == 0 && tid < TRI_QUEUES) other_queue[tid * TRI_QSTRIDE] = 0u;
-  if (blockIdx.x == 0 && tid == 0) { other_queue[TRI_XCD_WORD] = 0xffffffffu; other_queue[TRI_XCD_WORD + 1] = 0u; }
-  if (!UPPER) {   // the upper solve's slots beyond this plan's own positions are re-armed here
-    for (long i = (long)NB * np + (long)blockIdx.x * blockDim.x + tid; i < reset_n; i += (long)gridDim.x * blockDim.x)
-      reset[i] = __longlong_as_double((long long)TRI_SENTINEL);
-  }
+  tri_prologue<UPPER, true>(other_queue, reset, (long)NB * np, reset_n, blockDim.x);
   __syncthreads();
   int q = blockIdx.x % TRI_QUEUES;
   if (one_xcd) {
@@ -802,7 +704,7 @@ __global__ __launch_bounds__(2 * MI355X_WAVE) void trisolve_node_split_kernel(
     q = me[1];
   }
   if (wave == 1) tri_split_loader<NB, UPPER>(tri_split_lds, lane, nslices, np, R, ptr, info, rowof, nszof, col, val, din, nsub, src, spos, reset, reset_n, queue, abort_flag, rscale, q);
-  else tri_split_solver<NB, UPPER>(tri_split_lds, lane, np, R, ptr, info, rowof, nszof, col, val, din, src, spos, w, y, reset, abort_flag, sleep_cap, rscale, one_xcd);
+  else tri_split_solver<NB, UPPER>(tri_split_lds, lane, np, R, ptr, info, rowof, nszof, col, val, din, src, spos, w, y, reset, abort_flag, sleep_cap, rscale);
 }
 
 template <int NB, bool UPPER, bool BLK>
@@ -846,8 +748,8 @@ __global__ __launch_bounds__(MI355X_BLOCK) void trisolve_level_kernel(int p0, in
   if (UPPER) y[row] = r;
 }
 
-// a host array that is not initialised on allocation (zeroed = true: zero pages from the allocator), and a loop over [0, n) dealt
-// to a few host threads in contiguous ranges (one thread below `grain` items per thread)
+// a host array that is not initialised on allocation (zeroed = true: zero pages from the allocator, first touched by the threads
+// that fill it), and a loop over [0, n) dealt to a few host threads in contiguous ranges (one thread below `grain` items per thread)
 template <class T> struct HostBuf {
   T *p; size_t n;
   explicit HostBuf(size_t n_, bool zeroed = false) : p((T *)(zeroed ? calloc(n_ ? n_ : 1, sizeof(T)) : malloc((n_ ? n_ : 1) * sizeof(T)))), n(n_) {}
@@ -869,43 +771,46 @@ __global__ __launch_bounds__(MI355X_BLOCK) void tri_arm_kernel(size_t n, double 
   for (size_t i = (size_t)blockIdx.x * MI355X_BLOCK + threadIdx.x; i < n; i += (size_t)gridDim.x * MI355X_BLOCK) w[i] = __longlong_as_double((long long)TRI_SENTINEL);
 }
 
-// What a row plan needs beside its sliced-ELL arrays (p->nslices, p->nchunks set): the solution vector armed with the sentinel,
-// the queue counters, the abort flag in pinned memory, the launch geometry.
-int trisolve_plan_finish(mi355x_handle_t h, mi355x_trisolve_plan_s *p, int nlev, int by_level) {
-  const size_t np = (size_t)p->nslices * MI355X_WAVE, npa = np > 0 ? np : 1;
-  MI355X_TRY(hipMalloc((void **)&p->d_w, sizeof(double) * npa));
-  hipLaunchKernelGGL(tri_arm_kernel, dim3(mi355x_grid_for(npa, 4)), dim3(MI355X_BLOCK), 0, h->stream, npa, p->d_w);
+// What a plan needs beside its layout arrays (p->nchunks set; node plans: p->split too): the nslots solution slots armed with the
+// sentinel, the queue counters, the abort flag in pinned memory, the launch geometry.
+int trisolve_plan_finish(mi355x_handle_t h, mi355x_trisolve_plan_s *p, size_t nslots, int nlev, tri_family family) {
+  MI355X_TRY(hipMalloc((void **)&p->d_w, sizeof(double) * nslots));
+  hipLaunchKernelGGL(tri_arm_kernel, dim3(mi355x_grid_for(nslots, 4)), dim3(MI355X_BLOCK), 0, h->stream, nslots, p->d_w);
   MI355X_LAUNCH_CHECK();
   MI355X_TRY(hipMalloc((void **)&p->d_queue, sizeof(unsigned int) * (TRI_QUEUES * TRI_QSTRIDE + 32)));
   MI355X_TRY(hipMemsetAsync(p->d_queue, 0, sizeof(unsigned int) * (TRI_QUEUES * TRI_QSTRIDE + 32), h->stream));
   MI355X_TRY(hipMemsetAsync(p->d_queue + TRI_XCD_WORD, 0xFF, sizeof(unsigned int), h->stream));
   MI355X_TRY(hipHostMalloc((void **)&p->abort_flag, 64, hipHostMallocMapped | hipHostMallocCoherent));
   *p->abort_flag = 0;
-  // fully resident grid: the occupancy the runtime reports, at most 4 workgroups per CU (MI355X_MICROARCH.md:
-  // the query can over-report by one; 4 of 256 threads is well inside what this kernel's registers admit)
-  int dev = 0, ncu = 256, per_cu = 0;
+  // fully resident grid.  Row plans: the occupancy the runtime reports, at most 4 workgroups per CU (MI355X_MICROARCH.md: the query
+  // can over-report by one; 4 of 256 threads is well inside what the row kernel's registers admit).  Node plans: register-heavy
+  // kernels (up to 254 VGPRs), one workgroup per CU is resident for every NB.
+  int dev = 0, per_cu = 1;
   hipDeviceProp_t prop;
   MI355X_TRY(hipGetDevice(&dev));
   MI355X_TRY(hipGetDeviceProperties(&prop, dev));
-  ncu = prop.multiProcessorCount;
-  MI355X_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trisolve_syncfree_kernel<true>, MI355X_BLOCK, 0));
-  p->by_level = by_level;
-  if (per_cu > 4) per_cu = 4;
-  if (per_cu < 1) return (int)hipErrorInvalidValue;
-  p->grid = ncu * per_cu;
+  if (family == TRI_ROWS) {
+    MI355X_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trisolve_syncfree_kernel<true>, MI355X_BLOCK, 0));
+    if (per_cu > 4) per_cu = 4;
+    if (per_cu < 1) return (int)hipErrorInvalidValue;
+  }
+  p->grid = prop.multiProcessorCount * per_cu;
   // ... and no larger than a few levels' worth of chunks: workgroups further ahead of the front could only spin
+  // (split-role kernels: profiles/r03_tri_variants.log, 21.9 ms at 4, 19.2 at 16, 19.1 at 64)
   { const char *e = getenv("MI355X_TRISOLVE_AHEAD");      // development knobs; the defaults are the measured best
-    const long ahead = e ? atol(e) : 4;
+    const long ahead = e ? atol(e) : (family == TRI_NODES && p->split ? 16 : 4);
     const long per_level = ((long)p->nchunks + nlev - 1) / (nlev > 0 ? nlev : 1);
     long g = ahead * per_level;
     if (g < TRI_QUEUES) g = TRI_QUEUES;
     if (g < p->grid) p->grid = (int)g; }
   if (p->grid > p->nchunks) p->grid = p->nchunks > 0 ? p->nchunks : 1;
   if (p->grid >= TRI_QUEUES) p->grid -= p->grid % TRI_QUEUES;    // every queue gets the same number of pullers
-  // poll back-off cap (x 128 clocks).  With a row's pending values polled together (one round trip per round) P7(256), 344
+  // poll back-off cap (x 128 clocks).  Row plans, a row's pending values polled together (one round trip per round): P7(256), 344
   // workgroups: cap 1 2.66 ms, 2 2.67, 4 2.76, 8 2.83 per application (polled one after the other: 8.1 ms at cap 2, 2.9 at cap 8:
-  // the polls flooded the L2); P7(128), 88 workgroups: cap 2 1.04 ms, cap 8 1.14
-  { const char *e = getenv("MI355X_TRISOLVE_SLEEP"); p->sleep_cap = e ? atoi(e) : 2; if (p->sleep_cap < 1) p->sleep_cap = 1; }
+  // the polls flooded the L2); P7(128), 88 workgroups: cap 2 1.04 ms, cap 8 1.14.  Node plans: 8 on grids of more than 128 workgroups.
+  { const char *e = getenv("MI355X_TRISOLVE_SLEEP");
+    p->sleep_cap = e ? atoi(e) : (family == TRI_NODES && p->grid > 128 ? 8 : 2);
+    if (p->sleep_cap < 1) p->sleep_cap = 1; }
   return 0;
 }
 
@@ -930,192 +835,198 @@ static int trisolve_plan_pair(MakeLo make_lo, MakeUp make_up, mi355x_trisolve_pl
   return 0;
 }
 
-extern "C" {
+// ---- host analysis: the steps the row plans and the node plans share ----
+// An ITEM is what a position holds: a row (row plans) or a node (node plans); its LIST the off-diagonal entries of the row, the
+// shared columns of the node.  Every failure of a builder leaves through TRI_TRY / TRI_FAIL (trisolve_plan.hpp): pending copies out
+// of the local arrays are drained first, and the caller hands the half-built plan to mi355x_trisolve_plan_destroy.
+#define TRI_UP(dst, vec, T) do { TRI_TRY(hipMalloc((void **)&(dst), sizeof(T) * (vec).size())); \
+    TRI_TRY(hipMemcpyAsync((dst), (vec).data(), sizeof(T) * (vec).size(), hipMemcpyHostToDevice, h->stream)); } while (0)
 
-// Host analysis + upload.  n rows; lev[i] = dependency level of row i (0-based, every level non-empty); len(i) and
-// the entries of row i come from (rp, cj, cv): row i's off-diagonal entries are cj/cv[rp[i] .. rp[i] + rl[i]).
-// dinv_host != NULL marks the upper solve (inverted diagonals per row).
-// by_level != 0: every row's entries are stored -- and therefore summed -- in the order of their dependencies' levels (oldest
-// first, column order among equals) instead of column order, and a level of TRI_ALIGN_MIN rows or more starts on a slice
-// boundary.  A row then waits only on its LAST entries, after everything older has been consumed, and a wavefront does not
-// hold rows of two large levels.  For factors of matrices with inodes (3-dof FEM: ~38 entries per row, recent dependencies
-// in the middle of the column order) the reference itself runs another routine with another order (MatSolve_SeqAIJ_Inode,
-// inode.c); results then agree with the natural-ordering loop to rounding, not bit for bit.  Deterministic either way.
-// every failure leaves through TRI_TRY / TRI_FAIL: pending copies out of the local vectors are drained first, and the caller
-// (trisolve_plan_create_impl) hands the half-built plan to mi355x_trisolve_plan_destroy
-#define TRI_TRY(expr) do { const int e__ = (int)(expr); if (e__) { (void)hipStreamSynchronize(h->stream); return e__; } } while (0)
-#define TRI_FAIL() do { (void)hipStreamSynchronize(h->stream); return (int)hipErrorInvalidValue; } while (0)
-static int trisolve_plan_fill(mi355x_handle_t h, mi355x_trisolve_plan_s *p, int n, int nlev, const int *lev, const int *rp, const int *rl, const int *cj,
-                              const double *cv, const double *dinv_host, const double *rscale_host, int by_level) {
-  p->n = n; p->upper = dinv_host != nullptr;
+// Positions: items by dependency level, longer lists first inside a level (stable in the item number); with `align` a level of
+// TRI_ALIGN_MIN items or more starts on a slice boundary (padding positions: no item, never read), so that a wavefront does not
+// hold items of two large levels.  order[t] = the t-th item, tpos[t] its position; p->nlev, p->levpos, p->nslices are set.
+// Refused: a level outside [0, nlev), a level without items, more than 2^31 slots (nb per position).
+struct TriLevelLayout { std::vector<int> order; std::vector<long> tpos; };
+static int tri_level_layout(mi355x_trisolve_plan_s *p, int nitems, int nlev, const int *lev, const int *len, bool align, int nb, TriLevelLayout &L) {
   const int W = MI355X_WAVE;
-  const bool timing = getenv("MI355X_TRISOLVE_TIMING") != nullptr, upper = dinv_host != nullptr;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double tlast = now();
-  auto tick = [&](const char *what) { if (timing) { const double t = now(); fprintf(stderr, "[mi355x trisolve plan %s] %-28s %.3f s\n", upper ? "U" : "L", what, t - tlast); tlast = t; } };
-  // positions: by level, longer rows first inside a level (stable in the row number)
-  std::vector<int> order((size_t)n), levptr((size_t)nlev + 1, 0);
-  for (int i = 0; i < n; ++i) levptr[(size_t)lev[i] + 1]++;
-  for (int l = 0; l < nlev; ++l) levptr[(size_t)l + 1] += levptr[(size_t)l];
+  std::vector<int> &order = L.order;
+  std::vector<int> levptr((size_t)nlev + 1, 0);
+  order.resize((size_t)nitems);
+  for (int i = 0; i < nitems; ++i) { if (lev[i] < 0 || lev[i] >= nlev) return (int)hipErrorInvalidValue; levptr[(size_t)lev[i] + 1]++; }
+  for (int l = 0; l < nlev; ++l) { if (levptr[(size_t)l + 1] < 1) return (int)hipErrorInvalidValue; levptr[(size_t)l + 1] += levptr[(size_t)l]; }
   { std::vector<int> next(levptr.begin(), levptr.end() - 1);
-    for (int i = 0; i < n; ++i) order[(size_t)next[(size_t)lev[i]]++] = i; }
-  // (longer rows first inside a level, stable in the row number: a counting sort over the row lengths when they are few -- the
-  // factors of a stencil operator have 0..3 entries per row -- instead of a comparison sort of 16.7 M rows)
+    for (int i = 0; i < nitems; ++i) order[(size_t)next[(size_t)lev[i]]++] = i; }
+  // (longer lists first: a counting sort over the lengths when they are few -- the factors of a stencil operator have 0..3
+  // entries per row -- instead of a comparison sort of 16.7 M rows)
   { int maxlen = 0;
-    for (int i = 0; i < n; ++i) if (rl[i] > maxlen) maxlen = rl[i];
+    for (int i = 0; i < nitems; ++i) if (len[i] > maxlen) maxlen = len[i];
     if (maxlen <= 4096) {
       std::vector<int> cnt((size_t)maxlen + 2), tmp;
       for (int l = 0; l < nlev; ++l) {
         const int a = levptr[(size_t)l], b = levptr[(size_t)l + 1];
         if (b - a < 2) continue;
         std::fill(cnt.begin(), cnt.end(), 0);
-        for (int t = a; t < b; ++t) cnt[(size_t)(maxlen - rl[order[(size_t)t]]) + 1]++;      // bucket 0 = the longest rows
+        for (int t = a; t < b; ++t) cnt[(size_t)(maxlen - len[order[(size_t)t]]) + 1]++;      // bucket 0 = the longest lists
         for (int q = 0; q <= maxlen; ++q) cnt[(size_t)q + 1] += cnt[(size_t)q];
         tmp.assign(order.begin() + a, order.begin() + b);
-        for (int t = 0; t < b - a; ++t) order[(size_t)a + (size_t)cnt[(size_t)(maxlen - rl[tmp[(size_t)t]])]++] = tmp[(size_t)t];
+        for (int t = 0; t < b - a; ++t) order[(size_t)a + (size_t)cnt[(size_t)(maxlen - len[tmp[(size_t)t]])]++] = tmp[(size_t)t];
       }
     } else {
       for (int l = 0; l < nlev; ++l)
-        std::stable_sort(order.begin() + levptr[(size_t)l], order.begin() + levptr[(size_t)l + 1], [&](int a, int b) { return rl[a] > rl[b]; });
+        std::stable_sort(order.begin() + levptr[(size_t)l], order.begin() + levptr[(size_t)l + 1], [&](int a, int b) { return len[a] > len[b]; });
     }
   }
-  tick("rows by level and length");
-  std::vector<long> tpos((size_t)(n > 0 ? n : 1));
+  L.tpos.resize((size_t)(nitems > 0 ? nitems : 1));
   long cur = 0;
   for (int l = 0; l < nlev; ++l) {
     const int sz = levptr[(size_t)l + 1] - levptr[(size_t)l];
-    if (by_level && sz >= TRI_ALIGN_MIN && (cur % W)) cur += W - cur % W;     // padding positions: no row, never read
-    for (int t = levptr[(size_t)l]; t < levptr[(size_t)l + 1]; ++t) tpos[(size_t)t] = cur++;
+    if (align && sz >= TRI_ALIGN_MIN && (cur % W)) cur += W - cur % W;
+    for (int t = levptr[(size_t)l]; t < levptr[(size_t)l + 1]; ++t) L.tpos[(size_t)t] = cur++;
   }
-  if (cur > 2147483000L) TRI_FAIL();
+  if (cur * nb > 2147483000L) return (int)hipErrorInvalidValue;
   p->nlev = nlev;
   p->levpos = (int *)malloc(sizeof(int) * 2 * (size_t)(nlev > 0 ? nlev : 1));
-  if (!p->levpos) TRI_FAIL();
+  if (!p->levpos) return (int)hipErrorInvalidValue;
   for (int l = 0; l < nlev; ++l) {
-    p->levpos[2 * l] = (int)tpos[(size_t)levptr[(size_t)l]];
-    p->levpos[2 * l + 1] = (int)tpos[(size_t)levptr[(size_t)l + 1] - 1] + 1;
+    p->levpos[2 * l] = (int)L.tpos[(size_t)levptr[(size_t)l]];
+    p->levpos[2 * l + 1] = (int)L.tpos[(size_t)levptr[(size_t)l + 1] - 1] + 1;
   }
   p->nslices = (int)((cur + W - 1) / W);
-  p->nchunks = (p->nslices + 3) / 4;
-  const size_t np = (size_t)p->nslices * W;
-  // (host arrays without an initialising pass of their own: every entry is written below, by several threads)
-  const size_t npa = np > 0 ? np : 1;
-  HostBuf<int> pos((size_t)(n > 0 ? n : 1)), info(npa), rowof(npa), ptr((size_t)p->nslices + 1), slicemax((size_t)(p->nslices > 0 ? p->nslices : 1));
-  HostBuf<unsigned char> nsub((size_t)(p->nslices > 0 ? p->nslices : 1));
-  HostBuf<double> dinv(npa), rsc(npa);
-  if (!pos.p || !info.p || !rowof.p || !ptr.p || !slicemax.p || !nsub.p || !dinv.p || !rsc.p) TRI_FAIL();
-  host_parallel_for((long)npa, 1 << 20, [&](long a, long b) { for (long P = a; P < b; ++P) { rowof[(size_t)P] = -1; info[(size_t)P] = 0; dinv[(size_t)P] = 1.0; rsc[(size_t)P] = 1.0; } });
-  host_parallel_for((long)n, 1 << 20, [&](long a, long b) { for (long t = a; t < b; ++t) { pos[(size_t)order[(size_t)t]] = (int)tpos[(size_t)t]; rowof[(size_t)tpos[(size_t)t]] = order[(size_t)t]; } });
-  tick("positions");
+  return 0;
+}
+
+// Per slice (item_at(P): the item at position P, -1 for padding): the positions' (list length << 8) | sub-step words -- a slice that
+// spans several levels walks them in sub-steps, at most 256 --, the sub-steps, the widest list (even: rounded up to pairs), and the
+// slice offsets ptr.  Returns the slots of all slices, -1: refused (sub-steps, more than 2^31 values at nb per slot).
+template <class ItemAt>
+static long tri_slice_layout(int nslices, ItemAt item_at, const int *lev, const int *len, bool even, int nb, int *info, unsigned char *nsub, int *ptr, int *widest) {
+  const int W = MI355X_WAVE;
   std::atomic<int> badslice(0);
-  host_parallel_for((long)p->nslices, 1 << 14, [&](long s0, long s1) {
+  host_parallel_for((long)nslices, 1 << 14, [&](long s0, long s1) {
     for (long s = s0; s < s1; ++s) {
       int mx = 0, l0 = -1, ns = 1;
       for (int j = 0; j < W; ++j) {
         const size_t P = (size_t)s * W + j;
-        const int i = rowof[P];
+        const int i = item_at(P);
         if (i < 0) continue;
-        if (l0 < 0) l0 = lev[i];                   // positions are in level order: the slice's first row has its lowest level
+        if (l0 < 0) l0 = lev[i];                   // positions are in level order: the slice's first item has its lowest level
         const int sub = lev[i] - l0;
         if (sub < 0 || sub > 255) { badslice.store(1); return; }
-        info[P] = (rl[i] << 8) | sub;
-        if (dinv_host) dinv[P] = dinv_host[i];
-        if (rscale_host) rsc[P] = rscale_host[i];
-        if (rl[i] > mx) mx = rl[i];
+        info[P] = (len[i] << 8) | sub;
+        if (len[i] > mx) mx = len[i];
         if (sub + 1 > ns) ns = sub + 1;
       }
-      slicemax[(size_t)s] = mx; nsub[(size_t)s] = (unsigned char)ns;
+      ptr[(size_t)s + 1] = even ? (mx + 1) & ~1 : mx;      // (the width; turned into the offset below)
+      nsub[(size_t)s] = (unsigned char)ns;
     }
   });
-  if (badslice.load()) TRI_FAIL();
+  if (badslice.load()) return -1;
   long total = 0;
-  for (int s = 0; s < p->nslices; ++s) {
+  *widest = 0;
+  for (int s = 0; s < nslices; ++s) {
+    const int mx = ptr[(size_t)s + 1];
+    if (mx > *widest) *widest = mx;
     ptr[(size_t)s] = (int)total;
-    total += (long)slicemax[(size_t)s] * W;
-    if (total > 2147483000L) TRI_FAIL();
+    total += (long)mx * W;
+    if (total * nb > 2147483000L) return -1;
   }
-  ptr[(size_t)p->nslices] = (int)total;
-  tick("slice layout");
-  // (zero pages from the allocator for the sliced ELL arrays, first touched by the fill threads)
+  ptr[(size_t)nslices] = (int)total;
+  return total;
+}
+
+// Every item writes its own slots of the layout arrays, host threads take contiguous ranges of positions (one thread below
+// `serial_below` items).  The list of item u is stored -- and therefore summed -- in the order perm: column order, or with by_level
+// its dependencies' levels, oldest first, column order among equals (dep_lev(u, q): the level of entry q's dependency).  A
+// dependency must come earlier (dep_pos(u, q): its position), or the plan is refused.  put(u, P, perm) writes item u at position P.
+template <class DepLev, class DepPos, class Put>
+static int tri_fill_lists(const TriLevelLayout &L, int nitems, int serial_below, const int *len, int by_level, DepLev dep_lev, DepPos dep_pos, Put put) {
+  std::atomic<int> bad(0);
+  auto fill = [&](int t0, int t1) {
+    std::vector<int> perm;
+    for (int t = t0; t < t1 && !bad.load(std::memory_order_relaxed); ++t) {
+      const int u = L.order[(size_t)t], P = (int)L.tpos[(size_t)t];
+      perm.resize((size_t)len[u]);
+      for (int q = 0; q < len[u]; ++q) perm[(size_t)q] = q;
+      if (by_level) std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return dep_lev(u, a) < dep_lev(u, b); });
+      for (int q = 0; q < len[u]; ++q) if (dep_pos(u, q) >= P) { bad.store(1); return; }
+      put(u, P, perm.data());
+    }
+  };
+  mi355x_parallel_ranges(nitems, nitems < serial_below ? 1 : mi355x_host_threads(8), fill);
+  return bad.load() ? (int)hipErrorInvalidValue : 0;
+}
+
+// ---- row plans: host analysis + upload ----
+// n rows; lev[i] = dependency level of row i (0-based, every level non-empty); len(i) and
+// the entries of row i come from (rp, cj, cv): row i's off-diagonal entries are cj/cv[rp[i] .. rp[i] + rl[i]).
+// dinv_host != NULL marks the upper solve (inverted diagonals per row).
+// by_level != 0: every row's entries are stored in the order of their dependencies' levels instead of column order, and large levels
+// start on a slice boundary (tri_fill_lists, tri_level_layout).  A row then waits only on its LAST entries, after everything older
+// has been consumed.  For factors of matrices with inodes (3-dof FEM: ~38 entries per row, recent dependencies
+// in the middle of the column order) the reference itself runs another routine with another order (MatSolve_SeqAIJ_Inode,
+// inode.c); results then agree with the natural-ordering loop to rounding, not bit for bit.  Deterministic either way.
+static int trisolve_plan_fill(mi355x_handle_t h, mi355x_trisolve_plan_s *p, int n, int nlev, const int *lev, const int *rp, const int *rl, const int *cj,
+                              const double *cv, const double *dinv_host, const double *rscale_host, int by_level) {
+  p->n = n; p->upper = dinv_host != nullptr; p->by_level = by_level;
+  const int W = MI355X_WAVE;
+  TriPlanTimer tm(p->upper);
+  TriLevelLayout L;
+  if (tri_level_layout(p, n, nlev, lev, rl, by_level != 0, 1, L)) TRI_FAIL();
+  const std::vector<int> &order = L.order; const std::vector<long> &tpos = L.tpos;
+  tm.tick("rows by level and length");
+  p->nchunks = (p->nslices + 3) / 4;
+  const size_t np = (size_t)p->nslices * W;
+  // (host arrays without an initialising pass of their own: every entry is written below, by several threads)
+  const size_t npa = np > 0 ? np : 1;
+  HostBuf<int> pos((size_t)(n > 0 ? n : 1)), info(npa), rowof(npa), ptr((size_t)p->nslices + 1);
+  HostBuf<unsigned char> nsub((size_t)(p->nslices > 0 ? p->nslices : 1));
+  HostBuf<double> dinv(npa), rsc(npa);
+  if (!pos.p || !info.p || !rowof.p || !ptr.p || !nsub.p || !dinv.p || !rsc.p) TRI_FAIL();
+  host_parallel_for((long)npa, 1 << 20, [&](long a, long b) { for (long P = a; P < b; ++P) { rowof[(size_t)P] = -1; info[(size_t)P] = 0; dinv[(size_t)P] = 1.0; rsc[(size_t)P] = 1.0; } });
+  host_parallel_for((long)n, 1 << 20, [&](long a, long b) {
+    for (long t = a; t < b; ++t) {
+      const int i = order[(size_t)t]; const size_t P = (size_t)tpos[(size_t)t];
+      pos[(size_t)i] = (int)P; rowof[P] = i;
+      if (dinv_host) dinv[P] = dinv_host[i];
+      if (rscale_host) rsc[P] = rscale_host[i];
+    }
+  });
+  tm.tick("positions");
+  int widest = 0;
+  const long total = tri_slice_layout(p->nslices, [&](size_t P) { return rowof[P]; }, lev, rl, false, 1, info.p, nsub.p, ptr.p, &widest);
+  if (total < 0) TRI_FAIL();
+  tm.tick("slice layout");
   const size_t ntot = (size_t)(total > 0 ? total : 1);
   HostBuf<int> col(ntot, true);
   HostBuf<double> val(ntot, true);
   if (!col.p || !val.p) TRI_FAIL();
-  tick("allocation");
-  // every row writes its own slots of the sliced ELL arrays: host threads take contiguous ranges of positions
-  { std::atomic<int> bad(0);
-    auto fill = [&](int t0, int t1) {
-      std::vector<int> perm;
-      for (int t = t0; t < t1 && !bad.load(std::memory_order_relaxed); ++t) {
-        const int i = order[(size_t)t], P = (int)tpos[(size_t)t], s = P / W, lane = P % W;
-        perm.resize((size_t)rl[i]);
-        for (int q = 0; q < rl[i]; ++q) perm[(size_t)q] = q;
-        if (by_level) std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return lev[cj[rp[i] + a]] < lev[cj[rp[i] + b]]; });
-        for (int q = 0; q < rl[i]; ++q) {
-          const int src_q = perm[(size_t)q];
-          const int dep = cj[rp[i] + src_q];
-          if (pos[(size_t)dep] >= P) { bad.store(1); break; }   // a dependency must come earlier
-          col[(size_t)ptr[(size_t)s] + (size_t)q * W + lane] = pos[(size_t)dep];
-          val[(size_t)ptr[(size_t)s] + (size_t)q * W + lane] = cv[rp[i] + src_q];
-        }
-      }
-    };
-    mi355x_parallel_ranges(n, n < 200000 ? 1 : mi355x_host_threads(8), fill);
-    if (bad.load()) TRI_FAIL(); }
-  tick("fill");
-#define TRI_UP(dst, vec, T) do { TRI_TRY(hipMalloc((void **)&(dst), sizeof(T) * (vec).size())); \
-    TRI_TRY(hipMemcpyAsync((dst), (vec).data(), sizeof(T) * (vec).size(), hipMemcpyHostToDevice, h->stream)); } while (0)
+  tm.tick("allocation");
+  if (tri_fill_lists(L, n, 200000, rl, by_level, [&](int i, int q) { return lev[cj[rp[i] + q]]; }, [&](int i, int q) { return pos[(size_t)cj[rp[i] + q]]; },
+                     [&](int i, int P, const int *perm) {
+                       const size_t at = (size_t)ptr[(size_t)(P / W)] + (size_t)(P % W);
+                       for (int q = 0; q < rl[i]; ++q) {
+                         col[at + (size_t)q * W] = pos[(size_t)cj[rp[i] + perm[q]]];
+                         val[at + (size_t)q * W] = cv[rp[i] + perm[q]];
+                       }
+                     })) TRI_FAIL();
+  tm.tick("fill");
   TRI_UP(p->d_ptr, ptr, int); TRI_UP(p->d_info, info, int); TRI_UP(p->d_row, rowof, int); TRI_UP(p->d_col, col, int);
   TRI_UP(p->d_val, val, double); TRI_UP(p->d_nsub, nsub, unsigned char); TRI_UP(p->d_pos, pos, int);
   if (dinv_host) TRI_UP(p->d_dinv, dinv, double);
   if (dinv_host && rscale_host) TRI_UP(p->d_rscale, rsc, double);
-#undef TRI_UP
   TRI_TRY(hipStreamSynchronize(h->stream));
-  tick("upload");
-  TRI_TRY(trisolve_plan_finish(h, p, nlev, by_level));
+  tm.tick("upload");
+  TRI_TRY(trisolve_plan_finish(h, p, npa, nlev, TRI_ROWS));
   TRI_TRY(hipStreamSynchronize(h->stream));
   return 0;
 }
-#undef TRI_TRY
-#undef TRI_FAIL
 
-static int trisolve_plan_fill_nodes(mi355x_handle_t h, mi355x_trisolve_plan_s *p, int n, int nnodes, const int *nstart_in, int nlev, const int *nodelev,
-                                    const int *rp, const int *rl, const int *cj, const double *cv, const double *dinv_host, int by_level, int blk,
-                                    const double *rscale_host, int singles);
-static int trisolve_plan_create_impl(mi355x_handle_t h, int n, int nlev, const int *lev, const int *rp, const int *rl, const int *cj,
-                                     const double *cv, const double *dinv_host, const double *rscale_host, int by_level,
-                                     mi355x_trisolve_plan_t *out, bool singles = false) {
-  *out = nullptr;
-  // Deep, narrow dependency graphs (the factor of an unstructured matrix: hundreds of rows per level, thousands of levels) are a
-  // chain of hand-offs: they run through the split-role kernels of the node plans with every row a node of its own (a loader and a
-  // solver wavefront per workgroup, lists end-aligned; same column order, one product after the other: the same bits).  Wide levels
-  // (a stencil operator: tens of thousands of rows per level) are throughput-bound and keep the one-wavefront-per-slice kernel.
-  // The choice is made for the two plans of a factor together (mi355x_trisolve_plan_create_pair).
-  // Row plans in column order are laid out ON THE DEVICE (trisolve_build.hip: the factor's arrays go up as they are, a radix sort
-  // orders the rows, kernels write the sliced-ELL arrays); MI355X_TRISOLVE_BUILD=host keeps the host threads' route, which also
-  // serves the orders the device route does not build (dependencies oldest first, node plans).  Same plan either way, bit for bit.
-  const char *bm = getenv("MI355X_TRISOLVE_BUILD");
-  const bool on_device = !singles && !by_level && n > 0 && !(bm && !strcmp(bm, "host"));
-  return mi355x_guard([&] {
-    tri_plan_ptr p(new mi355x_trisolve_plan_s(), mi355x_trisolve_plan_destroy);   // (zeroed) one cleanup path: nothing allocated so far survives a failure
-    const int rc = singles ? trisolve_plan_fill_nodes(h, p.get(), n, n, nullptr, nlev, lev, rp, rl, cj, cv, dinv_host, by_level, 0, rscale_host, 1)
-                   : on_device ? trisolve_plan_fill_device(h, p.get(), n, nlev, lev, rp, rl, cj, cv, dinv_host, rscale_host, by_level)
-                               : trisolve_plan_fill(h, p.get(), n, nlev, lev, rp, rl, cj, cv, dinv_host, rscale_host, by_level);
-    if (rc) return rc;
-    *out = p.release();
-    return 0;
-  });
-}
-
-
-// ---- node plans: host analysis ----
+// ---- node plans: host analysis + upload ----
 // n rows in nnodes nodes (nstart[u] .. nstart[u + 1] the rows of node u, sizes 1 .. 5); nodelev[u] its dependency level among the
 // nodes (every level non-empty).  Row-level factor as for the row plans: row i's off-diagonal entries cj/cv[rp[i] .. rp[i] + rl[i])
 // in the reference's stored order -- lower: the shared columns (those of the node's first row), then the node's own earlier rows;
 // upper: the node's own later rows, then the shared columns (those of the node's last row).  A factor whose rows do not have that
 // shape is refused (hipErrorInvalidValue): the caller keeps the row-granular plan.
-#define TRI_TRY(expr) do { const int e__ = (int)(expr); if (e__) { (void)hipStreamSynchronize(h->stream); return e__; } } while (0)
-#define TRI_FAIL() do { (void)hipStreamSynchronize(h->stream); return (int)hipErrorInvalidValue; } while (0)
 // singles != 0: every row is a node of its own (nstart may be NULL) -- the row-granular solves (MatSolve_SeqAIJ_NaturalOrdering, one
 // product after the other) through the same layout and kernels; rscale_host as in trisolve_plan_fill
 static int trisolve_plan_fill_nodes(mi355x_handle_t h, mi355x_trisolve_plan_s *p, int n, int nnodes, const int *nstart_in, int nlev, const int *nodelev,
@@ -1130,12 +1041,8 @@ static int trisolve_plan_fill_nodes(mi355x_handle_t h, mi355x_trisolve_plan_s *p
   const int *nstart = nstart_in ? nstart_in : nstart_own.data();
   const int W = MI355X_WAVE;
   const bool upper = dinv_host != nullptr;
-  // MI355X_TRISOLVE_TIMING: where the set-up time of a plan goes (stderr)
-  const bool timing = getenv("MI355X_TRISOLVE_TIMING") != nullptr;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double tlast = now();
-  auto tick = [&](const char *what) { if (timing) { const double t = now(); fprintf(stderr, "[mi355x trisolve plan %s] %-28s %.3f s\n", upper ? "U" : "L", what, t - tlast); tlast = t; } };
-  p->n = n; p->upper = upper; p->by_level = by_level; p->nlev = nlev;
+  TriPlanTimer tm(upper);
+  p->n = n; p->upper = upper; p->by_level = by_level;
   int NB = 1;
   for (int u = 0; u < nnodes; ++u) { const int z = nstart[u + 1] - nstart[u]; if (z < 1 || z > 5) TRI_FAIL(); if (z > NB) NB = z; }
   if (NB < 2 && !singles) TRI_FAIL();
@@ -1175,34 +1082,13 @@ static int trisolve_plan_fill_nodes(mi355x_handle_t h, mi355x_trisolve_plan_s *p
     };
     mi355x_parallel_ranges(nnodes, nnodes < 100000 ? 1 : mi355x_host_threads(8), check);
     if (bad.load()) TRI_FAIL(); }
-  tick("shape check");
-  // positions: nodes by level, more shared columns first inside a level (stable)
-  std::vector<int> order((size_t)nnodes), levptr((size_t)nlev + 1, 0);
-  for (int u = 0; u < nnodes; ++u) { if (nodelev[u] < 0 || nodelev[u] >= nlev) TRI_FAIL(); levptr[(size_t)nodelev[u] + 1]++; }
-  for (int l = 0; l < nlev; ++l) levptr[(size_t)l + 1] += levptr[(size_t)l];
-  { std::vector<int> next(levptr.begin(), levptr.end() - 1);
-    for (int u = 0; u < nnodes; ++u) order[(size_t)next[(size_t)nodelev[u]]++] = u; }
-  for (int l = 0; l < nlev; ++l)
-    std::stable_sort(order.begin() + levptr[(size_t)l], order.begin() + levptr[(size_t)l + 1], [&](int a, int b) { return nsh[(size_t)a] > nsh[(size_t)b]; });
-  std::vector<long> tpos((size_t)(nnodes > 0 ? nnodes : 1));
-  long cur = 0;
-  for (int l = 0; l < nlev; ++l) {
-    const int sz = levptr[(size_t)l + 1] - levptr[(size_t)l];
-    if (sz < 1) TRI_FAIL();
-    // a level of TRI_ALIGN_MIN nodes or more starts on a slice boundary, whatever the order of the columns inside the lists
-    // (positions do not enter the sums): such slices have no dependent sub-steps and take the batched path of the split-role kernels
-    if (sz >= TRI_ALIGN_MIN && (cur % W)) cur += W - cur % W;
-    for (int t = levptr[(size_t)l]; t < levptr[(size_t)l + 1]; ++t) tpos[(size_t)t] = cur++;
-  }
-  if (cur * NB > 2147483000L) TRI_FAIL();
-  tick("positions");
-  p->levpos = (int *)malloc(sizeof(int) * 2 * (size_t)(nlev > 0 ? nlev : 1));
-  if (!p->levpos) TRI_FAIL();
-  for (int l = 0; l < nlev; ++l) {
-    p->levpos[2 * l] = (int)tpos[(size_t)levptr[(size_t)l]];
-    p->levpos[2 * l + 1] = (int)tpos[(size_t)levptr[(size_t)l + 1] - 1] + 1;
-  }
-  p->nslices = (int)((cur + W - 1) / W);
+  tm.tick("shape check");
+  // positions: large levels always start on a slice boundary, whatever the order of the columns inside the lists (positions do not
+  // enter the sums): such slices have no dependent sub-steps and take the batched path of the split-role kernels
+  TriLevelLayout L;
+  if (tri_level_layout(p, nnodes, nlev, nodelev, nsh.data(), true, NB, L)) TRI_FAIL();
+  const std::vector<int> &order = L.order; const std::vector<long> &tpos = L.tpos;
+  tm.tick("positions");
   { const char *e = getenv("MI355X_TRISOLVE_NODE_WAVES"); p->spw = e ? atoi(e) : 4; if (p->spw != 1 && p->spw != 2 && p->spw != 4) p->spw = 4; }
   { const char *e = getenv("MI355X_TRISOLVE_SPLIT"); p->split = blk ? 0 : (e ? atoi(e) != 0 : 1); if (p->split) p->spw = 1; }
   // one-XCD form (trisolve_node_split_kernel): OFF unless MI355X_TRISOLVE_ONE_XCD=1 asks for it (development).  Its workgroups are
@@ -1223,115 +1109,86 @@ static int trisolve_plan_fill_nodes(mi355x_handle_t h, mi355x_trisolve_plan_s *p
     posn[(size_t)u] = (int)P; rowof[(size_t)P] = nstart[u]; nszv[(size_t)P] = (unsigned char)(nstart[u + 1] - nstart[u]);
     for (int r = nstart[u]; r < nstart[u + 1]; ++r) slot[(size_t)r] = blk ? (int)((size_t)P * NB + (size_t)(r - nstart[u])) : (int)((size_t)(r - nstart[u]) * np + (size_t)P);
   }
-  long total = 0;
-  for (int s = 0; s < p->nslices; ++s) {
-    int mx = 0, l0 = -1;
-    for (int j = 0; j < W; ++j) {
-      const size_t P = (size_t)s * W + j;
-      if (rowof[P] < 0) continue;
-      const int u = nodeof[(size_t)rowof[P]];
-      if (l0 < 0) l0 = nodelev[u];
-      const int sub = nodelev[u] - l0;
-      if (sub < 0 || sub > 255) TRI_FAIL();
-      info[P] = (nsh[(size_t)u] << 8) | sub;
-      if (nsh[(size_t)u] > mx) mx = nsh[(size_t)u];
-      if (sub + 1 > nsub[(size_t)s]) nsub[(size_t)s] = (unsigned char)(sub + 1);
-    }
-    // without block columns the slice is an even number of slots wide and every lane's list ENDS at the slice's last pair of slots
-    // (an even number of padding slots first: the pairs of the reference's summation stay pairs): the newest dependencies of all
-    // lanes then sit in the slice's last batch, whatever the lengths of their lists
-    if (!blk) mx = (mx + 1) & ~1;
-    ptr[(size_t)s] = (int)total;
-    total += (long)mx * W;
-    if (mx > p->maxcol) p->maxcol = mx;
-    if (total * NB > 2147483000L) TRI_FAIL();
-  }
-  ptr[(size_t)p->nslices] = (int)total;
+  // without block columns the slice is an even number of slots wide and every lane's list ENDS at the slice's last pair of slots
+  // (an even number of padding slots first: the pairs of the reference's summation stay pairs): the newest dependencies of all
+  // lanes then sit in the slice's last batch, whatever the lengths of their lists
+  const long total = tri_slice_layout(p->nslices, [&](size_t P) { return rowof[P] < 0 ? -1 : nodeof[(size_t)rowof[P]]; }, nodelev, nsh.data(), !blk, NB, info.data(),
+                                      nsub.data(), ptr.data(), &p->maxcol);
+  if (total < 0) TRI_FAIL();
   std::vector<int> col((size_t)(total > 0 ? total : 1) / (blk ? NB : 1) + 1, 0);     // blk: one entry per dependency node
-  // (zero pages from the allocator, first touched by the fill threads: a memset of the ~0.5 GB here cost 0.13 s)
-  const size_t nval = (size_t)(total > 0 ? total : 1) * NB;
-  std::unique_ptr<double, decltype(&free)> val_mem((double *)calloc(nval, sizeof(double)), &free);
-  if (!val_mem) TRI_FAIL();
-  double *val = val_mem.get();
-  tick("slice layout + allocation");
-  { std::atomic<int> bad(0);
-    auto fill = [&](int t0, int t1) {
-      std::vector<int> perm;
-      for (int t = t0; t < t1 && !bad.load(std::memory_order_relaxed); ++t) {
-        const int u = order[(size_t)t], P = (int)tpos[(size_t)t], s = P / W, lane = P % W;
-        const int r0 = nstart[u], z = nstart[u + 1] - r0, rL = r0 + z - 1, sh = nsh[(size_t)u];
-        const int *shared = upper ? cj + rp[rL] : cj + rp[r0];
-        const int off = blk ? 0 : ((ptr[(size_t)s + 1] - ptr[(size_t)s]) / W - sh) & ~1;
-        perm.resize((size_t)sh);
-        for (int q = 0; q < sh; ++q) perm[(size_t)q] = q;
-        // (stable, and the columns of one dependency node share a level: whole nodes stay together and in their own order)
-        if (by_level) std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return nodelev[nodeof[(size_t)shared[a]]] < nodelev[nodeof[(size_t)shared[b]]]; });
-        for (int q = 0; q < sh; ++q) {
-          const int sq = perm[(size_t)q], dep = shared[sq];
-          if (posn[(size_t)nodeof[(size_t)dep]] >= P) { bad.store(1); break; }        // a dependency must come earlier
-          if (blk) { if (q % NB == 0) col[(size_t)ptr[(size_t)s] / NB + (size_t)(q / NB) * W + lane] = posn[(size_t)nodeof[(size_t)dep]]; }
-          else col[(size_t)ptr[(size_t)s] + (size_t)(off + q) * W + lane] = slot[(size_t)dep];
-          for (int k = 0; k < z; ++k) {
-            const int r = upper ? rL - k : r0 + k;
-            val[(size_t)ptr[(size_t)s] * NB + ((size_t)(off + q) * NB + k) * W + lane] = cv[rp[r] + (upper ? k : 0) + sq];
-          }
-        }
-        for (int k = 0; k < z; ++k) {
-          const int r = upper ? rL - k : r0 + k;
-          for (int l = 0; l < k; ++l) din[(size_t)(k * (k - 1) / 2 + l) * np + P] = cv[rp[r] + (upper ? l : sh + l)];
-          if (upper) din[(size_t)(NT + k) * np + P] = dinv_host[r];
-        }
-      }
-    };
-    mi355x_parallel_ranges(nnodes, nnodes < 100000 ? 1 : mi355x_host_threads(8), fill);
-    if (bad.load()) TRI_FAIL(); }
-  tick("fill");
+  // (a memset of the ~0.5 GB of values here cost 0.13 s)
+  HostBuf<double> val((size_t)(total > 0 ? total : 1) * NB, true);
+  if (!val.p) TRI_FAIL();
+  tm.tick("slice layout + allocation");
+  if (tri_fill_lists(L, nnodes, 100000, nsh.data(), by_level,
+                     // (the columns of one dependency node share a level: whole nodes stay together and in their own order)
+                     [&](int u, int q) { return nodelev[nodeof[(size_t)cj[rp[upper ? nstart[u + 1] - 1 : nstart[u]] + q]]]; },
+                     [&](int u, int q) { return posn[(size_t)nodeof[(size_t)cj[rp[upper ? nstart[u + 1] - 1 : nstart[u]] + q]]]; },
+                     [&](int u, int P, const int *perm) {
+                       const int s = P / W, lane = P % W;
+                       const int r0 = nstart[u], z = nstart[u + 1] - r0, rL = r0 + z - 1, sh = nsh[(size_t)u];
+                       const int *shared = upper ? cj + rp[rL] : cj + rp[r0];
+                       const int off = blk ? 0 : ((ptr[(size_t)s + 1] - ptr[(size_t)s]) / W - sh) & ~1;
+                       for (int q = 0; q < sh; ++q) {
+                         const int sq = perm[q], dep = shared[sq];
+                         if (blk) { if (q % NB == 0) col[(size_t)ptr[(size_t)s] / NB + (size_t)(q / NB) * W + lane] = posn[(size_t)nodeof[(size_t)dep]]; }
+                         else col[(size_t)ptr[(size_t)s] + (size_t)(off + q) * W + lane] = slot[(size_t)dep];
+                         for (int k = 0; k < z; ++k) {
+                           const int r = upper ? rL - k : r0 + k;
+                           val[(size_t)ptr[(size_t)s] * NB + ((size_t)(off + q) * NB + k) * W + lane] = cv[rp[r] + (upper ? k : 0) + sq];
+                         }
+                       }
+                       for (int k = 0; k < z; ++k) {
+                         const int r = upper ? rL - k : r0 + k;
+                         for (int l = 0; l < k; ++l) din[(size_t)(k * (k - 1) / 2 + l) * np + P] = cv[rp[r] + (upper ? l : sh + l)];
+                         if (upper) din[(size_t)(NT + k) * np + P] = dinv_host[r];
+                       }
+                     })) TRI_FAIL();
+  tm.tick("fill");
   std::vector<double> rsc;        // (built before the copies out of the local vectors start: an exception must not leave them in flight)
   if (rscale_host && singles && upper) {
     rsc.assign(np > 0 ? np : 1, 1.0);
     for (size_t P = 0; P < np; ++P) if (rowof[P] >= 0) rsc[P] = rscale_host[rowof[P]];
   }
-#define TRI_UP(dst, vec, T) do { TRI_TRY(hipMalloc((void **)&(dst), sizeof(T) * (vec).size())); \
-    TRI_TRY(hipMemcpyAsync((dst), (vec).data(), sizeof(T) * (vec).size(), hipMemcpyHostToDevice, h->stream)); } while (0)
   TRI_UP(p->d_ptr, ptr, int); TRI_UP(p->d_info, info, int); TRI_UP(p->d_row, rowof, int); TRI_UP(p->d_col, col, int);
-  TRI_TRY(hipMalloc((void **)&p->d_val, sizeof(double) * nval));
-  TRI_TRY(hipMemcpyAsync(p->d_val, val, sizeof(double) * nval, hipMemcpyHostToDevice, h->stream));
-  TRI_UP(p->d_nsub, nsub, unsigned char); TRI_UP(p->d_pos, slot, int);
+  TRI_UP(p->d_val, val, double); TRI_UP(p->d_nsub, nsub, unsigned char); TRI_UP(p->d_pos, slot, int);
   TRI_UP(p->d_nsz, nszv, unsigned char); TRI_UP(p->d_din, din, double);
   if (!rsc.empty()) TRI_UP(p->d_rscale, rsc, double);
-#undef TRI_UP
-  const size_t nw = (np > 0 ? np : 1) * (size_t)NB;
   TRI_TRY(hipStreamSynchronize(h->stream));
-  tick("upload");
-  TRI_TRY(hipMalloc((void **)&p->d_w, sizeof(double) * nw));
-  { std::vector<unsigned long long> sent(nw, TRI_SENTINEL);
-    TRI_TRY(hipMemcpyAsync(p->d_w, sent.data(), sizeof(double) * sent.size(), hipMemcpyHostToDevice, h->stream));
-    TRI_TRY(hipStreamSynchronize(h->stream)); }
-  TRI_TRY(hipMalloc((void **)&p->d_queue, sizeof(unsigned int) * (TRI_QUEUES * TRI_QSTRIDE + 32)));
-  TRI_TRY(hipMemsetAsync(p->d_queue, 0, sizeof(unsigned int) * (TRI_QUEUES * TRI_QSTRIDE + 32), h->stream));
-  TRI_TRY(hipMemsetAsync(p->d_queue + TRI_XCD_WORD, 0xFF, sizeof(unsigned int), h->stream));
-  TRI_TRY(hipHostMalloc((void **)&p->abort_flag, 64, hipHostMallocMapped | hipHostMallocCoherent));
-  *p->abort_flag = 0;
-  int dev = 0;
-  hipDeviceProp_t prop;
-  TRI_TRY(hipGetDevice(&dev));
-  TRI_TRY(hipGetDeviceProperties(&prop, dev));
-  p->grid = prop.multiProcessorCount;                // register-heavy kernels (up to 254 VGPRs): one workgroup per CU is resident for every NB
-  { const char *e = getenv("MI355X_TRISOLVE_AHEAD");
-    const long ahead = e ? atol(e) : (p->split ? 16 : 4);      // (split-role kernels: profiles/r03_tri_variants.log, 21.9 ms at 4, 19.2 at 16, 19.1 at 64)
-    const long per_level = ((long)p->nchunks + nlev - 1) / (nlev > 0 ? nlev : 1);
-    long g = ahead * per_level;
-    if (g < TRI_QUEUES) g = TRI_QUEUES;
-    if (g < p->grid) p->grid = (int)g; }
-  if (p->grid > p->nchunks) p->grid = p->nchunks > 0 ? p->nchunks : 1;
-  if (p->grid >= TRI_QUEUES) p->grid -= p->grid % TRI_QUEUES;
-  { const char *e = getenv("MI355X_TRISOLVE_SLEEP"); p->sleep_cap = e ? atoi(e) : (p->grid <= 128 ? 2 : 8); if (p->sleep_cap < 1) p->sleep_cap = 1; }
+  tm.tick("upload");
+  TRI_TRY(trisolve_plan_finish(h, p, (np > 0 ? np : 1) * (size_t)NB, nlev, TRI_NODES));
   TRI_TRY(hipStreamSynchronize(h->stream));
-  tick("solution slots, queues");
+  tm.tick("solution slots, queues");
   return 0;
 }
-#undef TRI_TRY
-#undef TRI_FAIL
+#undef TRI_UP
+
+static int trisolve_plan_create_impl(mi355x_handle_t h, int n, int nlev, const int *lev, const int *rp, const int *rl, const int *cj,
+                                     const double *cv, const double *dinv_host, const double *rscale_host, int by_level,
+                                     mi355x_trisolve_plan_t *out, bool singles = false) {
+  *out = nullptr;
+  // Deep, narrow dependency graphs (the factor of an unstructured matrix: hundreds of rows per level, thousands of levels) are a
+  // chain of hand-offs: they run through the split-role kernels of the node plans with every row a node of its own (a loader and a
+  // solver wavefront per workgroup, lists end-aligned; same column order, one product after the other: the same bits).  Wide levels
+  // (a stencil operator: tens of thousands of rows per level) are throughput-bound and keep the one-wavefront-per-slice kernel.
+  // The choice is made for the two plans of a factor together (mi355x_trisolve_plan_create_pair).
+  // Row plans in column order are laid out ON THE DEVICE (trisolve_build.hip: the factor's arrays go up as they are, a radix sort
+  // orders the rows, kernels write the sliced-ELL arrays); MI355X_TRISOLVE_BUILD=host keeps the host threads' route, which also
+  // serves the orders the device route does not build (dependencies oldest first, node plans).  Same plan either way, bit for bit.
+  const char *bm = getenv("MI355X_TRISOLVE_BUILD");
+  const bool on_device = !singles && !by_level && n > 0 && !(bm && !strcmp(bm, "host"));
+  return mi355x_guard([&] {
+    tri_plan_ptr p(new mi355x_trisolve_plan_s(), mi355x_trisolve_plan_destroy);   // (zeroed) one cleanup path: nothing allocated so far survives a failure
+    const int rc = singles ? trisolve_plan_fill_nodes(h, p.get(), n, n, nullptr, nlev, lev, rp, rl, cj, cv, dinv_host, by_level, 0, rscale_host, 1)
+                   : on_device ? trisolve_plan_fill_device(h, p.get(), n, nlev, lev, rp, rl, cj, cv, dinv_host, rscale_host, by_level)
+                               : trisolve_plan_fill(h, p.get(), n, nlev, lev, rp, rl, cj, cv, dinv_host, rscale_host, by_level);
+    if (rc) return rc;
+    *out = p.release();
+    return 0;
+  });
+}
+
+extern "C" {
 
 int mi355x_trisolve_plan_create_nodes(mi355x_handle_t h, int n, int nnodes, const int *nstart, int nlev, const int *nodelev, const int *rp, const int *rl,
                                       const int *cj, const double *cv, const double *dinv_host, int by_level, int block_columns, mi355x_trisolve_plan_t *out) {
@@ -1376,14 +1233,28 @@ int mi355x_trisolve_plan_create_nodes_pair(mi355x_handle_t h, int n, int nnodes,
 
 }  // extern "C"
 
+// ---- launching ----
+// With fewer chunks than queues some queues have no puller: chunk c is then only served through queue c % 8 ... so tiny systems
+// use ONE workgroup per queue that exists (grid >= min(nchunks, 8) is guaranteed by trisolve_plan_finish)
+static int tri_grid(const mi355x_trisolve_plan_s *p) { return p->grid < TRI_QUEUES ? TRI_QUEUES : p->grid; }
+// one launch per dependency level of the plan: launch(grid, block, p0, p1) for the positions [p0, p1) of every level in turn
+template <class Launch> static int tri_by_level(const mi355x_trisolve_plan_s *p, Launch launch) {
+  for (int l = 0; l < p->nlev; ++l) {
+    const int p0 = p->levpos[2 * l], p1 = p->levpos[2 * l + 1];
+    launch(dim3((p1 - p0 + MI355X_BLOCK - 1) / MI355X_BLOCK), dim3(MI355X_BLOCK), p0, p1);
+    MI355X_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
 template <int NB, bool BLK>
 static int tri_node_go(mi355x_handle_t h, mi355x_trisolve_plan_t lo, mi355x_trisolve_plan_t up, const double *b, double *y, bool levels) {
+  const int glo = tri_grid(lo), gup = tri_grid(up);
   if (!levels && !BLK && lo->split && up->split) {
-    // split-role kernels: the LDS ring holds a whole slice's batches (and a spare one) where that fits
+    // split-role kernels: the LDS ring holds a whole slice's batches (and a spare one) where that fits, 3 batches at least
     using G = TriSplitGeom<NB>;
-    const int glo = lo->grid < TRI_QUEUES ? TRI_QUEUES : lo->grid, gup = up->grid < TRI_QUEUES ? TRI_QUEUES : up->grid;
     const int rmax = (int)((TRI_SPLIT_LDS_BYTES - 64 - 2 * G::HB) / G::SB);
-    auto ring = [&](int maxcol) { int r = (maxcol + G::B - 1) / G::B + 1; if (r < TRI_LOOKAHEAD + 3) r = TRI_LOOKAHEAD + 3; if (r > rmax) r = rmax; return r; };
+    auto ring = [&](int maxcol) { int r = (maxcol + G::B - 1) / G::B + 1; if (r < 3) r = 3; if (r > rmax) r = rmax; return r; };
     const int rlo = ring(lo->maxcol), rup = ring(up->maxcol);
     const size_t blo = 64 + 2 * (size_t)G::HB + (size_t)rlo * G::SB, bup = 64 + 2 * (size_t)G::HB + (size_t)rup * G::SB;
     static int attr_dev = -2;         // the device the attribute was set on (per NB: this function is a template); -1: it refused
@@ -1413,7 +1284,6 @@ static int tri_node_go(mi355x_handle_t h, mi355x_trisolve_plan_t lo, mi355x_tris
     return 0;
   }
   if (!levels) {
-    const int glo = lo->grid < TRI_QUEUES ? TRI_QUEUES : lo->grid, gup = up->grid < TRI_QUEUES ? TRI_QUEUES : up->grid;
     hipLaunchKernelGGL((trisolve_node_kernel<NB, false, BLK>), dim3(glo), dim3(lo->spw * MI355X_WAVE), 0, h->stream, lo->nslices, lo->nchunks, lo->np, lo->d_ptr, lo->d_info,
                        lo->d_row, lo->d_nsz, lo->d_col, lo->d_val, lo->d_din, lo->d_nsub, b, (const int *)nullptr, lo->d_w, (double *)nullptr, up->d_w,
                        up->np * NB, lo->d_queue, up->d_queue, lo->abort_flag, lo->sleep_cap, (const double *)nullptr);
@@ -1424,19 +1294,15 @@ static int tri_node_go(mi355x_handle_t h, mi355x_trisolve_plan_t lo, mi355x_tris
     MI355X_LAUNCH_CHECK();
     return 0;
   }
-  for (int l = 0; l < lo->nlev; ++l) {
-    const int p0 = lo->levpos[2 * l], p1 = lo->levpos[2 * l + 1];
-    hipLaunchKernelGGL((trisolve_node_level_kernel<NB, false, BLK>), dim3((p1 - p0 + MI355X_BLOCK - 1) / MI355X_BLOCK), dim3(MI355X_BLOCK), 0, h->stream, p0, p1, lo->np,
+  const int rc = tri_by_level(lo, [&](dim3 grid, dim3 block, int p0, int p1) {
+    hipLaunchKernelGGL((trisolve_node_level_kernel<NB, false, BLK>), grid, block, 0, h->stream, p0, p1, lo->np,
                        lo->d_ptr, lo->d_info, lo->d_row, lo->d_nsz, lo->d_col, lo->d_val, lo->d_din, b, (const int *)nullptr, lo->d_w, (double *)nullptr, (const double *)nullptr);
-    MI355X_LAUNCH_CHECK();
-  }
-  for (int l = 0; l < up->nlev; ++l) {
-    const int p0 = up->levpos[2 * l], p1 = up->levpos[2 * l + 1];
-    hipLaunchKernelGGL((trisolve_node_level_kernel<NB, true, BLK>), dim3((p1 - p0 + MI355X_BLOCK - 1) / MI355X_BLOCK), dim3(MI355X_BLOCK), 0, h->stream, p0, p1, up->np,
+  });
+  if (rc) return rc;
+  return tri_by_level(up, [&](dim3 grid, dim3 block, int p0, int p1) {
+    hipLaunchKernelGGL((trisolve_node_level_kernel<NB, true, BLK>), grid, block, 0, h->stream, p0, p1, up->np,
                        up->d_ptr, up->d_info, up->d_row, up->d_nsz, up->d_col, up->d_val, up->d_din, lo->d_w, lo->d_pos, up->d_w, y, (const double *)up->d_rscale);
-    MI355X_LAUNCH_CHECK();
-  }
-  return 0;
+  });
 }
 static int tri_node_dispatch(mi355x_handle_t h, mi355x_trisolve_plan_t lo, mi355x_trisolve_plan_t up, const double *b, double *y, bool levels) {
   if (lo->nb != up->nb || lo->blkcols != up->blkcols) return (int)hipErrorInvalidValue;
@@ -1482,11 +1348,8 @@ int mi355x_trisolve_plan_destroy(mi355x_trisolve_plan_t p) {
   if (!p) return 0;
   (void)hipFree(p->d_ptr); (void)hipFree(p->d_info); (void)hipFree(p->d_row); (void)hipFree(p->d_col); (void)hipFree(p->d_val);
   (void)hipFree(p->d_nsub); (void)hipFree(p->d_pos); (void)hipFree(p->d_w); (void)hipFree(p->d_queue);
-  if (p->d_dinv) (void)hipFree(p->d_dinv);
-  if (p->d_rscale) (void)hipFree(p->d_rscale);
-  if (p->d_nsz) (void)hipFree(p->d_nsz);
-  if (p->d_din) (void)hipFree(p->d_din);
-  if (p->abort_flag) (void)hipHostFree(p->abort_flag);
+  (void)hipFree(p->d_dinv); (void)hipFree(p->d_rscale); (void)hipFree(p->d_nsz); (void)hipFree(p->d_din);
+  (void)hipHostFree(p->abort_flag);
   free(p->levpos);
   delete p;
   return 0;
@@ -1499,24 +1362,16 @@ int mi355x_trisolve_apply(mi355x_handle_t h, mi355x_trisolve_plan_t lo, mi355x_t
   if (*lo->abort_flag || *up->abort_flag) return (int)hipErrorLaunchFailure;
   if (lo->n == 0) return 0;
   if (lo->nb >= 1 || up->nb >= 1) return tri_node_dispatch(h, lo, up, b, y, false);
-  // with fewer chunks than queues some queues have no puller: chunk c is then only served through queue c % 8 ...
-  // so tiny systems use ONE workgroup per queue that exists (grid >= min(nchunks, 8) is guaranteed by plan_create)
-  const int glo = lo->grid < TRI_QUEUES ? TRI_QUEUES : lo->grid, gup = up->grid < TRI_QUEUES ? TRI_QUEUES : up->grid;
-#define TRI_GO()                                                                                                                 \
-  do {                                                                                                                            \
-    hipLaunchKernelGGL((trisolve_syncfree_kernel<false>), dim3(glo), dim3(MI355X_BLOCK), 0, h->stream, lo->nslices, lo->nchunks, \
-                       lo->d_ptr, lo->d_info, lo->d_row, lo->d_col, lo->d_val, (const double *)nullptr, lo->d_nsub, b,          \
-                       (const int *)nullptr, lo->d_w, (double *)nullptr, up->d_w, up->nslices * MI355X_WAVE, lo->d_queue, up->d_queue, lo->abort_flag, lo->sleep_cap, \
-                       (const double *)nullptr); \
-    MI355X_LAUNCH_CHECK();                                                                                                        \
-    hipLaunchKernelGGL((trisolve_syncfree_kernel<true>), dim3(gup), dim3(MI355X_BLOCK), 0, h->stream, up->nslices, up->nchunks,  \
-                       up->d_ptr, up->d_info, up->d_row, up->d_col, up->d_val, up->d_dinv, up->d_nsub, lo->d_w, lo->d_pos,       \
-                       up->d_w, y, lo->d_w, 0, up->d_queue, lo->d_queue, up->abort_flag, up->sleep_cap, (const double *)up->d_rscale); \
-    MI355X_LAUNCH_CHECK();                                                                                                        \
-  } while (0)
   if (lo->by_level != up->by_level) return (int)hipErrorInvalidValue;
-  TRI_GO();
-#undef TRI_GO
+  hipLaunchKernelGGL((trisolve_syncfree_kernel<false>), dim3(tri_grid(lo)), dim3(MI355X_BLOCK), 0, h->stream, lo->nslices, lo->nchunks,
+                     lo->d_ptr, lo->d_info, lo->d_row, lo->d_col, lo->d_val, (const double *)nullptr, lo->d_nsub, b,
+                     (const int *)nullptr, lo->d_w, (double *)nullptr, up->d_w, up->nslices * MI355X_WAVE, lo->d_queue, up->d_queue, lo->abort_flag, lo->sleep_cap,
+                     (const double *)nullptr);
+  MI355X_LAUNCH_CHECK();
+  hipLaunchKernelGGL((trisolve_syncfree_kernel<true>), dim3(tri_grid(up)), dim3(MI355X_BLOCK), 0, h->stream, up->nslices, up->nchunks,
+                     up->d_ptr, up->d_info, up->d_row, up->d_col, up->d_val, up->d_dinv, up->d_nsub, lo->d_w, lo->d_pos,
+                     up->d_w, y, lo->d_w, 0, up->d_queue, lo->d_queue, up->abort_flag, up->sleep_cap, (const double *)up->d_rscale);
+  MI355X_LAUNCH_CHECK();
   return 0;
 }
 
@@ -1526,21 +1381,17 @@ int mi355x_trisolve_apply_levels(mi355x_handle_t h, mi355x_trisolve_plan_t lo, m
   if (!lo || !up || lo->n != up->n || lo->upper || !up->upper) return (int)hipErrorInvalidValue;
   if (lo->n == 0) return 0;
   if (lo->nb >= 1 || up->nb >= 1) return tri_node_dispatch(h, lo, up, b, y, true);
-  for (int l = 0; l < lo->nlev; ++l) {
-    const int p0 = lo->levpos[2 * l], p1 = lo->levpos[2 * l + 1];
-    hipLaunchKernelGGL((trisolve_level_kernel<false>), dim3((p1 - p0 + MI355X_BLOCK - 1) / MI355X_BLOCK), dim3(MI355X_BLOCK), 0, h->stream, p0, p1,
+  const int rc = tri_by_level(lo, [&](dim3 grid, dim3 block, int p0, int p1) {
+    hipLaunchKernelGGL((trisolve_level_kernel<false>), grid, block, 0, h->stream, p0, p1,
                        lo->d_ptr, lo->d_info, lo->d_row, lo->d_col, lo->d_val, (const double *)nullptr, b, (const int *)nullptr, lo->d_w,
                        (double *)nullptr, (const double *)nullptr);
-    MI355X_LAUNCH_CHECK();
-  }
-  for (int l = 0; l < up->nlev; ++l) {
-    const int p0 = up->levpos[2 * l], p1 = up->levpos[2 * l + 1];
-    hipLaunchKernelGGL((trisolve_level_kernel<true>), dim3((p1 - p0 + MI355X_BLOCK - 1) / MI355X_BLOCK), dim3(MI355X_BLOCK), 0, h->stream, p0, p1,
+  });
+  if (rc) return rc;
+  return tri_by_level(up, [&](dim3 grid, dim3 block, int p0, int p1) {
+    hipLaunchKernelGGL((trisolve_level_kernel<true>), grid, block, 0, h->stream, p0, p1,
                        up->d_ptr, up->d_info, up->d_row, up->d_col, up->d_val, up->d_dinv, lo->d_w, lo->d_pos, up->d_w, y,
                        (const double *)up->d_rscale);
-    MI355X_LAUNCH_CHECK();
-  }
-  return 0;
+  });
 }
 
 // tests: one array of a ROW plan back on the host.  which: 0 slice offsets (nslices + 1 ints), 1 (length, sub-step) words, 2 position -> row,

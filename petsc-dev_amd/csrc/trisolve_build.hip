@@ -15,7 +15,6 @@
 // Column order only: the by-level entry order and the node plans stay with the host route.
 #include "trisolve_plan.hpp"
 #include <hipcub/hipcub.hpp>
-#include <chrono>
 #include <vector>
 #include <stdio.h>
 #include <stdlib.h>
@@ -143,79 +142,75 @@ struct DevTmp {                       // temporaries of one construction, releas
 
 }  // namespace
 
-#define B_TRY(expr) do { const int e__ = (int)(expr); if (e__) { (void)hipStreamSynchronize(st); return e__; } } while (0)
-#define B_FAIL() do { (void)hipStreamSynchronize(st); return (int)hipErrorInvalidValue; } while (0)
 #define B_GRID(cnt) dim3(mi355x_grid_for((size_t)(cnt), 4)), dim3(MI355X_BLOCK), 0, st
 
 int trisolve_plan_fill_device(mi355x_handle_t h, mi355x_trisolve_plan_s *p, int n, int nlev, const int *lev, const int *rp, const int *rl, const int *cj,
                               const double *cv, const double *dinv_host, const double *rscale_host, int by_level) {
   hipStream_t st = h->stream;
   const int W = MI355X_WAVE;
-  const bool timing = getenv("MI355X_TRISOLVE_TIMING") != nullptr, upper = dinv_host != nullptr;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double tlast = now();
-  auto tick = [&](const char *what) { if (timing) { (void)hipStreamSynchronize(st); const double t = now(); fprintf(stderr, "[mi355x trisolve plan %s, device] %-22s %.3f s\n", upper ? "U" : "L", what, t - tlast); tlast = t; } };
+  const bool upper = dinv_host != nullptr;
+  TriPlanTimer tm(upper, true, st);
   if (by_level || n <= 0 || nlev <= 0) return (int)hipErrorInvalidValue;
   p->n = n; p->upper = upper; p->nlev = nlev;
   DevTmp tmp;
   int *d_lev, *d_rp, *d_rl, *d_ext;
   double *d_dinvrow = nullptr, *d_rscrow = nullptr;
-  B_TRY(tmp.get(&d_lev, (size_t)n)); B_TRY(tmp.get(&d_rp, (size_t)n)); B_TRY(tmp.get(&d_rl, (size_t)n)); B_TRY(tmp.get(&d_ext, 4));
-  B_TRY(hipMemcpyAsync(d_lev, lev, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
-  B_TRY(hipMemcpyAsync(d_rp, rp, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
-  B_TRY(hipMemcpyAsync(d_rl, rl, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
-  if (dinv_host) { B_TRY(tmp.get(&d_dinvrow, (size_t)n)); B_TRY(hipMemcpyAsync(d_dinvrow, dinv_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st)); }
-  if (dinv_host && rscale_host) { B_TRY(tmp.get(&d_rscrow, (size_t)n)); B_TRY(hipMemcpyAsync(d_rscrow, rscale_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st)); }
+  TRI_TRY(tmp.get(&d_lev, (size_t)n)); TRI_TRY(tmp.get(&d_rp, (size_t)n)); TRI_TRY(tmp.get(&d_rl, (size_t)n)); TRI_TRY(tmp.get(&d_ext, 4));
+  TRI_TRY(hipMemcpyAsync(d_lev, lev, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
+  TRI_TRY(hipMemcpyAsync(d_rp, rp, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
+  TRI_TRY(hipMemcpyAsync(d_rl, rl, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
+  if (dinv_host) { TRI_TRY(tmp.get(&d_dinvrow, (size_t)n)); TRI_TRY(hipMemcpyAsync(d_dinvrow, dinv_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st)); }
+  if (dinv_host && rscale_host) { TRI_TRY(tmp.get(&d_rscrow, (size_t)n)); TRI_TRY(hipMemcpyAsync(d_rscrow, rscale_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st)); }
   int ext[4] = {0, 0, 0x7fffffff, 0};
-  B_TRY(hipMemcpyAsync(d_ext, ext, sizeof(ext), hipMemcpyHostToDevice, st));
+  TRI_TRY(hipMemcpyAsync(d_ext, ext, sizeof(ext), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(tri_extent_kernel, B_GRID(n), n, nlev, d_lev, d_rp, d_rl, d_ext);
-  B_TRY(hipGetLastError());
-  B_TRY(hipMemcpyAsync(ext, d_ext, sizeof(ext), hipMemcpyDeviceToHost, st));
-  B_TRY(hipStreamSynchronize(st));
-  if (ext[3]) B_FAIL();
+  TRI_TRY(hipGetLastError());
+  TRI_TRY(hipMemcpyAsync(ext, d_ext, sizeof(ext), hipMemcpyDeviceToHost, st));
+  TRI_TRY(hipStreamSynchronize(st));
+  if (ext[3]) TRI_FAIL();
   const int maxlen = ext[0], ext_hi = ext[1], ext_lo = ext[1] > 0 ? ext[2] : 0;
-  tick("row arrays up, extents");
+  tm.tick("row arrays up, extents");
   // the entries the rows name: one contiguous range of the host's column / value arrays
   const size_t nent = ext_hi > ext_lo ? (size_t)(ext_hi - ext_lo) : 0;
   int *d_cj; double *d_cv;
-  B_TRY(tmp.get(&d_cj, nent)); B_TRY(tmp.get(&d_cv, nent));
+  TRI_TRY(tmp.get(&d_cj, nent)); TRI_TRY(tmp.get(&d_cv, nent));
   if (nent) {
-    B_TRY(hipMemcpyAsync(d_cj, cj + ext_lo, sizeof(int) * nent, hipMemcpyHostToDevice, st));
-    B_TRY(hipMemcpyAsync(d_cv, cv + ext_lo, sizeof(double) * nent, hipMemcpyHostToDevice, st));
+    TRI_TRY(hipMemcpyAsync(d_cj, cj + ext_lo, sizeof(int) * nent, hipMemcpyHostToDevice, st));
+    TRI_TRY(hipMemcpyAsync(d_cv, cv + ext_lo, sizeof(double) * nent, hipMemcpyHostToDevice, st));
   }
-  tick("factor entries up");
+  tm.tick("factor entries up");
   // 1. rows by (level, longer first), stable in the row number
   unsigned long long *d_k0, *d_k1; int *d_r0, *d_order;
-  B_TRY(tmp.get(&d_k0, (size_t)n)); B_TRY(tmp.get(&d_k1, (size_t)n)); B_TRY(tmp.get(&d_r0, (size_t)n)); B_TRY(tmp.get(&d_order, (size_t)n));
+  TRI_TRY(tmp.get(&d_k0, (size_t)n)); TRI_TRY(tmp.get(&d_k1, (size_t)n)); TRI_TRY(tmp.get(&d_r0, (size_t)n)); TRI_TRY(tmp.get(&d_order, (size_t)n));
   hipLaunchKernelGGL(tri_keys_kernel, B_GRID(n), n, maxlen, d_lev, d_rl, d_k0, d_r0);
-  B_TRY(hipGetLastError());
+  TRI_TRY(hipGetLastError());
   { int bits = 1;
     const unsigned long long top = (unsigned long long)nlev * (unsigned long long)(maxlen + 1);
     while (bits < 64 && (top >> bits)) ++bits;
     size_t tb = 0;
-    B_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, d_k0, d_k1, d_r0, d_order, n, 0, bits, st));
-    unsigned char *d_t; B_TRY(tmp.get(&d_t, tb));
-    B_TRY(hipcub::DeviceRadixSort::SortPairs(d_t, tb, d_k0, d_k1, d_r0, d_order, n, 0, bits, st)); }
+    TRI_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, d_k0, d_k1, d_r0, d_order, n, 0, bits, st));
+    unsigned char *d_t; TRI_TRY(tmp.get(&d_t, tb));
+    TRI_TRY(hipcub::DeviceRadixSort::SortPairs(d_t, tb, d_k0, d_k1, d_r0, d_order, n, 0, bits, st)); }
   // 2. level boundaries; the first position of every level
   int *d_levptr, *d_levbase;
-  B_TRY(tmp.get(&d_levptr, (size_t)nlev)); B_TRY(tmp.get(&d_levbase, (size_t)nlev));
-  B_TRY(hipMemsetAsync(d_levptr, 0xFF, sizeof(int) * (size_t)nlev, st));
+  TRI_TRY(tmp.get(&d_levptr, (size_t)nlev)); TRI_TRY(tmp.get(&d_levbase, (size_t)nlev));
+  TRI_TRY(hipMemsetAsync(d_levptr, 0xFF, sizeof(int) * (size_t)nlev, st));
   hipLaunchKernelGGL(tri_levptr_kernel, B_GRID(n), n, d_order, d_lev, d_levptr);
-  B_TRY(hipGetLastError());
+  TRI_TRY(hipGetLastError());
   std::vector<int> levptr((size_t)nlev + 1), levbase((size_t)nlev);
-  B_TRY(hipMemcpyAsync(levptr.data(), d_levptr, sizeof(int) * (size_t)nlev, hipMemcpyDeviceToHost, st));
-  B_TRY(hipStreamSynchronize(st));
+  TRI_TRY(hipMemcpyAsync(levptr.data(), d_levptr, sizeof(int) * (size_t)nlev, hipMemcpyDeviceToHost, st));
+  TRI_TRY(hipStreamSynchronize(st));
   levptr[(size_t)nlev] = n;
-  if (levptr[0] != 0) B_FAIL();
-  for (int l = 0; l < nlev; ++l) if (levptr[(size_t)l] < 0) B_FAIL();       // a level without rows
+  if (levptr[0] != 0) TRI_FAIL();
+  for (int l = 0; l < nlev; ++l) if (levptr[(size_t)l] < 0) TRI_FAIL();       // a level without rows
   long cur = 0;
   p->levpos = (int *)malloc(sizeof(int) * 2 * (size_t)nlev);
-  if (!p->levpos) B_FAIL();
+  if (!p->levpos) TRI_FAIL();
   for (int l = 0; l < nlev; ++l) {
     const int sz = levptr[(size_t)l + 1] - levptr[(size_t)l];
-    if (sz <= 0) B_FAIL();                                // every level holds a row
+    if (sz <= 0) TRI_FAIL();                                // every level holds a row
     if (by_level && sz >= TRI_ALIGN_MIN && (cur % W)) cur += W - cur % W;
-    if (cur + sz > 2147483000L) B_FAIL();
+    if (cur + sz > 2147483000L) TRI_FAIL();
     levbase[(size_t)l] = (int)cur;
     p->levpos[2 * l] = (int)cur; p->levpos[2 * l + 1] = (int)cur + sz;
     cur += sz;
@@ -223,58 +218,58 @@ int trisolve_plan_fill_device(mi355x_handle_t h, mi355x_trisolve_plan_s *p, int 
   p->nslices = (int)((cur + W - 1) / W);
   p->nchunks = (p->nslices + 3) / 4;
   const size_t np = (size_t)p->nslices * W;
-  B_TRY(hipMemcpyAsync(d_levbase, levbase.data(), sizeof(int) * (size_t)nlev, hipMemcpyHostToDevice, st));
-  tick("sort, levels");
+  TRI_TRY(hipMemcpyAsync(d_levbase, levbase.data(), sizeof(int) * (size_t)nlev, hipMemcpyHostToDevice, st));
+  tm.tick("sort, levels");
   // 3. positions
-  B_TRY(hipMalloc((void **)&p->d_pos, sizeof(int) * (size_t)n));
-  B_TRY(hipMalloc((void **)&p->d_row, sizeof(int) * np));
-  B_TRY(hipMemsetAsync(p->d_row, 0xFF, sizeof(int) * np, st));
+  TRI_TRY(hipMalloc((void **)&p->d_pos, sizeof(int) * (size_t)n));
+  TRI_TRY(hipMalloc((void **)&p->d_row, sizeof(int) * np));
+  TRI_TRY(hipMemsetAsync(p->d_row, 0xFF, sizeof(int) * np, st));
   hipLaunchKernelGGL(tri_positions_kernel, B_GRID(n), n, d_order, d_lev, d_levptr, d_levbase, p->d_pos, p->d_row);
-  B_TRY(hipGetLastError());
+  TRI_TRY(hipGetLastError());
   // 4. per-position words, per-slice widths
-  B_TRY(hipMalloc((void **)&p->d_info, sizeof(int) * np));
-  B_TRY(hipMalloc((void **)&p->d_nsub, (size_t)p->nslices));
-  if (dinv_host) B_TRY(hipMalloc((void **)&p->d_dinv, sizeof(double) * np));
-  if (dinv_host && rscale_host) B_TRY(hipMalloc((void **)&p->d_rscale, sizeof(double) * np));
+  TRI_TRY(hipMalloc((void **)&p->d_info, sizeof(int) * np));
+  TRI_TRY(hipMalloc((void **)&p->d_nsub, (size_t)p->nslices));
+  if (dinv_host) TRI_TRY(hipMalloc((void **)&p->d_dinv, sizeof(double) * np));
+  if (dinv_host && rscale_host) TRI_TRY(hipMalloc((void **)&p->d_rscale, sizeof(double) * np));
   long long *d_width, *d_ptr64; int *d_bad;
-  B_TRY(tmp.get(&d_width, (size_t)p->nslices + 1)); B_TRY(tmp.get(&d_ptr64, (size_t)p->nslices + 1)); B_TRY(tmp.get(&d_bad, 1));
-  B_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), st));
-  B_TRY(hipMemsetAsync(d_width + p->nslices, 0, sizeof(long long), st));
+  TRI_TRY(tmp.get(&d_width, (size_t)p->nslices + 1)); TRI_TRY(tmp.get(&d_ptr64, (size_t)p->nslices + 1)); TRI_TRY(tmp.get(&d_bad, 1));
+  TRI_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), st));
+  TRI_TRY(hipMemsetAsync(d_width + p->nslices, 0, sizeof(long long), st));
   { const long threads = (long)p->nslices * W;
     hipLaunchKernelGGL(tri_slices_kernel, dim3((unsigned)((threads + MI355X_BLOCK - 1) / MI355X_BLOCK)), dim3(MI355X_BLOCK), 0, st, p->nslices, p->d_row, d_lev,
                        d_rl, d_dinvrow, d_rscrow, p->d_info, p->d_dinv, p->d_rscale, d_width, p->d_nsub, d_bad);
-    B_TRY(hipGetLastError()); }
+    TRI_TRY(hipGetLastError()); }
   // 5. slice offsets
   { size_t tb = 0;
-    B_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_width, d_ptr64, p->nslices + 1, st));
-    unsigned char *d_t; B_TRY(tmp.get(&d_t, tb));
-    B_TRY(hipcub::DeviceScan::ExclusiveSum(d_t, tb, d_width, d_ptr64, p->nslices + 1, st)); }
+    TRI_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_width, d_ptr64, p->nslices + 1, st));
+    unsigned char *d_t; TRI_TRY(tmp.get(&d_t, tb));
+    TRI_TRY(hipcub::DeviceScan::ExclusiveSum(d_t, tb, d_width, d_ptr64, p->nslices + 1, st)); }
   long long total = 0; int bad = 0;
-  B_TRY(hipMemcpyAsync(&total, d_ptr64 + p->nslices, sizeof(long long), hipMemcpyDeviceToHost, st));
-  B_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
-  B_TRY(hipStreamSynchronize(st));
-  if (bad || total > 2147483000LL) B_FAIL();              // a slice spanning more than 255 levels / offsets beyond int: as the host route
-  B_TRY(hipMalloc((void **)&p->d_ptr, sizeof(int) * ((size_t)p->nslices + 1)));
+  TRI_TRY(hipMemcpyAsync(&total, d_ptr64 + p->nslices, sizeof(long long), hipMemcpyDeviceToHost, st));
+  TRI_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
+  TRI_TRY(hipStreamSynchronize(st));
+  if (bad || total > 2147483000LL) TRI_FAIL();              // a slice spanning more than 255 levels / offsets beyond int: as the host route
+  TRI_TRY(hipMalloc((void **)&p->d_ptr, sizeof(int) * ((size_t)p->nslices + 1)));
   hipLaunchKernelGGL(tri_narrow_kernel, B_GRID(p->nslices + 1), p->nslices + 1, d_ptr64, p->d_ptr);
-  B_TRY(hipGetLastError());
-  tick("positions, slices");
+  TRI_TRY(hipGetLastError());
+  tm.tick("positions, slices");
   // 6. the sliced-ELL arrays (padding entries: zero, never read)
   const size_t ntot = (size_t)(total > 0 ? total : 1);
-  B_TRY(hipMalloc((void **)&p->d_col, sizeof(int) * ntot));
-  B_TRY(hipMalloc((void **)&p->d_val, sizeof(double) * ntot));
-  B_TRY(hipMemsetAsync(p->d_col, 0, sizeof(int) * ntot, st));
-  B_TRY(hipMemsetAsync(p->d_val, 0, sizeof(double) * ntot, st));
+  TRI_TRY(hipMalloc((void **)&p->d_col, sizeof(int) * ntot));
+  TRI_TRY(hipMalloc((void **)&p->d_val, sizeof(double) * ntot));
+  TRI_TRY(hipMemsetAsync(p->d_col, 0, sizeof(int) * ntot, st));
+  TRI_TRY(hipMemsetAsync(p->d_val, 0, sizeof(double) * ntot, st));
   if (np) {
     hipLaunchKernelGGL(tri_fill_kernel, dim3((unsigned)((np + MI355X_BLOCK - 1) / MI355X_BLOCK)), dim3(MI355X_BLOCK), 0, st, (long)np, n, p->d_row, p->d_info,
                        p->d_ptr, d_rp, ext_lo, d_cj, d_cv, p->d_pos, p->d_col, p->d_val, d_bad);
-    B_TRY(hipGetLastError());
+    TRI_TRY(hipGetLastError());
   }
-  B_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
-  B_TRY(hipStreamSynchronize(st));
-  if (bad) B_FAIL();
-  tick("fill");
-  B_TRY(trisolve_plan_finish(h, p, nlev, by_level));
-  B_TRY(hipStreamSynchronize(st));
-  tick("finish");
+  TRI_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
+  TRI_TRY(hipStreamSynchronize(st));
+  if (bad) TRI_FAIL();
+  tm.tick("fill");
+  TRI_TRY(trisolve_plan_finish(h, p, np > 0 ? np : 1, nlev, TRI_ROWS));
+  TRI_TRY(hipStreamSynchronize(st));
+  tm.tick("finish");
   return 0;
 }

@@ -2,6 +2,9 @@
 // of the row plans (trisolve_build.hip).
 #pragma once
 #include "common.hpp"
+#include <chrono>
+#include <stdio.h>
+#include <stdlib.h>
 
 #define TRI_SENTINEL 0xFFF8DEADBEEFCAFEull
 #define TRI_QUEUES 8
@@ -34,16 +37,40 @@ struct mi355x_trisolve_plan_s {
   // values per shared column, d_din = the couplings inside the node and (upper) the inverted diagonals, d_w = nb * np slots
   int nb, np;
   int spw;                 // node plans: slices (waves) per workgroup
-  int split, ring, maxcol; // split-role kernel (loader + solver wavefront per workgroup): on, batches in the LDS ring, widest slice
+  int split, maxcol;       // split-role kernel (loader + solver wavefront per workgroup): on, widest slice
   int one_xcd;             // split-role kernels: all participating workgroups on one XCD (hand-offs through its L2)
   int blkcols;             // the shared lists hold whole dependency nodes: one list entry per node, solution stored node by node
   unsigned char *d_nsz;    // per position: rows in the node
   double *d_din;           // [nb (nb - 1) / 2 + nb][np]
 };
 
-// the part of a plan that does not depend on who laid out the sliced-ELL arrays: solution vector armed with the sentinel, queue
-// counters, abort flag, launch geometry (trisolve.hip)
-int trisolve_plan_finish(mi355x_handle_t h, mi355x_trisolve_plan_s *p, int nlev, int by_level);
+// every failure of a plan builder (`h`: the handle) leaves through these: pending copies out of the builder's local arrays are
+// drained first, and the caller hands the half-built plan to mi355x_trisolve_plan_destroy
+#define TRI_TRY(expr) do { const int e__ = (int)(expr); if (e__) { (void)hipStreamSynchronize(h->stream); return e__; } } while (0)
+#define TRI_FAIL() do { (void)hipStreamSynchronize(h->stream); return (int)hipErrorInvalidValue; } while (0)
+
+// MI355X_TRISOLVE_TIMING: where the set-up time of a plan goes (stderr), one line per step of a builder.  The device route's
+// steps are asynchronous: its timer waits for `sync` before it reads the clock.
+struct TriPlanTimer {
+  bool on, upper, device;
+  hipStream_t sync;
+  double tlast;
+  explicit TriPlanTimer(bool upper_, bool device_ = false, hipStream_t sync_ = nullptr)
+      : on(getenv("MI355X_TRISOLVE_TIMING") != nullptr), upper(upper_), device(device_), sync(sync_), tlast(now()) {}
+  static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  void tick(const char *what) {
+    if (!on) return;
+    if (device) (void)hipStreamSynchronize(sync);
+    const double t = now();
+    fprintf(stderr, "[mi355x trisolve plan %s%s] %-*s %.3f s\n", upper ? "U" : "L", device ? ", device" : "", device ? 22 : 28, what, t - tlast);
+    tlast = t;
+  }
+};
+
+// the part of a plan that does not depend on who laid out its arrays: the nslots solution slots armed with the sentinel, queue
+// counters, abort flag, launch geometry with the defaults of the kernel family (trisolve.hip)
+enum tri_family { TRI_ROWS, TRI_NODES };
+int trisolve_plan_finish(mi355x_handle_t h, mi355x_trisolve_plan_s *p, size_t nslots, int nlev, tri_family family);
 // construction of a row plan on the device from the host's factor arrays (trisolve_build.hip); same arrays as the host route's
 int trisolve_plan_fill_device(mi355x_handle_t h, mi355x_trisolve_plan_s *p, int n, int nlev, const int *lev, const int *rp, const int *rl, const int *cj,
                               const double *cv, const double *dinv_host, const double *rscale_host, int by_level);

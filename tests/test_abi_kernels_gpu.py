@@ -446,23 +446,32 @@ def _tri_case(shape, scaled):
     return f, rhs, [tri_reference_apply(f, b) for b in rhs]
 
 
-@pytest.mark.parametrize("route", ["host", "device"])
+# (route, family): `onewave` switches the split-role kernels off; `default` leaves MI355X_TRISOLVE_SPLIT unset, which sends these
+# narrow shapes (n >= 64) through "every row a node of its own" -- that route ignores the build route, so it runs once, under host
+@pytest.mark.parametrize("route,family", [pytest.param("host", "onewave", id="host"), pytest.param("device", "onewave", id="device"),
+                                          pytest.param("host", "default", id="host-default")])
 @pytest.mark.parametrize("kind", ["upper", "upper_scaled"])
 @pytest.mark.parametrize("shape", TRI_APPLY_SHAPES)
-def test_trisolve_apply_on_synthetic_shapes_bitexact(dev, shape, kind, route, monkeypatch):
+def test_trisolve_apply_on_synthetic_shapes_bitexact(dev, shape, kind, route, family, monkeypatch):
     """mi355x_trisolve_plan_create_pair (both build routes) + mi355x_trisolve_apply / _apply_levels on the shapes the plan-build
     test generates: long rows of thousands of entries, n = 1 / 64 / 65, rows without entries, a dense 5 x 5.  Lower plan from the
     structure, upper plan from its mirror image with an inverted diagonal, `upper_scaled` with ICC(0)'s right-hand-side scale.
     Three applications in a row with different right-hand sides each equal their own reference bit for bit (a hand-off buffer not
     returned to the sentinel shows up only then); the level-by-level application leaves the same bits; no application reports an
-    abort.  Reference: tri.tri_reference_apply, validated on the CPU against scipy (test_host_cpu.py).  ilu.c never applies with
+    abort.  family `default`: the kernel family the library chooses by itself -- for n >= 64 single-row node plans (NB = 1) on the
+    split-role kernels with their end-aligned lists and right-hand-side scale (n64 / n65: slice boundaries; longrow: more batches than
+    the LDS ring holds; chain: sub-steps inside a slice, solved by the solver wavefront with the one-wavefront routine); one product
+    after the other, so the same reference.  Reference: tri.tri_reference_apply, validated on the CPU against scipy (test_host_cpu.py).  ilu.c never applies with
     b aliasing y, so that is not exercised."""
     k = dev.k
     monkeypatch.setenv("MI355X_TRISOLVE_BUILD", route)
-    monkeypatch.setenv("MI355X_TRISOLVE_SPLIT", "0")
+    if family == "onewave":
+        monkeypatch.setenv("MI355X_TRISOLVE_SPLIT", "0")
+    else:
+        monkeypatch.delenv("MI355X_TRISOLVE_SPLIT", raising=False)
     f, rhs, refs = _tri_case(shape, kind == "upper_scaled")
     n = f["n"]
-    where = "shape %s, %s, build route %s" % (shape, kind, route)
+    where = "shape %s, %s, build route %s, family %s" % (shape, kind, route, family)
     lo, up = C.c_void_p(), C.c_void_p()
     p = lambda a: a.ctypes.data if a is not None else None      # noqa: E731
     rc = k.mi355x_trisolve_plan_create_pair(dev.h, n, 0, f["nlev"], p(f["lev"]), p(f["rp"]), p(f["rl"]), p(f["cj"]), p(f["cv"]),

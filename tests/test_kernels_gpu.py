@@ -1186,8 +1186,8 @@ def test_trisolve_row_plans_built_on_the_device_equal_the_host_built_plans(dev, 
 
 
 def test_trisolve_device_built_plan_rejects_what_the_host_route_rejects(dev, monkeypatch):
-    """a column index outside the matrix, a dependency that does not come earlier, a level without rows: an error code from either
-    route, no fault"""
+    """a column index outside the matrix, a dependency that does not come earlier, a level without rows, a level number equal to
+    nlev: an error code from either route, no fault, no plan handed back"""
     k = dev.k
     n = 300
     rl = np.ones(n, dtype=np.int32); rl[0] = 0
@@ -1204,6 +1204,17 @@ def test_trisolve_device_built_plan_rejects_what_the_host_route_rejects(dev, mon
         k.mi355x_trisolve_plan_destroy(pl)
         bad_lev = lev.copy(); bad_lev[10] = 5                 # row 10 would run before row 9, which it depends on (and level 10 is empty)
         assert k.mi355x_trisolve_plan_create(dev.h, n, n, bad_lev.ctypes.data, rp.ctypes.data, rl.ctypes.data, cj.ctypes.data, cv.ctypes.data, None, C.byref(pl)) != 0
+        # levels alone, no dependencies (nothing else to object to): an entry equal to nlev; a level nobody is in
+        HIP_ERROR_INVALID_VALUE = 1
+        m, nl = 200, 4
+        zl, zp = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32)
+        none_i, none_d = np.zeros(1, dtype=np.int32), np.zeros(1)
+        over = (np.arange(m, dtype=np.int32) % nl); over[77] = nl
+        empty = (np.arange(m, dtype=np.int32) % nl); empty[empty == 2] = 3
+        for what, lv in (("level == nlev", over), ("empty level", empty)):
+            pl = C.c_void_p(0x1)
+            rc = k.mi355x_trisolve_plan_create(dev.h, m, nl, lv.ctypes.data, zp.ctypes.data, zl.ctypes.data, none_i.ctypes.data, none_d.ctypes.data, None, C.byref(pl))
+            assert rc == HIP_ERROR_INVALID_VALUE and not pl.value, "%s, build route %s: rc = %d, plan %s" % (what, route, rc, pl.value)
     monkeypatch.setenv("MI355X_TRISOLVE_BUILD", "device")
     pl = C.c_void_p()
     bad_cj = cj.copy(); bad_cj[50] = n + 5
