@@ -584,8 +584,10 @@ struct CGUpdateF {
     }
   }
   __device__ __forceinline__ void step(double pv, double wv, double dv, double &xv, double &rv, double &zv, double (&acc)[3]) const {
-    xv = xv + a * pv;
-    rv = rv + ma * wv;
+    if (a != 0.0) {            // VecAXPY leaves y alone for alpha == 0 (bvec1.c:253); uniform over the launch
+      xv = xv + a * pv;
+      rv = rv + ma * wv;
+    }
     zv = rv * dv;
     acc[0] += zv * zv;
     acc[1] += zv * rv;
@@ -602,7 +604,7 @@ struct CGUpdateF {
 // wait for the dot before it can launch the update -- one host synchronisation per CG iteration instead of two.
 // KSPSolve_CG's break-down tests on dpi (cg.c:196-199) are evaluated here too (CGStepLen): when one fires nothing is
 // modified, and the host, which receives dpi in out[3], takes the reference's exit with x, r, z untouched.  out[3] carries
-// dpi through the reduction tree unchanged (lane 0 of workgroup 0 contributes it, every other lane +0.0).
+// dpi through the reduction tree unchanged but for the sign of a zero (lane 0 of workgroup 0 contributes it, every other lane +0.0).
 // x == NULL: x += a p is left to the AYPX that follows (aypx_dev_kernel<NT, true>), and neither p nor x is read here:
 // 5 vector passes instead of 8; same lanes, same order, same sums.
 struct CGUpdateDevF {

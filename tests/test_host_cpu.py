@@ -696,7 +696,6 @@ UNTESTED = {
     "mi355x_device_name": "runtime query, used by bench.py's report only",
     "mi355x_get_device": "hipGetDevice passed through",
     "mi355x_handle_destroy": "hipStreamDestroy + frees; the test processes end with their handles",
-    "mi355x_handle_device_scratch": "accessor of a buffer the host library owns",
     "mi355x_handle_stream": "accessor (the raw stream, for the RCCL layer)",
     "mi355x_handle_publish_at": "mi355x_handle_publish (tested) is this with dst_offset = 0; offsets are driven through the solvers of test_host_gpu.py",
     "mi355x_handle_wait_event": "hipStreamWaitEvent passed through (multi-stream overlap in the host library)",
