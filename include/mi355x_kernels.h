@@ -358,7 +358,9 @@ int mi355x_ilu0_factor_info(mi355x_ilu0_factor_t ctx, int *lanes, int *nlev);
  * (a sentinel bit pattern means "not computed yet"; write-through stores, polling loads).  Same one-lane-per-row,
  * column-order arithmetic: same bits.  plan_create: lev[i] = dependency level of row i (every level non-empty), row i's
  * off-diagonal entries are cj/cv[rp[i] .. rp[i]+rl[i]), dinv != NULL (inverted diagonal per row) marks the upper solve.
- * apply: y = U^-1 L^-1 b; returns non-zero without launching if an earlier application timed out on a dependency. */
+ * apply: y = U^-1 L^-1 b; returns non-zero without launching if an earlier application timed out on a dependency.  A NaN is a
+ * solution value like any other, except the one bit pattern of the sentinel (0xFFF8DEADBEEFCAFE): a solution value with exactly
+ * those bits cannot be told from "not computed yet" -- its consumers wait until they give up and the application aborts. */
 typedef struct mi355x_trisolve_plan_s *mi355x_trisolve_plan_t;
 int mi355x_trisolve_plan_create(mi355x_handle_t h, int n, int nlev, const int *lev, const int *rp, const int *rl, const int *cj,
                                 const double *cv, const double *dinv, mi355x_trisolve_plan_t *plan);
@@ -405,7 +407,7 @@ int mi355x_trisolve_aborted(mi355x_trisolve_plan_t plan, int *aborted);
 int mi355x_trisolve_debug_get(mi355x_trisolve_plan_t plan, int which, void *out, size_t cap_bytes, size_t *bytes);
 /* the same application over the same plans with one launch per dependency level and no hand-off between wavefronts (same
  * per-row order of the products: same bits): what a caller falls back to after a sync-free application gave up, whatever the
- * factor (ILU(0), ICC(0)); does not consult or change the abort flags */
+ * factor (ILU(0), ICC(0)); does not consult or change the abort flags; a sync-free application may follow */
 int mi355x_trisolve_apply_levels(mi355x_handle_t h, mi355x_trisolve_plan_t lower, mi355x_trisolve_plan_t upper, const double *b, double *y);
 /* development / tests: raise a plan's abort flag as a dependency wait that gave up would */
 int mi355x_trisolve_debug_set_aborted(mi355x_trisolve_plan_t plan, int value);

@@ -775,6 +775,7 @@ __global__ __launch_bounds__(MI355X_BLOCK) void tri_arm_kernel(size_t n, double 
 // sentinel, the queue counters, the abort flag in pinned memory, the launch geometry.
 int trisolve_plan_finish(mi355x_handle_t h, mi355x_trisolve_plan_s *p, size_t nslots, int nlev, tri_family family) {
   MI355X_TRY(hipMalloc((void **)&p->d_w, sizeof(double) * nslots));
+  p->nslots = nslots;
   hipLaunchKernelGGL(tri_arm_kernel, dim3(mi355x_grid_for(nslots, 4)), dim3(MI355X_BLOCK), 0, h->stream, nslots, p->d_w);
   MI355X_LAUNCH_CHECK();
   MI355X_TRY(hipMalloc((void **)&p->d_queue, sizeof(unsigned int) * (TRI_QUEUES * TRI_QSTRIDE + 32)));
@@ -1304,6 +1305,17 @@ static int tri_node_go(mi355x_handle_t h, mi355x_trisolve_plan_t lo, mi355x_tris
                        up->d_ptr, up->d_info, up->d_row, up->d_nsz, up->d_col, up->d_val, up->d_din, lo->d_w, lo->d_pos, up->d_w, y, (const double *)up->d_rscale);
   });
 }
+// The level-by-level kernels read the lower solve's w and leave it as it is, where the sync-free upper solve returns every slot it
+// reads to the sentinel: after a level-by-level application the lower solve's slots are re-armed here, so that a sync-free
+// application that follows waits for its own values instead of taking the previous application's.  (The upper solve's slots are
+// re-armed by the next sync-free lower solve, tri_prologue / tri_rearm_position.)  Only mi355x_trisolve_apply_levels does this: the
+// level-by-level fall-back inside tri_node_go (a device that refuses the split-role kernels' LDS) leaves the slots filled, and is
+// followed by nothing but itself on such a device.
+static int tri_rearm_lower(mi355x_handle_t h, mi355x_trisolve_plan_t lo) {
+  hipLaunchKernelGGL(tri_arm_kernel, dim3(mi355x_grid_for(lo->nslots, 4)), dim3(MI355X_BLOCK), 0, h->stream, lo->nslots, lo->d_w);
+  MI355X_LAUNCH_CHECK();
+  return 0;
+}
 static int tri_node_dispatch(mi355x_handle_t h, mi355x_trisolve_plan_t lo, mi355x_trisolve_plan_t up, const double *b, double *y, bool levels) {
   if (lo->nb != up->nb || lo->blkcols != up->blkcols) return (int)hipErrorInvalidValue;
   if (lo->blkcols) {
@@ -1376,22 +1388,27 @@ int mi355x_trisolve_apply(mi355x_handle_t h, mi355x_trisolve_plan_t lo, mi355x_t
 }
 
 // y = U^-1 L^-1 b over the same plans, one launch per dependency level (nlevL + nlevU launches), no hand-off between
-// wavefronts: usable after an abort (the flags are not consulted, nothing is left armed or disarmed for the sync-free form)
+// wavefronts: usable after an abort (the flags are not consulted); the lower solve's slots go back to the sentinel at the end, so
+// that the sync-free form may follow
 int mi355x_trisolve_apply_levels(mi355x_handle_t h, mi355x_trisolve_plan_t lo, mi355x_trisolve_plan_t up, const double *b, double *y) {
   if (!lo || !up || lo->n != up->n || lo->upper || !up->upper) return (int)hipErrorInvalidValue;
   if (lo->n == 0) return 0;
-  if (lo->nb >= 1 || up->nb >= 1) return tri_node_dispatch(h, lo, up, b, y, true);
+  if (lo->nb >= 1 || up->nb >= 1) {
+    const int rcn = tri_node_dispatch(h, lo, up, b, y, true);
+    return rcn ? rcn : tri_rearm_lower(h, lo);
+  }
   const int rc = tri_by_level(lo, [&](dim3 grid, dim3 block, int p0, int p1) {
     hipLaunchKernelGGL((trisolve_level_kernel<false>), grid, block, 0, h->stream, p0, p1,
                        lo->d_ptr, lo->d_info, lo->d_row, lo->d_col, lo->d_val, (const double *)nullptr, b, (const int *)nullptr, lo->d_w,
                        (double *)nullptr, (const double *)nullptr);
   });
   if (rc) return rc;
-  return tri_by_level(up, [&](dim3 grid, dim3 block, int p0, int p1) {
+  const int rcu = tri_by_level(up, [&](dim3 grid, dim3 block, int p0, int p1) {
     hipLaunchKernelGGL((trisolve_level_kernel<true>), grid, block, 0, h->stream, p0, p1,
                        up->d_ptr, up->d_info, up->d_row, up->d_col, up->d_val, up->d_dinv, lo->d_w, lo->d_pos, up->d_w, y,
                        (const double *)up->d_rscale);
   });
+  return rcu ? rcu : tri_rearm_lower(h, lo);
 }
 
 // tests: one array of a ROW plan back on the host.  which: 0 slice offsets (nslices + 1 ints), 1 (length, sub-step) words, 2 position -> row,

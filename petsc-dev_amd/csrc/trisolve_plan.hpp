@@ -26,6 +26,7 @@ struct mi355x_trisolve_plan_s {
   unsigned char *d_nsub;   // sub-steps per slice
   int *d_pos;        // per row: its position (for the other solve's gather of this solve's result)
   double *d_w;       // solution in position order, 64 * nslices doubles
+  size_t nslots;     // doubles of d_w (node plans: nb per position)
   unsigned int *d_queue;   // TRI_QUEUES counters
   int *abort_flag;   // pinned + mapped
   int grid, sleep_cap;

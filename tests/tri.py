@@ -103,3 +103,47 @@ def tri_reference_apply(f, b):
             s -= cv[q] * x[cj[q]]
         x[i] = s * dinv[i]
     return np.array(x, dtype=np.float64).reshape(n)
+
+
+def tri_node_reference_apply(f, b):
+    """y = U^-1 L^-1 b as MatSolve_SeqAIJ_Inode sums it (inode.c:2327-2760; the oracle's orc_ilu0_solve_inode restated on row-level
+    arrays): the rows nstart[u] .. nstart[u + 1] of node u share one column list (the first row's in L, the last row's in U); every
+    row's sum takes the shared columns two at a time, sum -= v0 * x0 + v1 * x1 (the two rounded products added first), an odd last
+    column alone, then the couplings inside the node -- lower: the node's earlier rows in row order; upper: its later rows, nearest
+    row last -- and, upper, times the inverted diagonal.  f: the row-level arrays of tri_factor's dict (lower: shared columns, then
+    the couplings; upper: the couplings, then the shared columns) and nstart.  Plain Python floats."""
+    n = f["n"]
+    ns = f["nstart"].tolist()
+    rp, rl, cj, cv = f["rp"].tolist(), f["rl"].tolist(), f["cj"].tolist(), f["cv"].tolist()
+    z = [0.0] * n
+    bl = b.tolist()
+    for u in range(len(ns) - 1):
+        r0, sz = ns[u], ns[u + 1] - ns[u]
+        sh, p0 = rl[r0], rp[r0]
+        for k in range(sz):
+            p, s, j = rp[r0 + k], bl[r0 + k], 0
+            while j < sh - 1:
+                s -= cv[p + j] * z[cj[p0 + j]] + cv[p + j + 1] * z[cj[p0 + j + 1]]
+                j += 2
+            if j == sh - 1:
+                s -= cv[p + j] * z[cj[p0 + j]]
+            for l in range(k):
+                s -= cv[p + sh + l] * z[r0 + l]
+            z[r0 + k] = s
+    rp, rl, cj, cv = f["rpu"].tolist(), f["rlu"].tolist(), f["cju"].tolist(), f["cvu"].tolist()
+    dinv = f["dinv"].tolist()
+    x = [0.0] * n
+    for u in range(len(ns) - 2, -1, -1):
+        sz, rL = ns[u + 1] - ns[u], ns[u + 1] - 1
+        sh, p0 = rl[rL], rp[rL]
+        for k in range(sz):
+            p, s, j = rp[rL - k] + k, z[rL - k], 0
+            while j < sh - 1:
+                s -= cv[p + j] * x[cj[p0 + j]] + cv[p + j + 1] * x[cj[p0 + j + 1]]
+                j += 2
+            if j == sh - 1:
+                s -= cv[p + j] * x[cj[p0 + j]]
+            for l in range(k):
+                s -= cv[p - 1 - l] * x[rL - l]
+            x[rL - k] = s * dinv[rL - k]
+    return np.array(x, dtype=np.float64).reshape(n)
