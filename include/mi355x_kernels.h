@@ -261,6 +261,19 @@ int mi355x_csr_assemble(mi355x_handle_t h, int nseg, const int *segptr, const in
 int mi355x_csr_diagonal_scale(mi355x_handle_t h, int m, const int *ai, const int *aj, double *aa, const double *l, const double *r);
 /* MatGetDiagonal_SeqAIJ  src/mat/impls/aij/seq/aij.c:1040   d[r] = A[r,r] or 0 */
 int mi355x_csr_get_diagonal(mi355x_handle_t h, int m, const int *ai, const int *aj, const double *aa, double *d);
+/* MatShift  src/mat/utils/axpy.c:170   with an unchanged pattern: aa[k] = aa[k] + alpha at the diagonal entry of every row (the row
+ * search of mi355x_csr_get_diagonal).  A row without a diagonal entry is not touched; nmissing_dev (device, may be NULL) receives
+ * the number of such rows. */
+int mi355x_csr_shift(mi355x_handle_t h, int m, const int *ai, const int *aj, double alpha, double *aa, int *nmissing_dev);
+/* MatAXPY_SeqAIJ with SUBSET_NONZERO_PATTERN  aij.c:2621   ya[xtoy[k]] = ya[xtoy[k]] + alpha * xa[k], k < nzx, two roundings;
+ * xtoy injective (no atomics); alpha == 0 does the arithmetic too (the same-pattern form, mi355x_vec_axpy on the value arrays,
+ * returns at once as daxpy does); same-pattern MatCopy is mi355x_memcpy_d2d.  xa may be ya with the identity map. */
+int mi355x_csr_axpy_map(mi355x_handle_t h, int nzx, const int *xtoy, double alpha, const double *xa, double *ya);
+/* the map of that update (host only, no device call): for every stored entry k of X, m rows, xtoy[k] = position of the same (row,
+ * column) in Y; the columns of a row ascending in both.  xcols / ycols (may be NULL): local -> global column translations, increasing
+ * (the off-diagonal blocks of MPIAIJ, compacted through each matrix's own garray).  X stores an entry Y lacks: non-zero, the first
+ * such row in *bad_row (-1 otherwise), xtoy undefined.  Rows are split over host threads from 200 000 entries. */
+int mi355x_csr_subset_map(int m, const int *xi, const int *xj, const int *xcols, const int *yi, const int *yj, const int *ycols, int *xtoy, int *bad_row);
 
 /* ---- column-tiled CSR SpMV: x staged in LDS (csrc/spmv_tiled.hip) ------ */
 /* For matrices whose x gathers miss the caches (rows that pick columns from a wide window without neighbouring rows sharing them):

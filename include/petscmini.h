@@ -255,6 +255,11 @@ PetscErrorCode MatMultTransposeAdd(Mat A, Vec x, Vec y, Vec z);
 PetscErrorCode MatGetDiagonal(Mat A, Vec d);
 PetscErrorCode MatScale(Mat A, PetscScalar a);
 PetscErrorCode MatZeroEntries(Mat A);
+/* value updates of an assembled matrix (src/mat/utils/axpy.c, matrix.c MatCopy): on the device copy when the pattern allows */
+PetscErrorCode MatShift(Mat Y, PetscScalar a);                           /* Y += a I */
+PetscErrorCode MatAXPY(Mat Y, PetscScalar a, Mat X, MatStructure str);   /* Y += a X; X's pattern must lie inside Y's */
+PetscErrorCode MatAYPX(Mat Y, PetscScalar a, Mat X, MatStructure str);   /* Y = a Y + X */
+PetscErrorCode MatCopy(Mat A, Mat B, MatStructure str);                  /* B <- A */
 PetscErrorCode MatSetOptionsPrefix(Mat A, const char prefix[]);
 /* matrix.c:3937-4010 (MatGetFactor looks "MatGetFactor_<package>_C" up on the operator), 2766-3144 (symbolic / numeric), 3196 (MatSolve) */
 PetscErrorCode MatFactorInfoInitialize(MatFactorInfo *info);

@@ -97,6 +97,9 @@ PetscErrorCode MatCreate_SeqAIJHIPMI355X(Mat B) {
   B->ops->scale            = MatScale_SeqAIJHIP;          /* host copy and device copy updated side by side */
   B->ops->zeroentries      = MatZeroEntries_SeqAIJHIP;
   B->ops->diagonalscale    = MatDiagonalScale_SeqAIJHIP;
+  B->ops->shift            = MatShift_SeqAIJHIP;          /* MatShift / MatAXPY / MatCopy with an unchanged pattern: the same model */
+  B->ops->axpy             = MatAXPY_SeqAIJHIP;
+  B->ops->copy             = MatCopy_SeqAIJHIP;
   B->ops->setvaluesbatch   = MatSetValuesBatch_SeqAIJHIP;
   B->ops->setfromoptions   = MatSetFromOptions_SeqAIJHIP;  /* the type's -mat_hipmi355x_* options under the matrix's prefix (slot 76); MatSetFromOptions_SeqAIJ has none of its own in 3.3 */
   /* ops->duplicate stays MatDuplicate_SeqAIJ (aij.c:3964): it creates the new matrix with MatSetType(type_name), i.e. through THIS

@@ -86,6 +86,9 @@ PetscErrorCode MatCreate_MPIAIJHIPMI355X(Mat B) {
   B->ops->multtranspose    = MatMultTranspose_MPIAIJHIP;
   B->ops->multtransposeadd = MatMultTransposeAdd_MPIAIJHIP;
   B->ops->diagonalscale    = MatDiagonalScale_MPIAIJHIP;
+  B->ops->shift            = MatShift_MPIAIJHIP;           /* through the blocks: host and device copies side by side */
+  B->ops->axpy             = MatAXPY_MPIAIJHIP;
+  B->ops->copy             = MatCopy_MPIAIJHIP;
   B->ops->assemblyend      = MatAssemblyEnd_MPIAIJHIPMI355X;
   B->ops->destroy          = MatDestroy_MPIAIJHIPMI355X;
   B->ops->getvecs          = MatGetVecs_HIPMI355X;

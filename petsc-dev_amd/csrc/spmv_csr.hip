@@ -779,6 +779,28 @@ __global__ __launch_bounds__(MI355X_BLOCK) void csr_diag_kernel(int m, const int
   d[r] = v;
 }
 
+// MatShift (axpy.c:170-200) with an unchanged pattern: a[k] = a[k] + alpha at the diagonal entry of every row, found by
+// csr_diag_kernel's search.  A row without one is counted (when a counter is given) and not touched.  One lane per row.
+__global__ __launch_bounds__(MI355X_BLOCK) void csr_shift_kernel(int m, const int *__restrict__ ai, const int *__restrict__ aj,
+                                                                double alpha, double *aa, int *nmissing) {
+  int r = blockIdx.x * MI355X_BLOCK + threadIdx.x;
+  if (r >= m) return;
+  for (int k = ai[r]; k < ai[r + 1]; ++k) {
+    if (aj[k] == r) { aa[k] = aa[k] + alpha; return; }
+  }
+  if (nmissing) atomicAdd(nmissing, 1);
+}
+
+// MatAXPY_SeqAIJ with SUBSET_NONZERO_PATTERN (aij.c:2621-2640): ya[xtoy[k]] = ya[xtoy[k]] + alpha * xa[k], product and sum rounded
+// separately.  xtoy is injective: one lane per entry of X, plain loads and stores.  xa may be ya (X == Y, the identity map).
+__global__ __launch_bounds__(MI355X_BLOCK) void csr_axpy_map_kernel(int nzx, const int *__restrict__ xtoy, double alpha,
+                                                                   const double *xa, double *ya) {
+  const long k = (long)blockIdx.x * MI355X_BLOCK + threadIdx.x;
+  if (k >= nzx) return;
+  const int t = xtoy[k];
+  ya[t] = ya[t] + alpha * xa[k];
+}
+
 // Which kernel a plan runs with these arrays: the one decision behind mi355x_spmv_csr / _add / _scaled, mi355x_spmv_csr_dot
 // and mi355x_spmv_plan_dot_available (CG relies on y carrying the same bits from the first two).  In order of precedence;
 // the compressed forms need whole rows (no compressed-row plan) and, all but the value patterns, 16-byte aligned values.
@@ -1410,6 +1432,53 @@ int mi355x_csr_get_diagonal(mi355x_handle_t h, int m, const int *ai, const int *
                      ai, aj, aa, d);
   MI355X_LAUNCH_CHECK();
   return 0;
+}
+
+int mi355x_csr_shift(mi355x_handle_t h, int m, const int *ai, const int *aj, double alpha, double *aa, int *nmissing_dev) {
+  if (nmissing_dev) MI355X_TRY(hipMemsetAsync(nmissing_dev, 0, sizeof(int), h->stream));
+  if (m <= 0) return 0;
+  hipLaunchKernelGGL(csr_shift_kernel, dim3((m + MI355X_BLOCK - 1) / MI355X_BLOCK), dim3(MI355X_BLOCK), 0, h->stream, m, ai, aj, alpha, aa, nmissing_dev);
+  MI355X_LAUNCH_CHECK();
+  return 0;
+}
+
+int mi355x_csr_axpy_map(mi355x_handle_t h, int nzx, const int *xtoy, double alpha, const double *xa, double *ya) {
+  if (nzx <= 0) return 0;
+  hipLaunchKernelGGL(csr_axpy_map_kernel, dim3((unsigned)(((long)nzx + MI355X_BLOCK - 1) / MI355X_BLOCK)), dim3(MI355X_BLOCK), 0, h->stream, nzx, xtoy, alpha, xa, ya);
+  MI355X_LAUNCH_CHECK();
+  return 0;
+}
+
+// Host only.  Rows lo .. hi - 1 of the map: both rows ascending in the (translated) column, so one merge walk per row.  Returns the
+// first row of the range in which X stores an entry Y lacks, or -1.
+static int subset_map_rows(int lo, int hi, const int *xi, const int *xj, const int *xcols, const int *yi, const int *yj, const int *ycols, int *xtoy) {
+  for (int r = lo; r < hi; ++r) {
+    int q = yi[r];
+    const int qe = yi[r + 1];
+    for (int k = xi[r]; k < xi[r + 1]; ++k) {
+      const int c = xcols ? xcols[xj[k]] : xj[k];
+      while (q < qe && (ycols ? ycols[yj[q]] : yj[q]) < c) ++q;
+      if (q == qe || (ycols ? ycols[yj[q]] : yj[q]) != c) return r;
+      xtoy[k] = q++;
+    }
+  }
+  return -1;
+}
+int mi355x_csr_subset_map(int m, const int *xi, const int *xj, const int *xcols, const int *yi, const int *yj, const int *ycols, int *xtoy, int *bad_row) {
+  if (bad_row) *bad_row = -1;
+  if (m <= 0) return 0;
+  return mi355x_guard([&]() -> int {
+    // one thread below 200 000 entries of X, unless MI355X_HOST_THREADS asks for a count; never more than one thread per row
+    int nth = (xi[m] < 200000 && !getenv("MI355X_HOST_THREADS")) ? 1 : mi355x_host_threads(16);
+    if (nth > m) nth = m;
+    std::vector<int> bad((size_t)nth, -1);
+    mi355x_parallel_chunks(nth, [&](int k) {
+      bad[(size_t)k] = subset_map_rows((int)((long)m * k / nth), (int)((long)m * (k + 1) / nth), xi, xj, xcols, yi, yj, ycols, xtoy);
+    });
+    for (int k = 0; k < nth; ++k)
+      if (bad[(size_t)k] >= 0) { if (bad_row) *bad_row = bad[(size_t)k]; return (int)hipErrorInvalidValue; }   // chunks are in row order: the first row
+    return 0;
+  });
 }
 
 }  // extern "C"

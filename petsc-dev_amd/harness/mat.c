@@ -232,6 +232,47 @@ PetscErrorCode MatZeroEntries(Mat A) {
   A->state++;
   return 0;
 }
+/* MatShift, axpy.c:170-200: the type's slot, else the loop of MatSetValues(ADD_VALUES) over the local rows and an assembly */
+PetscErrorCode MatShift(Mat Y, PetscScalar a) {
+  PetscErrorCode ierr;
+  MatTypeSet(Y, 1); MatAssembled(Y);
+  if (Y->ops->shift) { ierr = (*Y->ops->shift)(Y, a);CHKERRQ(ierr); }
+  else {
+    for (PetscInt i = Y->rmap->rstart; i < Y->rmap->rend; i++) { ierr = MatSetValues(Y, 1, &i, 1, &i, &a, ADD_VALUES);CHKERRQ(ierr); }
+    ierr = MatAssemblyBegin(Y, MAT_FINAL_ASSEMBLY);CHKERRQ(ierr);
+    ierr = MatAssemblyEnd(Y, MAT_FINAL_ASSEMBLY);CHKERRQ(ierr);
+  }
+  Y->state++;
+  return 0;
+}
+/* MatAXPY, axpy.c:26-56 */
+PetscErrorCode MatAXPY(Mat Y, PetscScalar a, Mat X, MatStructure str) {
+  PetscErrorCode ierr;
+  MatTypeSet(Y, 1); MatTypeSet(X, 3); MatAssembled(Y); MatAssembled(X);
+  if (X->rmap->N != Y->rmap->N || X->cmap->N != Y->cmap->N) SETERRQ(Y->comm, PETSC_ERR_ARG_SIZ, "Non conforming matrix add: %d %d %d %d", X->rmap->N, Y->rmap->N, X->cmap->N, Y->cmap->N);
+  if (X->rmap->n != Y->rmap->n || X->cmap->n != Y->cmap->n) SETERRQ(Y->comm, PETSC_ERR_ARG_SIZ, "Non conforming matrix add: local sizes %d %d %d %d", X->rmap->n, Y->rmap->n, X->cmap->n, Y->cmap->n);
+  if (!Y->ops->axpy) SETERRQ(Y->comm, PETSC_ERR_SUP, "Mat type %s", Y->type_name);
+  ierr = (*Y->ops->axpy)(Y, a, X, str);CHKERRQ(ierr);
+  Y->state++;
+  return 0;
+}
+/* MatAYPX, axpy.c:307-322: Y = a Y + X */
+PetscErrorCode MatAYPX(Mat Y, PetscScalar a, Mat X, MatStructure str) {
+  PetscErrorCode ierr = MatScale(Y, a);CHKERRQ(ierr);
+  return MatAXPY(Y, 1.0, X, str);
+}
+/* MatCopy, matrix.c:3700-3745: B <- A through A's slot */
+PetscErrorCode MatCopy(Mat A, Mat B, MatStructure str) {
+  PetscErrorCode ierr;
+  MatTypeSet(A, 1); MatTypeSet(B, 2); MatAssembled(A);
+  if (A->factortype) SETERRQ(A->comm, PETSC_ERR_ARG_WRONGSTATE, "Not for factored matrix");
+  if (A->rmap->N != B->rmap->N || A->cmap->N != B->cmap->N) SETERRQ(A->comm, PETSC_ERR_ARG_SIZ, "Mat A,Mat B: global dim (%d,%d) (%d,%d)", A->rmap->N, B->rmap->N, A->cmap->N, B->cmap->N);
+  if (A == B) return 0;
+  if (!A->ops->copy) SETERRQ(A->comm, PETSC_ERR_SUP, "Mat type %s", A->type_name);
+  ierr = (*A->ops->copy)(A, B, str);CHKERRQ(ierr);
+  B->state++;
+  return 0;
+}
 
 /* ---- type-specific methods reached through composed functions, as in the reference (PetscTryMethod / PetscUseMethod,
  * e.g. MatSeqAIJSetPreallocation aij.c:3435, MatMPIAIJSetPreallocation mpiaij.c:4274, MatGetDiagonalBlock matrix.c) ---- */

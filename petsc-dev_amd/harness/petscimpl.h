@@ -127,6 +127,9 @@ struct _MatOps {
   PetscErrorCode (*zeroentries)(Mat);                    /* slot 23 */
   PetscErrorCode (*setup)(Mat);                          /* slot 29 */
   PetscErrorCode (*scale)(Mat, PetscScalar);
+  PetscErrorCode (*shift)(Mat, PetscScalar);                      /* a(i,i) += alpha (axpy.c MatShift) */
+  PetscErrorCode (*axpy)(Mat, PetscScalar, Mat, MatStructure);   /* Y += a X */
+  PetscErrorCode (*copy)(Mat, Mat, MatStructure);                /* B <- A: A's slot */
   PetscErrorCode (*duplicate)(Mat, MatDuplicateOption, Mat *);   /* slot 34 */
   PetscErrorCode (*setfromoptions)(Mat);                 /* slot 76 */
   PetscErrorCode (*destroy)(Mat);                        /* slot 60 */

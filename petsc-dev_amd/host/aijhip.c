@@ -155,13 +155,14 @@ static PetscErrorCode seqaij_check_inode(Mat A) {
 }
 
 /* ---------------------------------------------------------------- the type's options
- * -mat_hipmi355x_index_compression, _row_patterns, _value_patterns, _tiled, _tiled_stage_min.  MatSetFromOptions (ops->setfromoptions,
+ * -mat_hipmi355x_index_compression, _row_patterns, _value_patterns, _tiled, _tiled_stage_min, _blocked, _update_on_device.  MatSetFromOptions (ops->setfromoptions,
  * slot 76, matimpl.h:110; gcreate.c:201-203) reads them under the matrix's own options prefix and keeps them with the matrix; a matrix
  * that was never asked falls back to the global database when its device copy is built (blocks of an MPIAIJ matrix, matrices created
  * by MatCreateSeqAIJWithArrays and used at once). */
-enum { HOPT_IC = 0, HOPT_RP, HOPT_VP, HOPT_TILED, HOPT_TILED_SMIN, HOPT_BLOCKED, HOPT_N };
+enum { HOPT_IC = 0, HOPT_RP, HOPT_VP, HOPT_TILED, HOPT_TILED_SMIN, HOPT_BLOCKED, HOPT_UPDATE_DEV, HOPT_N };
 static const char *const hopt_name[HOPT_N] = {"-mat_hipmi355x_index_compression", "-mat_hipmi355x_row_patterns", "-mat_hipmi355x_value_patterns",
-                                              "-mat_hipmi355x_tiled", "-mat_hipmi355x_tiled_stage_min", "-mat_hipmi355x_blocked"};
+                                              "-mat_hipmi355x_tiled", "-mat_hipmi355x_tiled_stage_min", "-mat_hipmi355x_blocked",
+                                              "-mat_hipmi355x_update_on_device"};
 static PetscErrorCode hip_mat_option(Mat A, int which, PetscInt *val) {
   Mat_SeqAIJHIP *d = SD(A);
   PetscBool set;
@@ -176,7 +177,7 @@ static PetscErrorCode MatSetFromOptions_SeqAIJHIP(Mat A) {
     ierr = PetscOptionsGetInt(HipObjPrefix(A), hopt_name[k], &v, &set);CHKERRQ(ierr);
     if (set && (!d->opt_set[k] || d->opt[k] != v)) {
       d->opt[k] = v; d->opt_set[k] = PETSC_TRUE;
-      mirror_reset(d);                                       /* the analyses run again with the new choice */
+      if (k != HOPT_UPDATE_DEV) mirror_reset(d);             /* the analyses run again with the new choice */
     }
   }
   return 0;
@@ -198,6 +199,13 @@ static void batch_map_free(Mat_SeqAIJHIP *d) {
   if (d->bm_segslot) mi355x_free(d->bm_segslot);
   d->bm_order = d->bm_segptr = d->bm_segslot = NULL;
 }
+static void value_maps_free(Mat_SeqAIJHIP *d) {   /* what MatShift / MatAXPY / MatCopy keep with the pattern */
+  HipFree(d->sh_diag); d->sh_diag = NULL; d->sh_gen = 0;
+  HipFree(d->xtoy_h); d->xtoy_h = NULL;
+  if (d->xtoy_d) mi355x_free(d->xtoy_d);
+  d->xtoy_d = NULL; d->xtoy_xgen = d->xtoy_ygen = 0; d->xtoy_from = NULL;
+  d->same_xgen = d->same_ygen = 0;
+}
 /* the arrays of the old pattern go; counts, requests, options, timing and (harness) the triangular factors outlive them */
 static PetscErrorCode device_free(Mat A) {
   Mat_SeqAIJHIP *d = SD(A);
@@ -205,6 +213,7 @@ static PetscErrorCode device_free(Mat A) {
   { PetscErrorCode ierr = VecHIPProductMatrixChanges(A);CHKERRQ(ierr); }   /* a noted product of this matrix runs while its arrays exist */
   form_free(&d->mat); form_free(&d->t); form_free(&d->b); form_free(&d->tb);
   batch_map_free(d);
+  value_maps_free(d);
   if (d->bm_v) mi355x_free(d->bm_v);
   d->bm_v = NULL; d->bm_vcap = 0;
   d->baij4_mfma = PETSC_FALSE;
@@ -1143,6 +1152,266 @@ static PetscErrorCode MatDiagonalScale_SeqAIJHIP(Mat A, Vec ll, Vec rr) {
   return 0;
 }
 
+/* MatShift, MatAXPY and MatCopy (axpy.c:170 MatShift; aij.c:2600-2660 MatAXPY_SeqAIJ, 2663-2690 MatCopy_SeqAIJ) on the same model: the
+ * host copy by loops on host threads, and -- when the device copy is current -- the same update queued on the device, no host wait.
+ * -mat_hipmi355x_update_on_device <1|0> (default 1; per matrix, for these three only): 0 updates the host copy alone and the values
+ * travel at the next use, the route a program took before these slots existed.  BAIJ, compressed-row forms: host copy only. */
+static PetscBool update_on_device(Mat A) {
+  PetscInt v = 1;
+  if (hip_mat_option(A, HOPT_UPDATE_DEV, &v)) return PETSC_TRUE;
+  return (PetscBool)(v != 0);
+}
+/* the serial number of A's pattern upload while the host pattern still is that pattern (entries are never removed: same nz), else 0 */
+static unsigned long long host_pattern_gen(Mat A) {
+  Mat_SeqAIJHIP *d = SD(A);
+  return (d->pattern_gen && SA(A)->compact && d->pattern_nz == SA(A)->nz) ? d->pattern_gen : 0;
+}
+static PetscErrorCode value_op_view(Mat A) {   /* inside a PETSc tree the parent may have replaced its arrays since the view was taken */
+#if defined(PETSCHIPMI355X_WITH_PETSC)
+  PetscErrorCode ierr = hipaij_refresh_view_if_stale(A);CHKERRQ(ierr);
+#endif
+  (void)A;
+  return 0;
+}
+typedef struct { PetscScalar *a; const PetscInt *pos, *ai, *aj; const PetscScalar *x; PetscScalar alpha; PetscInt *out; } ValUpd;
+static void upd_find_diag(void *c_, PetscInt lo, PetscInt hi) {
+  ValUpd *c = (ValUpd *)c_;
+  for (PetscInt r = lo; r < hi; r++) { PetscInt k = c->ai[r]; while (k < c->ai[r + 1] && c->aj[k] != r) k++; c->out[r] = k < c->ai[r + 1] ? k : -1; }
+}
+static void upd_shift(void *c_, PetscInt lo, PetscInt hi) { ValUpd *c = (ValUpd *)c_; for (PetscInt r = lo; r < hi; r++) c->a[c->pos[r]] = c->a[c->pos[r]] + c->alpha; }
+static void upd_axpy(void *c_, PetscInt lo, PetscInt hi) { ValUpd *c = (ValUpd *)c_; for (PetscInt k = lo; k < hi; k++) c->a[k] = c->a[k] + c->alpha * c->x[k]; }
+static void upd_copy(void *c_, PetscInt lo, PetscInt hi) { ValUpd *c = (ValUpd *)c_; memcpy(c->a + lo, c->x + lo, sizeof(PetscScalar) * (size_t)(hi - lo)); }
+static void upd_axpy_map(void *c_, PetscInt lo, PetscInt hi) {
+  ValUpd *c = (ValUpd *)c_;
+  for (PetscInt k = lo; k < hi; k++) { const PetscInt t = c->pos[k]; c->a[t] = c->a[t] + c->alpha * c->x[k]; }
+}
+/* where every row's diagonal entry is; full: a square matrix every row of which has one -- decided once per pattern upload */
+static PetscErrorCode shift_diag_positions(Mat A, const PetscInt **pos, PetscBool *full) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
+  const unsigned long long gen = host_pattern_gen(A);
+  *pos = NULL; *full = PETSC_FALSE;
+  if (!(d->sh_diag && gen && d->sh_gen == gen)) {
+    PetscInt *p;
+    HipFree(d->sh_diag); d->sh_diag = NULL; d->sh_gen = 0; d->sh_full = PETSC_FALSE;
+    if (a->m != a->n) return 0;
+    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(a->m, 1), &p);CHKERRQ(ierr);
+    { ValUpd u = {NULL, NULL, a->i, a->j, NULL, 0.0, p};
+      HipParallelRanges(a->m, upd_find_diag, &u); }
+    d->sh_full = PETSC_TRUE;
+    for (PetscInt r = 0; r < a->m; r++) if (p[r] < 0) { d->sh_full = PETSC_FALSE; break; }
+    d->sh_diag = p; d->sh_gen = gen;
+  }
+  *pos = d->sh_diag; *full = d->sh_full;
+  return 0;
+}
+static PetscErrorCode MatShift_SeqAIJHIP(Mat A, PetscScalar alpha) {
+  PetscErrorCode ierr;
+  HipAIJ *a; Mat_SeqAIJHIP *d = SD(A);
+  const PetscInt *pos; PetscBool full;
+  ierr = value_op_view(A);CHKERRQ(ierr);
+  a = SA(A);
+  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  if (a->bs > 1) {   /* BAIJ: the diagonal of every diagonal block (column-major blocks), on the host copy; the values travel at the next use */
+    const PetscInt bs = a->bs, bs2 = bs * bs;
+    for (PetscInt br = 0; br < a->m; br++) {
+      PetscInt k = a->i[br];
+      while (k < a->i[br + 1] && a->j[k] != br) k++;
+      if (k == a->i[br + 1]) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "block row %d has no diagonal block", br);
+    }
+    for (PetscInt br = 0; br < a->m; br++) {
+      PetscInt k = a->i[br];
+      while (a->j[k] != br) k++;
+      for (PetscInt q = 0; q < bs; q++) a->a[(size_t)k * bs2 + q * bs + q] = a->a[(size_t)k * bs2 + q * bs + q] + alpha;
+    }
+    d->uploaded_state = -1;
+    return PetscLogFlops((PetscLogDouble)a->m * bs);
+  }
+  ierr = shift_diag_positions(A, &pos, &full);CHKERRQ(ierr);
+  if (!full) {   /* the reference's default (axpy.c:185-192): new entries may appear -- today's pattern-change route */
+    PetscInt rs = A->rmap->rstart, re = A->rmap->rend;
+    for (PetscInt i = rs; i < re; i++) { ierr = MatSetValues(A, 1, &i, 1, &i, &alpha, ADD_VALUES);CHKERRQ(ierr); }
+    ierr = MatAssemblyBegin(A, MAT_FINAL_ASSEMBLY);CHKERRQ(ierr);
+    ierr = MatAssemblyEnd(A, MAT_FINAL_ASSEMBLY);CHKERRQ(ierr);
+    return PetscLogFlops((PetscLogDouble)a->m);
+  }
+  const PetscBool on_device = (PetscBool)(update_on_device(A) && device_values_current(A) && !d->cprow);
+  { ValUpd u = {a->a, pos, NULL, NULL, NULL, alpha, NULL};
+    HipParallelRanges(a->m, upd_shift, &u); }
+  if (on_device) {
+    PetscDeviceCtx *dc;
+    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+    ierr = device_values_changed(A);CHKERRQ(ierr);
+    CHKHIP(mi355x_csr_shift(dc->h, a->m, d->mat.i, d->mat.j, alpha, d->mat.a, NULL));
+  } else d->uploaded_state = -1;
+#if defined(PETSCHIPMI355X_WITH_PETSC)
+  HipStateIncrease(A);   /* MatShift of 3.3 leaves the state to the assembly of its default loop: what device_values_changed stamped is this bump */
+#endif
+  return PetscLogFlops((PetscLogDouble)a->m);
+}
+
+/* SAME_NONZERO_PATTERN claimed for X and Y: sizes and nz always, the arrays by one memcmp per pair of pattern uploads */
+static PetscErrorCode same_pattern(Mat Y, Mat X, const PetscInt *xcols, const PetscInt *ycols, PetscBool *same) {
+  HipAIJ *x = SA(X), *y = SA(Y); Mat_SeqAIJHIP *dy = SD(Y);
+  *same = PETSC_FALSE;
+  if (x->m != y->m || x->n != y->n || x->nz != y->nz) return 0;
+  if (X == Y) { *same = PETSC_TRUE; return 0; }
+  const unsigned long long gx = host_pattern_gen(X), gy = host_pattern_gen(Y);
+  if (!xcols && !ycols && gx && gy && dy->same_xgen == gx && dy->same_ygen == gy) { *same = PETSC_TRUE; return 0; }
+  if (memcmp(x->i, y->i, sizeof(PetscInt) * (size_t)(x->m + 1)) || memcmp(x->j, y->j, sizeof(PetscInt) * (size_t)x->nz)) return 0;
+  if ((xcols || ycols) && (!xcols || !ycols || memcmp(xcols, ycols, sizeof(PetscInt) * (size_t)(x->bs > 1 ? x->n / x->bs : x->n)))) return 0;
+  if (!xcols && !ycols && gx && gy) { dy->same_xgen = gx; dy->same_ygen = gy; }
+  *same = PETSC_TRUE;
+  return 0;
+}
+/* the map of a subset update of Y by X, kept with Y: on the host, and on the device when asked.  *bad_row >= 0: X has an entry in that
+ * row that Y lacks, no map */
+static PetscErrorCode subset_map_get(Mat Y, Mat X, const PetscInt *xcols, const PetscInt *ycols, PetscBool fresh, PetscBool want_dev, PetscInt *bad_row) {
+  PetscErrorCode ierr;
+  HipAIJ *x = SA(X), *y = SA(Y); Mat_SeqAIJHIP *dy = SD(Y);
+  const unsigned long long gx = host_pattern_gen(X), gy = host_pattern_gen(Y);
+  /* (the column translations of two off-diagonal blocks change only with their patterns, which then lose their serial numbers);
+   * fresh: the caller has just had the map built for this very pair (MatValueOpsCheck_SeqAIJHIP) and nothing happened since */
+  const PetscBool keyed = (PetscBool)(gx && gy && dy->xtoy_xgen == gx && dy->xtoy_ygen == gy);
+  *bad_row = -1;
+  if (!(dy->xtoy_h && dy->xtoy_from == (void *)X && dy->xtoy_nz == x->nz && (keyed || fresh))) {
+    PetscInt *map; int bad = -1;
+    HipFree(dy->xtoy_h); dy->xtoy_h = NULL;
+    if (dy->xtoy_d) mi355x_free(dy->xtoy_d);
+    dy->xtoy_d = NULL; dy->xtoy_xgen = dy->xtoy_ygen = 0; dy->xtoy_from = NULL;
+    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(x->nz, 1), &map);CHKERRQ(ierr);
+    const int rc = mi355x_csr_subset_map(x->m, x->i, x->j, xcols, y->i, y->j, ycols, map, &bad);
+    if (rc) {
+      HipFree(map);
+      if (bad < 0) CHKHIP(rc);
+      *bad_row = bad;
+      return 0;
+    }
+    dy->xtoy_h = map; dy->xtoy_nz = x->nz; dy->xtoy_from = (void *)X;
+    dy->xtoy_xgen = gx; dy->xtoy_ygen = gy;
+  }
+  if (want_dev && !dy->xtoy_d && x->nz > 0) {
+    PetscDeviceCtx *dc;
+    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+    CHKHIP(mi355x_malloc((void **)&dy->xtoy_d, sizeof(PetscInt) * (size_t)x->nz));
+    CHKHIP(mi355x_memcpy_h2d(dc->h, dy->xtoy_d, dy->xtoy_h, sizeof(PetscInt) * (size_t)x->nz));
+    CHKHIP(mi355x_handle_synchronize(dc->h));       /* once per map: the host array is pageable */
+  }
+  return 0;
+}
+static PetscErrorCode value_op_pair(Mat Y, Mat X, PetscBool cols) {   /* what MatAXPY and MatCopy ask of their two matrices */
+  PetscErrorCode ierr;
+  if (!X || !Y || X->ops->mult != MatMult_SeqAIJHIP || Y->ops->mult != MatMult_SeqAIJHIP) SETERRQ(Y ? HipObjComm(Y) : 0, PETSC_ERR_SUP, "both matrices must be sequential HIPMI355X matrices");
+  ierr = value_op_view(X);CHKERRQ(ierr);
+  ierr = value_op_view(Y);CHKERRQ(ierr);
+  HipAIJ *x = SA(X), *y = SA(Y);
+  if (!x->compact || !y->compact) SETERRQ(HipObjComm(Y), PETSC_ERR_ARG_WRONGSTATE, "both matrices must be assembled");
+  if (x->m != y->m || (!cols && x->n != y->n) || (x->bs > 1 ? x->bs : 1) != (y->bs > 1 ? y->bs : 1)) SETERRQ(HipObjComm(Y), PETSC_ERR_ARG_SIZ, "Non conforming matrices: %d x %d and %d x %d", x->m, x->n, y->m, y->n);
+  return 0;
+}
+/* Y's update by an AXPY (or a basic copy into it) runs on the device copy too */
+static PetscBool axpy_on_device(Mat Y) { return (PetscBool)(update_on_device(Y) && device_values_current(Y) && !SD(Y)->cprow); }
+/* the errors MatAXPY (copy: MatCopy) of this pair would return, with nothing changed.  When Y's device copy will take the update, a source
+ * that is not current is sent first (reading it is a use; its pattern upload keys the map); a map built here serves the call that follows
+ * (its `checked` argument) */
+PetscErrorCode MatValueOpsCheck_SeqAIJHIP(Mat Y, Mat X, MatStructure str, const PetscInt *xcols, const PetscInt *ycols, PetscBool copy) {
+  PetscErrorCode ierr;
+  PetscBool same = PETSC_FALSE; PetscInt bad;
+  ierr = value_op_pair(Y, X, (PetscBool)(xcols || ycols));CHKERRQ(ierr);
+  if (X != Y && axpy_on_device(Y)) { ierr = MatSeqAIJHIPUpload(X);CHKERRQ(ierr); }
+  if (str == SAME_NONZERO_PATTERN) {
+    ierr = same_pattern(Y, X, xcols, ycols, &same);CHKERRQ(ierr);
+    if (same) return 0;
+    if (!copy) SETERRQ(HipObjComm(Y), PETSC_ERR_ARG_WRONG, "SAME_NONZERO_PATTERN given, but the nonzero patterns of X and Y differ");
+  }
+  if (SA(Y)->bs > 1) SETERRQ(HipObjComm(Y), PETSC_ERR_SUP, "block matrices: SAME_NONZERO_PATTERN with equal patterns only");
+  ierr = subset_map_get(Y, X, xcols, ycols, PETSC_FALSE, PETSC_FALSE, &bad);CHKERRQ(ierr);
+  if (bad >= 0) {
+    if (str == DIFFERENT_NONZERO_PATTERN && !copy) SETERRQ(HipObjComm(Y), PETSC_ERR_SUP, "X has an entry in local row %d that Y lacks: an update that changes Y's nonzero pattern is not supported", bad);
+    SETERRQ(HipObjComm(Y), PETSC_ERR_ARG_WRONG, "the nonzero pattern of X is not a subset of Y's: X has an entry in local row %d that Y lacks", bad);
+  }
+  return 0;
+}
+/* ya[xtoy[k]] += alpha xa[k] on the host copy and, when Y's device copy is current, on the device; zero_first: Y's values zeroed before
+ * (MatCopy_Basic: MatZeroEntries, then every entry of the source set) */
+static PetscErrorCode axpy_subset(Mat Y, PetscScalar alpha, Mat X, const PetscInt *xcols, const PetscInt *ycols, PetscBool zero_first) {
+  PetscErrorCode ierr;
+  HipAIJ *x = SA(X), *y = SA(Y); Mat_SeqAIJHIP *dx = SD(X), *dy = SD(Y);
+  PetscInt bad;
+  if (zero_first) {   /* the existing operator; its stamp looks one state bump ahead */
+    ierr = MatZeroEntries_SeqAIJHIP(Y);CHKERRQ(ierr);
+    HipStateIncrease(Y);
+  }
+  const PetscBool on_device = axpy_on_device(Y);
+  if (on_device && X != Y) { ierr = MatSeqAIJHIPUpload(X);CHKERRQ(ierr); }   /* (the check has sent a source that was not current) */
+  ierr = subset_map_get(Y, X, xcols, ycols, PETSC_TRUE, on_device, &bad);CHKERRQ(ierr);
+  if (bad >= 0) SETERRQ(HipObjComm(Y), PETSC_ERR_ARG_WRONG, "the nonzero pattern of X is not a subset of Y's (local row %d)", bad);
+  { ValUpd u = {y->a, dy->xtoy_h, NULL, NULL, x->a, alpha, NULL};
+    HipParallelRanges(x->nz, upd_axpy_map, &u); }
+  if (on_device) {
+    PetscDeviceCtx *dc;
+    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+    ierr = device_values_changed(Y);CHKERRQ(ierr);
+    CHKHIP(mi355x_csr_axpy_map(dc->h, x->nz, dy->xtoy_d, alpha, dx->mat.a, dy->mat.a));
+  } else dy->uploaded_state = -1;
+  return 0;
+}
+PetscErrorCode MatAXPY_SeqAIJHIP_Cols(Mat Y, PetscScalar alpha, Mat X, MatStructure str, const PetscInt *xcols, const PetscInt *ycols, PetscBool checked) {
+  PetscErrorCode ierr;
+  if (!checked) { ierr = MatValueOpsCheck_SeqAIJHIP(Y, X, str, xcols, ycols, PETSC_FALSE);CHKERRQ(ierr); }
+  HipAIJ *x = SA(X), *y = SA(Y); Mat_SeqAIJHIP *dx = SD(X), *dy = SD(Y);
+  if (str == SAME_NONZERO_PATTERN) {   /* daxpy on the value arrays: alpha == 0 returns at once (so does mi355x_vec_axpy) */
+    const size_t vals = (size_t)y->nz * (size_t)(y->bs > 1 ? y->bs * y->bs : 1);
+    const PetscBool on_device = axpy_on_device(Y);
+    if (alpha == 0.0) {   /* nothing changes on either copy: a current device copy stays current over the wrapper's state bump */
+      if (device_values_current(Y)) dy->uploaded_state = HipObjState(Y) + 1;
+      return PetscLogFlops(2.0 * (PetscLogDouble)x->nz * (x->bs > 1 ? x->bs * x->bs : 1));
+    }
+    if (on_device && X != Y) { ierr = MatSeqAIJHIPUpload(X);CHKERRQ(ierr); }
+    { ValUpd u = {y->a, NULL, NULL, NULL, x->a, alpha, NULL};
+      HipParallelRanges((PetscInt)vals, upd_axpy, &u); }
+    if (on_device) {
+      PetscDeviceCtx *dc;
+      ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+      ierr = device_values_changed(Y);CHKERRQ(ierr);
+      CHKHIP(mi355x_vec_axpy(dc->h, vals, alpha, dx->mat.a, dy->mat.a));
+    } else dy->uploaded_state = -1;
+  } else {
+    ierr = axpy_subset(Y, alpha, X, xcols, ycols, PETSC_FALSE);CHKERRQ(ierr);
+  }
+  return PetscLogFlops(2.0 * (PetscLogDouble)x->nz * (x->bs > 1 ? x->bs * x->bs : 1));
+}
+static PetscErrorCode MatAXPY_SeqAIJHIP(Mat Y, PetscScalar alpha, Mat X, MatStructure str) {
+  PetscErrorCode ierr = MatAXPY_SeqAIJHIP_Cols(Y, alpha, X, str, NULL, NULL, PETSC_FALSE);CHKERRQ(ierr);
+#if defined(PETSCHIPMI355X_WITH_PETSC)
+  HipStateIncrease(Y);   /* MatAXPY of 3.3 (axpy.c:26-56) does not bump the state after the slot: what device_values_changed stamped is this bump */
+#endif
+  return 0;
+}
+PetscErrorCode MatCopy_SeqAIJHIP_Cols(Mat A, Mat B, MatStructure str, const PetscInt *acols, const PetscInt *bcols, PetscBool checked) {
+  PetscErrorCode ierr;
+  PetscBool same = PETSC_FALSE;
+  if (A == B) return 0;
+  if (!checked) { ierr = MatValueOpsCheck_SeqAIJHIP(B, A, str, acols, bcols, PETSC_TRUE);CHKERRQ(ierr); }
+  HipAIJ *a = SA(A), *b = SA(B); Mat_SeqAIJHIP *da = SD(A), *db = SD(B);
+  if (str == SAME_NONZERO_PATTERN) { ierr = same_pattern(B, A, acols, bcols, &same);CHKERRQ(ierr); }
+  if (!same) return axpy_subset(B, 1.0, A, acols, bcols, PETSC_TRUE);   /* any other structure: MatCopy_Basic */
+  const size_t vals = (size_t)a->nz * (size_t)(a->bs > 1 ? a->bs * a->bs : 1);
+  /* B's own values do not matter: its device arrays for this pattern do.  B becomes current when A is (A is sent first when it is not) */
+  const PetscBool on_device = (PetscBool)(update_on_device(B) && b->bs <= 1 && !da->cprow && !db->cprow && db->mat.a && db->mat.plan && host_pattern_gen(B));
+  if (on_device) { ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr); }
+  { ValUpd u = {b->a, NULL, NULL, NULL, a->a, 0.0, NULL};
+    HipParallelRanges((PetscInt)vals, upd_copy, &u); }
+  if (on_device) {
+    PetscDeviceCtx *dc;
+    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+    ierr = device_values_changed(B);CHKERRQ(ierr);
+    CHKHIP(mi355x_memcpy_d2d(dc->h, db->mat.a, da->mat.a, sizeof(PetscScalar) * vals));
+  } else db->uploaded_state = -1;
+  return 0;
+}
+static PetscErrorCode MatCopy_SeqAIJHIP(Mat A, Mat B, MatStructure str) { return MatCopy_SeqAIJHIP_Cols(A, B, str, NULL, NULL, PETSC_FALSE); }
+
 static PetscErrorCode MatGetVecs_HIP(Mat A, Vec *right, Vec *left) {   /* MatGetVecs_SeqAIJCUSP aijcusp.cu:324-345 */
   PetscErrorCode ierr;
   if (right) {
@@ -1208,6 +1477,9 @@ static PetscErrorCode create_common(Mat B, const char *tname, PetscInt bs) {
   B->ops->zeroentries = MatZeroEntries_SeqAIJHIP;
   B->ops->setup = MatSetUp_SeqAIJHIP;
   B->ops->scale = MatScale_SeqAIJHIP;
+  B->ops->shift = MatShift_SeqAIJHIP;
+  B->ops->axpy = MatAXPY_SeqAIJHIP;
+  B->ops->copy = MatCopy_SeqAIJHIP;
   B->ops->diagonalscale = MatDiagonalScale_SeqAIJHIP;
   B->ops->setvaluesbatch = MatSetValuesBatch_SeqAIJHIP;
   B->ops->duplicate = MatDuplicate_SeqAIJHIP;

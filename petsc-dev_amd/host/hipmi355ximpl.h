@@ -240,6 +240,14 @@ typedef struct {
   /* the blocked companion of an AIJ matrix whose nodes are complete bs x bs blocks (3-dof FEM matrices): BCSR arrays multiplied by the
    * BAIJ row-block kernel (host/aijhip.c, "blocked companion"), and its block transpose, for the transpose products */
   HipDevForm b, tb;
+  /* MatShift / MatAXPY / MatCopy with an unchanged pattern (host/aijhip.c, "MatShift, MatAXPY and MatCopy"): the position of every row's
+   * diagonal entry (host; sh_full: every row has one), kept for the pattern upload sh_gen; the map of a SUBSET_NONZERO_PATTERN update
+   * into this matrix, xtoy[k] = position in this matrix of entry k of X (host and device), kept for the pair of pattern uploads
+   * (xtoy_xgen of X, xtoy_ygen of this matrix; 0: built for one call -- a matrix never sent to the device has no serial number, and
+   * its map is built again by every update); the pair a same-pattern claim was last verified for */
+  PetscInt *sh_diag; PetscBool sh_full; unsigned long long sh_gen;
+  PetscInt *xtoy_h, *xtoy_d, xtoy_nz; unsigned long long xtoy_xgen, xtoy_ygen; void *xtoy_from;
+  unsigned long long same_xgen, same_ygen;
   PetscInt opt[8]; PetscBool opt_set[8];   /* the type's options as MatSetFromOptions read them under the matrix's prefix (host/aijhip.c) */
   /* per-launch device timing for bench.py (hipEvent pairs on the compute stream) */
   PetscBool timing; PetscInt time_n, time_cap; mi355x_event_t *time_ev;
@@ -287,6 +295,12 @@ PetscErrorCode MatCreate_SeqBAIJHIPMI355X(Mat);
 PetscErrorCode MatSeqAIJHIPUpload(Mat A);
 PetscErrorCode MatSeqAIJHIPGetInodes(Mat A, PetscInt *count, const PetscInt **sizes);
 PetscErrorCode MatSeqAIJHIPSetCompressedRow(Mat A, PetscBool flg);
+/* Y += a X and B <- A between sequential matrices of this type whose columns are numbered through xcols / ycols (NULL: as stored; the
+ * off-diagonal blocks of two MPIAIJ matrices, each compacted through its own garray); ...Check: the errors these would return, nothing
+ * changed; checked: the caller has just made that check for this pair and nothing happened since */
+PetscErrorCode MatAXPY_SeqAIJHIP_Cols(Mat Y, PetscScalar a, Mat X, MatStructure str, const PetscInt *xcols, const PetscInt *ycols, PetscBool checked);
+PetscErrorCode MatCopy_SeqAIJHIP_Cols(Mat A, Mat B, MatStructure str, const PetscInt *acols, const PetscInt *bcols, PetscBool checked);
+PetscErrorCode MatValueOpsCheck_SeqAIJHIP(Mat Y, Mat X, MatStructure str, const PetscInt *xcols, const PetscInt *ycols, PetscBool copy);
 PetscErrorCode MatSetUpMultiply_MPIAIJ(Mat mat);
 PetscErrorCode MatTimingBegin(Mat A, mi355x_handle_t h);
 PetscErrorCode MatTimingEnd(Mat A, mi355x_handle_t h);

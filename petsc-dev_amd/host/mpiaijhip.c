@@ -235,6 +235,60 @@ static PetscErrorCode MatZeroEntries_MPIAIJHIP(Mat A) {
   ierr = MatZeroEntries(MA(A)->B);CHKERRQ(ierr);
   return 0;
 }
+/* MatShift / MatAXPY / MatCopy (axpy.c:170, mpiaij.c:2470-2520 MatAXPY_MPIAIJ, 2290-2310 MatCopy_MPIAIJ): through the blocks, whose own
+ * operators keep host and device copies side by side (host/aijhip.c).  The blocks' states are bumped here, as the public wrappers
+ * would.  The off-diagonal blocks number their columns through each matrix's own garray. */
+static PetscErrorCode MatShift_MPIAIJHIP(Mat A, PetscScalar alpha) {
+  PetscErrorCode ierr;
+  HipMPIAIJ *a = MA(A);
+  if (a->A && a->A->ops->shift && A->rmap->rstart == A->cmap->rstart && A->rmap->rend == A->cmap->rend) {   /* the diagonal lies in the diagonal block */
+    ierr = (*a->A->ops->shift)(a->A, alpha);CHKERRQ(ierr);
+#if !defined(PETSCHIPMI355X_WITH_PETSC)   /* (inside a PETSc tree the block's own operator bumps its state: MatShift of 3.3 does not) */
+    HipStateIncrease(a->A);
+#endif
+    return 0;
+  }
+  for (PetscInt i = A->rmap->rstart; i < A->rmap->rend; i++) { ierr = MatSetValues(A, 1, &i, 1, &i, &alpha, ADD_VALUES);CHKERRQ(ierr); }   /* the reference's default */
+  ierr = MatAssemblyBegin(A, MAT_FINAL_ASSEMBLY);CHKERRQ(ierr);
+  ierr = MatAssemblyEnd(A, MAT_FINAL_ASSEMBLY);CHKERRQ(ierr);
+  return 0;
+}
+static PetscErrorCode mpi_value_op_pair(Mat Y, Mat X) {
+  if (!X || strcmp(HipObjTypeName(X), MATMPIAIJHIPMI355X) || strcmp(HipObjTypeName(Y), MATMPIAIJHIPMI355X)) SETERRQ(HipObjComm(Y), PETSC_ERR_SUP, "both matrices must be MPIAIJHIPMI355X matrices");
+  if (X->rmap->rstart != Y->rmap->rstart || X->rmap->rend != Y->rmap->rend || X->cmap->rstart != Y->cmap->rstart || X->cmap->rend != Y->cmap->rend)
+    SETERRQ(HipObjComm(Y), PETSC_ERR_ARG_SIZ, "the two matrices must have the same row and column layouts");
+  if (!MA(X)->A || !MA(Y)->A || !MA(X)->garray || !MA(Y)->garray) SETERRQ(HipObjComm(Y), PETSC_ERR_ARG_WRONGSTATE, "both matrices must be assembled");
+  return 0;
+}
+static PetscErrorCode MatAXPY_MPIAIJHIP(Mat Y, PetscScalar alpha, Mat X, MatStructure str) {
+  PetscErrorCode ierr;
+  ierr = mpi_value_op_pair(Y, X);CHKERRQ(ierr);
+  HipMPIAIJ *x = MA(X), *y = MA(Y);
+  /* both blocks are checked before either is changed: an error leaves Y as it was */
+  ierr = MatValueOpsCheck_SeqAIJHIP(y->A, x->A, str, NULL, NULL, PETSC_FALSE);CHKERRQ(ierr);
+  ierr = MatValueOpsCheck_SeqAIJHIP(y->B, x->B, str, x->garray, y->garray, PETSC_FALSE);CHKERRQ(ierr);
+  ierr = MatAXPY_SeqAIJHIP_Cols(y->A, alpha, x->A, str, NULL, NULL, PETSC_TRUE);CHKERRQ(ierr);
+  HipStateIncrease(y->A);
+  ierr = MatAXPY_SeqAIJHIP_Cols(y->B, alpha, x->B, str, x->garray, y->garray, PETSC_TRUE);CHKERRQ(ierr);
+  HipStateIncrease(y->B);
+#if defined(PETSCHIPMI355X_WITH_PETSC)
+  HipStateIncrease(Y);
+#endif
+  return 0;
+}
+static PetscErrorCode MatCopy_MPIAIJHIP(Mat A, Mat B, MatStructure str) {
+  PetscErrorCode ierr;
+  if (A == B) return 0;
+  ierr = mpi_value_op_pair(B, A);CHKERRQ(ierr);
+  HipMPIAIJ *a = MA(A), *b = MA(B);
+  ierr = MatValueOpsCheck_SeqAIJHIP(b->A, a->A, str, NULL, NULL, PETSC_TRUE);CHKERRQ(ierr);
+  ierr = MatValueOpsCheck_SeqAIJHIP(b->B, a->B, str, a->garray, b->garray, PETSC_TRUE);CHKERRQ(ierr);
+  ierr = MatCopy_SeqAIJHIP_Cols(a->A, b->A, str, NULL, NULL, PETSC_TRUE);CHKERRQ(ierr);
+  HipStateIncrease(b->A);
+  ierr = MatCopy_SeqAIJHIP_Cols(a->B, b->B, str, a->garray, b->garray, PETSC_TRUE);CHKERRQ(ierr);
+  HipStateIncrease(b->B);
+  return 0;
+}
 #if defined(PETSCHIPMI355X_WITH_PETSC)
 #include "mpiaijhipmi355x_ctor.h"   /* integration/petsc-3.3/: the constructor as a subclass of the reference's MATMPIAIJ */
 #else
@@ -273,6 +327,9 @@ PetscErrorCode MatCreate_MPIAIJHIPMI355X(Mat B) {   /* MatCreate_MPIAIJCUSP, mpi
   B->ops->zeroentries = MatZeroEntries_MPIAIJHIP;
   B->ops->setup = MatSetUp_MPIAIJHIP;
   B->ops->scale = MatScale_MPIAIJHIP;
+  B->ops->shift = MatShift_MPIAIJHIP;
+  B->ops->axpy = MatAXPY_MPIAIJHIP;
+  B->ops->copy = MatCopy_MPIAIJHIP;
   B->ops->diagonalscale = MatDiagonalScale_MPIAIJHIP;
   B->ops->destroy = MatDestroy_MPIAIJHIP;
   B->ops->getvecs = MatGetVecs_HIPMI355X;

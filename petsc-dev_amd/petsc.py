@@ -45,6 +45,7 @@ _SIG = {
     "MatGetOwnershipRange": [vp, P(i32), P(i32)], "MatGetVecs": [vp, P(vp), P(vp)],
     "MatDuplicate": [vp, i32, P(vp)], "MatSetOptionsPrefix": [vp, C.c_char_p], "MatDiagonalScale": [vp, vp, vp], "MatSetValuesBatch": [vp, i32, i32, vp, vp], "MatMult": [vp, vp, vp], "MatMultAdd": [vp, vp, vp, vp], "MatMultTranspose": [vp, vp, vp],
     "MatMultTransposeAdd": [vp, vp, vp, vp], "MatGetDiagonal": [vp, vp], "MatScale": [vp, dbl], "MatZeroEntries": [vp],
+    "MatShift": [vp, dbl], "MatAXPY": [vp, dbl, vp, i32], "MatAYPX": [vp, dbl, vp, i32], "MatCopy": [vp, vp, i32],
     "MatSeqAIJGetArrays": [vp, P(i32), P(vp), P(vp), P(vp)], "MatMPIAIJGetSeqAIJ": [vp, P(vp), P(vp), P(vp)],
     "MatMPIAIJGetScatter": [vp, P(vp), P(vp), P(i32)],
     "MatHIPMI355XSetTiming": [vp, i32], "MatHIPMI355XGetTiming": [vp, P(i32), P(dbl)],
@@ -73,6 +74,7 @@ SCATTER_FORWARD, SCATTER_REVERSE = 0, 1
 NORM_1, NORM_2, NORM_FROBENIUS, NORM_INFINITY, NORM_1_AND_2 = 0, 1, 2, 3, 4
 MAT_FINAL_ASSEMBLY, MAT_FLUSH_ASSEMBLY = 0, 1
 PETSC_DECIDE, PETSC_DEFAULT = -1, -2
+DIFFERENT_NONZERO_PATTERN, SUBSET_NONZERO_PATTERN, SAME_NONZERO_PATTERN = 0, 1, 2
 
 
 class PetscError(RuntimeError):
@@ -256,6 +258,18 @@ class Mat:
 
     def mult(self, x, y):
         lib().MatMult(self.h, x.h, y.h)
+
+    def shift(self, alpha):
+        """a(i,i) += alpha for every local row (MatShift)"""
+        lib().MatShift(self.h, alpha)
+
+    def axpy(self, alpha, X, structure=SAME_NONZERO_PATTERN):
+        """self += alpha X (MatAXPY)"""
+        lib().MatAXPY(self.h, alpha, X.h, structure)
+
+    def copy(self, B, structure=SAME_NONZERO_PATTERN):
+        """B <- self (MatCopy)"""
+        lib().MatCopy(self.h, B.h, structure)
 
     def local_size(self):
         m, n = i32(), i32()
