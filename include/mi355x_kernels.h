@@ -265,6 +265,18 @@ int mi355x_csr_get_diagonal(mi355x_handle_t h, int m, const int *ai, const int *
  * search of mi355x_csr_get_diagonal).  A row without a diagonal entry is not touched; nmissing_dev (device, may be NULL) receives
  * the number of such rows. */
 int mi355x_csr_shift(mi355x_handle_t h, int m, const int *ai, const int *aj, double alpha, double *aa, int *nmissing_dev);
+/* MatZeroRows_SeqAIJ with MAT_KEEP_NONZERO_PATTERN  aij.c   rows[nrows] (device; duplicates allowed, every row in [0, m)): every stored
+ * entry of a listed row is stored as +0.0, its diagonal entry as diag when diag != 0 (-0.0 counts as zero); each entry is written once.
+ * x and b (device, both or neither): b[row] = diag * x[row].  nrows <= 0: nothing is launched. */
+int mi355x_csr_zero_rows(mi355x_handle_t h, int nrows, const int *rows, const int *ai, const int *aj, double *aa, double diag,
+                         const double *x, double *b);
+/* The column half of MatZeroRowsColumns_SeqAIJ  aij.c   on a square matrix through its row-block plan (not a compressed-row plan:
+ * hipErrorNotSupported).  mask (device): one bit per row = column, bit (c & 31) of word c >> 5, (m + 31) / 32 words, set for the
+ * listed ones.  For every row i whose bit is clear, in stored column order, every entry whose column's bit is set: b[i] = b[i] - a_ij *
+ * x[col] (two roundings; x and b both or neither), then a_ij = +0.0.  Rows whose bit is set are not touched (mi355x_csr_zero_rows owns
+ * them); a row block without such an entry reads its column indices and nothing else.  aj with 16 bytes of slack as for mi355x_spmv_csr. */
+int mi355x_csr_zero_columns(mi355x_handle_t h, mi355x_spmv_plan_t plan, const int *ai, const int *aj, double *aa, const unsigned int *mask,
+                            const double *x, double *b);
 /* MatAXPY_SeqAIJ with SUBSET_NONZERO_PATTERN  aij.c:2621   ya[xtoy[k]] = ya[xtoy[k]] + alpha * xa[k], k < nzx, two roundings;
  * xtoy injective (no atomics); alpha == 0 does the arithmetic too (the same-pattern form, mi355x_vec_axpy on the value arrays,
  * returns at once as daxpy does); same-pattern MatCopy is mi355x_memcpy_d2d.  xa may be ya with the identity map. */

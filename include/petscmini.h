@@ -61,6 +61,13 @@ typedef enum { NORM_1 = 0, NORM_2 = 1, NORM_FROBENIUS = 2, NORM_INFINITY = 3, NO
 typedef enum { MAT_FLUSH_ASSEMBLY = 1, MAT_FINAL_ASSEMBLY = 0 } MatAssemblyType;               /* petscmat.h:347 */
 typedef enum { MAT_DO_NOT_COPY_VALUES, MAT_COPY_VALUES, MAT_SHARE_NONZERO_PATTERN } MatDuplicateOption;   /* petscmat.h:440 */
 typedef enum { DIFFERENT_NONZERO_PATTERN, SUBSET_NONZERO_PATTERN, SAME_NONZERO_PATTERN, SAME_PRECONDITIONER } MatStructure;
+/* MatSetOption (include/petscmat.h, the list of 3.3 in its order).  The HIPMI355X types act on MAT_KEEP_NONZERO_PATTERN (MatZeroRows);
+ * the others are accepted and have no effect here */
+typedef enum { MAT_ROW_ORIENTED, MAT_NEW_NONZERO_LOCATIONS, MAT_SYMMETRIC, MAT_STRUCTURALLY_SYMMETRIC, MAT_NEW_DIAGONALS,
+               MAT_IGNORE_OFF_PROC_ENTRIES, MAT_NEW_NONZERO_LOCATION_ERR, MAT_NEW_NONZERO_ALLOCATION_ERR, MAT_USE_HASH_TABLE,
+               MAT_KEEP_NONZERO_PATTERN, MAT_IGNORE_ZERO_ENTRIES, MAT_USE_INODES, MAT_HERMITIAN, MAT_SYMMETRY_ETERNAL,
+               MAT_CHECK_COMPRESSED_ROW, MAT_IGNORE_LOWER_TRIANGULAR, MAT_ERROR_LOWER_TRIANGULAR, MAT_GETROW_UPPERTRIANGULAR,
+               MAT_UNUSED_NONZERO_LOCATION_ERR, MAT_SPD, MAT_NO_OFF_PROC_ENTRIES, MAT_NO_OFF_PROC_ZERO_ROWS, NUM_MAT_OPTIONS } MatOption;
 /* matrix factorisation interface (include/petscmat.h:100-131,1042-1088): the factored matrix is a Mat of its own, obtained from the
  * operator with MatGetFactor, filled by a symbolic and a numeric call, applied with MatSolve */
 typedef enum { MAT_FACTOR_NONE, MAT_FACTOR_LU, MAT_FACTOR_CHOLESKY, MAT_FACTOR_ILU, MAT_FACTOR_ICC, MAT_FACTOR_ILUDT } MatFactorType;
@@ -260,6 +267,14 @@ PetscErrorCode MatShift(Mat Y, PetscScalar a);                           /* Y +=
 PetscErrorCode MatAXPY(Mat Y, PetscScalar a, Mat X, MatStructure str);   /* Y += a X; X's pattern must lie inside Y's */
 PetscErrorCode MatAYPX(Mat Y, PetscScalar a, Mat X, MatStructure str);   /* Y = a Y + X */
 PetscErrorCode MatCopy(Mat A, Mat B, MatStructure str);                  /* B <- A */
+/* Dirichlet rows (matrix.c MatZeroRows / MatZeroRowsColumns; aij.c, mpiaij.c): the listed rows -- local indices on a sequential matrix,
+ * global ones owned by any rank on a parallel one, where the call is collective -- are zeroed and get diag on the diagonal (diag != 0);
+ * MatZeroRowsColumns zeroes the listed columns too and keeps a symmetric operator symmetric.  x and b, both or neither:
+ * b[r] = diag * x[r] on the listed rows, and (columns) b[i] -= a_ij x[j] for every eliminated entry.  MatZeroRows removes the rows' entries
+ * from the nonzero pattern unless MatSetOption(A, MAT_KEEP_NONZERO_PATTERN, PETSC_TRUE) was given; MatZeroRowsColumns always keeps it */
+PetscErrorCode MatZeroRows(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, Vec x, Vec b);
+PetscErrorCode MatZeroRowsColumns(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, Vec x, Vec b);
+PetscErrorCode MatSetOption(Mat A, MatOption op, PetscBool flg);
 PetscErrorCode MatSetOptionsPrefix(Mat A, const char prefix[]);
 /* matrix.c:3937-4010 (MatGetFactor looks "MatGetFactor_<package>_C" up on the operator), 2766-3144 (symbolic / numeric), 3196 (MatSolve) */
 PetscErrorCode MatFactorInfoInitialize(MatFactorInfo *info);

@@ -11,6 +11,7 @@
 typedef struct {                      /* the parent's routines this type calls through (saved from the table MatCreate_SeqAIJ filled) */
   PetscErrorCode (*assemblyend)(Mat, MatAssemblyType);
   PetscErrorCode (*destroy)(Mat);
+  PetscErrorCode (*zerorows)(Mat, PetscInt, const PetscInt[], PetscScalar, Vec, Vec);
 } HipAIJParentOps;
 static HipAIJParentOps seqaij_parent;
 
@@ -60,6 +61,21 @@ static PetscErrorCode MatAssemblyEnd_SeqAIJHIPMI355X(Mat A, MatAssemblyType mode
   PetscFunctionReturn(0);
 }
 
+/* MAT_KEEP_NONZERO_PATTERN lives with the host matrix: the parent's member, set by the parent's ops->setoption (MatSetOption_SeqAIJ, left
+ * in place) and copied by MatDuplicate_SeqAIJ */
+static PetscBool keep_nonzero_pattern(Mat A) { return SD(A)->baij_parent ? PETSC_FALSE : ((Mat_SeqAIJ *)A->data)->keepnonzeropattern; }
+/* MatZeroRows without that option changes the pattern: the parent's routine on the parent's container (it ends in MatAssemblyEnd_SeqAIJ),
+ * then the view of its arrays again and a device copy that is built again at the next use */
+static PetscErrorCode zero_rows_new_pattern(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, Vec xx, Vec bb) {
+  PetscErrorCode ierr;
+  PetscFunctionBegin;
+  if (SD(A)->baij_parent) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "MatZeroRows on scalar rows of a block matrix");
+  ierr = device_free(A);CHKERRQ(ierr);
+  ierr = (*seqaij_parent.zerorows)(A, n, rows, diag, xx, bb);CHKERRQ(ierr);
+  ierr = hipaij_refresh_view(A);CHKERRQ(ierr);
+  PetscFunctionReturn(0);
+}
+
 static PetscErrorCode MatDestroy_SeqAIJHIPMI355X(Mat A) {   /* MatDestroy_SeqAIJCUSP, aijcusp.cu:575-590: mirror first, spptr zeroed, then the parent */
   PetscErrorCode ierr;
   PetscFunctionBegin;
@@ -86,6 +102,7 @@ PetscErrorCode MatCreate_SeqAIJHIPMI355X(Mat B) {
   aij->inode.use = PETSC_FALSE;                    /* this type runs its own Mat_CheckInode (seqaij_check_inode) and keeps ops->mult */
   seqaij_parent.assemblyend = B->ops->assemblyend;
   seqaij_parent.destroy = B->ops->destroy;
+  seqaij_parent.zerorows = B->ops->zerorows;
   ierr = PetscNewLog(B, Mat_SeqAIJHIP, &d);CHKERRQ(ierr);
   mirror_reset(d);
   B->spptr = d;
@@ -100,6 +117,9 @@ PetscErrorCode MatCreate_SeqAIJHIPMI355X(Mat B) {
   B->ops->shift            = MatShift_SeqAIJHIP;          /* MatShift / MatAXPY / MatCopy with an unchanged pattern: the same model */
   B->ops->axpy             = MatAXPY_SeqAIJHIP;
   B->ops->copy             = MatCopy_SeqAIJHIP;
+  B->ops->zerorows         = MatZeroRows_SeqAIJHIP;       /* with MAT_KEEP_NONZERO_PATTERN the same model; without it the parent's routine (saved above) */
+  B->ops->zerorowscolumns  = MatZeroRowsColumns_SeqAIJHIP; /* always keeps the pattern */
+  /* ops->setoption stays MatSetOption_SeqAIJ: MAT_KEEP_NONZERO_PATTERN is the parent's keepnonzeropattern, read by keep_nonzero_pattern() */
   B->ops->setvaluesbatch   = MatSetValuesBatch_SeqAIJHIP;
   B->ops->setfromoptions   = MatSetFromOptions_SeqAIJHIP;  /* the type's -mat_hipmi355x_* options under the matrix's prefix (slot 76); MatSetFromOptions_SeqAIJ has none of its own in 3.3 */
   /* ops->duplicate stays MatDuplicate_SeqAIJ (aij.c:3964): it creates the new matrix with MatSetType(type_name), i.e. through THIS

@@ -89,6 +89,9 @@ PetscErrorCode MatCreate_MPIAIJHIPMI355X(Mat B) {
   B->ops->shift            = MatShift_MPIAIJHIP;           /* through the blocks: host and device copies side by side */
   B->ops->axpy             = MatAXPY_MPIAIJHIP;
   B->ops->copy             = MatCopy_MPIAIJHIP;
+  B->ops->zerorows         = MatZeroRows_MPIAIJHIP;        /* the owners' rows through both blocks' zerorows slots */
+  B->ops->zerorowscolumns  = MatZeroRowsColumns_MPIAIJHIP; /* PETSC_ERR_SUP: the mask and x are not carried through the halo scatter yet */
+  /* ops->setoption stays MatSetOption_MPIAIJ: it hands MAT_KEEP_NONZERO_PATTERN to both blocks */
   B->ops->assemblyend      = MatAssemblyEnd_MPIAIJHIPMI355X;
   B->ops->destroy          = MatDestroy_MPIAIJHIPMI355X;
   B->ops->getvecs          = MatGetVecs_HIPMI355X;

@@ -128,6 +128,8 @@ KERNEL_API = {
     "mi355x_csr_assemble": [vp, i32, vp, vp, vp, vp, vp],
     "mi355x_csr_shift": [vp, i32, vp, vp, dbl, vp, vp],
     "mi355x_csr_axpy_map": [vp, i32, vp, dbl, vp, vp],
+    "mi355x_csr_zero_rows": [vp, i32, vp, vp, vp, vp, dbl, vp, vp],
+    "mi355x_csr_zero_columns": [vp, vp, vp, vp, vp, vp, vp, vp],
     "mi355x_csr_subset_map": [i32, vp, vp, vp, vp, vp, vp, vp, pi32],
     "mi355x_spmv_bsr": [vp, i32, i32, vp, vp, vp, vp, vp],
     "mi355x_spmv_bsr_planned": [vp, vp, i32, vp, vp, vp, vp, vp],

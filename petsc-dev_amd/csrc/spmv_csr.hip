@@ -801,6 +801,138 @@ __global__ __launch_bounds__(MI355X_BLOCK) void csr_axpy_map_kernel(int nzx, con
   ya[t] = ya[t] + alpha * xa[k];
 }
 
+// MatZeroRows_SeqAIJ with the pattern kept (aij.c): every stored entry of a listed row becomes +0.0 -- a store, so whatever was there is
+// gone -- and the diagonal entry becomes diag when diag != 0 (-0.0 counts as zero, NaN does not).  Each entry is written exactly once with
+// its final value: there is no zeroing pass and diagonal pass to order.  A group of ZR_GROUP lanes per listed row loops over the row;
+// the group's first lane writes b[row] = diag * x[row].  A row listed twice is written twice with the same values.
+// ZR_GROUP = 16: the rows this serves (boundary rows of stencil and FEM matrices) hold 5 to ~80 entries, so a group needs one to a few
+// steps, and one step of a group covers one 128-byte line of the value array; a wavefront per row would idle three quarters of its
+// lanes on a 7-point row, a lane per row would write 8 bytes per line touched.
+#define ZR_GROUP 16
+static_assert(MI355X_BLOCK % ZR_GROUP == 0 && MI355X_WAVE % ZR_GROUP == 0, "whole groups per wavefront");
+__global__ __launch_bounds__(MI355X_BLOCK) void csr_zero_rows_kernel(int nrows, const int *__restrict__ rows, const int *__restrict__ ai,
+                                                                    const int *__restrict__ aj, double *aa, double diag,
+                                                                    const double *__restrict__ x, double *b) {
+  const long t = (long)blockIdx.x * MI355X_BLOCK + threadIdx.x;
+  const long g = t / ZR_GROUP;
+  const int sub = (int)(t % ZR_GROUP);
+  if (g >= nrows) return;
+  const int row = rows[g];
+  const bool set = diag != 0.0;
+  const int end = ai[row + 1];
+  for (int k = ai[row] + sub; k < end; k += ZR_GROUP) aa[k] = (set && aj[k] == row) ? diag : 0.0;
+  if (sub == 0 && b) b[row] = diag * x[row];
+}
+
+// The column half of MatZeroRowsColumns_SeqAIJ (aij.c): in every row i that is NOT listed, an entry whose column is listed gives
+// b[i] = b[i] - a_ij * x[col] (product and difference rounded separately, in stored column order) and becomes +0.0.  Listed rows and
+// columns are the same set (square matrix), kept as a bitmap on the device: one bit per column, 2 MiB for 16.8 M columns, so the
+// gathers of a sweep stay in the L2 where a byte map (16 MiB) or the list itself (a search per entry) would not.
+// The matrix's own row-block plan: a workgroup sweeps its block's column indices with the family's unconditional pair loads and tests
+// the bitmap.  A block without a hit -- almost every block when the listed rows are a boundary -- leaves after that sweep: it has read
+// its indices and a few bitmap words, never a, x or b, and has written nothing.  In a block with hits the sweeping lane parks
+// a_ij * x[col] in the entry's LDS slot and marks the slot; after one barrier lane r, owner of row r as in the SpMV family, walks its
+// row's slots in column order, subtracts the parked products from b[r] one after the other -- the reference's bits -- and stores the
+// +0.0 (the owner knows whether its row is listed; the sweeping lane does not know the entry's row).  No atomics anywhere; rows of a
+// block belong to one workgroup, so b[r] has one writer.  Listed rows are left to csr_zero_rows_kernel.
+__device__ __forceinline__ bool zc_listed(const unsigned *__restrict__ mask, int c) { return (mask[c >> 5] >> (c & 31)) & 1u; }
+#define ZC_PER_LANE (SPMV_BLOCK_NNZ / SPMV_THREADS)
+// entry e of lane tid in the chunk [c0, c1) of the stream: the halves of the lane's pairs (VEC), else a stride of the workgroup's width
+template <bool VEC> __device__ __forceinline__ int zc_entry_k(int c0, int tid, int e) {
+  return VEC ? pair_k(c0, tid, e >> 1) + (e & 1) : c0 + tid + e * SPMV_THREADS;
+}
+// Sweep of one chunk of at most SPMV_BLOCK_NNZ entries (VEC: at most SPMV_BLOCK_CAP, any alignment of the first pair).  Returns false on
+// every lane when no entry of the chunk has a listed column.  Otherwise hit[k - c0] says whether entry k has, prod[k - c0] holds
+// a_k * x[col] for those (x given), and with zero_now the entries hit are already +0.0.  Every lane of the workgroup must call it: one
+// voting barrier, and one more when there is a hit.
+template <bool VEC>
+__device__ __forceinline__ bool zc_sweep(const int *__restrict__ aj, double *aa, const unsigned *__restrict__ mask, const double *__restrict__ x,
+                                         int c0, int c1, int tid, double *prod, unsigned char *hit, bool zero_now) {
+  int col[ZC_PER_LANE];
+  if (VEC) {
+#pragma unroll
+    for (int p = 0; p < SPMV_PAIRS; ++p) {
+      const v2i c = load_pair<v2i>(aj, c0, c1, pair_k(c0, tid, p));
+      const pair_src s = pair_source(pair_k(c0, tid, p), c0, c1);   // a half outside the chunk takes a column of the chunk: no gather is predicated
+      col[2 * p] = s.s0 ? c.y : c.x;
+      col[2 * p + 1] = s.s1 ? c.y : c.x;
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < ZC_PER_LANE; ++e) { const int k = zc_entry_k<false>(c0, tid, e); col[e] = SPMV_LOAD(aj + (k < c1 ? k : c0)); }
+  }
+  unsigned h = 0;
+#pragma unroll
+  for (int e = 0; e < ZC_PER_LANE; ++e) {
+    const int k = zc_entry_k<VEC>(c0, tid, e);
+    const bool listed = zc_listed(mask, col[e]);
+    if (k >= c0 && k < c1 && listed) h |= 1u << e;
+  }
+  if (!__syncthreads_or(h != 0)) return false;
+#pragma unroll
+  for (int e = 0; e < ZC_PER_LANE; ++e) {
+    const int k = zc_entry_k<VEC>(c0, tid, e);
+    if (k >= c0 && k < c1) {
+      const bool is = (h >> e) & 1u;
+      hit[k - c0] = is;
+      if (is) {
+        if (x) prod[k - c0] = aa[k] * x[col[e]];
+        if (zero_now) aa[k] = 0.0;
+      }
+    }
+  }
+  __syncthreads();
+  return true;
+}
+template <bool VEC>
+__global__ __launch_bounds__(SPMV_THREADS) void csr_zero_columns_kernel(const int2 *__restrict__ rowblk, int nblocks, const int *__restrict__ ai,
+                                                                       const int *__restrict__ aj, double *aa, const unsigned *__restrict__ mask,
+                                                                       const double *__restrict__ x, double *b) {
+  __shared__ double prod[SPMV_BLOCK_NNZ];
+  __shared__ unsigned char hit[SPMV_BLOCK_NNZ];
+  const int lb = rowblock_of_workgroup(SPMV_CH);
+  if (lb >= nblocks) return;
+  const int2 b0 = rowblk[lb];
+  const int2 b1 = rowblk[lb + 1];
+  const int r0 = b0.x, nrows = b1.x - b0.x, k0 = b0.y, k1 = b1.y;
+  const int tid = threadIdx.x;
+  if (k1 == k0) return;
+  if (k1 - k0 > SPMV_BLOCK_CAP) {
+    // one long row, a stage at a time (every branch here is taken by the whole workgroup).  The row is not listed, so the sweeping
+    // lanes store the +0.0 themselves; lane 0 carries b[r0] through the stages
+    if (zc_listed(mask, r0)) return;
+    double bv = 0.0;
+    bool touched = false;
+    for (int c0 = k0; c0 < k1; c0 += SPMV_BLOCK_NNZ) {
+      const int c1 = c0 + SPMV_BLOCK_NNZ < k1 ? c0 + SPMV_BLOCK_NNZ : k1;
+      if (!zc_sweep<false>(aj, aa, mask, x, c0, c1, tid, prod, hit, true)) continue;
+      if (tid == 0 && b) {
+        if (!touched) { bv = b[r0]; touched = true; }
+        for (int k = 0; k < c1 - c0; ++k) if (hit[k]) bv = bv - prod[k];
+      }
+      __syncthreads();   // the next stage overwrites the slots
+    }
+    if (tid == 0 && touched) b[r0] = bv;
+    return;
+  }
+  if (!zc_sweep<VEC>(aj, aa, mask, x, k0, k1, tid, prod, hit, false)) return;
+  if (tid < nrows && !zc_listed(mask, r0 + tid)) {
+    const int r = r0 + tid;
+    const int rs = ai[r] - k0, re = ai[r + 1] - k0;
+    double bv = 0.0;
+    bool touched = false;
+    for (int k = rs; k < re; ++k) {
+      if (!hit[k]) continue;
+      if (b) {
+        if (!touched) { bv = b[r]; touched = true; }
+        bv = bv - prod[k];
+      }
+      aa[k0 + k] = 0.0;
+    }
+    if (touched) b[r] = bv;
+  }
+}
+
 // Which kernel a plan runs with these arrays: the one decision behind mi355x_spmv_csr / _add / _scaled, mi355x_spmv_csr_dot
 // and mi355x_spmv_plan_dot_available (CG relies on y carrying the same bits from the first two).  In order of precedence;
 // the compressed forms need whole rows (no compressed-row plan) and, all but the value patterns, 16-byte aligned values.
@@ -1438,6 +1570,29 @@ int mi355x_csr_shift(mi355x_handle_t h, int m, const int *ai, const int *aj, dou
   if (nmissing_dev) MI355X_TRY(hipMemsetAsync(nmissing_dev, 0, sizeof(int), h->stream));
   if (m <= 0) return 0;
   hipLaunchKernelGGL(csr_shift_kernel, dim3((m + MI355X_BLOCK - 1) / MI355X_BLOCK), dim3(MI355X_BLOCK), 0, h->stream, m, ai, aj, alpha, aa, nmissing_dev);
+  MI355X_LAUNCH_CHECK();
+  return 0;
+}
+
+int mi355x_csr_zero_rows(mi355x_handle_t h, int nrows, const int *rows, const int *ai, const int *aj, double *aa, double diag,
+                         const double *x, double *b) {
+  if ((x == nullptr) != (b == nullptr)) return (int)hipErrorInvalidValue;
+  if (nrows <= 0) return 0;
+  const long groups_per_block = MI355X_BLOCK / ZR_GROUP;
+  hipLaunchKernelGGL(csr_zero_rows_kernel, dim3((unsigned)(((long)nrows + groups_per_block - 1) / groups_per_block)), dim3(MI355X_BLOCK), 0, h->stream,
+                     nrows, rows, ai, aj, aa, diag, x, b);
+  MI355X_LAUNCH_CHECK();
+  return 0;
+}
+
+int mi355x_csr_zero_columns(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai, const int *aj, double *aa, const unsigned int *mask,
+                            const double *x, double *b) {
+  if (!p || !mask || (x == nullptr) != (b == nullptr)) return (int)hipErrorInvalidValue;
+  if (p->d_rows) return (int)hipErrorNotSupported;   // compressed rows: the plan's rows are not the matrix's
+  if (p->nblocks == 0) return 0;
+  const dim3 grid(rowblock_grid(p->nblocks, SPMV_CH)), block(SPMV_THREADS);
+  if ((((uintptr_t)aj) & 7u) == 0) hipLaunchKernelGGL((csr_zero_columns_kernel<true>), grid, block, 0, h->stream, p->d_rowblk, p->nblocks, ai, aj, aa, mask, x, b);
+  else hipLaunchKernelGGL((csr_zero_columns_kernel<false>), grid, block, 0, h->stream, p->d_rowblk, p->nblocks, ai, aj, aa, mask, x, b);
   MI355X_LAUNCH_CHECK();
   return 0;
 }

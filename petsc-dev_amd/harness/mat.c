@@ -274,6 +274,44 @@ PetscErrorCode MatCopy(Mat A, Mat B, MatStructure str) {
   return 0;
 }
 
+/* MatZeroRows / MatZeroRowsColumns, matrix.c: the type's slot (also for n == 0: collective on a parallel matrix), then the state bump.
+ * x and b come together, and are different vectors */
+static PetscErrorCode zero_rows_args(Mat A, PetscInt n, const PetscInt rows[], Vec x, Vec b) {
+  if (n < 0) SETERRQ(A->comm, PETSC_ERR_ARG_OUTOFRANGE, "Negative number of rows %d", n);
+  if (n && !rows) SETERRQ(A->comm, PETSC_ERR_ARG_NULL, "Null array of rows");
+  if ((x != NULL) != (b != NULL)) SETERRQ(A->comm, PETSC_ERR_ARG_WRONG, "x and b must both be given or both be NULL");
+  if (x && x == b) SETERRQ(A->comm, PETSC_ERR_ARG_IDN, "x and b must be different vectors");
+  if (x && (x->map->n != A->cmap->n || b->map->n != A->rmap->n)) SETERRQ(A->comm, PETSC_ERR_ARG_SIZ, "Mat mat,Vec x,Vec b: local dim (%d,%d) %d %d", A->rmap->n, A->cmap->n, x->map->n, b->map->n);
+  return 0;
+}
+PetscErrorCode MatZeroRows(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, Vec x, Vec b) {
+  PetscErrorCode ierr;
+  MatTypeSet(A, 1); MatAssembled(A);
+  if (A->factortype) SETERRQ(A->comm, PETSC_ERR_ARG_WRONGSTATE, "Not for factored matrix");
+  ierr = zero_rows_args(A, n, rows, x, b);CHKERRQ(ierr);
+  if (!A->ops->zerorows) SETERRQ(A->comm, PETSC_ERR_SUP, "Mat type %s", A->type_name);
+  ierr = (*A->ops->zerorows)(A, n, rows, diag, x, b);CHKERRQ(ierr);
+  A->state++;
+  return 0;
+}
+PetscErrorCode MatZeroRowsColumns(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, Vec x, Vec b) {
+  PetscErrorCode ierr;
+  MatTypeSet(A, 1); MatAssembled(A);
+  if (A->factortype) SETERRQ(A->comm, PETSC_ERR_ARG_WRONGSTATE, "Not for factored matrix");
+  ierr = zero_rows_args(A, n, rows, x, b);CHKERRQ(ierr);
+  if (!A->ops->zerorowscolumns) SETERRQ(A->comm, PETSC_ERR_SUP, "Mat type %s", A->type_name);
+  ierr = (*A->ops->zerorowscolumns)(A, n, rows, diag, x, b);CHKERRQ(ierr);
+  A->state++;
+  return 0;
+}
+/* MatSetOption, matrix.c: a type without the slot, and an option its slot does not know, are not errors */
+PetscErrorCode MatSetOption(Mat A, MatOption op, PetscBool flg) {
+  MatTypeSet(A, 1);
+  if ((int)op < 0 || op >= NUM_MAT_OPTIONS) SETERRQ(A->comm, PETSC_ERR_ARG_OUTOFRANGE, "Options %d is out of range", (int)op);
+  if (A->ops->setoption) { PetscErrorCode ierr = (*A->ops->setoption)(A, op, flg);CHKERRQ(ierr); }
+  return 0;
+}
+
 /* ---- type-specific methods reached through composed functions, as in the reference (PetscTryMethod / PetscUseMethod,
  * e.g. MatSeqAIJSetPreallocation aij.c:3435, MatMPIAIJSetPreallocation mpiaij.c:4274, MatGetDiagonalBlock matrix.c) ---- */
 PetscErrorCode MatSeqAIJSetPreallocation(Mat A, PetscInt nz, const PetscInt nnz[]) {

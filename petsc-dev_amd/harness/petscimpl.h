@@ -130,6 +130,9 @@ struct _MatOps {
   PetscErrorCode (*shift)(Mat, PetscScalar);                      /* a(i,i) += alpha (axpy.c MatShift) */
   PetscErrorCode (*axpy)(Mat, PetscScalar, Mat, MatStructure);   /* Y += a X */
   PetscErrorCode (*copy)(Mat, Mat, MatStructure);                /* B <- A: A's slot */
+  PetscErrorCode (*zerorows)(Mat, PetscInt, const PetscInt[], PetscScalar, Vec, Vec);          /* slot 24 */
+  PetscErrorCode (*zerorowscolumns)(Mat, PetscInt, const PetscInt[], PetscScalar, Vec, Vec);
+  PetscErrorCode (*setoption)(Mat, MatOption, PetscBool);
   PetscErrorCode (*duplicate)(Mat, MatDuplicateOption, Mat *);   /* slot 34 */
   PetscErrorCode (*setfromoptions)(Mat);                 /* slot 76 */
   PetscErrorCode (*destroy)(Mat);                        /* slot 60 */

@@ -205,6 +205,10 @@ static void value_maps_free(Mat_SeqAIJHIP *d) {   /* what MatShift / MatAXPY / M
   if (d->xtoy_d) mi355x_free(d->xtoy_d);
   d->xtoy_d = NULL; d->xtoy_xgen = d->xtoy_ygen = 0; d->xtoy_from = NULL;
   d->same_xgen = d->same_ygen = 0;
+  HipFree(d->zr_rows_h); HipFree(d->zr_mask_h); d->zr_rows_h = NULL; d->zr_mask_h = NULL;
+  if (d->zr_rows_d) mi355x_free(d->zr_rows_d);
+  if (d->zr_mask_d) mi355x_free(d->zr_mask_d);
+  d->zr_rows_d = NULL; d->zr_mask_d = NULL; d->zr_n = d->zr_words = 0; d->zr_have = PETSC_FALSE;
 }
 /* the arrays of the old pattern go; counts, requests, options, timing and (harness) the triangular factors outlive them */
 static PetscErrorCode device_free(Mat A) {
@@ -1412,6 +1416,166 @@ PetscErrorCode MatCopy_SeqAIJHIP_Cols(Mat A, Mat B, MatStructure str, const Pets
 }
 static PetscErrorCode MatCopy_SeqAIJHIP(Mat A, Mat B, MatStructure str) { return MatCopy_SeqAIJHIP_Cols(A, B, str, NULL, NULL, PETSC_FALSE); }
 
+/* MatZeroRows and MatZeroRowsColumns (MatZeroRows_SeqAIJ, MatZeroRowsColumns_SeqAIJ, aij.c) on the same model when the pattern is kept --
+ * MatZeroRowsColumns always, MatZeroRows with MAT_KEEP_NONZERO_PATTERN: the host copy by a loop over the rows on host threads and, when the
+ * device copy is current, the same update queued on the device (mi355x_csr_zero_columns, mi355x_csr_zero_rows), b with it, no host wait.
+ * The list and its bitmap stay with the matrix: a loop that fixes the same boundary every step sends them once.
+ * MatZeroRows without the option (the reference's default) removes the rows' entries from the pattern: host copy only, then the type's
+ * pattern-change route -- the device forms go and the next use builds them again.
+ * BAIJ: PETSC_ERR_SUP; a compressed-row form: host copy only.  Every error is raised before anything is changed. */
+#define ZR_LISTED(mask, c) (((mask)[(c) >> 5] >> ((c) & 31)) & 1u)
+typedef struct { const PetscInt *ai, *aj; PetscScalar *a; const unsigned int *mask; PetscScalar diag; const PetscScalar *x; PetscScalar *b; PetscBool cols; } ZeroUpd;
+static void upd_zero_rows(void *c_, PetscInt lo, PetscInt hi) {
+  ZeroUpd *c = (ZeroUpd *)c_;
+  const PetscBool set = (PetscBool)(c->diag != 0.0);
+  for (PetscInt r = lo; r < hi; r++) {
+    if (ZR_LISTED(c->mask, r)) {   /* each entry written once: +0.0, or diag on the diagonal */
+      for (PetscInt k = c->ai[r]; k < c->ai[r + 1]; k++) c->a[k] = (set && c->aj[k] == r) ? c->diag : 0.0;
+      if (c->b) c->b[r] = c->diag * c->x[r];
+    } else if (c->cols) {
+      for (PetscInt k = c->ai[r]; k < c->ai[r + 1]; k++) if (ZR_LISTED(c->mask, c->aj[k])) {
+        if (c->b) c->b[r] = c->b[r] - c->a[k] * c->x[c->aj[k]];
+        c->a[k] = 0.0;
+      }
+    }
+  }
+}
+/* the list of this call with the matrix: kept when it is the list of the last call, else built again; on the device when asked */
+static PetscErrorCode zero_rows_list(Mat A, PetscInt n, const PetscInt rows[], PetscBool want_dev) {
+  PetscErrorCode ierr;
+  Mat_SeqAIJHIP *d = SD(A);
+  const PetscInt m = SA(A)->m, words = PetscMax((m + 31) / 32, 1);
+  if (!(d->zr_have && d->zr_n == n && d->zr_words == words && (!n || !memcmp(d->zr_rows_h, rows, sizeof(PetscInt) * (size_t)n)))) {
+    HipFree(d->zr_rows_h); HipFree(d->zr_mask_h); d->zr_rows_h = NULL; d->zr_mask_h = NULL; d->zr_have = PETSC_FALSE;
+    if (d->zr_rows_d) mi355x_free(d->zr_rows_d);
+    if (d->zr_mask_d) mi355x_free(d->zr_mask_d);
+    d->zr_rows_d = NULL; d->zr_mask_d = NULL;
+    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(n, 1), &d->zr_rows_h);CHKERRQ(ierr);
+    ierr = PetscMalloc(sizeof(unsigned int) * (size_t)words, &d->zr_mask_h);CHKERRQ(ierr);
+    memset(d->zr_mask_h, 0, sizeof(unsigned int) * (size_t)words);
+    for (PetscInt q = 0; q < n; q++) { d->zr_rows_h[q] = rows[q]; d->zr_mask_h[rows[q] >> 5] |= 1u << (rows[q] & 31); }
+    d->zr_n = n; d->zr_words = words; d->zr_have = PETSC_TRUE;
+  }
+  if (want_dev && !d->zr_rows_d) {
+    PetscDeviceCtx *dc;
+    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+    CHKHIP(mi355x_malloc((void **)&d->zr_rows_d, sizeof(PetscInt) * (size_t)PetscMax(n, 1)));
+    CHKHIP(mi355x_malloc((void **)&d->zr_mask_d, sizeof(unsigned int) * (size_t)words));
+    CHKHIP(mi355x_memcpy_h2d(dc->h, d->zr_rows_d, d->zr_rows_h, sizeof(PetscInt) * (size_t)n));
+    CHKHIP(mi355x_memcpy_h2d(dc->h, d->zr_mask_d, d->zr_mask_h, sizeof(unsigned int) * (size_t)words));
+    CHKHIP(mi355x_handle_synchronize(dc->h));       /* once per list: the host arrays are pageable */
+    d->zr_list_uploads++;
+  }
+  return 0;
+}
+/* what both operations ask of the matrix and the list, and the diagonal rules of the forms that keep the pattern */
+static PetscErrorCode zero_rows_check(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, PetscBool keep, PetscBool cols) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A);
+  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  if (a->bs > 1) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "MatZeroRows / MatZeroRowsColumns on scalar rows of a block matrix");
+  for (PetscInt q = 0; q < n; q++) if (rows[q] < 0 || rows[q] >= a->m) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_OUTOFRANGE, "row %d out of range [0,%d)", rows[q], a->m);
+  if (cols && a->m != a->n) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_SIZ, "Only works for square matrices: %d x %d", a->m, a->n);
+  if (diag != 0.0) {
+    if (a->m != a->n) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "a nonzero diagonal value on a matrix that is not square: %d x %d", a->m, a->n);
+    if (keep) {   /* MatMissingDiagonal_SeqAIJ on the whole matrix, as the reference asks it */
+      const PetscInt *pos; PetscBool full;
+      ierr = shift_diag_positions(A, &pos, &full);CHKERRQ(ierr);
+      if (!full) for (PetscInt r = 0; r < a->m; r++) if (pos[r] < 0) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "Matrix is missing diagonal entry in row %d", r);
+    }
+  }
+  return 0;
+}
+static PetscErrorCode zero_rows_keep_pattern(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, Vec xx, Vec bb, PetscBool cols) {
+  PetscErrorCode ierr;
+  HipAIJ *a; Mat_SeqAIJHIP *d = SD(A);
+  ierr = value_op_view(A);CHKERRQ(ierr);
+  a = SA(A);
+  ierr = zero_rows_check(A, n, rows, diag, PETSC_TRUE, cols);CHKERRQ(ierr);
+  if (!n) {   /* nothing changes on either copy: a current device copy stays current over the wrapper's state bump */
+    if (device_values_current(A)) d->uploaded_state = HipObjState(A) + 1;
+    return 0;
+  }
+  const PetscBool on_device = (PetscBool)(update_on_device(A) && device_values_current(A) && !d->cprow);
+  const PetscScalar *x = NULL, *dx = NULL; PetscScalar *b = NULL, *db = NULL;
+  ierr = zero_rows_list(A, n, rows, on_device);CHKERRQ(ierr);
+  if (xx && on_device) {   /* the vectors stay on the device: b is updated there */
+    ierr = VecHIPGetRead(xx, &dx);CHKERRQ(ierr);
+    ierr = VecHIPGetReadWrite(bb, &db);CHKERRQ(ierr);
+  } else if (xx) {
+    ierr = VecGetArrayRead(xx, &x);CHKERRQ(ierr);
+    ierr = VecGetArray(bb, &b);CHKERRQ(ierr);
+  }
+  { ZeroUpd u = {a->i, a->j, a->a, d->zr_mask_h, diag, x, b, cols};
+    HipParallelRanges(a->m, upd_zero_rows, &u); }
+  if (xx && !on_device) {
+    ierr = VecRestoreArrayRead(xx, &x);CHKERRQ(ierr);
+    ierr = VecRestoreArray(bb, &b);CHKERRQ(ierr);
+  }
+  if (on_device) {
+    PetscDeviceCtx *dc;
+    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+    ierr = device_values_changed(A);CHKERRQ(ierr);
+    /* the two kernels write disjoint entries and disjoint rows of b: the columns of the rows that are not listed, then the listed rows */
+    if (cols) CHKHIP(mi355x_csr_zero_columns(dc->h, d->mat.plan, d->mat.i, d->mat.j, d->mat.a, d->zr_mask_d, dx, db));
+    CHKHIP(mi355x_csr_zero_rows(dc->h, (int)n, d->zr_rows_d, d->mat.i, d->mat.j, d->mat.a, diag, dx, db));
+    if (xx) { ierr = VecHIPRestoreWrite(bb);CHKERRQ(ierr); }
+    d->zr_device_updates++;
+  } else d->uploaded_state = -1;
+  return 0;
+}
+static PetscErrorCode zero_rows_new_pattern(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, Vec xx, Vec bb);   /* per flavour, below */
+static PetscBool keep_nonzero_pattern(Mat A);
+static PetscErrorCode MatZeroRows_SeqAIJHIP(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, Vec xx, Vec bb) {
+  if (keep_nonzero_pattern(A)) return zero_rows_keep_pattern(A, n, rows, diag, xx, bb, PETSC_FALSE);
+  return zero_rows_new_pattern(A, n, rows, diag, xx, bb);
+}
+static PetscErrorCode MatZeroRowsColumns_SeqAIJHIP(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, Vec xx, Vec bb) {
+  return zero_rows_keep_pattern(A, n, rows, diag, xx, bb, PETSC_TRUE);
+}
+/* uploads of a row list to the device / updates that ran on the device copy so far (tests: the same list given again is not sent again) */
+PetscErrorCode MatHIPMI355XGetZeroRowsCounts(Mat A, PetscInt *list_uploads, PetscInt *device_updates) {
+  if (!A || A->ops->mult != MatMult_SeqAIJHIP) SETERRQ(A ? HipObjComm(A) : 0, PETSC_ERR_ARG_WRONG, "not a sequential HIPMI355X AIJ matrix");
+  if (list_uploads) *list_uploads = SD(A)->zr_list_uploads;
+  if (device_updates) *device_updates = SD(A)->zr_device_updates;
+  return 0;
+}
+#if !defined(PETSCHIPMI355X_WITH_PETSC)
+static PetscBool keep_nonzero_pattern(Mat A) { return SA(A)->keepnonzeropattern; }
+static PetscErrorCode MatSetOption_SeqAIJHIP(Mat A, MatOption op, PetscBool flg) {   /* MatSetOption_SeqAIJ, aij.c: the one option this container acts on */
+  if (op == MAT_KEEP_NONZERO_PATTERN) SA(A)->keepnonzeropattern = flg;
+  return 0;
+}
+/* the else branch of MatZeroRows_SeqAIJ: a listed row keeps (r, r) = diag in its first slot (diag != 0; a row without a slot gets one
+ * inserted) or nothing, the rows are squeezed as after an assembly, and the device forms of the old pattern go */
+static PetscErrorCode zero_rows_new_pattern(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, Vec xx, Vec bb) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A);
+  ierr = zero_rows_check(A, n, rows, diag, PETSC_FALSE, PETSC_FALSE);CHKERRQ(ierr);
+  if (xx) {
+    const PetscScalar *x; PetscScalar *b;
+    ierr = VecGetArrayRead(xx, &x);CHKERRQ(ierr);
+    ierr = VecGetArray(bb, &b);CHKERRQ(ierr);
+    for (PetscInt q = 0; q < n; q++) b[rows[q]] = diag * x[rows[q]];
+    ierr = VecRestoreArrayRead(xx, &x);CHKERRQ(ierr);
+    ierr = VecRestoreArray(bb, &b);CHKERRQ(ierr);
+  }
+  if (!n) {
+    if (device_values_current(A)) SD(A)->uploaded_state = HipObjState(A) + 1;
+    return 0;
+  }
+  ierr = device_free(A);CHKERRQ(ierr);
+  for (PetscInt q = 0; q < n; q++) {
+    const PetscInt r = rows[q];
+    if (diag != 0.0) {
+      if (a->ilen[r] > 0) { a->ilen[r] = 1; a->a[a->i[r]] = diag; a->j[a->i[r]] = r; }
+      else { ierr = seqaij_set(a, r, r, diag, INSERT_VALUES, NULL);CHKERRQ(ierr); }
+    } else a->ilen[r] = 0;
+  }
+  return seqaij_compact(a);
+}
+#endif
+
 static PetscErrorCode MatGetVecs_HIP(Mat A, Vec *right, Vec *left) {   /* MatGetVecs_SeqAIJCUSP aijcusp.cu:324-345 */
   PetscErrorCode ierr;
   if (right) {
@@ -1480,6 +1644,9 @@ static PetscErrorCode create_common(Mat B, const char *tname, PetscInt bs) {
   B->ops->shift = MatShift_SeqAIJHIP;
   B->ops->axpy = MatAXPY_SeqAIJHIP;
   B->ops->copy = MatCopy_SeqAIJHIP;
+  B->ops->zerorows = MatZeroRows_SeqAIJHIP;
+  B->ops->zerorowscolumns = MatZeroRowsColumns_SeqAIJHIP;
+  B->ops->setoption = MatSetOption_SeqAIJHIP;
   B->ops->diagonalscale = MatDiagonalScale_SeqAIJHIP;
   B->ops->setvaluesbatch = MatSetValuesBatch_SeqAIJHIP;
   B->ops->duplicate = MatDuplicate_SeqAIJHIP;
@@ -1517,6 +1684,7 @@ static PetscErrorCode MatDuplicate_SeqAIJHIP(Mat A, MatDuplicateOption op, Mat *
   if (op != MAT_COPY_VALUES) memset(SA(B)->a, 0, sizeof(PetscScalar) * (size_t)a->nz * (size_t)(a->bs > 1 ? a->bs * a->bs : 1));
   memcpy(SD(B)->opt, SD(A)->opt, sizeof(SD(A)->opt)); memcpy(SD(B)->opt_set, SD(A)->opt_set, sizeof(SD(A)->opt_set));
   SD(B)->cprow = SD(A)->cprow;
+  SA(B)->keepnonzeropattern = a->keepnonzeropattern;
   *M = B;
   return 0;
 }

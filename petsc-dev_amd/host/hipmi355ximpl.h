@@ -136,6 +136,7 @@ typedef struct {
   PetscBool compact;        /* rows are packed (after assembly) */
   PetscInt nonzerorows;
   PetscInt inode_count, *inode_size;   /* Mat_SeqAIJ_Inode node_count / size (aij.h:99-115); 0 / NULL: plain routines */
+  PetscBool keepnonzeropattern;        /* MAT_KEEP_NONZERO_PATTERN (aij.h); on the harness only: inside a PETSc tree the parent's member is read */
 } HipAIJ;
 
 /* ---- factored matrices: what MatGetFactor(A, "petsc", MAT_FACTOR_ILU | MAT_FACTOR_ICC, &F) hangs on F (host/ilu.c, host/icc.c;
@@ -248,6 +249,12 @@ typedef struct {
   PetscInt *sh_diag; PetscBool sh_full; unsigned long long sh_gen;
   PetscInt *xtoy_h, *xtoy_d, xtoy_nz; unsigned long long xtoy_xgen, xtoy_ygen; void *xtoy_from;
   unsigned long long same_xgen, same_ygen;
+  /* MatZeroRows / MatZeroRowsColumns with the pattern kept (host/aijhip.c, "MatZeroRows and MatZeroRowsColumns"): the list of the last
+   * call as it was passed (host copy, zr_n entries; zr_have: there is one, possibly empty), the same list and its bitmap -- one bit per
+   * row, zr_words words -- on the device.  A call with a list of the same length and content reuses them.  The counts outlive them:
+   * uploads of a list to the device, updates that ran on the device copy */
+  PetscInt *zr_rows_h, *zr_rows_d, zr_n, zr_words; unsigned int *zr_mask_h, *zr_mask_d; PetscBool zr_have;
+  PetscInt zr_list_uploads, zr_device_updates;
   PetscInt opt[8]; PetscBool opt_set[8];   /* the type's options as MatSetFromOptions read them under the matrix's prefix (host/aijhip.c) */
   /* per-launch device timing for bench.py (hipEvent pairs on the compute stream) */
   PetscBool timing; PetscInt time_n, time_cap; mi355x_event_t *time_ev;
@@ -281,6 +288,7 @@ typedef struct {
   HipScatter hscat;
   PetscInt rstart, rend, cstart, cend;
   HipStash stash;           /* off-process MatSetValues (harness flavour) */
+  PetscBool keepnonzeropattern;   /* MAT_KEEP_NONZERO_PATTERN for blocks that are made later (harness flavour; the blocks hold their own) */
 } HipMPIAIJ;
 #if defined(PETSCHIPMI355X_WITH_PETSC)
 #define HipMPIAIJGet(A) ((HipMPIAIJ *)(A)->spptr)

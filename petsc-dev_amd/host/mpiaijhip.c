@@ -13,6 +13,7 @@ static PetscErrorCode make_block(Mat parent, PetscInt m, PetscInt n, Mat *blk) {
   ierr = MatCreate(PETSC_COMM_SELF, blk);CHKERRQ(ierr);
   ierr = MatSetSizes(*blk, m, n, m, n);CHKERRQ(ierr);
   ierr = MatSetType(*blk, MATSEQAIJHIPMI355X);CHKERRQ(ierr);
+  if (MA(parent)->keepnonzeropattern && (*blk)->ops->setoption) { ierr = (*(*blk)->ops->setoption)(*blk, MAT_KEEP_NONZERO_PATTERN, PETSC_TRUE);CHKERRQ(ierr); }   /* MatSetOption came first */
   return 0;
 }
 
@@ -253,6 +254,61 @@ static PetscErrorCode MatShift_MPIAIJHIP(Mat A, PetscScalar alpha) {
   ierr = MatAssemblyEnd(A, MAT_FINAL_ASSEMBLY);CHKERRQ(ierr);
   return 0;
 }
+/* MatZeroRows_MPIAIJ (mpiaij.c): rows[] are global and may belong to any rank.  The lists of all ranks are gathered over the communicator's
+ * host collective (the reference routes each row to its owner; a gather of a few boundary rows is the same information), every rank keeps
+ * the rows it owns, and both blocks get them through their own zerorows slots -- whose host and device copies move side by side
+ * (host/aijhip.c): the diagonal block with diag and the vectors (b[r] = diag x[r], once per owned row), the off-diagonal block with 0 and
+ * none.  The blocks' states are bumped here, as the public wrapper would.  Without MAT_KEEP_NONZERO_PATTERN the blocks shrink their own
+ * patterns; garray, the local vector and the scatter stay (they may then carry columns no entry uses, as in the reference).
+ * Every rank sees every row: a row out of range is the same error everywhere.  n == 0 is a rank that only takes part. */
+static PetscErrorCode MatZeroRows_MPIAIJHIP(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, Vec xx, Vec bb) {
+  PetscErrorCode ierr;
+  HipMPIAIJ *a = MA(A);
+  MPI_Comm comm = HipObjComm(A);
+  const int size = HipCommSize(comm);
+  const PetscInt rs = A->rmap->rstart, re = A->rmap->rend;
+  PetscInt *counts, *all = NULL, *lrows, maxn = 0, nl = 0, bad = 0; PetscBool isbad = PETSC_FALSE;
+  if (!a->A || !a->B || !a->garray) SETERRQ(comm, PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  if (!a->A->ops->zerorows || !a->B->ops->zerorows) SETERRQ(comm, PETSC_ERR_SUP, "the blocks have no MatZeroRows");
+  double odd = (A->rmap->rstart == A->cmap->rstart && A->rmap->rend == A->cmap->rend) ? 0.0 : 1.0;   /* on any rank: the diagonal is not in the diagonal blocks */
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)size, &counts);CHKERRQ(ierr);
+  counts[0] = n;
+  if (size > 1) {
+    if (HipCommAllgather(comm, &n, (int)sizeof(PetscInt), counts)) SETERRQ(comm, PETSC_ERR_LIB, "allgather failed");
+    if (HipCommAllreduce(comm, &odd, 1, 1, 0)) SETERRQ(comm, PETSC_ERR_LIB, "allreduce failed");
+  }
+  for (int p = 0; p < size; p++) maxn = PetscMax(maxn, counts[p]);
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(maxn, 1) * (size_t)size, &all);CHKERRQ(ierr);
+  if (size > 1 && maxn > 0) {
+    PetscInt *mine;
+    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)maxn, &mine);CHKERRQ(ierr);
+    memset(mine, 0, sizeof(PetscInt) * (size_t)maxn);
+    memcpy(mine, rows, sizeof(PetscInt) * (size_t)n);
+    if (HipCommAllgather(comm, mine, (int)(sizeof(PetscInt) * (size_t)maxn), all)) SETERRQ(comm, PETSC_ERR_LIB, "allgather failed");
+    HipFree(mine);
+  } else if (n > 0) memcpy(all, rows, sizeof(PetscInt) * (size_t)n);
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(maxn, 1) * (size_t)size, &lrows);CHKERRQ(ierr);
+  for (int p = 0; p < size; p++) for (PetscInt q = 0; q < counts[p]; q++) {
+    const PetscInt r = all[(size_t)p * (size_t)maxn + q];
+    if (r < 0 || r >= A->rmap->N) { if (!isbad) { bad = r; isbad = PETSC_TRUE; } }
+    else if (r >= rs && r < re) lrows[nl++] = r - rs;
+  }
+  HipFree(counts); HipFree(all);
+  if (isbad) { HipFree(lrows); SETERRQ(comm, PETSC_ERR_ARG_OUTOFRANGE, "row %d out of range [0,%d)", bad, A->rmap->N); }
+  if (odd > 0.0 && (diag != 0.0 || xx)) { HipFree(lrows); SETERRQ(comm, PETSC_ERR_SUP, "row and column ownership ranges differ: only diag == 0 without vectors"); }
+  ierr = (*a->A->ops->zerorows)(a->A, nl, lrows, diag, xx, bb);
+  if (!ierr) { HipStateIncrease(a->A); ierr = (*a->B->ops->zerorows)(a->B, nl, lrows, 0.0, NULL, NULL); }
+  if (!ierr) HipStateIncrease(a->B);
+  HipFree(lrows);
+  CHKERRQ(ierr);
+  return 0;
+}
+/* the columns of MatZeroRowsColumns belong to other ranks' rows as well: the mask and x have to travel through the halo scatter first.
+ * Not written yet (sections 8 and 11) */
+static PetscErrorCode MatZeroRowsColumns_MPIAIJHIP(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, Vec xx, Vec bb) {
+  (void)n; (void)rows; (void)diag; (void)xx; (void)bb;
+  SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "MatZeroRowsColumns of a parallel matrix is not supported: use MatZeroRows, or a sequential matrix");
+}
 static PetscErrorCode mpi_value_op_pair(Mat Y, Mat X) {
   if (!X || strcmp(HipObjTypeName(X), MATMPIAIJHIPMI355X) || strcmp(HipObjTypeName(Y), MATMPIAIJHIPMI355X)) SETERRQ(HipObjComm(Y), PETSC_ERR_SUP, "both matrices must be MPIAIJHIPMI355X matrices");
   if (X->rmap->rstart != Y->rmap->rstart || X->rmap->rend != Y->rmap->rend || X->cmap->rstart != Y->cmap->rstart || X->cmap->rend != Y->cmap->rend)
@@ -292,6 +348,16 @@ static PetscErrorCode MatCopy_MPIAIJHIP(Mat A, Mat B, MatStructure str) {
 #if defined(PETSCHIPMI355X_WITH_PETSC)
 #include "mpiaijhipmi355x_ctor.h"   /* integration/petsc-3.3/: the constructor as a subclass of the reference's MATMPIAIJ */
 #else
+/* MatSetOption_MPIAIJ, mpiaij.c: MAT_KEEP_NONZERO_PATTERN goes to both blocks (now, or when they are made) */
+static PetscErrorCode MatSetOption_MPIAIJHIP(Mat A, MatOption op, PetscBool flg) {
+  PetscErrorCode ierr;
+  HipMPIAIJ *a = MA(A);
+  if (op != MAT_KEEP_NONZERO_PATTERN) return 0;
+  a->keepnonzeropattern = flg;
+  if (a->A && a->A->ops->setoption) { ierr = (*a->A->ops->setoption)(a->A, op, flg);CHKERRQ(ierr); }
+  if (a->B && a->B->ops->setoption) { ierr = (*a->B->ops->setoption)(a->B, op, flg);CHKERRQ(ierr); }
+  return 0;
+}
 static PetscErrorCode MatDestroy_MPIAIJHIP(Mat A) {
   PetscErrorCode ierr;
   HipMPIAIJ *a = MA(A);
@@ -330,6 +396,9 @@ PetscErrorCode MatCreate_MPIAIJHIPMI355X(Mat B) {   /* MatCreate_MPIAIJCUSP, mpi
   B->ops->shift = MatShift_MPIAIJHIP;
   B->ops->axpy = MatAXPY_MPIAIJHIP;
   B->ops->copy = MatCopy_MPIAIJHIP;
+  B->ops->zerorows = MatZeroRows_MPIAIJHIP;
+  B->ops->zerorowscolumns = MatZeroRowsColumns_MPIAIJHIP;
+  B->ops->setoption = MatSetOption_MPIAIJHIP;
   B->ops->diagonalscale = MatDiagonalScale_MPIAIJHIP;
   B->ops->destroy = MatDestroy_MPIAIJHIP;
   B->ops->getvecs = MatGetVecs_HIPMI355X;

@@ -46,6 +46,8 @@ _SIG = {
     "MatDuplicate": [vp, i32, P(vp)], "MatSetOptionsPrefix": [vp, C.c_char_p], "MatDiagonalScale": [vp, vp, vp], "MatSetValuesBatch": [vp, i32, i32, vp, vp], "MatMult": [vp, vp, vp], "MatMultAdd": [vp, vp, vp, vp], "MatMultTranspose": [vp, vp, vp],
     "MatMultTransposeAdd": [vp, vp, vp, vp], "MatGetDiagonal": [vp, vp], "MatScale": [vp, dbl], "MatZeroEntries": [vp],
     "MatShift": [vp, dbl], "MatAXPY": [vp, dbl, vp, i32], "MatAYPX": [vp, dbl, vp, i32], "MatCopy": [vp, vp, i32],
+    "MatZeroRows": [vp, i32, vp, dbl, vp, vp], "MatZeroRowsColumns": [vp, i32, vp, dbl, vp, vp], "MatSetOption": [vp, i32, i32],
+    "MatHIPMI355XGetZeroRowsCounts": [vp, P(i32), P(i32)],
     "MatSeqAIJGetArrays": [vp, P(i32), P(vp), P(vp), P(vp)], "MatMPIAIJGetSeqAIJ": [vp, P(vp), P(vp), P(vp)],
     "MatMPIAIJGetScatter": [vp, P(vp), P(vp), P(i32)],
     "MatHIPMI355XSetTiming": [vp, i32], "MatHIPMI355XGetTiming": [vp, P(i32), P(dbl)],
@@ -75,6 +77,7 @@ NORM_1, NORM_2, NORM_FROBENIUS, NORM_INFINITY, NORM_1_AND_2 = 0, 1, 2, 3, 4
 MAT_FINAL_ASSEMBLY, MAT_FLUSH_ASSEMBLY = 0, 1
 PETSC_DECIDE, PETSC_DEFAULT = -1, -2
 DIFFERENT_NONZERO_PATTERN, SUBSET_NONZERO_PATTERN, SAME_NONZERO_PATTERN = 0, 1, 2
+MAT_KEEP_NONZERO_PATTERN = 9          # MatOption (petscmini.h)
 
 
 class PetscError(RuntimeError):
@@ -270,6 +273,24 @@ class Mat:
     def copy(self, B, structure=SAME_NONZERO_PATTERN):
         """B <- self (MatCopy)"""
         lib().MatCopy(self.h, B.h, structure)
+
+    @staticmethod
+    def _rows(rows):
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        return r, r.size, r.ctypes.data_as(vp)
+
+    def zero_rows(self, rows, diag=0.0, x=None, b=None):
+        """zero the listed rows, diag on their diagonal; b[r] = diag x[r] when x and b are given (MatZeroRows)"""
+        r, n, p = self._rows(rows)
+        lib().MatZeroRows(self.h, n, p, diag, x.h if x is not None else None, b.h if b is not None else None)
+
+    def zero_rows_columns(self, rows, diag=0.0, x=None, b=None):
+        """zero the listed rows and columns, diag on the diagonal, b corrected by the eliminated entries (MatZeroRowsColumns)"""
+        r, n, p = self._rows(rows)
+        lib().MatZeroRowsColumns(self.h, n, p, diag, x.h if x is not None else None, b.h if b is not None else None)
+
+    def set_option(self, op, flag=True):
+        lib().MatSetOption(self.h, op, 1 if flag else 0)
 
     def local_size(self):
         m, n = i32(), i32()
