@@ -10,6 +10,7 @@
 // non-temporally.  Compiled with -ffp-contract=off so a*x+y is a rounded multiply then a rounded add, as in the
 // reference's C loops (src/vec/vec/impls/seq/{bvec1,bvec2,dvec2}.c).
 #include "common.hpp"
+#include <type_traits>
 
 // Streaming accesses for operands nobody reads again soon.  In a CG iteration x and r are touched by the update sweep only and z
 // by the AYPX that follows it only; loaded / stored non-temporally they stop evicting p, w and z from the L2 / Infinity Cache,
@@ -43,65 +44,75 @@ template <bool NT> __device__ __forceinline__ void st2(double2 *p, double2 v) { 
 __device__ __forceinline__ double2 ldq(const double2 *p, int nt) { return nt ? nt_load2(p) : *p; }
 __device__ __forceinline__ void stq(double2 *p, double2 v, int nt) { if (nt) nt_store2(p, v); else *p = v; }
 
-// vec_ok: workgroup b owns the tile [b * MI355X_MAP_TILE2, (b + 1) * MI355X_MAP_TILE2) of double2's, lane t its entries t and t + 256
-template <int NIN, class Op, bool NT>
-__global__ __launch_bounds__(MI355X_BLOCK) void map_kernel(Op op, const double *a, const double *b, const double *c,
-                                                          double *out, size_t n, int vec_ok) {
+// all of them 16-byte aligned (NULL, an operand a form of the kernel does not touch, counts as aligned)
+template <class... P> static inline int all_aligned16(const P *...p) { return (mi355x_aligned16(p) && ...); }
+
+// The element-wise tile walk.  vec_ok: workgroup b owns the tile [b * PER * 256, (b + 1) * PER * 256) of double2's and lane t its
+// entries t, t + 256, .. : at2(i, U) is called once, for the U = PER double2's at i, i + 256, .. (U a std::integral_constant; at
+// the edge of the vector, and for PER == 1, U = 1), so that a body can issue the loads of all its entries before the first store;
+// lane 0 of workgroup 0 takes the odd last double with at1(n - 1).  An unaligned view: at1(k) over a scalar grid-stride loop.
+template <int PER, class At2, class At1>
+__device__ __forceinline__ void tile_walk(size_t n, int vec_ok, const At2 &at2, const At1 &at1) {
   const size_t tid = (size_t)blockIdx.x * MI355X_BLOCK + threadIdx.x;
   if (vec_ok) {
     const size_t n2 = n >> 1;
-    const double2 *a2 = reinterpret_cast<const double2 *>(a);
-    const double2 *b2 = reinterpret_cast<const double2 *>(b);
-    const double2 *c2 = reinterpret_cast<const double2 *>(c);
-    double2 *o2 = reinterpret_cast<double2 *>(out);
-    const size_t stride = MI355X_BLOCK;
-    const size_t i = (size_t)blockIdx.x * MI355X_MAP_TILE2 + threadIdx.x;
-    if (i + stride < n2) {
-      double2 av0 = {0, 0}, bv0 = {0, 0}, cv0 = {0, 0}, av1 = {0, 0}, bv1 = {0, 0}, cv1 = {0, 0};
-      if (NIN >= 1) { av0 = ld2<NT>(a2 + i); av1 = ld2<NT>(a2 + i + stride); }
-      if (NIN >= 2) { bv0 = ld2<NT>(b2 + i); bv1 = ld2<NT>(b2 + i + stride); }
-      if (NIN >= 3) { cv0 = ld2<NT>(c2 + i); cv1 = ld2<NT>(c2 + i + stride); }
-      double2 r0, r1;
-      r0.x = op(av0.x, bv0.x, cv0.x); r0.y = op(av0.y, bv0.y, cv0.y);
-      r1.x = op(av1.x, bv1.x, cv1.x); r1.y = op(av1.y, bv1.y, cv1.y);
-      st2<NT>(o2 + i, r0);
-      st2<NT>(o2 + i + stride, r1);
-    } else if (i < n2) {
-      double2 av = {0, 0}, bv = {0, 0}, cv = {0, 0};
-      if (NIN >= 1) av = a2[i];
-      if (NIN >= 2) bv = b2[i];
-      if (NIN >= 3) cv = c2[i];
-      double2 r;
-      r.x = op(av.x, bv.x, cv.x); r.y = op(av.y, bv.y, cv.y);
-      o2[i] = r;
-    }
-    if ((n & 1) && tid == 0) {
-      const size_t k = n - 1;
-      out[k] = op(NIN >= 1 ? a[k] : 0.0, NIN >= 2 ? b[k] : 0.0, NIN >= 3 ? c[k] : 0.0);
-    }
+    const size_t i = (size_t)blockIdx.x * (PER * MI355X_BLOCK) + threadIdx.x;
+    if (PER > 1 && i + (PER - 1) * MI355X_BLOCK < n2) at2(i, std::integral_constant<int, PER>());
+    else if (i < n2) at2(i, std::integral_constant<int, 1>());
+    if ((n & 1) && tid == 0) at1(n - 1);
   } else {
     const size_t stride = (size_t)gridDim.x * MI355X_BLOCK;
-    for (size_t i = tid; i < n; i += stride)
-      out[i] = op(NIN >= 1 ? a[i] : 0.0, NIN >= 2 ? b[i] : 0.0, NIN >= 3 ? c[i] : 0.0);
+    for (size_t k = tid; k < n; k += stride) at1(k);
   }
 }
-
-// workgroups of an element-wise launch: one per tile of MI355X_MAP_TILE2 double2's (an unaligned view takes the scalar grid-stride loop)
-static inline unsigned int map_grid(size_t n, int vec_ok) {
-  if (!vec_ok) return (unsigned int)mi355x_grid_for(n, 4);
-  const size_t n2 = n >> 1, nt = (n2 + MI355X_MAP_TILE2 - 1) / MI355X_MAP_TILE2;
+// its workgroups: one per tile (an unaligned view: the capped grid of the scalar loop, 2 PER doubles per lane and trip)
+template <int PER> static inline unsigned int tile_grid(size_t n, int vec_ok) {
+  if (!vec_ok) return (unsigned int)mi355x_grid_for(n, 2 * PER);
+  const size_t nt = ((n >> 1) + PER * MI355X_BLOCK - 1) / (PER * MI355X_BLOCK);
   return (unsigned int)(nt ? nt : 1);
 }
+// the U entries of a lane in its tile: v[u] <-> p[i + 256 u]
+template <bool NT, int U> __device__ __forceinline__ void ld_tile(const double2 *p, size_t i, double2 (&v)[U]) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) v[u] = ld2<NT>(p + i + u * MI355X_BLOCK);
+}
+template <bool NT, int U> __device__ __forceinline__ void st_tile(double2 *p, size_t i, const double2 (&v)[U]) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) st2<NT>(p + i + u * MI355X_BLOCK, v[u]);
+}
+// A kernel over tiles of MI355X_MAP_TILE2 double2's comes in two instances, streamed (vec_streams) or not, and takes n and vec_ok last
+template <class Kernel, class... A>
+static int launch_tiles(mi355x_handle_t h, size_t n, int vec_ok, Kernel streamed, Kernel cached, A... args) {
+  if (vec_streams(n)) hipLaunchKernelGGL(streamed, dim3(tile_grid<2>(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, args..., n, vec_ok);
+  else hipLaunchKernelGGL(cached, dim3(tile_grid<2>(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, args..., n, vec_ok);
+  MI355X_LAUNCH_CHECK();
+  return 0;
+}
+
+template <int NIN, class Op, bool NT>
+__global__ __launch_bounds__(MI355X_BLOCK) void map_kernel(Op op, const double *a, const double *b, const double *c,
+                                                          double *out, size_t n, int vec_ok) {
+  const double2 *a2 = reinterpret_cast<const double2 *>(a), *b2 = reinterpret_cast<const double2 *>(b);
+  const double2 *c2 = reinterpret_cast<const double2 *>(c);
+  double2 *o2 = reinterpret_cast<double2 *>(out);
+  tile_walk<2>(n, vec_ok,
+    [&](size_t i, auto u) {
+      constexpr int U = decltype(u)::value;
+      double2 av[U] = {}, bv[U] = {}, cv[U] = {}, r[U];
+      if (NIN >= 1) ld_tile<NT>(a2, i, av);
+      if (NIN >= 2) ld_tile<NT>(b2, i, bv);
+      if (NIN >= 3) ld_tile<NT>(c2, i, cv);
+#pragma unroll
+      for (int j = 0; j < U; ++j) { r[j].x = op(av[j].x, bv[j].x, cv[j].x); r[j].y = op(av[j].y, bv[j].y, cv[j].y); }
+      st_tile<NT>(o2, i, r);
+    },
+    [&](size_t k) { out[k] = op(NIN >= 1 ? a[k] : 0.0, NIN >= 2 ? b[k] : 0.0, NIN >= 3 ? c[k] : 0.0); });
+}
+
 template <int NIN, class Op>
 static int launch_map(mi355x_handle_t h, Op op, const double *a, const double *b, const double *c, double *out, size_t n) {
   if (n == 0) return 0;
-  int vec_ok = mi355x_aligned16(out) && (NIN < 1 || mi355x_aligned16(a)) && (NIN < 2 || mi355x_aligned16(b)) &&
-               (NIN < 3 || mi355x_aligned16(c));
-  const unsigned int grid = map_grid(n, vec_ok);
-  if (vec_streams(n)) hipLaunchKernelGGL((map_kernel<NIN, Op, true>), dim3(grid), dim3(MI355X_BLOCK), 0, h->stream, op, a, b, c, out, n, vec_ok);
-  else hipLaunchKernelGGL((map_kernel<NIN, Op, false>), dim3(grid), dim3(MI355X_BLOCK), 0, h->stream, op, a, b, c, out, n, vec_ok);
-  MI355X_LAUNCH_CHECK();
-  return 0;
+  return launch_tiles(h, n, all_aligned16(out, a, b, c), map_kernel<NIN, Op, true>, map_kernel<NIN, Op, false>, op, a, b, c, out);   // an input beyond NIN is NULL
 }
 
 struct OpSet      { double al; __device__ double operator()(double, double, double) const { return al; } };
@@ -163,56 +174,78 @@ __device__ __forceinline__ double maxpy_elem(double xv, const double *a, const d
   return xv;
 }
 
-template <int G0, int NG4>
-__global__ __launch_bounds__(MI355X_BLOCK) void maxpy_kernel(MaxpyArgs args, double *x, size_t n, int vec_ok) {
-  const size_t tid = (size_t)blockIdx.x * MI355X_BLOCK + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * MI355X_BLOCK;
-  constexpr int NV = G0 + 4 * NG4;
-  if (vec_ok) {
-    const size_t n2 = n >> 1;
-    double2 *x2 = reinterpret_cast<double2 *>(x);
-    const size_t i = tid;                            // one double2 of every stream per lane, one contiguous tile per workgroup (grid = all tiles)
-    if (i < n2) {
-      double2 yv[NV];
-      if (args.nt) {                               // see gs_streams()
+// the double2's at i of the NV basis vectors, streamed past the caches or not (see gs_streams())
+template <int NV>
+__device__ __forceinline__ void load_basis(const double *const *y, size_t i, int nt, double2 (&yv)[NV]) {
+  if (nt) {
 #pragma unroll
-        for (int j = 0; j < NV; ++j) yv[j] = nt_load2(reinterpret_cast<const double2 *>(args.y[j]) + i);
-      } else {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) yv[j] = reinterpret_cast<const double2 *>(args.y[j])[i];
-      }
-      double2 xv = x2[i];
-      double lo[NV], hi[NV];
-#pragma unroll
-      for (int j = 0; j < NV; ++j) { lo[j] = yv[j].x; hi[j] = yv[j].y; }
-      xv.x = maxpy_elem<G0, NG4>(xv.x, args.a, lo);
-      xv.y = maxpy_elem<G0, NG4>(xv.y, args.a, hi);
-      x2[i] = xv;
-    }
-    if ((n & 1) && tid == 0) {
-      const size_t k = n - 1;
-      double v[NV];
-#pragma unroll
-      for (int j = 0; j < NV; ++j) v[j] = args.y[j][k];
-      x[k] = maxpy_elem<G0, NG4>(x[k], args.a, v);
-    }
+    for (int j = 0; j < NV; ++j) yv[j] = nt_load2(reinterpret_cast<const double2 *>(y[j]) + i);
   } else {
-    for (size_t k = tid; k < n; k += stride) {
-      double v[NV];
 #pragma unroll
-      for (int j = 0; j < NV; ++j) v[j] = args.y[j][k];
-      x[k] = maxpy_elem<G0, NG4>(x[k], args.a, v);
-    }
+    for (int j = 0; j < NV; ++j) yv[j] = reinterpret_cast<const double2 *>(y[j])[i];
   }
 }
-
+// x after the grouped update: the double2 at i (the basis is requested first, then x) and the double at k
 template <int G0, int NG4>
-static int launch_maxpy(mi355x_handle_t h, const MaxpyArgs &args, double *x, size_t n, int vec_ok) {
-  const size_t nt2 = ((n >> 1) + MI355X_BLOCK - 1) / MI355X_BLOCK;
-  const unsigned int grid = vec_ok ? (unsigned int)(nt2 ? nt2 : 1) : (unsigned int)mi355x_grid_for(n, 2);
-  hipLaunchKernelGGL((maxpy_kernel<G0, NG4>), dim3(grid), dim3(MI355X_BLOCK), 0, h->stream, args, x, n, vec_ok);
-  MI355X_LAUNCH_CHECK();
+__device__ __forceinline__ double2 maxpy_at2(const double *const *y, const double *a, int nt, const double *x, size_t i) {
+  constexpr int NV = G0 + 4 * NG4;
+  double2 yv[NV];
+  load_basis<NV>(y, i, nt, yv);
+  double2 xv = reinterpret_cast<const double2 *>(x)[i];
+  double lo[NV], hi[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) { lo[j] = yv[j].x; hi[j] = yv[j].y; }
+  xv.x = maxpy_elem<G0, NG4>(xv.x, a, lo);
+  xv.y = maxpy_elem<G0, NG4>(xv.y, a, hi);
+  return xv;
+}
+template <int G0, int NG4>
+__device__ __forceinline__ double maxpy_at1(const double *const *y, const double *a, const double *x, size_t k) {
+  constexpr int NV = G0 + 4 * NG4;
+  double v[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) v[j] = y[j][k];
+  return maxpy_elem<G0, NG4>(x[k], a, v);
+}
+
+// one double2 of every stream per lane, one contiguous tile of 256 per workgroup
+template <int G0, int NG4>
+__global__ __launch_bounds__(MI355X_BLOCK) void maxpy_kernel(MaxpyArgs args, double *x, size_t n, int vec_ok) {
+  tile_walk<1>(n, vec_ok,
+    [&](size_t i, auto) { reinterpret_cast<double2 *>(x)[i] = maxpy_at2<G0, NG4>(args.y, args.a, args.nt, x, i); },
+    [&](size_t k) { x[k] = maxpy_at1<G0, NG4>(args.y, args.a, x, k); });
+}
+
+// VecMAXPY's chunking of nv vectors into sweeps: f(pos, g0, ng4) for the vectors from pos on.  First group: the remainder
+// nv % 4 if there is one (dvec2.c:853-877 handles it first), else four; then up to seven more groups of four in the same sweep.
+template <class F> static int for_each_sweep(int nv, F f) {
+  const int rem = nv & 3;
+  for (int pos = 0; pos < nv;) {
+    const int g0 = (pos == 0 && rem) ? rem : 4;
+    int ng4 = (nv - pos - g0) / 4;
+    if (ng4 > 7) ng4 = 7;
+    const int rc = f(pos, g0, ng4);
+    if (rc) return rc;
+    pos += g0 + 4 * ng4;
+  }
   return 0;
+}
+// ... and from (g0, ng4) to the template instance: f(G0, NG4) with both a std::integral_constant
+template <class F> static int with_groups(int g0, int ng4, F f) {
+#define GS_CASE(G, N4) case (G) * 10 + (N4): return f(std::integral_constant<int, G>(), std::integral_constant<int, N4>())
+#define GS_ROW(G) GS_CASE(G, 0); GS_CASE(G, 1); GS_CASE(G, 2); GS_CASE(G, 3); GS_CASE(G, 4); GS_CASE(G, 5); GS_CASE(G, 6); GS_CASE(G, 7)
+  switch (g0 * 10 + ng4) {
+    GS_ROW(1); GS_ROW(2); GS_ROW(3); GS_ROW(4);
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef GS_ROW
+#undef GS_CASE
+}
+// dst[j] = y[j] for the cnt vectors of a sweep; returns whether all of them are 16-byte aligned
+static inline int fill_basis(const double **dst, const double *const *y, int cnt) {
+  int ok = 1;
+  for (int j = 0; j < cnt; ++j) { dst[j] = y[j]; ok = ok && mi355x_aligned16(y[j]); }
+  return ok;
 }
 
 // ------------------------------------------------------------------------
@@ -273,53 +306,37 @@ struct CGStepLen {
 // formed as the update forms it (CGStepLen); for a == 0 (a refused step) sol is left alone, as VecAXPY leaves y alone
 // (bvec1.c:253).  x (= z) and sol have their last reader of the iteration here: streamed (see nt_load2).
 template <bool NT, bool WX>
-__global__ __launch_bounds__(MI355X_BLOCK) void aypx_dev_kernel(const double *num, double den, const double *x, double *y, size_t n, int vec_ok,
-                                                              CGStepLen sl, double *sol) {
+__global__ __launch_bounds__(MI355X_BLOCK) void aypx_dev_kernel(const double *num, double den, const double *x, double *y, CGStepLen sl, double *sol,
+                                                              size_t n, int vec_ok) {
   const double alpha = *num / den;
   const bool copy = (alpha == 0.0);
   double a = 0.0;
   if (WX) sl(a);
   const bool ax = WX && a != 0.0;
-  const size_t tid = (size_t)blockIdx.x * MI355X_BLOCK + threadIdx.x;
-  if (vec_ok) {                                    // one tile of MI355X_MAP_TILE2 double2's per workgroup (see map_kernel)
-    const size_t n2 = n >> 1;
-    const double2 *x2 = reinterpret_cast<const double2 *>(x);
-    double2 *y2 = reinterpret_cast<double2 *>(y), *s2 = reinterpret_cast<double2 *>(sol);
-    const size_t stride = MI355X_BLOCK;
-    const size_t i = (size_t)blockIdx.x * MI355X_MAP_TILE2 + threadIdx.x;
-    if (i + stride < n2) {
-      double2 xv0 = nt_load2(x2 + i), xv1 = nt_load2(x2 + i + stride), yv0 = ld2<NT>(y2 + i), yv1 = ld2<NT>(y2 + i + stride), r0, r1;   // x = z: its last reader (see nt_load2)
+  const auto y_new = [=](double xv, double yv) { return copy ? xv : xv + alpha * yv; };
+  const double2 *x2 = reinterpret_cast<const double2 *>(x);
+  double2 *y2 = reinterpret_cast<double2 *>(y), *s2 = reinterpret_cast<double2 *>(sol);
+  tile_walk<2>(n, vec_ok,
+    [&](size_t i, auto u) {
+      constexpr int U = decltype(u)::value;
+      double2 xv[U], yv[U], r[U];
+      ld_tile<true>(x2, i, xv);                    // x = z: its last reader (see nt_load2)
+      ld_tile<NT>(y2, i, yv);
       if (ax) {
-        double2 sv0 = nt_load2(s2 + i), sv1 = nt_load2(s2 + i + stride);
-        sv0.x = sv0.x + a * yv0.x; sv0.y = sv0.y + a * yv0.y;
-        sv1.x = sv1.x + a * yv1.x; sv1.y = sv1.y + a * yv1.y;
-        nt_store2(s2 + i, sv0); nt_store2(s2 + i + stride, sv1);
+        double2 sv[U];
+        ld_tile<true>(s2, i, sv);
+#pragma unroll
+        for (int j = 0; j < U; ++j) { sv[j].x = sv[j].x + a * yv[j].x; sv[j].y = sv[j].y + a * yv[j].y; }
+        st_tile<true>(s2, i, sv);
       }
-      r0.x = copy ? xv0.x : xv0.x + alpha * yv0.x; r0.y = copy ? xv0.y : xv0.y + alpha * yv0.y;
-      r1.x = copy ? xv1.x : xv1.x + alpha * yv1.x; r1.y = copy ? xv1.y : xv1.y + alpha * yv1.y;
-      st2<NT>(y2 + i, r0);
-      st2<NT>(y2 + i + stride, r1);
-    } else if (i < n2) {
-      double2 xv = nt_load2(x2 + i), yv = y2[i], r;
-      if (ax) {
-        double2 sv = nt_load2(s2 + i);
-        sv.x = sv.x + a * yv.x; sv.y = sv.y + a * yv.y;
-        nt_store2(s2 + i, sv);
-      }
-      r.x = copy ? xv.x : xv.x + alpha * yv.x; r.y = copy ? xv.y : xv.y + alpha * yv.y;
-      y2[i] = r;
-    }
-    if ((n & 1) && tid == 0) {
-      if (ax) sol[n - 1] = sol[n - 1] + a * y[n - 1];
-      y[n - 1] = copy ? x[n - 1] : x[n - 1] + alpha * y[n - 1];
-    }
-  } else {
-    const size_t stride = (size_t)gridDim.x * MI355X_BLOCK;
-    for (size_t i = tid; i < n; i += stride) {
-      if (ax) sol[i] = sol[i] + a * y[i];
-      y[i] = copy ? x[i] : x[i] + alpha * y[i];
-    }
-  }
+#pragma unroll
+      for (int j = 0; j < U; ++j) { r[j].x = y_new(xv[j].x, yv[j].x); r[j].y = y_new(xv[j].y, yv[j].y); }
+      st_tile<NT>(y2, i, r);
+    },
+    [&](size_t k) {
+      if (ax) sol[k] = sol[k] + a * y[k];
+      y[k] = y_new(x[k], y[k]);
+    });
 }
 
 // copy <= 64 doubles from device memory to the handle's pinned scratch, then store the completion number the host
@@ -330,49 +347,16 @@ __global__ void publish_kernel(const double *src, double *host_dst, int count, u
   publish_to_host(host_seq, seq);
 }
 
-// functors that need a once-per-lane hook before the sweep specialise this
-template <class F> struct has_prologue { static constexpr bool value = false; };
-
-// F::accum(i2 or i, acc): adds element contributions
-// RUNS == false: grid-stride (lane t of workgroup b meets double2's b * 256 + t, + grid * 256, ...): vectors that live in the caches.
-// RUNS == true: workgroup b owns a contiguous run of tiles of MI355X_TILE2 double2's, [s0, s1), and lane t meets s0 + t, s0 + t + 256,
-// ...: vectors of >= 256 MiB, where one compact window of tiles in flight streams 6.0-7.0 TB/s and 512 strided workgroups 4.9-6.1
-// (profiles/r04_stream_probe*.log).  The functors' sweeps take a first index, a step and an end, so they serve both.  The oracle's
-// device-order emulation (oracle/vecmat_oracle.c dev_reduce) restates both geometries and the size that separates them: change together.
-template <int NOUT, int MODE, class F, bool RUNS>
-__global__ __launch_bounds__(MI355X_BLOCK) void reduce_kernel(F f, size_t n, int vec_ok, double *partials,
-                                                             unsigned int *ticket, double *out, double *host_copy,
-                                                             unsigned long long *host_seq, unsigned long long seq) {
-  __shared__ double lds[MI355X_BLOCK / MI355X_WAVE][NOUT];
-  __shared__ int is_last;
-  const size_t tid = (size_t)blockIdx.x * MI355X_BLOCK + threadIdx.x;
-  double acc[NOUT];
+template <int NOUT> __device__ __forceinline__ void zero(double (&acc)[NOUT]) {
 #pragma unroll
   for (int j = 0; j < NOUT; ++j) acc[j] = 0.0;
-  if constexpr (has_prologue<F>::value) f.prologue(tid, acc);
-  if (vec_ok) {
-    const size_t n2 = n >> 1;
-    if (RUNS) {
-      const size_t ntiles = (n2 + MI355X_TILE2 - 1) / MI355X_TILE2;
-      const size_t per = (ntiles + gridDim.x - 1) / gridDim.x;
-      size_t s0 = (size_t)blockIdx.x * per * MI355X_TILE2, s1 = s0 + per * MI355X_TILE2;
-      if (s0 > n2) s0 = n2;
-      if (s1 > n2) s1 = n2;
-      f.template sweep<NOUT>(s0 + threadIdx.x, (size_t)MI355X_BLOCK, s1, acc);
-    } else {
-      f.template sweep<NOUT>(tid, (size_t)gridDim.x * MI355X_BLOCK, n2, acc);
-    }
-    if ((n & 1) && tid == 0) f.accum1(n - 1, acc);
-  } else {
-    const size_t stride = (size_t)gridDim.x * MI355X_BLOCK;
-    for (size_t i = tid; i < n; i += stride) f.accum1(i, acc);
-  }
-  if (gridDim.x == 1) {  // single workgroup: no hand-off needed
-    block_reduce_store<NOUT, MODE>(acc, out, lds);
-    if (host_copy) { __syncthreads(); if (threadIdx.x < NOUT) host_copy[threadIdx.x] = out[threadIdx.x]; }
-    publish_to_host(host_seq, seq);
-    return;
-  }
+}
+
+// The hand-off of a launch of several workgroups: each stores its partial sums; the one that arrives last gets true and, in acc,
+// every lane's share of all partials.
+template <int NOUT, int MODE>
+__device__ __forceinline__ bool last_workgroup_gathers(double (&acc)[NOUT], double *partials, unsigned int *ticket, double (*lds)[NOUT]) {
+  __shared__ int is_last;
   block_reduce_store<NOUT, MODE, true>(acc, partials + (size_t)blockIdx.x * NOUT, lds);
   // Publish: the partials were stored write-through (sc1) by lanes of wavefront 0; once those stores have left
   // (vmcnt(0)) lane 0 of the SAME wavefront takes a ticket with a relaxed agent-scope add.  The workgroup that draws
@@ -398,10 +382,9 @@ __global__ __launch_bounds__(MI355X_BLOCK) void reduce_kernel(F f, size_t n, int
     }
   }
   __syncthreads();
-  if (!is_last) return;
+  if (!is_last) return false;
   // last-arriving workgroup: sum the per-workgroup partials in workgroup order
-#pragma unroll
-  for (int j = 0; j < NOUT; ++j) acc[j] = 0.0;
+  zero(acc);
   // (a lane's partials b = t, t + 256, ... are added in that order; up to four workgroups' worth requested together)
   for (unsigned int b0 = threadIdx.x; b0 < gridDim.x; b0 += 4 * MI355X_BLOCK) {
     double v[4][NOUT];
@@ -419,9 +402,48 @@ __global__ __launch_bounds__(MI355X_BLOCK) void reduce_kernel(F f, size_t n, int
       }
     }
   }
+  if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // every workgroup has drawn its ticket
   __syncthreads();
+  return true;
+}
+
+// functors that need a once-per-lane hook before the sweep specialise this
+template <class F> struct has_prologue { static constexpr bool value = false; };
+
+// F::accum(i2 or i, acc): adds element contributions
+// RUNS == false: grid-stride (lane t of workgroup b meets double2's b * 256 + t, + grid * 256, ...): vectors that live in the caches.
+// RUNS == true: workgroup b owns a contiguous run of tiles of MI355X_TILE2 double2's, [s0, s1), and lane t meets s0 + t, s0 + t + 256,
+// ...: vectors of >= 256 MiB, where one compact window of tiles in flight streams 6.0-7.0 TB/s and 512 strided workgroups 4.9-6.1
+// (profiles/r04_stream_probe*.log).  The functors' sweeps take a first index, a step and an end, so they serve both.  The oracle's
+// device-order emulation (oracle/vecmat_oracle.c dev_reduce) restates both geometries and the size that separates them: change together.
+template <int NOUT, int MODE, class F, bool RUNS>
+__global__ __launch_bounds__(MI355X_BLOCK) void reduce_kernel(F f, size_t n, int vec_ok, double *partials,
+                                                             unsigned int *ticket, double *out, double *host_copy,
+                                                             unsigned long long *host_seq, unsigned long long seq) {
+  __shared__ double lds[MI355X_BLOCK / MI355X_WAVE][NOUT];
+  const size_t tid = (size_t)blockIdx.x * MI355X_BLOCK + threadIdx.x;
+  double acc[NOUT];
+  zero(acc);
+  if constexpr (has_prologue<F>::value) f.prologue(tid, acc);
+  if (vec_ok) {
+    const size_t n2 = n >> 1;
+    if (RUNS) {
+      const size_t ntiles = (n2 + MI355X_TILE2 - 1) / MI355X_TILE2;
+      const size_t per = (ntiles + gridDim.x - 1) / gridDim.x;
+      size_t s0 = (size_t)blockIdx.x * per * MI355X_TILE2, s1 = s0 + per * MI355X_TILE2;
+      if (s0 > n2) s0 = n2;
+      if (s1 > n2) s1 = n2;
+      f.template sweep<NOUT>(s0 + threadIdx.x, (size_t)MI355X_BLOCK, s1, acc);
+    } else {
+      f.template sweep<NOUT>(tid, (size_t)gridDim.x * MI355X_BLOCK, n2, acc);
+    }
+    if ((n & 1) && tid == 0) f.accum1(n - 1, acc);
+  } else {
+    const size_t stride = (size_t)gridDim.x * MI355X_BLOCK;
+    for (size_t i = tid; i < n; i += stride) f.accum1(i, acc);
+  }
+  if (gridDim.x > 1 && !last_workgroup_gathers<NOUT, MODE>(acc, partials, ticket, lds)) return;   // a single workgroup needs no hand-off
   block_reduce_store<NOUT, MODE>(acc, out, lds);
-  if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   // a result that stays on the device for the next kernel can be handed to the host as well (same lanes that stored it)
   if (host_copy) { __syncthreads(); if (threadIdx.x < NOUT) host_copy[threadIdx.x] = out[threadIdx.x]; }
   publish_to_host(host_seq, seq);
@@ -461,19 +483,22 @@ static int launch_reduce(mi355x_handle_t h, F f, size_t n, int vec_ok, double *o
   return 0;
 }
 
-// default sweep: 4 grid-stride iterations' loads issued together, consumed in order
-#define DEFAULT_SWEEP()                                                                              \
+// default sweep: four grid-stride iterations at a time (i, i + stride, i + 2 stride, i + 3 stride in that order, .x then .y within
+// each), then one at a time.  BATCHED_SWEEP: the functor has a form of the four, accum2x4, that issues all their loads together.
+#define SWEEP_BY_FOUR(FOUR)                                                                          \
   template <int NOUT_>                                                                               \
   __device__ __forceinline__ void sweep(size_t tid, size_t stride, size_t n2, double (&a)[NOUT_]) const { \
     size_t i = tid;                                                                                  \
-    for (; i + 3 * stride < n2; i += 4 * stride) accum2x4(i, stride, a);                             \
+    for (; i + 3 * stride < n2; i += 4 * stride) { FOUR; }                                           \
     for (; i < n2; i += stride) accum2(i, a);                                                        \
   }
+#define DEFAULT_SWEEP() SWEEP_BY_FOUR(accum2(i, a); accum2(i + stride, a); accum2(i + 2 * stride, a); accum2(i + 3 * stride, a))
+#define BATCHED_SWEEP() SWEEP_BY_FOUR(accum2x4(i, stride, a))
 
 struct DotF {
   const double *x, *y;
   int nt = 0;                  // vectors too large for the cache: streamed (vec_streams)
-  DEFAULT_SWEEP()
+  BATCHED_SWEEP()
   __device__ void accum2x4(size_t i, size_t st, double (&a)[1]) const {
     const double2 *x2 = reinterpret_cast<const double2 *>(x), *y2 = reinterpret_cast<const double2 *>(y);
     double2 xv0 = ldq(x2 + i, nt), xv1 = ldq(x2 + i + st, nt), xv2 = ldq(x2 + i + 2 * st, nt), xv3 = ldq(x2 + i + 3 * st, nt);
@@ -491,7 +516,7 @@ struct DotF {
 struct SumSqF {
   const double *x;
   int nt = 0;
-  DEFAULT_SWEEP()
+  BATCHED_SWEEP()
   __device__ void accum2x4(size_t i, size_t st, double (&a)[1]) const {
     const double2 *x2 = reinterpret_cast<const double2 *>(x);
     double2 v0 = ldq(x2 + i, nt), v1 = ldq(x2 + i + st, nt), v2 = ldq(x2 + i + 2 * st, nt), v3 = ldq(x2 + i + 3 * st, nt);
@@ -508,7 +533,6 @@ struct SumSqF {
 struct SumAbsF {
   const double *x;
   DEFAULT_SWEEP()
-  __device__ void accum2x4(size_t i, size_t st, double (&a)[1]) const { accum2(i, a); accum2(i + st, a); accum2(i + 2 * st, a); accum2(i + 3 * st, a); }
   __device__ void accum1(size_t i, double (&a)[1]) const { a[0] += fabs(x[i]); }
   __device__ void accum2(size_t i, double (&a)[1]) const {
     double2 xv = reinterpret_cast<const double2 *>(x)[i];
@@ -519,7 +543,6 @@ struct SumAbsF {
 struct MaxAbsF {
   const double *x;
   DEFAULT_SWEEP()
-  __device__ void accum2x4(size_t i, size_t st, double (&a)[1]) const { accum2(i, a); accum2(i + st, a); accum2(i + 2 * st, a); accum2(i + 3 * st, a); }
   __device__ void accum1(size_t i, double (&a)[1]) const { a[0] = nanmax(a[0], fabs(x[i])); }
   __device__ void accum2(size_t i, double (&a)[1]) const {
     double2 xv = reinterpret_cast<const double2 *>(x)[i];
@@ -530,7 +553,6 @@ struct MaxAbsF {
 struct Norm12F {
   const double *x;
   DEFAULT_SWEEP()
-  __device__ void accum2x4(size_t i, size_t st, double (&a)[2]) const { accum2(i, a); accum2(i + st, a); accum2(i + 2 * st, a); accum2(i + 3 * st, a); }
   __device__ void accum1(size_t i, double (&a)[2]) const { a[0] += fabs(x[i]); a[1] += x[i] * x[i]; }
   __device__ void accum2(size_t i, double (&a)[2]) const {
     double2 xv = reinterpret_cast<const double2 *>(x)[i];
@@ -541,7 +563,6 @@ struct Norm12F {
 struct DotNorm2F {
   const double *s, *t;
   DEFAULT_SWEEP()
-  __device__ void accum2x4(size_t i, size_t st, double (&a)[2]) const { accum2(i, a); accum2(i + st, a); accum2(i + 2 * st, a); accum2(i + 3 * st, a); }
   __device__ void accum1(size_t i, double (&a)[2]) const { a[0] += s[i] * t[i]; a[1] += t[i] * t[i]; }
   __device__ void accum2(size_t i, double (&a)[2]) const {
     double2 sv = reinterpret_cast<const double2 *>(s)[i], tv = reinterpret_cast<const double2 *>(t)[i];
@@ -554,50 +575,63 @@ struct DotNorm2F {
 // Element-wise arithmetic is that of the separate kernels (OpAxpy, OpAxpy, OpMul) and each lane meets its elements in
 // the same order as SumSqF / DotF do under launch_reduce, so x, r, z and both sums carry the same bits as the five
 // separate launches; HBM passes drop from 12 to 8.
-struct CGUpdateF {
-  double a, ma;
+// WX == false: x += a p is left to the AYPX that follows (aypx_dev_kernel<NT, true>), and neither p nor x is read here:
+// 5 vector passes instead of 8; same lanes, same order, same sums.
+struct CGVecs {
   const double *p, *w, *d;
   double *x, *r, *z;
-  int big = 0;                 // vectors too large for the cache: p, w and z are streams as well (vec_streams)
+  int big;                     // vectors too large for the cache: p, w and z are streams as well (vec_streams)
+};
+template <bool WX, int NOUT>
+__device__ __forceinline__ void cg_step(double a, double pv, double wv, double dv, double &xv, double &rv, double &zv, double (&acc)[NOUT]) {
+  if (a != 0.0) {              // VecAXPY leaves y alone for alpha == 0 (bvec1.c:253); uniform over the launch
+    if (WX) xv = xv + a * pv;
+    rv = rv + (-a) * wv;
+  }
+  zv = rv * dv;
+  acc[0] += zv * zv;
+  acc[1] += zv * rv;
+  acc[2] += rv * rv;           // VecNorm(R) for KSP_NORM_UNPRECONDITIONED (cg.c:246)
+}
+template <bool WX, int NOUT>
+__device__ __forceinline__ void cg_sweep(const CGVecs &v, double a, size_t tid, size_t stride, size_t n2, double (&acc)[NOUT]) {
+  const double2 *p2 = reinterpret_cast<const double2 *>(v.p), *w2 = reinterpret_cast<const double2 *>(v.w);
+  const double2 *d2 = reinterpret_cast<const double2 *>(v.d);
+  const double2 one2 = {1.0, 1.0}, zero2 = {0.0, 0.0};
+  double2 *x2 = reinterpret_cast<double2 *>(v.x), *r2 = reinterpret_cast<double2 *>(v.r), *z2 = reinterpret_cast<double2 *>(v.z);
+  const int big = v.big;
+  size_t i = tid;
+  for (; i + stride < n2; i += 2 * stride) {
+    double2 pv0 = WX ? ldq(p2 + i, big) : zero2, pv1 = WX ? ldq(p2 + i + stride, big) : zero2, wv0 = ldq(w2 + i, big), wv1 = ldq(w2 + i + stride, big), dv0 = d2 ? nt_load2(d2 + i) : one2, dv1 = d2 ? nt_load2(d2 + i + stride) : one2;
+    double2 xv0 = WX ? nt_load2(x2 + i) : zero2, xv1 = WX ? nt_load2(x2 + i + stride) : zero2, rv0 = nt_load2(r2 + i), rv1 = nt_load2(r2 + i + stride), zv0, zv1;
+    cg_step<WX>(a, pv0.x, wv0.x, dv0.x, xv0.x, rv0.x, zv0.x, acc); cg_step<WX>(a, pv0.y, wv0.y, dv0.y, xv0.y, rv0.y, zv0.y, acc);
+    cg_step<WX>(a, pv1.x, wv1.x, dv1.x, xv1.x, rv1.x, zv1.x, acc); cg_step<WX>(a, pv1.y, wv1.y, dv1.y, xv1.y, rv1.y, zv1.y, acc);
+    if (WX) nt_store2(x2 + i, xv0);
+    nt_store2(r2 + i, rv0); stq(z2 + i, zv0, big);
+    if (WX) nt_store2(x2 + i + stride, xv1);
+    nt_store2(r2 + i + stride, rv1); stq(z2 + i + stride, zv1, big);
+  }
+  for (; i < n2; i += stride) {
+    double2 pv = WX ? p2[i] : zero2, wv = w2[i], dv = d2 ? nt_load2(d2 + i) : one2, xv = WX ? nt_load2(x2 + i) : zero2, rv = nt_load2(r2 + i), zv;
+    cg_step<WX>(a, pv.x, wv.x, dv.x, xv.x, rv.x, zv.x, acc); cg_step<WX>(a, pv.y, wv.y, dv.y, xv.y, rv.y, zv.y, acc);
+    if (WX) nt_store2(x2 + i, xv);
+    nt_store2(r2 + i, rv); z2[i] = zv;
+  }
+}
+template <bool WX, int NOUT>
+__device__ __forceinline__ void cg_accum1(const CGVecs &v, double a, size_t i, double (&acc)[NOUT]) {
+  double xv = WX ? v.x[i] : 0.0, rv = v.r[i], zv;
+  cg_step<WX>(a, WX ? v.p[i] : 0.0, v.w[i], v.d ? v.d[i] : 1.0, xv, rv, zv, acc);
+  if (WX) v.x[i] = xv;
+  v.r[i] = rv; v.z[i] = zv;
+}
+// the step length from the host
+struct CGUpdateF {
+  double a;
+  CGVecs v;
   template <int NOUT_>
-  __device__ __forceinline__ void sweep(size_t tid, size_t stride, size_t n2, double (&acc)[NOUT_]) const {
-    size_t i = tid;
-    for (; i + stride < n2; i += 2 * stride) {
-      const double2 *p2 = reinterpret_cast<const double2 *>(p), *w2 = reinterpret_cast<const double2 *>(w);
-      const double2 *d2 = reinterpret_cast<const double2 *>(d);
-      double2 *x2 = reinterpret_cast<double2 *>(x), *r2 = reinterpret_cast<double2 *>(r), *z2 = reinterpret_cast<double2 *>(z);
-      const double2 one2 = {1.0, 1.0};
-      double2 pv0 = ldq(p2 + i, big), pv1 = ldq(p2 + i + stride, big), wv0 = ldq(w2 + i, big), wv1 = ldq(w2 + i + stride, big), dv0 = d ? nt_load2(d2 + i) : one2, dv1 = d ? nt_load2(d2 + i + stride) : one2;
-      double2 xv0 = nt_load2(x2 + i), xv1 = nt_load2(x2 + i + stride), rv0 = nt_load2(r2 + i), rv1 = nt_load2(r2 + i + stride), zv0, zv1;
-      step(pv0.x, wv0.x, dv0.x, xv0.x, rv0.x, zv0.x, acc); step(pv0.y, wv0.y, dv0.y, xv0.y, rv0.y, zv0.y, acc);
-      step(pv1.x, wv1.x, dv1.x, xv1.x, rv1.x, zv1.x, acc); step(pv1.y, wv1.y, dv1.y, xv1.y, rv1.y, zv1.y, acc);
-      nt_store2(x2 + i, xv0); nt_store2(r2 + i, rv0); stq(z2 + i, zv0, big);
-      nt_store2(x2 + i + stride, xv1); nt_store2(r2 + i + stride, rv1); stq(z2 + i + stride, zv1, big);
-    }
-    for (; i < n2; i += stride) {
-      const double2 one2 = {1.0, 1.0};
-      double2 pv = reinterpret_cast<const double2 *>(p)[i], wv = reinterpret_cast<const double2 *>(w)[i];
-      double2 dv = d ? nt_load2(reinterpret_cast<const double2 *>(d) + i) : one2;
-      double2 xv = nt_load2(reinterpret_cast<double2 *>(x) + i), rv = nt_load2(reinterpret_cast<double2 *>(r) + i), zv;
-      step(pv.x, wv.x, dv.x, xv.x, rv.x, zv.x, acc); step(pv.y, wv.y, dv.y, xv.y, rv.y, zv.y, acc);
-      nt_store2(reinterpret_cast<double2 *>(x) + i, xv); nt_store2(reinterpret_cast<double2 *>(r) + i, rv); reinterpret_cast<double2 *>(z)[i] = zv;
-    }
-  }
-  __device__ __forceinline__ void step(double pv, double wv, double dv, double &xv, double &rv, double &zv, double (&acc)[3]) const {
-    if (a != 0.0) {            // VecAXPY leaves y alone for alpha == 0 (bvec1.c:253); uniform over the launch
-      xv = xv + a * pv;
-      rv = rv + ma * wv;
-    }
-    zv = rv * dv;
-    acc[0] += zv * zv;
-    acc[1] += zv * rv;
-    acc[2] += rv * rv;         // VecNorm(R) for KSP_NORM_UNPRECONDITIONED (cg.c:246)
-  }
-  __device__ void accum1(size_t i, double (&acc)[3]) const {
-    double xv = x[i], rv = r[i], zv;
-    step(p[i], w[i], d ? d[i] : 1.0, xv, rv, zv, acc);
-    x[i] = xv; r[i] = rv; z[i] = zv;
-  }
+  __device__ __forceinline__ void sweep(size_t tid, size_t stride, size_t n2, double (&acc)[NOUT_]) const { cg_sweep<true>(v, a, tid, stride, n2, acc); }
+  __device__ void accum1(size_t i, double (&acc)[3]) const { cg_accum1<true>(v, a, i, acc); }
 };
 // The same sweep with the step length computed on the device: a = beta / dpi where dpi = p'w is still in device memory
 // (the VecTDot kernel, all-reduced in place over RCCL on several ranks, wrote it there), so the host does not have to
@@ -605,71 +639,25 @@ struct CGUpdateF {
 // KSPSolve_CG's break-down tests on dpi (cg.c:196-199) are evaluated here too (CGStepLen): when one fires nothing is
 // modified, and the host, which receives dpi in out[3], takes the reference's exit with x, r, z untouched.  out[3] carries
 // dpi through the reduction tree unchanged but for the sign of a zero (lane 0 of workgroup 0 contributes it, every other lane +0.0).
-// x == NULL: x += a p is left to the AYPX that follows (aypx_dev_kernel<NT, true>), and neither p nor x is read here:
-// 5 vector passes instead of 8; same lanes, same order, same sums.
+// x == NULL: the form without x and p (WX == false).
 struct CGUpdateDevF {
   CGStepLen sl;
-  const double *p, *w, *d;
-  double *x, *r, *z;
-  int big = 0;                 // see CGUpdateF
+  CGVecs v;
   __device__ __forceinline__ void prologue(size_t tid, double (&acc)[4]) const {
     if (tid == 0) acc[3] = *sl.dpi_ptr;
-  }
-  template <bool WX>
-  __device__ __forceinline__ void step(double a, double pv, double wv, double dv, double &xv, double &rv, double &zv, double (&acc)[4]) const {
-    if (a != 0.0) {            // VecAXPY leaves y alone for alpha == 0 (bvec1.c:253)
-      if (WX) xv = xv + a * pv;
-      rv = rv + (-a) * wv;
-    }
-    zv = rv * dv;
-    acc[0] += zv * zv;
-    acc[1] += zv * rv;
-    acc[2] += rv * rv;
   }
   template <int NOUT_>
   __device__ __forceinline__ void sweep(size_t tid, size_t stride, size_t n2, double (&acc)[NOUT_]) const {
     double a;
     if (!sl(a)) return;
-    if (x) sweep_as<true>(a, tid, stride, n2, acc);
-    else sweep_as<false>(a, tid, stride, n2, acc);
-  }
-  template <bool WX>
-  __device__ __forceinline__ void sweep_as(double a, size_t tid, size_t stride, size_t n2, double (&acc)[4]) const {
-    const double2 *p2 = reinterpret_cast<const double2 *>(p), *w2 = reinterpret_cast<const double2 *>(w);
-    const double2 *d2 = reinterpret_cast<const double2 *>(d);
-    const double2 one2 = {1.0, 1.0}, zero2 = {0.0, 0.0};
-    double2 *x2 = reinterpret_cast<double2 *>(x), *r2 = reinterpret_cast<double2 *>(r), *z2 = reinterpret_cast<double2 *>(z);
-    size_t i = tid;
-    for (; i + stride < n2; i += 2 * stride) {
-      double2 pv0 = WX ? ldq(p2 + i, big) : zero2, pv1 = WX ? ldq(p2 + i + stride, big) : zero2, wv0 = ldq(w2 + i, big), wv1 = ldq(w2 + i + stride, big), dv0 = d ? nt_load2(d2 + i) : one2, dv1 = d ? nt_load2(d2 + i + stride) : one2;
-      double2 xv0 = WX ? nt_load2(x2 + i) : zero2, xv1 = WX ? nt_load2(x2 + i + stride) : zero2, rv0 = nt_load2(r2 + i), rv1 = nt_load2(r2 + i + stride), zv0, zv1;
-      step<WX>(a, pv0.x, wv0.x, dv0.x, xv0.x, rv0.x, zv0.x, acc); step<WX>(a, pv0.y, wv0.y, dv0.y, xv0.y, rv0.y, zv0.y, acc);
-      step<WX>(a, pv1.x, wv1.x, dv1.x, xv1.x, rv1.x, zv1.x, acc); step<WX>(a, pv1.y, wv1.y, dv1.y, xv1.y, rv1.y, zv1.y, acc);
-      if (WX) nt_store2(x2 + i, xv0);
-      nt_store2(r2 + i, rv0); stq(z2 + i, zv0, big);
-      if (WX) nt_store2(x2 + i + stride, xv1);
-      nt_store2(r2 + i + stride, rv1); stq(z2 + i + stride, zv1, big);
-    }
-    for (; i < n2; i += stride) {
-      double2 pv = WX ? p2[i] : zero2, wv = w2[i], dv = d ? nt_load2(d2 + i) : one2, xv = WX ? nt_load2(x2 + i) : zero2, rv = nt_load2(r2 + i), zv;
-      step<WX>(a, pv.x, wv.x, dv.x, xv.x, rv.x, zv.x, acc); step<WX>(a, pv.y, wv.y, dv.y, xv.y, rv.y, zv.y, acc);
-      if (WX) nt_store2(x2 + i, xv);
-      nt_store2(r2 + i, rv); z2[i] = zv;
-    }
+    if (v.x) cg_sweep<true>(v, a, tid, stride, n2, acc);
+    else cg_sweep<false>(v, a, tid, stride, n2, acc);
   }
   __device__ void accum1(size_t i, double (&acc)[4]) const {
     double a;
     if (!sl(a)) return;
-    double rv = r[i], zv;
-    if (x) {
-      double xv = x[i];
-      step<true>(a, p[i], w[i], d ? d[i] : 1.0, xv, rv, zv, acc);
-      x[i] = xv;
-    } else {
-      double xv = 0.0;
-      step<false>(a, 0.0, w[i], d ? d[i] : 1.0, xv, rv, zv, acc);
-    }
-    r[i] = rv; z[i] = zv;
+    if (v.x) cg_accum1<true>(v, a, i, acc);
+    else cg_accum1<false>(v, a, i, acc);
   }
 };
 template <> struct has_prologue<CGUpdateDevF> { static constexpr bool value = true; };
@@ -681,7 +669,6 @@ struct PMultDotF {
   const double *x, *d, *y;
   double *w;
   DEFAULT_SWEEP()
-  __device__ void accum2x4(size_t i, size_t st, double (&a)[1]) const { accum2(i, a); accum2(i + st, a); accum2(i + 2 * st, a); accum2(i + 3 * st, a); }
   __device__ void accum1(size_t i, double (&a)[1]) const {
     const double wv = x[i] * (d ? d[i] : 1.0);
     w[i] = wv;
@@ -702,7 +689,6 @@ struct PMultDotNorm2F {
   const double *x, *d, *s;
   double *w;
   DEFAULT_SWEEP()
-  __device__ void accum2x4(size_t i, size_t st, double (&a)[2]) const { accum2(i, a); accum2(i + st, a); accum2(i + 2 * st, a); accum2(i + 3 * st, a); }
   __device__ void accum1(size_t i, double (&a)[2]) const {
     const double wv = x[i] * (d ? d[i] : 1.0);
     w[i] = wv;
@@ -725,7 +711,6 @@ struct BcgsUpdateF {
   const double *p, *s, *t, *rp;
   double *x, *r;
   DEFAULT_SWEEP()
-  __device__ void accum2x4(size_t i, size_t st, double (&a)[2]) const { accum2(i, a); accum2(i + st, a); accum2(i + 2 * st, a); accum2(i + 3 * st, a); }
   __device__ __forceinline__ void one(double pv, double sv, double tv, double rpv, double &xv, double &rv, double (&a)[2]) const {
     xv = alpha * pv + omega * sv + xv;
     rv = (momega == 0.0) ? sv : sv + momega * tv;      // VecWAXPY copies for alpha == 0
@@ -768,13 +753,7 @@ struct MDotF {
   __device__ void accum2(size_t i, double (&a)[NV]) const {
     double2 xv = reinterpret_cast<const double2 *>(x)[i];
     double2 yv[NV];
-    if (nt) {                                      // basis larger than the caches: see gs_streams()
-#pragma unroll
-      for (int j = 0; j < NV; ++j) yv[j] = nt_load2(reinterpret_cast<const double2 *>(y[j]) + i);
-    } else {
-#pragma unroll
-      for (int j = 0; j < NV; ++j) yv[j] = reinterpret_cast<const double2 *>(y[j])[i];
-    }
+    load_basis<NV>(y, i, nt, yv);
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
       a[j] += xv.x * yv[j].x;
@@ -807,44 +786,18 @@ struct MaxpyNormF {
     for (size_t i = tid; i < n2; i += stride) accum2(i, acc);
   }
   __device__ __forceinline__ void accum1(size_t i, double (&acc)[1]) const {
-    double v[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) v[j] = y[j][i];
-    const double xv = maxpy_elem<G0, NG4>(x[i], a, v);
+    const double xv = maxpy_at1<G0, NG4>(y, a, x, i);
     x[i] = xv;
     acc[0] += xv * xv;
   }
   __device__ __forceinline__ void accum2(size_t i, double (&acc)[1]) const {
-    double2 yv[NV];
-    if (nt) {                                      // basis larger than the caches: see gs_streams()
-#pragma unroll
-      for (int j = 0; j < NV; ++j) yv[j] = nt_load2(reinterpret_cast<const double2 *>(y[j]) + i);
-    } else {
-#pragma unroll
-      for (int j = 0; j < NV; ++j) yv[j] = reinterpret_cast<const double2 *>(y[j])[i];
-    }
-    double2 xv = reinterpret_cast<double2 *>(x)[i];
-    double lo[NV], hi[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) { lo[j] = yv[j].x; hi[j] = yv[j].y; }
-    xv.x = maxpy_elem<G0, NG4>(xv.x, a, lo);
-    xv.y = maxpy_elem<G0, NG4>(xv.y, a, hi);
+    const double2 xv = maxpy_at2<G0, NG4>(y, a, nt, x, i);
     reinterpret_cast<double2 *>(x)[i] = xv;
     acc[0] += xv.x * xv.x;
     acc[0] += xv.y * xv.y;
   }
 };
 template <int G0, int NG4> struct has_prologue<MaxpyNormF<G0, NG4>> { static constexpr bool value = true; };
-
-template <int G0, int NG4>
-static int launch_maxpy_norm(mi355x_handle_t h, size_t n, const double *adev, double sign, const double *const *y, double *x, double *out) {
-  MaxpyNormF<G0, NG4> f;
-  int vec_ok = mi355x_aligned16(x);
-  for (int j = 0; j < G0 + 4 * NG4; ++j) { f.y[j] = y[j]; vec_ok = vec_ok && mi355x_aligned16(y[j]); }
-  f.adev = adev; f.sign = sign; f.x = x;
-  f.nt = gs_streams(n, G0 + 4 * NG4);
-  return launch_reduce<1, RED_SUM>(h, f, n, vec_ok, out);
-}
 
 // x *= 1/sqrt(*norm2) with the cases of VecNormalize (rvector.c:308-314: a zero norm leaves x alone, so does a norm of one)
 // and of VecScale_Seq (bvec1.c:183: alpha == 0 sets zero); sqrt and the division are IEEE-exact on the device as on the host
@@ -853,23 +806,16 @@ __global__ __launch_bounds__(MI355X_BLOCK) void scale_rnorm_dev_kernel(const dou
   if (nrm == 0.0 || nrm == 1.0) return;
   const double alpha = 1.0 / nrm;
   if (alpha == 1.0) return;
-  const size_t tid = (size_t)blockIdx.x * MI355X_BLOCK + threadIdx.x;
-  if (vec_ok) {                                    // one tile of MI355X_MAP_TILE2 double2's per workgroup (see map_kernel)
-    const size_t n2 = n >> 1;
-    double2 *x2 = reinterpret_cast<double2 *>(x);
-    const size_t stride = MI355X_BLOCK;
-    const size_t i = (size_t)blockIdx.x * MI355X_MAP_TILE2 + threadIdx.x;
-    if (i + stride < n2) {
-      double2 v0 = x2[i], v1 = x2[i + stride];
-      v0.x = alpha == 0.0 ? 0.0 : v0.x * alpha; v0.y = alpha == 0.0 ? 0.0 : v0.y * alpha;
-      v1.x = alpha == 0.0 ? 0.0 : v1.x * alpha; v1.y = alpha == 0.0 ? 0.0 : v1.y * alpha;
-      x2[i] = v0; x2[i + stride] = v1;
-    } else if (i < n2) { double2 v = x2[i]; v.x = alpha == 0.0 ? 0.0 : v.x * alpha; v.y = alpha == 0.0 ? 0.0 : v.y * alpha; x2[i] = v; }
-    if ((n & 1) && tid == 0) x[n - 1] = alpha == 0.0 ? 0.0 : x[n - 1] * alpha;
-  } else {
-    const size_t stride = (size_t)gridDim.x * MI355X_BLOCK;
-    for (size_t i = tid; i < n; i += stride) x[i] = alpha == 0.0 ? 0.0 : x[i] * alpha;
-  }
+  const auto scaled = [=](double v) { return alpha == 0.0 ? 0.0 : v * alpha; };
+  double2 *x2 = reinterpret_cast<double2 *>(x);
+  tile_walk<2>(n, vec_ok,
+    [&](size_t i, auto u) {
+      double2 v[decltype(u)::value];
+      ld_tile<false>(x2, i, v);
+      for (double2 &e : v) { e.x = scaled(e.x); e.y = scaled(e.y); }
+      st_tile<false>(x2, i, v);
+    },
+    [&](size_t k) { x[k] = scaled(x[k]); });
 }
 
 template <int NV>
@@ -877,11 +823,7 @@ static int launch_mdot(mi355x_handle_t h, size_t n, const double *x, const doubl
   MDotF<NV> f;
   f.x = x;
   f.nt = gs_streams(n, NV);
-  int vec_ok = mi355x_aligned16(x);
-  for (int j = 0; j < NV; ++j) {
-    f.y[j] = y[j];
-    vec_ok = vec_ok && mi355x_aligned16(y[j]);
-  }
+  const int vec_ok = fill_basis(f.y, y, NV) && all_aligned16(x);
   return launch_reduce<NV, RED_SUM>(h, f, n, vec_ok, out);
 }
 
@@ -919,22 +861,14 @@ int mi355x_vec_aypx(mi355x_handle_t h, size_t n, double alpha, const double *x, 
 }
 int mi355x_vec_aypx_dev(mi355x_handle_t h, size_t n, const double *num_dev, double den, const double *x, double *y) {
   if (n == 0) return 0;
-  int vec_ok = mi355x_aligned16(x) && mi355x_aligned16(y);
-  const CGStepLen none{0.0, 0.0, 0, nullptr};
-  if (vec_streams(n)) hipLaunchKernelGGL((aypx_dev_kernel<true, false>), dim3(map_grid(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, num_dev, den, x, y, n, vec_ok, none, (double *)nullptr);
-  else hipLaunchKernelGGL((aypx_dev_kernel<false, false>), dim3(map_grid(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, num_dev, den, x, y, n, vec_ok, none, (double *)nullptr);
-  MI355X_LAUNCH_CHECK();
-  return 0;
+  return launch_tiles(h, n, all_aligned16(x, y), aypx_dev_kernel<true, false>, aypx_dev_kernel<false, false>, num_dev, den, x, y,
+                      CGStepLen{0.0, 0.0, 0, nullptr}, (double *)nullptr);
 }
 int mi355x_vec_aypx_dev_x(mi355x_handle_t h, size_t n, const double *num_dev, double den, const double *x, double *y,
                           double beta, const double *dpi_dev, double dpiold, int check_sign, double *sol) {
   if (n == 0) return 0;
-  int vec_ok = mi355x_aligned16(x) && mi355x_aligned16(y) && mi355x_aligned16(sol);
-  const CGStepLen sl{beta, dpiold, check_sign, dpi_dev};
-  if (vec_streams(n)) hipLaunchKernelGGL((aypx_dev_kernel<true, true>), dim3(map_grid(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, num_dev, den, x, y, n, vec_ok, sl, sol);
-  else hipLaunchKernelGGL((aypx_dev_kernel<false, true>), dim3(map_grid(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, num_dev, den, x, y, n, vec_ok, sl, sol);
-  MI355X_LAUNCH_CHECK();
-  return 0;
+  return launch_tiles(h, n, all_aligned16(x, y, sol), aypx_dev_kernel<true, true>, aypx_dev_kernel<false, true>, num_dev, den, x, y,
+                      CGStepLen{beta, dpiold, check_sign, dpi_dev}, sol);
 }
 int mi355x_handle_publish_at(mi355x_handle_t h, const double *src_dev, int count, int dst_offset) {
   if (count < 0 || dst_offset < 0 || dst_offset + count > MI355X_SCRATCH_DOUBLES) return (int)hipErrorInvalidValue;
@@ -986,45 +920,27 @@ int mi355x_stream_triad(mi355x_handle_t h, size_t n, double alpha, const double 
 
 int mi355x_vec_maxpy(mi355x_handle_t h, size_t n, int nv, const double *alpha, const double *const *y, double *x) {
   if (nv <= 0 || n == 0) return 0;
-  int pos = 0;
-  const int rem = nv & 3;
-  while (pos < nv) {
-    MaxpyArgs args;
-    // first group: the remainder nv % 4 if there is one (dvec2.c:853-877 handles it first), else four; then up to
-    // seven more groups of four in the same sweep
-    const int g0 = (pos == 0 && rem) ? rem : 4;
-    int ng4 = (nv - pos - g0) / 4;
-    if (ng4 > 7) ng4 = 7;
+  return for_each_sweep(nv, [&](int pos, int g0, int ng4) {
     const int cnt = g0 + 4 * ng4;
-    int vec_ok = mi355x_aligned16(x);
-    for (int j = 0; j < 32; ++j) {
-      args.y[j] = (j < cnt) ? y[pos + j] : nullptr;
-      args.a[j] = (j < cnt) ? alpha[pos + j] : 0.0;
-      if (j < cnt) vec_ok = vec_ok && mi355x_aligned16(y[pos + j]);
-    }
+    MaxpyArgs args = {};
+    const int vec_ok = fill_basis(args.y, y + pos, cnt) && all_aligned16(x);
+    for (int j = 0; j < cnt; ++j) args.a[j] = alpha[pos + j];
     args.nt = gs_streams(n, cnt);
-    int rc = 0;
-#define MAXPY_CASE(G, N4) case (G) * 10 + (N4): rc = launch_maxpy<G, N4>(h, args, x, n, vec_ok); break
-#define MAXPY_ROW(G) MAXPY_CASE(G, 0); MAXPY_CASE(G, 1); MAXPY_CASE(G, 2); MAXPY_CASE(G, 3); MAXPY_CASE(G, 4); MAXPY_CASE(G, 5); MAXPY_CASE(G, 6); MAXPY_CASE(G, 7)
-    switch (g0 * 10 + ng4) {
-      MAXPY_ROW(1); MAXPY_ROW(2); MAXPY_ROW(3); MAXPY_ROW(4);
-      default: return (int)hipErrorInvalidValue;
-    }
-#undef MAXPY_ROW
-#undef MAXPY_CASE
-    if (rc) return rc;
-    pos += cnt;
-  }
-  return 0;
+    return with_groups(g0, ng4, [&](auto G0, auto NG4) {
+      hipLaunchKernelGGL((maxpy_kernel<G0, NG4>), dim3(tile_grid<1>(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, args, x, n, vec_ok);
+      MI355X_LAUNCH_CHECK();
+      return 0;
+    });
+  });
 }
 
 int mi355x_vec_dot(mi355x_handle_t h, size_t n, const double *x, const double *y, double *out) {
   DotF f{x, y};
   f.nt = vec_streams(n);
-  return launch_reduce<1, RED_SUM>(h, f, n, mi355x_aligned16(x) && mi355x_aligned16(y), out);
+  return launch_reduce<1, RED_SUM>(h, f, n, all_aligned16(x, y), out);
 }
 int mi355x_vec_norm(mi355x_handle_t h, size_t n, int type, const double *x, double *out) {
-  int v = mi355x_aligned16(x);
+  const int v = all_aligned16(x);
   switch (type) {
     case 0: return launch_reduce<1, RED_SUM>(h, SumAbsF{x}, n, v, out);
     case 1:
@@ -1036,24 +952,19 @@ int mi355x_vec_norm(mi355x_handle_t h, size_t n, int type, const double *x, doub
 }
 int mi355x_vec_dotnorm2(mi355x_handle_t h, size_t n, const double *s, const double *t, double *out) {
   DotNorm2F f{s, t};
-  return launch_reduce<2, RED_SUM>(h, f, n, mi355x_aligned16(s) && mi355x_aligned16(t), out);
+  return launch_reduce<2, RED_SUM>(h, f, n, all_aligned16(s, t), out);
 }
 int mi355x_vec_cg_update(mi355x_handle_t h, size_t n, double a, const double *p, const double *w, const double *d,
                          double *x, double *r, double *z, double *out) {
-  CGUpdateF f{a, -a, p, w, d, x, r, z};
-  f.big = vec_streams(n);
-  int v = mi355x_aligned16(p) && mi355x_aligned16(w) && mi355x_aligned16(d) && mi355x_aligned16(x) && mi355x_aligned16(r) &&
-          mi355x_aligned16(z);   /* d == NULL (identity preconditioner) counts as aligned */
-  return launch_reduce<3, RED_SUM>(h, f, n, v, out);
+  const CGUpdateF f{a, {p, w, d, x, r, z, vec_streams(n)}};
+  return launch_reduce<3, RED_SUM>(h, f, n, all_aligned16(p, w, d, x, r, z), out);   // d == NULL (identity preconditioner) counts as aligned
 }
 int mi355x_vec_cg_update_dev(mi355x_handle_t h, size_t n, double beta, const double *dpi_dev, double dpiold, int check_sign,
                              const double *p, const double *w, const double *d, double *x, double *r, double *z, double *out,
                              int also_to_host) {
-  CGUpdateDevF f{{beta, dpiold, check_sign, dpi_dev}, p, w, d, x, r, z};
-  f.big = vec_streams(n);
-  int v = mi355x_aligned16(p) && mi355x_aligned16(w) && mi355x_aligned16(d) && mi355x_aligned16(x) && mi355x_aligned16(r) &&
-          mi355x_aligned16(z);   /* d == NULL (identity preconditioner) and p, x == NULL (the x-less form) count as aligned */
-  return launch_reduce<4, RED_SUM>(h, f, n, v, out, also_to_host != 0);
+  const CGUpdateDevF f{{beta, dpiold, check_sign, dpi_dev}, {p, w, d, x, r, z, vec_streams(n)}};
+  // d == NULL (identity preconditioner) and p, x == NULL (the x-less form) count as aligned
+  return launch_reduce<4, RED_SUM>(h, f, n, all_aligned16(p, w, d, x, r, z), out, also_to_host != 0);
 }
 int mi355x_vec_cg_update_dev_nox(mi355x_handle_t h, size_t n, double beta, const double *dpi_dev, double dpiold, int check_sign,
                                  const double *w, const double *d, double *r, double *z, double *out, int also_to_host) {
@@ -1061,17 +972,16 @@ int mi355x_vec_cg_update_dev_nox(mi355x_handle_t h, size_t n, double beta, const
 }
 int mi355x_vec_pmult_dot(mi355x_handle_t h, size_t n, const double *x, const double *d, const double *y, double *w, double *out) {
   PMultDotF f{x, d, y, w};
-  return launch_reduce<1, RED_SUM>(h, f, n, mi355x_aligned16(x) && mi355x_aligned16(d) && mi355x_aligned16(y) && mi355x_aligned16(w), out);
+  return launch_reduce<1, RED_SUM>(h, f, n, all_aligned16(x, d, y, w), out);
 }
 int mi355x_vec_pmult_dotnorm2(mi355x_handle_t h, size_t n, const double *x, const double *d, const double *s, double *w, double *out) {
   PMultDotNorm2F f{x, d, s, w};
-  return launch_reduce<2, RED_SUM>(h, f, n, mi355x_aligned16(x) && mi355x_aligned16(d) && mi355x_aligned16(s) && mi355x_aligned16(w), out);
+  return launch_reduce<2, RED_SUM>(h, f, n, all_aligned16(x, d, s, w), out);
 }
 int mi355x_vec_bcgs_update(mi355x_handle_t h, size_t n, double alpha, double omega, const double *p, const double *s, const double *t,
                            const double *rp, double *x, double *r, double *out) {
   BcgsUpdateF f{alpha, omega, -omega, p, s, t, rp, x, r};
-  int v = mi355x_aligned16(p) && mi355x_aligned16(s) && mi355x_aligned16(t) && mi355x_aligned16(rp) && mi355x_aligned16(x) && mi355x_aligned16(r);
-  return launch_reduce<2, RED_SUM>(h, f, n, v, out);
+  return launch_reduce<2, RED_SUM>(h, f, n, all_aligned16(p, s, t, rp, x, r), out);
 }
 
 // borthog2.c:63-64 + the norm of gmres.c:146: x += sum_j sign * coef_dev[j] * y_j, *out = sum x_new^2 (out: device or the
@@ -1080,33 +990,22 @@ int mi355x_vec_maxpy_dev_norm2(mi355x_handle_t h, size_t n, int nv, const double
                                double *x, double *out) {
   if (nv <= 0) return mi355x_vec_norm(h, n, 2, x, out);
   if (n == 0) return launch_reduce<1, RED_SUM>(h, SumSqF{x}, n, 1, out);
-  int pos = 0;
-  const int rem = nv & 3;
-  while (pos < nv) {
-    const int g0 = (pos == 0 && rem) ? rem : 4;
-    int ng4 = (nv - pos - g0) / 4;
-    if (ng4 > 7) ng4 = 7;
-    const int cnt = g0 + 4 * ng4;
-    const bool last = pos + cnt == nv;
+  return for_each_sweep(nv, [&](int pos, int g0, int ng4) {
     // an earlier sweep's sum is of no use: it goes to the last device scratch slot
-    double *o = last ? out : h->dev_scratch + (MI355X_SCRATCH_DOUBLES - 1);
-    int rc = 0;
-#define MN_CASE(G, N4) case (G) * 10 + (N4): rc = launch_maxpy_norm<G, N4>(h, n, coef_dev + pos, sign, y + pos, x, o); break
-#define MN_ROW(G) MN_CASE(G, 0); MN_CASE(G, 1); MN_CASE(G, 2); MN_CASE(G, 3); MN_CASE(G, 4); MN_CASE(G, 5); MN_CASE(G, 6); MN_CASE(G, 7)
-    switch (g0 * 10 + ng4) {
-      MN_ROW(1); MN_ROW(2); MN_ROW(3); MN_ROW(4);
-      default: return (int)hipErrorInvalidValue;
-    }
-#undef MN_ROW
-#undef MN_CASE
-    if (rc) return rc;
-    pos += cnt;
-  }
-  return 0;
+    double *o = pos + g0 + 4 * ng4 == nv ? out : h->dev_scratch + (MI355X_SCRATCH_DOUBLES - 1);
+    return with_groups(g0, ng4, [&](auto G0, auto NG4) {
+      MaxpyNormF<G0, NG4> f;
+      const int vec_ok = fill_basis(f.y, y + pos, f.NV) && all_aligned16(x);
+      f.adev = coef_dev + pos; f.sign = sign; f.x = x;
+      f.nt = gs_streams(n, f.NV);
+      return launch_reduce<1, RED_SUM>(h, f, n, vec_ok, o);
+    });
+  });
 }
 int mi355x_vec_scale_rnorm_dev(mi355x_handle_t h, size_t n, const double *norm2_dev, double *x) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(scale_rnorm_dev_kernel, dim3(map_grid(n, mi355x_aligned16(x))), dim3(MI355X_BLOCK), 0, h->stream, norm2_dev, x, n, mi355x_aligned16(x));
+  const int vec_ok = all_aligned16(x);
+  hipLaunchKernelGGL(scale_rnorm_dev_kernel, dim3(tile_grid<2>(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, norm2_dev, x, n, vec_ok);
   MI355X_LAUNCH_CHECK();
   return 0;
 }

@@ -356,6 +356,44 @@ def test_e_mdot_beyond_one_pass(dev, nv):
         X.free()
 
 
+@pytest.mark.parametrize("n", [1 << 19, (1 << 19) + 3])
+def test_e_gram_schmidt_sweeps_at_the_streaming_threshold(dev, n):
+    """32 basis vectors on either side of gs_streams()'s threshold (nv * n * 8 > 128 MiB): at n = 2^19 the sweep of
+    mi355x_vec_maxpy and of mi355x_vec_maxpy_dev_norm2 loads the basis through the caches, at 2^19 + 3 (an odd tail) non-temporally.
+    A cache hint is not a result: x of both is that of the oracle's MAXPY loop bit for bit, the fused sum that of the device-order
+    oracle and of mi355x_vec_norm(2) on the updated x, the 32 sums of mi355x_vec_mdot (two passes of 16 at the default width, whose
+    basis of 64 MiB stays cacheable at both sizes) those of the device-order oracle; the basis comes back unchanged, every guard intact."""
+    k, nv = dev.k, 32
+    case, fused, md = vs._maxpy_case(nv), vs._maxpy_norm_case(nv), vs._mdot_case(nv)
+    ys = case.ops[1:]
+    v = vs.operands(case, n, 0, finite=True)
+    X = Run(dev, case.ops, n, (0,) * len(case.ops))
+    X.load(v)
+    what = "nv = %d n = %d" % (nv, n)
+    dev.chk(md.call(X, ()))
+    got = dev.scalar_out(nv)
+    with orc.device_reduction_order():
+        same(got, [vs.dsum(v["x"], v[y]) for y in ys], "mdot " + what)
+    t = case.tuples[0]
+    dev.chk(case.call(X, t))
+    dev.sync()
+    same(X.g["x"].get(), case.ref(t, v)[0]["x"], "maxpy x " + what)
+    X.g["x"].load(v["x"])
+    t = fused.tuples[0]
+    dev.chk(fused.call(X, t))
+    n2 = dev.scalar_out()[0]
+    ref, sums = fused.ref(t, v)
+    same(X.g["x"].get(), ref["x"], "maxpy_dev_norm2 x " + what)
+    with orc.device_reduction_order():
+        same(n2, vs.sum_value(sums[0])[0], "maxpy_dev_norm2 sum against the oracle " + what)
+    dev.chk(k.mi355x_vec_norm(dev.h, n, 2, X.p["x"], X.res))
+    same(dev.scalar_out()[0], n2, "maxpy_dev_norm2 sum against mi355x_vec_norm " + what)
+    for y in ys:
+        same(X.g[y].get(), v[y], y + " (read only) " + what)
+    guards_intact(*X.g.values(), names=case.ops)
+    X.free()
+
+
 # ------------------------------------------------------------------------------------------------------------------- F
 def test_f_scale_rnorm_dev_over_the_range(dev):
     """x *= 1 / sqrt(*norm2) for 300 norm2 values log-uniform in [1e-320, 1e300] and the edges: numpy's sqrt and division are
