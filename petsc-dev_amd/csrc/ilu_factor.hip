@@ -216,7 +216,8 @@ int mi355x_ilu0_factor_create(mi355x_handle_t h, int n, const int *bi, const int
     std::vector<int> blkof((size_t)(n > 0 ? n : 1), 0);
     if (nblk > 1) {
       if (blk[0] != 0 || blk[nblk] != n) return (int)hipErrorInvalidValue;
-      for (int b = 0; b < nblk; ++b) { if (blk[b + 1] < blk[b]) return (int)hipErrorInvalidValue; for (int i = blk[b]; i < blk[b + 1]; ++i) blkof[i] = b; }
+      for (int b = 0; b < nblk; ++b) if (blk[b + 1] < blk[b]) return (int)hipErrorInvalidValue;   // (every range inside [0, n] before blkof is written)
+      for (int b = 0; b < nblk; ++b) for (int i = blk[b]; i < blk[b + 1]; ++i) blkof[i] = b;
     }
     c->pending.assign((size_t)c->nblk, 1);
     c->flag.assign((size_t)c->nblk, INT_MAX);
