@@ -194,6 +194,16 @@ int mi355x_spmv_plan_compress_indices(mi355x_handle_t h, mi355x_spmv_plan_t plan
 /* row-pattern kernel (stencil matrices: 4 bytes per row instead of 1 byte per nonzero + the row pointer; found by mi355x_spmv_plan_compress_indices):
  * on = 0/1 switches it, on < 0 only asks; *npat = size of the dictionary, 0 when the plan has none */
 int mi355x_spmv_plan_use_patterns(mi355x_spmv_plan_t p, int on, int *npat);
+/* run-coded row patterns: a row block whose rows form <= 4 runs of equal patterns (a grid line: first, interior, last) is described by
+ * one 32-byte descriptor and does not read its rows' words; other blocks keep them.  Same bits.  on = 0/1 switches, on < 0 only asks;
+ * *nblocks_run_coded = row blocks described by runs, 0 when the plan has no row patterns */
+int mi355x_spmv_plan_use_pattern_runs(mi355x_spmv_plan_t p, int on, int *nblocks_run_coded);
+/* The analysis behind it, host arrays only (no device): rowblk = {first row, first nonzero} of nblocks + 1 row blocks, prow[r] =
+ * {table start of row r's pattern : 16 (low), first nonzero in its block : 16}, pattab[start] = the pattern's length.
+ * runs[8 b + 2 i], runs[8 b + 2 i + 1], i < 4: run i of block b as {prow word of its first row, first row in the block : 16 (low) |
+ * length : 16}; unused runs {0, 0xffff}; a block of more than 4 runs has unused runs only. */
+int mi355x_spmv_pattern_runs_host(int nblocks, const int *rowblk, const unsigned int *prow, const int *pattab, unsigned int *runs,
+                                  int *nblocks_run_coded);
 /* value patterns (constant-coefficient operators: whole rows -- offsets AND values, bit for bit -- taken from a table of
  * <= 512 entries; 2 bytes per row, the value array is not read).  _value_patterns derives the table from the host copy of
  * the values that are (about to be) on the device and must be called again after every upload; _drop_ after any change of

@@ -95,6 +95,8 @@ KERNEL_API = {
     "mi355x_spmv_plan_destroy": [vp],
     "mi355x_spmv_plan_compress_indices": [vp, vp, vp, vp],
     "mi355x_spmv_plan_use_patterns": [vp, i32, vp],
+    "mi355x_spmv_plan_use_pattern_runs": [vp, i32, vp],
+    "mi355x_spmv_pattern_runs_host": [i32, vp, vp, vp, vp, vp],
     "mi355x_spmv_plan_value_patterns": [vp, vp, vp, vp, vp, vp],
     "mi355x_spmv_plan_drop_value_patterns": [vp],
     "mi355x_spmv_plan_use_value_patterns": [vp, i32, vp],

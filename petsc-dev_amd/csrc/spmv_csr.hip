@@ -64,10 +64,14 @@ struct mi355x_spmv_plan_s {
   int *d_offtab;
   int ntab;
   // row patterns (stencil matrices): the offset lists of the rows come from a small dictionary; per row the start of its
-  // list in the table (2 bytes per ROW instead of 1 byte per nonzero)
+  // list in the table and its first nonzero relative to its row block (one 4-byte word per ROW instead of 1 byte per nonzero)
   unsigned int *d_prow;
   int *d_pattab;       // SPMV_PAT_CAP ints
   int npat, use_pat;
+  // run-coded patterns: per row block SPMV_RUN_WORDS words that describe its rows as <= SPMV_RUNS runs of equal patterns (see
+  // spmv_pattern_runs); a block they describe does not read d_prow.  Structure only: lives and dies with d_prow / d_pattab
+  unsigned int *d_pruns;
+  int nruncoded, use_runs;
   int ch;              // run length (row blocks) of the row-pattern kernel's block -> XCD map, from the operator's largest offset
   // value patterns (constant-coefficient operators): rows whose offsets AND values repeat; per row 2 bytes, the values
   // live in the table.  Valid only for the values they were derived from (mi355x_spmv_plan_value_patterns / _drop_)
@@ -387,17 +391,32 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
 // Row-pattern variant for stencil matrices.  When the rows' offset lists (col - row, in column order) come from a small
 // dictionary -- 27 lists of <= 7 offsets for the 7-point operator on a box: interior rows and the boundary cases -- the
 // analysis stores, per ROW, one 4-byte word -- where its list starts in a table, and the row's first nonzero relative to its row
-// block -- and nothing per nonzero: the kernel streams the values (8 B per nonzero) and 4 bytes per row; the row pointer is
-// not read at all (a table entry carries its list's length).  Work layout: the block's values go to LDS with coalesced 16-byte loads; after ONE
+// block -- and nothing per nonzero; the row pointer is not read at all (a table entry carries its list's length).
+// Run-coded blocks: along a row block of a stencil matrix the pattern changes a few times only (a block of P7(256) is one x-line:
+// first row, 254 interior rows, last row), and inside a run of equal patterns a row's first nonzero is the run's plus
+// (row - run's first row) * length.  The analysis therefore describes each block by up to SPMV_RUNS runs in one 32-byte
+// descriptor, indexed by block like rowblk -- the same kind of workgroup-uniform load, issued with it, no new dependent load --
+// and a lane finds its run with SPMV_RUNS - 1 compares instead of loading its row word: the kernel streams the values (8 B per
+// nonzero) and 32 B per block where it streamed 4 B per row (1024 B per full block).  SPMV_RUNS = 4: an x-line needs 3 runs, a
+// block that crosses from one line into the next (line lengths that are no multiple of 256) needs 4 -- interior, last, first,
+// interior -- and 4 runs of {row word of the run's first row, first row : 16 | length : 16} are 32 bytes, one aligned 8-dword load;
+// the length travels with the run, so a run-coded lane does not read it from LDS either.  Unused runs start at row 0xffff, which no lane
+// reaches; a block with more runs (many short lines per block, irregular patterns) has no run at row 0 and reads the row words,
+// which stay complete for every row.
+// Work layout: the block's values go to LDS with coalesced 16-byte loads; after ONE
 // barrier lane r owns row r and gathers x[row + offset_q] itself -- for a fixed q the lanes of a wavefront read
 // consecutive x entries (the rows are consecutive, the offsets equal), so the gathers are coalesced, which the per-nonzero
 // layouts above cannot offer -- multiplies with the staged values and adds in column order (or two at a time, pairsum):
 // the arithmetic and order of the other kernels, same bits.  No row markers, no per-nonzero index stream, one barrier less.
-// DOT as in the idx8 kernel; ch: run length of the block -> XCD map (mi355x_spmv_plan_compress_indices).
+// DOT as in the idx8 kernel; ch: run length of the block -> XCD map (mi355x_spmv_plan_compress_indices); pruns == nullptr: row words only.
 #define SPMV_PAT_CAP 512
+#define SPMV_RUNS 4
+#define SPMV_RUN_WORDS (2 * SPMV_RUNS)     // per row block: SPMV_RUNS x {row word of the run's first row, first row : 16 | length : 16}
+#define SPMV_RUN_NONE 0xffffu              // first row of an unused run
+static_assert(SPMV_RUNS == 4, "the kernel loads a block's runs as two uint4");
 template <int ADD, bool DOT>
 __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock_pat_kernel(
-    const int2 *__restrict__ rowblk, int nblocks, const unsigned int *__restrict__ prow,
+    const int2 *__restrict__ rowblk, int nblocks, const unsigned int *__restrict__ prow, const uint4 *__restrict__ pruns,
     const int *__restrict__ pattab_g, const double *__restrict__ aa, const double *__restrict__ x, const double *yin, double *yout,
     double *__restrict__ dotpart, int pairsum, int ch, int nty) {
   __shared__ double vs[SPMV_BLOCK_NNZ];
@@ -406,6 +425,8 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
   if (lb >= nblocks) return;
   const int2 b0 = rowblk[lb];
   const int2 b1 = rowblk[lb + 1];
+  uint4 d0 = make_uint4(0u, SPMV_RUN_NONE, 0u, SPMV_RUN_NONE), d1 = d0;   // the block's runs (workgroup-uniform)
+  if (pruns) { d0 = pruns[2 * (size_t)lb]; d1 = pruns[2 * (size_t)lb + 1]; }
   const int r0 = b0.x, r1 = b1.x, k0 = b0.y, k1 = b1.y;
   const int nrows = r1 - r0;
   const int tid = threadIdx.x;
@@ -416,8 +437,17 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
     return;
   }
   const int rc = tid < nrows ? tid : nrows - 1;
-  const unsigned int pw = prow[r0 + rc];          // {where the row's list starts in the table : 16, its first nonzero in the block : 16}
-  const int pst = (int)(pw & 0xffffu), rs = (int)(pw >> 16);
+  const bool coded = (d0.y & 0xffffu) == 0u;      // run-coded block: its first run starts at row 0
+  // this lane's run, the last one that starts at or before its row: pw = {where the row's list starts in the table : 16, first nonzero
+  // in the block : 16} of the run's first row, rn = {the run's first row : 16, length : 16}.  Selects on uniform values and no branch
+  // around them; a block without runs holds unused runs only (length 0, so the row's offset in its run below is 0) and loads its row's word.
+  unsigned int pw = d0.x, rn = d0.y;
+  if ((unsigned int)rc >= (d0.w & 0xffffu)) { pw = d0.z; rn = d0.w; }
+  if ((unsigned int)rc >= (d1.y & 0xffffu)) { pw = d1.x; rn = d1.y; }
+  if ((unsigned int)rc >= (d1.w & 0xffffu)) { pw = d1.z; rn = d1.w; }
+  if (!coded) pw = prow[r0 + rc];
+  const int pst = (int)(pw & 0xffffu);
+  const int rs = (int)(pw >> 16) + (rc - (int)(rn & 0xffffu)) * (int)(rn >> 16);
   double ysum = 0.0;
   if (ADD) ysum = yin[r0 + rc];
   v2d v[SPMV_PAIRS];
@@ -429,7 +459,7 @@ __global__ __launch_bounds__(SPMV_THREADS, SPMV_MINWAVES) void spmv_csr_rowblock
   for (int p = 0; p < SPMV_PAIRS; ++p) park_pair(vs, pair_k(k0, tid, p), k0, k1, v[p].x, v[p].y);
   __syncthreads();
   if (!DOT && tid >= nrows) return;
-  const int len = tid < nrows ? pattab[pst] : 0;   // table entry: {length, offsets ...}
+  const int len = tid < nrows ? (coded ? (int)(rn >> 16) : pattab[pst]) : 0;   // table entry: {length, offsets ...}
   const long xbase = (long)r0 + rc;
   double sum = (ADD == 1) ? ysum : 0.0;
   for (int q0 = 0; q0 < len; q0 += 8) {
@@ -948,6 +978,8 @@ static spmv_form_t spmv_form(const mi355x_spmv_plan_s *p, const double *aa, cons
   return (a16 && (((uintptr_t)aj) & 7u) == 0) ? SPMV_PLAIN : SPMV_PLAIN_SCALAR;   // pair loads of aa and aj, or the scalar stream
 }
 
+static inline const uint4 *spmv_runs_of(const mi355x_spmv_plan_s *p) { return p->use_runs ? reinterpret_cast<const uint4 *>(p->d_pruns) : nullptr; }
+
 template <int ADD>
 static int launch_spmv(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai, const int *aj, const double *aa,
                        const double *x, const double *yin, double *yout, const double *dsc = nullptr) {
@@ -965,7 +997,7 @@ static int launch_spmv(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai, c
       break;
     case SPMV_ROWPAT:
       hipLaunchKernelGGL((spmv_csr_rowblock_pat_kernel<ADD, false>), dim3(rowblock_grid(p->nblocks, p->ch)), block, 0, h->stream, p->d_rowblk,
-                         p->nblocks, p->d_prow, p->d_pattab, aa, x, yin, yout, (double *)nullptr, p->pairsum, p->ch, spmv_y_streams(p->nrows));
+                         p->nblocks, p->d_prow, spmv_runs_of(p), p->d_pattab, aa, x, yin, yout, (double *)nullptr, p->pairsum, p->ch, spmv_y_streams(p->nrows));
       break;
     case SPMV_IDX8:
       hipLaunchKernelGGL((spmv_csr_rowblock_idx8_kernel<ADD, false>), grid, block, 0, h->stream, p->d_rowblk,
@@ -989,7 +1021,7 @@ static int spmv_plan_create(mi355x_handle_t h, int nrows, const int *ai_host, co
   // one cleanup path: a failure frees what was allocated so far
   std::unique_ptr<mi355x_spmv_plan_s, decltype(&mi355x_spmv_plan_destroy)> p(new mi355x_spmv_plan_s(), mi355x_spmv_plan_destroy);   // (zeroed)
   p->nrows = nrows;
-  p->use_pat = 1; p->ch = SPMV_CH; p->use_vpat = 1;
+  p->use_pat = 1; p->use_runs = 1; p->ch = SPMV_CH; p->use_vpat = 1;
   std::vector<int2> rb;
   rb.reserve((size_t)nrows / 128 + 2);
   rb.push_back(make_int2(0, ai_host[0]));
@@ -1034,6 +1066,39 @@ static int analysis_threads(int m, int cap) {
   if (e && atoi(e) > 0) nth = atoi(e) > 64 ? 64 : atoi(e);
   if (nth > m) nth = m > 0 ? m : 1;
   return nth;
+}
+
+// Run descriptors of the row-pattern kernel, from the finished row words (host arrays; no device involved): block b's rows
+// [rowblk[2 b], rowblk[2 b + 2]) as maximal runs of consecutive rows with one table start -- an empty row is the pattern of length
+// 0 and forms runs like any other.  Inside a run the rows' first nonzeros advance by the pattern's length (CSR rows lie one after
+// the other), so the run keeps its first row's word.  runs[SPMV_RUN_WORDS * b ...]: per run {that word, first row in the block : 16 |
+// length : 16}, unused runs {0, SPMV_RUN_NONE}; a block of more than SPMV_RUNS runs gets unused runs only and keeps its row words.
+// *ncoded: blocks described by runs.
+static void spmv_pattern_runs(int nblocks, const int *rowblk, const unsigned int *prow, const int *pattab, unsigned int *runs, int b_lo, int b_hi, int *ncoded) {
+  int coded = 0;
+  for (int b = b_lo; b < b_hi; ++b) {
+    unsigned int *d = runs + (size_t)SPMV_RUN_WORDS * (size_t)b;
+    const int r0 = rowblk[2 * (size_t)b], r1 = rowblk[2 * (size_t)b + 2];
+    int n = 0;
+    for (int r = r0; r < r1; ++r) {
+      if (r > r0 && (prow[r] & 0xffffu) == (prow[r - 1] & 0xffffu)) continue;
+      if (n == SPMV_RUNS) { n = SPMV_RUNS + 1; break; }
+      d[2 * n] = prow[r];
+      d[2 * n + 1] = (unsigned int)(r - r0) | ((unsigned int)pattab[prow[r] & 0xffffu] << 16);
+      ++n;
+    }
+    if (n > SPMV_RUNS) n = 0; else ++coded;
+    for (; n < SPMV_RUNS; ++n) { d[2 * n] = 0u; d[2 * n + 1] = SPMV_RUN_NONE; }
+  }
+  (void)nblocks;
+  *ncoded = coded;
+}
+int mi355x_spmv_pattern_runs_host(int nblocks, const int *rowblk, const unsigned int *prow, const int *pattab, unsigned int *runs, int *nblocks_run_coded) {
+  if (nblocks < 0 || (nblocks > 0 && (!rowblk || !prow || !pattab || !runs))) return (int)hipErrorInvalidValue;
+  int coded = 0;
+  spmv_pattern_runs(nblocks, rowblk, prow, pattab, runs, 0, nblocks, &coded);
+  if (nblocks_run_coded) *nblocks_run_coded = coded;
+  return 0;
 }
 
 // Offset-dictionary analysis: idx8[k] = position of (aj[k] - row) in a table of <= 256 distinct offsets.
@@ -1186,8 +1251,19 @@ static int spmv_compress_indices(mi355x_handle_t h, mi355x_spmv_plan_t p, const 
         for (int r = chunk_lo(k); r < chunk_lo(k + 1); ++r) prow[(size_t)r] = (prow[(size_t)r] & 0xffff0000u) | (unsigned int)t[prow[(size_t)r] & 0xffffu];
       });
       ptab.resize(SPMV_PAT_CAP, 0);
+      // the blocks' runs of equal patterns, from the row words just finished (chunks of blocks this time)
+      const size_t nb = (size_t)p->nblocks;
+      std::unique_ptr<unsigned int[]> runs(new unsigned int[SPMV_RUN_WORDS * nb]);
+      std::vector<int> coded((size_t)nth, 0);
+      mi355x_parallel_chunks(nth, [&](int k) {
+        spmv_pattern_runs(p->nblocks, reinterpret_cast<const int *>(blk.data()), prow.get(), ptab.data(), runs.get(), (int)((long)nb * k / nth), (int)((long)nb * (k + 1) / nth), &coded[(size_t)k]);
+      });
+      p->nruncoded = 0;
+      for (int c : coded) p->nruncoded += c;
       MI355X_TRY(hipMalloc((void **)&p->d_prow, sizeof(unsigned int) * (size_t)m + 16));
       MI355X_TRY(hipMalloc((void **)&p->d_pattab, sizeof(int) * SPMV_PAT_CAP));
+      MI355X_TRY(hipMalloc((void **)&p->d_pruns, sizeof(unsigned int) * SPMV_RUN_WORDS * nb));
+      MI355X_TRY(hipMemcpyAsync(p->d_pruns, runs.get(), sizeof(unsigned int) * SPMV_RUN_WORDS * nb, hipMemcpyHostToDevice, h->stream));
       MI355X_TRY(hipMemcpyAsync(p->d_prow, prow.get(), sizeof(unsigned int) * (size_t)m, hipMemcpyHostToDevice, h->stream));
       MI355X_TRY(hipMemcpyAsync(p->d_pattab, ptab.data(), sizeof(int) * SPMV_PAT_CAP, hipMemcpyHostToDevice, h->stream));
       MI355X_TRY(hipStreamSynchronize(h->stream));
@@ -1205,6 +1281,15 @@ int mi355x_spmv_plan_use_patterns(mi355x_spmv_plan_t p, int on, int *npat) {
   if (!p) return (int)hipErrorInvalidValue;
   if (on >= 0) p->use_pat = on ? 1 : 0;
   if (npat) *npat = p->d_prow ? p->npat : 0;
+  return 0;
+}
+
+// A/B switch for the run-coded blocks of the row-pattern kernel (on by default): on = 0 makes every block read its row words,
+// on < 0 only asks; *nblocks_run_coded: row blocks the analysis described by runs, 0 when the plan has no row patterns
+int mi355x_spmv_plan_use_pattern_runs(mi355x_spmv_plan_t p, int on, int *nblocks_run_coded) {
+  if (!p) return (int)hipErrorInvalidValue;
+  if (on >= 0) p->use_runs = on ? 1 : 0;
+  if (nblocks_run_coded) *nblocks_run_coded = p->d_pruns ? p->nruncoded : 0;
   return 0;
 }
 
@@ -1412,6 +1497,7 @@ int mi355x_spmv_plan_destroy(mi355x_spmv_plan_t p) {
   hipFree(p->d_offtab);
   hipFree(p->d_prow);
   hipFree(p->d_pattab);
+  hipFree(p->d_pruns);
   hipFree(p->d_vrow);
   hipFree(p->d_vpattab);
   hipFree(p->d_vpatval);
@@ -1439,7 +1525,8 @@ int mi355x_spmv_plan_dot_available(mi355x_spmv_plan_t p, const double *aa, int *
 int mi355x_spmv_plan_info(mi355x_spmv_plan_t p, int *nblocks, int *nlong, size_t *workspace_bytes) {
   if (nblocks) *nblocks = p->nblocks;
   if (nlong) *nlong = p->nlong;
-  if (workspace_bytes) *workspace_bytes = sizeof(int) * (2 * ((size_t)p->nblocks + 1) + (p->d_rows ? (size_t)p->nrows : 0));
+  if (workspace_bytes) *workspace_bytes = sizeof(int) * (2 * ((size_t)p->nblocks + 1) + (p->d_rows ? (size_t)p->nrows : 0) +
+                                                              (p->d_pruns ? SPMV_RUN_WORDS * (size_t)p->nblocks : 0));
   return 0;
 }
 
@@ -1476,7 +1563,7 @@ int mi355x_spmv_csr_dot(mi355x_handle_t h, mi355x_spmv_plan_t p, const int *ai, 
       break;
     case SPMV_ROWPAT:
       hipLaunchKernelGGL((spmv_csr_rowblock_pat_kernel<0, true>), dim3(rowblock_grid(p->nblocks, p->ch)), block, 0, h->stream, p->d_rowblk,
-                         p->nblocks, p->d_prow, p->d_pattab, aa, x, no_yin, y, p->d_dotpart, p->pairsum, p->ch, spmv_y_streams(p->nrows));
+                         p->nblocks, p->d_prow, spmv_runs_of(p), p->d_pattab, aa, x, no_yin, y, p->d_dotpart, p->pairsum, p->ch, spmv_y_streams(p->nrows));
       break;
     default:   // SPMV_IDX8
       hipLaunchKernelGGL((spmv_csr_rowblock_idx8_kernel<0, true>), dim3(rowblock_grid(p->nblocks, SPMV_CH)), block, 0, h->stream, p->d_rowblk,

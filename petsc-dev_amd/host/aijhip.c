@@ -155,14 +155,14 @@ static PetscErrorCode seqaij_check_inode(Mat A) {
 }
 
 /* ---------------------------------------------------------------- the type's options
- * -mat_hipmi355x_index_compression, _row_patterns, _value_patterns, _tiled, _tiled_stage_min, _blocked, _update_on_device.  MatSetFromOptions (ops->setfromoptions,
+ * -mat_hipmi355x_index_compression, _row_patterns, _pattern_runs, _value_patterns, _tiled, _tiled_stage_min, _blocked, _update_on_device.  MatSetFromOptions (ops->setfromoptions,
  * slot 76, matimpl.h:110; gcreate.c:201-203) reads them under the matrix's own options prefix and keeps them with the matrix; a matrix
  * that was never asked falls back to the global database when its device copy is built (blocks of an MPIAIJ matrix, matrices created
  * by MatCreateSeqAIJWithArrays and used at once). */
-enum { HOPT_IC = 0, HOPT_RP, HOPT_VP, HOPT_TILED, HOPT_TILED_SMIN, HOPT_BLOCKED, HOPT_UPDATE_DEV, HOPT_N };
+enum { HOPT_IC = 0, HOPT_RP, HOPT_VP, HOPT_TILED, HOPT_TILED_SMIN, HOPT_BLOCKED, HOPT_UPDATE_DEV, HOPT_PR, HOPT_N };
 static const char *const hopt_name[HOPT_N] = {"-mat_hipmi355x_index_compression", "-mat_hipmi355x_row_patterns", "-mat_hipmi355x_value_patterns",
                                               "-mat_hipmi355x_tiled", "-mat_hipmi355x_tiled_stage_min", "-mat_hipmi355x_blocked",
-                                              "-mat_hipmi355x_update_on_device"};
+                                              "-mat_hipmi355x_update_on_device", "-mat_hipmi355x_pattern_runs"};
 static PetscErrorCode hip_mat_option(Mat A, int which, PetscInt *val) {
   Mat_SeqAIJHIP *d = SD(A);
   PetscBool set;
@@ -461,12 +461,16 @@ static PetscErrorCode upload_pattern(Mat A, PetscDeviceCtx *dc, UpTick *tk) {
    * when the matrix uses <= 256 distinct (col - row) offsets; plain CSR otherwise */
   ierr = hip_mat_option(A, HOPT_IC, &ic);CHKERRQ(ierr);
   if (ic && !use_cprow) {
-    PetscInt rp = 1;
+    PetscInt rp = 1, pr = 1;
     CHKHIP(mi355x_spmv_plan_compress_indices(dc->h, d->mat.plan, a->i, a->j));
     /* -mat_hipmi355x_row_patterns <0|1> (default 1): stencil matrices whose rows' offset lists come from a small dictionary
      * stream 4 bytes per ROW instead of 1 byte per nonzero + the row pointer (spmv_csr_rowblock_pat_kernel); same bits */
     ierr = hip_mat_option(A, HOPT_RP, &rp);CHKERRQ(ierr);
     CHKHIP(mi355x_spmv_plan_use_patterns(d->mat.plan, rp ? 1 : 0, NULL));
+    /* -mat_hipmi355x_pattern_runs <0|1> (default 1): row blocks whose rows form a few runs of equal patterns (grid lines) read one
+     * 32-byte descriptor instead of 4 bytes per row; same bits */
+    ierr = hip_mat_option(A, HOPT_PR, &pr);CHKERRQ(ierr);
+    CHKHIP(mi355x_spmv_plan_use_pattern_runs(d->mat.plan, pr ? 1 : 0, NULL));
     up_tick(tk, dc, "offset / row-pattern dictionaries");
   }
   /* inodes: when the reference's Mat_CheckInode would switch this matrix to MatMult_SeqAIJ_Inode, the row sums take
@@ -609,12 +613,14 @@ static PetscErrorCode transpose_current(Mat A, PetscDeviceCtx *dc) {
   ierr = form_upload(dc, &d->t, nbc, bs, ti, tj, bs > 1 ? NULL : tperm, ta);CHKERRQ(ierr);
   if (bs == 1) {
     /* the transpose of a stencil matrix is a stencil matrix: same index compression / row patterns as the matrix itself */
-    PetscInt ic = 1, rp = 1;
+    PetscInt ic = 1, rp = 1, pr = 1;
     ierr = hip_mat_option(A, HOPT_IC, &ic);CHKERRQ(ierr);
     ierr = hip_mat_option(A, HOPT_RP, &rp);CHKERRQ(ierr);
+    ierr = hip_mat_option(A, HOPT_PR, &pr);CHKERRQ(ierr);
     if (ic) {
       CHKHIP(mi355x_spmv_plan_compress_indices(dc->h, d->t.plan, ti, tj));
       CHKHIP(mi355x_spmv_plan_use_patterns(d->t.plan, rp ? 1 : 0, NULL));
+      CHKHIP(mi355x_spmv_plan_use_pattern_runs(d->t.plan, pr ? 1 : 0, NULL));
     }
     CHKHIP(mi355x_handle_synchronize(dc->h));
   }
