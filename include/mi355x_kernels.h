@@ -388,6 +388,41 @@ int mi355x_ilu0_factor_arrays(mi355x_ilu0_factor_t ctx, const int **bi, const in
 int mi355x_ilu0_factor_to_sweeps(mi355x_handle_t h, mi355x_ilu0_factor_t ctx, const int *iU, const double *ba, double *aL, double *aU, double *dinv);
 int mi355x_ilu0_factor_info(mi355x_ilu0_factor_t ctx, int *lanes, int *nlev);
 
+/* ---- SOR / SSOR sweeps on a square CSR matrix as it is (csrc/sor.hip) ----
+ * MatSOR_SeqAIJ  src/mat/impls/aij/seq/aij.c:1463 with the point sweeps (never the inode routine), level by level: one lane per row, a
+ * row's products subtracted in storage order, each product and each difference rounded -- x carries the sequential loop's bits.
+ *   _levels_host  lev[i] = 0, or 1 + max lev[j] over the j < i with a(i,j) OR a(j,i) stored (the pattern of A + A^T); *nlev = levels.
+ *             Host arrays, no device.  Every coupled pair j < i has lev[j] < lev[i]: ascending levels are a forward sweep, descending
+ *             levels a backward one (why one set serves both: csrc/sor.hip).
+ *   _plan_create  once per pattern, from HOST ai / aj: checks the pattern (m >= 0, ai increasing from 0, every row's columns strictly
+ *             increasing and inside [0, m), a stored diagonal in every row: hipErrorInvalidValue, *bad_row -- may be NULL -- the first
+ *             offending row or -1), then the levels, the rows in level order and every row's diagonal position, on the device.
+ *             A maximal run of consecutive levels of at most 256 rows each becomes ONE launch of one workgroup that walks the run's
+ *             levels with a barrier between them; MI355X_SOR_NO_FUSE in flags gives every level its own launch.  Same bits either way.
+ *   _plan_info    levels, launches per sweep (either direction), levels that sit inside fused runs
+ *   _idiag    mdiag[i] = a(i,i); idiag[i] = 1 / a(i,i) when omega == 1 and fshift == 0, else omega / (fshift + a(i,i))
+ *   _sweep    one sweep of one kind over the device CSR arrays (the pattern the plan was made from):
+ *               ZERO_FORWARD         sum = b[i] - sum_{j<i} a_ij x[j];  t[i] = sum;  x[i] = sum idiag[i]                 (levels ascending)
+ *               ZERO_BACKWARD        sum = b[i] - sum_{j>i} a_ij x[j];  x[i] = sum idiag[i]                             (descending)
+ *               ZERO_BACKWARD_AFTER  sum = t[i] - sum_{j>i} a_ij x[j];  x[i] = (1 - omega) x[i] + sum idiag[i]          (descending)
+ *               FORWARD / BACKWARD   sum = b[i] - sum_j a_ij x[j];  x[i] = (1 - omega) x[i] + (sum + mdiag[i] x[i]) idiag[i]
+ *             t may be NULL for the kinds that do not touch it.  b and x must not overlap.
+ *   _apply    the whole of MatSOR_SeqAIJ after its checks: flag is a MatSORType bit set (FORWARD 1, BACKWARD 2, LOCAL_FORWARD 4,
+ *             LOCAL_BACKWARD 8, ZERO_INITIAL_GUESS 16; any other bit: hipErrorInvalidValue), its > 0 the product its * lits.
+ * Nothing here waits for the device. */
+typedef struct mi355x_sor_plan_s *mi355x_sor_plan_t;
+enum { MI355X_SOR_ZERO_FORWARD = 0, MI355X_SOR_ZERO_BACKWARD = 1, MI355X_SOR_ZERO_BACKWARD_AFTER = 2, MI355X_SOR_FORWARD = 3, MI355X_SOR_BACKWARD = 4 };
+#define MI355X_SOR_NO_FUSE 1
+int mi355x_sor_levels_host(int m, const int *ai, const int *aj, int *lev, int *nlev);
+int mi355x_sor_plan_create(mi355x_handle_t h, int m, const int *ai, const int *aj, int flags, mi355x_sor_plan_t *plan, int *bad_row);
+int mi355x_sor_plan_destroy(mi355x_sor_plan_t plan);
+int mi355x_sor_plan_info(mi355x_sor_plan_t plan, int *nlev, int *launches_per_sweep, int *fused_levels);
+int mi355x_sor_idiag(mi355x_handle_t h, mi355x_sor_plan_t plan, const double *aa, double omega, double fshift, double *idiag, double *mdiag);
+int mi355x_sor_sweep(mi355x_handle_t h, mi355x_sor_plan_t plan, int kind, const int *ai, const int *aj, const double *aa, const double *idiag,
+                     const double *mdiag, double omega, const double *b, double *t, double *x);
+int mi355x_sor_apply(mi355x_handle_t h, mi355x_sor_plan_t plan, const int *ai, const int *aj, const double *aa, const double *idiag,
+                     const double *mdiag, double omega, int flag, int its, const double *b, double *t, double *x);
+
 /* The same two solves WITHOUT a kernel boundary per level: one launch per triangular solve, rows sorted by level and
  * stored as sliced ELL (one wavefront per 64 rows), dependencies handed over through the solution values themselves
  * (a sentinel bit pattern means "not computed yet"; write-through stores, polling loads).  Same one-lane-per-row,

@@ -94,6 +94,9 @@ PetscErrorCode MatMPIAIJHIPMI355XGetHaloTiming(Mat A, PetscInt *nproducts, Petsc
 PetscErrorCode MatHIPMI355XGetUploadCount(Mat A, PetscInt *n);   /* value uploads host -> device of a sequential matrix so far */
 PetscErrorCode MatHIPMI355XGetTransposeCounts(Mat A, PetscInt *host_builds, PetscInt *device_refreshes);   /* of the cached explicit A^T behind MatMultTranspose */
 PetscErrorCode MatHIPMI355XGetZeroRowsCounts(Mat A, PetscInt *list_uploads, PetscInt *device_updates);   /* MatZeroRows / MatZeroRowsColumns of a sequential matrix: row lists sent to the device, updates run on the device copy */
+/* MatSOR of a sequential matrix: dependency levels and launches per sweep of its level plan (0, 0: no plan yet), and so far: builds of the
+ * inverted diagonal, builds of the plan, applications that ran on the device */
+PetscErrorCode MatHIPMI355XGetSORInfo(Mat A, PetscInt *levels, PetscInt *launches_per_sweep, PetscInt *idiag_builds, PetscInt *plan_builds, PetscInt *device_applications);
 PetscErrorCode MatHIPMI355XGetInodeInfo(Mat A, PetscInt *nodes, PetscInt *groups, PetscInt *shared_indices);   /* Mat_CheckInode's node count; groups / column indices the device plan stores once per group */
 PetscErrorCode MatHIPMI355XGetBlockedInfo(Mat A, PetscInt *bs, PetscInt *nblocks);   /* blocked companion of an AIJ matrix whose nodes are complete bs x bs blocks (products by the BAIJ kernel); 0, 0: not in use */
 PetscErrorCode MatHIPMI355XGetTiledInfo(Mat A, PetscInt *staged, PetscInt *remainder);   /* column-tiled product (x tiles in LDS): nonzeros gathering from LDS / left to the row-block kernel; 0, 0: not in use */

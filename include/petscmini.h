@@ -68,6 +68,10 @@ typedef enum { MAT_ROW_ORIENTED, MAT_NEW_NONZERO_LOCATIONS, MAT_SYMMETRIC, MAT_S
                MAT_KEEP_NONZERO_PATTERN, MAT_IGNORE_ZERO_ENTRIES, MAT_USE_INODES, MAT_HERMITIAN, MAT_SYMMETRY_ETERNAL,
                MAT_CHECK_COMPRESSED_ROW, MAT_IGNORE_LOWER_TRIANGULAR, MAT_ERROR_LOWER_TRIANGULAR, MAT_GETROW_UPPERTRIANGULAR,
                MAT_UNUSED_NONZERO_LOCATION_ERR, MAT_SPD, MAT_NO_OFF_PROC_ENTRIES, MAT_NO_OFF_PROC_ZERO_ROWS, NUM_MAT_OPTIONS } MatOption;
+/* MatSOR (include/petscmat.h MatSORType, the reference's values): which sweeps run, on the whole matrix or on each process's diagonal
+ * block (LOCAL); ZERO_INITIAL_GUESS: x is not read; EISENSTAT, APPLY_UPPER, APPLY_LOWER are refused by the HIPMI355X types */
+typedef enum { SOR_FORWARD_SWEEP = 1, SOR_BACKWARD_SWEEP = 2, SOR_SYMMETRIC_SWEEP = 3, SOR_LOCAL_FORWARD_SWEEP = 4, SOR_LOCAL_BACKWARD_SWEEP = 8,
+               SOR_LOCAL_SYMMETRIC_SWEEP = 12, SOR_ZERO_INITIAL_GUESS = 16, SOR_EISENSTAT = 32, SOR_APPLY_UPPER = 64, SOR_APPLY_LOWER = 128 } MatSORType;
 /* matrix factorisation interface (include/petscmat.h:100-131,1042-1088): the factored matrix is a Mat of its own, obtained from the
  * operator with MatGetFactor, filled by a symbolic and a numeric call, applied with MatSolve */
 typedef enum { MAT_FACTOR_NONE, MAT_FACTOR_LU, MAT_FACTOR_CHOLESKY, MAT_FACTOR_ILU, MAT_FACTOR_ICC, MAT_FACTOR_ILUDT } MatFactorType;
@@ -131,6 +135,7 @@ typedef const char *PCType;
 #define PCPBJACOBI "pbjacobi"  /* point-block Jacobi (src/ksp/pc/impls/pbjacobi/pbjacobi.c), SURVEY 8f.4 */
 #define PCILU      "ilu"       /* ILU(0), natural ordering, sequential AIJ */
 #define PCICC      "icc"       /* ICC(0), natural ordering, sequential AIJ */
+#define PCSOR      "sor"       /* SOR / SSOR through the operator's MatSOR (src/ksp/pc/impls/sor/sor.c) */
 
 /* ---- Sys ----------------------------------------------------------------------------------- */
 extern PetscComm PETSC_COMM_SELF, PETSC_COMM_WORLD;
@@ -275,6 +280,9 @@ PetscErrorCode MatCopy(Mat A, Mat B, MatStructure str);                  /* B <-
 PetscErrorCode MatZeroRows(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, Vec x, Vec b);
 PetscErrorCode MatZeroRowsColumns(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, Vec x, Vec b);
 PetscErrorCode MatSetOption(Mat A, MatOption op, PetscBool flg);
+/* its * lits sweeps of (S)SOR on A x = b with relaxation omega and diagonal shift fshift (matrix.c MatSOR; MatSOR_SeqAIJ aij.c:1463,
+ * MatSOR_MPIAIJ mpiaij.c: local sweeps only, its outer steps of lits local sweeps each).  b and x are different vectors, its, lits > 0 */
+PetscErrorCode MatSOR(Mat A, Vec b, PetscReal omega, MatSORType flag, PetscReal fshift, PetscInt its, PetscInt lits, Vec x);
 PetscErrorCode MatSetOptionsPrefix(Mat A, const char prefix[]);
 /* matrix.c:3937-4010 (MatGetFactor looks "MatGetFactor_<package>_C" up on the operator), 2766-3144 (symbolic / numeric), 3196 (MatSolve) */
 PetscErrorCode MatFactorInfoInitialize(MatFactorInfo *info);

@@ -119,6 +119,7 @@ PetscErrorCode MatCreate_SeqAIJHIPMI355X(Mat B) {
   B->ops->copy             = MatCopy_SeqAIJHIP;
   B->ops->zerorows         = MatZeroRows_SeqAIJHIP;       /* with MAT_KEEP_NONZERO_PATTERN the same model; without it the parent's routine (saved above) */
   B->ops->zerorowscolumns  = MatZeroRowsColumns_SeqAIJHIP; /* always keeps the pattern */
+  B->ops->sor              = MatSOR_SeqAIJHIP;             /* the point sweeps on the device copy (never MatSOR_SeqAIJ_Inode); the tree's own PCSOR calls it */
   /* ops->setoption stays MatSetOption_SeqAIJ: MAT_KEEP_NONZERO_PATTERN is the parent's keepnonzeropattern, read by keep_nonzero_pattern() */
   B->ops->setvaluesbatch   = MatSetValuesBatch_SeqAIJHIP;
   B->ops->setfromoptions   = MatSetFromOptions_SeqAIJHIP;  /* the type's -mat_hipmi355x_* options under the matrix's prefix (slot 76); MatSetFromOptions_SeqAIJ has none of its own in 3.3 */

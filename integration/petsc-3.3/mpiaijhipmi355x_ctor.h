@@ -62,6 +62,7 @@ static PetscErrorCode MatDestroy_MPIAIJHIPMI355X(Mat A) {
   if (h) {
     ierr = HipScatterDestroy(&h->hscat);CHKERRQ(ierr);
     ierr = VecDestroy(&h->lvec);CHKERRQ(ierr);
+    ierr = VecDestroy(&h->sor_bb1);CHKERRQ(ierr);
     ierr = PetscFree(A->spptr);CHKERRQ(ierr);
     A->spptr = 0;
   }
@@ -91,6 +92,7 @@ PetscErrorCode MatCreate_MPIAIJHIPMI355X(Mat B) {
   B->ops->copy             = MatCopy_MPIAIJHIP;
   B->ops->zerorows         = MatZeroRows_MPIAIJHIP;        /* the owners' rows through both blocks' zerorows slots */
   B->ops->zerorowscolumns  = MatZeroRowsColumns_MPIAIJHIP; /* PETSC_ERR_SUP: the mask and x are not carried through the halo scatter yet */
+  B->ops->sor              = MatSOR_MPIAIJHIP;             /* local sweeps over the plug-in's halo scatter and the blocks' own slots */
   /* ops->setoption stays MatSetOption_MPIAIJ: it hands MAT_KEEP_NONZERO_PATTERN to both blocks */
   B->ops->assemblyend      = MatAssemblyEnd_MPIAIJHIPMI355X;
   B->ops->destroy          = MatDestroy_MPIAIJHIPMI355X;

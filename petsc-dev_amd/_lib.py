@@ -146,6 +146,13 @@ KERNEL_API = {
     "mi355x_ilu0_factor_arrays": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
     "mi355x_ilu0_factor_to_sweeps": [vp, vp, vp, vp, vp, vp, vp],
     "mi355x_ilu0_factor_info": [vp, pi32, pi32],
+    "mi355x_sor_levels_host": [i32, vp, vp, vp, pi32],
+    "mi355x_sor_plan_create": [vp, i32, vp, vp, i32, C.POINTER(vp), pi32],
+    "mi355x_sor_plan_destroy": [vp],
+    "mi355x_sor_plan_info": [vp, pi32, pi32, pi32],
+    "mi355x_sor_idiag": [vp, vp, vp, dbl, dbl, vp, vp],
+    "mi355x_sor_sweep": [vp, vp, i32, vp, vp, vp, vp, vp, dbl, vp, vp, vp],
+    "mi355x_sor_apply": [vp, vp, vp, vp, vp, vp, vp, dbl, i32, i32, vp, vp, vp],
     "mi355x_pack": [vp, sz, vp, vp, vp],
     "mi355x_unpack_insert": [vp, sz, vp, vp, vp],
     "mi355x_unpack_add": [vp, sz, vp, vp, vp],

@@ -312,6 +312,23 @@ PetscErrorCode MatSetOption(Mat A, MatOption op, PetscBool flg) {
   return 0;
 }
 
+/* MatSOR, matrix.c: the argument checks, then the type's slot; x changes, the matrix does not */
+PetscErrorCode MatSOR(Mat A, Vec b, PetscReal omega, MatSORType flag, PetscReal fshift, PetscInt its, PetscInt lits, Vec x) {
+  PetscErrorCode ierr;
+  MatTypeSet(A, 1); MatAssembled(A);
+  if (!b || !x) SETERRQ(A->comm, PETSC_ERR_ARG_NULL, "Null vector");
+  if (A->factortype) SETERRQ(A->comm, PETSC_ERR_ARG_WRONGSTATE, "Not for factored matrix");
+  if (!A->ops->sor) SETERRQ(A->comm, PETSC_ERR_SUP, "Mat type %s", A->type_name);
+  if (A->rmap->N != b->map->N || A->cmap->N != x->map->N) SETERRQ(A->comm, PETSC_ERR_ARG_SIZ, "Mat mat,Vec b,Vec x: global dim (%d,%d) %d %d", A->rmap->N, A->cmap->N, b->map->N, x->map->N);
+  if (A->rmap->n != b->map->n || A->cmap->n != x->map->n) SETERRQ(A->comm, PETSC_ERR_ARG_SIZ, "Mat mat,Vec b,Vec x: local dim (%d,%d) %d %d", A->rmap->n, A->cmap->n, b->map->n, x->map->n);
+  if (its <= 0) SETERRQ(A->comm, PETSC_ERR_ARG_WRONG, "Relaxation requires global its %d positive", its);
+  if (lits <= 0) SETERRQ(A->comm, PETSC_ERR_ARG_WRONG, "Relaxation requires local its %d positive", lits);
+  if (b == x) SETERRQ(A->comm, PETSC_ERR_ARG_IDN, "b and x vector cannot be the same");
+  ierr = (*A->ops->sor)(A, b, omega, flag, fshift, its, lits, x);CHKERRQ(ierr);
+  PetscObjectStateIncrease(x);
+  return 0;
+}
+
 /* ---- type-specific methods reached through composed functions, as in the reference (PetscTryMethod / PetscUseMethod,
  * e.g. MatSeqAIJSetPreallocation aij.c:3435, MatMPIAIJSetPreallocation mpiaij.c:4274, MatGetDiagonalBlock matrix.c) ---- */
 PetscErrorCode MatSeqAIJSetPreallocation(Mat A, PetscInt nz, const PetscInt nnz[]) {

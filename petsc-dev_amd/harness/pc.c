@@ -40,6 +40,7 @@ PetscErrorCode PetscMiniInitialize(void) {
   ierr = PCRegister(PCBJACOBI, 0, "PCCreate_BJacobi", PCCreate_BJacobi);CHKERRQ(ierr);
   ierr = PCRegister(PCILU, 0, "PCCreate_ILU", PCCreate_ILU);CHKERRQ(ierr);      /* pcfactor.c: control flow only; the factored matrix comes from the operator's type */
   ierr = PCRegister(PCICC, 0, "PCCreate_ICC", PCCreate_ICC);CHKERRQ(ierr);
+  ierr = PCRegister(PCSOR, 0, "PCCreate_SOR", PCCreate_SOR);CHKERRQ(ierr);
   ierr = KSPRegister(KSPCG, 0, "KSPCreate_CG", KSPCreate_CG);CHKERRQ(ierr);
   ierr = KSPRegister(KSPGROPPCG, 0, "KSPCreate_GROPPCG", KSPCreate_GROPPCG);CHKERRQ(ierr);
   ierr = KSPRegister(KSPPIPECG, 0, "KSPCreate_PIPECG", KSPCreate_PIPECG);CHKERRQ(ierr);
@@ -168,6 +169,40 @@ PetscErrorCode PCCreate_Jacobi(PC pc) {
   jac->diag = NULL;
   pc->data = jac;
   pc->ops->setup = PCSetUp_Jacobi; pc->ops->apply = PCApply_Jacobi; pc->ops->destroy = PCDestroy_Jacobi;
+  return 0;
+}
+
+/* ---------------------------------------------------------------- PCSOR (src/ksp/pc/impls/sor/sor.c): the operator's MatSOR from a zero guess */
+typedef struct { PetscInt its, lits; MatSORType sym; PetscReal omega, fshift; } PC_SOR;
+static PetscErrorCode PCApply_SOR(PC pc, Vec x, Vec y) {   /* sor.c:30-42 */
+  PC_SOR *jac = (PC_SOR *)pc->data;
+  return MatSOR(pc->pmat, x, jac->omega, (MatSORType)(jac->sym | SOR_ZERO_INITIAL_GUESS), jac->fshift, jac->its, jac->lits, y);
+}
+static PetscErrorCode PCSetFromOptions_SOR(PC pc) {   /* sor.c:75-105: the sweep options in the reference's order, the last one given wins */
+  static const struct { const char *name; MatSORType sym; } kinds[] = {
+    {"-pc_sor_symmetric", SOR_SYMMETRIC_SWEEP}, {"-pc_sor_backward", SOR_BACKWARD_SWEEP}, {"-pc_sor_forward", SOR_FORWARD_SWEEP},
+    {"-pc_sor_local_symmetric", SOR_LOCAL_SYMMETRIC_SWEEP}, {"-pc_sor_local_backward", SOR_LOCAL_BACKWARD_SWEEP}, {"-pc_sor_local_forward", SOR_LOCAL_FORWARD_SWEEP}};
+  PetscErrorCode ierr;
+  PC_SOR *jac = (PC_SOR *)pc->data;
+  PetscBool set; char buf[16];
+  ierr = PetscOptionsGetReal(pc->prefix, "-pc_sor_omega", &jac->omega, &set);CHKERRQ(ierr);
+  if (set && (jac->omega >= 2.0 || jac->omega <= 0.0)) SETERRQ(pc->comm, PETSC_ERR_ARG_OUTOFRANGE, "Relaxation out of range");
+  ierr = PetscOptionsGetReal(pc->prefix, "-pc_sor_diagonal_shift", &jac->fshift, &set);CHKERRQ(ierr);
+  ierr = PetscOptionsGetInt(pc->prefix, "-pc_sor_its", &jac->its, &set);CHKERRQ(ierr);
+  ierr = PetscOptionsGetInt(pc->prefix, "-pc_sor_lits", &jac->lits, &set);CHKERRQ(ierr);
+  for (size_t k = 0; k < sizeof(kinds) / sizeof(kinds[0]); k++) {
+    ierr = PetscOptionsGetString(pc->prefix, kinds[k].name, buf, sizeof(buf), &set);CHKERRQ(ierr);
+    if (set && strcmp(buf, "0") && strcmp(buf, "false")) jac->sym = kinds[k].sym;
+  }
+  return 0;
+}
+static PetscErrorCode PCDestroy_SOR(PC pc) { free(pc->data); pc->data = NULL; return 0; }
+PetscErrorCode PCCreate_SOR(PC pc) {   /* sor.c:330-350 */
+  PC_SOR *jac;
+  PetscErrorCode ierr = PetscMalloc(sizeof(*jac), &jac);CHKERRQ(ierr);
+  jac->sym = SOR_LOCAL_SYMMETRIC_SWEEP; jac->omega = 1.0; jac->fshift = 0.0; jac->its = 1; jac->lits = 1;
+  pc->data = jac;
+  pc->ops->apply = PCApply_SOR; pc->ops->setfromoptions = PCSetFromOptions_SOR; pc->ops->destroy = PCDestroy_SOR;
   return 0;
 }
 

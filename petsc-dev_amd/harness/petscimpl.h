@@ -133,6 +133,7 @@ struct _MatOps {
   PetscErrorCode (*zerorows)(Mat, PetscInt, const PetscInt[], PetscScalar, Vec, Vec);          /* slot 24 */
   PetscErrorCode (*zerorowscolumns)(Mat, PetscInt, const PetscInt[], PetscScalar, Vec, Vec);
   PetscErrorCode (*setoption)(Mat, MatOption, PetscBool);
+  PetscErrorCode (*sor)(Mat, Vec, PetscReal, MatSORType, PetscReal, PetscInt, PetscInt, Vec);   /* slot 13 */
   PetscErrorCode (*duplicate)(Mat, MatDuplicateOption, Mat *);   /* slot 34 */
   PetscErrorCode (*setfromoptions)(Mat);                 /* slot 76 */
   PetscErrorCode (*destroy)(Mat);                        /* slot 60 */
@@ -213,7 +214,7 @@ PetscErrorCode KSP_MatMult(KSP ksp, Mat A, Vec x, Vec y);
 PetscErrorCode KSP_PCApply(KSP ksp, Vec x, Vec y);
 PetscErrorCode KSP_PCApplyBAorAB(KSP ksp, Vec x, Vec y, Vec w);
 PetscErrorCode KSPCreate_CG(KSP), KSPCreate_GROPPCG(KSP), KSPCreate_PIPECG(KSP), KSPCreate_GMRES(KSP), KSPCreate_BCGS(KSP), KSPCreate_PREONLY(KSP);
-PetscErrorCode PCCreate_None(PC), PCCreate_Jacobi(PC), PCCreate_BJacobi(PC), PCCreate_ILU(PC), PCCreate_ICC(PC);
+PetscErrorCode PCCreate_None(PC), PCCreate_Jacobi(PC), PCCreate_BJacobi(PC), PCCreate_ILU(PC), PCCreate_ICC(PC), PCCreate_SOR(PC);
 
 #include "petsckrylovfused.h"   /* the optional fused-kernel tables a Vec / Mat type may compose */
 

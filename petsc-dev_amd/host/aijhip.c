@@ -169,6 +169,17 @@ static PetscErrorCode hip_mat_option(Mat A, int which, PetscInt *val) {
   if (d->opt_set[which]) { *val = d->opt[which]; return 0; }
   return PetscOptionsGetInt(NULL, hopt_name[which], val, &set);
 }
+/* -mat_hipmi355x_sor <device|host> (default device): where MatSOR runs; 0: the option is not given under this prefix */
+static PetscErrorCode sor_route_option(Mat A, const char *prefix, int *route) {
+  PetscErrorCode ierr;
+  char kind[16] = ""; PetscBool set = PETSC_FALSE;
+  *route = 0;
+  ierr = PetscOptionsGetString(prefix, "-mat_hipmi355x_sor", kind, sizeof(kind), &set);CHKERRQ(ierr);
+  if (!set) return 0;
+  if (strcmp(kind, "device") && strcmp(kind, "host")) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "-mat_hipmi355x_sor <device|host>, got %s", kind);
+  *route = strcmp(kind, "host") ? 1 : 2;
+  return 0;
+}
 static PetscErrorCode MatSetFromOptions_SeqAIJHIP(Mat A) {
   PetscErrorCode ierr;
   Mat_SeqAIJHIP *d = SD(A);
@@ -180,6 +191,9 @@ static PetscErrorCode MatSetFromOptions_SeqAIJHIP(Mat A) {
       if (k != HOPT_UPDATE_DEV) mirror_reset(d);             /* the analyses run again with the new choice */
     }
   }
+  { int route = 0;
+    ierr = sor_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
+    if (route) d->sor.route = route; }
   return 0;
 }
 
@@ -209,6 +223,14 @@ static void value_maps_free(Mat_SeqAIJHIP *d) {   /* what MatShift / MatAXPY / M
   if (d->zr_rows_d) mi355x_free(d->zr_rows_d);
   if (d->zr_mask_d) mi355x_free(d->zr_mask_d);
   d->zr_rows_d = NULL; d->zr_mask_d = NULL; d->zr_n = d->zr_words = 0; d->zr_have = PETSC_FALSE;
+  /* MatSOR: the level plan and the work arrays of both routes */
+  if (d->sor.plan) mi355x_sor_plan_destroy(d->sor.plan);
+  if (d->sor.d_idiag) mi355x_free(d->sor.d_idiag);
+  if (d->sor.d_mdiag) mi355x_free(d->sor.d_mdiag);
+  if (d->sor.d_t) mi355x_free(d->sor.d_t);
+  HipFree(d->sor.h_idiag); HipFree(d->sor.h_mdiag); HipFree(d->sor.h_t);
+  d->sor.plan = NULL; d->sor.plan_gen = 0; d->sor.d_idiag = d->sor.d_mdiag = d->sor.d_t = NULL; d->sor.have = PETSC_FALSE;
+  d->sor.h_idiag = d->sor.h_mdiag = d->sor.h_t = NULL; d->sor.h_have = PETSC_FALSE; d->sor.h_m = 0;
 }
 /* the arrays of the old pattern go; counts, requests, options, timing and (harness) the triangular factors outlive them */
 static PetscErrorCode device_free(Mat A) {
@@ -1582,6 +1604,164 @@ static PetscErrorCode zero_rows_new_pattern(Mat A, PetscInt n, const PetscInt ro
 }
 #endif
 
+/* MatSOR (MatSOR_SeqAIJ, aij.c:1463; the inverted diagonal of MatInvertDiagonal_SeqAIJ): its * lits point sweeps of the enabled directions,
+ * the first one in the zero-guess form when SOR_ZERO_INITIAL_GUESS is set.  A matrix with inodes takes the point sweeps too (the reference
+ * under -mat_no_inode).
+ * Device route: the matrix's own device arrays (sent first when the host copy is newer, as for a product), the vectors on the device, the
+ * sweeps level by level (csrc/sor.hip); t, the two diagonals and the level plan stay with the matrix -- the plan for one pattern upload,
+ * the diagonals for one upload state and one (omega, fshift).  No host wait per call.
+ * Host route: the same loops on the host copy -- a compressed-row form, or -mat_hipmi355x_sor host (per matrix; a matrix never asked reads
+ * the global database).  Same bits: one product and one difference per entry, in storage order, on both.
+ * Every error is raised before anything is written. */
+enum { SOR_FWD_BITS = SOR_FORWARD_SWEEP | SOR_LOCAL_FORWARD_SWEEP, SOR_BWD_BITS = SOR_BACKWARD_SWEEP | SOR_LOCAL_BACKWARD_SWEEP };
+#define SOR_MINUS_DOT(sum, k0, k1) do { for (PetscInt k_ = (k0); k_ < (k1); k_++) (sum) -= aa[k_] * x[aj[k_]]; } while (0)
+static void sor_host_sweeps(const HipAIJ *a, const PetscInt *pos, const PetscScalar *idiag, const PetscScalar *mdiag, PetscReal omega, int flag,
+                            PetscInt its, const PetscScalar *b, PetscScalar *t, PetscScalar *x) {
+  const PetscInt m = a->m, *ai = a->i, *aj = a->j; const PetscScalar *aa = a->a;
+  const PetscBool fwd = (PetscBool)((flag & SOR_FWD_BITS) != 0), bwd = (PetscBool)((flag & SOR_BWD_BITS) != 0);
+  if (flag & SOR_ZERO_INITIAL_GUESS) {
+    const PetscScalar *xb = b;
+    if (fwd) {
+      for (PetscInt i = 0; i < m; i++) { PetscScalar sum = b[i]; SOR_MINUS_DOT(sum, ai[i], pos[i]); t[i] = sum; x[i] = sum * idiag[i]; }
+      xb = t;
+    }
+    if (bwd) for (PetscInt i = m - 1; i >= 0; i--) {
+      PetscScalar sum = xb[i];
+      SOR_MINUS_DOT(sum, pos[i] + 1, ai[i + 1]);
+      if (xb == b) x[i] = sum * idiag[i];
+      else x[i] = (1. - omega) * x[i] + sum * idiag[i];
+    }
+    its--;
+  }
+  while (its--) {
+    if (fwd) for (PetscInt i = 0; i < m; i++) {
+      PetscScalar sum = b[i];
+      SOR_MINUS_DOT(sum, ai[i], ai[i + 1]);
+      x[i] = (1. - omega) * x[i] + (sum + mdiag[i] * x[i]) * idiag[i];
+    }
+    if (bwd) for (PetscInt i = m - 1; i >= 0; i--) {
+      PetscScalar sum = b[i];
+      SOR_MINUS_DOT(sum, ai[i], ai[i + 1]);
+      x[i] = (1. - omega) * x[i] + (sum + mdiag[i] * x[i]) * idiag[i];
+    }
+  }
+}
+/* what MatInvertDiagonal_SeqAIJ refuses, on the host copy: a row without a diagonal entry; a stored zero that would be inverted as it is */
+static PetscErrorCode sor_diag_check(Mat A, PetscReal omega, PetscReal fshift, const PetscInt **pos_) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A);
+  const PetscInt *pos; PetscBool full;
+  ierr = shift_diag_positions(A, &pos, &full);CHKERRQ(ierr);
+  if (!full) for (PetscInt r = 0; r < a->m; r++) if (pos[r] < 0) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "Matrix is missing diagonal entry in row %d", r);
+  if (omega == 1.0 && fshift == 0.0) for (PetscInt r = 0; r < a->m; r++) if (a->a[pos[r]] == 0.0) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_INCOMP, "Zero diagonal on row %d", r);
+  *pos_ = pos;
+  return 0;
+}
+static PetscErrorCode sor_on_host(Mat A, Vec bb, PetscReal omega, int flag, PetscReal fshift, PetscInt its, Vec xx) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
+  const PetscInt m = a->m, *pos = NULL;
+  const PetscScalar *b; PetscScalar *x;
+  const PetscBool fresh = (PetscBool)(d->sor.h_have && d->sor.h_m == m && d->sor.h_state == HipObjState(A) && d->sor.h_omega == omega && d->sor.h_fshift == fshift);
+  ierr = sor_diag_check(A, omega, fshift, &pos);CHKERRQ(ierr);
+  if (!fresh) {
+    if (d->sor.h_m != m || !d->sor.h_idiag) {
+      HipFree(d->sor.h_idiag); HipFree(d->sor.h_mdiag); HipFree(d->sor.h_t); d->sor.h_idiag = d->sor.h_mdiag = d->sor.h_t = NULL; d->sor.h_have = PETSC_FALSE;
+      ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(m, 1), &d->sor.h_idiag);CHKERRQ(ierr);
+      ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(m, 1), &d->sor.h_mdiag);CHKERRQ(ierr);
+      ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(m, 1), &d->sor.h_t);CHKERRQ(ierr);
+      d->sor.h_m = m;
+    }
+    for (PetscInt i = 0; i < m; i++) {
+      const PetscScalar v = a->a[pos[i]];
+      d->sor.h_mdiag[i] = v;
+      d->sor.h_idiag[i] = (omega == 1.0 && fshift == 0.0) ? 1.0 / v : omega / (fshift + v);
+    }
+    d->sor.h_state = HipObjState(A); d->sor.h_omega = omega; d->sor.h_fshift = fshift; d->sor.h_have = PETSC_TRUE;
+    d->sor.idiag_builds++;
+  }
+  ierr = VecGetArrayRead(bb, &b);CHKERRQ(ierr);
+  ierr = VecGetArray(xx, &x);CHKERRQ(ierr);
+  sor_host_sweeps(a, pos, d->sor.h_idiag, d->sor.h_mdiag, omega, flag, its, b, d->sor.h_t, x);
+  ierr = VecRestoreArrayRead(bb, &b);CHKERRQ(ierr);
+  ierr = VecRestoreArray(xx, &x);CHKERRQ(ierr);
+  ierr = VecHIPFlushBorrowed(xx);CHKERRQ(ierr);              /* a block-Jacobi block's slice of the parallel vector */
+  return 0;
+}
+static PetscErrorCode MatSOR_SeqAIJHIP(Mat A, Vec bb, PetscReal omega, MatSORType flag_, PetscReal fshift, PetscInt its, PetscInt lits, Vec xx) {
+  PetscErrorCode ierr;
+  HipAIJ *a; Mat_SeqAIJHIP *d = SD(A);
+  const int flag = (int)flag_;
+  int route;
+  ierr = value_op_view(A);CHKERRQ(ierr);
+  a = SA(A);
+  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  if (a->bs > 1) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "MatSOR on a block matrix");
+  if (flag & SOR_EISENSTAT) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "No support yet for Eisenstat");
+  if (flag & (SOR_APPLY_UPPER | SOR_APPLY_LOWER)) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "SOR_APPLY_UPPER or SOR_APPLY_LOWER is not implemented");
+  if (a->m != a->n) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "MatSOR on a matrix that is not square: %d x %d", a->m, a->n);
+  if (its <= 0 || lits <= 0) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "Relaxation requires global its %d and local its %d both positive", its, lits);
+  if (bb == xx) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_IDN, "b and x vector cannot be the same");
+  its *= lits;
+  if (!d->sor.route) {                                          /* never asked under its prefix: the global database, once per matrix */
+    ierr = sor_route_option(A, NULL, &route);CHKERRQ(ierr);
+    d->sor.route = route ? route : 1;
+  }
+  route = d->sor.route;
+  if (route != 2) {
+    PetscDeviceCtx *dc;
+    const PetscScalar *db; PetscScalar *dx;
+    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+    ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);               /* the device values current, as before a product */
+    if (!d->cprow) {
+      const PetscBool rebuilt = (PetscBool)(!d->sor.plan || d->sor.plan_gen != d->pattern_gen);
+      if (rebuilt || !d->sor.have || d->sor.idiag_state != d->uploaded_state || d->sor.omega != omega || d->sor.fshift != fshift) {
+        const PetscInt *pos;
+        ierr = sor_diag_check(A, omega, fshift, &pos);CHKERRQ(ierr);
+        if (rebuilt) {
+          const size_t bytes = sizeof(PetscScalar) * (size_t)PetscMax(a->m, 1);
+          int bad = -1, rc;
+          if (d->sor.plan) mi355x_sor_plan_destroy(d->sor.plan);
+          d->sor.plan = NULL; d->sor.have = PETSC_FALSE;
+          rc = mi355x_sor_plan_create(dc->h, (int)a->m, a->i, a->j, 0, &d->sor.plan, &bad);
+          if (rc && bad >= 0) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "MatSOR: the columns of row %d are not sorted and distinct", bad);
+          CHKHIP(rc);
+          d->sor.plan_gen = d->pattern_gen; d->sor.plan_builds++;
+          if (!d->sor.d_t) {
+            CHKHIP(mi355x_malloc((void **)&d->sor.d_t, bytes));
+            CHKHIP(mi355x_malloc((void **)&d->sor.d_idiag, bytes));
+            CHKHIP(mi355x_malloc((void **)&d->sor.d_mdiag, bytes));
+          }
+        }
+        CHKHIP(mi355x_sor_idiag(dc->h, d->sor.plan, d->mat.a, omega, fshift, d->sor.d_idiag, d->sor.d_mdiag));
+        d->sor.idiag_state = d->uploaded_state; d->sor.omega = omega; d->sor.fshift = fshift; d->sor.have = PETSC_TRUE;
+        d->sor.idiag_builds++;
+      }
+      ierr = VecHIPGetRead(bb, &db);CHKERRQ(ierr);
+      if ((flag & SOR_ZERO_INITIAL_GUESS) && (flag & (SOR_FWD_BITS | SOR_BWD_BITS))) { ierr = VecHIPGetWrite(xx, &dx);CHKERRQ(ierr); }   /* every entry is written before it is read */
+      else { ierr = VecHIPGetReadWrite(xx, &dx);CHKERRQ(ierr); }
+      CHKHIP(mi355x_sor_apply(dc->h, d->sor.plan, d->mat.i, d->mat.j, d->mat.a, d->sor.d_idiag, d->sor.d_mdiag, omega,
+                              flag & (SOR_FWD_BITS | SOR_BWD_BITS | SOR_ZERO_INITIAL_GUESS), (int)its, db, d->sor.d_t, dx));
+      ierr = VecHIPRestoreWrite(xx);CHKERRQ(ierr);
+      d->sor.device_applications++;
+      return PetscLogFlops(2.0 * (PetscLogDouble)a->nz * (PetscLogDouble)its);
+    }
+  }
+  ierr = sor_on_host(A, bb, omega, flag, fshift, its, xx);CHKERRQ(ierr);
+  return PetscLogFlops(2.0 * (PetscLogDouble)a->nz * (PetscLogDouble)its);
+}
+PetscErrorCode MatHIPMI355XGetSORInfo(Mat A, PetscInt *levels, PetscInt *launches_per_sweep, PetscInt *idiag_builds, PetscInt *plan_builds, PetscInt *device_applications) {
+  if (!A || A->ops->mult != MatMult_SeqAIJHIP) SETERRQ(A ? HipObjComm(A) : 0, PETSC_ERR_ARG_WRONG, "not a sequential HIPMI355X AIJ matrix");
+  int nlev = 0, launches = 0;
+  if (SD(A)->sor.plan) CHKHIP(mi355x_sor_plan_info(SD(A)->sor.plan, &nlev, &launches, NULL));
+  if (levels) *levels = nlev;
+  if (launches_per_sweep) *launches_per_sweep = launches;
+  if (idiag_builds) *idiag_builds = SD(A)->sor.idiag_builds;
+  if (plan_builds) *plan_builds = SD(A)->sor.plan_builds;
+  if (device_applications) *device_applications = SD(A)->sor.device_applications;
+  return 0;
+}
+
 static PetscErrorCode MatGetVecs_HIP(Mat A, Vec *right, Vec *left) {   /* MatGetVecs_SeqAIJCUSP aijcusp.cu:324-345 */
   PetscErrorCode ierr;
   if (right) {
@@ -1653,6 +1833,7 @@ static PetscErrorCode create_common(Mat B, const char *tname, PetscInt bs) {
   B->ops->zerorows = MatZeroRows_SeqAIJHIP;
   B->ops->zerorowscolumns = MatZeroRowsColumns_SeqAIJHIP;
   B->ops->setoption = MatSetOption_SeqAIJHIP;
+  B->ops->sor = MatSOR_SeqAIJHIP;
   B->ops->diagonalscale = MatDiagonalScale_SeqAIJHIP;
   B->ops->setvaluesbatch = MatSetValuesBatch_SeqAIJHIP;
   B->ops->duplicate = MatDuplicate_SeqAIJHIP;
@@ -1689,7 +1870,7 @@ static PetscErrorCode MatDuplicate_SeqAIJHIP(Mat A, MatDuplicateOption op, Mat *
   ierr = adopt_csr(B, a->m, a->bs > 1 ? a->bs : 1, a->i, a->j, a->a);CHKERRQ(ierr);
   if (op != MAT_COPY_VALUES) memset(SA(B)->a, 0, sizeof(PetscScalar) * (size_t)a->nz * (size_t)(a->bs > 1 ? a->bs * a->bs : 1));
   memcpy(SD(B)->opt, SD(A)->opt, sizeof(SD(A)->opt)); memcpy(SD(B)->opt_set, SD(A)->opt_set, sizeof(SD(A)->opt_set));
-  SD(B)->cprow = SD(A)->cprow;
+  SD(B)->cprow = SD(A)->cprow; SD(B)->sor.route = SD(A)->sor.route;
   SA(B)->keepnonzeropattern = a->keepnonzeropattern;
   *M = B;
   return 0;

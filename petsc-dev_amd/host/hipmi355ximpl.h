@@ -75,6 +75,7 @@ PetscErrorCode VecHIPGetRead(Vec v, const PetscScalar **d);
 PetscErrorCode VecHIPGetWrite(Vec v, PetscScalar **d);       /* contents will be overwritten */
 PetscErrorCode VecHIPGetReadWrite(Vec v, PetscScalar **d);
 PetscErrorCode VecHIPRestoreWrite(Vec v);                    /* device newer; state++ */
+PetscErrorCode VecHIPFlushBorrowed(Vec v);                   /* v borrows another vector's device storage and was written on the host: the values go there now (else nothing) */
 #define PETSC_HIP_DPI_SLOT 8   /* device scratch slot holding p'w between the dot (or the SpMV by-product) and the CG update */
 PetscErrorCode MatMultTDotBegin_HIPMI355X(Mat A, Vec x, Vec y, PetscBool *ok);   /* y = A x, x'y left on the device */
 PetscErrorCode MatMultDiagonalScale_HIPMI355X(Mat A, Vec d, Vec x, Vec y, PetscBool *ok);   /* y = d .* (A x) */
@@ -255,6 +256,17 @@ typedef struct {
    * uploads of a list to the device, updates that ran on the device copy */
   PetscInt *zr_rows_h, *zr_rows_d, zr_n, zr_words; unsigned int *zr_mask_h, *zr_mask_d; PetscBool zr_have;
   PetscInt zr_list_uploads, zr_device_updates;
+  /* MatSOR (host/aijhip.c, "MatSOR"): the level plan of the pattern upload plan_gen (csrc/sor.hip), and with the matrix the work vector t
+   * and the inverted / plain diagonal -- on the device as built for the values of upload state idiag_state with (omega, fshift), on the
+   * host (the host route) for the object state h_state.  route: -mat_hipmi355x_sor <device|host> as MatSetFromOptions read it, or as the first
+   * MatSOR found it in the global database (0: not looked up yet, 1 device, 2 host).  The counts outlive the arrays: diagonal builds (either route), plan builds, applications on the device */
+  struct {
+    mi355x_sor_plan_t plan; unsigned long long plan_gen;
+    PetscScalar *d_idiag, *d_mdiag, *d_t; int idiag_state; PetscReal omega, fshift; PetscBool have;
+    PetscScalar *h_idiag, *h_mdiag, *h_t; int h_state; PetscReal h_omega, h_fshift; PetscBool h_have; PetscInt h_m;
+    int route;
+    PetscInt idiag_builds, plan_builds, device_applications;
+  } sor;
   PetscInt opt[8]; PetscBool opt_set[8];   /* the type's options as MatSetFromOptions read them under the matrix's prefix (host/aijhip.c) */
   /* per-launch device timing for bench.py (hipEvent pairs on the compute stream) */
   PetscBool timing; PetscInt time_n, time_cap; mi355x_event_t *time_ev;
@@ -289,6 +301,7 @@ typedef struct {
   PetscInt rstart, rend, cstart, cend;
   HipStash stash;           /* off-process MatSetValues (harness flavour) */
   PetscBool keepnonzeropattern;   /* MAT_KEEP_NONZERO_PATTERN for blocks that are made later (harness flavour; the blocks hold their own) */
+  Vec sor_bb1;              /* MatSOR: b + B lvec of the outer steps; made by the first call that needs it */
 } HipMPIAIJ;
 #if defined(PETSCHIPMI355X_WITH_PETSC)
 #define HipMPIAIJGet(A) ((HipMPIAIJ *)(A)->spptr)

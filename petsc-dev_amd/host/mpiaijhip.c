@@ -309,6 +309,43 @@ static PetscErrorCode MatZeroRowsColumns_MPIAIJHIP(Mat A, PetscInt n, const Pets
   (void)n; (void)rows; (void)diag; (void)xx; (void)bb;
   SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "MatZeroRowsColumns of a parallel matrix is not supported: use MatZeroRows, or a sequential matrix");
 }
+/* MatSOR_MPIAIJ (mpiaij.c): the local sweeps only -- each process relaxes its diagonal block, the other processes' unknowns frozen for
+ * the lits sweeps of one outer step.  From a zero guess the first step is the block's own MatSOR on b; every further step moves x into
+ * the halo (the MatMult scatter), forms bb1 = b - B x_halo (lvec negated, then the off-diagonal block's multadd) and relaxes the block on
+ * bb1 with the non-local twin of the sweep.  bb1 stays with the matrix and is made by the first call that takes such a step.  A sweep
+ * over the whole parallel matrix (a non-local bit), Eisenstat's trick and the triangular applications are refused */
+static PetscErrorCode MatSOR_MPIAIJHIP(Mat A, Vec bb, PetscReal omega, MatSORType flag_, PetscReal fshift, PetscInt its, PetscInt lits, Vec xx) {
+  PetscErrorCode ierr;
+  HipMPIAIJ *a = MA(A);
+  MPI_Comm comm = HipObjComm(A);
+  const int flag = (int)flag_;
+  MatSORType twin;
+  (void)comm;
+  if (!a->A || !a->B || !a->garray) SETERRQ(comm, PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  if (flag & (SOR_EISENSTAT | SOR_APPLY_UPPER | SOR_APPLY_LOWER)) SETERRQ(comm, PETSC_ERR_SUP, "Eisenstat and SOR_APPLY_UPPER / SOR_APPLY_LOWER are not supported on a parallel matrix");
+  if (flag & SOR_SYMMETRIC_SWEEP) SETERRQ(comm, PETSC_ERR_SUP, "Parallel SOR not supported");
+  if ((flag & SOR_LOCAL_SYMMETRIC_SWEEP) == SOR_LOCAL_SYMMETRIC_SWEEP) twin = SOR_SYMMETRIC_SWEEP;
+  else if (flag & SOR_LOCAL_FORWARD_SWEEP) twin = SOR_FORWARD_SWEEP;
+  else if (flag & SOR_LOCAL_BACKWARD_SWEEP) twin = SOR_BACKWARD_SWEEP;
+  else SETERRQ(comm, PETSC_ERR_SUP, "Parallel SOR not supported");
+  if (!a->A->ops->sor || !a->B->ops->multadd) SETERRQ(comm, PETSC_ERR_SUP, "the blocks have no MatSOR");
+  if (its <= 0 || lits <= 0) SETERRQ(comm, PETSC_ERR_ARG_WRONG, "Relaxation requires global its %d and local its %d both positive", its, lits);
+  if (bb == xx) SETERRQ(comm, PETSC_ERR_ARG_IDN, "b and x vector cannot be the same");
+  if (flag & SOR_ZERO_INITIAL_GUESS) {
+    ierr = (*a->A->ops->sor)(a->A, bb, omega, (MatSORType)flag, fshift, lits, 1, xx);CHKERRQ(ierr);
+    its--;
+  }
+  if (its > 0 && !a->sor_bb1) { ierr = VecDuplicate(bb, &a->sor_bb1);CHKERRQ(ierr); }
+  while (its-- > 0) {
+    ierr = HipScatterBegin(a->hscat, xx, a->lvec, INSERT_VALUES, SCATTER_FORWARD);CHKERRQ(ierr);
+    ierr = HipScatterEnd(a->hscat, xx, a->lvec, INSERT_VALUES, SCATTER_FORWARD);CHKERRQ(ierr);
+    ierr = (*a->lvec->ops->scale)(a->lvec, -1.0);CHKERRQ(ierr);   /* the vector's own slot: the plug-in takes no VecScale from the object model */
+    HipStateIncrease(a->lvec);
+    ierr = (*a->B->ops->multadd)(a->B, a->lvec, bb, a->sor_bb1);CHKERRQ(ierr);
+    ierr = (*a->A->ops->sor)(a->A, a->sor_bb1, omega, twin, fshift, lits, 1, xx);CHKERRQ(ierr);
+  }
+  return 0;
+}
 static PetscErrorCode mpi_value_op_pair(Mat Y, Mat X) {
   if (!X || strcmp(HipObjTypeName(X), MATMPIAIJHIPMI355X) || strcmp(HipObjTypeName(Y), MATMPIAIJHIPMI355X)) SETERRQ(HipObjComm(Y), PETSC_ERR_SUP, "both matrices must be MPIAIJHIPMI355X matrices");
   if (X->rmap->rstart != Y->rmap->rstart || X->rmap->rend != Y->rmap->rend || X->cmap->rstart != Y->cmap->rstart || X->cmap->rend != Y->cmap->rend)
@@ -365,6 +402,7 @@ static PetscErrorCode MatDestroy_MPIAIJHIP(Mat A) {
   ierr = MatDestroy(&a->A);CHKERRQ(ierr);
   ierr = MatDestroy(&a->B);CHKERRQ(ierr);
   ierr = VecDestroy(&a->lvec);CHKERRQ(ierr);
+  ierr = VecDestroy(&a->sor_bb1);CHKERRQ(ierr);
   ierr = HipScatterDestroy(&a->hscat);CHKERRQ(ierr);
   HipFree(a->garray);
   HipStashFree(&a->stash);
@@ -399,6 +437,7 @@ PetscErrorCode MatCreate_MPIAIJHIPMI355X(Mat B) {   /* MatCreate_MPIAIJCUSP, mpi
   B->ops->zerorows = MatZeroRows_MPIAIJHIP;
   B->ops->zerorowscolumns = MatZeroRowsColumns_MPIAIJHIP;
   B->ops->setoption = MatSetOption_MPIAIJHIP;
+  B->ops->sor = MatSOR_MPIAIJHIP;
   B->ops->diagonalscale = MatDiagonalScale_MPIAIJHIP;
   B->ops->destroy = MatDestroy_MPIAIJHIP;
   B->ops->getvecs = MatGetVecs_HIPMI355X;

@@ -1116,6 +1116,13 @@ static PetscErrorCode VecShareSubArrayEnd_HIP(Vec sub, Vec parent, PetscInt offs
   if (write) return VecHIPRestoreWrite(parent);
   return 0;
 }
+/* a vector that borrows storage keeps no host result past VecShareSubArrayEnd (its own flags come back): an operation that wrote such a
+ * vector through VecGetArray sends the values into the borrowed storage before it returns */
+PetscErrorCode VecHIPFlushBorrowed(Vec v) {
+  const PetscScalar *d;
+  if (!v || !v->data || !strstr(HipObjTypeName(v), "hipmi355x") || !VH(v)->alias_save || (VH(v)->valid & VALID_DEVICE)) return 0;
+  return VecHIPGetRead(v, &d);
+}
 static PetscErrorCode VecShareArrayBegin_HIP(Vec sub, Vec parent, PetscBool write) {
   if (sub->map->n != parent->map->n) SETERRQ(HipObjComm(sub), PETSC_ERR_ARG_SIZ, "local sizes %d and %d differ", sub->map->n, parent->map->n);
   return VecShareSubArrayBegin_HIP(sub, parent, 0, write);

@@ -48,6 +48,7 @@ _SIG = {
     "MatShift": [vp, dbl], "MatAXPY": [vp, dbl, vp, i32], "MatAYPX": [vp, dbl, vp, i32], "MatCopy": [vp, vp, i32],
     "MatZeroRows": [vp, i32, vp, dbl, vp, vp], "MatZeroRowsColumns": [vp, i32, vp, dbl, vp, vp], "MatSetOption": [vp, i32, i32],
     "MatHIPMI355XGetZeroRowsCounts": [vp, P(i32), P(i32)],
+    "MatSOR": [vp, vp, dbl, i32, dbl, i32, i32, vp], "MatHIPMI355XGetSORInfo": [vp, P(i32), P(i32), P(i32), P(i32), P(i32)],
     "MatSeqAIJGetArrays": [vp, P(i32), P(vp), P(vp), P(vp)], "MatMPIAIJGetSeqAIJ": [vp, P(vp), P(vp), P(vp)],
     "MatMPIAIJGetScatter": [vp, P(vp), P(vp), P(i32)],
     "MatHIPMI355XSetTiming": [vp, i32], "MatHIPMI355XGetTiming": [vp, P(i32), P(dbl)],
@@ -57,6 +58,7 @@ _SIG = {
     "PetscMiniGenPoisson7": [i32, i32, i32, C.c_long, C.c_long, vp, vp, vp, P(C.c_long)],
     "PetscViewerBinaryOpen": [vp, C.c_char_p, i32, P(vp)], "PetscViewerDestroy": [P(vp)],
     "MatLoad": [vp, vp], "MatView": [vp, vp], "VecLoad": [vp, vp], "VecView": [vp, vp],
+    "PCCreate": [vp, P(vp)], "PCSetOperators": [vp, vp, vp, i32], "PCSetFromOptions": [vp], "PCApply": [vp, vp, vp], "PCDestroy": [P(vp)],
     "PCSetType": [vp, C.c_char_p], "PCILUGetLevels_HIPMI355X": [vp, P(i32), P(i32)], "PCILUGetShiftCount_HIPMI355X": [vp, P(i32)], "PCICCGetInfo_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCILUGetSolver_HIPMI355X": [vp, P(i32), P(i32)], "PCFactorDebugSetAborted_HIPMI355X": [vp], "PCILUGetSweeps_HIPMI355X": [vp, P(i32)], "PCILUGetNumeric_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCILUApplyInPlace_HIPMI355X": [vp, vp], "PCILUGetNodeInfo_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCFactorGetMatrix": [vp, P(vp)], "MatSolve": [vp, vp, vp], "PCBJacobiGetSubKSP": [vp, P(i32), P(i32), P(vp)],
     "KSPCreate": [vp, P(vp)], "KSPSetType": [vp, C.c_char_p], "KSPSetOperators": [vp, vp, vp, i32], "KSPGetPC": [vp, P(vp)],
     "KSPSetTolerances": [vp, dbl, dbl, dbl, i32], "KSPSetNormType": [vp, i32], "KSPSetPCSide": [vp, i32], "KSPSetInitialGuessNonzero": [vp, i32], "KSPSetOptionsPrefix": [vp, C.c_char_p],
@@ -78,6 +80,10 @@ MAT_FINAL_ASSEMBLY, MAT_FLUSH_ASSEMBLY = 0, 1
 PETSC_DECIDE, PETSC_DEFAULT = -1, -2
 DIFFERENT_NONZERO_PATTERN, SUBSET_NONZERO_PATTERN, SAME_NONZERO_PATTERN = 0, 1, 2
 MAT_KEEP_NONZERO_PATTERN = 9          # MatOption (petscmini.h)
+# MatSORType (petscmini.h)
+SOR_FORWARD_SWEEP, SOR_BACKWARD_SWEEP, SOR_SYMMETRIC_SWEEP = 1, 2, 3
+SOR_LOCAL_FORWARD_SWEEP, SOR_LOCAL_BACKWARD_SWEEP, SOR_LOCAL_SYMMETRIC_SWEEP = 4, 8, 12
+SOR_ZERO_INITIAL_GUESS, SOR_EISENSTAT, SOR_APPLY_UPPER, SOR_APPLY_LOWER = 16, 32, 64, 128
 
 
 class PetscError(RuntimeError):
@@ -291,6 +297,16 @@ class Mat:
 
     def set_option(self, op, flag=True):
         lib().MatSetOption(self.h, op, 1 if flag else 0)
+
+    def sor(self, b, x, omega=1.0, flag=SOR_LOCAL_SYMMETRIC_SWEEP, shift=0.0, its=1, lits=1):
+        """its * lits (S)SOR sweeps on A x = b, x updated in place; flag: SOR_* bits, SOR_ZERO_INITIAL_GUESS to ignore x's content (MatSOR)"""
+        lib().MatSOR(self.h, b.h, omega, flag, shift, its, lits, x.h)
+
+    def sor_info(self):
+        """levels, launches per sweep, inverted-diagonal builds, plan builds, device applications (MatHIPMI355XGetSORInfo)"""
+        v = [i32() for _ in range(5)]
+        lib().MatHIPMI355XGetSORInfo(self.h, *[C.byref(q) for q in v])
+        return tuple(q.value for q in v)
 
     def local_size(self):
         m, n = i32(), i32()
