@@ -64,6 +64,7 @@ PetscErrorCode PetscCommDeviceAllreduceLatency(PetscComm comm, PetscInt reps, Pe
  * off).  Every access to a vector's storage does this by itself; the call exists for timing code. */
 PetscErrorCode VecHIPMI355XFlushDeferred(void);
 PetscErrorCode VecHIPMI355XSetDeferral(PetscInt on);   /* 1 / 0; negative: back to what -vec_hipmi355x_defer says */
+PetscErrorCode VecHIPMI355XGetDeferralCounts(PetscInt counts[8]);   /* read-only: how often each shortcut of the noted operations was taken so far */
 PetscErrorCode VecScatterBegin(VecScatter ctx, Vec x, Vec y, InsertMode addv, ScatterMode mode);
 PetscErrorCode VecScatterEnd(VecScatter ctx, Vec x, Vec y, InsertMode addv, ScatterMode mode);
 PetscErrorCode VecScatterDestroy(VecScatter *ctx);

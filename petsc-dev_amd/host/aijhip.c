@@ -1547,7 +1547,7 @@ static PetscErrorCode zero_rows_keep_pattern(Mat A, PetscInt n, const PetscInt r
     /* the two kernels write disjoint entries and disjoint rows of b: the columns of the rows that are not listed, then the listed rows */
     if (cols) CHKHIP(mi355x_csr_zero_columns(dc->h, d->mat.plan, d->mat.i, d->mat.j, d->mat.a, d->zr_mask_d, dx, db));
     CHKHIP(mi355x_csr_zero_rows(dc->h, (int)n, d->zr_rows_d, d->mat.i, d->mat.j, d->mat.a, diag, dx, db));
-    if (xx) { ierr = VecHIPRestoreWrite(bb);CHKERRQ(ierr); }
+    if (xx) { ierr = VecHIPRestoreWrite(bb);CHKERRQ(ierr); HipStateIncrease(bb); }   /* as the host route's VecRestoreArray does */
     d->zr_device_updates++;
   } else d->uploaded_state = -1;
   return 0;

@@ -202,6 +202,7 @@ PetscErrorCode VecHIPNoteProduct(Mat A, Vec x, Vec t, HipProductNowFn now, HipPr
 PetscErrorCode VecHIPProductMatrixChanges(Mat A);              /* to be called before A's device values change or go away */
 PetscErrorCode VecHIPMI355XFlushDeferred(void);                /* host/vechip.c: run the noted element-wise operations */
 PetscErrorCode VecHIPMI355XSetDeferral(PetscInt on);
+PetscErrorCode VecHIPMI355XGetDeferralCounts(PetscInt counts[8]);   /* shortcuts taken so far: CG sweep, BiCGStab update, MAXPY + norm, product + dot, product + dotnorm2, scaled product, work vector written late, dot answered from the kept value */
 void HipFactorJoinHelpers(void);                              /* host/ilu.c: the thread that returns the factorisation's work arrays */
 PetscErrorCode HipTriWatchCheck(void);                     /* at every host wait: did a sync-free solve queued earlier give up? */
 void HipTriWatchAdd(HipTriFactors *f);

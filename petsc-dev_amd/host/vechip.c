@@ -73,6 +73,10 @@ static struct {
 typedef struct { int on; Mat A; long astate; Vec x, t; HipProductNowFn now; HipProductScaledFn scaled; } PendingProduct;
 static PendingProduct pp, pl;
 static int pp_busy;
+/* how often each shortcut was taken (VecHIPMI355XGetDeferralCounts): counted where it succeeds, read by the tests only */
+enum { DC_CG_SWEEP, DC_BCGS_UPDATE, DC_MAXPY_NORM, DC_PMULT_DOT, DC_PMULT_DOTNORM2, DC_SCALED_PRODUCT, DC_LATE_PRODUCT, DC_KEPT_DOT, DC_N };
+static PetscInt dcount[DC_N];
+PetscErrorCode VecHIPMI355XGetDeferralCounts(PetscInt counts[8]) { for (int k = 0; k < DC_N; k++) counts[k] = dcount[k]; return 0; }
 static PetscErrorCode product_run(PendingProduct *q);
 static PetscErrorCode deferred_flush(void);
 #define FLUSH_DEFERRED() do { if ((dq.n && !dq.busy) || (pp.on && !pp_busy)) { PetscErrorCode e__ = deferred_flush();CHKERRQ(e__); } } while (0)
@@ -284,6 +288,7 @@ static PetscErrorCode product_run(PendingProduct *q) {
   ierr = (*r.now)(r.A, r.x, r.t);
   pp_busy = 0;
   CHKERRQ(ierr);
+  if (q == &pl) dcount[DC_LATE_PRODUCT]++;
   return 0;
 }
 /* a vector is about to be written by something that does not pass the accessors' checks (pp_busy): the unwritten t is dead if it is
@@ -356,6 +361,7 @@ static PetscErrorCode deferred_sweep(PetscScalar *zz, PetscScalar *zr, PetscBool
   CHKERRQ(ierr);
   if (!*done) return deferred_flush();
   dq.n = 0;
+  dcount[DC_CG_SWEEP]++;
   dq_keep(z, r, *zr);
   return 0;
 }
@@ -375,6 +381,7 @@ static PetscErrorCode deferred_bcgs_update(Vec rp, PetscScalar *rr, PetscScalar 
   CHKERRQ(ierr);
   if (!*done) return deferred_flush();
   dq.n = 0;
+  dcount[DC_BCGS_UPDATE]++;
   dq_keep(r, rp, *rho);
   return 0;
 }
@@ -470,6 +477,7 @@ static PetscErrorCode VecPointwiseMult_HIP(Vec w, Vec x, Vec y) {
       if (ok) {
         if (pl.on) { ierr = product_run(&pl);CHKERRQ(ierr); }          /* one unwritten work vector at a time */
         pl = pp; pp.on = 0;
+        dcount[DC_SCALED_PRODUCT]++;
         return 0;
       }
     }
@@ -607,8 +615,9 @@ static PetscErrorCode VecDot_HIP(Vec x, Vec y, PetscScalar *val) {
       ierr = VecPMultDot_HIPMI355X(o.o, o.a, o.b, x == o.o ? y : x, &v, &done);
       dq.busy = 0;
       CHKERRQ(ierr);
-      if (done) { dq.n = 0; *val = v; return 0; }
+      if (done) { dq.n = 0; dcount[DC_PMULT_DOT]++; *val = v; return 0; }
     } else if (!dq.n && dq_kept(x, y, &v)) {          /* left by the fused sweep that answered the VecNorm before */
+      dcount[DC_KEPT_DOT]++;
       *val = v;
       return 0;
     }
@@ -660,6 +669,7 @@ static PetscErrorCode deferred_maxpy_norm(PetscScalar *sumsq, PetscBool *done) {
   HipStateIncrease(y);
   ierr = reduce_finish(y, dc, 1, 0, sumsq);CHKERRQ(ierr);
   ierr = PetscLogFlops(nv * 2.0 * y->map->n + PetscMax(2.0 * y->map->n - 1, 0.0));CHKERRQ(ierr);
+  dcount[DC_MAXPY_NORM]++;
   *done = PETSC_TRUE;
   return 0;
 }
@@ -708,7 +718,7 @@ static PetscErrorCode VecDotNorm2_HIP(Vec s, Vec t, PetscScalar *dp, PetscScalar
     ierr = VecPMultDotNorm2_HIPMI355X(o.o, o.a, o.b, s, dp, &nrm2, &done);
     dq.busy = 0;
     CHKERRQ(ierr);
-    if (done) { dq.n = 0; *nm = nrm2; return 0; }
+    if (done) { dq.n = 0; dcount[DC_PMULT_DOTNORM2]++; *nm = nrm2; return 0; }
   }
   ierr = VecHIPGetRead(s, &ds_);CHKERRQ(ierr);
   ierr = VecHIPGetRead(t, &dt);CHKERRQ(ierr);
@@ -1113,7 +1123,7 @@ static PetscErrorCode VecShareSubArrayEnd_HIP(Vec sub, Vec parent, PetscInt offs
   if (pl.on && !pp_busy) { PetscErrorCode e__ = product_run(&pl);CHKERRQ(e__); }
   s->dev = s->alias_save; s->valid = s->alias_valid; s->alias_save = NULL;
   HipStateIncrease(sub);
-  if (write) return VecHIPRestoreWrite(parent);
+  if (write) { HipStateIncrease(parent); return VecHIPRestoreWrite(parent); }   /* the parent changed through the borrower: what is kept per object state (a dot, the wrappers' norms) is stale */
   return 0;
 }
 /* a vector that borrows storage keeps no host result past VecShareSubArrayEnd (its own flags come back): an operation that wrote such a

@@ -2707,6 +2707,52 @@ def test_noted_products_are_transparent(P):
     assert np.array_equal(bits(a1[1]), bits(t_ref)) and np.array_equal(bits(a1[2]), bits(w_ref))
 
 
+def test_values_changed_behind_the_wrappers_bump_the_object_state(P):
+    """Two programs the random call programs of tests/vecprog.py found, at their shortest.  A vector's values changed where no public
+    wrapper sees it -- through a borrower ("VecShareSubArrayEnd_C" with write access), and as the right-hand side MatZeroRows /
+    MatZeroRowsColumns correct on the device copy -- and its object state stayed: VecNorm answered with the norm kept for the old values,
+    and a VecTDot behind a fused sweep with the product kept for them.  The type bumps the state in both places now."""
+    import vecprog as vp
+    L = P.lib()
+    ai, aj, aa = pb.lap2d(23, 19)
+    n = ai.size - 1
+    rng = np.random.default_rng(11)
+    base = {k: rng.standard_normal(n) for k in "xprwzdb"}
+    val = C.c_double()
+    for on in (0, 1):
+        _deferral(P, on)
+        made = []
+        try:
+            v = {k: P.Vec.from_array(base[k], comm=L.COMM_SELF) for k in "xprwzdb"}
+            sub = P.Vec.from_array(np.ones(100), comm=L.COMM_SELF)
+            made += list(v.values()) + [sub]
+            begin, end = vp.share_functions(P, sub)
+            a = 0.37
+            L.VecAXPY(v["x"].h, a, v["p"].h); L.VecAXPY(v["r"].h, -a, v["w"].h); L.VecPointwiseMult(v["z"].h, v["r"].h, v["d"].h)
+            v["z"].norm()                                              # (the fused sweep with the noting on: z'r is kept)
+            L.chk(begin(sub.h, v["z"].h, 33, 1)); L.VecSet(sub.h, 3.0); L.chk(end(sub.h, v["z"].h, 33, 1))
+            z = (base["r"] - a * base["w"]) * base["d"]; z[33:133] = 3.0
+            r = base["r"] - a * base["w"]
+            L.VecTDot(v["z"].h, v["r"].h, C.byref(val))
+            assert abs(val.value - z @ r) <= 1e-12 * np.abs(z * r).sum(), on
+            assert abs(v["z"].norm() - np.linalg.norm(z)) <= 1e-12 * np.linalg.norm(z), on
+            # the right-hand side of MatZeroRows, updated on the device copy of a matrix that is current there
+            A = P.Mat.from_csr(ai, aj, aa); A.set_option(P.MAT_KEEP_NONZERO_PATTERN, True)
+            made.append(A)
+            A.mult(v["p"], v["w"])
+            rows = [3, 40, 200]
+            for f in (A.zero_rows, A.zero_rows_columns):
+                before = v["b"].norm()
+                f(rows, 2.0, v["d"], v["b"])
+                got = v["b"].array()
+                assert abs(np.linalg.norm(got) - before) > 1e-3 * before
+                assert abs(v["b"].norm() - np.linalg.norm(got)) <= 1e-12 * np.linalg.norm(got), (on, f.__name__)
+        finally:
+            _deferral(P, -1)
+            for o in made:
+                o.destroy()
+
+
 def test_noting_follows_the_options_database(P):
     """-vec_hipmi355x_defer <0|1> (read when the next operation asks; default 1) switches the noted operations: the plain CG calls run
     the fused sweep once per iteration with it, never without it; same bits."""
