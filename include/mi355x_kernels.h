@@ -176,7 +176,23 @@ int mi355x_vec_mdot(mi355x_handle_t h, size_t n, int nv, const double *x, const 
 int mi355x_vec_maxpy_dev_norm2(mi355x_handle_t h, size_t n, int nv, const double *coef_dev, double sign, const double *const *y,
                                double *x, double *out);
 int mi355x_vec_scale_rnorm_dev(mi355x_handle_t h, size_t n, const double *norm2_dev, double *x);
-/* VecSum / VecMax helpers are not on the Krylov path and are not provided. */
+/* VecSum              src/vec/vec/utils/vinv.c (VecSum)    out[0] = sum x_i.  DotF's lanes, order and streaming threshold with
+ * y == 1.0: the bits of mi355x_vec_dot(x, ones) for any alignment of x; for a 16-byte aligned x also the bits of the oracle's device-order
+ * dot (the oracle restates the aligned tree only; a view off a 16-byte boundary takes the scalar grid-stride loop, another fixed
+ * order, within 1e-13 * sum|x_i| of it).  With a null space attached (MatNullSpaceRemove, src/mat/interface/matnull.c)
+ * this and the shift below run once per Krylov iteration. */
+int mi355x_vec_sum(mi355x_handle_t h, size_t n, const double *x, double *out);
+/* VecShift            src/vec/vec/interface/rvector.c      x[i] = x[i] + alpha (no special case for alpha == 0) */
+int mi355x_vec_shift(mi355x_handle_t h, size_t n, double alpha, double *x);
+/* the same with the shift formed on the device, x[i] = x[i] + (*num_dev / den): num_dev is a sum that never left the device
+ * (mi355x_vec_sum into the device scratch); IEEE division, the bits of the host's sum / den */
+int mi355x_vec_shift_dev(mi355x_handle_t h, size_t n, const double *num_dev, double den, double *x);
+/* VecMax_Seq / VecMin_Seq  src/vec/vec/impls/seq/dvec2.c   out[0] = the extremum, out[1] = its location as a double (exact below
+ * 2^53; VecMax_MPI carries it the same way).  What the reference's loop gives -- it starts from x[0] and replaces on a strict > (<):
+ * ties return the lowest index and that element's own value (-0.0 against +0.0); a NaN is selected only at position 0 (location 0);
+ * n == 0: PETSC_MIN_REAL (PETSC_MAX_REAL for min) and location -1. */
+int mi355x_vec_max(mi355x_handle_t h, size_t n, const double *x, double *out);
+int mi355x_vec_min(mi355x_handle_t h, size_t n, const double *x, double *out);
 
 /* ---- CSR SpMV (MatMult_SeqAIJ family) --------------------------------- */
 /* Analysis: partitions rows into row blocks (<= MI355X_SPMV_BLOCK_NNZ nonzeros staged

@@ -75,6 +75,12 @@ PetscErrorCode VecHIPMI355XGetArray(Vec v, PetscScalar **d);
 PetscErrorCode VecHIPMI355XRestoreArray(Vec v, PetscScalar **d);
 PetscErrorCode VecHIPMI355XGetArrayRead(Vec v, const PetscScalar **d);
 
+/* The constant null space projected out on the device, in the form MatNullSpaceSetFunction takes: create the null space WITHOUT
+ * has_cnst and set this as its function.  Inside a PETSc tree MatNullSpaceRemove's own VecSum reads the vector through
+ * VecGetArrayRead (a download per Krylov iteration); this takes the Vec type's "VecShiftByMean_C" (one rank: the sum never leaves the
+ * device) or its "VecSum_C" followed by VecShift.  Arithmetic of matnull.c: every entry + sum / (-1.0 * N).   */
+PetscErrorCode MatNullSpaceRemoveConstantHIPMI355X(MatNullSpace sp, Vec v, void *ctx);
+
 /* introspection for parity tests: the index lists of a scatter (to/from of VecScatter_MPI_General, vecimpl.h:509-537),
  * the host CSR of a SeqAIJ block, the pieces of an MPIAIJ matrix (Mat_MPIAIJ, mpiaij.h:35-77) */
 PetscErrorCode VecScatterGetLists(VecScatter ctx, PetscInt *nrecv, const PetscInt **rprocs, const PetscInt **rstarts, const PetscInt **rindices,

@@ -107,6 +107,7 @@ typedef struct _p_VecScatter *VecScatter;
 typedef struct _p_KSP        *KSP;
 typedef struct _p_PC         *PC;
 typedef struct _p_PetscViewer *PetscViewer;
+typedef struct _p_MatNullSpace *MatNullSpace;
 typedef struct _p_IS         *IS;           /* index set: only ever NULL here (the natural ordering) */
 typedef enum { FILE_MODE_READ, FILE_MODE_WRITE } PetscFileMode;
 typedef const char *VecType;
@@ -227,6 +228,10 @@ PetscErrorCode VecMTDot(Vec x, PetscInt nv, const Vec y[], PetscScalar val[]);
 PetscErrorCode VecNorm(Vec x, NormType type, PetscReal *val);
 PetscErrorCode VecNormalize(Vec x, PetscReal *val);
 PetscErrorCode VecDotNorm2(Vec s, Vec t, PetscScalar *dp, PetscReal *nm);
+PetscErrorCode VecSum(Vec v, PetscScalar *sum);                /* vinv.c VecSum */
+PetscErrorCode VecShift(Vec v, PetscScalar shift);             /* rvector.c VecShift: v[i] += shift */
+PetscErrorCode VecMax(Vec x, PetscInt *p, PetscReal *val);     /* rvector.c: the first location of the maximum (p may be NULL); no entries: PETSC_MIN_REAL, -1 */
+PetscErrorCode VecMin(Vec x, PetscInt *p, PetscReal *val);
 /* split-phase reductions (src/vec/vec/utils/comb.c:402-721) */
 PetscErrorCode VecDotBegin(Vec x, Vec y, PetscScalar *result);
 PetscErrorCode VecDotEnd(Vec x, Vec y, PetscScalar *result);
@@ -294,6 +299,14 @@ PetscErrorCode MatICCFactorSymbolic(Mat fact, Mat mat, IS perm, const MatFactorI
 PetscErrorCode MatCholeskyFactorNumeric(Mat fact, Mat mat, const MatFactorInfo *info);
 PetscErrorCode MatSolve(Mat mat, Vec b, Vec x);
 PetscErrorCode MatDiagonalScale(Mat A, Vec l, Vec r);   /* A <- diag(l) A diag(r); l or r may be NULL (aij.c:2055, mpiaij.c:2183) */
+/* null spaces of singular operators (src/mat/interface/matnull.c): the constant vector (has_cnst) and / or n orthonormal vectors, which
+ * the null space keeps references to.  MatNullSpaceRemove: the constant first (VecSum, sum / (-N), VecShift), then the vectors (VecMDot,
+ * VecMAXPY), then the function set with MatNullSpaceSetFunction; out != NULL: the result goes to an internal copy returned in *out */
+PetscErrorCode MatNullSpaceCreate(PetscComm comm, PetscBool has_cnst, PetscInt n, const Vec vecs[], MatNullSpace *SP);
+PetscErrorCode MatNullSpaceDestroy(MatNullSpace *sp);
+PetscErrorCode MatNullSpaceSetFunction(MatNullSpace sp, PetscErrorCode (*rem)(MatNullSpace, Vec, void *), void *ctx);
+PetscErrorCode MatNullSpaceRemove(MatNullSpace sp, Vec vec, Vec *out);
+PetscErrorCode MatNullSpaceTest(MatNullSpace sp, Mat mat, PetscBool *isNull);
 /* ---- binary IO (PETSc binary format, big-endian; src/mat/impls/aij/seq/aij.c:4093-4157, src/vec/vec/utils/vecio.c) ---- */
 PetscErrorCode PetscViewerBinaryOpen(PetscComm comm, const char name[], PetscFileMode mode, PetscViewer *viewer);
 PetscErrorCode PetscViewerDestroy(PetscViewer *viewer);
@@ -330,6 +343,10 @@ PetscErrorCode KSPSetTolerances(KSP ksp, PetscReal rtol, PetscReal abstol, Petsc
 PetscErrorCode KSPSetInitialGuessNonzero(KSP ksp, PetscBool flg);
 PetscErrorCode KSPSetNormType(KSP ksp, KSPNormType normtype);
 PetscErrorCode KSPSetPCSide(KSP ksp, PCSide side);   /* -ksp_pc_side <left|right>; right: KSPGMRES only */
+/* itfunc.c KSPSetNullSpace: removed from the result of every preconditioner application while the preconditioner is on the left
+ * (kspimpl.h KSP_RemoveNullSpace); the KSP keeps a reference; NULL takes it away again */
+PetscErrorCode KSPSetNullSpace(KSP ksp, MatNullSpace nullsp);
+PetscErrorCode KSPGetNullSpace(KSP ksp, MatNullSpace *nullsp);
 PetscErrorCode KSPSetOptionsPrefix(KSP ksp, const char prefix[]);
 PetscErrorCode KSPSetFromOptions(KSP ksp);   /* -ksp_type -ksp_rtol -ksp_atol -ksp_max_it -ksp_gmres_restart -ksp_gmres_cgs_refinement_type -pc_type -sub_* */
 PetscErrorCode KSPGMRESSetRestart(KSP ksp, PetscInt restart);

@@ -62,6 +62,8 @@ KERNEL_API = {
     "mi355x_vec_jacobi_invert": [vp, sz, vp, vp],
     "mi355x_vec_maxpy": [vp, sz, i32, pdbl, C.POINTER(vp), vp],
     "mi355x_vec_dot": [vp, sz, vp, vp, vp],
+    "mi355x_vec_sum": [vp, sz, vp, vp], "mi355x_vec_max": [vp, sz, vp, vp], "mi355x_vec_min": [vp, sz, vp, vp],
+    "mi355x_vec_shift": [vp, sz, dbl, vp], "mi355x_vec_shift_dev": [vp, sz, vp, dbl, vp],
     "mi355x_vec_norm": [vp, sz, i32, vp, vp],
     "mi355x_vec_dotnorm2": [vp, sz, vp, vp, vp],
     "mi355x_vec_mdot": [vp, sz, i32, vp, C.POINTER(vp), vp],

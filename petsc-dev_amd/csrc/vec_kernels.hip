@@ -133,6 +133,7 @@ struct OpAxpbypczA1 { double be, ga; __device__ double operator()(double x, doub
 struct OpAxpbypczG1 { double al, be; __device__ double operator()(double x, double y, double z) const { return al * x + be * y + z; } };
 struct OpAxpbypczG0 { double al, be; __device__ double operator()(double x, double y, double) const { return al * x + be * y; } };
 struct OpAxpbypcz   { double al, be, ga; __device__ double operator()(double x, double y, double z) const { return al * x + be * y + ga * z; } };
+struct OpShift    { double al; __device__ double operator()(double x, double, double) const { return x + al; } };
 struct OpTriad    { double al; __device__ double operator()(double b, double c, double) const { return b + al * c; } };
 
 // swap needs two outputs
@@ -251,12 +252,48 @@ static inline int fill_basis(const double **dst, const double *const *y, int cnt
 // ------------------------------------------------------------------------
 // reductions: single launch, fixed tree, last-arriving workgroup finishes
 // ------------------------------------------------------------------------
-enum { RED_SUM = 0, RED_MAX = 1 };
+enum { RED_SUM = 0, RED_MAX = 1, RED_ARGMAX = 2, RED_ARGMIN = 3 };
+// RED_ARGMAX / RED_ARGMIN (NOUT == 2): acc is ONE (value, location) pair, the location a double (exact below 2^53, the way VecMax_MPI
+// carries it; < 0: no element met yet).  VecMax_Seq / VecMin_Seq (dvec2.c) start from x[0] and replace on a strict > / <: of the
+// elements that are no NaN the extremum with the lowest index, carrying that element's own value (-0.0 and +0.0 tie).  As a rule for
+// combining pairs: a NaN and an empty pair are never taken, a larger value is, an equal value only with a lower index.  Locations
+// are distinct, so the rule orders the pairs totally and the tree may combine them in any order.  (x[0] being NaN: ExtremumF::epilogue.)
+template <int MODE> struct is_pair_mode { static constexpr bool value = (MODE == RED_ARGMAX || MODE == RED_ARGMIN); };
+template <int MODE>
+__device__ __forceinline__ void pair_take(double (&a)[2], double v, double idx) {
+  if (idx < 0.0 || v != v) return;
+  const bool better = a[1] < 0.0 || (MODE == RED_ARGMAX ? v > a[0] : v < a[0]) || (v == a[0] && idx < a[1]);
+  if (better) { a[0] = v; a[1] = idx; }
+}
+template <int MODE>
+__device__ __forceinline__ void wave_pair(double (&a)[2]) {
+#pragma unroll
+  for (int off = MI355X_WAVE / 2; off > 0; off >>= 1) {
+    const double v = __shfl_down(a[0], off, MI355X_WAVE), idx = __shfl_down(a[1], off, MI355X_WAVE);
+    pair_take<MODE>(a, v, idx);
+  }
+}
 
 template <int NOUT, int MODE, bool PUBLISH = false>
 __device__ __forceinline__ void block_reduce_store(double (&acc)[NOUT], double *dst /* NOUT doubles */, double (*lds)[NOUT]) {
   const int lane = threadIdx.x & (MI355X_WAVE - 1);
   const int wave = threadIdx.x / MI355X_WAVE;
+  if constexpr (is_pair_mode<MODE>::value) {
+    static_assert(NOUT == 2, "a pair reduction carries (value, location)");
+    wave_pair<MODE>(acc);
+    if (lane == 0) { lds[wave][0] = acc[0]; lds[wave][1] = acc[1]; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double s[2] = {lds[0][0], lds[0][1]};
+#pragma unroll
+      for (int w = 1; w < MI355X_BLOCK / MI355X_WAVE; ++w) pair_take<MODE>(s, lds[w][0], lds[w][1]);
+      if (PUBLISH) {
+        __hip_atomic_store(dst, s[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(dst + 1, s[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      } else { dst[0] = s[0]; dst[1] = s[1]; }
+    }
+    return;
+  }
 #pragma unroll
   for (int j = 0; j < NOUT; ++j) {
     double v = (MODE == RED_MAX) ? wave_max(acc[j]) : wave_sum(acc[j]);
@@ -339,6 +376,22 @@ __global__ __launch_bounds__(MI355X_BLOCK) void aypx_dev_kernel(const double *nu
     });
 }
 
+// x += *num / den with the numerator still in device memory (MatNullSpaceRemove's constant part, matnull.c: the VecSum the kernel
+// before this one on the stream has just reduced, over -N): the quotient is formed once per lane, IEEE division as on the host
+template <bool NT>
+__global__ __launch_bounds__(MI355X_BLOCK) void shift_dev_kernel(const double *num, double den, double *x, size_t n, int vec_ok) {
+  const double alpha = *num / den;
+  double2 *x2 = reinterpret_cast<double2 *>(x);
+  tile_walk<2>(n, vec_ok,
+    [&](size_t i, auto u) {
+      double2 v[decltype(u)::value];
+      ld_tile<NT>(x2, i, v);
+      for (double2 &e : v) { e.x = e.x + alpha; e.y = e.y + alpha; }
+      st_tile<NT>(x2, i, v);
+    },
+    [&](size_t k) { x[k] = x[k] + alpha; });
+}
+
 // copy <= 64 doubles from device memory to the handle's pinned scratch, then store the completion number the host
 // polls (mi355x_handle_wait_result): how a result that had to stay on the device first (RCCL all-reduce, a later kernel
 // reading it) reaches the host without a stream synchronisation
@@ -350,6 +403,11 @@ __global__ void publish_kernel(const double *src, double *host_dst, int count, u
 template <int NOUT> __device__ __forceinline__ void zero(double (&acc)[NOUT]) {
 #pragma unroll
   for (int j = 0; j < NOUT; ++j) acc[j] = 0.0;
+}
+// what a lane starts from: zeros; the pair modes: no element met yet
+template <int MODE, int NOUT> __device__ __forceinline__ void init_acc(double (&acc)[NOUT]) {
+  zero(acc);
+  if (is_pair_mode<MODE>::value) acc[NOUT - 1] = -1.0;
 }
 
 // The hand-off of a launch of several workgroups: each stores its partial sums; the one that arrives last gets true and, in acc,
@@ -383,8 +441,8 @@ __device__ __forceinline__ bool last_workgroup_gathers(double (&acc)[NOUT], doub
   }
   __syncthreads();
   if (!is_last) return false;
-  // last-arriving workgroup: sum the per-workgroup partials in workgroup order
-  zero(acc);
+  // last-arriving workgroup: sum the per-workgroup partials in workgroup order (pairs: combine them, see pair_take)
+  init_acc<MODE>(acc);
   // (a lane's partials b = t, t + 256, ... are added in that order; up to four workgroups' worth requested together)
   for (unsigned int b0 = threadIdx.x; b0 < gridDim.x; b0 += 4 * MI355X_BLOCK) {
     double v[4][NOUT];
@@ -397,8 +455,11 @@ __device__ __forceinline__ bool last_workgroup_gathers(double (&acc)[NOUT], doub
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       if (b0 + u * MI355X_BLOCK < gridDim.x) {
+        if constexpr (is_pair_mode<MODE>::value) pair_take<MODE>(acc, v[u][0], v[u][1]);
+        else {
 #pragma unroll
-        for (int j = 0; j < NOUT; ++j) acc[j] = (MODE == RED_MAX) ? nanmax(acc[j], v[u][j]) : acc[j] + v[u][j];
+          for (int j = 0; j < NOUT; ++j) acc[j] = (MODE == RED_MAX) ? nanmax(acc[j], v[u][j]) : acc[j] + v[u][j];
+        }
       }
     }
   }
@@ -409,6 +470,8 @@ __device__ __forceinline__ bool last_workgroup_gathers(double (&acc)[NOUT], doub
 
 // functors that need a once-per-lane hook before the sweep specialise this
 template <class F> struct has_prologue { static constexpr bool value = false; };
+// ... a hook on the finished result (the lane that stored it: lane 0) specialise this
+template <class F> struct has_epilogue { static constexpr bool value = false; };
 
 // F::accum(i2 or i, acc): adds element contributions
 // RUNS == false: grid-stride (lane t of workgroup b meets double2's b * 256 + t, + grid * 256, ...): vectors that live in the caches.
@@ -423,7 +486,7 @@ __global__ __launch_bounds__(MI355X_BLOCK) void reduce_kernel(F f, size_t n, int
   __shared__ double lds[MI355X_BLOCK / MI355X_WAVE][NOUT];
   const size_t tid = (size_t)blockIdx.x * MI355X_BLOCK + threadIdx.x;
   double acc[NOUT];
-  zero(acc);
+  init_acc<MODE>(acc);
   if constexpr (has_prologue<F>::value) f.prologue(tid, acc);
   if (vec_ok) {
     const size_t n2 = n >> 1;
@@ -444,6 +507,7 @@ __global__ __launch_bounds__(MI355X_BLOCK) void reduce_kernel(F f, size_t n, int
   }
   if (gridDim.x > 1 && !last_workgroup_gathers<NOUT, MODE>(acc, partials, ticket, lds)) return;   // a single workgroup needs no hand-off
   block_reduce_store<NOUT, MODE>(acc, out, lds);
+  if constexpr (has_epilogue<F>::value) { if (threadIdx.x == 0) f.epilogue(n, out); }
   // a result that stays on the device for the next kernel can be handed to the host as well (same lanes that stored it)
   if (host_copy) { __syncthreads(); if (threadIdx.x < NOUT) host_copy[threadIdx.x] = out[threadIdx.x]; }
   publish_to_host(host_seq, seq);
@@ -513,6 +577,44 @@ struct DotF {
     a[0] += xv.y * yv.y;
   }
 };
+// VecSum: DotF with y == 1.0 everywhere (x * 1.0 is x): same lanes, same order, same streaming threshold -- the bits of
+// mi355x_vec_dot(x, ones)
+struct SumF {
+  const double *x;
+  int nt = 0;
+  BATCHED_SWEEP()
+  __device__ void accum2x4(size_t i, size_t st, double (&a)[1]) const {
+    const double2 *x2 = reinterpret_cast<const double2 *>(x);
+    double2 v0 = ldq(x2 + i, nt), v1 = ldq(x2 + i + st, nt), v2 = ldq(x2 + i + 2 * st, nt), v3 = ldq(x2 + i + 3 * st, nt);
+    a[0] += v0.x; a[0] += v0.y; a[0] += v1.x; a[0] += v1.y;
+    a[0] += v2.x; a[0] += v2.y; a[0] += v3.x; a[0] += v3.y;
+  }
+  __device__ void accum1(size_t i, double (&a)[1]) const { a[0] += x[i]; }
+  __device__ void accum2(size_t i, double (&a)[1]) const {
+    double2 xv = reinterpret_cast<const double2 *>(x)[i];
+    a[0] += xv.x;
+    a[0] += xv.y;
+  }
+};
+// VecMax_Seq / VecMin_Seq (dvec2.c): the (value, location) pair under launch_reduce<2, RED_ARGMAX / RED_ARGMIN>.  The combining rule
+// never takes a NaN; the reference starts from x[0] and nothing compares greater (or less) than a NaN, so a NaN at position 0 IS the
+// answer: the epilogue puts it there.  No element at all: PETSC_MIN_REAL / PETSC_MAX_REAL and location -1.
+template <int MODE>
+struct ExtremumF {
+  const double *x;
+  DEFAULT_SWEEP()
+  __device__ void accum1(size_t i, double (&a)[2]) const { pair_take<MODE>(a, x[i], (double)i); }
+  __device__ void accum2(size_t i, double (&a)[2]) const {
+    double2 xv = reinterpret_cast<const double2 *>(x)[i];
+    pair_take<MODE>(a, xv.x, (double)(2 * i));
+    pair_take<MODE>(a, xv.y, (double)(2 * i + 1));
+  }
+  __device__ void epilogue(size_t n, double *out) const {
+    if (n == 0) { out[0] = MODE == RED_ARGMAX ? -1.7976931348623157e308 : 1.7976931348623157e308; out[1] = -1.0; }
+    else if (x[0] != x[0]) { out[0] = x[0]; out[1] = 0.0; }
+  }
+};
+template <int MODE> struct has_epilogue<ExtremumF<MODE>> { static constexpr bool value = true; };
 struct SumSqF {
   const double *x;
   int nt = 0;
@@ -870,6 +972,13 @@ int mi355x_vec_aypx_dev_x(mi355x_handle_t h, size_t n, const double *num_dev, do
   return launch_tiles(h, n, all_aligned16(x, y, sol), aypx_dev_kernel<true, true>, aypx_dev_kernel<false, true>, num_dev, den, x, y,
                       CGStepLen{beta, dpiold, check_sign, dpi_dev}, sol);
 }
+int mi355x_vec_shift(mi355x_handle_t h, size_t n, double alpha, double *x) {
+  return launch_map<1>(h, OpShift{alpha}, x, nullptr, nullptr, x, n);   // VecShift's loop (rvector.c): no special case for alpha == 0
+}
+int mi355x_vec_shift_dev(mi355x_handle_t h, size_t n, const double *num_dev, double den, double *x) {
+  if (n == 0) return 0;
+  return launch_tiles(h, n, all_aligned16(x), shift_dev_kernel<true>, shift_dev_kernel<false>, num_dev, den, x);
+}
 int mi355x_handle_publish_at(mi355x_handle_t h, const double *src_dev, int count, int dst_offset) {
   if (count < 0 || dst_offset < 0 || dst_offset + count > MI355X_SCRATCH_DOUBLES) return (int)hipErrorInvalidValue;
   const unsigned long long seq = ++h->seq;
@@ -938,6 +1047,17 @@ int mi355x_vec_dot(mi355x_handle_t h, size_t n, const double *x, const double *y
   DotF f{x, y};
   f.nt = vec_streams(n);
   return launch_reduce<1, RED_SUM>(h, f, n, all_aligned16(x, y), out);
+}
+int mi355x_vec_sum(mi355x_handle_t h, size_t n, const double *x, double *out) {
+  SumF f{x};
+  f.nt = vec_streams(n);
+  return launch_reduce<1, RED_SUM>(h, f, n, all_aligned16(x), out);
+}
+int mi355x_vec_max(mi355x_handle_t h, size_t n, const double *x, double *out) {
+  return launch_reduce<2, RED_ARGMAX>(h, ExtremumF<RED_ARGMAX>{x}, n, all_aligned16(x), out);
+}
+int mi355x_vec_min(mi355x_handle_t h, size_t n, const double *x, double *out) {
+  return launch_reduce<2, RED_ARGMIN>(h, ExtremumF<RED_ARGMIN>{x}, n, all_aligned16(x), out);
 }
 int mi355x_vec_norm(mi355x_handle_t h, size_t n, int type, const double *x, double *out) {
   const int v = all_aligned16(x);

@@ -110,6 +110,14 @@ PetscErrorCode KSPSetTolerances(KSP ksp, PetscReal rtol, PetscReal abstol, Petsc
   if (maxits != PETSC_DEFAULT) { if (maxits < 0) SETERRQ(ksp->comm, PETSC_ERR_ARG_OUTOFRANGE, "Maximum number of iterations %d must be non-negative", maxits); ksp->max_it = maxits; }
   return 0;
 }
+PetscErrorCode KSPSetNullSpace(KSP ksp, MatNullSpace nullsp) {   /* itfunc.c KSPSetNullSpace: reference the new one, release the old one */
+  KSPValid(ksp);
+  if (nullsp) nullsp->refct++;
+  PetscErrorCode ierr = MatNullSpaceDestroy(&ksp->nullsp);CHKERRQ(ierr);
+  ksp->nullsp = nullsp;
+  return 0;
+}
+PetscErrorCode KSPGetNullSpace(KSP ksp, MatNullSpace *nullsp) { KSPValid(ksp); *nullsp = ksp->nullsp; return 0; }
 PetscErrorCode KSPSetInitialGuessNonzero(KSP ksp, PetscBool flg) { KSPValid(ksp); ksp->guess_zero = (PetscBool)!flg; return 0; }
 PetscErrorCode KSPSetNormType(KSP ksp, KSPNormType t) {   /* itcreate.c:221-235: no norm -> the test that only counts iterations */
   KSPValid(ksp);
@@ -308,6 +316,7 @@ PetscErrorCode KSPDestroy(KSP *pksp) {
   if (ksp->ops->destroy) { ierr = (*ksp->ops->destroy)(ksp);CHKERRQ(ierr); }
   if (ksp->work) { ierr = VecDestroyVecs(ksp->nwork, &ksp->work);CHKERRQ(ierr); }
   ierr = PCDestroy(&ksp->pc);CHKERRQ(ierr);
+  ierr = MatNullSpaceDestroy(&ksp->nullsp);CHKERRQ(ierr);
   ierr = PetscObjectListDestroy_Private((PetscObject)ksp);CHKERRQ(ierr);
   free(ksp->res_hist_alloc);
   free(ksp); *pksp = NULL;
@@ -316,7 +325,13 @@ PetscErrorCode KSPDestroy(KSP *pksp) {
 
 /* kspimpl.h:181-188 */
 PetscErrorCode KSP_MatMult(KSP ksp, Mat A, Vec x, Vec y) { (void)ksp; return MatMult(A, x, y); }
-PetscErrorCode KSP_PCApply(KSP ksp, Vec x, Vec y) { return PCApply(ksp->pc, x, y); }
+/* KSP_RemoveNullSpace: only with a null space set and the preconditioner on the left */
+#define KSP_RemoveNullSpace(ksp, y) do { if ((ksp)->nullsp && (ksp)->pc_side == PC_LEFT) { PetscErrorCode e__ = MatNullSpaceRemove((ksp)->nullsp, (y), NULL);CHKERRQ(e__); } } while (0)
+PetscErrorCode KSP_PCApply(KSP ksp, Vec x, Vec y) {
+  PetscErrorCode ierr = PCApply(ksp->pc, x, y);CHKERRQ(ierr);
+  KSP_RemoveNullSpace(ksp, y);
+  return 0;
+}
 /* PCApplyBAorAB, src/ksp/pc/interface/precon.c:553-640 (no diagonal scaling) */
 PetscErrorCode KSP_PCApplyBAorAB(KSP ksp, Vec x, Vec y, Vec w) {
   PetscErrorCode ierr;
@@ -324,6 +339,7 @@ PetscErrorCode KSP_PCApplyBAorAB(KSP ksp, Vec x, Vec y, Vec w) {
   if (ksp->pc_side == PC_RIGHT) { ierr = PCApply(ksp->pc, x, w);CHKERRQ(ierr); ierr = MatMult(ksp->pc->mat, w, y);CHKERRQ(ierr); }
   else if (ksp->pc_side == PC_LEFT) { ierr = MatMult(ksp->pc->mat, x, w);CHKERRQ(ierr); ierr = PCApply(ksp->pc, w, y);CHKERRQ(ierr); }
   else SETERRQ(ksp->comm, PETSC_ERR_SUP, "symmetric preconditioning is outside the ported path");
+  KSP_RemoveNullSpace(ksp, y);
   return 0;
 }
 

@@ -100,6 +100,9 @@ struct _VecOps {
   PetscErrorCode (*destroy)(Vec);
   PetscErrorCode (*reciprocal)(Vec);
   PetscErrorCode (*dotnorm2)(Vec, Vec, PetscScalar *, PetscScalar *);
+  PetscErrorCode (*max)(Vec, PetscInt *, PetscReal *);        /* rvector.c VecMax / VecMin call these two without a test */
+  PetscErrorCode (*min)(Vec, PetscInt *, PetscReal *);
+  PetscErrorCode (*shift)(Vec, PetscScalar);                  /* rvector.c VecShift: the slot, or the array loop */
 };
 typedef struct _VecOps VecOps;
 
@@ -111,6 +114,20 @@ struct _p_Vec {
   /* norm cache keyed on state (rvector.c:205-224; the reference keeps it in composed data) */
   int norm_state[4];
   PetscReal norm_val[4];
+  int xrefs;                      /* references beyond the creator's (PetscObjectReference: a MatNullSpace keeps its vectors); VecDestroy drops one */
+};
+
+/* ---- MatNullSpace (struct _p_MatNullSpace, include/petsc-private/matimpl.h) ---- */
+struct _p_MatNullSpace {
+  PetscComm comm;
+  int refct;
+  PetscBool has_cnst;
+  PetscInt n;
+  Vec *vecs;
+  PetscScalar *alpha;             /* for the projections: VecMDot's results, negated for VecMAXPY */
+  Vec vec;                        /* for the out-of-place removal and MatNullSpaceTest */
+  PetscErrorCode (*remove)(MatNullSpace, Vec, void *);
+  void *rmctx;
 };
 
 /* ---- Mat ---- */
@@ -201,6 +218,7 @@ struct _p_KSP {
   PetscReal *res_hist; PetscInt res_hist_len, res_hist_max; PetscBool res_hist_reset; PetscReal *res_hist_alloc;
   PetscErrorCode (*monitor)(KSP, PetscInt, PetscReal, void *); void *mctx;
   PetscBool printreason;   /* -ksp_converged_reason */
+  MatNullSpace nullsp;     /* KSPSetNullSpace (kspimpl.h): removed after every left preconditioner application */
   void *data;
 };
 PetscErrorCode KSPDefaultConverged(KSP ksp, PetscInt n, PetscReal rnorm, KSPConvergedReason *reason, void *ctx);   /* iterativ.c:702 */

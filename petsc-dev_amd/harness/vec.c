@@ -91,6 +91,7 @@ PetscErrorCode VecDestroyVecs(PetscInt m, Vec **V) {
 PetscErrorCode VecDestroy(Vec *v) {
   PetscErrorCode ierr;
   if (!*v) return 0;
+  if ((*v)->xrefs > 0) { (*v)->xrefs--; *v = NULL; return 0; }   /* somebody else still holds it */
   if ((*v)->ops->destroy) { ierr = (*(*v)->ops->destroy)(*v);CHKERRQ(ierr); }
   ierr = PetscLayoutDestroy(&(*v)->map);CHKERRQ(ierr);
   ierr = PetscObjectListDestroy_Private((PetscObject)*v);CHKERRQ(ierr);
@@ -307,6 +308,50 @@ PetscErrorCode VecDotNorm2(Vec s, Vec t, PetscScalar *dp, PetscReal *nm) {   /* 
   return 0;
 }
 
+/* vinv.c VecSum: the local entries summed in order, then MPI_SUM over the ranks; a type may answer by name ("VecSum_C": it is no slot of
+ * struct _VecOps) */
+PetscErrorCode VecSum(Vec v, PetscScalar *sum) {
+  PetscErrorCode ierr;
+  PetscVoidFunction f = NULL;
+  VecTypeSet(v, 1);
+  ierr = PetscObjectQueryFunction((PetscObject)v, "VecSum_C", &f);CHKERRQ(ierr);
+  if (f) { ierr = ((PetscErrorCode (*)(Vec, PetscScalar *))f)(v, sum);CHKERRQ(ierr); return 0; }
+  const PetscScalar *x;
+  PetscScalar lsum = 0.0;
+  ierr = VecGetArrayRead(v, &x);CHKERRQ(ierr);
+  for (PetscInt i = 0; i < v->map->n; i++) lsum += x[i];
+  ierr = VecRestoreArrayRead(v, &x);CHKERRQ(ierr);
+  if (v->comm->size > 1 && v->comm->allreduce(v->comm->ctx, &lsum, 1, 1, 0)) SETERRQ(v->comm, PETSC_ERR_LIB, "allreduce failed");
+  *sum = lsum;
+  return 0;
+}
+PetscErrorCode VecShift(Vec v, PetscScalar shift) {   /* rvector.c VecShift */
+  PetscErrorCode ierr;
+  VecTypeSet(v, 1);
+  if (v->ops->shift) { ierr = (*v->ops->shift)(v, shift);CHKERRQ(ierr); }
+  else {
+    PetscScalar *x;
+    ierr = VecGetArray(v, &x);CHKERRQ(ierr);
+    for (PetscInt i = 0; i < v->map->n; i++) x[i] += shift;
+    ierr = VecRestoreArray(v, &x);CHKERRQ(ierr);
+  }
+  PetscObjectStateIncrease(v);
+  return 0;
+}
+PetscErrorCode VecMax(Vec x, PetscInt *p, PetscReal *val) {   /* rvector.c VecMax */
+  VecTypeSet(x, 1);
+  if (!val) SETERRQ(x->comm, PETSC_ERR_ARG_NULL, "Null Pointer: Parameter # 3");
+  if (!x->ops->max) SETERRQ(x->comm, PETSC_ERR_SUP, "VecMax() is not provided by vectors of type %s", x->type_name);
+  PetscErrorCode ierr = (*x->ops->max)(x, p, val);CHKERRQ(ierr);
+  return 0;
+}
+PetscErrorCode VecMin(Vec x, PetscInt *p, PetscReal *val) {   /* rvector.c VecMin */
+  VecTypeSet(x, 1);
+  if (!val) SETERRQ(x->comm, PETSC_ERR_ARG_NULL, "Null Pointer: Parameter # 3");
+  if (!x->ops->min) SETERRQ(x->comm, PETSC_ERR_SUP, "VecMin() is not provided by vectors of type %s", x->type_name);
+  PetscErrorCode ierr = (*x->ops->min)(x, p, val);CHKERRQ(ierr);
+  return 0;
+}
 
 /* ---- split-phase reductions (src/vec/vec/utils/comb.c:402-721).  The reference queues the local parts and starts one
  * MPI_Iallreduce in PetscCommSplitReductionBegin; here a vector type may provide the three phases itself

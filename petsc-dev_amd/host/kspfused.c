@@ -71,6 +71,10 @@ static PetscErrorCode pc_diagonal_form(KSP ksp, Vec like, Vec *dinv, HipPCKind *
   }
   return 0;
 }
+/* A null space (KSPSetNullSpace) is projected out of every preconditioned vector by KSP_PCApply / KSP_PCApplyBAorAB (kspimpl.h
+ * KSP_RemoveNullSpace).  A sweep that folds the preconditioner into a product or takes the dots of z in the pass that forms z has no
+ * place for that projection: with a null space every preconditioner counts as PCKIND_GENERAL and goes through those two calls. */
+static PetscBool has_null_space(KSP ksp) { return (PetscBool)(ksp->nullsp != NULL); }   /* kspimpl.h: what KSPGetNullSpace returns */
 #define KSPCheckDot(ksp, v) do { if (PetscIsInfOrNanScalar(v)) SETERRQ(HipObjComm(ksp), PETSC_ERR_FP, "Infinite or not-a-number generated in dot product"); } while (0)
 #define KSPTestConvergence(ksp, it, rn) (*(ksp)->converged)((ksp), (it), (rn), &(ksp)->reason, (ksp)->cnvP)
 static PetscErrorCode report(KSP ksp, PetscInt it, PetscReal rn) {   /* what every solver does with a new residual norm */
@@ -139,7 +143,7 @@ static PetscErrorCode KSPSolve_CGHIP(KSP ksp) {
   PetscInt it;
 
   ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
-  if (level > 0) {
+  if (level > 0 && !has_null_space(ksp)) {                /* with a null space: pck stays general, sweep stays off, every z from KSP_PCApply */
     ierr = pc_diagonal_form(ksp, x, &cg->dinv, &pck);CHKERRQ(ierr);
     if (pck != PCKIND_GENERAL) { d = pck == PCKIND_DIAGONAL ? cg->dinv : NULL; ierr = F->cg_update_check(x, r, z, p, w, d, &sweep);CHKERRQ(ierr); }
   }
@@ -397,7 +401,7 @@ static PetscErrorCode gmres_cycle(KSP ksp, PetscInt *steps) {
 
   if (F && !F->gmres_orthog_normalize) F = NULL;
   ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
-  if (gm->fused && ksp->pc_side == PC_LEFT) {
+  if (gm->fused && ksp->pc_side == PC_LEFT && !has_null_space(ksp)) {
     HipPCKind kind;
     ierr = pc_diagonal_form(ksp, BASIS(gm, 0), &gm->dinv, &kind);CHKERRQ(ierr);
     if (kind == PCKIND_DIAGONAL) d = gm->dinv;
@@ -548,7 +552,7 @@ static PetscErrorCode KSPSolve_BCGSHIP(KSP ksp) {
 
   if (ksp->pc_side == PC_RIGHT) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "right-preconditioned BiCGStab is outside the ported path");
   ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
-  if (F) { ierr = pc_diagonal_form(ksp, x, &bc->dinv, &pck);CHKERRQ(ierr); if (pck == PCKIND_DIAGONAL) d = bc->dinv; }
+  if (F && !has_null_space(ksp)) { ierr = pc_diagonal_form(ksp, x, &bc->dinv, &pck);CHKERRQ(ierr); if (pck == PCKIND_DIAGONAL) d = bc->dinv; }
   ierr = KSPInitialResidual(ksp, x, v, t, r, rhs);CHKERRQ(ierr);
   if (!nonorm) { ierr = VecNorm(r, NORM_2, &rn);CHKERRQ(ierr); }
   ksp->its = 0;

@@ -730,6 +730,101 @@ static PetscErrorCode VecDotNorm2_HIP(Vec s, Vec t, PetscScalar *dp, PetscScalar
   return 0;
 }
 
+/* ---- VecSum, VecShift, VecMax, VecMin: what MatNullSpaceRemove (src/mat/interface/matnull.c) is made of, and the three slots of
+ * struct _VecOps PETSc 3.3 jumps through without a test (rvector.c VecMax / VecMin).  They are no part of a noted sequence: the
+ * accessors run whatever is pending first (a VecSum of the z a noted VecPointwiseMult is about to write gets it written). ---- */
+static PetscErrorCode VecSum_HIP(Vec x, PetscScalar *sum) {   /* "VecSum_C" (vinv.c VecSum: the local sum, then MPI_SUM) */
+  PetscErrorCode ierr; const PetscScalar *dx; double *out; DEVCTX;
+  ierr = VecHIPGetRead(x, &dx);CHKERRQ(ierr);
+  ierr = reduce_target(x, dc, &out);CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_sum(dc->h, N_(x), dx, out));
+  ierr = reduce_finish(x, dc, 1, 0, sum);CHKERRQ(ierr);
+  ierr = PetscLogFlops(PetscMax(x->map->n - 1.0, 0.0));CHKERRQ(ierr);
+  return 0;
+}
+static PetscErrorCode VecShift_HIP(Vec x, PetscScalar shift) {   /* rvector.c VecShift's loop: x[i] += shift */
+  PetscErrorCode ierr; PetscScalar *d; DEVCTX;
+  ierr = VecHIPGetReadWrite(x, &d);CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_shift(dc->h, N_(x), shift, d));
+  ierr = PetscLogFlops((PetscLogDouble)x->map->n);CHKERRQ(ierr);
+  return VecHIPRestoreWrite(x);
+}
+/* "VecShiftByMean_C" (one rank): v += sum(v) / den, the sum staying on the device -- MatNullSpaceRemove's constant part with
+ * den = -N (matnull.c: VecSum; sum = sum / (-1.0 * N); VecShift) as two launches and no host wait.  Same bits as the two calls. */
+#define SUM_SLOT 40      /* device scratch slot of that sum: clear of the ordinary reductions (<= 32 from 0) and of the split-phase ones (48..) */
+static PetscErrorCode VecShiftByMean_HIP(Vec v, PetscScalar den) {
+  PetscErrorCode ierr; PetscScalar *d; double *ds; DEVCTX;
+  ierr = VecHIPGetReadWrite(v, &d);CHKERRQ(ierr);
+  ds = mi355x_handle_device_scratch(dc->h) + SUM_SLOT;
+  CHKHIP(mi355x_vec_sum(dc->h, N_(v), d, ds));
+  CHKHIP(mi355x_vec_shift_dev(dc->h, N_(v), ds, den, d));
+  VecHIPRestoreWrite(v);
+  HipStateIncrease(v);
+  ierr = PetscLogFlops(PetscMax(2.0 * v->map->n - 1.0, 0.0));CHKERRQ(ierr);
+  return 0;
+}
+/* VecMax_Seq / VecMin_Seq (dvec2.c) on this rank, then VecMax_MPI / VecMin_MPI (pvec2.c).  Without a location: one max all-reduce
+ * (the min of x is -max(-x), exactly).  With one: the (value, global index) pairs of all ranks are gathered on the host and the
+ * reference's loop runs over them in rank order -- the extremum with the lowest global index, as VecMax_Local_Op gives. */
+static PetscErrorCode extremum_HIP(Vec x, int is_max, PetscInt *p, PetscReal *val) {
+  PetscErrorCode ierr; const PetscScalar *dx; DEVCTX;
+  MPI_Comm comm = HipObjComm(x);
+  const int size = hip_local_only ? 1 : (int)HipCommSize(comm);
+  const int on_device = (size > 1 && !p && DEVICE_COLLECTIVES(x));
+  double *out = on_device ? mi355x_handle_device_scratch(dc->h) : mi355x_handle_host_scratch(dc->h);
+  ierr = VecHIPGetRead(x, &dx);CHKERRQ(ierr);
+  if (is_max) CHKHIP(mi355x_vec_max(dc->h, N_(x), dx, out));
+  else CHKHIP(mi355x_vec_min(dc->h, N_(x), dx, out));
+  if (on_device) {
+    if (!is_max) CHKHIP(mi355x_vec_scale(dc->h, 1, -1.0, out));
+    CHKHIP(mi355x_comm_allreduce_max(HipCommDevice(comm), dc->h, out, 1));
+    CHKHIP(mi355x_handle_publish(dc->h, out, 1));
+  }
+  CHKHIP(mi355x_handle_wait_result(dc->h)); { PetscErrorCode e_ = HipTriWatchCheck();CHKERRQ(e_); }
+  const double *hs = mi355x_handle_host_scratch(dc->h);
+  double v = hs[0], loc = on_device ? -1.0 : hs[1];
+  if (on_device) v = is_max ? v : -v;
+  else if (size > 1 && !p) {
+    if (!is_max) v = -v;
+    if (HipCommAllreduce(comm, &v, 1, 1, 1)) SETERRQ(comm, PETSC_ERR_LIB, "allreduce failed");
+    if (!is_max) v = -v;
+  } else if (size > 1) {
+    double mine[2], *all;
+    mine[0] = v; mine[1] = loc < 0.0 ? -1.0 : loc + (double)x->map->rstart;
+    ierr = PetscMalloc(sizeof(double) * 2 * (size_t)size, &all);CHKERRQ(ierr);
+    if (HipCommAllgather(comm, mine, (int)sizeof(mine), all)) { HipFree(all); SETERRQ(comm, PETSC_ERR_LIB, "allgather failed"); }
+    loc = -1.0;
+    for (int r = 0; r < size; r++) {
+      if (all[2 * r + 1] < 0.0) continue;                           /* a rank without elements */
+      if (loc < 0.0 || (is_max ? all[2 * r] > v : all[2 * r] < v)) { v = all[2 * r]; loc = all[2 * r + 1]; }
+    }
+    HipFree(all);
+  }
+  *val = v;
+  if (p) *p = (PetscInt)loc;
+  return 0;
+}
+static PetscErrorCode VecMax_HIP(Vec x, PetscInt *p, PetscReal *val) { return extremum_HIP(x, 1, p, val); }
+static PetscErrorCode VecMin_HIP(Vec x, PetscInt *p, PetscReal *val) { return extremum_HIP(x, 0, p, val); }
+
+/* MatNullSpaceSetFunction(sp, MatNullSpaceRemoveConstantHIPMI355X, NULL) on a null space created WITHOUT has_cnst: the constant is
+ * projected out on the device.  Inside a PETSc tree MatNullSpaceRemove is PETSc's, and its generic VecSum reads the vector through
+ * VecGetArrayRead -- a download per Krylov iteration; this callback takes the type's own sum-and-shift without a host wait (one rank: what
+ * "VecShiftByMean_C" offers) or its sum followed by its shift (several ranks) instead.  The arithmetic is matnull.c's: sum / (-1.0 * N), added to every entry. */
+PetscErrorCode MatNullSpaceRemoveConstantHIPMI355X(MatNullSpace sp, Vec v, void *ctx) {
+  PetscErrorCode ierr; PetscScalar sum;
+  (void)sp; (void)ctx;
+  CheckHIP(v);
+  const PetscInt N = v->map->N;
+  if (N <= 0) return 0;
+  if (HipCommSize(HipObjComm(v)) == 1) return VecShiftByMean_HIP(v, -1.0 * N);
+  ierr = VecSum_HIP(v, &sum);CHKERRQ(ierr);
+  sum = sum / (-1.0 * N);
+  ierr = VecShift_HIP(v, sum);CHKERRQ(ierr);
+  HipStateIncrease(v);
+  return 0;
+}
+
 /* per-launch device timing of the fused CG update for bench.py (hipEvent pairs on the compute stream, like
  * MatHIPMI355XSetTiming for the product) */
 static struct { PetscBool on; PetscInt n, cap; mi355x_event_t *ev; } cgu_time;
@@ -1233,6 +1328,11 @@ static PetscErrorCode VecCreate_HIP_common(Vec v, const char *tname) {
   v->ops->destroy = VecDestroy_HIP;
   v->ops->reciprocal = VecReciprocal_HIP;
   v->ops->dotnorm2 = VecDotNorm2_HIP;
+  v->ops->shift = VecShift_HIP;
+  v->ops->max = VecMax_HIP;
+  v->ops->min = VecMin_HIP;
+  ierr = PetscObjectComposeFunction((PetscObject)v, "VecSum_C", "VecSum_HIP", (PetscVoidFunction)VecSum_HIP);CHKERRQ(ierr);
+  if (HipCommSize(HipObjComm(v)) == 1) { ierr = PetscObjectComposeFunction((PetscObject)v, "VecShiftByMean_C", "VecShiftByMean_HIP", (PetscVoidFunction)VecShiftByMean_HIP);CHKERRQ(ierr); }
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecJacobiInvert_C", "VecJacobiInvert_HIP", (PetscVoidFunction)VecJacobiInvert_HIP);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecShareArrayBegin_C", "VecShareArrayBegin_HIP", (PetscVoidFunction)VecShareArrayBegin_HIP);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecShareArrayEnd_C", "VecShareArrayEnd_HIP", (PetscVoidFunction)VecShareArrayEnd_HIP);CHKERRQ(ierr);

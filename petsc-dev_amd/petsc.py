@@ -32,6 +32,10 @@ _SIG = {
     "VecPointwiseDivide": [vp, vp, vp], "VecReciprocal": [vp], "VecDot": [vp, vp, P(dbl)], "VecDotBegin": [vp, vp, P(dbl)], "VecDotEnd": [vp, vp, P(dbl)], "VecNormBegin": [vp, i32, P(dbl)], "VecNormEnd": [vp, i32, P(dbl)], "PetscCommSplitReductionBegin": [vp], "VecTDot": [vp, vp, P(dbl)],
     "VecMDot": [vp, i32, vp, vp], "VecMTDot": [vp, i32, vp, vp], "VecNorm": [vp, i32, P(dbl)], "VecNormalize": [vp, P(dbl)],
     "VecDotNorm2": [vp, vp, P(dbl), P(dbl)],
+    "VecSum": [vp, P(dbl)], "VecShift": [vp, dbl], "VecMax": [vp, P(i32), P(dbl)], "VecMin": [vp, P(i32), P(dbl)],
+    "MatNullSpaceCreate": [vp, i32, i32, vp, P(vp)], "MatNullSpaceDestroy": [P(vp)], "MatNullSpaceSetFunction": [vp, vp, vp],
+    "MatNullSpaceRemove": [vp, vp, P(vp)], "MatNullSpaceTest": [vp, vp, P(i32)], "MatNullSpaceRemoveConstantHIPMI355X": [vp, vp, vp],
+    "KSPSetNullSpace": [vp, vp], "KSPGetNullSpace": [vp, P(vp)],
     "VecScatterBegin": [vp, vp, vp, i32, i32], "VecScatterEnd": [vp, vp, vp, i32, i32],
     "VecScatterGetLists": [vp, P(i32), P(vp), P(vp), P(vp), P(i32), P(vp), P(vp), P(vp), P(i32), P(vp), P(vp)],
     "MatCreate": [vp, P(vp)], "MatSetSizes": [vp, i32, i32, i32, i32], "MatSetType": [vp, C.c_char_p], "MatSetFromOptions": [vp],
@@ -207,6 +211,27 @@ class Vec:
         lib().VecDot(self.h, y.h, C.byref(r))
         return r.value
 
+    def sum(self):
+        r = dbl()
+        lib().VecSum(self.h, C.byref(r))
+        return r.value
+
+    def shift(self, a):
+        """every entry + a (VecShift)"""
+        lib().VecShift(self.h, float(a))
+
+    def max(self):
+        """(location, value) of the maximum, the first one among equals (VecMax)"""
+        p, r = i32(), dbl()
+        lib().VecMax(self.h, C.byref(p), C.byref(r))
+        return p.value, r.value
+
+    def min(self):
+        """(location, value) of the minimum, the first one among equals (VecMin)"""
+        p, r = i32(), dbl()
+        lib().VecMin(self.h, C.byref(p), C.byref(r))
+        return p.value, r.value
+
     def destroy(self):
         if self.own and self.h:
             lib().VecDestroy(C.byref(self.h))
@@ -324,11 +349,53 @@ class Mat:
             pass
 
 
+class NullSpace:
+    """MatNullSpace: the constant vector (constant=True) and / or orthonormal vectors; remove() projects it out of a vector"""
+
+    def __init__(self, constant=True, vecs=(), comm=None):
+        self.h = vp()
+        self.vecs = list(vecs)
+        lib().MatNullSpaceCreate(comm or lib().COMM_WORLD, 1 if constant else 0, len(self.vecs), vec_table(self.vecs) if self.vecs else None, C.byref(self.h))
+
+    def set_device_constant(self):
+        """project the constant out through the plug-in's callback (MatNullSpaceSetFunction with MatNullSpaceRemoveConstantHIPMI355X)"""
+        fn = C.cast(lib().raw("MatNullSpaceRemoveConstantHIPMI355X"), vp)
+        lib().MatNullSpaceSetFunction(self.h, fn, None)
+
+    def remove(self, v, out=False):
+        """in place, or (out=True) into the null space's own copy, which is returned (not owned by the caller)"""
+        if not out:
+            lib().MatNullSpaceRemove(self.h, v.h, None)
+            return v
+        w = Vec(own=False)
+        lib().MatNullSpaceRemove(self.h, v.h, C.byref(w.h))
+        return w
+
+    def test(self, A):
+        k = i32()
+        lib().MatNullSpaceTest(self.h, A.h, C.byref(k))
+        return bool(k.value)
+
+    def destroy(self):
+        if self.h:
+            lib().MatNullSpaceDestroy(C.byref(self.h))
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
 class KSP:
     def __init__(self, comm=None):
         self.h = vp()
         lib().KSPCreate(comm or lib().COMM_WORLD, C.byref(self.h))
         self._hist = None
+
+    def set_null_space(self, nullsp):
+        """KSPSetNullSpace; None takes it away"""
+        lib().KSPSetNullSpace(self.h, nullsp.h if nullsp is not None else None)
 
     def set_operators(self, A, P_=None):
         lib().KSPSetOperators(self.h, A.h, (P_ or A).h, 0)
