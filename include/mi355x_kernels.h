@@ -169,6 +169,20 @@ int mi355x_vec_pmult_dot(mi355x_handle_t h, size_t n, const double *x, const dou
 int mi355x_vec_pmult_dotnorm2(mi355x_handle_t h, size_t n, const double *x, const double *d, const double *s, double *w, double *out);
 int mi355x_vec_bcgs_update(mi355x_handle_t h, size_t n, double alpha, double omega, const double *p, const double *s, const double *t,
                            const double *rp, double *x, double *r, double *out);
+/* One step of KSPSolve_Chebychev (src/ksp/ksp/impls/cheby/cheby.c) / KSPSolve_Richardson (src/ksp/ksp/impls/rich/rich.c) behind
+ * the product w = A p: the residual, a diagonal preconditioner and the update in one sweep, same bits as mi355x_vec_aypx(-1),
+ * mi355x_vec_pointwise_mult, mi355x_vec_scale and mi355x_vec_axpy (x2) in sequence.
+ * cheby_step:  rv = b - w ; r != NULL: r = rv (r may be w) ; zv = d ? rv * d : rv ;
+ *              t = s == 1 ? zv : (s == 0 ? +0.0 : s * zv) ; a != 0: t = t + a * pm ; c != 0: t = t + c * pk ; pn = t
+ *              sums != 0: out[0] = sum zv*zv, out[1] = sum rv*rv (the trees of mi355x_vec_norm(type 1) over z and r for an aligned
+ *              view; out: device or the handle's pinned scratch) ; sums == 0: out is not touched, nothing is reduced.
+ *              b == NULL: w already is the preconditioned residual (zv = w; d, r must be NULL, sums 0), and then w may be pn.
+ * rich_step:   rv = b - w ; r != NULL: r = rv (r may be w) ; zv = d ? rv * d : rv ; z != NULL: z = zv ; scale != 0: x = x + scale * zv
+ * pn overlaps no input (but for w with b == NULL); an operand a form does not read (pm for a == 0, pk for c == 0) may be NULL;
+ * n == 0 launches nothing and, with sums, leaves zeros in out. */
+int mi355x_vec_cheby_step(mi355x_handle_t h, size_t n, double s, double a, double c, const double *w, const double *b, const double *d,
+                          const double *pm, const double *pk, double *r, double *pn, int sums, double *out);
+int mi355x_vec_rich_step(mi355x_handle_t h, size_t n, double scale, const double *w, const double *b, const double *d, double *r, double *z, double *x);
 /* VecMDot_Seq         src/vec/vec/impls/seq/dvec2.c:146     out[j] = sum_i x_i y_j,i , j<nv ; x read once per 16 y's */
 int mi355x_vec_mdot(mi355x_handle_t h, size_t n, int nv, const double *x, const double *const *y, double *out);
 /* KSPGMRESCycle fusions (gmres.c:118-209, borthog2.c:60-66): x += sum_j sign*coef_dev[j]*y_j in VecMAXPY_Seq's grouping with

@@ -34,6 +34,8 @@ extern "C" {
 #define KSPCGHIPMI355X      "cghipmi355x"
 #define KSPGMRESHIPMI355X   "gmreshipmi355x"
 #define KSPBCGSHIPMI355X    "bcgshipmi355x"
+#define KSPCHEBYCHEVHIPMI355X  "chebychevhipmi355x"    /* needs vectors whose type offers "cheby_step" (include/petsckrylovfused.h): PETSC_ERR_SUP at set-up otherwise */
+#define KSPRICHARDSONHIPMI355X "richardsonhipmi355x"
 
 /* One call after PetscInitialize (or a PetscDLLibraryRegister entry, src/sys/dll): registers the types above with
  * VecRegister / MatRegister / PCRegister.  On the harness the same constructors are also registered under the

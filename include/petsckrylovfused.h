@@ -30,6 +30,16 @@ typedef struct {
    * computes what cg_update_dev_begin followed by aypx_dev computes, with one pass over p fewer */
   PetscErrorCode (*cg_update_dev_begin_nox)(Vec r, Vec z, Vec w, Vec d, PetscScalar beta, PetscScalar dpiold, PetscBool check_sign);
   PetscErrorCode (*aypx_dev_x)(Vec p, PetscScalar den, Vec z, Vec x, PetscScalar beta, PetscScalar dpiold, PetscBool check_sign);
+  /* One step of KSPSolve_Chebychev (cheby.c) behind w = A p[k]: r = b - w (VecAYPX; stored only with r != NULL, r may be w),
+   * z = d .* r (PCApply_Jacobi; d == NULL: identity), pn = s z (VecScale) + a pm (VecAXPY) + c pk (VecAXPY) with the special cases of
+   * those calls, and with zz, rr != NULL *zz = z'z, *rr = r'r (the sums VecNorm roots) -- one sweep, the bits of the separate calls.
+   * zz == rr == NULL: the pure element-wise form, nothing reduced, no host wait.  b == NULL: w is the preconditioned residual as
+   * given (any PC applied it, a null space was removed): z = w, d and r must be NULL, no sums, and w may be pn itself.
+   * pn overlaps no other operand.  *done = PETSC_FALSE and nothing touched otherwise. */
+  PetscErrorCode (*cheby_step)(Vec pn, Vec r, Vec w, Vec b, Vec d, Vec pm, Vec pk, PetscScalar s, PetscScalar a, PetscScalar c, PetscScalar *zz, PetscScalar *rr, PetscBool *done);
+  /* One step of KSPSolve_Richardson (rich.c) behind w = A x: r = b - w (stored with r != NULL, r may be w), z = d .* r (stored with
+   * z != NULL), x += scale z (VecAXPY) */
+  PetscErrorCode (*rich_step)(Vec x, Vec r, Vec z, Vec w, Vec b, Vec d, PetscScalar scale, PetscBool *done);
 } VecKrylovFusedOps;
 typedef const VecKrylovFusedOps *(*VecKrylovFusedOpsGetFn)(void);
 typedef PetscErrorCode (*MatMultTDotBeginFn)(Mat A, Vec x, Vec y, PetscBool *ok);

@@ -100,6 +100,9 @@ typedef enum { /* petscksp.h:403-430 */
   KSP_DIVERGED_NAN = -9, KSP_DIVERGED_INDEFINITE_MAT = -10, KSP_CONVERGED_ITERATING = 0
 } KSPConvergedReason;
 
+/* how PCApplyRichardson ended (include/petscpc.h); the values are those of the KSPConvergedReason of the same name */
+typedef enum { PCRICHARDSON_CONVERGED_RTOL = 2, PCRICHARDSON_CONVERGED_ATOL = 3, PCRICHARDSON_CONVERGED_ITS = 4, PCRICHARDSON_DIVERGED_DTOL = -4 } PCRichardsonConvergedReason;
+
 typedef struct _p_PetscComm  *PetscComm;    /* stands in for PetscComm (own name: coexists with <mpi.h>) */
 typedef struct _p_Vec        *Vec;
 typedef struct _p_Mat        *Mat;
@@ -130,6 +133,8 @@ typedef const char *PCType;
 #define KSPPREONLY "preonly"
 #define KSPPIPECG  "pipecg"    /* pipelined CG (src/ksp/ksp/impls/cg/pipecg/pipecg.c), SURVEY 8f.4 */
 #define KSPGROPPCG "groppcg"   /* Gropp's overlapped CG (src/ksp/ksp/impls/cg/groppcg/groppcg.c), SURVEY 8f.4 */
+#define KSPCHEBYCHEV  "chebychev"    /* Chebyshev iteration with given eigenvalue bounds (src/ksp/ksp/impls/cheby/cheby.c) */
+#define KSPRICHARDSON "richardson"   /* (damped) Richardson iteration (src/ksp/ksp/impls/rich/rich.c) */
 #define PCNONE     "none"
 #define PCJACOBI   "jacobi"
 #define PCBJACOBI  "bjacobi"
@@ -328,6 +333,10 @@ PetscErrorCode PCGetOperators(PC pc, Mat *Amat, Mat *Pmat, MatStructure *flag);
 PetscErrorCode PCSetUp(PC pc);
 PetscErrorCode PCSetUpOnBlocks(PC pc);
 PetscErrorCode PCApply(PC pc, Vec x, Vec y);
+/* precon.c PCApplyRichardson: `its` steps of Richardson's iteration with this preconditioner on A y = b done by the PC itself (PCSOR:
+ * ONE MatSOR call of its sweeps); w: a work vector; PETSC_ERR_SUP when the PC has no such method (KSPRICHARDSON asks first) */
+PetscErrorCode PCApplyRichardson(PC pc, Vec b, Vec y, Vec w, PetscReal rtol, PetscReal abstol, PetscReal dtol, PetscInt its, PetscBool guesszero, PetscInt *outits, PCRichardsonConvergedReason *reason);
+PetscErrorCode PCApplyRichardsonExists(PC pc, PetscBool *exists);
 PetscErrorCode PCSetFromOptions(PC pc);
 PetscErrorCode PCDestroy(PC *pc);
 PetscErrorCode PCFactorGetMatrix(PC pc, Mat *mat);   /* the factored matrix of a PCILU / PCICC (precon.c PCFactorGetMatrix) */
@@ -351,6 +360,10 @@ PetscErrorCode KSPSetOptionsPrefix(KSP ksp, const char prefix[]);
 PetscErrorCode KSPSetFromOptions(KSP ksp);   /* -ksp_type -ksp_rtol -ksp_atol -ksp_max_it -ksp_gmres_restart -ksp_gmres_cgs_refinement_type -pc_type -sub_* */
 PetscErrorCode KSPGMRESSetRestart(KSP ksp, PetscInt restart);
 PetscErrorCode KSPGMRESSetCGSRefinementType(KSP ksp, KSPGMRESCGSRefinementType type);
+/* cheby.c / rich.c: PetscTryMethod on "KSPChebychevSetEigenvalues_C" / "KSPRichardsonSetScale_C" -- a type that composed the method
+ * answers, any other type ignores the call.  Options: -ksp_chebychev_eigenvalues <emin,emax>, -ksp_richardson_scale <s> */
+PetscErrorCode KSPChebychevSetEigenvalues(KSP ksp, PetscReal emax, PetscReal emin);
+PetscErrorCode KSPRichardsonSetScale(KSP ksp, PetscReal scale);
 PetscErrorCode KSPSetUp(KSP ksp);
 PetscErrorCode KSPSetUpOnBlocks(KSP ksp);
 PetscErrorCode KSPSolve(KSP ksp, Vec b, Vec x);

@@ -836,6 +836,97 @@ struct BcgsUpdateF {
   }
 };
 
+// ---- one step of KSPSolve_Chebychev (cheby.c) or KSPSolve_Richardson (rich.c) behind the product w = A p, KSP_NORM_NONE's whole
+// iteration besides that product.  The residual, the diagonal preconditioner and the update in one sweep:
+//   rv = b - w                (VecAYPX(r, -1, b) on r = w: OpXmY);     b == NULL: w is the preconditioned residual itself, zv = w
+//   zv = rv * d               (PCApply_Jacobi: OpMul;  d == NULL: PCNONE's copy)
+//   Chebyshev:   o = s zv + a pm + c pk     (VecScale, VecAXPY, VecAXPY with their special cases: OpScale, OpAxpy, OpAxpy)
+//   Richardson:  o = o + s zv               (VecAXPY: OpAxpy)
+// Each product and each sum is rounded as in those kernels, and with sums a lane meets its elements in SumSqF's order under
+// launch_reduce: every output carries the bits of the separate launches.  An operand a special case skips is not loaded.
+// Streaming (see nt_load2): b, d and pm have their only reader of the iteration here and r, z (when somebody wants them stored) no
+// reader soon: non-temporal at every size, as the CG sweep treats d, x and r.  w (just written by the product), pk (next
+// iteration's pm) and o (gathered by the next product) stay cacheable below 256 MiB and are streamed from there on like every
+// other tile kernel.  A choice by analogy with the CG sweep: DESIGN.md has what was measured.
+struct KrylovStepF {
+  double s, a, c;
+  const double *w, *b, *d, *pm, *pk;
+  double *r, *z, *o;
+  int rich, big;
+  __device__ __forceinline__ void one(double wv, double bv, double dv, double pmv, double pkv, double &rv, double &zv, double &ov) const {
+    rv = b ? bv - wv : wv;
+    zv = d ? rv * dv : rv;
+    if (rich) { ov = (s == 0.0) ? ov : ov + s * zv; return; }          // VecAXPY returns at once for alpha == 0 (bvec1.c:253)
+    double t = (s == 1.0) ? zv : ((s == 0.0) ? 0.0 : s * zv);          // VecScale_Seq (bvec1.c:183): 1 -> nothing, 0 -> VecSet(0)
+    t = (a == 0.0) ? t : t + a * pmv;
+    ov = (c == 0.0) ? t : t + c * pkv;
+  }
+  // which operands this form reads (uniform over the launch)
+  __device__ __forceinline__ bool reads_pm() const { return !rich && a != 0.0; }
+  __device__ __forceinline__ bool reads_pk() const { return !rich && c != 0.0; }
+  __device__ __forceinline__ bool reads_o() const { return rich && s != 0.0; }
+  __device__ __forceinline__ bool writes_o() const { return !rich || s != 0.0; }
+  // the U double2's of a lane in its tile; every load is issued before the first store, so r may be w and (b == NULL) o may be w
+  template <bool BIG, int U>
+  __device__ __forceinline__ void tile(size_t i, double2 (&rv)[U], double2 (&zv)[U]) const {
+    double2 wv[U], bv[U] = {}, dv[U] = {}, pmv[U] = {}, pkv[U] = {}, ov[U] = {};
+    ld_tile<BIG>(reinterpret_cast<const double2 *>(w), i, wv);
+    if (b) ld_tile<true>(reinterpret_cast<const double2 *>(b), i, bv);
+    if (d) ld_tile<true>(reinterpret_cast<const double2 *>(d), i, dv);
+    if (reads_pm()) ld_tile<true>(reinterpret_cast<const double2 *>(pm), i, pmv);
+    if (reads_pk()) ld_tile<BIG>(reinterpret_cast<const double2 *>(pk), i, pkv);
+    if (reads_o()) ld_tile<BIG>(reinterpret_cast<const double2 *>(o), i, ov);
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      one(wv[j].x, bv[j].x, dv[j].x, pmv[j].x, pkv[j].x, rv[j].x, zv[j].x, ov[j].x);
+      one(wv[j].y, bv[j].y, dv[j].y, pmv[j].y, pkv[j].y, rv[j].y, zv[j].y, ov[j].y);
+    }
+    if (r) st_tile<true>(reinterpret_cast<double2 *>(r), i, rv);
+    if (z) st_tile<true>(reinterpret_cast<double2 *>(z), i, zv);
+    if (writes_o()) st_tile<BIG>(reinterpret_cast<double2 *>(o), i, ov);
+  }
+  __device__ __forceinline__ void at1(size_t k, double &rv, double &zv) const {
+    double ov = reads_o() ? o[k] : 0.0;
+    one(w[k], b ? b[k] : 0.0, d ? d[k] : 0.0, reads_pm() ? pm[k] : 0.0, reads_pk() ? pk[k] : 0.0, rv, zv, ov);
+    if (r) r[k] = rv;
+    if (z) z[k] = zv;
+    if (writes_o()) o[k] = ov;
+  }
+  // under launch_reduce: out = { sum zv*zv, sum rv*rv }, the trees of mi355x_vec_norm(type 1) over z and over r
+  template <int NOUT_>
+  __device__ __forceinline__ void sweep(size_t tid, size_t stride, size_t n2, double (&acc)[NOUT_]) const {
+    for (size_t i = tid; i < n2; i += stride) {
+      double2 rv[1], zv[1];
+      if (big) tile<true, 1>(i, rv, zv); else tile<false, 1>(i, rv, zv);
+      acc[0] += zv[0].x * zv[0].x; acc[1] += rv[0].x * rv[0].x;
+      acc[0] += zv[0].y * zv[0].y; acc[1] += rv[0].y * rv[0].y;
+    }
+  }
+  __device__ __forceinline__ void accum1(size_t k, double (&acc)[2]) const {
+    double rv, zv;
+    at1(k, rv, zv);
+    acc[0] += zv * zv; acc[1] += rv * rv;
+  }
+};
+// the same body as a pure map: one tile of 256 x 2 double2 per workgroup, nothing reduced
+template <bool BIG>
+__global__ __launch_bounds__(MI355X_BLOCK) void krylov_step_kernel(KrylovStepF f, size_t n, int vec_ok) {
+  tile_walk<2>(n, vec_ok,
+    [&](size_t i, auto u) {
+      constexpr int U = decltype(u)::value;
+      double2 rv[U], zv[U];
+      f.template tile<BIG, U>(i, rv, zv);
+    },
+    [&](size_t k) { double rv, zv; f.at1(k, rv, zv); });
+}
+static int launch_krylov_step(mi355x_handle_t h, size_t n, KrylovStepF f, int sums, double *out) {
+  const int vec_ok = all_aligned16(f.w, f.b, f.d, f.pm, f.pk, f.r, f.z, f.o);   // an operand the form does not touch is NULL
+  f.big = vec_streams(n);
+  if (sums) return launch_reduce<2, RED_SUM>(h, f, n, vec_ok, out);             // n == 0: zeros
+  if (n == 0) return 0;
+  return launch_tiles(h, n, vec_ok, krylov_step_kernel<true>, krylov_step_kernel<false>, f);
+}
+
 template <int NV>
 struct MDotF {
   const double *x;
@@ -1102,6 +1193,17 @@ int mi355x_vec_bcgs_update(mi355x_handle_t h, size_t n, double alpha, double ome
                            const double *rp, double *x, double *r, double *out) {
   BcgsUpdateF f{alpha, omega, -omega, p, s, t, rp, x, r};
   return launch_reduce<2, RED_SUM>(h, f, n, all_aligned16(p, s, t, rp, x, r), out);
+}
+
+int mi355x_vec_cheby_step(mi355x_handle_t h, size_t n, double s, double a, double c, const double *w, const double *b, const double *d,
+                          const double *pm, const double *pk, double *r, double *pn, int sums, double *out) {
+  // b == NULL: w is the preconditioned residual as given (a general PC applied it): nothing to precondition, store or sum here
+  if (!w || !pn || (!b && (d || r || sums)) || (sums && !out) || (a != 0.0 && !pm) || (c != 0.0 && !pk)) return (int)hipErrorInvalidValue;
+  return launch_krylov_step(h, n, KrylovStepF{s, a, c, w, b, d, pm, pk, r, nullptr, pn, 0, 0}, sums, out);
+}
+int mi355x_vec_rich_step(mi355x_handle_t h, size_t n, double scale, const double *w, const double *b, const double *d, double *r, double *z, double *x) {
+  if (!w || !b || !x) return (int)hipErrorInvalidValue;
+  return launch_krylov_step(h, n, KrylovStepF{scale, 0.0, 0.0, w, b, d, nullptr, nullptr, r, z, x, 1, 0}, 0, nullptr);
 }
 
 // borthog2.c:63-64 + the norm of gmres.c:146: x += sum_j sign * coef_dev[j] * y_j, *out = sum x_new^2 (out: device or the

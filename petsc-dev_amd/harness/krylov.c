@@ -11,6 +11,8 @@
  *   pipelined CG  src/ksp/ksp/impls/cg/pipecg/pipecg.c:49-205
  *   GMRES(m)      src/ksp/ksp/impls/gmres/gmres.c:118-409, classical Gram-Schmidt src/ksp/ksp/impls/gmres/borthog2.c:35-119
  *   BiCGStab      src/ksp/ksp/impls/bcgs/bcgs.c:43-160
+ *   Chebyshev     src/ksp/ksp/impls/cheby/cheby.c (KSPSolve_Chebychev; eigenvalue bounds from the user, no estimation)
+ *   Richardson    src/ksp/ksp/impls/rich/rich.c (KSPSolve_Richardson; fixed scale, no self-scaling), PCApplyRichardson precon.c, sor.c
  * and are written here over a few shared pieces: one checkpoint routine (history, monitor, convergence test), one start-residual
  * routine for the CG family, index-addressed Hessenberg columns for GMRES. */
 #include "petscimpl.h"
@@ -590,5 +592,210 @@ PetscErrorCode KSPCreate_BCGS(KSP ksp) {   /* bcgs.c:246 (left preconditioning o
   ksp->normsupporttable[KSP_NORM_PRECONDITIONED][PC_LEFT] = 2;
   ksp->ops->setup = KSPSetUp_BCGS;
   ksp->ops->solve = KSPSolve_BCGS;
+  return 0;
+}
+
+/* the norms the two stationary-type solvers accept (cheby.c, rich.c KSPCreate_*): preconditioned first, left preconditioning only */
+static void stationary_norm_table(KSP ksp) {
+  ksp->normsupporttable[KSP_NORM_PRECONDITIONED][PC_LEFT] = 2;
+  ksp->normsupporttable[KSP_NORM_UNPRECONDITIONED][PC_LEFT] = 1;
+}
+/* "-name <real>[,<real>]" read as text; returns how many numbers were given */
+static PetscErrorCode option_reals(KSP ksp, const char *name, PetscReal v[2], int *count) {
+  char text[96], *end; PetscBool given;
+  *count = 0;
+  OK(PetscOptionsGetString(ksp->prefix, name, text, sizeof(text), &given));
+  if (!given) return 0;
+  v[0] = strtod(text, &end);
+  if (end == text) SETERRQ(ksp->comm, PETSC_ERR_ARG_WRONG, "%s needs a number, got \"%s\"", name, text);
+  *count = 1;
+  if (*end == ',') { char *second = end + 1; v[1] = strtod(second, &end); if (end != second) *count = 2; }
+  return 0;
+}
+
+/* ================================================================== Chebyshev (cheby.c KSPSolve_Chebychev), eigenvalue bounds from the user
+ * The three-term recurrence over x itself and two work vectors, rotated after every update; a third work vector takes the residual.
+ * Without a norm an iteration is one product, one preconditioner application and the update. */
+typedef struct { PetscReal emin, emax; } ChebyData;
+#define CHD(ksp) ((ChebyData *)(ksp)->data)
+
+static PetscErrorCode KSPChebychevSetEigenvalues_Chebychev(KSP ksp, PetscReal emax, PetscReal emin) {   /* cheby.c:27-39 */
+  if (emax <= emin) SETERRQ(ksp->comm, PETSC_ERR_ARG_INCOMP, "Maximum eigenvalue must be larger than minimum: max %g min %g", emax, emin);
+  if (emax * emin <= 0.0) SETERRQ(ksp->comm, PETSC_ERR_ARG_INCOMP, "Both eigenvalues must be of the same sign: max %g min %g", emax, emin);
+  CHD(ksp)->emax = emax; CHD(ksp)->emin = emin;
+  return 0;
+}
+static PetscErrorCode KSPSetUp_Chebychev(KSP ksp) { return KSPDefaultGetWork(ksp, 3); }
+static PetscErrorCode KSPSetFromOptions_Chebychev(KSP ksp) {   /* -ksp_chebychev_eigenvalues <emin,emax> */
+  PetscReal v[2]; int count;
+  OK(option_reals(ksp, "-ksp_chebychev_eigenvalues", v, &count));
+  if (count == 1) SETERRQ(ksp->comm, PETSC_ERR_ARG_INCOMP, "-ksp_chebychev_eigenvalues: must specify 2 parameters, min and max eigenvalues");
+  if (count == 2) OK(KSPChebychevSetEigenvalues(ksp, v[1], v[0]));
+  return 0;
+}
+static PetscErrorCode KSPDestroy_Chebychev(KSP ksp) {
+  free(ksp->data); ksp->data = NULL;
+  (void)PetscObjectComposeFunction((PetscObject)ksp, "KSPChebychevSetEigenvalues_C", "", (PetscVoidFunction)NULL);
+  return 0;
+}
+
+static PetscErrorCode KSPSolve_Chebychev(KSP ksp) {
+  const KSPNormType norm = ksp->normtype;
+  const PetscReal emin = CHD(ksp)->emin, emax = CHD(ksp)->emax;
+  Vec x = ksp->vec_sol, rhs = ksp->vec_rhs, res = ksp->work[2];
+  Vec p[3] = {x, ksp->work[0], ksp->work[1]};
+  Mat A = ksp->pc->mat;
+  PetscScalar c[3], scale, mu, omegaprod, omega, Gamma = 1.0;
+  PetscReal rn = 0.0;
+  PetscInt km1 = 0, k = 1, kp1 = 2, i;
+
+  ksp->its = 0;
+  scale = 2.0 / (emax + emin);
+  mu = 1.0 / (1.0 - scale * emin);
+  omegaprod = 2.0 / (1.0 - scale * emin);
+  c[km1] = 1.0; c[k] = mu;
+  OK(cg_family_start(ksp, A, x, rhs, res));
+  OK(KSP_PCApply(ksp, res, p[k]));
+  OK(VecAYPX(p[k], scale, x));                                      /* p[k] <- x + scale B res */
+  for (i = 0; i < ksp->max_it; i++) {
+    ksp->its++;
+    c[kp1] = 2.0 * mu * c[k] - c[km1];
+    omega = omegaprod * c[k] / c[kp1];
+    OK(KSP_MatMult(ksp, A, p[k], res));
+    OK(VecAYPX(res, -1.0, rhs));
+    OK(KSP_PCApply(ksp, res, p[kp1]));
+    if (norm != KSP_NORM_NONE) {                                    /* the checkpoint sees p[k]'s residual; p[kp1] holds B res only */
+      OK(VecNorm(norm == KSP_NORM_UNPRECONDITIONED ? res : p[kp1], NORM_2, &rn));
+      ksp->vec_sol = p[k];
+      OK(checkpoint(ksp, i, rn));
+      if (ksp->reason) break;
+    }
+    OK(VecScale(p[kp1], omega * Gamma * scale));                    /* p[kp1] <- omega Gamma scale B res + (1 - omega) p[km1] + omega p[k] */
+    OK(VecAXPY(p[kp1], 1.0 - omega, p[km1]));
+    OK(VecAXPY(p[kp1], omega, p[k]));
+    { const PetscInt was = km1; km1 = k; k = kp1; kp1 = was; }
+  }
+  if (!ksp->reason) {
+    if (norm != KSP_NORM_NONE) {
+      OK(KSP_MatMult(ksp, A, p[k], res));
+      OK(VecAYPX(res, -1.0, rhs));
+      if (norm == KSP_NORM_UNPRECONDITIONED) OK(VecNorm(res, NORM_2, &rn));
+      else { OK(KSP_PCApply(ksp, res, p[kp1])); OK(VecNorm(p[kp1], NORM_2, &rn)); }
+      ksp->vec_sol = p[k];
+      ksp->rnorm = rn;
+      KSPLogResidualHistory(ksp, rn);
+      OK(KSPMonitor(ksp, ksp->its, rn));
+    }
+    if (ksp->its >= ksp->max_it) {
+      if (norm != KSP_NORM_NONE) {
+        OK((*ksp->converged)(ksp, ksp->its, rn, &ksp->reason, ksp->cnvP));
+        if (!ksp->reason) ksp->reason = KSP_DIVERGED_ITS;
+      } else ksp->reason = KSP_CONVERGED_ITS;
+    }
+  }
+  ksp->vec_sol = x;
+  if (p[k] != x) OK(VecCopy(p[k], x));
+  return 0;
+}
+PetscErrorCode KSPCreate_Chebychev(KSP ksp) {   /* cheby.c KSPCreate_Chebychev: emin 1e-2, emax 1e+2 */
+  ChebyData *data;
+  OK(PetscMalloc(sizeof(*data), &data));
+  data->emin = 1.0e-2; data->emax = 1.0e+2;
+  ksp->data = data;
+  stationary_norm_table(ksp);
+  ksp->ops->setup = KSPSetUp_Chebychev;
+  ksp->ops->solve = KSPSolve_Chebychev;
+  ksp->ops->setfromoptions = KSPSetFromOptions_Chebychev;
+  ksp->ops->destroy = KSPDestroy_Chebychev;
+  OK(PetscObjectComposeFunction((PetscObject)ksp, "KSPChebychevSetEigenvalues_C", "KSPChebychevSetEigenvalues_Chebychev", (PetscVoidFunction)KSPChebychevSetEigenvalues_Chebychev));
+  return 0;
+}
+
+/* ================================================================== Richardson (rich.c KSPSolve_Richardson), fixed damping
+ * x <- x + scale B (rhs - A x).  A preconditioner that can run the whole iteration itself (PCApplyRichardson: PCSOR) does, when nobody
+ * watches the residuals: -pc_type sor then costs ONE MatSOR call of max_it sweeps. */
+typedef struct { PetscReal scale; } RichData;
+#define RID(ksp) ((RichData *)(ksp)->data)
+
+static PetscErrorCode KSPRichardsonSetScale_Richardson(KSP ksp, PetscReal scale) { RID(ksp)->scale = scale; return 0; }
+static PetscErrorCode KSPSetUp_Richardson(KSP ksp) { return KSPDefaultGetWork(ksp, 2); }
+static PetscErrorCode KSPSetFromOptions_Richardson(KSP ksp) {   /* -ksp_richardson_scale <s> */
+  PetscReal v[2]; int count;
+  OK(option_reals(ksp, "-ksp_richardson_scale", v, &count));
+  if (count) OK(KSPRichardsonSetScale(ksp, v[0]));
+  return 0;
+}
+static PetscErrorCode KSPDestroy_Richardson(KSP ksp) {
+  free(ksp->data); ksp->data = NULL;
+  (void)PetscObjectComposeFunction((PetscObject)ksp, "KSPRichardsonSetScale_C", "", (PetscVoidFunction)NULL);
+  return 0;
+}
+
+static PetscErrorCode KSPSolve_Richardson(KSP ksp) {
+  const KSPNormType norm = ksp->normtype;
+  const PetscReal scale = RID(ksp)->scale;
+  Vec x = ksp->vec_sol, rhs = ksp->vec_rhs, res = ksp->work[0], z = ksp->work[1];
+  Mat A = ksp->pc->mat;
+  PetscReal rn = 0.0;
+  PetscBool whole;
+  PetscInt i;
+
+  OK(PCApplyRichardsonExists(ksp->pc, &whole));
+  if (whole && !ksp->monitor && !ksp->nullsp) {                     /* rich.c:47-56 */
+    PCRichardsonConvergedReason why;
+    OK(PCApplyRichardson(ksp->pc, rhs, x, res, ksp->rtol, ksp->abstol, ksp->divtol, ksp->max_it, ksp->guess_zero, &ksp->its, &why));
+    ksp->reason = (KSPConvergedReason)why;
+    return 0;
+  }
+  OK(cg_family_start(ksp, A, x, rhs, res));
+  ksp->its = 0;
+  for (i = 0; i < ksp->max_it; i++) {
+    if (norm == KSP_NORM_UNPRECONDITIONED) {
+      OK(VecNorm(res, NORM_2, &rn));
+      OK(checkpoint(ksp, i, rn));
+      if (ksp->reason) break;
+    }
+    OK(KSP_PCApply(ksp, res, z));
+    if (norm == KSP_NORM_PRECONDITIONED) {
+      OK(VecNorm(z, NORM_2, &rn));
+      OK(checkpoint(ksp, i, rn));
+      if (ksp->reason) break;
+    }
+    OK(VecAXPY(x, scale, z));
+    ksp->its++;
+    if (i + 1 < ksp->max_it || norm != KSP_NORM_NONE) {
+      OK(KSP_MatMult(ksp, A, x, res));
+      OK(VecAYPX(res, -1.0, rhs));
+    }
+  }
+  if (!ksp->reason) {
+    if (norm != KSP_NORM_NONE) {
+      if (norm == KSP_NORM_UNPRECONDITIONED) OK(VecNorm(res, NORM_2, &rn));
+      else { OK(KSP_PCApply(ksp, res, z)); OK(VecNorm(z, NORM_2, &rn)); }
+      ksp->rnorm = rn;
+      KSPLogResidualHistory(ksp, rn);
+      OK(KSPMonitor(ksp, ksp->its, rn));
+    }
+    if (ksp->its >= ksp->max_it) {
+      if (norm == KSP_NORM_NONE) ksp->reason = KSP_CONVERGED_ITS;
+      else {
+        OK((*ksp->converged)(ksp, ksp->its, rn, &ksp->reason, ksp->cnvP));
+        if (!ksp->reason) ksp->reason = KSP_DIVERGED_ITS;
+      }
+    }
+  }
+  return 0;
+}
+PetscErrorCode KSPCreate_Richardson(KSP ksp) {   /* rich.c KSPCreate_Richardson: scale 1.0 */
+  RichData *data;
+  OK(PetscMalloc(sizeof(*data), &data));
+  data->scale = 1.0;
+  ksp->data = data;
+  stationary_norm_table(ksp);
+  ksp->ops->setup = KSPSetUp_Richardson;
+  ksp->ops->solve = KSPSolve_Richardson;
+  ksp->ops->setfromoptions = KSPSetFromOptions_Richardson;
+  ksp->ops->destroy = KSPDestroy_Richardson;
+  OK(PetscObjectComposeFunction((PetscObject)ksp, "KSPRichardsonSetScale_C", "KSPRichardsonSetScale_Richardson", (PetscVoidFunction)KSPRichardsonSetScale_Richardson));
   return 0;
 }

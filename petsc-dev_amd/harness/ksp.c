@@ -150,6 +150,21 @@ PetscErrorCode KSPGMRESSetCGSRefinementType(KSP ksp, KSPGMRESCGSRefinementType t
   if (f) { ierr = ((PetscErrorCode (*)(KSP, KSPGMRESCGSRefinementType))f)(ksp, type);CHKERRQ(ierr); }
   return 0;
 }
+/* KSPChebychevSetEigenvalues (cheby.c), KSPRichardsonSetScale (rich.c): PetscTryMethod as well */
+PetscErrorCode KSPChebychevSetEigenvalues(KSP ksp, PetscReal emax, PetscReal emin) {
+  PetscVoidFunction f = NULL;
+  KSPValid(ksp);
+  PetscErrorCode ierr = PetscObjectQueryFunction((PetscObject)ksp, "KSPChebychevSetEigenvalues_C", &f);CHKERRQ(ierr);
+  if (f) { ierr = ((PetscErrorCode (*)(KSP, PetscReal, PetscReal))f)(ksp, emax, emin);CHKERRQ(ierr); }
+  return 0;
+}
+PetscErrorCode KSPRichardsonSetScale(KSP ksp, PetscReal scale) {
+  PetscVoidFunction f = NULL;
+  KSPValid(ksp);
+  PetscErrorCode ierr = PetscObjectQueryFunction((PetscObject)ksp, "KSPRichardsonSetScale_C", &f);CHKERRQ(ierr);
+  if (f) { ierr = ((PetscErrorCode (*)(KSP, PetscReal))f)(ksp, scale);CHKERRQ(ierr); }
+  return 0;
+}
 PetscErrorCode KSPSetOptionsPrefix(KSP ksp, const char prefix[]) {
   KSPValid(ksp);
   snprintf(ksp->prefix, sizeof(ksp->prefix), "%s", prefix ? prefix : "");

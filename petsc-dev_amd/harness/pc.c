@@ -47,6 +47,8 @@ PetscErrorCode PetscMiniInitialize(void) {
   ierr = KSPRegister(KSPGMRES, 0, "KSPCreate_GMRES", KSPCreate_GMRES);CHKERRQ(ierr);
   ierr = KSPRegister(KSPBCGS, 0, "KSPCreate_BCGS", KSPCreate_BCGS);CHKERRQ(ierr);
   ierr = KSPRegister(KSPPREONLY, 0, "KSPCreate_PREONLY", KSPCreate_PREONLY);CHKERRQ(ierr);
+  ierr = KSPRegister(KSPCHEBYCHEV, 0, "KSPCreate_Chebychev", KSPCreate_Chebychev);CHKERRQ(ierr);
+  ierr = KSPRegister(KSPRICHARDSON, 0, "KSPCreate_Richardson", KSPCreate_Richardson);CHKERRQ(ierr);
   return 0;
 }
 
@@ -116,6 +118,21 @@ PetscErrorCode PCApply(PC pc, Vec x, Vec y) {   /* precon.c:369-388 */
   ierr = (*pc->ops->apply)(pc, x, y);CHKERRQ(ierr);
   return 0;
 }
+/* precon.c PCApplyRichardsonExists / PCApplyRichardson */
+PetscErrorCode PCApplyRichardsonExists(PC pc, PetscBool *exists) {
+  if (!pc) SETERRQ(0, PETSC_ERR_ARG_NULL, "Null PC");
+  *exists = (PetscBool)(pc->ops->applyrichardson != NULL);
+  return 0;
+}
+PetscErrorCode PCApplyRichardson(PC pc, Vec b, Vec y, Vec w, PetscReal rtol, PetscReal abstol, PetscReal dtol, PetscInt its, PetscBool guesszero, PetscInt *outits, PCRichardsonConvergedReason *reason) {
+  PetscErrorCode ierr;
+  if (!pc) SETERRQ(0, PETSC_ERR_ARG_NULL, "Null PC");
+  if (b == y) SETERRQ(pc->comm, PETSC_ERR_ARG_IDN, "b and y must be different vectors");
+  if (pc->setupcalled < 2) { ierr = PCSetUp(pc);CHKERRQ(ierr); }
+  if (!pc->ops->applyrichardson) SETERRQ(pc->comm, PETSC_ERR_SUP, "PC does not have apply richardson");
+  ierr = (*pc->ops->applyrichardson)(pc, b, y, w, rtol, abstol, dtol, its, guesszero, outits, reason);CHKERRQ(ierr);
+  return 0;
+}
 PetscErrorCode PCDestroy(PC *ppc) {
   PetscErrorCode ierr;
   PC pc = *ppc;
@@ -178,6 +195,16 @@ static PetscErrorCode PCApply_SOR(PC pc, Vec x, Vec y) {   /* sor.c:30-42 */
   PC_SOR *jac = (PC_SOR *)pc->data;
   return MatSOR(pc->pmat, x, jac->omega, (MatSORType)(jac->sym | SOR_ZERO_INITIAL_GUESS), jac->fshift, jac->its, jac->lits, y);
 }
+/* PCApplyRichardson_SOR, sor.c:44-58: its Richardson steps with this PC ARE its * jac->its sweeps of the operator's own MatSOR on y */
+static PetscErrorCode PCApplyRichardson_SOR(PC pc, Vec b, Vec y, Vec w, PetscReal rtol, PetscReal abstol, PetscReal dtol, PetscInt its, PetscBool guesszero, PetscInt *outits, PCRichardsonConvergedReason *reason) {
+  PC_SOR *jac = (PC_SOR *)pc->data;
+  const MatSORType stype = (MatSORType)(jac->sym | (guesszero ? SOR_ZERO_INITIAL_GUESS : 0));
+  (void)w; (void)rtol; (void)abstol; (void)dtol;
+  PetscErrorCode ierr = MatSOR(pc->pmat, b, jac->omega, stype, jac->fshift, its * jac->its, jac->lits, y);CHKERRQ(ierr);
+  *outits = its;
+  *reason = PCRICHARDSON_CONVERGED_ITS;
+  return 0;
+}
 static PetscErrorCode PCSetFromOptions_SOR(PC pc) {   /* sor.c:75-105: the sweep options in the reference's order, the last one given wins */
   static const struct { const char *name; MatSORType sym; } kinds[] = {
     {"-pc_sor_symmetric", SOR_SYMMETRIC_SWEEP}, {"-pc_sor_backward", SOR_BACKWARD_SWEEP}, {"-pc_sor_forward", SOR_FORWARD_SWEEP},
@@ -202,7 +229,7 @@ PetscErrorCode PCCreate_SOR(PC pc) {   /* sor.c:330-350 */
   PetscErrorCode ierr = PetscMalloc(sizeof(*jac), &jac);CHKERRQ(ierr);
   jac->sym = SOR_LOCAL_SYMMETRIC_SWEEP; jac->omega = 1.0; jac->fshift = 0.0; jac->its = 1; jac->lits = 1;
   pc->data = jac;
-  pc->ops->apply = PCApply_SOR; pc->ops->setfromoptions = PCSetFromOptions_SOR; pc->ops->destroy = PCDestroy_SOR;
+  pc->ops->apply = PCApply_SOR; pc->ops->applyrichardson = PCApplyRichardson_SOR; pc->ops->setfromoptions = PCSetFromOptions_SOR; pc->ops->destroy = PCDestroy_SOR;
   return 0;
 }
 

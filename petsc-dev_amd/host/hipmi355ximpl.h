@@ -331,5 +331,7 @@ PetscErrorCode PCCreate_PBJacobi_HIPMI355X(PC);
 PetscErrorCode KSPCreate_CGHIPMI355X(KSP);
 PetscErrorCode KSPCreate_GMRESHIPMI355X(KSP);
 PetscErrorCode KSPCreate_BCGSHIPMI355X(KSP);
+PetscErrorCode KSPCreate_ChebychevHIPMI355X(KSP);
+PetscErrorCode KSPCreate_RichardsonHIPMI355X(KSP);
 
 #endif

@@ -4,13 +4,17 @@
  *     KSPCGHIPMI355X    "cghipmi355x"      CG        (the recurrence of KSPCG,    src/ksp/ksp/impls/cg/cg.c:92-286)
  *     KSPGMRESHIPMI355X "gmreshipmi355x"   GMRES(m)  (the cycle of KSPGMRES,      src/ksp/ksp/impls/gmres/gmres.c:118-409, borthog2.c:35-119)
  *     KSPBCGSHIPMI355X  "bcgshipmi355x"    BiCGStab  (the recurrence of KSPBCGS,  src/ksp/ksp/impls/bcgs/bcgs.c:43-160)
+ *     KSPCHEBYCHEVHIPMI355X  "chebychevhipmi355x"   Chebyshev  (the sequence of KSPCHEBYCHEV,  src/ksp/ksp/impls/cheby/cheby.c)
+ *     KSPRICHARDSONHIPMI355X "richardsonhipmi355x"  Richardson (the sequence of KSPRICHARDSON, src/ksp/ksp/impls/rich/rich.c)
  *
  * They compute what the reference's solvers compute -- same iterates, same residual history, same exits, bit for bit against
  * the op-by-op sequences (tests/test_host_gpu.py) -- but group the vector work between two reductions into the fused sweeps a
  * Vec / Mat type may offer by name ("VecKrylovFusedOps_C", "MatMultTDotBegin_C", "MatMultDiagonalScale_C";
  * include/petsckrylovfused.h), keep scalars that only the device needs on the device, and queue the front half of the next
  * iteration before the host has looked at the residual norm.  On vectors of a type without those methods every step falls
- * back to the public Vec / Mat / PC calls, so the types work on any PETSc objects.
+ * back to the public Vec / Mat / PC calls, so the types work on any PETSc objects -- with ONE exception: chebychevhipmi355x.  The
+ * three-term Chebyshev update needs VecScale, which is not among the calls this library takes from PETSc, so there is nothing to fall
+ * back to: KSPSetUp of that type returns PETSC_ERR_SUP on vectors whose type lacks "cheby_step" and names -ksp_type chebychev.
  *
  * Written against the public API and the KSP implementation header only (petsc-private/kspimpl.h inside a PETSc tree, the
  * harness's petscimpl.h on a box without PETSc): nothing here reaches into a Vec, a Mat or a PC.  An unchanged PETSc program
@@ -617,5 +621,250 @@ PetscErrorCode KSPCreate_BCGSHIPMI355X(KSP ksp) {
   ksp->data = bc;
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);
   ksp->ops->setup = KSPSetUp_BCGSHIP; ksp->ops->solve = KSPSolve_BCGSHIP; ksp->ops->setfromoptions = KSPSetFromOptions_BCGSHIP; ksp->ops->destroy = KSPDestroy_BCGSHIP;
+  return 0;
+}
+
+/* ================================================================================================ Chebyshev and Richardson
+ * The sequences of KSPSolve_Chebychev (src/ksp/ksp/impls/cheby/cheby.c; eigenvalue bounds from the user: KSPChebychevSetEigenvalues,
+ * -ksp_chebychev_eigenvalues <emin,emax>) and KSPSolve_Richardson (src/ksp/ksp/impls/rich/rich.c; KSPRichardsonSetScale,
+ * -ksp_richardson_scale <s>; never PCApplyRichardson), same iterates, histories and exits as those.  What follows the product of an
+ * iteration -- residual, PCJACOBI / PCNONE, update, and for Chebyshev the norm's sums -- is ONE sweep ("cheby_step", "rich_step" of
+ * include/petsckrylovfused.h): with KSP_NORM_NONE an iteration is a product and an element-wise pass, nothing is reduced and the host
+ * never waits.  Any other PC, or a null space: the public calls, and for Chebyshev the three-term update alone in the sweep. */
+static PetscErrorCode option_reals(KSP ksp, const char *name, PetscReal v[2], int *count) {   /* "-name <real>[,<real>]" */
+  char t[96], *comma; PetscBool set;
+  PetscErrorCode ierr = PetscOptionsGetString(HipObjPrefix(ksp), name, t, sizeof(t), &set);CHKERRQ(ierr);
+  *count = 0;
+  if (!set || !t[0]) return 0;
+  comma = strchr(t, ',');
+  if (comma) { *comma = 0; v[1] = atof(comma + 1); }
+  v[0] = atof(t);
+  *count = comma ? 2 : 1;
+  return 0;
+}
+static PetscErrorCode start_residual(KSP ksp, Mat A, Vec x, Vec rhs, Vec r) {
+  PetscErrorCode ierr;
+  if (ksp->guess_zero) { ierr = VecCopy(rhs, r);CHKERRQ(ierr); }
+  else { ierr = KSP_MatMult(ksp, A, x, r);CHKERRQ(ierr); ierr = VecAYPX(r, -1.0, rhs);CHKERRQ(ierr); }
+  return 0;
+}
+/* the exit both solvers share once the loop has ended without a reason (cheby.c, rich.c): the budget is spent */
+static PetscErrorCode stationary_out_of_iterations(KSP ksp, PetscReal rn) {
+  PetscErrorCode ierr;
+  if (ksp->its < ksp->max_it) return 0;
+  if (ksp->normtype == KSP_NORM_NONE) { ksp->reason = KSP_CONVERGED_ITS; return 0; }
+  ierr = KSPTestConvergence(ksp, ksp->its, rn);CHKERRQ(ierr);
+  if (!ksp->reason) ksp->reason = KSP_DIVERGED_ITS;
+  return 0;
+}
+
+typedef struct { PetscReal emin, emax; Vec dinv; } KSP_ChebyHIP;
+
+static PetscErrorCode KSPChebychevSetEigenvalues_ChebyHIP(KSP ksp, PetscReal emax, PetscReal emin) {
+  KSP_ChebyHIP *ch = (KSP_ChebyHIP *)ksp->data;
+  if (emax <= emin) SETERRQ(HipObjComm(ksp), PETSC_ERR_ARG_INCOMP, "Maximum eigenvalue must be larger than minimum: max %g min %g", (double)emax, (double)emin);
+  if (emax * emin <= 0.0) SETERRQ(HipObjComm(ksp), PETSC_ERR_ARG_INCOMP, "Both eigenvalues must be of the same sign: max %g min %g", (double)emax, (double)emin);
+  ch->emax = emax; ch->emin = emin;
+  return 0;
+}
+/* the three-term update cannot be written with the public calls this library may use (no VecScale): the vectors' type must offer it */
+static PetscErrorCode KSPSetUp_ChebyHIP(KSP ksp) {
+  PetscErrorCode ierr = KSPDefaultGetWork(ksp, 3);CHKERRQ(ierr);
+  const VecKrylovFusedOps *F = vec_fused_ops(ksp->vec_sol ? ksp->vec_sol : ksp->work[0]);   /* the vectors the solve will run on */
+  if (!F || !F->cheby_step) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s needs vectors whose type offers the fused Chebyshev step (\"VecKrylovFusedOps_C\"); use -ksp_type chebychev on these vectors", KSPCHEBYCHEVHIPMI355X);
+  return 0;
+}
+static PetscErrorCode KSPSetFromOptions_ChebyHIP(KSP ksp) {
+  PetscReal v[2]; int count;
+  PetscErrorCode ierr = option_reals(ksp, "-ksp_chebychev_eigenvalues", v, &count);CHKERRQ(ierr);
+  if (count == 1) SETERRQ(HipObjComm(ksp), PETSC_ERR_ARG_INCOMP, "-ksp_chebychev_eigenvalues: must specify 2 parameters, min and max eigenvalues");
+  if (count == 2) { ierr = KSPChebychevSetEigenvalues_ChebyHIP(ksp, v[1], v[0]);CHKERRQ(ierr); }
+  return 0;
+}
+static PetscErrorCode KSPDestroy_ChebyHIP(KSP ksp) {
+  KSP_ChebyHIP *ch = (KSP_ChebyHIP *)ksp->data;
+  PetscErrorCode ierr;
+  if (!ch) return 0;
+  ierr = VecDestroy(&ch->dinv);CHKERRQ(ierr);
+  HipFree(ch); ksp->data = NULL;
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPChebychevSetEigenvalues_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
+  return 0;
+}
+
+static PetscErrorCode KSPSolve_ChebyHIP(KSP ksp) {
+  PetscErrorCode ierr;
+  KSP_ChebyHIP *ch = (KSP_ChebyHIP *)ksp->data;
+  const KSPNormType nt = ksp->normtype;
+  Vec x = ksp->vec_sol, rhs = ksp->vec_rhs, r = ksp->work[2];
+  Vec p[3] = {x, ksp->work[0], ksp->work[1]};
+  const VecKrylovFusedOps *F = vec_fused_ops(x);
+  HipPCKind pck = PCKIND_GENERAL;
+  Vec d = NULL;
+  Mat A;
+  PetscScalar c[3], scale, mu, omegaprod, omega, Gamma = 1.0, zz = 0.0, rr = 0.0;
+  PetscReal rn = 0.0;
+  PetscInt km1 = 0, k = 1, kp1 = 2, i;
+  PetscBool done;
+
+  if (!F || !F->cheby_step) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s needs vectors whose type offers the fused Chebyshev step; use -ksp_type chebychev on these vectors", KSPCHEBYCHEVHIPMI355X);
+  ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
+  if (!has_null_space(ksp)) { ierr = pc_diagonal_form(ksp, x, &ch->dinv, &pck);CHKERRQ(ierr); if (pck == PCKIND_DIAGONAL) d = ch->dinv; }
+  ksp->its = 0;
+  scale = 2.0 / (ch->emax + ch->emin);
+  mu = 1.0 / (1.0 - scale * ch->emin);
+  omegaprod = 2.0 / (1.0 - scale * ch->emin);
+  c[km1] = 1.0; c[k] = mu;
+  ierr = start_residual(ksp, A, x, rhs, r);CHKERRQ(ierr);
+  ierr = KSP_PCApply(ksp, r, p[k]);CHKERRQ(ierr);
+  ierr = VecAYPX(p[k], scale, x);CHKERRQ(ierr);                                         /* p[k] = x + scale B r */
+  for (i = 0; i < ksp->max_it; i++) {
+    ksp->its++;
+    c[kp1] = 2.0 * mu * c[k] - c[km1];
+    omega = omegaprod * c[k] / c[kp1];
+    ierr = KSP_MatMult(ksp, A, p[k], r);CHKERRQ(ierr);
+    if (pck != PCKIND_GENERAL) {
+      /* residual, B, the norm's sums and p[kp1] in one sweep.  p[kp1] is a work vector (the iterate the test sees is p[k]), so a
+       * solve that stops at this checkpoint has lost nothing; r itself is not stored, nobody reads it */
+      const PetscBool sums = (PetscBool)(nt != KSP_NORM_NONE);
+      ierr = F->cheby_step(p[kp1], NULL, r, rhs, d, p[km1], p[k], omega * Gamma * scale, 1.0 - omega, omega, sums ? &zz : NULL, sums ? &rr : NULL, &done);CHKERRQ(ierr);
+      if (!done) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "the fused Chebyshev step refused these vectors; use -ksp_type chebychev");
+      if (sums) {
+        rn = PetscSqrtReal(nt == KSP_NORM_UNPRECONDITIONED ? rr : zz);                  /* the square is reduced, then rooted (pvec2.c:62-64) */
+        ksp->vec_sol = p[k];
+        ierr = report(ksp, i, rn);CHKERRQ(ierr);
+        ierr = KSPTestConvergence(ksp, i, rn);CHKERRQ(ierr);
+        if (ksp->reason) break;
+      }
+    } else {
+      ierr = VecAYPX(r, -1.0, rhs);CHKERRQ(ierr);
+      ierr = KSP_PCApply(ksp, r, p[kp1]);CHKERRQ(ierr);
+      if (nt != KSP_NORM_NONE) {
+        ierr = VecNorm(nt == KSP_NORM_UNPRECONDITIONED ? r : p[kp1], NORM_2, &rn);CHKERRQ(ierr);
+        ksp->vec_sol = p[k];
+        ierr = report(ksp, i, rn);CHKERRQ(ierr);
+        ierr = KSPTestConvergence(ksp, i, rn);CHKERRQ(ierr);
+        if (ksp->reason) break;
+      }
+      /* p[kp1] holds B r as KSP_PCApply left it: the update alone, in place */
+      ierr = F->cheby_step(p[kp1], NULL, p[kp1], NULL, NULL, p[km1], p[k], omega * Gamma * scale, 1.0 - omega, omega, NULL, NULL, &done);CHKERRQ(ierr);
+      if (!done) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "the fused Chebyshev step refused these vectors; use -ksp_type chebychev");
+    }
+    { const PetscInt was = km1; km1 = k; k = kp1; kp1 = was; }
+  }
+  if (!ksp->reason) {
+    if (nt != KSP_NORM_NONE) {
+      ierr = KSP_MatMult(ksp, A, p[k], r);CHKERRQ(ierr);
+      ierr = VecAYPX(r, -1.0, rhs);CHKERRQ(ierr);
+      if (nt == KSP_NORM_UNPRECONDITIONED) { ierr = VecNorm(r, NORM_2, &rn);CHKERRQ(ierr); }
+      else { ierr = KSP_PCApply(ksp, r, p[kp1]);CHKERRQ(ierr); ierr = VecNorm(p[kp1], NORM_2, &rn);CHKERRQ(ierr); }
+      ksp->vec_sol = p[k];
+      ierr = report(ksp, ksp->its, rn);CHKERRQ(ierr);
+    }
+    ierr = stationary_out_of_iterations(ksp, rn);CHKERRQ(ierr);
+  }
+  ksp->vec_sol = x;
+  if (p[k] != x) { ierr = VecCopy(p[k], x);CHKERRQ(ierr); }
+  return 0;
+}
+
+PetscErrorCode KSPCreate_ChebychevHIPMI355X(KSP ksp) {
+  KSP_ChebyHIP *ch;
+  PetscErrorCode ierr = PetscMalloc(sizeof(*ch), &ch);CHKERRQ(ierr);
+  ch->emin = 1.0e-2; ch->emax = 1.0e+2; ch->dinv = NULL;                                 /* KSPCreate_Chebychev's defaults */
+  ksp->data = ch;
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_LEFT, 1);CHKERRQ(ierr);
+  ksp->ops->setup = KSPSetUp_ChebyHIP; ksp->ops->solve = KSPSolve_ChebyHIP; ksp->ops->setfromoptions = KSPSetFromOptions_ChebyHIP; ksp->ops->destroy = KSPDestroy_ChebyHIP;
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPChebychevSetEigenvalues_C", "KSPChebychevSetEigenvalues_ChebyHIP", (PetscVoidFunction)KSPChebychevSetEigenvalues_ChebyHIP);CHKERRQ(ierr);
+  return 0;
+}
+
+typedef struct { PetscReal scale; Vec dinv; } KSP_RichHIP;
+
+static PetscErrorCode KSPRichardsonSetScale_RichHIP(KSP ksp, PetscReal scale) { ((KSP_RichHIP *)ksp->data)->scale = scale; return 0; }
+static PetscErrorCode KSPSetUp_RichHIP(KSP ksp) { return KSPDefaultGetWork(ksp, 2); }
+static PetscErrorCode KSPSetFromOptions_RichHIP(KSP ksp) {
+  PetscReal v[2]; int count;
+  PetscErrorCode ierr = option_reals(ksp, "-ksp_richardson_scale", v, &count);CHKERRQ(ierr);
+  if (count) ((KSP_RichHIP *)ksp->data)->scale = v[0];
+  return 0;
+}
+static PetscErrorCode KSPDestroy_RichHIP(KSP ksp) {
+  KSP_RichHIP *ri = (KSP_RichHIP *)ksp->data;
+  PetscErrorCode ierr;
+  if (!ri) return 0;
+  ierr = VecDestroy(&ri->dinv);CHKERRQ(ierr);
+  HipFree(ri); ksp->data = NULL;
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPRichardsonSetScale_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
+  return 0;
+}
+
+static PetscErrorCode KSPSolve_RichHIP(KSP ksp) {
+  PetscErrorCode ierr;
+  KSP_RichHIP *ri = (KSP_RichHIP *)ksp->data;
+  const KSPNormType nt = ksp->normtype;
+  Vec x = ksp->vec_sol, rhs = ksp->vec_rhs, r = ksp->work[0], z = ksp->work[1];
+  const VecKrylovFusedOps *F = vec_fused_ops(x);
+  HipPCKind pck = PCKIND_GENERAL;
+  Vec d = NULL;
+  Mat A;
+  PetscReal rn = 0.0;
+  PetscBool product_only = PETSC_FALSE;   /* r holds A x, not yet rhs - A x: the sweep of the coming iteration forms the residual itself */
+  PetscInt i;
+
+  ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
+  if (nt == KSP_NORM_NONE && F && F->rich_step && !has_null_space(ksp)) { ierr = pc_diagonal_form(ksp, x, &ri->dinv, &pck);CHKERRQ(ierr); if (pck == PCKIND_DIAGONAL) d = ri->dinv; }
+  ierr = start_residual(ksp, A, x, rhs, r);CHKERRQ(ierr);
+  ksp->its = 0;
+  for (i = 0; i < ksp->max_it; i++) {
+    PetscBool done = PETSC_FALSE;
+    if (nt == KSP_NORM_UNPRECONDITIONED) {
+      ierr = VecNorm(r, NORM_2, &rn);CHKERRQ(ierr);
+      ierr = report(ksp, i, rn);CHKERRQ(ierr);
+      ierr = KSPTestConvergence(ksp, i, rn);CHKERRQ(ierr);
+      if (ksp->reason) break;
+    }
+    if (product_only) {                                                                  /* r = rhs - r, z = B r, x += scale z in one sweep */
+      ierr = F->rich_step(x, NULL, NULL, r, rhs, d, ri->scale, &done);CHKERRQ(ierr);
+      if (!done) { ierr = VecAYPX(r, -1.0, rhs);CHKERRQ(ierr); }
+    }
+    if (!done) {
+      ierr = KSP_PCApply(ksp, r, z);CHKERRQ(ierr);
+      if (nt == KSP_NORM_PRECONDITIONED) {
+        ierr = VecNorm(z, NORM_2, &rn);CHKERRQ(ierr);
+        ierr = report(ksp, i, rn);CHKERRQ(ierr);
+        ierr = KSPTestConvergence(ksp, i, rn);CHKERRQ(ierr);
+        if (ksp->reason) break;
+      }
+      ierr = VecAXPY(x, ri->scale, z);CHKERRQ(ierr);
+    }
+    ksp->its++;
+    product_only = PETSC_FALSE;
+    if (i + 1 < ksp->max_it || nt != KSP_NORM_NONE) {
+      ierr = KSP_MatMult(ksp, A, x, r);CHKERRQ(ierr);
+      if (pck != PCKIND_GENERAL) product_only = PETSC_TRUE;                              /* (KSP_NORM_NONE: another iteration follows) */
+      else { ierr = VecAYPX(r, -1.0, rhs);CHKERRQ(ierr); }
+    }
+  }
+  if (!ksp->reason) {
+    if (nt != KSP_NORM_NONE) {
+      if (nt == KSP_NORM_UNPRECONDITIONED) { ierr = VecNorm(r, NORM_2, &rn);CHKERRQ(ierr); }
+      else { ierr = KSP_PCApply(ksp, r, z);CHKERRQ(ierr); ierr = VecNorm(z, NORM_2, &rn);CHKERRQ(ierr); }
+      ierr = report(ksp, ksp->its, rn);CHKERRQ(ierr);
+    }
+    ierr = stationary_out_of_iterations(ksp, rn);CHKERRQ(ierr);
+  }
+  return 0;
+}
+
+PetscErrorCode KSPCreate_RichardsonHIPMI355X(KSP ksp) {
+  KSP_RichHIP *ri;
+  PetscErrorCode ierr = PetscMalloc(sizeof(*ri), &ri);CHKERRQ(ierr);
+  ri->scale = 1.0; ri->dinv = NULL;                                                      /* KSPCreate_Richardson's default */
+  ksp->data = ri;
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_LEFT, 1);CHKERRQ(ierr);
+  ksp->ops->setup = KSPSetUp_RichHIP; ksp->ops->solve = KSPSolve_RichHIP; ksp->ops->setfromoptions = KSPSetFromOptions_RichHIP; ksp->ops->destroy = KSPDestroy_RichHIP;
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPRichardsonSetScale_C", "KSPRichardsonSetScale_RichHIP", (PetscVoidFunction)KSPRichardsonSetScale_RichHIP);CHKERRQ(ierr);
   return 0;
 }

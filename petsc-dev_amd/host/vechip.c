@@ -1045,6 +1045,60 @@ PetscErrorCode VecBCGSUpdate_HIPMI355X(Vec x, Vec r, Vec p, Vec s_, Vec t, Vec r
   return 0;
 }
 
+/* Fused forms for KSPSolve_Chebychev / KSPSolve_Richardson (include/petsckrylovfused.h cheby_step, rich_step): the residual behind
+ * w = A p, a diagonal preconditioner and the update in one sweep; *done = PETSC_FALSE and nothing touched unless every operand is a
+ * HIPMI355X vector of the same local size and the written vector overlaps nothing it may not. */
+PetscErrorCode VecChebyStep_HIPMI355X(Vec pn, Vec r, Vec w, Vec b, Vec d, Vec pm, Vec pk, PetscScalar s, PetscScalar a, PetscScalar c, PetscScalar *zz, PetscScalar *rr, PetscBool *done) {
+  PetscErrorCode ierr; const PetscScalar *dw, *db = NULL, *dd = NULL, *dpm, *dpk; PetscScalar *dr = NULL, *dpn; double *out = NULL; PetscScalar res[2]; DEVCTX;
+  const int sums = zz || rr;
+  *done = PETSC_FALSE;
+  if (!pn || !w || !pm || !pk || !all_hip_same_size(pn, w, pm, pk, b, d) || (r && (!is_hip(r) || r->map->n != pn->map->n))) return 0;
+  if (!b && (d || r || sums)) return 0;                                           /* w given as the preconditioned residual: nothing else to form */
+  if (pn == b || pn == d || pn == pm || pn == pk || pn == r || (pn == w && b)) return 0;
+  if (r && (r == b || r == d || r == pm || r == pk)) return 0;
+  ierr = VecHIPGetRead(w, &dw);CHKERRQ(ierr);
+  if (b) { ierr = VecHIPGetRead(b, &db);CHKERRQ(ierr); }
+  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
+  ierr = VecHIPGetRead(pm, &dpm);CHKERRQ(ierr);
+  ierr = VecHIPGetRead(pk, &dpk);CHKERRQ(ierr);
+  if (r) { ierr = VecHIPGetReadWrite(r, &dr);CHKERRQ(ierr); }
+  if (pn == w) { ierr = VecHIPGetReadWrite(pn, &dpn);CHKERRQ(ierr); }
+  else { ierr = VecHIPGetWrite(pn, &dpn);CHKERRQ(ierr); }
+  if (sums) { ierr = reduce_target(pn, dc, &out);CHKERRQ(ierr); }
+  CHKHIP(mi355x_vec_cheby_step(dc->h, N_(pn), s, a, c, dw, db, dd, dpm, dpk, dr, dpn, sums, out));
+  VecHIPRestoreWrite(pn); HipStateIncrease(pn);
+  if (r) { VecHIPRestoreWrite(r); HipStateIncrease(r); }
+  if (sums) {
+    ierr = reduce_finish(pn, dc, 2, 0, res);CHKERRQ(ierr);
+    if (zz) *zz = res[0];
+    if (rr) *rr = res[1];
+  }
+  ierr = PetscLogFlops((b ? 1.0 : 0.0) * pn->map->n + (d ? 1.0 : 0.0) * pn->map->n + 5.0 * pn->map->n + (sums ? 4.0 * pn->map->n : 0.0));CHKERRQ(ierr);
+  *done = PETSC_TRUE;
+  return 0;
+}
+PetscErrorCode VecRichStep_HIPMI355X(Vec x, Vec r, Vec z, Vec w, Vec b, Vec d, PetscScalar scale, PetscBool *done) {
+  PetscErrorCode ierr; const PetscScalar *dw, *db, *dd = NULL; PetscScalar *dr = NULL, *dz = NULL, *dx; DEVCTX;
+  *done = PETSC_FALSE;
+  if (!x || !w || !b || !all_hip_same_size(x, w, b, d, r, z)) return 0;
+  if (x == w || x == b || x == d || x == r || x == z) return 0;
+  if (r && (r == b || r == d || r == z)) return 0;
+  if (z && (z == w || z == b || z == d)) return 0;
+  ierr = VecHIPGetRead(w, &dw);CHKERRQ(ierr);
+  ierr = VecHIPGetRead(b, &db);CHKERRQ(ierr);
+  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
+  if (r) { ierr = VecHIPGetReadWrite(r, &dr);CHKERRQ(ierr); }
+  if (z) { ierr = VecHIPGetWrite(z, &dz);CHKERRQ(ierr); }
+  ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_rich_step(dc->h, N_(x), scale, dw, db, dd, dr, dz, dx));
+  VecHIPRestoreWrite(x); HipStateIncrease(x);
+  if (r) { VecHIPRestoreWrite(r); HipStateIncrease(r); }
+  if (z) { VecHIPRestoreWrite(z); HipStateIncrease(z); }
+  ierr = PetscLogFlops((d ? 4.0 : 3.0) * x->map->n);CHKERRQ(ierr);
+  *done = PETSC_TRUE;
+  return 0;
+}
+
 /* ---- split-phase reductions (src/vec/vec/utils/comb.c:402-721: VecDotBegin/End, VecNormBegin/End,
  * PetscCommSplitReductionBegin).  Begin launches the device reduction into the next slot of the device scratch (no
  * host involvement); PetscCommSplitReductionBegin starts what brings the queued results to the host -- one RCCL
@@ -1267,7 +1321,7 @@ static const VecKrylovFusedOps *VecKrylovFusedOps_HIP(void) {
   static const VecKrylovFusedOps ops = {
     VecCGUpdate_HIPMI355X, VecCGUpdateCheck_HIPMI355X, VecTDotBegin_HIPMI355X, VecCGUpdateDevBegin_HIPMI355X, VecCGUpdateDevEnd_HIPMI355X,
     VecAYPXDev_HIPMI355X, VecPMultDot_HIPMI355X, VecPMultDotNorm2_HIPMI355X, VecBCGSUpdate_HIPMI355X, VecGMRESOrthogNormalize_HIPMI355X,
-    VecCGUpdateDevBeginNoX_HIPMI355X, VecAYPXDevX_HIPMI355X};
+    VecCGUpdateDevBeginNoX_HIPMI355X, VecAYPXDevX_HIPMI355X, VecChebyStep_HIPMI355X, VecRichStep_HIPMI355X};
   return &ops;
 }
 /* "VecSplitReductionOps_C": VecDotBegin/End, VecNormBegin/End, PetscCommSplitReductionBegin (comb.c:402-721) with the

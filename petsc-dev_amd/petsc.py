@@ -67,6 +67,8 @@ _SIG = {
     "KSPCreate": [vp, P(vp)], "KSPSetType": [vp, C.c_char_p], "KSPSetOperators": [vp, vp, vp, i32], "KSPGetPC": [vp, P(vp)],
     "KSPSetTolerances": [vp, dbl, dbl, dbl, i32], "KSPSetNormType": [vp, i32], "KSPSetPCSide": [vp, i32], "KSPSetInitialGuessNonzero": [vp, i32], "KSPSetOptionsPrefix": [vp, C.c_char_p],
     "KSPSetFromOptions": [vp], "KSPGMRESSetRestart": [vp, i32], "KSPGMRESSetCGSRefinementType": [vp, i32],
+    "KSPChebychevSetEigenvalues": [vp, dbl, dbl], "KSPRichardsonSetScale": [vp, dbl], "KSPMonitorSet": [vp, vp, vp, vp],
+    "PCApplyRichardson": [vp, vp, vp, vp, dbl, dbl, dbl, i32, i32, P(i32), P(i32)], "PCApplyRichardsonExists": [vp, P(i32)],
     "KSPSetUp": [vp], "KSPSolve": [vp, vp, vp], "KSPGetIterationNumber": [vp, P(i32)], "KSPGetResidualNorm": [vp, P(dbl)],
     "KSPGetConvergedReason": [vp, P(i32)], "KSPSetResidualHistory": [vp, vp, i32, i32],
     "KSPGetResidualHistory": [vp, P(vp), P(i32)], "KSPDestroy": [P(vp)],
@@ -83,6 +85,7 @@ NORM_1, NORM_2, NORM_FROBENIUS, NORM_INFINITY, NORM_1_AND_2 = 0, 1, 2, 3, 4
 MAT_FINAL_ASSEMBLY, MAT_FLUSH_ASSEMBLY = 0, 1
 PETSC_DECIDE, PETSC_DEFAULT = -1, -2
 DIFFERENT_NONZERO_PATTERN, SUBSET_NONZERO_PATTERN, SAME_NONZERO_PATTERN = 0, 1, 2
+KSP_NORM_NONE, KSP_NORM_PRECONDITIONED, KSP_NORM_UNPRECONDITIONED, KSP_NORM_NATURAL = 0, 1, 2, 3   # KSPNormType (petscmini.h)
 MAT_KEEP_NONZERO_PATTERN = 9          # MatOption (petscmini.h)
 # MatSORType (petscmini.h)
 SOR_FORWARD_SWEEP, SOR_BACKWARD_SWEEP, SOR_SYMMETRIC_SWEEP = 1, 2, 3
@@ -413,6 +416,22 @@ class KSP:
 
     def set_from_options(self):
         lib().KSPSetFromOptions(self.h)
+
+    def set_norm_type(self, norm):
+        """KSPSetNormType: "none", "preconditioned", "unpreconditioned", "natural" or the KSPNormType number"""
+        names = {"none": KSP_NORM_NONE, "preconditioned": KSP_NORM_PRECONDITIONED, "unpreconditioned": KSP_NORM_UNPRECONDITIONED, "natural": KSP_NORM_NATURAL}
+        lib().KSPSetNormType(self.h, names[norm] if isinstance(norm, str) else int(norm))
+
+    def set_initial_guess_nonzero(self, flag=True):
+        lib().KSPSetInitialGuessNonzero(self.h, 1 if flag else 0)
+
+    def set_chebychev_eigenvalues(self, emax, emin):
+        """KSPChebychevSetEigenvalues: bounds of the preconditioned operator's spectrum (the chebychev types; ignored by any other)"""
+        lib().KSPChebychevSetEigenvalues(self.h, float(emax), float(emin))
+
+    def set_richardson_scale(self, scale):
+        """KSPRichardsonSetScale: the damping factor (the richardson types; ignored by any other)"""
+        lib().KSPRichardsonSetScale(self.h, float(scale))
 
     def record_history(self, n=20000):
         self._hist = np.zeros(n)
