@@ -453,6 +453,32 @@ int mi355x_sor_sweep(mi355x_handle_t h, mi355x_sor_plan_t plan, int kind, const 
 int mi355x_sor_apply(mi355x_handle_t h, mi355x_sor_plan_t plan, const int *ai, const int *aj, const double *aa, const double *idiag,
                      const double *mdiag, double omega, int flag, int its, const double *b, double *t, double *x);
 
+/* ---- C = A B for CSR matrices: symbolic pass on the host, numeric pass on the device (csrc/spgemm.hip) ----
+ * MatMatMult_SeqAIJ_SeqAIJ  src/mat/impls/aij/seq/matmatmult.c.  A is m x k, B is k x n, every row's columns ascending.  Row i of C
+ * stores the union of the column lists of the rows B[aj[t], :], t over row i of A, ascending, also where a value comes out zero.
+ * Every c_ij starts at +0.0; the stored entries t of A's row i are taken in storage order and every stored b = B[aj[t], j] gives
+ * c_ij = c_ij + (a_it * b), product and sum rounded separately; nothing is skipped (a stored 0.0 against an Inf is a NaN).  C carries
+ * the sequential loop's bits whatever the lane width and launch shape.
+ *   _symbolic_host  host arrays, no device call; called twice: with cj == NULL it fills ci[m + 1], with cj it fills the sorted columns
+ *             at the offsets of ci.  Rows are split over nthreads host threads (<= 0: one below 200 000 entries of A, else
+ *             mi355x_host_threads(16)); the result does not depend on the count.
+ *   _geometry     the LDS slots a row of C has before it is processed in column windows, and the workgroup size
+ *   _plan_create  once per pattern triple, from HOST arrays: checks them (row pointers ascending from 0, columns strictly ascending
+ *             and inside their matrix: hipErrorInvalidValue), picks the lanes per row -- the smallest of 8, 16, 32, 64 that is >= the
+ *             mean length of the B rows the product visits -- and uploads the list of C's non-empty rows, the windowed ones last
+ *   _plan_info    lanes per row, rows of C longer than the LDS budget, bytes of device memory the plan holds
+ *   _numeric      DEVICE arrays of the patterns the plan was made from: writes every one of the ci[m] slots of ca and nothing else;
+ *             does not wait for the device */
+typedef struct mi355x_spgemm_plan_s *mi355x_spgemm_plan_t;
+int mi355x_spgemm_symbolic_host(int m, int n, const int *ai, const int *aj, const int *bi, const int *bj, int *ci, int *cj, int nthreads);
+int mi355x_spgemm_geometry(int *lds_entries_per_row_group, int *block);
+int mi355x_spgemm_plan_create(mi355x_handle_t h, int m, int k, int n, const int *ai, const int *aj, const int *bi, const int *bj, const int *ci,
+                              const int *cj, mi355x_spgemm_plan_t *plan);
+int mi355x_spgemm_plan_destroy(mi355x_spgemm_plan_t plan);
+int mi355x_spgemm_plan_info(mi355x_spgemm_plan_t plan, int *lanes, int *nwindowed_rows, size_t *workspace_bytes);
+int mi355x_spgemm_numeric(mi355x_handle_t h, mi355x_spgemm_plan_t plan, const int *ai, const int *aj, const double *aa, const int *bi,
+                          const int *bj, const double *ba, const int *ci, const int *cj, double *ca);
+
 /* The same two solves WITHOUT a kernel boundary per level: one launch per triangular solve, rows sorted by level and
  * stored as sliced ELL (one wavefront per 64 rows), dependencies handed over through the solution values themselves
  * (a sentinel bit pattern means "not computed yet"; write-through stores, polling loads).  Same one-lane-per-row,

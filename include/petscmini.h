@@ -60,6 +60,7 @@ typedef enum { SCATTER_FORWARD = 0, SCATTER_REVERSE = 1 } ScatterMode;          
 typedef enum { NORM_1 = 0, NORM_2 = 1, NORM_FROBENIUS = 2, NORM_INFINITY = 3, NORM_1_AND_2 = 4 } NormType; /* petscvec.h:155 */
 typedef enum { MAT_FLUSH_ASSEMBLY = 1, MAT_FINAL_ASSEMBLY = 0 } MatAssemblyType;               /* petscmat.h:347 */
 typedef enum { MAT_DO_NOT_COPY_VALUES, MAT_COPY_VALUES, MAT_SHARE_NONZERO_PATTERN } MatDuplicateOption;   /* petscmat.h:440 */
+typedef enum { MAT_INITIAL_MATRIX, MAT_REUSE_MATRIX } MatReuse;   /* petscmat.h: a product builds its result, or fills the one an earlier call built */
 typedef enum { DIFFERENT_NONZERO_PATTERN, SUBSET_NONZERO_PATTERN, SAME_NONZERO_PATTERN, SAME_PRECONDITIONER } MatStructure;
 /* MatSetOption (include/petscmat.h, the list of 3.3 in its order).  The HIPMI355X types act on MAT_KEEP_NONZERO_PATTERN (MatZeroRows);
  * the others are accepted and have no effect here */
@@ -294,6 +295,16 @@ PetscErrorCode MatSetOption(Mat A, MatOption op, PetscBool flg);
  * MatSOR_MPIAIJ mpiaij.c: local sweeps only, its outer steps of lits local sweeps each).  b and x are different vectors, its, lits > 0 */
 PetscErrorCode MatSOR(Mat A, Vec b, PetscReal omega, MatSORType flag, PetscReal fshift, PetscInt its, PetscInt lits, Vec x);
 PetscErrorCode MatSetOptionsPrefix(Mat A, const char prefix[]);
+/* sparse matrix products (matrix.c MatMatMult, MatTranspose, MatPtAP; MatMatMult_SeqAIJ_SeqAIJ matmatmult.c, MatPtAP_SeqAIJ_SeqAIJ
+ * matptap.c): dispatch on A's type; operands of different types PETSC_ERR_SUP, inner dimensions that do not match PETSC_ERR_ARG_SIZ.
+ * MAT_INITIAL_MATRIX builds *C (symbolic and numeric phase); MAT_REUSE_MATRIX fills the *C an earlier call built from the same
+ * operands with unchanged patterns (else PETSC_ERR_ARG_WRONG).  fill, the expected nnz(C) / (nnz(A) + nnz(B)), is a hint the
+ * HIPMI355X types do not need (PETSC_DEFAULT).  MatPtAP is MatMatMult(MatTranspose(P), MatMatMult(A, P)) with exactly those bits. */
+PetscErrorCode MatMatMult(Mat A, Mat B, MatReuse scall, PetscReal fill, Mat *C);           /* C = A B */
+PetscErrorCode MatMatMultSymbolic(Mat A, Mat B, PetscReal fill, Mat *C);                   /* C's pattern, values zero */
+PetscErrorCode MatMatMultNumeric(Mat A, Mat B, Mat C);                                     /* the values of a C from MatMatMultSymbolic / MatMatMult */
+PetscErrorCode MatTranspose(Mat A, MatReuse reuse, Mat *B);                                /* B = A^T, out of place */
+PetscErrorCode MatPtAP(Mat A, Mat P, MatReuse scall, PetscReal fill, Mat *C);              /* C = P^T A P */
 /* matrix.c:3937-4010 (MatGetFactor looks "MatGetFactor_<package>_C" up on the operator), 2766-3144 (symbolic / numeric), 3196 (MatSolve) */
 PetscErrorCode MatFactorInfoInitialize(MatFactorInfo *info);
 PetscErrorCode MatGetFactor(Mat mat, const MatSolverPackage type, MatFactorType ftype, Mat *f);

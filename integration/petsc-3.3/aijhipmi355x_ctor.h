@@ -81,6 +81,7 @@ static PetscErrorCode MatDestroy_SeqAIJHIPMI355X(Mat A) {   /* MatDestroy_SeqAIJ
   PetscFunctionBegin;
   if (SD(A)) {
     Mat_SeqAIJHIP *d = SD(A);
+    product_free(A);
     device_free(A);
     if (d->time_ev) { for (PetscInt k = 0; k < 2 * d->time_cap; k++) mi355x_event_destroy(d->time_ev[k]); HipFree(d->time_ev); }
     HipFree(d->view.inode_size);
@@ -121,6 +122,11 @@ PetscErrorCode MatCreate_SeqAIJHIPMI355X(Mat B) {
   B->ops->zerorowscolumns  = MatZeroRowsColumns_SeqAIJHIP; /* always keeps the pattern */
   B->ops->sor              = MatSOR_SeqAIJHIP;             /* the point sweeps on the device copy (never MatSOR_SeqAIJ_Inode); the tree's own PCSOR calls it */
   /* ops->setoption stays MatSetOption_SeqAIJ: MAT_KEEP_NONZERO_PATTERN is the parent's keepnonzeropattern, read by keep_nonzero_pattern() */
+  B->ops->matmult          = MatMatMult_SeqAIJHIP;          /* slots 89-91, 15 and 92 (matimpl.h): C = A B, A^T and P^T A P of two matrices of this type, */
+  B->ops->matmultsymbolic  = MatMatMultSymbolic_SeqAIJHIP;  /* numeric phase on the device, pattern reuse; MatMatMult looks a pair of DIFFERENT types up by */
+  B->ops->matmultnumeric   = MatMatMultNumeric_SeqAIJHIP;   /* name and finds the parent's "MatMatMult_seqaij_seqaij_C" no longer -- such a call is PETSC_ERR_SUP */
+  B->ops->transpose        = MatTranspose_SeqAIJHIP;
+  B->ops->ptap             = MatPtAP_SeqAIJHIP;
   B->ops->setvaluesbatch   = MatSetValuesBatch_SeqAIJHIP;
   B->ops->setfromoptions   = MatSetFromOptions_SeqAIJHIP;  /* the type's -mat_hipmi355x_* options under the matrix's prefix (slot 76); MatSetFromOptions_SeqAIJ has none of its own in 3.3 */
   /* ops->duplicate stays MatDuplicate_SeqAIJ (aij.c:3964): it creates the new matrix with MatSetType(type_name), i.e. through THIS

@@ -157,6 +157,12 @@ KERNEL_API = {
     "mi355x_sor_idiag": [vp, vp, vp, dbl, dbl, vp, vp],
     "mi355x_sor_sweep": [vp, vp, i32, vp, vp, vp, vp, vp, dbl, vp, vp, vp],
     "mi355x_sor_apply": [vp, vp, vp, vp, vp, vp, vp, dbl, i32, i32, vp, vp, vp],
+    "mi355x_spgemm_symbolic_host": [i32, i32, vp, vp, vp, vp, vp, vp, i32],
+    "mi355x_spgemm_geometry": [pi32, pi32],
+    "mi355x_spgemm_plan_create": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp)],
+    "mi355x_spgemm_plan_destroy": [vp],
+    "mi355x_spgemm_plan_info": [vp, pi32, pi32, C.POINTER(sz)],
+    "mi355x_spgemm_numeric": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "mi355x_pack": [vp, sz, vp, vp, vp],
     "mi355x_unpack_insert": [vp, sz, vp, vp, vp],
     "mi355x_unpack_add": [vp, sz, vp, vp, vp],

@@ -329,6 +329,68 @@ PetscErrorCode MatSOR(Mat A, Vec b, PetscReal omega, MatSORType flag, PetscReal 
   return 0;
 }
 
+/* MatMatMult, MatMatMultSymbolic / Numeric, MatTranspose, MatPtAP (matrix.c): the argument checks, then the slot of A's type.  The
+ * reference looks a product of two types up by name ("MatMatMult_<typeA>_<typeB>_C"); here the operands are of one type or the call
+ * is PETSC_ERR_SUP.  The type's slot bumps the result's state itself (the reference's numeric phases end in MatAssemblyEnd). */
+static PetscErrorCode product_pair(Mat A, Mat B, PetscInt inner_a, PetscInt inner_b) {
+  MatTypeSet(A, 1); MatTypeSet(B, 2); MatAssembled(A); MatAssembled(B);
+  if (A->factortype || B->factortype) SETERRQ(A->comm, PETSC_ERR_ARG_WRONGSTATE, "Not for factored matrix");
+  if (strcmp(A->type_name, B->type_name)) SETERRQ(A->comm, PETSC_ERR_SUP, "Product of Mat types %s and %s", A->type_name, B->type_name);
+  if (inner_a != inner_b) SETERRQ(A->comm, PETSC_ERR_ARG_SIZ, "Matrix dimensions are incompatible, %d != %d", inner_a, inner_b);
+  return 0;
+}
+PetscErrorCode MatMatMult(Mat A, Mat B, MatReuse scall, PetscReal fill, Mat *C) {
+  PetscErrorCode ierr;
+  MatValid(A, 1); MatValid(B, 2);
+  if (!C) SETERRQ(A->comm, PETSC_ERR_ARG_NULL, "Null Pointer: Parameter # 5");
+  ierr = product_pair(A, B, A->cmap->N, B->rmap->N);CHKERRQ(ierr);
+  if (scall == MAT_REUSE_MATRIX && !*C) SETERRQ(A->comm, PETSC_ERR_ARG_NULL, "MAT_REUSE_MATRIX needs the matrix of an earlier call");
+  if (fill != (PetscReal)PETSC_DEFAULT && fill < 1.0) SETERRQ(A->comm, PETSC_ERR_ARG_SIZ, "Expected fill=%g must be >= 1.0", (double)fill);
+  if (!A->ops->matmult) SETERRQ(A->comm, PETSC_ERR_SUP, "MatMatMult for Mat type %s", A->type_name);
+  ierr = (*A->ops->matmult)(A, B, scall, fill, C);CHKERRQ(ierr);
+  return 0;
+}
+PetscErrorCode MatMatMultSymbolic(Mat A, Mat B, PetscReal fill, Mat *C) {
+  PetscErrorCode ierr;
+  MatValid(A, 1); MatValid(B, 2);
+  if (!C) SETERRQ(A->comm, PETSC_ERR_ARG_NULL, "Null Pointer: Parameter # 4");
+  ierr = product_pair(A, B, A->cmap->N, B->rmap->N);CHKERRQ(ierr);
+  if (!A->ops->matmultsymbolic) SETERRQ(A->comm, PETSC_ERR_SUP, "MatMatMultSymbolic for Mat type %s", A->type_name);
+  ierr = (*A->ops->matmultsymbolic)(A, B, fill, C);CHKERRQ(ierr);
+  return 0;
+}
+PetscErrorCode MatMatMultNumeric(Mat A, Mat B, Mat C) {
+  PetscErrorCode ierr;
+  MatValid(A, 1); MatValid(B, 2); MatTypeSet(C, 3);
+  ierr = product_pair(A, B, A->cmap->N, B->rmap->N);CHKERRQ(ierr);
+  if (!A->ops->matmultnumeric) SETERRQ(A->comm, PETSC_ERR_SUP, "MatMatMultNumeric for Mat type %s", A->type_name);
+  ierr = (*A->ops->matmultnumeric)(A, B, C);CHKERRQ(ierr);
+  return 0;
+}
+PetscErrorCode MatTranspose(Mat A, MatReuse reuse, Mat *B) {   /* out of place only: *B == A (the reference's in-place form) is not offered */
+  PetscErrorCode ierr;
+  MatTypeSet(A, 1); MatAssembled(A);
+  if (A->factortype) SETERRQ(A->comm, PETSC_ERR_ARG_WRONGSTATE, "Not for factored matrix");
+  if (!B) SETERRQ(A->comm, PETSC_ERR_ARG_NULL, "Null Pointer: Parameter # 3");
+  if (reuse == MAT_REUSE_MATRIX && !*B) SETERRQ(A->comm, PETSC_ERR_ARG_NULL, "MAT_REUSE_MATRIX needs the matrix of an earlier call");
+  if (reuse == MAT_REUSE_MATRIX && *B == A) SETERRQ(A->comm, PETSC_ERR_SUP, "In-place MatTranspose");
+  if (!A->ops->transpose) SETERRQ(A->comm, PETSC_ERR_SUP, "Mat type %s", A->type_name);
+  ierr = (*A->ops->transpose)(A, reuse, B);CHKERRQ(ierr);
+  return 0;
+}
+PetscErrorCode MatPtAP(Mat A, Mat P, MatReuse scall, PetscReal fill, Mat *C) {
+  PetscErrorCode ierr;
+  MatValid(A, 1); MatValid(P, 2);
+  if (!C) SETERRQ(A->comm, PETSC_ERR_ARG_NULL, "Null Pointer: Parameter # 5");
+  ierr = product_pair(A, P, A->cmap->N, P->rmap->N);CHKERRQ(ierr);
+  if (A->rmap->N != A->cmap->N) SETERRQ(A->comm, PETSC_ERR_ARG_SIZ, "Matrix A must be square, %d != %d", A->rmap->N, A->cmap->N);
+  if (scall == MAT_REUSE_MATRIX && !*C) SETERRQ(A->comm, PETSC_ERR_ARG_NULL, "MAT_REUSE_MATRIX needs the matrix of an earlier call");
+  if (fill != (PetscReal)PETSC_DEFAULT && fill < 1.0) SETERRQ(A->comm, PETSC_ERR_ARG_SIZ, "Expected fill=%g must be >= 1.0", (double)fill);
+  if (!A->ops->ptap) SETERRQ(A->comm, PETSC_ERR_SUP, "MatPtAP for Mat type %s", A->type_name);
+  ierr = (*A->ops->ptap)(A, P, scall, fill, C);CHKERRQ(ierr);
+  return 0;
+}
+
 /* ---- type-specific methods reached through composed functions, as in the reference (PetscTryMethod / PetscUseMethod,
  * e.g. MatSeqAIJSetPreallocation aij.c:3435, MatMPIAIJSetPreallocation mpiaij.c:4274, MatGetDiagonalBlock matrix.c) ---- */
 PetscErrorCode MatSeqAIJSetPreallocation(Mat A, PetscInt nz, const PetscInt nnz[]) {

@@ -152,6 +152,11 @@ struct _MatOps {
   PetscErrorCode (*setoption)(Mat, MatOption, PetscBool);
   PetscErrorCode (*sor)(Mat, Vec, PetscReal, MatSORType, PetscReal, PetscInt, PetscInt, Vec);   /* slot 13 */
   PetscErrorCode (*duplicate)(Mat, MatDuplicateOption, Mat *);   /* slot 34 */
+  PetscErrorCode (*transpose)(Mat, MatReuse, Mat *);             /* slot 15 */
+  PetscErrorCode (*matmult)(Mat, Mat, MatReuse, PetscReal, Mat *);   /* slot 89: C = A B */
+  PetscErrorCode (*matmultsymbolic)(Mat, Mat, PetscReal, Mat *);
+  PetscErrorCode (*matmultnumeric)(Mat, Mat, Mat);
+  PetscErrorCode (*ptap)(Mat, Mat, MatReuse, PetscReal, Mat *);      /* slot 92: C = P^T A P */
   PetscErrorCode (*setfromoptions)(Mat);                 /* slot 76 */
   PetscErrorCode (*destroy)(Mat);                        /* slot 60 */
   PetscErrorCode (*getvecs)(Mat, Vec *, Vec *);          /* slot 88 */

@@ -170,6 +170,7 @@ static PetscErrorCode hip_mat_option(Mat A, int which, PetscInt *val) {
   return PetscOptionsGetInt(NULL, hopt_name[which], val, &set);
 }
 /* -mat_hipmi355x_sor <device|host> (default device): where MatSOR runs; 0: the option is not given under this prefix */
+static PetscErrorCode product_route_option(Mat A, const char *prefix, int *route);   /* -mat_hipmi355x_product, with the products below */
 static PetscErrorCode sor_route_option(Mat A, const char *prefix, int *route) {
   PetscErrorCode ierr;
   char kind[16] = ""; PetscBool set = PETSC_FALSE;
@@ -193,7 +194,9 @@ static PetscErrorCode MatSetFromOptions_SeqAIJHIP(Mat A) {
   }
   { int route = 0;
     ierr = sor_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
-    if (route) d->sor.route = route; }
+    if (route) d->sor.route = route;
+    ierr = product_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
+    if (route) d->product_route = route; }
   return 0;
 }
 
@@ -1762,6 +1765,288 @@ PetscErrorCode MatHIPMI355XGetSORInfo(Mat A, PetscInt *levels, PetscInt *launche
   return 0;
 }
 
+/* ---------------------------------------------------------------- Sparse matrix products: MatMatMult, MatTranspose, MatPtAP
+ * C = A B (MatMatMult_SeqAIJ_SeqAIJ), B = A^T (MatTranspose_SeqAIJ) and C = P^T A P = MatMatMult(MatTranspose(P), MatMatMult(A, P)) for
+ * sequential AIJ matrices of this type, on the model of the device ILU(0): the host does the symbolic work once (MAT_INITIAL_MATRIX:
+ * the pattern of the result, its upload, the kernel plan), the device reproduces the sequential loop's arithmetic bit for bit
+ * (csrc/spgemm.hip; the transpose's values are the a = d_a[perm] gather of the derived forms), and MAT_REUSE_MATRIX on unchanged patterns
+ * launches kernels only.  The operands' device values follow the ordinary upload rule -- an operand changed on the device by MatScale,
+ * MatShift, MatAXPY is not sent again.  The result's host values are brought back with one copy, its device copy is stamped current and
+ * its derived forms go stale through device_values_changed like after every other device-side value change.
+ * -mat_hipmi355x_product <device|host> (default device; under A's prefix, else the global database, read at the symbolic phase and kept
+ * with the result): the host route is the sequential loop over host threads followed by the ordinary upload at the result's next use.
+ * A product ends in the result's own state bump (the reference's numeric phases end in MatAssemblyEnd). */
+static PetscErrorCode product_route_option(Mat A, const char *prefix, int *route) {
+  PetscErrorCode ierr;
+  char kind[16] = ""; PetscBool set = PETSC_FALSE;
+  *route = 0;
+  ierr = PetscOptionsGetString(prefix, "-mat_hipmi355x_product", kind, sizeof(kind), &set);CHKERRQ(ierr);
+  if (!set) return 0;
+  if (strcmp(kind, "device") && strcmp(kind, "host")) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "-mat_hipmi355x_product <device|host>, got %s", kind);
+  *route = strcmp(kind, "host") ? 1 : 2;
+  return 0;
+}
+static PetscErrorCode product_route(Mat A, int *route) {
+  PetscErrorCode ierr;
+  *route = SD(A)->product_route;
+  if (!*route) { ierr = product_route_option(A, NULL, route);CHKERRQ(ierr); }
+  if (!*route) *route = 1;
+  return 0;
+}
+static void product_free(Mat C) {
+  Mat_SeqAIJHIP *d = SD(C);
+  HipMatProduct *p = d ? d->prod : NULL;
+  if (!p) return;
+  if (p->plan) mi355x_spgemm_plan_destroy(p->plan);
+  HipFree(p->perm_h);
+  if (p->perm_d) mi355x_free(p->perm_d);
+  (void)MatDestroy(&p->Pt); (void)MatDestroy(&p->AP);
+  HipFree(p); d->prod = NULL;
+}
+/* operands of a product: assembled sequential AIJ matrices of this type (BAIJ has the constructor in common) */
+static PetscErrorCode product_operand(Mat X) {
+  PetscErrorCode ierr;
+  if (!X->spptr || X->ops->mult != MatMult_SeqAIJHIP) SETERRQ(HipObjComm(X), PETSC_ERR_SUP, "Matrix products of Mat type %s", HipObjTypeName(X));
+  ierr = value_op_view(X);CHKERRQ(ierr);
+  if (SA(X)->bs > 1) SETERRQ(HipObjComm(X), PETSC_ERR_SUP, "Matrix products of block matrices (%s)", HipObjTypeName(X));
+  if (!SA(X)->compact) SETERRQ(HipObjComm(X), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  return 0;
+}
+/* the device copies of the operands current; compressed rows (an off-diagonal block's form) are not the CSR the kernel reads: host route */
+static PetscErrorCode product_operands_up(Mat X, Mat Y, int *route) {
+  PetscErrorCode ierr;
+  if (*route != 1) return 0;
+  ierr = MatSeqAIJHIPUpload(X);CHKERRQ(ierr);
+  if (Y) { ierr = MatSeqAIJHIPUpload(Y);CHKERRQ(ierr); }
+  if (SD(X)->cprow || (Y && SD(Y)->cprow)) *route = 2;
+  return 0;
+}
+static void product_note(HipMatProduct *p, int k, Mat X) { p->op[k] = X; p->op_nz[k] = SA(X)->nz; p->op_gen[k] = SD(X)->pattern_gen; }
+static PetscBool product_noted(const HipMatProduct *p, int k, Mat X) {
+  return (PetscBool)(p->op[k] == (void *)X && p->op_nz[k] == SA(X)->nz && (!p->op_gen[k] || p->op_gen[k] == SD(X)->pattern_gen));
+}
+/* MAT_REUSE_MATRIX: C came from this operation on these operands, and no pattern was uploaded anew since */
+static PetscErrorCode product_reuse_check(Mat C, int kind, Mat X, Mat Y, HipMatProduct **p_) {
+  PetscErrorCode ierr;
+  HipMatProduct *p;
+  if (!C->spptr || C->ops->mult != MatMult_SeqAIJHIP || !SD(C)->prod || SD(C)->prod->kind != kind)
+    SETERRQ(HipObjComm(X), PETSC_ERR_ARG_WRONG, "MAT_REUSE_MATRIX: the matrix is not the result of this operation");
+  p = SD(C)->prod;
+  { int route = p->route; ierr = product_operands_up(X, Y, &route);CHKERRQ(ierr);
+    if (route != p->route) SETERRQ(HipObjComm(X), PETSC_ERR_ARG_WRONG, "MAT_REUSE_MATRIX: an operand changed its device form since the symbolic phase"); }
+  if (!product_noted(p, 0, X) || (Y && !product_noted(p, 1, Y)))
+    SETERRQ(HipObjComm(X), PETSC_ERR_ARG_WRONG, "MAT_REUSE_MATRIX: not the operands, or not the operand patterns, of the symbolic phase");
+  *p_ = p;
+  return 0;
+}
+/* the result as a matrix of the operands' type with the given pattern and zero values; the type's options go along (as MatDuplicate) */
+static PetscErrorCode product_result(Mat A, PetscInt m, PetscInt n, const PetscInt *ci, const PetscInt *cj, int kind, int route, Mat *C_, HipMatProduct **p_) {
+  PetscErrorCode ierr;
+  Mat C; HipMatProduct *p; PetscScalar *ca;
+  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(ci[m], 1), &ca);CHKERRQ(ierr);
+  memset(ca, 0, sizeof(PetscScalar) * (size_t)PetscMax(ci[m], 1));
+  ierr = MatCreate(HipObjComm(A), &C);CHKERRQ(ierr);
+  ierr = MatSetSizes(C, m, n, m, n);CHKERRQ(ierr);
+  ierr = MatSetType(C, MATSEQAIJHIPMI355X);CHKERRQ(ierr);
+  ierr = MatSeqAIJSetPreallocationCSR(C, ci, cj, ca);CHKERRQ(ierr);
+  HipFree(ca);
+  ierr = value_op_view(C);CHKERRQ(ierr);
+  memcpy(SD(C)->opt, SD(A)->opt, sizeof(SD(A)->opt)); memcpy(SD(C)->opt_set, SD(A)->opt_set, sizeof(SD(A)->opt_set));
+  SD(C)->product_route = SD(A)->product_route; SD(C)->sor.route = SD(A)->sor.route;
+  ierr = PetscMalloc(sizeof(*p), &p);CHKERRQ(ierr);
+  memset(p, 0, sizeof(*p));
+  p->kind = kind; p->route = route; p->symbolic_builds = 1;
+  SD(C)->prod = p;
+  if (route == 1) { ierr = MatSeqAIJHIPUpload(C);CHKERRQ(ierr); }   /* the one pattern upload */
+  *C_ = C; *p_ = p;
+  return 0;
+}
+/* after the device numeric phase: the host copy by one device-to-host copy; both routes: the result's state */
+static PetscErrorCode product_values_back(Mat C, PetscDeviceCtx *dc) {
+  const size_t bytes = sizeof(PetscScalar) * (size_t)SA(C)->nz;
+  if (bytes) CHKHIP(mi355x_memcpy_d2h(dc->h, SA(C)->a, SD(C)->mat.a, bytes));
+  CHKHIP(mi355x_handle_synchronize(dc->h));
+  return 0;
+}
+
+/* C = A B.  The host route's loop: MatMatMultNumeric_SeqAIJ_SeqAIJ's, a row of C at a time, both column lists ascending */
+typedef struct { const HipAIJ *a, *b, *c; } ProdHost;
+static void product_host_rows(void *c_, PetscInt lo, PetscInt hi) {
+  const ProdHost *h = (const ProdHost *)c_;
+  const HipAIJ *a = h->a, *b = h->b, *c = h->c;
+  for (PetscInt i = lo; i < hi; i++) {
+    const PetscInt *cc = c->j + c->i[i]; PetscScalar *cr = c->a + c->i[i];
+    for (PetscInt p = 0; p < c->i[i + 1] - c->i[i]; p++) cr[p] = 0.0;
+    for (PetscInt t = a->i[i]; t < a->i[i + 1]; t++) {
+      const PetscScalar av = a->a[t]; const PetscInt r = a->j[t];
+      PetscInt p = 0;
+      for (PetscInt q = b->i[r]; q < b->i[r + 1]; q++) {
+        while (cc[p] != b->j[q]) p++;
+        cr[p] = cr[p] + av * b->a[q];
+        p++;
+      }
+    }
+  }
+}
+static PetscErrorCode matmult_symbolic(Mat A, Mat B, int route, Mat *C_) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A), *b = SA(B);
+  const PetscInt m = a->m, n = b->n;
+  PetscInt *ci, *cj; HipMatProduct *p;
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(m + 1), &ci);CHKERRQ(ierr);
+  CHKHIP(mi355x_spgemm_symbolic_host((int)m, (int)n, a->i, a->j, b->i, b->j, ci, NULL, 0));
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(ci[m], 1), &cj);CHKERRQ(ierr);
+  CHKHIP(mi355x_spgemm_symbolic_host((int)m, (int)n, a->i, a->j, b->i, b->j, ci, cj, 0));
+  ierr = product_result(A, m, n, ci, cj, 1, route, C_, &p);CHKERRQ(ierr);
+  product_note(p, 0, A); product_note(p, 1, B);
+  if (route == 1) {
+    PetscDeviceCtx *dc;
+    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+    CHKHIP(mi355x_spgemm_plan_create(dc->h, (int)m, (int)a->n, (int)n, a->i, a->j, b->i, b->j, ci, cj, &p->plan));
+  }
+  HipFree(ci); HipFree(cj);
+  return 0;
+}
+static PetscErrorCode matmult_numeric(Mat A, Mat B, Mat C) {
+  PetscErrorCode ierr;
+  HipMatProduct *p = SD(C)->prod;
+  if (SA(C)->nz != SA(C)->i[SA(C)->m] || !SA(C)->compact) SETERRQ(HipObjComm(C), PETSC_ERR_ARG_WRONGSTATE, "the product's pattern was changed");
+  if (p->route == 1) {
+    PetscDeviceCtx *dc;
+    Mat_SeqAIJHIP *da = SD(A), *db = SD(B), *dd = SD(C);
+    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+    ierr = MatSeqAIJHIPUpload(C);CHKERRQ(ierr);                   /* (its arrays exist; nothing moves unless someone changed C) */
+    ierr = device_values_changed(C);CHKERRQ(ierr);
+    CHKHIP(mi355x_spgemm_numeric(dc->h, p->plan, da->mat.i, da->mat.j, da->mat.a, db->mat.i, db->mat.j, db->mat.a, dd->mat.i, dd->mat.j, dd->mat.a));
+    ierr = product_values_back(C, dc);CHKERRQ(ierr);
+    p->device_numerics++;
+  } else {
+    ProdHost h = {SA(A), SA(B), SA(C)};
+    HipParallelRanges(SA(A)->m, product_host_rows, &h);
+    p->host_numerics++;
+  }
+  HipStateIncrease(C);
+  return 0;
+}
+/* B = A^T: the stable counting sort behind the cached transpose (transpose_pattern), the values by the gather through its permutation */
+typedef struct { const PetscInt *perm; const PetscScalar *src; PetscScalar *dst; } GatherHost;
+static void product_gather_host(void *c_, PetscInt lo, PetscInt hi) { const GatherHost *g = (const GatherHost *)c_; for (PetscInt k = lo; k < hi; k++) g->dst[k] = g->src[g->perm[k]]; }
+static PetscErrorCode transpose_symbolic(Mat A, int route, Mat *B_) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A);
+  PetscInt *ti, *tj, *tperm; HipMatProduct *p;
+  ierr = transpose_pattern(a->m, a->n, a->i, a->j, 1, NULL, &ti, &tj, &tperm);CHKERRQ(ierr);
+  ierr = product_result(A, a->n, a->m, ti, tj, 2, route, B_, &p);CHKERRQ(ierr);
+  product_note(p, 0, A);
+  p->perm_h = tperm;
+  if (route == 1) {
+    PetscDeviceCtx *dc;
+    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+    CHKHIP(mi355x_malloc((void **)&p->perm_d, sizeof(PetscInt) * (size_t)PetscMax(a->nz, 1)));
+    CHKHIP(mi355x_memcpy_h2d(dc->h, p->perm_d, tperm, sizeof(PetscInt) * (size_t)a->nz));
+    CHKHIP(mi355x_handle_synchronize(dc->h));
+  }
+  HipFree(ti); HipFree(tj);
+  return 0;
+}
+static PetscErrorCode transpose_numeric(Mat A, Mat B) {
+  PetscErrorCode ierr;
+  HipMatProduct *p = SD(B)->prod;
+  if (SA(B)->nz != SA(A)->nz || !SA(B)->compact) SETERRQ(HipObjComm(B), PETSC_ERR_ARG_WRONGSTATE, "the transpose's pattern was changed");
+  if (p->route == 1) {
+    PetscDeviceCtx *dc;
+    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+    ierr = MatSeqAIJHIPUpload(B);CHKERRQ(ierr);
+    ierr = device_values_changed(B);CHKERRQ(ierr);
+    if (SA(A)->nz) CHKHIP(mi355x_pack(dc->h, (size_t)SA(A)->nz, p->perm_d, SD(A)->mat.a, SD(B)->mat.a));
+    ierr = product_values_back(B, dc);CHKERRQ(ierr);
+    p->device_numerics++;
+  } else {
+    GatherHost g = {p->perm_h, SA(A)->a, SA(B)->a};
+    HipParallelRanges(SA(A)->nz, product_gather_host, &g);
+    p->host_numerics++;
+  }
+  HipStateIncrease(B);
+  return 0;
+}
+
+static PetscErrorCode MatMatMultSymbolic_SeqAIJHIP(Mat A, Mat B, PetscReal fill, Mat *C) {
+  PetscErrorCode ierr;
+  int route;
+  (void)fill;
+  ierr = product_operand(A);CHKERRQ(ierr);
+  ierr = product_operand(B);CHKERRQ(ierr);
+  if (SA(A)->n != SA(B)->m) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_SIZ, "Matrix dimensions are incompatible, %d != %d", SA(A)->n, SA(B)->m);
+  ierr = product_route(A, &route);CHKERRQ(ierr);
+  ierr = product_operands_up(A, B, &route);CHKERRQ(ierr);
+  ierr = matmult_symbolic(A, B, route, C);CHKERRQ(ierr);      /* (the new matrix's first state is its constructor's: the device copy just made stays current) */
+  return 0;
+}
+static PetscErrorCode MatMatMultNumeric_SeqAIJHIP(Mat A, Mat B, Mat C) {
+  PetscErrorCode ierr;
+  HipMatProduct *p;
+  ierr = product_operand(A);CHKERRQ(ierr);
+  ierr = product_operand(B);CHKERRQ(ierr);
+  ierr = product_reuse_check(C, 1, A, B, &p);CHKERRQ(ierr);
+  return matmult_numeric(A, B, C);
+}
+static PetscErrorCode MatMatMult_SeqAIJHIP(Mat A, Mat B, MatReuse scall, PetscReal fill, Mat *C) {
+  PetscErrorCode ierr;
+  if (scall == MAT_INITIAL_MATRIX) { ierr = MatMatMultSymbolic_SeqAIJHIP(A, B, fill, C);CHKERRQ(ierr); }
+  return MatMatMultNumeric_SeqAIJHIP(A, B, *C);
+}
+static PetscErrorCode MatTranspose_SeqAIJHIP(Mat A, MatReuse reuse, Mat *B) {
+  PetscErrorCode ierr;
+  HipMatProduct *p;
+  ierr = product_operand(A);CHKERRQ(ierr);
+  if (reuse == MAT_INITIAL_MATRIX || !*B) {
+    int route;
+    ierr = product_route(A, &route);CHKERRQ(ierr);
+    ierr = product_operands_up(A, NULL, &route);CHKERRQ(ierr);
+    ierr = transpose_symbolic(A, route, B);CHKERRQ(ierr);
+  }
+  ierr = product_reuse_check(*B, 2, A, NULL, &p);CHKERRQ(ierr);
+  return transpose_numeric(A, *B);
+}
+static PetscErrorCode MatPtAP_SeqAIJHIP(Mat A, Mat P, MatReuse scall, PetscReal fill, Mat *C) {
+  PetscErrorCode ierr;
+  HipMatProduct *p;
+  (void)fill;
+  ierr = product_operand(A);CHKERRQ(ierr);
+  ierr = product_operand(P);CHKERRQ(ierr);
+  if (SA(A)->m != SA(A)->n || SA(A)->n != SA(P)->m) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_SIZ, "Matrix dimensions are incompatible, A %d x %d, P %d x %d", SA(A)->m, SA(A)->n, SA(P)->m, SA(P)->n);
+  if (scall == MAT_INITIAL_MATRIX) {
+    int route;
+    Mat Pt = NULL, AP = NULL;
+    ierr = product_route(A, &route);CHKERRQ(ierr);
+    ierr = product_operands_up(A, P, &route);CHKERRQ(ierr);
+    ierr = transpose_symbolic(P, route, &Pt);CHKERRQ(ierr);
+    ierr = transpose_numeric(P, Pt);CHKERRQ(ierr);             /* (the symbolic phase of Pt (A P) reads patterns only; the inner results are complete matrices all the same) */
+    ierr = matmult_symbolic(A, P, route, &AP);CHKERRQ(ierr);
+    ierr = matmult_numeric(A, P, AP);CHKERRQ(ierr);
+    ierr = matmult_symbolic(Pt, AP, route, C);CHKERRQ(ierr);
+    p = SD(*C)->prod;
+    p->kind = 3; p->Pt = Pt; p->AP = AP;
+    product_note(p, 0, A); product_note(p, 1, P);
+    p->device_numerics = p->host_numerics = 0;
+  } else {
+    HipMatProduct *q;
+    ierr = product_reuse_check(*C, 3, A, P, &p);CHKERRQ(ierr);
+    ierr = product_reuse_check(p->Pt, 2, P, NULL, &q);CHKERRQ(ierr);
+    ierr = product_reuse_check(p->AP, 1, A, P, &q);CHKERRQ(ierr);
+    ierr = transpose_numeric(P, p->Pt);CHKERRQ(ierr);
+    ierr = matmult_numeric(A, P, p->AP);CHKERRQ(ierr);
+  }
+  return matmult_numeric(p->Pt, p->AP, *C);
+}
+PetscErrorCode MatHIPMI355XGetProductCounts(Mat C, PetscInt *symbolic_builds, PetscInt *device_numerics, PetscInt *host_numerics) {
+  if (!C || !C->spptr || C->ops->mult != MatMult_SeqAIJHIP || !SD(C)->prod) SETERRQ(C ? HipObjComm(C) : 0, PETSC_ERR_ARG_WRONG, "not the result of MatMatMult, MatTranspose or MatPtAP");
+  if (symbolic_builds) *symbolic_builds = SD(C)->prod->symbolic_builds;
+  if (device_numerics) *device_numerics = SD(C)->prod->device_numerics;
+  if (host_numerics) *host_numerics = SD(C)->prod->host_numerics;
+  return 0;
+}
+
 static PetscErrorCode MatGetVecs_HIP(Mat A, Vec *right, Vec *left) {   /* MatGetVecs_SeqAIJCUSP aijcusp.cu:324-345 */
   PetscErrorCode ierr;
   if (right) {
@@ -1784,6 +2069,7 @@ static PetscErrorCode MatDestroy_SeqAIJHIP(Mat A) {   /* free the mirror and zer
   if (SD(A)) {
     Mat_SeqAIJHIP *d = SD(A);
     (void)HipTriFactorsDestroy(&d->tri);    /* a factored matrix: its triangular factors */
+    product_free(A);                        /* the result of a product: its plan and inner results */
     device_free(A);
     if (d->time_ev) { for (PetscInt k = 0; k < 2 * d->time_cap; k++) mi355x_event_destroy(d->time_ev[k]); HipFree(d->time_ev); }
     HipFree(A->spptr); A->spptr = NULL;
@@ -1837,6 +2123,11 @@ static PetscErrorCode create_common(Mat B, const char *tname, PetscInt bs) {
   B->ops->diagonalscale = MatDiagonalScale_SeqAIJHIP;
   B->ops->setvaluesbatch = MatSetValuesBatch_SeqAIJHIP;
   B->ops->duplicate = MatDuplicate_SeqAIJHIP;
+  B->ops->matmult = MatMatMult_SeqAIJHIP;                     /* sequential AIJ operands; the block type answers PETSC_ERR_SUP */
+  B->ops->matmultsymbolic = MatMatMultSymbolic_SeqAIJHIP;
+  B->ops->matmultnumeric = MatMatMultNumeric_SeqAIJHIP;
+  B->ops->transpose = MatTranspose_SeqAIJHIP;
+  B->ops->ptap = MatPtAP_SeqAIJHIP;
   B->ops->setfromoptions = MatSetFromOptions_SeqAIJHIP;
   B->ops->destroy = MatDestroy_SeqAIJHIP;
   B->ops->getvecs = MatGetVecs_HIP;
@@ -1870,7 +2161,7 @@ static PetscErrorCode MatDuplicate_SeqAIJHIP(Mat A, MatDuplicateOption op, Mat *
   ierr = adopt_csr(B, a->m, a->bs > 1 ? a->bs : 1, a->i, a->j, a->a);CHKERRQ(ierr);
   if (op != MAT_COPY_VALUES) memset(SA(B)->a, 0, sizeof(PetscScalar) * (size_t)a->nz * (size_t)(a->bs > 1 ? a->bs * a->bs : 1));
   memcpy(SD(B)->opt, SD(A)->opt, sizeof(SD(A)->opt)); memcpy(SD(B)->opt_set, SD(A)->opt_set, sizeof(SD(A)->opt_set));
-  SD(B)->cprow = SD(A)->cprow; SD(B)->sor.route = SD(A)->sor.route;
+  SD(B)->cprow = SD(A)->cprow; SD(B)->sor.route = SD(A)->sor.route; SD(B)->product_route = SD(A)->product_route;
   SA(B)->keepnonzeropattern = a->keepnonzeropattern;
   *M = B;
   return 0;

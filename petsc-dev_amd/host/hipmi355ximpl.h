@@ -222,9 +222,22 @@ typedef struct {
   PetscBool fresh;                  /* a (and the tiled layout's copy of it) hold the matrix's current device values */
 } HipDevForm;
 
+/* what the result of MatMatMult / MatTranspose / MatPtAP carries (host/aijhip.c, "Sparse matrix products"): the operands it was built
+ * from -- told by address, sizes, entry counts and the serial numbers of their pattern uploads (0: never uploaded, the host route), never
+ * dereferenced through here -- and what a repeated numeric phase on unchanged patterns needs */
+typedef struct {
+  int kind;                                  /* 1: C = A B; 2: B = A^T; 3: C = P^T A P */
+  int route;                                 /* 1 device, 2 host: as the symbolic phase found -mat_hipmi355x_product */
+  void *op[2]; PetscInt op_nz[2]; unsigned long long op_gen[2];
+  mi355x_spgemm_plan_t plan;                 /* kind 1, and kind 3 for Pt (AP) */
+  PetscInt *perm_h, *perm_d;                 /* kind 2: position in A^T -> position in A (device copy on the device route) */
+  Mat Pt, AP;                                /* kind 3: the inner results, products of kind 2 and 1 themselves */
+  PetscInt symbolic_builds, device_numerics, host_numerics;
+} HipMatProduct;
+
 /* device mirror */
 typedef struct {
-  HipDevForm mat;            /* the device copy of the matrix (compressed rows: the rows with entries only) */
+  HipDevForm mat;           /* the device copy of the matrix (compressed rows: the rows with entries only) */
   int uploaded_state;        /* Mat state at last upload (compare state instead of valid_GPU_matrix) */
   /* compressed-row form for mostly-empty blocks (src/mat/utils/compressedrow.c:28) */
   PetscBool cprow;            /* compressed-row form requested (off-diagonal block) */
@@ -268,6 +281,8 @@ typedef struct {
     int route;
     PetscInt idiag_builds, plan_builds, device_applications;
   } sor;
+  HipMatProduct *prod;       /* the matrix is the result of a product (NULL: an ordinary matrix) */
+  int product_route;         /* -mat_hipmi355x_product <device|host> as MatSetFromOptions read it under the matrix's prefix (0: not given there) */
   PetscInt opt[8]; PetscBool opt_set[8];   /* the type's options as MatSetFromOptions read them under the matrix's prefix (host/aijhip.c) */
   /* per-launch device timing for bench.py (hipEvent pairs on the compute stream) */
   PetscBool timing; PetscInt time_n, time_cap; mi355x_event_t *time_ev;

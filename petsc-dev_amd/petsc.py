@@ -52,6 +52,8 @@ _SIG = {
     "MatShift": [vp, dbl], "MatAXPY": [vp, dbl, vp, i32], "MatAYPX": [vp, dbl, vp, i32], "MatCopy": [vp, vp, i32],
     "MatZeroRows": [vp, i32, vp, dbl, vp, vp], "MatZeroRowsColumns": [vp, i32, vp, dbl, vp, vp], "MatSetOption": [vp, i32, i32],
     "MatHIPMI355XGetZeroRowsCounts": [vp, P(i32), P(i32)],
+    "MatMatMult": [vp, vp, i32, dbl, P(vp)], "MatMatMultSymbolic": [vp, vp, dbl, P(vp)], "MatMatMultNumeric": [vp, vp, vp],
+    "MatTranspose": [vp, i32, P(vp)], "MatPtAP": [vp, vp, i32, dbl, P(vp)], "MatHIPMI355XGetProductCounts": [vp, P(i32), P(i32), P(i32)],
     "MatSOR": [vp, vp, dbl, i32, dbl, i32, i32, vp], "MatHIPMI355XGetSORInfo": [vp, P(i32), P(i32), P(i32), P(i32), P(i32)],
     "MatSeqAIJGetArrays": [vp, P(i32), P(vp), P(vp), P(vp)], "MatMPIAIJGetSeqAIJ": [vp, P(vp), P(vp), P(vp)],
     "MatMPIAIJGetScatter": [vp, P(vp), P(vp), P(i32)],
@@ -85,6 +87,7 @@ NORM_1, NORM_2, NORM_FROBENIUS, NORM_INFINITY, NORM_1_AND_2 = 0, 1, 2, 3, 4
 MAT_FINAL_ASSEMBLY, MAT_FLUSH_ASSEMBLY = 0, 1
 PETSC_DECIDE, PETSC_DEFAULT = -1, -2
 DIFFERENT_NONZERO_PATTERN, SUBSET_NONZERO_PATTERN, SAME_NONZERO_PATTERN = 0, 1, 2
+MAT_INITIAL_MATRIX, MAT_REUSE_MATRIX = 0, 1          # MatReuse (petscmini.h)
 KSP_NORM_NONE, KSP_NORM_PRECONDITIONED, KSP_NORM_UNPRECONDITIONED, KSP_NORM_NATURAL = 0, 1, 2, 3   # KSPNormType (petscmini.h)
 MAT_KEEP_NONZERO_PATTERN = 9          # MatOption (petscmini.h)
 # MatSORType (petscmini.h)
@@ -335,6 +338,40 @@ class Mat:
         v = [i32() for _ in range(5)]
         lib().MatHIPMI355XGetSORInfo(self.h, *[C.byref(q) for q in v])
         return tuple(q.value for q in v)
+
+    def matmult(self, B, reuse=None):
+        """C = self B (MatMatMult); reuse: the Mat an earlier call with the same operands returned, filled again (MAT_REUSE_MATRIX)"""
+        Cm = reuse if reuse is not None else Mat()
+        lib().MatMatMult(self.h, B.h, MAT_INITIAL_MATRIX if reuse is None else MAT_REUSE_MATRIX, float(PETSC_DEFAULT), C.byref(Cm.h))
+        return Cm
+
+    def transpose(self, reuse=None):
+        """B = self^T as a matrix of its own (MatTranspose); reuse as in matmult"""
+        Bm = reuse if reuse is not None else Mat()
+        lib().MatTranspose(self.h, MAT_INITIAL_MATRIX if reuse is None else MAT_REUSE_MATRIX, C.byref(Bm.h))
+        return Bm
+
+    def ptap(self, Pm, reuse=None):
+        """C = Pm^T self Pm (MatPtAP); reuse as in matmult"""
+        Cm = reuse if reuse is not None else Mat()
+        lib().MatPtAP(self.h, Pm.h, MAT_INITIAL_MATRIX if reuse is None else MAT_REUSE_MATRIX, float(PETSC_DEFAULT), C.byref(Cm.h))
+        return Cm
+
+    def product_counts(self):
+        """of the result of matmult / transpose / ptap: host symbolic passes, device numerics, host numerics (MatHIPMI355XGetProductCounts)"""
+        v = [i32() for _ in range(3)]
+        lib().MatHIPMI355XGetProductCounts(self.h, *[C.byref(q) for q in v])
+        return tuple(q.value for q in v)
+
+    def csr(self):
+        """copies of a sequential matrix's host arrays: row pointer, columns, values (MatSeqAIJGetArrays)"""
+        m, pi_, pj, pa = i32(), vp(), vp(), vp()
+        lib().MatSeqAIJGetArrays(self.h, C.byref(m), C.byref(pi_), C.byref(pj), C.byref(pa))
+        ai = np.ctypeslib.as_array(C.cast(pi_, P(i32)), (m.value + 1,)).copy()
+        nz = int(ai[-1])
+        aj = np.ctypeslib.as_array(C.cast(pj, P(i32)), (max(nz, 1),))[:nz].copy()
+        aa = np.ctypeslib.as_array(C.cast(pa, P(dbl)), (max(nz, 1),))[:nz].copy()
+        return ai, aj, aa
 
     def local_size(self):
         m, n = i32(), i32()
