@@ -183,6 +183,19 @@ int mi355x_vec_bcgs_update(mi355x_handle_t h, size_t n, double alpha, double ome
 int mi355x_vec_cheby_step(mi355x_handle_t h, size_t n, double s, double a, double c, const double *w, const double *b, const double *d,
                           const double *pm, const double *pk, double *r, double *pn, int sums, double *out);
 int mi355x_vec_rich_step(mi355x_handle_t h, size_t n, double scale, const double *w, const double *b, const double *d, double *r, double *z, double *x);
+/* The body of KSPSolve_PIPECG's loop (src/ksp/ksp/impls/cg/pipecg/pipecg.c:138-175) behind m = B w (mv) and n = A m (nv), one sweep with
+ * the bits of mi355x_vec_copy / _aypx (x4), mi355x_vec_axpy (x4), mi355x_vec_pointwise_mult and mi355x_vec_dot / _norm(type 1) in sequence:
+ *   first != 0: zrec = nv ; qrec = mv ; p = u ; s = w (the old contents are not read)
+ *   otherwise:  zrec = nv + ratio zrec ; qrec = mv + ratio qrec ; p = u + ratio p ; s = w + ratio s  (mi355x_vec_aypx's cases 0, 1, -1)
+ *   step != 0:  x = x + step p ; u = u + (-step) qrec ; w = w + (-step) zrec ; r = r + (-step) s  (step == 0: none of the four is written)
+ *   m_next != NULL: m_next = w .* d (d == NULL: a copy of w); m_next may be mv, every load of an element precedes its stores
+ *   out != NULL: out[0] = sum w*u, out[1] = sum r*r (rides 1), sum u*u (rides 2) or sum r*u (rides 3) over the updated vectors (for an
+ *   aligned view the trees of mi355x_vec_dot / mi355x_vec_norm(type 1); out: device or the handle's pinned scratch); n == 0: zeros.
+ *   out == NULL: the pure element-wise form, nothing reduced.
+ * An operand a special case skips is not loaded.  A missing vector, or rides outside 1..3 with out: nonzero, nothing touched. */
+int mi355x_vec_pipecg_step(mi355x_handle_t h, size_t n, int first, double ratio, double step, const double *nv, const double *mv, const double *d,
+                           double *zrec, double *qrec, double *p, double *s, double *x, double *u, double *w, double *r, double *m_next,
+                           int rides, double *out);
 /* VecMDot_Seq         src/vec/vec/impls/seq/dvec2.c:146     out[j] = sum_i x_i y_j,i , j<nv ; x read once per 16 y's */
 int mi355x_vec_mdot(mi355x_handle_t h, size_t n, int nv, const double *x, const double *const *y, double *out);
 /* KSPGMRESCycle fusions (gmres.c:118-209, borthog2.c:60-66): x += sum_j sign*coef_dev[j]*y_j in VecMAXPY_Seq's grouping with

@@ -42,6 +42,22 @@ typedef struct {
   PetscErrorCode (*rich_step)(Vec x, Vec r, Vec z, Vec w, Vec b, Vec d, PetscScalar scale, PetscBool *done);
 } VecKrylovFusedOps;
 typedef const VecKrylovFusedOps *(*VecKrylovFusedOpsGetFn)(void);
+/* "VecPipelinedCGFusedOps_C" on a Vec returns the sweeps of the pipelined CG family, a table of its own.  Their sums are not waited
+ * for: a sweep leaves them PENDING as the VecNormBegin / VecDotBegin calls it replaces would have, same kinds in the same order, and
+ * the driver's PetscCommSplitReductionBegin, VecNormEnd and VecDotEnd follow as in the op-by-op sequence.  A split phase already
+ * begun: PETSC_ERR_ORDER.  *done = PETSC_FALSE and nothing touched when the sweep refuses its operands. */
+typedef struct {
+  /* The body of KSPSolve_PIPECG's loop (pipecg.c:138-175) behind mv = B w and nv = A mv:
+   *   first: zrec = nv, qrec = mv, p = u, s = w (VecCopy x4); else zrec = nv + ratio zrec, .. , s = w + ratio s (VecAYPX x4);
+   *   x += step p, u -= step qrec, w -= step zrec, r -= step s (VecAXPY x4);
+   *   m_next != NULL: m_next = d .* w, the next iteration's PCApply_Jacobi (d == NULL: PCNONE's copy); m_next may be mv;
+   *   rides 1 / 2 / 3: VecNormBegin(r) / VecNormBegin(u) / VecDotBegin(r, u), then VecDotBegin(w, u), on the updated vectors, pending;
+   *   rides 0: nothing is reduced.
+   * No written vector is another operand (but m_next == mv). */
+  PetscErrorCode (*pipecg_step)(Vec x, Vec u, Vec w, Vec r, Vec zrec, Vec qrec, Vec p, Vec s, Vec nv, Vec mv, Vec d, Vec m_next,
+                                PetscBool first, PetscScalar ratio, PetscScalar step, PetscInt rides, PetscBool *done);
+} VecPipelinedCGFusedOps;
+typedef const VecPipelinedCGFusedOps *(*VecPipelinedCGFusedOpsGetFn)(void);
 typedef PetscErrorCode (*MatMultTDotBeginFn)(Mat A, Vec x, Vec y, PetscBool *ok);
 typedef PetscErrorCode (*MatMultDiagonalScaleFn)(Mat A, Vec d, Vec x, Vec y, PetscBool *ok);
 

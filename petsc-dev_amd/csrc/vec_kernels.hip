@@ -927,6 +927,117 @@ static int launch_krylov_step(mi355x_handle_t h, size_t n, KrylovStepF f, int su
   return launch_tiles(h, n, vec_ok, krylov_step_kernel<true>, krylov_step_kernel<false>, f);
 }
 
+// ---- the body of KSPSolve_PIPECG's loop (pipecg.c:138-175) after the reduction has ended, behind m = B w and n = A m.  In one sweep:
+//   zrec = nv + ratio zrec ; qrec = mv + ratio qrec ; p = u + ratio p ; s = w + ratio s      (VecAYPX x4: OpAypx with mi355x_vec_aypx's
+//                                                        special cases 0 -> copy, 1 -> OpAxpy{1}, -1 -> OpXmY; first: VecCopy x4, nothing old read)
+//   x = x + step p ; u = u + (-step) qrec ; w = w + (-step) zrec ; r = r + (-step) s         (VecAXPY x4: OpAxpy; step == 0: the four untouched)
+//   m_next = w .* d                                      (PCApply_Jacobi: OpMul; d == NULL: PCNONE's copy; m_next == NULL: not formed)
+//   out = { sum w*u , sum r*r | sum u*u | sum r*u }      (the next iteration's VecDot(w, u) and what rides with it)
+// Each product and sum is rounded as in those kernels and with sums a lane meets its elements in DotF's / SumSqF's order under
+// launch_reduce: every output carries the bits of the separate launches.  An operand a special case skips is not loaded.
+// Streaming (see nt_load2), a choice by analogy with KrylovStepF, not a measurement: d, the four recurrences, x, u and r
+// have their only reader of the iteration here and are non-temporal at every size; so is w when the preconditioner rides along
+// (m_next), else PCApply reads it next.  nv (just written by the product), mv and m_next (gathered by the next product) stay
+// cacheable below 256 MiB and are streamed from there on like every other tile kernel.
+__device__ __forceinline__ void ldq_tile1(const double *p, size_t i, int nt, double2 &v) { v = ldq(reinterpret_cast<const double2 *>(p) + i, nt); }
+template <int U> __device__ __forceinline__ void ldq_tile(const double *p, size_t i, int nt, double2 (&v)[U]) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) ldq_tile1(p, i + u * MI355X_BLOCK, nt, v[u]);
+}
+template <int U> __device__ __forceinline__ void stq_tile(double *p, size_t i, int nt, const double2 (&v)[U]) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) stq(reinterpret_cast<double2 *>(p) + i + u * MI355X_BLOCK, v[u], nt);
+}
+// y_new of VecAYPX(y, ratio, x) with the special cases of mi355x_vec_aypx; copy: VecCopy, or ratio == 0
+__device__ __forceinline__ double aypx_elem(bool copy, double ratio, double xv, double yv) {
+  if (copy) return xv;
+  if (ratio == 1.0) return OpAxpy{1.0}(xv, yv, 0.0);
+  if (ratio == -1.0) return OpXmY{}(xv, yv, 0.0);
+  return OpAypx{ratio}(xv, yv, 0.0);
+}
+struct PipeCGStepF {
+  double ratio, step;
+  const double *nv, *mv, *d;
+  double *zrec, *qrec, *p, *s, *x, *u, *w, *r, *m_next;
+  int first, rides, big;       // rides: what the second sum is (1 r*r, 2 u*u, 3 r*u; 0: no sums at all)
+  // which operands this form reads or writes (uniform over the launch)
+  __device__ __forceinline__ bool copies() const { return first || ratio == 0.0; }
+  __device__ __forceinline__ bool steps() const { return step != 0.0; }
+  __device__ __forceinline__ bool reads_r() const { return steps() || rides == 1 || rides == 3; }
+  __device__ __forceinline__ int w_nt() const { return big || m_next != nullptr; }
+  __device__ __forceinline__ void one(double nvv, double mvv, double dv, double &zr, double &qr, double &pv, double &sv, double &xv, double &uv,
+                                      double &wv, double &rv, double &mn) const {
+    const bool cp = copies();
+    zr = aypx_elem(cp, ratio, nvv, zr); qr = aypx_elem(cp, ratio, mvv, qr);
+    pv = aypx_elem(cp, ratio, uv, pv); sv = aypx_elem(cp, ratio, wv, sv);
+    if (steps()) {                                                   // VecAXPY returns at once for alpha == 0 (bvec1.c:253)
+      xv = OpAxpy{step}(pv, xv, 0.0); uv = OpAxpy{-step}(qr, uv, 0.0);
+      wv = OpAxpy{-step}(zr, wv, 0.0); rv = OpAxpy{-step}(sv, rv, 0.0);
+    }
+    mn = d ? OpMul{}(wv, dv, 0.0) : wv;
+  }
+  __device__ __forceinline__ void sums(double uv, double wv, double rv, double (&acc)[2]) const {
+    acc[0] += wv * uv;
+    acc[1] += rides == 1 ? rv * rv : (rides == 2 ? uv * uv : rv * uv);
+  }
+  // the U double2's of a lane in its tile; every load is issued before the first store, so m_next may be mv
+  template <int U>
+  __device__ __forceinline__ void tile(size_t i, double2 (&uv)[U], double2 (&wv)[U], double2 (&rv)[U]) const {
+    double2 nvv[U], mvv[U], dv[U] = {}, zr[U] = {}, qr[U] = {}, pv[U] = {}, sv[U] = {}, xv[U] = {}, mn[U];
+    ldq_tile(nv, i, big, nvv);
+    ldq_tile(mv, i, big, mvv);
+    if (d && m_next) ldq_tile(d, i, 1, dv);
+    if (!copies()) { ldq_tile(zrec, i, 1, zr); ldq_tile(qrec, i, 1, qr); ldq_tile(p, i, 1, pv); ldq_tile(s, i, 1, sv); }
+    if (steps()) ldq_tile(x, i, 1, xv);
+    ldq_tile(u, i, 1, uv);
+    ldq_tile(w, i, w_nt(), wv);
+    if (reads_r()) ldq_tile(r, i, 1, rv);
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      one(nvv[j].x, mvv[j].x, dv[j].x, zr[j].x, qr[j].x, pv[j].x, sv[j].x, xv[j].x, uv[j].x, wv[j].x, rv[j].x, mn[j].x);
+      one(nvv[j].y, mvv[j].y, dv[j].y, zr[j].y, qr[j].y, pv[j].y, sv[j].y, xv[j].y, uv[j].y, wv[j].y, rv[j].y, mn[j].y);
+    }
+    stq_tile(zrec, i, 1, zr); stq_tile(qrec, i, 1, qr); stq_tile(p, i, 1, pv); stq_tile(s, i, 1, sv);
+    if (steps()) { stq_tile(x, i, 1, xv); stq_tile(u, i, 1, uv); stq_tile(w, i, w_nt(), wv); stq_tile(r, i, 1, rv); }
+    if (m_next) stq_tile(m_next, i, big, mn);
+  }
+  __device__ __forceinline__ void at1(size_t k, double &uv, double &wv, double &rv) const {
+    const bool cp = copies();
+    const double nvv = nv[k], mvv = mv[k], dv = (d && m_next) ? d[k] : 0.0;
+    double zr = cp ? 0.0 : zrec[k], qr = cp ? 0.0 : qrec[k], pv = cp ? 0.0 : p[k], sv = cp ? 0.0 : s[k], xv = steps() ? x[k] : 0.0, mn;
+    uv = u[k]; wv = w[k]; rv = reads_r() ? r[k] : 0.0;
+    one(nvv, mvv, dv, zr, qr, pv, sv, xv, uv, wv, rv, mn);
+    zrec[k] = zr; qrec[k] = qr; p[k] = pv; s[k] = sv;
+    if (steps()) { x[k] = xv; u[k] = uv; w[k] = wv; r[k] = rv; }
+    if (m_next) m_next[k] = mn;
+  }
+  // under launch_reduce: the trees of mi355x_vec_dot / mi355x_vec_norm(type 1) over the updated vectors
+  template <int NOUT_>
+  __device__ __forceinline__ void sweep(size_t tid, size_t stride, size_t n2, double (&acc)[NOUT_]) const {
+    for (size_t i = tid; i < n2; i += stride) {
+      double2 uv[1], wv[1], rv[1] = {};
+      tile<1>(i, uv, wv, rv);
+      sums(uv[0].x, wv[0].x, rv[0].x, acc);
+      sums(uv[0].y, wv[0].y, rv[0].y, acc);
+    }
+  }
+  __device__ __forceinline__ void accum1(size_t k, double (&acc)[2]) const {
+    double uv, wv, rv;
+    at1(k, uv, wv, rv);
+    sums(uv, wv, rv, acc);
+  }
+};
+// the same body as a pure map: one tile of 256 x 2 double2 per workgroup, nothing reduced
+__global__ __launch_bounds__(MI355X_BLOCK) void pipecg_step_kernel(PipeCGStepF f, size_t n, int vec_ok) {
+  tile_walk<2>(n, vec_ok,
+    [&](size_t i, auto u) {
+      constexpr int U = decltype(u)::value;
+      double2 uv[U], wv[U], rv[U] = {};
+      f.template tile<U>(i, uv, wv, rv);
+    },
+    [&](size_t k) { double uv, wv, rv; f.at1(k, uv, wv, rv); });
+}
+
 template <int NV>
 struct MDotF {
   const double *x;
@@ -1204,6 +1315,17 @@ int mi355x_vec_cheby_step(mi355x_handle_t h, size_t n, double s, double a, doubl
 int mi355x_vec_rich_step(mi355x_handle_t h, size_t n, double scale, const double *w, const double *b, const double *d, double *r, double *z, double *x) {
   if (!w || !b || !x) return (int)hipErrorInvalidValue;
   return launch_krylov_step(h, n, KrylovStepF{scale, 0.0, 0.0, w, b, d, nullptr, nullptr, r, z, x, 1, 0}, 0, nullptr);
+}
+
+int mi355x_vec_pipecg_step(mi355x_handle_t h, size_t n, int first, double ratio, double step, const double *nv, const double *mv, const double *d,
+                           double *zrec, double *qrec, double *p, double *s, double *x, double *u, double *w, double *r, double *m_next,
+                           int rides, double *out) {
+  if (!nv || !mv || !zrec || !qrec || !p || !s || !x || !u || !w || !r || (out && (rides < 1 || rides > 3))) return (int)hipErrorInvalidValue;
+  const PipeCGStepF f{ratio, step, nv, mv, d, zrec, qrec, p, s, x, u, w, r, m_next, first != 0, out ? rides : 0, vec_streams(n)};
+  const int vec_ok = all_aligned16(nv, mv, d, zrec, qrec, p, s, x, u, w, r, m_next);   // d, m_next == NULL count as aligned
+  if (out) return launch_reduce<2, RED_SUM>(h, f, n, vec_ok, out);                      // n == 0: zeros
+  if (n == 0) return 0;
+  return launch_tiles(h, n, vec_ok, pipecg_step_kernel, pipecg_step_kernel, f);
 }
 
 // borthog2.c:63-64 + the norm of gmres.c:146: x += sum_j sign * coef_dev[j] * y_j, *out = sum x_new^2 (out: device or the

@@ -343,10 +343,21 @@ PetscErrorCode MatTimingBegin(Mat A, mi355x_handle_t h);
 PetscErrorCode MatTimingEnd(Mat A, mi355x_handle_t h);
 PetscErrorCode MatGetVecs_HIPMI355X(Mat A, Vec *right, Vec *left);
 PetscErrorCode PCCreate_PBJacobi_HIPMI355X(PC);
+/* "VecSplitReductionOps_C" on a Vec: the three phases of a split reduction as the type provides them (host/vechip.c composes it, the
+ * object model's VecDotBegin / VecNormBegin / VecDotEnd / VecNormEnd / PetscCommSplitReductionBegin look it up, and so does
+ * host/kspfused.c, which takes none of those five names from the object model's library) */
+typedef struct {
+  PetscErrorCode (*dot_begin)(Vec, Vec, PetscScalar *);
+  PetscErrorCode (*dot_end)(Vec, Vec, PetscScalar *);
+  PetscErrorCode (*norm_begin)(Vec, NormType, PetscReal *);
+  PetscErrorCode (*norm_end)(Vec, NormType, PetscReal *);
+  PetscErrorCode (*comm_begin)(MPI_Comm);
+} VecSplitReductionOps;
 PetscErrorCode KSPCreate_CGHIPMI355X(KSP);
 PetscErrorCode KSPCreate_GMRESHIPMI355X(KSP);
 PetscErrorCode KSPCreate_BCGSHIPMI355X(KSP);
 PetscErrorCode KSPCreate_ChebychevHIPMI355X(KSP);
 PetscErrorCode KSPCreate_RichardsonHIPMI355X(KSP);
+PetscErrorCode KSPCreate_PIPECGHIPMI355X(KSP);
 
 #endif

@@ -6,6 +6,7 @@
  *     KSPBCGSHIPMI355X  "bcgshipmi355x"    BiCGStab  (the recurrence of KSPBCGS,  src/ksp/ksp/impls/bcgs/bcgs.c:43-160)
  *     KSPCHEBYCHEVHIPMI355X  "chebychevhipmi355x"   Chebyshev  (the sequence of KSPCHEBYCHEV,  src/ksp/ksp/impls/cheby/cheby.c)
  *     KSPRICHARDSONHIPMI355X "richardsonhipmi355x"  Richardson (the sequence of KSPRICHARDSON, src/ksp/ksp/impls/rich/rich.c)
+ *     KSPPIPECGHIPMI355X     "pipecghipmi355x"      pipelined CG (the sequence of KSPPIPECG, src/ksp/ksp/impls/cg/pipecg/pipecg.c:49-205)
  *
  * They compute what the reference's solvers compute -- same iterates, same residual history, same exits, bit for bit against
  * the op-by-op sequences (tests/test_host_gpu.py) -- but group the vector work between two reductions into the fused sweeps a
@@ -776,6 +777,179 @@ PetscErrorCode KSPCreate_ChebychevHIPMI355X(KSP ksp) {
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_LEFT, 1);CHKERRQ(ierr);
   ksp->ops->setup = KSPSetUp_ChebyHIP; ksp->ops->solve = KSPSolve_ChebyHIP; ksp->ops->setfromoptions = KSPSetFromOptions_ChebyHIP; ksp->ops->destroy = KSPDestroy_ChebyHIP;
   ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPChebychevSetEigenvalues_C", "KSPChebychevSetEigenvalues_ChebyHIP", (PetscVoidFunction)KSPChebychevSetEigenvalues_ChebyHIP);CHKERRQ(ierr);
+  return 0;
+}
+
+/* ================================================================================================ pipelined CG
+ * The sequence of KSPSolve_PIPECG (src/ksp/ksp/impls/cg/pipecg/pipecg.c:49-205): nine work vectors, the norm table of KSPPIPECG, ONE
+ * split-phase reduction per iteration in flight over m = B w and n = A m, the same quantity riding with w'u in each iteration (with the
+ * preconditioned or the unpreconditioned norm res'u is reduced in iteration 0 only), same iterates, histories and exits.  The solve
+ * start and iteration 0 are the public calls.  From then on what follows the End calls of iteration k -- four VecAYPX (VecCopy), four
+ * VecAXPY, with PCJACOBI / PCNONE and no null space iteration k+1's m = B w, and iteration k+1's VecNormBegin / VecDotBegin pair -- is
+ * ONE sweep ("pipecg_step" of "VecPipelinedCGFusedOps_C", include/petsckrylovfused.h) that leaves the sums pending; the driver goes on
+ * with the communicator-wide Begin, the product, and the End calls (all of them through the type's "VecSplitReductionOps_C").  The sweep of the last permitted iteration queues no sums, so no
+ * exit leaves a split phase pending.  Vectors without the table, a sweep that refuses, or -ksp_pipecg_fused false: the public calls
+ * of that step.  KSPHIPMI355XGetFusedStepCounts: steps taken by each route. */
+typedef struct { PetscBool fused; Vec dinv; PetscInt nfused, nopbyop; } KSP_PipeCGHIP;
+
+static const VecPipelinedCGFusedOps *vec_pipelined_ops(Vec x) {
+  PetscVoidFunction f = NULL;
+  if (PetscObjectQueryFunction((PetscObject)x, "VecPipelinedCGFusedOps_C", &f) || !f) return NULL;
+  return ((VecPipelinedCGFusedOpsGetFn)f)();
+}
+/* The split-phase reductions as the vectors' type provides them ("VecSplitReductionOps_C", what VecDotBegin / VecNormBegin / VecDotEnd /
+ * VecNormEnd / PetscCommSplitReductionBegin of the object model dispatch to for these vectors).  A type without the table: Begin is
+ * the whole reduction (VecDot / VecNorm), nothing is in flight and End has nothing left to do -- the vectors do not change between the
+ * two, so the value is the one End would have delivered. */
+static const VecSplitReductionOps *vec_split_ops(Vec x) {
+  PetscVoidFunction f = NULL;
+  if (PetscObjectQueryFunction((PetscObject)x, "VecSplitReductionOps_C", &f) || !f) return NULL;
+  return ((const VecSplitReductionOps *(*)(void))f)();
+}
+static PetscErrorCode split_dot_begin(const VecSplitReductionOps *S, Vec x, Vec y, PetscScalar *v) { return S ? S->dot_begin(x, y, v) : VecDot(x, y, v); }
+static PetscErrorCode split_dot_end(const VecSplitReductionOps *S, Vec x, Vec y, PetscScalar *v) { return S ? S->dot_end(x, y, v) : 0; }
+static PetscErrorCode split_norm_begin(const VecSplitReductionOps *S, Vec x, PetscReal *v) { return S ? S->norm_begin(x, NORM_2, v) : VecNorm(x, NORM_2, v); }
+static PetscErrorCode split_norm_end(const VecSplitReductionOps *S, Vec x, PetscReal *v) { return S ? S->norm_end(x, NORM_2, v) : 0; }
+static PetscErrorCode split_comm_begin(const VecSplitReductionOps *S, Vec x) { return S && S->comm_begin ? S->comm_begin(HipObjComm(x)) : 0; }
+
+static PetscErrorCode KSPGetFusedStepCounts_PipeCGHIP(KSP ksp, PetscInt *fused, PetscInt *opbyop) {
+  const KSP_PipeCGHIP *pd = (const KSP_PipeCGHIP *)ksp->data;
+  *fused = pd->nfused; *opbyop = pd->nopbyop;
+  return 0;
+}
+PetscErrorCode KSPHIPMI355XGetFusedStepCounts(KSP ksp, PetscInt *fused, PetscInt *opbyop) {
+  PetscVoidFunction f = NULL;
+  PetscErrorCode ierr = PetscObjectQueryFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", &f);CHKERRQ(ierr);
+  *fused = 0; *opbyop = 0;
+  if (f) { ierr = ((PetscErrorCode (*)(KSP, PetscInt *, PetscInt *))f)(ksp, fused, opbyop);CHKERRQ(ierr); }
+  return 0;
+}
+static PetscErrorCode KSPSetUp_PipeCGHIP(KSP ksp) { return KSPDefaultGetWork(ksp, 9); }
+static PetscErrorCode KSPSetFromOptions_PipeCGHIP(KSP ksp) {
+  PetscInt iv = ((KSP_PipeCGHIP *)ksp->data)->fused;
+  PetscErrorCode ierr = option_level(ksp, "-ksp_pipecg_fused", 0, 1, &iv);CHKERRQ(ierr);
+  ((KSP_PipeCGHIP *)ksp->data)->fused = (PetscBool)iv;
+  return 0;
+}
+static PetscErrorCode KSPDestroy_PipeCGHIP(KSP ksp) {
+  KSP_PipeCGHIP *pd = (KSP_PipeCGHIP *)ksp->data;
+  PetscErrorCode ierr;
+  if (!pd) return 0;
+  ierr = VecDestroy(&pd->dinv);CHKERRQ(ierr);
+  HipFree(pd); ksp->data = NULL;
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
+  return 0;
+}
+
+enum { PIPE_NOTHING = 0, PIPE_RR = 1, PIPE_UU = 2, PIPE_RU = 3 };   /* what rides with w'u in an iteration's reduction: "rides" of pipecg_step */
+static int pipecg_rides(KSPNormType norm, PetscInt k) {             /* pipecg.c:124-131,138-145 */
+  const PetscBool normed = (PetscBool)(norm == KSP_NORM_UNPRECONDITIONED || norm == KSP_NORM_PRECONDITIONED);
+  if (k > 0 && normed) return norm == KSP_NORM_UNPRECONDITIONED ? PIPE_RR : PIPE_UU;
+  if (k == 0 && norm == KSP_NORM_NATURAL) return PIPE_NOTHING;      /* res'u is iteration 0's norm already */
+  return PIPE_RU;
+}
+
+static PetscErrorCode KSPSolve_PipeCGHIP(KSP ksp) {
+  PetscErrorCode ierr;
+  KSP_PipeCGHIP *pd = (KSP_PipeCGHIP *)ksp->data;
+  const KSPNormType norm = ksp->normtype;
+  Vec x = ksp->vec_sol, rhs = ksp->vec_rhs;
+  Vec m = ksp->work[0], ABs_rec = ksp->work[1], dir = ksp->work[2], n = ksp->work[3], w = ksp->work[4];
+  Vec Bs_rec = ksp->work[5], u = ksp->work[6], res = ksp->work[7], s = ksp->work[8];
+  Vec normed = norm == KSP_NORM_UNPRECONDITIONED ? res : norm == KSP_NORM_PRECONDITIONED ? u : NULL;
+  const VecSplitReductionOps *S = vec_split_ops(x);
+  const VecPipelinedCGFusedOps *P = pd->fused && S ? vec_pipelined_ops(x) : NULL;   /* a sweep leaves its sums pending in the type's split phase */
+  HipPCKind pck = PCKIND_GENERAL;
+  Vec d = NULL;
+  Mat A;
+  PetscScalar step = 0.0, ratio = 0.0, ru = 0.0, ru_last = 0.0, wu = 0.0;
+  PetscReal rn = 0.0;
+  PetscInt k = 0;
+  PetscBool pending = PETSC_FALSE;    /* the sweep of the iteration before has queued this iteration's sums ... */
+  PetscBool m_formed = PETSC_FALSE;   /* ... and formed m = B w */
+
+  if (norm != KSP_NORM_PRECONDITIONED && norm != KSP_NORM_UNPRECONDITIONED && norm != KSP_NORM_NATURAL && norm != KSP_NORM_NONE) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "norm type %d", (int)norm);
+  ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
+  if (P && P->pipecg_step && !has_null_space(ksp)) { ierr = pc_diagonal_form(ksp, x, &pd->dinv, &pck);CHKERRQ(ierr); if (pck == PCKIND_DIAGONAL) d = pd->dinv; }
+  ksp->its = 0;
+  ierr = start_residual(ksp, A, x, rhs, res);CHKERRQ(ierr);
+  ierr = KSP_PCApply(ksp, res, u);CHKERRQ(ierr);
+  /* iteration 0's norm, its reduction in flight over w <- A u */
+  if (normed) { ierr = split_norm_begin(S, normed, &rn);CHKERRQ(ierr); ierr = split_comm_begin(S, normed);CHKERRQ(ierr); }
+  else if (norm == KSP_NORM_NATURAL) { ierr = split_dot_begin(S, res, u, &ru);CHKERRQ(ierr); ierr = split_comm_begin(S, res);CHKERRQ(ierr); }
+  ierr = KSP_MatMult(ksp, A, u, w);CHKERRQ(ierr);
+  if (normed) { ierr = split_norm_end(S, normed, &rn);CHKERRQ(ierr); }
+  else if (norm == KSP_NORM_NATURAL) { ierr = split_dot_end(S, res, u, &ru);CHKERRQ(ierr); KSPCheckDot(ksp, ru); rn = PetscSqrtReal(PetscAbsScalar(ru)); }
+  ierr = report(ksp, 0, rn);CHKERRQ(ierr);
+  ierr = KSPTestConvergence(ksp, 0, rn);CHKERRQ(ierr);
+  if (ksp->reason) return 0;
+
+  do {
+    const int rides = pipecg_rides(norm, k);
+    PetscBool done = PETSC_FALSE;
+    if (!pending) {
+      if (rides == PIPE_RR || rides == PIPE_UU) { ierr = split_norm_begin(S, normed, &rn);CHKERRQ(ierr); }
+      else if (rides == PIPE_RU) { ierr = split_dot_begin(S, res, u, &ru);CHKERRQ(ierr); }
+      ierr = split_dot_begin(S, w, u, &wu);CHKERRQ(ierr);
+    }
+    ierr = split_comm_begin(S, res);CHKERRQ(ierr);
+    if (!m_formed) { ierr = KSP_PCApply(ksp, w, m);CHKERRQ(ierr); }                     /* the work the reduction hides behind */
+    ierr = KSP_MatMult(ksp, A, m, n);CHKERRQ(ierr);
+    if (rides == PIPE_RR || rides == PIPE_UU) { ierr = split_norm_end(S, normed, &rn);CHKERRQ(ierr); }
+    else if (rides == PIPE_RU) { ierr = split_dot_end(S, res, u, &ru);CHKERRQ(ierr); }
+    ierr = split_dot_end(S, w, u, &wu);CHKERRQ(ierr);
+    pending = PETSC_FALSE; m_formed = PETSC_FALSE;
+    if (k > 0) {
+      if (norm == KSP_NORM_NATURAL) rn = PetscSqrtReal(PetscAbsScalar(ru));
+      else if (norm == KSP_NORM_NONE) rn = 0.0;
+      ierr = report(ksp, k, rn);CHKERRQ(ierr);
+      ierr = KSPTestConvergence(ksp, k, rn);CHKERRQ(ierr);
+      if (ksp->reason) break;
+      ratio = ru / ru_last;
+      step = ru / (wu - ratio / step * ru);
+    } else step = ru / wu;
+    if (P && P->pipecg_step) {
+      /* the whole update, iteration k+1's m and its sums in one sweep; the last permitted iteration has no successor to reduce for */
+      const int next = k + 1 < ksp->max_it ? pipecg_rides(norm, k + 1) : PIPE_NOTHING;
+      ierr = P->pipecg_step(x, u, w, res, ABs_rec, Bs_rec, dir, s, n, m, d, pck != PCKIND_GENERAL ? m : NULL, (PetscBool)(k == 0), k == 0 ? 0.0 : ratio, step, next, &done);CHKERRQ(ierr);
+      if (done) { pending = (PetscBool)(next != PIPE_NOTHING); m_formed = (PetscBool)(pck != PCKIND_GENERAL); pd->nfused++; }
+    }
+    if (!done) {
+      if (k > 0) {
+        ierr = VecAYPX(ABs_rec, ratio, n);CHKERRQ(ierr);
+        ierr = VecAYPX(Bs_rec, ratio, m);CHKERRQ(ierr);
+        ierr = VecAYPX(dir, ratio, u);CHKERRQ(ierr);
+        ierr = VecAYPX(s, ratio, w);CHKERRQ(ierr);
+      } else {
+        ierr = VecCopy(n, ABs_rec);CHKERRQ(ierr);
+        ierr = VecCopy(m, Bs_rec);CHKERRQ(ierr);
+        ierr = VecCopy(u, dir);CHKERRQ(ierr);
+        ierr = VecCopy(w, s);CHKERRQ(ierr);
+      }
+      ierr = VecAXPY(x, step, dir);CHKERRQ(ierr);
+      ierr = VecAXPY(u, -step, Bs_rec);CHKERRQ(ierr);
+      ierr = VecAXPY(w, -step, ABs_rec);CHKERRQ(ierr);
+      ierr = VecAXPY(res, -step, s);CHKERRQ(ierr);
+      pd->nopbyop++;
+    }
+    ru_last = ru;
+    ksp->its = ++k;
+  } while (k < ksp->max_it);
+  if (k >= ksp->max_it) ksp->reason = KSP_DIVERGED_ITS;
+  return 0;
+}
+
+PetscErrorCode KSPCreate_PIPECGHIPMI355X(KSP ksp) {
+  KSP_PipeCGHIP *pd;
+  PetscErrorCode ierr = PetscMalloc(sizeof(*pd), &pd);CHKERRQ(ierr);
+  pd->fused = PETSC_TRUE; pd->dinv = NULL; pd->nfused = 0; pd->nopbyop = 0;
+  ksp->data = pd;
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 1);CHKERRQ(ierr);    /* the four of KSPPIPECG, pipecg.c:199-202 */
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_LEFT, 1);CHKERRQ(ierr);
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_NATURAL, PC_LEFT, 1);CHKERRQ(ierr);
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_NONE, PC_LEFT, 1);CHKERRQ(ierr);
+  ksp->ops->setup = KSPSetUp_PipeCGHIP; ksp->ops->solve = KSPSolve_PipeCGHIP; ksp->ops->setfromoptions = KSPSetFromOptions_PipeCGHIP; ksp->ops->destroy = KSPDestroy_PipeCGHIP;
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "KSPGetFusedStepCounts_PipeCGHIP", (PetscVoidFunction)KSPGetFusedStepCounts_PipeCGHIP);CHKERRQ(ierr);
   return 0;
 }
 

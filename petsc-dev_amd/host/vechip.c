@@ -1108,7 +1108,7 @@ PetscErrorCode VecRichStep_HIPMI355X(Vec x, Vec r, Vec z, Vec w, Vec b, Vec d, P
 #define SR_SLOT0 48      /* device scratch slots of the pending results (ordinary reductions use <= 32 from slot 0) */
 #define SR_HOST0 48      /* where they land in the pinned scratch: clear of what ordinary reductions (<= 32 values) use meanwhile */
 #define SR_MAX 8
-static struct { int n, started, fetched; int kind[SR_MAX]; PetscScalar val[SR_MAX]; Vec owner; mi355x_event_t ev; } sr;
+static struct { int n, started, fetched; int kind[SR_MAX], src[SR_MAX]; PetscScalar val[SR_MAX]; Vec owner; mi355x_event_t ev; } sr;   /* src: the slot End's j-th value sits in */
 static PetscErrorCode sr_queue(Vec x, int kind, const PetscScalar *dx, const PetscScalar *dy) {
   PetscErrorCode ierr; DEVCTX;
   if (sr.started) SETERRQ(HipObjComm(x), PETSC_ERR_ORDER, "Called VecxxxBegin() in a different order or number of times than VecxxxEnd(): a split reduction is still pending");
@@ -1116,8 +1116,23 @@ static PetscErrorCode sr_queue(Vec x, int kind, const PetscScalar *dx, const Pet
   double *slot = HOST_STAGED(x) ? mi355x_handle_host_scratch(dc->h) + SR_HOST0 + sr.n : mi355x_handle_device_scratch(dc->h) + SR_SLOT0 + sr.n;
   if (kind == 0) CHKHIP(mi355x_vec_dot(dc->h, N_(x), dx, dy, slot));
   else CHKHIP(mi355x_vec_norm(dc->h, N_(x), 1, dx, slot));
-  sr.kind[sr.n++] = kind; sr.owner = x;
+  sr.src[sr.n] = sr.n; sr.kind[sr.n++] = kind; sr.owner = x;
   return 0;
+}
+/* A fused sweep that leaves `count` sums of a coming split phase in consecutive slots.  sr_fused_slots: may they be queued, and where
+ * the sweep stores them; sr_fused_queued, after the launch: they are pending as `count` Begin calls of these kinds, in this order, would
+ * have left them, the j-th of them being the sweep's out[from[j]]. */
+static PetscErrorCode sr_fused_slots(Vec x, int count, double **slot) {
+  PetscErrorCode ierr; DEVCTX;
+  if (sr.started) SETERRQ(HipObjComm(x), PETSC_ERR_ORDER, "Called VecxxxBegin() in a different order or number of times than VecxxxEnd(): a split reduction is still pending");
+  if (sr.n + count > SR_MAX) SETERRQ(HipObjComm(x), PETSC_ERR_SUP, "at most %d reductions per split phase", SR_MAX);
+  *slot = HOST_STAGED(x) ? mi355x_handle_host_scratch(dc->h) + SR_HOST0 + sr.n : mi355x_handle_device_scratch(dc->h) + SR_SLOT0 + sr.n;
+  return 0;
+}
+static void sr_fused_queued(Vec x, int count, const int *kind, const int *from) {
+  const int base = sr.n;
+  for (int j = 0; j < count; j++) { sr.src[sr.n] = base + from[j]; sr.kind[sr.n++] = kind[j]; }
+  sr.owner = x;
 }
 static PetscErrorCode VecDotBegin_HIP(Vec x, Vec y, PetscScalar *result) {
   PetscErrorCode ierr; const PetscScalar *dx, *dy;
@@ -1168,13 +1183,13 @@ static PetscErrorCode sr_fetch(Vec x) {
     if (HOST_STAGED(o)) {
       CHKHIP(mi355x_handle_synchronize(dc->h));
       const double *hs = mi355x_handle_host_scratch(dc->h) + SR_HOST0;
-      for (int j = 0; j < sr.n; j++) sr.val[j] = hs[j];
+      for (int j = 0; j < sr.n; j++) sr.val[j] = hs[sr.src[j]];
       if (HipCommAllreduce(HipObjComm(o), sr.val, sr.n, 1, 0)) SETERRQ(HipObjComm(o), PETSC_ERR_LIB, "allreduce failed");
     } else {
       mi355x_handle_t hh = DEVICE_COLLECTIVES(o) ? dc->hcomm : dc->h;
       CHKHIP(mi355x_handle_wait_result(hh)); { PetscErrorCode e_ = HipTriWatchCheck();CHKERRQ(e_); }
       const double *hs = mi355x_handle_host_scratch(hh) + SR_HOST0;
-      for (int j = 0; j < sr.n; j++) sr.val[j] = hs[j];
+      for (int j = 0; j < sr.n; j++) sr.val[j] = hs[sr.src[j]];
       /* the slots may be rewritten by the next phase only after the all-reduce that read them has finished */
       if (DEVICE_COLLECTIVES(o)) { CHKHIP(mi355x_event_record(sr.ev, dc->hcomm)); CHKHIP(mi355x_handle_wait_event(dc->h, sr.ev)); }
     }
@@ -1195,6 +1210,46 @@ static PetscErrorCode VecNormEnd_HIP(Vec x, NormType type, PetscReal *result) {
   PetscErrorCode ierr = sr_take(x, 1, &v);CHKERRQ(ierr);
   *result = PetscSqrtReal(v);                                     /* squares reduced, then rooted (comb.c / pvec2.c:62) */
   return 0;
+}
+
+/* Fused form for KSPSolve_PIPECG (include/petsckrylovfused.h pipecg_step): the eight vector updates behind m = B w and n = A m, the next
+ * m = B w for a diagonal B, and the sums of the next iteration's reduction in one sweep.  The sums are not waited for: they are left
+ * pending as VecNormBegin / VecDotBegin(r, u) followed by VecDotBegin(w, u) would have left them, and the caller's
+ * PetscCommSplitReductionBegin / VecNormEnd / VecDotEnd bring them home.  *done = PETSC_FALSE and nothing touched unless every
+ * operand is a HIPMI355X vector of the same local size and no written vector is another operand (m_next alone may be mv). */
+PetscErrorCode VecPipeCGStep_HIPMI355X(Vec x, Vec u, Vec w, Vec r, Vec zrec, Vec qrec, Vec p, Vec s_, Vec nv, Vec mv, Vec d, Vec m_next,
+                                       PetscBool first, PetscScalar ratio, PetscScalar step, PetscInt rides, PetscBool *done) {
+  PetscErrorCode ierr; DEVCTX;
+  Vec wr[8] = {x, u, w, r, zrec, qrec, p, s_}, all[12] = {x, u, w, r, zrec, qrec, p, s_, nv, mv, d, m_next};
+  PetscScalar *dwr[8], *dm = NULL; const PetscScalar *dnv, *dmv, *dd = NULL; double *out = NULL;
+  *done = PETSC_FALSE;
+  if (rides < 0 || rides > 3) return 0;
+  for (int i = 0; i < 10; i++) if (!all[i]) return 0;
+  for (int i = 0; i < 12; i++) if (all[i] && (!is_hip(all[i]) || all[i]->map->n != x->map->n)) return 0;
+  for (int i = 0; i < 8; i++) for (int j = i + 1; j < 12; j++) if (wr[i] == all[j]) return 0;
+  if (m_next && (m_next == nv || m_next == d)) return 0;
+  if (rides) { ierr = sr_fused_slots(x, 2, &out);CHKERRQ(ierr); }
+  ierr = VecHIPGetRead(nv, &dnv);CHKERRQ(ierr);
+  if (m_next != mv) { ierr = VecHIPGetRead(mv, &dmv);CHKERRQ(ierr); }
+  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
+  for (int i = 0; i < 8; i++) { ierr = VecHIPGetReadWrite(wr[i], &dwr[i]);CHKERRQ(ierr); }
+  if (m_next == mv) { ierr = VecHIPGetReadWrite(m_next, &dm);CHKERRQ(ierr); dmv = dm; }
+  else if (m_next) { ierr = VecHIPGetWrite(m_next, &dm);CHKERRQ(ierr); }
+  CHKHIP(mi355x_vec_pipecg_step(dc->h, N_(x), first ? 1 : 0, ratio, step, dnv, dmv, dd, dwr[4], dwr[5], dwr[6], dwr[7], dwr[0], dwr[1], dwr[2], dwr[3], dm, (int)rides, out));
+  for (int i = 0; i < 8; i++) { VecHIPRestoreWrite(wr[i]); HipStateIncrease(wr[i]); }
+  if (m_next) { VecHIPRestoreWrite(m_next); HipStateIncrease(m_next); }
+  if (rides) {                                                      /* Begin order: what rides, then w'u; the sweep stores w'u first */
+    const int kind[2] = {rides == 3 ? 0 : 1, 0}, from[2] = {1, 0};
+    sr_fused_queued(w, 2, kind, from);
+  }
+  ierr = PetscLogFlops(((first ? 0.0 : 8.0) + (step != 0.0 ? 8.0 : 0.0) + (m_next && d ? 1.0 : 0.0) + (rides ? 4.0 : 0.0)) * x->map->n);CHKERRQ(ierr);
+  *done = PETSC_TRUE;
+  return 0;
+}
+/* "VecPipelinedCGFusedOps_C": the sweeps of the pipelined CG family */
+static const VecPipelinedCGFusedOps *VecPipelinedCGFusedOps_HIP(void) {
+  static const VecPipelinedCGFusedOps ops = {VecPipeCGStep_HIPMI355X};
+  return &ops;
 }
 
 /* the *_local slots of struct _VecOps (vecimpl.h:262-266): the same device reductions without the step across ranks;
@@ -1325,14 +1380,7 @@ static const VecKrylovFusedOps *VecKrylovFusedOps_HIP(void) {
   return &ops;
 }
 /* "VecSplitReductionOps_C": VecDotBegin/End, VecNormBegin/End, PetscCommSplitReductionBegin (comb.c:402-721) with the
- * all-reduce on the halo stream */
-typedef struct {
-  PetscErrorCode (*dot_begin)(Vec, Vec, PetscScalar *);
-  PetscErrorCode (*dot_end)(Vec, Vec, PetscScalar *);
-  PetscErrorCode (*norm_begin)(Vec, NormType, PetscReal *);
-  PetscErrorCode (*norm_end)(Vec, NormType, PetscReal *);
-  PetscErrorCode (*comm_begin)(MPI_Comm);
-} VecSplitReductionOps;
+ * all-reduce on the halo stream (the table: hipmi355ximpl.h) */
 static const VecSplitReductionOps *VecSplitReductionOps_HIP(void) {
   static const VecSplitReductionOps ops = {VecDotBegin_HIP, VecDotEnd_HIP, VecNormBegin_HIP, VecNormEnd_HIP, PetscCommSplitReductionBegin_HIP};
   return &ops;
@@ -1394,6 +1442,7 @@ static PetscErrorCode VecCreate_HIP_common(Vec v, const char *tname) {
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecShareSubArrayEnd_C", "VecShareSubArrayEnd_HIP", (PetscVoidFunction)VecShareSubArrayEnd_HIP);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecKrylovFusedOps_C", "VecKrylovFusedOps_HIP", (PetscVoidFunction)VecKrylovFusedOps_HIP);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecSplitReductionOps_C", "VecSplitReductionOps_HIP", (PetscVoidFunction)VecSplitReductionOps_HIP);CHKERRQ(ierr);
+  ierr = PetscObjectComposeFunction((PetscObject)v, "VecPipelinedCGFusedOps_C", "VecPipelinedCGFusedOps_HIP", (PetscVoidFunction)VecPipelinedCGFusedOps_HIP);CHKERRQ(ierr);
   return 0;
 }
 

@@ -71,6 +71,7 @@ _SIG = {
     "KSPSetFromOptions": [vp], "KSPGMRESSetRestart": [vp, i32], "KSPGMRESSetCGSRefinementType": [vp, i32],
     "KSPChebychevSetEigenvalues": [vp, dbl, dbl], "KSPRichardsonSetScale": [vp, dbl], "KSPMonitorSet": [vp, vp, vp, vp],
     "PCApplyRichardson": [vp, vp, vp, vp, dbl, dbl, dbl, i32, i32, P(i32), P(i32)], "PCApplyRichardsonExists": [vp, P(i32)],
+    "KSPHIPMI355XGetFusedStepCounts": [vp, P(i32), P(i32)],
     "KSPSetUp": [vp], "KSPSolve": [vp, vp, vp], "KSPGetIterationNumber": [vp, P(i32)], "KSPGetResidualNorm": [vp, P(dbl)],
     "KSPGetConvergedReason": [vp, P(i32)], "KSPSetResidualHistory": [vp, vp, i32, i32],
     "KSPGetResidualHistory": [vp, P(vp), P(i32)], "KSPDestroy": [P(vp)],
@@ -469,6 +470,12 @@ class KSP:
     def set_richardson_scale(self, scale):
         """KSPRichardsonSetScale: the damping factor (the richardson types; ignored by any other)"""
         lib().KSPRichardsonSetScale(self.h, float(scale))
+
+    def fused_step_counts(self):
+        """KSPHIPMI355XGetFusedStepCounts: (fused, opbyop) update steps of the pipelined CG types since the type was set; (0, 0) for any other"""
+        f = i32(); o = i32()
+        lib().KSPHIPMI355XGetFusedStepCounts(self.h, C.byref(f), C.byref(o))
+        return f.value, o.value
 
     def record_history(self, n=20000):
         self._hist = np.zeros(n)
