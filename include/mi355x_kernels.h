@@ -431,6 +431,28 @@ int mi355x_ilu0_factor_arrays(mi355x_ilu0_factor_t ctx, const int **bi, const in
 int mi355x_ilu0_factor_to_sweeps(mi355x_handle_t h, mi355x_ilu0_factor_t ctx, const int *iU, const double *ba, double *aL, double *aU, double *dinv);
 int mi355x_ilu0_factor_info(mi355x_ilu0_factor_t ctx, int *lanes, int *nlev);
 
+/* ---- ILU(k): level-of-fill pattern on the host, numeric factorisation on a pattern with fill on the device (csrc/ilu_factor.hip) ----
+ * MatILUFactorSymbolic_SeqAIJ with natural ordering, in the layout of MatILUFactorSymbolic_SeqAIJ_ilu0 that everything above reads (L rows
+ * forward from bi, U rows stored from the last row backwards, the diagonal at bdiag[i], bdiag[n] = bi[n] - 1).
+ *   _iluk_symbolic_host  host arrays, no device call, one thread (row i reads the levels of the U rows before it).  A stored a_ij has
+ *             level 0; row i is built from the sorted list of its columns: for every list column k < i in ascending order, fill that
+ *             entered earlier included, incr = lev(i,k) + 1 and every strict-upper entry (k,j) of row k with lev(k,j) + incr <= levels
+ *             enters the list with that level (an entry already there keeps the smaller one).  levels == 0 is A's own pattern.
+ *             Called twice: with bj == NULL it fills bi[n + 1] and bdiag[n + 1]; with bj (and those two arrays as the first call left
+ *             them) it fills the columns and, with bjlev (may be NULL), every stored entry's level.  bj and bjlev hold bdiag[0] + 2
+ *             ints; the last one is not written.  hipErrorInvalidValue with *bad_row (may be NULL; -1 when no row is at fault) for an
+ *             empty row, a row without its diagonal entry, unsorted columns or columns outside the matrix, and for levels < 0.
+ *   _create_fill  mi355x_ilu0_factor_create for a factor pattern that contains A's: ai_host / aj_host are A's pattern (host).  The
+ *             same layout checks, and every row of A must be a sorted subset of its factor row (hipErrorInvalidValue).  The lanes per
+ *             row come from the widest FACTOR row.  The context serves _reset / _run / _arrays / _to_sweeps / _info / _destroy as
+ *             above; _run then starts every work row from A's entry at the factor's column or +0.0 where A stores none, skips a
+ *             multiplier that is == 0.0 (a fill entry nothing has touched included), and leaves the sequential loop's bits in ba
+ *             (bdiag[0] + 2 doubles, the last one never written). */
+int mi355x_iluk_symbolic_host(int n, const int *ai, const int *aj, int levels, int *bi, int *bdiag, int *bj, int *bjlev, int *bad_row);
+int mi355x_ilu0_factor_create_fill(mi355x_handle_t h, int n, const int *ai_host, const int *aj_host, const int *bi, const int *bj,
+                                   const int *bdiag, int nlev, const int *levptr, const int *rows, int nblk, const int *blk,
+                                   mi355x_ilu0_factor_t *ctx);
+
 /* ---- SOR / SSOR sweeps on a square CSR matrix as it is (csrc/sor.hip) ----
  * MatSOR_SeqAIJ  src/mat/impls/aij/seq/aij.c:1463 with the point sweeps (never the inode routine), level by level: one lane per row, a
  * row's products subtracted in storage order, each product and each difference rounded -- x carries the sequential loop's bits.

@@ -126,6 +126,7 @@ PetscErrorCode PCILUGetShiftCount_HIPMI355X(PC pc, PetscInt *nshift);   /* resta
 PetscErrorCode PCILUGetLevels_HIPMI355X(PC pc, PetscInt *nlevL, PetscInt *nlevU);   /* dependency levels of the two triangular solves */
 PetscErrorCode PCILUGetNodeInfo_HIPMI355X(PC pc, PetscInt *nodes, PetscInt *nlevL, PetscInt *nlevU);   /* node-blocked triangular solves (factor of a matrix with inodes): nodes in the plans (0: row-granular), dependency levels over nodes */
 PetscErrorCode PCILUGetSweeps_HIPMI355X(PC pc, PetscInt *k);   /* Jacobi sweeps per triangular solve (-pc_factor_hipmi355x_trisolve sweeps:<k>, an approximate application); 0: exact solves */
+PetscErrorCode PCILUGetFill_HIPMI355X(PC pc, PetscInt *levels, PetscInt *nz_factor, PetscInt *nz_A);   /* ILU(k): levels of fill of the last factorisation (-pc_factor_levels / PCFactorSetLevels), stored entries of the factor and of the operator */
 PetscErrorCode PCILUGetNumeric_HIPMI355X(PC pc, PetscInt *on_device, PetscInt *symbolic_builds, PetscInt *numeric_runs);   /* 1: the last numeric factorisation ran on the device (-pc_factor_hipmi355x_numeric device); host symbolic passes and numeric factorisations of this factor so far */
 PetscErrorCode PCILUApplyInPlace_HIPMI355X(PC pc, Vec v);   /* v <- factor applied to v, for a sweeps:<k> factor (PCApply / MatSolve refuse identical vectors, as the reference's do) */
 PetscErrorCode PCFactorDebugSetAborted_HIPMI355X(PC pc);   /* tests: raise the "a dependency wait gave up" flag of this PC's sync-free plans */

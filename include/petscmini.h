@@ -350,6 +350,7 @@ PetscErrorCode PCApplyRichardson(PC pc, Vec b, Vec y, Vec w, PetscReal rtol, Pet
 PetscErrorCode PCApplyRichardsonExists(PC pc, PetscBool *exists);
 PetscErrorCode PCSetFromOptions(PC pc);
 PetscErrorCode PCDestroy(PC *pc);
+PetscErrorCode PCFactorSetLevels(PC pc, PetscInt levels);   /* levels of fill of a PCILU / PCICC (factor.c PCFactorSetLevels; -pc_factor_levels); a changed level after set-up has the next set-up redo the symbolic phase */
 PetscErrorCode PCFactorGetMatrix(PC pc, Mat *mat);   /* the factored matrix of a PCILU / PCICC (precon.c PCFactorGetMatrix) */
 PetscErrorCode PCBJacobiGetSubKSP(PC pc, PetscInt *n_local, PetscInt *first_local, KSP **ksp);
 

@@ -37,11 +37,25 @@ static PetscErrorCode PCFactorSetIndependentBlocks_Factor(PC pc, PetscInt nblk, 
   return 0;
 }
 
+/* PCFactorSetLevels (factor.c) over PCFactorSetLevels_ILU (ilu.c): before the first set-up the level is noted; a different level
+ * afterwards has the next set-up run the symbolic phase again (the reference resets the PC) */
+PetscErrorCode PCFactorSetLevels(PC pc, PetscInt levels) {
+  if (!pc) SETERRQ(0, PETSC_ERR_ARG_NULL, "Null PC");
+  if (levels < 0) SETERRQ(pc->comm, PETSC_ERR_ARG_OUTOFRANGE, "negative levels");
+  if (pc->ops->getfactoredmatrix != PCFactorGetMatrix_Factor) return 0;   /* (PetscTryMethod: other PC types ignore the call) */
+  PC_Factor *f = (PC_Factor *)pc->data;
+  if (f->info.levels == (PetscReal)levels) return 0;
+  f->info.levels = (PetscReal)levels;
+  f->symbolic_done = 0;
+  if (pc->setupcalled == 2) pc->setupcalled = 1;
+  return 0;
+}
+
 static PetscErrorCode PCSetFromOptions_Factor(PC pc) {   /* factor.c PCSetFromOptions_Factor, ilu.c:110-150: the options the path uses */
   PC_Factor *f = (PC_Factor *)pc->data;
   PetscErrorCode ierr; PetscInt iv; PetscBool set; char t[64]; PetscReal r;
   ierr = PetscOptionsGetInt(pc->prefix, "-pc_factor_levels", &iv, &set);CHKERRQ(ierr);
-  if (set) f->info.levels = iv;
+  if (set) { ierr = PCFactorSetLevels(pc, iv);CHKERRQ(ierr); }
   ierr = PetscOptionsGetString(pc->prefix, "-pc_factor_shift_type", t, sizeof(t), &set);CHKERRQ(ierr);
   if (set) {
     if (!strcmp(t, "none") || !strcmp(t, "NONE")) f->info.shifttype = (PetscReal)MAT_SHIFT_NONE;

@@ -144,7 +144,8 @@ typedef struct {
  * the role of Mat_SeqAIJCUSPARSETriFactors, src/mat/impls/aij/seq/seqcusparse/cusparsematimpl.h) ---- */
 typedef struct {
   MatFactorType kind;                                      /* MAT_FACTOR_ILU or MAT_FACTOR_ICC */
-  PetscInt n, nz;
+  PetscInt n, nz;                                          /* rows; stored entries of the FACTOR (the operator's with zero fill) */
+  PetscInt levels, nzA;                                    /* ILU(k): the levels of fill of the last factorisation and the operator's entry count */
   /* one member per form of the factor; releasing a form frees its members and zeroes it (host/ilu.c, "releasing a factor") */
   /* ILU(0): host factor in the reference's L / reversed-U layout (aijfact.c:1628-1700); owns: ours (harness), or the arrays of F's own Mat_SeqAIJ (inside PETSc) */
   struct { PetscInt *bi, *bj, *bdiag; PetscScalar *ba; PetscBool owns; } host;
@@ -176,8 +177,9 @@ typedef struct {
   /* -pc_factor_hipmi355x_numeric device: the numeric factorisation runs on the device (mi355x_ilu0_factor_*), level by level, into
    * launch.d_ba.  The context is built once per pattern; with it stay the host pattern (host.bi / bj / bdiag), the row levels
    * (lev.rlevL / rlevU) and what the level-launch solves borrow from it (launch.borrowed).  gen / n / nz: the serial number of the
-   * operator's pattern upload (Mat_SeqAIJHIP.pattern_gen) and its sizes at the time -- what "the pattern of the last factorisation" is told by */
-  struct { mi355x_ilu0_factor_t dfac; int stale; unsigned long long gen; PetscInt n, nz, nblk, *blk; } dev;
+   * operator's pattern upload (Mat_SeqAIJHIP.pattern_gen) and its sizes at the time, levels: the levels of fill the factor's pattern was built
+   * with -- what "the pattern of the last factorisation" is told by */
+  struct { mi355x_ilu0_factor_t dfac; int stale; unsigned long long gen; PetscInt n, nz, levels, nblk, *blk; } dev;
   PetscInt symbolic_builds, numeric_runs;                  /* host symbolic passes / numeric factorisations so far (both routes) */
   int aborted;                                             /* a sync-free application of this factor gave up at some time (kept over re-factorisations) */
   PetscInt nshift;                                         /* restarts / shifts the factorisation took (largest count over the blocks) */

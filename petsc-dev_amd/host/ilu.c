@@ -169,7 +169,8 @@ static PetscErrorCode level_order(PetscInt n, const PetscInt *lev, PetscInt nlev
 }
 
 static PetscErrorCode natural_ordering_only(Mat A, IS row, IS col, const MatFactorInfo *info, const char *what) {
-  if (info->levels != 0.0) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "%s(%d): only zero fill is on the ported path", what, (int)info->levels);
+  if (info->levels != 0.0 && strcmp(what, "ILU")) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "%s(%d): only zero fill is on the ported path", what, (int)info->levels);   /* ILU(k): ilu_symbolic_host below */
+  if (info->levels < 0.0) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_OUTOFRANGE, "Levels of fill negative %d", (int)info->levels);
 #if defined(PETSCHIPMI355X_WITH_PETSC)
   { PetscErrorCode ierr; PetscBool id = PETSC_TRUE;
     if (row) { ierr = ISIdentity(row, &id);CHKERRQ(ierr); if (!id) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "%s on the device: natural ordering only (-pc_factor_mat_ordering_type natural)", what); }
@@ -399,6 +400,43 @@ static PetscErrorCode ilu0_symbolic_host(Mat A, PetscInt n, const PetscInt *ai, 
   if (adiag_out) *adiag_out = adiag; else HipFree(adiag);
   return 0;
 }
+/* MatILUFactorSymbolic_SeqAIJ (levels of fill, natural ordering) for the harness: f->host.bi / bj / bdiag (ours) in the same layout,
+ * from the kernel library's host routine (mi355x_iluk_symbolic_host: one thread, the rows depend on each other in sequence) */
+static PetscErrorCode iluk_symbolic_host(Mat A, PetscInt n, const PetscInt *ai, const PetscInt *aj, PetscInt levels, HipTriFactors *f) {
+  PetscErrorCode ierr;
+  int bad = -1, rc;
+  f->host.owns = PETSC_TRUE;
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(n + 1), &f->host.bi);CHKERRQ(ierr);
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(n + 1), &f->host.bdiag);CHKERRQ(ierr);
+  rc = mi355x_iluk_symbolic_host(n, ai, aj, levels, f->host.bi, f->host.bdiag, NULL, NULL, &bad);
+  if (!rc) {
+    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(f->host.bdiag[0] + 2), &f->host.bj);CHKERRQ(ierr);
+    f->host.bj[f->host.bdiag[0] + 1] = 0;                      /* (the slot past the last column: compared with the sweep form's copy, never read as a column) */
+    rc = mi355x_iluk_symbolic_host(n, ai, aj, levels, f->host.bi, f->host.bdiag, f->host.bj, NULL, &bad);
+  }
+  if (rc == 1 && bad >= 0 && bad < n) {                        /* hipErrorInvalidValue: the row at fault */
+    PetscBool diag = PETSC_FALSE;
+    for (PetscInt q = ai[bad]; q < ai[bad + 1]; q++) if (aj[q] == bad) diag = PETSC_TRUE;
+    if (!diag) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "Matrix is missing diagonal entry %d", bad);
+    SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "ILU(%d): the columns of row %d are not sorted inside the matrix", levels, bad);
+  }
+  CHKHIP(rc);
+  return 0;
+}
+/* the factor's pattern for the level of fill asked for.  Zero fill is ilu0_symbolic_host as it always was */
+static PetscErrorCode ilu_symbolic_host(Mat A, PetscInt n, const PetscInt *ai, const PetscInt *aj, PetscInt levels, HipTriFactors *f, PetscInt **adiag_out, const char *diag_phase, double *clock) {
+  PetscErrorCode ierr;
+  f->levels = levels; f->nzA = ai[n];
+  if (!levels) {
+    ierr = ilu0_symbolic_host(A, n, ai, aj, f, adiag_out, diag_phase, clock);CHKERRQ(ierr);
+    f->nz = ai[n];
+  } else {
+    if (adiag_out) *adiag_out = NULL;
+    ierr = iluk_symbolic_host(A, n, ai, aj, levels, f);CHKERRQ(ierr);
+    f->nz = f->host.bdiag[0] + 1;
+  }
+  return 0;
+}
 /* MatILUFactorSymbolic_SeqAIJ_ilu0 + MatLUFactorNumeric_SeqAIJ restated for the harness (inside a PETSc tree the parent's
  * routines run instead): the pattern (ilu0_symbolic_host); row by row with a dense work row, pivots stored inverted
  * (aijfact.c:505-570); MatPivotCheck_nz's restarts (ilu0_next_shift) */
@@ -408,8 +446,8 @@ static PetscErrorCode ilu0_factor_host(Mat F, Mat A, const MatFactorInfo *info) 
   PetscInt n, *adiag, whole[2]; const PetscInt *ai, *aj, *blk; const PetscScalar *aa;
   double tick0 = HipWallSeconds();
   ierr = MatSeqAIJGetArrays(A, &n, &ai, &aj, &aa);CHKERRQ(ierr);
-  f->n = n; f->nz = ai[n];
-  ierr = ilu0_symbolic_host(A, n, ai, aj, f, &adiag, "factor: diagonal positions", &tick0);CHKERRQ(ierr);
+  f->n = n;
+  ierr = ilu_symbolic_host(A, n, ai, aj, (PetscInt)info->levels, f, &adiag, "factor: diagonal positions", &tick0);CHKERRQ(ierr);   /* f->nz: the factor's entries */
   ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)(f->nz + 1), &f->host.ba);
   if (ierr) { HipFree(adiag); CHKERRQ(ierr); }
   f->host.ba[f->nz] = 0.0;                 /* (every other entry is written by the numeric pass) */
@@ -699,10 +737,13 @@ static PetscErrorCode ilu0_syncfree_plans(Mat F, Mat A, HipTriFactors *f, PetscD
     ra.rpU = ra.rlL + n; ra.rlU = ra.rpU + n;
     HipParallelRanges(n, ilu0_row_arrays, &ra);
     HipSetupNote("ILU(0): ... row arrays + inode query at %.3f s\n", HipWallSeconds() - ta0);
-    if (nodes > 0 && !(nset && (!strcmp(nodeopt, "0") || !strcmp(nodeopt, "false")))) ierr = ilu0_node_plans(F, f, dc, nodes, nsizes, set ? !strcmp(ord, "level") : 1, &ra, ta0, &made);
+    /* ILU(k): the node plans take a node's shared column list from A's inodes, which says nothing about the factor's rows once
+     * there is fill, so they stay ILU(0)-only: the factor gets the row-granular plans, in column order unless the option asks otherwise -- the bits of MatSolve_SeqAIJ_NaturalOrdering; where the
+     * reference would install its inode routines the two agree to rounding */
+    if (nodes > 0 && !f->levels && !(nset && (!strcmp(nodeopt, "0") || !strcmp(nodeopt, "false")))) ierr = ilu0_node_plans(F, f, dc, nodes, nsizes, set ? !strcmp(ord, "level") : 1, &ra, ta0, &made);
   }
   if (!ierr && !made) {
-    f->syncfree.by_level = set ? !strcmp(ord, "level") : (nodes > 0);
+    f->syncfree.by_level = set ? !strcmp(ord, "level") : (nodes > 0 && !f->levels);
     rc = mi355x_trisolve_plan_create_pair(dc->h, n, f->syncfree.by_level, f->lev.nlevL, f->lev.rlevL, ra.bi, ra.rlL, f->host.bj, ra.ba, f->lev.nlevU, f->lev.rlevU, ra.rpU, ra.rlU, f->host.bj, ra.ba, ra.dinv, NULL, &f->syncfree.tri_lo, &f->syncfree.tri_up);
   }
   HipFree(ra.rlL); HipFree(ra.dinv);
@@ -775,7 +816,7 @@ static PetscErrorCode ilu0_analyse_and_upload(Mat F, Mat A) {
 }
 
 /* the device route's symbolic side, once per pattern: pattern and row levels on the host (kept), the context, the array of the values */
-static PetscErrorCode ilu0_device_symbolic(Mat F, Mat A, PetscDeviceCtx *dc, PetscInt nblk, const PetscInt *blk, double *clock) {
+static PetscErrorCode ilu0_device_symbolic(Mat F, Mat A, PetscDeviceCtx *dc, PetscInt levels, PetscInt nblk, const PetscInt *blk, double *clock) {
   PetscErrorCode ierr;
   HipTriFactors *f = HipTriGet(F);
   PetscInt n, *levptr = NULL, *rows = NULL; const PetscInt *ai, *aj;
@@ -784,24 +825,27 @@ static PetscErrorCode ilu0_device_symbolic(Mat F, Mat A, PetscDeviceCtx *dc, Pet
   tri_free_sweeps(f);
   f->n = n; f->nz = ai[n];
 #if defined(PETSCHIPMI355X_WITH_PETSC)
-  { Mat_SeqAIJ *b = (Mat_SeqAIJ *)F->data;   /* the parent's symbolic arrays (MatILUFactorSymbolic_SeqAIJ_ilu0) */
-    f->nz = b->nz; f->host.bi = b->i; f->host.bj = b->j; f->host.bdiag = b->diag; f->host.ba = b->a; f->host.owns = PETSC_FALSE; }
+  { Mat_SeqAIJ *b = (Mat_SeqAIJ *)F->data;   /* the parent's symbolic arrays (MatILUFactorSymbolic_SeqAIJ_ilu0, or MatILUFactorSymbolic_SeqAIJ with levels of fill) */
+    f->nz = b->nz; f->host.bi = b->i; f->host.bj = b->j; f->host.bdiag = b->diag; f->host.ba = b->a; f->host.owns = PETSC_FALSE;
+    f->levels = levels; f->nzA = ai[n]; }
 #else
-  ierr = ilu0_symbolic_host(A, n, ai, aj, f, NULL, NULL, NULL);CHKERRQ(ierr);
+  ierr = ilu_symbolic_host(A, n, ai, aj, levels, f, NULL, NULL, NULL);CHKERRQ(ierr);
 #endif
   HipSetupTick(*clock, "factor (device): pattern of L and U");
   ierr = ilu0_check_blocks(A, ai, aj, nblk, blk);CHKERRQ(ierr);
   ierr = ilu0_row_levels(n, f->host.bi, f->host.bj, f->host.bdiag, &f->lev.rlevL, &f->lev.nlevL, &f->lev.rlevU, &f->lev.nlevU);CHKERRQ(ierr);
   ierr = level_order(n, f->lev.rlevL, f->lev.nlevL, &levptr, &rows);CHKERRQ(ierr);
   HipSetupTick(*clock, "factor (device): levels of L and U");
-  int rc = mi355x_ilu0_factor_create(dc->h, n, f->host.bi, f->host.bj, f->host.bdiag, f->lev.nlevL, levptr, rows, nblk, blk, &f->dev.dfac);
+  /* zero fill: position p of A's row IS position p of the factor's row, the ILU(0) kernel; with fill the kernel that finds A's entries by column */
+  int rc = levels ? mi355x_ilu0_factor_create_fill(dc->h, n, ai, aj, f->host.bi, f->host.bj, f->host.bdiag, f->lev.nlevL, levptr, rows, nblk, blk, &f->dev.dfac)
+                  : mi355x_ilu0_factor_create(dc->h, n, f->host.bi, f->host.bj, f->host.bdiag, f->lev.nlevL, levptr, rows, nblk, blk, &f->dev.dfac);
   HipFree(levptr); HipFree(rows);
   if (!rc) rc = mi355x_malloc((void **)&f->launch.d_ba, sizeof(PetscScalar) * (size_t)(f->nz + 1));
   if (!rc) rc = mi355x_memset(dc->h, f->launch.d_ba, 0, sizeof(PetscScalar) * (size_t)(f->nz + 1));   /* (the slot past the last value is never written) */
   CHKHIP(rc);
   ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(nblk + 1), &f->dev.blk);CHKERRQ(ierr);
   memcpy(f->dev.blk, blk, sizeof(PetscInt) * (size_t)(nblk + 1));
-  f->dev.gen = ((Mat_SeqAIJHIP *)A->spptr)->pattern_gen; f->dev.n = n; f->dev.nz = ai[n]; f->dev.nblk = nblk; f->dev.stale = 0;
+  f->dev.gen = ((Mat_SeqAIJHIP *)A->spptr)->pattern_gen; f->dev.n = n; f->dev.nz = ai[n]; f->dev.levels = levels; f->dev.nblk = nblk; f->dev.stale = 0;
   f->symbolic_builds++;
   HipSetupTick(*clock, "factor (device): context and index upload");
   return 0;
@@ -856,12 +900,12 @@ static PetscErrorCode ilu0_factor_device(Mat F, Mat A, const MatFactorInfo *info
   HipSetupTick(tick0, "factor (device): operator current");
   const PetscInt nblk = HipTriFactorsBlocks(f, n, whole, &blk);
   const int same = f->dev.dfac && !f->dev.stale && d->pattern_gen && f->dev.gen == d->pattern_gen && f->dev.n == n && f->dev.nz == ai[n] &&
-                   f->dev.nblk == nblk && !memcmp(f->dev.blk, blk, sizeof(PetscInt) * (size_t)(nblk + 1));
+                   f->dev.levels == (PetscInt)info->levels && f->dev.nblk == nblk && !memcmp(f->dev.blk, blk, sizeof(PetscInt) * (size_t)(nblk + 1));
   f->factored_state = -1;
   if (same) {   /* values only: the plans that carry values go, everything built from the pattern stays */
     tri_free_syncfree(f);
     f->nshift = 0; f->sw.sweeps = 0;
-  } else { ierr = ilu0_device_symbolic(F, A, dc, nblk, blk, &tick0);CHKERRQ(ierr); }
+  } else { ierr = ilu0_device_symbolic(F, A, dc, (PetscInt)info->levels, nblk, blk, &tick0);CHKERRQ(ierr); }
   ierr = ilu0_device_numeric(A, f, dc, nblk, info, &tick0);CHKERRQ(ierr);
 #if defined(PETSCHIPMI355X_WITH_PETSC)
   ierr = ilu0_fetch_host_ba(f, dc);CHKERRQ(ierr);                        /* the parent's b->a holds the factor, as after its own routine */
@@ -889,7 +933,8 @@ static PetscErrorCode MatLUFactorNumeric_SeqAIJHIP(Mat F, Mat A, const MatFactor
 #if defined(PETSCHIPMI355X_WITH_PETSC)
     ierr = MatLUFactorNumeric_SeqAIJ(F, A, info);CHKERRQ(ierr);            /* the parent's factorisation into F's own Mat_SeqAIJ */
     { Mat_SeqAIJ *b = (Mat_SeqAIJ *)F->data;
-      f->n = A->rmap->n; f->nz = b->nz; f->host.bi = b->i; f->host.bj = b->j; f->host.bdiag = b->diag; f->host.ba = b->a; f->host.owns = PETSC_FALSE; }
+      f->n = A->rmap->n; f->nz = b->nz; f->host.bi = b->i; f->host.bj = b->j; f->host.bdiag = b->diag; f->host.ba = b->a; f->host.owns = PETSC_FALSE;
+      f->levels = (PetscInt)info->levels; f->nzA = ((Mat_SeqAIJ *)A->data)->nz; }
 #else
     ierr = ilu0_factor_host(F, A, info);CHKERRQ(ierr);
 #endif
@@ -1003,7 +1048,7 @@ static PetscErrorCode MatDestroy_Factor_SeqAIJHIP(Mat F) {   /* the factor's dev
 PetscErrorCode MatGetFactor_seqaijhipmi355x_petsc(Mat A, MatFactorType ftype, Mat *B) {   /* MatGetFactor_seqaij_cusparse, aijcusparse.cu:57-75 */
   PetscErrorCode ierr;
   HipTriFactors *f;
-  if (ftype != MAT_FACTOR_ILU && ftype != MAT_FACTOR_ICC) SETERRQ(PETSC_COMM_SELF, PETSC_ERR_SUP, "Factor type not supported for HIPMI355X matrix types (ILU(0) and ICC(0) are)");
+  if (ftype != MAT_FACTOR_ILU && ftype != MAT_FACTOR_ICC) SETERRQ(PETSC_COMM_SELF, PETSC_ERR_SUP, "Factor type not supported for HIPMI355X matrix types (ILU(k) and ICC(0) are)");
   ierr = PetscMalloc(sizeof(*f), &f);CHKERRQ(ierr);
   memset(f, 0, sizeof(*f));
   f->kind = ftype; f->factored_state = -1;
@@ -1070,6 +1115,16 @@ PetscErrorCode PCILUGetNumeric_HIPMI355X(PC pc, PetscInt *on_device, PetscInt *s
   if (on_device) *on_device = f->dev.dfac ? 1 : 0;
   if (symbolic_builds) *symbolic_builds = f->symbolic_builds;
   if (numeric_runs) *numeric_runs = f->numeric_runs;
+  return 0;
+}
+/* ILU(k): the levels of fill of the last factorisation (-pc_factor_levels / PCFactorSetLevels), the stored entries of the factor (L, the
+ * diagonal and U) and those of the operator it was made from */
+PetscErrorCode PCILUGetFill_HIPMI355X(PC pc, PetscInt *levels, PetscInt *nz_factor, PetscInt *nz_A) {
+  HipTriFactors *f;
+  PetscErrorCode ierr = pc_factors(pc, MAT_FACTOR_ILU, &f);CHKERRQ(ierr);
+  if (levels) *levels = f->levels;
+  if (nz_factor) *nz_factor = f->nz;
+  if (nz_A) *nz_A = f->nzA;
   return 0;
 }
 /* v <- the factor's application to v, input and result in ONE vector.  PCApply and MatSolve refuse identical vectors as the
