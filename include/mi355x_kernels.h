@@ -196,6 +196,22 @@ int mi355x_vec_rich_step(mi355x_handle_t h, size_t n, double scale, const double
 int mi355x_vec_pipecg_step(mi355x_handle_t h, size_t n, int first, double ratio, double step, const double *nv, const double *mv, const double *d,
                            double *zrec, double *qrec, double *p, double *s, double *x, double *u, double *w, double *r, double *m_next,
                            int rides, double *out);
+/* The two sweeps of an iteration of KSPSolve_MINRES (src/ksp/ksp/impls/minres/minres.c) behind r = A u and alpha = u'r, with the bits of
+ * mi355x_vec_pointwise_mult, mi355x_vec_axpy, mi355x_vec_copy, mi355x_vec_scale and mi355x_vec_dot run one call at a time.
+ * lanczos:  d != NULL: z = r .* d (PCApply_Jacobi, z not read); d == NULL: z as given;
+ *           r = r + (-alpha) v ; z = z + (-alpha) u ; r = r + (-beta) vold ; z = z + (-beta) uold   (in this order; alpha == 0 / beta == 0:
+ *           that pair untouched and v, u / vold, uold not loaded);  out[0] = sum r*z over the updated vectors (for an aligned view the tree
+ *           of mi355x_vec_dot), out[1] = alpha;  out: device or the handle's pinned scratch;  n == 0: { 0, alpha }.
+ *           alpha_dev != NULL: alpha is read from device memory (what mi355x_vec_dot left there) and the host argument is ignored.
+ * update:   wn = u ; wn = wn + (-rho2) w ; wn = wn + (-rho3) wold ; wn = irho1 wn, stored over wold ; x = x + ceta wn ;
+ *           vnew = ibeta r ; unew = ibeta z.   rho2 / rho3 / ceta == 0: that AXPY skipped, its operand not loaded (ceta == 0: x untouched);
+ *           irho1, ibeta: mi355x_vec_scale's cases (0: zeros, nothing loaded; 1: a copy).  first != 0 (the solve start): vnew and unew
+ *           alone, nothing else read or written (u, w, wold, x may be NULL).  A pure map: nothing reduced.
+ * No written vector is another operand of the same call (wold is read and written in place).  A missing vector: nonzero, nothing touched. */
+int mi355x_vec_minres_lanczos(mi355x_handle_t h, size_t n, double alpha, const double *alpha_dev, double beta, const double *d, double *r, double *z,
+                              const double *v, const double *u, const double *vold, const double *uold, double *out);
+int mi355x_vec_minres_update(mi355x_handle_t h, size_t n, int first, double rho2, double rho3, double irho1, double ceta, double ibeta,
+                             const double *u, const double *w, double *wold, double *x, const double *r, const double *z, double *vnew, double *unew);
 /* VecMDot_Seq         src/vec/vec/impls/seq/dvec2.c:146     out[j] = sum_i x_i y_j,i , j<nv ; x read once per 16 y's */
 int mi355x_vec_mdot(mi355x_handle_t h, size_t n, int nv, const double *x, const double *const *y, double *out);
 /* KSPGMRESCycle fusions (gmres.c:118-209, borthog2.c:60-66): x += sum_j sign*coef_dev[j]*y_j in VecMAXPY_Seq's grouping with

@@ -37,6 +37,7 @@ extern "C" {
 #define KSPCHEBYCHEVHIPMI355X  "chebychevhipmi355x"    /* needs vectors whose type offers "cheby_step" (include/petsckrylovfused.h): PETSC_ERR_SUP at set-up otherwise */
 #define KSPRICHARDSONHIPMI355X "richardsonhipmi355x"
 #define KSPPIPECGHIPMI355X  "pipecghipmi355x"          /* KSPPIPECG with the vector work of an iteration in one sweep ("VecPipelinedCGFusedOps_C") */
+#define KSPMINRESHIPMI355X  "minreshipmi355x"          /* KSPMINRES with two sweeps per iteration; needs vectors that offer "VecMinresFusedOps_C": PETSC_ERR_SUP at set-up otherwise */
 
 /* One call after PetscInitialize (or a PetscDLLibraryRegister entry, src/sys/dll): registers the types above with
  * VecRegister / MatRegister / PCRegister.  On the harness the same constructors are also registered under the
@@ -115,7 +116,8 @@ PetscErrorCode MatHIPMI355XGetBlockedInfo(Mat A, PetscInt *bs, PetscInt *nblocks
 PetscErrorCode MatHIPMI355XGetTiledInfo(Mat A, PetscInt *staged, PetscInt *remainder);   /* column-tiled product (x tiles in LDS): nonzeros gathering from LDS / left to the row-block kernel; 0, 0: not in use */
 PetscErrorCode MatHIPMI355XGetRowPatterns(Mat A, PetscInt *npat);   /* 0: none; else the size of the row-pattern dictionary the SpMV runs with */
 PetscErrorCode MatHIPMI355XSetValuePatterns(Mat A, PetscBool on);   /* A/B switch for one matrix until its next upload (the option -mat_hipmi355x_value_patterns decides at every upload) */
-/* the pipelined CG types: update steps taken in one fused sweep / through the public Vec calls, since the KSP took its type (any other type: 0, 0) */
+/* the pipelined CG types: update steps taken in one fused sweep / through the public Vec calls, since the KSP took its type;
+ * minreshipmi355x: (Lanczos sweeps run, 0); any other type: 0, 0 */
 PetscErrorCode KSPHIPMI355XGetFusedStepCounts(KSP ksp, PetscInt *fused, PetscInt *opbyop);
 PetscErrorCode VecHIPMI355XSetCGUpdateTiming(PetscBool on);   /* hipEvent pairs around the fused CG update (bench.py's roofline for that kernel) */
 PetscErrorCode VecHIPMI355XGetCGUpdateTiming(PetscInt *nlaunches, PetscLogDouble *total_ms);

@@ -58,6 +58,23 @@ typedef struct {
                                 PetscBool first, PetscScalar ratio, PetscScalar step, PetscInt rides, PetscBool *done);
 } VecPipelinedCGFusedOps;
 typedef const VecPipelinedCGFusedOps *(*VecPipelinedCGFusedOpsGetFn)(void);
+/* "VecMinresFusedOps_C" on a Vec returns the two sweeps of a MINRES iteration (KSPSolve_MINRES, minres.c), a third table.  *done =
+ * PETSC_FALSE and nothing touched when a sweep refuses its operands: a vector of another type, unequal local sizes, or a written
+ * vector that is another operand of the call. */
+typedef struct {
+  /* Behind r = A u and alpha = u'r:  d != NULL: z = d .* r (PCApply_Jacobi; z is not read), d == NULL: z as KSP_PCApply left it;
+   *   r -= alpha v ; z -= alpha u ; r -= beta vold ; z -= beta uold (VecAXPY x4 in this order) ; *dp = r'z (VecDot, all-reduced).
+   * alpha_on_device: alpha is what tdot_begin(u, r) of "VecKrylovFusedOps_C" left on the device and the argument is ignored; either
+   * way *alpha_out returns the value the sweep used, with the one wait that brings *dp. */
+  PetscErrorCode (*minres_lanczos)(Vec r, Vec z, Vec v, Vec u, Vec vold, Vec uold, Vec d, PetscScalar alpha, PetscBool alpha_on_device, PetscScalar beta,
+                                   PetscScalar *dp, PetscScalar *alpha_out, PetscBool *done);
+  /* wold = (u - rho2 w - rho3 wold) irho1 (VecCopy, VecAXPY x2, VecScale: the new W, the caller rotates its three names) ;
+   * x += ceta wold (VecAXPY) ; vnew = ibeta r ; unew = ibeta z (VecCopy + VecScale x2).  first: vnew and unew alone (the solve start;
+   * x, u, w, wold may be NULL).  Nothing is reduced and the host does not wait. */
+  PetscErrorCode (*minres_update)(Vec x, Vec u, Vec w, Vec wold, Vec r, Vec z, Vec vnew, Vec unew, PetscBool first,
+                                  PetscScalar rho2, PetscScalar rho3, PetscScalar irho1, PetscScalar ceta, PetscScalar ibeta, PetscBool *done);
+} VecMinresFusedOps;
+typedef const VecMinresFusedOps *(*VecMinresFusedOpsGetFn)(void);
 typedef PetscErrorCode (*MatMultTDotBeginFn)(Mat A, Vec x, Vec y, PetscBool *ok);
 typedef PetscErrorCode (*MatMultDiagonalScaleFn)(Mat A, Vec d, Vec x, Vec y, PetscBool *ok);
 

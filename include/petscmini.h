@@ -136,6 +136,7 @@ typedef const char *PCType;
 #define KSPGROPPCG "groppcg"   /* Gropp's overlapped CG (src/ksp/ksp/impls/cg/groppcg/groppcg.c), SURVEY 8f.4 */
 #define KSPCHEBYCHEV  "chebychev"    /* Chebyshev iteration with given eigenvalue bounds (src/ksp/ksp/impls/cheby/cheby.c) */
 #define KSPRICHARDSON "richardson"   /* (damped) Richardson iteration (src/ksp/ksp/impls/rich/rich.c) */
+#define KSPMINRES  "minres"    /* minimum residual method for symmetric indefinite operators (src/ksp/ksp/impls/minres/minres.c) */
 #define PCNONE     "none"
 #define PCJACOBI   "jacobi"
 #define PCBJACOBI  "bjacobi"

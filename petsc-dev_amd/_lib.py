@@ -77,6 +77,8 @@ KERNEL_API = {
     "mi355x_vec_cheby_step": [vp, sz, dbl, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, i32, vp],
     "mi355x_vec_rich_step": [vp, sz, dbl, vp, vp, vp, vp, vp, vp],
     "mi355x_vec_pipecg_step": [vp, sz, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
+    "mi355x_vec_minres_lanczos": [vp, sz, dbl, vp, dbl, vp, vp, vp, vp, vp, vp, vp, vp],
+    "mi355x_vec_minres_update": [vp, sz, i32, dbl, dbl, dbl, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp],
     "mi355x_handle_publish": [vp, vp, i32],
     "mi355x_handle_publish_at": [vp, vp, i32, i32],
     "mi355x_vec_cg_update_dev": [vp, sz, dbl, vp, dbl, i32, vp, vp, vp, vp, vp, vp, vp, i32],

@@ -1038,6 +1038,137 @@ __global__ __launch_bounds__(MI355X_BLOCK) void pipecg_step_kernel(PipeCGStepF f
     [&](size_t k) { double uv, wv, rv; f.at1(k, uv, wv, rv); });
 }
 
+// ---- the two sweeps of a MINRES iteration (KSPSolve_MINRES, src/ksp/ksp/impls/minres/minres.c) behind r = A u and alpha = u'r.
+// MinresLanczosF, under launch_reduce:
+//   z = r .* d                                           (PCApply_Jacobi: OpMul; d == NULL: z is taken as given)
+//   r = r + (-alpha) v ; z = z + (-alpha) u ; r = r + (-beta) vold ; z = z + (-beta) uold     (VecAXPY x4 in this order: OpAxpy;
+//                                                        alpha == 0 / beta == 0: that pair is skipped, as mi355x_vec_axpy returns at once)
+//   out = { sum r*z , alpha }                            (VecDot(r, z) over the updated vectors; alpha rides home as lane 0's only term)
+// alpha comes from the host or, alpha_dev != NULL, from the device slot the dot before left it in.  Each product and sum is rounded as
+// in those kernels and a lane meets its elements in DotF's order: every output carries the bits of the separate launches.  An operand a
+// special case skips is not loaded, a vector no case changes is not stored.
+// Streaming (see nt_load2), a choice by analogy with PipeCGStepF, not a measurement: d, vold and uold have their only reader
+// of the iteration here (the update sweep overwrites the two buffers) and are non-temporal at every size; r (just written by the
+// product), z, v and u (read again by the update sweep or the next Lanczos sweep) stay cacheable below 256 MiB and are streamed from
+// there on like every other tile kernel.
+__device__ __forceinline__ double scale_elem(double al, double xv) {      // mi355x_vec_scale's cases: 0 -> VecSet(0), 1 -> nothing
+  return al == 0.0 ? 0.0 : (al == 1.0 ? xv : OpScale{al}(xv, 0.0, 0.0));
+}
+struct MinresLanczosF {
+  double alpha, beta;
+  const double *alpha_dev, *d, *v, *u, *vold, *uold;
+  double *r, *z;
+  int big;
+  __device__ __forceinline__ double al() const { return alpha_dev ? *alpha_dev : alpha; }
+  __device__ __forceinline__ void prologue(size_t tid, double (&acc)[2]) const {
+    if (tid == 0) acc[1] = al();
+  }
+  __device__ __forceinline__ void one(double a, double dv, double vv, double uv, double vo, double uo, double &rv, double &zv) const {
+    if (d) zv = OpMul{}(rv, dv, 0.0);
+    if (a != 0.0) { rv = OpAxpy{-a}(vv, rv, 0.0); zv = OpAxpy{-a}(uv, zv, 0.0); }
+    if (beta != 0.0) { rv = OpAxpy{-beta}(vo, rv, 0.0); zv = OpAxpy{-beta}(uo, zv, 0.0); }
+  }
+  __device__ __forceinline__ void at2(size_t i, double a, double2 &rv, double2 &zv) const {
+    double2 dv = {}, vv = {}, uv = {}, vo = {}, uo = {};
+    zv = double2{};
+    ldq_tile1(r, i, big, rv);
+    if (d) ldq_tile1(d, i, 1, dv); else ldq_tile1(z, i, big, zv);
+    if (a != 0.0) { ldq_tile1(v, i, big, vv); ldq_tile1(u, i, big, uv); }
+    if (beta != 0.0) { ldq_tile1(vold, i, 1, vo); ldq_tile1(uold, i, 1, uo); }
+    one(a, dv.x, vv.x, uv.x, vo.x, uo.x, rv.x, zv.x);
+    one(a, dv.y, vv.y, uv.y, vo.y, uo.y, rv.y, zv.y);
+    const bool moved = a != 0.0 || beta != 0.0;
+    if (moved) stq(reinterpret_cast<double2 *>(r) + i, rv, big);
+    if (moved || d) stq(reinterpret_cast<double2 *>(z) + i, zv, big);
+  }
+  __device__ __forceinline__ void at1(size_t k, double a, double &rv, double &zv) const {
+    rv = r[k]; zv = d ? 0.0 : z[k];
+    one(a, d ? d[k] : 0.0, a != 0.0 ? v[k] : 0.0, a != 0.0 ? u[k] : 0.0, beta != 0.0 ? vold[k] : 0.0, beta != 0.0 ? uold[k] : 0.0, rv, zv);
+    const bool moved = a != 0.0 || beta != 0.0;
+    if (moved) r[k] = rv;
+    if (moved || d) z[k] = zv;
+  }
+  template <int NOUT_>
+  __device__ __forceinline__ void sweep(size_t tid, size_t stride, size_t n2, double (&acc)[NOUT_]) const {
+    const double a = al();
+    for (size_t i = tid; i < n2; i += stride) {
+      double2 rv, zv;
+      at2(i, a, rv, zv);
+      acc[0] += rv.x * zv.x;
+      acc[0] += rv.y * zv.y;
+    }
+  }
+  __device__ __forceinline__ void accum1(size_t k, double (&acc)[2]) const {
+    double rv, zv;
+    at1(k, al(), rv, zv);
+    acc[0] += rv * zv;
+  }
+};
+template <> struct has_prologue<MinresLanczosF> { static constexpr bool value = true; };
+
+// MinresUpdateF, a pure map (nothing reduced, no host wait):
+//   wn = u ; wn = wn + (-rho2) w ; wn = wn + (-rho3) wold ; wn = irho1 wn     (VecCopy, VecAXPY x2 in this order, VecScale; wn is stored
+//                                                        over wold: the caller rotates (WOOLD, WOLD, W) <- (WOLD, W, that buffer))
+//   x = x + ceta wn                                      (VecAXPY; ceta == 0: x neither read nor written)
+//   vnew = ibeta r ; unew = ibeta z                      (VecCopy + VecScale x2, into the buffers of the old VOLD / UOLD)
+// first != 0, the solve start: the last line alone.  mi355x_vec_axpy's alpha == 0 and mi355x_vec_scale's 0 -> VecSet(0), 1 -> nothing
+// are honoured, and an operand a special case skips is not loaded (irho1 == 0: none of u, w, wold).
+// Streaming, by the same analogy: x, r and z have their only reader of the iteration here (the next product overwrites r, the next
+// preconditioner z) and wold is read for the last time: non-temporal loads at every size, and so is x's store.  u and w (next
+// iteration's UOLD and WOLD), the new W, vnew (read by the next Lanczos sweep) and unew (gathered by the next product) stay cacheable
+// below 256 MiB.
+struct MinresUpdateF {
+  double rho2, rho3, irho1, ceta, ibeta;
+  const double *u, *w, *r, *z;
+  double *wold, *x, *vnew, *unew;
+  int first, big;
+  __device__ __forceinline__ bool reads_u() const { return !first && irho1 != 0.0; }
+  __device__ __forceinline__ bool reads_w() const { return reads_u() && rho2 != 0.0; }
+  __device__ __forceinline__ bool reads_wold() const { return reads_u() && rho3 != 0.0; }
+  __device__ __forceinline__ bool steps() const { return !first && ceta != 0.0; }
+  __device__ __forceinline__ bool reads_rz() const { return ibeta != 0.0; }
+  __device__ __forceinline__ void one(double uv, double wv, double wo, double rv, double zv, double &wn, double &xv, double &vn, double &un) const {
+    if (!first) {
+      double t = uv;
+      if (rho2 != 0.0) t = OpAxpy{-rho2}(wv, t, 0.0);
+      if (rho3 != 0.0) t = OpAxpy{-rho3}(wo, t, 0.0);
+      wn = scale_elem(irho1, t);
+      if (ceta != 0.0) xv = OpAxpy{ceta}(wn, xv, 0.0);
+    }
+    vn = scale_elem(ibeta, rv); un = scale_elem(ibeta, zv);
+  }
+  // the U double2's of a lane in its tile; every load is issued before the first store
+  template <int U>
+  __device__ __forceinline__ void tile(size_t i) const {
+    double2 uv[U] = {}, wv[U] = {}, wo[U] = {}, rv[U] = {}, zv[U] = {}, xv[U] = {}, wn[U] = {}, vn[U], un[U];
+    if (reads_u()) ldq_tile(u, i, big, uv);
+    if (reads_w()) ldq_tile(w, i, big, wv);
+    if (reads_wold()) ldq_tile(wold, i, 1, wo);
+    if (steps()) ldq_tile(x, i, 1, xv);
+    if (reads_rz()) { ldq_tile(r, i, 1, rv); ldq_tile(z, i, 1, zv); }
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      one(uv[j].x, wv[j].x, wo[j].x, rv[j].x, zv[j].x, wn[j].x, xv[j].x, vn[j].x, un[j].x);
+      one(uv[j].y, wv[j].y, wo[j].y, rv[j].y, zv[j].y, wn[j].y, xv[j].y, vn[j].y, un[j].y);
+    }
+    if (!first) stq_tile(wold, i, big, wn);
+    if (steps()) stq_tile(x, i, 1, xv);
+    stq_tile(vnew, i, big, vn); stq_tile(unew, i, big, un);
+  }
+  __device__ __forceinline__ void at1(size_t k) const {
+    double wn = 0.0, xv = steps() ? x[k] : 0.0, vn, un;
+    one(reads_u() ? u[k] : 0.0, reads_w() ? w[k] : 0.0, reads_wold() ? wold[k] : 0.0, reads_rz() ? r[k] : 0.0, reads_rz() ? z[k] : 0.0, wn, xv, vn, un);
+    if (!first) wold[k] = wn;
+    if (steps()) x[k] = xv;
+    vnew[k] = vn; unew[k] = un;
+  }
+};
+__global__ __launch_bounds__(MI355X_BLOCK) void minres_update_kernel(MinresUpdateF f, size_t n, int vec_ok) {
+  tile_walk<2>(n, vec_ok,
+    [&](size_t i, auto u) { f.template tile<decltype(u)::value>(i); },
+    [&](size_t k) { f.at1(k); });
+}
+
 template <int NV>
 struct MDotF {
   const double *x;
@@ -1326,6 +1457,21 @@ int mi355x_vec_pipecg_step(mi355x_handle_t h, size_t n, int first, double ratio,
   if (out) return launch_reduce<2, RED_SUM>(h, f, n, vec_ok, out);                      // n == 0: zeros
   if (n == 0) return 0;
   return launch_tiles(h, n, vec_ok, pipecg_step_kernel, pipecg_step_kernel, f);
+}
+
+int mi355x_vec_minres_lanczos(mi355x_handle_t h, size_t n, double alpha, const double *alpha_dev, double beta, const double *d, double *r, double *z,
+                              const double *v, const double *u, const double *vold, const double *uold, double *out) {
+  if (!r || !z || !v || !u || !vold || !uold || !out) return (int)hipErrorInvalidValue;
+  const MinresLanczosF f{alpha, beta, alpha_dev, d, v, u, vold, uold, r, z, vec_streams(n)};
+  return launch_reduce<2, RED_SUM>(h, f, n, all_aligned16(d, r, z, v, u, vold, uold), out);   // d == NULL counts as aligned; n == 0: { 0, alpha }
+}
+int mi355x_vec_minres_update(mi355x_handle_t h, size_t n, int first, double rho2, double rho3, double irho1, double ceta, double ibeta,
+                             const double *u, const double *w, double *wold, double *x, const double *r, const double *z, double *vnew, double *unew) {
+  if (!r || !z || !vnew || !unew || (!first && (!u || !w || !wold || !x))) return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  if (first) { u = w = nullptr; wold = x = nullptr; }                                        // not touched: their alignment does not count
+  const MinresUpdateF f{rho2, rho3, irho1, ceta, ibeta, u, w, r, z, wold, x, vnew, unew, first != 0, vec_streams(n)};
+  return launch_tiles(h, n, all_aligned16(u, w, wold, x, r, z, vnew, unew), minres_update_kernel, minres_update_kernel, f);
 }
 
 // borthog2.c:63-64 + the norm of gmres.c:146: x += sum_j sign * coef_dev[j] * y_j, *out = sum x_new^2 (out: device or the

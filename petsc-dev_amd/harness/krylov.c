@@ -13,6 +13,7 @@
  *   BiCGStab      src/ksp/ksp/impls/bcgs/bcgs.c:43-160
  *   Chebyshev     src/ksp/ksp/impls/cheby/cheby.c (KSPSolve_Chebychev; eigenvalue bounds from the user, no estimation)
  *   Richardson    src/ksp/ksp/impls/rich/rich.c (KSPSolve_Richardson; fixed scale, no self-scaling), PCApplyRichardson precon.c, sor.c
+ *   MINRES        src/ksp/ksp/impls/minres/minres.c (KSPSolve_MINRES)
  * and are written here over a few shared pieces: one checkpoint routine (history, monitor, convergence test), one start-residual
  * routine for the CG family, index-addressed Hessenberg columns for GMRES. */
 #include "petscimpl.h"
@@ -797,5 +798,97 @@ PetscErrorCode KSPCreate_Richardson(KSP ksp) {   /* rich.c KSPCreate_Richardson:
   ksp->ops->setfromoptions = KSPSetFromOptions_Richardson;
   ksp->ops->destroy = KSPDestroy_Richardson;
   OK(PetscObjectComposeFunction((PetscObject)ksp, "KSPRichardsonSetScale_C", "KSPRichardsonSetScale_Richardson", (PetscVoidFunction)KSPRichardsonSetScale_Richardson));
+  return 0;
+}
+
+/* ================================================================== MINRES (minres.c KSPSolve_MINRES), symmetric indefinite operators
+ * The preconditioned Lanczos recurrence over (R, Z) with the two previous pairs (V, U), (VOLD, UOLD), one Givens rotation per step
+ * applied to the last column of the tridiagonal matrix, and the three-term recurrence of the search direction W.  Left preconditioning
+ * with the preconditioned norm only; the preconditioner must be positive definite.  The residual norm is the recurrence's estimate
+ * rnorm |s|, never recomputed.  dp = r'z below 1e-18 ends the solve (at the start: KSP_DIVERGED_INDEFINITE_MAT; in the loop, before x
+ * is updated: KSP_DIVERGED_INDEFINITE_PC) -- also on a lucky breakdown, when the Krylov space is exhausted and x is already exact:
+ * the reference does the same. */
+static PetscErrorCode KSPSetUp_MINRES(KSP ksp) { return KSPDefaultGetWork(ksp, 9); }
+
+static PetscErrorCode KSPSolve_MINRES(KSP ksp) {
+  const PetscReal haptol = 1.e-18;
+  Vec X = ksp->vec_sol, B = ksp->vec_rhs;
+  Vec R = ksp->work[0], Z = ksp->work[1], U = ksp->work[2], V = ksp->work[3], W = ksp->work[4];
+  Vec UOLD = ksp->work[5], VOLD = ksp->work[6], WOLD = ksp->work[7], WOOLD = ksp->work[8];
+  Mat A = ksp->pc->mat;
+  PetscScalar alpha, beta, betaold, eta, c = 1.0, cold = 1.0, coold, s = 0.0, sold = 0.0, soold, rho0, rho1, rho2, rho3, dp = 0.0;
+  PetscReal np;
+  PetscInt i;
+
+  ksp->its = 0;
+  OK(VecSet(UOLD, 0.0));
+  OK(VecCopy(UOLD, VOLD));
+  OK(VecCopy(UOLD, W));
+  OK(VecCopy(UOLD, WOLD));
+  OK(cg_family_start(ksp, A, X, B, R));                             /* R <- B - A X */
+  OK(KSP_PCApply(ksp, R, Z));
+  OK(VecNorm(Z, NORM_2, &np));
+  OK(VecDot(R, Z, &dp));
+  if (dp < haptol) { ksp->reason = KSP_DIVERGED_INDEFINITE_MAT; return 0; }
+  dp = PetscAbsScalar(dp);
+  dp = PetscSqrtReal(dp);
+  beta = dp;
+  eta = beta;
+  OK(VecCopy(R, V));
+  OK(VecCopy(Z, U));
+  OK(VecScale(V, 1.0 / beta));
+  OK(VecScale(U, 1.0 / beta));
+  OK(checkpoint(ksp, 0, np));
+  if (ksp->reason) return 0;
+
+  for (i = 0; i < ksp->max_it; i++) {
+    ksp->its = i + 1;
+    /* Lanczos */
+    OK(KSP_MatMult(ksp, A, U, R));
+    OK(VecDot(U, R, &alpha));
+    OK(KSP_PCApply(ksp, R, Z));
+    OK(VecAXPY(R, -alpha, V));
+    OK(VecAXPY(Z, -alpha, U));
+    OK(VecAXPY(R, -beta, VOLD));
+    OK(VecAXPY(Z, -beta, UOLD));
+    betaold = beta;
+    OK(VecDot(R, Z, &dp));
+    if (dp < haptol) { ksp->reason = KSP_DIVERGED_INDEFINITE_PC; break; }
+    dp = PetscAbsScalar(dp);
+    beta = PetscSqrtReal(dp);
+    /* QR factorisation */
+    coold = cold; cold = c; soold = sold; sold = s;
+    rho0 = cold * alpha - coold * sold * betaold;
+    rho1 = PetscSqrtReal(rho0 * rho0 + beta * beta);
+    rho2 = sold * alpha + coold * cold * betaold;
+    rho3 = soold * betaold;
+    c = rho0 / rho1;
+    s = beta / rho1;
+    /* search direction and solution */
+    OK(VecCopy(WOLD, WOOLD));
+    OK(VecCopy(W, WOLD));
+    OK(VecCopy(U, W));
+    OK(VecAXPY(W, -rho2, WOLD));
+    OK(VecAXPY(W, -rho3, WOOLD));
+    OK(VecScale(W, 1.0 / rho1));
+    OK(VecAXPY(X, c * eta, W));
+    eta = -s * eta;
+    OK(VecCopy(V, VOLD));
+    OK(VecCopy(U, UOLD));
+    OK(VecCopy(R, V));
+    OK(VecCopy(Z, U));
+    OK(VecScale(V, 1.0 / beta));
+    OK(VecScale(U, 1.0 / beta));
+    np = ksp->rnorm * PetscAbsScalar(s);
+    OK(checkpoint(ksp, i + 1, np));
+    if (ksp->reason) break;
+  }
+  if (i >= ksp->max_it) ksp->reason = KSP_DIVERGED_ITS;
+  return 0;
+}
+PetscErrorCode KSPCreate_MINRES(KSP ksp) {   /* minres.c KSPCreate_MINRES */
+  ksp->normsupporttable[KSP_NORM_PRECONDITIONED][PC_LEFT] = 2;
+  ksp->ops->setup = KSPSetUp_MINRES;
+  ksp->ops->solve = KSPSolve_MINRES;
   return 0;
 }

@@ -49,6 +49,7 @@ PetscErrorCode PetscMiniInitialize(void) {
   ierr = KSPRegister(KSPPREONLY, 0, "KSPCreate_PREONLY", KSPCreate_PREONLY);CHKERRQ(ierr);
   ierr = KSPRegister(KSPCHEBYCHEV, 0, "KSPCreate_Chebychev", KSPCreate_Chebychev);CHKERRQ(ierr);
   ierr = KSPRegister(KSPRICHARDSON, 0, "KSPCreate_Richardson", KSPCreate_Richardson);CHKERRQ(ierr);
+  ierr = KSPRegister(KSPMINRES, 0, "KSPCreate_MINRES", KSPCreate_MINRES);CHKERRQ(ierr);
   return 0;
 }
 

@@ -361,5 +361,6 @@ PetscErrorCode KSPCreate_BCGSHIPMI355X(KSP);
 PetscErrorCode KSPCreate_ChebychevHIPMI355X(KSP);
 PetscErrorCode KSPCreate_RichardsonHIPMI355X(KSP);
 PetscErrorCode KSPCreate_PIPECGHIPMI355X(KSP);
+PetscErrorCode KSPCreate_MINRESHIPMI355X(KSP);
 
 #endif

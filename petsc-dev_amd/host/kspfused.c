@@ -7,13 +7,14 @@
  *     KSPCHEBYCHEVHIPMI355X  "chebychevhipmi355x"   Chebyshev  (the sequence of KSPCHEBYCHEV,  src/ksp/ksp/impls/cheby/cheby.c)
  *     KSPRICHARDSONHIPMI355X "richardsonhipmi355x"  Richardson (the sequence of KSPRICHARDSON, src/ksp/ksp/impls/rich/rich.c)
  *     KSPPIPECGHIPMI355X     "pipecghipmi355x"      pipelined CG (the sequence of KSPPIPECG, src/ksp/ksp/impls/cg/pipecg/pipecg.c:49-205)
+ *     KSPMINRESHIPMI355X     "minreshipmi355x"      MINRES     (the sequence of KSPMINRES,  src/ksp/ksp/impls/minres/minres.c)
  *
  * They compute what the reference's solvers compute -- same iterates, same residual history, same exits, bit for bit against
  * the op-by-op sequences (tests/test_host_gpu.py) -- but group the vector work between two reductions into the fused sweeps a
  * Vec / Mat type may offer by name ("VecKrylovFusedOps_C", "MatMultTDotBegin_C", "MatMultDiagonalScale_C";
  * include/petsckrylovfused.h), keep scalars that only the device needs on the device, and queue the front half of the next
  * iteration before the host has looked at the residual norm.  On vectors of a type without those methods every step falls
- * back to the public Vec / Mat / PC calls, so the types work on any PETSc objects -- with ONE exception: chebychevhipmi355x.  The
+ * back to the public Vec / Mat / PC calls, so the types work on any PETSc objects -- with TWO exceptions: minreshipmi355x (see there) and chebychevhipmi355x.  The
  * three-term Chebyshev update needs VecScale, which is not among the calls this library takes from PETSc, so there is nothing to fall
  * back to: KSPSetUp of that type returns PETSC_ERR_SUP on vectors whose type lacks "cheby_step" and names -ksp_type chebychev.
  *
@@ -950,6 +951,130 @@ PetscErrorCode KSPCreate_PIPECGHIPMI355X(KSP ksp) {
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_NONE, PC_LEFT, 1);CHKERRQ(ierr);
   ksp->ops->setup = KSPSetUp_PipeCGHIP; ksp->ops->solve = KSPSolve_PipeCGHIP; ksp->ops->setfromoptions = KSPSetFromOptions_PipeCGHIP; ksp->ops->destroy = KSPDestroy_PipeCGHIP;
   ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "KSPGetFusedStepCounts_PipeCGHIP", (PetscVoidFunction)KSPGetFusedStepCounts_PipeCGHIP);CHKERRQ(ierr);
+  return 0;
+}
+
+/* ================================================================================================ MINRES
+ * The sequence of KSPSolve_MINRES (src/ksp/ksp/impls/minres/minres.c): left preconditioning, the preconditioned norm, the residual
+ * estimate rnorm |s| of the recurrence, the exits at r'z < 1e-18 (also taken on a lucky breakdown, as the reference takes them); same
+ * iterates, histories and exits as the op-by-op type, bit for bit.  Behind the product an iteration is TWO sweeps of
+ * "VecMinresFusedOps_C" (include/petsckrylovfused.h) instead of 2 dots, 7 VecAXPY, 7 VecCopy, 3 VecScale and PCApply_Jacobi:
+ *   - alpha = u'r through tdot_begin where the vectors accept it: VecDot's bits, left on the device, no wait (VecDot otherwise);
+ *   - the Lanczos sweep: Jacobi, the four AXPYs and r'z, which comes home with alpha in the iteration's one wait;
+ *   - the Givens scalars on the host;
+ *   - the update sweep: the new search direction, x, and the next Lanczos pair scaled into the buffers of the pair that drops out.
+ * The copies of the reference are pointer rotations here: (V, VOLD), (U, UOLD) and (W, WOLD) swap after every update, and WOOLD is
+ * never needed (the update reads the old WOLD in place before it stores the new W over it).  Any PC but Jacobi, or a null space:
+ * KSP_PCApply forms z and the Lanczos sweep takes it as given.  The solve start is the public calls but for its two VecScale, which
+ * are the `first` form of the update sweep: VecScale is not among the calls this library takes from PETSc, so like chebychevhipmi355x
+ * the type has no op-by-op route and KSPSetUp returns PETSC_ERR_SUP on vectors without the table (-ksp_type minres is that route).
+ * KSPHIPMI355XGetFusedStepCounts: (Lanczos sweeps run, 0). */
+typedef struct { Vec dinv; PetscInt nsweeps; } KSP_MinresHIP;
+
+static const VecMinresFusedOps *vec_minres_ops(Vec x) {
+  PetscVoidFunction f = NULL;
+  if (PetscObjectQueryFunction((PetscObject)x, "VecMinresFusedOps_C", &f) || !f) return NULL;
+  return ((VecMinresFusedOpsGetFn)f)();
+}
+static PetscErrorCode KSPGetFusedStepCounts_MinresHIP(KSP ksp, PetscInt *fused, PetscInt *opbyop) {
+  *fused = ((const KSP_MinresHIP *)ksp->data)->nsweeps; *opbyop = 0;
+  return 0;
+}
+static PetscErrorCode KSPSetUp_MinresHIP(KSP ksp) {
+  PetscErrorCode ierr = KSPDefaultGetWork(ksp, 8);CHKERRQ(ierr);
+  const VecMinresFusedOps *M = vec_minres_ops(ksp->vec_sol ? ksp->vec_sol : ksp->work[0]);   /* the vectors the solve will run on */
+  if (!M || !M->minres_lanczos || !M->minres_update) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s needs vectors whose type offers the fused MINRES sweeps (\"VecMinresFusedOps_C\"); use -ksp_type minres on these vectors", KSPMINRESHIPMI355X);
+  return 0;
+}
+static PetscErrorCode KSPDestroy_MinresHIP(KSP ksp) {
+  KSP_MinresHIP *md = (KSP_MinresHIP *)ksp->data;
+  PetscErrorCode ierr;
+  if (!md) return 0;
+  ierr = VecDestroy(&md->dinv);CHKERRQ(ierr);
+  HipFree(md); ksp->data = NULL;
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
+  return 0;
+}
+
+static PetscErrorCode KSPSolve_MinresHIP(KSP ksp) {
+  PetscErrorCode ierr;
+  KSP_MinresHIP *md = (KSP_MinresHIP *)ksp->data;
+  const PetscReal haptol = 1.e-18;
+  Vec X = ksp->vec_sol, B = ksp->vec_rhs;
+  Vec R = ksp->work[0], Z = ksp->work[1], U = ksp->work[2], V = ksp->work[3], W = ksp->work[4], UOLD = ksp->work[5], VOLD = ksp->work[6], WOLD = ksp->work[7];
+  const VecMinresFusedOps *M = vec_minres_ops(X);
+  const VecKrylovFusedOps *F = vec_fused_ops(X);
+  HipPCKind pck = PCKIND_GENERAL;
+  Vec d = NULL;
+  Mat A;
+  PetscScalar alpha = 0.0, beta, betaold, eta, c = 1.0, cold = 1.0, coold, s = 0.0, sold = 0.0, soold, rho0, rho1, rho2, rho3, dp = 0.0;
+  PetscReal np;
+  PetscInt i;
+  PetscBool done;
+
+  if (!M || !M->minres_lanczos || !M->minres_update) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s needs vectors whose type offers the fused MINRES sweeps; use -ksp_type minres on these vectors", KSPMINRESHIPMI355X);
+  ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
+  if (!has_null_space(ksp)) { ierr = pc_diagonal_form(ksp, X, &md->dinv, &pck);CHKERRQ(ierr); if (pck == PCKIND_DIAGONAL) d = md->dinv; }
+  ksp->its = 0;
+  ierr = VecSet(UOLD, 0.0);CHKERRQ(ierr);
+  ierr = VecCopy(UOLD, VOLD);CHKERRQ(ierr);
+  ierr = VecCopy(UOLD, W);CHKERRQ(ierr);
+  ierr = VecCopy(UOLD, WOLD);CHKERRQ(ierr);
+  ierr = start_residual(ksp, A, X, B, R);CHKERRQ(ierr);
+  ierr = KSP_PCApply(ksp, R, Z);CHKERRQ(ierr);
+  ierr = VecNorm(Z, NORM_2, &np);CHKERRQ(ierr);
+  ierr = VecDot(R, Z, &dp);CHKERRQ(ierr);
+  if (dp < haptol) { ksp->reason = KSP_DIVERGED_INDEFINITE_MAT; return 0; }
+  beta = PetscSqrtReal(PetscAbsScalar(dp));
+  eta = beta;
+  ierr = M->minres_update(NULL, NULL, NULL, NULL, R, Z, V, U, PETSC_TRUE, 0.0, 0.0, 0.0, 0.0, 1.0 / beta, &done);CHKERRQ(ierr);   /* V = R / beta, U = Z / beta */
+  if (!done) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "the fused MINRES sweep refused these vectors; use -ksp_type minres");
+  ierr = report(ksp, 0, np);CHKERRQ(ierr);
+  ierr = KSPTestConvergence(ksp, 0, np);CHKERRQ(ierr);
+  if (ksp->reason) return 0;
+
+  for (i = 0; i < ksp->max_it; i++) {
+    PetscBool on_device = PETSC_FALSE;
+    ksp->its = i + 1;
+    ierr = KSP_MatMult(ksp, A, U, R);CHKERRQ(ierr);
+    if (F && F->tdot_begin) { ierr = F->tdot_begin(U, R, &on_device);CHKERRQ(ierr); }
+    if (!on_device) { ierr = VecDot(U, R, &alpha);CHKERRQ(ierr); }
+    if (!d) { ierr = KSP_PCApply(ksp, R, Z);CHKERRQ(ierr); }
+    ierr = M->minres_lanczos(R, Z, V, U, VOLD, UOLD, d, alpha, on_device, beta, &dp, &alpha, &done);CHKERRQ(ierr);
+    if (!done) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "the fused MINRES sweep refused these vectors; use -ksp_type minres");
+    md->nsweeps++;
+    betaold = beta;
+    if (dp < haptol) { ksp->reason = KSP_DIVERGED_INDEFINITE_PC; break; }
+    beta = PetscSqrtReal(PetscAbsScalar(dp));
+    coold = cold; cold = c; soold = sold; sold = s;
+    rho0 = cold * alpha - coold * sold * betaold;
+    rho1 = PetscSqrtReal(rho0 * rho0 + beta * beta);
+    rho2 = sold * alpha + coold * cold * betaold;
+    rho3 = soold * betaold;
+    c = rho0 / rho1;
+    s = beta / rho1;
+    /* the new W over the old WOLD, x, and the new (V, U) into the buffers of (VOLD, UOLD); then the names rotate */
+    ierr = M->minres_update(X, U, W, WOLD, R, Z, VOLD, UOLD, PETSC_FALSE, rho2, rho3, 1.0 / rho1, c * eta, 1.0 / beta, &done);CHKERRQ(ierr);
+    if (!done) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "the fused MINRES sweep refused these vectors; use -ksp_type minres");
+    { Vec t = W; W = WOLD; WOLD = t; t = V; V = VOLD; VOLD = t; t = U; U = UOLD; UOLD = t; }
+    eta = -s * eta;
+    np = ksp->rnorm * PetscAbsScalar(s);
+    ierr = report(ksp, i + 1, np);CHKERRQ(ierr);
+    ierr = KSPTestConvergence(ksp, i + 1, np);CHKERRQ(ierr);
+    if (ksp->reason) break;
+  }
+  if (i >= ksp->max_it) ksp->reason = KSP_DIVERGED_ITS;
+  return 0;
+}
+
+PetscErrorCode KSPCreate_MINRESHIPMI355X(KSP ksp) {
+  KSP_MinresHIP *md;
+  PetscErrorCode ierr = PetscMalloc(sizeof(*md), &md);CHKERRQ(ierr);
+  md->dinv = NULL; md->nsweeps = 0;
+  ksp->data = md;
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);    /* the one of KSPMINRES */
+  ksp->ops->setup = KSPSetUp_MinresHIP; ksp->ops->solve = KSPSolve_MinresHIP; ksp->ops->destroy = KSPDestroy_MinresHIP;
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "KSPGetFusedStepCounts_MinresHIP", (PetscVoidFunction)KSPGetFusedStepCounts_MinresHIP);CHKERRQ(ierr);
   return 0;
 }
 

@@ -1252,6 +1252,75 @@ static const VecPipelinedCGFusedOps *VecPipelinedCGFusedOps_HIP(void) {
   return &ops;
 }
 
+/* Fused forms for KSPSolve_MINRES (include/petsckrylovfused.h minres_lanczos, minres_update).  *done = PETSC_FALSE and nothing touched
+ * unless every operand is a HIPMI355X vector of the same local size and no written vector is another operand of the call.
+ * The Lanczos sweep: PCApply_Jacobi (d), the four VecAXPY and VecDot(r, z) behind r = A u and alpha = u'r.  alpha_on_device: alpha is
+ * what VecTDotBegin_HIPMI355X(u, r) left in slot DPI_SLOT (all-reduced there over RCCL), never fetched before; it comes home beside
+ * r'z, so the iteration has one wait.  r'z is all-reduced as every fused reduction is (reduce_finish2: RCCL, host-staged or one rank);
+ * alpha rides along as it is, being the same number on every rank already. */
+PetscErrorCode VecMinresLanczos_HIPMI355X(Vec r, Vec z, Vec v, Vec u, Vec vold, Vec uold, Vec d, PetscScalar alpha, PetscBool alpha_on_device, PetscScalar beta,
+                                          PetscScalar *dp, PetscScalar *alpha_out, PetscBool *done) {
+  PetscErrorCode ierr; DEVCTX;
+  Vec all[7] = {r, z, v, u, vold, uold, d};
+  const PetscScalar *dv, *du, *dvo, *duo, *dd = NULL; PetscScalar *dr, *dz, res[2]; double *out;
+  *done = PETSC_FALSE;
+  for (int i = 0; i < 6; i++) if (!all[i]) return 0;
+  for (int i = 0; i < 7; i++) if (all[i] && (!is_hip(all[i]) || all[i]->map->n != r->map->n)) return 0;
+  if (r == z) return 0;
+  for (int j = 2; j < 7; j++) if (all[j] == r || all[j] == z) return 0;
+  if (alpha_on_device && HOST_STAGED(r)) return 0;                     /* VecTDotBegin refuses there: nothing can be in the slot */
+  ierr = VecHIPGetRead(v, &dv);CHKERRQ(ierr);
+  ierr = VecHIPGetRead(u, &du);CHKERRQ(ierr);
+  ierr = VecHIPGetRead(vold, &dvo);CHKERRQ(ierr);
+  ierr = VecHIPGetRead(uold, &duo);CHKERRQ(ierr);
+  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
+  ierr = VecHIPGetReadWrite(r, &dr);CHKERRQ(ierr);
+  if (d) { ierr = VecHIPGetWrite(z, &dz);CHKERRQ(ierr); }
+  else { ierr = VecHIPGetReadWrite(z, &dz);CHKERRQ(ierr); }
+  ierr = reduce_target(r, dc, &out);CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_minres_lanczos(dc->h, N_(r), alpha, alpha_on_device ? mi355x_handle_device_scratch(dc->h) + DPI_SLOT : NULL, beta, dd, dr, dz, dv, du, dvo, duo, out));
+  VecHIPRestoreWrite(r); VecHIPRestoreWrite(z);
+  HipStateIncrease(r); HipStateIncrease(z);
+  ierr = reduce_finish2(r, dc, 1, 2, 0, res);CHKERRQ(ierr);
+  *dp = res[0]; *alpha_out = res[1];
+  ierr = PetscLogFlops(((d ? 1.0 : 0.0) + 10.0) * r->map->n);CHKERRQ(ierr);   /* n + 4 x 2n + 2n */
+  *done = PETSC_TRUE;
+  return 0;
+}
+/* The update sweep: the new search direction over wold's storage, x, and the next Lanczos pair scaled into vnew / unew; first: the
+ * two scales of the solve start alone.  A pure map: nothing comes back to the host. */
+PetscErrorCode VecMinresUpdate_HIPMI355X(Vec x, Vec u, Vec w, Vec wold, Vec r, Vec z, Vec vnew, Vec unew, PetscBool first,
+                                         PetscScalar rho2, PetscScalar rho3, PetscScalar irho1, PetscScalar ceta, PetscScalar ibeta, PetscBool *done) {
+  PetscErrorCode ierr; DEVCTX;
+  Vec wr[4] = {vnew, unew, wold, x}, all[8] = {vnew, unew, wold, x, u, w, r, z};
+  const int nwr = first ? 2 : 4;
+  const PetscScalar *du = NULL, *dw = NULL, *dr, *dz; PetscScalar *dwo = NULL, *dx = NULL, *dvn, *dun;
+  *done = PETSC_FALSE;
+  if (first) { all[2] = all[3] = all[4] = all[5] = NULL; }             /* not touched, so not looked at */
+  if (!vnew || !unew || !r || !z) return 0;
+  for (int i = 2; i < 6; i++) if (!first && !all[i]) return 0;
+  for (int i = 0; i < 8; i++) if (all[i] && (!is_hip(all[i]) || all[i]->map->n != vnew->map->n)) return 0;
+  for (int i = 0; i < nwr; i++) for (int j = 0; j < 8; j++) if (j != i && all[j] && wr[i] == all[j]) return 0;
+  if (!first) { ierr = VecHIPGetRead(u, &du);CHKERRQ(ierr); ierr = VecHIPGetRead(w, &dw);CHKERRQ(ierr); }
+  ierr = VecHIPGetRead(r, &dr);CHKERRQ(ierr);
+  ierr = VecHIPGetRead(z, &dz);CHKERRQ(ierr);
+  if (!first) { ierr = VecHIPGetReadWrite(wold, &dwo);CHKERRQ(ierr); ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr); }
+  ierr = VecHIPGetWrite(vnew, &dvn);CHKERRQ(ierr);
+  ierr = VecHIPGetWrite(unew, &dun);CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_minres_update(dc->h, N_(vnew), first ? 1 : 0, rho2, rho3, irho1, ceta, ibeta, du, dw, dwo, dx, dr, dz, dvn, dun));
+  VecHIPRestoreWrite(vnew); VecHIPRestoreWrite(unew);
+  HipStateIncrease(vnew); HipStateIncrease(unew);
+  if (!first) { VecHIPRestoreWrite(wold); VecHIPRestoreWrite(x); HipStateIncrease(wold); HipStateIncrease(x); }
+  ierr = PetscLogFlops((first ? 2.0 : 9.0) * vnew->map->n);CHKERRQ(ierr);     /* 2 x 2n + n + 2n + 2 x n */
+  *done = PETSC_TRUE;
+  return 0;
+}
+/* "VecMinresFusedOps_C": the sweeps of MINRES */
+static const VecMinresFusedOps *VecMinresFusedOps_HIP(void) {
+  static const VecMinresFusedOps ops = {VecMinresLanczos_HIPMI355X, VecMinresUpdate_HIPMI355X};
+  return &ops;
+}
+
 /* the *_local slots of struct _VecOps (vecimpl.h:262-266): the same device reductions without the step across ranks;
  * NORM_2 returns the root of the local sum, as VecNorm_Seq does for VecNormBegin (comb.c squares it again) */
 static PetscErrorCode VecDot_HIP_local(Vec x, Vec y, PetscScalar *val) { hip_local_only = 1; PetscErrorCode ierr = VecDot_HIP(x, y, val); hip_local_only = 0; return ierr; }
@@ -1443,6 +1512,7 @@ static PetscErrorCode VecCreate_HIP_common(Vec v, const char *tname) {
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecKrylovFusedOps_C", "VecKrylovFusedOps_HIP", (PetscVoidFunction)VecKrylovFusedOps_HIP);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecSplitReductionOps_C", "VecSplitReductionOps_HIP", (PetscVoidFunction)VecSplitReductionOps_HIP);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecPipelinedCGFusedOps_C", "VecPipelinedCGFusedOps_HIP", (PetscVoidFunction)VecPipelinedCGFusedOps_HIP);CHKERRQ(ierr);
+  ierr = PetscObjectComposeFunction((PetscObject)v, "VecMinresFusedOps_C", "VecMinresFusedOps_HIP", (PetscVoidFunction)VecMinresFusedOps_HIP);CHKERRQ(ierr);
   return 0;
 }
 
