@@ -163,7 +163,7 @@ typedef struct {
     int by_level;                                          /* rows summed in dependency-level order (inode matrices) instead of column order */
     int block_columns;                                     /* node plans whose columns are whole dependency nodes */
     PetscInt nodes, nlevL_nodes, nlevU_nodes;              /* node-blocked plans (the factor of a matrix with inodes): nodes and their levels; 0: row-granular */
-    int use_levels;                                        /* a sync-free application gave up: the same plans run level by level from now on */
+    int use_levels;                                        /* a sync-free application gave up: THESE plans run level by level from now on; the next factorisation builds new plans and starts sync-free again (f->aborted remembers) */
   } syncfree;
   /* -pc_factor_hipmi355x_trisolve sweeps:<k>: k Jacobi sweeps per triangle instead of the exact solves (sweeps 0: exact).  The negated
    * strict triangles as CSR with their SpMV plans, the inverted pivots, two work vectors.  A numeric factorisation with the pattern

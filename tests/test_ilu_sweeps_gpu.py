@@ -13,6 +13,7 @@ import pytest
 
 import orc
 import problems as pb
+from sweeps_ref import ref_add_scaled, strict_triangles  # noqa: F401 (the restatements; other test modules take them from here)
 from test_kernels_gpu import bits, dev, make_plan, random_csr, rnd  # noqa: F401 (dev: fixture)
 
 pytestmark = pytest.mark.gpu
@@ -112,17 +113,6 @@ def test_enough_sweeps_are_the_exact_solve_bit_for_bit(P):
 
 
 # ---------------------------------------------------------------- 2. the kernel form through the C ABI
-def ref_add_scaled(ai, aj, aa, x, y, d=None):
-    """numpy, one row after the other: s = y_r; s = s + a_j x_j in column order (product rounded, then the sum); d_r * s"""
-    out = np.empty(ai.size - 1)
-    for r in range(ai.size - 1):
-        s = y[r]
-        for q in range(ai[r], ai[r + 1]):
-            s = s + aa[q] * x[aj[q]]
-        out[r] = s if d is None else d[r] * s
-    return out
-
-
 def put_csr(dev, ai, aj, aa):
     """device CSR with the 16 bytes of slack past the value and index arrays that the row-block kernels' paired loads ask for"""
     return dev.put(ai), dev.put(np.concatenate([aj, np.zeros(4, np.int32)])), dev.put(np.concatenate([aa, np.zeros(2)]))
@@ -181,17 +171,6 @@ def test_add_scaled_long_rows_within_the_long_row_bound(dev, alias):
     err = np.abs(got - ref)
     print("long rows: max |err| / sum|a x| = %.3g" % np.max(err[~empty] / scale[~empty]))
     assert np.all(err[~empty] <= 1e-12 * scale[~empty])
-
-
-def strict_triangles(f):
-    """the negated strict triangles of an oracle factor as CSR, and the inverted pivots"""
-    bi, bj, bd, ba = f
-    n = bi.size - 1
-    iL, jL, aL = bi.copy(), bj[:bi[n]].copy(), -ba[:bi[n]]
-    lenU = (bd[:-1] - bd[1:] - 1).astype(np.int32)
-    iU = np.zeros(n + 1, np.int32); iU[1:] = np.cumsum(lenU)
-    src = np.concatenate([np.arange(bd[i + 1] + 1, bd[i]) for i in range(n)]).astype(np.int64) if iU[n] else np.zeros(0, np.int64)
-    return (iL, jL, aL), (iU, bj[src].astype(np.int32), -ba[src]), ba[bd[:-1]].copy()
 
 
 def test_sweep_steps_on_the_strict_triangles_of_a_factor(dev):
