@@ -212,6 +212,23 @@ int mi355x_vec_minres_lanczos(mi355x_handle_t h, size_t n, double alpha, const d
                               const double *v, const double *u, const double *vold, const double *uold, double *out);
 int mi355x_vec_minres_update(mi355x_handle_t h, size_t n, int first, double rho2, double rho3, double irho1, double ceta, double ibeta,
                              const double *u, const double *w, double *wold, double *x, const double *r, const double *z, double *vnew, double *unew);
+/* The three sweeps of an iteration of KSPSolve_TFQMR (src/ksp/ksp/impls/tfqmr/tfqmr.c) and KSPSolve_CGS (src/ksp/ksp/impls/cgs/cgs.c) around
+ * the two applications of the preconditioned operator, with the bits of mi355x_vec_waxpy, mi355x_vec_axpy, mi355x_vec_aypx,
+ * mi355x_vec_norm(type 1) and mi355x_vec_dot run one call at a time, their scalar special cases (0, 1, -1) included; an operand a special
+ * case skips is not loaded, a vector no case changes is not stored.
+ * qt:      q = u + (-a) v ; t = q + u ; x != NULL (CGS): x = x + a t.   a == 0: q = u, v not loaded, x untouched.  A pure map.
+ * resid:   r = r + (-a) auq ; out = { sum r*r , sum r*rp } over the updated r (for an aligned view the trees of mi355x_vec_norm(type 1)
+ *          and mi355x_vec_dot);  a == 0: r untouched, auq not loaded;  out: device or the handle's pinned scratch;  n == 0: { 0, 0 }.
+ * update:  nhalves >= 1: d = u + cf0 d ; x = x + eta0 d.   nhalves == 2: then d = q + cf1 d ; x = x + eta1 d (the halves read the OLD u
+ *          and q).   tail != 0: un = r + b q ; qn = q + b p ; pn = un + b qn, stored to u, q, p.   nhalves == 0 (CGS): d and x not
+ *          touched and may be NULL; tail == 0: u, q, p, r not touched by the tail (r, p may be NULL; q too when nhalves < 2; u too when
+ *          nhalves == 0).  A pure map: nothing reduced.
+ * Nonzero and nothing touched: a vector the form touches is missing, nhalves is not 0, 1 or 2, or a written vector (q, t, x; r; d, x, u,
+ * q, p) is another operand of the same call. */
+int mi355x_vec_tfqmr_qt(mi355x_handle_t h, size_t n, double a, const double *u, const double *v, double *q, double *t, double *x);
+int mi355x_vec_tfqmr_resid(mi355x_handle_t h, size_t n, double a, const double *auq, const double *rp, double *r, double *out);
+int mi355x_vec_tfqmr_update(mi355x_handle_t h, size_t n, int nhalves, double cf0, double eta0, double cf1, double eta1, int tail, double b,
+                            double *d, double *x, double *u, double *q, const double *r, double *p);
 /* VecMDot_Seq         src/vec/vec/impls/seq/dvec2.c:146     out[j] = sum_i x_i y_j,i , j<nv ; x read once per 16 y's */
 int mi355x_vec_mdot(mi355x_handle_t h, size_t n, int nv, const double *x, const double *const *y, double *out);
 /* KSPGMRESCycle fusions (gmres.c:118-209, borthog2.c:60-66): x += sum_j sign*coef_dev[j]*y_j in VecMAXPY_Seq's grouping with

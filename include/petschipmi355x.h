@@ -37,6 +37,8 @@ extern "C" {
 #define KSPCHEBYCHEVHIPMI355X  "chebychevhipmi355x"    /* needs vectors whose type offers "cheby_step" (include/petsckrylovfused.h): PETSC_ERR_SUP at set-up otherwise */
 #define KSPRICHARDSONHIPMI355X "richardsonhipmi355x"
 #define KSPPIPECGHIPMI355X  "pipecghipmi355x"          /* KSPPIPECG with the vector work of an iteration in one sweep ("VecPipelinedCGFusedOps_C") */
+#define KSPTFQMRHIPMI355X   "tfqmrhipmi355x"           /* KSPTFQMR with three sweeps per iteration ("VecTfqmrFusedOps_C"); on other vectors the same function runs op by op */
+#define KSPCGSHIPMI355X     "cgshipmi355x"             /* KSPCGS on the same three sweeps */
 #define KSPMINRESHIPMI355X  "minreshipmi355x"          /* KSPMINRES with two sweeps per iteration; needs vectors that offer "VecMinresFusedOps_C": PETSC_ERR_SUP at set-up otherwise */
 
 /* One call after PetscInitialize (or a PetscDLLibraryRegister entry, src/sys/dll): registers the types above with
@@ -117,7 +119,7 @@ PetscErrorCode MatHIPMI355XGetTiledInfo(Mat A, PetscInt *staged, PetscInt *remai
 PetscErrorCode MatHIPMI355XGetRowPatterns(Mat A, PetscInt *npat);   /* 0: none; else the size of the row-pattern dictionary the SpMV runs with */
 PetscErrorCode MatHIPMI355XSetValuePatterns(Mat A, PetscBool on);   /* A/B switch for one matrix until its next upload (the option -mat_hipmi355x_value_patterns decides at every upload) */
 /* the pipelined CG types: update steps taken in one fused sweep / through the public Vec calls, since the KSP took its type;
- * minreshipmi355x: (Lanczos sweeps run, 0); any other type: 0, 0 */
+ * minreshipmi355x: (Lanczos sweeps run, 0); tfqmrhipmi355x, cgshipmi355x: (fused sweeps run, iterations run op by op); any other type: 0, 0 */
 PetscErrorCode KSPHIPMI355XGetFusedStepCounts(KSP ksp, PetscInt *fused, PetscInt *opbyop);
 PetscErrorCode VecHIPMI355XSetCGUpdateTiming(PetscBool on);   /* hipEvent pairs around the fused CG update (bench.py's roofline for that kernel) */
 PetscErrorCode VecHIPMI355XGetCGUpdateTiming(PetscInt *nlaunches, PetscLogDouble *total_ms);

@@ -75,6 +75,23 @@ typedef struct {
                                   PetscScalar rho2, PetscScalar rho3, PetscScalar irho1, PetscScalar ceta, PetscScalar ibeta, PetscBool *done);
 } VecMinresFusedOps;
 typedef const VecMinresFusedOps *(*VecMinresFusedOpsGetFn)(void);
+/* "VecTfqmrFusedOps_C" on a Vec returns the three sweeps of an iteration of KSPSolve_TFQMR (tfqmr.c) and KSPSolve_CGS (cgs.c), a fourth
+ * table.  *done = PETSC_FALSE and nothing touched when a sweep refuses its operands: a vector of another type or on another device,
+ * unequal local sizes, or a written vector that is another operand of the call. */
+typedef struct {
+  /* q = u - a v (VecWAXPY(Q, -a, V, U)) ; t = u + q (VecWAXPY(T, 1.0, U, Q)) ; x != NULL (CGS): x += a t (VecAXPY(X, a, T)).
+   * Nothing is reduced and the host does not wait. */
+  PetscErrorCode (*tfqmr_qt)(Vec u, Vec v, Vec q, Vec t, Vec x, PetscScalar a, PetscBool *done);
+  /* r -= a auq (VecAXPY(R, -a, AUQ)) ; *rr = r'r (the sum VecNorm(R, NORM_2) takes the root of) ; *rrp = r'rp (VecDot(R, RP)), both over
+   * the updated r and all-reduced, in one wait. */
+  PetscErrorCode (*tfqmr_resid)(Vec r, Vec auq, Vec rp, PetscScalar a, PetscScalar *rr, PetscScalar *rrp, PetscBool *done);
+  /* nhalves >= 1: d = u + cf0 d ; x += eta0 d.  nhalves == 2: then d = q + cf1 d ; x += eta1 d (VecAYPX + VecAXPY per half step of TFQMR;
+   * the halves read the old u and q).  tail: u = r + b q ; q += b p ; p = u + b q (VecWAXPY, VecAXPY, VecWAXPY).  nhalves == 0 (CGS):
+   * d and x are not touched and may be NULL; !tail (an exit inside the half steps): r and p likewise.  Nothing is reduced. */
+  PetscErrorCode (*tfqmr_update)(Vec d, Vec x, Vec u, Vec q, Vec r, Vec p, PetscInt nhalves, PetscScalar cf0, PetscScalar eta0, PetscScalar cf1, PetscScalar eta1,
+                                 PetscBool tail, PetscScalar b, PetscBool *done);
+} VecTfqmrFusedOps;
+typedef const VecTfqmrFusedOps *(*VecTfqmrFusedOpsGetFn)(void);
 typedef PetscErrorCode (*MatMultTDotBeginFn)(Mat A, Vec x, Vec y, PetscBool *ok);
 typedef PetscErrorCode (*MatMultDiagonalScaleFn)(Mat A, Vec d, Vec x, Vec y, PetscBool *ok);
 

@@ -137,6 +137,8 @@ typedef const char *PCType;
 #define KSPCHEBYCHEV  "chebychev"    /* Chebyshev iteration with given eigenvalue bounds (src/ksp/ksp/impls/cheby/cheby.c) */
 #define KSPRICHARDSON "richardson"   /* (damped) Richardson iteration (src/ksp/ksp/impls/rich/rich.c) */
 #define KSPMINRES  "minres"    /* minimum residual method for symmetric indefinite operators (src/ksp/ksp/impls/minres/minres.c) */
+#define KSPTFQMR   "tfqmr"     /* transpose-free QMR for nonsymmetric operators (src/ksp/ksp/impls/tfqmr/tfqmr.c) */
+#define KSPCGS     "cgs"       /* conjugate gradient squared (src/ksp/ksp/impls/cgs/cgs.c) */
 #define PCNONE     "none"
 #define PCJACOBI   "jacobi"
 #define PCBJACOBI  "bjacobi"

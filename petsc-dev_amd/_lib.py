@@ -79,6 +79,9 @@ KERNEL_API = {
     "mi355x_vec_pipecg_step": [vp, sz, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
     "mi355x_vec_minres_lanczos": [vp, sz, dbl, vp, dbl, vp, vp, vp, vp, vp, vp, vp, vp],
     "mi355x_vec_minres_update": [vp, sz, i32, dbl, dbl, dbl, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp],
+    "mi355x_vec_tfqmr_qt": [vp, sz, dbl, vp, vp, vp, vp, vp],
+    "mi355x_vec_tfqmr_resid": [vp, sz, dbl, vp, vp, vp, vp],
+    "mi355x_vec_tfqmr_update": [vp, sz, i32, dbl, dbl, dbl, dbl, i32, dbl, vp, vp, vp, vp, vp, vp],
     "mi355x_handle_publish": [vp, vp, i32],
     "mi355x_handle_publish_at": [vp, vp, i32, i32],
     "mi355x_vec_cg_update_dev": [vp, sz, dbl, vp, dbl, i32, vp, vp, vp, vp, vp, vp, vp, i32],

@@ -1169,6 +1169,171 @@ __global__ __launch_bounds__(MI355X_BLOCK) void minres_update_kernel(MinresUpdat
     [&](size_t k) { f.at1(k); });
 }
 
+// ---- the three sweeps of an iteration of KSPSolve_TFQMR (src/ksp/ksp/impls/tfqmr/tfqmr.c) and KSPSolve_CGS (src/ksp/ksp/impls/cgs/cgs.c),
+// which share one skeleton, around the two applications of the preconditioned operator.  Each product and sum is rounded as in
+// mi355x_vec_waxpy, _axpy and _aypx, whose scalar special cases are kept; an operand a special case skips is not loaded, a vector no case
+// changes is not stored; under launch_reduce a lane meets its elements in SumSqF's / DotF's order: every output carries the bits of the
+// separate launches.
+// w of VecWAXPY(w, al, x, y) with the cases of mi355x_vec_waxpy (1, -1, 0 -> copy of y)
+__device__ __forceinline__ double waxpy_elem(double al, double xv, double yv) {
+  if (al == 1.0) return OpXpY{}(xv, yv, 0.0);
+  if (al == -1.0) return OpYmX{}(xv, yv, 0.0);
+  if (al == 0.0) return yv;
+  return OpAxpy{al}(xv, yv, 0.0);
+}
+// TfqmrQTF, a pure map:
+//   q = u + (-a) v                                       (VecWAXPY(Q, -a, V, U); a == 0: a copy of u, v not loaded)
+//   t = q + u                                            (VecWAXPY(T, 1.0, U, Q): the alpha == 1 form)
+//   x = x + a t                                          (CGS, x != NULL: VecAXPY(X, a, T); a == 0: x neither read nor written)
+// Streaming (see nt_load2), a choice by analogy with the MINRES sweeps, not a measurement: v has its last reader here (the
+// product that follows overwrites its buffer) and x is touched here only: non-temporal at every size; u and q (read again by the update
+// sweep) and t (gathered by the product that follows) stay cacheable below 256 MiB and are streamed from there on like every other
+// tile kernel.
+struct TfqmrQTF {
+  double a;
+  const double *u, *v;
+  double *q, *t, *x;
+  int big;
+  __device__ __forceinline__ bool reads_v() const { return a != 0.0; }
+  __device__ __forceinline__ bool steps() const { return x != nullptr && a != 0.0; }
+  __device__ __forceinline__ void one(double uv, double vv, double &qv, double &tv, double &xv) const {
+    qv = waxpy_elem(-a, vv, uv);
+    tv = OpXpY{}(uv, qv, 0.0);
+    if (steps()) xv = OpAxpy{a}(tv, xv, 0.0);
+  }
+  template <int U>
+  __device__ __forceinline__ void tile(size_t i) const {
+    double2 uv[U], vv[U] = {}, xv[U] = {}, qv[U], tv[U];
+    ldq_tile(u, i, big, uv);
+    if (reads_v()) ldq_tile(v, i, 1, vv);
+    if (steps()) ldq_tile(x, i, 1, xv);
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      one(uv[j].x, vv[j].x, qv[j].x, tv[j].x, xv[j].x);
+      one(uv[j].y, vv[j].y, qv[j].y, tv[j].y, xv[j].y);
+    }
+    stq_tile(q, i, big, qv); stq_tile(t, i, big, tv);
+    if (steps()) stq_tile(x, i, 1, xv);
+  }
+  __device__ __forceinline__ void at1(size_t k) const {
+    double qv, tv, xv = steps() ? x[k] : 0.0;
+    one(u[k], reads_v() ? v[k] : 0.0, qv, tv, xv);
+    q[k] = qv; t[k] = tv;
+    if (steps()) x[k] = xv;
+  }
+};
+__global__ __launch_bounds__(MI355X_BLOCK) void tfqmr_qt_kernel(TfqmrQTF f, size_t n, int vec_ok) {
+  tile_walk<2>(n, vec_ok,
+    [&](size_t i, auto u) { f.template tile<decltype(u)::value>(i); },
+    [&](size_t k) { f.at1(k); });
+}
+
+// TfqmrResidF, under launch_reduce:
+//   r = r + (-a) auq                                     (VecAXPY(R, -a, AUQ); a == 0: r not stored, auq not loaded)
+//   out = { sum r*r , sum r*rp }                         (VecNorm(R, NORM_2)'s sum and VecDot(R, RP) over the updated r)
+// Streaming, by the same analogy: auq has its only reader here (the next product overwrites its buffer): non-temporal at every size;
+// r (read again by the update sweep) and rp (read by every iteration's two reductions) stay cacheable below 256 MiB.
+struct TfqmrResidF {
+  double ma;                   // -a, the scalar VecAXPY is called with
+  const double *auq, *rp;
+  double *r;
+  int big;
+  __device__ __forceinline__ bool moves() const { return ma != 0.0; }
+  template <int NOUT_>
+  __device__ __forceinline__ void sweep(size_t tid, size_t stride, size_t n2, double (&acc)[NOUT_]) const {
+    for (size_t i = tid; i < n2; i += stride) {
+      double2 rv, pv, av = {};
+      ldq_tile1(r, i, big, rv);
+      ldq_tile1(rp, i, big, pv);
+      if (moves()) {
+        ldq_tile1(auq, i, 1, av);
+        rv.x = OpAxpy{ma}(av.x, rv.x, 0.0); rv.y = OpAxpy{ma}(av.y, rv.y, 0.0);
+        stq(reinterpret_cast<double2 *>(r) + i, rv, big);
+      }
+      acc[0] += rv.x * rv.x; acc[1] += rv.x * pv.x;
+      acc[0] += rv.y * rv.y; acc[1] += rv.y * pv.y;
+    }
+  }
+  __device__ __forceinline__ void accum1(size_t k, double (&acc)[2]) const {
+    double rv = r[k];
+    if (moves()) { rv = OpAxpy{ma}(auq[k], rv, 0.0); r[k] = rv; }
+    acc[0] += rv * rv; acc[1] += rv * rp[k];
+  }
+};
+
+// TfqmrUpdateF, a pure map (nothing reduced, no host wait):
+//   nhalves >= 1:  d = u + cf0 d ; x = x + eta0 d        (VecAYPX(D, cf0, U), VecAXPY(X, eta0, D): the m = 0 half of TFQMR's inner loop)
+//   nhalves == 2:  d = q + cf1 d ; x = x + eta1 d        (VecAYPX(D, cf1, Q), VecAXPY(X, eta1, D): the m = 1 half)
+//   tail != 0:     un = r + b q ; qn = q + b p ; pn = un + b qn, stored to u, q, p
+//                                                        (VecWAXPY(U, b, Q, R), VecAXPY(Q, b, P), VecWAXPY(P, b, Q, U))
+// The halves read the OLD u and q: every operand is loaded before the first store.  mi355x_vec_aypx's cases (cf == 0: a copy, d not
+// loaded; 1; -1), mi355x_vec_axpy's (eta == 0, b == 0: untouched) and mi355x_vec_waxpy's (b == 1, -1, 0: copies, q and p not loaded) are
+// honoured.  nhalves == 0 (CGS) touches neither d nor x; tail == 0 (an exit inside TFQMR's inner loop) none of u, q, p, r.
+// Streaming, by the same analogy: d and x are touched here only, the old u, q, p and r are read for the last time, and the new q has no
+// reader at all (the next TfqmrQTF overwrites it): non-temporal at every size.  The new u (read by the next TfqmrQTF) and the new p
+// (gathered by the product that follows) stay cacheable below 256 MiB.
+struct TfqmrUpdateF {
+  double cf0, eta0, cf1, eta1, b;
+  const double *r;
+  double *d, *x, *u, *q, *p;
+  int nhalves, tail, big;
+  __device__ __forceinline__ bool reads_d() const { return nhalves >= 1 && cf0 != 0.0; }
+  __device__ __forceinline__ bool steps() const { return (nhalves >= 1 && eta0 != 0.0) || (nhalves == 2 && eta1 != 0.0); }
+  __device__ __forceinline__ bool reads_u() const { return nhalves >= 1; }
+  __device__ __forceinline__ bool moves_q() const { return tail && b != 0.0; }       // VecAXPY(Q, b, P) does something; p is read
+  __device__ __forceinline__ bool reads_q() const { return nhalves == 2 || moves_q(); }
+  __device__ __forceinline__ void one(double rv, double &dv, double &xv, double &uv, double &qv, double &pv) const {
+    if (nhalves >= 1) {
+      dv = aypx_elem(cf0 == 0.0, cf0, uv, dv);
+      if (eta0 != 0.0) xv = OpAxpy{eta0}(dv, xv, 0.0);
+    }
+    if (nhalves == 2) {
+      dv = aypx_elem(cf1 == 0.0, cf1, qv, dv);
+      if (eta1 != 0.0) xv = OpAxpy{eta1}(dv, xv, 0.0);
+    }
+    if (tail) {
+      uv = waxpy_elem(b, qv, rv);
+      if (b != 0.0) qv = OpAxpy{b}(pv, qv, 0.0);
+      pv = waxpy_elem(b, qv, uv);
+    }
+  }
+  // the U double2's of a lane in its tile; every load is issued before the first store
+  template <int U>
+  __device__ __forceinline__ void tile(size_t i) const {
+    double2 rv[U] = {}, dv[U] = {}, xv[U] = {}, uv[U] = {}, qv[U] = {}, pv[U] = {};
+    if (reads_d()) ldq_tile(d, i, 1, dv);
+    if (steps()) ldq_tile(x, i, 1, xv);
+    if (reads_u()) ldq_tile(u, i, 1, uv);
+    if (reads_q()) ldq_tile(q, i, 1, qv);
+    if (tail) ldq_tile(r, i, 1, rv);
+    if (moves_q()) ldq_tile(p, i, 1, pv);
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      one(rv[j].x, dv[j].x, xv[j].x, uv[j].x, qv[j].x, pv[j].x);
+      one(rv[j].y, dv[j].y, xv[j].y, uv[j].y, qv[j].y, pv[j].y);
+    }
+    if (nhalves >= 1) stq_tile(d, i, 1, dv);
+    if (steps()) stq_tile(x, i, 1, xv);
+    if (tail) stq_tile(u, i, big, uv);
+    if (moves_q()) stq_tile(q, i, 1, qv);
+    if (tail) stq_tile(p, i, big, pv);
+  }
+  __device__ __forceinline__ void at1(size_t k) const {
+    double dv = reads_d() ? d[k] : 0.0, xv = steps() ? x[k] : 0.0, uv = reads_u() ? u[k] : 0.0, qv = reads_q() ? q[k] : 0.0, pv = moves_q() ? p[k] : 0.0;
+    one(tail ? r[k] : 0.0, dv, xv, uv, qv, pv);
+    if (nhalves >= 1) d[k] = dv;
+    if (steps()) x[k] = xv;
+    if (tail) u[k] = uv;
+    if (moves_q()) q[k] = qv;
+    if (tail) p[k] = pv;
+  }
+};
+__global__ __launch_bounds__(MI355X_BLOCK) void tfqmr_update_kernel(TfqmrUpdateF f, size_t n, int vec_ok) {
+  tile_walk<2>(n, vec_ok,
+    [&](size_t i, auto u) { f.template tile<decltype(u)::value>(i); },
+    [&](size_t k) { f.at1(k); });
+}
+
 template <int NV>
 struct MDotF {
   const double *x;
@@ -1472,6 +1637,47 @@ int mi355x_vec_minres_update(mi355x_handle_t h, size_t n, int first, double rho2
   if (first) { u = w = nullptr; wold = x = nullptr; }                                        // not touched: their alignment does not count
   const MinresUpdateF f{rho2, rho3, irho1, ceta, ibeta, u, w, r, z, wold, x, vnew, unew, first != 0, vec_streams(n)};
   return launch_tiles(h, n, all_aligned16(u, w, wold, x, r, z, vnew, unew), minres_update_kernel, minres_update_kernel, f);
+}
+
+// a written vector of the three TFQMR / CGS sweeps that is another operand of the same call (NULL: an operand the form does not touch)
+static inline bool written_is_operand(const double *const *written, int nw, const double *const *all, int na) {
+  for (int i = 0; i < nw; ++i) {
+    int seen = 0;
+    for (int j = 0; j < na; ++j) seen += (written[i] != nullptr && all[j] == written[i]);
+    if (seen > 1) return true;
+  }
+  return false;
+}
+int mi355x_vec_tfqmr_qt(mi355x_handle_t h, size_t n, double a, const double *u, const double *v, double *q, double *t, double *x) {
+  if (!u || !v || !q || !t) return (int)hipErrorInvalidValue;
+  const double *const written[] = {q, t, x}, *const all[] = {u, v, q, t, x};
+  if (written_is_operand(written, 3, all, 5)) return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  if (a == 0.0) { v = nullptr; x = nullptr; }                                               // not touched: their alignment does not count
+  const TfqmrQTF f{a, u, v, q, t, x, vec_streams(n)};
+  return launch_tiles(h, n, all_aligned16(u, v, q, t, x), tfqmr_qt_kernel, tfqmr_qt_kernel, f);
+}
+int mi355x_vec_tfqmr_resid(mi355x_handle_t h, size_t n, double a, const double *auq, const double *rp, double *r, double *out) {
+  if (!auq || !rp || !r || !out || auq == r || rp == r) return (int)hipErrorInvalidValue;
+  if (a == 0.0) auq = nullptr;
+  const TfqmrResidF f{-a, auq, rp, r, vec_streams(n)};
+  return launch_reduce<2, RED_SUM>(h, f, n, all_aligned16(auq, rp, r), out);                 // n == 0: zeros
+}
+int mi355x_vec_tfqmr_update(mi355x_handle_t h, size_t n, int nhalves, double cf0, double eta0, double cf1, double eta1, int tail, double b,
+                            double *d, double *x, double *u, double *q, const double *r, double *p) {
+  if (nhalves < 0 || nhalves > 2) return (int)hipErrorInvalidValue;
+  if (nhalves == 0) { d = nullptr; x = nullptr; }                                           // what this form does not touch is not looked at
+  if (nhalves < 2 && !tail) q = nullptr;
+  if (nhalves == 0 && !tail) u = nullptr;
+  if (!tail) { r = nullptr; p = nullptr; }
+  if ((nhalves >= 1 && (!d || !x || !u)) || (nhalves == 2 && !q) || (tail && (!u || !q || !r || !p))) return (int)hipErrorInvalidValue;
+  const double *const written[] = {d, x, u, q, p}, *const all[] = {d, x, u, q, r, p};
+  if (written_is_operand(written, 5, all, 6)) return (int)hipErrorInvalidValue;
+  if (n == 0 || (nhalves == 0 && !tail)) return 0;
+  const TfqmrUpdateF f{cf0, eta0, cf1, eta1, b, r, d, x, u, q, p, nhalves, tail != 0, vec_streams(n)};
+  if (!((nhalves >= 1 && eta0 != 0.0) || (nhalves == 2 && eta1 != 0.0))) x = nullptr;       // alignment of what is neither loaded nor stored does not count
+  if (tail && b == 0.0 && nhalves < 2) q = nullptr;
+  return launch_tiles(h, n, all_aligned16(d, x, u, q, r, p), tfqmr_update_kernel, tfqmr_update_kernel, f);
 }
 
 // borthog2.c:63-64 + the norm of gmres.c:146: x += sum_j sign * coef_dev[j] * y_j, *out = sum x_new^2 (out: device or the

@@ -14,6 +14,8 @@
  *   Chebyshev     src/ksp/ksp/impls/cheby/cheby.c (KSPSolve_Chebychev; eigenvalue bounds from the user, no estimation)
  *   Richardson    src/ksp/ksp/impls/rich/rich.c (KSPSolve_Richardson; fixed scale, no self-scaling), PCApplyRichardson precon.c, sor.c
  *   MINRES        src/ksp/ksp/impls/minres/minres.c (KSPSolve_MINRES)
+ *   TFQMR         src/ksp/ksp/impls/tfqmr/tfqmr.c (KSPSolve_TFQMR)
+ *   CGS           src/ksp/ksp/impls/cgs/cgs.c (KSPSolve_CGS)
  * and are written here over a few shared pieces: one checkpoint routine (history, monitor, convergence test), one start-residual
  * routine for the CG family, index-addressed Hessenberg columns for GMRES. */
 #include "petscimpl.h"
@@ -890,5 +892,129 @@ PetscErrorCode KSPCreate_MINRES(KSP ksp) {   /* minres.c KSPCreate_MINRES */
   ksp->normsupporttable[KSP_NORM_PRECONDITIONED][PC_LEFT] = 2;
   ksp->ops->setup = KSPSetUp_MINRES;
   ksp->ops->solve = KSPSolve_MINRES;
+  return 0;
+}
+
+/* ================================================================== TFQMR (tfqmr.c KSPSolve_TFQMR) and CGS (cgs.c KSPSolve_CGS)
+ * The two transpose-free short-recurrence methods for nonsymmetric operators.  They share the CGS recurrence over (R, U, P, Q) with the
+ * shadow residual RP and two applications of K = B A per iteration (V = K P, AUQ = K T; AUQ lives in V's buffer).  CGS takes x and the
+ * residual norm from the recurrence itself; TFQMR smooths it: two half steps per iteration over the direction D, a residual ESTIMATE
+ * sqrt(m + 1) tau per half step (two history entries per iteration), and ksp->its counts the iterations completed, so an exit inside
+ * the half steps of iteration i leaves its = i.  Left preconditioning with the preconditioned norm only.
+ * s = V'RP == 0 sets KSP_DIVERGED_BREAKDOWN where the reference divides by it. */
+enum { TQ_R = 0, TQ_RP, TQ_V, TQ_T, TQ_Q, TQ_P, TQ_U, TQ_T1, TQ_D };
+static PetscErrorCode KSPSetUp_TFQMR(KSP ksp) { return KSPDefaultGetWork(ksp, 9); }
+static PetscErrorCode KSPSetUp_CGS(KSP ksp) { return KSPDefaultGetWork(ksp, 8); }      /* the same vectors without D */
+
+/* the solve start both share: the residual, the checkpoint of iteration 0, RP, rhoold, U, P and V = K P */
+static PetscErrorCode cgs_family_start(KSP ksp, PetscReal *dp, PetscScalar *rhoold) {
+  Vec X = ksp->vec_sol, B = ksp->vec_rhs, *w = ksp->work;
+  if (ksp->pc_side == PC_RIGHT) SETERRQ(ksp->comm, PETSC_ERR_SUP, "KSP %s does not support right preconditioning", ksp->type_name);
+  ksp->its = 0;
+  OK(KSPInitialResidual(ksp, X, w[TQ_V], w[TQ_T], w[TQ_R], B));
+  OK(VecNorm(w[TQ_R], NORM_2, dp));
+  OK(checkpoint(ksp, 0, *dp));
+  if (ksp->reason) return 0;
+  OK(VecCopy(w[TQ_R], w[TQ_RP]));
+  OK(VecDot(w[TQ_R], w[TQ_RP], rhoold));
+  OK(VecCopy(w[TQ_R], w[TQ_U]));
+  OK(VecCopy(w[TQ_R], w[TQ_P]));
+  OK(KSP_PCApplyBAorAB(ksp, w[TQ_P], w[TQ_V], w[TQ_T1]));
+  return 0;
+}
+
+static PetscErrorCode KSPSolve_TFQMR(KSP ksp) {
+  Vec X = ksp->vec_sol, *w = ksp->work;
+  Vec R = w[TQ_R], RP = w[TQ_RP], V = w[TQ_V], T = w[TQ_T], Q = w[TQ_Q], P = w[TQ_P], U = w[TQ_U], T1 = w[TQ_T1], D = w[TQ_D], AUQ = V;
+  PetscScalar rho, rhoold, a, s, b, eta, etaold = 0.0, psiold = 0.0, cf;
+  PetscReal dp, dpold, wt, dpest, tau, psi, cm;
+  PetscInt i, m;
+
+  OK(cgs_family_start(ksp, &dp, &rhoold));
+  if (ksp->reason) return 0;
+  OK(VecSet(D, 0.0));
+  tau = dp; dpold = dp;
+  for (i = 0; i < ksp->max_it; i++) {
+    OK(VecDot(V, RP, &s));
+    if (s == 0.0) { ksp->reason = KSP_DIVERGED_BREAKDOWN; break; }
+    a = rhoold / s;
+    OK(VecWAXPY(Q, -a, V, U));
+    OK(VecWAXPY(T, 1.0, U, Q));
+    OK(KSP_PCApplyBAorAB(ksp, T, AUQ, T1));
+    OK(VecAXPY(R, -a, AUQ));
+    OK(VecNorm(R, NORM_2, &dp));
+    for (m = 0; m < 2; m++) {
+      wt = m ? dp : PetscSqrtReal(dp * dpold);
+      psi = wt / tau;
+      cm = 1.0 / PetscSqrtReal(1.0 + psi * psi);
+      tau = tau * psi * cm;
+      eta = cm * cm * a;
+      cf = psiold * psiold * etaold / a;
+      OK(VecAYPX(D, cf, m ? Q : U));
+      OK(VecAXPY(X, eta, D));
+      dpest = PetscSqrtReal(m + 1.0) * tau;
+      OK(checkpoint(ksp, i + 1, dpest));
+      if (ksp->reason) break;
+      etaold = eta;
+      psiold = psi;
+    }
+    if (ksp->reason) break;
+    ksp->its = i + 1;
+    OK(VecDot(R, RP, &rho));
+    b = rho / rhoold;
+    OK(VecWAXPY(U, b, Q, R));
+    OK(VecAXPY(Q, b, P));
+    OK(VecWAXPY(P, b, Q, U));
+    OK(KSP_PCApplyBAorAB(ksp, P, V, T1));
+    rhoold = rho;
+    dpold = dp;
+  }
+  if (i >= ksp->max_it) ksp->reason = KSP_DIVERGED_ITS;
+  return 0;
+}
+
+static PetscErrorCode KSPSolve_CGS(KSP ksp) {
+  Vec X = ksp->vec_sol, *w = ksp->work;
+  Vec R = w[TQ_R], RP = w[TQ_RP], V = w[TQ_V], T = w[TQ_T], Q = w[TQ_Q], P = w[TQ_P], U = w[TQ_U], T1 = w[TQ_T1], AUQ = V;
+  PetscScalar rho, rhoold, a, s, b;
+  PetscReal dp;
+  PetscInt i;
+
+  OK(cgs_family_start(ksp, &dp, &rhoold));
+  if (ksp->reason) return 0;
+  for (i = 0; i < ksp->max_it; i++) {
+    OK(VecDot(V, RP, &s));
+    if (s == 0.0) { ksp->reason = KSP_DIVERGED_BREAKDOWN; break; }
+    a = rhoold / s;
+    OK(VecWAXPY(Q, -a, V, U));
+    OK(VecWAXPY(T, 1.0, U, Q));
+    OK(VecAXPY(X, a, T));
+    OK(KSP_PCApplyBAorAB(ksp, T, AUQ, T1));
+    OK(VecAXPY(R, -a, AUQ));
+    OK(VecDot(R, RP, &rho));
+    OK(VecNorm(R, NORM_2, &dp));
+    ksp->its = i + 1;
+    OK(checkpoint(ksp, i + 1, dp));
+    if (ksp->reason) break;
+    b = rho / rhoold;
+    OK(VecWAXPY(U, b, Q, R));
+    OK(VecAXPY(Q, b, P));
+    OK(VecWAXPY(P, b, Q, U));
+    OK(KSP_PCApplyBAorAB(ksp, P, V, T1));
+    rhoold = rho;
+  }
+  if (i >= ksp->max_it) ksp->reason = KSP_DIVERGED_ITS;
+  return 0;
+}
+PetscErrorCode KSPCreate_TFQMR(KSP ksp) {   /* tfqmr.c KSPCreate_TFQMR */
+  ksp->normsupporttable[KSP_NORM_PRECONDITIONED][PC_LEFT] = 2;
+  ksp->ops->setup = KSPSetUp_TFQMR;
+  ksp->ops->solve = KSPSolve_TFQMR;
+  return 0;
+}
+PetscErrorCode KSPCreate_CGS(KSP ksp) {   /* cgs.c KSPCreate_CGS */
+  ksp->normsupporttable[KSP_NORM_PRECONDITIONED][PC_LEFT] = 2;
+  ksp->ops->setup = KSPSetUp_CGS;
+  ksp->ops->solve = KSPSolve_CGS;
   return 0;
 }

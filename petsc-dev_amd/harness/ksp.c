@@ -58,7 +58,7 @@ static PetscErrorCode ksp_setup_norms(KSP ksp) {
   return 0;
 }
 
-#define MAXKSPTYPES 16
+#define MAXKSPTYPES 32
 static struct { char name[32]; PetscErrorCode (*fn)(KSP); } ksp_types[MAXKSPTYPES + 1];
 static int n_ksp_types = 0;
 PetscErrorCode KSPRegister(const char name[], const char path[], const char fname[], PetscErrorCode (*fn)(KSP)) {   /* src/ksp/ksp/interface/itregis.c */

@@ -50,6 +50,8 @@ PetscErrorCode PetscMiniInitialize(void) {
   ierr = KSPRegister(KSPCHEBYCHEV, 0, "KSPCreate_Chebychev", KSPCreate_Chebychev);CHKERRQ(ierr);
   ierr = KSPRegister(KSPRICHARDSON, 0, "KSPCreate_Richardson", KSPCreate_Richardson);CHKERRQ(ierr);
   ierr = KSPRegister(KSPMINRES, 0, "KSPCreate_MINRES", KSPCreate_MINRES);CHKERRQ(ierr);
+  ierr = KSPRegister(KSPTFQMR, 0, "KSPCreate_TFQMR", KSPCreate_TFQMR);CHKERRQ(ierr);
+  ierr = KSPRegister(KSPCGS, 0, "KSPCreate_CGS", KSPCreate_CGS);CHKERRQ(ierr);
   return 0;
 }
 

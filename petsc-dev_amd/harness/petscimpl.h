@@ -237,7 +237,7 @@ PetscErrorCode KSPInitialResidual(KSP ksp, Vec vsoln, Vec vt1, Vec vt2, Vec vres
 PetscErrorCode KSP_MatMult(KSP ksp, Mat A, Vec x, Vec y);
 PetscErrorCode KSP_PCApply(KSP ksp, Vec x, Vec y);
 PetscErrorCode KSP_PCApplyBAorAB(KSP ksp, Vec x, Vec y, Vec w);
-PetscErrorCode KSPCreate_CG(KSP), KSPCreate_GROPPCG(KSP), KSPCreate_PIPECG(KSP), KSPCreate_GMRES(KSP), KSPCreate_BCGS(KSP), KSPCreate_PREONLY(KSP), KSPCreate_Chebychev(KSP), KSPCreate_Richardson(KSP), KSPCreate_MINRES(KSP);
+PetscErrorCode KSPCreate_CG(KSP), KSPCreate_GROPPCG(KSP), KSPCreate_PIPECG(KSP), KSPCreate_GMRES(KSP), KSPCreate_BCGS(KSP), KSPCreate_PREONLY(KSP), KSPCreate_Chebychev(KSP), KSPCreate_Richardson(KSP), KSPCreate_MINRES(KSP), KSPCreate_TFQMR(KSP), KSPCreate_CGS(KSP);
 PetscErrorCode PCCreate_None(PC), PCCreate_Jacobi(PC), PCCreate_BJacobi(PC), PCCreate_ILU(PC), PCCreate_ICC(PC), PCCreate_SOR(PC);
 
 #include "petsckrylovfused.h"   /* the optional fused-kernel tables a Vec / Mat type may compose */

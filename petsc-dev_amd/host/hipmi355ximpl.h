@@ -362,5 +362,7 @@ PetscErrorCode KSPCreate_ChebychevHIPMI355X(KSP);
 PetscErrorCode KSPCreate_RichardsonHIPMI355X(KSP);
 PetscErrorCode KSPCreate_PIPECGHIPMI355X(KSP);
 PetscErrorCode KSPCreate_MINRESHIPMI355X(KSP);
+PetscErrorCode KSPCreate_TFQMRHIPMI355X(KSP);
+PetscErrorCode KSPCreate_CGSHIPMI355X(KSP);
 
 #endif

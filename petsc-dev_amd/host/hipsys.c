@@ -63,6 +63,8 @@ PetscErrorCode PetscHIPMI355XRegisterAll(void) {
   ierr = KSPRegister(KSPRICHARDSONHIPMI355X, 0, "KSPCreate_RichardsonHIPMI355X", KSPCreate_RichardsonHIPMI355X);CHKERRQ(ierr);
   ierr = KSPRegister(KSPPIPECGHIPMI355X, 0, "KSPCreate_PIPECGHIPMI355X", KSPCreate_PIPECGHIPMI355X);CHKERRQ(ierr);
   ierr = KSPRegister(KSPMINRESHIPMI355X, 0, "KSPCreate_MINRESHIPMI355X", KSPCreate_MINRESHIPMI355X);CHKERRQ(ierr);
+  ierr = KSPRegister(KSPTFQMRHIPMI355X, 0, "KSPCreate_TFQMRHIPMI355X", KSPCreate_TFQMRHIPMI355X);CHKERRQ(ierr);
+  ierr = KSPRegister(KSPCGSHIPMI355X, 0, "KSPCreate_CGSHIPMI355X", KSPCreate_CGSHIPMI355X);CHKERRQ(ierr);
 #if !defined(PETSCHIPMI355X_WITH_PETSC)
   /* the harness has no CPU types: the reference's generic names select the HIPMI355X implementation of the same shape
    * (with a real PETSc they keep meaning the CPU types, and -vec_type hipmi355x -mat_type aijhipmi355x select these) */

@@ -8,6 +8,8 @@
  *     KSPRICHARDSONHIPMI355X "richardsonhipmi355x"  Richardson (the sequence of KSPRICHARDSON, src/ksp/ksp/impls/rich/rich.c)
  *     KSPPIPECGHIPMI355X     "pipecghipmi355x"      pipelined CG (the sequence of KSPPIPECG, src/ksp/ksp/impls/cg/pipecg/pipecg.c:49-205)
  *     KSPMINRESHIPMI355X     "minreshipmi355x"      MINRES     (the sequence of KSPMINRES,  src/ksp/ksp/impls/minres/minres.c)
+ *     KSPTFQMRHIPMI355X      "tfqmrhipmi355x"       TFQMR      (the sequence of KSPTFQMR,   src/ksp/ksp/impls/tfqmr/tfqmr.c)
+ *     KSPCGSHIPMI355X        "cgshipmi355x"         CGS        (the sequence of KSPCGS,     src/ksp/ksp/impls/cgs/cgs.c)
  *
  * They compute what the reference's solvers compute -- same iterates, same residual history, same exits, bit for bit against
  * the op-by-op sequences (tests/test_host_gpu.py) -- but group the vector work between two reductions into the fused sweeps a
@@ -1077,6 +1079,193 @@ PetscErrorCode KSPCreate_MINRESHIPMI355X(KSP ksp) {
   ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "KSPGetFusedStepCounts_MinresHIP", (PetscVoidFunction)KSPGetFusedStepCounts_MinresHIP);CHKERRQ(ierr);
   return 0;
 }
+
+/* ================================================================================================ TFQMR and CGS
+ * The sequences of KSPSolve_TFQMR (src/ksp/ksp/impls/tfqmr/tfqmr.c) and KSPSolve_CGS (src/ksp/ksp/impls/cgs/cgs.c), one function for
+ * both (they share the recurrence over R, U, P, Q and the shadow residual RP): left preconditioning, the preconditioned norm; same
+ * iterates, histories and exits as the op-by-op types, bit for bit.  -ksp_tfqmr_fused / -ksp_cgs_fused <bool> (default true).  Around
+ * the two applications of K = B A an iteration is THREE sweeps of "VecTfqmrFusedOps_C" (include/petsckrylovfused.h):
+ *   - tfqmr_qt:     q = u - a v, t = u + q (CGS: and x += a t);
+ *   - tfqmr_resid:  r -= a K t with r'r and r'rp, which come home together: the host waits twice per iteration (s = v'rp, then
+ *                   these two) where the call-by-call sequence waits three times;
+ *   - tfqmr_update: TFQMR's two half steps on d and x, then the new u, q, p.  The half steps' residual estimates depend on scalars only,
+ *                   so the host runs both checkpoints FIRST and then launches the one sweep with the half steps that were taken (an
+ *                   exit inside them: without the tail).  A monitor that looks at x therefore sees the x of before this iteration's
+ *                   half steps; the history, the exits and the x returned are those of the call-by-call sequence.
+ * K goes the way of bcgs_apply: PCJACOBI on a matrix that offers it: d .* (A x) in the product's own kernel; PCJACOBI / PCNONE
+ * otherwise: PCApply fused with s = v'rp ("pmult_dot"); any other PC, or a null space: KSP_PCApplyBAorAB.  The three sweeps do not
+ * involve the PC.  Like bcgshipmi355x -- and unlike minreshipmi355x -- the types work on any vectors: without the table, with the option
+ * off, or when a sweep answers done = PETSC_FALSE, the same function makes the public calls of the sequence.
+ * s == 0 sets KSP_DIVERGED_BREAKDOWN where the reference divides.
+ * KSPHIPMI355XGetFusedStepCounts: (fused sweeps run, iterations in which a step ran through the public calls). */
+typedef struct { PetscBool fused, cgs; Vec dinv; PetscInt nsweeps, nopbyop; } KSP_TfqmrHIP;
+
+static const VecTfqmrFusedOps *vec_tfqmr_ops(Vec x) {
+  PetscVoidFunction f = NULL;
+  const VecTfqmrFusedOps *M;
+  if (PetscObjectQueryFunction((PetscObject)x, "VecTfqmrFusedOps_C", &f) || !f) return NULL;
+  M = ((VecTfqmrFusedOpsGetFn)f)();
+  return (M && M->tfqmr_qt && M->tfqmr_resid && M->tfqmr_update) ? M : NULL;
+}
+static PetscErrorCode KSPGetFusedStepCounts_TfqmrHIP(KSP ksp, PetscInt *fused, PetscInt *opbyop) {
+  const KSP_TfqmrHIP *td = (const KSP_TfqmrHIP *)ksp->data;
+  *fused = td->nsweeps; *opbyop = td->nopbyop;
+  return 0;
+}
+static PetscErrorCode KSPSetUp_TfqmrHIP(KSP ksp) { return KSPDefaultGetWork(ksp, ((KSP_TfqmrHIP *)ksp->data)->cgs ? 8 : 9); }   /* CGS: no D */
+static PetscErrorCode KSPSetFromOptions_TfqmrHIP(KSP ksp) {
+  KSP_TfqmrHIP *td = (KSP_TfqmrHIP *)ksp->data;
+  PetscInt iv = td->fused;
+  PetscErrorCode ierr = option_level(ksp, td->cgs ? "-ksp_cgs_fused" : "-ksp_tfqmr_fused", 0, 1, &iv);CHKERRQ(ierr);
+  td->fused = (PetscBool)iv;
+  return 0;
+}
+static PetscErrorCode KSPDestroy_TfqmrHIP(KSP ksp) {
+  KSP_TfqmrHIP *td = (KSP_TfqmrHIP *)ksp->data;
+  PetscErrorCode ierr;
+  if (!td) return 0;
+  ierr = VecDestroy(&td->dinv);CHKERRQ(ierr);
+  HipFree(td); ksp->data = NULL;
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
+  return 0;
+}
+
+/* out = K in by the route of bcgs_apply; other != NULL: *s = (out, other), in the preconditioner's pass where the types can */
+static PetscErrorCode tfqmr_apply(KSP ksp, Mat A, const VecKrylovFusedOps *F, HipPCKind pck, Vec d, Vec in, Vec out, Vec scratch, Vec other, PetscScalar *s) {
+  PetscErrorCode ierr;
+  PetscBool done = PETSC_FALSE, scaled = PETSC_FALSE;
+  if (F && pck != PCKIND_GENERAL) {
+    if (d) { ierr = mat_mult_scaled(A, d, in, out, &scaled);CHKERRQ(ierr); }
+    if (!scaled) {
+      ierr = KSP_MatMult(ksp, A, in, scratch);CHKERRQ(ierr);
+      if (other) { ierr = F->pmult_dot(out, scratch, d, other, s, &done);CHKERRQ(ierr); }
+      if (!done) { ierr = KSP_PCApply(ksp, scratch, out);CHKERRQ(ierr); }
+    }
+  } else { ierr = KSP_PCApplyBAorAB(ksp, in, out, scratch);CHKERRQ(ierr); }
+  if (other && !done) { ierr = VecDot(out, other, s);CHKERRQ(ierr); }
+  return 0;
+}
+
+static PetscErrorCode KSPSolve_TfqmrHIP(KSP ksp) {
+  PetscErrorCode ierr;
+  KSP_TfqmrHIP *td = (KSP_TfqmrHIP *)ksp->data;
+  const PetscBool cgs = td->cgs;
+  Vec X = ksp->vec_sol, B = ksp->vec_rhs;
+  Vec R = ksp->work[0], RP = ksp->work[1], V = ksp->work[2], T = ksp->work[3], Q = ksp->work[4], P = ksp->work[5], U = ksp->work[6], T1 = ksp->work[7];
+  Vec D = cgs ? NULL : ksp->work[8], AUQ = V;
+  const VecTfqmrFusedOps *M = td->fused ? vec_tfqmr_ops(X) : NULL;
+  const VecKrylovFusedOps *F = td->fused ? vec_fused_ops(X) : NULL;
+  HipPCKind pck = PCKIND_GENERAL;
+  Vec d = NULL;
+  Mat A;
+  PetscScalar rho = 0.0, rhoold, a, s, b, rr, etaold = 0.0, psiold = 0.0;
+  PetscReal dp, dpold, tau;
+  PetscInt i;
+
+  if (ksp->pc_side == PC_RIGHT) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s does not support right preconditioning", cgs ? KSPCGSHIPMI355X : KSPTFQMRHIPMI355X);
+  ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
+  if (F && !has_null_space(ksp)) { ierr = pc_diagonal_form(ksp, X, &td->dinv, &pck);CHKERRQ(ierr); if (pck == PCKIND_DIAGONAL) d = td->dinv; }
+  ksp->its = 0;
+  ierr = KSPInitialResidual(ksp, X, V, T, R, B);CHKERRQ(ierr);
+  ierr = VecNorm(R, NORM_2, &dp);CHKERRQ(ierr);
+  ierr = report(ksp, 0, dp);CHKERRQ(ierr);
+  ierr = KSPTestConvergence(ksp, 0, dp);CHKERRQ(ierr);
+  if (ksp->reason) return 0;
+  ierr = VecCopy(R, RP);CHKERRQ(ierr);
+  ierr = VecDot(R, RP, &rhoold);CHKERRQ(ierr);
+  ierr = VecCopy(R, U);CHKERRQ(ierr);
+  ierr = VecCopy(R, P);CHKERRQ(ierr);
+  ierr = tfqmr_apply(ksp, A, F, pck, d, P, V, T1, RP, &s);CHKERRQ(ierr);                /* V <- K P and s = V'RP of iteration 0 */
+  if (!cgs) { ierr = VecSet(D, 0.0);CHKERRQ(ierr); }
+  tau = dp; dpold = dp;
+
+  for (i = 0; i < ksp->max_it; i++) {
+    PetscBool done = PETSC_FALSE, have_rho = PETSC_FALSE, all_fused = PETSC_TRUE;
+    PetscScalar cfm[2] = {0.0, 0.0}, etam[2] = {0.0, 0.0};
+    PetscInt nhalves = 0, m;
+    if (s == 0.0) { ksp->reason = KSP_DIVERGED_BREAKDOWN; break; }
+    a = rhoold / s;
+    if (M) { ierr = M->tfqmr_qt(U, V, Q, T, cgs ? X : NULL, a, &done);CHKERRQ(ierr); }
+    if (done) td->nsweeps++;
+    else {
+      all_fused = PETSC_FALSE;
+      ierr = VecWAXPY(Q, -a, V, U);CHKERRQ(ierr);
+      ierr = VecWAXPY(T, 1.0, U, Q);CHKERRQ(ierr);
+      if (cgs) { ierr = VecAXPY(X, a, T);CHKERRQ(ierr); }
+    }
+    ierr = tfqmr_apply(ksp, A, F, pck, d, T, AUQ, T1, NULL, NULL);CHKERRQ(ierr);        /* AUQ <- K T */
+    done = PETSC_FALSE;
+    if (M) { ierr = M->tfqmr_resid(R, AUQ, RP, a, &rr, &rho, &done);CHKERRQ(ierr); }
+    if (done) { td->nsweeps++; dp = PetscSqrtReal(rr); have_rho = PETSC_TRUE; }
+    else {
+      all_fused = PETSC_FALSE;
+      ierr = VecAXPY(R, -a, AUQ);CHKERRQ(ierr);
+      if (cgs) { ierr = VecDot(R, RP, &rho);CHKERRQ(ierr); have_rho = PETSC_TRUE; }
+      ierr = VecNorm(R, NORM_2, &dp);CHKERRQ(ierr);
+    }
+    if (cgs) {
+      ksp->its = i + 1;
+      ierr = report(ksp, i + 1, dp);CHKERRQ(ierr);
+      ierr = KSPTestConvergence(ksp, i + 1, dp);CHKERRQ(ierr);
+    } else {
+      /* the two half steps: scalars and checkpoints now, their vector work in the sweep below */
+      for (m = 0; m < 2; m++) {
+        const PetscReal w = m ? dp : PetscSqrtReal(dp * dpold), psi = w / tau, cm = 1.0 / PetscSqrtReal(1.0 + psi * psi);
+        PetscReal dpest;
+        tau = tau * psi * cm;
+        etam[m] = cm * cm * a;
+        cfm[m] = psiold * psiold * etaold / a;
+        nhalves = m + 1;
+        dpest = PetscSqrtReal(m + 1.0) * tau;
+        ierr = report(ksp, i + 1, dpest);CHKERRQ(ierr);
+        ierr = KSPTestConvergence(ksp, i + 1, dpest);CHKERRQ(ierr);
+        if (ksp->reason) break;
+        etaold = etam[m]; psiold = psi;
+      }
+      if (!ksp->reason) ksp->its = i + 1;
+    }
+    if (cgs && ksp->reason) { if (!all_fused) td->nopbyop++; break; }
+    b = 0.0;
+    if (!ksp->reason) {
+      if (!have_rho) { ierr = VecDot(R, RP, &rho);CHKERRQ(ierr); }
+      b = rho / rhoold;
+    }
+    done = PETSC_FALSE;
+    if (M) { ierr = M->tfqmr_update(D, X, U, Q, R, P, nhalves, cfm[0], etam[0], cfm[1], etam[1], (PetscBool)!ksp->reason, b, &done);CHKERRQ(ierr); }
+    if (done) td->nsweeps++;
+    else {
+      all_fused = PETSC_FALSE;
+      for (m = 0; m < nhalves; m++) {
+        ierr = VecAYPX(D, cfm[m], m ? Q : U);CHKERRQ(ierr);
+        ierr = VecAXPY(X, etam[m], D);CHKERRQ(ierr);
+      }
+      if (!ksp->reason) {
+        ierr = VecWAXPY(U, b, Q, R);CHKERRQ(ierr);
+        ierr = VecAXPY(Q, b, P);CHKERRQ(ierr);
+        ierr = VecWAXPY(P, b, Q, U);CHKERRQ(ierr);
+      }
+    }
+    if (!all_fused) td->nopbyop++;
+    if (ksp->reason) break;
+    ierr = tfqmr_apply(ksp, A, F, pck, d, P, V, T1, RP, &s);CHKERRQ(ierr);              /* V <- K P and the next s = V'RP */
+    rhoold = rho; dpold = dp;
+  }
+  if (i >= ksp->max_it) ksp->reason = KSP_DIVERGED_ITS;
+  return 0;
+}
+
+static PetscErrorCode tfqmr_create(KSP ksp, PetscBool cgs) {
+  KSP_TfqmrHIP *td;
+  PetscErrorCode ierr = PetscMalloc(sizeof(*td), &td);CHKERRQ(ierr);
+  td->fused = PETSC_TRUE; td->cgs = cgs; td->dinv = NULL; td->nsweeps = 0; td->nopbyop = 0;
+  ksp->data = td;
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);    /* the one of KSPTFQMR and KSPCGS */
+  ksp->ops->setup = KSPSetUp_TfqmrHIP; ksp->ops->solve = KSPSolve_TfqmrHIP; ksp->ops->setfromoptions = KSPSetFromOptions_TfqmrHIP; ksp->ops->destroy = KSPDestroy_TfqmrHIP;
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "KSPGetFusedStepCounts_TfqmrHIP", (PetscVoidFunction)KSPGetFusedStepCounts_TfqmrHIP);CHKERRQ(ierr);
+  return 0;
+}
+PetscErrorCode KSPCreate_TFQMRHIPMI355X(KSP ksp) { return tfqmr_create(ksp, PETSC_FALSE); }
+PetscErrorCode KSPCreate_CGSHIPMI355X(KSP ksp) { return tfqmr_create(ksp, PETSC_TRUE); }
 
 typedef struct { PetscReal scale; Vec dinv; } KSP_RichHIP;
 

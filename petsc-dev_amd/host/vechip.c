@@ -1321,6 +1321,95 @@ static const VecMinresFusedOps *VecMinresFusedOps_HIP(void) {
   return &ops;
 }
 
+/* Fused forms for KSPSolve_TFQMR and KSPSolve_CGS (include/petsckrylovfused.h tfqmr_qt, tfqmr_resid, tfqmr_update).  *done = PETSC_FALSE
+ * and nothing touched unless every operand the form touches is a HIPMI355X vector of the same local size and no written vector is
+ * another operand of the call.  The accessors run the noted operations first, as everywhere. */
+static int tfqmr_operands_ok(Vec *all, int nall, int nwritten) {       /* the first nwritten of all[] are written; NULL: not touched */
+  Vec first = NULL;
+  for (int i = 0; i < nall; i++) {
+    if (!all[i]) continue;
+    if (!first) first = all[i];
+    if (!is_hip(all[i]) || all[i]->map->n != first->map->n) return 0;
+  }
+  for (int i = 0; i < nwritten; i++) for (int j = 0; j < nall; j++) if (j != i && all[i] && all[i] == all[j]) return 0;
+  return 1;
+}
+PetscErrorCode VecTfqmrQT_HIPMI355X(Vec u, Vec v, Vec q, Vec t, Vec x, PetscScalar a, PetscBool *done) {
+  PetscErrorCode ierr; DEVCTX;
+  Vec all[5] = {q, t, x, u, v};
+  const PetscScalar *du, *dv; PetscScalar *dq, *dt, *dx = NULL;
+  *done = PETSC_FALSE;
+  if (!u || !v || !q || !t || !tfqmr_operands_ok(all, 5, 3)) return 0;
+  ierr = VecHIPGetRead(u, &du);CHKERRQ(ierr);
+  ierr = VecHIPGetRead(v, &dv);CHKERRQ(ierr);
+  ierr = VecHIPGetWrite(q, &dq);CHKERRQ(ierr);
+  ierr = VecHIPGetWrite(t, &dt);CHKERRQ(ierr);
+  if (x) { ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr); }
+  CHKHIP(mi355x_vec_tfqmr_qt(dc->h, N_(q), a, du, dv, dq, dt, dx));
+  VecHIPRestoreWrite(q); VecHIPRestoreWrite(t);
+  HipStateIncrease(q); HipStateIncrease(t);
+  if (x && a != 0.0) { VecHIPRestoreWrite(x); HipStateIncrease(x); }
+  ierr = PetscLogFlops((x ? 5.0 : 3.0) * q->map->n);CHKERRQ(ierr);           /* 2n + n (+ 2n) */
+  *done = PETSC_TRUE;
+  return 0;
+}
+/* r'r and r'rp are all-reduced as every fused reduction is (reduce_finish2: RCCL, host-staged or one rank) */
+PetscErrorCode VecTfqmrResid_HIPMI355X(Vec r, Vec auq, Vec rp, PetscScalar a, PetscScalar *rr, PetscScalar *rrp, PetscBool *done) {
+  PetscErrorCode ierr; DEVCTX;
+  Vec all[3] = {r, auq, rp};
+  const PetscScalar *da, *drp; PetscScalar *dr, res[2]; double *out;
+  *done = PETSC_FALSE;
+  if (!r || !auq || !rp || !tfqmr_operands_ok(all, 3, 1)) return 0;
+  ierr = VecHIPGetRead(auq, &da);CHKERRQ(ierr);
+  ierr = VecHIPGetRead(rp, &drp);CHKERRQ(ierr);
+  ierr = VecHIPGetReadWrite(r, &dr);CHKERRQ(ierr);
+  ierr = reduce_target(r, dc, &out);CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_tfqmr_resid(dc->h, N_(r), a, da, drp, dr, out));
+  if (a != 0.0) { VecHIPRestoreWrite(r); HipStateIncrease(r); }
+  ierr = reduce_finish2(r, dc, 2, 2, 0, res);CHKERRQ(ierr);
+  *rr = res[0]; *rrp = res[1];
+  ierr = PetscLogFlops(6.0 * r->map->n);CHKERRQ(ierr);                         /* 2n + 2n + 2n */
+  *done = PETSC_TRUE;
+  return 0;
+}
+PetscErrorCode VecTfqmrUpdate_HIPMI355X(Vec d, Vec x, Vec u, Vec q, Vec r, Vec p, PetscInt nhalves, PetscScalar cf0, PetscScalar eta0, PetscScalar cf1, PetscScalar eta1,
+                                        PetscBool tail, PetscScalar b, PetscBool *done) {
+  PetscErrorCode ierr; DEVCTX;
+  Vec all[6];
+  const PetscScalar *dr = NULL; PetscScalar *dd = NULL, *dx = NULL, *du = NULL, *dq = NULL, *dp_ = NULL;
+  *done = PETSC_FALSE;
+  if (nhalves < 0 || nhalves > 2) return 0;
+  if (nhalves == 0) d = x = NULL;                                       /* what the form does not touch is not looked at */
+  if (nhalves < 2 && !tail) q = NULL;
+  if (nhalves == 0 && !tail) u = NULL;
+  if (!tail) r = p = NULL;
+  if ((nhalves >= 1 && (!d || !x || !u)) || (nhalves == 2 && !q) || (tail && (!u || !q || !r || !p))) return 0;
+  all[0] = d; all[1] = x; all[2] = u; all[3] = q; all[4] = p; all[5] = r;
+  if (!tfqmr_operands_ok(all, 6, 5)) return 0;
+  if (nhalves == 0 && !tail) { *done = PETSC_TRUE; return 0; }
+  if (d) { ierr = VecHIPGetReadWrite(d, &dd);CHKERRQ(ierr); }
+  if (x) { ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr); }
+  if (u) { ierr = VecHIPGetReadWrite(u, &du);CHKERRQ(ierr); }
+  if (q) { ierr = VecHIPGetReadWrite(q, &dq);CHKERRQ(ierr); }
+  if (r) { ierr = VecHIPGetRead(r, &dr);CHKERRQ(ierr); }
+  if (p) { ierr = VecHIPGetReadWrite(p, &dp_);CHKERRQ(ierr); }
+  CHKHIP(mi355x_vec_tfqmr_update(dc->h, N_(u), (int)nhalves, cf0, eta0, cf1, eta1, tail ? 1 : 0, b, dd, dx, du, dq, dr, dp_));
+  if (d) { VecHIPRestoreWrite(d); HipStateIncrease(d); }
+  if (x && (eta0 != 0.0 || (nhalves == 2 && eta1 != 0.0))) { VecHIPRestoreWrite(x); HipStateIncrease(x); }
+  if (tail) {
+    VecHIPRestoreWrite(u); HipStateIncrease(u); VecHIPRestoreWrite(p); HipStateIncrease(p);
+    if (b != 0.0) { VecHIPRestoreWrite(q); HipStateIncrease(q); }
+  }
+  ierr = PetscLogFlops((4.0 * nhalves + (tail ? 6.0 : 0.0)) * u->map->n);CHKERRQ(ierr);
+  *done = PETSC_TRUE;
+  return 0;
+}
+/* "VecTfqmrFusedOps_C": the sweeps of TFQMR and CGS */
+static const VecTfqmrFusedOps *VecTfqmrFusedOps_HIP(void) {
+  static const VecTfqmrFusedOps ops = {VecTfqmrQT_HIPMI355X, VecTfqmrResid_HIPMI355X, VecTfqmrUpdate_HIPMI355X};
+  return &ops;
+}
+
 /* the *_local slots of struct _VecOps (vecimpl.h:262-266): the same device reductions without the step across ranks;
  * NORM_2 returns the root of the local sum, as VecNorm_Seq does for VecNormBegin (comb.c squares it again) */
 static PetscErrorCode VecDot_HIP_local(Vec x, Vec y, PetscScalar *val) { hip_local_only = 1; PetscErrorCode ierr = VecDot_HIP(x, y, val); hip_local_only = 0; return ierr; }
@@ -1513,6 +1602,7 @@ static PetscErrorCode VecCreate_HIP_common(Vec v, const char *tname) {
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecSplitReductionOps_C", "VecSplitReductionOps_HIP", (PetscVoidFunction)VecSplitReductionOps_HIP);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecPipelinedCGFusedOps_C", "VecPipelinedCGFusedOps_HIP", (PetscVoidFunction)VecPipelinedCGFusedOps_HIP);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecMinresFusedOps_C", "VecMinresFusedOps_HIP", (PetscVoidFunction)VecMinresFusedOps_HIP);CHKERRQ(ierr);
+  ierr = PetscObjectComposeFunction((PetscObject)v, "VecTfqmrFusedOps_C", "VecTfqmrFusedOps_HIP", (PetscVoidFunction)VecTfqmrFusedOps_HIP);CHKERRQ(ierr);
   return 0;
 }
 

@@ -472,7 +472,7 @@ class KSP:
         lib().KSPRichardsonSetScale(self.h, float(scale))
 
     def fused_step_counts(self):
-        """KSPHIPMI355XGetFusedStepCounts: (fused, opbyop) update steps of the pipelined CG types since the type was set; minreshipmi355x: (Lanczos sweeps run, 0); (0, 0) for any other"""
+        """KSPHIPMI355XGetFusedStepCounts: (fused, opbyop) update steps of the pipelined CG types since the type was set; minreshipmi355x: (Lanczos sweeps run, 0); tfqmrhipmi355x / cgshipmi355x: (fused sweeps run, iterations with a step run op by op); (0, 0) for any other"""
         f = i32(); o = i32()
         lib().KSPHIPMI355XGetFusedStepCounts(self.h, C.byref(f), C.byref(o))
         return f.value, o.value
