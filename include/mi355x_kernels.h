@@ -486,6 +486,35 @@ int mi355x_ilu0_factor_create_fill(mi355x_handle_t h, int n, const int *ai_host,
                                    const int *bdiag, int nlev, const int *levptr, const int *rows, int nblk, const int *blk,
                                    mi355x_ilu0_factor_t *ctx);
 
+/* ---- Block ILU(k) of a BAIJ matrix: level-scheduled block triangular solves, host numeric factorisation (csrc/bilu.hip) ----
+ * MatSolve_SeqBAIJ_<bs>_NaturalOrdering  src/mat/impls/baij/seq/baijfact2.c on the point factor's layout over BLOCK rows and columns (bi,
+ * bj, bdiag as above; mi355x_iluk_symbolic_host on the block pattern builds it) with ba holding one column-major bs x bs block per
+ * stored entry and the INVERTED diagonal block at bdiag[i], 2 <= bs <= 7.  One launch per dependency level, `rows` the block rows of
+ * the level (device array); one lane per scalar row, the bs lanes of a block row in one wavefront.
+ *   _lower_level  component r of block row i: s = b[bs i + r]; for every stored L block (i,k) in storage order, with v the block and
+ *             x_k the solution of block row k, s = s - (v[r] x_k[0] + v[r + bs] x_k[1] + ... + v[r + (bs-1) bs] x_k[bs-1]) -- the
+ *             products summed left to right, then one subtraction; x[bs i + r] = s.  b may alias x.
+ *   _upper_level  the same accumulation over the strict-upper blocks bdiag[i+1]+1 .. bdiag[i]-1 starting from x[bs i + r], then
+ *             x[bs i + r] = d[r] s_0 + d[r + bs] s_1 + ... left to right, d the inverted diagonal block, s_c the sums of the row's
+ *             bs components.
+ *   bs outside 2..7: hipErrorInvalidValue, nothing launched.  nrows <= 0 launches nothing.  Padding lanes and rows past nrows neither
+ *   load nor store.  No hand-off between workgroups: the kernel boundary between levels is the only synchronisation.
+ *   _numeric_host  MatLUFactorNumeric_SeqBAIJ_<bs>_NaturalOrdering restated on HOST arrays, one thread, no device call: A's block
+ *             CSR (ai, aj, aa; mbs block rows) into ba on a factor pattern that contains A's.  Block row i: every work block of the
+ *             factor row starts at +0.0 with A's blocks copied in; for every L block (i,k) in ascending k, fill included, that is not
+ *             entirely == 0.0: M = W_k D_k^-1, stored as the L block, and W_j = W_j - M U_kj for every strict-upper block (k,j) of
+ *             row k whose column the factor row i holds -- every entry of a block product a left-to-right sum of bs products, then
+ *             one subtraction; the L and U blocks are stored; D_i^-1 by LINPACK dgefa + dgedi (mi355x_block_inverse.h) in the
+ *             diagonal's slot.  A zero pivot there: hipErrorUnknown with the scalar row in *zero_pivot_row (may be NULL; -1
+ *             otherwise) and the block rows before it as computed.  hipErrorInvalidValue for bs outside 2..7, a NULL array, a factor
+ *             row whose diagonal slot does not name the row, and a block of A the factor's pattern lacks. */
+int mi355x_bilu_lower_level(mi355x_handle_t h, int nrows, const int *rows, int bs, const int *bi, const int *bj, const double *ba,
+                            const double *b, double *x);
+int mi355x_bilu_upper_level(mi355x_handle_t h, int nrows, const int *rows, int bs, const int *bj, const double *ba, const int *bdiag,
+                            double *x);
+int mi355x_bilu_numeric_host(int mbs, int bs, const int *ai, const int *aj, const double *aa, const int *bi, const int *bj,
+                             const int *bdiag, double *ba, int *zero_pivot_row);
+
 /* ---- SOR / SSOR sweeps on a square CSR matrix as it is (csrc/sor.hip) ----
  * MatSOR_SeqAIJ  src/mat/impls/aij/seq/aij.c:1463 with the point sweeps (never the inode routine), level by level: one lane per row, a
  * row's products subtracted in storage order, each product and each difference rounded -- x carries the sequential loop's bits.

@@ -158,6 +158,9 @@ KERNEL_API = {
     "mi355x_ilu0_factor_info": [vp, pi32, pi32],
     "mi355x_iluk_symbolic_host": [i32, vp, vp, i32, vp, vp, vp, vp, pi32],
     "mi355x_ilu0_factor_create_fill": [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, C.POINTER(vp)],
+    "mi355x_bilu_lower_level": [vp, i32, vp, i32, vp, vp, vp, vp, vp],
+    "mi355x_bilu_upper_level": [vp, i32, vp, i32, vp, vp, vp, vp],
+    "mi355x_bilu_numeric_host": [i32, i32, vp, vp, vp, vp, vp, vp, vp, pi32],
     "mi355x_sor_levels_host": [i32, vp, vp, vp, pi32],
     "mi355x_sor_plan_create": [vp, i32, vp, vp, i32, C.POINTER(vp), pi32],
     "mi355x_sor_plan_destroy": [vp],

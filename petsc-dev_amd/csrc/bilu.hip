@@ -1,0 +1,174 @@
+// Block ILU(k) of MATSEQBAIJ: level-scheduled block triangular solves on the device and the numeric factorisation restated on the
+// host (mi355x_kernels.h, "Block ILU").  Reference: MatSolve_SeqBAIJ_<bs>_NaturalOrdering (src/mat/impls/baij/seq/baijfact2.c) and
+// MatLUFactorNumeric_SeqBAIJ_<bs>_NaturalOrdering (baijfact*.c) on the factor layout of the point ILU (aijfact.c:1628-1700) with
+// one bs x bs column-major block per stored entry: L block rows forward from bi, U block rows stored from the last row backwards,
+// each followed by its INVERTED diagonal block at bdiag[i].
+//
+// Solves.  One lane per scalar row; the bs lanes of a block row are one group, padded to a power of two (2, 4 or 8 lanes) so that
+// 256 / width groups tile a workgroup and no group straddles a wavefront.  A lane walks the stored blocks of its block row in
+// storage order; the bs solution values of the dependency block are loaded by every lane of the group from the same addresses (one
+// broadcast load each), the lane's own row of the block is a strided read of ba.  The upper solve ends in the product with the
+// inverted diagonal block, which needs the group's bs sums: they travel by cross-lane shuffles, never through memory.  Padding
+// lanes and the groups past nrows take part in the shuffles with an empty block range and neither load nor store.
+// Rows of one dependency level do not read each other, a kernel boundary separates the levels: nothing here waits on anything.
+#include "common.hpp"
+#include "mi355x_block_inverse.h"
+#include <string.h>
+#include <stdlib.h>
+
+#define BILU_MIN_BS 2
+#define BILU_MAX_BS 7
+
+// lanes of a block row's group: the smallest power of two >= BS
+template <int BS> struct BiluGroup { static constexpr int W = BS <= 2 ? 2 : (BS <= 4 ? 4 : 8); };
+
+// s - (v[r] x[0] + v[r + BS] x[1] + ...): row r of one column-major block times the dependency block's values, the products summed
+// left to right, then one subtraction (-ffp-contract=off: every product and every sum rounded)
+template <int BS> __device__ __forceinline__ double bilu_minus_row(double s, const double *__restrict__ v, int r, const double *xk) {
+  double t = v[r] * xk[0];
+#pragma unroll
+  for (int c = 1; c < BS; ++c) t = t + v[r + c * BS] * xk[c];
+  return s - t;
+}
+
+// the accumulation both solves share: the blocks q0 .. q1 - 1 of ba against the x values their block columns name
+template <int BS> __device__ __forceinline__ double bilu_sweep(double s, int q0, int q1, int r, const int *__restrict__ bj,
+                                                               const double *__restrict__ ba, const double *x) {
+  for (int q = q0; q < q1; ++q) s = bilu_minus_row<BS>(s, ba + (size_t)q * (BS * BS), r, x + (size_t)bj[q] * BS);
+  return s;
+}
+
+// UPPER = false: x_i = b_i - sum_k L_ik x_k (bdiag unused).  UPPER = true: x_i = D_i^-1 (x_i - sum_k U_ik x_k) in place.
+template <int BS, bool UPPER>
+__global__ __launch_bounds__(MI355X_BLOCK) void bilu_level_kernel(int nrows, const int *__restrict__ rows, const int *__restrict__ bi,
+                                                                  const int *__restrict__ bj, const double *__restrict__ ba,
+                                                                  const int *__restrict__ bdiag, const double *b, double *x) {
+  constexpr int W = BiluGroup<BS>::W;
+  const int t = blockIdx.x * MI355X_BLOCK + threadIdx.x;
+  const int g = t / W, r = t & (W - 1);
+  const bool live = g < nrows && r < BS;
+  int i = 0, q0 = 0, q1 = 0;
+  double s = 0.0;
+  if (live) {
+    i = rows[g];
+    if (UPPER) { q0 = bdiag[i + 1] + 1; q1 = bdiag[i]; s = x[(size_t)i * BS + r]; }
+    else { q0 = bi[i]; q1 = bi[i + 1]; s = b[(size_t)i * BS + r]; }
+  }
+  s = bilu_sweep<BS>(s, q0, q1, r, bj, ba, x);      // (an idle lane: an empty range)
+  if (UPPER) {
+    // every lane of the wavefront is here: the group's sums, lane by lane
+    const int first = (threadIdx.x & (MI355X_WAVE - 1)) & ~(W - 1);
+    double sv[BS];
+#pragma unroll
+    for (int c = 0; c < BS; ++c) sv[c] = __shfl(s, first + c, MI355X_WAVE);
+    if (live) {
+      const double *__restrict__ d = ba + (size_t)q1 * (BS * BS);     // the inverted diagonal block at bdiag[i]
+      double acc = d[r] * sv[0];
+#pragma unroll
+      for (int c = 1; c < BS; ++c) acc = acc + d[r + c * BS] * sv[c];
+      x[(size_t)i * BS + r] = acc;
+    }
+  } else if (live) x[(size_t)i * BS + r] = s;
+}
+
+template <int BS, bool UPPER>
+static int bilu_launch(mi355x_handle_t h, int nrows, const int *rows, const int *bi, const int *bj, const double *ba, const int *bdiag,
+                       const double *b, double *x) {
+  constexpr int per_block = MI355X_BLOCK / BiluGroup<BS>::W;       // block rows per workgroup
+  const unsigned grid = (unsigned)(((long)nrows + per_block - 1) / per_block);
+  hipLaunchKernelGGL((bilu_level_kernel<BS, UPPER>), dim3(grid), dim3(MI355X_BLOCK), 0, h->stream, nrows, rows, bi, bj, ba, bdiag, b, x);
+  MI355X_LAUNCH_CHECK();
+  return 0;
+}
+template <bool UPPER>
+static int bilu_dispatch(mi355x_handle_t h, int nrows, const int *rows, int bs, const int *bi, const int *bj, const double *ba,
+                         const int *bdiag, const double *b, double *x) {
+  if (bs < BILU_MIN_BS || bs > BILU_MAX_BS) return (int)hipErrorInvalidValue;
+  if (nrows <= 0) return 0;
+  switch (bs) {
+    case 2: return bilu_launch<2, UPPER>(h, nrows, rows, bi, bj, ba, bdiag, b, x);
+    case 3: return bilu_launch<3, UPPER>(h, nrows, rows, bi, bj, ba, bdiag, b, x);
+    case 4: return bilu_launch<4, UPPER>(h, nrows, rows, bi, bj, ba, bdiag, b, x);
+    case 5: return bilu_launch<5, UPPER>(h, nrows, rows, bi, bj, ba, bdiag, b, x);
+    case 6: return bilu_launch<6, UPPER>(h, nrows, rows, bi, bj, ba, bdiag, b, x);
+    default: return bilu_launch<7, UPPER>(h, nrows, rows, bi, bj, ba, bdiag, b, x);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- numeric factorisation, host
+// c = a b for column-major bs x bs blocks: every entry a left-to-right sum of bs products
+static void bilu_block_mult(int bs, const double *a, const double *b, double *c) {
+  for (int col = 0; col < bs; ++col)
+    for (int r = 0; r < bs; ++r) {
+      double t = a[r] * b[col * bs];
+      for (int k = 1; k < bs; ++k) t = t + a[r + k * bs] * b[k + col * bs];
+      c[r + col * bs] = t;
+    }
+}
+// w = w - m u: the same sums, then one subtraction per entry
+static void bilu_block_minus_mult(int bs, double *w, const double *m, const double *u) {
+  for (int col = 0; col < bs; ++col)
+    for (int r = 0; r < bs; ++r) {
+      double t = m[r] * u[col * bs];
+      for (int k = 1; k < bs; ++k) t = t + m[r + k * bs] * u[k + col * bs];
+      w[r + col * bs] = w[r + col * bs] - t;
+    }
+}
+
+extern "C" {
+
+int mi355x_bilu_lower_level(mi355x_handle_t h, int nrows, const int *rows, int bs, const int *bi, const int *bj, const double *ba,
+                            const double *b, double *x) {
+  return bilu_dispatch<false>(h, nrows, rows, bs, bi, bj, ba, nullptr, b, x);
+}
+
+int mi355x_bilu_upper_level(mi355x_handle_t h, int nrows, const int *rows, int bs, const int *bj, const double *ba, const int *bdiag,
+                            double *x) {
+  return bilu_dispatch<true>(h, nrows, rows, bs, nullptr, bj, ba, bdiag, nullptr, x);
+}
+
+int mi355x_bilu_numeric_host(int mbs, int bs, const int *ai, const int *aj, const double *aa, const int *bi, const int *bj,
+                             const int *bdiag, double *ba, int *zero_pivot_row) {
+  if (zero_pivot_row) *zero_pivot_row = -1;
+  if (bs < BILU_MIN_BS || bs > BILU_MAX_BS || mbs < 0 || !ai || !bi || !bdiag) return (int)hipErrorInvalidValue;
+  if (mbs == 0) return 0;
+  if (!aj || !aa || !bj || !ba) return (int)hipErrorInvalidValue;
+  const size_t bs2 = (size_t)bs * bs;
+  // one work block per block column; in_row[j] == i: block column j belongs to the factor's row i
+  double *work = (double *)malloc(sizeof(double) * bs2 * (size_t)mbs);
+  int *in_row = (int *)malloc(sizeof(int) * (size_t)mbs);
+  if (!work || !in_row) { free(work); free(in_row); return (int)hipErrorOutOfMemory; }
+  for (int j = 0; j < mbs; ++j) in_row[j] = -1;
+  double m[BILU_MAX_BS * BILU_MAX_BS];
+  int rc = 0;
+  for (int i = 0; i < mbs && !rc; ++i) {
+    const int l0 = bi[i], l1 = bi[i + 1], u0 = bdiag[i + 1] + 1, u1 = bdiag[i];     // L blocks, strict-upper blocks; the diagonal at u1
+    if (l0 > l1 || u0 > u1 || bj[u1] != i) { rc = (int)hipErrorInvalidValue; break; }
+    for (int q = l0; q < l1 && !rc; ++q) { if (bj[q] < 0 || bj[q] >= i) rc = (int)hipErrorInvalidValue; else { in_row[bj[q]] = i; memset(work + bs2 * bj[q], 0, sizeof(double) * bs2); } }
+    for (int q = u0; q <= u1 && !rc; ++q) { if (bj[q] < i || bj[q] >= mbs) rc = (int)hipErrorInvalidValue; else { in_row[bj[q]] = i; memset(work + bs2 * bj[q], 0, sizeof(double) * bs2); } }
+    for (int q = ai[i]; q < ai[i + 1] && !rc; ++q) {                                 // A's blocks: the factor's pattern contains A's
+      if (aj[q] < 0 || aj[q] >= mbs || in_row[aj[q]] != i) rc = (int)hipErrorInvalidValue;
+      else memcpy(work + bs2 * aj[q], aa + bs2 * q, sizeof(double) * bs2);
+    }
+    if (rc) break;
+    for (int q = l0; q < l1; ++q) {                                                  // ascending k, fill included
+      const int k = bj[q];
+      double *wk = work + bs2 * k;
+      bool any = false;
+      for (size_t e = 0; e < bs2; ++e) if (wk[e] != 0.0) { any = true; break; }
+      if (!any) continue;
+      bilu_block_mult(bs, wk, ba + bs2 * bdiag[k], m);                               // M = W_k D_k^-1
+      memcpy(wk, m, sizeof(double) * bs2);
+      for (int p = bdiag[k + 1] + 1; p < bdiag[k]; ++p)
+        if (in_row[bj[p]] == i) bilu_block_minus_mult(bs, work + bs2 * bj[p], m, ba + bs2 * p);
+    }
+    for (int q = l0; q < l1; ++q) memcpy(ba + bs2 * q, work + bs2 * bj[q], sizeof(double) * bs2);
+    for (int q = u0; q <= u1; ++q) memcpy(ba + bs2 * q, work + bs2 * bj[q], sizeof(double) * bs2);
+    const int z = mi355x_block_inverse(bs, ba + bs2 * u1);                           // D_i^-1 in the diagonal's slot
+    if (z) { if (zero_pivot_row) *zero_pivot_row = i * bs + z - 1; rc = (int)hipErrorUnknown; }
+  }
+  free(work); free(in_row);
+  return rc;
+}
+
+}  // extern "C"

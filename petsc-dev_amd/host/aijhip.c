@@ -2069,6 +2069,7 @@ static PetscErrorCode MatDestroy_SeqAIJHIP(Mat A) {   /* free the mirror and zer
   if (SD(A)) {
     Mat_SeqAIJHIP *d = SD(A);
     (void)HipTriFactorsDestroy(&d->tri);    /* a factored matrix: its triangular factors */
+    (void)HipBlockFactorsDestroy(&d->btri); /* ... of a BAIJ operator: its block triangular factors (host/bilu.c) */
     product_free(A);                        /* the result of a product: its plan and inner results */
     device_free(A);
     if (d->time_ev) { for (PetscInt k = 0; k < 2 * d->time_cap; k++) mi355x_event_destroy(d->time_ev[k]); HipFree(d->time_ev); }
@@ -2142,6 +2143,9 @@ static PetscErrorCode create_common(Mat B, const char *tname, PetscInt bs) {
     ierr = PetscObjectComposeFunction((PetscObject)B, "MatSeqAIJSetPreallocation_C", "MatSeqAIJSetPreallocation_SeqAIJHIP", (PetscVoidFunction)MatSeqAIJSetPreallocation_SeqAIJHIP);CHKERRQ(ierr);
     ierr = PetscObjectComposeFunction((PetscObject)B, "MatSeqAIJSetPreallocationCSR_C", "MatSeqAIJSetPreallocationCSR_SeqAIJHIP", (PetscVoidFunction)MatSeqAIJSetPreallocationCSR_SeqAIJHIP);CHKERRQ(ierr);
   } else {
+    /* block ILU(k) of the block type (host/bilu.c): ILU only; ICC and LU answer PETSC_ERR_SUP */
+    ierr = PetscObjectComposeFunction((PetscObject)B, "MatGetFactor_petsc_C", "MatGetFactor_seqbaijhipmi355x_petsc", (PetscVoidFunction)MatGetFactor_seqbaijhipmi355x_petsc);CHKERRQ(ierr);
+    ierr = PetscObjectComposeFunction((PetscObject)B, "MatGetFactorAvailable_petsc_C", "MatGetFactorAvailable_seqbaijhipmi355x_petsc", (PetscVoidFunction)MatGetFactorAvailable_seqbaijhipmi355x_petsc);CHKERRQ(ierr);
     ierr = PetscObjectComposeFunction((PetscObject)B, "MatSeqBAIJSetPreallocationCSR_C", "MatSeqBAIJSetPreallocationCSR_SeqBAIJHIP", (PetscVoidFunction)MatSeqBAIJSetPreallocationCSR_SeqBAIJHIP);CHKERRQ(ierr);
   }
   return 0;

@@ -212,6 +212,26 @@ PetscErrorCode MatICCFactorSymbolic_SeqAIJHIP(Mat F, Mat A, IS perm, const MatFa
 PetscErrorCode MatGetFactor_seqaijhipmi355x_petsc(Mat A, MatFactorType ftype, Mat *B);
 PetscErrorCode MatGetFactorAvailable_seqaijhipmi355x_petsc(Mat A, MatFactorType ftype, PetscBool *flg);
 
+/* ---- block ILU(k) of MATSEQBAIJHIPMI355X (host/bilu.c; harness flavour -- inside a PETSc tree the BAIJ type composes no factor): what
+ * MatGetFactor(A, "petsc", MAT_FACTOR_ILU, &F) hangs on F for a block matrix.  The factor in the point factor's layout over block rows
+ * and columns, one column-major bs x bs block per stored entry, the inverted diagonal block at bdiag[i].  Two forms, each released by
+ * one function: the pattern side (host layout, level lists, their device copies; once per pattern) and the values (host ba, d_ba). ---- */
+typedef struct {
+  PetscInt mbs, bs, levels, nzb, nzbA;                     /* block rows, block size, levels of fill, stored blocks of the factor / of the operator */
+  struct {
+    PetscInt *bi, *bj, *bdiag;                             /* host layout (mi355x_iluk_symbolic_host on the block pattern) */
+    PetscInt nlevL, nlevU, *levptrL, *levptrU;             /* dependency levels of L / U over block rows; where each level's rows start (host) */
+    PetscInt *d_bi, *d_bj, *d_bdiag, *d_rowsL, *d_rowsU;   /* device: the layout, the block rows ordered by level */
+    int stale; unsigned long long gen;                     /* a new symbolic phase was asked for; serial number of the operator's pattern upload the layout was built for */
+  } pat;
+  PetscScalar *ba, *d_ba;                                  /* the factor's (nzb + 1) bs^2 values, host and device */
+  PetscInt symbolic_builds, numeric_runs;                  /* pattern passes / numeric factorisations so far */
+  int factored_state; void *factored_of;                   /* operator and operator state of the last numeric factorisation */
+} HipBlockFactors;
+PetscErrorCode HipBlockFactorsDestroy(HipBlockFactors **f);
+PetscErrorCode MatGetFactor_seqbaijhipmi355x_petsc(Mat A, MatFactorType ftype, Mat *B);
+PetscErrorCode MatGetFactorAvailable_seqbaijhipmi355x_petsc(Mat A, MatFactorType ftype, PetscBool *flg);
+
 /* one device form of the product: (B)CSR arrays (bs = 1: CSR) with the row-block plan over their value stream, and the column-tiled layout
  * when one was chosen for it.  The device copy of the matrix is one; the forms derived from it (the cached transpose, the blocked companion
  * and its block transpose) hold the matrix's values in another order, a = d_a[perm], refreshed by one gather (host/aijhip.c) */
@@ -293,6 +313,7 @@ typedef struct {
   PetscBool baij_parent;
 #else
   HipTriFactors *tri;        /* a factored matrix (A->factortype != MAT_FACTOR_NONE): its triangular factors on the device */
+  HipBlockFactors *btri;     /* ... of a BAIJ operator: its block triangular factors (host/bilu.c); at most one of the two is set */
 #endif
 } Mat_SeqAIJHIP;
 /* where a factored matrix keeps its device-side factors: inside PETSc the factor is the PARENT's matrix (MATSEQAIJ for ILU, MATSEQSBAIJ
@@ -301,6 +322,7 @@ typedef struct {
 #define HipTriGet(F) ((HipTriFactors *)(F)->spptr)
 #else
 #define HipTriGet(F) (((Mat_SeqAIJHIP *)(F)->spptr)->tri)
+#define HipBlockGet(F) (((Mat_SeqAIJHIP *)(F)->spptr)->btri)
 #endif
 #if defined(PETSCHIPMI355X_WITH_PETSC)
 #define HipAIJGet(A) (&((Mat_SeqAIJHIP *)(A)->spptr)->view)

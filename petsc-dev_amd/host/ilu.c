@@ -1111,7 +1111,18 @@ PetscErrorCode PCILUGetSweeps_HIPMI355X(PC pc, PetscInt *k) {
  * levels, context) and numeric factorisations of this factor so far */
 PetscErrorCode PCILUGetNumeric_HIPMI355X(PC pc, PetscInt *on_device, PetscInt *symbolic_builds, PetscInt *numeric_runs) {
   HipTriFactors *f;
-  PetscErrorCode ierr = pc_factors(pc, MAT_FACTOR_ILU, &f);CHKERRQ(ierr);
+  PetscErrorCode ierr;
+#if !defined(PETSCHIPMI355X_WITH_PETSC)
+  { Mat F = NULL;   /* the block factor of a BAIJ operator (host/bilu.c) keeps the same two counts; it is always factored on the host */
+    ierr = PCFactorGetMatrix(pc, &F);CHKERRQ(ierr);
+    if (F && F->factortype && F->spptr && HipBlockGet(F)) {
+      if (on_device) *on_device = 0;
+      if (symbolic_builds) *symbolic_builds = HipBlockGet(F)->symbolic_builds;
+      if (numeric_runs) *numeric_runs = HipBlockGet(F)->numeric_runs;
+      return 0;
+    } }
+#endif
+  ierr = pc_factors(pc, MAT_FACTOR_ILU, &f);CHKERRQ(ierr);
   if (on_device) *on_device = f->dev.dfac ? 1 : 0;
   if (symbolic_builds) *symbolic_builds = f->symbolic_builds;
   if (numeric_runs) *numeric_runs = f->numeric_runs;

@@ -4,52 +4,13 @@
  *            (dgefa.c, dgefa2.c .. dgefa7.c, dgedi.c) -- then one upload of the inverted blocks;
  *   apply  : PCApply_PBJacobi_N (pbjacobi.c:20-200), one kernel (mi355x_pbjacobi_apply), the reference's row sums. */
 #include "hipmi355ximpl.h"
+#include "mi355x_block_inverse.h"   /* dgefa + dgedi, shared with the block ILU numeric pass (csrc/bilu.hip) */
 
 typedef struct {
   PetscInt mbs, bs;
   PetscScalar *d_idiag;     /* mbs * bs * bs, HBM */
   int setup_state;
 } PC_PBJacobi_HIP;
-
-/* in-place inverse of a column-major n x n block (n <= 16); returns the 1-based zero-pivot row or 0 */
-static int block_inverse(int n, PetscScalar *a) {
-  int ipvt[16]; PetscScalar work[16];
-#define E(i, j) a[(i) + (j) * n]
-  for (int k = 0; k + 1 < n; k++) {                       /* dgefa: elimination with partial pivoting, multipliers negated */
-    int l = k; PetscReal big = PetscAbsScalar(E(k, k));
-    for (int i = k + 1; i < n; i++) if (PetscAbsScalar(E(i, k)) > big) { big = PetscAbsScalar(E(i, k)); l = i; }
-    ipvt[k] = l;
-    if (E(l, k) == 0.0) return k + 1;
-    if (l != k) { PetscScalar t = E(l, k); E(l, k) = E(k, k); E(k, k) = t; }
-    const PetscScalar m = -1. / E(k, k);
-    for (int i = k + 1; i < n; i++) E(i, k) *= m;
-    for (int j = k + 1; j < n; j++) {
-      const PetscScalar t = E(l, j);
-      if (l != k) { E(l, j) = E(k, j); E(k, j) = t; }
-      for (int i = k + 1; i < n; i++) E(i, j) += t * E(i, k);
-    }
-  }
-  ipvt[n - 1] = n - 1;
-  if (E(n - 1, n - 1) == 0.0) return n;
-  for (int k = 0; k < n; k++) {                           /* dgedi: inverse(U) ... */
-    E(k, k) = 1.0 / E(k, k);
-    const PetscScalar t0 = -E(k, k);
-    for (int i = 0; i < k; i++) E(i, k) *= t0;
-    for (int j = k + 1; j < n; j++) {
-      const PetscScalar t = E(k, j);
-      E(k, j) = 0.0;
-      for (int i = 0; i <= k; i++) E(i, j) += t * E(i, k);
-    }
-  }
-  for (int k = n - 2; k >= 0; k--) {                      /* ... times inverse(L), interchanges undone */
-    for (int i = k + 1; i < n; i++) { work[i] = E(i, k); E(i, k) = 0.0; }
-    for (int j = k + 1; j < n; j++) { const PetscScalar t = work[j]; for (int i = 0; i < n; i++) E(i, k) += t * E(i, j); }
-    const int l = ipvt[k];
-    if (l != k) for (int i = 0; i < n; i++) { const PetscScalar t = E(i, k); E(i, k) = E(i, l); E(i, l) = t; }
-  }
-#undef E
-  return 0;
-}
 
 static PetscErrorCode PCSetUp_PBJacobi_HIP(PC pc) {
   PetscErrorCode ierr;
@@ -70,7 +31,7 @@ static PetscErrorCode PCSetUp_PBJacobi_HIP(PC pc) {
     while (k < bi[i + 1] && bj[k] != i) k++;
     if (k == bi[i + 1]) { HipFree(idiag); SETERRQ(HipObjComm(pc), PETSC_ERR_ARG_WRONGSTATE, "Matrix is missing diagonal block %d", i); }
     memcpy(idiag + (size_t)i * bs2, ba + (size_t)k * bs2, sizeof(PetscScalar) * (size_t)bs2);
-    const int z = block_inverse((int)bs, idiag + (size_t)i * bs2);
+    const int z = mi355x_block_inverse((int)bs, idiag + (size_t)i * bs2);
     if (z) { HipFree(idiag); SETERRQ(HipObjComm(pc), 71 /* PETSC_ERR_MAT_LU_ZRPVT */, "Zero pivot, row %d", i * bs + z - 1); }
   }
   ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
