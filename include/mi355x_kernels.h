@@ -229,6 +229,19 @@ int mi355x_vec_tfqmr_qt(mi355x_handle_t h, size_t n, double a, const double *u, 
 int mi355x_vec_tfqmr_resid(mi355x_handle_t h, size_t n, double a, const double *auq, const double *rp, double *r, double *out);
 int mi355x_vec_tfqmr_update(mi355x_handle_t h, size_t n, int nhalves, double cf0, double eta0, double cf1, double eta1, int tail, double b,
                             double *d, double *x, double *u, double *q, const double *r, double *p);
+/* The two sweeps of an iteration of KSPSolve_BiCG (src/ksp/ksp/impls/bicg/bicg.c), every output with the bits of the separate calls.
+ *   _dirs    first: pr = zr, pl = zl (VecCopy x2); else pr = zr + b pr, pl = zl + b pl (VecAYPX x2 with its special cases).  Nothing is
+ *            reduced.  No two of the four may be the same array (hipErrorInvalidValue, nothing written).
+ *   _update  x += a pr ; rr -= a zr ; rl -= a zl (VecAXPY x3; a == 0: nothing moved).  pcmode 1: zr = rr .* d, zl = rl .* d (PCJACOBI both
+ *            ways); pcmode 2: zr = rr, zl = rl (PCNONE); pcmode 0: zr and zl are only read.  out[0] = sum zr*rl (VecDot(Zr, Rl)), out[1] =
+ *            sum zr*zr (which == 0) or sum rr*rr (which == 1), the sum VecNorm takes the root of, over the updated vectors in the
+ *            fixed-tree order of mi355x_vec_dot / _norm; pcmode 0: out = { 0, sum rr*rr }.  out: device memory or the handle's pinned
+ *            scratch.  hipErrorInvalidValue and nothing written for a NULL operand, d given without pcmode 1 or missing with it, pcmode
+ *            or which out of range, or a written vector that is another operand. */
+int mi355x_vec_bicg_dirs(mi355x_handle_t h, size_t n, int first, double b, const double *zr, const double *zl, double *pr, double *pl);
+int mi355x_vec_bicg_update(mi355x_handle_t h, size_t n, double a, int pcmode, int which, const double *pr, const double *d, double *x,
+                           double *rr, double *rl, double *zr, double *zl, double *out);
+
 /* VecMDot_Seq         src/vec/vec/impls/seq/dvec2.c:146     out[j] = sum_i x_i y_j,i , j<nv ; x read once per 16 y's */
 int mi355x_vec_mdot(mi355x_handle_t h, size_t n, int nv, const double *x, const double *const *y, double *out);
 /* KSPGMRESCycle fusions (gmres.c:118-209, borthog2.c:60-66): x += sum_j sign*coef_dev[j]*y_j in VecMAXPY_Seq's grouping with
@@ -437,6 +450,28 @@ int mi355x_ilu0_lower_level(mi355x_handle_t h, int nrows, const int *rows, const
                             const double *ba, const double *b, double *x);
 int mi355x_ilu0_upper_level(mi355x_handle_t h, int nrows, const int *rows, const int *bj, const double *ba,
                             const int *bdiag, double *x);
+
+/* ---- transposed triangular solves of the same factors (csrc/trisolve_transpose.hip) ----
+ * MatSolveTranspose_SeqAIJ  src/mat/impls/aij/seq/aijfact.c with the natural ordering: the forward solve with U^T (scaled by the inverted
+ * diagonal), then the backward solve with L^T (unit diagonal).  The device runs the GATHER form over the transposed triangles, stored as
+ * two CSR triangles whose rows are in the order the reference's scatter loop reaches an entry: U^T's row c lists the rows i < c of U that
+ * hold column c ASCENDING, L^T's row c the rows i > c of L DESCENDING.  One launch per dependency level, `rows` the level's rows (device
+ * array), one lane per row, the row walked in storage order, every product rounded before its subtraction: x carries the loop's bits.
+ *   _first_level   x[c] = (b[c] - ta[q] x[tj[q]] - ...) * dinv[c] over q = ti[c] .. ti[c + 1] - 1.  b may alias x.
+ *   _second_level  x[c] =  x[c] - sa[q] x[sj[q]] - ...            over q = si[c] .. si[c + 1] - 1, in place.
+ *   nrows <= 0 launches nothing.  No hand-off between workgroups: the kernel boundary between levels is the only synchronisation.
+ *   _build_host    HOST arrays, no device call, one thread: from the factor's bi / bj / bdiag the two patterns (ti, si: n + 1 ints; tj,
+ *             tperm: one int per strict-upper entry, bdiag[0] + 1 - bi[n] - n of them; sj, sperm: bi[n] ints), tperm / sperm the position in
+ *             ba of every value (the inverted diagonal of row c is ba[bdiag[c]]; mi355x_pack gathers values through such a list on the
+ *             device), and the dependency level of every row of each triangle: 0 for a row without entries, else one more than the
+ *             deepest row it reads; *nlev_* = levels, every one of them non-empty (0 for n == 0).  hipErrorInvalidValue for a layout
+ *             that is not the one above (a column on the wrong side of the diagonal or outside the matrix, pointers that do not
+ *             increase) or a missing array; nothing is thrown across this interface. */
+int mi355x_ilut_first_level(mi355x_handle_t h, int nrows, const int *rows, const int *ti, const int *tj, const double *ta,
+                            const double *dinv, const double *b, double *x);
+int mi355x_ilut_second_level(mi355x_handle_t h, int nrows, const int *rows, const int *si, const int *sj, const double *sa, double *x);
+int mi355x_ilut_build_host(int n, const int *bi, const int *bj, const int *bdiag, int *ti, int *tj, int *tperm, int *si, int *sj,
+                           int *sperm, int *levT_first, int *nlev_first, int *levT_second, int *nlev_second);
 
 /* ---- ILU(0) numeric factorisation, level by level (csrc/ilu_factor.hip) ------------------------------------------------------
  * MatLUFactorNumeric_SeqAIJ  src/mat/impls/aij/seq/aijfact.c:505-570 with the restarts of MatPivotCheck_nz (matimpl.h:512-528), on

@@ -38,6 +38,7 @@ extern "C" {
 #define KSPRICHARDSONHIPMI355X "richardsonhipmi355x"
 #define KSPPIPECGHIPMI355X  "pipecghipmi355x"          /* KSPPIPECG with the vector work of an iteration in one sweep ("VecPipelinedCGFusedOps_C") */
 #define KSPTFQMRHIPMI355X   "tfqmrhipmi355x"           /* KSPTFQMR with three sweeps per iteration ("VecTfqmrFusedOps_C"); on other vectors the same function runs op by op */
+#define KSPBICGHIPMI355X    "bicghipmi355x"            /* KSPBICG with two sweeps per iteration ("VecBicgFusedOps_C", -ksp_bicg_fused <bool>); on other vectors the same function runs op by op */
 #define KSPCGSHIPMI355X     "cgshipmi355x"             /* KSPCGS on the same three sweeps */
 #define KSPMINRESHIPMI355X  "minreshipmi355x"          /* KSPMINRES with two sweeps per iteration; needs vectors that offer "VecMinresFusedOps_C": PETSC_ERR_SUP at set-up otherwise */
 
@@ -131,6 +132,7 @@ PetscErrorCode PCILUGetLevels_HIPMI355X(PC pc, PetscInt *nlevL, PetscInt *nlevU)
 PetscErrorCode PCILUGetNodeInfo_HIPMI355X(PC pc, PetscInt *nodes, PetscInt *nlevL, PetscInt *nlevU);   /* node-blocked triangular solves (factor of a matrix with inodes): nodes in the plans (0: row-granular), dependency levels over nodes */
 PetscErrorCode PCILUGetSweeps_HIPMI355X(PC pc, PetscInt *k);   /* Jacobi sweeps per triangular solve (-pc_factor_hipmi355x_trisolve sweeps:<k>, an approximate application); 0: exact solves */
 PetscErrorCode PCILUGetFill_HIPMI355X(PC pc, PetscInt *levels, PetscInt *nz_factor, PetscInt *nz_A);   /* ILU(k): levels of fill of the last factorisation (-pc_factor_levels / PCFactorSetLevels), stored entries of the factor and of the operator */
+PetscErrorCode PCILUGetTransposeBuilds_HIPMI355X(PC pc, PetscInt *pattern_builds, PetscInt *value_refreshes);   /* the transposed factor behind MatSolveTranspose / PCApplyTranspose: builds of its pattern side (transposed patterns, levels, index upload), and refills of its values on a pattern that was already there */
 PetscErrorCode PCILUGetNumeric_HIPMI355X(PC pc, PetscInt *on_device, PetscInt *symbolic_builds, PetscInt *numeric_runs);   /* 1: the last numeric factorisation ran on the device (-pc_factor_hipmi355x_numeric device); host symbolic passes and numeric factorisations of this factor so far */
 PetscErrorCode PCILUApplyInPlace_HIPMI355X(PC pc, Vec v);   /* v <- factor applied to v, for a sweeps:<k> factor (PCApply / MatSolve refuse identical vectors, as the reference's do) */
 PetscErrorCode PCFactorDebugSetAborted_HIPMI355X(PC pc);   /* tests: raise the "a dependency wait gave up" flag of this PC's sync-free plans */

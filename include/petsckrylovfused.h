@@ -92,6 +92,20 @@ typedef struct {
                                  PetscBool tail, PetscScalar b, PetscBool *done);
 } VecTfqmrFusedOps;
 typedef const VecTfqmrFusedOps *(*VecTfqmrFusedOpsGetFn)(void);
+/* "VecBicgFusedOps_C" on a Vec returns the two sweeps of an iteration of KSPSolve_BiCG (bicg.c), a fifth table.  *done = PETSC_FALSE and
+ * nothing touched when a sweep refuses its operands: a vector of another type or on another device, unequal local sizes, or a written
+ * vector that is another operand of the call. */
+typedef struct {
+  /* first: pr = zr ; pl = zl (VecCopy x2).  Else pr = zr + b pr ; pl = zl + b pl (VecAYPX x2).  Nothing is reduced, no host wait. */
+  PetscErrorCode (*bicg_dirs)(Vec pr, Vec pl, Vec zr, Vec zl, PetscScalar b, PetscBool first, PetscBool *done);
+  /* x += a pr ; rr -= a zr ; rl -= a zl (VecAXPY x3 in this order).  d != NULL (PCJACOBI: PCApply and PCApplyTranspose alike) or identity
+   * (PCNONE): zr = d .* rr and zl = d .* rl (or the copies) in the same pass, with *beta = zr'rl (VecDot(Zr, Rl)) and *nrm2 = zr'zr
+   * (which == 0) or rr'rr (which == 1), the sum VecNorm(.., NORM_2) takes the root of.  Otherwise zr and zl are only read, *beta is not
+   * set and *nrm2 = rr'rr.  The sums are over the updated vectors, all-reduced, and arrive in one wait. */
+  PetscErrorCode (*bicg_update)(Vec x, Vec rr, Vec rl, Vec pr, Vec zr, Vec zl, Vec d, PetscBool identity, PetscScalar a, PetscInt which,
+                                PetscScalar *beta, PetscScalar *nrm2, PetscBool *done);
+} VecBicgFusedOps;
+typedef const VecBicgFusedOps *(*VecBicgFusedOpsGetFn)(void);
 typedef PetscErrorCode (*MatMultTDotBeginFn)(Mat A, Vec x, Vec y, PetscBool *ok);
 typedef PetscErrorCode (*MatMultDiagonalScaleFn)(Mat A, Vec d, Vec x, Vec y, PetscBool *ok);
 

@@ -139,6 +139,7 @@ typedef const char *PCType;
 #define KSPMINRES  "minres"    /* minimum residual method for symmetric indefinite operators (src/ksp/ksp/impls/minres/minres.c) */
 #define KSPTFQMR   "tfqmr"     /* transpose-free QMR for nonsymmetric operators (src/ksp/ksp/impls/tfqmr/tfqmr.c) */
 #define KSPCGS     "cgs"       /* conjugate gradient squared (src/ksp/ksp/impls/cgs/cgs.c) */
+#define KSPBICG    "bicg"      /* biconjugate gradients: A^T p and B^T r per iteration (src/ksp/ksp/impls/bicg/bicg.c) */
 #define PCNONE     "none"
 #define PCJACOBI   "jacobi"
 #define PCBJACOBI  "bjacobi"
@@ -317,6 +318,7 @@ PetscErrorCode MatLUFactorNumeric(Mat fact, Mat mat, const MatFactorInfo *info);
 PetscErrorCode MatICCFactorSymbolic(Mat fact, Mat mat, IS perm, const MatFactorInfo *info);
 PetscErrorCode MatCholeskyFactorNumeric(Mat fact, Mat mat, const MatFactorInfo *info);
 PetscErrorCode MatSolve(Mat mat, Vec b, Vec x);
+PetscErrorCode MatSolveTranspose(Mat mat, Vec b, Vec x);   /* matrix.c MatSolveTranspose: x = (factor)^-T b; PETSC_ERR_SUP without ops->solvetranspose */
 PetscErrorCode MatDiagonalScale(Mat A, Vec l, Vec r);   /* A <- diag(l) A diag(r); l or r may be NULL (aij.c:2055, mpiaij.c:2183) */
 /* null spaces of singular operators (src/mat/interface/matnull.c): the constant vector (has_cnst) and / or n orthonormal vectors, which
  * the null space keeps references to.  MatNullSpaceRemove: the constant first (VecSum, sum / (-N), VecShift), then the vectors (VecMDot,
@@ -347,6 +349,8 @@ PetscErrorCode PCGetOperators(PC pc, Mat *Amat, Mat *Pmat, MatStructure *flag);
 PetscErrorCode PCSetUp(PC pc);
 PetscErrorCode PCSetUpOnBlocks(PC pc);
 PetscErrorCode PCApply(PC pc, Vec x, Vec y);
+PetscErrorCode PCApplyTranspose(PC pc, Vec x, Vec y);           /* precon.c PCApplyTranspose: y = B^T x; PETSC_ERR_SUP for a type without ops->applytranspose */
+PetscErrorCode PCApplyTransposeExists(PC pc, PetscBool *flg);
 /* precon.c PCApplyRichardson: `its` steps of Richardson's iteration with this preconditioner on A y = b done by the PC itself (PCSOR:
  * ONE MatSOR call of its sweeps); w: a work vector; PETSC_ERR_SUP when the PC has no such method (KSPRICHARDSON asks first) */
 PetscErrorCode PCApplyRichardson(PC pc, Vec b, Vec y, Vec w, PetscReal rtol, PetscReal abstol, PetscReal dtol, PetscInt its, PetscBool guesszero, PetscInt *outits, PCRichardsonConvergedReason *reason);

@@ -82,6 +82,8 @@ KERNEL_API = {
     "mi355x_vec_tfqmr_qt": [vp, sz, dbl, vp, vp, vp, vp, vp],
     "mi355x_vec_tfqmr_resid": [vp, sz, dbl, vp, vp, vp, vp],
     "mi355x_vec_tfqmr_update": [vp, sz, i32, dbl, dbl, dbl, dbl, i32, dbl, vp, vp, vp, vp, vp, vp],
+    "mi355x_vec_bicg_dirs": [vp, sz, i32, dbl, vp, vp, vp, vp],
+    "mi355x_vec_bicg_update": [vp, sz, dbl, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "mi355x_handle_publish": [vp, vp, i32],
     "mi355x_handle_publish_at": [vp, vp, i32, i32],
     "mi355x_vec_cg_update_dev": [vp, sz, dbl, vp, dbl, i32, vp, vp, vp, vp, vp, vp, vp, i32],
@@ -158,6 +160,9 @@ KERNEL_API = {
     "mi355x_ilu0_factor_info": [vp, pi32, pi32],
     "mi355x_iluk_symbolic_host": [i32, vp, vp, i32, vp, vp, vp, vp, pi32],
     "mi355x_ilu0_factor_create_fill": [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, C.POINTER(vp)],
+    "mi355x_ilut_first_level": [vp, i32, vp, vp, vp, vp, vp, vp, vp],
+    "mi355x_ilut_second_level": [vp, i32, vp, vp, vp, vp, vp],
+    "mi355x_ilut_build_host": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, pi32, vp, pi32],
     "mi355x_bilu_lower_level": [vp, i32, vp, i32, vp, vp, vp, vp, vp],
     "mi355x_bilu_upper_level": [vp, i32, vp, i32, vp, vp, vp, vp],
     "mi355x_bilu_numeric_host": [i32, i32, vp, vp, vp, vp, vp, vp, vp, pi32],

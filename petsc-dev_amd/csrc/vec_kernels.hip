@@ -1334,6 +1334,94 @@ __global__ __launch_bounds__(MI355X_BLOCK) void tfqmr_update_kernel(TfqmrUpdateF
     [&](size_t k) { f.at1(k); });
 }
 
+// ---- the two sweeps of an iteration of KSPSolve_BiCG (src/ksp/ksp/impls/bicg/bicg.c) around A pr, A^T pl and the preconditioner, over
+// the shared steps above (aypx_elem, OpAxpy, the tile loads and stores); every output carries the bits of the separate launches.
+// BicgDirsF, a pure map (nothing reduced, no host wait):
+//   first:  pr = zr ; pl = zl                              (VecCopy x2)
+//   else:   pr = zr + b pr ; pl = zl + b pl                (VecAYPX(Pr, b, Zr), VecAYPX(Pl, b, Zl); b == 0: copies, pr / pl not loaded; 1; -1)
+// zr and zl have their last readers here (the two products that follow overwrite them): non-temporal at every size; the new pr and pl
+// are gathered by those products and stay cacheable below 256 MiB.
+struct BicgDirsF {
+  double b;
+  const double *zr, *zl;
+  double *pr, *pl;
+  int first, big;
+  __device__ __forceinline__ bool copies() const { return first || b == 0.0; }
+  template <int U>
+  __device__ __forceinline__ void tile(size_t i) const {
+    double2 zrv[U], zlv[U], prv[U] = {}, plv[U] = {};
+    ldq_tile(zr, i, 1, zrv); ldq_tile(zl, i, 1, zlv);
+    if (!copies()) { ldq_tile(pr, i, big, prv); ldq_tile(pl, i, big, plv); }
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      prv[j].x = aypx_elem(copies(), b, zrv[j].x, prv[j].x); prv[j].y = aypx_elem(copies(), b, zrv[j].y, prv[j].y);
+      plv[j].x = aypx_elem(copies(), b, zlv[j].x, plv[j].x); plv[j].y = aypx_elem(copies(), b, zlv[j].y, plv[j].y);
+    }
+    stq_tile(pr, i, big, prv); stq_tile(pl, i, big, plv);
+  }
+  __device__ __forceinline__ void at1(size_t k) const {
+    pr[k] = aypx_elem(copies(), b, zr[k], copies() ? 0.0 : pr[k]);
+    pl[k] = aypx_elem(copies(), b, zl[k], copies() ? 0.0 : pl[k]);
+  }
+};
+__global__ __launch_bounds__(MI355X_BLOCK) void bicg_dirs_kernel(BicgDirsF f, size_t n, int vec_ok) {
+  tile_walk<2>(n, vec_ok,
+    [&](size_t i, auto u) { f.template tile<decltype(u)::value>(i); },
+    [&](size_t k) { f.at1(k); });
+}
+
+// BicgUpdateF, under launch_reduce:
+//   x = x + a pr ; rr = rr + (-a) zr ; rl = rl + (-a) zl   (VecAXPY x3; a == 0: nothing moved, pr / zr / zl not loaded as inputs)
+//   pcmode 1 (PCJACOBI): zr = rr * d ; zl = rl * d         (VecPointwiseMult(Zr, Rr, diag), (Zl, Rl, diag): a diagonal is its own transpose)
+//   pcmode 2 (PCNONE):   zr = rr ; zl = rl                 (VecCopy x2)
+//   pcmode 0:            zr and zl are left to the caller's PCApply / PCApplyTranspose
+//   out = { sum zr*rl , sum zr*zr or sum rr*rr }           (VecDot(Zr, Rl) = the next beta; VecNorm(Zr or Rr, NORM_2)'s sum, by `which`);
+//                                                          pcmode 0: { 0 , sum rr*rr }
+// over the updated vectors, a lane meeting its elements in DotF's / SumSqF's order.  x is touched here only and the old zr / zl are read
+// for the last time: non-temporal at every size; rr, rl and the new zr, zl stay cacheable below 256 MiB.
+struct BicgUpdateF {
+  double a;
+  const double *pr, *d;
+  double *x, *rr, *rl, *zr, *zl;
+  int pcmode, which, big;      // which: 0 the sum of zr*zr, 1 of rr*rr
+  __device__ __forceinline__ bool moves() const { return a != 0.0; }
+  __device__ __forceinline__ void one(double prv, double dv, double &xv, double &rrv, double &rlv, double &zrv, double &zlv, double (&acc)[2]) const {
+    if (moves()) {
+      xv = OpAxpy{a}(prv, xv, 0.0);
+      rrv = OpAxpy{-a}(zrv, rrv, 0.0);
+      rlv = OpAxpy{-a}(zlv, rlv, 0.0);
+    }
+    if (pcmode == 1) { zrv = rrv * dv; zlv = rlv * dv; }
+    else if (pcmode == 2) { zrv = rrv; zlv = rlv; }
+    if (pcmode) acc[0] += zrv * rlv;
+    if (pcmode && !which) acc[1] += zrv * zrv;
+    else acc[1] += rrv * rrv;
+  }
+  template <int NOUT_>
+  __device__ __forceinline__ void sweep(size_t tid, size_t stride, size_t n2, double (&acc)[NOUT_]) const {
+    for (size_t i = tid; i < n2; i += stride) {
+      double2 xv = {}, prv = {}, rrv, rlv, zrv = {}, zlv = {}, dv = {};
+      ldq_tile1(rr, i, big, rrv); ldq_tile1(rl, i, big, rlv);
+      if (moves()) { ldq_tile1(x, i, 1, xv); ldq_tile1(pr, i, 1, prv); ldq_tile1(zr, i, 1, zrv); ldq_tile1(zl, i, 1, zlv); }
+      if (pcmode == 1) ldq_tile1(d, i, big, dv);
+      one(prv.x, dv.x, xv.x, rrv.x, rlv.x, zrv.x, zlv.x, acc);
+      one(prv.y, dv.y, xv.y, rrv.y, rlv.y, zrv.y, zlv.y, acc);
+      if (moves()) {
+        stq(reinterpret_cast<double2 *>(x) + i, xv, 1);
+        stq(reinterpret_cast<double2 *>(rr) + i, rrv, big); stq(reinterpret_cast<double2 *>(rl) + i, rlv, big);
+      }
+      if (pcmode) { stq(reinterpret_cast<double2 *>(zr) + i, zrv, big); stq(reinterpret_cast<double2 *>(zl) + i, zlv, big); }
+    }
+  }
+  __device__ __forceinline__ void accum1(size_t k, double (&acc)[2]) const {
+    double xv = 0.0, prv = 0.0, rrv = rr[k], rlv = rl[k], zrv = 0.0, zlv = 0.0;
+    if (moves()) { xv = x[k]; prv = pr[k]; zrv = zr[k]; zlv = zl[k]; }
+    one(prv, pcmode == 1 ? d[k] : 0.0, xv, rrv, rlv, zrv, zlv, acc);
+    if (moves()) { x[k] = xv; rr[k] = rrv; rl[k] = rlv; }
+    if (pcmode) { zr[k] = zrv; zl[k] = zlv; }
+  }
+};
+
 template <int NV>
 struct MDotF {
   const double *x;
@@ -1678,6 +1766,23 @@ int mi355x_vec_tfqmr_update(mi355x_handle_t h, size_t n, int nhalves, double cf0
   if (!((nhalves >= 1 && eta0 != 0.0) || (nhalves == 2 && eta1 != 0.0))) x = nullptr;       // alignment of what is neither loaded nor stored does not count
   if (tail && b == 0.0 && nhalves < 2) q = nullptr;
   return launch_tiles(h, n, all_aligned16(d, x, u, q, r, p), tfqmr_update_kernel, tfqmr_update_kernel, f);
+}
+
+int mi355x_vec_bicg_dirs(mi355x_handle_t h, size_t n, int first, double b, const double *zr, const double *zl, double *pr, double *pl) {
+  if (!zr || !zl || !pr || !pl || pr == pl || pr == zr || pr == zl || pl == zr || pl == zl) return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  const BicgDirsF f{b, zr, zl, pr, pl, first != 0, vec_streams(n)};
+  return launch_tiles(h, n, all_aligned16(zr, zl, pr, pl), bicg_dirs_kernel, bicg_dirs_kernel, f);
+}
+int mi355x_vec_bicg_update(mi355x_handle_t h, size_t n, double a, int pcmode, int which, const double *pr, const double *d, double *x,
+                           double *rr, double *rl, double *zr, double *zl, double *out) {
+  if (pcmode < 0 || pcmode > 2 || (which != 0 && which != 1) || !pr || !x || !rr || !rl || !zr || !zl || !out) return (int)hipErrorInvalidValue;
+  if ((pcmode == 1) != (d != nullptr)) return (int)hipErrorInvalidValue;
+  const double *const written[] = {x, rr, rl, zr, zl}, *const all[] = {x, rr, rl, zr, zl, pr, d};
+  if (written_is_operand(written, 5, all, 7)) return (int)hipErrorInvalidValue;
+  const BicgUpdateF f{a, pr, d, x, rr, rl, zr, zl, pcmode, which, vec_streams(n)};
+  if (a == 0.0) { x = nullptr; pr = nullptr; if (!pcmode) { zr = nullptr; zl = nullptr; } }   // alignment of what is neither loaded nor stored does not count
+  return launch_reduce<2, RED_SUM>(h, f, n, all_aligned16(pr, d, x, rr, rl, zr, zl), out);   // n == 0: zeros
 }
 
 // borthog2.c:63-64 + the norm of gmres.c:146: x += sum_j sign * coef_dev[j] * y_j, *out = sum x_new^2 (out: device or the

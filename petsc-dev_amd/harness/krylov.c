@@ -16,6 +16,7 @@
  *   MINRES        src/ksp/ksp/impls/minres/minres.c (KSPSolve_MINRES)
  *   TFQMR         src/ksp/ksp/impls/tfqmr/tfqmr.c (KSPSolve_TFQMR)
  *   CGS           src/ksp/ksp/impls/cgs/cgs.c (KSPSolve_CGS)
+ *   BiCG          src/ksp/ksp/impls/bicg/bicg.c (KSPSolve_BiCG)
  * and are written here over a few shared pieces: one checkpoint routine (history, monitor, convergence test), one start-residual
  * routine for the CG family, index-addressed Hessenberg columns for GMRES. */
 #include "petscimpl.h"
@@ -1016,5 +1017,79 @@ PetscErrorCode KSPCreate_CGS(KSP ksp) {   /* cgs.c KSPCreate_CGS */
   ksp->normsupporttable[KSP_NORM_PRECONDITIONED][PC_LEFT] = 2;
   ksp->ops->setup = KSPSetUp_CGS;
   ksp->ops->solve = KSPSolve_CGS;
+  return 0;
+}
+
+/* ================================================================== BiCG (bicg.c KSPSolve_BiCG)
+ * The biconjugate-gradient method: the residual Rr with its directions Pr runs under A and B, the shadow residual Rl with Pl under A^T
+ * and B^T (KSP_MatMultTranspose, KSP_PCApplyTranspose).  Work vectors Rr, Rl, Zr, Zl, Pr, Pl; Zr / Zl hold B Rr / B^T Rl between the
+ * iterations and A Pr / A^T Pl inside one.  Real scalars: the reference's conjugations are no-ops and are not restated.  Left
+ * preconditioning; the preconditioned norm ||B r|| by default, the unpreconditioned one on request -- then the two preconditioner
+ * applications follow the checkpoint instead of preceding it.  There is no transposed null-space removal in the reference, so a
+ * null space is refused at set-up.  beta == 0 in the first iteration is the reference's breakdown exit; dpi = Zr'Pl == 0 sets
+ * KSP_DIVERGED_BREAKDOWN where the reference divides by it. */
+enum { BG_RR = 0, BG_RL, BG_ZR, BG_ZL, BG_PR, BG_PL };
+static PetscErrorCode KSPSetUp_BICG(KSP ksp) {
+  if (ksp->pc_side == PC_RIGHT) SETERRQ(ksp->comm, PETSC_ERR_SUP, "no right preconditioning for KSPBiCG");
+  if (ksp->pc_side == PC_SYMMETRIC) SETERRQ(ksp->comm, PETSC_ERR_SUP, "no symmetric preconditioning for KSPBiCG");
+  if (ksp->nullsp) SETERRQ(ksp->comm, PETSC_ERR_SUP, "KSPBiCG with a null space: there is no removal behind the transposed preconditioner application");
+  return KSPDefaultGetWork(ksp, 6);
+}
+static PetscErrorCode bicg_precondition(KSP ksp, Vec Rr, Vec Rl, Vec Zr, Vec Zl) {
+  OK(KSP_PCApply(ksp, Rr, Zr));
+  return KSP_PCApplyTranspose(ksp, Rl, Zl);
+}
+static PetscErrorCode KSPSolve_BICG(KSP ksp) {
+  Vec X = ksp->vec_sol, B = ksp->vec_rhs, *w = ksp->work;
+  Vec Rr = w[BG_RR], Rl = w[BG_RL], Zr = w[BG_ZR], Zl = w[BG_ZL], Pr = w[BG_PR], Pl = w[BG_PL];
+  Mat A = ksp->pc->mat;
+  const PetscBool pnorm = (PetscBool)(ksp->normtype == KSP_NORM_PRECONDITIONED);
+  PetscScalar dpi, a, beta, betaold = 1.0;
+  PetscReal dp;
+  PetscInt i;
+
+  if (ksp->nullsp) SETERRQ(ksp->comm, PETSC_ERR_SUP, "KSPBiCG with a null space: there is no removal behind the transposed preconditioner application");
+  ksp->its = 0;
+  OK(cg_family_start(ksp, A, X, B, Rr));
+  OK(VecCopy(Rr, Rl));
+  OK(bicg_precondition(ksp, Rr, Rl, Zr, Zl));
+  OK(VecNorm(pnorm ? Zr : Rr, NORM_2, &dp));
+  OK(checkpoint(ksp, 0, dp));
+  if (ksp->reason) return 0;
+  for (i = 0; i < ksp->max_it; i++) {
+    OK(VecDot(Zr, Rl, &beta));
+    if (!i) {
+      if (beta == 0.0) { ksp->reason = KSP_DIVERGED_BREAKDOWN; return 0; }
+      OK(VecCopy(Zr, Pr));
+      OK(VecCopy(Zl, Pl));
+    } else {
+      const PetscScalar b = beta / betaold;
+      OK(VecAYPX(Pr, b, Zr));
+      OK(VecAYPX(Pl, b, Zl));
+    }
+    betaold = beta;
+    OK(KSP_MatMult(ksp, A, Pr, Zr));
+    OK(KSP_MatMultTranspose(ksp, A, Pl, Zl));
+    OK(VecDot(Zr, Pl, &dpi));
+    if (dpi == 0.0) { ksp->reason = KSP_DIVERGED_BREAKDOWN; break; }
+    a = beta / dpi;
+    OK(VecAXPY(X, a, Pr));
+    OK(VecAXPY(Rr, -a, Zr));
+    OK(VecAXPY(Rl, -a, Zl));
+    if (pnorm) OK(bicg_precondition(ksp, Rr, Rl, Zr, Zl));
+    OK(VecNorm(pnorm ? Zr : Rr, NORM_2, &dp));
+    ksp->its = i + 1;
+    OK(checkpoint(ksp, i + 1, dp));
+    if (ksp->reason) break;
+    if (!pnorm) OK(bicg_precondition(ksp, Rr, Rl, Zr, Zl));
+  }
+  if (i >= ksp->max_it) ksp->reason = KSP_DIVERGED_ITS;
+  return 0;
+}
+PetscErrorCode KSPCreate_BICG(KSP ksp) {   /* bicg.c KSPCreate_BiCG */
+  ksp->normsupporttable[KSP_NORM_PRECONDITIONED][PC_LEFT] = 2;
+  ksp->normsupporttable[KSP_NORM_UNPRECONDITIONED][PC_LEFT] = 1;
+  ksp->ops->setup = KSPSetUp_BICG;
+  ksp->ops->solve = KSPSolve_BICG;
   return 0;
 }

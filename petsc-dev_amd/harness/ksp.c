@@ -347,6 +347,9 @@ PetscErrorCode KSP_PCApply(KSP ksp, Vec x, Vec y) {
   KSP_RemoveNullSpace(ksp, y);
   return 0;
 }
+/* the transposed pair KSPBICG asks for.  No null-space removal behind the transposed application: KSPBICG refuses a null space at set-up */
+PetscErrorCode KSP_MatMultTranspose(KSP ksp, Mat A, Vec x, Vec y) { (void)ksp; return MatMultTranspose(A, x, y); }
+PetscErrorCode KSP_PCApplyTranspose(KSP ksp, Vec x, Vec y) { return PCApplyTranspose(ksp->pc, x, y); }
 /* PCApplyBAorAB, src/ksp/pc/interface/precon.c:553-640 (no diagonal scaling) */
 PetscErrorCode KSP_PCApplyBAorAB(KSP ksp, Vec x, Vec y, Vec w) {
   PetscErrorCode ierr;

@@ -534,3 +534,16 @@ PetscErrorCode MatSolve(Mat mat, Vec b, Vec x) {   /* matrix.c:3196-3225 */
   PetscObjectStateIncrease(x);
   return 0;
 }
+PetscErrorCode MatSolveTranspose(Mat mat, Vec b, Vec x) {   /* matrix.c MatSolveTranspose: the checks of MatSolve */
+  PetscErrorCode ierr;
+  MatValid(mat, 1);
+  if (x == b) SETERRQ(mat->comm, PETSC_ERR_ARG_IDN, "x and b must be different vectors");
+  if (!mat->factortype) SETERRQ(mat->comm, PETSC_ERR_ARG_WRONGSTATE, "Unfactored matrix");
+  if (!mat->ops->solvetranspose) SETERRQ(mat->comm, PETSC_ERR_SUP, "Matrix type %s: MatSolveTranspose", mat->type_name);
+  if (mat->rmap->N != x->map->N) SETERRQ(mat->comm, PETSC_ERR_ARG_SIZ, "Mat mat,Vec x: global dim %d %d", mat->rmap->N, x->map->N);
+  if (mat->cmap->N != b->map->N) SETERRQ(mat->comm, PETSC_ERR_ARG_SIZ, "Mat mat,Vec b: global dim %d %d", mat->cmap->N, b->map->N);
+  if (!mat->rmap->N && !mat->cmap->N) return 0;
+  ierr = (*mat->ops->solvetranspose)(mat, b, x);CHKERRQ(ierr);
+  PetscObjectStateIncrease(x);
+  return 0;
+}

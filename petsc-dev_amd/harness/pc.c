@@ -52,6 +52,7 @@ PetscErrorCode PetscMiniInitialize(void) {
   ierr = KSPRegister(KSPMINRES, 0, "KSPCreate_MINRES", KSPCreate_MINRES);CHKERRQ(ierr);
   ierr = KSPRegister(KSPTFQMR, 0, "KSPCreate_TFQMR", KSPCreate_TFQMR);CHKERRQ(ierr);
   ierr = KSPRegister(KSPCGS, 0, "KSPCreate_CGS", KSPCreate_CGS);CHKERRQ(ierr);
+  ierr = KSPRegister(KSPBICG, 0, "KSPCreate_BICG", KSPCreate_BICG);CHKERRQ(ierr);
   return 0;
 }
 
@@ -121,6 +122,21 @@ PetscErrorCode PCApply(PC pc, Vec x, Vec y) {   /* precon.c:369-388 */
   ierr = (*pc->ops->apply)(pc, x, y);CHKERRQ(ierr);
   return 0;
 }
+/* precon.c PCApplyTranspose / PCApplyTransposeExists: a type that leaves the slot empty has no transposed application */
+PetscErrorCode PCApplyTranspose(PC pc, Vec x, Vec y) {
+  PetscErrorCode ierr;
+  if (!pc) SETERRQ(0, PETSC_ERR_ARG_NULL, "Null PC");
+  if (x == y) SETERRQ(pc->comm, PETSC_ERR_ARG_IDN, "x and y must be different vectors");
+  if (pc->setupcalled < 2) { ierr = PCSetUp(pc);CHKERRQ(ierr); }
+  if (!pc->ops->applytranspose) SETERRQ(pc->comm, PETSC_ERR_SUP, "PC does not have apply transpose");
+  ierr = (*pc->ops->applytranspose)(pc, x, y);CHKERRQ(ierr);
+  return 0;
+}
+PetscErrorCode PCApplyTransposeExists(PC pc, PetscBool *flg) {
+  if (!pc) SETERRQ(0, PETSC_ERR_ARG_NULL, "Null PC");
+  *flg = (PetscBool)(pc->ops->applytranspose != NULL);
+  return 0;
+}
 /* precon.c PCApplyRichardsonExists / PCApplyRichardson */
 PetscErrorCode PCApplyRichardsonExists(PC pc, PetscBool *exists) {
   if (!pc) SETERRQ(0, PETSC_ERR_ARG_NULL, "Null PC");
@@ -148,7 +164,7 @@ PetscErrorCode PCDestroy(PC *ppc) {
 
 /* ---------------------------------------------------------------- PCNONE (src/ksp/pc/impls/none/none.c) */
 static PetscErrorCode PCApply_None(PC pc, Vec x, Vec y) { (void)pc; return VecCopy(x, y); }
-PetscErrorCode PCCreate_None(PC pc) { pc->ops->apply = PCApply_None; return 0; }
+PetscErrorCode PCCreate_None(PC pc) { pc->ops->apply = PCApply_None; pc->ops->applytranspose = PCApply_None; return 0; }   /* none.c: the copy both ways */
 
 /* ---------------------------------------------------------------- PCJACOBI */
 typedef struct { Vec diag; } PC_Jacobi;
@@ -189,6 +205,7 @@ PetscErrorCode PCCreate_Jacobi(PC pc) {
   jac->diag = NULL;
   pc->data = jac;
   pc->ops->setup = PCSetUp_Jacobi; pc->ops->apply = PCApply_Jacobi; pc->ops->destroy = PCDestroy_Jacobi;
+  pc->ops->applytranspose = PCApply_Jacobi;   /* jacobi.c:390: a diagonal is its own transpose */
   return 0;
 }
 

@@ -97,6 +97,7 @@ static PetscErrorCode PCSetUp_Factor(PC pc) {
   return 0;
 }
 static PetscErrorCode PCApply_Factor(PC pc, Vec x, Vec y) { return MatSolve(((PC_Factor *)pc->data)->fact, x, y); }   /* PCApply_ILU ilu.c:262, PCApply_ICC icc.c:65 */
+static PetscErrorCode PCApplyTranspose_Factor(PC pc, Vec x, Vec y) { return MatSolveTranspose(((PC_Factor *)pc->data)->fact, x, y); }   /* PCApplyTranspose_ILU ilu.c, _ICC icc.c */
 static PetscErrorCode PCDestroy_Factor(PC pc) {
   PC_Factor *f = (PC_Factor *)pc->data;
   if (f) { PetscErrorCode ierr = MatDestroy(&f->fact);CHKERRQ(ierr); free(f->blk); free(f); pc->data = NULL; }
@@ -116,7 +117,7 @@ static PetscErrorCode create_factor(PC pc, MatFactorType ft, MatFactorShiftType 
   f->info.zeropivot = 100.0 * 2.220446049250313e-16;
   f->info.pivotinblocks = 1.0;
   pc->data = f;
-  pc->ops->setup = PCSetUp_Factor; pc->ops->apply = PCApply_Factor; pc->ops->destroy = PCDestroy_Factor;
+  pc->ops->setup = PCSetUp_Factor; pc->ops->apply = PCApply_Factor; pc->ops->applytranspose = PCApplyTranspose_Factor; pc->ops->destroy = PCDestroy_Factor;
   pc->ops->setfromoptions = PCSetFromOptions_Factor; pc->ops->getfactoredmatrix = PCFactorGetMatrix_Factor;
   ierr = PetscObjectComposeFunction((PetscObject)pc, "PCFactorSetIndependentBlocks_C", "PCFactorSetIndependentBlocks_Factor", (PetscVoidFunction)PCFactorSetIndependentBlocks_Factor);CHKERRQ(ierr);
   return 0;

@@ -163,6 +163,7 @@ struct _MatOps {
   PetscErrorCode (*setvaluesbatch)(Mat, PetscInt, PetscInt, PetscInt[], const PetscScalar[]);
   /* the factorisation slots PCILU / PCICC drive (matimpl.h: solve 8, lufactornumeric 30/..., ilufactorsymbolic, iccfactorsymbolic) */
   PetscErrorCode (*solve)(Mat, Vec, Vec);
+  PetscErrorCode (*solvetranspose)(Mat, Vec, Vec);       /* slot 10 */
   PetscErrorCode (*lufactornumeric)(Mat, Mat, const MatFactorInfo *);
   PetscErrorCode (*choleskyfactornumeric)(Mat, Mat, const MatFactorInfo *);
   PetscErrorCode (*ilufactorsymbolic)(Mat, Mat, IS, IS, const MatFactorInfo *);
@@ -185,6 +186,7 @@ struct _p_Mat {
 struct _PCOps {
   PetscErrorCode (*setup)(PC);
   PetscErrorCode (*apply)(PC, Vec, Vec);
+  PetscErrorCode (*applytranspose)(PC, Vec, Vec);   /* PCApplyTranspose: KSPBICG's B^T r; NULL: the type has none */
   PetscErrorCode (*setfromoptions)(PC);
   PetscErrorCode (*destroy)(PC);
   PetscErrorCode (*getfactoredmatrix)(PC, Mat *);
@@ -236,8 +238,10 @@ PetscErrorCode KSPDefaultGetWork(KSP ksp, PetscInt nw);
 PetscErrorCode KSPInitialResidual(KSP ksp, Vec vsoln, Vec vt1, Vec vt2, Vec vres, Vec vb);
 PetscErrorCode KSP_MatMult(KSP ksp, Mat A, Vec x, Vec y);
 PetscErrorCode KSP_PCApply(KSP ksp, Vec x, Vec y);
+PetscErrorCode KSP_MatMultTranspose(KSP ksp, Mat A, Vec x, Vec y);
+PetscErrorCode KSP_PCApplyTranspose(KSP ksp, Vec x, Vec y);
 PetscErrorCode KSP_PCApplyBAorAB(KSP ksp, Vec x, Vec y, Vec w);
-PetscErrorCode KSPCreate_CG(KSP), KSPCreate_GROPPCG(KSP), KSPCreate_PIPECG(KSP), KSPCreate_GMRES(KSP), KSPCreate_BCGS(KSP), KSPCreate_PREONLY(KSP), KSPCreate_Chebychev(KSP), KSPCreate_Richardson(KSP), KSPCreate_MINRES(KSP), KSPCreate_TFQMR(KSP), KSPCreate_CGS(KSP);
+PetscErrorCode KSPCreate_CG(KSP), KSPCreate_GROPPCG(KSP), KSPCreate_PIPECG(KSP), KSPCreate_GMRES(KSP), KSPCreate_BCGS(KSP), KSPCreate_PREONLY(KSP), KSPCreate_Chebychev(KSP), KSPCreate_Richardson(KSP), KSPCreate_MINRES(KSP), KSPCreate_TFQMR(KSP), KSPCreate_CGS(KSP), KSPCreate_BICG(KSP);
 PetscErrorCode PCCreate_None(PC), PCCreate_Jacobi(PC), PCCreate_BJacobi(PC), PCCreate_ILU(PC), PCCreate_ICC(PC), PCCreate_SOR(PC);
 
 #include "petsckrylovfused.h"   /* the optional fused-kernel tables a Vec / Mat type may compose */

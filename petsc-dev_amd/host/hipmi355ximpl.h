@@ -180,6 +180,19 @@ typedef struct {
    * operator's pattern upload (Mat_SeqAIJHIP.pattern_gen) and its sizes at the time, levels: the levels of fill the factor's pattern was built
    * with -- what "the pattern of the last factorisation" is told by */
   struct { mi355x_ilu0_factor_t dfac; int stale; unsigned long long gen; PetscInt n, nz, levels, nblk, *blk; } dev;
+  /* MatSolveTranspose (host/ilu.c, "the transposed factor"): U^T and L^T as two CSR triangles on the device, rows in the order the
+   * reference's scatter loop reaches an entry (csrc/trisolve_transpose.hip), built at the first transposed solve after a factorisation.
+   * Pattern side, once per pattern: the index arrays, perm (position in ba of every value: U^T's, L^T's, then the n inverted diagonals),
+   * the level lists, the captured graph of the nlev1 + nlev2 launches, and the host pattern they were built for (bi / bj / bdiag: a
+   * factorisation that leaves the same one refills val only).  fresh: val holds the current factor's values */
+  struct {
+    PetscInt n, nz, levels, nzU, nzL, *bi, *bj, *bdiag, *perm;   /* (perm: host copy, for a factor whose values are on the host only) */
+    PetscInt *d_ti, *d_tj, *d_si, *d_sj, *d_perm; PetscScalar *d_val;
+    PetscInt nlev1, nlev2, *levptr1, *levptr2, *d_rows1, *d_rows2;
+    PetscScalar *d_work; void *graph; int graph_tried;
+    int built, fresh;
+    PetscInt pattern_builds, value_refreshes;              /* (the counts outlive the form) */
+  } tr;
   PetscInt symbolic_builds, numeric_runs;                  /* host symbolic passes / numeric factorisations so far (both routes) */
   int aborted;                                             /* a sync-free application of this factor gave up at some time (kept over re-factorisations) */
   PetscInt nshift;                                         /* restarts / shifts the factorisation took (largest count over the blocks) */
@@ -386,5 +399,6 @@ PetscErrorCode KSPCreate_PIPECGHIPMI355X(KSP);
 PetscErrorCode KSPCreate_MINRESHIPMI355X(KSP);
 PetscErrorCode KSPCreate_TFQMRHIPMI355X(KSP);
 PetscErrorCode KSPCreate_CGSHIPMI355X(KSP);
+PetscErrorCode KSPCreate_BICGHIPMI355X(KSP);
 
 #endif

@@ -260,6 +260,7 @@ static PetscErrorCode MatCholeskyFactorNumeric_SeqAIJHIP(Mat F, Mat A, const Mat
 #endif
   if (f->syncfree.tri_lo) HipTriWatchAdd(f);
   F->ops->solve = MatSolve_SeqAIJHIP_ICC;
+  F->ops->solvetranspose = MatSolve_SeqAIJHIP_ICC;                       /* the factor is symmetric: the reference's assignment for SBAIJ factors (sbaijfact.c) */
   f->factored_state = HipObjState(A); f->factored_of = (void *)A;
   return 0;
 }

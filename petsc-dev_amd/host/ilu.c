@@ -105,11 +105,25 @@ static void tri_free_dev(HipTriFactors *f) {
   HipFree(f->dev.blk);
   memset(&f->dev, 0, sizeof(f->dev));
 }
+/* the transposed factor (MatSolveTranspose).  whole == 0: its values are those of a factorisation that is being forgotten -- the
+ * value array itself stays, the captured graph names it and the next build refills it in place when the pattern is the same */
+static void tri_free_transpose(HipTriFactors *f, int whole) {
+  const PetscInt pb = f->tr.pattern_builds, vr = f->tr.value_refreshes;
+  f->tr.fresh = 0;
+  if (!whole) return;
+  if (f->tr.graph) mi355x_graph_destroy(f->tr.graph);
+  void *dev[] = {f->tr.d_ti, f->tr.d_tj, f->tr.d_si, f->tr.d_sj, f->tr.d_perm, f->tr.d_val, f->tr.d_rows1, f->tr.d_rows2, f->tr.d_work};
+  for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); i++) if (dev[i]) mi355x_free(dev[i]);
+  HipFree(f->tr.bi); HipFree(f->tr.bj); HipFree(f->tr.bdiag); HipFree(f->tr.perm); HipFree(f->tr.levptr1); HipFree(f->tr.levptr2);
+  memset(&f->tr, 0, sizeof(f->tr));
+  f->tr.pattern_builds = pb; f->tr.value_refreshes = vr;
+}
 /* forget one numeric factorisation (ILU(0) and ICC(0) alike); the symbolic choices, the block list and the watch slot stay, and so
  * do the sweep form's device arrays: the next factorisation may only have new values.  The one order that matters: the level-launch
  * form goes BEFORE the device route's context -- its captured graph names the context's arrays, and the pointers it borrowed from the
  * context are forgotten (tri_free_launch) while the context still owns them, never freed twice. */
 void HipTriFactorsResetNumeric(HipTriFactors *f) {
+  tri_free_transpose(f, 0);
   tri_free_launch(f); tri_free_dev(f);
   tri_free_host(f); tri_free_lev(f); tri_free_syncfree(f);
   f->sw.sweeps = 0; f->nshift = 0;
@@ -121,6 +135,7 @@ PetscErrorCode HipTriFactorsDestroy(HipTriFactors **pf) {
   tri_watch_remove(f);
   HipTriFactorsResetNumeric(f);
   tri_free_sweeps(f);
+  tri_free_transpose(f, 1);
   HipFree(f->blk);
   HipFree(f);
   *pf = NULL;
@@ -904,6 +919,7 @@ static PetscErrorCode ilu0_factor_device(Mat F, Mat A, const MatFactorInfo *info
   f->factored_state = -1;
   if (same) {   /* values only: the plans that carry values go, everything built from the pattern stays */
     tri_free_syncfree(f);
+    tri_free_transpose(f, 0);
     f->nshift = 0; f->sw.sweeps = 0;
   } else { ierr = ilu0_device_symbolic(F, A, dc, (PetscInt)info->levels, nblk, blk, &tick0);CHKERRQ(ierr); }
   ierr = ilu0_device_numeric(A, f, dc, nblk, info, &tick0);CHKERRQ(ierr);
@@ -916,6 +932,7 @@ static PetscErrorCode ilu0_factor_device(Mat F, Mat A, const MatFactorInfo *info
 }
 
 static PetscErrorCode MatSolve_SeqAIJHIP_ILU(Mat F, Vec b, Vec x);
+static PetscErrorCode MatSolveTranspose_SeqAIJHIP_ILU(Mat F, Vec b, Vec x);
 static PetscErrorCode MatLUFactorNumeric_SeqAIJHIP(Mat F, Mat A, const MatFactorInfo *info) {   /* MatLUFactorNumeric_SeqAIJCUSPARSE, aijcusparse.cu:358-376 */
   PetscErrorCode ierr;
   HipTriFactors *f = HipTriGet(F);
@@ -944,6 +961,7 @@ static PetscErrorCode MatLUFactorNumeric_SeqAIJHIP(Mat F, Mat A, const MatFactor
   ierr = ilu0_analyse_and_upload(F, A);CHKERRQ(ierr);
   HipSetupNote("ILU(0) n=%d: %s factorisation %.3f s, level analysis + plans + upload %.3f s\n", (int)f->n, on_device ? "device" : "host", t1 - t0, HipWallSeconds() - t1);
   F->ops->solve = MatSolve_SeqAIJHIP_ILU;                                 /* aijcusparse.cu:372-373 */
+  F->ops->solvetranspose = MatSolveTranspose_SeqAIJHIP_ILU;
   f->factored_state = HipObjState(A); f->factored_of = (void *)A;
   return 0;
 }
@@ -1026,6 +1044,137 @@ static PetscErrorCode MatSolve_SeqAIJHIP_ILU(Mat F, Vec b, Vec x) {   /* MatSolv
     if (!rc) rc = mi355x_graph_launch(dc->h, f->launch.graph);
     if (!rc) rc = mi355x_vec_copy(dc->h, (size_t)f->n, f->launch.d_work, dx);
   } else rc = ilu0_launch_levels(dc, f, db, dx);
+  ierr = VecHIPRestoreWrite(x);CHKERRQ(ierr);
+  HipStateIncrease(x);
+  CHKHIP(rc);
+  ierr = PetscLogFlops(2.0 * f->nz - f->n);CHKERRQ(ierr);
+  return 0;
+}
+
+/* ---------------------------------------------------------------- the transposed factor: MatSolveTranspose
+ * MatSolveTranspose_SeqAIJ (aijfact.c) with the natural ordering -- t = b; forward with U^T: s = t[i] * inverted diagonal, t[j] -= s u(i,j)
+ * over U's strict row i, t[i] = s; backward with L^T: t[j] -= t[i] l(i,j) over L's row i -- run as a gather over the two transposed
+ * triangles (csrc/trisolve_transpose.hip: the same bits, no atomics), one launch per dependency level, replayed from a hipGraph when
+ * there are more than a handful.  It serves ILU(0) and ILU(k) whatever -pc_factor_hipmi355x_trisolve chose for the forward application,
+ * except sweeps:<k>: that application is approximate and has no transposed counterpart.  Row-granular also for the factor of a matrix
+ * with inodes.  The form is built at the first transposed solve after a factorisation: pattern work (transposed patterns, levels, row
+ * lists, index upload) once per pattern of the FACTOR, told by comparing the host pattern (bi / bj / bdiag are on the host on every
+ * route today -- the symbolic phase runs there also under -pc_factor_hipmi355x_numeric device, which has no host VALUES only; a route
+ * without a host pattern would have to key this form like f->dev, by pattern_gen, n, nz and the levels of fill; the comparison costs one
+ * pass over nz ints per factorisation and does not depend on the operator having been uploaded); the values by one gather from the factor's
+ * device values (launch.d_ba) when they are there, else gathered on the host and uploaded. */
+static PetscErrorCode ilut_pattern(HipTriFactors *f, PetscDeviceCtx *dc) {
+  PetscErrorCode ierr;
+  const PetscInt n = f->n, nz = f->nz, *bi = f->host.bi, *bj = f->host.bj, *bdiag = f->host.bdiag;
+  const PetscInt nzL = bi[n], nzU = nz - nzL - n;
+  const size_t ni = sizeof(PetscInt) * (size_t)(n + 1), nj = sizeof(PetscInt) * (size_t)PetscMax(nz, 1);
+  PetscInt *hw, *rows1 = NULL, *rows2 = NULL; int rc;
+  tri_free_transpose(f, 1);
+  /* one host work array: ti, si (n + 1 each), tj, sj, then perm = tperm | sperm | bdiag[0 .. n), then the two level arrays */
+  ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(2 * (n + 1) + 2 * (nzU + nzL) + 3 * n + 1), &hw);CHKERRQ(ierr);
+  PetscInt *ti = hw, *si = ti + n + 1, *tj = si + n + 1, *sj = tj + nzU, *perm = sj + nzL, *lev1 = perm + nzU + nzL + n, *lev2 = lev1 + n;
+  int nlev1 = 0, nlev2 = 0;
+  rc = mi355x_ilut_build_host(n, bi, bj, bdiag, ti, tj, perm, si, sj, perm + nzU, lev1, &nlev1, lev2, &nlev2);
+  if (rc) { HipFree(hw); CHKHIP(rc); }
+  memcpy(perm + nzU + nzL, bdiag, sizeof(PetscInt) * (size_t)n);
+  f->tr.nlev1 = nlev1; f->tr.nlev2 = nlev2;
+  ierr = level_order(n, lev1, nlev1, &f->tr.levptr1, &rows1);
+  if (!ierr) ierr = level_order(n, lev2, nlev2, &f->tr.levptr2, &rows2);
+  if (!ierr) {
+    struct { void *p; const void *from; size_t bytes; } up[] = {{&f->tr.d_ti, ti, ni}, {&f->tr.d_si, si, ni}, {&f->tr.d_tj, tj, sizeof(PetscInt) * (size_t)nzU},
+      {&f->tr.d_sj, sj, sizeof(PetscInt) * (size_t)nzL}, {&f->tr.d_perm, perm, sizeof(PetscInt) * (size_t)(nzU + nzL + n)},
+      {&f->tr.d_rows1, rows1, sizeof(PetscInt) * (size_t)n}, {&f->tr.d_rows2, rows2, sizeof(PetscInt) * (size_t)n}};
+    for (size_t i = 0; i < sizeof(up) / sizeof(up[0]) && !rc; i++) {
+      rc = mi355x_malloc((void **)up[i].p, PetscMax(up[i].bytes, sizeof(PetscInt)));
+      if (!rc && up[i].bytes) rc = mi355x_memcpy_h2d(dc->h, *(void **)up[i].p, up[i].from, up[i].bytes);
+    }
+    if (!rc) rc = mi355x_malloc((void **)&f->tr.d_val, sizeof(PetscScalar) * (size_t)PetscMax(nzU + nzL + n, 1));
+    if (!rc) rc = mi355x_handle_synchronize(dc->h);   /* the host arrays go away below */
+  }
+  if (!ierr && !rc) {   /* what the form was built for */
+    ierr = PetscMalloc(ni, &f->tr.bi); if (!ierr) ierr = PetscMalloc(ni, &f->tr.bdiag); if (!ierr) ierr = PetscMalloc(nj, &f->tr.bj);
+    if (!ierr) ierr = PetscMalloc(sizeof(PetscInt) * (size_t)PetscMax(nzU + nzL + n, 1), &f->tr.perm);
+    if (!ierr) { memcpy(f->tr.bi, bi, ni); memcpy(f->tr.bdiag, bdiag, ni); memcpy(f->tr.bj, bj, sizeof(PetscInt) * (size_t)nz); memcpy(f->tr.perm, perm, sizeof(PetscInt) * (size_t)(nzU + nzL + n)); }
+  }
+  HipFree(hw); HipFree(rows1); HipFree(rows2);
+  if (ierr || rc) tri_free_transpose(f, 1);
+  CHKERRQ(ierr);
+  CHKHIP(rc);
+  f->tr.n = n; f->tr.nz = nz; f->tr.levels = f->levels; f->tr.nzU = nzU; f->tr.nzL = nzL; f->tr.built = 1;
+  f->tr.pattern_builds++;
+  return 0;
+}
+static PetscErrorCode ilut_values(HipTriFactors *f, PetscDeviceCtx *dc) {
+  PetscErrorCode ierr;
+  const PetscInt nv = f->tr.nzU + f->tr.nzL + f->tr.n;
+  int rc = 0;
+  if (f->launch.d_ba) rc = mi355x_pack(dc->h, (size_t)nv, f->tr.d_perm, f->launch.d_ba, f->tr.d_val);
+  else {   /* the factor's values are on the host only (the sync-free plans took them from there) */
+    const PetscScalar *ba = f->host.ba; PetscScalar *val;
+    if (!ba) SETERRQ(PETSC_COMM_SELF, PETSC_ERR_PLIB, "the factor's values are neither on the device nor on the host");
+    ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(nv, 1), &val);CHKERRQ(ierr);
+    for (PetscInt k = 0; k < nv; k++) val[k] = ba[f->tr.perm[k]];
+    if (nv) rc = mi355x_memcpy_h2d(dc->h, f->tr.d_val, val, sizeof(PetscScalar) * (size_t)nv);
+    if (!rc) rc = mi355x_handle_synchronize(dc->h);      /* val goes away below */
+    HipFree(val);
+  }
+  CHKHIP(rc);
+  f->tr.fresh = 1;
+  return 0;
+}
+static PetscErrorCode ilut_form(HipTriFactors *f, PetscDeviceCtx *dc) {
+  PetscErrorCode ierr;
+  const PetscInt n = f->n, nz = f->nz;
+  const size_t ni = sizeof(PetscInt) * (size_t)(n + 1);
+  if (f->tr.built && f->tr.fresh) return 0;
+  if (!f->host.bi || !f->host.bj || !f->host.bdiag) SETERRQ(PETSC_COMM_SELF, PETSC_ERR_ARG_WRONGSTATE, "MatSolveTranspose: the matrix holds no numeric factorisation");
+  const int same = f->tr.built && f->tr.n == n && f->tr.nz == nz && f->tr.levels == f->levels &&
+                   !memcmp(f->tr.bi, f->host.bi, ni) && !memcmp(f->tr.bdiag, f->host.bdiag, ni) && !memcmp(f->tr.bj, f->host.bj, sizeof(PetscInt) * (size_t)nz);
+  if (!same) { ierr = ilut_pattern(f, dc);CHKERRQ(ierr); }
+  ierr = ilut_values(f, dc);CHKERRQ(ierr);
+  if (same) f->tr.value_refreshes++;
+  return 0;
+}
+/* U^T's levels forward from in to out, then L^T's in place on out (in == out: in place throughout) */
+static int ilut_launch_levels(PetscDeviceCtx *dc, const HipTriFactors *f, const PetscScalar *in, PetscScalar *out) {
+  const PetscScalar *ta = f->tr.d_val, *sa = ta + f->tr.nzU, *dinv = sa + f->tr.nzL;
+  int rc = 0;
+  for (PetscInt l = 0; l < f->tr.nlev1 && !rc; l++)
+    rc = mi355x_ilut_first_level(dc->h, f->tr.levptr1[l + 1] - f->tr.levptr1[l], f->tr.d_rows1 + f->tr.levptr1[l], f->tr.d_ti, f->tr.d_tj, ta, dinv, in, out);
+  for (PetscInt l = 0; l < f->tr.nlev2 && !rc; l++)
+    rc = mi355x_ilut_second_level(dc->h, f->tr.levptr2[l + 1] - f->tr.levptr2[l], f->tr.d_rows2 + f->tr.levptr2[l], f->tr.d_si, f->tr.d_sj, sa, out);
+  return rc;
+}
+static PetscErrorCode MatSolveTranspose_SeqAIJHIP_ILU(Mat F, Vec b, Vec x) {
+  PetscErrorCode ierr;
+  HipTriFactors *f = HipTriGet(F);
+  const PetscScalar *db; PetscScalar *dx; PetscDeviceCtx *dc;
+  if (b == x) SETERRQ(HipObjComm(F), PETSC_ERR_ARG_IDN, "x and b must be different vectors");
+  if (f->sw.sweeps) SETERRQ(HipObjComm(F), PETSC_ERR_SUP, "MatSolveTranspose with -pc_factor_hipmi355x_trisolve sweeps:<k>: the sweeps apply the factor approximately and no transposed counterpart is defined");
+  if (!f->n) return 0;
+  ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+  ierr = ilut_form(f, dc);CHKERRQ(ierr);
+  ierr = VecHIPGetRead(b, &db);CHKERRQ(ierr);
+  ierr = VecHIPGetWrite(x, &dx);CHKERRQ(ierr);
+  /* as MatSolve's level launches: a single chain of kernels, captured once per pattern in place on a fixed buffer (the value array it
+   * names is refilled in place by a later factorisation of the same pattern) */
+  if (!f->tr.graph_tried && f->tr.nlev1 + f->tr.nlev2 > 16) {
+    f->tr.graph_tried = 1;
+    if (!mi355x_malloc((void **)&f->tr.d_work, sizeof(PetscScalar) * (size_t)PetscMax(f->n, 1)) && !mi355x_graph_capture_begin(dc->h)) {
+      const int bad = ilut_launch_levels(dc, f, f->tr.d_work, f->tr.d_work);
+      void *g = NULL;
+      if (mi355x_graph_capture_end(dc->h, &g)) g = NULL;
+      else if (bad) { mi355x_graph_destroy(g); g = NULL; }        /* a launch failed inside the capture: the graph is of no use */
+      f->tr.graph = g;
+    }
+    if (!f->tr.graph && f->tr.d_work) { mi355x_free(f->tr.d_work); f->tr.d_work = NULL; }   /* capture failed: plain launches, no buffer kept */
+  }
+  int rc = 0;
+  if (f->tr.graph) {
+    rc = mi355x_vec_copy(dc->h, (size_t)f->n, db, f->tr.d_work);
+    if (!rc) rc = mi355x_graph_launch(dc->h, f->tr.graph);
+    if (!rc) rc = mi355x_vec_copy(dc->h, (size_t)f->n, f->tr.d_work, dx);
+  } else rc = ilut_launch_levels(dc, f, db, dx);
   ierr = VecHIPRestoreWrite(x);CHKERRQ(ierr);
   HipStateIncrease(x);
   CHKHIP(rc);
@@ -1126,6 +1275,14 @@ PetscErrorCode PCILUGetNumeric_HIPMI355X(PC pc, PetscInt *on_device, PetscInt *s
   if (on_device) *on_device = f->dev.dfac ? 1 : 0;
   if (symbolic_builds) *symbolic_builds = f->symbolic_builds;
   if (numeric_runs) *numeric_runs = f->numeric_runs;
+  return 0;
+}
+/* the transposed factor (MatSolveTranspose): builds of its pattern side, and refills of its values on a pattern that was already there */
+PetscErrorCode PCILUGetTransposeBuilds_HIPMI355X(PC pc, PetscInt *pattern_builds, PetscInt *value_refreshes) {
+  HipTriFactors *f;
+  PetscErrorCode ierr = pc_factors(pc, MAT_FACTOR_ILU, &f);CHKERRQ(ierr);
+  if (pattern_builds) *pattern_builds = f->tr.pattern_builds;
+  if (value_refreshes) *value_refreshes = f->tr.value_refreshes;
   return 0;
 }
 /* ILU(k): the levels of fill of the last factorisation (-pc_factor_levels / PCFactorSetLevels), the stored entries of the factor (L, the

@@ -1267,6 +1267,169 @@ static PetscErrorCode tfqmr_create(KSP ksp, PetscBool cgs) {
 PetscErrorCode KSPCreate_TFQMRHIPMI355X(KSP ksp) { return tfqmr_create(ksp, PETSC_FALSE); }
 PetscErrorCode KSPCreate_CGSHIPMI355X(KSP ksp) { return tfqmr_create(ksp, PETSC_TRUE); }
 
+/* ================================================================================================ BiCG
+ * The sequence of KSPSolve_BiCG (src/ksp/ksp/impls/bicg/bicg.c) as the harness's KSPBICG restates it -- same iterates, histories and exits,
+ * bit for bit -- with the vector work of an iteration in the TWO sweeps of "VecBicgFusedOps_C" (include/petsckrylovfused.h) around the
+ * products A pr and A^T pl.  -ksp_bicg_fused <bool> (default true).
+ *   - bicg_dirs:    pr = zr + b pr, pl = zl + b pl (the copies in the first iteration); no host wait;
+ *   - bicg_update:  x += a pr, rr -= a zr, rl -= a zl; with PCJACOBI or PCNONE also zr = B rr, zl = B^T rl, the next beta = zr'rl and the
+ *                   norm's sum in the same pass -- the host waits twice per iteration (dpi = zr'pl, then these sums).  Any other PC: the
+ *                   sweep returns rr'rr, KSP_PCApply / PCApplyTranspose follow, then VecNorm(Zr) (preconditioned norm) and VecDot(Zr, Rl).
+ * With the unpreconditioned norm the reference applies the preconditioner after the checkpoint; the folded form has zr and zl already
+ * (work vectors only: an exit at that checkpoint leaves x and the history as they are).
+ * Without the table, with the option off, or when a sweep answers done = PETSC_FALSE, the same function makes the public calls.
+ * Left preconditioning; a null space is PETSC_ERR_SUP at set-up; beta == 0 in the first iteration and dpi == 0 set KSP_DIVERGED_BREAKDOWN.
+ * KSPHIPMI355XGetFusedStepCounts: (fused sweeps run, iterations in which a step ran through the public calls).  bicg_dirs runs once per
+ * iteration entered, bicg_update once per iteration that gets past dpi: 2 its sweeps, and 2 its + 1 after a breakdown at dpi == 0. */
+typedef struct { PetscBool fused; Vec dinv; PetscInt nsweeps, nopbyop; } KSP_BicgHIP;
+
+static const VecBicgFusedOps *vec_bicg_ops(Vec x) {
+  PetscVoidFunction f = NULL;
+  const VecBicgFusedOps *M;
+  if (PetscObjectQueryFunction((PetscObject)x, "VecBicgFusedOps_C", &f) || !f) return NULL;
+  M = ((VecBicgFusedOpsGetFn)f)();
+  return (M && M->bicg_dirs && M->bicg_update) ? M : NULL;
+}
+/* KSP_MatMultTranspose / KSP_PCApplyTranspose of kspimpl.h.  On the harness the plug-in dispatches through the function tables it can see,
+ * as an implementation does (the library exports the two for the harness's own KSPBICG) */
+static PetscErrorCode bicg_mult_transpose(KSP ksp, Mat A, Vec x, Vec y) {
+#if defined(PETSCHIPMI355X_WITH_PETSC)
+  return KSP_MatMultTranspose(ksp, A, x, y);
+#else
+  PetscErrorCode ierr;
+  if (x == y) SETERRQ(HipObjComm(ksp), PETSC_ERR_ARG_IDN, "x and y must be different vectors");
+  if (!A->ops->multtranspose) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "This matrix type does not have a multiply tranpose defined");
+  ierr = (*A->ops->multtranspose)(A, x, y);CHKERRQ(ierr);
+  HipStateIncrease(y);
+  return 0;
+#endif
+}
+static PetscErrorCode bicg_pc_apply_transpose(KSP ksp, Vec x, Vec y) {
+#if defined(PETSCHIPMI355X_WITH_PETSC)
+  return KSP_PCApplyTranspose(ksp, x, y);
+#else
+  PetscErrorCode ierr;
+  if (x == y) SETERRQ(HipObjComm(ksp), PETSC_ERR_ARG_IDN, "x and y must be different vectors");
+  if (!ksp->pc->ops->applytranspose) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "PC does not have apply transpose");
+  ierr = (*ksp->pc->ops->applytranspose)(ksp->pc, x, y);CHKERRQ(ierr);
+  return 0;
+#endif
+}
+static PetscErrorCode KSPGetFusedStepCounts_BicgHIP(KSP ksp, PetscInt *fused, PetscInt *opbyop) {
+  const KSP_BicgHIP *bd = (const KSP_BicgHIP *)ksp->data;
+  *fused = bd->nsweeps; *opbyop = bd->nopbyop;
+  return 0;
+}
+static PetscErrorCode KSPSetUp_BicgHIP(KSP ksp) {
+  if (ksp->pc_side == PC_RIGHT || ksp->pc_side == PC_SYMMETRIC) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s: left preconditioning only", KSPBICGHIPMI355X);
+  if (has_null_space(ksp)) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s with a null space: there is no removal behind the transposed preconditioner application", KSPBICGHIPMI355X);
+  return KSPDefaultGetWork(ksp, 6);
+}
+static PetscErrorCode KSPSetFromOptions_BicgHIP(KSP ksp) {
+  KSP_BicgHIP *bd = (KSP_BicgHIP *)ksp->data;
+  PetscInt iv = bd->fused;
+  PetscErrorCode ierr = option_level(ksp, "-ksp_bicg_fused", 0, 1, &iv);CHKERRQ(ierr);
+  bd->fused = (PetscBool)iv;
+  return 0;
+}
+static PetscErrorCode KSPDestroy_BicgHIP(KSP ksp) {
+  KSP_BicgHIP *bd = (KSP_BicgHIP *)ksp->data;
+  PetscErrorCode ierr;
+  if (!bd) return 0;
+  ierr = VecDestroy(&bd->dinv);CHKERRQ(ierr);
+  HipFree(bd); ksp->data = NULL;
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
+  return 0;
+}
+static PetscErrorCode bicg_precondition(KSP ksp, Vec Rr, Vec Rl, Vec Zr, Vec Zl) {
+  PetscErrorCode ierr = KSP_PCApply(ksp, Rr, Zr);CHKERRQ(ierr);
+  return bicg_pc_apply_transpose(ksp, Rl, Zl);
+}
+static PetscErrorCode KSPSolve_BicgHIP(KSP ksp) {
+  PetscErrorCode ierr;
+  KSP_BicgHIP *bd = (KSP_BicgHIP *)ksp->data;
+  Vec X = ksp->vec_sol, B = ksp->vec_rhs;
+  Vec Rr = ksp->work[0], Rl = ksp->work[1], Zr = ksp->work[2], Zl = ksp->work[3], Pr = ksp->work[4], Pl = ksp->work[5];
+  const VecBicgFusedOps *M = bd->fused ? vec_bicg_ops(X) : NULL;
+  const PetscBool pnorm = (PetscBool)(ksp->normtype == KSP_NORM_PRECONDITIONED);
+  HipPCKind pck = PCKIND_GENERAL;
+  Vec d = NULL;
+  Mat A;
+  PetscScalar dpi, a, beta = 0.0, betaold = 1.0, nrm2 = 0.0;
+  PetscBool have_beta = PETSC_FALSE;
+  PetscReal dp;
+  PetscInt i;
+
+  if (has_null_space(ksp)) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s with a null space: there is no removal behind the transposed preconditioner application", KSPBICGHIPMI355X);
+  ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
+  if (M) { ierr = pc_diagonal_form(ksp, X, &bd->dinv, &pck);CHKERRQ(ierr); if (pck == PCKIND_DIAGONAL) d = bd->dinv; }
+  ksp->its = 0;
+  if (ksp->guess_zero) { ierr = VecCopy(B, Rr);CHKERRQ(ierr); }
+  else { ierr = KSP_MatMult(ksp, A, X, Rr);CHKERRQ(ierr); ierr = VecAYPX(Rr, -1.0, B);CHKERRQ(ierr); }
+  ierr = VecCopy(Rr, Rl);CHKERRQ(ierr);
+  ierr = bicg_precondition(ksp, Rr, Rl, Zr, Zl);CHKERRQ(ierr);
+  ierr = VecNorm(pnorm ? Zr : Rr, NORM_2, &dp);CHKERRQ(ierr);
+  ierr = report(ksp, 0, dp);CHKERRQ(ierr);
+  ierr = KSPTestConvergence(ksp, 0, dp);CHKERRQ(ierr);
+  if (ksp->reason) return 0;
+
+  for (i = 0; i < ksp->max_it; i++) {
+    PetscBool done = PETSC_FALSE, all_fused = PETSC_TRUE, folded = PETSC_FALSE;
+    PetscScalar b;
+    if (!have_beta) { ierr = VecDot(Zr, Rl, &beta);CHKERRQ(ierr); }
+    if (!i && beta == 0.0) { ksp->reason = KSP_DIVERGED_BREAKDOWN; return 0; }
+    b = i ? beta / betaold : 0.0;
+    if (M) { ierr = M->bicg_dirs(Pr, Pl, Zr, Zl, b, (PetscBool)!i, &done);CHKERRQ(ierr); }
+    if (done) bd->nsweeps++;
+    else {
+      all_fused = PETSC_FALSE;
+      if (!i) { ierr = VecCopy(Zr, Pr);CHKERRQ(ierr); ierr = VecCopy(Zl, Pl);CHKERRQ(ierr); }
+      else { ierr = VecAYPX(Pr, b, Zr);CHKERRQ(ierr); ierr = VecAYPX(Pl, b, Zl);CHKERRQ(ierr); }
+    }
+    betaold = beta; have_beta = PETSC_FALSE;
+    ierr = KSP_MatMult(ksp, A, Pr, Zr);CHKERRQ(ierr);
+    ierr = bicg_mult_transpose(ksp, A, Pl, Zl);CHKERRQ(ierr);
+    ierr = VecDot(Zr, Pl, &dpi);CHKERRQ(ierr);
+    if (dpi == 0.0) { ksp->reason = KSP_DIVERGED_BREAKDOWN; if (!all_fused) bd->nopbyop++; break; }
+    a = beta / dpi;
+    done = PETSC_FALSE;
+    if (M) { ierr = M->bicg_update(X, Rr, Rl, Pr, Zr, Zl, d, (PetscBool)(pck == PCKIND_IDENTITY), a, pnorm ? 0 : 1, &beta, &nrm2, &done);CHKERRQ(ierr); }
+    if (done) {
+      bd->nsweeps++;
+      folded = (PetscBool)(pck != PCKIND_GENERAL);
+      if (folded) { have_beta = PETSC_TRUE; dp = PetscSqrtReal(nrm2); }
+      else if (pnorm) { ierr = bicg_precondition(ksp, Rr, Rl, Zr, Zl);CHKERRQ(ierr); ierr = VecNorm(Zr, NORM_2, &dp);CHKERRQ(ierr); }
+      else dp = PetscSqrtReal(nrm2);
+    } else {
+      all_fused = PETSC_FALSE;
+      ierr = VecAXPY(X, a, Pr);CHKERRQ(ierr);
+      ierr = VecAXPY(Rr, -a, Zr);CHKERRQ(ierr);
+      ierr = VecAXPY(Rl, -a, Zl);CHKERRQ(ierr);
+      if (pnorm) { ierr = bicg_precondition(ksp, Rr, Rl, Zr, Zl);CHKERRQ(ierr); }
+      ierr = VecNorm(pnorm ? Zr : Rr, NORM_2, &dp);CHKERRQ(ierr);
+    }
+    if (!all_fused) bd->nopbyop++;
+    ksp->its = i + 1;
+    ierr = report(ksp, i + 1, dp);CHKERRQ(ierr);
+    ierr = KSPTestConvergence(ksp, i + 1, dp);CHKERRQ(ierr);
+    if (ksp->reason) break;
+    if (!pnorm && !folded) { ierr = bicg_precondition(ksp, Rr, Rl, Zr, Zl);CHKERRQ(ierr); }
+  }
+  if (i >= ksp->max_it) ksp->reason = KSP_DIVERGED_ITS;
+  return 0;
+}
+PetscErrorCode KSPCreate_BICGHIPMI355X(KSP ksp) {
+  KSP_BicgHIP *bd;
+  PetscErrorCode ierr = PetscMalloc(sizeof(*bd), &bd);CHKERRQ(ierr);
+  bd->fused = PETSC_TRUE; bd->dinv = NULL; bd->nsweeps = 0; bd->nopbyop = 0;
+  ksp->data = bd;
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);      /* the two of KSPBICG */
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_LEFT, 1);CHKERRQ(ierr);
+  ksp->ops->setup = KSPSetUp_BicgHIP; ksp->ops->solve = KSPSolve_BicgHIP; ksp->ops->setfromoptions = KSPSetFromOptions_BicgHIP; ksp->ops->destroy = KSPDestroy_BicgHIP;
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "KSPGetFusedStepCounts_BicgHIP", (PetscVoidFunction)KSPGetFusedStepCounts_BicgHIP);CHKERRQ(ierr);
+  return 0;
+}
+
 typedef struct { PetscReal scale; Vec dinv; } KSP_RichHIP;
 
 static PetscErrorCode KSPRichardsonSetScale_RichHIP(KSP ksp, PetscReal scale) { ((KSP_RichHIP *)ksp->data)->scale = scale; return 0; }

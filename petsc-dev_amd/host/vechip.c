@@ -1410,6 +1410,57 @@ static const VecTfqmrFusedOps *VecTfqmrFusedOps_HIP(void) {
   return &ops;
 }
 
+/* Fused forms for KSPSolve_BiCG (include/petsckrylovfused.h bicg_dirs, bicg_update), under the rules of the TFQMR forms above */
+PetscErrorCode VecBicgDirs_HIPMI355X(Vec pr, Vec pl, Vec zr, Vec zl, PetscScalar b, PetscBool first, PetscBool *done) {
+  PetscErrorCode ierr; DEVCTX;
+  Vec all[4] = {pr, pl, zr, zl};
+  const PetscScalar *dzr, *dzl; PetscScalar *dpr, *dpl;
+  *done = PETSC_FALSE;
+  if (!pr || !pl || !zr || !zl || !tfqmr_operands_ok(all, 4, 2)) return 0;
+  ierr = VecHIPGetRead(zr, &dzr);CHKERRQ(ierr);
+  ierr = VecHIPGetRead(zl, &dzl);CHKERRQ(ierr);
+  if (first || b == 0.0) { ierr = VecHIPGetWrite(pr, &dpr);CHKERRQ(ierr); ierr = VecHIPGetWrite(pl, &dpl);CHKERRQ(ierr); }
+  else { ierr = VecHIPGetReadWrite(pr, &dpr);CHKERRQ(ierr); ierr = VecHIPGetReadWrite(pl, &dpl);CHKERRQ(ierr); }
+  CHKHIP(mi355x_vec_bicg_dirs(dc->h, N_(pr), first ? 1 : 0, b, dzr, dzl, dpr, dpl));
+  VecHIPRestoreWrite(pr); VecHIPRestoreWrite(pl);
+  HipStateIncrease(pr); HipStateIncrease(pl);
+  ierr = PetscLogFlops(first ? 0.0 : 4.0 * pr->map->n);CHKERRQ(ierr);
+  *done = PETSC_TRUE;
+  return 0;
+}
+/* zr'rl and the norm's sum are all-reduced as every fused reduction is (reduce_finish2: RCCL, host-staged or one rank) */
+PetscErrorCode VecBicgUpdate_HIPMI355X(Vec x, Vec rr, Vec rl, Vec pr, Vec zr, Vec zl, Vec d, PetscBool identity, PetscScalar a, PetscInt which,
+                                       PetscScalar *beta, PetscScalar *nrm2, PetscBool *done) {
+  PetscErrorCode ierr; DEVCTX;
+  Vec all[7] = {x, rr, rl, zr, zl, pr, d};
+  const int pcmode = d ? 1 : (identity ? 2 : 0);
+  const PetscScalar *dpr, *dd = NULL; PetscScalar *dx, *drr, *drl, *dzr, *dzl, res[2]; double *out;
+  *done = PETSC_FALSE;
+  if (!x || !rr || !rl || !pr || !zr || !zl || (which != 0 && which != 1) || (d && identity) || !tfqmr_operands_ok(all, 7, 5)) return 0;
+  ierr = VecHIPGetRead(pr, &dpr);CHKERRQ(ierr);
+  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
+  ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr);
+  ierr = VecHIPGetReadWrite(rr, &drr);CHKERRQ(ierr);
+  ierr = VecHIPGetReadWrite(rl, &drl);CHKERRQ(ierr);
+  ierr = VecHIPGetReadWrite(zr, &dzr);CHKERRQ(ierr);
+  ierr = VecHIPGetReadWrite(zl, &dzl);CHKERRQ(ierr);
+  ierr = reduce_target(rr, dc, &out);CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_bicg_update(dc->h, N_(rr), a, pcmode, (int)which, dpr, dd, dx, drr, drl, dzr, dzl, out));
+  if (a != 0.0) { VecHIPRestoreWrite(x); HipStateIncrease(x); VecHIPRestoreWrite(rr); HipStateIncrease(rr); VecHIPRestoreWrite(rl); HipStateIncrease(rl); }
+  if (pcmode) { VecHIPRestoreWrite(zr); HipStateIncrease(zr); VecHIPRestoreWrite(zl); HipStateIncrease(zl); }
+  ierr = reduce_finish2(rr, dc, 2, 2, 0, res);CHKERRQ(ierr);
+  if (pcmode && beta) *beta = res[0];
+  *nrm2 = res[1];
+  ierr = PetscLogFlops((6.0 + (pcmode == 1 ? 2.0 : 0.0) + (pcmode ? 4.0 : 2.0)) * rr->map->n);CHKERRQ(ierr);
+  *done = PETSC_TRUE;
+  return 0;
+}
+/* "VecBicgFusedOps_C": the sweeps of BiCG */
+static const VecBicgFusedOps *VecBicgFusedOps_HIP(void) {
+  static const VecBicgFusedOps ops = {VecBicgDirs_HIPMI355X, VecBicgUpdate_HIPMI355X};
+  return &ops;
+}
+
 /* the *_local slots of struct _VecOps (vecimpl.h:262-266): the same device reductions without the step across ranks;
  * NORM_2 returns the root of the local sum, as VecNorm_Seq does for VecNormBegin (comb.c squares it again) */
 static PetscErrorCode VecDot_HIP_local(Vec x, Vec y, PetscScalar *val) { hip_local_only = 1; PetscErrorCode ierr = VecDot_HIP(x, y, val); hip_local_only = 0; return ierr; }
@@ -1603,6 +1654,7 @@ static PetscErrorCode VecCreate_HIP_common(Vec v, const char *tname) {
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecPipelinedCGFusedOps_C", "VecPipelinedCGFusedOps_HIP", (PetscVoidFunction)VecPipelinedCGFusedOps_HIP);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecMinresFusedOps_C", "VecMinresFusedOps_HIP", (PetscVoidFunction)VecMinresFusedOps_HIP);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecTfqmrFusedOps_C", "VecTfqmrFusedOps_HIP", (PetscVoidFunction)VecTfqmrFusedOps_HIP);CHKERRQ(ierr);
+  ierr = PetscObjectComposeFunction((PetscObject)v, "VecBicgFusedOps_C", "VecBicgFusedOps_HIP", (PetscVoidFunction)VecBicgFusedOps_HIP);CHKERRQ(ierr);
   return 0;
 }
 
