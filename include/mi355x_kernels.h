@@ -525,7 +525,8 @@ int mi355x_ilu0_factor_create_fill(mi355x_handle_t h, int n, const int *ai_host,
  * MatSolve_SeqBAIJ_<bs>_NaturalOrdering  src/mat/impls/baij/seq/baijfact2.c on the point factor's layout over BLOCK rows and columns (bi,
  * bj, bdiag as above; mi355x_iluk_symbolic_host on the block pattern builds it) with ba holding one column-major bs x bs block per
  * stored entry and the INVERTED diagonal block at bdiag[i], 2 <= bs <= 7.  One launch per dependency level, `rows` the block rows of
- * the level (device array); one lane per scalar row, the bs lanes of a block row in one wavefront.
+ * the level (device array); one lane per scalar row, the bs lanes of a block row in one wavefront.  Or one launch for a run of
+ * consecutive levels (_chain), the same arithmetic in the same order: the two ways give the same bits.
  *   _lower_level  component r of block row i: s = b[bs i + r]; for every stored L block (i,k) in storage order, with v the block and
  *             x_k the solution of block row k, s = s - (v[r] x_k[0] + v[r + bs] x_k[1] + ... + v[r + (bs-1) bs] x_k[bs-1]) -- the
  *             products summed left to right, then one subtraction; x[bs i + r] = s.  b may alias x.
@@ -534,6 +535,19 @@ int mi355x_ilu0_factor_create_fill(mi355x_handle_t h, int n, const int *ai_host,
  *             bs components.
  *   bs outside 2..7: hipErrorInvalidValue, nothing launched.  nrows <= 0 launches nothing.  Padding lanes and rows past nrows neither
  *   load nor store.  No hand-off between workgroups: the kernel boundary between levels is the only synchronisation.
+ *   _lower_chain / _upper_chain  nlev consecutive levels in ONE launch of ONE workgroup of 1024 threads: level l is the block rows
+ *             rows[levptr[l]] .. rows[levptr[l+1] - 1] (levptr: nlev + 1 non-decreasing offsets into rows, a DEVICE array; a sub-range
+ *             of a factor's levels is levptr + l0 with nlev = l1 - l0 and the same rows).  The workgroup takes a level 1024 / W block
+ *             rows at a time (W = 2, 4, 8 lanes for bs = 2, 3..4, 5..7), each pass the body of the level kernel, then ONE
+ *             __syncthreads() per level; an empty level costs that barrier.  x is written with plain stores and read behind the
+ *             barrier by waves of the same workgroup: no hand-off between workgroups, no polling, no atomics, nothing that can
+ *             hang.  Worth it for levels too narrow to fill more than one CU; a wide level wants _level's grid.  b may alias x in
+ *             _lower_chain.  bs outside 2..7: hipErrorInvalidValue, nothing launched; nlev <= 0 launches nothing.
+ *   _chain_plan_host  which levels to chain, on HOST arrays, no device call: a level is narrow when it has at most max_rows block
+ *             rows (max_rows <= 0: no level is).  [0, nlev) is cut into *nseg segments seg_ptr[s] .. seg_ptr[s+1] - 1 in order: every
+ *             maximal run of narrow levels is one segment with seg_fused[s] = 1 (a run of one level included), every wide level
+ *             a segment of its own with seg_fused[s] = 0.  seg_ptr holds nlev + 1 ints, seg_fused nlev.  nlev = 0: *nseg = 0, the
+ *             arrays untouched.  hipErrorInvalidValue for nlev < 0, a NULL array with nlev > 0, a NULL nseg, a decreasing levptr.
  *   _numeric_host  MatLUFactorNumeric_SeqBAIJ_<bs>_NaturalOrdering restated on HOST arrays, one thread, no device call: A's block
  *             CSR (ai, aj, aa; mbs block rows) into ba on a factor pattern that contains A's.  Block row i: every work block of the
  *             factor row starts at +0.0 with A's blocks copied in; for every L block (i,k) in ascending k, fill included, that is not
@@ -547,6 +561,11 @@ int mi355x_bilu_lower_level(mi355x_handle_t h, int nrows, const int *rows, int b
                             const double *b, double *x);
 int mi355x_bilu_upper_level(mi355x_handle_t h, int nrows, const int *rows, int bs, const int *bj, const double *ba, const int *bdiag,
                             double *x);
+int mi355x_bilu_lower_chain(mi355x_handle_t h, int nlev, const int *levptr, const int *rows, int bs, const int *bi, const int *bj,
+                            const double *ba, const double *b, double *x);
+int mi355x_bilu_upper_chain(mi355x_handle_t h, int nlev, const int *levptr, const int *rows, int bs, const int *bj, const double *ba,
+                            const int *bdiag, double *x);
+int mi355x_bilu_chain_plan_host(int nlev, const int *levptr, int max_rows, int *seg_ptr, int *seg_fused, int *nseg);
 int mi355x_bilu_numeric_host(int mbs, int bs, const int *ai, const int *aj, const double *aa, const int *bi, const int *bj,
                              const int *bdiag, double *ba, int *zero_pivot_row);
 

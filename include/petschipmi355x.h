@@ -138,6 +138,7 @@ PetscErrorCode PCILUApplyInPlace_HIPMI355X(PC pc, Vec v);   /* v <- factor appli
 PetscErrorCode PCFactorDebugSetAborted_HIPMI355X(PC pc);   /* tests: raise the "a dependency wait gave up" flag of this PC's sync-free plans */
 PetscErrorCode PCILUGetSolver_HIPMI355X(PC pc, PetscInt *syncfree, PetscInt *aborted);   /* 1: two-launch sync-free solves (-pc_factor_hipmi355x_trisolve syncfree, default above 16 levels); 0: one launch per level */
 PetscErrorCode PCBILUGetInfo_HIPMI355X(PC pc, PetscInt *bs, PetscInt *levels_L, PetscInt *levels_U, PetscInt *nz_blocks);   /* PCILU over a BAIJ operator (block ILU(k), host/bilu.c): block size, dependency levels of the two block triangular solves, stored blocks of the factor */
+PetscErrorCode PCBILUGetSolvePlan_HIPMI355X(PC pc, PetscInt *fused, PetscInt *launches_L, PetscInt *launches_U);   /* the same PC: 1 under -pc_factor_hipmi355x_trisolve fused (runs of narrow levels in one launch each), 0 level by level; the launches one application makes for L and for U */
 
 #ifdef __cplusplus
 }

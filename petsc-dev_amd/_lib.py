@@ -165,6 +165,9 @@ KERNEL_API = {
     "mi355x_ilut_build_host": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, pi32, vp, pi32],
     "mi355x_bilu_lower_level": [vp, i32, vp, i32, vp, vp, vp, vp, vp],
     "mi355x_bilu_upper_level": [vp, i32, vp, i32, vp, vp, vp, vp],
+    "mi355x_bilu_lower_chain": [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp],
+    "mi355x_bilu_upper_chain": [vp, i32, vp, vp, i32, vp, vp, vp, vp],
+    "mi355x_bilu_chain_plan_host": [i32, vp, i32, vp, vp, pi32],
     "mi355x_bilu_numeric_host": [i32, i32, vp, vp, vp, vp, vp, vp, vp, pi32],
     "mi355x_sor_levels_host": [i32, vp, vp, vp, pi32],
     "mi355x_sor_plan_create": [vp, i32, vp, vp, i32, C.POINTER(vp), pi32],

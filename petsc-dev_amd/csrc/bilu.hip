@@ -11,6 +11,9 @@
 // inverted diagonal block, which needs the group's bs sums: they travel by cross-lane shuffles, never through memory.  Padding
 // lanes and the groups past nrows take part in the shuffles with an empty block range and neither load nor store.
 // Rows of one dependency level do not read each other, a kernel boundary separates the levels: nothing here waits on anything.
+// The chain kernels run the same body for a run of consecutive levels in one launch of ONE workgroup of 1024 threads, with a
+// workgroup barrier where the level route has a kernel boundary (worth it for levels well under one pass of that workgroup:
+// DESIGN.md, "Block ILU(k)"); mi355x_bilu_chain_plan_host says which levels to chain.
 #include "common.hpp"
 #include "mi355x_block_inverse.h"
 #include <string.h>
@@ -38,14 +41,15 @@ template <int BS> __device__ __forceinline__ double bilu_sweep(double s, int q0,
   return s;
 }
 
-// UPPER = false: x_i = b_i - sum_k L_ik x_k (bdiag unused).  UPPER = true: x_i = D_i^-1 (x_i - sum_k U_ik x_k) in place.
+// One pass of a level: group g of `nrows` block rows, lane r of the group.  UPPER = false: x_i = b_i - sum_k L_ik x_k (bdiag unused).
+// UPPER = true: x_i = D_i^-1 (x_i - sum_k U_ik x_k) in place.  Every lane of the wavefront calls this, a lane without a scalar row
+// (padding, g >= nrows) with an empty block range: it takes part in the shuffles and neither loads nor stores.  The level kernel and
+// the chain kernel both run this body and nothing else on the values.
 template <int BS, bool UPPER>
-__global__ __launch_bounds__(MI355X_BLOCK) void bilu_level_kernel(int nrows, const int *__restrict__ rows, const int *__restrict__ bi,
-                                                                  const int *__restrict__ bj, const double *__restrict__ ba,
-                                                                  const int *__restrict__ bdiag, const double *b, double *x) {
+__device__ __forceinline__ void bilu_pass(int g, int nrows, int r, const int *__restrict__ rows, const int *__restrict__ bi,
+                                          const int *__restrict__ bj, const double *__restrict__ ba, const int *__restrict__ bdiag,
+                                          const double *b, double *x) {
   constexpr int W = BiluGroup<BS>::W;
-  const int t = blockIdx.x * MI355X_BLOCK + threadIdx.x;
-  const int g = t / W, r = t & (W - 1);
   const bool live = g < nrows && r < BS;
   int i = 0, q0 = 0, q1 = 0;
   double s = 0.0;
@@ -72,6 +76,38 @@ __global__ __launch_bounds__(MI355X_BLOCK) void bilu_level_kernel(int nrows, con
 }
 
 template <int BS, bool UPPER>
+__global__ __launch_bounds__(MI355X_BLOCK) void bilu_level_kernel(int nrows, const int *__restrict__ rows, const int *__restrict__ bi,
+                                                                  const int *__restrict__ bj, const double *__restrict__ ba,
+                                                                  const int *__restrict__ bdiag, const double *b, double *x) {
+  constexpr int W = BiluGroup<BS>::W;
+  const int t = blockIdx.x * MI355X_BLOCK + threadIdx.x;
+  bilu_pass<BS, UPPER>(t / W, nrows, t & (W - 1), rows, bi, bj, ba, bdiag, b, x);
+}
+
+// The levels 0 .. nlev - 1 of levptr by ONE workgroup of BILU_CHAIN_BLOCK threads: level l is the block rows rows[levptr[l]] ..
+// rows[levptr[l + 1] - 1], taken BILU_CHAIN_BLOCK / W at a time, then one barrier (the rows of a level do not read each other).
+// nlev is a kernel argument and levptr[l] one address for the whole workgroup, so every trip count is the same in every thread:
+// every thread runs every pass (past the level's end with an empty block range) and reaches every barrier.  x is written with
+// plain stores and read after __syncthreads() by the waves of the same workgroup, which share one L1: the barrier's
+// workgroup-scope fence is all the ordering there is, and x and b are plain pointers so that no load of x moves across it.
+#define BILU_CHAIN_BLOCK 1024
+template <int BS, bool UPPER>
+__global__ __launch_bounds__(BILU_CHAIN_BLOCK) void bilu_chain_kernel(int nlev, const int *__restrict__ levptr, const int *__restrict__ rows,
+                                                                      const int *__restrict__ bi, const int *__restrict__ bj,
+                                                                      const double *__restrict__ ba, const int *__restrict__ bdiag,
+                                                                      const double *b, double *x) {
+  constexpr int W = BiluGroup<BS>::W, PER_PASS = BILU_CHAIN_BLOCK / W;
+  const int g = (int)threadIdx.x / W, r = (int)threadIdx.x & (W - 1);
+  int r0 = levptr[0];
+  for (int l = 0; l < nlev; ++l) {
+    const int r1 = levptr[l + 1], n = r1 - r0;
+    for (int base = 0; base < n; base += PER_PASS) bilu_pass<BS, UPPER>(base + g, n, r, rows + r0, bi, bj, ba, bdiag, b, x);
+    __syncthreads();
+    r0 = r1;
+  }
+}
+
+template <int BS, bool UPPER>
 static int bilu_launch(mi355x_handle_t h, int nrows, const int *rows, const int *bi, const int *bj, const double *ba, const int *bdiag,
                        const double *b, double *x) {
   constexpr int per_block = MI355X_BLOCK / BiluGroup<BS>::W;       // block rows per workgroup
@@ -80,19 +116,26 @@ static int bilu_launch(mi355x_handle_t h, int nrows, const int *rows, const int 
   MI355X_LAUNCH_CHECK();
   return 0;
 }
+template <int BS, bool UPPER>
+static int bilu_chain_launch(mi355x_handle_t h, int nlev, const int *levptr, const int *rows, const int *bi, const int *bj, const double *ba,
+                             const int *bdiag, const double *b, double *x) {
+  hipLaunchKernelGGL((bilu_chain_kernel<BS, UPPER>), dim3(1), dim3(BILU_CHAIN_BLOCK), 0, h->stream, nlev, levptr, rows, bi, bj, ba, bdiag, b, x);
+  MI355X_LAUNCH_CHECK();
+  return 0;
+}
+// nlev == 0: one level launch of `count` block rows of `rows`; nlev > 0: one chain launch over the levels of levptr
 template <bool UPPER>
-static int bilu_dispatch(mi355x_handle_t h, int nrows, const int *rows, int bs, const int *bi, const int *bj, const double *ba,
-                         const int *bdiag, const double *b, double *x) {
+static int bilu_dispatch(mi355x_handle_t h, int count, int nlev, const int *levptr, const int *rows, int bs, const int *bi, const int *bj,
+                         const double *ba, const int *bdiag, const double *b, double *x) {
   if (bs < BILU_MIN_BS || bs > BILU_MAX_BS) return (int)hipErrorInvalidValue;
-  if (nrows <= 0) return 0;
+  if (count <= 0 && nlev <= 0) return 0;
+#define BILU_CASE(BS) case BS: return nlev > 0 ? bilu_chain_launch<BS, UPPER>(h, nlev, levptr, rows, bi, bj, ba, bdiag, b, x) \
+                                               : bilu_launch<BS, UPPER>(h, count, rows, bi, bj, ba, bdiag, b, x)
   switch (bs) {
-    case 2: return bilu_launch<2, UPPER>(h, nrows, rows, bi, bj, ba, bdiag, b, x);
-    case 3: return bilu_launch<3, UPPER>(h, nrows, rows, bi, bj, ba, bdiag, b, x);
-    case 4: return bilu_launch<4, UPPER>(h, nrows, rows, bi, bj, ba, bdiag, b, x);
-    case 5: return bilu_launch<5, UPPER>(h, nrows, rows, bi, bj, ba, bdiag, b, x);
-    case 6: return bilu_launch<6, UPPER>(h, nrows, rows, bi, bj, ba, bdiag, b, x);
-    default: return bilu_launch<7, UPPER>(h, nrows, rows, bi, bj, ba, bdiag, b, x);
+    BILU_CASE(2); BILU_CASE(3); BILU_CASE(4); BILU_CASE(5); BILU_CASE(6);
+    default: BILU_CASE(7);
   }
+#undef BILU_CASE
 }
 
 // ---------------------------------------------------------------------------------------------------- numeric factorisation, host
@@ -119,12 +162,42 @@ extern "C" {
 
 int mi355x_bilu_lower_level(mi355x_handle_t h, int nrows, const int *rows, int bs, const int *bi, const int *bj, const double *ba,
                             const double *b, double *x) {
-  return bilu_dispatch<false>(h, nrows, rows, bs, bi, bj, ba, nullptr, b, x);
+  return bilu_dispatch<false>(h, nrows, 0, nullptr, rows, bs, bi, bj, ba, nullptr, b, x);
 }
 
 int mi355x_bilu_upper_level(mi355x_handle_t h, int nrows, const int *rows, int bs, const int *bj, const double *ba, const int *bdiag,
                             double *x) {
-  return bilu_dispatch<true>(h, nrows, rows, bs, nullptr, bj, ba, bdiag, nullptr, x);
+  return bilu_dispatch<true>(h, nrows, 0, nullptr, rows, bs, nullptr, bj, ba, bdiag, nullptr, x);
+}
+
+int mi355x_bilu_lower_chain(mi355x_handle_t h, int nlev, const int *levptr, const int *rows, int bs, const int *bi, const int *bj,
+                            const double *ba, const double *b, double *x) {
+  return bilu_dispatch<false>(h, 0, nlev, levptr, rows, bs, bi, bj, ba, nullptr, b, x);
+}
+
+int mi355x_bilu_upper_chain(mi355x_handle_t h, int nlev, const int *levptr, const int *rows, int bs, const int *bj, const double *ba,
+                            const int *bdiag, double *x) {
+  return bilu_dispatch<true>(h, 0, nlev, levptr, rows, bs, nullptr, bj, ba, bdiag, nullptr, x);
+}
+
+int mi355x_bilu_chain_plan_host(int nlev, const int *levptr, int max_rows, int *seg_ptr, int *seg_fused, int *nseg) {
+  if (!nseg) return (int)hipErrorInvalidValue;
+  *nseg = 0;
+  if (nlev < 0) return (int)hipErrorInvalidValue;
+  if (nlev == 0) return 0;
+  if (!levptr || !seg_ptr || !seg_fused) return (int)hipErrorInvalidValue;
+  for (int l = 0; l < nlev; ++l) if (levptr[l + 1] < levptr[l]) return (int)hipErrorInvalidValue;
+  int ns = 0;
+  for (int l = 0; l < nlev;) {
+    int e = l + 1;                                                     // a wide level: a segment of its own
+    const bool narrow = max_rows > 0 && levptr[l + 1] - levptr[l] <= max_rows;
+    if (narrow) while (e < nlev && levptr[e + 1] - levptr[e] <= max_rows) ++e;   // the maximal run of narrow levels from l
+    seg_ptr[ns] = l; seg_fused[ns] = narrow ? 1 : 0; ++ns;
+    l = e;
+  }
+  seg_ptr[ns] = nlev;
+  *nseg = ns;
+  return 0;
 }
 
 int mi355x_bilu_numeric_host(int mbs, int bs, const int *ai, const int *aj, const double *aa, const int *bi, const int *bj,

@@ -14,10 +14,14 @@
  *              whose operator has the pattern of the last one (Mat_SeqAIJHIP.pattern_gen, sizes, levels of fill) repeats these two only;
  *   solve    : mi355x_bilu_lower_level for L's levels in ascending order, then mi355x_bilu_upper_level for U's: one launch per level on
  *              the compute stream, no host wait.  A kernel boundary per level is the only synchronisation, so this route cannot hang.
+ *              -pc_factor_hipmi355x_trisolve fused (opt-in; level is the default): every maximal run of consecutive levels of at most
+ *              -pc_factor_hipmi355x_bilu_chain_rows <n> (default 128) block rows each is ONE launch of one workgroup (mi355x_bilu_lower_chain /
+ *              _upper_chain: a barrier between levels, no hand-off between workgroups, so no hang either), wider levels keep their
+ *              own launch; the plan (mi355x_bilu_chain_plan_host) is cut once per pattern and chain_rows.  Same bits as level.
  *
  * PETSC_ERR_SUP, before anything is changed: ICC and LU of a block matrix, a -pc_factor_shift_type other than none (PCILU's unset default
  * is taken as none here: the reference's BAIJ factorisation has no shift loop either), -pc_factor_hipmi355x_numeric device,
- * -pc_factor_hipmi355x_trisolve other than level, 1 = bs or bs > 7, a non-square matrix, an ordering other than the natural one.
+ * -pc_factor_hipmi355x_trisolve other than level or fused, 1 = bs or bs > 7, a non-square matrix, an ordering other than the natural one.
  * Inside a PETSc tree (PETSCHIPMI355X_WITH_PETSC) the block type composes no factor: PETSc's own MATSEQBAIJ factorisation is what
  * MatGetFactor finds there. */
 #include "hipmi355ximpl.h"
@@ -31,9 +35,10 @@ static void bilu_free_values(HipBlockFactors *f) {
   f->factored_state = -1;
 }
 static void bilu_free_pattern(HipBlockFactors *f) {
-  void *dev[] = {f->pat.d_bi, f->pat.d_bj, f->pat.d_bdiag, f->pat.d_rowsL, f->pat.d_rowsU};
+  void *dev[] = {f->pat.d_bi, f->pat.d_bj, f->pat.d_bdiag, f->pat.d_rowsL, f->pat.d_rowsU, f->pat.d_levptrL, f->pat.d_levptrU};
   for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); i++) if (dev[i]) mi355x_free(dev[i]);
   HipFree(f->pat.bi); HipFree(f->pat.bj); HipFree(f->pat.bdiag); HipFree(f->pat.levptrL); HipFree(f->pat.levptrU);
+  HipFree(f->pat.segL); HipFree(f->pat.segU);
   memset(&f->pat, 0, sizeof(f->pat));
 }
 PetscErrorCode HipBlockFactorsDestroy(HipBlockFactors **pf) {
@@ -45,16 +50,38 @@ PetscErrorCode HipBlockFactorsDestroy(HipBlockFactors **pf) {
   return 0;
 }
 
-/* what this route does not offer, asked for under the factor's prefix: refused before anything is changed */
-static PetscErrorCode bilu_refuse_options(Mat F) {
+/* what this route does not offer, asked for under the factor's prefix: refused before anything is changed.  What it does offer, if the
+ * caller wants it: *fused = -pc_factor_hipmi355x_trisolve fused, *chain_rows = -pc_factor_hipmi355x_bilu_chain_rows (-1: not given) */
+static PetscErrorCode bilu_refuse_options(Mat F, int *fused, PetscInt *chain_rows) {
   PetscErrorCode ierr;
   char v[64]; PetscBool set;
+  PetscInt n = -1;
   ierr = PetscOptionsGetString(HipObjPrefix(F), "-pc_factor_shift_type", v, sizeof(v), &set);CHKERRQ(ierr);
   if (set && strcmp(v, "none") && strcmp(v, "NONE")) SETERRQ(HipObjComm(F), PETSC_ERR_SUP, "-pc_factor_shift_type %s: block ILU of a BAIJ matrix has no shifts (none only)", v);
   ierr = PetscOptionsGetString(HipObjPrefix(F), "-pc_factor_hipmi355x_numeric", v, sizeof(v), &set);CHKERRQ(ierr);
   if (set && strcmp(v, "host")) SETERRQ(HipObjComm(F), PETSC_ERR_SUP, "-pc_factor_hipmi355x_numeric %s: block ILU of a BAIJ matrix is factored on the host", v);
   ierr = PetscOptionsGetString(HipObjPrefix(F), "-pc_factor_hipmi355x_trisolve", v, sizeof(v), &set);CHKERRQ(ierr);
-  if (set && strcmp(v, "level")) SETERRQ(HipObjComm(F), PETSC_ERR_SUP, "-pc_factor_hipmi355x_trisolve %s: block ILU of a BAIJ matrix solves level by level (level only)", v);
+  if (set && strcmp(v, "level") && strcmp(v, "fused")) SETERRQ(HipObjComm(F), PETSC_ERR_SUP, "-pc_factor_hipmi355x_trisolve %s: block ILU of a BAIJ matrix solves level by level, one launch per level (level) or per run of narrow levels (fused)", v);
+  if (fused) *fused = set && !strcmp(v, "fused");
+  ierr = PetscOptionsGetInt(HipObjPrefix(F), "-pc_factor_hipmi355x_bilu_chain_rows", &n, &set);CHKERRQ(ierr);
+  if (set && n < 0) SETERRQ(HipObjComm(F), PETSC_ERR_ARG_OUTOFRANGE, "-pc_factor_hipmi355x_bilu_chain_rows %d: a number of block rows >= 0 (0: no level is chained)", n);
+  if (chain_rows) *chain_rows = set ? n : -1;
+  return 0;
+}
+
+/* the launches of one application under trisolve fused, from the host level lists: once per pattern and per max_rows */
+static PetscErrorCode bilu_plan(HipBlockFactors *f, PetscInt max_rows) {
+  PetscErrorCode ierr;
+  struct { PetscInt nlev; const PetscInt *levptr; PetscInt **seg, *nseg; } tri[2] = {{f->pat.nlevL, f->pat.levptrL, &f->pat.segL, &f->pat.nsegL},
+                                                                                    {f->pat.nlevU, f->pat.levptrU, &f->pat.segU, &f->pat.nsegU}};
+  for (int t = 0; t < 2; t++) {
+    int nseg = 0;
+    HipFree(*tri[t].seg); *tri[t].seg = NULL; *tri[t].nseg = 0;
+    ierr = PetscMalloc(sizeof(PetscInt) * (size_t)(2 * tri[t].nlev + 2), tri[t].seg);CHKERRQ(ierr);
+    CHKHIP(mi355x_bilu_chain_plan_host((int)tri[t].nlev, tri[t].levptr, (int)max_rows, *tri[t].seg, *tri[t].seg + tri[t].nlev + 1, &nseg));
+    *tri[t].nseg = nseg;
+  }
+  f->pat.plan_rows = max_rows;
   return 0;
 }
 
@@ -73,7 +100,7 @@ static PetscErrorCode bilu_level_order(PetscInt n, const PetscInt *lev, PetscInt
 }
 
 /* the pattern side, once per pattern: the level-of-fill layout over blocks, the levels of L and U, everything but the values uploaded */
-static PetscErrorCode bilu_pattern(Mat A, HipBlockFactors *f, PetscDeviceCtx *dc, PetscInt mbs, PetscInt bs, const PetscInt *ai, const PetscInt *aj, PetscInt levels) {
+static PetscErrorCode bilu_pattern(Mat A, HipBlockFactors *f, PetscDeviceCtx *dc, PetscInt mbs, PetscInt bs, const PetscInt *ai, const PetscInt *aj, PetscInt levels, PetscInt max_rows) {
   PetscErrorCode ierr = 0;
   PetscInt *lev = NULL, *rows = NULL;
   int bad = -1, rc;
@@ -118,7 +145,9 @@ static PetscErrorCode bilu_pattern(Mat A, HipBlockFactors *f, PetscDeviceCtx *dc
     f->pat.nlevU = nlev;
     if (!ierr && !rc) ierr = bilu_level_order(mbs, lev, nlev, &f->pat.levptrU, rows);
     if (!ierr && !rc) { rc = mi355x_malloc((void **)&f->pat.d_rowsU, nr); if (!rc) rc = mi355x_memcpy_h2d(dc->h, f->pat.d_rowsU, rows, nr); }
-    struct { void *p; const void *from; size_t bytes; } up[] = {{&f->pat.d_bi, bi, ni}, {&f->pat.d_bj, bj, nj}, {&f->pat.d_bdiag, bdiag, ni}};
+    struct { void *p; const void *from; size_t bytes; } up[] = {{&f->pat.d_bi, bi, ni}, {&f->pat.d_bj, bj, nj}, {&f->pat.d_bdiag, bdiag, ni},
+                                                                {&f->pat.d_levptrL, f->pat.levptrL, sizeof(PetscInt) * (size_t)(f->pat.nlevL + 1)},
+                                                                {&f->pat.d_levptrU, f->pat.levptrU, sizeof(PetscInt) * (size_t)(f->pat.nlevU + 1)}};
     for (size_t i = 0; i < sizeof(up) / sizeof(up[0]) && !ierr && !rc; i++) {
       rc = mi355x_malloc((void **)up[i].p, up[i].bytes);
       if (!rc) rc = mi355x_memcpy_h2d(dc->h, *(void **)up[i].p, up[i].from, up[i].bytes);
@@ -128,6 +157,7 @@ static PetscErrorCode bilu_pattern(Mat A, HipBlockFactors *f, PetscDeviceCtx *dc
   HipFree(lev);
   CHKERRQ(ierr);
   CHKHIP(rc);
+  ierr = bilu_plan(f, max_rows);CHKERRQ(ierr);
   f->pat.gen = ((Mat_SeqAIJHIP *)A->spptr)->pattern_gen; f->pat.stale = 0;
   f->symbolic_builds++;
   return 0;
@@ -145,11 +175,17 @@ static PetscErrorCode MatLUFactorNumeric_SeqBAIJHIP(Mat F, Mat A, const MatFacto
   Mat_SeqAIJHIP *d = (Mat_SeqAIJHIP *)A->spptr;
   PetscDeviceCtx *dc;
   PetscInt mbs; const PetscInt *ai, *aj; const PetscScalar *aa;
-  int zrow = -1, rc;
+  int zrow = -1, rc, fused = 0;
+  PetscInt chain_rows = -1;
   if (strcmp(HipObjTypeName(A), MATSEQBAIJHIPMI355X)) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "block ILU on the device needs a sequential BAIJ matrix of this type; got %s", HipObjTypeName(A));
   if (A->rmap->n != A->cmap->n) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "block ILU of a BAIJ matrix: square matrices only, rows %d columns %d", A->rmap->n, A->cmap->n);
-  ierr = bilu_refuse_options(F);CHKERRQ(ierr);
-  if (f->factored_state == HipObjState(A) && f->factored_of == (void *)A && f->d_ba && !f->pat.stale) return 0;   /* same operator, same values: nothing to redo */
+  ierr = bilu_refuse_options(F, &fused, &chain_rows);CHKERRQ(ierr);
+  if (f->factored_state == HipObjState(A) && f->factored_of == (void *)A && f->d_ba && !f->pat.stale) {   /* same operator, same values: nothing to redo ... */
+    f->fused = fused;                                                                                      /* ... but the route of this set-up */
+    if (chain_rows < 0) chain_rows = HIP_BILU_CHAIN_ROWS;
+    if (chain_rows != f->pat.plan_rows) { ierr = bilu_plan(f, chain_rows);CHKERRQ(ierr); }
+    return 0;
+  }
   ierr = MatSeqAIJGetArrays(A, &mbs, &ai, &aj, &aa);CHKERRQ(ierr);
   const PetscInt bs = mbs ? A->rmap->n / mbs : HipAIJGet(A)->bs;
   if (bs < 2 || bs > 7) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "block ILU of a BAIJ matrix: block sizes 2 .. 7, got %d", bs);
@@ -158,7 +194,10 @@ static PetscErrorCode MatLUFactorNumeric_SeqBAIJHIP(Mat F, Mat A, const MatFacto
   const int same = f->pat.bi && !f->pat.stale && d->pattern_gen && f->pat.gen == d->pattern_gen && f->mbs == mbs && f->bs == bs && f->nzbA == ai[mbs] &&
                    f->levels == (PetscInt)info->levels;
   f->factored_state = -1;
-  if (!same) { ierr = bilu_pattern(A, f, dc, mbs, bs, ai, aj, (PetscInt)info->levels);CHKERRQ(ierr); }
+  if (chain_rows < 0) chain_rows = HIP_BILU_CHAIN_ROWS;
+  if (!same) { ierr = bilu_pattern(A, f, dc, mbs, bs, ai, aj, (PetscInt)info->levels, chain_rows);CHKERRQ(ierr); }
+  else if (chain_rows != f->pat.plan_rows) { ierr = bilu_plan(f, chain_rows);CHKERRQ(ierr); }
+  f->fused = fused;
   const size_t na = sizeof(PetscScalar) * (size_t)(f->nzb + 1) * (size_t)(bs * bs);
   if (!f->ba) { ierr = PetscMalloc(na, &f->ba);CHKERRQ(ierr); memset(f->ba, 0, na); }
   rc = mi355x_bilu_numeric_host(mbs, bs, ai, aj, aa, f->pat.bi, f->pat.bj, f->pat.bdiag, f->ba, &zrow);
@@ -180,7 +219,7 @@ static PetscErrorCode MatILUFactorSymbolic_SeqBAIJHIP(Mat F, Mat A, IS row, IS c
   if (A->rmap->n != A->cmap->n) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "block ILU of a BAIJ matrix: square matrices only, rows %d columns %d", A->rmap->n, A->cmap->n);
   if (info->levels < 0.0) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_OUTOFRANGE, "Levels of fill negative %d", (int)info->levels);
   if (row || col) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "block ILU of a BAIJ matrix: natural ordering only");
-  ierr = bilu_refuse_options(F);CHKERRQ(ierr);
+  ierr = bilu_refuse_options(F, NULL, NULL);CHKERRQ(ierr);
   HipBlockGet(F)->factored_state = -1;
   HipBlockGet(F)->pat.stale = 1;                                           /* a new symbolic phase: the layout is of the old pattern or level */
   F->ops->lufactornumeric = MatLUFactorNumeric_SeqBAIJHIP;
@@ -197,10 +236,25 @@ static PetscErrorCode MatSolve_SeqBAIJHIP_ILU(Mat F, Vec b, Vec x) {   /* MatSol
   ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
   ierr = VecHIPGetRead(b, &db);CHKERRQ(ierr);
   ierr = VecHIPGetWrite(x, &dx);CHKERRQ(ierr);
-  for (PetscInt l = 0; l < f->pat.nlevL && !rc; l++)
-    rc = mi355x_bilu_lower_level(dc->h, f->pat.levptrL[l + 1] - f->pat.levptrL[l], f->pat.d_rowsL + f->pat.levptrL[l], (int)f->bs, f->pat.d_bi, f->pat.d_bj, f->d_ba, db, dx);
-  for (PetscInt l = 0; l < f->pat.nlevU && !rc; l++)
-    rc = mi355x_bilu_upper_level(dc->h, f->pat.levptrU[l + 1] - f->pat.levptrU[l], f->pat.d_rowsU + f->pat.levptrU[l], (int)f->bs, f->pat.d_bj, f->d_ba, f->pat.d_bdiag, dx);
+  if (f->fused) {   /* segment by segment: a run of narrow levels in one chain launch, a wide level in its own */
+    const PetscInt *seg = f->pat.segL, *chain = f->pat.segL + f->pat.nlevL + 1;
+    for (PetscInt s = 0; s < f->pat.nsegL && !rc; s++) {
+      const PetscInt l = seg[s];
+      if (chain[s]) rc = mi355x_bilu_lower_chain(dc->h, (int)(seg[s + 1] - l), f->pat.d_levptrL + l, f->pat.d_rowsL, (int)f->bs, f->pat.d_bi, f->pat.d_bj, f->d_ba, db, dx);
+      else rc = mi355x_bilu_lower_level(dc->h, f->pat.levptrL[l + 1] - f->pat.levptrL[l], f->pat.d_rowsL + f->pat.levptrL[l], (int)f->bs, f->pat.d_bi, f->pat.d_bj, f->d_ba, db, dx);
+    }
+    seg = f->pat.segU; chain = f->pat.segU + f->pat.nlevU + 1;
+    for (PetscInt s = 0; s < f->pat.nsegU && !rc; s++) {
+      const PetscInt l = seg[s];
+      if (chain[s]) rc = mi355x_bilu_upper_chain(dc->h, (int)(seg[s + 1] - l), f->pat.d_levptrU + l, f->pat.d_rowsU, (int)f->bs, f->pat.d_bj, f->d_ba, f->pat.d_bdiag, dx);
+      else rc = mi355x_bilu_upper_level(dc->h, f->pat.levptrU[l + 1] - f->pat.levptrU[l], f->pat.d_rowsU + f->pat.levptrU[l], (int)f->bs, f->pat.d_bj, f->d_ba, f->pat.d_bdiag, dx);
+    }
+  } else {
+    for (PetscInt l = 0; l < f->pat.nlevL && !rc; l++)
+      rc = mi355x_bilu_lower_level(dc->h, f->pat.levptrL[l + 1] - f->pat.levptrL[l], f->pat.d_rowsL + f->pat.levptrL[l], (int)f->bs, f->pat.d_bi, f->pat.d_bj, f->d_ba, db, dx);
+    for (PetscInt l = 0; l < f->pat.nlevU && !rc; l++)
+      rc = mi355x_bilu_upper_level(dc->h, f->pat.levptrU[l + 1] - f->pat.levptrU[l], f->pat.d_rowsU + f->pat.levptrU[l], (int)f->bs, f->pat.d_bj, f->d_ba, f->pat.d_bdiag, dx);
+  }
   ierr = VecHIPRestoreWrite(x);CHKERRQ(ierr);
   HipStateIncrease(x);
   CHKHIP(rc);
@@ -248,6 +302,25 @@ PetscErrorCode PCBILUGetInfo_HIPMI355X(PC pc, PetscInt *bs, PetscInt *levels_L, 
   if (levels_L) *levels_L = f->pat.nlevL;
   if (levels_U) *levels_U = f->pat.nlevU;
   if (nz_blocks) *nz_blocks = f->nzb;
+  return 0;
+#endif
+}
+
+/* how one application of the same factor is launched: *fused = 1 under -pc_factor_hipmi355x_trisolve fused, and the launches it makes for
+ * L and for U (level route: one per dependency level; fused: one per segment of the plan, a chained run or a wide level) */
+PetscErrorCode PCBILUGetSolvePlan_HIPMI355X(PC pc, PetscInt *fused, PetscInt *launches_L, PetscInt *launches_U) {
+#if defined(PETSCHIPMI355X_WITH_PETSC)
+  (void)fused; (void)launches_L; (void)launches_U;
+  SETERRQ(HipObjComm(pc), PETSC_ERR_SUP, "inside a PETSc tree the BAIJ type composes no factor of its own");
+#else
+  PetscErrorCode ierr;
+  Mat F = NULL;
+  ierr = PCFactorGetMatrix(pc, &F);CHKERRQ(ierr);
+  if (!F || !F->factortype || !F->spptr || !HipBlockGet(F) || !HipBlockGet(F)->d_ba) SETERRQ(HipObjComm(pc), PETSC_ERR_ARG_WRONG, "not a set-up PCILU over a HIPMI355X block factored matrix");
+  const HipBlockFactors *f = HipBlockGet(F);
+  if (fused) *fused = f->fused ? 1 : 0;
+  if (launches_L) *launches_L = f->fused ? f->pat.nsegL : f->pat.nlevL;
+  if (launches_U) *launches_U = f->fused ? f->pat.nsegU : f->pat.nlevU;
   return 0;
 #endif
 }

@@ -228,18 +228,24 @@ PetscErrorCode MatGetFactorAvailable_seqaijhipmi355x_petsc(Mat A, MatFactorType 
 /* ---- block ILU(k) of MATSEQBAIJHIPMI355X (host/bilu.c; harness flavour -- inside a PETSc tree the BAIJ type composes no factor): what
  * MatGetFactor(A, "petsc", MAT_FACTOR_ILU, &F) hangs on F for a block matrix.  The factor in the point factor's layout over block rows
  * and columns, one column-major bs x bs block per stored entry, the inverted diagonal block at bdiag[i].  Two forms, each released by
- * one function: the pattern side (host layout, level lists, their device copies; once per pattern) and the values (host ba, d_ba). ---- */
+ * one function: the pattern side (host layout, level lists, their device copies, the launch plans; once per pattern) and the values
+ * (host ba, d_ba). ---- */
+#define HIP_BILU_CHAIN_ROWS 128                            /* default of -pc_factor_hipmi355x_bilu_chain_rows: the best value of the measured sweep (block ILU(k)) */
 typedef struct {
   PetscInt mbs, bs, levels, nzb, nzbA;                     /* block rows, block size, levels of fill, stored blocks of the factor / of the operator */
   struct {
     PetscInt *bi, *bj, *bdiag;                             /* host layout (mi355x_iluk_symbolic_host on the block pattern) */
     PetscInt nlevL, nlevU, *levptrL, *levptrU;             /* dependency levels of L / U over block rows; where each level's rows start (host) */
     PetscInt *d_bi, *d_bj, *d_bdiag, *d_rowsL, *d_rowsU;   /* device: the layout, the block rows ordered by level */
+    PetscInt *d_levptrL, *d_levptrU;                       /* device copies of levptrL / levptrU: what a chain launch walks (trisolve fused) */
+    PetscInt nsegL, nsegU, *segL, *segU, plan_rows;        /* host: the launches of one application per triangle (mi355x_bilu_chain_plan_host): seg[0 .. nseg] where each
+                                                              segment's levels start, then seg[nlev + 1 + s] != 0: segment s is one chain launch; the max_rows they were cut for */
     int stale; unsigned long long gen;                     /* a new symbolic phase was asked for; serial number of the operator's pattern upload the layout was built for */
   } pat;
   PetscScalar *ba, *d_ba;                                  /* the factor's (nzb + 1) bs^2 values, host and device */
   PetscInt symbolic_builds, numeric_runs;                  /* pattern passes / numeric factorisations so far */
   int factored_state; void *factored_of;                   /* operator and operator state of the last numeric factorisation */
+  int fused; PetscInt chain_rows;                          /* -pc_factor_hipmi355x_trisolve fused, -pc_factor_hipmi355x_bilu_chain_rows of the last set-up */
 } HipBlockFactors;
 PetscErrorCode HipBlockFactorsDestroy(HipBlockFactors **f);
 PetscErrorCode MatGetFactor_seqbaijhipmi355x_petsc(Mat A, MatFactorType ftype, Mat *B);

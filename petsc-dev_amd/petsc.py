@@ -65,7 +65,7 @@ _SIG = {
     "PetscViewerBinaryOpen": [vp, C.c_char_p, i32, P(vp)], "PetscViewerDestroy": [P(vp)],
     "MatLoad": [vp, vp], "MatView": [vp, vp], "VecLoad": [vp, vp], "VecView": [vp, vp],
     "PCCreate": [vp, P(vp)], "PCSetOperators": [vp, vp, vp, i32], "PCSetFromOptions": [vp], "PCApply": [vp, vp, vp], "PCDestroy": [P(vp)],
-    "PCSetType": [vp, C.c_char_p], "PCILUGetLevels_HIPMI355X": [vp, P(i32), P(i32)], "PCILUGetShiftCount_HIPMI355X": [vp, P(i32)], "PCICCGetInfo_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCILUGetSolver_HIPMI355X": [vp, P(i32), P(i32)], "PCFactorDebugSetAborted_HIPMI355X": [vp], "PCILUGetSweeps_HIPMI355X": [vp, P(i32)], "PCILUGetNumeric_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCILUGetFill_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCBILUGetInfo_HIPMI355X": [vp, P(i32), P(i32), P(i32), P(i32)], "PCFactorSetLevels": [vp, i32], "PCILUApplyInPlace_HIPMI355X": [vp, vp], "PCILUGetNodeInfo_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCFactorGetMatrix": [vp, P(vp)], "MatSolve": [vp, vp, vp], "MatSolveTranspose": [vp, vp, vp], "PCApplyTranspose": [vp, vp, vp], "PCApplyTransposeExists": [vp, P(i32)], "PCILUGetTransposeBuilds_HIPMI355X": [vp, P(i32), P(i32)], "PCBJacobiGetSubKSP": [vp, P(i32), P(i32), P(vp)],
+    "PCSetType": [vp, C.c_char_p], "PCILUGetLevels_HIPMI355X": [vp, P(i32), P(i32)], "PCILUGetShiftCount_HIPMI355X": [vp, P(i32)], "PCICCGetInfo_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCILUGetSolver_HIPMI355X": [vp, P(i32), P(i32)], "PCFactorDebugSetAborted_HIPMI355X": [vp], "PCILUGetSweeps_HIPMI355X": [vp, P(i32)], "PCILUGetNumeric_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCILUGetFill_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCBILUGetInfo_HIPMI355X": [vp, P(i32), P(i32), P(i32), P(i32)], "PCBILUGetSolvePlan_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCFactorSetLevels": [vp, i32], "PCILUApplyInPlace_HIPMI355X": [vp, vp], "PCILUGetNodeInfo_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCFactorGetMatrix": [vp, P(vp)], "MatSolve": [vp, vp, vp], "MatSolveTranspose": [vp, vp, vp], "PCApplyTranspose": [vp, vp, vp], "PCApplyTransposeExists": [vp, P(i32)], "PCILUGetTransposeBuilds_HIPMI355X": [vp, P(i32), P(i32)], "PCBJacobiGetSubKSP": [vp, P(i32), P(i32), P(vp)],
     "KSPCreate": [vp, P(vp)], "KSPSetType": [vp, C.c_char_p], "KSPSetOperators": [vp, vp, vp, i32], "KSPGetPC": [vp, P(vp)],
     "KSPSetTolerances": [vp, dbl, dbl, dbl, i32], "KSPSetNormType": [vp, i32], "KSPSetPCSide": [vp, i32], "KSPSetInitialGuessNonzero": [vp, i32], "KSPSetOptionsPrefix": [vp, C.c_char_p],
     "KSPSetFromOptions": [vp], "KSPGMRESSetRestart": [vp, i32], "KSPGMRESSetCGSRefinementType": [vp, i32],
