@@ -241,6 +241,23 @@ int mi355x_vec_tfqmr_update(mi355x_handle_t h, size_t n, int nhalves, double cf0
 int mi355x_vec_bicg_dirs(mi355x_handle_t h, size_t n, int first, double b, const double *zr, const double *zl, double *pr, double *pl);
 int mi355x_vec_bicg_update(mi355x_handle_t h, size_t n, double a, int pcmode, int which, const double *pr, const double *d, double *x,
                            double *rr, double *rl, double *zr, double *zl, double *out);
+/* The two sweeps of an iteration of KSPSolve_LSQR (src/ksp/ksp/impls/lsqr/lsqr.c) around u1 = A v and v1 = A^T u1, with the bits of
+ * mi355x_vec_axpy, mi355x_vec_norm(type 2), mi355x_vec_scale, mi355x_vec_copy, mi355x_vec_pointwise_mult and mi355x_vec_aypx run one call at
+ * a time.
+ * bidiag:  y = y + (-coef) x ; out[0] = sum y*y over the updated y (for an aligned view the tree of mi355x_vec_norm(type 2): the square,
+ *          the caller roots it); out: device or the handle's pinned scratch; n == 0: { 0 }.  coef == 0: y untouched, x not loaded (may be
+ *          NULL).  coef2_dev != NULL: coef = sqrt(*coef2_dev) is formed on the device -- the sum an earlier call of this function left in
+ *          device memory, rooted as the host roots it -- and the host argument is ignored.
+ * update:  v1 = ialpha v1 (mi355x_vec_scale's cases: 1: v1 not stored; 0: zeros, v1 not loaded) ; x = x + step w (step == 0: x untouched,
+ *          may be NULL) ; se != NULL: se = se + irho2 (w .* w) (the four calls copy, square, scale, AXPY) ; w = v1 + cf w over the scaled v1
+ *          (mi355x_vec_aypx's cases 0, 1, -1).  skip_w == 1: w is not stored (LSQR's breakdown exit: x and se still take the old w; with
+ *          ialpha == 1 v1 may be NULL; with step == 0 and se == NULL as well w may be NULL and the call is a plain scaling of v1).  A pure
+ *          map: nothing reduced.
+ * hipErrorInvalidValue and nothing touched for an operand the form needs that is NULL, skip_w outside {0, 1}, or a written vector that is
+ * another operand of the same call. */
+int mi355x_vec_lsqr_bidiag(mi355x_handle_t h, size_t n, double coef, const double *coef2_dev, const double *x, double *y, double *out);
+int mi355x_vec_lsqr_update(mi355x_handle_t h, size_t n, double ialpha, double step, double cf, double irho2, int skip_w,
+                           double *v1, double *x, double *w, double *se);
 
 /* VecMDot_Seq         src/vec/vec/impls/seq/dvec2.c:146     out[j] = sum_i x_i y_j,i , j<nv ; x read once per 16 y's */
 int mi355x_vec_mdot(mi355x_handle_t h, size_t n, int nv, const double *x, const double *const *y, double *out);

@@ -38,6 +38,7 @@ extern "C" {
 #define KSPRICHARDSONHIPMI355X "richardsonhipmi355x"
 #define KSPPIPECGHIPMI355X  "pipecghipmi355x"          /* KSPPIPECG with the vector work of an iteration in one sweep ("VecPipelinedCGFusedOps_C") */
 #define KSPTFQMRHIPMI355X   "tfqmrhipmi355x"           /* KSPTFQMR with three sweeps per iteration ("VecTfqmrFusedOps_C"); on other vectors the same function runs op by op */
+#define KSPLSQRHIPMI355X    "lsqrhipmi355x"            /* KSPLSQR with the vector work of an iteration in 5 launches ("VecLsqrFusedOps_C") and, with PCNONE on one rank, one host wait; needs vectors that offer the table: PETSC_ERR_SUP at set-up otherwise */
 #define KSPBICGHIPMI355X    "bicghipmi355x"            /* KSPBICG with two sweeps per iteration ("VecBicgFusedOps_C", -ksp_bicg_fused <bool>); on other vectors the same function runs op by op */
 #define KSPCGSHIPMI355X     "cgshipmi355x"             /* KSPCGS on the same three sweeps */
 #define KSPMINRESHIPMI355X  "minreshipmi355x"          /* KSPMINRES with two sweeps per iteration; needs vectors that offer "VecMinresFusedOps_C": PETSC_ERR_SUP at set-up otherwise */

@@ -106,6 +106,27 @@ typedef struct {
                                 PetscScalar *beta, PetscScalar *nrm2, PetscBool *done);
 } VecBicgFusedOps;
 typedef const VecBicgFusedOps *(*VecBicgFusedOpsGetFn)(void);
+/* "VecLsqrFusedOps_C" on a Vec returns the two sweeps of an iteration of KSPSolve_LSQR (lsqr.c), a sixth table.  *done = PETSC_FALSE and
+ * nothing touched when a sweep refuses its operands: a vector of another type or on another device, unequal local sizes, a written
+ * vector that is another operand of the call, or a route the communicator cannot take. */
+typedef enum {
+  LSQR_BIDIAG_WAIT = 0,   /* coef from the host; sums[0] = y'y, all-reduced, comes home in one wait */
+  LSQR_BIDIAG_QUEUE = 1,  /* coef from the host; y'y stays in a device slot and y = y / sqrt(y'y) is queued behind the sweep (VecNormalize's rule:
+                             a zero norm leaves y alone); the host does not wait and sums is not written.  One rank only: the slot would hold a
+                             local partial sum */
+  LSQR_BIDIAG_FINISH = 2  /* coef = sqrt of the sum the QUEUE call before it left in the slot, formed on the device, the argument ignored;
+                             sums[0] = that sum, sums[1] = y'y: both in one wait.  One rank only, and only behind a QUEUE call */
+} VecLsqrBidiagRoute;
+typedef struct {
+  /* y -= coef x (VecAXPY(Y, -coef, X)) ; y'y, the sum VecNorm(Y, NORM_2) takes the root of, over the updated y */
+  PetscErrorCode (*lsqr_bidiag)(Vec x, Vec y, PetscScalar coef, VecLsqrBidiagRoute route, PetscScalar sums[2], PetscBool *done);
+  /* v1 = ialpha v1 (VecScale) ; x += step w (VecAXPY) ; se != NULL: se += irho2 (w .* w) (VecCopy, VecPointwiseMult, VecScale, VecAXPY) ;
+   * w = v1 + cf w (VecAYPX).  skip_w: w is not stored (the breakdown exit).  x == NULL with step == 0, and w == NULL with skip_w, step == 0
+   * and se == NULL: that vector is not looked at; the last form is a plain scaling of v1.  Nothing is reduced, the host does not wait. */
+  PetscErrorCode (*lsqr_update)(Vec v1, Vec x, Vec w, Vec se, PetscScalar ialpha, PetscScalar step, PetscScalar cf, PetscScalar irho2, PetscBool skip_w,
+                                PetscBool *done);
+} VecLsqrFusedOps;
+typedef const VecLsqrFusedOps *(*VecLsqrFusedOpsGetFn)(void);
 typedef PetscErrorCode (*MatMultTDotBeginFn)(Mat A, Vec x, Vec y, PetscBool *ok);
 typedef PetscErrorCode (*MatMultDiagonalScaleFn)(Mat A, Vec d, Vec x, Vec y, PetscBool *ok);
 

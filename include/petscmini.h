@@ -139,6 +139,7 @@ typedef const char *PCType;
 #define KSPMINRES  "minres"    /* minimum residual method for symmetric indefinite operators (src/ksp/ksp/impls/minres/minres.c) */
 #define KSPTFQMR   "tfqmr"     /* transpose-free QMR for nonsymmetric operators (src/ksp/ksp/impls/tfqmr/tfqmr.c) */
 #define KSPCGS     "cgs"       /* conjugate gradient squared (src/ksp/ksp/impls/cgs/cgs.c) */
+#define KSPLSQR    "lsqr"      /* least squares for rectangular operators: A v and A^T u per iteration (src/ksp/ksp/impls/lsqr/lsqr.c) */
 #define KSPBICG    "bicg"      /* biconjugate gradients: A^T p and B^T r per iteration (src/ksp/ksp/impls/bicg/bicg.c) */
 #define PCNONE     "none"
 #define PCJACOBI   "jacobi"
@@ -397,6 +398,21 @@ PetscErrorCode KSPMonitorDefault(KSP ksp, PetscInt n, PetscReal rnorm, void *dum
 PetscErrorCode KSPMonitorDefaultShort(KSP ksp, PetscInt n, PetscReal rnorm, void *dummy);
 PetscErrorCode KSPMonitorSet(KSP ksp, PetscErrorCode (*monitor)(KSP, PetscInt, PetscReal, void *), void *mctx, PetscErrorCode (*destroy)(void **));
 PetscErrorCode KSPDestroy(KSP *ksp);
+/* itfunc.c KSPSetConvergenceTest: converge(ksp, it, rnorm, &reason, cctx) decides at every checkpoint; destroy (may be NULL) releases cctx
+ * when the test is replaced or the KSP destroyed */
+PetscErrorCode KSPSetConvergenceTest(KSP ksp, PetscErrorCode (*converge)(KSP, PetscInt, PetscReal, KSPConvergedReason *, void *), void *cctx, PetscErrorCode (*destroy)(void *));
+PetscErrorCode KSPDefaultConverged(KSP ksp, PetscInt n, PetscReal rnorm, KSPConvergedReason *reason, void *ctx);
+/* lsqr.c.  PetscTryMethod / PetscUseMethod on "KSPLSQRSetStandardErrorVec_C", "KSPLSQRGetStandardErrorVec_C", "KSPLSQRGetArnorm_C": the LSQR
+ * types answer, any other type ignores the setter and returns NULL / zeros from the getters.
+ *   SetStandardErrorVec: se (length: the columns of A) takes the running sum of (w .* w) / rho^2; the KSP takes over the caller's reference.
+ *                        -ksp_lsqr_set_standard_error has KSPSetUp create the vector.
+ *   GetArnorm:           the estimates ||A^T r||, ||b|| (of the start residual) and ||A||_F of the last solve; any pointer may be NULL.
+ *   KSPLSQRDefaultConverged: KSPDefaultConverged, then arnorm <= abstol -> KSP_CONVERGED_ATOL_NORMAL and arnorm <= rtol * anorm * rnorm ->
+ *                        KSP_CONVERGED_RTOL_NORMAL; installed with KSPSetConvergenceTest */
+PetscErrorCode KSPLSQRSetStandardErrorVec(KSP ksp, Vec se);
+PetscErrorCode KSPLSQRGetStandardErrorVec(KSP ksp, Vec *se);
+PetscErrorCode KSPLSQRGetArnorm(KSP ksp, PetscReal *arnorm, PetscReal *rhs_norm, PetscReal *anorm);
+PetscErrorCode KSPLSQRDefaultConverged(KSP ksp, PetscInt n, PetscReal rnorm, KSPConvergedReason *reason, void *ctx);
 
 #ifdef __cplusplus
 }

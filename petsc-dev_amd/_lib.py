@@ -84,6 +84,8 @@ KERNEL_API = {
     "mi355x_vec_tfqmr_update": [vp, sz, i32, dbl, dbl, dbl, dbl, i32, dbl, vp, vp, vp, vp, vp, vp],
     "mi355x_vec_bicg_dirs": [vp, sz, i32, dbl, vp, vp, vp, vp],
     "mi355x_vec_bicg_update": [vp, sz, dbl, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "mi355x_vec_lsqr_bidiag": [vp, sz, dbl, vp, vp, vp, vp],
+    "mi355x_vec_lsqr_update": [vp, sz, dbl, dbl, dbl, dbl, i32, vp, vp, vp, vp],
     "mi355x_handle_publish": [vp, vp, i32],
     "mi355x_handle_publish_at": [vp, vp, i32, i32],
     "mi355x_vec_cg_update_dev": [vp, sz, dbl, vp, dbl, i32, vp, vp, vp, vp, vp, vp, vp, i32],

@@ -1422,6 +1422,101 @@ struct BicgUpdateF {
   }
 };
 
+// ---- the two sweeps of an LSQR iteration (the Golub-Kahan bidiagonalisation of KSPSolve_LSQR, src/ksp/ksp/impls/lsqr/lsqr.c) around the
+// products u1 = A v and v1 = A^T u1.
+// LsqrBidiagF, under launch_reduce:
+//   y = y + (-coef) x                                    (VecAXPY(Y, -coef, X): OpAxpy; coef == 0: y not stored, x not loaded)
+//   out = sum y*y                                        (VecNorm(Y, NORM_2)'s sum over the updated y; a lane meets its elements in SumSqF's order)
+// coef comes from the host or, coef2_dev != NULL, is sqrt(*coef2_dev) formed on the device: the sum the same sweep left in a device slot
+// one product earlier, rooted as the host roots it (IEEE sqrt is correctly rounded on both sides).
+// Streaming (see nt_load2), a choice by analogy with TfqmrResidF, not a measurement: x (the previous u or v) has its last
+// reader of the iteration here -- the next product overwrites its buffer -- and is non-temporal at every size; y (just written by the
+// product, read again by the scaling or the update sweep and gathered by the next product) stays cacheable below 256 MiB.
+struct LsqrBidiagF {
+  double coef;
+  const double *coef2_dev, *x;
+  double *y;
+  int big;
+  __device__ __forceinline__ double ma() const { return -(coef2_dev ? sqrt(*coef2_dev) : coef); }   // the scalar VecAXPY is called with
+  template <int NOUT_>
+  __device__ __forceinline__ void sweep(size_t tid, size_t stride, size_t n2, double (&acc)[NOUT_]) const {
+    const double a = ma();
+    for (size_t i = tid; i < n2; i += stride) {
+      double2 yv, xv;
+      ldq_tile1(y, i, big, yv);
+      if (a != 0.0) {
+        ldq_tile1(x, i, 1, xv);
+        yv.x = OpAxpy{a}(xv.x, yv.x, 0.0); yv.y = OpAxpy{a}(xv.y, yv.y, 0.0);
+        stq(reinterpret_cast<double2 *>(y) + i, yv, big);
+      }
+      acc[0] += yv.x * yv.x;
+      acc[0] += yv.y * yv.y;
+    }
+  }
+  __device__ __forceinline__ void accum1(size_t k, double (&acc)[1]) const {
+    const double a = ma();
+    double yv = y[k];
+    if (a != 0.0) { yv = OpAxpy{a}(x[k], yv, 0.0); y[k] = yv; }
+    acc[0] += yv * yv;
+  }
+};
+
+// LsqrUpdateF, a pure map (nothing reduced, no host wait):
+//   v1 = ialpha v1                                       (VecScale; 1: v1 not stored, 0: zeros and v1 not loaded)
+//   x = x + step w                                       (VecAXPY; step == 0: x neither read nor written)
+//   se = se + irho2 (w .* w)                             (se != NULL: VecCopy, VecPointwiseMult, VecScale, VecAXPY(1.0) through a scratch vector)
+//   w = v1 + cf w                                        (VecAYPX with mi355x_vec_aypx's cases, over the SCALED v1 held in registers;
+//                                                         skip_w: w not stored -- the breakdown exit, where x and se still take the old w)
+// An operand no line of the form needs is not loaded.
+// Streaming, by the same analogy: x and se are touched here only: non-temporal at every size; v1 (just written by the bidiagonalisation
+// sweep, gathered by the next product) and w (read again by the next update) stay cacheable below 256 MiB.
+struct LsqrUpdateF {
+  double ialpha, step, cf, irho2;
+  double *v1, *x, *w, *se;
+  int skip_w, big;
+  __device__ __forceinline__ bool reads_v1() const { return ialpha != 0.0 && (ialpha != 1.0 || !skip_w); }
+  __device__ __forceinline__ bool writes_v1() const { return ialpha != 1.0; }
+  __device__ __forceinline__ bool steps() const { return step != 0.0; }
+  __device__ __forceinline__ bool reads_w() const { return steps() || se != nullptr || (!skip_w && cf != 0.0); }
+  __device__ __forceinline__ void one(double &vv, double &xv, double &wv, double &sv) const {
+    vv = scale_elem(ialpha, vv);
+    if (steps()) xv = OpAxpy{step}(wv, xv, 0.0);
+    if (se) sv = OpAxpy{1.0}(scale_elem(irho2, OpMul{}(wv, wv, 0.0)), sv, 0.0);
+    if (!skip_w) wv = aypx_elem(cf == 0.0, cf, vv, wv);
+  }
+  // the U double2's of a lane in its tile; every load is issued before the first store
+  template <int U>
+  __device__ __forceinline__ void tile(size_t i) const {
+    double2 vv[U] = {}, xv[U] = {}, wv[U] = {}, sv[U] = {};
+    if (reads_v1()) ldq_tile(v1, i, big, vv);
+    if (steps()) ldq_tile(x, i, 1, xv);
+    if (reads_w()) ldq_tile(w, i, big, wv);
+    if (se) ldq_tile(se, i, 1, sv);
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      one(vv[j].x, xv[j].x, wv[j].x, sv[j].x);
+      one(vv[j].y, xv[j].y, wv[j].y, sv[j].y);
+    }
+    if (writes_v1()) stq_tile(v1, i, big, vv);
+    if (steps()) stq_tile(x, i, 1, xv);
+    if (se) stq_tile(se, i, 1, sv);
+    if (!skip_w) stq_tile(w, i, big, wv);
+  }
+  __device__ __forceinline__ void at1(size_t k) const {
+    double vv = reads_v1() ? v1[k] : 0.0, xv = steps() ? x[k] : 0.0, wv = reads_w() ? w[k] : 0.0, sv = se ? se[k] : 0.0;
+    one(vv, xv, wv, sv);
+    if (writes_v1()) v1[k] = vv;
+    if (steps()) x[k] = xv;
+    if (se) se[k] = sv;
+    if (!skip_w) w[k] = wv;
+  }
+};
+__global__ __launch_bounds__(MI355X_BLOCK) void lsqr_update_kernel(LsqrUpdateF f, size_t n, int vec_ok) {
+  tile_walk<2>(n, vec_ok,
+    [&](size_t i, auto u) { f.template tile<decltype(u)::value>(i); },
+    [&](size_t k) { f.at1(k); });
+}
+
 template <int NV>
 struct MDotF {
   const double *x;
@@ -1783,6 +1878,28 @@ int mi355x_vec_bicg_update(mi355x_handle_t h, size_t n, double a, int pcmode, in
   const BicgUpdateF f{a, pr, d, x, rr, rl, zr, zl, pcmode, which, vec_streams(n)};
   if (a == 0.0) { x = nullptr; pr = nullptr; if (!pcmode) { zr = nullptr; zl = nullptr; } }   // alignment of what is neither loaded nor stored does not count
   return launch_reduce<2, RED_SUM>(h, f, n, all_aligned16(pr, d, x, rr, rl, zr, zl), out);   // n == 0: zeros
+}
+
+int mi355x_vec_lsqr_bidiag(mi355x_handle_t h, size_t n, double coef, const double *coef2_dev, const double *x, double *y, double *out) {
+  const bool needs_x = coef2_dev != nullptr || coef != 0.0;
+  if (!y || !out || (needs_x && !x) || x == y) return (int)hipErrorInvalidValue;
+  if (!needs_x) x = nullptr;                                                                  // not loaded: its alignment does not count
+  const LsqrBidiagF f{coef, coef2_dev, x, y, vec_streams(n)};
+  return launch_reduce<1, RED_SUM>(h, f, n, all_aligned16(x, y), out);                        // n == 0: { 0 }
+}
+int mi355x_vec_lsqr_update(mi355x_handle_t h, size_t n, double ialpha, double step, double cf, double irho2, int skip_w,
+                           double *v1, double *x, double *w, double *se) {
+  if (skip_w != 0 && skip_w != 1) return (int)hipErrorInvalidValue;
+  const bool needs_v1 = !skip_w || ialpha != 1.0, needs_x = step != 0.0, needs_w = !skip_w || needs_x || se != nullptr;
+  if ((needs_v1 && !v1) || (needs_x && !x) || (needs_w && !w)) return (int)hipErrorInvalidValue;
+  if (!needs_v1) v1 = nullptr;                                                                // neither loaded nor stored: alignment and aliasing do not count
+  if (!needs_x) x = nullptr;
+  if (!needs_w) w = nullptr;
+  const double *const vecs[] = {v1, x, w, se};
+  if (written_is_operand(vecs, 4, vecs, 4)) return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  const LsqrUpdateF f{ialpha, step, cf, irho2, v1, x, w, se, skip_w, vec_streams(n)};
+  return launch_tiles(h, n, all_aligned16(v1, x, w, se), lsqr_update_kernel, lsqr_update_kernel, f);
 }
 
 // borthog2.c:63-64 + the norm of gmres.c:146: x += sum_j sign * coef_dev[j] * y_j, *out = sum x_new^2 (out: device or the

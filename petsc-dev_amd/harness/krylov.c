@@ -17,6 +17,7 @@
  *   TFQMR         src/ksp/ksp/impls/tfqmr/tfqmr.c (KSPSolve_TFQMR)
  *   CGS           src/ksp/ksp/impls/cgs/cgs.c (KSPSolve_CGS)
  *   BiCG          src/ksp/ksp/impls/bicg/bicg.c (KSPSolve_BiCG)
+ *   LSQR          src/ksp/ksp/impls/lsqr/lsqr.c (KSPSolve_LSQR; the contract is the sequence stated in DESIGN.md section 4)
  * and are written here over a few shared pieces: one checkpoint routine (history, monitor, convergence test), one start-residual
  * routine for the CG family, index-addressed Hessenberg columns for GMRES. */
 #include "petscimpl.h"
@@ -1091,5 +1092,169 @@ PetscErrorCode KSPCreate_BICG(KSP ksp) {   /* bicg.c KSPCreate_BiCG */
   ksp->normsupporttable[KSP_NORM_UNPRECONDITIONED][PC_LEFT] = 1;
   ksp->ops->setup = KSPSetUp_BICG;
   ksp->ops->solve = KSPSolve_BICG;
+  return 0;
+}
+
+/* ================================================================== LSQR (lsqr.c KSPSolve_LSQR), rectangular operators
+ * Paige and Saunders' least-squares method: the Golub-Kahan bidiagonalisation of the m x n operator A started from the residual of the
+ * guess -- U, U1 in the row space (length m), V, V1 in the column space (length n) -- one Givens rotation per step, the search direction
+ * W and the update of x.  min ||b - A x||; for a wide consistent system the minimum-norm solution.  The work vectors come from
+ * MatGetVecs(A), never from vec_sol.  A preconditioner acts on the normal equations (its matrix is n x n): Z = B V, alpha = sqrt(V'Z), and
+ * Z takes V's place in the product and in W.  The norm is the recurrence's estimate phibar of ||b - A x||; arnorm = alpha |s phi|
+ * estimates ||A^T r|| and anorm the Frobenius norm of A (KSPLSQRGetArnorm, KSPLSQRDefaultConverged).  With KSPLSQRSetStandardErrorVec the
+ * running sum of (W .* W) / rho^2 is kept.  A null space and a side other than left are refused at set-up.
+ * Deviations from the reference: beta == 0 or alpha == 0 in the loop finishes the step -- x takes the update that
+ * makes it exact -- and ends with KSP_CONVERGED_HAPPY_BREAKDOWN where the reference leaves with KSP_DIVERGED_BREAKDOWN before the update;
+ * alpha == 0 at the start is KSP_CONVERGED_ATOL_NORMAL; the standard-error vector is left as the running sum. */
+typedef struct { Vec se; PetscBool se_flg; PetscReal arnorm, anorm, rhs_norm; Vec U, U1, V, V1, W, Z, Z1, W2; } LsqrData;
+#define LSQRD(ksp) ((LsqrData *)(ksp)->data)
+
+static PetscBool lsqr_no_pc(KSP ksp) { return (PetscBool)(!strcmp(ksp->pc->type_name, PCNONE)); }
+/* the vectors this configuration needs and does not have yet; set-up and solve both ask */
+static PetscErrorCode lsqr_get_work(KSP ksp) {
+  LsqrData *ld = LSQRD(ksp);
+  const PetscBool nopc = lsqr_no_pc(ksp);
+  Vec right = NULL, left = NULL;
+  Vec *m_side[] = {&ld->U, &ld->U1}, *n_side[] = {&ld->V, &ld->V1, &ld->W, &ld->Z, &ld->Z1, &ld->W2, &ld->se};
+  const PetscBool n_needed[] = {PETSC_TRUE, PETSC_TRUE, PETSC_TRUE, (PetscBool)!nopc, (PetscBool)!nopc, (PetscBool)(ld->se || ld->se_flg), ld->se_flg};
+  OK(MatGetVecs(ksp->pc->mat, &right, &left));
+  for (int k = 0; k < 2; k++) if (!*m_side[k]) OK(VecDuplicate(left, m_side[k]));
+  for (int k = 0; k < 7; k++) if (n_needed[k] && !*n_side[k]) OK(VecDuplicate(right, n_side[k]));
+  OK(VecDestroy(&right));
+  return VecDestroy(&left);
+}
+static PetscErrorCode lsqr_check(KSP ksp) {
+  if (ksp->nullsp) SETERRQ(ksp->comm, PETSC_ERR_SUP, "KSPLSQR with a null space: there is no removal behind the transposed product");
+  if (ksp->pc_side == PC_RIGHT || ksp->pc_side == PC_SYMMETRIC) SETERRQ(ksp->comm, PETSC_ERR_SUP, "KSPLSQR: left preconditioning (of the normal equations) only");
+  if (!lsqr_no_pc(ksp)) {
+    Mat A = ksp->pc->mat, Pm = ksp->pc->pmat;
+    if (Pm->rmap->N != A->cmap->N || Pm->cmap->N != A->cmap->N) SETERRQ(ksp->comm, PETSC_ERR_ARG_SIZ, "KSPLSQR preconditions the normal equations: the preconditioner matrix must be %d x %d, it is %d x %d", A->cmap->N, A->cmap->N, Pm->rmap->N, Pm->cmap->N);
+  }
+  return 0;
+}
+static PetscErrorCode KSPSetUp_LSQR(KSP ksp) {
+  OK(lsqr_check(ksp));
+  return lsqr_get_work(ksp);
+}
+static PetscErrorCode KSPSetFromOptions_LSQR(KSP ksp) {   /* lsqr.c: -ksp_lsqr_set_standard_error */
+  char text[16]; PetscBool given;
+  OK(PetscOptionsGetString(ksp->prefix, "-ksp_lsqr_set_standard_error", text, sizeof(text), &given));
+  if (given) LSQRD(ksp)->se_flg = option_is_on(text);
+  return 0;
+}
+static PetscErrorCode KSPLSQRSetStandardErrorVec_LSQR(KSP ksp, Vec se) {
+  LsqrData *ld = LSQRD(ksp);
+  if (se == ld->se) return 0;
+  OK(VecDestroy(&ld->se));
+  ld->se = se;
+  return 0;
+}
+static PetscErrorCode KSPLSQRGetStandardErrorVec_LSQR(KSP ksp, Vec *se) { *se = LSQRD(ksp)->se; return 0; }
+static PetscErrorCode KSPLSQRGetArnorm_LSQR(KSP ksp, PetscReal *arnorm, PetscReal *rhs_norm, PetscReal *anorm) {
+  *arnorm = LSQRD(ksp)->arnorm; *rhs_norm = LSQRD(ksp)->rhs_norm; *anorm = LSQRD(ksp)->anorm;
+  return 0;
+}
+static PetscErrorCode KSPDestroy_LSQR(KSP ksp) {
+  LsqrData *ld = LSQRD(ksp);
+  if (!ld) return 0;
+  Vec *all[] = {&ld->U, &ld->U1, &ld->V, &ld->V1, &ld->W, &ld->Z, &ld->Z1, &ld->W2, &ld->se};
+  for (int k = 0; k < 9; k++) OK(VecDestroy(all[k]));
+  free(ld); ksp->data = NULL;
+  OK(PetscObjectComposeFunction((PetscObject)ksp, "KSPLSQRSetStandardErrorVec_C", "", (PetscVoidFunction)NULL));
+  OK(PetscObjectComposeFunction((PetscObject)ksp, "KSPLSQRGetStandardErrorVec_C", "", (PetscVoidFunction)NULL));
+  OK(PetscObjectComposeFunction((PetscObject)ksp, "KSPLSQRGetArnorm_C", "", (PetscVoidFunction)NULL));
+  OK(PetscObjectComposeFunction((PetscObject)ksp, "KSPDefaultPCNone_C", "", (PetscVoidFunction)NULL));
+  return 0;
+}
+
+static PetscErrorCode KSPSolve_LSQR(KSP ksp) {
+  LsqrData *ld = LSQRD(ksp);
+  Vec X = ksp->vec_sol, B = ksp->vec_rhs, U, U1, V, V1, W, Z, Z1, SE, W2, t;
+  Mat A = ksp->pc->mat;
+  const PetscBool nopc = lsqr_no_pc(ksp);
+  PetscScalar alpha, beta, rho, rhobar, phi, phibar, theta, c, s, dot;
+  PetscReal anorm2;
+  PetscInt i;
+
+  OK(lsqr_check(ksp));
+  OK(lsqr_get_work(ksp));
+  U = ld->U; U1 = ld->U1; V = ld->V; V1 = ld->V1; W = ld->W; Z = ld->Z; Z1 = ld->Z1; SE = ld->se; W2 = ld->W2;
+  ksp->its = 0;
+  OK(cg_family_start(ksp, A, X, B, U));                               /* U <- B - A X: the method iterates on the correction */
+  OK(VecNorm(U, NORM_2, &beta));
+  ld->rhs_norm = beta; ld->arnorm = 0.0; ld->anorm = 0.0;
+  OK(checkpoint(ksp, 0, beta));
+  if (ksp->reason) return 0;
+  if (beta != 0.0) OK(VecScale(U, 1.0 / beta));
+  OK(KSP_MatMultTranspose(ksp, A, U, V));
+  if (nopc) OK(VecNorm(V, NORM_2, &alpha));
+  else {
+    OK(KSP_PCApply(ksp, V, Z));
+    OK(VecDot(V, Z, &dot));
+    alpha = PetscSqrtReal(dot);
+    if (alpha != 0.0) OK(VecScale(Z, 1.0 / alpha));
+  }
+  if (alpha == 0.0) { ksp->reason = KSP_CONVERGED_ATOL_NORMAL; return 0; }   /* A^T r0 = 0: x already is a least-squares solution */
+  OK(VecScale(V, 1.0 / alpha));
+  OK(VecCopy(nopc ? V : Z, W));
+  if (SE) OK(VecSet(SE, 0.0));
+  phibar = beta; rhobar = alpha; anorm2 = alpha * alpha;
+  ld->arnorm = alpha * beta; ld->anorm = PetscSqrtReal(anorm2);
+
+  for (i = 0; i < ksp->max_it; i++) {
+    PetscBool broke;
+    OK(KSP_MatMult(ksp, A, nopc ? V : Z, U1));
+    OK(VecAXPY(U1, -alpha, U));
+    OK(VecNorm(U1, NORM_2, &beta));
+    if (beta != 0.0) OK(VecScale(U1, 1.0 / beta));
+    OK(KSP_MatMultTranspose(ksp, A, U1, V1));
+    OK(VecAXPY(V1, -beta, V));
+    if (nopc) OK(VecNorm(V1, NORM_2, &alpha));
+    else {
+      OK(KSP_PCApply(ksp, V1, Z1));
+      OK(VecDot(V1, Z1, &dot));
+      alpha = PetscSqrtReal(dot);
+      if (alpha != 0.0) OK(VecScale(Z1, 1.0 / alpha));
+    }
+    if (alpha != 0.0) OK(VecScale(V1, 1.0 / alpha));
+    broke = (PetscBool)(beta == 0.0 || alpha == 0.0);
+    rho = PetscSqrtReal(rhobar * rhobar + beta * beta);
+    c = rhobar / rho; s = beta / rho;
+    theta = s * alpha; rhobar = -c * alpha;
+    phi = c * phibar; phibar = s * phibar;
+    OK(VecAXPY(X, phi / rho, W));
+    if (SE) {
+      OK(VecCopy(W, W2));
+      OK(VecPointwiseMult(W2, W2, W2));
+      OK(VecScale(W2, 1.0 / (rho * rho)));
+      OK(VecAXPY(SE, 1.0, W2));
+    }
+    if (!broke) OK(VecAYPX(W, -theta / rho, nopc ? V1 : Z1));
+    ld->arnorm = alpha * PetscAbsScalar(s * phi);
+    anorm2 += alpha * alpha + beta * beta;
+    ld->anorm = PetscSqrtReal(anorm2);
+    ksp->its = i + 1;
+    OK(checkpoint(ksp, i + 1, phibar));
+    if (broke && !ksp->reason) ksp->reason = KSP_CONVERGED_HAPPY_BREAKDOWN;
+    if (ksp->reason) break;
+    t = U; U = U1; U1 = t; t = V; V = V1; V1 = t; t = Z; Z = Z1; Z1 = t;
+  }
+  if (i >= ksp->max_it && !ksp->reason) ksp->reason = KSP_DIVERGED_ITS;
+  return 0;
+}
+static PetscErrorCode KSPDefaultPCNone_LSQR(KSP ksp) { (void)ksp; return 0; }   /* its presence is the message: see KSPSetUp */
+PetscErrorCode KSPCreate_LSQR(KSP ksp) {   /* lsqr.c KSPCreate_LSQR */
+  LsqrData *ld = (LsqrData *)calloc(1, sizeof(*ld));
+  if (!ld) SETERRQ(ksp->comm, PETSC_ERR_MEM, "out of memory");
+  ksp->data = ld;
+  ksp->normsupporttable[KSP_NORM_UNPRECONDITIONED][PC_LEFT] = 2;
+  ksp->ops->setup = KSPSetUp_LSQR;
+  ksp->ops->solve = KSPSolve_LSQR;
+  ksp->ops->setfromoptions = KSPSetFromOptions_LSQR;
+  ksp->ops->destroy = KSPDestroy_LSQR;
+  OK(PetscObjectComposeFunction((PetscObject)ksp, "KSPLSQRSetStandardErrorVec_C", "KSPLSQRSetStandardErrorVec_LSQR", (PetscVoidFunction)KSPLSQRSetStandardErrorVec_LSQR));
+  OK(PetscObjectComposeFunction((PetscObject)ksp, "KSPLSQRGetStandardErrorVec_C", "KSPLSQRGetStandardErrorVec_LSQR", (PetscVoidFunction)KSPLSQRGetStandardErrorVec_LSQR));
+  OK(PetscObjectComposeFunction((PetscObject)ksp, "KSPLSQRGetArnorm_C", "KSPLSQRGetArnorm_LSQR", (PetscVoidFunction)KSPLSQRGetArnorm_LSQR));
+  OK(PetscObjectComposeFunction((PetscObject)ksp, "KSPDefaultPCNone_C", "KSPDefaultPCNone_LSQR", (PetscVoidFunction)KSPDefaultPCNone_LSQR));
   return 0;
 }

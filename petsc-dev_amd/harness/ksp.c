@@ -231,6 +231,13 @@ PetscErrorCode KSPSetUp(KSP ksp) {   /* itfunc.c:175 */
   if (!ksp->type_name[0]) { ierr = KSPSetType(ksp, KSPGMRES);CHKERRQ(ierr); }
   if (ksp->setupcalled == 2) return 0;
   if (!ksp->pc || !ksp->pc->mat) SETERRQ(ksp->comm, PETSC_ERR_ARG_WRONGSTATE, "Matrix must be set first");
+  /* A KSP type for rectangular operators composes "KSPDefaultPCNone_C" on its KSP: PCGetDefaultType_Private's choice (ILU, Jacobi) cannot
+   * be built from such an operator, so a PC nobody gave a type becomes PCNONE, before the type's set-up looks at it */
+  if (!ksp->pc->type_name[0]) {
+    PetscVoidFunction none = NULL;
+    ierr = PetscObjectQueryFunction((PetscObject)ksp, "KSPDefaultPCNone_C", &none);CHKERRQ(ierr);
+    if (none) { ierr = PCSetType(ksp->pc, PCNONE);CHKERRQ(ierr); }
+  }
   if (!ksp->setupcalled) { ierr = (*ksp->ops->setup)(ksp);CHKERRQ(ierr); }
   ierr = ksp_setup_norms(ksp);CHKERRQ(ierr);   /* itfunc.c:225 */
   if (ksp->normtype == KSP_NORM_NONE) ksp->converged = KSPSkipConverged;
@@ -252,6 +259,11 @@ PetscErrorCode KSPSolve(KSP ksp, Vec b, Vec x) {   /* itfunc.c:335 */
   KSPValid(ksp);
   if (b == x) SETERRQ(ksp->comm, PETSC_ERR_SUP, "in-place solve (b == x) is outside the ported path");
   ksp->vec_rhs = b; ksp->vec_sol = x;
+  if (ksp->pc && ksp->pc->mat && ksp->pc->mat->rmap && ksp->pc->mat->cmap) {   /* b lives in the row space of A, x in its column space */
+    Mat A = ksp->pc->mat;
+    if (b->map->N != A->rmap->N || b->map->n != A->rmap->n) SETERRQ(ksp->comm, PETSC_ERR_ARG_SIZ, "Mat A,Vec b: rows %d (local %d), vector %d (local %d)", A->rmap->N, A->rmap->n, b->map->N, b->map->n);
+    if (x->map->N != A->cmap->N || x->map->n != A->cmap->n) SETERRQ(ksp->comm, PETSC_ERR_ARG_SIZ, "Mat A,Vec x: columns %d (local %d), vector %d (local %d)", A->cmap->N, A->cmap->n, x->map->N, x->map->n);
+  }
   ierr = KSPSetUp(ksp);CHKERRQ(ierr);
   ierr = KSPSetUpOnBlocks(ksp);CHKERRQ(ierr);                          /* itfunc.c:377 */
   if (ksp->guess_zero) { ierr = VecSet(ksp->vec_sol, 0.0);CHKERRQ(ierr); }
@@ -330,6 +342,7 @@ PetscErrorCode KSPDestroy(KSP *pksp) {
   if (!ksp) return 0;
   if (ksp->ops->destroy) { ierr = (*ksp->ops->destroy)(ksp);CHKERRQ(ierr); }
   if (ksp->work) { ierr = VecDestroyVecs(ksp->nwork, &ksp->work);CHKERRQ(ierr); }
+  if (ksp->convergeddestroy) { ierr = (*ksp->convergeddestroy)(ksp->cnvP);CHKERRQ(ierr); }
   ierr = PCDestroy(&ksp->pc);CHKERRQ(ierr);
   ierr = MatNullSpaceDestroy(&ksp->nullsp);CHKERRQ(ierr);
   ierr = PetscObjectListDestroy_Private((PetscObject)ksp);CHKERRQ(ierr);
@@ -412,6 +425,53 @@ PetscErrorCode KSPDefaultConverged(KSP ksp, PetscInt n, PetscReal rnorm, KSPConv
   if (PetscIsInfOrNanScalar(rnorm)) *reason = KSP_DIVERGED_NAN;
   else if (rnorm <= ksp->ttol) *reason = (rnorm < ksp->abstol) ? KSP_CONVERGED_ATOL : KSP_CONVERGED_RTOL;
   else if (rnorm >= ksp->divtol * ksp->rnorm0) *reason = KSP_DIVERGED_DTOL;
+  return 0;
+}
+
+/* KSPSetConvergenceTest, itfunc.c: the old context is released through the old destroy routine */
+PetscErrorCode KSPSetConvergenceTest(KSP ksp, PetscErrorCode (*converge)(KSP, PetscInt, PetscReal, KSPConvergedReason *, void *), void *cctx, PetscErrorCode (*destroy)(void *)) {
+  KSPValid(ksp);
+  if (!converge) SETERRQ(ksp->comm, PETSC_ERR_ARG_NULL, "Null convergence test");
+  if (ksp->convergeddestroy) { PetscErrorCode ierr = (*ksp->convergeddestroy)(ksp->cnvP);CHKERRQ(ierr); }
+  ksp->converged = converge; ksp->cnvP = cctx; ksp->convergeddestroy = destroy;
+  return 0;
+}
+
+/* The public face of the LSQR types (lsqr.c): composed methods, so that the harness's lsqr and the plug-in's lsqrhipmi355x both answer */
+PetscErrorCode KSPLSQRSetStandardErrorVec(KSP ksp, Vec se) {
+  PetscVoidFunction f = NULL;
+  KSPValid(ksp);
+  PetscErrorCode ierr = PetscObjectQueryFunction((PetscObject)ksp, "KSPLSQRSetStandardErrorVec_C", &f);CHKERRQ(ierr);
+  if (f) { ierr = ((PetscErrorCode (*)(KSP, Vec))f)(ksp, se);CHKERRQ(ierr); }
+  return 0;
+}
+PetscErrorCode KSPLSQRGetStandardErrorVec(KSP ksp, Vec *se) {
+  PetscVoidFunction f = NULL;
+  KSPValid(ksp);
+  *se = NULL;
+  PetscErrorCode ierr = PetscObjectQueryFunction((PetscObject)ksp, "KSPLSQRGetStandardErrorVec_C", &f);CHKERRQ(ierr);
+  if (f) { ierr = ((PetscErrorCode (*)(KSP, Vec *))f)(ksp, se);CHKERRQ(ierr); }
+  return 0;
+}
+PetscErrorCode KSPLSQRGetArnorm(KSP ksp, PetscReal *arnorm, PetscReal *rhs_norm, PetscReal *anorm) {
+  PetscVoidFunction f = NULL;
+  PetscReal v[3] = {0.0, 0.0, 0.0};
+  KSPValid(ksp);
+  PetscErrorCode ierr = PetscObjectQueryFunction((PetscObject)ksp, "KSPLSQRGetArnorm_C", &f);CHKERRQ(ierr);
+  if (f) { ierr = ((PetscErrorCode (*)(KSP, PetscReal *, PetscReal *, PetscReal *))f)(ksp, &v[0], &v[1], &v[2]);CHKERRQ(ierr); }
+  if (arnorm) *arnorm = v[0];
+  if (rhs_norm) *rhs_norm = v[1];
+  if (anorm) *anorm = v[2];
+  return 0;
+}
+/* KSPLSQRDefaultConverged, lsqr.c: the default test first, then the two tests on the normal equations' residual */
+PetscErrorCode KSPLSQRDefaultConverged(KSP ksp, PetscInt n, PetscReal rnorm, KSPConvergedReason *reason, void *ctx) {
+  PetscReal arnorm, anorm;
+  PetscErrorCode ierr = KSPDefaultConverged(ksp, n, rnorm, reason, ctx);CHKERRQ(ierr);
+  if (!n || *reason) return 0;
+  ierr = KSPLSQRGetArnorm(ksp, &arnorm, NULL, &anorm);CHKERRQ(ierr);
+  if (arnorm <= ksp->abstol) *reason = KSP_CONVERGED_ATOL_NORMAL;
+  else if (arnorm <= ksp->rtol * anorm * rnorm) *reason = KSP_CONVERGED_RTOL_NORMAL;
   return 0;
 }
 

@@ -53,6 +53,7 @@ PetscErrorCode PetscMiniInitialize(void) {
   ierr = KSPRegister(KSPTFQMR, 0, "KSPCreate_TFQMR", KSPCreate_TFQMR);CHKERRQ(ierr);
   ierr = KSPRegister(KSPCGS, 0, "KSPCreate_CGS", KSPCreate_CGS);CHKERRQ(ierr);
   ierr = KSPRegister(KSPBICG, 0, "KSPCreate_BICG", KSPCreate_BICG);CHKERRQ(ierr);
+  ierr = KSPRegister(KSPLSQR, 0, "KSPCreate_LSQR", KSPCreate_LSQR);CHKERRQ(ierr);
   return 0;
 }
 

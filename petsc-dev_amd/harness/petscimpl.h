@@ -221,6 +221,7 @@ struct _p_KSP {
   PetscInt normsupporttable[KSP_NORM_MAX][PC_SIDE_MAX];   /* KSPSetSupportedNorm (kspimpl.h:52, itcreate.c:309-372) */
   PetscErrorCode (*converged)(KSP, PetscInt, PetscReal, KSPConvergedReason *, void *);   /* kspimpl.h:87 */
   void *cnvP;
+  PetscErrorCode (*convergeddestroy)(void *);   /* KSPSetConvergenceTest's third argument: releases cnvP */
   KSPConvergedReason reason;
   int setupcalled;
   PetscReal *res_hist; PetscInt res_hist_len, res_hist_max; PetscBool res_hist_reset; PetscReal *res_hist_alloc;
@@ -241,7 +242,7 @@ PetscErrorCode KSP_PCApply(KSP ksp, Vec x, Vec y);
 PetscErrorCode KSP_MatMultTranspose(KSP ksp, Mat A, Vec x, Vec y);
 PetscErrorCode KSP_PCApplyTranspose(KSP ksp, Vec x, Vec y);
 PetscErrorCode KSP_PCApplyBAorAB(KSP ksp, Vec x, Vec y, Vec w);
-PetscErrorCode KSPCreate_CG(KSP), KSPCreate_GROPPCG(KSP), KSPCreate_PIPECG(KSP), KSPCreate_GMRES(KSP), KSPCreate_BCGS(KSP), KSPCreate_PREONLY(KSP), KSPCreate_Chebychev(KSP), KSPCreate_Richardson(KSP), KSPCreate_MINRES(KSP), KSPCreate_TFQMR(KSP), KSPCreate_CGS(KSP), KSPCreate_BICG(KSP);
+PetscErrorCode KSPCreate_CG(KSP), KSPCreate_GROPPCG(KSP), KSPCreate_PIPECG(KSP), KSPCreate_GMRES(KSP), KSPCreate_BCGS(KSP), KSPCreate_PREONLY(KSP), KSPCreate_Chebychev(KSP), KSPCreate_Richardson(KSP), KSPCreate_MINRES(KSP), KSPCreate_TFQMR(KSP), KSPCreate_CGS(KSP), KSPCreate_BICG(KSP), KSPCreate_LSQR(KSP);
 PetscErrorCode PCCreate_None(PC), PCCreate_Jacobi(PC), PCCreate_BJacobi(PC), PCCreate_ILU(PC), PCCreate_ICC(PC), PCCreate_SOR(PC);
 
 #include "petsckrylovfused.h"   /* the optional fused-kernel tables a Vec / Mat type may compose */

@@ -406,5 +406,6 @@ PetscErrorCode KSPCreate_MINRESHIPMI355X(KSP);
 PetscErrorCode KSPCreate_TFQMRHIPMI355X(KSP);
 PetscErrorCode KSPCreate_CGSHIPMI355X(KSP);
 PetscErrorCode KSPCreate_BICGHIPMI355X(KSP);
+PetscErrorCode KSPCreate_LSQRHIPMI355X(KSP);
 
 #endif

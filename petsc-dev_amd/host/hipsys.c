@@ -65,6 +65,7 @@ PetscErrorCode PetscHIPMI355XRegisterAll(void) {
   ierr = KSPRegister(KSPMINRESHIPMI355X, 0, "KSPCreate_MINRESHIPMI355X", KSPCreate_MINRESHIPMI355X);CHKERRQ(ierr);
   ierr = KSPRegister(KSPTFQMRHIPMI355X, 0, "KSPCreate_TFQMRHIPMI355X", KSPCreate_TFQMRHIPMI355X);CHKERRQ(ierr);
   ierr = KSPRegister(KSPBICGHIPMI355X, 0, "KSPCreate_BICGHIPMI355X", KSPCreate_BICGHIPMI355X);CHKERRQ(ierr);
+  ierr = KSPRegister(KSPLSQRHIPMI355X, 0, "KSPCreate_LSQRHIPMI355X", KSPCreate_LSQRHIPMI355X);CHKERRQ(ierr);
   ierr = KSPRegister(KSPCGSHIPMI355X, 0, "KSPCreate_CGSHIPMI355X", KSPCreate_CGSHIPMI355X);CHKERRQ(ierr);
 #if !defined(PETSCHIPMI355X_WITH_PETSC)
   /* the harness has no CPU types: the reference's generic names select the HIPMI355X implementation of the same shape

@@ -10,13 +10,15 @@
  *     KSPMINRESHIPMI355X     "minreshipmi355x"      MINRES     (the sequence of KSPMINRES,  src/ksp/ksp/impls/minres/minres.c)
  *     KSPTFQMRHIPMI355X      "tfqmrhipmi355x"       TFQMR      (the sequence of KSPTFQMR,   src/ksp/ksp/impls/tfqmr/tfqmr.c)
  *     KSPCGSHIPMI355X        "cgshipmi355x"         CGS        (the sequence of KSPCGS,     src/ksp/ksp/impls/cgs/cgs.c)
+ *     KSPBICGHIPMI355X       "bicghipmi355x"        BiCG       (the sequence of KSPBICG,    src/ksp/ksp/impls/bicg/bicg.c)
+ *     KSPLSQRHIPMI355X       "lsqrhipmi355x"        LSQR       (the sequence of KSPLSQR,    src/ksp/ksp/impls/lsqr/lsqr.c; rectangular operators)
  *
  * They compute what the reference's solvers compute -- same iterates, same residual history, same exits, bit for bit against
  * the op-by-op sequences (tests/test_host_gpu.py) -- but group the vector work between two reductions into the fused sweeps a
  * Vec / Mat type may offer by name ("VecKrylovFusedOps_C", "MatMultTDotBegin_C", "MatMultDiagonalScale_C";
  * include/petsckrylovfused.h), keep scalars that only the device needs on the device, and queue the front half of the next
  * iteration before the host has looked at the residual norm.  On vectors of a type without those methods every step falls
- * back to the public Vec / Mat / PC calls, so the types work on any PETSc objects -- with TWO exceptions: minreshipmi355x (see there) and chebychevhipmi355x.  The
+ * back to the public Vec / Mat / PC calls, so the types work on any PETSc objects -- with THREE exceptions: minreshipmi355x, lsqrhipmi355x (see there) and chebychevhipmi355x.  The
  * three-term Chebyshev update needs VecScale, which is not among the calls this library takes from PETSc, so there is nothing to fall
  * back to: KSPSetUp of that type returns PETSC_ERR_SUP on vectors whose type lacks "cheby_step" and names -ksp_type chebychev.
  *
@@ -1427,6 +1429,234 @@ PetscErrorCode KSPCreate_BICGHIPMI355X(KSP ksp) {
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_LEFT, 1);CHKERRQ(ierr);
   ksp->ops->setup = KSPSetUp_BicgHIP; ksp->ops->solve = KSPSolve_BicgHIP; ksp->ops->setfromoptions = KSPSetFromOptions_BicgHIP; ksp->ops->destroy = KSPDestroy_BicgHIP;
   ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "KSPGetFusedStepCounts_BicgHIP", (PetscVoidFunction)KSPGetFusedStepCounts_BicgHIP);CHKERRQ(ierr);
+  return 0;
+}
+
+/* ================================================================================================ LSQR
+ * The sequence of KSPSolve_LSQR (src/ksp/ksp/impls/lsqr/lsqr.c) as the harness's KSPLSQR restates it -- rectangular operators, work vectors
+ * from MatGetVecs(A), the unpreconditioned norm (the recurrence's estimate of ||b - A x||), a preconditioner on the normal equations, the
+ * same exits (the happy-breakdown one included) -- same iterates, histories and estimates, bit for bit.  Behind the two
+ * products an iteration's vector work is the two sweeps of "VecLsqrFusedOps_C" (include/petsckrylovfused.h):
+ *   PCNONE:   u1 = A v ; lsqr_bidiag QUEUE (u1 -= alpha u, |u1|^2 into a device slot, u1 normalised from the slot) ; v1 = A^T u1, queued
+ *             without a wait ; lsqr_bidiag FINISH (v1 -= beta v with beta rooted from the slot on the device, |v1|^2) -- beta^2 and alpha^2
+ *             come home together, the iteration's ONE wait ; the Givens scalars on the host ; lsqr_update (v1 /= alpha, x, the standard-error
+ *             sum, w).  5 launches besides the products: the two sweeps, the scaling, the publish kernel, the update.  A beta == 0 found at that wait has cost one product on work
+ *             vectors and nothing in x.
+ *   other PC: the row-space side through lsqr_bidiag WAIT (beta comes home), steps 6-7 through VecAXPY, KSP_PCApply and VecDot, and the
+ *             update sweep takes Z1 with its scaling.  Two waits.
+ * VecScale is not among the calls this library takes from PETSc: the scalings outside the sweeps (the solve start, u1 and v1 in the mixed
+ * route) are the update sweep's scaling form, so like minreshipmi355x the type has no op-by-op route and KSPSetUp returns PETSC_ERR_SUP on
+ * vectors without the table (-ksp_type lsqr is that route).  On several ranks the Vec type refuses the slot routes (the slot would hold a
+ * local partial sum): both sweeps take the WAIT route, the sums are all-reduced, step 6 takes beta from the host -- two waits.
+ * KSPHIPMI355XGetFusedStepCounts: (bidiagonalisation sweeps run, update sweeps run; the scaling forms are not counted). */
+typedef struct { Vec se; PetscBool se_flg; PetscReal arnorm, anorm, rhs_norm; Vec U, U1, V, V1, W, Z, Z1; PetscInt nbidiag, nupdate; } KSP_LsqrHIP;
+
+static const VecLsqrFusedOps *vec_lsqr_ops(Vec x) {
+  PetscVoidFunction f = NULL;
+  const VecLsqrFusedOps *L;
+  if (PetscObjectQueryFunction((PetscObject)x, "VecLsqrFusedOps_C", &f) || !f) return NULL;
+  L = ((VecLsqrFusedOpsGetFn)f)();
+  return (L && L->lsqr_bidiag && L->lsqr_update) ? L : NULL;
+}
+static PetscErrorCode lsqr_no_pc(KSP ksp, PetscBool *nopc) {
+  PCType t = NULL;
+  PetscErrorCode ierr = PCGetType(ksp->pc, &t);CHKERRQ(ierr);
+  *nopc = (PetscBool)(t && !strcmp(t, PCNONE));
+  return 0;
+}
+static PetscErrorCode lsqr_get_work(KSP ksp) {   /* what this configuration needs and does not have yet; set-up and solve both ask */
+  KSP_LsqrHIP *ld = (KSP_LsqrHIP *)ksp->data;
+  PetscErrorCode ierr;
+  PetscBool nopc;
+  Mat A;
+  Vec right = NULL, left = NULL;
+  Vec *m_side[] = {&ld->U, &ld->U1}, *n_side[] = {&ld->V, &ld->V1, &ld->W, &ld->Z, &ld->Z1, &ld->se};
+  ierr = lsqr_no_pc(ksp, &nopc);CHKERRQ(ierr);
+  const PetscBool n_needed[] = {PETSC_TRUE, PETSC_TRUE, PETSC_TRUE, (PetscBool)!nopc, (PetscBool)!nopc, ld->se_flg};
+  ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
+  ierr = MatGetVecs(A, &right, &left);CHKERRQ(ierr);
+  for (int k = 0; k < 2; k++) if (!*m_side[k]) { ierr = VecDuplicate(left, m_side[k]);CHKERRQ(ierr); }
+  for (int k = 0; k < 6; k++) if (n_needed[k] && !*n_side[k]) { ierr = VecDuplicate(right, n_side[k]);CHKERRQ(ierr); }
+  ierr = VecDestroy(&right);CHKERRQ(ierr);
+  ierr = VecDestroy(&left);CHKERRQ(ierr);
+  return 0;
+}
+static PetscErrorCode lsqr_check(KSP ksp) {
+  PetscErrorCode ierr;
+  PetscBool nopc;
+  Mat A, Pm;
+  if (has_null_space(ksp)) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s with a null space: there is no removal behind the transposed product", KSPLSQRHIPMI355X);
+  if (ksp->pc_side == PC_RIGHT || ksp->pc_side == PC_SYMMETRIC) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s: left preconditioning (of the normal equations) only", KSPLSQRHIPMI355X);
+  ierr = lsqr_no_pc(ksp, &nopc);CHKERRQ(ierr);
+  ierr = PCGetOperators(ksp->pc, &A, &Pm, NULL);CHKERRQ(ierr);
+  if (!nopc && (Pm->rmap->N != A->cmap->N || Pm->cmap->N != A->cmap->N)) SETERRQ(HipObjComm(ksp), PETSC_ERR_ARG_SIZ, "KSP type %s preconditions the normal equations: the preconditioner matrix must be %d x %d, it is %d x %d", KSPLSQRHIPMI355X, (int)A->cmap->N, (int)A->cmap->N, (int)Pm->rmap->N, (int)Pm->cmap->N);
+  return 0;
+}
+static PetscErrorCode lsqr_needs_table(KSP ksp) {
+  const KSP_LsqrHIP *ld = (const KSP_LsqrHIP *)ksp->data;
+  if (!vec_lsqr_ops(ld->V) || !vec_lsqr_ops(ld->U) || (ksp->vec_sol && !vec_lsqr_ops(ksp->vec_sol)) || (ksp->vec_rhs && !vec_lsqr_ops(ksp->vec_rhs)))
+    SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s needs vectors whose type offers the fused LSQR sweeps (\"VecLsqrFusedOps_C\"); use -ksp_type lsqr on these vectors", KSPLSQRHIPMI355X);
+  return 0;
+}
+static PetscErrorCode KSPSetUp_LsqrHIP(KSP ksp) {
+  PetscErrorCode ierr = lsqr_check(ksp);CHKERRQ(ierr);
+  ierr = lsqr_get_work(ksp);CHKERRQ(ierr);
+  return lsqr_needs_table(ksp);
+}
+static PetscErrorCode KSPSetFromOptions_LsqrHIP(KSP ksp) {
+  KSP_LsqrHIP *ld = (KSP_LsqrHIP *)ksp->data;
+  PetscInt iv = ld->se_flg;
+  PetscErrorCode ierr = option_level(ksp, "-ksp_lsqr_set_standard_error", 0, 1, &iv);CHKERRQ(ierr);
+  ld->se_flg = (PetscBool)iv;
+  return 0;
+}
+static PetscErrorCode KSPLSQRSetStandardErrorVec_LsqrHIP(KSP ksp, Vec se) {
+  KSP_LsqrHIP *ld = (KSP_LsqrHIP *)ksp->data;
+  if (se == ld->se) return 0;
+  PetscErrorCode ierr = VecDestroy(&ld->se);CHKERRQ(ierr);
+  ld->se = se;
+  return 0;
+}
+static PetscErrorCode KSPLSQRGetStandardErrorVec_LsqrHIP(KSP ksp, Vec *se) { *se = ((KSP_LsqrHIP *)ksp->data)->se; return 0; }
+static PetscErrorCode KSPLSQRGetArnorm_LsqrHIP(KSP ksp, PetscReal *arnorm, PetscReal *rhs_norm, PetscReal *anorm) {
+  const KSP_LsqrHIP *ld = (const KSP_LsqrHIP *)ksp->data;
+  *arnorm = ld->arnorm; *rhs_norm = ld->rhs_norm; *anorm = ld->anorm;
+  return 0;
+}
+static PetscErrorCode KSPGetFusedStepCounts_LsqrHIP(KSP ksp, PetscInt *fused, PetscInt *opbyop) {
+  const KSP_LsqrHIP *ld = (const KSP_LsqrHIP *)ksp->data;
+  *fused = ld->nbidiag; *opbyop = ld->nupdate;
+  return 0;
+}
+static PetscErrorCode KSPDefaultPCNone_LsqrHIP(KSP ksp) { (void)ksp; return 0; }   /* its presence is the message: see the harness's KSPSetUp */
+static const char *const lsqr_methods[] = {"KSPLSQRSetStandardErrorVec_C", "KSPLSQRGetStandardErrorVec_C", "KSPLSQRGetArnorm_C", "KSPHIPMI355XGetFusedStepCounts_C", "KSPDefaultPCNone_C"};
+static PetscErrorCode KSPDestroy_LsqrHIP(KSP ksp) {
+  KSP_LsqrHIP *ld = (KSP_LsqrHIP *)ksp->data;
+  PetscErrorCode ierr;
+  if (!ld) return 0;
+  Vec *all[] = {&ld->U, &ld->U1, &ld->V, &ld->V1, &ld->W, &ld->Z, &ld->Z1, &ld->se};
+  for (int k = 0; k < 8; k++) { ierr = VecDestroy(all[k]);CHKERRQ(ierr); }
+  HipFree(ld); ksp->data = NULL;
+  for (int k = 0; k < 5; k++) { ierr = PetscObjectComposeFunction((PetscObject)ksp, lsqr_methods[k], "", (PetscVoidFunction)NULL);CHKERRQ(ierr); }
+  return 0;
+}
+#define LSQR_REFUSED(ksp) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "the fused LSQR sweep refused these vectors; use -ksp_type lsqr")
+/* v = a v through the update sweep's scaling form (a == 1: nothing) */
+static PetscErrorCode lsqr_scale(KSP ksp, const VecLsqrFusedOps *L, Vec v, PetscScalar a) {
+  PetscBool done;
+  PetscErrorCode ierr = L->lsqr_update(v, NULL, NULL, NULL, a, 0.0, 0.0, 0.0, PETSC_TRUE, &done);CHKERRQ(ierr);
+  if (!done) LSQR_REFUSED(ksp);
+  return 0;
+}
+static PetscErrorCode KSPSolve_LsqrHIP(KSP ksp) {
+  PetscErrorCode ierr;
+  KSP_LsqrHIP *ld = (KSP_LsqrHIP *)ksp->data;
+  Vec X = ksp->vec_sol, B = ksp->vec_rhs, U, U1, V, V1, W, Z, Z1, SE, t;
+  const VecLsqrFusedOps *L;
+  Mat A;
+  PetscBool nopc, done, one_wait = PETSC_TRUE;                       /* until the Vec type refuses the slot route (several ranks) */
+  PetscScalar alpha, beta, rho, rhobar, phi, phibar, theta, c, s, dot, sums[2];
+  PetscReal anorm2;
+  PetscInt i;
+
+  ierr = lsqr_check(ksp);CHKERRQ(ierr);
+  ierr = lsqr_get_work(ksp);CHKERRQ(ierr);
+  ierr = lsqr_needs_table(ksp);CHKERRQ(ierr);
+  ierr = lsqr_no_pc(ksp, &nopc);CHKERRQ(ierr);
+  ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
+  if (B->map->n != A->rmap->n || X->map->n != A->cmap->n) SETERRQ(HipObjComm(ksp), PETSC_ERR_ARG_SIZ, "KSP type %s: b must have the rows of A (%d, it has %d) and x its columns (%d, it has %d)", KSPLSQRHIPMI355X, (int)A->rmap->n, (int)B->map->n, (int)A->cmap->n, (int)X->map->n);
+  U = ld->U; U1 = ld->U1; V = ld->V; V1 = ld->V1; W = ld->W; Z = ld->Z; Z1 = ld->Z1; SE = ld->se;
+  L = vec_lsqr_ops(X);
+  ksp->its = 0;
+  ierr = start_residual(ksp, A, X, B, U);CHKERRQ(ierr);
+  ierr = VecNorm(U, NORM_2, &beta);CHKERRQ(ierr);
+  ld->rhs_norm = beta; ld->arnorm = 0.0; ld->anorm = 0.0;
+  ierr = report(ksp, 0, beta);CHKERRQ(ierr);
+  ierr = KSPTestConvergence(ksp, 0, beta);CHKERRQ(ierr);
+  if (ksp->reason) return 0;
+  ierr = lsqr_scale(ksp, L, U, beta != 0.0 ? 1.0 / beta : 1.0);CHKERRQ(ierr);
+  ierr = bicg_mult_transpose(ksp, A, U, V);CHKERRQ(ierr);
+  if (nopc) { ierr = VecNorm(V, NORM_2, &alpha);CHKERRQ(ierr); }
+  else {
+    ierr = KSP_PCApply(ksp, V, Z);CHKERRQ(ierr);
+    ierr = VecDot(V, Z, &dot);CHKERRQ(ierr);
+    alpha = PetscSqrtReal(dot);
+    ierr = lsqr_scale(ksp, L, Z, alpha != 0.0 ? 1.0 / alpha : 1.0);CHKERRQ(ierr);
+  }
+  if (alpha == 0.0) { ksp->reason = KSP_CONVERGED_ATOL_NORMAL; return 0; }
+  ierr = lsqr_scale(ksp, L, V, 1.0 / alpha);CHKERRQ(ierr);
+  ierr = VecCopy(nopc ? V : Z, W);CHKERRQ(ierr);
+  if (SE) { ierr = VecSet(SE, 0.0);CHKERRQ(ierr); }
+  phibar = beta; rhobar = alpha; anorm2 = alpha * alpha;
+  ld->arnorm = alpha * beta; ld->anorm = PetscSqrtReal(anorm2);
+
+  for (i = 0; i < ksp->max_it; i++) {
+    PetscBool broke;
+    ierr = KSP_MatMult(ksp, A, nopc ? V : Z, U1);CHKERRQ(ierr);
+    done = PETSC_FALSE;
+    if (nopc && one_wait) { ierr = L->lsqr_bidiag(U, U1, alpha, LSQR_BIDIAG_QUEUE, sums, &done);CHKERRQ(ierr); one_wait = done; }
+    if (nopc && one_wait) {
+      ierr = bicg_mult_transpose(ksp, A, U1, V1);CHKERRQ(ierr);
+      ierr = L->lsqr_bidiag(V, V1, 0.0, LSQR_BIDIAG_FINISH, sums, &done);CHKERRQ(ierr);
+      if (!done) LSQR_REFUSED(ksp);
+      ld->nbidiag += 2;
+      beta = PetscSqrtReal(sums[0]); alpha = PetscSqrtReal(sums[1]);
+    } else if (nopc) {                                               /* several ranks: both sums all-reduced, beta and alpha come home one by one */
+      ierr = L->lsqr_bidiag(U, U1, alpha, LSQR_BIDIAG_WAIT, sums, &done);CHKERRQ(ierr);
+      if (!done) LSQR_REFUSED(ksp);
+      beta = PetscSqrtReal(sums[0]);
+      ierr = lsqr_scale(ksp, L, U1, beta != 0.0 ? 1.0 / beta : 1.0);CHKERRQ(ierr);
+      ierr = bicg_mult_transpose(ksp, A, U1, V1);CHKERRQ(ierr);
+      ierr = L->lsqr_bidiag(V, V1, beta, LSQR_BIDIAG_WAIT, sums, &done);CHKERRQ(ierr);
+      if (!done) LSQR_REFUSED(ksp);
+      ld->nbidiag += 2;
+      alpha = PetscSqrtReal(sums[0]);
+    } else {
+      ierr = L->lsqr_bidiag(U, U1, alpha, LSQR_BIDIAG_WAIT, sums, &done);CHKERRQ(ierr);
+      if (!done) LSQR_REFUSED(ksp);
+      ld->nbidiag++;
+      beta = PetscSqrtReal(sums[0]);
+      ierr = lsqr_scale(ksp, L, U1, beta != 0.0 ? 1.0 / beta : 1.0);CHKERRQ(ierr);
+      ierr = bicg_mult_transpose(ksp, A, U1, V1);CHKERRQ(ierr);
+      ierr = VecAXPY(V1, -beta, V);CHKERRQ(ierr);
+      ierr = KSP_PCApply(ksp, V1, Z1);CHKERRQ(ierr);
+      ierr = VecDot(V1, Z1, &dot);CHKERRQ(ierr);
+      alpha = PetscSqrtReal(dot);
+      ierr = lsqr_scale(ksp, L, V1, alpha != 0.0 ? 1.0 / alpha : 1.0);CHKERRQ(ierr);
+    }
+    broke = (PetscBool)(beta == 0.0 || alpha == 0.0);
+    rho = PetscSqrtReal(rhobar * rhobar + beta * beta);
+    c = rhobar / rho; s = beta / rho;
+    theta = s * alpha; rhobar = -c * alpha;
+    phi = c * phibar; phibar = s * phibar;
+    ierr = L->lsqr_update(nopc ? V1 : Z1, X, W, SE, alpha != 0.0 ? 1.0 / alpha : 1.0, phi / rho, -theta / rho, 1.0 / (rho * rho), broke, &done);CHKERRQ(ierr);
+    if (!done) LSQR_REFUSED(ksp);
+    ld->nupdate++;
+    ld->arnorm = alpha * PetscAbsScalar(s * phi);
+    anorm2 += alpha * alpha + beta * beta;
+    ld->anorm = PetscSqrtReal(anorm2);
+    ksp->its = i + 1;
+    ierr = report(ksp, i + 1, phibar);CHKERRQ(ierr);
+    ierr = KSPTestConvergence(ksp, i + 1, phibar);CHKERRQ(ierr);
+    if (broke && !ksp->reason) ksp->reason = KSP_CONVERGED_HAPPY_BREAKDOWN;
+    if (ksp->reason) break;
+    t = U; U = U1; U1 = t; t = V; V = V1; V1 = t; t = Z; Z = Z1; Z1 = t;
+  }
+  if (i >= ksp->max_it && !ksp->reason) ksp->reason = KSP_DIVERGED_ITS;
+  return 0;
+}
+PetscErrorCode KSPCreate_LSQRHIPMI355X(KSP ksp) {
+  KSP_LsqrHIP *ld;
+  PetscErrorCode ierr = PetscMalloc(sizeof(*ld), &ld);CHKERRQ(ierr);
+  memset(ld, 0, sizeof(*ld));
+  ksp->data = ld;
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);    /* the one of KSPLSQR */
+  ksp->ops->setup = KSPSetUp_LsqrHIP; ksp->ops->solve = KSPSolve_LsqrHIP; ksp->ops->setfromoptions = KSPSetFromOptions_LsqrHIP; ksp->ops->destroy = KSPDestroy_LsqrHIP;
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, lsqr_methods[0], "KSPLSQRSetStandardErrorVec_LsqrHIP", (PetscVoidFunction)KSPLSQRSetStandardErrorVec_LsqrHIP);CHKERRQ(ierr);
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, lsqr_methods[1], "KSPLSQRGetStandardErrorVec_LsqrHIP", (PetscVoidFunction)KSPLSQRGetStandardErrorVec_LsqrHIP);CHKERRQ(ierr);
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, lsqr_methods[2], "KSPLSQRGetArnorm_LsqrHIP", (PetscVoidFunction)KSPLSQRGetArnorm_LsqrHIP);CHKERRQ(ierr);
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, lsqr_methods[3], "KSPGetFusedStepCounts_LsqrHIP", (PetscVoidFunction)KSPGetFusedStepCounts_LsqrHIP);CHKERRQ(ierr);
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, lsqr_methods[4], "KSPDefaultPCNone_LsqrHIP", (PetscVoidFunction)KSPDefaultPCNone_LsqrHIP);CHKERRQ(ierr);
   return 0;
 }
 

@@ -1461,6 +1461,81 @@ static const VecBicgFusedOps *VecBicgFusedOps_HIP(void) {
   return &ops;
 }
 
+/* Fused forms for KSPSolve_LSQR (include/petsckrylovfused.h lsqr_bidiag, lsqr_update), under the rules of the TFQMR forms above.
+ * The bidiagonalisation sweep: VecAXPY(Y, -coef, X) and the sum of VecNorm(Y, NORM_2).
+ *   WAIT:    the sum is all-reduced as every fused reduction is (reduce_finish: RCCL, host-staged or one rank) and comes home: one wait.
+ *   QUEUE:   the sum goes to device slot LSQR_SLOT and y is scaled by its rooted reciprocal behind the sweep (mi355x_vec_scale_rnorm_dev:
+ *            VecNormalize's and VecScale's cases); nothing comes home, the caller queues the next product at once.
+ *   FINISH:  coef is the root of slot LSQR_SLOT, formed by the sweep itself; the new sum goes to slot LSQR_SLOT + 1 and both are handed
+ *            to the host by the publish kernel: the iteration's one wait.
+ * QUEUE and FINISH are refused on more than one rank: the slot would hold this rank's partial sum. */
+#define LSQR_SLOT 42     /* two device scratch slots clear of the ordinary reductions (<= 32 from 0), SUM_SLOT and the split-phase ones (48..) */
+PetscErrorCode VecLsqrBidiag_HIPMI355X(Vec x, Vec y, PetscScalar coef, VecLsqrBidiagRoute route, PetscScalar sums[2], PetscBool *done) {
+  PetscErrorCode ierr; DEVCTX;
+  Vec all[2] = {y, x};
+  const PetscScalar *dx; PetscScalar *dy; double *out, *ds;
+  *done = PETSC_FALSE;
+  if (!x || !y || (route != LSQR_BIDIAG_WAIT && route != LSQR_BIDIAG_QUEUE && route != LSQR_BIDIAG_FINISH)) return 0;
+  if (!tfqmr_operands_ok(all, 2, 1)) return 0;
+  if (route != LSQR_BIDIAG_WAIT && (hip_local_only || HipCommSize(HipObjComm(y)) > 1 || DEVICE_COLLECTIVES(y))) return 0;
+  ierr = VecHIPGetRead(x, &dx);CHKERRQ(ierr);
+  ierr = VecHIPGetReadWrite(y, &dy);CHKERRQ(ierr);
+  ds = mi355x_handle_device_scratch(dc->h) + LSQR_SLOT;
+  if (route == LSQR_BIDIAG_WAIT) {
+    ierr = reduce_target(y, dc, &out);CHKERRQ(ierr);
+    CHKHIP(mi355x_vec_lsqr_bidiag(dc->h, N_(y), coef, NULL, dx, dy, out));
+  } else if (route == LSQR_BIDIAG_QUEUE) {
+    CHKHIP(mi355x_vec_lsqr_bidiag(dc->h, N_(y), coef, NULL, dx, dy, ds));
+    CHKHIP(mi355x_vec_scale_rnorm_dev(dc->h, N_(y), ds, dy));
+  } else {
+    CHKHIP(mi355x_vec_lsqr_bidiag(dc->h, N_(y), 0.0, ds, dx, dy, ds + 1));
+    CHKHIP(mi355x_handle_publish(dc->h, ds, 2));
+  }
+  VecHIPRestoreWrite(y);
+  HipStateIncrease(y);
+  if (route == LSQR_BIDIAG_WAIT) { ierr = reduce_finish(y, dc, 1, 0, sums);CHKERRQ(ierr); }
+  else if (route == LSQR_BIDIAG_FINISH) {
+    CHKHIP(mi355x_handle_wait_result(dc->h)); { PetscErrorCode e_ = HipTriWatchCheck();CHKERRQ(e_); }
+    sums[0] = mi355x_handle_host_scratch(dc->h)[0]; sums[1] = mi355x_handle_host_scratch(dc->h)[1];
+  }
+  ierr = PetscLogFlops((route == LSQR_BIDIAG_QUEUE ? 5.0 : 4.0) * y->map->n);CHKERRQ(ierr);   /* 2n + 2n (+ n) */
+  *done = PETSC_TRUE;
+  return 0;
+}
+/* The update sweep: step 8's VecScale of v1, x += step w, the standard-error sum and the new w in one pass; nothing comes back */
+PetscErrorCode VecLsqrUpdate_HIPMI355X(Vec v1, Vec x, Vec w, Vec se, PetscScalar ialpha, PetscScalar step, PetscScalar cf, PetscScalar irho2, PetscBool skip_w,
+                                       PetscBool *done) {
+  PetscErrorCode ierr; DEVCTX;
+  Vec all[4];
+  PetscScalar *dv = NULL, *dx = NULL, *dw = NULL, *dse = NULL;
+  *done = PETSC_FALSE;
+  if (step == 0.0) x = NULL;                                            /* not touched, so not looked at */
+  if (skip_w && step == 0.0 && !se) w = NULL;
+  if (skip_w && ialpha == 1.0) v1 = NULL;
+  if ((!v1 && !(skip_w && ialpha == 1.0)) || (!x && step != 0.0) || (!w && (!skip_w || step != 0.0 || se))) return 0;
+  all[0] = v1; all[1] = x; all[2] = w; all[3] = se;
+  if (!tfqmr_operands_ok(all, 4, 4)) return 0;
+  if (!v1 && !x && !w && !se) { *done = PETSC_TRUE; return 0; }
+  if (v1) { ierr = VecHIPGetReadWrite(v1, &dv);CHKERRQ(ierr); }
+  if (x) { ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr); }
+  if (w) { ierr = VecHIPGetReadWrite(w, &dw);CHKERRQ(ierr); }
+  if (se) { ierr = VecHIPGetReadWrite(se, &dse);CHKERRQ(ierr); }
+  Vec any = v1 ? v1 : (w ? w : (x ? x : se));
+  CHKHIP(mi355x_vec_lsqr_update(dc->h, N_(any), ialpha, step, cf, irho2, skip_w ? 1 : 0, dv, dx, dw, dse));
+  if (v1 && ialpha != 1.0) { VecHIPRestoreWrite(v1); HipStateIncrease(v1); }
+  if (x) { VecHIPRestoreWrite(x); HipStateIncrease(x); }
+  if (se) { VecHIPRestoreWrite(se); HipStateIncrease(se); }
+  if (w && !skip_w) { VecHIPRestoreWrite(w); HipStateIncrease(w); }
+  ierr = PetscLogFlops(((v1 && ialpha != 1.0 ? 1.0 : 0.0) + (x ? 2.0 : 0.0) + (se ? 3.0 : 0.0) + (skip_w ? 0.0 : 2.0)) * any->map->n);CHKERRQ(ierr);
+  *done = PETSC_TRUE;
+  return 0;
+}
+/* "VecLsqrFusedOps_C": the sweeps of LSQR */
+static const VecLsqrFusedOps *VecLsqrFusedOps_HIP(void) {
+  static const VecLsqrFusedOps ops = {VecLsqrBidiag_HIPMI355X, VecLsqrUpdate_HIPMI355X};
+  return &ops;
+}
+
 /* the *_local slots of struct _VecOps (vecimpl.h:262-266): the same device reductions without the step across ranks;
  * NORM_2 returns the root of the local sum, as VecNorm_Seq does for VecNormBegin (comb.c squares it again) */
 static PetscErrorCode VecDot_HIP_local(Vec x, Vec y, PetscScalar *val) { hip_local_only = 1; PetscErrorCode ierr = VecDot_HIP(x, y, val); hip_local_only = 0; return ierr; }
@@ -1655,6 +1730,7 @@ static PetscErrorCode VecCreate_HIP_common(Vec v, const char *tname) {
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecMinresFusedOps_C", "VecMinresFusedOps_HIP", (PetscVoidFunction)VecMinresFusedOps_HIP);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecTfqmrFusedOps_C", "VecTfqmrFusedOps_HIP", (PetscVoidFunction)VecTfqmrFusedOps_HIP);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecBicgFusedOps_C", "VecBicgFusedOps_HIP", (PetscVoidFunction)VecBicgFusedOps_HIP);CHKERRQ(ierr);
+  ierr = PetscObjectComposeFunction((PetscObject)v, "VecLsqrFusedOps_C", "VecLsqrFusedOps_HIP", (PetscVoidFunction)VecLsqrFusedOps_HIP);CHKERRQ(ierr);
   return 0;
 }
 

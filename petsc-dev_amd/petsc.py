@@ -72,6 +72,8 @@ _SIG = {
     "KSPChebychevSetEigenvalues": [vp, dbl, dbl], "KSPRichardsonSetScale": [vp, dbl], "KSPMonitorSet": [vp, vp, vp, vp],
     "PCApplyRichardson": [vp, vp, vp, vp, dbl, dbl, dbl, i32, i32, P(i32), P(i32)], "PCApplyRichardsonExists": [vp, P(i32)],
     "KSPHIPMI355XGetFusedStepCounts": [vp, P(i32), P(i32)],
+    "KSPSetConvergenceTest": [vp, vp, vp, vp], "KSPLSQRSetStandardErrorVec": [vp, vp], "KSPLSQRGetStandardErrorVec": [vp, P(vp)],
+    "KSPLSQRGetArnorm": [vp, P(dbl), P(dbl), P(dbl)],
     "KSPSetUp": [vp], "KSPSolve": [vp, vp, vp], "KSPGetIterationNumber": [vp, P(i32)], "KSPGetResidualNorm": [vp, P(dbl)],
     "KSPGetConvergedReason": [vp, P(i32)], "KSPSetResidualHistory": [vp, vp, i32, i32],
     "KSPGetResidualHistory": [vp, P(vp), P(i32)], "KSPDestroy": [P(vp)],
@@ -498,8 +500,29 @@ class KSP:
         """KSPRichardsonSetScale: the damping factor (the richardson types; ignored by any other)"""
         lib().KSPRichardsonSetScale(self.h, float(scale))
 
+    def set_convergence_test(self, name="KSPDefaultConverged"):
+        """KSPSetConvergenceTest with one of the library's own tests, by name: KSPDefaultConverged, KSPSkipConverged, KSPLSQRDefaultConverged"""
+        lib().KSPSetConvergenceTest(self.h, C.cast(lib().raw(name), vp), None, None)
+
+    def lsqr_set_standard_error_vec(self, se):
+        """KSPLSQRSetStandardErrorVec: the LSQR types keep the running sum of (w .* w) / rho^2 in se; the KSP takes over the reference"""
+        lib().KSPLSQRSetStandardErrorVec(self.h, se.h)
+        se.own = False
+
+    def lsqr_get_standard_error_vec(self):
+        """KSPLSQRGetStandardErrorVec: the vector (not owned by the caller), or None"""
+        se = vp()
+        lib().KSPLSQRGetStandardErrorVec(self.h, C.byref(se))
+        return Vec(se, own=False) if se.value else None
+
+    def lsqr_get_arnorm(self):
+        """KSPLSQRGetArnorm: the estimates (||A^T r||, ||b||, ||A||_F) of the last solve of an LSQR type"""
+        a, r, n = dbl(), dbl(), dbl()
+        lib().KSPLSQRGetArnorm(self.h, C.byref(a), C.byref(r), C.byref(n))
+        return a.value, r.value, n.value
+
     def fused_step_counts(self):
-        """KSPHIPMI355XGetFusedStepCounts: (fused, opbyop) update steps of the pipelined CG types since the type was set; minreshipmi355x: (Lanczos sweeps run, 0); tfqmrhipmi355x / cgshipmi355x: (fused sweeps run, iterations with a step run op by op); (0, 0) for any other"""
+        """KSPHIPMI355XGetFusedStepCounts: (fused, opbyop) update steps of the pipelined CG types since the type was set; minreshipmi355x: (Lanczos sweeps run, 0); tfqmrhipmi355x / cgshipmi355x: (fused sweeps run, iterations with a step run op by op); lsqrhipmi355x: (bidiagonalisation sweeps run, update sweeps run); (0, 0) for any other"""
         f = i32(); o = i32()
         lib().KSPHIPMI355XGetFusedStepCounts(self.h, C.byref(f), C.byref(o))
         return f.value, o.value
