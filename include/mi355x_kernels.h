@@ -336,6 +336,9 @@ int mi355x_spmv_plan_group_rows(mi355x_handle_t h, mi355x_spmv_plan_t plan, cons
 int mi355x_spmv_plan_set_pairsum(mi355x_spmv_plan_t plan, int on);
 int mi355x_spmv_plan_group_info(mi355x_spmv_plan_t plan, int *ngroups, long *nshared_indices, int *pairsum);
 int mi355x_spmv_plan_info(mi355x_spmv_plan_t plan, int *nblocks, int *nlong, size_t *workspace_bytes);
+/* the device copy of rows_host a compressed-row plan keeps (NULL otherwise; the plan's own, valid while it lives) and the plan's row
+ * count: what mi355x_mat_row_reduce takes as `rows` / `mbs` for a matrix whose device row pointer is the compressed one */
+int mi355x_spmv_plan_rows(mi355x_spmv_plan_t plan, const int **rows_dev, int *nrows);
 /* MatMult_SeqAIJ      src/mat/impls/aij/seq/aij.c:1225 (loop 1269-1277, macro aij.h:383-386)
  *   y[r] = sum_k a[k] x[j[k]], products summed in k order starting from 0.0
  * aa and aj must be allocated with 16 bytes of slack past their last element (mi355x_malloc of nz elements + 16 B):
@@ -402,6 +405,32 @@ int mi355x_csr_axpy_map(mi355x_handle_t h, int nzx, const int *xtoy, double alph
  * (the off-diagonal blocks of MPIAIJ, compacted through each matrix's own garray).  X stores an entry Y lacks: non-zero, the first
  * such row in *bad_row (-1 otherwise), xtoy undefined.  Rows are split over host threads from 200 000 entries. */
 int mi355x_csr_subset_map(int m, const int *xi, const int *xj, const int *xcols, const int *yi, const int *yj, const int *ycols, int *xtoy, int *bad_row);
+
+/* ---- row reductions over the stored values (csrc/mat_reduce.hip) ------- */
+/* MatNorm_SeqAIJ / MatGetRowMaxAbs_SeqAIJ / MatGetRowMax_SeqAIJ / MatGetRowMin_SeqAIJ (aij.c), MatNorm_SeqBAIJ (baij.c): one result per
+ * point row of a CSR (bs = 1) or BCSR (bs = 2 .. 7, blocks column-major) matrix of mbs block rows and ncols scalar columns.  A point
+ * row's entries are taken in storage order -- block after block, a block's columns left to right -- by one lane, so every result
+ * carries the bits of the sequential loop:
+ *   MI355X_ROW_SUM / _ABSSUM / _SQSUM   s = acc ? acc[row] : 0.0; then s = s + a, s + |a|, s + a * a (product and sum rounded separately)
+ *                                       entry by entry.  acc (may be NULL, may be out) continues a sum: the off-diagonal block of an
+ *                                       MPIAIJ row after its diagonal block.
+ *   MI355X_ROW_MAXABS                   starts at (0.0, column 0); an entry replaces the current value on cur < |a| only: the first of
+ *                                       equals stays, a NaN never replaces and is never replaced.
+ *   MI355X_ROW_MAX / _MIN               a row that stores fewer than ncols entries starts at the implicit (0.0, the smallest column
+ *                                       the row does not store -- columns ascending within the row), a full row at its first entry, a
+ *                                       row without entries gives (0.0, 0); replacement on cur < a (a < cur) only.
+ * out[row] gets the value, idx[row] (extrema only; may be NULL; needs aj) the scalar column.  rows (bs = 1 only, may be NULL): the
+ * compressed-row form, row r of ai is row rows[r] of acc / out / idx and no other row is written.  Value offsets are 32-bit:
+ * ai[mbs] bs^2 < 2^31.  All arrays on the device.  Nothing outside out[0, mbs bs) / idx[0, mbs bs) is written; empty rows are legal.
+ * The maximum or the sum over the results is mi355x_vec_max / mi355x_vec_norm on out. */
+#define MI355X_ROW_SUM    0
+#define MI355X_ROW_ABSSUM 1
+#define MI355X_ROW_SQSUM  2
+#define MI355X_ROW_MAXABS 3
+#define MI355X_ROW_MAX    4
+#define MI355X_ROW_MIN    5
+int mi355x_mat_row_reduce(mi355x_handle_t h, int op, int mbs, int bs, int ncols, const int *ai, const int *aj, const double *aa,
+                          const int *rows, const double *acc, double *out, int *idx);
 
 /* ---- column-tiled CSR SpMV: x staged in LDS (csrc/spmv_tiled.hip) ------ */
 /* For matrices whose x gathers miss the caches (rows that pick columns from a wide window without neighbouring rows sharing them):

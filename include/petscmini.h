@@ -321,6 +321,18 @@ PetscErrorCode MatCholeskyFactorNumeric(Mat fact, Mat mat, const MatFactorInfo *
 PetscErrorCode MatSolve(Mat mat, Vec b, Vec x);
 PetscErrorCode MatSolveTranspose(Mat mat, Vec b, Vec x);   /* matrix.c MatSolveTranspose: x = (factor)^-T b; PETSC_ERR_SUP without ops->solvetranspose */
 PetscErrorCode MatDiagonalScale(Mat A, Vec l, Vec r);   /* A <- diag(l) A diag(r); l or r may be NULL (aij.c:2055, mpiaij.c:2183) */
+/* queries about the stored values (matrix.c; MatNorm_SeqAIJ, MatGetRowMaxAbs_SeqAIJ, MatGetRowMax_SeqAIJ, MatGetRowMin_SeqAIJ,
+ * MatGetColumnNorms_SeqAIJ aij.c).  MatNorm: NORM_1 (largest column sum of |a|), NORM_FROBENIUS, NORM_INFINITY (largest row sum);
+ * NORM_2 is PETSC_ERR_SUP.  The row extrema go to v (the matrix's row layout), the column each one was found at to idx (a host array
+ * of the local rows, or NULL): the first of equal entries, NaNs never chosen over a number; MatGetRowMax / MatGetRowMin let a row
+ * that stores fewer entries than the matrix has columns compete with one implicit 0.0 at its smallest missing column.
+ * MatGetRowSum is MatMult with a vector of ones.  MatGetColumnNorms: NORM_1, NORM_2 or NORM_INFINITY of every column into norms[N]. */
+PetscErrorCode MatNorm(Mat A, NormType type, PetscReal *nrm);
+PetscErrorCode MatGetRowMaxAbs(Mat A, Vec v, PetscInt idx[]);
+PetscErrorCode MatGetRowMax(Mat A, Vec v, PetscInt idx[]);
+PetscErrorCode MatGetRowMin(Mat A, Vec v, PetscInt idx[]);
+PetscErrorCode MatGetRowSum(Mat A, Vec v);
+PetscErrorCode MatGetColumnNorms(Mat A, NormType type, PetscReal norms[]);
 /* null spaces of singular operators (src/mat/interface/matnull.c): the constant vector (has_cnst) and / or n orthonormal vectors, which
  * the null space keeps references to.  MatNullSpaceRemove: the constant first (VecSum, sum / (-N), VecShift), then the vectors (VecMDot,
  * VecMAXPY), then the function set with MatNullSpaceSetFunction; out != NULL: the result goes to an internal copy returned in *out */

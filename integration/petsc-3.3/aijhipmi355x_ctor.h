@@ -127,6 +127,11 @@ PetscErrorCode MatCreate_SeqAIJHIPMI355X(Mat B) {
   B->ops->matmultnumeric   = MatMatMultNumeric_SeqAIJHIP;   /* name and finds the parent's "MatMatMult_seqaij_seqaij_C" no longer -- such a call is PETSC_ERR_SUP */
   B->ops->transpose        = MatTranspose_SeqAIJHIP;
   B->ops->ptap             = MatPtAP_SeqAIJHIP;
+  B->ops->norm             = MatNorm_SeqAIJHIP;             /* slots norm, getrowmaxabs, getrowmax, getrowmin, getcolumnnorms (matimpl.h): the row */
+  B->ops->getrowmaxabs     = MatGetRowMaxAbs_SeqAIJHIP;     /* reductions of csrc/mat_reduce.hip over the device copy (and its cached transpose), or the */
+  B->ops->getrowmax        = MatGetRowMax_SeqAIJHIP;        /* same contracts as loops over the host copy: -mat_hipmi355x_reductions <device|host> */
+  B->ops->getrowmin        = MatGetRowMin_SeqAIJHIP;
+  B->ops->getcolumnnorms   = MatGetColumnNorms_SeqAIJHIP;
   B->ops->setvaluesbatch   = MatSetValuesBatch_SeqAIJHIP;
   B->ops->setfromoptions   = MatSetFromOptions_SeqAIJHIP;  /* the type's -mat_hipmi355x_* options under the matrix's prefix (slot 76); MatSetFromOptions_SeqAIJ has none of its own in 3.3 */
   /* ops->duplicate stays MatDuplicate_SeqAIJ (aij.c:3964): it creates the new matrix with MatSetType(type_name), i.e. through THIS

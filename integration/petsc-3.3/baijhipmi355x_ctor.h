@@ -103,6 +103,11 @@ PetscErrorCode MatCreate_SeqBAIJHIPMI355X(Mat B) {
   B->ops->multadd     = MatMultAdd_SeqAIJHIP;
   B->ops->multtranspose    = MatMultTranspose_SeqAIJHIP;      /* MatMultTranspose_SeqBAIJ / MatMultTransposeAdd_SeqBAIJ, baij2.c:1579, 1740: the block transpose */
   B->ops->multtransposeadd = MatMultTransposeAdd_SeqAIJHIP;
+  B->ops->norm           = MatNorm_SeqAIJHIP;             /* the BCSR instances of the row reductions (csrc/mat_reduce.hip): per point row, */
+  B->ops->getrowmaxabs   = MatGetRowMaxAbs_SeqAIJHIP;     /* block after block, a block's columns left to right */
+  B->ops->getrowmax      = MatGetRowMax_SeqAIJHIP;
+  B->ops->getrowmin      = MatGetRowMin_SeqAIJHIP;
+  B->ops->getcolumnnorms = MatGetColumnNorms_SeqAIJHIP;
   B->ops->assemblyend = MatAssemblyEnd_SeqBAIJHIPMI355X;
   B->ops->destroy     = MatDestroy_SeqBAIJHIPMI355X;
   B->ops->getvecs     = MatGetVecs_HIP;

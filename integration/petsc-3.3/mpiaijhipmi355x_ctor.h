@@ -93,6 +93,11 @@ PetscErrorCode MatCreate_MPIAIJHIPMI355X(Mat B) {
   B->ops->zerorows         = MatZeroRows_MPIAIJHIP;        /* the owners' rows through both blocks' zerorows slots */
   B->ops->zerorowscolumns  = MatZeroRowsColumns_MPIAIJHIP; /* PETSC_ERR_SUP: the mask and x are not carried through the halo scatter yet */
   B->ops->sor              = MatSOR_MPIAIJHIP;             /* local sweeps over the plug-in's halo scatter and the blocks' own slots */
+  B->ops->norm             = MatNorm_MPIAIJHIP;            /* the blocks' own reductions (host/aijhip.c) and one all-reduce: the off-diagonal block continues the */
+  B->ops->getrowmaxabs     = MatGetRowMaxAbs_MPIAIJHIP;    /* diagonal block's row sums, column results meet in an array of the N global columns, the row */
+  B->ops->getrowmax        = MatGetRowMax_MPIAIJHIP;       /* extrema of the two blocks compete with global column numbers */
+  B->ops->getrowmin        = MatGetRowMin_MPIAIJHIP;
+  B->ops->getcolumnnorms   = MatGetColumnNorms_MPIAIJHIP;
   /* ops->setoption stays MatSetOption_MPIAIJ: it hands MAT_KEEP_NONZERO_PATTERN to both blocks */
   B->ops->assemblyend      = MatAssemblyEnd_MPIAIJHIPMI355X;
   B->ops->destroy          = MatDestroy_MPIAIJHIPMI355X;

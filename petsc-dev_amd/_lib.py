@@ -184,6 +184,8 @@ KERNEL_API = {
     "mi355x_spgemm_plan_destroy": [vp],
     "mi355x_spgemm_plan_info": [vp, pi32, pi32, C.POINTER(sz)],
     "mi355x_spgemm_numeric": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "mi355x_spmv_plan_rows": [vp, C.POINTER(vp), pi32],
+    "mi355x_mat_row_reduce": [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "mi355x_pack": [vp, sz, vp, vp, vp],
     "mi355x_unpack_insert": [vp, sz, vp, vp, vp],
     "mi355x_unpack_add": [vp, sz, vp, vp, vp],

@@ -232,6 +232,69 @@ PetscErrorCode MatZeroEntries(Mat A) {
   A->state++;
   return 0;
 }
+/* MatNorm, MatGetRowMaxAbs / MatGetRowMax / MatGetRowMin, MatGetColumnNorms (matrix.c): the argument checks, then the type's slot.  The
+ * matrix does not change; the result vector does.  idx (may be NULL): the column of each row's extremum, a host array of the local rows. */
+PetscErrorCode MatNorm(Mat A, NormType type, PetscReal *nrm) {
+  MatTypeSet(A, 1); MatAssembled(A);
+  if (!nrm) SETERRQ(A->comm, PETSC_ERR_ARG_NULL, "Null pointer for the norm");
+  if ((int)type < (int)NORM_1 || (int)type > (int)NORM_INFINITY) SETERRQ(A->comm, PETSC_ERR_ARG_OUTOFRANGE, "Unknown NormType %d", (int)type);
+  if (!A->ops->norm) SETERRQ(A->comm, PETSC_ERR_SUP, "Mat type %s", A->type_name);
+  return (*A->ops->norm)(A, type, nrm);
+}
+static PetscErrorCode row_extremum_args(Mat A, Vec v) {
+  if (!v) SETERRQ(A->comm, PETSC_ERR_ARG_NULL, "Null vector");
+  if (A->factortype) SETERRQ(A->comm, PETSC_ERR_ARG_WRONGSTATE, "Not for factored matrix");
+  if (A->rmap->N != v->map->N || A->rmap->n != v->map->n) SETERRQ(A->comm, PETSC_ERR_ARG_SIZ, "Mat mat,Vec v: dim (%d,%d) local (%d,%d)", A->rmap->N, v->map->N, A->rmap->n, v->map->n);
+  return 0;
+}
+PetscErrorCode MatGetRowMaxAbs(Mat A, Vec v, PetscInt idx[]) {
+  PetscErrorCode ierr;
+  MatTypeSet(A, 1); MatAssembled(A);
+  ierr = row_extremum_args(A, v);CHKERRQ(ierr);
+  if (!A->ops->getrowmaxabs) SETERRQ(A->comm, PETSC_ERR_SUP, "Mat type %s", A->type_name);
+  ierr = (*A->ops->getrowmaxabs)(A, v, idx);CHKERRQ(ierr);
+  PetscObjectStateIncrease(v);
+  return 0;
+}
+PetscErrorCode MatGetRowMax(Mat A, Vec v, PetscInt idx[]) {
+  PetscErrorCode ierr;
+  MatTypeSet(A, 1); MatAssembled(A);
+  ierr = row_extremum_args(A, v);CHKERRQ(ierr);
+  if (!A->ops->getrowmax) SETERRQ(A->comm, PETSC_ERR_SUP, "Mat type %s", A->type_name);
+  ierr = (*A->ops->getrowmax)(A, v, idx);CHKERRQ(ierr);
+  PetscObjectStateIncrease(v);
+  return 0;
+}
+PetscErrorCode MatGetRowMin(Mat A, Vec v, PetscInt idx[]) {
+  PetscErrorCode ierr;
+  MatTypeSet(A, 1); MatAssembled(A);
+  ierr = row_extremum_args(A, v);CHKERRQ(ierr);
+  if (!A->ops->getrowmin) SETERRQ(A->comm, PETSC_ERR_SUP, "Mat type %s", A->type_name);
+  ierr = (*A->ops->getrowmin)(A, v, idx);CHKERRQ(ierr);
+  PetscObjectStateIncrease(v);
+  return 0;
+}
+/* MatGetRowSum, matrix.c: generic, as in the reference -- MatMult with a vector of ones, so it works for every type and carries the
+ * bits of the type's product */
+PetscErrorCode MatGetRowSum(Mat A, Vec v) {
+  PetscErrorCode ierr;
+  Vec ones;
+  MatTypeSet(A, 1); MatAssembled(A);
+  ierr = row_extremum_args(A, v);CHKERRQ(ierr);
+  ierr = MatGetVecs(A, &ones, NULL);CHKERRQ(ierr);
+  ierr = VecSet(ones, 1.0);CHKERRQ(ierr);
+  ierr = MatMult(A, ones, v);
+  { PetscErrorCode e2 = VecDestroy(&ones); if (!ierr) ierr = e2; }
+  return ierr;
+}
+PetscErrorCode MatGetColumnNorms(Mat A, NormType type, PetscReal norms[]) {
+  MatTypeSet(A, 1); MatAssembled(A);
+  if (A->cmap->N && !norms) SETERRQ(A->comm, PETSC_ERR_ARG_NULL, "Null array of norms");
+  if (type != NORM_1 && type != NORM_2 && type != NORM_INFINITY) SETERRQ(A->comm, PETSC_ERR_ARG_WRONG, "Unknown NormType %d", (int)type);
+  if (!A->ops->getcolumnnorms) SETERRQ(A->comm, PETSC_ERR_SUP, "Mat type %s", A->type_name);
+  return (*A->ops->getcolumnnorms)(A, type, norms);
+}
+
 /* MatShift, axpy.c:170-200: the type's slot, else the loop of MatSetValues(ADD_VALUES) over the local rows and an assembly */
 PetscErrorCode MatShift(Mat Y, PetscScalar a) {
   PetscErrorCode ierr;

@@ -157,6 +157,11 @@ struct _MatOps {
   PetscErrorCode (*matmultsymbolic)(Mat, Mat, PetscReal, Mat *);
   PetscErrorCode (*matmultnumeric)(Mat, Mat, Mat);
   PetscErrorCode (*ptap)(Mat, Mat, MatReuse, PetscReal, Mat *);      /* slot 92: C = P^T A P */
+  PetscErrorCode (*norm)(Mat, NormType, PetscReal *);             /* the queries about the stored values (matrix.c MatNorm, MatGetRowMaxAbs ...) */
+  PetscErrorCode (*getrowmaxabs)(Mat, Vec, PetscInt[]);
+  PetscErrorCode (*getrowmax)(Mat, Vec, PetscInt[]);
+  PetscErrorCode (*getrowmin)(Mat, Vec, PetscInt[]);
+  PetscErrorCode (*getcolumnnorms)(Mat, NormType, PetscReal *);
   PetscErrorCode (*setfromoptions)(Mat);                 /* slot 76 */
   PetscErrorCode (*destroy)(Mat);                        /* slot 60 */
   PetscErrorCode (*getvecs)(Mat, Vec *, Vec *);          /* slot 88 */

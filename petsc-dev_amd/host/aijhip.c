@@ -171,6 +171,7 @@ static PetscErrorCode hip_mat_option(Mat A, int which, PetscInt *val) {
 }
 /* -mat_hipmi355x_sor <device|host> (default device): where MatSOR runs; 0: the option is not given under this prefix */
 static PetscErrorCode product_route_option(Mat A, const char *prefix, int *route);   /* -mat_hipmi355x_product, with the products below */
+static PetscErrorCode reductions_route_option(Mat A, const char *prefix, int *route);   /* -mat_hipmi355x_reductions, with the reductions below */
 static PetscErrorCode sor_route_option(Mat A, const char *prefix, int *route) {
   PetscErrorCode ierr;
   char kind[16] = ""; PetscBool set = PETSC_FALSE;
@@ -196,7 +197,9 @@ static PetscErrorCode MatSetFromOptions_SeqAIJHIP(Mat A) {
     ierr = sor_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
     if (route) d->sor.route = route;
     ierr = product_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
-    if (route) d->product_route = route; }
+    if (route) d->product_route = route;
+    ierr = reductions_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
+    if (route) d->reductions_route = route; }
   return 0;
 }
 
@@ -245,6 +248,8 @@ static PetscErrorCode device_free(Mat A) {
   value_maps_free(d);
   if (d->bm_v) mi355x_free(d->bm_v);
   d->bm_v = NULL; d->bm_vcap = 0;
+  if (d->red_work) mi355x_free(d->red_work);
+  d->red_work = NULL; d->red_cap = 0;
   d->baij4_mfma = PETSC_FALSE;
   mirror_reset(d);
   return 0;
@@ -2047,6 +2052,288 @@ PetscErrorCode MatHIPMI355XGetProductCounts(Mat C, PetscInt *symbolic_builds, Pe
   return 0;
 }
 
+/* ---------------------------------------------------------------- Norms and row / column reductions
+ * MatNorm (MatNorm_SeqAIJ aij.c, MatNorm_SeqBAIJ baij.c), MatGetRowMaxAbs / MatGetRowMax / MatGetRowMin (aij.c), MatGetColumnNorms
+ * (MatGetColumnNorms_SeqAIJ aij.c) of the two sequential types.  A point row's entries are taken in storage order (BAIJ: block after
+ * block, a block's columns left to right), one at a time:
+ *   NORM_INFINITY   the row sums of |a|, then their maximum as VecMax takes it (0.0 for a matrix without rows)
+ *   NORM_1          the same over the columns; a column's entries are added in ascending row order.  On the device the rows of the cached
+ *                   transpose -- the one MatMultTranspose builds and refreshes -- whose rows list their entries in exactly that order
+ *   NORM_FROBENIUS  the root of the sum of squares of the stored value array: on the device VecNorm's tree over that array (the bits of
+ *                   mi355x_vec_norm), on the host the sequential sum; the two differ by at most (nnz - 1) 2^-53 sum a^2 before the root
+ *   NORM_2          PETSC_ERR_SUP, as in the reference
+ *   row max-abs     starts at (0.0, column 0), replaced on cur < |a| only
+ *   row max / min   a row with fewer stored entries than the matrix has columns starts at the implicit (0.0, its smallest missing
+ *                   column), a full row at its first entry, a row without entries gives (0.0, 0); replaced on cur < a (a < cur) only
+ *   column norms    NORM_1 / NORM_2 / NORM_INFINITY: the sums of |a|, the roots of the sums of a * a, the max-abs of the columns
+ * -mat_hipmi355x_reductions <device|host> (default device; host when the process has no device): the device route runs the row
+ * reductions of csrc/mat_reduce.hip over the plain device value array -- the one every device-side value update writes, current after
+ * MatSeqAIJHIPUpload whatever form the products take -- and its transposed form; the host route is the loops below over the host
+ * copy.  Except for NORM_FROBENIUS the two give the same bits. */
+static PetscErrorCode reductions_route_option(Mat A, const char *prefix, int *route) {
+  PetscErrorCode ierr;
+  char kind[16] = ""; PetscBool set = PETSC_FALSE;
+  *route = 0;
+  ierr = PetscOptionsGetString(prefix, "-mat_hipmi355x_reductions", kind, sizeof(kind), &set);CHKERRQ(ierr);
+  if (!set) return 0;
+  if (strcmp(kind, "device") && strcmp(kind, "host")) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "-mat_hipmi355x_reductions <device|host>, got %s", kind);
+  *route = strcmp(kind, "host") ? 1 : 2;
+  return 0;
+}
+static PetscErrorCode reductions_route(Mat A, int *route) {
+  PetscErrorCode ierr;
+  *route = SD(A)->reductions_route;
+  if (!*route) { ierr = reductions_route_option(A, NULL, route);CHKERRQ(ierr); }
+  if (!*route) { int n = 0; *route = (mi355x_device_count(&n) || n < 1) ? 2 : 1; }
+  SD(A)->reductions_route = *route;       /* resolved once per matrix; MatSetFromOptions reads the option again */
+  return 0;
+}
+/* entry j of point row I bs + r (block row I starts at block a0) and its scalar column */
+#define RED_VALUE(m_, bs_, a0_, r_, e_) ((m_)->a[(size_t)(a0_) * (size_t)((bs_) * (bs_)) + (size_t)(e_) * (size_t)(bs_) + (size_t)(r_)])
+#define RED_COLUMN(m_, bs_, a0_, e_) ((m_)->j[(a0_) + (e_) / (bs_)] * (bs_) + (e_) % (bs_))
+static PetscScalar red_term(int op, PetscScalar v) { return (op == MI355X_ROW_ABSSUM || op == MI355X_ROW_MAXABS) ? fabs(v) : (op == MI355X_ROW_SQSUM ? v * v : v); }
+/* the host route of mi355x_mat_row_reduce: out[i] (and idx[i], extrema only, may be NULL) for every point row of a matrix of ncols
+ * columns; add: a sum continues from out[i] */
+static void host_row_reduce(const HipAIJ *a, int op, PetscInt ncols, PetscBool add, PetscScalar *out, PetscInt *idx) {
+  const PetscInt bs = a->bs > 1 ? a->bs : 1;
+  for (PetscInt I = 0; I < a->m; I++) for (PetscInt r = 0; r < bs; r++) {
+    const PetscInt a0 = a->i[I], n = (a->i[I + 1] - a0) * bs, row = I * bs + r;
+    PetscScalar cur = (add && op <= MI355X_ROW_SQSUM) ? out[row] : 0.0; PetscInt best = -1;
+    if (op <= MI355X_ROW_SQSUM) { for (PetscInt j = 0; j < n; j++) cur = cur + red_term(op, RED_VALUE(a, bs, a0, r, j)); }
+    else {
+      const PetscBool full = (PetscBool)(n > 0 && n == ncols);
+      for (PetscInt j = 0; j < n; j++) {
+        const PetscScalar v = red_term(op, RED_VALUE(a, bs, a0, r, j));
+        if ((op != MI355X_ROW_MAXABS && j == 0 && full) || (op == MI355X_ROW_MIN ? v < cur : cur < v)) { cur = v; best = j; }
+      }
+    }
+    out[row] = cur;
+    if (idx && op > MI355X_ROW_SQSUM) {
+      PetscInt col = 0;
+      if (best >= 0) col = RED_COLUMN(a, bs, a0, best);
+      else if (op != MI355X_ROW_MAXABS && n > 0) { while (col < n && RED_COLUMN(a, bs, a0, col) == col) col++; }
+      idx[row] = col;
+    }
+  }
+}
+/* the same per column (op: MI355X_ROW_ABSSUM, _SQSUM or _MAXABS), a column's entries taken in ascending row order */
+static void host_col_reduce(const HipAIJ *a, int op, PetscScalar *out) {
+  const PetscInt bs = a->bs > 1 ? a->bs : 1;
+  for (PetscInt c = 0; c < a->n; c++) out[c] = 0.0;
+  for (PetscInt I = 0; I < a->m; I++) for (PetscInt r = 0; r < bs; r++) {
+    const PetscInt a0 = a->i[I], n = (a->i[I + 1] - a0) * bs;
+    for (PetscInt j = 0; j < n; j++) {
+      const PetscScalar v = red_term(op, RED_VALUE(a, bs, a0, r, j));
+      const PetscInt c = RED_COLUMN(a, bs, a0, j);
+      if (op == MI355X_ROW_MAXABS) { if (out[c] < v) out[c] = v; }
+      else out[c] = out[c] + v;
+    }
+  }
+}
+/* VecMax_Seq's loop (dvec2.c): what mi355x_vec_max gives; 0.0 for no elements */
+static PetscReal host_max_of(const PetscScalar *x, PetscInt n) {
+  if (n <= 0) return 0.0;
+  PetscReal m = x[0];
+  for (PetscInt k = 1; k < n; k++) if (x[k] > m) m = x[k];
+  return m;
+}
+static PetscErrorCode device_max_of(PetscDeviceCtx *dc, const PetscScalar *x, PetscInt n, PetscReal *val) {
+  *val = 0.0;
+  if (n <= 0) return 0;
+  CHKHIP(mi355x_vec_max(dc->h, (size_t)n, x, mi355x_handle_host_scratch(dc->h)));
+  CHKHIP(mi355x_handle_wait_result(dc->h)); { PetscErrorCode e_ = HipTriWatchCheck();CHKERRQ(e_); }
+  *val = mi355x_handle_host_scratch(dc->h)[0];
+  return 0;
+}
+static PetscErrorCode red_work_get(Mat A, size_t bytes, void **w) {
+  Mat_SeqAIJHIP *d = SD(A);
+  if (d->red_cap < bytes || !d->red_work) {
+    if (d->red_work) mi355x_free(d->red_work);
+    d->red_work = NULL; d->red_cap = 0;
+    CHKHIP(mi355x_malloc(&d->red_work, PetscMax(bytes, 16)));
+    d->red_cap = PetscMax(bytes, 16);
+  }
+  *w = d->red_work;
+  return 0;
+}
+/* the device copy current, for the device route; the compressed-row form of an MPIAIJ matrix's off-diagonal block is not a matrix a
+ * user holds, and its rows are not the matrix's */
+static PetscErrorCode red_device_copy(Mat A, PetscDeviceCtx **dc) {
+  PetscErrorCode ierr;
+  if (!SA(A)->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  ierr = PetscDeviceGet(dc);CHKERRQ(ierr);
+  ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
+  if (SD(A)->cprow) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "reductions over a compressed-row device copy");
+  return 0;
+}
+/* out_dev[c] for every column c through the rows of the transposed form (the blocked companion's block transpose when there is one) */
+static PetscErrorCode device_col_reduce(Mat A, PetscDeviceCtx *dc, int op, PetscScalar *out_dev) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A); HipDevForm *f = NULL;
+  const PetscInt bs = a->bs > 1 ? a->bs : 1;
+  ierr = product_form(A, PETSC_TRUE, dc, &f);CHKERRQ(ierr);
+  CHKHIP(mi355x_mat_row_reduce(dc->h, op, (int)(a->n / f->bs), (int)f->bs, (int)(a->m * bs), f->i, f->j, f->a, NULL, NULL, out_dev, NULL));
+  return 0;
+}
+static PetscErrorCode MatNorm_SeqAIJHIP(Mat A, NormType type, PetscReal *nrm) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
+  const PetscInt bs = a->bs > 1 ? a->bs : 1, mrows = a->m * bs;
+  const size_t nvals = (size_t)a->nz * (size_t)(bs * bs);
+  int route;
+  if (type == NORM_2) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "No support for two norm");
+  if (type != NORM_1 && type != NORM_FROBENIUS && type != NORM_INFINITY) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_OUTOFRANGE, "Unknown NormType %d", (int)type);
+  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  ierr = reductions_route(A, &route);CHKERRQ(ierr);
+  if (route == 2) {
+    if (type == NORM_FROBENIUS) {
+      PetscReal s = 0.0;
+      for (size_t k = 0; k < nvals; k++) s = s + a->a[k] * a->a[k];
+      *nrm = sqrt(s);
+    } else {
+      const PetscInt len = type == NORM_1 ? a->n : mrows;
+      PetscScalar *w;
+      ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(len, 1), &w);CHKERRQ(ierr);
+      if (type == NORM_1) host_col_reduce(a, MI355X_ROW_ABSSUM, w); else host_row_reduce(a, MI355X_ROW_ABSSUM, a->n, PETSC_FALSE, w, NULL);
+      *nrm = host_max_of(w, len);
+      HipFree(w);
+    }
+  } else {
+    PetscDeviceCtx *dc; void *w;
+    ierr = red_device_copy(A, &dc);CHKERRQ(ierr);
+    if (type == NORM_FROBENIUS) {
+      *nrm = 0.0;
+      if (nvals) {
+        CHKHIP(mi355x_vec_norm(dc->h, nvals, 2, d->mat.a, mi355x_handle_host_scratch(dc->h)));
+        CHKHIP(mi355x_handle_wait_result(dc->h)); { PetscErrorCode e_ = HipTriWatchCheck();CHKERRQ(e_); }
+        *nrm = sqrt(mi355x_handle_host_scratch(dc->h)[0]);
+      }
+    } else if (type == NORM_1) {
+      ierr = red_work_get(A, sizeof(PetscScalar) * (size_t)a->n, &w);CHKERRQ(ierr);
+      ierr = device_col_reduce(A, dc, MI355X_ROW_ABSSUM, (PetscScalar *)w);CHKERRQ(ierr);
+      ierr = device_max_of(dc, (const PetscScalar *)w, a->n, nrm);CHKERRQ(ierr);
+    } else {
+      ierr = red_work_get(A, sizeof(PetscScalar) * (size_t)mrows, &w);CHKERRQ(ierr);
+      CHKHIP(mi355x_mat_row_reduce(dc->h, MI355X_ROW_ABSSUM, (int)a->m, (int)bs, (int)a->n, d->mat.i, d->mat.j, d->mat.a, NULL, NULL, (PetscScalar *)w, NULL));
+      ierr = device_max_of(dc, (const PetscScalar *)w, mrows, nrm);CHKERRQ(ierr);
+    }
+  }
+  return PetscLogFlops(type == NORM_FROBENIUS ? 2.0 * (double)nvals : (double)nvals);
+}
+static int red_is_hip_vec(Vec v) { return v && v->data && strstr(HipObjTypeName(v), "hipmi355x") != NULL; }
+static PetscErrorCode row_extremum(Mat A, int op, Vec v, PetscInt idx[]) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
+  const PetscInt bs = a->bs > 1 ? a->bs : 1, mrows = a->m * bs;
+  int route;
+  if (!red_is_hip_vec(v)) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "the result must be a HIPMI355X vector");
+  if (v->map->n != A->rmap->n) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_SIZ, "Nonconforming matrix and vector");
+  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  ierr = reductions_route(A, &route);CHKERRQ(ierr);
+  if (route == 2) {
+    PetscScalar *h;
+    ierr = VecGetArray(v, &h);CHKERRQ(ierr);
+    host_row_reduce(a, op, a->n, PETSC_FALSE, h, idx);
+    return VecRestoreArray(v, &h);
+  }
+  PetscDeviceCtx *dc; PetscScalar *dv; void *w = NULL;
+  ierr = red_device_copy(A, &dc);CHKERRQ(ierr);
+  if (idx) { ierr = red_work_get(A, sizeof(PetscInt) * (size_t)mrows, &w);CHKERRQ(ierr); }
+  ierr = VecHIPGetWrite(v, &dv);CHKERRQ(ierr);
+  CHKHIP(mi355x_mat_row_reduce(dc->h, op, (int)a->m, (int)bs, (int)a->n, d->mat.i, d->mat.j, d->mat.a, NULL, NULL, dv, (int *)w));
+  ierr = VecHIPRestoreWrite(v);CHKERRQ(ierr);
+  if (idx && mrows > 0) {
+    CHKHIP(mi355x_memcpy_d2h(dc->h, idx, w, sizeof(PetscInt) * (size_t)mrows));
+    CHKHIP(mi355x_handle_synchronize(dc->h));
+  }
+  return 0;
+}
+static PetscErrorCode MatGetRowMaxAbs_SeqAIJHIP(Mat A, Vec v, PetscInt idx[]) { return row_extremum(A, MI355X_ROW_MAXABS, v, idx); }
+static PetscErrorCode MatGetRowMax_SeqAIJHIP(Mat A, Vec v, PetscInt idx[]) { return row_extremum(A, MI355X_ROW_MAX, v, idx); }
+static PetscErrorCode MatGetRowMin_SeqAIJHIP(Mat A, Vec v, PetscInt idx[]) { return row_extremum(A, MI355X_ROW_MIN, v, idx); }
+static PetscErrorCode MatGetColumnNorms_SeqAIJHIP(Mat A, NormType type, PetscReal *norms) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A);
+  int route;
+  const int op = type == NORM_1 ? MI355X_ROW_ABSSUM : (type == NORM_2 ? MI355X_ROW_SQSUM : MI355X_ROW_MAXABS);
+  if (type != NORM_1 && type != NORM_2 && type != NORM_INFINITY) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "Unknown NormType %d", (int)type);
+  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  ierr = reductions_route(A, &route);CHKERRQ(ierr);
+  if (route == 2) host_col_reduce(a, op, norms);
+  else if (a->n > 0) {
+    PetscDeviceCtx *dc; void *w;
+    ierr = red_device_copy(A, &dc);CHKERRQ(ierr);
+    ierr = red_work_get(A, sizeof(PetscScalar) * (size_t)a->n, &w);CHKERRQ(ierr);
+    ierr = device_col_reduce(A, dc, op, (PetscScalar *)w);CHKERRQ(ierr);
+    CHKHIP(mi355x_memcpy_d2h(dc->h, norms, w, sizeof(PetscScalar) * (size_t)a->n));
+    CHKHIP(mi355x_handle_synchronize(dc->h));
+  }
+  if (type == NORM_2) for (PetscInt c = 0; c < a->n; c++) norms[c] = sqrt(norms[c]);
+  return 0;
+}
+
+/* The same reductions over ONE BLOCK of an MPIAIJ matrix (host/mpiaijhip.c), on the route the parent chose (1 device, 2 host).
+ * Route 1: out / idx are device arrays of the block's rows; the off-diagonal block's compressed-row device copy is walked through
+ * its plan's row list, and the rows it does not list keep what out / idx hold (add) or get (0.0, 0), an empty row's result.
+ * Route 2: host arrays.  ncols: the columns of the matrix the block is a part of (a row is full only with that many entries). */
+PetscErrorCode MatReductionsRoute_SeqAIJHIP(Mat A, int *route) { return reductions_route(A, route); }
+PetscErrorCode MatBlockRowReduce_SeqAIJHIP(Mat A, int route, int op, PetscInt ncols, PetscBool add, PetscScalar *out, PetscInt *idx) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
+  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  if (a->bs > 1) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "blocks of an MPIAIJ matrix are point matrices");
+  if (route == 2) { host_row_reduce(a, op, ncols, add, out, idx); return 0; }
+  PetscDeviceCtx *dc; const int *rows = NULL; int nrows = (int)a->m;
+  ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+  ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
+  if (d->cprow) {
+    CHKHIP(mi355x_spmv_plan_rows(d->mat.plan, &rows, &nrows));
+    if (!add && a->m > 0) {
+      CHKHIP(mi355x_memset(dc->h, out, 0, sizeof(PetscScalar) * (size_t)a->m));
+      if (idx) CHKHIP(mi355x_memset(dc->h, idx, 0, sizeof(PetscInt) * (size_t)a->m));
+    }
+  }
+  CHKHIP(mi355x_mat_row_reduce(dc->h, op, nrows, 1, (int)ncols, d->mat.i, d->mat.j, d->mat.a, rows, add ? out : NULL, out, (int *)idx));
+  return 0;
+}
+/* per column of the block (host array of the block's columns), either route */
+PetscErrorCode MatBlockColReduce_SeqAIJHIP(Mat A, int route, int op, PetscScalar *out_host) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A);
+  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  if (route == 2) { host_col_reduce(a, op, out_host); return 0; }
+  if (a->n <= 0) return 0;
+  PetscDeviceCtx *dc; void *w;
+  ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+  ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
+  ierr = red_work_get(A, sizeof(PetscScalar) * (size_t)a->n, &w);CHKERRQ(ierr);
+  ierr = device_col_reduce(A, dc, op, (PetscScalar *)w);CHKERRQ(ierr);
+  CHKHIP(mi355x_memcpy_d2h(dc->h, out_host, w, sizeof(PetscScalar) * (size_t)a->n));
+  CHKHIP(mi355x_handle_synchronize(dc->h));
+  return 0;
+}
+/* the sum of squares of the block's stored values: VecNorm's tree over the device value array, or the sequential sum */
+PetscErrorCode MatBlockSquareSum_SeqAIJHIP(Mat A, int route, PetscReal *s) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A);
+  *s = 0.0;
+  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  if (route == 2) { for (PetscInt k = 0; k < a->nz; k++) *s = *s + a->a[k] * a->a[k]; return 0; }
+  if (a->nz <= 0) return 0;
+  PetscDeviceCtx *dc;
+  ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+  ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_norm(dc->h, (size_t)a->nz, 2, SD(A)->mat.a, mi355x_handle_host_scratch(dc->h)));
+  CHKHIP(mi355x_handle_wait_result(dc->h)); { PetscErrorCode e_ = HipTriWatchCheck();CHKERRQ(e_); }
+  *s = mi355x_handle_host_scratch(dc->h)[0];
+  return 0;
+}
+PetscErrorCode HipDeviceMaxOf(const PetscScalar *x_dev, PetscInt n, PetscReal *val) {
+  PetscDeviceCtx *dc;
+  PetscErrorCode ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+  return device_max_of(dc, x_dev, n, val);
+}
+
 static PetscErrorCode MatGetVecs_HIP(Mat A, Vec *right, Vec *left) {   /* MatGetVecs_SeqAIJCUSP aijcusp.cu:324-345 */
   PetscErrorCode ierr;
   if (right) {
@@ -2123,6 +2410,11 @@ static PetscErrorCode create_common(Mat B, const char *tname, PetscInt bs) {
   B->ops->sor = MatSOR_SeqAIJHIP;
   B->ops->diagonalscale = MatDiagonalScale_SeqAIJHIP;
   B->ops->setvaluesbatch = MatSetValuesBatch_SeqAIJHIP;
+  B->ops->norm = MatNorm_SeqAIJHIP;
+  B->ops->getrowmaxabs = MatGetRowMaxAbs_SeqAIJHIP;
+  B->ops->getrowmax = MatGetRowMax_SeqAIJHIP;
+  B->ops->getrowmin = MatGetRowMin_SeqAIJHIP;
+  B->ops->getcolumnnorms = MatGetColumnNorms_SeqAIJHIP;
   B->ops->duplicate = MatDuplicate_SeqAIJHIP;
   B->ops->matmult = MatMatMult_SeqAIJHIP;                     /* sequential AIJ operands; the block type answers PETSC_ERR_SUP */
   B->ops->matmultsymbolic = MatMatMultSymbolic_SeqAIJHIP;
@@ -2166,6 +2458,7 @@ static PetscErrorCode MatDuplicate_SeqAIJHIP(Mat A, MatDuplicateOption op, Mat *
   if (op != MAT_COPY_VALUES) memset(SA(B)->a, 0, sizeof(PetscScalar) * (size_t)a->nz * (size_t)(a->bs > 1 ? a->bs * a->bs : 1));
   memcpy(SD(B)->opt, SD(A)->opt, sizeof(SD(A)->opt)); memcpy(SD(B)->opt_set, SD(A)->opt_set, sizeof(SD(A)->opt_set));
   SD(B)->cprow = SD(A)->cprow; SD(B)->sor.route = SD(A)->sor.route; SD(B)->product_route = SD(A)->product_route;
+  SD(B)->reductions_route = SD(A)->reductions_route;
   SA(B)->keepnonzeropattern = a->keepnonzeropattern;
   *M = B;
   return 0;

@@ -324,6 +324,11 @@ typedef struct {
   } sor;
   HipMatProduct *prod;       /* the matrix is the result of a product (NULL: an ordinary matrix) */
   int product_route;         /* -mat_hipmi355x_product <device|host> as MatSetFromOptions read it under the matrix's prefix (0: not given there) */
+  /* MatNorm / MatGetRowMaxAbs / Max / Min / MatGetColumnNorms (host/aijhip.c, "Norms and row / column reductions"): -mat_hipmi355x_reductions
+   * <device|host> as MatSetFromOptions read it under the matrix's prefix (0: not given there), and the device work array the row results
+   * and their locations go to before the finishing pass or the copy to the caller's host array (red_cap bytes; goes with the pattern) */
+  int reductions_route;
+  void *red_work; size_t red_cap;
   PetscInt opt[8]; PetscBool opt_set[8];   /* the type's options as MatSetFromOptions read them under the matrix's prefix (host/aijhip.c) */
   /* per-launch device timing for bench.py (hipEvent pairs on the compute stream) */
   PetscBool timing; PetscInt time_n, time_cap; mi355x_event_t *time_ev;
@@ -381,6 +386,12 @@ PetscErrorCode MatSeqAIJHIPSetCompressedRow(Mat A, PetscBool flg);
 PetscErrorCode MatAXPY_SeqAIJHIP_Cols(Mat Y, PetscScalar a, Mat X, MatStructure str, const PetscInt *xcols, const PetscInt *ycols, PetscBool checked);
 PetscErrorCode MatCopy_SeqAIJHIP_Cols(Mat A, Mat B, MatStructure str, const PetscInt *acols, const PetscInt *bcols, PetscBool checked);
 PetscErrorCode MatValueOpsCheck_SeqAIJHIP(Mat Y, Mat X, MatStructure str, const PetscInt *xcols, const PetscInt *ycols, PetscBool copy);
+/* the reductions over one block of an MPIAIJ matrix (host/aijhip.c, "Norms and row / column reductions"); route: 1 device, 2 host */
+PetscErrorCode MatReductionsRoute_SeqAIJHIP(Mat A, int *route);
+PetscErrorCode MatBlockRowReduce_SeqAIJHIP(Mat A, int route, int op, PetscInt ncols, PetscBool add, PetscScalar *out, PetscInt *idx);
+PetscErrorCode MatBlockColReduce_SeqAIJHIP(Mat A, int route, int op, PetscScalar *out_host);
+PetscErrorCode MatBlockSquareSum_SeqAIJHIP(Mat A, int route, PetscReal *s);
+PetscErrorCode HipDeviceMaxOf(const PetscScalar *x_dev, PetscInt n, PetscReal *val);
 PetscErrorCode MatSetUpMultiply_MPIAIJ(Mat mat);
 PetscErrorCode MatTimingBegin(Mat A, mi355x_handle_t h);
 PetscErrorCode MatTimingEnd(Mat A, mi355x_handle_t h);

@@ -346,6 +346,187 @@ static PetscErrorCode MatSOR_MPIAIJHIP(Mat A, Vec bb, PetscReal omega, MatSORTyp
   }
   return 0;
 }
+/* ---------------------------------------------------------------- Norms and row / column reductions (MatNorm_MPIAIJ, MatGetRowMaxAbs_MPIAIJ,
+ * MatGetRowMax_MPIAIJ, MatGetRowMin_MPIAIJ mpiaij.c; MatGetColumnNorms_MPIAIJ): through the blocks' own reductions (host/aijhip.c, either
+ * route as the diagonal block resolves -mat_hipmi355x_reductions) and the communicator's host collectives.
+ *   NORM_INFINITY   a row's sum of |a| runs over its diagonal-block entries and continues, from that value, over its off-diagonal-block
+ *                   entries (the ADD form; the compressed-row device copy of B through its row list); local maximum, one max all-reduce.
+ *                   A local quantity per row: the bits do not depend on the number of ranks' reduction order
+ *   NORM_FROBENIUS  the two blocks' sums of squares added, one sum all-reduce, the root
+ *   NORM_1, column norms   local column results into an array of the N global columns -- the diagonal block's at cstart + c, the
+ *                   off-diagonal block's at garray[c] --, one all-reduce of N doubles (sum; max for NORM_INFINITY), then the maximum / the roots
+ *   row max-abs / max / min   both blocks are reduced as parts of a matrix of N columns (a block's row is full only with N entries) and
+ *                   compete on the host: the larger (smaller) value wins, equal values go to the smaller global column; a row whose two
+ *                   blocks both end at the implicit zero, and a row that stores all N columns, is scanned over its merged columns in
+ *                   ascending global order -- the sequential contract itself.  Columns are global. */
+static PetscReal mpi_host_max_of(const PetscScalar *x, PetscInt n) {
+  if (n <= 0) return 0.0;
+  PetscReal m = x[0];
+  for (PetscInt k = 1; k < n; k++) if (x[k] > m) m = x[k];
+  return m;
+}
+/* the local column results of both blocks in an array of the N global columns (zero elsewhere) */
+static PetscErrorCode mpi_local_columns(Mat A, int route, int op, PetscScalar *glob) {
+  PetscErrorCode ierr;
+  HipMPIAIJ *a = MA(A);
+  const PetscInt nd = A->cmap->n, ec = a->ec, N = A->cmap->N, cstart = A->cmap->rstart;
+  PetscScalar *w;
+  ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(PetscMax(nd, ec), 1), &w);CHKERRQ(ierr);
+  for (PetscInt c = 0; c < N; c++) glob[c] = 0.0;
+  ierr = MatBlockColReduce_SeqAIJHIP(a->A, route, op, w);
+  if (!ierr) { for (PetscInt c = 0; c < nd; c++) glob[cstart + c] = w[c]; }
+  if (!ierr && ec > 0) {
+    ierr = MatBlockColReduce_SeqAIJHIP(a->B, route, op, w);
+    if (!ierr) for (PetscInt c = 0; c < ec; c++) glob[a->garray[c]] = w[c];
+  }
+  HipFree(w);
+  return ierr;
+}
+static PetscErrorCode MatNorm_MPIAIJHIP(Mat A, NormType type, PetscReal *nrm) {
+  PetscErrorCode ierr;
+  HipMPIAIJ *a = MA(A);
+  MPI_Comm comm = HipObjComm(A);
+  const PetscInt m = A->rmap->n, N = A->cmap->N;
+  int route;
+  if (type == NORM_2) SETERRQ(comm, PETSC_ERR_SUP, "No support for two norm");
+  if (type != NORM_1 && type != NORM_FROBENIUS && type != NORM_INFINITY) SETERRQ(comm, PETSC_ERR_ARG_OUTOFRANGE, "Unknown NormType %d", (int)type);
+  ierr = MatReductionsRoute_SeqAIJHIP(a->A, &route);CHKERRQ(ierr);
+  if (type == NORM_FROBENIUS) {
+    PetscReal s1, s2, s;
+    ierr = MatBlockSquareSum_SeqAIJHIP(a->A, route, &s1);CHKERRQ(ierr);
+    ierr = MatBlockSquareSum_SeqAIJHIP(a->B, route, &s2);CHKERRQ(ierr);
+    s = s1 + s2;
+    if (HipCommSize(comm) > 1 && HipCommAllreduce(comm, &s, 1, 1, 0)) SETERRQ(comm, PETSC_ERR_LIB, "allreduce failed");
+    *nrm = sqrt(s);
+  } else if (type == NORM_1) {
+    PetscScalar *glob;
+    ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(N, 1), &glob);CHKERRQ(ierr);
+    ierr = mpi_local_columns(A, route, MI355X_ROW_ABSSUM, glob);
+    if (!ierr && HipCommSize(comm) > 1 && N > 0 && HipCommAllreduce(comm, glob, (int)N, 1, 0)) { HipFree(glob); SETERRQ(comm, PETSC_ERR_LIB, "allreduce failed"); }
+    if (!ierr) *nrm = mpi_host_max_of(glob, N);
+    HipFree(glob);
+    CHKERRQ(ierr);
+  } else {
+    PetscReal v = 0.0;
+    if (route == 2) {
+      PetscScalar *w;
+      ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(m, 1), &w);CHKERRQ(ierr);
+      ierr = MatBlockRowReduce_SeqAIJHIP(a->A, 2, MI355X_ROW_ABSSUM, N, PETSC_FALSE, w, NULL);
+      if (!ierr) ierr = MatBlockRowReduce_SeqAIJHIP(a->B, 2, MI355X_ROW_ABSSUM, N, PETSC_TRUE, w, NULL);
+      if (!ierr) v = mpi_host_max_of(w, m);
+      HipFree(w);
+      CHKERRQ(ierr);
+    } else {
+      void *w = NULL;
+      CHKHIP(mi355x_malloc(&w, sizeof(PetscScalar) * (size_t)PetscMax(m, 2)));
+      ierr = MatBlockRowReduce_SeqAIJHIP(a->A, 1, MI355X_ROW_ABSSUM, N, PETSC_FALSE, (PetscScalar *)w, NULL);
+      if (!ierr) ierr = MatBlockRowReduce_SeqAIJHIP(a->B, 1, MI355X_ROW_ABSSUM, N, PETSC_TRUE, (PetscScalar *)w, NULL);
+      if (!ierr) ierr = HipDeviceMaxOf((const PetscScalar *)w, m, &v);
+      mi355x_free(w);
+      CHKERRQ(ierr);
+    }
+    if (HipCommSize(comm) > 1 && HipCommAllreduce(comm, &v, 1, 1, 1)) SETERRQ(comm, PETSC_ERR_LIB, "allreduce failed");
+    *nrm = v;
+  }
+  return 0;
+}
+static PetscErrorCode MatGetColumnNorms_MPIAIJHIP(Mat A, NormType type, PetscReal *norms) {
+  PetscErrorCode ierr;
+  MPI_Comm comm = HipObjComm(A);
+  const PetscInt N = A->cmap->N;
+  int route;
+  const int op = type == NORM_1 ? MI355X_ROW_ABSSUM : (type == NORM_2 ? MI355X_ROW_SQSUM : MI355X_ROW_MAXABS);
+  if (type != NORM_1 && type != NORM_2 && type != NORM_INFINITY) SETERRQ(comm, PETSC_ERR_ARG_WRONG, "Unknown NormType %d", (int)type);
+  ierr = MatReductionsRoute_SeqAIJHIP(MA(A)->A, &route);CHKERRQ(ierr);
+  ierr = mpi_local_columns(A, route, op, norms);CHKERRQ(ierr);
+  if (HipCommSize(comm) > 1 && N > 0 && HipCommAllreduce(comm, norms, (int)N, 1, type == NORM_INFINITY ? 1 : 0)) SETERRQ(comm, PETSC_ERR_LIB, "allreduce failed");
+  if (type == NORM_2) for (PetscInt c = 0; c < N; c++) norms[c] = sqrt(norms[c]);
+  return 0;
+}
+/* row r of the parallel matrix by the sequential contract over its merged columns (ascending global column) */
+static void mpi_row_scan(Mat A, int op, PetscInt r, PetscScalar *val, PetscInt *col) {
+  HipMPIAIJ *a = MA(A);
+  const HipAIJ *d = HipAIJGet(a->A), *o = HipAIJGet(a->B);
+  const PetscInt cstart = A->cmap->rstart, N = A->cmap->N;
+  PetscInt kd = d->i[r], ko = o->i[r];
+  const PetscInt ed = d->i[r + 1], eo = o->i[r + 1], n = (ed - kd) + (eo - ko);
+  const PetscBool full = (PetscBool)(n > 0 && n == N);
+  PetscScalar cur = 0.0; PetscInt best = -1, missing = -1, expect = 0;
+  for (PetscInt j = 0; j < n; j++) {
+    const PetscBool from_d = (PetscBool)(kd < ed && (ko >= eo || cstart + d->j[kd] < a->garray[o->j[ko]]));
+    const PetscInt c = from_d ? cstart + d->j[kd] : a->garray[o->j[ko]];
+    PetscScalar v = from_d ? d->a[kd++] : o->a[ko++];
+    if (op == MI355X_ROW_MAXABS) v = fabs(v);
+    if (missing < 0 && c != expect) missing = expect;
+    expect = c + 1;
+    if ((op != MI355X_ROW_MAXABS && j == 0 && full) || (op == MI355X_ROW_MIN ? v < cur : cur < v)) { cur = v; best = c; }
+  }
+  if (missing < 0) missing = n;                       /* columns 0 .. n - 1 are stored: the next one is the first missing */
+  *val = cur;
+  *col = best >= 0 ? best : ((op == MI355X_ROW_MAXABS || n == 0) ? 0 : missing);
+}
+static PetscErrorCode mpi_row_extremum(Mat A, int op, Vec v, PetscInt idx[]) {
+  PetscErrorCode ierr;
+  HipMPIAIJ *a = MA(A);
+  MPI_Comm comm = HipObjComm(A); (void)comm;
+  const HipAIJ *hd = HipAIJGet(a->A), *ho = HipAIJGet(a->B);
+  const PetscInt m = A->rmap->n, N = A->cmap->N, cstart = A->cmap->rstart;
+  const size_t mm = (size_t)PetscMax(m, 2);
+  PetscScalar *vd, *vo, *out; PetscInt *id, *io;
+  int route;
+  if (!v || !v->data || !strstr(HipObjTypeName(v), "hipmi355x")) SETERRQ(comm, PETSC_ERR_ARG_WRONG, "the result must be a HIPMI355X vector");
+  if (v->map->n != m) SETERRQ(comm, PETSC_ERR_ARG_SIZ, "Nonconforming matrix and vector");
+  ierr = MatReductionsRoute_SeqAIJHIP(a->A, &route);CHKERRQ(ierr);
+  ierr = PetscMalloc(2 * sizeof(PetscScalar) * mm + 2 * sizeof(PetscInt) * mm, &vd);CHKERRQ(ierr);
+  vo = vd + mm; id = (PetscInt *)(vo + mm); io = id + mm;
+  if (route == 2) {
+    ierr = MatBlockRowReduce_SeqAIJHIP(a->A, 2, op, N, PETSC_FALSE, vd, id);
+    if (!ierr) ierr = MatBlockRowReduce_SeqAIJHIP(a->B, 2, op, N, PETSC_FALSE, vo, io);
+  } else {
+    PetscDeviceCtx *dc; void *w = NULL;
+    ierr = PetscDeviceGet(&dc);
+    if (!ierr) {
+      int rc = mi355x_malloc(&w, 2 * sizeof(PetscScalar) * mm + 2 * sizeof(PetscInt) * mm);
+      if (rc) { HipFree(vd); CHKHIP(rc); }
+      PetscScalar *wd = (PetscScalar *)w, *wo = wd + mm; PetscInt *xd = (PetscInt *)(wo + mm), *xo = xd + mm;
+      ierr = MatBlockRowReduce_SeqAIJHIP(a->A, 1, op, N, PETSC_FALSE, wd, xd);
+      if (!ierr) ierr = MatBlockRowReduce_SeqAIJHIP(a->B, 1, op, N, PETSC_FALSE, wo, xo);
+      if (!ierr && m > 0) {
+        rc = mi355x_memcpy_d2h(dc->h, vd, w, 2 * sizeof(PetscScalar) * mm + 2 * sizeof(PetscInt) * mm);
+        if (!rc) rc = mi355x_handle_synchronize(dc->h);
+        if (rc) { mi355x_free(w); HipFree(vd); CHKHIP(rc); }
+      }
+      mi355x_free(w);
+    }
+  }
+  if (ierr) { HipFree(vd); CHKERRQ(ierr); }
+  ierr = VecGetArray(v, &out);
+  if (ierr) { HipFree(vd); CHKERRQ(ierr); }
+  for (PetscInt r = 0; r < m; r++) {
+    const PetscInt nd = hd->i[r + 1] - hd->i[r], no = ho->i[r + 1] - ho->i[r];
+    /* a block's value is 0.0 exactly when no stored entry of it won: max-abs 0.0 at column 0, max / min the implicit zero (a stored
+     * +-0.0 never replaces the start, and no block row is full unless the whole row lies in it) */
+    PetscScalar val; PetscInt col;
+    if ((vd[r] == 0.0 && vo[r] == 0.0) || (nd + no == N && N > 0) || vd[r] != vd[r] || vo[r] != vo[r]) mpi_row_scan(A, op, r, &val, &col);
+    else {
+      const PetscInt cd = cstart + id[r], co = no > 0 ? a->garray[io[r]] : 0;
+      PetscBool take_o;
+      if (vd[r] == 0.0) take_o = PETSC_TRUE;               /* the diagonal block offers its start only: the other block's stored entry beat 0.0 */
+      else if (vo[r] == 0.0) take_o = PETSC_FALSE;
+      else if (vd[r] == vo[r]) take_o = (PetscBool)(co < cd);
+      else take_o = (PetscBool)(op == MI355X_ROW_MIN ? vo[r] < vd[r] : vd[r] < vo[r]);
+      val = take_o ? vo[r] : vd[r]; col = take_o ? co : cd;
+    }
+    out[r] = val;
+    if (idx) idx[r] = col;
+  }
+  HipFree(vd);
+  return VecRestoreArray(v, &out);
+}
+static PetscErrorCode MatGetRowMaxAbs_MPIAIJHIP(Mat A, Vec v, PetscInt idx[]) { return mpi_row_extremum(A, MI355X_ROW_MAXABS, v, idx); }
+static PetscErrorCode MatGetRowMax_MPIAIJHIP(Mat A, Vec v, PetscInt idx[]) { return mpi_row_extremum(A, MI355X_ROW_MAX, v, idx); }
+static PetscErrorCode MatGetRowMin_MPIAIJHIP(Mat A, Vec v, PetscInt idx[]) { return mpi_row_extremum(A, MI355X_ROW_MIN, v, idx); }
+
 static PetscErrorCode mpi_value_op_pair(Mat Y, Mat X) {
   if (!X || strcmp(HipObjTypeName(X), MATMPIAIJHIPMI355X) || strcmp(HipObjTypeName(Y), MATMPIAIJHIPMI355X)) SETERRQ(HipObjComm(Y), PETSC_ERR_SUP, "both matrices must be MPIAIJHIPMI355X matrices");
   if (X->rmap->rstart != Y->rmap->rstart || X->rmap->rend != Y->rmap->rend || X->cmap->rstart != Y->cmap->rstart || X->cmap->rend != Y->cmap->rend)
@@ -439,6 +620,11 @@ PetscErrorCode MatCreate_MPIAIJHIPMI355X(Mat B) {   /* MatCreate_MPIAIJCUSP, mpi
   B->ops->setoption = MatSetOption_MPIAIJHIP;
   B->ops->sor = MatSOR_MPIAIJHIP;
   B->ops->diagonalscale = MatDiagonalScale_MPIAIJHIP;
+  B->ops->norm = MatNorm_MPIAIJHIP;
+  B->ops->getrowmaxabs = MatGetRowMaxAbs_MPIAIJHIP;
+  B->ops->getrowmax = MatGetRowMax_MPIAIJHIP;
+  B->ops->getrowmin = MatGetRowMin_MPIAIJHIP;
+  B->ops->getcolumnnorms = MatGetColumnNorms_MPIAIJHIP;
   B->ops->destroy = MatDestroy_MPIAIJHIP;
   B->ops->getvecs = MatGetVecs_HIPMI355X;
   ierr = PetscObjectComposeFunction((PetscObject)B, "MatMPIAIJSetPreallocation_C", "MatMPIAIJSetPreallocation_MPIAIJHIP", (PetscVoidFunction)MatMPIAIJSetPreallocation_MPIAIJHIP);CHKERRQ(ierr);

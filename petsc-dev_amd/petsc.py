@@ -52,6 +52,8 @@ _SIG = {
     "MatShift": [vp, dbl], "MatAXPY": [vp, dbl, vp, i32], "MatAYPX": [vp, dbl, vp, i32], "MatCopy": [vp, vp, i32],
     "MatZeroRows": [vp, i32, vp, dbl, vp, vp], "MatZeroRowsColumns": [vp, i32, vp, dbl, vp, vp], "MatSetOption": [vp, i32, i32],
     "MatHIPMI355XGetZeroRowsCounts": [vp, P(i32), P(i32)],
+    "MatNorm": [vp, i32, P(dbl)], "MatGetRowMaxAbs": [vp, vp, vp], "MatGetRowMax": [vp, vp, vp], "MatGetRowMin": [vp, vp, vp],
+    "MatGetRowSum": [vp, vp], "MatGetColumnNorms": [vp, i32, vp],
     "MatMatMult": [vp, vp, i32, dbl, P(vp)], "MatMatMultSymbolic": [vp, vp, dbl, P(vp)], "MatMatMultNumeric": [vp, vp, vp],
     "MatTranspose": [vp, i32, P(vp)], "MatPtAP": [vp, vp, i32, dbl, P(vp)], "MatHIPMI355XGetProductCounts": [vp, P(i32), P(i32), P(i32)],
     "MatSOR": [vp, vp, dbl, i32, dbl, i32, i32, vp], "MatHIPMI355XGetSORInfo": [vp, P(i32), P(i32), P(i32), P(i32), P(i32)],
@@ -328,6 +330,44 @@ class Mat:
         """zero the listed rows and columns, diag on the diagonal, b corrected by the eliminated entries (MatZeroRowsColumns)"""
         r, n, p = self._rows(rows)
         lib().MatZeroRowsColumns(self.h, n, p, diag, x.h if x is not None else None, b.h if b is not None else None)
+
+    def norm(self, kind=NORM_FROBENIUS):
+        """NORM_1, NORM_FROBENIUS or NORM_INFINITY of the matrix (MatNorm)"""
+        r = dbl()
+        lib().MatNorm(self.h, kind, C.byref(r))
+        return r.value
+
+    def _row_extremum(self, name):
+        _, v = self.get_vecs()
+        idx = np.full(max(v.n, 1), -1, np.int32)
+        getattr(lib(), name)(self.h, v.h, _ptr(idx))
+        return v, idx[:v.n]
+
+    def row_max_abs(self):
+        """(Vec of max_j |a_ij|, ndarray of the columns they were found at) (MatGetRowMaxAbs)"""
+        return self._row_extremum("MatGetRowMaxAbs")
+
+    def row_max(self):
+        """(Vec of the rows' largest entries, an implicit zero included, ndarray of their columns) (MatGetRowMax)"""
+        return self._row_extremum("MatGetRowMax")
+
+    def row_min(self):
+        """(Vec of the rows' smallest entries, an implicit zero included, ndarray of their columns) (MatGetRowMin)"""
+        return self._row_extremum("MatGetRowMin")
+
+    def row_sum(self):
+        """Vec of the row sums: the product with a vector of ones (MatGetRowSum)"""
+        _, v = self.get_vecs()
+        lib().MatGetRowSum(self.h, v.h)
+        return v
+
+    def column_norms(self, kind=NORM_2):
+        """ndarray of the NORM_1, NORM_2 or NORM_INFINITY norms of all columns (MatGetColumnNorms)"""
+        n = i32()
+        lib().MatGetSize(self.h, None, C.byref(n))
+        out = np.zeros(max(n.value, 1))
+        lib().MatGetColumnNorms(self.h, kind, _ptr(out))
+        return out[:n.value]
 
     def set_option(self, op, flag=True):
         lib().MatSetOption(self.h, op, 1 if flag else 0)
