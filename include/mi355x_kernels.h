@@ -266,6 +266,12 @@ int mi355x_vec_mdot(mi355x_handle_t h, size_t n, int nv, const double *x, const 
 int mi355x_vec_maxpy_dev_norm2(mi355x_handle_t h, size_t n, int nv, const double *coef_dev, double sign, const double *const *y,
                                double *x, double *out);
 int mi355x_vec_scale_rnorm_dev(mi355x_handle_t h, size_t n, const double *norm2_dev, double *x);
+/* KSPFGMRESCycle fusion: mi355x_vec_scale_rnorm_dev (same rules: x is stored unless the norm is 0 or 1 or alpha == 1; alpha == 0 stores
+ * zeros) and, from the registers of the same pass, z[i] = x_new[i] * d[i] (d == NULL: z[i] = x_new[i]) for all n entries -- the bits of
+ * VecScale followed by VecPointwiseMult (PCApply_Jacobi) or VecCopy (PCApply_None).  One read of n doubles and one launch fewer than
+ * the two calls.  hipErrorInvalidValue and nothing touched for a NULL norm2_dev, x or z, and for z == x, z == d or d == x; n == 0 launches
+ * nothing.  *norm2_dev may be written by the launch queued before this one on the same stream, not while this one runs. */
+int mi355x_vec_scale_rnorm_dev_pmult(mi355x_handle_t h, size_t n, const double *norm2_dev, double *x, const double *d, double *z);
 /* VecSum              src/vec/vec/utils/vinv.c (VecSum)    out[0] = sum x_i.  DotF's lanes, order and streaming threshold with
  * y == 1.0: the bits of mi355x_vec_dot(x, ones) for any alignment of x; for a 16-byte aligned x also the bits of the oracle's device-order
  * dot (the oracle restates the aligned tree only; a view off a 16-byte boundary takes the scalar grid-stride loop, another fixed

@@ -42,6 +42,7 @@ extern "C" {
 #define KSPBICGHIPMI355X    "bicghipmi355x"            /* KSPBICG with two sweeps per iteration ("VecBicgFusedOps_C", -ksp_bicg_fused <bool>); on other vectors the same function runs op by op */
 #define KSPCGSHIPMI355X     "cgshipmi355x"             /* KSPCGS on the same three sweeps */
 #define KSPMINRESHIPMI355X  "minreshipmi355x"          /* KSPMINRES with two sweeps per iteration; needs vectors that offer "VecMinresFusedOps_C": PETSC_ERR_SUP at set-up otherwise */
+#define KSPFGMRESHIPMI355X  "fgmreshipmi355x"          /* KSPFGMRES with one host wait per step; with PCNONE / PCJACOBI the normalising sweep writes the next preconditioned direction as well ("VecFgmresFusedOps_C", -ksp_fgmres_fused <bool>, default false); on other vectors the same function runs op by op */
 
 /* One call after PetscInitialize (or a PetscDLLibraryRegister entry, src/sys/dll): registers the types above with
  * VecRegister / MatRegister / PCRegister.  On the harness the same constructors are also registered under the

@@ -127,6 +127,17 @@ typedef struct {
                                 PetscBool *done);
 } VecLsqrFusedOps;
 typedef const VecLsqrFusedOps *(*VecLsqrFusedOpsGetFn)(void);
+/* "VecFgmresFusedOps_C" on a Vec returns the Gram-Schmidt step of flexible GMRES (KSPFGMRESCycle, fgmres.c), a seventh table */
+typedef struct {
+  /* gmres_orthog_normalize of "VecKrylovFusedOps_C" (dots[j] = <w, V_j>, w -= sum_j dots[j] V_j, *nrm = |w|, w *= 1 / |w| under
+   * VecNormalize's rules) whose last sweep also writes the next step's preconditioned direction from the values it holds:
+   * z = d .* w_new (PCApply_Jacobi), or z = w_new with identity set (PCApply_None; d is not looked at).  The bits of the separate calls;
+   * one host wait.  *done = PETSC_FALSE and nothing touched for vectors of another type, unequal local sizes, nv < 1 or nv > 32,
+   * host-staged vectors, or a z or d that is w or one of the V_j.  On several ranks the sums are all-reduced on the device. */
+  PetscErrorCode (*fgmres_orthog_normalize_pc)(Vec w, PetscInt nv, const Vec V[], Vec d, PetscBool identity, Vec z, PetscScalar *dots, PetscReal *nrm,
+                                               PetscBool *done);
+} VecFgmresFusedOps;
+typedef const VecFgmresFusedOps *(*VecFgmresFusedOpsGetFn)(void);
 typedef PetscErrorCode (*MatMultTDotBeginFn)(Mat A, Vec x, Vec y, PetscBool *ok);
 typedef PetscErrorCode (*MatMultDiagonalScaleFn)(Mat A, Vec d, Vec x, Vec y, PetscBool *ok);
 

@@ -141,6 +141,7 @@ typedef const char *PCType;
 #define KSPCGS     "cgs"       /* conjugate gradient squared (src/ksp/ksp/impls/cgs/cgs.c) */
 #define KSPLSQR    "lsqr"      /* least squares for rectangular operators: A v and A^T u per iteration (src/ksp/ksp/impls/lsqr/lsqr.c) */
 #define KSPBICG    "bicg"      /* biconjugate gradients: A^T p and B^T r per iteration (src/ksp/ksp/impls/bicg/bicg.c) */
+#define KSPFGMRES  "fgmres"    /* flexible GMRES: right preconditioning with a preconditioner that may change from step to step (src/ksp/ksp/impls/gmres/fgmres/fgmres.c) */
 #define PCNONE     "none"
 #define PCJACOBI   "jacobi"
 #define PCBJACOBI  "bjacobi"
@@ -148,6 +149,7 @@ typedef const char *PCType;
 #define PCILU      "ilu"       /* ILU(0), natural ordering, sequential AIJ */
 #define PCICC      "icc"       /* ICC(0), natural ordering, sequential AIJ */
 #define PCSOR      "sor"       /* SOR / SSOR through the operator's MatSOR (src/ksp/pc/impls/sor/sor.c) */
+#define PCKSP      "ksp"       /* a Krylov solver as the preconditioner: every application is a KSPSolve of the inner KSP (src/ksp/pc/impls/ksp/pcksp.c) */
 
 /* ---- Sys ----------------------------------------------------------------------------------- */
 extern PetscComm PETSC_COMM_SELF, PETSC_COMM_WORLD;
@@ -373,6 +375,11 @@ PetscErrorCode PCDestroy(PC *pc);
 PetscErrorCode PCFactorSetLevels(PC pc, PetscInt levels);   /* levels of fill of a PCILU / PCICC (factor.c PCFactorSetLevels; -pc_factor_levels); a changed level after set-up has the next set-up redo the symbolic phase */
 PetscErrorCode PCFactorGetMatrix(PC pc, Mat *mat);   /* the factored matrix of a PCILU / PCICC (precon.c PCFactorGetMatrix) */
 PetscErrorCode PCBJacobiGetSubKSP(PC pc, PetscInt *n_local, PetscInt *first_local, KSP **ksp);
+/* pcksp.c.  The inner solver of a PCKSP, created at the first call or at set-up on the PC's communicator with the options prefix
+ * "<pc prefix>ksp_" (-ksp_ksp_type, -ksp_pc_type, -ksp_ksp_max_it ...); not owned by the caller.  GetTotalIterations: the inner iterations of
+ * all applications so far.  Both return PETSC_ERR_ARG_WRONG for a PC of another type. */
+PetscErrorCode PCKSPGetKSP(PC pc, KSP *ksp);
+PetscErrorCode PCKSPGetTotalIterations(PC pc, PetscInt *n);
 
 /* ---- KSP (include/petscksp.h) ---------------------------------------------------------------- */
 PetscErrorCode KSPCreate(PetscComm comm, KSP *ksp);
@@ -381,9 +388,10 @@ PetscErrorCode KSPGetType(KSP ksp, KSPType *type);
 PetscErrorCode KSPSetOperators(KSP ksp, Mat Amat, Mat Pmat, MatStructure flag);
 PetscErrorCode KSPGetPC(KSP ksp, PC *pc);
 PetscErrorCode KSPSetTolerances(KSP ksp, PetscReal rtol, PetscReal abstol, PetscReal dtol, PetscInt maxits);
+PetscErrorCode KSPGetTolerances(KSP ksp, PetscReal *rtol, PetscReal *abstol, PetscReal *dtol, PetscInt *maxits);   /* any pointer may be NULL */
 PetscErrorCode KSPSetInitialGuessNonzero(KSP ksp, PetscBool flg);
 PetscErrorCode KSPSetNormType(KSP ksp, KSPNormType normtype);
-PetscErrorCode KSPSetPCSide(KSP ksp, PCSide side);   /* -ksp_pc_side <left|right>; right: KSPGMRES only */
+PetscErrorCode KSPSetPCSide(KSP ksp, PCSide side);   /* -ksp_pc_side <left|right>; right: the GMRES types, and the only side of KSPFGMRES */
 /* itfunc.c KSPSetNullSpace: removed from the result of every preconditioner application while the preconditioner is on the left
  * (kspimpl.h KSP_RemoveNullSpace); the KSP keeps a reference; NULL takes it away again */
 PetscErrorCode KSPSetNullSpace(KSP ksp, MatNullSpace nullsp);
@@ -392,6 +400,12 @@ PetscErrorCode KSPSetOptionsPrefix(KSP ksp, const char prefix[]);
 PetscErrorCode KSPSetFromOptions(KSP ksp);   /* -ksp_type -ksp_rtol -ksp_atol -ksp_max_it -ksp_gmres_restart -ksp_gmres_cgs_refinement_type -pc_type -sub_* */
 PetscErrorCode KSPGMRESSetRestart(KSP ksp, PetscInt restart);
 PetscErrorCode KSPGMRESSetCGSRefinementType(KSP ksp, KSPGMRESCGSRefinementType type);
+/* fgmres.c.  PetscTryMethod on "KSPFGMRESSetModifyPC_C": fcn(ksp, total_its, loc_its, res_norm, ctx) runs before every preconditioner
+ * application of the flexible GMRES types (total_its: iterations so far, loc_its: position in the restart cycle, res_norm: the current
+ * residual norm) and may change the preconditioner; d (may be NULL) releases ctx when the routine is replaced or the KSP destroyed.
+ * KSPFGMRESModifyPCNoChange, the default, does nothing.  Any other KSP type ignores the call. */
+PetscErrorCode KSPFGMRESSetModifyPC(KSP ksp, PetscErrorCode (*fcn)(KSP, PetscInt, PetscInt, PetscReal, void *), void *ctx, PetscErrorCode (*d)(void *));
+PetscErrorCode KSPFGMRESModifyPCNoChange(KSP ksp, PetscInt total_its, PetscInt loc_its, PetscReal res_norm, void *ctx);
 /* cheby.c / rich.c: PetscTryMethod on "KSPChebychevSetEigenvalues_C" / "KSPRichardsonSetScale_C" -- a type that composed the method
  * answers, any other type ignores the call.  Options: -ksp_chebychev_eigenvalues <emin,emax>, -ksp_richardson_scale <s> */
 PetscErrorCode KSPChebychevSetEigenvalues(KSP ksp, PetscReal emax, PetscReal emin);

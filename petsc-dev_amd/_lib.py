@@ -69,6 +69,7 @@ KERNEL_API = {
     "mi355x_vec_mdot": [vp, sz, i32, vp, C.POINTER(vp), vp],
     "mi355x_vec_maxpy_dev_norm2": [vp, sz, i32, vp, C.c_double, C.POINTER(vp), vp, vp],
     "mi355x_vec_scale_rnorm_dev": [vp, sz, vp, vp],
+    "mi355x_vec_scale_rnorm_dev_pmult": [vp, sz, vp, vp, vp, vp],
     "mi355x_vec_cg_update": [vp, sz, dbl, vp, vp, vp, vp, vp, vp, vp],
     "mi355x_vec_aypx_dev": [vp, sz, vp, dbl, vp, vp],
     "mi355x_vec_pmult_dot": [vp, sz, vp, vp, vp, vp, vp],

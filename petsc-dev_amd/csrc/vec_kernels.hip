@@ -1601,6 +1601,39 @@ __global__ __launch_bounds__(MI355X_BLOCK) void scale_rnorm_dev_kernel(const dou
     [&](size_t k) { x[k] = scaled(x[k]); });
 }
 
+// scale_rnorm_dev_kernel and, in the same pass, z = d .* x_new (d == NULL: z = x_new): gmres.c:146's VecNormalize followed by the
+// PCApply_Jacobi / PCApply_None of the NEXT flexible-GMRES step (VecPointwiseMult / VecCopy), whose input is still in registers.
+// x is stored under the rules above only (a norm of 0 or 1, alpha == 1: not stored); z is written for every entry.
+__global__ __launch_bounds__(MI355X_BLOCK) void scale_rnorm_dev_pmult_kernel(const double *norm2, double *x, const double *d, double *z, size_t n, int vec_ok) {
+  const double nrm = sqrt(*norm2);
+  const double alpha = 1.0 / nrm;
+  const bool keep = nrm == 0.0 || nrm == 1.0 || alpha == 1.0;
+  const auto scaled = [=](double v) { return alpha == 0.0 ? 0.0 : v * alpha; };
+  double2 *x2 = reinterpret_cast<double2 *>(x), *z2 = reinterpret_cast<double2 *>(z);
+  const double2 *d2 = reinterpret_cast<const double2 *>(d);
+  tile_walk<2>(n, vec_ok,
+    [&](size_t i, auto u) {
+      constexpr int U = decltype(u)::value;
+      double2 v[U], dv[U] = {};
+      ld_tile<false>(x2, i, v);
+      if (d) ld_tile<false>(d2, i, dv);
+      if (!keep) {
+        for (double2 &e : v) { e.x = scaled(e.x); e.y = scaled(e.y); }
+        st_tile<false>(x2, i, v);
+      }
+      if (d) {
+#pragma unroll
+        for (int j = 0; j < U; ++j) { v[j].x = v[j].x * dv[j].x; v[j].y = v[j].y * dv[j].y; }
+      }
+      st_tile<false>(z2, i, v);
+    },
+    [&](size_t k) {
+      double v = x[k];
+      if (!keep) { v = scaled(v); x[k] = v; }
+      z[k] = d ? v * d[k] : v;
+    });
+}
+
 template <int NV>
 static int launch_mdot(mi355x_handle_t h, size_t n, const double *x, const double *const *y, double *out) {
   MDotF<NV> f;
@@ -1924,6 +1957,14 @@ int mi355x_vec_scale_rnorm_dev(mi355x_handle_t h, size_t n, const double *norm2_
   if (n == 0) return 0;
   const int vec_ok = all_aligned16(x);
   hipLaunchKernelGGL(scale_rnorm_dev_kernel, dim3(tile_grid<2>(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, norm2_dev, x, n, vec_ok);
+  MI355X_LAUNCH_CHECK();
+  return 0;
+}
+int mi355x_vec_scale_rnorm_dev_pmult(mi355x_handle_t h, size_t n, const double *norm2_dev, double *x, const double *d, double *z) {
+  if (!norm2_dev || !x || !z || z == x || z == d || d == x) return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  const int vec_ok = all_aligned16(x, d, z);
+  hipLaunchKernelGGL(scale_rnorm_dev_pmult_kernel, dim3(tile_grid<2>(n, vec_ok)), dim3(MI355X_BLOCK), 0, h->stream, norm2_dev, x, d, z, n, vec_ok);
   MI355X_LAUNCH_CHECK();
   return 0;
 }

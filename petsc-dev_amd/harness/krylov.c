@@ -18,6 +18,7 @@
  *   CGS           src/ksp/ksp/impls/cgs/cgs.c (KSPSolve_CGS)
  *   BiCG          src/ksp/ksp/impls/bicg/bicg.c (KSPSolve_BiCG)
  *   LSQR          src/ksp/ksp/impls/lsqr/lsqr.c (KSPSolve_LSQR; the contract is the sequence stated in DESIGN.md section 4)
+ *   FGMRES(m)     src/ksp/ksp/impls/gmres/fgmres/fgmres.c (the contract is the sequence stated in DESIGN.md section 4, restated without the source)
  * and are written here over a few shared pieces: one checkpoint routine (history, monitor, convergence test), one start-residual
  * routine for the CG family, index-addressed Hessenberg columns for GMRES. */
 #include "petscimpl.h"
@@ -326,12 +327,17 @@ typedef struct {
   KSPGMRESCGSRefinementType refinement;
   PetscScalar *H, *giv_c, *giv_s, *rot_rhs, *coef, *y;
   Vec *pool;
-  PetscInt npool;
+  PetscInt npool, nscratch;           /* vectors of the pool in front of the basis: GMRES 2 (update, scratch), FGMRES 1 (update) */
+  /* FGMRES only: the preconditioned directions Z[k] = B_k V[k] and the routine that may change B before every application */
+  Vec *Z;
+  PetscErrorCode (*modifypc)(KSP, PetscInt, PetscInt, PetscReal, void *);
+  void *modifyctx;
+  PetscErrorCode (*modifydestroy)(void *);
 } GmresData;
 #define GMD(ksp) ((GmresData *)(ksp)->data)
 #define UPDATE(g) ((g)->pool[0])
 #define SCRATCH(g) ((g)->pool[1])
-#define BASIS(g) ((g)->pool + 2)
+#define BASIS(g) ((g)->pool + (g)->nscratch)
 
 static PetscErrorCode KSPGMRESSetRestart_GMRES(KSP ksp, PetscInt restart) {   /* gmres.c:752-770 */
   if (restart < 1) SETERRQ(ksp->comm, PETSC_ERR_ARG_OUTOFRANGE, "Restart must be positive");
@@ -369,7 +375,7 @@ static PetscErrorCode KSPSetUp_GMRES(KSP ksp) {   /* gmres.c:36-96; the whole ba
   g->rot_rhs = host; host += m + 2;
   g->coef = host; host += m + 2;
   g->y = host;
-  g->npool = g->restart + 4;
+  g->npool = g->restart + 1 + g->nscratch;
   if (ksp->vec_sol) return VecDuplicateVecs(ksp->vec_sol, g->npool, &g->pool);
   Vec like;
   OK(MatGetVecs(ksp->pc->mat, &like, NULL));
@@ -524,6 +530,7 @@ PetscErrorCode KSPCreate_GMRES(KSP ksp) {   /* defaults of the reference's const
   g->restart = 30;
   g->happy_tol = 1.0e-30;
   g->refinement = KSP_GMRES_CGS_REFINE_NEVER;
+  g->nscratch = 2;
   ksp->data = g;
   ksp->normsupporttable[KSP_NORM_PRECONDITIONED][PC_LEFT] = 2;      /* gmres.c:909-910 */
   ksp->normsupporttable[KSP_NORM_UNPRECONDITIONED][PC_RIGHT] = 1;
@@ -533,6 +540,137 @@ PetscErrorCode KSPCreate_GMRES(KSP ksp) {   /* defaults of the reference's const
   ksp->ops->setfromoptions = KSPSetFromOptions_GMRES;
   OK(PetscObjectComposeFunction((PetscObject)ksp, "KSPGMRESSetRestart_C", "KSPGMRESSetRestart_GMRES", (PetscVoidFunction)KSPGMRESSetRestart_GMRES));   /* gmres.c:931-942 */
   OK(PetscObjectComposeFunction((PetscObject)ksp, "KSPGMRESSetCGSRefinementType_C", "KSPGMRESSetCGSRefinementType_GMRES", (PetscVoidFunction)KSPGMRESSetCGSRefinementType_GMRES));
+  return 0;
+}
+
+/* ================================================================== flexible GMRES(m): right preconditioning with a preconditioner that
+ * may change from step to step (fgmres.c).  The sequence is the one DESIGN.md section 4 states -- it was restated without the reference's
+ * source at hand.  GMRES's state with one scratch vector fewer and, beside the basis V[0..m], the preconditioned directions Z[0..m-1]:
+ * Z[k] = B_k V[k] is kept, so the update is x += Z y and nothing is unwound through a preconditioner that may have changed meanwhile.
+ * Gram-Schmidt and the rotations are GMRES's own routines; the norm is the true residual's. */
+PetscErrorCode KSPFGMRESModifyPCNoChange(KSP ksp, PetscInt total_its, PetscInt loc_its, PetscReal res_norm, void *ctx) {
+  (void)ksp; (void)total_its; (void)loc_its; (void)res_norm; (void)ctx;
+  return 0;
+}
+static PetscErrorCode KSPFGMRESSetModifyPC_FGMRES(KSP ksp, PetscErrorCode (*fcn)(KSP, PetscInt, PetscInt, PetscReal, void *), void *ctx, PetscErrorCode (*d)(void *)) {
+  GmresData *g = GMD(ksp);
+  if (g->modifydestroy) OK((*g->modifydestroy)(g->modifyctx));
+  g->modifypc = fcn ? fcn : KSPFGMRESModifyPCNoChange;
+  g->modifyctx = ctx;
+  g->modifydestroy = d;
+  return 0;
+}
+
+static PetscErrorCode KSPSetUp_FGMRES(KSP ksp) {   /* V[0..m], Z[0..m-1] and the update vector, all up front */
+  GmresData *g = GMD(ksp);
+  OK(KSPSetUp_GMRES(ksp));
+  return VecDuplicateVecs(UPDATE(g), g->restart, &g->Z);
+}
+
+/* V[0] = b - A x: the true residual, nothing preconditioned */
+static PetscErrorCode fgmres_residual(KSP ksp) {
+  Vec v0 = BASIS(GMD(ksp))[0];
+  OK(KSP_MatMult(ksp, ksp->pc->mat, ksp->vec_sol, v0));
+  return VecAYPX(v0, -1.0, ksp->vec_rhs);
+}
+
+/* x += Z y with R y = rotated right-hand side over the first n columns; a zero last pivot gives y[n-1] = 0 instead of a break-down */
+static PetscErrorCode fgmres_update_solution(KSP ksp, PetscInt n) {
+  GmresData *g = GMD(ksp);
+  const size_t ld = (size_t)g->ld;
+  PetscScalar *y = g->y;
+  if (n < 1) return 0;
+  y[n - 1] = g->H[(size_t)(n - 1) * ld + (size_t)(n - 1)] != 0.0 ? g->rot_rhs[n - 1] / g->H[(size_t)(n - 1) * ld + (size_t)(n - 1)] : 0.0;
+  for (PetscInt r = n - 2; r >= 0; r--) {
+    PetscScalar acc = g->rot_rhs[r];
+    for (PetscInt j = r + 1; j < n; j++) acc = acc - g->H[(size_t)j * ld + r] * y[j];
+    y[r] = acc / g->H[(size_t)r * ld + r];
+  }
+  OK(VecSet(UPDATE(g), 0.0));
+  OK(VecMAXPY(UPDATE(g), n, y, g->Z));
+  return VecAXPY(ksp->vec_sol, 1.0, UPDATE(g));
+}
+
+/* one restart cycle from the residual in V[0].  The history sees a step's norm when the next step starts and once more when the
+ * cycle ends; the monitor runs at the head of every step and once after the last one of the solve. */
+static PetscErrorCode fgmres_cycle(KSP ksp) {
+  GmresData *g = GMD(ksp);
+  Vec *V = BASIS(g), *Z = g->Z;
+  PetscReal rn, tt, hapbnd;
+  PetscBool hapend = PETSC_FALSE;
+  PetscInt k = 0;
+
+  OK(VecNorm(V[0], NORM_2, &rn));
+  g->rot_rhs[0] = rn;
+  ksp->rnorm = rn;
+  KSPLogResidualHistory(ksp, rn);
+  OK((*ksp->converged)(ksp, ksp->its, rn, &ksp->reason, ksp->cnvP));
+  if (ksp->reason) return 0;                                         /* no step, no monitor call, x as it is */
+  OK(VecScale(V[0], 1.0 / rn));
+  while (!ksp->reason && k < g->restart && ksp->its < ksp->max_it) {
+    if (k) KSPLogResidualHistory(ksp, rn);
+    OK(KSPMonitor(ksp, ksp->its, rn));
+    OK((*g->modifypc)(ksp, ksp->its, k, rn, g->modifyctx));
+    OK(KSP_PCApply(ksp, V[k], Z[k]));
+    OK(KSP_MatMult(ksp, ksp->pc->mat, Z[k], V[k + 1]));
+    OK(gmres_orthogonalize(ksp, k));
+    OK(VecNorm(V[k + 1], NORM_2, &tt));
+    g->H[(size_t)k * (size_t)g->ld + k + 1] = tt;
+    hapbnd = PetscAbsScalar(tt / g->rot_rhs[k]);
+    if (hapbnd > g->happy_tol) hapbnd = g->happy_tol;
+    if (tt > hapbnd) OK(VecScale(V[k + 1], 1.0 / tt));
+    else hapend = PETSC_TRUE;
+    OK(gmres_rotate(ksp, k, hapend, &rn));
+    if (ksp->reason) break;                                          /* a rotation of length 0: the column does not count */
+    k++;
+    ksp->its++;
+    ksp->rnorm = rn;
+    OK((*ksp->converged)(ksp, ksp->its, rn, &ksp->reason, ksp->cnvP));
+    if (hapend) {
+      if (!ksp->reason) SETERRQ(ksp->comm, PETSC_ERR_PLIB, "You reached the happy break down, but convergence was not indicated. Residual norm = %g", rn);
+      break;
+    }
+  }
+  KSPLogResidualHistory(ksp, rn);
+  if (ksp->reason || ksp->its >= ksp->max_it) OK(KSPMonitor(ksp, ksp->its, rn));
+  return fgmres_update_solution(ksp, k);
+}
+
+static PetscErrorCode KSPSolve_FGMRES(KSP ksp) {
+  ksp->its = 0;
+  ksp->reason = KSP_CONVERGED_ITERATING;
+  if (ksp->guess_zero) OK(VecCopy(ksp->vec_rhs, BASIS(GMD(ksp))[0]));
+  else OK(fgmres_residual(ksp));
+  OK(fgmres_cycle(ksp));
+  while (!ksp->reason) {
+    OK(fgmres_residual(ksp));
+    if (ksp->its >= ksp->max_it) break;
+    OK(fgmres_cycle(ksp));
+  }
+  if (ksp->its >= ksp->max_it && !ksp->reason) ksp->reason = KSP_DIVERGED_ITS;
+  return 0;
+}
+
+static PetscErrorCode KSPDestroy_FGMRES(KSP ksp) {
+  GmresData *g = GMD(ksp);
+  if (!g) return 0;
+  if (g->Z) OK(VecDestroyVecs(g->restart, &g->Z));
+  if (g->modifydestroy) OK((*g->modifydestroy)(g->modifyctx));
+  (void)PetscObjectComposeFunction((PetscObject)ksp, "KSPFGMRESSetModifyPC_C", "", (PetscVoidFunction)NULL);
+  return KSPDestroy_GMRES(ksp);
+}
+
+PetscErrorCode KSPCreate_FGMRES(KSP ksp) {   /* GMRES's defaults; right preconditioning only, the norm of the true residual or none */
+  OK(KSPCreate_GMRES(ksp));
+  GMD(ksp)->nscratch = 1;
+  GMD(ksp)->modifypc = KSPFGMRESModifyPCNoChange;
+  memset(ksp->normsupporttable, 0, sizeof(ksp->normsupporttable));
+  ksp->normsupporttable[KSP_NORM_UNPRECONDITIONED][PC_RIGHT] = 2;
+  ksp->normsupporttable[KSP_NORM_NONE][PC_RIGHT] = 1;
+  ksp->ops->setup = KSPSetUp_FGMRES;
+  ksp->ops->solve = KSPSolve_FGMRES;
+  ksp->ops->destroy = KSPDestroy_FGMRES;
+  OK(PetscObjectComposeFunction((PetscObject)ksp, "KSPFGMRESSetModifyPC_C", "KSPFGMRESSetModifyPC_FGMRES", (PetscVoidFunction)KSPFGMRESSetModifyPC_FGMRES));
   return 0;
 }
 

@@ -110,6 +110,14 @@ PetscErrorCode KSPSetTolerances(KSP ksp, PetscReal rtol, PetscReal abstol, Petsc
   if (maxits != PETSC_DEFAULT) { if (maxits < 0) SETERRQ(ksp->comm, PETSC_ERR_ARG_OUTOFRANGE, "Maximum number of iterations %d must be non-negative", maxits); ksp->max_it = maxits; }
   return 0;
 }
+PetscErrorCode KSPGetTolerances(KSP ksp, PetscReal *rtol, PetscReal *abstol, PetscReal *dtol, PetscInt *maxits) {   /* itfunc.c; any pointer may be NULL */
+  KSPValid(ksp);
+  if (rtol) *rtol = ksp->rtol;
+  if (abstol) *abstol = ksp->abstol;
+  if (dtol) *dtol = ksp->divtol;
+  if (maxits) *maxits = ksp->max_it;
+  return 0;
+}
 PetscErrorCode KSPSetNullSpace(KSP ksp, MatNullSpace nullsp) {   /* itfunc.c KSPSetNullSpace: reference the new one, release the old one */
   KSPValid(ksp);
   if (nullsp) nullsp->refct++;
@@ -148,6 +156,14 @@ PetscErrorCode KSPGMRESSetCGSRefinementType(KSP ksp, KSPGMRESCGSRefinementType t
   KSPValid(ksp);
   PetscErrorCode ierr = PetscObjectQueryFunction((PetscObject)ksp, "KSPGMRESSetCGSRefinementType_C", &f);CHKERRQ(ierr);
   if (f) { ierr = ((PetscErrorCode (*)(KSP, KSPGMRESCGSRefinementType))f)(ksp, type);CHKERRQ(ierr); }
+  return 0;
+}
+/* KSPFGMRESSetModifyPC, fgmres.c: PetscTryMethod as well -- the flexible GMRES types answer */
+PetscErrorCode KSPFGMRESSetModifyPC(KSP ksp, PetscErrorCode (*fcn)(KSP, PetscInt, PetscInt, PetscReal, void *), void *ctx, PetscErrorCode (*d)(void *)) {
+  PetscVoidFunction f = NULL;
+  KSPValid(ksp);
+  PetscErrorCode ierr = PetscObjectQueryFunction((PetscObject)ksp, "KSPFGMRESSetModifyPC_C", &f);CHKERRQ(ierr);
+  if (f) { ierr = ((PetscErrorCode (*)(KSP, PetscErrorCode (*)(KSP, PetscInt, PetscInt, PetscReal, void *), void *, PetscErrorCode (*)(void *)))f)(ksp, fcn, ctx, d);CHKERRQ(ierr); }
   return 0;
 }
 /* KSPChebychevSetEigenvalues (cheby.c), KSPRichardsonSetScale (rich.c): PetscTryMethod as well */

@@ -41,6 +41,7 @@ PetscErrorCode PetscMiniInitialize(void) {
   ierr = PCRegister(PCILU, 0, "PCCreate_ILU", PCCreate_ILU);CHKERRQ(ierr);      /* pcfactor.c: control flow only; the factored matrix comes from the operator's type */
   ierr = PCRegister(PCICC, 0, "PCCreate_ICC", PCCreate_ICC);CHKERRQ(ierr);
   ierr = PCRegister(PCSOR, 0, "PCCreate_SOR", PCCreate_SOR);CHKERRQ(ierr);
+  ierr = PCRegister(PCKSP, 0, "PCCreate_KSP", PCCreate_KSP);CHKERRQ(ierr);
   ierr = KSPRegister(KSPCG, 0, "KSPCreate_CG", KSPCreate_CG);CHKERRQ(ierr);
   ierr = KSPRegister(KSPGROPPCG, 0, "KSPCreate_GROPPCG", KSPCreate_GROPPCG);CHKERRQ(ierr);
   ierr = KSPRegister(KSPPIPECG, 0, "KSPCreate_PIPECG", KSPCreate_PIPECG);CHKERRQ(ierr);
@@ -54,6 +55,7 @@ PetscErrorCode PetscMiniInitialize(void) {
   ierr = KSPRegister(KSPCGS, 0, "KSPCreate_CGS", KSPCreate_CGS);CHKERRQ(ierr);
   ierr = KSPRegister(KSPBICG, 0, "KSPCreate_BICG", KSPCreate_BICG);CHKERRQ(ierr);
   ierr = KSPRegister(KSPLSQR, 0, "KSPCreate_LSQR", KSPCreate_LSQR);CHKERRQ(ierr);
+  ierr = KSPRegister(KSPFGMRES, 0, "KSPCreate_FGMRES", KSPCreate_FGMRES);CHKERRQ(ierr);
   return 0;
 }
 
@@ -251,6 +253,67 @@ PetscErrorCode PCCreate_SOR(PC pc) {   /* sor.c:330-350 */
   jac->sym = SOR_LOCAL_SYMMETRIC_SWEEP; jac->omega = 1.0; jac->fshift = 0.0; jac->its = 1; jac->lits = 1;
   pc->data = jac;
   pc->ops->apply = PCApply_SOR; pc->ops->applyrichardson = PCApplyRichardson_SOR; pc->ops->setfromoptions = PCSetFromOptions_SOR; pc->ops->destroy = PCDestroy_SOR;
+  return 0;
+}
+
+/* ---------------------------------------------------------------- PCKSP (src/ksp/pc/impls/ksp/pcksp.c): y = KSPSolve(inner, x) from a zero
+ * guess.  Unless the inner solver runs a fixed number of steps of a stationary method this is NOT one linear operator: the outer
+ * method has to tolerate that (KSPFGMRES).  No transposed application. */
+typedef struct { KSP ksp; PetscInt its; } PC_KSP;
+static PetscErrorCode pcksp_create_inner(PC pc) {
+  PC_KSP *jac = (PC_KSP *)pc->data;
+  char prefix[80];
+  if (jac->ksp) return 0;
+  if (strlen(pc->prefix) + sizeof("ksp_") > sizeof(pc->prefix)) SETERRQ(pc->comm, PETSC_ERR_ARG_SIZ, "The options prefix %s leaves no room for the inner solver's ksp_", pc->prefix);
+  PetscErrorCode ierr = KSPCreate(pc->comm, &jac->ksp);CHKERRQ(ierr);
+  snprintf(prefix, sizeof(prefix), "%sksp_", pc->prefix);
+  ierr = KSPSetOptionsPrefix(jac->ksp, prefix);CHKERRQ(ierr);
+  return 0;
+}
+static PetscErrorCode PCSetUp_KSP(PC pc) {   /* a repeated set-up hands the new operators on */
+  PC_KSP *jac = (PC_KSP *)pc->data;
+  PetscErrorCode ierr = pcksp_create_inner(pc);CHKERRQ(ierr);
+  ierr = KSPSetOperators(jac->ksp, pc->pmat, pc->pmat, SAME_NONZERO_PATTERN);CHKERRQ(ierr);
+  ierr = KSPSetFromOptions(jac->ksp);CHKERRQ(ierr);
+  ierr = KSPSetUp(jac->ksp);CHKERRQ(ierr);
+  return 0;
+}
+static PetscErrorCode PCSetUpOnBlocks_KSP(PC pc) { return KSPSetUpOnBlocks(((PC_KSP *)pc->data)->ksp); }
+static PetscErrorCode PCApply_KSP(PC pc, Vec x, Vec y) {   /* the inner solver's reason is its own business: a negative one is no error here */
+  PC_KSP *jac = (PC_KSP *)pc->data;
+  PetscInt its;
+  PetscErrorCode ierr = KSPSetInitialGuessNonzero(jac->ksp, PETSC_FALSE);CHKERRQ(ierr);
+  ierr = KSPSolve(jac->ksp, x, y);CHKERRQ(ierr);
+  ierr = KSPGetIterationNumber(jac->ksp, &its);CHKERRQ(ierr);
+  jac->its += its;
+  return 0;
+}
+static PetscErrorCode PCDestroy_KSP(PC pc) {
+  PC_KSP *jac = (PC_KSP *)pc->data;
+  if (!jac) return 0;
+  PetscErrorCode ierr = KSPDestroy(&jac->ksp);CHKERRQ(ierr);
+  free(jac); pc->data = NULL;
+  return 0;
+}
+PetscErrorCode PCKSPGetKSP(PC pc, KSP *ksp) {
+  if (!pc) SETERRQ(0, PETSC_ERR_ARG_NULL, "Null PC");
+  if (strcmp(pc->type_name, PCKSP)) SETERRQ(pc->comm, PETSC_ERR_ARG_WRONG, "Cannot get the inner solver of a PC of type %s", pc->type_name);
+  PetscErrorCode ierr = pcksp_create_inner(pc);CHKERRQ(ierr);
+  *ksp = ((PC_KSP *)pc->data)->ksp;
+  return 0;
+}
+PetscErrorCode PCKSPGetTotalIterations(PC pc, PetscInt *n) {
+  if (!pc) SETERRQ(0, PETSC_ERR_ARG_NULL, "Null PC");
+  if (strcmp(pc->type_name, PCKSP)) SETERRQ(pc->comm, PETSC_ERR_ARG_WRONG, "A PC of type %s counts no inner iterations", pc->type_name);
+  *n = ((PC_KSP *)pc->data)->its;
+  return 0;
+}
+PetscErrorCode PCCreate_KSP(PC pc) {
+  PC_KSP *jac;
+  PetscErrorCode ierr = PetscMalloc(sizeof(*jac), &jac);CHKERRQ(ierr);
+  memset(jac, 0, sizeof(*jac));
+  pc->data = jac;
+  pc->ops->setup = PCSetUp_KSP; pc->ops->apply = PCApply_KSP; pc->ops->destroy = PCDestroy_KSP; pc->ops->setuponblocks = PCSetUpOnBlocks_KSP;
   return 0;
 }
 

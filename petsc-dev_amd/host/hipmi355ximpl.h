@@ -418,5 +418,6 @@ PetscErrorCode KSPCreate_TFQMRHIPMI355X(KSP);
 PetscErrorCode KSPCreate_CGSHIPMI355X(KSP);
 PetscErrorCode KSPCreate_BICGHIPMI355X(KSP);
 PetscErrorCode KSPCreate_LSQRHIPMI355X(KSP);
+PetscErrorCode KSPCreate_FGMRESHIPMI355X(KSP);
 
 #endif

@@ -67,6 +67,7 @@ PetscErrorCode PetscHIPMI355XRegisterAll(void) {
   ierr = KSPRegister(KSPBICGHIPMI355X, 0, "KSPCreate_BICGHIPMI355X", KSPCreate_BICGHIPMI355X);CHKERRQ(ierr);
   ierr = KSPRegister(KSPLSQRHIPMI355X, 0, "KSPCreate_LSQRHIPMI355X", KSPCreate_LSQRHIPMI355X);CHKERRQ(ierr);
   ierr = KSPRegister(KSPCGSHIPMI355X, 0, "KSPCreate_CGSHIPMI355X", KSPCreate_CGSHIPMI355X);CHKERRQ(ierr);
+  ierr = KSPRegister(KSPFGMRESHIPMI355X, 0, "KSPCreate_FGMRESHIPMI355X", KSPCreate_FGMRESHIPMI355X);CHKERRQ(ierr);
 #if !defined(PETSCHIPMI355X_WITH_PETSC)
   /* the harness has no CPU types: the reference's generic names select the HIPMI355X implementation of the same shape
    * (with a real PETSc they keep meaning the CPU types, and -vec_type hipmi355x -mat_type aijhipmi355x select these) */

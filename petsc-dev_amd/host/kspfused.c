@@ -12,6 +12,7 @@
  *     KSPCGSHIPMI355X        "cgshipmi355x"         CGS        (the sequence of KSPCGS,     src/ksp/ksp/impls/cgs/cgs.c)
  *     KSPBICGHIPMI355X       "bicghipmi355x"        BiCG       (the sequence of KSPBICG,    src/ksp/ksp/impls/bicg/bicg.c)
  *     KSPLSQRHIPMI355X       "lsqrhipmi355x"        LSQR       (the sequence of KSPLSQR,    src/ksp/ksp/impls/lsqr/lsqr.c; rectangular operators)
+ *     KSPFGMRESHIPMI355X     "fgmreshipmi355x"      FGMRES(m)  (the cycle of KSPFGMRES,     src/ksp/ksp/impls/gmres/fgmres/fgmres.c; a varying preconditioner)
  *
  * They compute what the reference's solvers compute -- same iterates, same residual history, same exits, bit for bit against
  * the op-by-op sequences (tests/test_host_gpu.py) -- but group the vector work between two reductions into the fused sweeps a
@@ -279,12 +280,20 @@ typedef struct {
   PetscBool fused;
   PetscScalar *H;                   /* Hessenberg matrix after the rotations, column j at H + j (m + 2) */
   PetscScalar *g, *cs, *sn, *coef, *y;   /* rotated right-hand side, rotations, Gram-Schmidt coefficients, triangular solve */
-  Vec *V; PetscInt nV;              /* V[0], V[1]: scratch; V[2 + k]: k-th basis vector */
+  Vec *V; PetscInt nV, nscr;        /* V[0 .. nscr - 1]: scratch (GMRES 2, FGMRES 1); V[nscr + k]: k-th basis vector */
   Vec dinv;
+  /* fgmreshipmi355x only: Z[k] = B_k V[k], the routine that may change B before every application, the form of B and the step counts */
+  PetscBool flexible;
+  Vec *Z;
+  PetscErrorCode (*modifypc)(KSP, PetscInt, PetscInt, PetscReal, void *);
+  void *modifyctx;
+  PetscErrorCode (*modifydestroy)(void *);
+  HipPCKind pckind;
+  PetscInt nfused, nunfused;
 } KSP_GMRESHIP;
 #define GH(ksp) ((KSP_GMRESHIP *)(ksp)->data)
 #define Hcol(gm, j) ((gm)->H + (size_t)(j) * (size_t)((gm)->m + 2))
-#define BASIS(gm, k) ((gm)->V[2 + (k)])
+#define BASIS(gm, k) ((gm)->V[(gm)->nscr + (k)])
 
 static PetscErrorCode KSPGMRESSetRestart_GMRESHIP(KSP ksp, PetscInt restart) {
   if (restart < 1) SETERRQ(HipObjComm(ksp), PETSC_ERR_ARG_OUTOFRANGE, "Restart must be positive");
@@ -306,7 +315,7 @@ static PetscErrorCode KSPSetFromOptions_GMRESHIP(KSP ksp) {
     else SETERRQ(HipObjComm(ksp), PETSC_ERR_ARG_UNKNOWN_TYPE, "Unknown refinement type %s", t);
   }
   iv = GH(ksp)->fused;
-  ierr = option_level(ksp, "-ksp_gmres_fused", 0, 1, &iv);CHKERRQ(ierr);
+  ierr = option_level(ksp, GH(ksp)->flexible ? "-ksp_fgmres_fused" : "-ksp_gmres_fused", 0, 1, &iv);CHKERRQ(ierr);
   GH(ksp)->fused = (PetscBool)iv;
   return 0;
 }
@@ -325,8 +334,9 @@ static PetscErrorCode KSPSetUp_GMRESHIP(KSP ksp) {
   memset(gm->H, 0, sizeof(PetscScalar) * (m + 2) * (m + 1));
   memset(gm->g, 0, sizeof(PetscScalar) * (m + 2)); memset(gm->cs, 0, sizeof(PetscScalar) * (m + 2)); memset(gm->sn, 0, sizeof(PetscScalar) * (m + 2));
   if (!like) { Mat A; ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr); ierr = MatGetVecs(A, &made, NULL);CHKERRQ(ierr); like = made; }
-  gm->nV = gm->m + 4;                                   /* all basis vectors up front (gmres.c:36-96 allocates them in chunks) */
+  gm->nV = gm->flexible ? gm->m + 2 : gm->m + 4;        /* all basis vectors up front (gmres.c:36-96 allocates them in chunks) */
   ierr = VecDuplicateVecs(like, gm->nV, &gm->V);CHKERRQ(ierr);
+  if (gm->flexible) { ierr = VecDuplicateVecs(like, gm->m, &gm->Z);CHKERRQ(ierr); }
   if (made) { ierr = VecDestroy(&made);CHKERRQ(ierr); }
   return 0;
 }
@@ -484,6 +494,8 @@ static PetscErrorCode KSPDestroy_GMRESHIP(KSP ksp) {
   if (!gm) return 0;
   HipFree(gm->H); HipFree(gm->g); HipFree(gm->cs); HipFree(gm->sn); HipFree(gm->coef); HipFree(gm->y);
   if (gm->V) { ierr = VecDestroyVecs(gm->nV, &gm->V);CHKERRQ(ierr); }
+  if (gm->Z) { ierr = VecDestroyVecs(gm->m, &gm->Z);CHKERRQ(ierr); }
+  if (gm->modifydestroy) { ierr = (*gm->modifydestroy)(gm->modifyctx);CHKERRQ(ierr); }
   ierr = VecDestroy(&gm->dinv);CHKERRQ(ierr);
   HipFree(gm); ksp->data = NULL;
   ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPGMRESSetRestart_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
@@ -496,12 +508,175 @@ PetscErrorCode KSPCreate_GMRESHIPMI355X(KSP ksp) {
   PetscErrorCode ierr = PetscMalloc(sizeof(*gm), &gm);CHKERRQ(ierr);
   memset(gm, 0, sizeof(*gm));
   gm->m = 30; gm->haptol = 1.0e-30; gm->refine = KSP_GMRES_CGS_REFINE_NEVER; gm->fused = PETSC_TRUE;   /* KSPGMRES's defaults, gmres.c:944-958 */
+  gm->nscr = 2;
   ksp->data = gm;
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);       /* gmres.c:909-910 */
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_RIGHT, 1);CHKERRQ(ierr);
   ksp->ops->setup = KSPSetUp_GMRESHIP; ksp->ops->solve = KSPSolve_GMRESHIP; ksp->ops->setfromoptions = KSPSetFromOptions_GMRESHIP; ksp->ops->destroy = KSPDestroy_GMRESHIP;
   ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPGMRESSetRestart_C", "KSPGMRESSetRestart_GMRESHIP", (PetscVoidFunction)KSPGMRESSetRestart_GMRESHIP);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPGMRESSetCGSRefinementType_C", "KSPGMRESSetCGSRefinementType_GMRESHIP", (PetscVoidFunction)KSPGMRESSetCGSRefinementType_GMRESHIP);CHKERRQ(ierr);
+  return 0;
+}
+
+/* ================================================================================================ flexible GMRES(m)
+ * The cycle of KSPFGMRES (fgmres.c; the sequence DESIGN.md section 4 states): right preconditioning with a preconditioner that may
+ * differ from step to step, Z[k] = B_k V[k] kept, x += Z y.  GMRES's state, Gram-Schmidt and rotations above are shared.
+ * Without refinement the Gram-Schmidt step is "gmres_orthog_normalize": one host wait per step with ANY preconditioner, PCKSP included.
+ * -ksp_fgmres_fused <bool> (default false: measured no faster, profiles/fgmres_rate.log): with PCNONE or PCJACOBI, no null space, no KSPFGMRESSetModifyPC routine and at most 32
+ * basis vectors the normalising sweep of step k also writes Z[k+1] = B V[k+1] ("fgmres_orthog_normalize_pc" of "VecFgmresFusedOps_C"),
+ * and step k + 1 skips its KSP_PCApply: 2 nv + 7 vector passes instead of 2 nv + 8 with Jacobi, one launch fewer, same bits.  The
+ * last step of a restart cycle has no Z[m] to write and takes the plain call.  After a happy breakdown V[k+1] and Z[k+1] are
+ * unspecified (the sweep scales what the reference leaves unscaled); x, the history, the iteration count and the reason are not.
+ * The start of a cycle normalises with VecNormalize: this library takes a fixed list of calls from PETSc (tests/test_host_cpu.py keeps
+ * it; VecScale is not on it, see the Chebyshev type above).  VecNormalize leaves a zero residual alone where VecScale(1 / 0) would fill
+ * the work vector with NaN: only seen with KSP_NORM_NONE, where no test stops the cycle.
+ * KSPHIPMI355XGetFusedStepCounts: (steps that wrote the next Z in the sweep, all other steps), summed over all solves since the type was set.  On vectors without the tables every
+ * step runs through the public calls.  Options of KSPGMRES kept: -ksp_gmres_restart, -ksp_gmres_cgs_refinement_type. */
+static const VecFgmresFusedOps *vec_fgmres_ops(Vec x) {
+  PetscVoidFunction f = NULL;
+  const VecFgmresFusedOps *P;
+  if (PetscObjectQueryFunction((PetscObject)x, "VecFgmresFusedOps_C", &f) || !f) return NULL;
+  P = ((VecFgmresFusedOpsGetFn)f)();
+  return (P && P->fgmres_orthog_normalize_pc) ? P : NULL;
+}
+static PetscErrorCode KSPFGMRESSetModifyPC_FGMRESHIP(KSP ksp, PetscErrorCode (*fcn)(KSP, PetscInt, PetscInt, PetscReal, void *), void *ctx, PetscErrorCode (*d)(void *)) {
+  KSP_GMRESHIP *gm = GH(ksp);
+  if (gm->modifydestroy) { PetscErrorCode ierr = (*gm->modifydestroy)(gm->modifyctx);CHKERRQ(ierr); }
+  gm->modifypc = fcn; gm->modifyctx = ctx; gm->modifydestroy = d;          /* NULL: the preconditioner is left alone (KSPFGMRESModifyPCNoChange) */
+  return 0;
+}
+static PetscErrorCode KSPGetFusedStepCounts_FGMRESHIP(KSP ksp, PetscInt *fused, PetscInt *opbyop) {
+  *fused = GH(ksp)->nfused; *opbyop = GH(ksp)->nunfused;
+  return 0;
+}
+
+static PetscErrorCode fgmres_residual(KSP ksp) {                        /* V[0] = b - A x, the true residual */
+  PetscErrorCode ierr;
+  KSP_GMRESHIP *gm = GH(ksp);
+  Mat A;
+  ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
+  ierr = KSP_MatMult(ksp, A, ksp->vec_sol, BASIS(gm, 0));CHKERRQ(ierr);
+  ierr = VecAYPX(BASIS(gm, 0), -1.0, ksp->vec_rhs);CHKERRQ(ierr);
+  return 0;
+}
+
+/* x += Z y with R y = g over the first n columns; a zero last pivot gives y[n-1] = 0, not a break-down */
+static PetscErrorCode fgmres_update_solution(KSP ksp, PetscInt n) {
+  PetscErrorCode ierr;
+  KSP_GMRESHIP *gm = GH(ksp);
+  PetscScalar *y = gm->y;
+  if (n < 1) return 0;
+  y[n - 1] = Hcol(gm, n - 1)[n - 1] != 0.0 ? gm->g[n - 1] / Hcol(gm, n - 1)[n - 1] : 0.0;
+  for (PetscInt k = n - 2; k >= 0; k--) {
+    PetscScalar t = gm->g[k];
+    for (PetscInt j = k + 1; j < n; j++) t = t - Hcol(gm, j)[k] * y[j];
+    y[k] = t / Hcol(gm, k)[k];
+  }
+  ierr = VecSet(gm->V[0], 0.0);CHKERRQ(ierr);
+  ierr = VecMAXPY(gm->V[0], n, y, gm->Z);CHKERRQ(ierr);
+  ierr = VecAXPY(ksp->vec_sol, 1.0, gm->V[0]);CHKERRQ(ierr);
+  return 0;
+}
+
+static PetscErrorCode fgmres_cycle(KSP ksp) {
+  PetscErrorCode ierr;
+  KSP_GMRESHIP *gm = GH(ksp);
+  const VecKrylovFusedOps *F = vec_fused_ops(BASIS(gm, 0));
+  const VecFgmresFusedOps *P = (gm->fused && gm->pckind != PCKIND_GENERAL) ? vec_fgmres_ops(BASIS(gm, 0)) : NULL;
+  Mat A;
+  PetscReal res, tt, hapbnd;
+  PetscInt k = 0;
+  PetscBool hapend = PETSC_FALSE, have_z = PETSC_FALSE, done;
+
+  if (F && !F->gmres_orthog_normalize) F = NULL;
+  ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
+  ierr = VecNormalize(BASIS(gm, 0), &res);CHKERRQ(ierr);
+  gm->g[0] = res;
+  ksp->rnorm = res;
+  KSPLogResidualHistory(ksp, res);
+  ierr = KSPTestConvergence(ksp, ksp->its, res);CHKERRQ(ierr);
+  if (ksp->reason) return 0;                                             /* no step, no monitor call, x as it is */
+  while (!ksp->reason && k < gm->m && ksp->its < ksp->max_it) {
+    PetscScalar *hcol = Hcol(gm, k);
+    if (k) KSPLogResidualHistory(ksp, res);
+    ierr = KSPMonitor(ksp, ksp->its, res);CHKERRQ(ierr);
+    if (gm->modifypc) { ierr = (*gm->modifypc)(ksp, ksp->its, k, res, gm->modifyctx);CHKERRQ(ierr); }
+    if (!have_z) { ierr = KSP_PCApply(ksp, BASIS(gm, k), gm->Z[k]);CHKERRQ(ierr); }      /* else the sweep of step k - 1 wrote Z[k] */
+    have_z = PETSC_FALSE;
+    ierr = KSP_MatMult(ksp, A, gm->Z[k], BASIS(gm, k + 1));CHKERRQ(ierr);
+    done = PETSC_FALSE;
+    if (gm->refine == KSP_GMRES_CGS_REFINE_NEVER) {
+      if (P && k + 1 < gm->m) {
+        ierr = P->fgmres_orthog_normalize_pc(BASIS(gm, k + 1), k + 1, &BASIS(gm, 0), gm->dinv, (PetscBool)(gm->pckind == PCKIND_IDENTITY), gm->Z[k + 1], gm->coef, &tt, &done);CHKERRQ(ierr);
+        have_z = done;
+      }
+      if (!done && F) { ierr = F->gmres_orthog_normalize(BASIS(gm, k + 1), k + 1, &BASIS(gm, 0), gm->coef, &tt, &done);CHKERRQ(ierr); }
+      if (done) for (PetscInt j = 0; j <= k; j++) { const PetscScalar c = -gm->coef[j]; hcol[j] = 0.0; hcol[j] -= c; }   /* borthog2.c:52-66 */
+    }
+    if (!done) {
+      ierr = gmres_orthogonalize(ksp, k, hcol);CHKERRQ(ierr);
+      ierr = VecNormalize(BASIS(gm, k + 1), &tt);CHKERRQ(ierr);
+    }
+    if (have_z) gm->nfused++; else gm->nunfused++;
+    hcol[k + 1] = tt;
+    hapbnd = PetscAbsScalar(tt / gm->g[k]);
+    if (hapbnd > gm->haptol) hapbnd = gm->haptol;
+    if (!(tt > hapbnd)) hapend = PETSC_TRUE;
+    gmres_rotate(ksp, k, hapend, &res);
+    if (ksp->reason) break;                                              /* a rotation of length 0: the column does not count */
+    k++;
+    ksp->its++;
+    ksp->rnorm = res;
+    ierr = KSPTestConvergence(ksp, ksp->its, res);CHKERRQ(ierr);
+    if (hapend) {
+      if (!ksp->reason) SETERRQ(HipObjComm(ksp), PETSC_ERR_PLIB, "You reached the happy break down, but convergence was not indicated. Residual norm = %g", (double)res);
+      break;
+    }
+  }
+  KSPLogResidualHistory(ksp, res);
+  if (ksp->reason || ksp->its >= ksp->max_it) { ierr = KSPMonitor(ksp, ksp->its, res);CHKERRQ(ierr); }
+  ierr = fgmres_update_solution(ksp, k);CHKERRQ(ierr);
+  return 0;
+}
+
+static PetscErrorCode KSPSolve_FGMRESHIP(KSP ksp) {
+  PetscErrorCode ierr;
+  KSP_GMRESHIP *gm = GH(ksp);
+  ksp->its = 0;
+  ksp->reason = KSP_CONVERGED_ITERATING;
+  gm->pckind = PCKIND_GENERAL;                                           /* what the sweep may apply itself: a PC nobody changes, nothing projected behind it */
+  if (gm->fused && !gm->modifypc && !has_null_space(ksp)) { ierr = pc_diagonal_form(ksp, BASIS(gm, 0), &gm->dinv, &gm->pckind);CHKERRQ(ierr); }
+  if (ksp->guess_zero) { ierr = VecCopy(ksp->vec_rhs, BASIS(gm, 0));CHKERRQ(ierr); }
+  else { ierr = fgmres_residual(ksp);CHKERRQ(ierr); }
+  ierr = fgmres_cycle(ksp);CHKERRQ(ierr);
+  while (!ksp->reason) {
+    ierr = fgmres_residual(ksp);CHKERRQ(ierr);
+    if (ksp->its >= ksp->max_it) break;
+    ierr = fgmres_cycle(ksp);CHKERRQ(ierr);
+  }
+  if (ksp->its >= ksp->max_it && !ksp->reason) ksp->reason = KSP_DIVERGED_ITS;
+  return 0;
+}
+
+static PetscErrorCode KSPDestroy_FGMRESHIP(KSP ksp) {
+  PetscErrorCode ierr;
+  if (!ksp->data) return 0;
+  ierr = KSPDestroy_GMRESHIP(ksp);CHKERRQ(ierr);
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPFGMRESSetModifyPC_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
+  return 0;
+}
+
+PetscErrorCode KSPCreate_FGMRESHIPMI355X(KSP ksp) {
+  PetscErrorCode ierr = KSPCreate_GMRESHIPMI355X(ksp);CHKERRQ(ierr);
+  GH(ksp)->flexible = PETSC_TRUE; GH(ksp)->nscr = 1; GH(ksp)->fused = PETSC_FALSE;
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 0);CHKERRQ(ierr);      /* right preconditioning only: the true residual's norm, or none */
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_NONE, PC_LEFT, 0);CHKERRQ(ierr);
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_RIGHT, 2);CHKERRQ(ierr);
+  ierr = KSPSetSupportedNorm(ksp, KSP_NORM_NONE, PC_RIGHT, 1);CHKERRQ(ierr);
+  ksp->ops->solve = KSPSolve_FGMRESHIP; ksp->ops->destroy = KSPDestroy_FGMRESHIP;
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPFGMRESSetModifyPC_C", "KSPFGMRESSetModifyPC_FGMRESHIP", (PetscVoidFunction)KSPFGMRESSetModifyPC_FGMRESHIP);CHKERRQ(ierr);
+  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "KSPGetFusedStepCounts_FGMRESHIP", (PetscVoidFunction)KSPGetFusedStepCounts_FGMRESHIP);CHKERRQ(ierr);
   return 0;
 }
 

@@ -1655,6 +1655,45 @@ PetscErrorCode VecGMRESOrthogNormalize_HIPMI355X(Vec w, PetscInt nv, const Vec V
   *done = PETSC_TRUE;
   return 0;
 }
+/* The same step for flexible GMRES (include/petsckrylovfused.h fgmres_orthog_normalize_pc): the scaling sweep at the end is
+ * mi355x_vec_scale_rnorm_dev_pmult, which writes z = d .* w_new (identity: z = w_new) from the values it holds -- the PCApply_Jacobi /
+ * PCApply_None of the next step, one read of w and one launch fewer.  2 nv + 7 vector passes per step with Jacobi instead of 2 nv + 8. */
+PetscErrorCode VecFgmresOrthogNormalizePC_HIPMI355X(Vec w, PetscInt nv, const Vec V[], Vec d, PetscBool identity, Vec z, PetscScalar *dots, PetscReal *nrm,
+                                                    PetscBool *done) {
+  PetscErrorCode ierr; const double *tab[32]; const PetscScalar *dd = NULL; PetscScalar *dw, *dz; double *ds; DEVCTX;
+  *done = PETSC_FALSE;
+  if (identity) d = NULL;
+  if (!is_hip(w) || !z || !is_hip(z) || z == w || (!identity && (!d || !is_hip(d) || d == w || d == z)) || nv < 1 || nv > 32 || HOST_STAGED(w)) return 0;
+  if (z->map->n != w->map->n || (d && d->map->n != w->map->n) || HOST_STAGED(z) || (d && HOST_STAGED(d))) return 0;
+  for (PetscInt j = 0; j < nv; j++) if (!is_hip(V[j]) || V[j] == w || V[j] == z || V[j] == d || V[j]->map->n != w->map->n) return 0;
+  for (PetscInt j = 0; j < nv; j++) { ierr = VecHIPGetRead(V[j], &tab[j]);CHKERRQ(ierr); }
+  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
+  ierr = VecHIPGetReadWrite(w, &dw);CHKERRQ(ierr);
+  ierr = VecHIPGetWrite(z, &dz);CHKERRQ(ierr);
+  ds = mi355x_handle_device_scratch(dc->h);
+  CHKHIP(mi355x_vec_mdot(dc->h, N_(w), (int)nv, dw, tab, ds));
+  if (DEVICE_COLLECTIVES(w)) CHKHIP(mi355x_comm_allreduce_sum(HipCommDevice(HipObjComm(w)), dc->h, ds, (size_t)nv));
+  CHKHIP(mi355x_vec_maxpy_dev_norm2(dc->h, N_(w), (int)nv, ds, -1.0, tab, dw, ds + nv));
+  if (DEVICE_COLLECTIVES(w)) CHKHIP(mi355x_comm_allreduce_sum(HipCommDevice(HipObjComm(w)), dc->h, ds + nv, 1));
+  CHKHIP(mi355x_handle_publish(dc->h, ds, (int)nv + 1));
+  if (N_(w)) CHKHIP(mi355x_vec_scale_rnorm_dev_pmult(dc->h, N_(w), ds + nv, dw, dd, dz));
+  VecHIPRestoreWrite(w);
+  HipStateIncrease(w);
+  VecHIPRestoreWrite(z);
+  HipStateIncrease(z);
+  CHKHIP(mi355x_handle_wait_result(dc->h)); { PetscErrorCode e_ = HipTriWatchCheck();CHKERRQ(e_); }
+  const double *hs = mi355x_handle_host_scratch(dc->h);
+  for (PetscInt j = 0; j < nv; j++) dots[j] = hs[j];
+  *nrm = PetscSqrtReal(hs[nv]);                                 /* pvec2.c:62-64: the square is reduced, then the root */
+  ierr = PetscLogFlops(PetscMax(nv * (2.0 * w->map->n - 1), 0.0) + 2.0 * nv * w->map->n + PetscMax(2.0 * w->map->n - 1, 0.0) + (d ? 2.0 : 1.0) * w->map->n);CHKERRQ(ierr);
+  *done = PETSC_TRUE;
+  return 0;
+}
+/* "VecFgmresFusedOps_C": the Gram-Schmidt step of flexible GMRES */
+static const VecFgmresFusedOps *VecFgmresFusedOps_HIP(void) {
+  static const VecFgmresFusedOps ops = {VecFgmresOrthogNormalizePC_HIPMI355X};
+  return &ops;
+}
 /* "VecKrylovFusedOps_C": the fused sweeps of KSPSolve_CG / KSPSolve_BCGS, bit-identical to the calls they replace */
 static const VecKrylovFusedOps *VecKrylovFusedOps_HIP(void) {
   static const VecKrylovFusedOps ops = {
@@ -1731,6 +1770,7 @@ static PetscErrorCode VecCreate_HIP_common(Vec v, const char *tname) {
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecTfqmrFusedOps_C", "VecTfqmrFusedOps_HIP", (PetscVoidFunction)VecTfqmrFusedOps_HIP);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecBicgFusedOps_C", "VecBicgFusedOps_HIP", (PetscVoidFunction)VecBicgFusedOps_HIP);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)v, "VecLsqrFusedOps_C", "VecLsqrFusedOps_HIP", (PetscVoidFunction)VecLsqrFusedOps_HIP);CHKERRQ(ierr);
+  ierr = PetscObjectComposeFunction((PetscObject)v, "VecFgmresFusedOps_C", "VecFgmresFusedOps_HIP", (PetscVoidFunction)VecFgmresFusedOps_HIP);CHKERRQ(ierr);
   return 0;
 }
 

@@ -68,6 +68,7 @@ _SIG = {
     "MatLoad": [vp, vp], "MatView": [vp, vp], "VecLoad": [vp, vp], "VecView": [vp, vp],
     "PCCreate": [vp, P(vp)], "PCSetOperators": [vp, vp, vp, i32], "PCSetFromOptions": [vp], "PCApply": [vp, vp, vp], "PCDestroy": [P(vp)],
     "PCSetType": [vp, C.c_char_p], "PCILUGetLevels_HIPMI355X": [vp, P(i32), P(i32)], "PCILUGetShiftCount_HIPMI355X": [vp, P(i32)], "PCICCGetInfo_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCILUGetSolver_HIPMI355X": [vp, P(i32), P(i32)], "PCFactorDebugSetAborted_HIPMI355X": [vp], "PCILUGetSweeps_HIPMI355X": [vp, P(i32)], "PCILUGetNumeric_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCILUGetFill_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCBILUGetInfo_HIPMI355X": [vp, P(i32), P(i32), P(i32), P(i32)], "PCBILUGetSolvePlan_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCFactorSetLevels": [vp, i32], "PCILUApplyInPlace_HIPMI355X": [vp, vp], "PCILUGetNodeInfo_HIPMI355X": [vp, P(i32), P(i32), P(i32)], "PCFactorGetMatrix": [vp, P(vp)], "MatSolve": [vp, vp, vp], "MatSolveTranspose": [vp, vp, vp], "PCApplyTranspose": [vp, vp, vp], "PCApplyTransposeExists": [vp, P(i32)], "PCILUGetTransposeBuilds_HIPMI355X": [vp, P(i32), P(i32)], "PCBJacobiGetSubKSP": [vp, P(i32), P(i32), P(vp)],
+    "PCKSPGetKSP": [vp, P(vp)], "PCKSPGetTotalIterations": [vp, P(i32)], "KSPFGMRESSetModifyPC": [vp, vp, vp, vp], "KSPGetTolerances": [vp, P(dbl), P(dbl), P(dbl), P(i32)], "KSPGetType": [vp, P(C.c_char_p)],
     "KSPCreate": [vp, P(vp)], "KSPSetType": [vp, C.c_char_p], "KSPSetOperators": [vp, vp, vp, i32], "KSPGetPC": [vp, P(vp)],
     "KSPSetTolerances": [vp, dbl, dbl, dbl, i32], "KSPSetNormType": [vp, i32], "KSPSetPCSide": [vp, i32], "KSPSetInitialGuessNonzero": [vp, i32], "KSPSetOptionsPrefix": [vp, C.c_char_p],
     "KSPSetFromOptions": [vp], "KSPGMRESSetRestart": [vp, i32], "KSPGMRESSetCGSRefinementType": [vp, i32],
@@ -491,12 +492,34 @@ class PC:
         lib().PCApplyTransposeExists(self.h, C.byref(flg))
         return bool(flg.value)
 
+    def ksp_get_ksp(self):
+        """PCKSPGetKSP: the inner solver of a PC of type "ksp" (options prefix "<pc prefix>ksp_"), created now if need be; a borrowed
+        KSP, never destroyed from here"""
+        k = vp()
+        lib().PCKSPGetKSP(self.h, C.byref(k))
+        return KSP(handle=k)
+
+    def ksp_total_iterations(self):
+        """PCKSPGetTotalIterations: the inner iterations of all applications of a PC of type "ksp" so far"""
+        n = i32()
+        lib().PCKSPGetTotalIterations(self.h, C.byref(n))
+        return n.value
+
+
+MODIFY_PC_FN = C.CFUNCTYPE(i32, vp, i32, i32, dbl, vp)   # KSPFGMRESSetModifyPC's routine: (ksp, total_its, loc_its, res_norm, ctx)
+
 
 class KSP:
-    def __init__(self, comm=None):
+    def __init__(self, comm=None, handle=None):
+        """a new KSP on comm, or (handle given) a borrowed one that is never destroyed from here"""
+        self._hist = None
+        self._modify_pc = None
+        self.own = handle is None
+        if handle is not None:
+            self.h = handle
+            return
         self.h = vp()
         lib().KSPCreate(comm or lib().COMM_WORLD, C.byref(self.h))
-        self._hist = None
 
     def set_null_space(self, nullsp):
         """KSPSetNullSpace; None takes it away"""
@@ -517,6 +540,31 @@ class KSP:
         pc = vp()
         lib().KSPGetPC(self.h, C.byref(pc))
         lib().PCSetType(pc, t.encode())
+
+    def get_type(self):
+        t = C.c_char_p()
+        lib().KSPGetType(self.h, C.byref(t))
+        return t.value.decode()
+
+    def get_tolerances(self):
+        """KSPGetTolerances: (rtol, abstol, dtol, max_it)"""
+        r, a, d, m = dbl(), dbl(), dbl(), i32()
+        lib().KSPGetTolerances(self.h, C.byref(r), C.byref(a), C.byref(d), C.byref(m))
+        return r.value, a.value, d.value, m.value
+
+    def fgmres_set_modify_pc(self, fn):
+        """KSPFGMRESSetModifyPC: fn(total_its, loc_its, res_norm) runs before every preconditioner application of the fgmres types
+        and may change the preconditioner; None restores KSPFGMRESModifyPCNoChange.  Ignored by any other type."""
+        if fn is None:
+            self._modify_pc = None
+            lib().KSPFGMRESSetModifyPC(self.h, None, None, None)
+            return
+
+        def call(ksp, its, k, rn, ctx):
+            fn(its, k, rn)
+            return 0
+        self._modify_pc = MODIFY_PC_FN(call)
+        lib().KSPFGMRESSetModifyPC(self.h, C.cast(self._modify_pc, vp), None, None)
 
     def set_tolerances(self, rtol=PETSC_DEFAULT, abstol=PETSC_DEFAULT, dtol=PETSC_DEFAULT, max_it=PETSC_DEFAULT):
         lib().KSPSetTolerances(self.h, float(rtol), float(abstol), float(dtol), int(max_it))
@@ -562,7 +610,7 @@ class KSP:
         return a.value, r.value, n.value
 
     def fused_step_counts(self):
-        """KSPHIPMI355XGetFusedStepCounts: (fused, opbyop) update steps of the pipelined CG types since the type was set; minreshipmi355x: (Lanczos sweeps run, 0); tfqmrhipmi355x / cgshipmi355x: (fused sweeps run, iterations with a step run op by op); lsqrhipmi355x: (bidiagonalisation sweeps run, update sweeps run); (0, 0) for any other"""
+        """KSPHIPMI355XGetFusedStepCounts: (fused, opbyop) update steps of the pipelined CG types since the type was set; minreshipmi355x: (Lanczos sweeps run, 0); tfqmrhipmi355x / cgshipmi355x: (fused sweeps run, iterations with a step run op by op); lsqrhipmi355x: (bidiagonalisation sweeps run, update sweeps run); fgmreshipmi355x: (steps whose sweep wrote the next preconditioned direction, all other steps), over all solves since the type was set; (0, 0) for any other"""
         f = i32(); o = i32()
         lib().KSPHIPMI355XGetFusedStepCounts(self.h, C.byref(f), C.byref(o))
         return f.value, o.value
@@ -598,7 +646,7 @@ class KSP:
         return self._hist[:n.value].copy()
 
     def destroy(self):
-        if self.h:
+        if self.own and self.h:
             lib().KSPDestroy(C.byref(self.h))
 
     def __del__(self):
