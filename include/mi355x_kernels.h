@@ -374,6 +374,14 @@ int mi355x_spmv_csr_add(mi355x_handle_t h, mi355x_spmv_plan_t plan, const int *a
  * z is stored non-temporally from 256 MiB. */
 int mi355x_spmv_csr_add_scaled(mi355x_handle_t h, mi355x_spmv_plan_t plan, const int *ai, const int *aj, const double *aa,
                                const double *x, const double *y, const double *d, double *z);
+/* r = b - A x (MatResidual): the row sum mi355x_spmv_csr forms -- from 0.0, in the order of the form the plan runs, pairsum and the
+ * long-row lane tree included -- then one subtraction from b_r: the bits of mi355x_spmv_csr(.., w) followed by
+ * mi355x_vec_aypx(w, -1, b), empty rows (b_r - 0.0), signed zeros and specials included, without writing and re-reading w.  All five
+ * forms mi355x_spmv_csr dispatches (plain, 8-bit offsets, row patterns, value patterns, grouped rows); rectangular plans are fine.
+ * r may alias b; x must not alias r (hipErrorInvalidValue, as for a NULL argument).  A compressed-row plan: hipErrorNotSupported
+ * (801), nothing written -- those kernels touch the listed rows only. */
+int mi355x_spmv_csr_residual(mi355x_handle_t h, mi355x_spmv_plan_t plan, const int *ai, const int *aj, const double *aa,
+                             const double *x, const double *b, double *r);
 /* MatMultTranspose[Add]_SeqAIJ  src/mat/impls/aij/seq/aij.c:1078-1135 is served by the same two
  * kernels applied to an explicit transpose whose rows list contributions in increasing
  * original-row order (the order the reference's scatter loop adds them in). */

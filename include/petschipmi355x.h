@@ -116,6 +116,11 @@ PetscErrorCode MatHIPMI355XGetSORInfo(Mat A, PetscInt *levels, PetscInt *launche
 /* the result C of MatMatMult, MatTranspose or MatPtAP on sequential matrices of this type, so far: host symbolic passes (1: MAT_REUSE_MATRIX
  * never repeats it), numeric phases on the device, numeric phases on the host (-mat_hipmi355x_product host) */
 PetscErrorCode MatHIPMI355XGetProductCounts(Mat C, PetscInt *symbolic_builds, PetscInt *device_numerics, PetscInt *host_numerics);
+/* MATSEQAIJHIPMI355X composes "MatResidual_C" (Mat A, Vec b, Vec x, Vec r): r = b - A x in the product's own launch
+ * (mi355x_spmv_csr_residual) when the product in force is a row-block form, by MatMult + VecAYPX(r, -1, b) otherwise (column-tiled,
+ * blocked companion, compressed rows, vectors of another type) -- the same bits either way.  -mat_hipmi355x_residual <fused|calls>.
+ * The counts: residuals of this matrix that took the fused kernel / the two calls, so far. */
+PetscErrorCode MatHIPMI355XGetResidualCounts(Mat A, PetscInt *fused, PetscInt *calls);
 PetscErrorCode MatHIPMI355XGetInodeInfo(Mat A, PetscInt *nodes, PetscInt *groups, PetscInt *shared_indices);   /* Mat_CheckInode's node count; groups / column indices the device plan stores once per group */
 PetscErrorCode MatHIPMI355XGetBlockedInfo(Mat A, PetscInt *bs, PetscInt *nblocks);   /* blocked companion of an AIJ matrix whose nodes are complete bs x bs blocks (products by the BAIJ kernel); 0, 0: not in use */
 PetscErrorCode MatHIPMI355XGetTiledInfo(Mat A, PetscInt *staged, PetscInt *remainder);   /* column-tiled product (x tiles in LDS): nonzeros gathering from LDS / left to the row-block kernel; 0, 0: not in use */
@@ -139,6 +144,7 @@ PetscErrorCode PCILUGetNumeric_HIPMI355X(PC pc, PetscInt *on_device, PetscInt *s
 PetscErrorCode PCILUApplyInPlace_HIPMI355X(PC pc, Vec v);   /* v <- factor applied to v, for a sweeps:<k> factor (PCApply / MatSolve refuse identical vectors, as the reference's do) */
 PetscErrorCode PCFactorDebugSetAborted_HIPMI355X(PC pc);   /* tests: raise the "a dependency wait gave up" flag of this PC's sync-free plans */
 PetscErrorCode PCILUGetSolver_HIPMI355X(PC pc, PetscInt *syncfree, PetscInt *aborted);   /* 1: two-launch sync-free solves (-pc_factor_hipmi355x_trisolve syncfree, default above 16 levels); 0: one launch per level */
+PetscErrorCode HIPMI355XGetLiveFactors(PetscInt *live, PetscInt *watched);   /* life-cycle tests: ILU / ICC factors of the AIJ type that MatGetFactor made and nothing destroyed yet; those of them on the sync-free watch list */
 PetscErrorCode PCBILUGetInfo_HIPMI355X(PC pc, PetscInt *bs, PetscInt *levels_L, PetscInt *levels_U, PetscInt *nz_blocks);   /* PCILU over a BAIJ operator (block ILU(k), host/bilu.c): block size, dependency levels of the two block triangular solves, stored blocks of the factor */
 PetscErrorCode PCBILUGetSolvePlan_HIPMI355X(PC pc, PetscInt *fused, PetscInt *launches_L, PetscInt *launches_U);   /* the same PC: 1 under -pc_factor_hipmi355x_trisolve fused (runs of narrow levels in one launch each), 0 level by level; the launches one application makes for L and for U */
 

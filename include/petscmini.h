@@ -150,6 +150,7 @@ typedef const char *PCType;
 #define PCICC      "icc"       /* ICC(0), natural ordering, sequential AIJ */
 #define PCSOR      "sor"       /* SOR / SSOR through the operator's MatSOR (src/ksp/pc/impls/sor/sor.c) */
 #define PCKSP      "ksp"       /* a Krylov solver as the preconditioner: every application is a KSPSolve of the inner KSP (src/ksp/pc/impls/ksp/pcksp.c) */
+#define PCMG       "mg"        /* multigrid cycles over level KSPs, grid transfers given as matrices (src/ksp/pc/impls/mg/mg.c) */
 
 /* ---- Sys ----------------------------------------------------------------------------------- */
 extern PetscComm PETSC_COMM_SELF, PETSC_COMM_WORLD;
@@ -338,6 +339,14 @@ PetscErrorCode MatGetColumnNorms(Mat A, NormType type, PetscReal norms[]);
 /* null spaces of singular operators (src/mat/interface/matnull.c): the constant vector (has_cnst) and / or n orthonormal vectors, which
  * the null space keeps references to.  MatNullSpaceRemove: the constant first (VecSum, sum / (-N), VecShift), then the vectors (VecMDot,
  * VecMAXPY), then the function set with MatNullSpaceSetFunction; out != NULL: the result goes to an internal copy returned in *out */
+/* grid transfers and the residual (matrix.c).  MatRestrict / MatInterpolate: y = A x when A's rows match y, y = A^T x when its columns do
+ * (one matrix serves both directions); MatInterpolateAdd: w = y + (A or A^T) x, w may be y; sizes that fit neither way PETSC_ERR_ARG_SIZ.
+ * MatResidual: r = b - A x by the type's own "MatResidual_C" (Mat, Vec b, Vec x, Vec r) if it composed one, else MatMult and
+ * VecAYPX(r, -1, b); r must be neither b nor x. */
+PetscErrorCode MatRestrict(Mat A, Vec x, Vec y);
+PetscErrorCode MatInterpolate(Mat A, Vec x, Vec y);
+PetscErrorCode MatInterpolateAdd(Mat A, Vec x, Vec y, Vec w);
+PetscErrorCode MatResidual(Mat A, Vec b, Vec x, Vec r);
 PetscErrorCode MatNullSpaceCreate(PetscComm comm, PetscBool has_cnst, PetscInt n, const Vec vecs[], MatNullSpace *SP);
 PetscErrorCode MatNullSpaceDestroy(MatNullSpace *sp);
 PetscErrorCode MatNullSpaceSetFunction(MatNullSpace sp, PetscErrorCode (*rem)(MatNullSpace, Vec, void *), void *ctx);
@@ -380,6 +389,37 @@ PetscErrorCode PCBJacobiGetSubKSP(PC pc, PetscInt *n_local, PetscInt *first_loca
  * all applications so far.  Both return PETSC_ERR_ARG_WRONG for a PC of another type. */
 PetscErrorCode PCKSPGetKSP(PC pc, KSP *ksp);
 PetscErrorCode PCKSPGetTotalIterations(PC pc, PetscInt *n);
+/* PCMG (include/petscpcmg.h; mg.c, mgfunc.c).  Level 0 is the coarsest, level n-1 the PC's own operators.  Level solvers: options prefix
+ * "<pc prefix>mg_coarse_" for level 0, "<pc prefix>mg_levels_<l>_" above it; an option under "mg_levels_" reaches every smoothed level and
+ * the same option under "mg_levels_<l>_" beats it.  Smoothers default to richardson + sor without a norm, one step, nonzero guess; the
+ * coarse solver to preonly + the PC default.  The up smoother is the down smoother's KSP until PCMGGetSmootherUp or unequal
+ * PCMGSetNumberSmoothDown / Up ask for a second one (same type, PC type and prefix).  The solvers are borrowed, not owned by the caller.
+ * PCMGSetLevels: comms must be NULL; after set-up PETSC_ERR_ORDER.  PCMGSetType: PC_MG_KASKADE is PETSC_ERR_SUP.
+ * PCMGSetInterpolation / SetRestriction (l >= 1): each defaults to the other; the direction is chosen from the sizes (MatRestrict).
+ * PCMGSetGalerkin: A_{l-1} = MatPtAP(A_l, P_l), the PC's own matrices, rebuilt with MAT_REUSE_MATRIX at every later set-up; the transfer
+ * must then be stored as the interpolation (fine x coarse).  Without it every level below the top needs KSPSetOperators on its smoother
+ * (PETSC_ERR_ARG_WRONGSTATE names the level).  PCMGSetResidual: fn NULL is PCMGDefaultResidual = MatResidual; mat NULL the level's operator.
+ * Options: -pc_mg_levels -pc_mg_type <multiplicative|additive|full> -pc_mg_cycle_type <v|w> -pc_mg_multiplicative_cycles -pc_mg_smoothdown
+ * -pc_mg_smoothup -pc_mg_galerkin. */
+typedef enum { PC_MG_MULTIPLICATIVE, PC_MG_ADDITIVE, PC_MG_FULL, PC_MG_KASKADE } PCMGType;
+typedef enum { PC_MG_CYCLE_V = 1, PC_MG_CYCLE_W = 2 } PCMGCycleType;
+typedef PetscErrorCode (*PCMGResidualFn)(Mat, Vec, Vec, Vec);
+PetscErrorCode PCMGSetLevels(PC pc, PetscInt levels, PetscComm *comms);
+PetscErrorCode PCMGGetLevels(PC pc, PetscInt *levels);
+PetscErrorCode PCMGSetType(PC pc, PCMGType form);
+PetscErrorCode PCMGSetCycleType(PC pc, PCMGCycleType c);
+PetscErrorCode PCMGMultiplicativeSetCycles(PC pc, PetscInt n);
+PetscErrorCode PCMGSetNumberSmoothDown(PC pc, PetscInt n);
+PetscErrorCode PCMGSetNumberSmoothUp(PC pc, PetscInt n);
+PetscErrorCode PCMGSetGalerkin(PC pc, PetscBool use);
+PetscErrorCode PCMGSetInterpolation(PC pc, PetscInt l, Mat mat);
+PetscErrorCode PCMGSetRestriction(PC pc, PetscInt l, Mat mat);
+PetscErrorCode PCMGSetResidual(PC pc, PetscInt l, PCMGResidualFn residual, Mat mat);
+PetscErrorCode PCMGDefaultResidual(Mat mat, Vec b, Vec x, Vec r);
+PetscErrorCode PCMGGetSmoother(PC pc, PetscInt l, KSP *ksp);
+PetscErrorCode PCMGGetSmootherDown(PC pc, PetscInt l, KSP *ksp);
+PetscErrorCode PCMGGetSmootherUp(PC pc, PetscInt l, KSP *ksp);
+PetscErrorCode PCMGGetCoarseSolve(PC pc, KSP *ksp);
 
 /* ---- KSP (include/petscksp.h) ---------------------------------------------------------------- */
 PetscErrorCode KSPCreate(PetscComm comm, KSP *ksp);

@@ -125,6 +125,7 @@ KERNEL_API = {
     "mi355x_spmv_csr_add": [vp, vp, vp, vp, vp, vp, vp, vp],
     "mi355x_spmv_csr_scaled": [vp, vp, vp, vp, vp, vp, vp, vp],
     "mi355x_spmv_csr_add_scaled": [vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "mi355x_spmv_csr_residual": [vp, vp, vp, vp, vp, vp, vp, vp],
     "mi355x_spmv_csr_dot": [vp, vp, vp, vp, vp, vp, vp],
     "mi355x_spmv_dot_finish": [vp, vp, vp],
     "mi355x_spmv_tiled_probe": [i32, vp, vp, C.POINTER(dbl)],

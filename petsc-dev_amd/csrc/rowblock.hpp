@@ -128,10 +128,13 @@ __device__ __forceinline__ double row_sum_lds(const double *prod, int rs, int re
 // ADD == 3: y = dv .* (yin + A x), one step of a Jacobi-sweep upper triangular solve (A the negated strict triangle, dv the
 // inverted pivots; host/ilu.c); the plain row-block kernel only.  The sum starts from yin as for ADD == 1, so a one-lane row
 // carries the bits of s = yin; s = s + a_j x_j ...; dv * s.
-template <int ADD> __device__ __forceinline__ double spmv_out(double yv, double t, double dv = 1.0) { return ADD == 3 ? dv * (yv + t) : (ADD == 1 ? yv + t : (ADD == 2 ? yv * t : t)); }
-template <int ADD> __device__ __forceinline__ double spmv_empty(double yv, double dv = 1.0) { return ADD == 3 ? dv * yv : (ADD == 1 ? yv : (ADD == 2 ? yv * 0.0 : 0.0)); }
-// same, for a sum that was started from yv when ADD == 1 or 3
-template <int ADD> __device__ __forceinline__ double spmv_fin(double yv, double s, double dv = 1.0) { return ADD == 3 ? dv * s : (ADD == 2 ? yv * s : s); }
+// ADD == 4: y = yin - A x, the residual r = b - A x (yin = b).  The row sum is the one ADD == 0 forms -- started from 0.0, the form's own
+// order -- followed by ONE subtraction: the bits of the product into a work vector and VecAYPX(w, -1, b) behind it (b - w), without
+// the write and the re-read of w.  A row without entries is b - 0.0.
+template <int ADD> __device__ __forceinline__ double spmv_out(double yv, double t, double dv = 1.0) { return ADD == 4 ? yv - t : (ADD == 3 ? dv * (yv + t) : (ADD == 1 ? yv + t : (ADD == 2 ? yv * t : t))); }
+template <int ADD> __device__ __forceinline__ double spmv_empty(double yv, double dv = 1.0) { return ADD == 4 ? yv - 0.0 : (ADD == 3 ? dv * yv : (ADD == 1 ? yv : (ADD == 2 ? yv * 0.0 : 0.0))); }
+// same, for a sum that was started from yv when ADD == 1 or 3 (from 0.0 otherwise)
+template <int ADD> __device__ __forceinline__ double spmv_fin(double yv, double s, double dv = 1.0) { return ADD == 4 ? yv - s : (ADD == 3 ? dv * s : (ADD == 2 ? yv * s : s)); }
 static inline int spmv_y_streams(long nrows) { return (size_t)nrows * sizeof(double) >= ((size_t)256 << 20); }   // (vec_kernels.hip: vec_streams)
 // nt: y beyond the Infinity Cache (vectors of >= 256 MiB) is written once and read by another kernel much later: a non-temporal store
 // there (+3 % on P7(512), three of three alternations on one box: profiles/r04_spmv_p7_512_ab.log; nothing either way at P7(256))

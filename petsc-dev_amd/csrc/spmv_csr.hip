@@ -1434,6 +1434,17 @@ int mi355x_spmv_csr_add_scaled(mi355x_handle_t h, mi355x_spmv_plan_t plan, const
   return launch_spmv<3>(h, plan, ai, aj, aa, x, y, z, d);
 }
 
+// r = b - A x: the product's row sum (mi355x_spmv_csr's, whatever form the plan runs) and one subtraction from b_r in the epilogue --
+// the bits of mi355x_spmv_csr into a work vector followed by mi355x_vec_aypx(w, -1, b), without the write and the re-read of w.
+// r may alias b (a row's b is read by the lanes that write its r); x must not alias r.  A compressed-row plan visits the listed
+// rows only, and a residual has to write every row: hipErrorNotSupported, nothing written.
+int mi355x_spmv_csr_residual(mi355x_handle_t h, mi355x_spmv_plan_t plan, const int *ai, const int *aj, const double *aa,
+                             const double *x, const double *b, double *r) {
+  if (!h || !plan || !ai || !aj || !aa || !x || !b || !r || x == r) return (int)hipErrorInvalidValue;
+  if (plan->d_rows) return (int)hipErrorNotSupported;
+  return launch_spmv<4>(h, plan, ai, aj, aa, x, b, r);
+}
+
 static int spmv_bsr_planned_impl(mi355x_handle_t h, mi355x_spmv_plan_t p, int bs, const int *ai, const int *aj,
                                  const double *aa, const double *x, const double *yin, double *y, bool xlds) {
   if (p->nblocks == 0) return 0;

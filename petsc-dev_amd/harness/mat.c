@@ -137,6 +137,7 @@ PetscErrorCode MatAssemblyEnd(Mat A, MatAssemblyType type) {   /* matrix.c:4881 
 PetscErrorCode MatDestroy(Mat *A) {
   PetscErrorCode ierr;
   if (!*A) return 0;
+  if ((*A)->xrefs > 0) { (*A)->xrefs--; *A = NULL; return 0; }   /* somebody else still holds it */
   if ((*A)->ops->destroy) { ierr = (*(*A)->ops->destroy)(*A);CHKERRQ(ierr); }
   ierr = PetscLayoutDestroy(&(*A)->rmap);CHKERRQ(ierr);
   ierr = PetscLayoutDestroy(&(*A)->cmap);CHKERRQ(ierr);
@@ -451,6 +452,50 @@ PetscErrorCode MatPtAP(Mat A, Mat P, MatReuse scall, PetscReal fill, Mat *C) {
   if (fill != (PetscReal)PETSC_DEFAULT && fill < 1.0) SETERRQ(A->comm, PETSC_ERR_ARG_SIZ, "Expected fill=%g must be >= 1.0", (double)fill);
   if (!A->ops->ptap) SETERRQ(A->comm, PETSC_ERR_SUP, "MatPtAP for Mat type %s", A->type_name);
   ierr = (*A->ops->ptap)(A, P, scall, fill, C);CHKERRQ(ierr);
+  return 0;
+}
+
+/* ---- grid transfers and the residual (matrix.c MatRestrict, MatInterpolate, MatInterpolateAdd, MatResidual): what PCMG calls.  One
+ * matrix serves as interpolation (coarse -> fine) and as restriction (fine -> coarse); the direction is chosen from the sizes: the
+ * product when the matrix's rows match the output, the transposed product otherwise. */
+static PetscErrorCode transfer_sizes(Mat A, Vec x, Vec y, PetscBool *forward) {
+  MatTypeSet(A, 1); MatAssembled(A);
+  if (A->rmap->N == y->map->N && A->cmap->N == x->map->N) *forward = PETSC_TRUE;
+  else if (A->cmap->N == y->map->N && A->rmap->N == x->map->N) *forward = PETSC_FALSE;
+  else SETERRQ(A->comm, PETSC_ERR_ARG_SIZ, "Mat %d x %d fits neither way between Vec x of %d and Vec y of %d entries", A->rmap->N, A->cmap->N, x->map->N, y->map->N);
+  return 0;
+}
+PetscErrorCode MatInterpolateAdd(Mat A, Vec x, Vec y, Vec w) {   /* w = y + A x  or  w = y + A^T x */
+  PetscBool forward;
+  PetscErrorCode ierr = transfer_sizes(A, x, w, &forward);CHKERRQ(ierr);
+  if (y->map->N != w->map->N) SETERRQ(A->comm, PETSC_ERR_ARG_SIZ, "Vec y of %d and Vec w of %d entries", y->map->N, w->map->N);
+  if (forward) { ierr = MatMultAdd(A, x, y, w);CHKERRQ(ierr); }
+  else { ierr = MatMultTransposeAdd(A, x, y, w);CHKERRQ(ierr); }
+  return 0;
+}
+PetscErrorCode MatInterpolate(Mat A, Vec x, Vec y) {   /* y = A x  or  y = A^T x */
+  PetscBool forward;
+  PetscErrorCode ierr = transfer_sizes(A, x, y, &forward);CHKERRQ(ierr);
+  if (forward) { ierr = MatMult(A, x, y);CHKERRQ(ierr); }
+  else { ierr = MatMultTranspose(A, x, y);CHKERRQ(ierr); }
+  return 0;
+}
+PetscErrorCode MatRestrict(Mat A, Vec x, Vec y) { return MatInterpolate(A, x, y); }   /* matrix.c: the same choice, made from the same sizes */
+/* r = b - A x: the type's own method "MatResidual_C" (Mat, Vec b, Vec x, Vec r) if it composed one, else the product and VecAYPX(r, -1, b) */
+PetscErrorCode MatResidual(Mat A, Vec b, Vec x, Vec r) {
+  PetscErrorCode ierr;
+  PetscVoidFunction f = NULL;
+  MatTypeSet(A, 1); MatAssembled(A);
+  if (r == x || r == b) SETERRQ(A->comm, PETSC_ERR_ARG_IDN, "r must differ from b and from x");
+  if (A->cmap->N != x->map->N) SETERRQ(A->comm, PETSC_ERR_ARG_SIZ, "Mat mat,Vec x: global dim %d %d", A->cmap->N, x->map->N);
+  if (A->rmap->N != b->map->N) SETERRQ(A->comm, PETSC_ERR_ARG_SIZ, "Mat mat,Vec b: global dim %d %d", A->rmap->N, b->map->N);
+  if (A->rmap->N != r->map->N || A->rmap->n != r->map->n) SETERRQ(A->comm, PETSC_ERR_ARG_SIZ, "Mat mat,Vec r: dim %d %d", A->rmap->N, r->map->N);
+  ierr = PetscObjectQueryFunction((PetscObject)A, "MatResidual_C", &f);CHKERRQ(ierr);
+  if (f) { ierr = ((PetscErrorCode (*)(Mat, Vec, Vec, Vec))f)(A, b, x, r);CHKERRQ(ierr); }   /* (the method moves r's state on itself) */
+  else {
+    ierr = MatMult(A, x, r);CHKERRQ(ierr);
+    ierr = VecAYPX(r, -1.0, b);CHKERRQ(ierr);
+  }
   return 0;
 }
 

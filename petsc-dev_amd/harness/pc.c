@@ -42,6 +42,7 @@ PetscErrorCode PetscMiniInitialize(void) {
   ierr = PCRegister(PCICC, 0, "PCCreate_ICC", PCCreate_ICC);CHKERRQ(ierr);
   ierr = PCRegister(PCSOR, 0, "PCCreate_SOR", PCCreate_SOR);CHKERRQ(ierr);
   ierr = PCRegister(PCKSP, 0, "PCCreate_KSP", PCCreate_KSP);CHKERRQ(ierr);
+  ierr = PCRegister(PCMG, 0, "PCCreate_MG", PCCreate_MG);CHKERRQ(ierr);           /* mg.c */
   ierr = KSPRegister(KSPCG, 0, "KSPCreate_CG", KSPCreate_CG);CHKERRQ(ierr);
   ierr = KSPRegister(KSPGROPPCG, 0, "KSPCreate_GROPPCG", KSPCreate_GROPPCG);CHKERRQ(ierr);
   ierr = KSPRegister(KSPPIPECG, 0, "KSPCreate_PIPECG", KSPCreate_PIPECG);CHKERRQ(ierr);

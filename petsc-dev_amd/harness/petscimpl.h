@@ -185,6 +185,7 @@ struct _p_Mat {
   MatFactorType factortype;   /* MAT_FACTOR_NONE for an operator (matimpl.h:306) */
   void *data;
   void *spptr;        /* for the implementation's accelerator mirror, as Mat->spptr (matimpl.h:323) */
+  int xrefs;          /* references beyond the creator's (PetscObjectReference: a PCMG keeps its transfer matrices); MatDestroy drops one */
 };
 
 /* ---- PC / KSP ---- */
@@ -248,7 +249,7 @@ PetscErrorCode KSP_MatMultTranspose(KSP ksp, Mat A, Vec x, Vec y);
 PetscErrorCode KSP_PCApplyTranspose(KSP ksp, Vec x, Vec y);
 PetscErrorCode KSP_PCApplyBAorAB(KSP ksp, Vec x, Vec y, Vec w);
 PetscErrorCode KSPCreate_CG(KSP), KSPCreate_GROPPCG(KSP), KSPCreate_PIPECG(KSP), KSPCreate_GMRES(KSP), KSPCreate_BCGS(KSP), KSPCreate_PREONLY(KSP), KSPCreate_Chebychev(KSP), KSPCreate_Richardson(KSP), KSPCreate_MINRES(KSP), KSPCreate_TFQMR(KSP), KSPCreate_CGS(KSP), KSPCreate_BICG(KSP), KSPCreate_LSQR(KSP), KSPCreate_FGMRES(KSP);
-PetscErrorCode PCCreate_None(PC), PCCreate_Jacobi(PC), PCCreate_BJacobi(PC), PCCreate_ILU(PC), PCCreate_ICC(PC), PCCreate_SOR(PC), PCCreate_KSP(PC);
+PetscErrorCode PCCreate_None(PC), PCCreate_Jacobi(PC), PCCreate_BJacobi(PC), PCCreate_ILU(PC), PCCreate_ICC(PC), PCCreate_SOR(PC), PCCreate_KSP(PC), PCCreate_MG(PC);
 
 #include "petsckrylovfused.h"   /* the optional fused-kernel tables a Vec / Mat type may compose */
 

@@ -172,6 +172,7 @@ static PetscErrorCode hip_mat_option(Mat A, int which, PetscInt *val) {
 /* -mat_hipmi355x_sor <device|host> (default device): where MatSOR runs; 0: the option is not given under this prefix */
 static PetscErrorCode product_route_option(Mat A, const char *prefix, int *route);   /* -mat_hipmi355x_product, with the products below */
 static PetscErrorCode reductions_route_option(Mat A, const char *prefix, int *route);   /* -mat_hipmi355x_reductions, with the reductions below */
+static PetscErrorCode residual_route_option(Mat A, const char *prefix, int *route);   /* -mat_hipmi355x_residual, with MatResidual below */
 static PetscErrorCode sor_route_option(Mat A, const char *prefix, int *route) {
   PetscErrorCode ierr;
   char kind[16] = ""; PetscBool set = PETSC_FALSE;
@@ -199,7 +200,9 @@ static PetscErrorCode MatSetFromOptions_SeqAIJHIP(Mat A) {
     ierr = product_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
     if (route) d->product_route = route;
     ierr = reductions_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
-    if (route) d->reductions_route = route; }
+    if (route) d->reductions_route = route;
+    ierr = residual_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
+    if (route) d->residual_route = route; }
   return 0;
 }
 
@@ -445,6 +448,7 @@ static PetscErrorCode upload_pattern(Mat A, PetscDeviceCtx *dc, UpTick *tk) {
   PetscErrorCode ierr;
   HipAIJ *a = SA(A);
   Mat_SeqAIJHIP *d = SD(A);
+  ierr = residual_route_option(A, NULL, &d->residual_global);CHKERRQ(ierr);   /* the global answer, once per device copy: MatResidual searches no table */
   device_free(A);
   if (a->bs > 1) {   /* BAIJ */
     if (a->bs == 4) {   /* -mat_hipmi355x_baij4 <mfma|fma>: the matrix cores (v_mfma_f64_4x4x4, 16-byte loads: 1.22-1.28 ms at 128^3 nodes, 27
@@ -1066,6 +1070,65 @@ PetscErrorCode MatMultDiagonalScale_HIPMI355X(Mat A, Vec dd, Vec xx, Vec yy, Pet
   HipStateIncrease(yy);
   ierr = PetscLogFlops(2.0 * a->nz - a->nonzerorows + a->m);CHKERRQ(ierr);
   *ok = PETSC_TRUE;
+  return 0;
+}
+
+/* "MatResidual_C": r = b - A x.  Fused: the product's row sum and one subtraction from b_r in the product's own launch
+ * (mi355x_spmv_csr_residual, every row-block form), where MatMult + VecAYPX write the work vector, read it again and read b: the same
+ * bits, two vector passes fewer.  The column-tiled product, the blocked companion and a compressed-row plan have no such epilogue, and
+ * vectors of another type have no device array: MatMult and VecAYPX(r, -1, b) run as they are.  Pending deferred Vec work and stale
+ * device values are settled as in MatMult_SeqAIJHIP: the upload first, the deferred queue by the vectors' accessors.
+ * -mat_hipmi355x_residual <fused|calls> under the matrix's prefix (MatSetFromOptions, at any time), else globally as read when the device
+ * copy was built (upload_pattern): no options table is searched per residual.  README "Multigrid" has the measurement behind the default. */
+#ifndef HIPMI355X_RESIDUAL_DEFAULT
+#define HIPMI355X_RESIDUAL_DEFAULT 1   /* 1 fused, 2 calls */
+#endif
+static PetscErrorCode residual_route_option(Mat A, const char *prefix, int *route) {
+  PetscErrorCode ierr;
+  char kind[16] = ""; PetscBool set = PETSC_FALSE;
+  *route = 0;
+  ierr = PetscOptionsGetString(prefix, "-mat_hipmi355x_residual", kind, sizeof(kind), &set);CHKERRQ(ierr);
+  if (!set) return 0;
+  if (strcmp(kind, "fused") && strcmp(kind, "calls")) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "-mat_hipmi355x_residual <fused|calls>, got %s", kind);
+  *route = strcmp(kind, "calls") ? 1 : 2;
+  return 0;
+}
+static int vec_on_device(Vec v) { return v && strstr(HipObjTypeName(v), "hipmi355x") != NULL; }
+static PetscErrorCode MatResidual_SeqAIJHIP(Mat A, Vec bb, Vec xx, Vec rr) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
+  int route;
+  if (rr == xx || rr == bb) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_IDN, "r must differ from b and from x");
+  ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);   /* (builds the device copy if need be, and with it reads the global option) */
+  route = d->residual_route ? d->residual_route : d->residual_global ? d->residual_global : HIPMI355X_RESIDUAL_DEFAULT;
+  if (route == 1 && a->bs <= 1 && vec_on_device(bb) && vec_on_device(xx) && vec_on_device(rr) &&
+      xx->map->n == a->n && bb->map->n == a->m && rr->map->n == a->m) {
+    if (d->mat.plan && !d->cprow && !d->mat.tiled && !d->b.plan) {
+      const PetscScalar *x, *b; PetscScalar *r; PetscDeviceCtx *dc;
+      ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
+      ierr = VecHIPGetRead(xx, &x);CHKERRQ(ierr);
+      ierr = VecHIPGetRead(bb, &b);CHKERRQ(ierr);
+      ierr = VecHIPGetWrite(rr, &r);CHKERRQ(ierr);
+      ierr = MatTimingBegin(A, dc->h);CHKERRQ(ierr);
+      CHKHIP(mi355x_spmv_csr_residual(dc->h, d->mat.plan, d->mat.i, d->mat.j, d->mat.a, x, b, r));
+      ierr = MatTimingEnd(A, dc->h);CHKERRQ(ierr);
+      ierr = VecHIPRestoreWrite(rr);CHKERRQ(ierr);
+      HipStateIncrease(rr);
+      ierr = PetscLogFlops(2.0 * a->nz - a->nonzerorows + a->m);CHKERRQ(ierr);
+      d->residual_fused++;
+      return 0;
+    }
+  }
+  ierr = MatMult_SeqAIJHIP(A, xx, rr);CHKERRQ(ierr);   /* (MatMult's own slot: sizes were checked by the caller) */
+  HipStateIncrease(rr);
+  ierr = VecAYPX(rr, -1.0, bb);CHKERRQ(ierr);
+  d->residual_calls++;
+  return 0;
+}
+PetscErrorCode MatHIPMI355XGetResidualCounts(Mat A, PetscInt *fused, PetscInt *calls) {
+  if (!A || A->ops->mult != MatMult_SeqAIJHIP) SETERRQ(A ? HipObjComm(A) : 0, PETSC_ERR_ARG_WRONG, "not a sequential HIPMI355X AIJ matrix");
+  if (fused) *fused = SD(A)->residual_fused;
+  if (calls) *calls = SD(A)->residual_calls;
   return 0;
 }
 
@@ -2434,6 +2497,7 @@ static PetscErrorCode create_common(Mat B, const char *tname, PetscInt bs) {
     ierr = PetscObjectComposeFunction((PetscObject)B, "MatGetFactorAvailable_petsc_C", "MatGetFactorAvailable_seqaijhipmi355x_petsc", (PetscVoidFunction)MatGetFactorAvailable_seqaijhipmi355x_petsc);CHKERRQ(ierr);
     ierr = PetscObjectComposeFunction((PetscObject)B, "MatSeqAIJSetPreallocation_C", "MatSeqAIJSetPreallocation_SeqAIJHIP", (PetscVoidFunction)MatSeqAIJSetPreallocation_SeqAIJHIP);CHKERRQ(ierr);
     ierr = PetscObjectComposeFunction((PetscObject)B, "MatSeqAIJSetPreallocationCSR_C", "MatSeqAIJSetPreallocationCSR_SeqAIJHIP", (PetscVoidFunction)MatSeqAIJSetPreallocationCSR_SeqAIJHIP);CHKERRQ(ierr);
+    ierr = PetscObjectComposeFunction((PetscObject)B, "MatResidual_C", "MatResidual_SeqAIJHIP", (PetscVoidFunction)MatResidual_SeqAIJHIP);CHKERRQ(ierr);   /* (the block type composes none: MatResidual takes the two calls) */
   } else {
     /* block ILU(k) of the block type (host/bilu.c): ILU only; ICC and LU answer PETSC_ERR_SUP */
     ierr = PetscObjectComposeFunction((PetscObject)B, "MatGetFactor_petsc_C", "MatGetFactor_seqbaijhipmi355x_petsc", (PetscVoidFunction)MatGetFactor_seqbaijhipmi355x_petsc);CHKERRQ(ierr);
@@ -2458,7 +2522,7 @@ static PetscErrorCode MatDuplicate_SeqAIJHIP(Mat A, MatDuplicateOption op, Mat *
   if (op != MAT_COPY_VALUES) memset(SA(B)->a, 0, sizeof(PetscScalar) * (size_t)a->nz * (size_t)(a->bs > 1 ? a->bs * a->bs : 1));
   memcpy(SD(B)->opt, SD(A)->opt, sizeof(SD(A)->opt)); memcpy(SD(B)->opt_set, SD(A)->opt_set, sizeof(SD(A)->opt_set));
   SD(B)->cprow = SD(A)->cprow; SD(B)->sor.route = SD(A)->sor.route; SD(B)->product_route = SD(A)->product_route;
-  SD(B)->reductions_route = SD(A)->reductions_route;
+  SD(B)->reductions_route = SD(A)->reductions_route; SD(B)->residual_route = SD(A)->residual_route;
   SA(B)->keepnonzeropattern = a->keepnonzeropattern;
   *M = B;
   return 0;

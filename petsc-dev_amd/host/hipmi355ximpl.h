@@ -329,6 +329,11 @@ typedef struct {
    * and their locations go to before the finishing pass or the copy to the caller's host array (red_cap bytes; goes with the pattern) */
   int reductions_route;
   void *red_work; size_t red_cap;
+  /* "MatResidual_C" (host/aijhip.c): -mat_hipmi355x_residual <fused|calls> as MatSetFromOptions read it under the matrix's prefix (1 fused,
+   * 2 calls, 0: not given there), the global answer as read when the device copy was built, and how many residuals took the fused kernel /
+   * the product and VecAYPX */
+  int residual_route, residual_global;
+  PetscInt residual_fused, residual_calls;
   PetscInt opt[8]; PetscBool opt_set[8];   /* the type's options as MatSetFromOptions read them under the matrix's prefix (host/aijhip.c) */
   /* per-launch device timing for bench.py (hipEvent pairs on the compute stream) */
   PetscBool timing; PetscInt time_n, time_cap; mi355x_event_t *time_ev;

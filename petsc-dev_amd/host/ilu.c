@@ -40,6 +40,7 @@ EXTERN_C_END
  * later application (MatSolve below), ILU(0) and ICC(0) alike. */
 static HipTriFactors **tri_watch = NULL;
 static int tri_watch_cap = 0;
+static PetscInt tri_live = 0;   /* factors MatGetFactor made and HipTriFactorsDestroy has not released yet (HIPMI355XGetLiveFactors) */
 /* the list grows with the number of live factors (multigrid levels, fieldsplit blocks, many KSPs); a factor that cannot be put on
  * it (out of memory) never runs the sync-free kernels unwatched: it takes the level launches */
 void HipTriWatchAdd(HipTriFactors *f) {
@@ -138,7 +139,14 @@ PetscErrorCode HipTriFactorsDestroy(HipTriFactors **pf) {
   tri_free_transpose(f, 1);
   HipFree(f->blk);
   HipFree(f);
+  tri_live--;
   *pf = NULL;
+  return 0;
+}
+/* life-cycle tests: ILU / ICC factors of the AIJ type alive in this process, and how many of them sit on the watch list */
+PetscErrorCode HIPMI355XGetLiveFactors(PetscInt *live, PetscInt *watched) {
+  if (live) *live = tri_live;
+  if (watched) { *watched = 0; for (int i = 0; i < tri_watch_cap; i++) if (tri_watch[i]) (*watched)++; }
   return 0;
 }
 
@@ -1201,6 +1209,7 @@ PetscErrorCode MatGetFactor_seqaijhipmi355x_petsc(Mat A, MatFactorType ftype, Ma
   ierr = PetscMalloc(sizeof(*f), &f);CHKERRQ(ierr);
   memset(f, 0, sizeof(*f));
   f->kind = ftype; f->factored_state = -1;
+  tri_live++;
 #if defined(PETSCHIPMI355X_WITH_PETSC)
   ierr = MatGetFactor_seqaij_petsc(A, ftype, B);CHKERRQ(ierr);           /* the parent's factor matrix (MATSEQAIJ / MATSEQSBAIJ) with its host routines */
   f->parent_destroy = (*B)->ops->destroy;

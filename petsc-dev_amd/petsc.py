@@ -77,6 +77,13 @@ _SIG = {
     "KSPHIPMI355XGetFusedStepCounts": [vp, P(i32), P(i32)],
     "KSPSetConvergenceTest": [vp, vp, vp, vp], "KSPLSQRSetStandardErrorVec": [vp, vp], "KSPLSQRGetStandardErrorVec": [vp, P(vp)],
     "KSPLSQRGetArnorm": [vp, P(dbl), P(dbl), P(dbl)],
+    "MatRestrict": [vp, vp, vp], "MatInterpolate": [vp, vp, vp], "MatInterpolateAdd": [vp, vp, vp, vp], "MatResidual": [vp, vp, vp, vp],
+    "MatHIPMI355XGetResidualCounts": [vp, P(i32), P(i32)], "HIPMI355XGetLiveFactors": [P(i32), P(i32)],
+    "PCMGSetLevels": [vp, i32, vp], "PCMGGetLevels": [vp, P(i32)], "PCMGSetType": [vp, i32], "PCMGSetCycleType": [vp, i32],
+    "PCMGMultiplicativeSetCycles": [vp, i32], "PCMGSetNumberSmoothDown": [vp, i32], "PCMGSetNumberSmoothUp": [vp, i32],
+    "PCMGSetGalerkin": [vp, i32], "PCMGSetInterpolation": [vp, i32, vp], "PCMGSetRestriction": [vp, i32, vp],
+    "PCMGSetResidual": [vp, i32, vp, vp], "PCMGDefaultResidual": [vp, vp, vp, vp], "PCMGGetSmoother": [vp, i32, P(vp)],
+    "PCMGGetSmootherDown": [vp, i32, P(vp)], "PCMGGetSmootherUp": [vp, i32, P(vp)], "PCMGGetCoarseSolve": [vp, P(vp)], "PCSetUp": [vp], "PCGetOperators": [vp, P(vp), P(vp), P(i32)],
     "KSPSetUp": [vp], "KSPSolve": [vp, vp, vp], "KSPGetIterationNumber": [vp, P(i32)], "KSPGetResidualNorm": [vp, P(dbl)],
     "KSPGetConvergedReason": [vp, P(i32)], "KSPSetResidualHistory": [vp, vp, i32, i32],
     "KSPGetResidualHistory": [vp, P(vp), P(i32)], "KSPDestroy": [P(vp)],
@@ -100,6 +107,8 @@ MAT_KEEP_NONZERO_PATTERN = 9          # MatOption (petscmini.h)
 SOR_FORWARD_SWEEP, SOR_BACKWARD_SWEEP, SOR_SYMMETRIC_SWEEP = 1, 2, 3
 SOR_LOCAL_FORWARD_SWEEP, SOR_LOCAL_BACKWARD_SWEEP, SOR_LOCAL_SYMMETRIC_SWEEP = 4, 8, 12
 SOR_ZERO_INITIAL_GUESS, SOR_EISENSTAT, SOR_APPLY_UPPER, SOR_APPLY_LOWER = 16, 32, 64, 128
+PC_MG_MULTIPLICATIVE, PC_MG_ADDITIVE, PC_MG_FULL, PC_MG_KASKADE = 0, 1, 2, 3   # PCMGType (petscmini.h)
+PC_MG_CYCLE_V, PC_MG_CYCLE_W = 1, 2                                           # PCMGCycleType (petscmini.h)
 
 
 class PetscError(RuntimeError):
@@ -407,6 +416,28 @@ class Mat:
         lib().MatHIPMI355XGetProductCounts(self.h, *[C.byref(q) for q in v])
         return tuple(q.value for q in v)
 
+    def residual(self, b, x, r):
+        """r = b - self x: the type's own method, or MatMult and VecAYPX(r, -1, b) (MatResidual)"""
+        lib().MatResidual(self.h, b.h, x.h, r.h)
+
+    def restrict(self, x, y):
+        """y = self x or self^T x, whichever fits the sizes (MatRestrict)"""
+        lib().MatRestrict(self.h, x.h, y.h)
+
+    def interpolate(self, x, y):
+        """y = self x or self^T x, whichever fits the sizes (MatInterpolate)"""
+        lib().MatInterpolate(self.h, x.h, y.h)
+
+    def interpolate_add(self, x, y, w):
+        """w = y + self x or y + self^T x, whichever fits the sizes; w may be y (MatInterpolateAdd)"""
+        lib().MatInterpolateAdd(self.h, x.h, y.h, w.h)
+
+    def residual_counts(self):
+        """residuals of a sequential AIJ matrix that took the fused kernel / MatMult and VecAYPX, so far (MatHIPMI355XGetResidualCounts)"""
+        f, c = i32(), i32()
+        lib().MatHIPMI355XGetResidualCounts(self.h, C.byref(f), C.byref(c))
+        return f.value, c.value
+
     def csr(self):
         """copies of a sequential matrix's host arrays: row pointer, columns, values (MatSeqAIJGetArrays)"""
         m, pi_, pj, pa = i32(), vp(), vp(), vp()
@@ -499,6 +530,78 @@ class PC:
         lib().PCKSPGetKSP(self.h, C.byref(k))
         return KSP(handle=k)
 
+    # ---- PCMG (type "mg"); the PC keeps a Python reference to the matrix in each slot it was handed one for; a new one replaces the old
+    def _hold(self, slot, M):
+        self.__dict__.setdefault("_mats", {})[slot] = M
+        return M.h if M is not None else None
+
+    def set_from_options(self):
+        lib().PCSetFromOptions(self.h)
+
+    def set_up(self):
+        lib().PCSetUp(self.h)
+
+    def mg_set_levels(self, n):
+        lib().PCMGSetLevels(self.h, int(n), None)
+
+    def mg_get_levels(self):
+        n = i32()
+        lib().PCMGGetLevels(self.h, C.byref(n))
+        return n.value
+
+    def mg_set_type(self, form):
+        """PCMGSetType: "multiplicative", "additive", "full" ("kaskade": PETSC_ERR_SUP) or the PCMGType number"""
+        names = {"multiplicative": PC_MG_MULTIPLICATIVE, "additive": PC_MG_ADDITIVE, "full": PC_MG_FULL, "kaskade": PC_MG_KASKADE}
+        lib().PCMGSetType(self.h, names[form] if isinstance(form, str) else int(form))
+
+    def mg_set_cycle_type(self, c):
+        """PCMGSetCycleType: "v", "w" or the PCMGCycleType number"""
+        names = {"v": PC_MG_CYCLE_V, "w": PC_MG_CYCLE_W}
+        lib().PCMGSetCycleType(self.h, names[c] if isinstance(c, str) else int(c))
+
+    def mg_set_cycles(self, n):
+        """PCMGMultiplicativeSetCycles: cycles per application of the multiplicative form"""
+        lib().PCMGMultiplicativeSetCycles(self.h, int(n))
+
+    def mg_set_number_smooth(self, down=None, up=None):
+        """PCMGSetNumberSmoothDown / PCMGSetNumberSmoothUp; unequal counts give every level a second smoother"""
+        if down is not None:
+            lib().PCMGSetNumberSmoothDown(self.h, int(down))
+        if up is not None:
+            lib().PCMGSetNumberSmoothUp(self.h, int(up))
+
+    def mg_set_galerkin(self, flag=True):
+        lib().PCMGSetGalerkin(self.h, 1 if flag else 0)
+
+    def mg_set_interpolation(self, l, Pm):
+        lib().PCMGSetInterpolation(self.h, int(l), self._hold(("interpolation", int(l)), Pm))
+
+    def mg_set_restriction(self, l, Rm):
+        lib().PCMGSetRestriction(self.h, int(l), self._hold(("restriction", int(l)), Rm))
+
+    def mg_set_residual(self, l, A=None):
+        """PCMGSetResidual with PCMGDefaultResidual (MatResidual) on A (None: the level's operator)"""
+        lib().PCMGSetResidual(self.h, int(l), C.cast(lib().raw("PCMGDefaultResidual"), vp), self._hold(("residual", int(l)), A))
+
+    def _mg_ksp(self, name, *a):
+        k = vp()
+        getattr(lib(), name)(self.h, *a, C.byref(k))
+        return KSP(handle=k)
+
+    def mg_get_smoother(self, l):
+        """PCMGGetSmoother: level l's (down) solver, prefix "<pc prefix>mg_levels_<l>_" ("mg_coarse_" for level 0); a borrowed KSP"""
+        return self._mg_ksp("PCMGGetSmoother", int(l))
+
+    def mg_get_smoother_down(self, l):
+        return self._mg_ksp("PCMGGetSmootherDown", int(l))
+
+    def mg_get_smoother_up(self, l):
+        """PCMGGetSmootherUp: level l's up smoother, made a solver of its own by this call; a borrowed KSP"""
+        return self._mg_ksp("PCMGGetSmootherUp", int(l))
+
+    def mg_get_coarse_solve(self):
+        return self._mg_ksp("PCMGGetCoarseSolve")
+
     def ksp_total_iterations(self):
         """PCKSPGetTotalIterations: the inner iterations of all applications of a PC of type "ksp" so far"""
         n = i32()
@@ -514,6 +617,7 @@ class KSP:
         """a new KSP on comm, or (handle given) a borrowed one that is never destroyed from here"""
         self._hist = None
         self._modify_pc = None
+        self._pc = None
         self.own = handle is None
         if handle is not None:
             self.h = handle
@@ -532,9 +636,12 @@ class KSP:
         lib().KSPSetType(self.h, t.encode())
 
     def get_pc(self):
+        """the KSP's PC: one wrapper per KSP, so that what the PC holds on to (the matrices of a PCMG) lives as long as the KSP's wrapper"""
         pc = vp()
         lib().KSPGetPC(self.h, C.byref(pc))
-        return PC(pc)
+        if self._pc is None or self._pc.h.value != pc.value:
+            self._pc = PC(pc)
+        return self._pc
 
     def set_pc_type(self, t):
         pc = vp()
