@@ -749,6 +749,29 @@ int mi355x_trisolve_apply_levels(mi355x_handle_t h, mi355x_trisolve_plan_t lower
 /* development / tests: raise a plan's abort flag as a dependency wait that gave up would */
 int mi355x_trisolve_debug_set_aborted(mi355x_trisolve_plan_t plan, int value);
 
+/* ---- coarsening for smoothed aggregation (csrc/coarsen.hip; PCGAMG, harness/gamg.c) -------- */
+/* Strength of connection over a square CSR matrix: for the stored entry t = (i, j)
+ *   strong[t] = (j != i) && (fabs(a_t) > theta * sqrt(fabs(diag[i]) * fabs(diag[j])))
+ * evaluated in double in exactly that order; a comparison with a NaN on either side is false, a zero diagonal entry makes every
+ * nonzero off-diagonal entry of its row and column strong.  diag: what mi355x_csr_get_diagonal leaves (0 for a row without one).
+ * One byte per stored entry, byte for byte the host twin's.  m == 0 launches nothing; m < 0 or a null array: hipErrorInvalidValue. */
+int mi355x_csr_strength(mi355x_handle_t h, int m, const int *ai, const int *aj, const double *aa, const double *diag, double theta,
+                        unsigned char *strong);
+int mi355x_csr_strength_host(int m, const int *ai, const int *aj, const double *aa, const double *diag, double theta, unsigned char *strong);
+/* Aggregation by a distance-2 maximal independent set of the undirected graph i ~ j <=> the stored entry (i, j) or (j, i) is strong
+ * (the pattern need not be symmetric).  Node i's priority is the key (mix(i) >> 2) << 32 | i with the 32-bit finaliser
+ * h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16.  The roots are the greedy set: nodes visited in decreasing
+ * key, a node is a root iff no root lies within distance 2 (paths through non-roots count).  A root's aggregate number is its rank
+ * among the roots in index order; a node with adjacent roots joins the one with the largest key, any other node the root with the
+ * largest key among its neighbours' choices; a node without strong connections is its own root.  agg[i] in [0, *nagg).
+ * The host twin is that loop.  The device entry runs rounds of two max-propagation steps (pull over a row, push with a 64-bit
+ * atomicMax) and one decision step, the undecided count read once per round; *rounds = rounds taken, at most
+ * mi355x_coarsen_round_cap() -- beyond it hipErrorNotReady and nothing is continued.  ai, aj, strong, agg: device arrays for the
+ * device entry; nagg, rounds: host.  agg, *nagg equal the host twin's as integers.  m == 0 launches nothing. */
+int mi355x_coarsen_mis2(mi355x_handle_t h, int m, const int *ai, const int *aj, const unsigned char *strong, int *agg, int *nagg, int *rounds);
+int mi355x_coarsen_mis2_host(int m, const int *ai, const int *aj, const unsigned char *strong, int *agg, int *nagg);
+int mi355x_coarsen_round_cap(void);
+
 /* ---- halo pack / unpack (VecScatter) ---------------------------------- */
 /* Pack_1    src/vec/vec/utils/vpscat.c:493   buf[k] = x[idx[k]] */
 int mi355x_pack(mi355x_handle_t h, size_t n, const int *idx, const double *x, double *buf);

@@ -121,6 +121,11 @@ PetscErrorCode MatHIPMI355XGetProductCounts(Mat C, PetscInt *symbolic_builds, Pe
  * blocked companion, compressed rows, vectors of another type) -- the same bits either way.  -mat_hipmi355x_residual <fused|calls>.
  * The counts: residuals of this matrix that took the fused kernel / the two calls, so far. */
 PetscErrorCode MatHIPMI355XGetResidualCounts(Mat A, PetscInt *fused, PetscInt *calls);
+/* MATSEQAIJHIPMI355X composes "MatCoarsenAggregate_C" (Mat A, PetscReal threshold, PetscInt *nagg, PetscInt agg[]): strength mask and
+ * distance-2 MIS aggregation over the device copy (mi355x_csr_strength, mi355x_coarsen_mis2), or their host twins over the host copy
+ * with -mat_hipmi355x_coarsen host (the default in a process without a device) -- the same integers either way.  The counts:
+ * coarsenings per route and the device rounds of the last one, of matrix A so far; A == NULL: of every matrix of the process. */
+PetscErrorCode MatHIPMI355XGetCoarsenCounts(Mat A, PetscInt *device, PetscInt *host, PetscInt *rounds);
 PetscErrorCode MatHIPMI355XGetInodeInfo(Mat A, PetscInt *nodes, PetscInt *groups, PetscInt *shared_indices);   /* Mat_CheckInode's node count; groups / column indices the device plan stores once per group */
 PetscErrorCode MatHIPMI355XGetBlockedInfo(Mat A, PetscInt *bs, PetscInt *nblocks);   /* blocked companion of an AIJ matrix whose nodes are complete bs x bs blocks (products by the BAIJ kernel); 0, 0: not in use */
 PetscErrorCode MatHIPMI355XGetTiledInfo(Mat A, PetscInt *staged, PetscInt *remainder);   /* column-tiled product (x tiles in LDS): nonzeros gathering from LDS / left to the row-block kernel; 0, 0: not in use */

@@ -150,6 +150,7 @@ typedef const char *PCType;
 #define PCICC      "icc"       /* ICC(0), natural ordering, sequential AIJ */
 #define PCSOR      "sor"       /* SOR / SSOR through the operator's MatSOR (src/ksp/pc/impls/sor/sor.c) */
 #define PCKSP      "ksp"       /* a Krylov solver as the preconditioner: every application is a KSPSolve of the inner KSP (src/ksp/pc/impls/ksp/pcksp.c) */
+#define PCGAMG     "gamg"      /* smoothed aggregation: builds the hierarchy of a PCMG from the operator (gamg.c) */
 #define PCMG       "mg"        /* multigrid cycles over level KSPs, grid transfers given as matrices (src/ksp/pc/impls/mg/mg.c) */
 
 /* ---- Sys ----------------------------------------------------------------------------------- */
@@ -331,6 +332,10 @@ PetscErrorCode MatDiagonalScale(Mat A, Vec l, Vec r);   /* A <- diag(l) A diag(r
  * that stores fewer entries than the matrix has columns compete with one implicit 0.0 at its smallest missing column.
  * MatGetRowSum is MatMult with a vector of ones.  MatGetColumnNorms: NORM_1, NORM_2 or NORM_INFINITY of every column into norms[N]. */
 PetscErrorCode MatNorm(Mat A, NormType type, PetscReal *nrm);
+/* aggregates for smoothed aggregation: agg[i] in [0, *nagg) for every row of a square matrix, by the strength mask
+ * |a_ij| > threshold sqrt(|a_ii| |a_jj|) and a distance-2 maximal independent set (the type's "MatCoarsenAggregate_C"; a type
+ * without one: PETSC_ERR_SUP) */
+PetscErrorCode MatCoarsenAggregate(Mat A, PetscReal threshold, PetscInt *nagg, PetscInt agg[]);
 PetscErrorCode MatGetRowMaxAbs(Mat A, Vec v, PetscInt idx[]);
 PetscErrorCode MatGetRowMax(Mat A, Vec v, PetscInt idx[]);
 PetscErrorCode MatGetRowMin(Mat A, Vec v, PetscInt idx[]);
@@ -420,6 +425,20 @@ PetscErrorCode PCMGGetSmoother(PC pc, PetscInt l, KSP *ksp);
 PetscErrorCode PCMGGetSmootherDown(PC pc, PetscInt l, KSP *ksp);
 PetscErrorCode PCMGGetSmootherUp(PC pc, PetscInt l, KSP *ksp);
 PetscErrorCode PCMGGetCoarseSolve(PC pc, KSP *ksp);
+/* PCGAMG (gamg.c; the reference's src/ksp/pc/impls/gamg/): smoothed aggregation that fills a PCMG and then is one -- cycle types, the
+ * PCMG calls above and the level solvers' prefixes mg_coarse_ / mg_levels_<l>_ are PCMG's own.  Sequential AIJ operators with the
+ * constant as near-null space.  Per level, from the PC's pmat: aggregates by MatCoarsenAggregate(A_l, threshold); the tentative
+ * prolongator T with one entry 1/sqrt(|aggregate|) per row; with nsmooths == 1 P = T - (4 / (3 rho)) D^-1 A_l T, rho the infinity
+ * norm of D^-1 A_l; A_{l+1} = MatPtAP(A_l, P).  Coarsening stops at n_l <= coarse_eq_limit, at the level cap (-pc_mg_levels), or when
+ * an aggregation stalls.  Smoothers default to chebychev + jacobi, two steps, eigenvalue bounds (rho_l / 10, rho_l); the coarse level to
+ * preonly + ILU with as many levels of fill as it has rows.  PCGAMGSetReuseInterpolation: a later set-up keeps aggregates and
+ * prolongators and only refills the Galerkin operators.  PCGAMGGetLevelSizes: sizes[0] is the fine level; at most maxn are written. */
+PetscErrorCode PCGAMGSetThreshold(PC pc, PetscReal threshold);          /* -pc_gamg_threshold, default 0 */
+PetscErrorCode PCGAMGSetCoarseEqLimit(PC pc, PetscInt n);               /* -pc_gamg_coarse_eq_limit, default 50 */
+PetscErrorCode PCGAMGSetNlevels(PC pc, PetscInt n);                     /* -pc_mg_levels, default 25 */
+PetscErrorCode PCGAMGSetNSmooths(PC pc, PetscInt n);                    /* -pc_gamg_agg_nsmooths, 0 or 1, default 1 */
+PetscErrorCode PCGAMGSetReuseInterpolation(PC pc, PetscBool reuse);     /* -pc_gamg_reuse_interpolation, default false */
+PetscErrorCode PCGAMGGetLevelSizes(PC pc, PetscInt maxn, PetscInt *nlevels, PetscInt sizes[]);
 
 /* ---- KSP (include/petscksp.h) ---------------------------------------------------------------- */
 PetscErrorCode KSPCreate(PetscComm comm, KSP *ksp);

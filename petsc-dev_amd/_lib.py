@@ -188,6 +188,11 @@ KERNEL_API = {
     "mi355x_spgemm_numeric": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "mi355x_spmv_plan_rows": [vp, C.POINTER(vp), pi32],
     "mi355x_mat_row_reduce": [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+    "mi355x_csr_strength": [vp, i32, vp, vp, vp, vp, dbl, vp],
+    "mi355x_csr_strength_host": [i32, vp, vp, vp, vp, dbl, vp],
+    "mi355x_coarsen_mis2": [vp, i32, vp, vp, vp, vp, pi32, pi32],
+    "mi355x_coarsen_mis2_host": [i32, vp, vp, vp, vp, pi32],
+    "mi355x_coarsen_round_cap": [],
     "mi355x_pack": [vp, sz, vp, vp, vp],
     "mi355x_unpack_insert": [vp, sz, vp, vp, vp],
     "mi355x_unpack_add": [vp, sz, vp, vp, vp],

@@ -455,6 +455,22 @@ PetscErrorCode MatPtAP(Mat A, Mat P, MatReuse scall, PetscReal fill, Mat *C) {
   return 0;
 }
 
+/* Aggregates for smoothed aggregation (what PCGAMG asks of a level operator; gamg.c): agg[i] in [0, *nagg) for every row of the square
+ * matrix A, from the strength mask |a_ij| > threshold sqrt(|a_ii| |a_jj|) and a distance-2 maximal independent set of its graph
+ * (include/mi355x_kernels.h states the rule).  Dispatches to the type's "MatCoarsenAggregate_C"; a type without one: PETSC_ERR_SUP. */
+PetscErrorCode MatCoarsenAggregate(Mat A, PetscReal threshold, PetscInt *nagg, PetscInt agg[]) {
+  PetscVoidFunction f = NULL;
+  PetscErrorCode ierr;
+  MatTypeSet(A, 1); MatAssembled(A);
+  if (!nagg) SETERRQ(A->comm, PETSC_ERR_ARG_NULL, "Null pointer for the number of aggregates");
+  if (A->factortype) SETERRQ(A->comm, PETSC_ERR_ARG_WRONGSTATE, "Not for factored matrix");
+  if (!(threshold >= 0.0)) SETERRQ(A->comm, PETSC_ERR_ARG_OUTOFRANGE, "threshold %g must be >= 0", (double)threshold);
+  if (!agg && A->rmap->n > 0) SETERRQ(A->comm, PETSC_ERR_ARG_NULL, "Null pointer for the aggregate numbers");
+  ierr = PetscObjectQueryFunction((PetscObject)A, "MatCoarsenAggregate_C", &f);CHKERRQ(ierr);
+  if (!f) SETERRQ(A->comm, PETSC_ERR_SUP, "MatCoarsenAggregate for Mat type %s", A->type_name);
+  return ((PetscErrorCode (*)(Mat, PetscReal, PetscInt *, PetscInt[]))f)(A, threshold, nagg, agg);
+}
+
 /* ---- grid transfers and the residual (matrix.c MatRestrict, MatInterpolate, MatInterpolateAdd, MatResidual): what PCMG calls.  One
  * matrix serves as interpolation (coarse -> fine) and as restriction (fine -> coarse); the direction is chosen from the sizes: the
  * product when the matrix's rows match the output, the transposed product otherwise. */

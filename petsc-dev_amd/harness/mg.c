@@ -23,6 +23,7 @@ typedef struct {
   Mat interpolate, restrct;    /* the user's, each with a reference of the PC's own; NULL: the other one serves (mg_interp, mg_restr) */
   PetscBool optd, optu;        /* the options of smoothd / smoothu were read (at the solver's first set-up, never again) */
   Mat A;                       /* level < n-1 with Galerkin: P^T A P, the PC's own */
+  PetscBool Aready;            /* A was handed over just computed (PCMGAdoptGalerkin_Private): the next set-up takes it as it is */
   PCMGResidualFn residual; Mat resmat;   /* PCMGSetResidual; NULL: MatResidual on the level's operator */
 } PC_MG_Level;
 typedef struct {
@@ -32,11 +33,13 @@ typedef struct {
   PCMGCycleType cycle;
   PetscInt cycles;             /* multiplicative cycles per application */
   PetscBool galerkin;
+  void *layer;                 /* the data of a type built on this one (PCGAMG, gamg.c); NULL for a plain PCMG */
 } PC_MG;
+static PetscErrorCode PCApply_MG(PC pc, Vec b, Vec y);
 
 #define PCMGValid(pc, mg) do { \
   if (!(pc)) SETERRQ(0, PETSC_ERR_ARG_NULL, "Null PC"); \
-  if (strcmp((pc)->type_name, PCMG)) SETERRQ((pc)->comm, PETSC_ERR_ARG_WRONG, "PC of type %s is not a PCMG", (pc)->type_name); \
+  if (strcmp((pc)->type_name, PCMG) && (pc)->ops->apply != PCApply_MG) SETERRQ((pc)->comm, PETSC_ERR_ARG_WRONG, "PC of type %s is not a PCMG", (pc)->type_name); \
   (mg) = (PC_MG *)(pc)->data; } while (0)
 #define PCMGLevel(pc, mg, l) do { \
   if (!(mg)->n) SETERRQ((pc)->comm, PETSC_ERR_ORDER, "PCMGSetLevels() first"); \
@@ -229,7 +232,8 @@ static PetscErrorCode PCSetUp_MG(PC pc) {
     if (mg->galerkin) {   /* A_{l-1} = P_l^T A_l P_l: symbolic and numeric the first time, numeric only from then on */
       Mat Af = l == n - 1 ? pc->pmat : mg->lev[l].A, P = mg_interp(&mg->lev[l]);
       if (P->rmap->N != Af->cmap->N) SETERRQ(pc->comm, PETSC_ERR_SUP, "Galerkin operators need the transfer of level %d stored as the interpolation (%d rows), got %d x %d", (int)l, Af->cmap->N, P->rmap->N, P->cmap->N);
-      ierr = MatPtAP(Af, P, c->A ? MAT_REUSE_MATRIX : MAT_INITIAL_MATRIX, (PetscReal)PETSC_DEFAULT, &c->A);CHKERRQ(ierr);
+      if (c->A && c->Aready) c->Aready = PETSC_FALSE;
+      else { ierr = MatPtAP(Af, P, c->A ? MAT_REUSE_MATRIX : MAT_INITIAL_MATRIX, (PetscReal)PETSC_DEFAULT, &c->A);CHKERRQ(ierr); }
       ierr = KSPSetOperators(c->smoothd, c->A, c->A, SAME_NONZERO_PATTERN);CHKERRQ(ierr);
     } else {
       if (!c->smoothd->pc || !c->smoothd->pc->mat) SETERRQ(pc->comm, PETSC_ERR_ARG_WRONGSTATE, "level %d has no operators: KSPSetOperators() on its smoother, or PCMGSetGalerkin()", (int)(l - 1));
@@ -307,12 +311,11 @@ static PetscErrorCode PCApply_MG(PC pc, Vec b, Vec y) {
   return 0;
 }
 
-static PetscErrorCode PCSetFromOptions_MG(PC pc) {
+/* -pc_mg_type, -pc_mg_cycle_type, -pc_mg_multiplicative_cycles: what needs no levels */
+PetscErrorCode PCMGCycleOptions_Private(PC pc) {
   PetscErrorCode ierr;
   PC_MG *mg = (PC_MG *)pc->data;
   PetscInt iv; PetscBool set; char t[32];
-  ierr = PetscOptionsGetInt(pc->prefix, "-pc_mg_levels", &iv, &set);CHKERRQ(ierr);
-  if (set && iv != mg->n) { ierr = PCMGSetLevels(pc, iv, NULL);CHKERRQ(ierr); }
   ierr = PetscOptionsGetString(pc->prefix, "-pc_mg_type", t, sizeof(t), &set);CHKERRQ(ierr);
   if (set) {
     static const char *const names[] = {"multiplicative", "additive", "full", "kaskade"};
@@ -329,6 +332,15 @@ static PetscErrorCode PCSetFromOptions_MG(PC pc) {
   }
   ierr = PetscOptionsGetInt(pc->prefix, "-pc_mg_multiplicative_cycles", &iv, &set);CHKERRQ(ierr);
   if (set) { ierr = PCMGMultiplicativeSetCycles(pc, iv);CHKERRQ(ierr); }
+  return 0;
+}
+static PetscErrorCode PCSetFromOptions_MG(PC pc) {
+  PetscErrorCode ierr;
+  PC_MG *mg = (PC_MG *)pc->data;
+  PetscInt iv; PetscBool set; char t[32];
+  ierr = PetscOptionsGetInt(pc->prefix, "-pc_mg_levels", &iv, &set);CHKERRQ(ierr);
+  if (set && iv != mg->n) { ierr = PCMGSetLevels(pc, iv, NULL);CHKERRQ(ierr); }
+  ierr = PCMGCycleOptions_Private(pc);CHKERRQ(ierr);
   ierr = PetscOptionsGetString(pc->prefix, "-pc_mg_galerkin", t, sizeof(t), &set);CHKERRQ(ierr);
   if (set) mg->galerkin = (PetscBool)(strcmp(t, "0") && strcmp(t, "false"));
   ierr = PetscOptionsGetInt(pc->prefix, "-pc_mg_smoothdown", &iv, &set);CHKERRQ(ierr);
@@ -344,6 +356,22 @@ static PetscErrorCode PCDestroy_MG(PC pc) {
   free(mg); pc->data = NULL;
   return 0;
 }
+/* ---- for the types built on this one (gamg.c) ---- */
+void **PCMGLayerData_Private(PC pc) { return &((PC_MG *)pc->data)->layer; }
+PetscErrorCode PCMGReset_Private(PC pc) {   /* back to "no levels, never set up": the level solvers, vectors, operators and transfers go */
+  PetscErrorCode ierr = mg_free_levels((PC_MG *)pc->data);CHKERRQ(ierr);
+  pc->setupcalled = 0;
+  return 0;
+}
+PetscErrorCode PCMGAdoptGalerkin_Private(PC pc, PetscInt l, Mat A) {   /* A = MatPtAP(A_{l+1}, P_{l+1}, MAT_INITIAL_MATRIX): the PC's own from here on */
+  PC_MG *mg = (PC_MG *)pc->data;
+  PCMGLevel(pc, mg, l);
+  if (mg->lev[l].A) SETERRQ(pc->comm, PETSC_ERR_ARG_WRONGSTATE, "level %d has a Galerkin operator", (int)l);
+  mg->lev[l].A = A; mg->lev[l].Aready = PETSC_TRUE;
+  return 0;
+}
+PetscErrorCode PCSetUp_MG_Private(PC pc) { return PCSetUp_MG(pc); }
+PetscErrorCode PCDestroy_MG_Private(PC pc) { return PCDestroy_MG(pc); }
 PetscErrorCode PCCreate_MG(PC pc) {
   PC_MG *mg;
   PetscErrorCode ierr = PetscMalloc(sizeof(*mg), &mg);CHKERRQ(ierr);

@@ -43,6 +43,7 @@ PetscErrorCode PetscMiniInitialize(void) {
   ierr = PCRegister(PCSOR, 0, "PCCreate_SOR", PCCreate_SOR);CHKERRQ(ierr);
   ierr = PCRegister(PCKSP, 0, "PCCreate_KSP", PCCreate_KSP);CHKERRQ(ierr);
   ierr = PCRegister(PCMG, 0, "PCCreate_MG", PCCreate_MG);CHKERRQ(ierr);           /* mg.c */
+  ierr = PCRegister(PCGAMG, 0, "PCCreate_GAMG", PCCreate_GAMG);CHKERRQ(ierr);     /* gamg.c */
   ierr = KSPRegister(KSPCG, 0, "KSPCreate_CG", KSPCreate_CG);CHKERRQ(ierr);
   ierr = KSPRegister(KSPGROPPCG, 0, "KSPCreate_GROPPCG", KSPCreate_GROPPCG);CHKERRQ(ierr);
   ierr = KSPRegister(KSPPIPECG, 0, "KSPCreate_PIPECG", KSPCreate_PIPECG);CHKERRQ(ierr);

@@ -249,7 +249,15 @@ PetscErrorCode KSP_MatMultTranspose(KSP ksp, Mat A, Vec x, Vec y);
 PetscErrorCode KSP_PCApplyTranspose(KSP ksp, Vec x, Vec y);
 PetscErrorCode KSP_PCApplyBAorAB(KSP ksp, Vec x, Vec y, Vec w);
 PetscErrorCode KSPCreate_CG(KSP), KSPCreate_GROPPCG(KSP), KSPCreate_PIPECG(KSP), KSPCreate_GMRES(KSP), KSPCreate_BCGS(KSP), KSPCreate_PREONLY(KSP), KSPCreate_Chebychev(KSP), KSPCreate_Richardson(KSP), KSPCreate_MINRES(KSP), KSPCreate_TFQMR(KSP), KSPCreate_CGS(KSP), KSPCreate_BICG(KSP), KSPCreate_LSQR(KSP), KSPCreate_FGMRES(KSP);
-PetscErrorCode PCCreate_None(PC), PCCreate_Jacobi(PC), PCCreate_BJacobi(PC), PCCreate_ILU(PC), PCCreate_ICC(PC), PCCreate_SOR(PC), PCCreate_KSP(PC), PCCreate_MG(PC);
+PetscErrorCode PCCreate_None(PC), PCCreate_Jacobi(PC), PCCreate_BJacobi(PC), PCCreate_ILU(PC), PCCreate_ICC(PC), PCCreate_SOR(PC), PCCreate_KSP(PC), PCCreate_MG(PC), PCCreate_GAMG(PC);
+/* what gamg.c needs of mg.c: the slot for its own data on a PC_MG, the levels of a set-up PC released for a rebuild, a level's Galerkin
+ * operator handed over ready (the next set-up does not compute it again), the options of the cycle, PCMG's own set-up and destroy */
+void **PCMGLayerData_Private(PC pc);
+PetscErrorCode PCMGReset_Private(PC pc);
+PetscErrorCode PCMGAdoptGalerkin_Private(PC pc, PetscInt l, Mat A);
+PetscErrorCode PCMGCycleOptions_Private(PC pc);
+PetscErrorCode PCSetUp_MG_Private(PC pc);
+PetscErrorCode PCDestroy_MG_Private(PC pc);
 
 #include "petsckrylovfused.h"   /* the optional fused-kernel tables a Vec / Mat type may compose */
 

@@ -173,6 +173,7 @@ static PetscErrorCode hip_mat_option(Mat A, int which, PetscInt *val) {
 static PetscErrorCode product_route_option(Mat A, const char *prefix, int *route);   /* -mat_hipmi355x_product, with the products below */
 static PetscErrorCode reductions_route_option(Mat A, const char *prefix, int *route);   /* -mat_hipmi355x_reductions, with the reductions below */
 static PetscErrorCode residual_route_option(Mat A, const char *prefix, int *route);   /* -mat_hipmi355x_residual, with MatResidual below */
+static PetscErrorCode coarsen_route_option(Mat A, const char *prefix, int *route);   /* -mat_hipmi355x_coarsen, with the coarsening below */
 static PetscErrorCode sor_route_option(Mat A, const char *prefix, int *route) {
   PetscErrorCode ierr;
   char kind[16] = ""; PetscBool set = PETSC_FALSE;
@@ -202,7 +203,9 @@ static PetscErrorCode MatSetFromOptions_SeqAIJHIP(Mat A) {
     ierr = reductions_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
     if (route) d->reductions_route = route;
     ierr = residual_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
-    if (route) d->residual_route = route; }
+    if (route) d->residual_route = route;
+    ierr = coarsen_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
+    if (route) d->coarsen_route = route; }
   return 0;
 }
 
@@ -1920,7 +1923,7 @@ static PetscErrorCode product_result(Mat A, PetscInt m, PetscInt n, const PetscI
   HipFree(ca);
   ierr = value_op_view(C);CHKERRQ(ierr);
   memcpy(SD(C)->opt, SD(A)->opt, sizeof(SD(A)->opt)); memcpy(SD(C)->opt_set, SD(A)->opt_set, sizeof(SD(A)->opt_set));
-  SD(C)->product_route = SD(A)->product_route; SD(C)->sor.route = SD(A)->sor.route;
+  SD(C)->product_route = SD(A)->product_route; SD(C)->sor.route = SD(A)->sor.route; SD(C)->coarsen_route = SD(A)->coarsen_route;
   ierr = PetscMalloc(sizeof(*p), &p);CHKERRQ(ierr);
   memset(p, 0, sizeof(*p));
   p->kind = kind; p->route = route; p->symbolic_builds = 1;
@@ -2335,6 +2338,72 @@ static PetscErrorCode MatGetColumnNorms_SeqAIJHIP(Mat A, NormType type, PetscRea
   return 0;
 }
 
+/* ---------------------------------------------------------------- Coarsening ("MatCoarsenAggregate_C", what PCGAMG asks of a level operator)
+ * Aggregates of a square sequential AIJ matrix: d = its diagonal, the strength mask |a_ij| > threshold sqrt(|d_i| |d_j|), and the
+ * distance-2 MIS aggregation of the strong graph (csrc/coarsen.hip; include/mi355x_kernels.h states the contract).  agg[i] in
+ * [0, *nagg) for every row, a host array.  -mat_hipmi355x_coarsen <device|host> (default device; host when the process has no device;
+ * read the way -mat_hipmi355x_product is): the device route works on the device copy of the pattern and the values, uploaded under
+ * the ordinary rule, and brings back the m numbers; the host route is the host twins over the host copy.  The same integers. */
+static PetscInt coarsen_total_device = 0, coarsen_total_host = 0, coarsen_total_rounds = 0;
+static PetscErrorCode coarsen_route_option(Mat A, const char *prefix, int *route) {
+  PetscErrorCode ierr;
+  char kind[16] = ""; PetscBool set = PETSC_FALSE;
+  *route = 0;
+  ierr = PetscOptionsGetString(prefix, "-mat_hipmi355x_coarsen", kind, sizeof(kind), &set);CHKERRQ(ierr);
+  if (!set) return 0;
+  if (strcmp(kind, "device") && strcmp(kind, "host")) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "-mat_hipmi355x_coarsen <device|host>, got %s", kind);
+  *route = strcmp(kind, "host") ? 1 : 2;
+  return 0;
+}
+static PetscErrorCode MatCoarsenAggregate_SeqAIJHIP(Mat A, PetscReal threshold, PetscInt *nagg, PetscInt agg[]) {
+  PetscErrorCode ierr;
+  HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
+  int route = d->coarsen_route, n = 0, rounds = 0;
+  if (strcmp(HipObjTypeName(A), MATSEQAIJHIPMI355X) || a->bs > 1) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "MatCoarsenAggregate for Mat type %s", HipObjTypeName(A));
+  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  if (a->m != a->n) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_SIZ, "Matrix must be square, %d != %d", (int)a->m, (int)a->n);
+  if (!route) { ierr = coarsen_route_option(A, NULL, &route);CHKERRQ(ierr); }
+  if (!route) { int ndev = 0; route = (mi355x_device_count(&ndev) || ndev < 1) ? 2 : 1; }
+  *nagg = 0;
+  if (route == 2) {
+    PetscScalar *diag; unsigned char *strong;
+    ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(a->m, 1), &diag);CHKERRQ(ierr);
+    ierr = PetscMalloc((size_t)PetscMax(a->nz, 1), &strong);CHKERRQ(ierr);
+    for (PetscInt r = 0; r < a->m; r++) { diag[r] = 0.0; for (PetscInt k = a->i[r]; k < a->i[r + 1]; k++) if (a->j[k] == r) { diag[r] = a->a[k]; break; } }
+    int rc = mi355x_csr_strength_host((int)a->m, a->i, a->j, a->a, diag, threshold, strong);
+    if (!rc) rc = mi355x_coarsen_mis2_host((int)a->m, a->i, a->j, strong, agg, &n);
+    HipFree(diag); HipFree(strong);
+    CHKHIP(rc);
+    d->coarsen_host++; coarsen_total_host++;
+  } else {
+    PetscDeviceCtx *dc; void *w = NULL;
+    ierr = red_device_copy(A, &dc);CHKERRQ(ierr);
+    if (a->m > 0) {
+      /* the diagonal, the aggregate numbers, the mask: one work array */
+      const size_t off_agg = sizeof(PetscScalar) * (size_t)a->m, off_strong = off_agg + ((sizeof(int) * (size_t)a->m + 7) & ~(size_t)7);
+      CHKHIP(mi355x_malloc(&w, off_strong + (size_t)PetscMax(a->nz, 1)));
+      int rc = mi355x_csr_get_diagonal(dc->h, (int)a->m, d->mat.i, d->mat.j, d->mat.a, (double *)w);
+      if (!rc) rc = mi355x_csr_strength(dc->h, (int)a->m, d->mat.i, d->mat.j, d->mat.a, (const double *)w, threshold, (unsigned char *)w + off_strong);
+      if (!rc) rc = mi355x_coarsen_mis2(dc->h, (int)a->m, d->mat.i, d->mat.j, (const unsigned char *)w + off_strong, (int *)((char *)w + off_agg), &n, &rounds);
+      if (!rc) rc = mi355x_memcpy_d2h(dc->h, agg, (char *)w + off_agg, sizeof(int) * (size_t)a->m);
+      if (!rc) rc = mi355x_handle_synchronize(dc->h);
+      mi355x_free(w);
+      CHKHIP(rc);
+    }
+    d->coarsen_device++; coarsen_total_device++;
+    d->coarsen_rounds = coarsen_total_rounds = rounds;
+  }
+  *nagg = n;
+  return 0;
+}
+PetscErrorCode MatHIPMI355XGetCoarsenCounts(Mat A, PetscInt *device, PetscInt *host, PetscInt *rounds) {
+  if (A && (!A->spptr || A->ops->mult != MatMult_SeqAIJHIP)) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "not a sequential HIPMI355X AIJ matrix");
+  if (device) *device = A ? SD(A)->coarsen_device : coarsen_total_device;
+  if (host) *host = A ? SD(A)->coarsen_host : coarsen_total_host;
+  if (rounds) *rounds = A ? SD(A)->coarsen_rounds : coarsen_total_rounds;
+  return 0;
+}
+
 /* The same reductions over ONE BLOCK of an MPIAIJ matrix (host/mpiaijhip.c), on the route the parent chose (1 device, 2 host).
  * Route 1: out / idx are device arrays of the block's rows; the off-diagonal block's compressed-row device copy is walked through
  * its plan's row list, and the rows it does not list keep what out / idx hold (add) or get (0.0, 0), an empty row's result.
@@ -2490,6 +2559,7 @@ static PetscErrorCode create_common(Mat B, const char *tname, PetscInt bs) {
   ierr = PetscObjectComposeFunction((PetscObject)B, "MatSeqAIJGetArrays_C", "MatSeqAIJGetArrays", (PetscVoidFunction)MatSeqAIJGetArrays);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)B, "MatMultTDotBegin_C", "MatMultTDotBegin_HIPMI355X", (PetscVoidFunction)MatMultTDotBegin_HIPMI355X);CHKERRQ(ierr);
   ierr = PetscObjectComposeFunction((PetscObject)B, "MatMultDiagonalScale_C", "MatMultDiagonalScale_HIPMI355X", (PetscVoidFunction)MatMultDiagonalScale_HIPMI355X);CHKERRQ(ierr);
+  ierr = PetscObjectComposeFunction((PetscObject)B, "MatCoarsenAggregate_C", "MatCoarsenAggregate_SeqAIJHIP", (PetscVoidFunction)MatCoarsenAggregate_SeqAIJHIP);CHKERRQ(ierr);   /* (the block type: PETSC_ERR_SUP) */
   if (bs == 1) {
     /* ILU(0) / ICC(0) of this type: the factored matrix carries the device triangular solves behind ops->solve (host/ilu.c), as
      * MatCreate_SeqAIJCUSPARSE overloads "MatGetFactor_petsc_C" (aijcusparse.cu:837-840) */
@@ -2522,7 +2592,7 @@ static PetscErrorCode MatDuplicate_SeqAIJHIP(Mat A, MatDuplicateOption op, Mat *
   if (op != MAT_COPY_VALUES) memset(SA(B)->a, 0, sizeof(PetscScalar) * (size_t)a->nz * (size_t)(a->bs > 1 ? a->bs * a->bs : 1));
   memcpy(SD(B)->opt, SD(A)->opt, sizeof(SD(A)->opt)); memcpy(SD(B)->opt_set, SD(A)->opt_set, sizeof(SD(A)->opt_set));
   SD(B)->cprow = SD(A)->cprow; SD(B)->sor.route = SD(A)->sor.route; SD(B)->product_route = SD(A)->product_route;
-  SD(B)->reductions_route = SD(A)->reductions_route; SD(B)->residual_route = SD(A)->residual_route;
+  SD(B)->reductions_route = SD(A)->reductions_route; SD(B)->residual_route = SD(A)->residual_route; SD(B)->coarsen_route = SD(A)->coarsen_route;
   SA(B)->keepnonzeropattern = a->keepnonzeropattern;
   *M = B;
   return 0;

@@ -334,6 +334,10 @@ typedef struct {
    * the product and VecAYPX */
   int residual_route, residual_global;
   PetscInt residual_fused, residual_calls;
+  /* "MatCoarsenAggregate_C" (host/aijhip.c): -mat_hipmi355x_coarsen <device|host> as MatSetFromOptions read it under the matrix's prefix
+   * (1 device, 2 host, 0: not given there), coarsenings of this matrix per route so far and the rounds of the last one on the device */
+  int coarsen_route;
+  PetscInt coarsen_device, coarsen_host, coarsen_rounds;
   PetscInt opt[8]; PetscBool opt_set[8];   /* the type's options as MatSetFromOptions read them under the matrix's prefix (host/aijhip.c) */
   /* per-launch device timing for bench.py (hipEvent pairs on the compute stream) */
   PetscBool timing; PetscInt time_n, time_cap; mi355x_event_t *time_ev;

@@ -83,7 +83,11 @@ _SIG = {
     "PCMGMultiplicativeSetCycles": [vp, i32], "PCMGSetNumberSmoothDown": [vp, i32], "PCMGSetNumberSmoothUp": [vp, i32],
     "PCMGSetGalerkin": [vp, i32], "PCMGSetInterpolation": [vp, i32, vp], "PCMGSetRestriction": [vp, i32, vp],
     "PCMGSetResidual": [vp, i32, vp, vp], "PCMGDefaultResidual": [vp, vp, vp, vp], "PCMGGetSmoother": [vp, i32, P(vp)],
-    "PCMGGetSmootherDown": [vp, i32, P(vp)], "PCMGGetSmootherUp": [vp, i32, P(vp)], "PCMGGetCoarseSolve": [vp, P(vp)], "PCSetUp": [vp], "PCGetOperators": [vp, P(vp), P(vp), P(i32)],
+    "PCMGGetSmootherDown": [vp, i32, P(vp)], "PCMGGetSmootherUp": [vp, i32, P(vp)], "PCMGGetCoarseSolve": [vp, P(vp)], "PCSetUp": [vp],
+    "MatCoarsenAggregate": [vp, dbl, P(i32), vp], "MatHIPMI355XGetCoarsenCounts": [vp, P(i32), P(i32), P(i32)],
+    "PCGAMGSetThreshold": [vp, dbl], "PCGAMGSetCoarseEqLimit": [vp, i32], "PCGAMGSetNlevels": [vp, i32], "PCGAMGSetNSmooths": [vp, i32],
+    "PCGAMGSetReuseInterpolation": [vp, i32], "PCGAMGGetLevelSizes": [vp, i32, P(i32), vp],
+    "PCGetOperators": [vp, P(vp), P(vp), P(i32)],
     "KSPSetUp": [vp], "KSPSolve": [vp, vp, vp], "KSPGetIterationNumber": [vp, P(i32)], "KSPGetResidualNorm": [vp, P(dbl)],
     "KSPGetConvergedReason": [vp, P(i32)], "KSPSetResidualHistory": [vp, vp, i32, i32],
     "KSPGetResidualHistory": [vp, P(vp), P(i32)], "KSPDestroy": [P(vp)],
@@ -416,6 +420,28 @@ class Mat:
         lib().MatHIPMI355XGetProductCounts(self.h, *[C.byref(q) for q in v])
         return tuple(q.value for q in v)
 
+    def aggregate(self, theta=0.0):
+        """MatCoarsenAggregate: (aggregate number of every row, number of aggregates) from the strength mask
+        |a_ij| > theta sqrt(|a_ii| |a_jj|) and a distance-2 maximal independent set of its graph"""
+        import numpy as np
+        agg = np.zeros(max(self.local_size()[0], 1), dtype=np.int32)
+        n = i32()
+        lib().MatCoarsenAggregate(self.h, float(theta), C.byref(n), agg.ctypes.data_as(vp))
+        return agg[:self.local_size()[0]], n.value
+
+    def coarsen_counts(self):
+        """coarsenings of this matrix on the device route, on the host route, device rounds of the last one (MatHIPMI355XGetCoarsenCounts)"""
+        v = [i32() for _ in range(3)]
+        lib().MatHIPMI355XGetCoarsenCounts(self.h, *[C.byref(q) for q in v])
+        return tuple(q.value for q in v)
+
+    @staticmethod
+    def coarsen_counts_total():
+        """the same over every matrix of the process (the level operators of a PCGAMG are the PC's own)"""
+        v = [i32() for _ in range(3)]
+        lib().MatHIPMI355XGetCoarsenCounts(None, *[C.byref(q) for q in v])
+        return tuple(q.value for q in v)
+
     def residual(self, b, x, r):
         """r = b - self x: the type's own method, or MatMult and VecAYPX(r, -1, b) (MatResidual)"""
         lib().MatResidual(self.h, b.h, x.h, r.h)
@@ -601,6 +627,29 @@ class PC:
 
     def mg_get_coarse_solve(self):
         return self._mg_ksp("PCMGGetCoarseSolve")
+
+    # ---- PCGAMG (type "gamg"): smoothed aggregation that fills a PCMG; the mg_* calls above work on it once it is set up
+    def gamg_set_threshold(self, theta):
+        lib().PCGAMGSetThreshold(self.h, float(theta))
+
+    def gamg_set_coarse_eq_limit(self, n):
+        lib().PCGAMGSetCoarseEqLimit(self.h, int(n))
+
+    def gamg_set_nlevels(self, n):
+        lib().PCGAMGSetNlevels(self.h, int(n))
+
+    def gamg_set_nsmooths(self, n):
+        lib().PCGAMGSetNSmooths(self.h, int(n))
+
+    def gamg_set_reuse_interpolation(self, flag=True):
+        lib().PCGAMGSetReuseInterpolation(self.h, 1 if flag else 0)
+
+    def gamg_level_sizes(self):
+        """PCGAMGGetLevelSizes: the rows of every level of the last set-up, the fine level first"""
+        n = i32()
+        sizes = (i32 * 1000)()
+        lib().PCGAMGGetLevelSizes(self.h, 1000, C.byref(n), sizes)
+        return [sizes[k] for k in range(n.value)]
 
     def ksp_total_iterations(self):
         """PCKSPGetTotalIterations: the inner iterations of all applications of a PC of type "ksp" so far"""
