@@ -26,14 +26,39 @@
  * Written against the public API and the KSP implementation header only (petsc-private/kspimpl.h inside a PETSc tree, the
  * harness's petscimpl.h on a box without PETSc): nothing here reaches into a Vec, a Mat or a PC.  An unchanged PETSc program
  * gets these solvers with -ksp_type cghipmi355x etc.; with its own -ksp_type cg it gets PETSc's KSPSolve_CG over the same
- * Vec/Mat ops, one kernel per call. */
+ * Vec/Mat ops, one kernel per call.
+ *
+ * What the types share is written once, and a new type is added by filling it in.  Every type's data struct starts with a KSPHipCommon
+ * (the diagonal of a PCJACOBI, the type's -ksp_<type>_fused switch, the two counters KSPHIPMI355XGetFusedStepCounts reports; a type
+ * without one of them leaves it at zero) and states the methods it composes on its KSP ONCE, in a static KSPHipMethod table.
+ * KSPCreate_* calls ksp_create_data with the struct's size and that table, sets its defaults and its ops; KSPDestroy_* releases what
+ * only the type owns and ends in ksp_destroy_data with the same table, so what create composed is what destroy takes away.  The
+ * solves themselves share helpers (the tables a Vec type offers, the diagonal form of the PC, K = B A with the dots that follow,
+ * the start residual), never a loop: each recurrence is read against its reference. */
 #include "hipmi355ximpl.h"
 
 /* ------------------------------------------------------------------------------------------------ what the types offer */
-static const VecKrylovFusedOps *vec_fused_ops(Vec x) {
-  PetscVoidFunction f = NULL;
-  if (PetscObjectQueryFunction((PetscObject)x, "VecKrylovFusedOps_C", &f) || !f) return NULL;
-  return ((VecKrylovFusedOpsGetFn)f)();
+/* fn(x): the table the type of x offers under name, or NULL when it offers none or one without the members `complete` asks of T */
+#define VEC_TABLE(fn, Table, name, complete) \
+  static const Table *fn(Vec x) { \
+    PetscVoidFunction f = NULL; \
+    const Table *T; \
+    if (PetscObjectQueryFunction((PetscObject)x, name, &f) || !f) return NULL; \
+    T = ((const Table *(*)(void))f)(); \
+    return (T && (complete)) ? T : NULL; \
+  }
+VEC_TABLE(vec_fused_ops, VecKrylovFusedOps, "VecKrylovFusedOps_C", PETSC_TRUE)
+VEC_TABLE(vec_fgmres_ops, VecFgmresFusedOps, "VecFgmresFusedOps_C", T->fgmres_orthog_normalize_pc)
+VEC_TABLE(vec_pipelined_ops, VecPipelinedCGFusedOps, "VecPipelinedCGFusedOps_C", PETSC_TRUE)
+VEC_TABLE(vec_split_ops, VecSplitReductionOps, "VecSplitReductionOps_C", PETSC_TRUE)
+VEC_TABLE(vec_minres_ops, VecMinresFusedOps, "VecMinresFusedOps_C", T->minres_lanczos && T->minres_update)
+VEC_TABLE(vec_tfqmr_ops, VecTfqmrFusedOps, "VecTfqmrFusedOps_C", T->tfqmr_qt && T->tfqmr_resid && T->tfqmr_update)
+VEC_TABLE(vec_bicg_ops, VecBicgFusedOps, "VecBicgFusedOps_C", T->bicg_dirs && T->bicg_update)
+VEC_TABLE(vec_lsqr_ops, VecLsqrFusedOps, "VecLsqrFusedOps_C", T->lsqr_bidiag && T->lsqr_update)
+/* the three types without an op-by-op route (chebychevhipmi355x, minreshipmi355x, lsqrhipmi355x) refuse other vectors at set-up and at solve */
+static PetscErrorCode needs_table(KSP ksp, PetscBool offered, const char *type, const char *sweeps, const char *table, const char *plain) {
+  if (!offered) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s needs vectors whose type offers the fused %s (\"%s\"); use -ksp_type %s on these vectors", type, sweeps, table, plain);
+  return 0;
 }
 static PetscErrorCode mat_mult_scaled(Mat A, Vec d, Vec x, Vec y, PetscBool *ok) {        /* y = d .* (A x) in one kernel */
   PetscVoidFunction f = NULL;
@@ -60,15 +85,74 @@ static PetscErrorCode option_level(KSP ksp, const char *name, PetscInt lo, Petsc
   else { PetscInt v = (PetscInt)atoi(t); *level = v < lo ? lo : (v > hi ? hi : v); }
   return 0;
 }
+static PetscErrorCode option_bool(KSP ksp, const char *name, PetscBool *flag) {                                /* "-name <bool>", as a level 0..1 */
+  PetscInt iv = *flag;
+  PetscErrorCode ierr = option_level(ksp, name, 0, 1, &iv);CHKERRQ(ierr);
+  *flag = (PetscBool)iv;
+  return 0;
+}
 
+/* ------------------------------------------------------------------------------------------------ what the types share */
+/* the head of every type's data struct: 1 / diagonal of a PCJACOBI (pc_diagonal_form), the -ksp_<type>_fused switch, the two counters of
+ * KSPHIPMI355XGetFusedStepCounts.  A type without a switch or without counters leaves them at zero */
+typedef struct { Vec dinv; PetscBool fused; PetscInt count[2]; } KSPHipCommon;
+#define COMMON(ksp) ((KSPHipCommon *)(ksp)->data)
+/* a method a type composes on its KSP; a type's table ends with a NULL name */
+typedef struct { const char *name, *fname; PetscVoidFunction fn; } KSPHipMethod;
+
+static PetscErrorCode ksp_compose(KSP ksp, const KSPHipMethod *m, PetscBool on) {
+  for (; m && m->name; m++) {
+    PetscErrorCode ierr = PetscObjectComposeFunction((PetscObject)ksp, m->name, on ? m->fname : "", on ? m->fn : (PetscVoidFunction)NULL);CHKERRQ(ierr);
+  }
+  return 0;
+}
+/* ksp->data: `size` zeroed bytes that start with a KSPHipCommon; the type's methods composed */
+static PetscErrorCode ksp_create_data(KSP ksp, size_t size, const KSPHipMethod *methods) {
+  void *data;
+  PetscErrorCode ierr = PetscMalloc(size, &data);CHKERRQ(ierr);
+  memset(data, 0, size);
+  ksp->data = data;
+  return ksp_compose(ksp, methods, PETSC_TRUE);
+}
+/* the end of every KSPDestroy_*: the common part and the struct released, the methods of create taken away */
+static PetscErrorCode ksp_destroy_data(KSP ksp, const KSPHipMethod *methods) {
+  PetscErrorCode ierr;
+  if (!ksp->data) return 0;
+  ierr = VecDestroy(&COMMON(ksp)->dinv);CHKERRQ(ierr);
+  HipFree(ksp->data); ksp->data = NULL;
+  return ksp_compose(ksp, methods, PETSC_FALSE);
+}
+/* the one getter behind KSPHIPMI355XGetFusedStepCounts, composed by the types that count (COUNTS_METHOD in their table); what the two counters mean is the type's (see each type) */
+static PetscErrorCode KSPGetFusedStepCounts_Common(KSP ksp, PetscInt *first, PetscInt *second) {
+  *first = COMMON(ksp)->count[0]; *second = COMMON(ksp)->count[1];
+  return 0;
+}
+#define COUNTS_METHOD {"KSPHIPMI355XGetFusedStepCounts_C", "KSPGetFusedStepCounts_Common", (PetscVoidFunction)KSPGetFusedStepCounts_Common}
+static const KSPHipMethod counts_only[] = {COUNTS_METHOD, {NULL, NULL, NULL}};   /* the types that compose nothing else */
+PetscErrorCode KSPHIPMI355XGetFusedStepCounts(KSP ksp, PetscInt *fused, PetscInt *opbyop) {
+  PetscVoidFunction f = NULL;
+  PetscErrorCode ierr = PetscObjectQueryFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", &f);CHKERRQ(ierr);
+  *fused = 0; *opbyop = 0;
+  if (f) { ierr = ((PetscErrorCode (*)(KSP, PetscInt *, PetscInt *))f)(ksp, fused, opbyop);CHKERRQ(ierr); }
+  return 0;
+}
+
+/* A null space (KSPSetNullSpace) is projected out of every preconditioned vector by KSP_PCApply / KSP_PCApplyBAorAB (kspimpl.h
+ * KSP_RemoveNullSpace).  A sweep that folds the preconditioner into a product or takes the dots of z in the pass that forms z has no
+ * place for that projection: with a null space every preconditioner counts as PCKIND_GENERAL and goes through those two calls. */
+static PetscBool has_null_space(KSP ksp) { return (PetscBool)(ksp->nullsp != NULL); }   /* kspimpl.h: what KSPGetNullSpace returns */
 /* A preconditioner that is a diagonal scaling can ride along in a fused sweep.  Which diagonal: asked of the PC itself through
  * its public face -- PCApply to a vector of ones returns exactly the numbers PCApply_Jacobi multiplies by (1.0 * d is d), for
- * every variant of PCJACOBI (-pc_jacobi_rowmax, ...) and without knowing the PC's data structure. */
+ * every variant of PCJACOBI (-pc_jacobi_rowmax, ...) and without knowing the PC's data structure.  Every solve opens with this:
+ * `wanted` is the solve's own condition for looking at all; not wanted, or a null space: PCKIND_GENERAL, nothing asked of the PC.
+ * *d: the diagonal (kept in the common header) of a PCKIND_DIAGONAL, NULL otherwise. */
 typedef enum { PCKIND_GENERAL = 0, PCKIND_IDENTITY, PCKIND_DIAGONAL } HipPCKind;
-static PetscErrorCode pc_diagonal_form(KSP ksp, Vec like, Vec *dinv, HipPCKind *kind) {
+static PetscErrorCode pc_diagonal_form(KSP ksp, PetscBool wanted, Vec like, HipPCKind *kind, Vec *d) {
   PetscErrorCode ierr;
   PCType t = NULL;
-  *kind = PCKIND_GENERAL;
+  Vec *dinv = &COMMON(ksp)->dinv;
+  *kind = PCKIND_GENERAL; *d = NULL;
+  if (!wanted || has_null_space(ksp)) return 0;
   ierr = PCGetType(ksp->pc, &t);CHKERRQ(ierr);
   if (t && !strcmp(t, PCNONE)) *kind = PCKIND_IDENTITY;
   else if (t && !strcmp(t, PCJACOBI)) {
@@ -78,14 +162,10 @@ static PetscErrorCode pc_diagonal_form(KSP ksp, Vec like, Vec *dinv, HipPCKind *
     ierr = VecSet(ones, 1.0);CHKERRQ(ierr);
     ierr = PCApply(ksp->pc, ones, *dinv);CHKERRQ(ierr);
     ierr = VecDestroy(&ones);CHKERRQ(ierr);
-    *kind = PCKIND_DIAGONAL;
+    *kind = PCKIND_DIAGONAL; *d = *dinv;
   }
   return 0;
 }
-/* A null space (KSPSetNullSpace) is projected out of every preconditioned vector by KSP_PCApply / KSP_PCApplyBAorAB (kspimpl.h
- * KSP_RemoveNullSpace).  A sweep that folds the preconditioner into a product or takes the dots of z in the pass that forms z has no
- * place for that projection: with a null space every preconditioner counts as PCKIND_GENERAL and goes through those two calls. */
-static PetscBool has_null_space(KSP ksp) { return (PetscBool)(ksp->nullsp != NULL); }   /* kspimpl.h: what KSPGetNullSpace returns */
 #define KSPCheckDot(ksp, v) do { if (PetscIsInfOrNanScalar(v)) SETERRQ(HipObjComm(ksp), PETSC_ERR_FP, "Infinite or not-a-number generated in dot product"); } while (0)
 #define KSPTestConvergence(ksp, it, rn) (*(ksp)->converged)((ksp), (it), (rn), &(ksp)->reason, (ksp)->cnvP)
 static PetscErrorCode report(KSP ksp, PetscInt it, PetscReal rn) {   /* what every solver does with a new residual norm */
@@ -93,6 +173,35 @@ static PetscErrorCode report(KSP ksp, PetscInt it, PetscReal rn) {   /* what eve
   ksp->rnorm = rn;
   KSPLogResidualHistory(ksp, rn);
   ierr = KSPMonitor(ksp, it, rn);CHKERRQ(ierr);
+  return 0;
+}
+static PetscErrorCode start_residual(KSP ksp, Mat A, Vec x, Vec rhs, Vec r) {   /* r = rhs - A x; a zero guess: the copy */
+  PetscErrorCode ierr;
+  if (ksp->guess_zero) { ierr = VecCopy(rhs, r);CHKERRQ(ierr); }
+  else { ierr = KSP_MatMult(ksp, A, x, r);CHKERRQ(ierr); ierr = VecAYPX(r, -1.0, rhs);CHKERRQ(ierr); }
+  return 0;
+}
+/* out = K in (K = B A, left preconditioning) and, when the types can, the reduction(s) that follow in the same pass: PCJACOBI on a
+ * matrix that offers it: d .* (A in) in the product's own kernel; PCJACOBI / PCNONE otherwise: PCApply fused with the dot(s)
+ * ("pmult_dot", "pmult_dotnorm2"); any other PC, a null space, or no table F: KSP_PCApplyBAorAB and the public dots.
+ * which = 0: nothing is reduced; which = 1: *s1 = (out, other); which = 2: *s1 = (other, out), *s2 = (out, out).  scratch: a vector for A in. */
+static PetscErrorCode apply_operator(KSP ksp, Mat A, const VecKrylovFusedOps *F, HipPCKind pck, Vec d, Vec in, Vec out, Vec scratch, int which, Vec other,
+                                     PetscScalar *s1, PetscReal *s2) {
+  PetscErrorCode ierr;
+  PetscBool done = PETSC_FALSE, scaled = PETSC_FALSE;
+  if (F && pck != PCKIND_GENERAL) {
+    if (d) { ierr = mat_mult_scaled(A, d, in, out, &scaled);CHKERRQ(ierr); }
+    if (!scaled) {
+      ierr = KSP_MatMult(ksp, A, in, scratch);CHKERRQ(ierr);
+      if (which == 1) { ierr = F->pmult_dot(out, scratch, d, other, s1, &done);CHKERRQ(ierr); }
+      else if (which == 2) { ierr = F->pmult_dotnorm2(out, scratch, d, other, s1, s2, &done);CHKERRQ(ierr); }
+      if (!done) { ierr = KSP_PCApply(ksp, scratch, out);CHKERRQ(ierr); }
+    }
+  } else { ierr = KSP_PCApplyBAorAB(ksp, in, out, scratch);CHKERRQ(ierr); }
+  if (!done) {
+    if (which == 1) { ierr = VecDot(out, other, s1);CHKERRQ(ierr); }
+    else if (which == 2) { ierr = VecDotNorm2(other, out, s1, s2);CHKERRQ(ierr); }
+  }
   return 0;
 }
 
@@ -111,22 +220,15 @@ static PetscErrorCode report(KSP ksp, PetscInt it, PetscReal rn) {   /* what eve
  * -ksp_cg_x_with_p <bool> (default true), levels 3 and 4: when the front half of iteration i+1 is queued, x += a p of iteration i
  * moves from the update sweep into the AYPX that reads p anyway (the same a, the same x + a*p): 12 vector passes per iteration
  * instead of 13, same bits.  Iterations that queue nothing keep x in the update sweep. */
-typedef struct { PetscInt level; PetscBool x_with_p; Vec dinv; } KSP_CGHIP;
+typedef struct { KSPHipCommon common; PetscInt level; PetscBool x_with_p; } KSP_CGHIP;   /* the switch is `level`: common.fused stays unused */
 
 static PetscErrorCode KSPSetUp_CGHIP(KSP ksp) { return KSPDefaultGetWork(ksp, 3); }
 static PetscErrorCode KSPSetFromOptions_CGHIP(KSP ksp) {
   KSP_CGHIP *cg = (KSP_CGHIP *)ksp->data;
-  PetscInt iv = cg->x_with_p;
   PetscErrorCode ierr = option_level(ksp, "-ksp_cg_fused", 0, 4, &cg->level);CHKERRQ(ierr);
-  ierr = option_level(ksp, "-ksp_cg_x_with_p", 0, 1, &iv);CHKERRQ(ierr);
-  cg->x_with_p = (PetscBool)iv;
-  return 0;
+  return option_bool(ksp, "-ksp_cg_x_with_p", &cg->x_with_p);
 }
-static PetscErrorCode KSPDestroy_CGHIP(KSP ksp) {
-  KSP_CGHIP *cg = (KSP_CGHIP *)ksp->data;
-  if (cg) { PetscErrorCode ierr = VecDestroy(&cg->dinv);CHKERRQ(ierr); HipFree(cg); ksp->data = NULL; }
-  return 0;
-}
+static PetscErrorCode KSPDestroy_CGHIP(KSP ksp) { return ksp_destroy_data(ksp, NULL); }
 
 static PetscReal cg_norm_from_sums(KSPNormType nt, PetscScalar zz, PetscScalar zr, PetscScalar rr) {
   switch (nt) {                                          /* the square is reduced, then rooted (pvec2.c:62-64) */
@@ -154,16 +256,13 @@ static PetscErrorCode KSPSolve_CGHIP(KSP ksp) {
   PetscInt it;
 
   ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
-  if (level > 0 && !has_null_space(ksp)) {                /* with a null space: pck stays general, sweep stays off, every z from KSP_PCApply */
-    ierr = pc_diagonal_form(ksp, x, &cg->dinv, &pck);CHKERRQ(ierr);
-    if (pck != PCKIND_GENERAL) { d = pck == PCKIND_DIAGONAL ? cg->dinv : NULL; ierr = F->cg_update_check(x, r, z, p, w, d, &sweep);CHKERRQ(ierr); }
-  }
+  ierr = pc_diagonal_form(ksp, (PetscBool)(level > 0), x, &pck, &d);CHKERRQ(ierr);   /* with a null space: pck stays general, sweep stays off, every z from KSP_PCApply */
+  if (pck != PCKIND_GENERAL) { ierr = F->cg_update_check(x, r, z, p, w, d, &sweep);CHKERRQ(ierr); }
   const PetscBool on_device = (PetscBool)(sweep && level > 1);
 
   /* ---- residual of the initial guess, its norm in the flavour the test wants, the first z'r ---- */
   ksp->its = 0;
-  if (ksp->guess_zero) { ierr = VecCopy(rhs, r);CHKERRQ(ierr); }
-  else { ierr = KSP_MatMult(ksp, A, x, r);CHKERRQ(ierr); ierr = VecAYPX(r, -1.0, rhs);CHKERRQ(ierr); }
+  ierr = start_residual(ksp, A, x, rhs, r);CHKERRQ(ierr);
   if (nt == KSP_NORM_PRECONDITIONED) { ierr = KSP_PCApply(ksp, r, z);CHKERRQ(ierr); ierr = VecNorm(z, NORM_2, &rn);CHKERRQ(ierr); }
   else if (nt == KSP_NORM_UNPRECONDITIONED) { ierr = VecNorm(r, NORM_2, &rn);CHKERRQ(ierr); }
   else if (nt == KSP_NORM_NATURAL) {
@@ -257,9 +356,9 @@ static PetscErrorCode KSPSolve_CGHIP(KSP ksp) {
 
 PetscErrorCode KSPCreate_CGHIPMI355X(KSP ksp) {
   KSP_CGHIP *cg;
-  PetscErrorCode ierr = PetscMalloc(sizeof(*cg), &cg);CHKERRQ(ierr);
-  cg->level = 4; cg->x_with_p = PETSC_TRUE; cg->dinv = NULL;
-  ksp->data = cg;
+  PetscErrorCode ierr = ksp_create_data(ksp, sizeof(*cg), NULL);CHKERRQ(ierr);
+  cg = (KSP_CGHIP *)ksp->data;
+  cg->level = 4; cg->x_with_p = PETSC_TRUE;
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);    /* the four of KSPCG, cg.c:439-442 */
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_LEFT, 1);CHKERRQ(ierr);
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_NATURAL, PC_LEFT, 1);CHKERRQ(ierr);
@@ -274,22 +373,20 @@ PetscErrorCode KSPCreate_CGHIPMI355X(KSP ksp) {
  * device-resident norm, one host wait instead of three ("gmres_orthog_normalize").  Same bits as the separate calls.
  * Options of KSPGMRES kept: -ksp_gmres_restart, -ksp_gmres_cgs_refinement_type, KSPGMRESSetRestart / SetCGSRefinementType. */
 typedef struct {
+  KSPHipCommon common;              /* count: fgmreshipmi355x only */
   PetscInt m;                       /* restart length */
   PetscReal haptol;
   KSPGMRESCGSRefinementType refine;
-  PetscBool fused;
   PetscScalar *H;                   /* Hessenberg matrix after the rotations, column j at H + j (m + 2) */
   PetscScalar *g, *cs, *sn, *coef, *y;   /* rotated right-hand side, rotations, Gram-Schmidt coefficients, triangular solve */
   Vec *V; PetscInt nV, nscr;        /* V[0 .. nscr - 1]: scratch (GMRES 2, FGMRES 1); V[nscr + k]: k-th basis vector */
-  Vec dinv;
-  /* fgmreshipmi355x only: Z[k] = B_k V[k], the routine that may change B before every application, the form of B and the step counts */
+  /* fgmreshipmi355x only: Z[k] = B_k V[k], the routine that may change B before every application, the form of B */
   PetscBool flexible;
   Vec *Z;
   PetscErrorCode (*modifypc)(KSP, PetscInt, PetscInt, PetscReal, void *);
   void *modifyctx;
   PetscErrorCode (*modifydestroy)(void *);
   HipPCKind pckind;
-  PetscInt nfused, nunfused;
 } KSP_GMRESHIP;
 #define GH(ksp) ((KSP_GMRESHIP *)(ksp)->data)
 #define Hcol(gm, j) ((gm)->H + (size_t)(j) * (size_t)((gm)->m + 2))
@@ -314,10 +411,7 @@ static PetscErrorCode KSPSetFromOptions_GMRESHIP(KSP ksp) {
     else if (!strcmp(t, "refine_always")) GH(ksp)->refine = KSP_GMRES_CGS_REFINE_ALWAYS;
     else SETERRQ(HipObjComm(ksp), PETSC_ERR_ARG_UNKNOWN_TYPE, "Unknown refinement type %s", t);
   }
-  iv = GH(ksp)->fused;
-  ierr = option_level(ksp, GH(ksp)->flexible ? "-ksp_fgmres_fused" : "-ksp_gmres_fused", 0, 1, &iv);CHKERRQ(ierr);
-  GH(ksp)->fused = (PetscBool)iv;
-  return 0;
+  return option_bool(ksp, GH(ksp)->flexible ? "-ksp_fgmres_fused" : "-ksp_gmres_fused", &COMMON(ksp)->fused);
 }
 
 static PetscErrorCode KSPSetUp_GMRESHIP(KSP ksp) {
@@ -412,8 +506,9 @@ static PetscErrorCode gmres_update_solution(KSP ksp, PetscInt n) {
 static PetscErrorCode gmres_cycle(KSP ksp, PetscInt *steps) {
   PetscErrorCode ierr;
   KSP_GMRESHIP *gm = GH(ksp);
-  const VecKrylovFusedOps *F = gm->fused ? vec_fused_ops(BASIS(gm, 0)) : NULL;
-  Vec d = NULL;
+  const VecKrylovFusedOps *F = gm->common.fused ? vec_fused_ops(BASIS(gm, 0)) : NULL;
+  HipPCKind pck;
+  Vec d;
   Mat A;
   PetscReal res, wnorm;
   PetscInt k = 0;
@@ -421,11 +516,7 @@ static PetscErrorCode gmres_cycle(KSP ksp, PetscInt *steps) {
 
   if (F && !F->gmres_orthog_normalize) F = NULL;
   ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
-  if (gm->fused && ksp->pc_side == PC_LEFT && !has_null_space(ksp)) {
-    HipPCKind kind;
-    ierr = pc_diagonal_form(ksp, BASIS(gm, 0), &gm->dinv, &kind);CHKERRQ(ierr);
-    if (kind == PCKIND_DIAGONAL) d = gm->dinv;
-  }
+  ierr = pc_diagonal_form(ksp, (PetscBool)(gm->common.fused && ksp->pc_side == PC_LEFT), BASIS(gm, 0), &pck, &d);CHKERRQ(ierr);
   ierr = VecNormalize(BASIS(gm, 0), &res);CHKERRQ(ierr);
   gm->g[0] = res;
   ierr = report(ksp, ksp->its, res);CHKERRQ(ierr);
@@ -488,6 +579,10 @@ static PetscErrorCode KSPSolve_GMRESHIP(KSP ksp) {
   return 0;
 }
 
+static const KSPHipMethod gmres_methods[] = {
+  {"KSPGMRESSetRestart_C", "KSPGMRESSetRestart_GMRESHIP", (PetscVoidFunction)KSPGMRESSetRestart_GMRESHIP},
+  {"KSPGMRESSetCGSRefinementType_C", "KSPGMRESSetCGSRefinementType_GMRESHIP", (PetscVoidFunction)KSPGMRESSetCGSRefinementType_GMRESHIP},
+  {NULL, NULL, NULL}};
 static PetscErrorCode KSPDestroy_GMRESHIP(KSP ksp) {
   PetscErrorCode ierr;
   KSP_GMRESHIP *gm = GH(ksp);
@@ -496,25 +591,18 @@ static PetscErrorCode KSPDestroy_GMRESHIP(KSP ksp) {
   if (gm->V) { ierr = VecDestroyVecs(gm->nV, &gm->V);CHKERRQ(ierr); }
   if (gm->Z) { ierr = VecDestroyVecs(gm->m, &gm->Z);CHKERRQ(ierr); }
   if (gm->modifydestroy) { ierr = (*gm->modifydestroy)(gm->modifyctx);CHKERRQ(ierr); }
-  ierr = VecDestroy(&gm->dinv);CHKERRQ(ierr);
-  HipFree(gm); ksp->data = NULL;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPGMRESSetRestart_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPGMRESSetCGSRefinementType_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
-  return 0;
+  return ksp_destroy_data(ksp, gmres_methods);
 }
 
 PetscErrorCode KSPCreate_GMRESHIPMI355X(KSP ksp) {
   KSP_GMRESHIP *gm;
-  PetscErrorCode ierr = PetscMalloc(sizeof(*gm), &gm);CHKERRQ(ierr);
-  memset(gm, 0, sizeof(*gm));
-  gm->m = 30; gm->haptol = 1.0e-30; gm->refine = KSP_GMRES_CGS_REFINE_NEVER; gm->fused = PETSC_TRUE;   /* KSPGMRES's defaults, gmres.c:944-958 */
+  PetscErrorCode ierr = ksp_create_data(ksp, sizeof(*gm), gmres_methods);CHKERRQ(ierr);
+  gm = GH(ksp);
+  gm->m = 30; gm->haptol = 1.0e-30; gm->refine = KSP_GMRES_CGS_REFINE_NEVER; gm->common.fused = PETSC_TRUE;   /* KSPGMRES's defaults, gmres.c:944-958 */
   gm->nscr = 2;
-  ksp->data = gm;
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);       /* gmres.c:909-910 */
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_RIGHT, 1);CHKERRQ(ierr);
   ksp->ops->setup = KSPSetUp_GMRESHIP; ksp->ops->solve = KSPSolve_GMRESHIP; ksp->ops->setfromoptions = KSPSetFromOptions_GMRESHIP; ksp->ops->destroy = KSPDestroy_GMRESHIP;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPGMRESSetRestart_C", "KSPGMRESSetRestart_GMRESHIP", (PetscVoidFunction)KSPGMRESSetRestart_GMRESHIP);CHKERRQ(ierr);
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPGMRESSetCGSRefinementType_C", "KSPGMRESSetCGSRefinementType_GMRESHIP", (PetscVoidFunction)KSPGMRESSetCGSRefinementType_GMRESHIP);CHKERRQ(ierr);
   return 0;
 }
 
@@ -532,21 +620,10 @@ PetscErrorCode KSPCreate_GMRESHIPMI355X(KSP ksp) {
  * the work vector with NaN: only seen with KSP_NORM_NONE, where no test stops the cycle.
  * KSPHIPMI355XGetFusedStepCounts: (steps that wrote the next Z in the sweep, all other steps), summed over all solves since the type was set.  On vectors without the tables every
  * step runs through the public calls.  Options of KSPGMRES kept: -ksp_gmres_restart, -ksp_gmres_cgs_refinement_type. */
-static const VecFgmresFusedOps *vec_fgmres_ops(Vec x) {
-  PetscVoidFunction f = NULL;
-  const VecFgmresFusedOps *P;
-  if (PetscObjectQueryFunction((PetscObject)x, "VecFgmresFusedOps_C", &f) || !f) return NULL;
-  P = ((VecFgmresFusedOpsGetFn)f)();
-  return (P && P->fgmres_orthog_normalize_pc) ? P : NULL;
-}
 static PetscErrorCode KSPFGMRESSetModifyPC_FGMRESHIP(KSP ksp, PetscErrorCode (*fcn)(KSP, PetscInt, PetscInt, PetscReal, void *), void *ctx, PetscErrorCode (*d)(void *)) {
   KSP_GMRESHIP *gm = GH(ksp);
   if (gm->modifydestroy) { PetscErrorCode ierr = (*gm->modifydestroy)(gm->modifyctx);CHKERRQ(ierr); }
   gm->modifypc = fcn; gm->modifyctx = ctx; gm->modifydestroy = d;          /* NULL: the preconditioner is left alone (KSPFGMRESModifyPCNoChange) */
-  return 0;
-}
-static PetscErrorCode KSPGetFusedStepCounts_FGMRESHIP(KSP ksp, PetscInt *fused, PetscInt *opbyop) {
-  *fused = GH(ksp)->nfused; *opbyop = GH(ksp)->nunfused;
   return 0;
 }
 
@@ -582,7 +659,7 @@ static PetscErrorCode fgmres_cycle(KSP ksp) {
   PetscErrorCode ierr;
   KSP_GMRESHIP *gm = GH(ksp);
   const VecKrylovFusedOps *F = vec_fused_ops(BASIS(gm, 0));
-  const VecFgmresFusedOps *P = (gm->fused && gm->pckind != PCKIND_GENERAL) ? vec_fgmres_ops(BASIS(gm, 0)) : NULL;
+  const VecFgmresFusedOps *P = (gm->common.fused && gm->pckind != PCKIND_GENERAL) ? vec_fgmres_ops(BASIS(gm, 0)) : NULL;
   Mat A;
   PetscReal res, tt, hapbnd;
   PetscInt k = 0;
@@ -607,7 +684,7 @@ static PetscErrorCode fgmres_cycle(KSP ksp) {
     done = PETSC_FALSE;
     if (gm->refine == KSP_GMRES_CGS_REFINE_NEVER) {
       if (P && k + 1 < gm->m) {
-        ierr = P->fgmres_orthog_normalize_pc(BASIS(gm, k + 1), k + 1, &BASIS(gm, 0), gm->dinv, (PetscBool)(gm->pckind == PCKIND_IDENTITY), gm->Z[k + 1], gm->coef, &tt, &done);CHKERRQ(ierr);
+        ierr = P->fgmres_orthog_normalize_pc(BASIS(gm, k + 1), k + 1, &BASIS(gm, 0), gm->common.dinv, (PetscBool)(gm->pckind == PCKIND_IDENTITY), gm->Z[k + 1], gm->coef, &tt, &done);CHKERRQ(ierr);
         have_z = done;
       }
       if (!done && F) { ierr = F->gmres_orthog_normalize(BASIS(gm, k + 1), k + 1, &BASIS(gm, 0), gm->coef, &tt, &done);CHKERRQ(ierr); }
@@ -617,7 +694,7 @@ static PetscErrorCode fgmres_cycle(KSP ksp) {
       ierr = gmres_orthogonalize(ksp, k, hcol);CHKERRQ(ierr);
       ierr = VecNormalize(BASIS(gm, k + 1), &tt);CHKERRQ(ierr);
     }
-    if (have_z) gm->nfused++; else gm->nunfused++;
+    gm->common.count[have_z ? 0 : 1]++;                                  /* (steps that wrote the next Z in the sweep, all other steps) */
     hcol[k + 1] = tt;
     hapbnd = PetscAbsScalar(tt / gm->g[k]);
     if (hapbnd > gm->haptol) hapbnd = gm->haptol;
@@ -642,10 +719,11 @@ static PetscErrorCode fgmres_cycle(KSP ksp) {
 static PetscErrorCode KSPSolve_FGMRESHIP(KSP ksp) {
   PetscErrorCode ierr;
   KSP_GMRESHIP *gm = GH(ksp);
+  Vec d;                                                                 /* the cycle takes the diagonal from the common header */
   ksp->its = 0;
   ksp->reason = KSP_CONVERGED_ITERATING;
-  gm->pckind = PCKIND_GENERAL;                                           /* what the sweep may apply itself: a PC nobody changes, nothing projected behind it */
-  if (gm->fused && !gm->modifypc && !has_null_space(ksp)) { ierr = pc_diagonal_form(ksp, BASIS(gm, 0), &gm->dinv, &gm->pckind);CHKERRQ(ierr); }
+  /* what the sweep may apply itself: a PC nobody changes, nothing projected behind it */
+  ierr = pc_diagonal_form(ksp, (PetscBool)(gm->common.fused && !gm->modifypc), BASIS(gm, 0), &gm->pckind, &d);CHKERRQ(ierr);
   if (ksp->guess_zero) { ierr = VecCopy(ksp->vec_rhs, BASIS(gm, 0));CHKERRQ(ierr); }
   else { ierr = fgmres_residual(ksp);CHKERRQ(ierr); }
   ierr = fgmres_cycle(ksp);CHKERRQ(ierr);
@@ -658,77 +736,43 @@ static PetscErrorCode KSPSolve_FGMRESHIP(KSP ksp) {
   return 0;
 }
 
+static const KSPHipMethod fgmres_methods[] = {   /* on top of gmres_methods */
+  {"KSPFGMRESSetModifyPC_C", "KSPFGMRESSetModifyPC_FGMRESHIP", (PetscVoidFunction)KSPFGMRESSetModifyPC_FGMRESHIP},
+  COUNTS_METHOD,
+  {NULL, NULL, NULL}};
 static PetscErrorCode KSPDestroy_FGMRESHIP(KSP ksp) {
   PetscErrorCode ierr;
   if (!ksp->data) return 0;
   ierr = KSPDestroy_GMRESHIP(ksp);CHKERRQ(ierr);
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPFGMRESSetModifyPC_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
-  return 0;
+  return ksp_compose(ksp, fgmres_methods, PETSC_FALSE);
 }
 
 PetscErrorCode KSPCreate_FGMRESHIPMI355X(KSP ksp) {
   PetscErrorCode ierr = KSPCreate_GMRESHIPMI355X(ksp);CHKERRQ(ierr);
-  GH(ksp)->flexible = PETSC_TRUE; GH(ksp)->nscr = 1; GH(ksp)->fused = PETSC_FALSE;
+  GH(ksp)->flexible = PETSC_TRUE; GH(ksp)->nscr = 1; COMMON(ksp)->fused = PETSC_FALSE;
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 0);CHKERRQ(ierr);      /* right preconditioning only: the true residual's norm, or none */
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_NONE, PC_LEFT, 0);CHKERRQ(ierr);
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_RIGHT, 2);CHKERRQ(ierr);
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_NONE, PC_RIGHT, 1);CHKERRQ(ierr);
   ksp->ops->solve = KSPSolve_FGMRESHIP; ksp->ops->destroy = KSPDestroy_FGMRESHIP;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPFGMRESSetModifyPC_C", "KSPFGMRESSetModifyPC_FGMRESHIP", (PetscVoidFunction)KSPFGMRESSetModifyPC_FGMRESHIP);CHKERRQ(ierr);
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "KSPGetFusedStepCounts_FGMRESHIP", (PetscVoidFunction)KSPGetFusedStepCounts_FGMRESHIP);CHKERRQ(ierr);
-  return 0;
+  return ksp_compose(ksp, fgmres_methods, PETSC_TRUE);
 }
 
 /* ================================================================================================ BiCGStab
  * -ksp_bcgs_fused <bool> (default true), left preconditioning.  PCJACOBI: both products write d .* (A x) themselves; PCJACOBI /
  * PCNONE on types without that method: PCApply fused with the dot(s) that follow it; the x / r update, |r| and the NEXT
  * iteration's rho are one sweep: 22 vector passes and 3 reductions per iteration instead of 27 and 4, identical bits. */
-typedef struct { PetscBool fused; Vec dinv; } KSP_BCGSHIP;
-
 static PetscErrorCode KSPSetUp_BCGSHIP(KSP ksp) { return KSPDefaultGetWork(ksp, 6); }
-static PetscErrorCode KSPSetFromOptions_BCGSHIP(KSP ksp) {
-  PetscInt iv = ((KSP_BCGSHIP *)ksp->data)->fused;
-  PetscErrorCode ierr = option_level(ksp, "-ksp_bcgs_fused", 0, 1, &iv);CHKERRQ(ierr);
-  ((KSP_BCGSHIP *)ksp->data)->fused = (PetscBool)iv;
-  return 0;
-}
-static PetscErrorCode KSPDestroy_BCGSHIP(KSP ksp) {
-  KSP_BCGSHIP *bc = (KSP_BCGSHIP *)ksp->data;
-  if (bc) { PetscErrorCode ierr = VecDestroy(&bc->dinv);CHKERRQ(ierr); HipFree(bc); ksp->data = NULL; }
-  return 0;
-}
-
-/* out = K in (K = B A, left preconditioning) and, when the types can, the reduction(s) that follow in the same pass.
- * which = 1: *s1 = (out, other); which = 2: *s1 = (other, out), *s2 = (out, out).  scratch: a vector for A in. */
-static PetscErrorCode bcgs_apply(KSP ksp, Mat A, const VecKrylovFusedOps *F, HipPCKind pck, Vec d, Vec in, Vec out, Vec scratch, int which, Vec other,
-                                 PetscScalar *s1, PetscReal *s2) {
-  PetscErrorCode ierr;
-  PetscBool done = PETSC_FALSE, scaled = PETSC_FALSE;
-  if (F && pck != PCKIND_GENERAL) {
-    if (d) { ierr = mat_mult_scaled(A, d, in, out, &scaled);CHKERRQ(ierr); }
-    if (!scaled) {
-      ierr = KSP_MatMult(ksp, A, in, scratch);CHKERRQ(ierr);
-      if (which == 1) { ierr = F->pmult_dot(out, scratch, d, other, s1, &done);CHKERRQ(ierr); }
-      else { ierr = F->pmult_dotnorm2(out, scratch, d, other, s1, s2, &done);CHKERRQ(ierr); }
-      if (!done) { ierr = KSP_PCApply(ksp, scratch, out);CHKERRQ(ierr); }
-    }
-  } else { ierr = KSP_PCApplyBAorAB(ksp, in, out, scratch);CHKERRQ(ierr); }
-  if (!done) {
-    if (which == 1) { ierr = VecDot(out, other, s1);CHKERRQ(ierr); }
-    else { ierr = VecDotNorm2(other, out, s1, s2);CHKERRQ(ierr); }
-  }
-  return 0;
-}
+static PetscErrorCode KSPSetFromOptions_BCGSHIP(KSP ksp) { return option_bool(ksp, "-ksp_bcgs_fused", &COMMON(ksp)->fused); }
+static PetscErrorCode KSPDestroy_BCGSHIP(KSP ksp) { return ksp_destroy_data(ksp, NULL); }
 
 static PetscErrorCode KSPSolve_BCGSHIP(KSP ksp) {
   PetscErrorCode ierr;
-  KSP_BCGSHIP *bc = (KSP_BCGSHIP *)ksp->data;
   Vec x = ksp->vec_sol, rhs = ksp->vec_rhs, r = ksp->work[0], rshadow = ksp->work[1], v = ksp->work[2], t = ksp->work[3], s = ksp->work[4], p = ksp->work[5];
   Mat A;
-  const VecKrylovFusedOps *F = bc->fused ? vec_fused_ops(x) : NULL;
-  HipPCKind pck = PCKIND_GENERAL;
-  Vec d = NULL;
+  const VecKrylovFusedOps *F = COMMON(ksp)->fused ? vec_fused_ops(x) : NULL;
+  HipPCKind pck;
+  Vec d;
   const PetscBool nonorm = (PetscBool)(ksp->normtype == KSP_NORM_NONE);
   PetscScalar rho = 0.0, rho_used, rho_prev = 1.0, alpha = 1.0, omega, omega_prev = 1.0, beta, sv;
   PetscReal rn = 0.0, tt;
@@ -737,7 +781,7 @@ static PetscErrorCode KSPSolve_BCGSHIP(KSP ksp) {
 
   if (ksp->pc_side == PC_RIGHT) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "right-preconditioned BiCGStab is outside the ported path");
   ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
-  if (F && !has_null_space(ksp)) { ierr = pc_diagonal_form(ksp, x, &bc->dinv, &pck);CHKERRQ(ierr); if (pck == PCKIND_DIAGONAL) d = bc->dinv; }
+  ierr = pc_diagonal_form(ksp, (PetscBool)(F != NULL), x, &pck, &d);CHKERRQ(ierr);
   ierr = KSPInitialResidual(ksp, x, v, t, r, rhs);CHKERRQ(ierr);
   if (!nonorm) { ierr = VecNorm(r, NORM_2, &rn);CHKERRQ(ierr); }
   ksp->its = 0;
@@ -755,11 +799,11 @@ static PetscErrorCode KSPSolve_BCGSHIP(KSP ksp) {
     rho_used = rho;
     beta = (rho / rho_prev) * (alpha / omega_prev);
     ierr = VecAXPBYPCZ(p, 1.0, -omega_prev * beta, beta, r, v);CHKERRQ(ierr);          /* p <- r - omega beta v + beta p */
-    ierr = bcgs_apply(ksp, A, F, pck, d, p, v, t, 1, rshadow, &sv, NULL);CHKERRQ(ierr); /* v <- K p, (v, r~) */
+    ierr = apply_operator(ksp, A, F, pck, d, p, v, t, 1, rshadow, &sv, NULL);CHKERRQ(ierr);   /* v <- K p, (v, r~) */
     if (sv == 0.0) SETERRQ(HipObjComm(ksp), PETSC_ERR_PLIB, "Divide by zero");
     alpha = rho / sv;
     ierr = VecWAXPY(s, -alpha, v, r);CHKERRQ(ierr);                                    /* s <- r - alpha v */
-    ierr = bcgs_apply(ksp, A, F, pck, d, s, t, r, 2, s, &sv, &tt);CHKERRQ(ierr);        /* t <- K s, (s, t), (t, t) */
+    ierr = apply_operator(ksp, A, F, pck, d, s, t, r, 2, s, &sv, &tt);CHKERRQ(ierr);    /* t <- K s, (s, t), (t, t) */
     if (tt == 0.0) {                                                                    /* t = 0: if s = 0 too, alpha p may be the solution */
       ierr = VecDot(s, s, &sv);CHKERRQ(ierr);
       if (sv != 0.0) { ksp->reason = KSP_DIVERGED_BREAKDOWN; break; }
@@ -796,10 +840,8 @@ static PetscErrorCode KSPSolve_BCGSHIP(KSP ksp) {
 }
 
 PetscErrorCode KSPCreate_BCGSHIPMI355X(KSP ksp) {
-  KSP_BCGSHIP *bc;
-  PetscErrorCode ierr = PetscMalloc(sizeof(*bc), &bc);CHKERRQ(ierr);
-  bc->fused = PETSC_TRUE; bc->dinv = NULL;
-  ksp->data = bc;
+  PetscErrorCode ierr = ksp_create_data(ksp, sizeof(KSPHipCommon), NULL);CHKERRQ(ierr);   /* the common header is all this type keeps */
+  COMMON(ksp)->fused = PETSC_TRUE;
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);
   ksp->ops->setup = KSPSetUp_BCGSHIP; ksp->ops->solve = KSPSolve_BCGSHIP; ksp->ops->setfromoptions = KSPSetFromOptions_BCGSHIP; ksp->ops->destroy = KSPDestroy_BCGSHIP;
   return 0;
@@ -823,12 +865,6 @@ static PetscErrorCode option_reals(KSP ksp, const char *name, PetscReal v[2], in
   *count = comma ? 2 : 1;
   return 0;
 }
-static PetscErrorCode start_residual(KSP ksp, Mat A, Vec x, Vec rhs, Vec r) {
-  PetscErrorCode ierr;
-  if (ksp->guess_zero) { ierr = VecCopy(rhs, r);CHKERRQ(ierr); }
-  else { ierr = KSP_MatMult(ksp, A, x, r);CHKERRQ(ierr); ierr = VecAYPX(r, -1.0, rhs);CHKERRQ(ierr); }
-  return 0;
-}
 /* the exit both solvers share once the loop has ended without a reason (cheby.c, rich.c): the budget is spent */
 static PetscErrorCode stationary_out_of_iterations(KSP ksp, PetscReal rn) {
   PetscErrorCode ierr;
@@ -839,7 +875,7 @@ static PetscErrorCode stationary_out_of_iterations(KSP ksp, PetscReal rn) {
   return 0;
 }
 
-typedef struct { PetscReal emin, emax; Vec dinv; } KSP_ChebyHIP;
+typedef struct { KSPHipCommon common; PetscReal emin, emax; } KSP_ChebyHIP;
 
 static PetscErrorCode KSPChebychevSetEigenvalues_ChebyHIP(KSP ksp, PetscReal emax, PetscReal emin) {
   KSP_ChebyHIP *ch = (KSP_ChebyHIP *)ksp->data;
@@ -849,11 +885,14 @@ static PetscErrorCode KSPChebychevSetEigenvalues_ChebyHIP(KSP ksp, PetscReal ema
   return 0;
 }
 /* the three-term update cannot be written with the public calls this library may use (no VecScale): the vectors' type must offer it */
+static PetscErrorCode cheby_ops(KSP ksp, Vec x, const VecKrylovFusedOps **F) {
+  *F = vec_fused_ops(x);
+  return needs_table(ksp, (PetscBool)(*F && (*F)->cheby_step), KSPCHEBYCHEVHIPMI355X, "Chebyshev step", "VecKrylovFusedOps_C", "chebychev");
+}
 static PetscErrorCode KSPSetUp_ChebyHIP(KSP ksp) {
+  const VecKrylovFusedOps *F;
   PetscErrorCode ierr = KSPDefaultGetWork(ksp, 3);CHKERRQ(ierr);
-  const VecKrylovFusedOps *F = vec_fused_ops(ksp->vec_sol ? ksp->vec_sol : ksp->work[0]);   /* the vectors the solve will run on */
-  if (!F || !F->cheby_step) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s needs vectors whose type offers the fused Chebyshev step (\"VecKrylovFusedOps_C\"); use -ksp_type chebychev on these vectors", KSPCHEBYCHEVHIPMI355X);
-  return 0;
+  return cheby_ops(ksp, ksp->vec_sol ? ksp->vec_sol : ksp->work[0], &F);   /* the vectors the solve will run on */
 }
 static PetscErrorCode KSPSetFromOptions_ChebyHIP(KSP ksp) {
   PetscReal v[2]; int count;
@@ -862,15 +901,10 @@ static PetscErrorCode KSPSetFromOptions_ChebyHIP(KSP ksp) {
   if (count == 2) { ierr = KSPChebychevSetEigenvalues_ChebyHIP(ksp, v[1], v[0]);CHKERRQ(ierr); }
   return 0;
 }
-static PetscErrorCode KSPDestroy_ChebyHIP(KSP ksp) {
-  KSP_ChebyHIP *ch = (KSP_ChebyHIP *)ksp->data;
-  PetscErrorCode ierr;
-  if (!ch) return 0;
-  ierr = VecDestroy(&ch->dinv);CHKERRQ(ierr);
-  HipFree(ch); ksp->data = NULL;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPChebychevSetEigenvalues_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
-  return 0;
-}
+static const KSPHipMethod cheby_methods[] = {
+  {"KSPChebychevSetEigenvalues_C", "KSPChebychevSetEigenvalues_ChebyHIP", (PetscVoidFunction)KSPChebychevSetEigenvalues_ChebyHIP},
+  {NULL, NULL, NULL}};
+static PetscErrorCode KSPDestroy_ChebyHIP(KSP ksp) { return ksp_destroy_data(ksp, cheby_methods); }
 
 static PetscErrorCode KSPSolve_ChebyHIP(KSP ksp) {
   PetscErrorCode ierr;
@@ -878,18 +912,18 @@ static PetscErrorCode KSPSolve_ChebyHIP(KSP ksp) {
   const KSPNormType nt = ksp->normtype;
   Vec x = ksp->vec_sol, rhs = ksp->vec_rhs, r = ksp->work[2];
   Vec p[3] = {x, ksp->work[0], ksp->work[1]};
-  const VecKrylovFusedOps *F = vec_fused_ops(x);
-  HipPCKind pck = PCKIND_GENERAL;
-  Vec d = NULL;
+  const VecKrylovFusedOps *F;
+  HipPCKind pck;
+  Vec d;
   Mat A;
   PetscScalar c[3], scale, mu, omegaprod, omega, Gamma = 1.0, zz = 0.0, rr = 0.0;
   PetscReal rn = 0.0;
   PetscInt km1 = 0, k = 1, kp1 = 2, i;
   PetscBool done;
 
-  if (!F || !F->cheby_step) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s needs vectors whose type offers the fused Chebyshev step; use -ksp_type chebychev on these vectors", KSPCHEBYCHEVHIPMI355X);
+  ierr = cheby_ops(ksp, x, &F);CHKERRQ(ierr);
   ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
-  if (!has_null_space(ksp)) { ierr = pc_diagonal_form(ksp, x, &ch->dinv, &pck);CHKERRQ(ierr); if (pck == PCKIND_DIAGONAL) d = ch->dinv; }
+  ierr = pc_diagonal_form(ksp, PETSC_TRUE, x, &pck, &d);CHKERRQ(ierr);
   ksp->its = 0;
   scale = 2.0 / (ch->emax + ch->emin);
   mu = 1.0 / (1.0 - scale * ch->emin);
@@ -950,13 +984,12 @@ static PetscErrorCode KSPSolve_ChebyHIP(KSP ksp) {
 
 PetscErrorCode KSPCreate_ChebychevHIPMI355X(KSP ksp) {
   KSP_ChebyHIP *ch;
-  PetscErrorCode ierr = PetscMalloc(sizeof(*ch), &ch);CHKERRQ(ierr);
-  ch->emin = 1.0e-2; ch->emax = 1.0e+2; ch->dinv = NULL;                                 /* KSPCreate_Chebychev's defaults */
-  ksp->data = ch;
+  PetscErrorCode ierr = ksp_create_data(ksp, sizeof(*ch), cheby_methods);CHKERRQ(ierr);
+  ch = (KSP_ChebyHIP *)ksp->data;
+  ch->emin = 1.0e-2; ch->emax = 1.0e+2;                                                  /* KSPCreate_Chebychev's defaults */
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_LEFT, 1);CHKERRQ(ierr);
   ksp->ops->setup = KSPSetUp_ChebyHIP; ksp->ops->solve = KSPSolve_ChebyHIP; ksp->ops->setfromoptions = KSPSetFromOptions_ChebyHIP; ksp->ops->destroy = KSPDestroy_ChebyHIP;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPChebychevSetEigenvalues_C", "KSPChebychevSetEigenvalues_ChebyHIP", (PetscVoidFunction)KSPChebychevSetEigenvalues_ChebyHIP);CHKERRQ(ierr);
   return 0;
 }
 
@@ -970,56 +1003,19 @@ PetscErrorCode KSPCreate_ChebychevHIPMI355X(KSP ksp) {
  * with the communicator-wide Begin, the product, and the End calls (all of them through the type's "VecSplitReductionOps_C").  The sweep of the last permitted iteration queues no sums, so no
  * exit leaves a split phase pending.  Vectors without the table, a sweep that refuses, or -ksp_pipecg_fused false: the public calls
  * of that step.  KSPHIPMI355XGetFusedStepCounts: steps taken by each route. */
-typedef struct { PetscBool fused; Vec dinv; PetscInt nfused, nopbyop; } KSP_PipeCGHIP;
-
-static const VecPipelinedCGFusedOps *vec_pipelined_ops(Vec x) {
-  PetscVoidFunction f = NULL;
-  if (PetscObjectQueryFunction((PetscObject)x, "VecPipelinedCGFusedOps_C", &f) || !f) return NULL;
-  return ((VecPipelinedCGFusedOpsGetFn)f)();
-}
 /* The split-phase reductions as the vectors' type provides them ("VecSplitReductionOps_C", what VecDotBegin / VecNormBegin / VecDotEnd /
  * VecNormEnd / PetscCommSplitReductionBegin of the object model dispatch to for these vectors).  A type without the table: Begin is
  * the whole reduction (VecDot / VecNorm), nothing is in flight and End has nothing left to do -- the vectors do not change between the
  * two, so the value is the one End would have delivered. */
-static const VecSplitReductionOps *vec_split_ops(Vec x) {
-  PetscVoidFunction f = NULL;
-  if (PetscObjectQueryFunction((PetscObject)x, "VecSplitReductionOps_C", &f) || !f) return NULL;
-  return ((const VecSplitReductionOps *(*)(void))f)();
-}
 static PetscErrorCode split_dot_begin(const VecSplitReductionOps *S, Vec x, Vec y, PetscScalar *v) { return S ? S->dot_begin(x, y, v) : VecDot(x, y, v); }
 static PetscErrorCode split_dot_end(const VecSplitReductionOps *S, Vec x, Vec y, PetscScalar *v) { return S ? S->dot_end(x, y, v) : 0; }
 static PetscErrorCode split_norm_begin(const VecSplitReductionOps *S, Vec x, PetscReal *v) { return S ? S->norm_begin(x, NORM_2, v) : VecNorm(x, NORM_2, v); }
 static PetscErrorCode split_norm_end(const VecSplitReductionOps *S, Vec x, PetscReal *v) { return S ? S->norm_end(x, NORM_2, v) : 0; }
 static PetscErrorCode split_comm_begin(const VecSplitReductionOps *S, Vec x) { return S && S->comm_begin ? S->comm_begin(HipObjComm(x)) : 0; }
 
-static PetscErrorCode KSPGetFusedStepCounts_PipeCGHIP(KSP ksp, PetscInt *fused, PetscInt *opbyop) {
-  const KSP_PipeCGHIP *pd = (const KSP_PipeCGHIP *)ksp->data;
-  *fused = pd->nfused; *opbyop = pd->nopbyop;
-  return 0;
-}
-PetscErrorCode KSPHIPMI355XGetFusedStepCounts(KSP ksp, PetscInt *fused, PetscInt *opbyop) {
-  PetscVoidFunction f = NULL;
-  PetscErrorCode ierr = PetscObjectQueryFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", &f);CHKERRQ(ierr);
-  *fused = 0; *opbyop = 0;
-  if (f) { ierr = ((PetscErrorCode (*)(KSP, PetscInt *, PetscInt *))f)(ksp, fused, opbyop);CHKERRQ(ierr); }
-  return 0;
-}
 static PetscErrorCode KSPSetUp_PipeCGHIP(KSP ksp) { return KSPDefaultGetWork(ksp, 9); }
-static PetscErrorCode KSPSetFromOptions_PipeCGHIP(KSP ksp) {
-  PetscInt iv = ((KSP_PipeCGHIP *)ksp->data)->fused;
-  PetscErrorCode ierr = option_level(ksp, "-ksp_pipecg_fused", 0, 1, &iv);CHKERRQ(ierr);
-  ((KSP_PipeCGHIP *)ksp->data)->fused = (PetscBool)iv;
-  return 0;
-}
-static PetscErrorCode KSPDestroy_PipeCGHIP(KSP ksp) {
-  KSP_PipeCGHIP *pd = (KSP_PipeCGHIP *)ksp->data;
-  PetscErrorCode ierr;
-  if (!pd) return 0;
-  ierr = VecDestroy(&pd->dinv);CHKERRQ(ierr);
-  HipFree(pd); ksp->data = NULL;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
-  return 0;
-}
+static PetscErrorCode KSPSetFromOptions_PipeCGHIP(KSP ksp) { return option_bool(ksp, "-ksp_pipecg_fused", &COMMON(ksp)->fused); }
+static PetscErrorCode KSPDestroy_PipeCGHIP(KSP ksp) { return ksp_destroy_data(ksp, counts_only); }
 
 enum { PIPE_NOTHING = 0, PIPE_RR = 1, PIPE_UU = 2, PIPE_RU = 3 };   /* what rides with w'u in an iteration's reduction: "rides" of pipecg_step */
 static int pipecg_rides(KSPNormType norm, PetscInt k) {             /* pipecg.c:124-131,138-145 */
@@ -1031,7 +1027,7 @@ static int pipecg_rides(KSPNormType norm, PetscInt k) {             /* pipecg.c:
 
 static PetscErrorCode KSPSolve_PipeCGHIP(KSP ksp) {
   PetscErrorCode ierr;
-  KSP_PipeCGHIP *pd = (KSP_PipeCGHIP *)ksp->data;
+  KSPHipCommon *pd = COMMON(ksp);      /* all this type keeps; count: (steps taken by the sweep, steps taken by the public calls) */
   const KSPNormType norm = ksp->normtype;
   Vec x = ksp->vec_sol, rhs = ksp->vec_rhs;
   Vec m = ksp->work[0], ABs_rec = ksp->work[1], dir = ksp->work[2], n = ksp->work[3], w = ksp->work[4];
@@ -1039,8 +1035,8 @@ static PetscErrorCode KSPSolve_PipeCGHIP(KSP ksp) {
   Vec normed = norm == KSP_NORM_UNPRECONDITIONED ? res : norm == KSP_NORM_PRECONDITIONED ? u : NULL;
   const VecSplitReductionOps *S = vec_split_ops(x);
   const VecPipelinedCGFusedOps *P = pd->fused && S ? vec_pipelined_ops(x) : NULL;   /* a sweep leaves its sums pending in the type's split phase */
-  HipPCKind pck = PCKIND_GENERAL;
-  Vec d = NULL;
+  HipPCKind pck;
+  Vec d;
   Mat A;
   PetscScalar step = 0.0, ratio = 0.0, ru = 0.0, ru_last = 0.0, wu = 0.0;
   PetscReal rn = 0.0;
@@ -1050,7 +1046,7 @@ static PetscErrorCode KSPSolve_PipeCGHIP(KSP ksp) {
 
   if (norm != KSP_NORM_PRECONDITIONED && norm != KSP_NORM_UNPRECONDITIONED && norm != KSP_NORM_NATURAL && norm != KSP_NORM_NONE) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "norm type %d", (int)norm);
   ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
-  if (P && P->pipecg_step && !has_null_space(ksp)) { ierr = pc_diagonal_form(ksp, x, &pd->dinv, &pck);CHKERRQ(ierr); if (pck == PCKIND_DIAGONAL) d = pd->dinv; }
+  ierr = pc_diagonal_form(ksp, (PetscBool)(P && P->pipecg_step), x, &pck, &d);CHKERRQ(ierr);
   ksp->its = 0;
   ierr = start_residual(ksp, A, x, rhs, res);CHKERRQ(ierr);
   ierr = KSP_PCApply(ksp, res, u);CHKERRQ(ierr);
@@ -1092,7 +1088,7 @@ static PetscErrorCode KSPSolve_PipeCGHIP(KSP ksp) {
       /* the whole update, iteration k+1's m and its sums in one sweep; the last permitted iteration has no successor to reduce for */
       const int next = k + 1 < ksp->max_it ? pipecg_rides(norm, k + 1) : PIPE_NOTHING;
       ierr = P->pipecg_step(x, u, w, res, ABs_rec, Bs_rec, dir, s, n, m, d, pck != PCKIND_GENERAL ? m : NULL, (PetscBool)(k == 0), k == 0 ? 0.0 : ratio, step, next, &done);CHKERRQ(ierr);
-      if (done) { pending = (PetscBool)(next != PIPE_NOTHING); m_formed = (PetscBool)(pck != PCKIND_GENERAL); pd->nfused++; }
+      if (done) { pending = (PetscBool)(next != PIPE_NOTHING); m_formed = (PetscBool)(pck != PCKIND_GENERAL); pd->count[0]++; }
     }
     if (!done) {
       if (k > 0) {
@@ -1110,7 +1106,7 @@ static PetscErrorCode KSPSolve_PipeCGHIP(KSP ksp) {
       ierr = VecAXPY(u, -step, Bs_rec);CHKERRQ(ierr);
       ierr = VecAXPY(w, -step, ABs_rec);CHKERRQ(ierr);
       ierr = VecAXPY(res, -step, s);CHKERRQ(ierr);
-      pd->nopbyop++;
+      pd->count[1]++;
     }
     ru_last = ru;
     ksp->its = ++k;
@@ -1120,16 +1116,13 @@ static PetscErrorCode KSPSolve_PipeCGHIP(KSP ksp) {
 }
 
 PetscErrorCode KSPCreate_PIPECGHIPMI355X(KSP ksp) {
-  KSP_PipeCGHIP *pd;
-  PetscErrorCode ierr = PetscMalloc(sizeof(*pd), &pd);CHKERRQ(ierr);
-  pd->fused = PETSC_TRUE; pd->dinv = NULL; pd->nfused = 0; pd->nopbyop = 0;
-  ksp->data = pd;
+  PetscErrorCode ierr = ksp_create_data(ksp, sizeof(KSPHipCommon), counts_only);CHKERRQ(ierr);
+  COMMON(ksp)->fused = PETSC_TRUE;
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 1);CHKERRQ(ierr);    /* the four of KSPPIPECG, pipecg.c:199-202 */
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_LEFT, 1);CHKERRQ(ierr);
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_NATURAL, PC_LEFT, 1);CHKERRQ(ierr);
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_NONE, PC_LEFT, 1);CHKERRQ(ierr);
   ksp->ops->setup = KSPSetUp_PipeCGHIP; ksp->ops->solve = KSPSolve_PipeCGHIP; ksp->ops->setfromoptions = KSPSetFromOptions_PipeCGHIP; ksp->ops->destroy = KSPDestroy_PipeCGHIP;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "KSPGetFusedStepCounts_PipeCGHIP", (PetscVoidFunction)KSPGetFusedStepCounts_PipeCGHIP);CHKERRQ(ierr);
   return 0;
 }
 
@@ -1148,52 +1141,35 @@ PetscErrorCode KSPCreate_PIPECGHIPMI355X(KSP ksp) {
  * are the `first` form of the update sweep: VecScale is not among the calls this library takes from PETSc, so like chebychevhipmi355x
  * the type has no op-by-op route and KSPSetUp returns PETSC_ERR_SUP on vectors without the table (-ksp_type minres is that route).
  * KSPHIPMI355XGetFusedStepCounts: (Lanczos sweeps run, 0). */
-typedef struct { Vec dinv; PetscInt nsweeps; } KSP_MinresHIP;
-
-static const VecMinresFusedOps *vec_minres_ops(Vec x) {
-  PetscVoidFunction f = NULL;
-  if (PetscObjectQueryFunction((PetscObject)x, "VecMinresFusedOps_C", &f) || !f) return NULL;
-  return ((VecMinresFusedOpsGetFn)f)();
-}
-static PetscErrorCode KSPGetFusedStepCounts_MinresHIP(KSP ksp, PetscInt *fused, PetscInt *opbyop) {
-  *fused = ((const KSP_MinresHIP *)ksp->data)->nsweeps; *opbyop = 0;
-  return 0;
+static PetscErrorCode minres_ops(KSP ksp, Vec x, const VecMinresFusedOps **M) {
+  *M = vec_minres_ops(x);
+  return needs_table(ksp, (PetscBool)(*M != NULL), KSPMINRESHIPMI355X, "MINRES sweeps", "VecMinresFusedOps_C", "minres");
 }
 static PetscErrorCode KSPSetUp_MinresHIP(KSP ksp) {
+  const VecMinresFusedOps *M;
   PetscErrorCode ierr = KSPDefaultGetWork(ksp, 8);CHKERRQ(ierr);
-  const VecMinresFusedOps *M = vec_minres_ops(ksp->vec_sol ? ksp->vec_sol : ksp->work[0]);   /* the vectors the solve will run on */
-  if (!M || !M->minres_lanczos || !M->minres_update) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s needs vectors whose type offers the fused MINRES sweeps (\"VecMinresFusedOps_C\"); use -ksp_type minres on these vectors", KSPMINRESHIPMI355X);
-  return 0;
+  return minres_ops(ksp, ksp->vec_sol ? ksp->vec_sol : ksp->work[0], &M);   /* the vectors the solve will run on */
 }
-static PetscErrorCode KSPDestroy_MinresHIP(KSP ksp) {
-  KSP_MinresHIP *md = (KSP_MinresHIP *)ksp->data;
-  PetscErrorCode ierr;
-  if (!md) return 0;
-  ierr = VecDestroy(&md->dinv);CHKERRQ(ierr);
-  HipFree(md); ksp->data = NULL;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
-  return 0;
-}
+static PetscErrorCode KSPDestroy_MinresHIP(KSP ksp) { return ksp_destroy_data(ksp, counts_only); }
 
 static PetscErrorCode KSPSolve_MinresHIP(KSP ksp) {
   PetscErrorCode ierr;
-  KSP_MinresHIP *md = (KSP_MinresHIP *)ksp->data;
   const PetscReal haptol = 1.e-18;
   Vec X = ksp->vec_sol, B = ksp->vec_rhs;
   Vec R = ksp->work[0], Z = ksp->work[1], U = ksp->work[2], V = ksp->work[3], W = ksp->work[4], UOLD = ksp->work[5], VOLD = ksp->work[6], WOLD = ksp->work[7];
-  const VecMinresFusedOps *M = vec_minres_ops(X);
+  const VecMinresFusedOps *M;
   const VecKrylovFusedOps *F = vec_fused_ops(X);
-  HipPCKind pck = PCKIND_GENERAL;
-  Vec d = NULL;
+  HipPCKind pck;
+  Vec d;
   Mat A;
   PetscScalar alpha = 0.0, beta, betaold, eta, c = 1.0, cold = 1.0, coold, s = 0.0, sold = 0.0, soold, rho0, rho1, rho2, rho3, dp = 0.0;
   PetscReal np;
   PetscInt i;
   PetscBool done;
 
-  if (!M || !M->minres_lanczos || !M->minres_update) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s needs vectors whose type offers the fused MINRES sweeps; use -ksp_type minres on these vectors", KSPMINRESHIPMI355X);
+  ierr = minres_ops(ksp, X, &M);CHKERRQ(ierr);
   ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
-  if (!has_null_space(ksp)) { ierr = pc_diagonal_form(ksp, X, &md->dinv, &pck);CHKERRQ(ierr); if (pck == PCKIND_DIAGONAL) d = md->dinv; }
+  ierr = pc_diagonal_form(ksp, PETSC_TRUE, X, &pck, &d);CHKERRQ(ierr);
   ksp->its = 0;
   ierr = VecSet(UOLD, 0.0);CHKERRQ(ierr);
   ierr = VecCopy(UOLD, VOLD);CHKERRQ(ierr);
@@ -1221,7 +1197,7 @@ static PetscErrorCode KSPSolve_MinresHIP(KSP ksp) {
     if (!d) { ierr = KSP_PCApply(ksp, R, Z);CHKERRQ(ierr); }
     ierr = M->minres_lanczos(R, Z, V, U, VOLD, UOLD, d, alpha, on_device, beta, &dp, &alpha, &done);CHKERRQ(ierr);
     if (!done) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "the fused MINRES sweep refused these vectors; use -ksp_type minres");
-    md->nsweeps++;
+    COMMON(ksp)->count[0]++;                                             /* (Lanczos sweeps run, 0) */
     betaold = beta;
     if (dp < haptol) { ksp->reason = KSP_DIVERGED_INDEFINITE_PC; break; }
     beta = PetscSqrtReal(PetscAbsScalar(dp));
@@ -1247,13 +1223,9 @@ static PetscErrorCode KSPSolve_MinresHIP(KSP ksp) {
 }
 
 PetscErrorCode KSPCreate_MINRESHIPMI355X(KSP ksp) {
-  KSP_MinresHIP *md;
-  PetscErrorCode ierr = PetscMalloc(sizeof(*md), &md);CHKERRQ(ierr);
-  md->dinv = NULL; md->nsweeps = 0;
-  ksp->data = md;
+  PetscErrorCode ierr = ksp_create_data(ksp, sizeof(KSPHipCommon), counts_only);CHKERRQ(ierr);
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);    /* the one of KSPMINRES */
   ksp->ops->setup = KSPSetUp_MinresHIP; ksp->ops->solve = KSPSolve_MinresHIP; ksp->ops->destroy = KSPDestroy_MinresHIP;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "KSPGetFusedStepCounts_MinresHIP", (PetscVoidFunction)KSPGetFusedStepCounts_MinresHIP);CHKERRQ(ierr);
   return 0;
 }
 
@@ -1269,59 +1241,19 @@ PetscErrorCode KSPCreate_MINRESHIPMI355X(KSP ksp) {
  *                   so the host runs both checkpoints FIRST and then launches the one sweep with the half steps that were taken (an
  *                   exit inside them: without the tail).  A monitor that looks at x therefore sees the x of before this iteration's
  *                   half steps; the history, the exits and the x returned are those of the call-by-call sequence.
- * K goes the way of bcgs_apply: PCJACOBI on a matrix that offers it: d .* (A x) in the product's own kernel; PCJACOBI / PCNONE
+ * K goes through apply_operator, as in bcgshipmi355x: PCJACOBI on a matrix that offers it: d .* (A x) in the product's own kernel; PCJACOBI / PCNONE
  * otherwise: PCApply fused with s = v'rp ("pmult_dot"); any other PC, or a null space: KSP_PCApplyBAorAB.  The three sweeps do not
  * involve the PC.  Like bcgshipmi355x -- and unlike minreshipmi355x -- the types work on any vectors: without the table, with the option
  * off, or when a sweep answers done = PETSC_FALSE, the same function makes the public calls of the sequence.
  * s == 0 sets KSP_DIVERGED_BREAKDOWN where the reference divides.
  * KSPHIPMI355XGetFusedStepCounts: (fused sweeps run, iterations in which a step ran through the public calls). */
-typedef struct { PetscBool fused, cgs; Vec dinv; PetscInt nsweeps, nopbyop; } KSP_TfqmrHIP;
+typedef struct { KSPHipCommon common; PetscBool cgs; } KSP_TfqmrHIP;   /* count: (fused sweeps run, iterations with a step through the public calls) */
 
-static const VecTfqmrFusedOps *vec_tfqmr_ops(Vec x) {
-  PetscVoidFunction f = NULL;
-  const VecTfqmrFusedOps *M;
-  if (PetscObjectQueryFunction((PetscObject)x, "VecTfqmrFusedOps_C", &f) || !f) return NULL;
-  M = ((VecTfqmrFusedOpsGetFn)f)();
-  return (M && M->tfqmr_qt && M->tfqmr_resid && M->tfqmr_update) ? M : NULL;
-}
-static PetscErrorCode KSPGetFusedStepCounts_TfqmrHIP(KSP ksp, PetscInt *fused, PetscInt *opbyop) {
-  const KSP_TfqmrHIP *td = (const KSP_TfqmrHIP *)ksp->data;
-  *fused = td->nsweeps; *opbyop = td->nopbyop;
-  return 0;
-}
 static PetscErrorCode KSPSetUp_TfqmrHIP(KSP ksp) { return KSPDefaultGetWork(ksp, ((KSP_TfqmrHIP *)ksp->data)->cgs ? 8 : 9); }   /* CGS: no D */
 static PetscErrorCode KSPSetFromOptions_TfqmrHIP(KSP ksp) {
-  KSP_TfqmrHIP *td = (KSP_TfqmrHIP *)ksp->data;
-  PetscInt iv = td->fused;
-  PetscErrorCode ierr = option_level(ksp, td->cgs ? "-ksp_cgs_fused" : "-ksp_tfqmr_fused", 0, 1, &iv);CHKERRQ(ierr);
-  td->fused = (PetscBool)iv;
-  return 0;
+  return option_bool(ksp, ((KSP_TfqmrHIP *)ksp->data)->cgs ? "-ksp_cgs_fused" : "-ksp_tfqmr_fused", &COMMON(ksp)->fused);
 }
-static PetscErrorCode KSPDestroy_TfqmrHIP(KSP ksp) {
-  KSP_TfqmrHIP *td = (KSP_TfqmrHIP *)ksp->data;
-  PetscErrorCode ierr;
-  if (!td) return 0;
-  ierr = VecDestroy(&td->dinv);CHKERRQ(ierr);
-  HipFree(td); ksp->data = NULL;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
-  return 0;
-}
-
-/* out = K in by the route of bcgs_apply; other != NULL: *s = (out, other), in the preconditioner's pass where the types can */
-static PetscErrorCode tfqmr_apply(KSP ksp, Mat A, const VecKrylovFusedOps *F, HipPCKind pck, Vec d, Vec in, Vec out, Vec scratch, Vec other, PetscScalar *s) {
-  PetscErrorCode ierr;
-  PetscBool done = PETSC_FALSE, scaled = PETSC_FALSE;
-  if (F && pck != PCKIND_GENERAL) {
-    if (d) { ierr = mat_mult_scaled(A, d, in, out, &scaled);CHKERRQ(ierr); }
-    if (!scaled) {
-      ierr = KSP_MatMult(ksp, A, in, scratch);CHKERRQ(ierr);
-      if (other) { ierr = F->pmult_dot(out, scratch, d, other, s, &done);CHKERRQ(ierr); }
-      if (!done) { ierr = KSP_PCApply(ksp, scratch, out);CHKERRQ(ierr); }
-    }
-  } else { ierr = KSP_PCApplyBAorAB(ksp, in, out, scratch);CHKERRQ(ierr); }
-  if (other && !done) { ierr = VecDot(out, other, s);CHKERRQ(ierr); }
-  return 0;
-}
+static PetscErrorCode KSPDestroy_TfqmrHIP(KSP ksp) { return ksp_destroy_data(ksp, counts_only); }
 
 static PetscErrorCode KSPSolve_TfqmrHIP(KSP ksp) {
   PetscErrorCode ierr;
@@ -1330,10 +1262,10 @@ static PetscErrorCode KSPSolve_TfqmrHIP(KSP ksp) {
   Vec X = ksp->vec_sol, B = ksp->vec_rhs;
   Vec R = ksp->work[0], RP = ksp->work[1], V = ksp->work[2], T = ksp->work[3], Q = ksp->work[4], P = ksp->work[5], U = ksp->work[6], T1 = ksp->work[7];
   Vec D = cgs ? NULL : ksp->work[8], AUQ = V;
-  const VecTfqmrFusedOps *M = td->fused ? vec_tfqmr_ops(X) : NULL;
-  const VecKrylovFusedOps *F = td->fused ? vec_fused_ops(X) : NULL;
-  HipPCKind pck = PCKIND_GENERAL;
-  Vec d = NULL;
+  const VecTfqmrFusedOps *M = td->common.fused ? vec_tfqmr_ops(X) : NULL;
+  const VecKrylovFusedOps *F = td->common.fused ? vec_fused_ops(X) : NULL;
+  HipPCKind pck;
+  Vec d;
   Mat A;
   PetscScalar rho = 0.0, rhoold, a, s, b, rr, etaold = 0.0, psiold = 0.0;
   PetscReal dp, dpold, tau;
@@ -1341,7 +1273,7 @@ static PetscErrorCode KSPSolve_TfqmrHIP(KSP ksp) {
 
   if (ksp->pc_side == PC_RIGHT) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s does not support right preconditioning", cgs ? KSPCGSHIPMI355X : KSPTFQMRHIPMI355X);
   ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
-  if (F && !has_null_space(ksp)) { ierr = pc_diagonal_form(ksp, X, &td->dinv, &pck);CHKERRQ(ierr); if (pck == PCKIND_DIAGONAL) d = td->dinv; }
+  ierr = pc_diagonal_form(ksp, (PetscBool)(F != NULL), X, &pck, &d);CHKERRQ(ierr);
   ksp->its = 0;
   ierr = KSPInitialResidual(ksp, X, V, T, R, B);CHKERRQ(ierr);
   ierr = VecNorm(R, NORM_2, &dp);CHKERRQ(ierr);
@@ -1352,7 +1284,7 @@ static PetscErrorCode KSPSolve_TfqmrHIP(KSP ksp) {
   ierr = VecDot(R, RP, &rhoold);CHKERRQ(ierr);
   ierr = VecCopy(R, U);CHKERRQ(ierr);
   ierr = VecCopy(R, P);CHKERRQ(ierr);
-  ierr = tfqmr_apply(ksp, A, F, pck, d, P, V, T1, RP, &s);CHKERRQ(ierr);                /* V <- K P and s = V'RP of iteration 0 */
+  ierr = apply_operator(ksp, A, F, pck, d, P, V, T1, 1, RP, &s, NULL);CHKERRQ(ierr);    /* V <- K P and s = V'RP of iteration 0 */
   if (!cgs) { ierr = VecSet(D, 0.0);CHKERRQ(ierr); }
   tau = dp; dpold = dp;
 
@@ -1363,17 +1295,17 @@ static PetscErrorCode KSPSolve_TfqmrHIP(KSP ksp) {
     if (s == 0.0) { ksp->reason = KSP_DIVERGED_BREAKDOWN; break; }
     a = rhoold / s;
     if (M) { ierr = M->tfqmr_qt(U, V, Q, T, cgs ? X : NULL, a, &done);CHKERRQ(ierr); }
-    if (done) td->nsweeps++;
+    if (done) td->common.count[0]++;
     else {
       all_fused = PETSC_FALSE;
       ierr = VecWAXPY(Q, -a, V, U);CHKERRQ(ierr);
       ierr = VecWAXPY(T, 1.0, U, Q);CHKERRQ(ierr);
       if (cgs) { ierr = VecAXPY(X, a, T);CHKERRQ(ierr); }
     }
-    ierr = tfqmr_apply(ksp, A, F, pck, d, T, AUQ, T1, NULL, NULL);CHKERRQ(ierr);        /* AUQ <- K T */
+    ierr = apply_operator(ksp, A, F, pck, d, T, AUQ, T1, 0, NULL, NULL, NULL);CHKERRQ(ierr);   /* AUQ <- K T */
     done = PETSC_FALSE;
     if (M) { ierr = M->tfqmr_resid(R, AUQ, RP, a, &rr, &rho, &done);CHKERRQ(ierr); }
-    if (done) { td->nsweeps++; dp = PetscSqrtReal(rr); have_rho = PETSC_TRUE; }
+    if (done) { td->common.count[0]++; dp = PetscSqrtReal(rr); have_rho = PETSC_TRUE; }
     else {
       all_fused = PETSC_FALSE;
       ierr = VecAXPY(R, -a, AUQ);CHKERRQ(ierr);
@@ -1401,7 +1333,7 @@ static PetscErrorCode KSPSolve_TfqmrHIP(KSP ksp) {
       }
       if (!ksp->reason) ksp->its = i + 1;
     }
-    if (cgs && ksp->reason) { if (!all_fused) td->nopbyop++; break; }
+    if (cgs && ksp->reason) { if (!all_fused) td->common.count[1]++; break; }
     b = 0.0;
     if (!ksp->reason) {
       if (!have_rho) { ierr = VecDot(R, RP, &rho);CHKERRQ(ierr); }
@@ -1409,7 +1341,7 @@ static PetscErrorCode KSPSolve_TfqmrHIP(KSP ksp) {
     }
     done = PETSC_FALSE;
     if (M) { ierr = M->tfqmr_update(D, X, U, Q, R, P, nhalves, cfm[0], etam[0], cfm[1], etam[1], (PetscBool)!ksp->reason, b, &done);CHKERRQ(ierr); }
-    if (done) td->nsweeps++;
+    if (done) td->common.count[0]++;
     else {
       all_fused = PETSC_FALSE;
       for (m = 0; m < nhalves; m++) {
@@ -1422,9 +1354,9 @@ static PetscErrorCode KSPSolve_TfqmrHIP(KSP ksp) {
         ierr = VecWAXPY(P, b, Q, U);CHKERRQ(ierr);
       }
     }
-    if (!all_fused) td->nopbyop++;
+    if (!all_fused) td->common.count[1]++;
     if (ksp->reason) break;
-    ierr = tfqmr_apply(ksp, A, F, pck, d, P, V, T1, RP, &s);CHKERRQ(ierr);              /* V <- K P and the next s = V'RP */
+    ierr = apply_operator(ksp, A, F, pck, d, P, V, T1, 1, RP, &s, NULL);CHKERRQ(ierr);  /* V <- K P and the next s = V'RP */
     rhoold = rho; dpold = dp;
   }
   if (i >= ksp->max_it) ksp->reason = KSP_DIVERGED_ITS;
@@ -1432,13 +1364,10 @@ static PetscErrorCode KSPSolve_TfqmrHIP(KSP ksp) {
 }
 
 static PetscErrorCode tfqmr_create(KSP ksp, PetscBool cgs) {
-  KSP_TfqmrHIP *td;
-  PetscErrorCode ierr = PetscMalloc(sizeof(*td), &td);CHKERRQ(ierr);
-  td->fused = PETSC_TRUE; td->cgs = cgs; td->dinv = NULL; td->nsweeps = 0; td->nopbyop = 0;
-  ksp->data = td;
+  PetscErrorCode ierr = ksp_create_data(ksp, sizeof(KSP_TfqmrHIP), counts_only);CHKERRQ(ierr);
+  COMMON(ksp)->fused = PETSC_TRUE; ((KSP_TfqmrHIP *)ksp->data)->cgs = cgs;
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);    /* the one of KSPTFQMR and KSPCGS */
   ksp->ops->setup = KSPSetUp_TfqmrHIP; ksp->ops->solve = KSPSolve_TfqmrHIP; ksp->ops->setfromoptions = KSPSetFromOptions_TfqmrHIP; ksp->ops->destroy = KSPDestroy_TfqmrHIP;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "KSPGetFusedStepCounts_TfqmrHIP", (PetscVoidFunction)KSPGetFusedStepCounts_TfqmrHIP);CHKERRQ(ierr);
   return 0;
 }
 PetscErrorCode KSPCreate_TFQMRHIPMI355X(KSP ksp) { return tfqmr_create(ksp, PETSC_FALSE); }
@@ -1458,15 +1387,6 @@ PetscErrorCode KSPCreate_CGSHIPMI355X(KSP ksp) { return tfqmr_create(ksp, PETSC_
  * Left preconditioning; a null space is PETSC_ERR_SUP at set-up; beta == 0 in the first iteration and dpi == 0 set KSP_DIVERGED_BREAKDOWN.
  * KSPHIPMI355XGetFusedStepCounts: (fused sweeps run, iterations in which a step ran through the public calls).  bicg_dirs runs once per
  * iteration entered, bicg_update once per iteration that gets past dpi: 2 its sweeps, and 2 its + 1 after a breakdown at dpi == 0. */
-typedef struct { PetscBool fused; Vec dinv; PetscInt nsweeps, nopbyop; } KSP_BicgHIP;
-
-static const VecBicgFusedOps *vec_bicg_ops(Vec x) {
-  PetscVoidFunction f = NULL;
-  const VecBicgFusedOps *M;
-  if (PetscObjectQueryFunction((PetscObject)x, "VecBicgFusedOps_C", &f) || !f) return NULL;
-  M = ((VecBicgFusedOpsGetFn)f)();
-  return (M && M->bicg_dirs && M->bicg_update) ? M : NULL;
-}
 /* KSP_MatMultTranspose / KSP_PCApplyTranspose of kspimpl.h.  On the harness the plug-in dispatches through the function tables it can see,
  * as an implementation does (the library exports the two for the harness's own KSPBICG) */
 static PetscErrorCode bicg_mult_transpose(KSP ksp, Mat A, Vec x, Vec y) {
@@ -1492,45 +1412,26 @@ static PetscErrorCode bicg_pc_apply_transpose(KSP ksp, Vec x, Vec y) {
   return 0;
 #endif
 }
-static PetscErrorCode KSPGetFusedStepCounts_BicgHIP(KSP ksp, PetscInt *fused, PetscInt *opbyop) {
-  const KSP_BicgHIP *bd = (const KSP_BicgHIP *)ksp->data;
-  *fused = bd->nsweeps; *opbyop = bd->nopbyop;
-  return 0;
-}
 static PetscErrorCode KSPSetUp_BicgHIP(KSP ksp) {
   if (ksp->pc_side == PC_RIGHT || ksp->pc_side == PC_SYMMETRIC) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s: left preconditioning only", KSPBICGHIPMI355X);
   if (has_null_space(ksp)) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s with a null space: there is no removal behind the transposed preconditioner application", KSPBICGHIPMI355X);
   return KSPDefaultGetWork(ksp, 6);
 }
-static PetscErrorCode KSPSetFromOptions_BicgHIP(KSP ksp) {
-  KSP_BicgHIP *bd = (KSP_BicgHIP *)ksp->data;
-  PetscInt iv = bd->fused;
-  PetscErrorCode ierr = option_level(ksp, "-ksp_bicg_fused", 0, 1, &iv);CHKERRQ(ierr);
-  bd->fused = (PetscBool)iv;
-  return 0;
-}
-static PetscErrorCode KSPDestroy_BicgHIP(KSP ksp) {
-  KSP_BicgHIP *bd = (KSP_BicgHIP *)ksp->data;
-  PetscErrorCode ierr;
-  if (!bd) return 0;
-  ierr = VecDestroy(&bd->dinv);CHKERRQ(ierr);
-  HipFree(bd); ksp->data = NULL;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
-  return 0;
-}
+static PetscErrorCode KSPSetFromOptions_BicgHIP(KSP ksp) { return option_bool(ksp, "-ksp_bicg_fused", &COMMON(ksp)->fused); }
+static PetscErrorCode KSPDestroy_BicgHIP(KSP ksp) { return ksp_destroy_data(ksp, counts_only); }
 static PetscErrorCode bicg_precondition(KSP ksp, Vec Rr, Vec Rl, Vec Zr, Vec Zl) {
   PetscErrorCode ierr = KSP_PCApply(ksp, Rr, Zr);CHKERRQ(ierr);
   return bicg_pc_apply_transpose(ksp, Rl, Zl);
 }
 static PetscErrorCode KSPSolve_BicgHIP(KSP ksp) {
   PetscErrorCode ierr;
-  KSP_BicgHIP *bd = (KSP_BicgHIP *)ksp->data;
+  KSPHipCommon *bd = COMMON(ksp);      /* all this type keeps; count: (fused sweeps run, iterations with a step through the public calls) */
   Vec X = ksp->vec_sol, B = ksp->vec_rhs;
   Vec Rr = ksp->work[0], Rl = ksp->work[1], Zr = ksp->work[2], Zl = ksp->work[3], Pr = ksp->work[4], Pl = ksp->work[5];
   const VecBicgFusedOps *M = bd->fused ? vec_bicg_ops(X) : NULL;
   const PetscBool pnorm = (PetscBool)(ksp->normtype == KSP_NORM_PRECONDITIONED);
-  HipPCKind pck = PCKIND_GENERAL;
-  Vec d = NULL;
+  HipPCKind pck;
+  Vec d;
   Mat A;
   PetscScalar dpi, a, beta = 0.0, betaold = 1.0, nrm2 = 0.0;
   PetscBool have_beta = PETSC_FALSE;
@@ -1539,10 +1440,9 @@ static PetscErrorCode KSPSolve_BicgHIP(KSP ksp) {
 
   if (has_null_space(ksp)) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s with a null space: there is no removal behind the transposed preconditioner application", KSPBICGHIPMI355X);
   ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
-  if (M) { ierr = pc_diagonal_form(ksp, X, &bd->dinv, &pck);CHKERRQ(ierr); if (pck == PCKIND_DIAGONAL) d = bd->dinv; }
+  ierr = pc_diagonal_form(ksp, (PetscBool)(M != NULL), X, &pck, &d);CHKERRQ(ierr);     /* (no null space here: refused above) */
   ksp->its = 0;
-  if (ksp->guess_zero) { ierr = VecCopy(B, Rr);CHKERRQ(ierr); }
-  else { ierr = KSP_MatMult(ksp, A, X, Rr);CHKERRQ(ierr); ierr = VecAYPX(Rr, -1.0, B);CHKERRQ(ierr); }
+  ierr = start_residual(ksp, A, X, B, Rr);CHKERRQ(ierr);
   ierr = VecCopy(Rr, Rl);CHKERRQ(ierr);
   ierr = bicg_precondition(ksp, Rr, Rl, Zr, Zl);CHKERRQ(ierr);
   ierr = VecNorm(pnorm ? Zr : Rr, NORM_2, &dp);CHKERRQ(ierr);
@@ -1557,7 +1457,7 @@ static PetscErrorCode KSPSolve_BicgHIP(KSP ksp) {
     if (!i && beta == 0.0) { ksp->reason = KSP_DIVERGED_BREAKDOWN; return 0; }
     b = i ? beta / betaold : 0.0;
     if (M) { ierr = M->bicg_dirs(Pr, Pl, Zr, Zl, b, (PetscBool)!i, &done);CHKERRQ(ierr); }
-    if (done) bd->nsweeps++;
+    if (done) bd->count[0]++;
     else {
       all_fused = PETSC_FALSE;
       if (!i) { ierr = VecCopy(Zr, Pr);CHKERRQ(ierr); ierr = VecCopy(Zl, Pl);CHKERRQ(ierr); }
@@ -1567,12 +1467,12 @@ static PetscErrorCode KSPSolve_BicgHIP(KSP ksp) {
     ierr = KSP_MatMult(ksp, A, Pr, Zr);CHKERRQ(ierr);
     ierr = bicg_mult_transpose(ksp, A, Pl, Zl);CHKERRQ(ierr);
     ierr = VecDot(Zr, Pl, &dpi);CHKERRQ(ierr);
-    if (dpi == 0.0) { ksp->reason = KSP_DIVERGED_BREAKDOWN; if (!all_fused) bd->nopbyop++; break; }
+    if (dpi == 0.0) { ksp->reason = KSP_DIVERGED_BREAKDOWN; if (!all_fused) bd->count[1]++; break; }
     a = beta / dpi;
     done = PETSC_FALSE;
     if (M) { ierr = M->bicg_update(X, Rr, Rl, Pr, Zr, Zl, d, (PetscBool)(pck == PCKIND_IDENTITY), a, pnorm ? 0 : 1, &beta, &nrm2, &done);CHKERRQ(ierr); }
     if (done) {
-      bd->nsweeps++;
+      bd->count[0]++;
       folded = (PetscBool)(pck != PCKIND_GENERAL);
       if (folded) { have_beta = PETSC_TRUE; dp = PetscSqrtReal(nrm2); }
       else if (pnorm) { ierr = bicg_precondition(ksp, Rr, Rl, Zr, Zl);CHKERRQ(ierr); ierr = VecNorm(Zr, NORM_2, &dp);CHKERRQ(ierr); }
@@ -1585,7 +1485,7 @@ static PetscErrorCode KSPSolve_BicgHIP(KSP ksp) {
       if (pnorm) { ierr = bicg_precondition(ksp, Rr, Rl, Zr, Zl);CHKERRQ(ierr); }
       ierr = VecNorm(pnorm ? Zr : Rr, NORM_2, &dp);CHKERRQ(ierr);
     }
-    if (!all_fused) bd->nopbyop++;
+    if (!all_fused) bd->count[1]++;
     ksp->its = i + 1;
     ierr = report(ksp, i + 1, dp);CHKERRQ(ierr);
     ierr = KSPTestConvergence(ksp, i + 1, dp);CHKERRQ(ierr);
@@ -1596,14 +1496,11 @@ static PetscErrorCode KSPSolve_BicgHIP(KSP ksp) {
   return 0;
 }
 PetscErrorCode KSPCreate_BICGHIPMI355X(KSP ksp) {
-  KSP_BicgHIP *bd;
-  PetscErrorCode ierr = PetscMalloc(sizeof(*bd), &bd);CHKERRQ(ierr);
-  bd->fused = PETSC_TRUE; bd->dinv = NULL; bd->nsweeps = 0; bd->nopbyop = 0;
-  ksp->data = bd;
+  PetscErrorCode ierr = ksp_create_data(ksp, sizeof(KSPHipCommon), counts_only);CHKERRQ(ierr);
+  COMMON(ksp)->fused = PETSC_TRUE;
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);      /* the two of KSPBICG */
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_LEFT, 1);CHKERRQ(ierr);
   ksp->ops->setup = KSPSetUp_BicgHIP; ksp->ops->solve = KSPSolve_BicgHIP; ksp->ops->setfromoptions = KSPSetFromOptions_BicgHIP; ksp->ops->destroy = KSPDestroy_BicgHIP;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPHIPMI355XGetFusedStepCounts_C", "KSPGetFusedStepCounts_BicgHIP", (PetscVoidFunction)KSPGetFusedStepCounts_BicgHIP);CHKERRQ(ierr);
   return 0;
 }
 
@@ -1624,15 +1521,8 @@ PetscErrorCode KSPCreate_BICGHIPMI355X(KSP ksp) {
  * vectors without the table (-ksp_type lsqr is that route).  On several ranks the Vec type refuses the slot routes (the slot would hold a
  * local partial sum): both sweeps take the WAIT route, the sums are all-reduced, step 6 takes beta from the host -- two waits.
  * KSPHIPMI355XGetFusedStepCounts: (bidiagonalisation sweeps run, update sweeps run; the scaling forms are not counted). */
-typedef struct { Vec se; PetscBool se_flg; PetscReal arnorm, anorm, rhs_norm; Vec U, U1, V, V1, W, Z, Z1; PetscInt nbidiag, nupdate; } KSP_LsqrHIP;
+typedef struct { KSPHipCommon common; Vec se; PetscBool se_flg; PetscReal arnorm, anorm, rhs_norm; Vec U, U1, V, V1, W, Z, Z1; } KSP_LsqrHIP;   /* dinv, fused: unused */
 
-static const VecLsqrFusedOps *vec_lsqr_ops(Vec x) {
-  PetscVoidFunction f = NULL;
-  const VecLsqrFusedOps *L;
-  if (PetscObjectQueryFunction((PetscObject)x, "VecLsqrFusedOps_C", &f) || !f) return NULL;
-  L = ((VecLsqrFusedOpsGetFn)f)();
-  return (L && L->lsqr_bidiag && L->lsqr_update) ? L : NULL;
-}
 static PetscErrorCode lsqr_no_pc(KSP ksp, PetscBool *nopc) {
   PCType t = NULL;
   PetscErrorCode ierr = PCGetType(ksp->pc, &t);CHKERRQ(ierr);
@@ -1669,22 +1559,15 @@ static PetscErrorCode lsqr_check(KSP ksp) {
 }
 static PetscErrorCode lsqr_needs_table(KSP ksp) {
   const KSP_LsqrHIP *ld = (const KSP_LsqrHIP *)ksp->data;
-  if (!vec_lsqr_ops(ld->V) || !vec_lsqr_ops(ld->U) || (ksp->vec_sol && !vec_lsqr_ops(ksp->vec_sol)) || (ksp->vec_rhs && !vec_lsqr_ops(ksp->vec_rhs)))
-    SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "KSP type %s needs vectors whose type offers the fused LSQR sweeps (\"VecLsqrFusedOps_C\"); use -ksp_type lsqr on these vectors", KSPLSQRHIPMI355X);
-  return 0;
+  const PetscBool offered = (PetscBool)(vec_lsqr_ops(ld->V) && vec_lsqr_ops(ld->U) && (!ksp->vec_sol || vec_lsqr_ops(ksp->vec_sol)) && (!ksp->vec_rhs || vec_lsqr_ops(ksp->vec_rhs)));
+  return needs_table(ksp, offered, KSPLSQRHIPMI355X, "LSQR sweeps", "VecLsqrFusedOps_C", "lsqr");
 }
 static PetscErrorCode KSPSetUp_LsqrHIP(KSP ksp) {
   PetscErrorCode ierr = lsqr_check(ksp);CHKERRQ(ierr);
   ierr = lsqr_get_work(ksp);CHKERRQ(ierr);
   return lsqr_needs_table(ksp);
 }
-static PetscErrorCode KSPSetFromOptions_LsqrHIP(KSP ksp) {
-  KSP_LsqrHIP *ld = (KSP_LsqrHIP *)ksp->data;
-  PetscInt iv = ld->se_flg;
-  PetscErrorCode ierr = option_level(ksp, "-ksp_lsqr_set_standard_error", 0, 1, &iv);CHKERRQ(ierr);
-  ld->se_flg = (PetscBool)iv;
-  return 0;
-}
+static PetscErrorCode KSPSetFromOptions_LsqrHIP(KSP ksp) { return option_bool(ksp, "-ksp_lsqr_set_standard_error", &((KSP_LsqrHIP *)ksp->data)->se_flg); }
 static PetscErrorCode KSPLSQRSetStandardErrorVec_LsqrHIP(KSP ksp, Vec se) {
   KSP_LsqrHIP *ld = (KSP_LsqrHIP *)ksp->data;
   if (se == ld->se) return 0;
@@ -1698,22 +1581,21 @@ static PetscErrorCode KSPLSQRGetArnorm_LsqrHIP(KSP ksp, PetscReal *arnorm, Petsc
   *arnorm = ld->arnorm; *rhs_norm = ld->rhs_norm; *anorm = ld->anorm;
   return 0;
 }
-static PetscErrorCode KSPGetFusedStepCounts_LsqrHIP(KSP ksp, PetscInt *fused, PetscInt *opbyop) {
-  const KSP_LsqrHIP *ld = (const KSP_LsqrHIP *)ksp->data;
-  *fused = ld->nbidiag; *opbyop = ld->nupdate;
-  return 0;
-}
 static PetscErrorCode KSPDefaultPCNone_LsqrHIP(KSP ksp) { (void)ksp; return 0; }   /* its presence is the message: see the harness's KSPSetUp */
-static const char *const lsqr_methods[] = {"KSPLSQRSetStandardErrorVec_C", "KSPLSQRGetStandardErrorVec_C", "KSPLSQRGetArnorm_C", "KSPHIPMI355XGetFusedStepCounts_C", "KSPDefaultPCNone_C"};
+static const KSPHipMethod lsqr_methods[] = {
+  {"KSPLSQRSetStandardErrorVec_C", "KSPLSQRSetStandardErrorVec_LsqrHIP", (PetscVoidFunction)KSPLSQRSetStandardErrorVec_LsqrHIP},
+  {"KSPLSQRGetStandardErrorVec_C", "KSPLSQRGetStandardErrorVec_LsqrHIP", (PetscVoidFunction)KSPLSQRGetStandardErrorVec_LsqrHIP},
+  {"KSPLSQRGetArnorm_C", "KSPLSQRGetArnorm_LsqrHIP", (PetscVoidFunction)KSPLSQRGetArnorm_LsqrHIP},
+  COUNTS_METHOD,                                                                    /* count: (bidiagonalisation sweeps run, update sweeps run) */
+  {"KSPDefaultPCNone_C", "KSPDefaultPCNone_LsqrHIP", (PetscVoidFunction)KSPDefaultPCNone_LsqrHIP},
+  {NULL, NULL, NULL}};
 static PetscErrorCode KSPDestroy_LsqrHIP(KSP ksp) {
   KSP_LsqrHIP *ld = (KSP_LsqrHIP *)ksp->data;
   PetscErrorCode ierr;
   if (!ld) return 0;
   Vec *all[] = {&ld->U, &ld->U1, &ld->V, &ld->V1, &ld->W, &ld->Z, &ld->Z1, &ld->se};
   for (int k = 0; k < 8; k++) { ierr = VecDestroy(all[k]);CHKERRQ(ierr); }
-  HipFree(ld); ksp->data = NULL;
-  for (int k = 0; k < 5; k++) { ierr = PetscObjectComposeFunction((PetscObject)ksp, lsqr_methods[k], "", (PetscVoidFunction)NULL);CHKERRQ(ierr); }
-  return 0;
+  return ksp_destroy_data(ksp, lsqr_methods);
 }
 #define LSQR_REFUSED(ksp) SETERRQ(HipObjComm(ksp), PETSC_ERR_SUP, "the fused LSQR sweep refused these vectors; use -ksp_type lsqr")
 /* v = a v through the update sweep's scaling form (a == 1: nothing) */
@@ -1774,7 +1656,7 @@ static PetscErrorCode KSPSolve_LsqrHIP(KSP ksp) {
       ierr = bicg_mult_transpose(ksp, A, U1, V1);CHKERRQ(ierr);
       ierr = L->lsqr_bidiag(V, V1, 0.0, LSQR_BIDIAG_FINISH, sums, &done);CHKERRQ(ierr);
       if (!done) LSQR_REFUSED(ksp);
-      ld->nbidiag += 2;
+      ld->common.count[0] += 2;
       beta = PetscSqrtReal(sums[0]); alpha = PetscSqrtReal(sums[1]);
     } else if (nopc) {                                               /* several ranks: both sums all-reduced, beta and alpha come home one by one */
       ierr = L->lsqr_bidiag(U, U1, alpha, LSQR_BIDIAG_WAIT, sums, &done);CHKERRQ(ierr);
@@ -1784,12 +1666,12 @@ static PetscErrorCode KSPSolve_LsqrHIP(KSP ksp) {
       ierr = bicg_mult_transpose(ksp, A, U1, V1);CHKERRQ(ierr);
       ierr = L->lsqr_bidiag(V, V1, beta, LSQR_BIDIAG_WAIT, sums, &done);CHKERRQ(ierr);
       if (!done) LSQR_REFUSED(ksp);
-      ld->nbidiag += 2;
+      ld->common.count[0] += 2;
       alpha = PetscSqrtReal(sums[0]);
     } else {
       ierr = L->lsqr_bidiag(U, U1, alpha, LSQR_BIDIAG_WAIT, sums, &done);CHKERRQ(ierr);
       if (!done) LSQR_REFUSED(ksp);
-      ld->nbidiag++;
+      ld->common.count[0]++;
       beta = PetscSqrtReal(sums[0]);
       ierr = lsqr_scale(ksp, L, U1, beta != 0.0 ? 1.0 / beta : 1.0);CHKERRQ(ierr);
       ierr = bicg_mult_transpose(ksp, A, U1, V1);CHKERRQ(ierr);
@@ -1806,7 +1688,7 @@ static PetscErrorCode KSPSolve_LsqrHIP(KSP ksp) {
     phi = c * phibar; phibar = s * phibar;
     ierr = L->lsqr_update(nopc ? V1 : Z1, X, W, SE, alpha != 0.0 ? 1.0 / alpha : 1.0, phi / rho, -theta / rho, 1.0 / (rho * rho), broke, &done);CHKERRQ(ierr);
     if (!done) LSQR_REFUSED(ksp);
-    ld->nupdate++;
+    ld->common.count[1]++;
     ld->arnorm = alpha * PetscAbsScalar(s * phi);
     anorm2 += alpha * alpha + beta * beta;
     ld->anorm = PetscSqrtReal(anorm2);
@@ -1821,21 +1703,13 @@ static PetscErrorCode KSPSolve_LsqrHIP(KSP ksp) {
   return 0;
 }
 PetscErrorCode KSPCreate_LSQRHIPMI355X(KSP ksp) {
-  KSP_LsqrHIP *ld;
-  PetscErrorCode ierr = PetscMalloc(sizeof(*ld), &ld);CHKERRQ(ierr);
-  memset(ld, 0, sizeof(*ld));
-  ksp->data = ld;
+  PetscErrorCode ierr = ksp_create_data(ksp, sizeof(KSP_LsqrHIP), lsqr_methods);CHKERRQ(ierr);
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);    /* the one of KSPLSQR */
   ksp->ops->setup = KSPSetUp_LsqrHIP; ksp->ops->solve = KSPSolve_LsqrHIP; ksp->ops->setfromoptions = KSPSetFromOptions_LsqrHIP; ksp->ops->destroy = KSPDestroy_LsqrHIP;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, lsqr_methods[0], "KSPLSQRSetStandardErrorVec_LsqrHIP", (PetscVoidFunction)KSPLSQRSetStandardErrorVec_LsqrHIP);CHKERRQ(ierr);
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, lsqr_methods[1], "KSPLSQRGetStandardErrorVec_LsqrHIP", (PetscVoidFunction)KSPLSQRGetStandardErrorVec_LsqrHIP);CHKERRQ(ierr);
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, lsqr_methods[2], "KSPLSQRGetArnorm_LsqrHIP", (PetscVoidFunction)KSPLSQRGetArnorm_LsqrHIP);CHKERRQ(ierr);
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, lsqr_methods[3], "KSPGetFusedStepCounts_LsqrHIP", (PetscVoidFunction)KSPGetFusedStepCounts_LsqrHIP);CHKERRQ(ierr);
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, lsqr_methods[4], "KSPDefaultPCNone_LsqrHIP", (PetscVoidFunction)KSPDefaultPCNone_LsqrHIP);CHKERRQ(ierr);
   return 0;
 }
 
-typedef struct { PetscReal scale; Vec dinv; } KSP_RichHIP;
+typedef struct { KSPHipCommon common; PetscReal scale; } KSP_RichHIP;
 
 static PetscErrorCode KSPRichardsonSetScale_RichHIP(KSP ksp, PetscReal scale) { ((KSP_RichHIP *)ksp->data)->scale = scale; return 0; }
 static PetscErrorCode KSPSetUp_RichHIP(KSP ksp) { return KSPDefaultGetWork(ksp, 2); }
@@ -1845,15 +1719,10 @@ static PetscErrorCode KSPSetFromOptions_RichHIP(KSP ksp) {
   if (count) ((KSP_RichHIP *)ksp->data)->scale = v[0];
   return 0;
 }
-static PetscErrorCode KSPDestroy_RichHIP(KSP ksp) {
-  KSP_RichHIP *ri = (KSP_RichHIP *)ksp->data;
-  PetscErrorCode ierr;
-  if (!ri) return 0;
-  ierr = VecDestroy(&ri->dinv);CHKERRQ(ierr);
-  HipFree(ri); ksp->data = NULL;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPRichardsonSetScale_C", "", (PetscVoidFunction)NULL);CHKERRQ(ierr);
-  return 0;
-}
+static const KSPHipMethod rich_methods[] = {
+  {"KSPRichardsonSetScale_C", "KSPRichardsonSetScale_RichHIP", (PetscVoidFunction)KSPRichardsonSetScale_RichHIP},
+  {NULL, NULL, NULL}};
+static PetscErrorCode KSPDestroy_RichHIP(KSP ksp) { return ksp_destroy_data(ksp, rich_methods); }
 
 static PetscErrorCode KSPSolve_RichHIP(KSP ksp) {
   PetscErrorCode ierr;
@@ -1861,15 +1730,15 @@ static PetscErrorCode KSPSolve_RichHIP(KSP ksp) {
   const KSPNormType nt = ksp->normtype;
   Vec x = ksp->vec_sol, rhs = ksp->vec_rhs, r = ksp->work[0], z = ksp->work[1];
   const VecKrylovFusedOps *F = vec_fused_ops(x);
-  HipPCKind pck = PCKIND_GENERAL;
-  Vec d = NULL;
+  HipPCKind pck;
+  Vec d;
   Mat A;
   PetscReal rn = 0.0;
   PetscBool product_only = PETSC_FALSE;   /* r holds A x, not yet rhs - A x: the sweep of the coming iteration forms the residual itself */
   PetscInt i;
 
   ierr = PCGetOperators(ksp->pc, &A, NULL, NULL);CHKERRQ(ierr);
-  if (nt == KSP_NORM_NONE && F && F->rich_step && !has_null_space(ksp)) { ierr = pc_diagonal_form(ksp, x, &ri->dinv, &pck);CHKERRQ(ierr); if (pck == PCKIND_DIAGONAL) d = ri->dinv; }
+  ierr = pc_diagonal_form(ksp, (PetscBool)(nt == KSP_NORM_NONE && F && F->rich_step), x, &pck, &d);CHKERRQ(ierr);
   ierr = start_residual(ksp, A, x, rhs, r);CHKERRQ(ierr);
   ksp->its = 0;
   for (i = 0; i < ksp->max_it; i++) {
@@ -1914,13 +1783,10 @@ static PetscErrorCode KSPSolve_RichHIP(KSP ksp) {
 }
 
 PetscErrorCode KSPCreate_RichardsonHIPMI355X(KSP ksp) {
-  KSP_RichHIP *ri;
-  PetscErrorCode ierr = PetscMalloc(sizeof(*ri), &ri);CHKERRQ(ierr);
-  ri->scale = 1.0; ri->dinv = NULL;                                                      /* KSPCreate_Richardson's default */
-  ksp->data = ri;
+  PetscErrorCode ierr = ksp_create_data(ksp, sizeof(KSP_RichHIP), rich_methods);CHKERRQ(ierr);
+  ((KSP_RichHIP *)ksp->data)->scale = 1.0;                                               /* KSPCreate_Richardson's default */
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_PRECONDITIONED, PC_LEFT, 2);CHKERRQ(ierr);
   ierr = KSPSetSupportedNorm(ksp, KSP_NORM_UNPRECONDITIONED, PC_LEFT, 1);CHKERRQ(ierr);
   ksp->ops->setup = KSPSetUp_RichHIP; ksp->ops->solve = KSPSolve_RichHIP; ksp->ops->setfromoptions = KSPSetFromOptions_RichHIP; ksp->ops->destroy = KSPDestroy_RichHIP;
-  ierr = PetscObjectComposeFunction((PetscObject)ksp, "KSPRichardsonSetScale_C", "KSPRichardsonSetScale_RichHIP", (PetscVoidFunction)KSPRichardsonSetScale_RichHIP);CHKERRQ(ierr);
   return 0;
 }
