@@ -111,6 +111,61 @@ PetscErrorCode VecHIPRestoreWrite(Vec v) { VH(v)->valid = VALID_DEVICE; return 0
 static int is_hip(Vec v) { return v && v->data && strstr(HipObjTypeName(v), "hipmi355x") != NULL; }
 #define CheckHIP(v) do { if (!is_hip(v)) SETERRQ(HipObjComm(v), PETSC_ERR_ARG_NOTSAMETYPE, "vector of type %s mixed with a HIPMI355X vector", HipObjTypeName(v)); } while (0)
 
+/* ---- the operands of a fused sweep.  Every fused form below states its vectors ONCE, as a table in the order they are acquired, and
+ * goes through three steps with it:
+ *   operands_ok    the gate: every vector the form touches (NULL: not touched) is a HIPMI355X vector, all have the same local size, and no
+ *                  WRITTEN vector (OP_WRITE, OP_RW) is the same object as another operand -- but for the pairs of table positions the form
+ *                  lists as permitted.  A form that fails it answers *done = PETSC_FALSE with nothing touched.  What a form requires to be
+ *                  present, its enum ranges and its transport conditions stand beside the gate in the form itself.
+ *   operands_get   the accessors in table order (they run what is noted and a late product, so the order is part of the launch sequence);
+ *                  a write-only operand that is also another operand -- a permitted pair, after the gate -- keeps its values (read-write).
+ *   operands_put   every written operand is marked: the device copy is the valid one and the object state moves on (the dot kept by a
+ *                  fused sweep and the norms a caller keeps hang on it).  `skip`: bit i set leaves table position i unmarked -- the special
+ *                  cases in which the kernel does not store that vector. ---- */
+typedef enum { OP_READ, OP_WRITE, OP_RW } OperandMode;
+typedef struct { Vec v; OperandMode mode; PetscScalar *d; } Operand;
+typedef int OperandPair[2];
+#define RD(v) {(v), OP_READ, NULL}
+#define WR(v) {(v), OP_WRITE, NULL}
+#define RW(v) {(v), OP_RW, NULL}
+#define NOPS(o) ((int)(sizeof(o) / sizeof((o)[0])))
+static int operands_ok(const Operand *o, int n, const OperandPair *may, int nmay) {
+  Vec first = NULL;
+  for (int i = 0; i < n; i++) {
+    if (!o[i].v) continue;
+    if (!first) first = o[i].v;
+    if (!is_hip(o[i].v) || o[i].v->map->n != first->map->n) return 0;
+  }
+  for (int i = 0; i < n; i++) {
+    if (!o[i].v || o[i].mode == OP_READ) continue;
+    for (int j = 0; j < n; j++) {
+      int allowed = (j == i || o[j].v != o[i].v);
+      for (int k = 0; k < nmay && !allowed; k++) allowed = (may[k][0] == i && may[k][1] == j) || (may[k][0] == j && may[k][1] == i);
+      if (!allowed) return 0;
+    }
+  }
+  return 1;
+}
+static PetscErrorCode operands_get(Operand *o, int n) {
+  PetscErrorCode ierr;
+  for (int i = 0; i < n; i++) {
+    int alias = 0;
+    if (!o[i].v) continue;
+    if (o[i].mode == OP_WRITE) for (int j = 0; j < n; j++) if (j != i && o[j].v == o[i].v) alias = 1;
+    if (o[i].mode == OP_READ) { ierr = VecHIPGetRead(o[i].v, (const PetscScalar **)&o[i].d);CHKERRQ(ierr); }
+    else if (o[i].mode == OP_RW || alias) { ierr = VecHIPGetReadWrite(o[i].v, &o[i].d);CHKERRQ(ierr); }
+    else { ierr = VecHIPGetWrite(o[i].v, &o[i].d);CHKERRQ(ierr); }
+  }
+  return 0;
+}
+static void operands_put(const Operand *o, int n, unsigned skip) {
+  for (int i = 0; i < n; i++) {
+    if (!o[i].v || o[i].mode == OP_READ || (i < 32 && (skip & (1u << i)))) continue;
+    VecHIPRestoreWrite(o[i].v);
+    HipStateIncrease(o[i].v);
+  }
+}
+
 PetscErrorCode VecHIPMI355XGetArray(Vec v, PetscScalar **d) { CheckHIP(v); return VecHIPGetReadWrite(v, d); }
 PetscErrorCode VecHIPMI355XRestoreArray(Vec v, PetscScalar **d) { if (d) *d = NULL; VecHIPRestoreWrite(v); HipStateIncrease(v); return 0; }
 PetscErrorCode VecHIPMI355XGetArrayRead(Vec v, const PetscScalar **d) { CheckHIP(v); return VecHIPGetRead(v, d); }
@@ -560,13 +615,17 @@ static PetscErrorCode VecMAXPY_HIP_now(Vec y, PetscInt nv, const PetscScalar *al
 static int hip_local_only = 0;   /* ops->dot_local / norm_local / mdot_local: this rank's part only (comb.c:402-721) */
 #define DEVICE_COLLECTIVES(x) (!hip_local_only && HipCommDevice(HipObjComm(x)) != NULL)
 #define HOST_STAGED(x) (!hip_local_only && HipCommSize(HipObjComm(x)) > 1 && !HipCommDevice(HipObjComm(x)))
-static PetscErrorCode reduce_target(Vec x, PetscDeviceCtx *dc, double **out) {
-  *out = DEVICE_COLLECTIVES(x) ? mi355x_handle_device_scratch(dc->h) : mi355x_handle_host_scratch(dc->h);
-  return 0;
+static double *reduce_target(Vec x, PetscDeviceCtx *dc) { return DEVICE_COLLECTIVES(x) ? mi355x_handle_device_scratch(dc->h) : mi355x_handle_host_scratch(dc->h); }
+/* the host waits for the result a kernel on this handle's stream publishes (it polls the completion number: no stream synchronisation),
+ * then asks whether a sync-free triangular solve queued before it gave up (host/ilu.c) */
+static PetscErrorCode result_wait(mi355x_handle_t h) {
+  CHKHIP(mi355x_handle_wait_result(h));
+  return HipTriWatchCheck();
 }
 /* count values were reduced on this rank into the target; the first nsum of them are summed (or max-ed) over the
  * ranks, the rest are carried along as they are */
-static PetscErrorCode reduce_finish2(Vec x, PetscDeviceCtx *dc, int nsum, int count, int is_max, PetscScalar *result) {
+static PetscErrorCode reduce_finish(Vec x, PetscDeviceCtx *dc, int nsum, int count, int is_max, PetscScalar *result) {
+  PetscErrorCode ierr;
   double *hs = mi355x_handle_host_scratch(dc->h);
   if (HOST_STAGED(x)) {
     /* host-staged transport (no RCCL communicator attached): the reference's own arrangement, a device
@@ -584,17 +643,12 @@ static PetscErrorCode reduce_finish2(Vec x, PetscDeviceCtx *dc, int nsum, int co
     /* device -> pinned host by a tiny kernel on the same stream that also stores the completion number the host
      * polls: no stream synchronisation, and kernels queued behind it do not delay the result */
     CHKHIP(mi355x_handle_publish(dc->h, ds, count));
-    CHKHIP(mi355x_handle_wait_result(dc->h)); { PetscErrorCode e_ = HipTriWatchCheck();CHKERRQ(e_); }
-  } else {
-    /* one rank: the reduction kernel wrote the result and then a completion number to pinned memory; polling that
-     * word is cheaper than a stream synchronisation and lets the next launches go out at once */
-    CHKHIP(mi355x_handle_wait_result(dc->h)); { PetscErrorCode e_ = HipTriWatchCheck();CHKERRQ(e_); }
   }
+  /* (one rank: the reduction kernel wrote the result and then a completion number to pinned memory; polling that
+   * word is cheaper than a stream synchronisation and lets the next launches go out at once) */
+  ierr = result_wait(dc->h);CHKERRQ(ierr);
   for (int j = 0; j < count; j++) result[j] = hs[j];
   return 0;
-}
-static PetscErrorCode reduce_finish(Vec x, PetscDeviceCtx *dc, int count, int is_max, PetscScalar *result) {
-  return reduce_finish2(x, dc, count, count, is_max, result);
 }
 
 static PetscErrorCode VecDot_HIP(Vec x, Vec y, PetscScalar *val) {
@@ -624,9 +678,9 @@ static PetscErrorCode VecDot_HIP(Vec x, Vec y, PetscScalar *val) {
   }
   ierr = VecHIPGetRead(x, &dx);CHKERRQ(ierr);
   ierr = VecHIPGetRead(y, &dy);CHKERRQ(ierr);
-  ierr = reduce_target(x, dc, &out);CHKERRQ(ierr);
+  out = reduce_target(x, dc);
   CHKHIP(mi355x_vec_dot(dc->h, N_(x), dx, dy, out));
-  ierr = reduce_finish(x, dc, 1, 0, val);CHKERRQ(ierr);
+  ierr = reduce_finish(x, dc, 1, 1, 0, val);CHKERRQ(ierr);
   if (x->map->n > 0) { ierr = PetscLogFlops(2.0 * x->map->n - 1);CHKERRQ(ierr); }
   return 0;
 }
@@ -637,9 +691,9 @@ static PetscErrorCode VecMDot_HIP(Vec x, PetscInt nv, const Vec y[], PetscScalar
   for (PetscInt pos = 0; pos < nv; pos += 32) {   /* pvec2.c:12-17 uses a 128-entry stack buffer; ours is the 64-double scratch */
     PetscInt cnt = PetscMin(32, nv - pos);
     for (PetscInt j = 0; j < cnt; j++) { CheckHIP(y[pos + j]); ierr = VecHIPGetRead(y[pos + j], &tab[j]);CHKERRQ(ierr); }
-    ierr = reduce_target(x, dc, &out);CHKERRQ(ierr);
+    out = reduce_target(x, dc);
     CHKHIP(mi355x_vec_mdot(dc->h, N_(x), cnt, dx, tab, out));
-    ierr = reduce_finish(x, dc, cnt, 0, val + pos);CHKERRQ(ierr);
+    ierr = reduce_finish(x, dc, cnt, cnt, 0, val + pos);CHKERRQ(ierr);
   }
   ierr = PetscLogFlops(PetscMax(nv * (2.0 * x->map->n - 1), 0.0));CHKERRQ(ierr);
   return 0;
@@ -649,25 +703,24 @@ static PetscErrorCode VecMDot_HIP(Vec x, PetscInt nv, const Vec y[], PetscScalar
 static PetscErrorCode deferred_maxpy_norm(PetscScalar *sumsq, PetscBool *done) {
   PetscErrorCode ierr; DEVCTX;
   static double *stage = NULL, *dcoef = NULL;
-  const double *tab[32]; PetscScalar *dy; double *out;
+  const double *tab[32]; Operand o[33];
   Vec y = dq.op[0].o; const PetscInt nv = dq.mnv;
   *done = PETSC_FALSE;
   if (!stage) {
     if (mi355x_host_malloc((void **)&stage, sizeof(double) * 32) || mi355x_malloc((void **)&dcoef, sizeof(double) * 32)) { stage = NULL; return deferred_flush(); }
   }
+  for (PetscInt j = 0; j < nv; j++) { stage[j] = dq.malpha[j]; o[j] = (Operand)RD(dq.mx[j]); }   /* (VecMAXPY_HIP looked at them when it noted the call) */
+  o[nv] = (Operand)RW(y);
   dq.busy = 1;
-  ierr = 0;
-  for (PetscInt j = 0; j < nv && !ierr; j++) { stage[j] = dq.malpha[j]; ierr = VecHIPGetRead(dq.mx[j], &tab[j]); }
-  if (!ierr) ierr = VecHIPGetReadWrite(y, &dy);
+  ierr = operands_get(o, (int)nv + 1);
   dq.busy = 0;
   CHKERRQ(ierr);
   dq.n = 0;
+  for (PetscInt j = 0; j < nv; j++) tab[j] = o[j].d;
   CHKHIP(mi355x_memcpy_h2d(dc->h, dcoef, stage, sizeof(double) * (size_t)nv));
-  ierr = reduce_target(y, dc, &out);CHKERRQ(ierr);
-  CHKHIP(mi355x_vec_maxpy_dev_norm2(dc->h, N_(y), (int)nv, dcoef, 1.0, tab, dy, out));
-  VecHIPRestoreWrite(y);
-  HipStateIncrease(y);
-  ierr = reduce_finish(y, dc, 1, 0, sumsq);CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_maxpy_dev_norm2(dc->h, N_(y), (int)nv, dcoef, 1.0, tab, o[nv].d, reduce_target(y, dc)));
+  operands_put(o, (int)nv + 1, 0);
+  ierr = reduce_finish(y, dc, 1, 1, 0, sumsq);CHKERRQ(ierr);
   ierr = PetscLogFlops(nv * 2.0 * y->map->n + PetscMax(2.0 * y->map->n - 1, 0.0));CHKERRQ(ierr);
   dcount[DC_MAXPY_NORM]++;
   *done = PETSC_TRUE;
@@ -694,16 +747,16 @@ static PetscErrorCode VecNorm_HIP(Vec x, NormType type, PetscReal *val) {
     }
   }
   ierr = VecHIPGetRead(x, &dx);CHKERRQ(ierr);
-  ierr = reduce_target(x, dc, &out);CHKERRQ(ierr);
+  out = reduce_target(x, dc);
   CHKHIP(mi355x_vec_norm(dc->h, N_(x), (int)type, dx, out));
   if (type == NORM_1_AND_2) {
-    ierr = reduce_finish(x, dc, 2, 0, r);CHKERRQ(ierr);
+    ierr = reduce_finish(x, dc, 2, 2, 0, r);CHKERRQ(ierr);
     val[0] = r[0]; val[1] = PetscSqrtReal(r[1]);           /* pvec2.c:80-82 */
   } else if (type == NORM_INFINITY) {
-    ierr = reduce_finish(x, dc, 1, 1, r);CHKERRQ(ierr);    /* MPIU_MAX, pvec2.c:74 */
+    ierr = reduce_finish(x, dc, 1, 1, 1, r);CHKERRQ(ierr);    /* MPIU_MAX, pvec2.c:74 */
     *val = r[0];
   } else {
-    ierr = reduce_finish(x, dc, 1, 0, r);CHKERRQ(ierr);
+    ierr = reduce_finish(x, dc, 1, 1, 0, r);CHKERRQ(ierr);
     *val = (type == NORM_1) ? r[0] : PetscSqrtReal(r[0]);  /* pvec2.c:62-64: reduce the square, then sqrt */
   }
   if (type != NORM_INFINITY) { ierr = PetscLogFlops(PetscMax(2.0 * x->map->n - 1, 0.0));CHKERRQ(ierr); }
@@ -722,9 +775,9 @@ static PetscErrorCode VecDotNorm2_HIP(Vec s, Vec t, PetscScalar *dp, PetscScalar
   }
   ierr = VecHIPGetRead(s, &ds_);CHKERRQ(ierr);
   ierr = VecHIPGetRead(t, &dt);CHKERRQ(ierr);
-  ierr = reduce_target(s, dc, &out);CHKERRQ(ierr);
+  out = reduce_target(s, dc);
   CHKHIP(mi355x_vec_dotnorm2(dc->h, N_(s), ds_, dt, out));
-  ierr = reduce_finish(s, dc, 2, 0, r);CHKERRQ(ierr);
+  ierr = reduce_finish(s, dc, 2, 2, 0, r);CHKERRQ(ierr);
   *dp = r[0]; *nm = r[1];
   ierr = PetscLogFlops(4.0 * s->map->n);CHKERRQ(ierr);
   return 0;
@@ -736,9 +789,9 @@ static PetscErrorCode VecDotNorm2_HIP(Vec s, Vec t, PetscScalar *dp, PetscScalar
 static PetscErrorCode VecSum_HIP(Vec x, PetscScalar *sum) {   /* "VecSum_C" (vinv.c VecSum: the local sum, then MPI_SUM) */
   PetscErrorCode ierr; const PetscScalar *dx; double *out; DEVCTX;
   ierr = VecHIPGetRead(x, &dx);CHKERRQ(ierr);
-  ierr = reduce_target(x, dc, &out);CHKERRQ(ierr);
+  out = reduce_target(x, dc);
   CHKHIP(mi355x_vec_sum(dc->h, N_(x), dx, out));
-  ierr = reduce_finish(x, dc, 1, 0, sum);CHKERRQ(ierr);
+  ierr = reduce_finish(x, dc, 1, 1, 0, sum);CHKERRQ(ierr);
   ierr = PetscLogFlops(PetscMax(x->map->n - 1.0, 0.0));CHKERRQ(ierr);
   return 0;
 }
@@ -780,7 +833,7 @@ static PetscErrorCode extremum_HIP(Vec x, int is_max, PetscInt *p, PetscReal *va
     CHKHIP(mi355x_comm_allreduce_max(HipCommDevice(comm), dc->h, out, 1));
     CHKHIP(mi355x_handle_publish(dc->h, out, 1));
   }
-  CHKHIP(mi355x_handle_wait_result(dc->h)); { PetscErrorCode e_ = HipTriWatchCheck();CHKERRQ(e_); }
+  ierr = result_wait(dc->h);CHKERRQ(ierr);
   const double *hs = mi355x_handle_host_scratch(dc->h);
   double v = hs[0], loc = on_device ? -1.0 : hs[1];
   if (on_device) v = is_max ? v : -v;
@@ -852,31 +905,33 @@ PetscErrorCode VecHIPMI355XGetCGUpdateTiming(PetscInt *nlaunches, PetscLogDouble
 #define CGU_TIME_BEGIN(h) do { if (cgu_time.on && cgu_time.n < cgu_time.cap) CHKHIP(mi355x_event_record(cgu_time.ev[2 * cgu_time.n], h)); } while (0)
 #define CGU_TIME_END(h)   do { if (cgu_time.on && cgu_time.n < cgu_time.cap) { CHKHIP(mi355x_event_record(cgu_time.ev[2 * cgu_time.n + 1], h)); cgu_time.n++; } } while (0)
 
+/* The six vectors of a CG iteration, in the order the sweeps acquire them.  z may be w (cg.c:122 keeps A*p in Z); x == NULL, p == NULL:
+ * the x-less sweep of VecCGUpdateDevBeginNoX_HIPMI355X; d == NULL: the identity preconditioner (PCNONE), z = r. */
+enum { CG_P, CG_W, CG_D, CG_X, CG_R, CG_Z };
+#define CG_OPERANDS(x, r, z, p, w, d) {RD(p), RD(w), RD(d), RW(x), RW(r), WR(z)}
+static const OperandPair cg_may[] = {{CG_Z, CG_W}};
+/* can the six vectors of a CG iteration take the fused update at all?  The gate, with z / w the one permitted pair. */
+PetscErrorCode VecCGUpdateCheck_HIPMI355X(Vec x, Vec r, Vec z, Vec p, Vec w, Vec d, PetscBool *ok) {
+  const Operand o[] = CG_OPERANDS(x, r, z, p, w, d);
+  *ok = (PetscBool)(x && r && z && p && w && operands_ok(o, NOPS(o), cg_may, NOPS(cg_may)));
+  return 0;
+}
 /* Fused CG update for HIPMI355X vectors (KSPSolve_CG cg.c:206-232 with a Jacobi PCApply in the middle):
  * x += a p; r -= a w; z = r .* d; *zz = z'z, *zr = z'r in one sweep and one reduction (one all-reduce of two
  * doubles on several ranks instead of two of one).  Results carry the bits of the separate VecAXPY, VecAXPY,
- * VecPointwiseMult, VecNorm, VecTDot calls.  Returns *done = PETSC_FALSE (and does nothing) when an operand is
- * not a HIPMI355X vector, so the caller keeps the unfused sequence. */
+ * VecPointwiseMult, VecNorm, VecTDot calls.  Returns *done = PETSC_FALSE (and does nothing) when the vectors fail
+ * VecCGUpdateCheck_HIPMI355X or a == 0, so the caller keeps the unfused sequence. */
 PetscErrorCode VecCGUpdate_HIPMI355X(Vec x, Vec r, Vec z, Vec p, Vec w, Vec d, PetscScalar a, PetscScalar *zz, PetscScalar *zr, PetscScalar *rr, PetscBool *done) {
-  PetscErrorCode ierr; const PetscScalar *dp_, *dw, *dd; PetscScalar *dx, *dr, *dz; double *out; PetscScalar res[3]; DEVCTX;
+  PetscErrorCode ierr; PetscScalar res[3]; DEVCTX;
+  Operand o[] = CG_OPERANDS(x, r, z, p, w, d);
   *done = PETSC_FALSE;
-  ierr = VecCGUpdateCheck_HIPMI355X(x, r, z, p, w, d, done);CHKERRQ(ierr);
-  if (!*done || a == 0.0) { *done = PETSC_FALSE; return 0; }
-  *done = PETSC_FALSE;
-  ierr = VecHIPGetRead(p, &dp_);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(w, &dw);CHKERRQ(ierr);
-  dd = NULL;
-  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
-  ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr);
-  ierr = VecHIPGetReadWrite(r, &dr);CHKERRQ(ierr);
-  ierr = VecHIPGetWrite(z, &dz);CHKERRQ(ierr);
-  ierr = reduce_target(x, dc, &out);CHKERRQ(ierr);
+  if (!x || !r || !z || !p || !w || !operands_ok(o, NOPS(o), cg_may, NOPS(cg_may)) || a == 0.0) return 0;
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
   CGU_TIME_BEGIN(dc->h);
-  CHKHIP(mi355x_vec_cg_update(dc->h, N_(x), a, dp_, dw, dd, dx, dr, dz, out));
+  CHKHIP(mi355x_vec_cg_update(dc->h, N_(x), a, o[CG_P].d, o[CG_W].d, o[CG_D].d, o[CG_X].d, o[CG_R].d, o[CG_Z].d, reduce_target(x, dc)));
   CGU_TIME_END(dc->h);
-  VecHIPRestoreWrite(x); VecHIPRestoreWrite(r); VecHIPRestoreWrite(z);
-  HipStateIncrease(x); HipStateIncrease(r); HipStateIncrease(z);
-  ierr = reduce_finish(x, dc, 3, 0, res);CHKERRQ(ierr);
+  operands_put(o, NOPS(o), 0);
+  ierr = reduce_finish(x, dc, 3, 3, 0, res);CHKERRQ(ierr);
   *zz = res[0]; *zr = res[1]; *rr = res[2];
   ierr = PetscLogFlops(9.0 * x->map->n);CHKERRQ(ierr);   /* 2n + 2n + n + 2n + 2n */
   *done = PETSC_TRUE;
@@ -886,16 +941,17 @@ PetscErrorCode VecCGUpdate_HIPMI355X(Vec x, Vec r, Vec z, Vec p, Vec w, Vec d, P
 /* Split form for KSPSolve_CG with device-resident scalars.  VecTDotBegin leaves p'w in slot DPI_SLOT of the
  * device scratch (all-reduced in place over RCCL when the communicator has one) without any host synchronisation;
  * VecCGUpdateDev then forms a = beta/dpi on the device, does the fused update and returns z'z, z'r and dpi with the
- * one synchronisation of the iteration.  Not available with the host-staged transport (*ok = PETSC_FALSE). */
+ * one synchronisation of the iteration.  Not available with the host-staged transport (*ok = PETSC_FALSE).
+ * Two operands, both read: they may be one vector. */
 #define DPI_SLOT PETSC_HIP_DPI_SLOT
 PetscErrorCode VecTDotBegin_HIPMI355X(Vec x, Vec y, PetscBool *ok) {
-  PetscErrorCode ierr; const PetscScalar *dx, *dy; double *ds; DEVCTX;
+  PetscErrorCode ierr; double *ds; DEVCTX;
+  Operand o[] = {RD(x), RD(y)};
   *ok = PETSC_FALSE;
-  if (!is_hip(x) || !is_hip(y) || HOST_STAGED(x) || x->map->n != y->map->n) return 0;
-  ierr = VecHIPGetRead(x, &dx);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(y, &dy);CHKERRQ(ierr);
+  if (!x || !y || !operands_ok(o, NOPS(o), NULL, 0) || HOST_STAGED(x)) return 0;
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
   ds = mi355x_handle_device_scratch(dc->h) + DPI_SLOT;
-  CHKHIP(mi355x_vec_dot(dc->h, N_(x), dx, dy, ds));
+  CHKHIP(mi355x_vec_dot(dc->h, N_(x), o[0].d, o[1].d, ds));
   if (DEVICE_COLLECTIVES(x)) CHKHIP(mi355x_comm_allreduce_sum(HipCommDevice(HipObjComm(x)), dc->h, ds, 1));
   if (x->map->n > 0) { ierr = PetscLogFlops(2.0 * x->map->n - 1);CHKERRQ(ierr); }
   *ok = PETSC_TRUE;
@@ -903,27 +959,20 @@ PetscErrorCode VecTDotBegin_HIPMI355X(Vec x, Vec y, PetscBool *ok) {
 }
 /* Begin queues the sweep (results go to device scratch slots 0..2, all-reduced there when the communicator has an
  * RCCL communicator, then published to pinned memory); End waits for exactly that point of the stream, so the caller
- * may queue more work in between (KSPSolve_CG queues the next iteration's AYPX, MatMult and dot there). */
-/* x == NULL (and p unused): the x-less sweep of VecCGUpdateDevBeginNoX_HIPMI355X */
+ * may queue more work in between (KSPSolve_CG queues the next iteration's AYPX, MatMult and dot there).
+ * No gate of its own: the caller has asked VecCGUpdateCheck_HIPMI355X about these vectors.  z keeps its values when it is w, and is
+ * left as it is when the update is refused on the device. */
 static PetscErrorCode cg_update_dev_begin(Vec x, Vec r, Vec z, Vec p, Vec w, Vec d, PetscScalar beta, PetscScalar dpiold, PetscBool check_sign) {
-  PetscErrorCode ierr; const PetscScalar *dp_ = NULL, *dw, *dd; PetscScalar *dx = NULL, *dr, *dz; double *ds; DEVCTX;
-  if (x) { ierr = VecHIPGetRead(p, &dp_);CHKERRQ(ierr); }
-  ierr = VecHIPGetRead(w, &dw);CHKERRQ(ierr);
-  dd = NULL;
-  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
-  if (x) { ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr); }
-  ierr = VecHIPGetReadWrite(r, &dr);CHKERRQ(ierr);
-  if (z == w) { ierr = VecHIPGetReadWrite(z, &dz);CHKERRQ(ierr); }   /* left as it is when the update is refused */
-  else { ierr = VecHIPGetWrite(z, &dz);CHKERRQ(ierr); }
+  PetscErrorCode ierr; double *ds; DEVCTX;
+  Operand o[] = CG_OPERANDS(x, r, z, x ? p : NULL, w, d);
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
   ds = mi355x_handle_device_scratch(dc->h);
   /* one rank: the finishing workgroup hands the sums to the host itself; several: all-reduce first, then publish */
   CGU_TIME_BEGIN(dc->h);
-  CHKHIP(mi355x_vec_cg_update_dev(dc->h, N_(r), beta, ds + DPI_SLOT, dpiold, (int)check_sign, dp_, dw, dd, dx, dr, dz, ds,
+  CHKHIP(mi355x_vec_cg_update_dev(dc->h, N_(r), beta, ds + DPI_SLOT, dpiold, (int)check_sign, o[CG_P].d, o[CG_W].d, o[CG_D].d, o[CG_X].d, o[CG_R].d, o[CG_Z].d, ds,
                                   DEVICE_COLLECTIVES(r) ? 0 : 1));
   CGU_TIME_END(dc->h);
-  if (x) { VecHIPRestoreWrite(x); HipStateIncrease(x); }
-  VecHIPRestoreWrite(r); VecHIPRestoreWrite(z);
-  HipStateIncrease(r); HipStateIncrease(z);
+  operands_put(o, NOPS(o), 0);
   if (DEVICE_COLLECTIVES(r)) {
     CHKHIP(mi355x_comm_allreduce_sum(HipCommDevice(HipObjComm(r)), dc->h, ds, 3));
     CHKHIP(mi355x_handle_publish(dc->h, ds, 4));
@@ -941,104 +990,74 @@ PetscErrorCode VecCGUpdateDevBeginNoX_HIPMI355X(Vec r, Vec z, Vec w, Vec d, Pets
 PetscErrorCode VecCGUpdateDevEnd_HIPMI355X(Vec x, PetscScalar *zz, PetscScalar *zr, PetscScalar *rr, PetscScalar *dpi) {
   PetscErrorCode ierr; DEVCTX;
   (void)x;
-  CHKHIP(mi355x_handle_wait_result(dc->h)); { PetscErrorCode e_ = HipTriWatchCheck();CHKERRQ(e_); }
+  ierr = result_wait(dc->h);CHKERRQ(ierr);
   const double *hs = mi355x_handle_host_scratch(dc->h);
   *zz = hs[0]; *zr = hs[1]; *rr = hs[2]; *dpi = hs[3];
   return 0;
 }
 /* p = z + (zr/den) p with zr = the z'r the last VecCGUpdateDevBegin left in device scratch slot 1 (VecAYPX(P,b,Z) of
- * cg.c:187 with b = beta_new/beta_old formed on the device) */
+ * cg.c:187 with b = beta_new/beta_old formed on the device).  The vectors of the iteration VecCGUpdateCheck_HIPMI355X passed: no gate. */
 PetscErrorCode VecAYPXDev_HIPMI355X(Vec p, PetscScalar den, Vec z) {
-  PetscErrorCode ierr; const PetscScalar *dz; PetscScalar *dp_; DEVCTX;
-  ierr = VecHIPGetRead(z, &dz);CHKERRQ(ierr);
-  ierr = VecHIPGetReadWrite(p, &dp_);CHKERRQ(ierr);
-  CHKHIP(mi355x_vec_aypx_dev(dc->h, N_(p), mi355x_handle_device_scratch(dc->h) + 1, den, dz, dp_));
-  VecHIPRestoreWrite(p);
-  HipStateIncrease(p);
+  PetscErrorCode ierr; DEVCTX;
+  Operand o[] = {RD(z), RW(p)};
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_aypx_dev(dc->h, N_(p), mi355x_handle_device_scratch(dc->h) + 1, den, o[0].d, o[1].d));
+  operands_put(o, NOPS(o), 0);
   ierr = PetscLogFlops(2.0 * p->map->n);CHKERRQ(ierr);
   return 0;
 }
 /* x += a p (a = beta / p'w formed and tested as VecCGUpdateDevBegin does, p'w still in slot DPI_SLOT; a refused step leaves x
  * alone), then p = z + (zr/den) p as VecAYPXDev: the second half of VecCGUpdateDevBeginNoX's iteration in the AYPX pass */
 PetscErrorCode VecAYPXDevX_HIPMI355X(Vec p, PetscScalar den, Vec z, Vec x, PetscScalar beta, PetscScalar dpiold, PetscBool check_sign) {
-  PetscErrorCode ierr; const PetscScalar *dz; PetscScalar *dp_, *dx; double *ds; DEVCTX;
-  ierr = VecHIPGetRead(z, &dz);CHKERRQ(ierr);
-  ierr = VecHIPGetReadWrite(p, &dp_);CHKERRQ(ierr);
-  ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr);
+  PetscErrorCode ierr; double *ds; DEVCTX;
+  Operand o[] = {RD(z), RW(p), RW(x)};
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
   ds = mi355x_handle_device_scratch(dc->h);
-  CHKHIP(mi355x_vec_aypx_dev_x(dc->h, N_(p), ds + 1, den, dz, dp_, beta, ds + DPI_SLOT, dpiold, (int)check_sign, dx));
-  VecHIPRestoreWrite(p); VecHIPRestoreWrite(x);
-  HipStateIncrease(p); HipStateIncrease(x);
+  CHKHIP(mi355x_vec_aypx_dev_x(dc->h, N_(p), ds + 1, den, o[0].d, o[1].d, beta, ds + DPI_SLOT, dpiold, (int)check_sign, o[2].d));
+  operands_put(o, NOPS(o), 0);
   ierr = PetscLogFlops(4.0 * p->map->n);CHKERRQ(ierr);
   return 0;
 }
-/* can the six vectors of a CG iteration take the fused update at all (types, sizes, aliasing)? */
-PetscErrorCode VecCGUpdateCheck_HIPMI355X(Vec x, Vec r, Vec z, Vec p, Vec w, Vec d, PetscBool *ok) {
-  *ok = PETSC_FALSE;
-  /* d == NULL: identity preconditioner (PCNONE), z = r */
-  if (!is_hip(x) || !is_hip(r) || !is_hip(z) || !is_hip(p) || !is_hip(w) || (d && !is_hip(d))) return 0;
-  if (x->map->n != r->map->n || x->map->n != z->map->n || x->map->n != p->map->n || x->map->n != w->map->n || (d && x->map->n != d->map->n)) return 0;
-  if (x == r || x == z || r == z || z == p || z == d) return 0;   /* z may be w (cg.c:122 keeps A*p in Z) */
-  *ok = PETSC_TRUE;
+
+/* Fused forms for KSPSolve_BCGS (krylov.c); *done = PETSC_FALSE and nothing touched unless the operands pass the gate: HIPMI355X
+ * vectors of one local size, the written ones (w; x and r) no other operand of the call.  d == NULL stands for the identity
+ * preconditioner. */
+static PetscErrorCode pmult_dot(Vec w, Vec x, Vec d, Vec y, int two, PetscScalar *res, PetscBool *done) {   /* w = x.*d ; (w,y) -- two: (y,w), (w,w) */
+  PetscErrorCode ierr; DEVCTX;
+  Operand o[] = {RD(x), RD(d), RD(y), WR(w)};
+  *done = PETSC_FALSE;
+  if (!w || !x || !y || !operands_ok(o, NOPS(o), NULL, 0)) return 0;
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
+  if (two) CHKHIP(mi355x_vec_pmult_dotnorm2(dc->h, N_(w), o[0].d, o[1].d, o[2].d, o[3].d, reduce_target(w, dc)));
+  else CHKHIP(mi355x_vec_pmult_dot(dc->h, N_(w), o[0].d, o[1].d, o[2].d, o[3].d, reduce_target(w, dc)));
+  operands_put(o, NOPS(o), 0);
+  ierr = reduce_finish(w, dc, two ? 2 : 1, two ? 2 : 1, 0, res);CHKERRQ(ierr);
+  ierr = PetscLogFlops((two ? 5.0 : 3.0) * w->map->n);CHKERRQ(ierr);
+  *done = PETSC_TRUE;
   return 0;
 }
-
-/* Fused forms for KSPSolve_BCGS (krylov.c); *done = PETSC_FALSE and nothing touched unless every operand is a
- * HIPMI355X vector of the same local size.  d == NULL stands for the identity preconditioner. */
-static int all_hip_same_size(Vec a, Vec b, Vec c, Vec d, Vec e, Vec f) {
-  Vec v[6] = {a, b, c, d, e, f};
-  for (int i = 0; i < 6; i++) if (v[i] && (!is_hip(v[i]) || v[i]->map->n != a->map->n)) return 0;
-  return 1;
-}
 PetscErrorCode VecPMultDot_HIPMI355X(Vec w, Vec x, Vec d, Vec y, PetscScalar *val, PetscBool *done) {   /* w = x.*d ; val = (w,y) */
-  PetscErrorCode ierr; const PetscScalar *dx, *dd = NULL, *dy; PetscScalar *dw; double *out; DEVCTX;
-  *done = PETSC_FALSE;
-  if (!all_hip_same_size(w, x, y, d, NULL, NULL) || w == x || w == y || w == d) return 0;
-  ierr = VecHIPGetRead(x, &dx);CHKERRQ(ierr);
-  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
-  ierr = VecHIPGetRead(y, &dy);CHKERRQ(ierr);
-  ierr = VecHIPGetWrite(w, &dw);CHKERRQ(ierr);
-  ierr = reduce_target(w, dc, &out);CHKERRQ(ierr);
-  CHKHIP(mi355x_vec_pmult_dot(dc->h, N_(w), dx, dd, dy, dw, out));
-  VecHIPRestoreWrite(w); HipStateIncrease(w);
-  ierr = reduce_finish(w, dc, 1, 0, val);CHKERRQ(ierr);
-  ierr = PetscLogFlops(3.0 * w->map->n);CHKERRQ(ierr);
-  *done = PETSC_TRUE;
+  PetscScalar res[2];
+  PetscErrorCode ierr = pmult_dot(w, x, d, y, 0, res, done);CHKERRQ(ierr);
+  if (*done) *val = res[0];
   return 0;
 }
 PetscErrorCode VecPMultDotNorm2_HIPMI355X(Vec w, Vec x, Vec d, Vec s_, PetscScalar *dp, PetscReal *nm, PetscBool *done) {   /* w = x.*d ; (s,w), (w,w) */
-  PetscErrorCode ierr; const PetscScalar *dx, *dd = NULL, *dsv; PetscScalar *dw; double *out; PetscScalar res[2]; DEVCTX;
-  *done = PETSC_FALSE;
-  if (!all_hip_same_size(w, x, s_, d, NULL, NULL) || w == x || w == s_ || w == d) return 0;
-  ierr = VecHIPGetRead(x, &dx);CHKERRQ(ierr);
-  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
-  ierr = VecHIPGetRead(s_, &dsv);CHKERRQ(ierr);
-  ierr = VecHIPGetWrite(w, &dw);CHKERRQ(ierr);
-  ierr = reduce_target(w, dc, &out);CHKERRQ(ierr);
-  CHKHIP(mi355x_vec_pmult_dotnorm2(dc->h, N_(w), dx, dd, dsv, dw, out));
-  VecHIPRestoreWrite(w); HipStateIncrease(w);
-  ierr = reduce_finish(w, dc, 2, 0, res);CHKERRQ(ierr);
-  *dp = res[0]; *nm = res[1];
-  ierr = PetscLogFlops(5.0 * w->map->n);CHKERRQ(ierr);
-  *done = PETSC_TRUE;
+  PetscScalar res[2];
+  PetscErrorCode ierr = pmult_dot(w, x, d, s_, 1, res, done);CHKERRQ(ierr);
+  if (*done) { *dp = res[0]; *nm = res[1]; }
   return 0;
 }
 /* x = alpha p + omega s + x ; r = s - omega t ; *rr = (r,r) ; *rho = (r,rp) */
 PetscErrorCode VecBCGSUpdate_HIPMI355X(Vec x, Vec r, Vec p, Vec s_, Vec t, Vec rp, PetscScalar alpha, PetscScalar omega, PetscScalar *rr, PetscScalar *rho, PetscBool *done) {
-  PetscErrorCode ierr; const PetscScalar *dp_, *dsv, *dt, *drp; PetscScalar *dx, *dr; double *out; PetscScalar res[2]; DEVCTX;
+  PetscErrorCode ierr; PetscScalar res[2]; DEVCTX;
+  Operand o[] = {RD(p), RD(s_), RD(t), RD(rp), RW(x), WR(r)};
   *done = PETSC_FALSE;
-  if (!all_hip_same_size(x, r, p, s_, t, rp) || x == r || x == p || x == s_ || x == t || x == rp || r == p || r == s_ || r == t || r == rp) return 0;
-  ierr = VecHIPGetRead(p, &dp_);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(s_, &dsv);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(t, &dt);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(rp, &drp);CHKERRQ(ierr);
-  ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr);
-  ierr = VecHIPGetWrite(r, &dr);CHKERRQ(ierr);
-  ierr = reduce_target(x, dc, &out);CHKERRQ(ierr);
-  CHKHIP(mi355x_vec_bcgs_update(dc->h, N_(x), alpha, omega, dp_, dsv, dt, drp, dx, dr, out));
-  VecHIPRestoreWrite(x); VecHIPRestoreWrite(r);
-  HipStateIncrease(x); HipStateIncrease(r);
-  ierr = reduce_finish(x, dc, 2, 0, res);CHKERRQ(ierr);
+  if (!x || !r || !p || !s_ || !t || !rp || !operands_ok(o, NOPS(o), NULL, 0)) return 0;
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_bcgs_update(dc->h, N_(x), alpha, omega, o[0].d, o[1].d, o[2].d, o[3].d, o[4].d, o[5].d, reduce_target(x, dc)));
+  operands_put(o, NOPS(o), 0);
+  ierr = reduce_finish(x, dc, 2, 2, 0, res);CHKERRQ(ierr);
   *rr = res[0]; *rho = res[1];
   ierr = PetscLogFlops(10.0 * x->map->n);CHKERRQ(ierr);
   *done = PETSC_TRUE;
@@ -1046,30 +1065,22 @@ PetscErrorCode VecBCGSUpdate_HIPMI355X(Vec x, Vec r, Vec p, Vec s_, Vec t, Vec r
 }
 
 /* Fused forms for KSPSolve_Chebychev / KSPSolve_Richardson (include/petsckrylovfused.h cheby_step, rich_step): the residual behind
- * w = A p, a diagonal preconditioner and the update in one sweep; *done = PETSC_FALSE and nothing touched unless every operand is a
- * HIPMI355X vector of the same local size and the written vector overlaps nothing it may not. */
+ * w = A p, a diagonal preconditioner and the update in one sweep; *done = PETSC_FALSE and nothing touched unless the operands pass the
+ * gate.  Permitted: the residual r may be w (it is formed over the product), and Chebyshev's pn may be w when there is no b (w given as
+ * the preconditioned residual: nothing else to form). */
 PetscErrorCode VecChebyStep_HIPMI355X(Vec pn, Vec r, Vec w, Vec b, Vec d, Vec pm, Vec pk, PetscScalar s, PetscScalar a, PetscScalar c, PetscScalar *zz, PetscScalar *rr, PetscBool *done) {
-  PetscErrorCode ierr; const PetscScalar *dw, *db = NULL, *dd = NULL, *dpm, *dpk; PetscScalar *dr = NULL, *dpn; double *out = NULL; PetscScalar res[2]; DEVCTX;
+  PetscErrorCode ierr; PetscScalar res[2]; DEVCTX;
+  enum { W_, B_, D_, PM_, PK_, R_, PN_ };
+  Operand o[] = {RD(w), RD(b), RD(d), RD(pm), RD(pk), RW(r), WR(pn)};
+  const OperandPair may[] = {{R_, W_}, {PN_, W_}};
   const int sums = zz || rr;
   *done = PETSC_FALSE;
-  if (!pn || !w || !pm || !pk || !all_hip_same_size(pn, w, pm, pk, b, d) || (r && (!is_hip(r) || r->map->n != pn->map->n))) return 0;
-  if (!b && (d || r || sums)) return 0;                                           /* w given as the preconditioned residual: nothing else to form */
-  if (pn == b || pn == d || pn == pm || pn == pk || pn == r || (pn == w && b)) return 0;
-  if (r && (r == b || r == d || r == pm || r == pk)) return 0;
-  ierr = VecHIPGetRead(w, &dw);CHKERRQ(ierr);
-  if (b) { ierr = VecHIPGetRead(b, &db);CHKERRQ(ierr); }
-  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
-  ierr = VecHIPGetRead(pm, &dpm);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(pk, &dpk);CHKERRQ(ierr);
-  if (r) { ierr = VecHIPGetReadWrite(r, &dr);CHKERRQ(ierr); }
-  if (pn == w) { ierr = VecHIPGetReadWrite(pn, &dpn);CHKERRQ(ierr); }
-  else { ierr = VecHIPGetWrite(pn, &dpn);CHKERRQ(ierr); }
-  if (sums) { ierr = reduce_target(pn, dc, &out);CHKERRQ(ierr); }
-  CHKHIP(mi355x_vec_cheby_step(dc->h, N_(pn), s, a, c, dw, db, dd, dpm, dpk, dr, dpn, sums, out));
-  VecHIPRestoreWrite(pn); HipStateIncrease(pn);
-  if (r) { VecHIPRestoreWrite(r); HipStateIncrease(r); }
+  if (!pn || !w || !pm || !pk || (!b && (d || r || sums)) || !operands_ok(o, NOPS(o), may, b ? 1 : 2)) return 0;
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_cheby_step(dc->h, N_(pn), s, a, c, o[W_].d, o[B_].d, o[D_].d, o[PM_].d, o[PK_].d, o[R_].d, o[PN_].d, sums, sums ? reduce_target(pn, dc) : NULL));
+  operands_put(o, NOPS(o), 0);
   if (sums) {
-    ierr = reduce_finish(pn, dc, 2, 0, res);CHKERRQ(ierr);
+    ierr = reduce_finish(pn, dc, 2, 2, 0, res);CHKERRQ(ierr);
     if (zz) *zz = res[0];
     if (rr) *rr = res[1];
   }
@@ -1078,22 +1089,15 @@ PetscErrorCode VecChebyStep_HIPMI355X(Vec pn, Vec r, Vec w, Vec b, Vec d, Vec pm
   return 0;
 }
 PetscErrorCode VecRichStep_HIPMI355X(Vec x, Vec r, Vec z, Vec w, Vec b, Vec d, PetscScalar scale, PetscBool *done) {
-  PetscErrorCode ierr; const PetscScalar *dw, *db, *dd = NULL; PetscScalar *dr = NULL, *dz = NULL, *dx; DEVCTX;
+  PetscErrorCode ierr; DEVCTX;
+  enum { W_, B_, D_, R_, Z_, X_ };
+  Operand o[] = {RD(w), RD(b), RD(d), RW(r), WR(z), RW(x)};
+  const OperandPair may[] = {{R_, W_}};
   *done = PETSC_FALSE;
-  if (!x || !w || !b || !all_hip_same_size(x, w, b, d, r, z)) return 0;
-  if (x == w || x == b || x == d || x == r || x == z) return 0;
-  if (r && (r == b || r == d || r == z)) return 0;
-  if (z && (z == w || z == b || z == d)) return 0;
-  ierr = VecHIPGetRead(w, &dw);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(b, &db);CHKERRQ(ierr);
-  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
-  if (r) { ierr = VecHIPGetReadWrite(r, &dr);CHKERRQ(ierr); }
-  if (z) { ierr = VecHIPGetWrite(z, &dz);CHKERRQ(ierr); }
-  ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr);
-  CHKHIP(mi355x_vec_rich_step(dc->h, N_(x), scale, dw, db, dd, dr, dz, dx));
-  VecHIPRestoreWrite(x); HipStateIncrease(x);
-  if (r) { VecHIPRestoreWrite(r); HipStateIncrease(r); }
-  if (z) { VecHIPRestoreWrite(z); HipStateIncrease(z); }
+  if (!x || !w || !b || !operands_ok(o, NOPS(o), may, NOPS(may))) return 0;
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_rich_step(dc->h, N_(x), scale, o[W_].d, o[B_].d, o[D_].d, o[R_].d, o[Z_].d, o[X_].d));
+  operands_put(o, NOPS(o), 0);
   ierr = PetscLogFlops((d ? 4.0 : 3.0) * x->map->n);CHKERRQ(ierr);
   *done = PETSC_TRUE;
   return 0;
@@ -1187,7 +1191,7 @@ static PetscErrorCode sr_fetch(Vec x) {
       if (HipCommAllreduce(HipObjComm(o), sr.val, sr.n, 1, 0)) SETERRQ(HipObjComm(o), PETSC_ERR_LIB, "allreduce failed");
     } else {
       mi355x_handle_t hh = DEVICE_COLLECTIVES(o) ? dc->hcomm : dc->h;
-      CHKHIP(mi355x_handle_wait_result(hh)); { PetscErrorCode e_ = HipTriWatchCheck();CHKERRQ(e_); }
+      ierr = result_wait(hh);CHKERRQ(ierr);
       const double *hs = mi355x_handle_host_scratch(hh) + SR_HOST0;
       for (int j = 0; j < sr.n; j++) sr.val[j] = hs[sr.src[j]];
       /* the slots may be rewritten by the next phase only after the all-reduce that read them has finished */
@@ -1215,29 +1219,22 @@ static PetscErrorCode VecNormEnd_HIP(Vec x, NormType type, PetscReal *result) {
 /* Fused form for KSPSolve_PIPECG (include/petsckrylovfused.h pipecg_step): the eight vector updates behind m = B w and n = A m, the next
  * m = B w for a diagonal B, and the sums of the next iteration's reduction in one sweep.  The sums are not waited for: they are left
  * pending as VecNormBegin / VecDotBegin(r, u) followed by VecDotBegin(w, u) would have left them, and the caller's
- * PetscCommSplitReductionBegin / VecNormEnd / VecDotEnd bring them home.  *done = PETSC_FALSE and nothing touched unless every
- * operand is a HIPMI355X vector of the same local size and no written vector is another operand (m_next alone may be mv). */
+ * PetscCommSplitReductionBegin / VecNormEnd / VecDotEnd bring them home.  *done = PETSC_FALSE and nothing touched unless the operands
+ * pass the gate; permitted: m_next may be mv (every load of an element precedes its stores).  d and m_next may be missing. */
 PetscErrorCode VecPipeCGStep_HIPMI355X(Vec x, Vec u, Vec w, Vec r, Vec zrec, Vec qrec, Vec p, Vec s_, Vec nv, Vec mv, Vec d, Vec m_next,
                                        PetscBool first, PetscScalar ratio, PetscScalar step, PetscInt rides, PetscBool *done) {
-  PetscErrorCode ierr; DEVCTX;
-  Vec wr[8] = {x, u, w, r, zrec, qrec, p, s_}, all[12] = {x, u, w, r, zrec, qrec, p, s_, nv, mv, d, m_next};
-  PetscScalar *dwr[8], *dm = NULL; const PetscScalar *dnv, *dmv, *dd = NULL; double *out = NULL;
+  PetscErrorCode ierr; double *out = NULL; DEVCTX;
+  enum { NV_, MV_, D_, X_, U_, W_, R_, ZREC_, QREC_, P_, S_, MNEXT_ };
+  Operand o[] = {RD(nv), RD(mv), RD(d), RW(x), RW(u), RW(w), RW(r), RW(zrec), RW(qrec), RW(p), RW(s_), WR(m_next)};
+  const OperandPair may[] = {{MNEXT_, MV_}};
   *done = PETSC_FALSE;
   if (rides < 0 || rides > 3) return 0;
-  for (int i = 0; i < 10; i++) if (!all[i]) return 0;
-  for (int i = 0; i < 12; i++) if (all[i] && (!is_hip(all[i]) || all[i]->map->n != x->map->n)) return 0;
-  for (int i = 0; i < 8; i++) for (int j = i + 1; j < 12; j++) if (wr[i] == all[j]) return 0;
-  if (m_next && (m_next == nv || m_next == d)) return 0;
+  if (!x || !u || !w || !r || !zrec || !qrec || !p || !s_ || !nv || !mv || !operands_ok(o, NOPS(o), may, NOPS(may))) return 0;
   if (rides) { ierr = sr_fused_slots(x, 2, &out);CHKERRQ(ierr); }
-  ierr = VecHIPGetRead(nv, &dnv);CHKERRQ(ierr);
-  if (m_next != mv) { ierr = VecHIPGetRead(mv, &dmv);CHKERRQ(ierr); }
-  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
-  for (int i = 0; i < 8; i++) { ierr = VecHIPGetReadWrite(wr[i], &dwr[i]);CHKERRQ(ierr); }
-  if (m_next == mv) { ierr = VecHIPGetReadWrite(m_next, &dm);CHKERRQ(ierr); dmv = dm; }
-  else if (m_next) { ierr = VecHIPGetWrite(m_next, &dm);CHKERRQ(ierr); }
-  CHKHIP(mi355x_vec_pipecg_step(dc->h, N_(x), first ? 1 : 0, ratio, step, dnv, dmv, dd, dwr[4], dwr[5], dwr[6], dwr[7], dwr[0], dwr[1], dwr[2], dwr[3], dm, (int)rides, out));
-  for (int i = 0; i < 8; i++) { VecHIPRestoreWrite(wr[i]); HipStateIncrease(wr[i]); }
-  if (m_next) { VecHIPRestoreWrite(m_next); HipStateIncrease(m_next); }
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_pipecg_step(dc->h, N_(x), first ? 1 : 0, ratio, step, o[NV_].d, o[MV_].d, o[D_].d, o[ZREC_].d, o[QREC_].d, o[P_].d, o[S_].d,
+                                o[X_].d, o[U_].d, o[W_].d, o[R_].d, o[MNEXT_].d, (int)rides, out));
+  operands_put(o, NOPS(o), 0);
   if (rides) {                                                      /* Begin order: what rides, then w'u; the sweep stores w'u first */
     const int kind[2] = {rides == 3 ? 0 : 1, 0}, from[2] = {1, 0};
     sr_fused_queued(w, 2, kind, from);
@@ -1253,64 +1250,44 @@ static const VecPipelinedCGFusedOps *VecPipelinedCGFusedOps_HIP(void) {
 }
 
 /* Fused forms for KSPSolve_MINRES (include/petsckrylovfused.h minres_lanczos, minres_update).  *done = PETSC_FALSE and nothing touched
- * unless every operand is a HIPMI355X vector of the same local size and no written vector is another operand of the call.
- * The Lanczos sweep: PCApply_Jacobi (d), the four VecAXPY and VecDot(r, z) behind r = A u and alpha = u'r.  alpha_on_device: alpha is
- * what VecTDotBegin_HIPMI355X(u, r) left in slot DPI_SLOT (all-reduced there over RCCL), never fetched before; it comes home beside
- * r'z, so the iteration has one wait.  r'z is all-reduced as every fused reduction is (reduce_finish2: RCCL, host-staged or one rank);
- * alpha rides along as it is, being the same number on every rank already. */
+ * unless the operands pass the gate; no pair is permitted.
+ * The Lanczos sweep: PCApply_Jacobi (d), the four VecAXPY and VecDot(r, z) behind r = A u and alpha = u'r; r and z are written, and z
+ * is not read when d forms it.  alpha_on_device: alpha is what VecTDotBegin_HIPMI355X(u, r) left in slot DPI_SLOT (all-reduced there
+ * over RCCL), never fetched before; it comes home beside r'z, so the iteration has one wait.  r'z is all-reduced as every fused
+ * reduction is (reduce_finish: RCCL, host-staged or one rank); alpha rides along as it is, being the same number on every rank already. */
 PetscErrorCode VecMinresLanczos_HIPMI355X(Vec r, Vec z, Vec v, Vec u, Vec vold, Vec uold, Vec d, PetscScalar alpha, PetscBool alpha_on_device, PetscScalar beta,
                                           PetscScalar *dp, PetscScalar *alpha_out, PetscBool *done) {
-  PetscErrorCode ierr; DEVCTX;
-  Vec all[7] = {r, z, v, u, vold, uold, d};
-  const PetscScalar *dv, *du, *dvo, *duo, *dd = NULL; PetscScalar *dr, *dz, res[2]; double *out;
+  PetscErrorCode ierr; PetscScalar res[2]; DEVCTX;
+  enum { V_, U_, VOLD_, UOLD_, D_, R_, Z_ };
+  Operand o[] = {RD(v), RD(u), RD(vold), RD(uold), RD(d), RW(r), RW(z)};
   *done = PETSC_FALSE;
-  for (int i = 0; i < 6; i++) if (!all[i]) return 0;
-  for (int i = 0; i < 7; i++) if (all[i] && (!is_hip(all[i]) || all[i]->map->n != r->map->n)) return 0;
-  if (r == z) return 0;
-  for (int j = 2; j < 7; j++) if (all[j] == r || all[j] == z) return 0;
+  if (d) o[Z_].mode = OP_WRITE;
+  if (!r || !z || !v || !u || !vold || !uold || !operands_ok(o, NOPS(o), NULL, 0)) return 0;
   if (alpha_on_device && HOST_STAGED(r)) return 0;                     /* VecTDotBegin refuses there: nothing can be in the slot */
-  ierr = VecHIPGetRead(v, &dv);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(u, &du);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(vold, &dvo);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(uold, &duo);CHKERRQ(ierr);
-  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
-  ierr = VecHIPGetReadWrite(r, &dr);CHKERRQ(ierr);
-  if (d) { ierr = VecHIPGetWrite(z, &dz);CHKERRQ(ierr); }
-  else { ierr = VecHIPGetReadWrite(z, &dz);CHKERRQ(ierr); }
-  ierr = reduce_target(r, dc, &out);CHKERRQ(ierr);
-  CHKHIP(mi355x_vec_minres_lanczos(dc->h, N_(r), alpha, alpha_on_device ? mi355x_handle_device_scratch(dc->h) + DPI_SLOT : NULL, beta, dd, dr, dz, dv, du, dvo, duo, out));
-  VecHIPRestoreWrite(r); VecHIPRestoreWrite(z);
-  HipStateIncrease(r); HipStateIncrease(z);
-  ierr = reduce_finish2(r, dc, 1, 2, 0, res);CHKERRQ(ierr);
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_minres_lanczos(dc->h, N_(r), alpha, alpha_on_device ? mi355x_handle_device_scratch(dc->h) + DPI_SLOT : NULL, beta, o[D_].d, o[R_].d, o[Z_].d,
+                                   o[V_].d, o[U_].d, o[VOLD_].d, o[UOLD_].d, reduce_target(r, dc)));
+  operands_put(o, NOPS(o), 0);
+  ierr = reduce_finish(r, dc, 1, 2, 0, res);CHKERRQ(ierr);
   *dp = res[0]; *alpha_out = res[1];
   ierr = PetscLogFlops(((d ? 1.0 : 0.0) + 10.0) * r->map->n);CHKERRQ(ierr);   /* n + 4 x 2n + 2n */
   *done = PETSC_TRUE;
   return 0;
 }
 /* The update sweep: the new search direction over wold's storage, x, and the next Lanczos pair scaled into vnew / unew; first: the
- * two scales of the solve start alone.  A pure map: nothing comes back to the host. */
+ * two scales of the solve start alone (x, u, w, wold are not touched, so not looked at).  A pure map: nothing comes back to the host. */
 PetscErrorCode VecMinresUpdate_HIPMI355X(Vec x, Vec u, Vec w, Vec wold, Vec r, Vec z, Vec vnew, Vec unew, PetscBool first,
                                          PetscScalar rho2, PetscScalar rho3, PetscScalar irho1, PetscScalar ceta, PetscScalar ibeta, PetscBool *done) {
   PetscErrorCode ierr; DEVCTX;
-  Vec wr[4] = {vnew, unew, wold, x}, all[8] = {vnew, unew, wold, x, u, w, r, z};
-  const int nwr = first ? 2 : 4;
-  const PetscScalar *du = NULL, *dw = NULL, *dr, *dz; PetscScalar *dwo = NULL, *dx = NULL, *dvn, *dun;
+  enum { U_, W_, R_, Z_, WOLD_, X_, VNEW_, UNEW_ };
   *done = PETSC_FALSE;
-  if (first) { all[2] = all[3] = all[4] = all[5] = NULL; }             /* not touched, so not looked at */
-  if (!vnew || !unew || !r || !z) return 0;
-  for (int i = 2; i < 6; i++) if (!first && !all[i]) return 0;
-  for (int i = 0; i < 8; i++) if (all[i] && (!is_hip(all[i]) || all[i]->map->n != vnew->map->n)) return 0;
-  for (int i = 0; i < nwr; i++) for (int j = 0; j < 8; j++) if (j != i && all[j] && wr[i] == all[j]) return 0;
-  if (!first) { ierr = VecHIPGetRead(u, &du);CHKERRQ(ierr); ierr = VecHIPGetRead(w, &dw);CHKERRQ(ierr); }
-  ierr = VecHIPGetRead(r, &dr);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(z, &dz);CHKERRQ(ierr);
-  if (!first) { ierr = VecHIPGetReadWrite(wold, &dwo);CHKERRQ(ierr); ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr); }
-  ierr = VecHIPGetWrite(vnew, &dvn);CHKERRQ(ierr);
-  ierr = VecHIPGetWrite(unew, &dun);CHKERRQ(ierr);
-  CHKHIP(mi355x_vec_minres_update(dc->h, N_(vnew), first ? 1 : 0, rho2, rho3, irho1, ceta, ibeta, du, dw, dwo, dx, dr, dz, dvn, dun));
-  VecHIPRestoreWrite(vnew); VecHIPRestoreWrite(unew);
-  HipStateIncrease(vnew); HipStateIncrease(unew);
-  if (!first) { VecHIPRestoreWrite(wold); VecHIPRestoreWrite(x); HipStateIncrease(wold); HipStateIncrease(x); }
+  if (first) x = u = w = wold = NULL;
+  Operand o[] = {RD(u), RD(w), RD(r), RD(z), RW(wold), RW(x), WR(vnew), WR(unew)};
+  if (!vnew || !unew || !r || !z || (!first && (!x || !u || !w || !wold)) || !operands_ok(o, NOPS(o), NULL, 0)) return 0;
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_minres_update(dc->h, N_(vnew), first ? 1 : 0, rho2, rho3, irho1, ceta, ibeta, o[U_].d, o[W_].d, o[WOLD_].d, o[X_].d, o[R_].d, o[Z_].d,
+                                  o[VNEW_].d, o[UNEW_].d));
+  operands_put(o, NOPS(o), 0);
   ierr = PetscLogFlops((first ? 2.0 : 9.0) * vnew->map->n);CHKERRQ(ierr);     /* 2 x 2n + n + 2n + 2 x n */
   *done = PETSC_TRUE;
   return 0;
@@ -1322,51 +1299,32 @@ static const VecMinresFusedOps *VecMinresFusedOps_HIP(void) {
 }
 
 /* Fused forms for KSPSolve_TFQMR and KSPSolve_CGS (include/petsckrylovfused.h tfqmr_qt, tfqmr_resid, tfqmr_update).  *done = PETSC_FALSE
- * and nothing touched unless every operand the form touches is a HIPMI355X vector of the same local size and no written vector is
- * another operand of the call.  The accessors run the noted operations first, as everywhere. */
-static int tfqmr_operands_ok(Vec *all, int nall, int nwritten) {       /* the first nwritten of all[] are written; NULL: not touched */
-  Vec first = NULL;
-  for (int i = 0; i < nall; i++) {
-    if (!all[i]) continue;
-    if (!first) first = all[i];
-    if (!is_hip(all[i]) || all[i]->map->n != first->map->n) return 0;
-  }
-  for (int i = 0; i < nwritten; i++) for (int j = 0; j < nall; j++) if (j != i && all[i] && all[i] == all[j]) return 0;
-  return 1;
-}
+ * and nothing touched unless the operands the form touches pass the gate; no pair is permitted.  A written vector the kernel does not
+ * store in a special case (a == 0, an eta of 0, b == 0, no tail) stays unmarked. */
 PetscErrorCode VecTfqmrQT_HIPMI355X(Vec u, Vec v, Vec q, Vec t, Vec x, PetscScalar a, PetscBool *done) {
   PetscErrorCode ierr; DEVCTX;
-  Vec all[5] = {q, t, x, u, v};
-  const PetscScalar *du, *dv; PetscScalar *dq, *dt, *dx = NULL;
+  enum { U_, V_, Q_, T_, X_ };
+  Operand o[] = {RD(u), RD(v), WR(q), WR(t), RW(x)};
   *done = PETSC_FALSE;
-  if (!u || !v || !q || !t || !tfqmr_operands_ok(all, 5, 3)) return 0;
-  ierr = VecHIPGetRead(u, &du);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(v, &dv);CHKERRQ(ierr);
-  ierr = VecHIPGetWrite(q, &dq);CHKERRQ(ierr);
-  ierr = VecHIPGetWrite(t, &dt);CHKERRQ(ierr);
-  if (x) { ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr); }
-  CHKHIP(mi355x_vec_tfqmr_qt(dc->h, N_(q), a, du, dv, dq, dt, dx));
-  VecHIPRestoreWrite(q); VecHIPRestoreWrite(t);
-  HipStateIncrease(q); HipStateIncrease(t);
-  if (x && a != 0.0) { VecHIPRestoreWrite(x); HipStateIncrease(x); }
+  if (!u || !v || !q || !t || !operands_ok(o, NOPS(o), NULL, 0)) return 0;
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_tfqmr_qt(dc->h, N_(q), a, o[U_].d, o[V_].d, o[Q_].d, o[T_].d, o[X_].d));
+  operands_put(o, NOPS(o), a != 0.0 ? 0 : 1u << X_);
   ierr = PetscLogFlops((x ? 5.0 : 3.0) * q->map->n);CHKERRQ(ierr);           /* 2n + n (+ 2n) */
   *done = PETSC_TRUE;
   return 0;
 }
-/* r'r and r'rp are all-reduced as every fused reduction is (reduce_finish2: RCCL, host-staged or one rank) */
+/* r'r and r'rp are all-reduced as every fused reduction is (reduce_finish: RCCL, host-staged or one rank) */
 PetscErrorCode VecTfqmrResid_HIPMI355X(Vec r, Vec auq, Vec rp, PetscScalar a, PetscScalar *rr, PetscScalar *rrp, PetscBool *done) {
-  PetscErrorCode ierr; DEVCTX;
-  Vec all[3] = {r, auq, rp};
-  const PetscScalar *da, *drp; PetscScalar *dr, res[2]; double *out;
+  PetscErrorCode ierr; PetscScalar res[2]; DEVCTX;
+  enum { AUQ_, RP_, R_ };
+  Operand o[] = {RD(auq), RD(rp), RW(r)};
   *done = PETSC_FALSE;
-  if (!r || !auq || !rp || !tfqmr_operands_ok(all, 3, 1)) return 0;
-  ierr = VecHIPGetRead(auq, &da);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(rp, &drp);CHKERRQ(ierr);
-  ierr = VecHIPGetReadWrite(r, &dr);CHKERRQ(ierr);
-  ierr = reduce_target(r, dc, &out);CHKERRQ(ierr);
-  CHKHIP(mi355x_vec_tfqmr_resid(dc->h, N_(r), a, da, drp, dr, out));
-  if (a != 0.0) { VecHIPRestoreWrite(r); HipStateIncrease(r); }
-  ierr = reduce_finish2(r, dc, 2, 2, 0, res);CHKERRQ(ierr);
+  if (!r || !auq || !rp || !operands_ok(o, NOPS(o), NULL, 0)) return 0;
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_tfqmr_resid(dc->h, N_(r), a, o[AUQ_].d, o[RP_].d, o[R_].d, reduce_target(r, dc)));
+  operands_put(o, NOPS(o), a != 0.0 ? 0 : 1u << R_);
+  ierr = reduce_finish(r, dc, 2, 2, 0, res);CHKERRQ(ierr);
   *rr = res[0]; *rrp = res[1];
   ierr = PetscLogFlops(6.0 * r->map->n);CHKERRQ(ierr);                         /* 2n + 2n + 2n */
   *done = PETSC_TRUE;
@@ -1374,9 +1332,8 @@ PetscErrorCode VecTfqmrResid_HIPMI355X(Vec r, Vec auq, Vec rp, PetscScalar a, Pe
 }
 PetscErrorCode VecTfqmrUpdate_HIPMI355X(Vec d, Vec x, Vec u, Vec q, Vec r, Vec p, PetscInt nhalves, PetscScalar cf0, PetscScalar eta0, PetscScalar cf1, PetscScalar eta1,
                                         PetscBool tail, PetscScalar b, PetscBool *done) {
-  PetscErrorCode ierr; DEVCTX;
-  Vec all[6];
-  const PetscScalar *dr = NULL; PetscScalar *dd = NULL, *dx = NULL, *du = NULL, *dq = NULL, *dp_ = NULL;
+  PetscErrorCode ierr; unsigned skip = 0; DEVCTX;
+  enum { D_, X_, U_, Q_, R_, P_ };
   *done = PETSC_FALSE;
   if (nhalves < 0 || nhalves > 2) return 0;
   if (nhalves == 0) d = x = NULL;                                       /* what the form does not touch is not looked at */
@@ -1384,22 +1341,15 @@ PetscErrorCode VecTfqmrUpdate_HIPMI355X(Vec d, Vec x, Vec u, Vec q, Vec r, Vec p
   if (nhalves == 0 && !tail) u = NULL;
   if (!tail) r = p = NULL;
   if ((nhalves >= 1 && (!d || !x || !u)) || (nhalves == 2 && !q) || (tail && (!u || !q || !r || !p))) return 0;
-  all[0] = d; all[1] = x; all[2] = u; all[3] = q; all[4] = p; all[5] = r;
-  if (!tfqmr_operands_ok(all, 6, 5)) return 0;
+  Operand o[] = {RW(d), RW(x), RW(u), RW(q), RD(r), RW(p)};
+  if (!operands_ok(o, NOPS(o), NULL, 0)) return 0;
   if (nhalves == 0 && !tail) { *done = PETSC_TRUE; return 0; }
-  if (d) { ierr = VecHIPGetReadWrite(d, &dd);CHKERRQ(ierr); }
-  if (x) { ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr); }
-  if (u) { ierr = VecHIPGetReadWrite(u, &du);CHKERRQ(ierr); }
-  if (q) { ierr = VecHIPGetReadWrite(q, &dq);CHKERRQ(ierr); }
-  if (r) { ierr = VecHIPGetRead(r, &dr);CHKERRQ(ierr); }
-  if (p) { ierr = VecHIPGetReadWrite(p, &dp_);CHKERRQ(ierr); }
-  CHKHIP(mi355x_vec_tfqmr_update(dc->h, N_(u), (int)nhalves, cf0, eta0, cf1, eta1, tail ? 1 : 0, b, dd, dx, du, dq, dr, dp_));
-  if (d) { VecHIPRestoreWrite(d); HipStateIncrease(d); }
-  if (x && (eta0 != 0.0 || (nhalves == 2 && eta1 != 0.0))) { VecHIPRestoreWrite(x); HipStateIncrease(x); }
-  if (tail) {
-    VecHIPRestoreWrite(u); HipStateIncrease(u); VecHIPRestoreWrite(p); HipStateIncrease(p);
-    if (b != 0.0) { VecHIPRestoreWrite(q); HipStateIncrease(q); }
-  }
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_tfqmr_update(dc->h, N_(u), (int)nhalves, cf0, eta0, cf1, eta1, tail ? 1 : 0, b, o[D_].d, o[X_].d, o[U_].d, o[Q_].d, o[R_].d, o[P_].d));
+  if (!(eta0 != 0.0 || (nhalves == 2 && eta1 != 0.0))) skip |= 1u << X_;
+  if (!tail) skip |= 1u << U_ | 1u << P_;                               /* the halves only read u and q */
+  if (!(tail && b != 0.0)) skip |= 1u << Q_;
+  operands_put(o, NOPS(o), skip);
   ierr = PetscLogFlops((4.0 * nhalves + (tail ? 6.0 : 0.0)) * u->map->n);CHKERRQ(ierr);
   *done = PETSC_TRUE;
   return 0;
@@ -1410,45 +1360,38 @@ static const VecTfqmrFusedOps *VecTfqmrFusedOps_HIP(void) {
   return &ops;
 }
 
-/* Fused forms for KSPSolve_BiCG (include/petsckrylovfused.h bicg_dirs, bicg_update), under the rules of the TFQMR forms above */
+/* Fused forms for KSPSolve_BiCG (include/petsckrylovfused.h bicg_dirs, bicg_update).  *done = PETSC_FALSE and nothing touched unless the
+ * operands pass the gate; no pair is permitted.  The directions keep their values only when the sweep reads them (not first, b != 0). */
 PetscErrorCode VecBicgDirs_HIPMI355X(Vec pr, Vec pl, Vec zr, Vec zl, PetscScalar b, PetscBool first, PetscBool *done) {
   PetscErrorCode ierr; DEVCTX;
-  Vec all[4] = {pr, pl, zr, zl};
-  const PetscScalar *dzr, *dzl; PetscScalar *dpr, *dpl;
+  enum { ZR_, ZL_, PR_, PL_ };
+  Operand o[] = {RD(zr), RD(zl), RW(pr), RW(pl)};
   *done = PETSC_FALSE;
-  if (!pr || !pl || !zr || !zl || !tfqmr_operands_ok(all, 4, 2)) return 0;
-  ierr = VecHIPGetRead(zr, &dzr);CHKERRQ(ierr);
-  ierr = VecHIPGetRead(zl, &dzl);CHKERRQ(ierr);
-  if (first || b == 0.0) { ierr = VecHIPGetWrite(pr, &dpr);CHKERRQ(ierr); ierr = VecHIPGetWrite(pl, &dpl);CHKERRQ(ierr); }
-  else { ierr = VecHIPGetReadWrite(pr, &dpr);CHKERRQ(ierr); ierr = VecHIPGetReadWrite(pl, &dpl);CHKERRQ(ierr); }
-  CHKHIP(mi355x_vec_bicg_dirs(dc->h, N_(pr), first ? 1 : 0, b, dzr, dzl, dpr, dpl));
-  VecHIPRestoreWrite(pr); VecHIPRestoreWrite(pl);
-  HipStateIncrease(pr); HipStateIncrease(pl);
+  if (first || b == 0.0) o[PR_].mode = o[PL_].mode = OP_WRITE;
+  if (!pr || !pl || !zr || !zl || !operands_ok(o, NOPS(o), NULL, 0)) return 0;
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_bicg_dirs(dc->h, N_(pr), first ? 1 : 0, b, o[ZR_].d, o[ZL_].d, o[PR_].d, o[PL_].d));
+  operands_put(o, NOPS(o), 0);
   ierr = PetscLogFlops(first ? 0.0 : 4.0 * pr->map->n);CHKERRQ(ierr);
   *done = PETSC_TRUE;
   return 0;
 }
-/* zr'rl and the norm's sum are all-reduced as every fused reduction is (reduce_finish2: RCCL, host-staged or one rank) */
+/* x, rr, rl stay unmarked for a == 0 (nothing moved), zr and zl without a preconditioner the sweep applies (they are only read).
+ * zr'rl and the norm's sum are all-reduced as every fused reduction is (reduce_finish: RCCL, host-staged or one rank) */
 PetscErrorCode VecBicgUpdate_HIPMI355X(Vec x, Vec rr, Vec rl, Vec pr, Vec zr, Vec zl, Vec d, PetscBool identity, PetscScalar a, PetscInt which,
                                        PetscScalar *beta, PetscScalar *nrm2, PetscBool *done) {
-  PetscErrorCode ierr; DEVCTX;
-  Vec all[7] = {x, rr, rl, zr, zl, pr, d};
+  PetscErrorCode ierr; PetscScalar res[2]; unsigned skip = 0; DEVCTX;
+  enum { PR_, D_, X_, RR_, RL_, ZR_, ZL_ };
+  Operand o[] = {RD(pr), RD(d), RW(x), RW(rr), RW(rl), RW(zr), RW(zl)};
   const int pcmode = d ? 1 : (identity ? 2 : 0);
-  const PetscScalar *dpr, *dd = NULL; PetscScalar *dx, *drr, *drl, *dzr, *dzl, res[2]; double *out;
   *done = PETSC_FALSE;
-  if (!x || !rr || !rl || !pr || !zr || !zl || (which != 0 && which != 1) || (d && identity) || !tfqmr_operands_ok(all, 7, 5)) return 0;
-  ierr = VecHIPGetRead(pr, &dpr);CHKERRQ(ierr);
-  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
-  ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr);
-  ierr = VecHIPGetReadWrite(rr, &drr);CHKERRQ(ierr);
-  ierr = VecHIPGetReadWrite(rl, &drl);CHKERRQ(ierr);
-  ierr = VecHIPGetReadWrite(zr, &dzr);CHKERRQ(ierr);
-  ierr = VecHIPGetReadWrite(zl, &dzl);CHKERRQ(ierr);
-  ierr = reduce_target(rr, dc, &out);CHKERRQ(ierr);
-  CHKHIP(mi355x_vec_bicg_update(dc->h, N_(rr), a, pcmode, (int)which, dpr, dd, dx, drr, drl, dzr, dzl, out));
-  if (a != 0.0) { VecHIPRestoreWrite(x); HipStateIncrease(x); VecHIPRestoreWrite(rr); HipStateIncrease(rr); VecHIPRestoreWrite(rl); HipStateIncrease(rl); }
-  if (pcmode) { VecHIPRestoreWrite(zr); HipStateIncrease(zr); VecHIPRestoreWrite(zl); HipStateIncrease(zl); }
-  ierr = reduce_finish2(rr, dc, 2, 2, 0, res);CHKERRQ(ierr);
+  if (!x || !rr || !rl || !pr || !zr || !zl || (which != 0 && which != 1) || (d && identity) || !operands_ok(o, NOPS(o), NULL, 0)) return 0;
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
+  CHKHIP(mi355x_vec_bicg_update(dc->h, N_(rr), a, pcmode, (int)which, o[PR_].d, o[D_].d, o[X_].d, o[RR_].d, o[RL_].d, o[ZR_].d, o[ZL_].d, reduce_target(rr, dc)));
+  if (!(a != 0.0)) skip |= 1u << X_ | 1u << RR_ | 1u << RL_;
+  if (!pcmode) skip |= 1u << ZR_ | 1u << ZL_;
+  operands_put(o, NOPS(o), skip);
+  ierr = reduce_finish(rr, dc, 2, 2, 0, res);CHKERRQ(ierr);
   if (pcmode && beta) *beta = res[0];
   *nrm2 = res[1];
   ierr = PetscLogFlops((6.0 + (pcmode == 1 ? 2.0 : 0.0) + (pcmode ? 4.0 : 2.0)) * rr->map->n);CHKERRQ(ierr);
@@ -1461,7 +1404,8 @@ static const VecBicgFusedOps *VecBicgFusedOps_HIP(void) {
   return &ops;
 }
 
-/* Fused forms for KSPSolve_LSQR (include/petsckrylovfused.h lsqr_bidiag, lsqr_update), under the rules of the TFQMR forms above.
+/* Fused forms for KSPSolve_LSQR (include/petsckrylovfused.h lsqr_bidiag, lsqr_update).  *done = PETSC_FALSE and nothing touched unless the
+ * operands the form touches pass the gate; no pair is permitted.
  * The bidiagonalisation sweep: VecAXPY(Y, -coef, X) and the sum of VecNorm(Y, NORM_2).
  *   WAIT:    the sum is all-reduced as every fused reduction is (reduce_finish: RCCL, host-staged or one rank) and comes home: one wait.
  *   QUEUE:   the sum goes to device slot LSQR_SLOT and y is scaled by its rooted reciprocal behind the sweep (mi355x_vec_scale_rnorm_dev:
@@ -1471,61 +1415,54 @@ static const VecBicgFusedOps *VecBicgFusedOps_HIP(void) {
  * QUEUE and FINISH are refused on more than one rank: the slot would hold this rank's partial sum. */
 #define LSQR_SLOT 42     /* two device scratch slots clear of the ordinary reductions (<= 32 from 0), SUM_SLOT and the split-phase ones (48..) */
 PetscErrorCode VecLsqrBidiag_HIPMI355X(Vec x, Vec y, PetscScalar coef, VecLsqrBidiagRoute route, PetscScalar sums[2], PetscBool *done) {
-  PetscErrorCode ierr; DEVCTX;
-  Vec all[2] = {y, x};
-  const PetscScalar *dx; PetscScalar *dy; double *out, *ds;
+  PetscErrorCode ierr; double *ds; DEVCTX;
+  enum { X_, Y_ };
+  Operand o[] = {RD(x), RW(y)};
   *done = PETSC_FALSE;
   if (!x || !y || (route != LSQR_BIDIAG_WAIT && route != LSQR_BIDIAG_QUEUE && route != LSQR_BIDIAG_FINISH)) return 0;
-  if (!tfqmr_operands_ok(all, 2, 1)) return 0;
+  if (!operands_ok(o, NOPS(o), NULL, 0)) return 0;
   if (route != LSQR_BIDIAG_WAIT && (hip_local_only || HipCommSize(HipObjComm(y)) > 1 || DEVICE_COLLECTIVES(y))) return 0;
-  ierr = VecHIPGetRead(x, &dx);CHKERRQ(ierr);
-  ierr = VecHIPGetReadWrite(y, &dy);CHKERRQ(ierr);
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
   ds = mi355x_handle_device_scratch(dc->h) + LSQR_SLOT;
   if (route == LSQR_BIDIAG_WAIT) {
-    ierr = reduce_target(y, dc, &out);CHKERRQ(ierr);
-    CHKHIP(mi355x_vec_lsqr_bidiag(dc->h, N_(y), coef, NULL, dx, dy, out));
+    CHKHIP(mi355x_vec_lsqr_bidiag(dc->h, N_(y), coef, NULL, o[X_].d, o[Y_].d, reduce_target(y, dc)));
   } else if (route == LSQR_BIDIAG_QUEUE) {
-    CHKHIP(mi355x_vec_lsqr_bidiag(dc->h, N_(y), coef, NULL, dx, dy, ds));
-    CHKHIP(mi355x_vec_scale_rnorm_dev(dc->h, N_(y), ds, dy));
+    CHKHIP(mi355x_vec_lsqr_bidiag(dc->h, N_(y), coef, NULL, o[X_].d, o[Y_].d, ds));
+    CHKHIP(mi355x_vec_scale_rnorm_dev(dc->h, N_(y), ds, o[Y_].d));
   } else {
-    CHKHIP(mi355x_vec_lsqr_bidiag(dc->h, N_(y), 0.0, ds, dx, dy, ds + 1));
+    CHKHIP(mi355x_vec_lsqr_bidiag(dc->h, N_(y), 0.0, ds, o[X_].d, o[Y_].d, ds + 1));
     CHKHIP(mi355x_handle_publish(dc->h, ds, 2));
   }
-  VecHIPRestoreWrite(y);
-  HipStateIncrease(y);
-  if (route == LSQR_BIDIAG_WAIT) { ierr = reduce_finish(y, dc, 1, 0, sums);CHKERRQ(ierr); }
+  operands_put(o, NOPS(o), 0);
+  if (route == LSQR_BIDIAG_WAIT) { ierr = reduce_finish(y, dc, 1, 1, 0, sums);CHKERRQ(ierr); }
   else if (route == LSQR_BIDIAG_FINISH) {
-    CHKHIP(mi355x_handle_wait_result(dc->h)); { PetscErrorCode e_ = HipTriWatchCheck();CHKERRQ(e_); }
+    ierr = result_wait(dc->h);CHKERRQ(ierr);
     sums[0] = mi355x_handle_host_scratch(dc->h)[0]; sums[1] = mi355x_handle_host_scratch(dc->h)[1];
   }
   ierr = PetscLogFlops((route == LSQR_BIDIAG_QUEUE ? 5.0 : 4.0) * y->map->n);CHKERRQ(ierr);   /* 2n + 2n (+ n) */
   *done = PETSC_TRUE;
   return 0;
 }
-/* The update sweep: step 8's VecScale of v1, x += step w, the standard-error sum and the new w in one pass; nothing comes back */
+/* The update sweep: step 8's VecScale of v1, x += step w, the standard-error sum and the new w in one pass; nothing comes back.
+ * v1 stays unmarked for ialpha == 1, w with skip_w: the kernel does not store them. */
 PetscErrorCode VecLsqrUpdate_HIPMI355X(Vec v1, Vec x, Vec w, Vec se, PetscScalar ialpha, PetscScalar step, PetscScalar cf, PetscScalar irho2, PetscBool skip_w,
                                        PetscBool *done) {
-  PetscErrorCode ierr; DEVCTX;
-  Vec all[4];
-  PetscScalar *dv = NULL, *dx = NULL, *dw = NULL, *dse = NULL;
+  PetscErrorCode ierr; unsigned skip = 0; DEVCTX;
+  enum { V1_, X_, W_, SE_ };
   *done = PETSC_FALSE;
   if (step == 0.0) x = NULL;                                            /* not touched, so not looked at */
   if (skip_w && step == 0.0 && !se) w = NULL;
   if (skip_w && ialpha == 1.0) v1 = NULL;
   if ((!v1 && !(skip_w && ialpha == 1.0)) || (!x && step != 0.0) || (!w && (!skip_w || step != 0.0 || se))) return 0;
-  all[0] = v1; all[1] = x; all[2] = w; all[3] = se;
-  if (!tfqmr_operands_ok(all, 4, 4)) return 0;
+  Operand o[] = {RW(v1), RW(x), RW(w), RW(se)};
+  if (!operands_ok(o, NOPS(o), NULL, 0)) return 0;
   if (!v1 && !x && !w && !se) { *done = PETSC_TRUE; return 0; }
-  if (v1) { ierr = VecHIPGetReadWrite(v1, &dv);CHKERRQ(ierr); }
-  if (x) { ierr = VecHIPGetReadWrite(x, &dx);CHKERRQ(ierr); }
-  if (w) { ierr = VecHIPGetReadWrite(w, &dw);CHKERRQ(ierr); }
-  if (se) { ierr = VecHIPGetReadWrite(se, &dse);CHKERRQ(ierr); }
+  ierr = operands_get(o, NOPS(o));CHKERRQ(ierr);
   Vec any = v1 ? v1 : (w ? w : (x ? x : se));
-  CHKHIP(mi355x_vec_lsqr_update(dc->h, N_(any), ialpha, step, cf, irho2, skip_w ? 1 : 0, dv, dx, dw, dse));
-  if (v1 && ialpha != 1.0) { VecHIPRestoreWrite(v1); HipStateIncrease(v1); }
-  if (x) { VecHIPRestoreWrite(x); HipStateIncrease(x); }
-  if (se) { VecHIPRestoreWrite(se); HipStateIncrease(se); }
-  if (w && !skip_w) { VecHIPRestoreWrite(w); HipStateIncrease(w); }
+  CHKHIP(mi355x_vec_lsqr_update(dc->h, N_(any), ialpha, step, cf, irho2, skip_w ? 1 : 0, o[V1_].d, o[X_].d, o[W_].d, o[SE_].d));
+  if (!(ialpha != 1.0)) skip |= 1u << V1_;
+  if (skip_w) skip |= 1u << W_;
+  operands_put(o, NOPS(o), skip);
   ierr = PetscLogFlops(((v1 && ialpha != 1.0 ? 1.0 : 0.0) + (x ? 2.0 : 0.0) + (se ? 3.0 : 0.0) + (skip_w ? 0.0 : 2.0)) * any->map->n);CHKERRQ(ierr);
   *done = PETSC_TRUE;
   return 0;
@@ -1630,64 +1567,50 @@ static PetscErrorCode VecShareArrayEnd_HIP(Vec sub, Vec parent, PetscBool write)
  * with the scalars staying on the device: VecMDot leaves <w, V_j> in device scratch (all-reduced there over RCCL when the
  * communicator has one), one sweep does w -= sum_j h_j V_j AND sum w^2 (mi355x_vec_maxpy_dev_norm2: VecMAXPY's grouping, VecNorm's
  * order), a tiny kernel hands h and |w|^2 to the host, and w *= 1/|w| reads |w|^2 from device memory while the host already
- * has its numbers.  One host wait per Krylov step instead of three; 2 nv + 5 vector passes instead of 2 nv + 6. */
-PetscErrorCode VecGMRESOrthogNormalize_HIPMI355X(Vec w, PetscInt nv, const Vec V[], PetscScalar *dots, PetscReal *nrm, PetscBool *done) {
-  PetscErrorCode ierr; const double *tab[32]; PetscScalar *dw; double *ds; DEVCTX;
+ * has its numbers.  One host wait per Krylov step instead of three; 2 nv + 5 vector passes instead of 2 nv + 6.
+ * z != NULL, the step of flexible GMRES: the scaling sweep is mi355x_vec_scale_rnorm_dev_pmult, which also writes z = d .* w_new
+ * (d == NULL: z = w_new) from the values it holds.
+ * The gate: the nv basis vectors and d are read, w and z written -- neither is a basis vector, d or the other; no pair is permitted. */
+static PetscErrorCode orthog_normalize(Vec w, PetscInt nv, const Vec V[], Vec d, Vec z, PetscScalar *dots, PetscReal *nrm, PetscBool *done) {
+  PetscErrorCode ierr; const double *tab[32]; Operand o[35]; double *ds; DEVCTX;
   *done = PETSC_FALSE;
-  if (!is_hip(w) || nv < 1 || nv > 32 || HOST_STAGED(w)) return 0;
-  for (PetscInt j = 0; j < nv; j++) if (!is_hip(V[j]) || V[j] == w || V[j]->map->n != w->map->n) return 0;
-  for (PetscInt j = 0; j < nv; j++) { ierr = VecHIPGetRead(V[j], &tab[j]);CHKERRQ(ierr); }
-  ierr = VecHIPGetReadWrite(w, &dw);CHKERRQ(ierr);
+  if (!w || nv < 1 || nv > 32 || !is_hip(w) || HOST_STAGED(w)) return 0;
+  for (PetscInt j = 0; j < nv; j++) { if (!V[j]) return 0; o[j] = (Operand)RD(V[j]); }
+  const int D_ = (int)nv, W_ = D_ + 1, Z_ = D_ + 2;
+  o[D_] = (Operand)RD(d); o[W_] = (Operand)RW(w); o[Z_] = (Operand)WR(z);
+  if (!operands_ok(o, Z_ + 1, NULL, 0)) return 0;
+  ierr = operands_get(o, Z_ + 1);CHKERRQ(ierr);
+  for (PetscInt j = 0; j < nv; j++) tab[j] = o[j].d;
   ds = mi355x_handle_device_scratch(dc->h);
-  CHKHIP(mi355x_vec_mdot(dc->h, N_(w), (int)nv, dw, tab, ds));
+  CHKHIP(mi355x_vec_mdot(dc->h, N_(w), (int)nv, o[W_].d, tab, ds));
   if (DEVICE_COLLECTIVES(w)) CHKHIP(mi355x_comm_allreduce_sum(HipCommDevice(HipObjComm(w)), dc->h, ds, (size_t)nv));
-  CHKHIP(mi355x_vec_maxpy_dev_norm2(dc->h, N_(w), (int)nv, ds, -1.0, tab, dw, ds + nv));
+  CHKHIP(mi355x_vec_maxpy_dev_norm2(dc->h, N_(w), (int)nv, ds, -1.0, tab, o[W_].d, ds + nv));
   if (DEVICE_COLLECTIVES(w)) CHKHIP(mi355x_comm_allreduce_sum(HipCommDevice(HipObjComm(w)), dc->h, ds + nv, 1));
   CHKHIP(mi355x_handle_publish(dc->h, ds, (int)nv + 1));
-  CHKHIP(mi355x_vec_scale_rnorm_dev(dc->h, N_(w), ds + nv, dw));
-  VecHIPRestoreWrite(w);
-  HipStateIncrease(w);
-  CHKHIP(mi355x_handle_wait_result(dc->h)); { PetscErrorCode e_ = HipTriWatchCheck();CHKERRQ(e_); }
+  if (!z) CHKHIP(mi355x_vec_scale_rnorm_dev(dc->h, N_(w), ds + nv, o[W_].d));
+  else if (N_(w)) CHKHIP(mi355x_vec_scale_rnorm_dev_pmult(dc->h, N_(w), ds + nv, o[W_].d, o[D_].d, o[Z_].d));
+  operands_put(o, Z_ + 1, 0);
+  ierr = result_wait(dc->h);CHKERRQ(ierr);
   const double *hs = mi355x_handle_host_scratch(dc->h);
   for (PetscInt j = 0; j < nv; j++) dots[j] = hs[j];
   *nrm = PetscSqrtReal(hs[nv]);                                 /* pvec2.c:62-64: the square is reduced, then the root */
-  ierr = PetscLogFlops(PetscMax(nv * (2.0 * w->map->n - 1), 0.0) + 2.0 * nv * w->map->n + PetscMax(2.0 * w->map->n - 1, 0.0) + w->map->n);CHKERRQ(ierr);
+  ierr = PetscLogFlops(PetscMax(nv * (2.0 * w->map->n - 1), 0.0) + 2.0 * nv * w->map->n + PetscMax(2.0 * w->map->n - 1, 0.0) + (z && d ? 2.0 : 1.0) * w->map->n);CHKERRQ(ierr);
   *done = PETSC_TRUE;
   return 0;
 }
-/* The same step for flexible GMRES (include/petsckrylovfused.h fgmres_orthog_normalize_pc): the scaling sweep at the end is
- * mi355x_vec_scale_rnorm_dev_pmult, which writes z = d .* w_new (identity: z = w_new) from the values it holds -- the PCApply_Jacobi /
- * PCApply_None of the next step, one read of w and one launch fewer.  2 nv + 7 vector passes per step with Jacobi instead of 2 nv + 8. */
+PetscErrorCode VecGMRESOrthogNormalize_HIPMI355X(Vec w, PetscInt nv, const Vec V[], PetscScalar *dots, PetscReal *nrm, PetscBool *done) {
+  return orthog_normalize(w, nv, V, NULL, NULL, dots, nrm, done);
+}
+/* The same step for flexible GMRES (include/petsckrylovfused.h fgmres_orthog_normalize_pc): z takes the PCApply_Jacobi / PCApply_None of
+ * the next step, one read of w and one launch fewer.  2 nv + 7 vector passes per step with Jacobi instead of 2 nv + 8.  z is required,
+ * and d unless `identity` says there is none (then a d given is not looked at); the diagonal is no basis vector either. */
 PetscErrorCode VecFgmresOrthogNormalizePC_HIPMI355X(Vec w, PetscInt nv, const Vec V[], Vec d, PetscBool identity, Vec z, PetscScalar *dots, PetscReal *nrm,
                                                     PetscBool *done) {
-  PetscErrorCode ierr; const double *tab[32]; const PetscScalar *dd = NULL; PetscScalar *dw, *dz; double *ds; DEVCTX;
   *done = PETSC_FALSE;
   if (identity) d = NULL;
-  if (!is_hip(w) || !z || !is_hip(z) || z == w || (!identity && (!d || !is_hip(d) || d == w || d == z)) || nv < 1 || nv > 32 || HOST_STAGED(w)) return 0;
-  if (z->map->n != w->map->n || (d && d->map->n != w->map->n) || HOST_STAGED(z) || (d && HOST_STAGED(d))) return 0;
-  for (PetscInt j = 0; j < nv; j++) if (!is_hip(V[j]) || V[j] == w || V[j] == z || V[j] == d || V[j]->map->n != w->map->n) return 0;
-  for (PetscInt j = 0; j < nv; j++) { ierr = VecHIPGetRead(V[j], &tab[j]);CHKERRQ(ierr); }
-  if (d) { ierr = VecHIPGetRead(d, &dd);CHKERRQ(ierr); }
-  ierr = VecHIPGetReadWrite(w, &dw);CHKERRQ(ierr);
-  ierr = VecHIPGetWrite(z, &dz);CHKERRQ(ierr);
-  ds = mi355x_handle_device_scratch(dc->h);
-  CHKHIP(mi355x_vec_mdot(dc->h, N_(w), (int)nv, dw, tab, ds));
-  if (DEVICE_COLLECTIVES(w)) CHKHIP(mi355x_comm_allreduce_sum(HipCommDevice(HipObjComm(w)), dc->h, ds, (size_t)nv));
-  CHKHIP(mi355x_vec_maxpy_dev_norm2(dc->h, N_(w), (int)nv, ds, -1.0, tab, dw, ds + nv));
-  if (DEVICE_COLLECTIVES(w)) CHKHIP(mi355x_comm_allreduce_sum(HipCommDevice(HipObjComm(w)), dc->h, ds + nv, 1));
-  CHKHIP(mi355x_handle_publish(dc->h, ds, (int)nv + 1));
-  if (N_(w)) CHKHIP(mi355x_vec_scale_rnorm_dev_pmult(dc->h, N_(w), ds + nv, dw, dd, dz));
-  VecHIPRestoreWrite(w);
-  HipStateIncrease(w);
-  VecHIPRestoreWrite(z);
-  HipStateIncrease(z);
-  CHKHIP(mi355x_handle_wait_result(dc->h)); { PetscErrorCode e_ = HipTriWatchCheck();CHKERRQ(e_); }
-  const double *hs = mi355x_handle_host_scratch(dc->h);
-  for (PetscInt j = 0; j < nv; j++) dots[j] = hs[j];
-  *nrm = PetscSqrtReal(hs[nv]);                                 /* pvec2.c:62-64: the square is reduced, then the root */
-  ierr = PetscLogFlops(PetscMax(nv * (2.0 * w->map->n - 1), 0.0) + 2.0 * nv * w->map->n + PetscMax(2.0 * w->map->n - 1, 0.0) + (d ? 2.0 : 1.0) * w->map->n);CHKERRQ(ierr);
-  *done = PETSC_TRUE;
-  return 0;
+  if (!z || (!identity && !d) || nv < 1 || nv > 32 || HOST_STAGED(z) || (d && HOST_STAGED(d))) return 0;
+  for (PetscInt j = 0; d && j < nv; j++) if (V[j] == d) return 0;
+  return orthog_normalize(w, nv, V, d, z, dots, nrm, done);
 }
 /* "VecFgmresFusedOps_C": the Gram-Schmidt step of flexible GMRES */
 static const VecFgmresFusedOps *VecFgmresFusedOps_HIP(void) {
