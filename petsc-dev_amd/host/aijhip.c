@@ -15,6 +15,12 @@ static PetscBool device_values_current(Mat A);
 /* the device copy is to be built again from the host at its next use */
 static unsigned long long pattern_serial = 0;   /* pattern uploads so far, over all matrices */
 static void mirror_reset(Mat_SeqAIJHIP *d) { d->uploaded_state = -1; d->pattern_nz = -1; d->pattern_gen = 0; }
+/* stored scalars of the container (BAIJ: bs^2 per block); where row r (BAIJ: block row) keeps its diagonal entry (block), -1: nowhere */
+static size_t value_count(const HipAIJ *a) { return (size_t)a->nz * (size_t)(a->bs > 1 ? a->bs * a->bs : 1); }
+static PetscInt diag_position(const PetscInt *ai, const PetscInt *aj, PetscInt r) {
+  for (PetscInt k = ai[r]; k < ai[r + 1]; k++) if (aj[k] == r) return k;
+  return -1;
+}
 
 #if !defined(PETSCHIPMI355X_WITH_PETSC)   /* inside a PETSc tree the parent type MATSEQAIJ owns the container and its assembly (aij.c) */
 /* ---------------------------------------------------------------- host container */
@@ -159,7 +165,6 @@ static PetscErrorCode seqaij_check_inode(Mat A) {
  * slot 76, matimpl.h:110; gcreate.c:201-203) reads them under the matrix's own options prefix and keeps them with the matrix; a matrix
  * that was never asked falls back to the global database when its device copy is built (blocks of an MPIAIJ matrix, matrices created
  * by MatCreateSeqAIJWithArrays and used at once). */
-enum { HOPT_IC = 0, HOPT_RP, HOPT_VP, HOPT_TILED, HOPT_TILED_SMIN, HOPT_BLOCKED, HOPT_UPDATE_DEV, HOPT_PR, HOPT_N };
 static const char *const hopt_name[HOPT_N] = {"-mat_hipmi355x_index_compression", "-mat_hipmi355x_row_patterns", "-mat_hipmi355x_value_patterns",
                                               "-mat_hipmi355x_tiled", "-mat_hipmi355x_tiled_stage_min", "-mat_hipmi355x_blocked",
                                               "-mat_hipmi355x_update_on_device", "-mat_hipmi355x_pattern_runs"};
@@ -169,19 +174,49 @@ static PetscErrorCode hip_mat_option(Mat A, int which, PetscInt *val) {
   if (d->opt_set[which]) { *val = d->opt[which]; return 0; }
   return PetscOptionsGetInt(NULL, hopt_name[which], val, &set);
 }
-/* -mat_hipmi355x_sor <device|host> (default device): where MatSOR runs; 0: the option is not given under this prefix */
-static PetscErrorCode product_route_option(Mat A, const char *prefix, int *route);   /* -mat_hipmi355x_product, with the products below */
-static PetscErrorCode reductions_route_option(Mat A, const char *prefix, int *route);   /* -mat_hipmi355x_reductions, with the reductions below */
-static PetscErrorCode residual_route_option(Mat A, const char *prefix, int *route);   /* -mat_hipmi355x_residual, with MatResidual below */
-static PetscErrorCode coarsen_route_option(Mat A, const char *prefix, int *route);   /* -mat_hipmi355x_coarsen, with the coarsening below */
-static PetscErrorCode sor_route_option(Mat A, const char *prefix, int *route) {
+/* The route options: each picks one of two ways an operation of the matrix runs, by one of two words (route 1: the first, 2: the second).
+ * Asked under the matrix's prefix (MatSetFromOptions, at any time) the answer stays with the matrix in route[]; a matrix never asked
+ * there reads the global database -- `when` -- and takes the default -- `dflt` -- when the option is given nowhere.  DESIGN.md, "Route
+ * options", has the same table in words. */
+#ifndef HIPMI355X_RESIDUAL_DEFAULT
+#define HIPMI355X_RESIDUAL_DEFAULT 1   /* 1 fused, 2 calls */
+#endif
+enum { ROUTE_EVERY_USE,    /* the global database is read at every use */
+       ROUTE_ONCE,         /* ... at the matrix's first use; the answer, default included, is kept in route[] like one given under the prefix */
+       ROUTE_AT_UPLOAD };  /* ... whenever the device copy is built for a new pattern, into residual_global (upload_pattern): the use reads fields only */
+static const struct {
+  const char *name, *word[2];
+  int when;
+  int dflt;                /* the route when the option is given nowhere; 0: the first with a device in the process, the second without */
+  PetscBool inherited;     /* the result of a product starts with its operand's route[] entry (product_result) */
+} hroute[HROUTE_N] = {
+  [HROUTE_SOR]        = {"-mat_hipmi355x_sor",        {"device", "host"}, ROUTE_ONCE,      1,                          PETSC_TRUE},
+  [HROUTE_PRODUCT]    = {"-mat_hipmi355x_product",    {"device", "host"}, ROUTE_EVERY_USE, 1,                          PETSC_TRUE},
+  [HROUTE_REDUCTIONS] = {"-mat_hipmi355x_reductions", {"device", "host"}, ROUTE_ONCE,      0,                          PETSC_FALSE},
+  [HROUTE_RESIDUAL]   = {"-mat_hipmi355x_residual",   {"fused", "calls"}, ROUTE_AT_UPLOAD, HIPMI355X_RESIDUAL_DEFAULT, PETSC_FALSE},
+  [HROUTE_COARSEN]    = {"-mat_hipmi355x_coarsen",    {"device", "host"}, ROUTE_EVERY_USE, 0,                          PETSC_TRUE},
+};
+/* the option as given under `prefix` (NULL: the global database); 0: not given there */
+static PetscErrorCode route_option(Mat A, int which, const char *prefix, int *route) {
   PetscErrorCode ierr;
+  const char *name = hroute[which].name, *const *word = hroute[which].word;
   char kind[16] = ""; PetscBool set = PETSC_FALSE;
   *route = 0;
-  ierr = PetscOptionsGetString(prefix, "-mat_hipmi355x_sor", kind, sizeof(kind), &set);CHKERRQ(ierr);
+  ierr = PetscOptionsGetString(prefix, name, kind, sizeof(kind), &set);CHKERRQ(ierr);
   if (!set) return 0;
-  if (strcmp(kind, "device") && strcmp(kind, "host")) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "-mat_hipmi355x_sor <device|host>, got %s", kind);
-  *route = strcmp(kind, "host") ? 1 : 2;
+  if (strcmp(kind, word[0]) && strcmp(kind, word[1])) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "%s <%s|%s>, got %s", name, word[0], word[1], kind);
+  *route = strcmp(kind, word[1]) ? 1 : 2;
+  return 0;
+}
+/* the route of an operation that reads the global database when it runs (every entry but ROUTE_AT_UPLOAD's, which MatResidual reads
+ * from the struct) */
+static PetscErrorCode route_resolve(Mat A, int which, int *route) {
+  PetscErrorCode ierr;
+  *route = SD(A)->route[which];
+  if (!*route) { ierr = route_option(A, which, NULL, route);CHKERRQ(ierr); }
+  if (!*route) *route = hroute[which].dflt;
+  if (!*route) { int n = 0; *route = (mi355x_device_count(&n) || n < 1) ? 2 : 1; }
+  if (hroute[which].when == ROUTE_ONCE) SD(A)->route[which] = *route;
   return 0;
 }
 static PetscErrorCode MatSetFromOptions_SeqAIJHIP(Mat A) {
@@ -195,17 +230,11 @@ static PetscErrorCode MatSetFromOptions_SeqAIJHIP(Mat A) {
       if (k != HOPT_UPDATE_DEV) mirror_reset(d);             /* the analyses run again with the new choice */
     }
   }
-  { int route = 0;
-    ierr = sor_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
-    if (route) d->sor.route = route;
-    ierr = product_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
-    if (route) d->product_route = route;
-    ierr = reductions_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
-    if (route) d->reductions_route = route;
-    ierr = residual_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
-    if (route) d->residual_route = route;
-    ierr = coarsen_route_option(A, HipObjPrefix(A), &route);CHKERRQ(ierr);
-    if (route) d->coarsen_route = route; }
+  for (int k = 0; k < HROUTE_N; k++) {
+    int route = 0;
+    ierr = route_option(A, k, HipObjPrefix(A), &route);CHKERRQ(ierr);
+    if (route) d->route[k] = route;
+  }
   return 0;
 }
 
@@ -451,7 +480,7 @@ static PetscErrorCode upload_pattern(Mat A, PetscDeviceCtx *dc, UpTick *tk) {
   PetscErrorCode ierr;
   HipAIJ *a = SA(A);
   Mat_SeqAIJHIP *d = SD(A);
-  ierr = residual_route_option(A, NULL, &d->residual_global);CHKERRQ(ierr);   /* the global answer, once per device copy: MatResidual searches no table */
+  ierr = route_option(A, HROUTE_RESIDUAL, NULL, &d->residual_global);CHKERRQ(ierr);   /* ROUTE_AT_UPLOAD: MatResidual searches no table */
   device_free(A);
   if (a->bs > 1) {   /* BAIJ */
     if (a->bs == 4) {   /* -mat_hipmi355x_baij4 <mfma|fma>: the matrix cores (v_mfma_f64_4x4x4, 16-byte loads: 1.22-1.28 ms at 128^3 nodes, 27
@@ -641,7 +670,7 @@ static PetscErrorCode transpose_current(Mat A, PetscDeviceCtx *dc) {
   /* BAIJ (MatMultTranspose_SeqBAIJ / MatMultTransposeAdd_SeqBAIJ, baij2.c:1579, 1740): the block transpose, its values placed on the host
    * (a->m counts block rows, a->n scalar columns) */
   const PetscInt bs = a->bs > 1 ? a->bs : 1, nbc = a->n / bs;
-  const size_t nvals = (size_t)a->nz * (size_t)(bs * bs);
+  const size_t nvals = value_count(a);
   PetscScalar *ta;
   form_free(&d->t);
   ierr = transpose_pattern(a->m, nbc, a->i, a->j, bs, NULL, &ti, &tj, &tperm);CHKERRQ(ierr);
@@ -881,12 +910,11 @@ static PetscErrorCode MatMultAdd_SeqAIJHIP(Mat A, Vec xx, Vec yy, Vec zz) {   /*
 static PetscErrorCode MatMultTranspose_SeqAIJHIP(Mat A, Vec xx, Vec yy) { return product(A, PETSC_TRUE, xx, NULL, yy); }   /* aij.c:1124: VecSet(yy,0); Add */
 static PetscErrorCode MatMultTransposeAdd_SeqAIJHIP(Mat A, Vec xx, Vec zz, Vec yy) { return product(A, PETSC_TRUE, xx, zz, yy); }   /* aij.c:1078: yy = zz + A^T xx */
 
-/* how many times the values of a sequential matrix of this type have crossed to the device (tests: value updates with an
- * unchanged pattern must not add to it) */
-PetscErrorCode MatHIPMI355XGetUploadCount(Mat A, PetscInt *n) {
-  *n = 0;
-  if (!A || A->ops->mult != MatMult_SeqAIJHIP) SETERRQ(A ? HipObjComm(A) : 0, PETSC_ERR_ARG_WRONG, "sequential HIPMI355X matrix expected");
-  *n = SD(A)->n_uploads;
+/* "Is this my matrix": a sequential matrix of this type (AIJ or BAIJ: they share the constructor), NULL included in the answer.  What
+ * an entry point does with a no is its own: PETSC_ERR_ARG_WRONG with its text (seq_hip_check), zeros, or the diagonal block (seq_block) */
+static PetscBool is_seq_hip(Mat A) { return (PetscBool)(A && A->spptr && A->ops->mult == MatMult_SeqAIJHIP); }
+static PetscErrorCode seq_hip_check(Mat A, const char *text) {
+  if (!is_seq_hip(A)) SETERRQ(A ? HipObjComm(A) : 0, PETSC_ERR_ARG_WRONG, "%s", text);
   return 0;
 }
 /* the sequential matrix of this type an info call answers for: A itself, or the diagonal block of an MPIAIJ matrix of this type; else NULL */
@@ -894,9 +922,20 @@ static PetscErrorCode seq_block(Mat A, Mat *S) {
   PetscErrorCode ierr;
   Mat Ad = NULL;
   *S = NULL;
-  if (A->ops->mult == MatMult_SeqAIJHIP) { *S = A; return 0; }
+  if (!A) return 0;
+  if (is_seq_hip(A)) { *S = A; return 0; }
   if (!strcmp(HipObjTypeName(A), MATMPIAIJHIPMI355X)) { ierr = MatMPIAIJGetSeqAIJ(A, &Ad, NULL, NULL);CHKERRQ(ierr); }
-  if (Ad && Ad->ops->mult == MatMult_SeqAIJHIP) *S = Ad;
+  if (is_seq_hip(Ad)) *S = Ad;
+  return 0;
+}
+#define CHK_ASSEMBLED(A) do { if (!SA(A)->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled"); } while (0)
+
+/* how many times the values of a sequential matrix of this type have crossed to the device (tests: value updates with an
+ * unchanged pattern must not add to it) */
+PetscErrorCode MatHIPMI355XGetUploadCount(Mat A, PetscInt *n) {
+  *n = 0;
+  { PetscErrorCode ierr = seq_hip_check(A, "sequential HIPMI355X matrix expected");CHKERRQ(ierr); }
+  *n = SD(A)->n_uploads;
   return 0;
 }
 /* number of distinct (col - row) offsets of the index-compressed SpMV plan, 0 when the matrix streams plain 4-byte
@@ -904,7 +943,6 @@ static PetscErrorCode seq_block(Mat A, Mat *S) {
 PetscErrorCode MatHIPMI355XGetIndexCompression(Mat A, PetscInt *noffsets) {
   PetscErrorCode ierr; int ntab = 0;
   *noffsets = 0;
-  if (!A) return 0;
   ierr = seq_block(A, &A);CHKERRQ(ierr);
   if (!A) return 0;
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
@@ -916,7 +954,7 @@ PetscErrorCode MatHIPMI355XGetIndexCompression(Mat A, PetscInt *noffsets) {
 /* the blocked companion of a sequential matrix, if the analysis chose it: block size and number of blocks (0, 0: none) */
 PetscErrorCode MatHIPMI355XGetBlockedInfo(Mat A, PetscInt *bs, PetscInt *nblocks) {
   *bs = 0; *nblocks = 0;
-  if (!A || A->ops->mult != MatMult_SeqAIJHIP) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "not a sequential HIPMI355X AIJ matrix");
+  { PetscErrorCode ierr = seq_hip_check(A, "not a sequential HIPMI355X AIJ matrix");CHKERRQ(ierr); }
   if (SD(A)->b.plan) { *bs = SD(A)->b.bs; *nblocks = SD(A)->b.nblocks; }
   return 0;
 }
@@ -926,7 +964,7 @@ PetscErrorCode MatHIPMI355XGetBlockedInfo(Mat A, PetscInt *bs, PetscInt *nblocks
 PetscErrorCode MatHIPMI355XGetTiledInfo(Mat A, PetscInt *staged, PetscInt *remainder) {
   PetscErrorCode ierr; long s_ = 0, r_ = 0;
   *staged = 0; *remainder = 0;
-  if (!A || A->ops->mult != MatMult_SeqAIJHIP) return 0;
+  if (!is_seq_hip(A)) return 0;
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
   if (SD(A)->mat.tiled) CHKHIP(mi355x_spmv_tiled_info(SD(A)->mat.tiled, &s_, &r_, NULL, NULL, NULL));
   *staged = (PetscInt)s_; *remainder = (PetscInt)r_;
@@ -937,7 +975,6 @@ PetscErrorCode MatHIPMI355XGetTiledInfo(Mat A, PetscInt *staged, PetscInt *remai
 PetscErrorCode MatHIPMI355XGetRowPatterns(Mat A, PetscInt *npat) {
   PetscErrorCode ierr; int np_ = 0;
   *npat = 0;
-  if (!A) return 0;
   ierr = seq_block(A, &A);CHKERRQ(ierr);
   if (!A) return 0;
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
@@ -956,7 +993,6 @@ PetscErrorCode MatHIPMI355XGetRowPatterns(Mat A, PetscInt *npat) {
 PetscErrorCode MatHIPMI355XGetValuePatterns(Mat A, PetscInt *nvpat) {
   PetscErrorCode ierr; int nv = 0;
   *nvpat = 0;
-  if (!A) return 0;
   ierr = seq_block(A, &A);CHKERRQ(ierr);
   if (!A) return 0;
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
@@ -981,12 +1017,10 @@ PetscErrorCode MatHIPMI355XSetValuePatterns(Mat A, PetscBool on) {
   return 0;
 }
 
-/* row grouping of the SpMV plan: number of nodes Mat_CheckInode found (0: plain routines), groups the device plan stores
- * one column list for (0: the plan streams per-nonzero indices), and the shared indices stored */
 /* host builds of the explicit transpose / device-side value refreshes of it so far (tests: a time-stepping caller of
  * MatMultTranspose must not go back to the host for A^T) */
 PetscErrorCode MatHIPMI355XGetTransposeCounts(Mat A, PetscInt *builds, PetscInt *refreshes) {
-  if (!A || A->ops->mult != MatMult_SeqAIJHIP) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "not a sequential HIPMI355X AIJ matrix");
+  { PetscErrorCode ierr = seq_hip_check(A, "not a sequential HIPMI355X AIJ matrix");CHKERRQ(ierr); }
   if (builds) *builds = SD(A)->t_builds;
   if (refreshes) *refreshes = SD(A)->t_refreshes;
   return 0;
@@ -997,18 +1031,19 @@ PetscErrorCode MatHIPMI355XGetTransposeCounts(Mat A, PetscInt *builds, PetscInt 
 PetscErrorCode MatSeqAIJHIPGetInodes(Mat A, PetscInt *count, const PetscInt **sizes) {
   PetscErrorCode ierr;
   *count = 0; *sizes = NULL;
-  if (!A || A->ops->mult != MatMult_SeqAIJHIP) return 0;
+  if (!is_seq_hip(A)) return 0;
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);          /* runs Mat_CheckInode's restatement on the current pattern */
   *count = SA(A)->inode_count; *sizes = SA(A)->inode_size;
   return 0;
 }
 
+/* row grouping of the SpMV plan: number of nodes Mat_CheckInode found (0: plain routines), groups the device plan stores
+ * one column list for (0: the plan streams per-nonzero indices), and the shared indices stored */
 PetscErrorCode MatHIPMI355XGetInodeInfo(Mat A, PetscInt *nodes, PetscInt *groups, PetscInt *shared_indices) {
   PetscErrorCode ierr; int ng = 0; long ngj = 0;
   if (nodes) *nodes = 0;
   if (groups) *groups = 0;
   if (shared_indices) *shared_indices = 0;
-  if (!A) return 0;
   ierr = seq_block(A, &A);CHKERRQ(ierr);
   if (!A) return 0;
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
@@ -1026,7 +1061,7 @@ PetscErrorCode MatHIPMI355XGetInodeInfo(Mat A, PetscInt *nodes, PetscInt *groups
 PetscErrorCode MatMultTDotBegin_HIPMI355X(Mat A, Vec xx, Vec yy, PetscBool *ok) {
   PetscErrorCode ierr;
   *ok = PETSC_FALSE;
-  if (!A || A->ops->mult != MatMult_SeqAIJHIP) return 0;
+  if (!is_seq_hip(A)) return 0;
   HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
   const PetscScalar *x; PetscScalar *y; PetscDeviceCtx *dc; int ntab = 0;
   if (a->bs > 1 || d->cprow || a->m != a->n || xx == yy) return 0;
@@ -1056,7 +1091,7 @@ PetscErrorCode MatMultTDotBegin_HIPMI355X(Mat A, Vec xx, Vec yy, PetscBool *ok) 
 PetscErrorCode MatMultDiagonalScale_HIPMI355X(Mat A, Vec dd, Vec xx, Vec yy, PetscBool *ok) {
   PetscErrorCode ierr;
   *ok = PETSC_FALSE;
-  if (!A || A->ops->mult != MatMult_SeqAIJHIP) return 0;
+  if (!is_seq_hip(A)) return 0;
   HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
   const PetscScalar *x, *dg; PetscScalar *y; PetscDeviceCtx *dc;
   if (a->bs > 1 || xx == yy || dd == yy || xx->map->n != a->n || yy->map->n != a->m || dd->map->n != a->m) return 0;
@@ -1081,29 +1116,16 @@ PetscErrorCode MatMultDiagonalScale_HIPMI355X(Mat A, Vec dd, Vec xx, Vec yy, Pet
  * bits, two vector passes fewer.  The column-tiled product, the blocked companion and a compressed-row plan have no such epilogue, and
  * vectors of another type have no device array: MatMult and VecAYPX(r, -1, b) run as they are.  Pending deferred Vec work and stale
  * device values are settled as in MatMult_SeqAIJHIP: the upload first, the deferred queue by the vectors' accessors.
- * -mat_hipmi355x_residual <fused|calls> under the matrix's prefix (MatSetFromOptions, at any time), else globally as read when the device
- * copy was built (upload_pattern): no options table is searched per residual.  README "Multigrid" has the measurement behind the default. */
-#ifndef HIPMI355X_RESIDUAL_DEFAULT
-#define HIPMI355X_RESIDUAL_DEFAULT 1   /* 1 fused, 2 calls */
-#endif
-static PetscErrorCode residual_route_option(Mat A, const char *prefix, int *route) {
-  PetscErrorCode ierr;
-  char kind[16] = ""; PetscBool set = PETSC_FALSE;
-  *route = 0;
-  ierr = PetscOptionsGetString(prefix, "-mat_hipmi355x_residual", kind, sizeof(kind), &set);CHKERRQ(ierr);
-  if (!set) return 0;
-  if (strcmp(kind, "fused") && strcmp(kind, "calls")) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "-mat_hipmi355x_residual <fused|calls>, got %s", kind);
-  *route = strcmp(kind, "calls") ? 1 : 2;
-  return 0;
-}
-static int vec_on_device(Vec v) { return v && strstr(HipObjTypeName(v), "hipmi355x") != NULL; }
+ * -mat_hipmi355x_residual (the route table's ROUTE_AT_UPLOAD entry): two fields of the struct are read per residual, no options table
+ * is searched.  README "Multigrid" has the measurement behind the default. */
+static int vec_on_device(Vec v) { return v && v->data && strstr(HipObjTypeName(v), "hipmi355x") != NULL; }   /* a vector of the HIPMI355X types */
 static PetscErrorCode MatResidual_SeqAIJHIP(Mat A, Vec bb, Vec xx, Vec rr) {
   PetscErrorCode ierr;
   HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
   int route;
   if (rr == xx || rr == bb) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_IDN, "r must differ from b and from x");
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);   /* (builds the device copy if need be, and with it reads the global option) */
-  route = d->residual_route ? d->residual_route : d->residual_global ? d->residual_global : HIPMI355X_RESIDUAL_DEFAULT;
+  route = d->route[HROUTE_RESIDUAL] ? d->route[HROUTE_RESIDUAL] : d->residual_global ? d->residual_global : HIPMI355X_RESIDUAL_DEFAULT;
   if (route == 1 && a->bs <= 1 && vec_on_device(bb) && vec_on_device(xx) && vec_on_device(rr) &&
       xx->map->n == a->n && bb->map->n == a->m && rr->map->n == a->m) {
     if (d->mat.plan && !d->cprow && !d->mat.tiled && !d->b.plan) {
@@ -1129,7 +1151,7 @@ static PetscErrorCode MatResidual_SeqAIJHIP(Mat A, Vec bb, Vec xx, Vec rr) {
   return 0;
 }
 PetscErrorCode MatHIPMI355XGetResidualCounts(Mat A, PetscInt *fused, PetscInt *calls) {
-  if (!A || A->ops->mult != MatMult_SeqAIJHIP) SETERRQ(A ? HipObjComm(A) : 0, PETSC_ERR_ARG_WRONG, "not a sequential HIPMI355X AIJ matrix");
+  { PetscErrorCode ierr = seq_hip_check(A, "not a sequential HIPMI355X AIJ matrix");CHKERRQ(ierr); }
   if (fused) *fused = SD(A)->residual_fused;
   if (calls) *calls = SD(A)->residual_calls;
   return 0;
@@ -1146,10 +1168,12 @@ static PetscErrorCode MatGetDiagonal_SeqAIJHIP(Mat A, Vec v) {   /* aij.c:1040 *
     if (a->bs > 1) {
       PetscInt bs = a->bs, mbs = a->m;                 /* BAIJ: a->m counts block rows */
       for (PetscInt r = 0; r < mbs * bs; r++) h[r] = 0.0;
-      for (PetscInt br = 0; br < mbs; br++) for (PetscInt k = a->i[br]; k < a->i[br + 1]; k++) if (a->j[k] == br)
-        for (PetscInt q = 0; q < bs; q++) h[br * bs + q] = a->a[(size_t)k * bs * bs + q * bs + q];
+      for (PetscInt br = 0; br < mbs; br++) {
+        const PetscInt k = diag_position(a->i, a->j, br);
+        if (k >= 0) for (PetscInt q = 0; q < bs; q++) h[br * bs + q] = a->a[(size_t)k * bs * bs + q * bs + q];
+      }
     } else {
-      for (PetscInt r = 0; r < a->m; r++) { h[r] = 0.0; for (PetscInt k = a->i[r]; k < a->i[r + 1]; k++) if (a->j[k] == r) { h[r] = a->a[k]; break; } }
+      for (PetscInt r = 0; r < a->m; r++) { const PetscInt k = diag_position(a->i, a->j, r); h[r] = k >= 0 ? a->a[k] : 0.0; }
     }
     return VecRestoreArray(v, &h);
   }
@@ -1168,32 +1192,50 @@ static PetscBool device_values_current(Mat A) {
   Mat_SeqAIJHIP *d = SD(A);
   return (PetscBool)(d->mat.a && d->uploaded_state == HipObjState(A) && SA(A)->bs <= 1);
 }
+static PetscBool update_on_device(Mat A) {   /* -mat_hipmi355x_update_on_device <1|0>, with MatShift below */
+  PetscInt v = 1;
+  if (hip_mat_option(A, HOPT_UPDATE_DEV, &v)) return PETSC_TRUE;
+  return (PetscBool)(v != 0);
+}
+/* The device-side step of a value update.  updates_device: the update of the host copy also runs on the device copy -- its values are
+ * current, and, where they apply to the operation, by_option: -mat_hipmi355x_update_on_device says so; no_cprow: the device copy is not
+ * a compressed-row form.  Then one of: device_update_begin just before the kernels that change the values (dc: the stream to queue them
+ * on); device_update_skipped when the host copy alone was changed (the values travel at the next use); device_update_none when
+ * neither copy changes (a current device copy stays current over the wrapper's bump) */
+static PetscBool updates_device(Mat A, PetscBool by_option, PetscBool no_cprow) {
+  if (!device_values_current(A) || (no_cprow && SD(A)->cprow)) return PETSC_FALSE;
+  return (PetscBool)(!by_option || update_on_device(A));
+}
+static PetscErrorCode device_update_begin(Mat A, PetscDeviceCtx **dc) {
+  PetscErrorCode ierr = PetscDeviceGet(dc);CHKERRQ(ierr);
+  return device_values_changed(A);
+}
+static void device_update_skipped(Mat A) { SD(A)->uploaded_state = -1; }
+static void device_update_none(Mat A) { if (device_values_current(A)) SD(A)->uploaded_state = HipObjState(A) + 1; }
 static PetscErrorCode MatScale_SeqAIJHIP(Mat A, PetscScalar alpha) {   /* MatScale_SeqAIJ: dscal on a->a */
   PetscErrorCode ierr;
   HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
-  size_t vals = (size_t)a->nz * (size_t)(a->bs > 1 ? a->bs * a->bs : 1);
-  const PetscBool on_device = (PetscBool)(device_values_current(A) && alpha != 0.0);   /* alpha == 0: signs of zero, take the upload */
+  const size_t vals = value_count(a);
+  const PetscBool on_device = (PetscBool)(updates_device(A, PETSC_FALSE, PETSC_FALSE) && alpha != 0.0);   /* alpha == 0: signs of zero, take the upload */
   for (size_t k = 0; k < vals; k++) a->a[k] = alpha * a->a[k];
   if (on_device) {
     PetscDeviceCtx *dc;
-    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-    ierr = device_values_changed(A);CHKERRQ(ierr);
+    ierr = device_update_begin(A, &dc);CHKERRQ(ierr);
     CHKHIP(mi355x_vec_scale(dc->h, vals, alpha, d->mat.a));
-  }
+  } else device_update_skipped(A);
   return PetscLogFlops((PetscLogDouble)vals);
 }
 static PetscErrorCode MatZeroEntries_SeqAIJHIP(Mat A) {
   PetscErrorCode ierr;
   HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
   size_t vals = (size_t)(a->compact ? a->nz : a->maxnz) * (size_t)(a->bs > 1 ? a->bs * a->bs : 1);
-  const PetscBool on_device = (PetscBool)(device_values_current(A) && a->compact);
+  const PetscBool on_device = (PetscBool)(updates_device(A, PETSC_FALSE, PETSC_FALSE) && a->compact);
   memset(a->a, 0, sizeof(PetscScalar) * vals);
   if (on_device) {
     PetscDeviceCtx *dc;
-    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-    ierr = device_values_changed(A);CHKERRQ(ierr);
+    ierr = device_update_begin(A, &dc);CHKERRQ(ierr);
     CHKHIP(mi355x_memset(dc->h, d->mat.a, 0, sizeof(PetscScalar) * vals));
-  }
+  } else device_update_skipped(A);
   return 0;
 }
 /* MatDiagonalScale_SeqAIJ, aij.c:2055-2092: left scaling pass, then right scaling pass ((a*l)*r) */
@@ -1201,7 +1243,7 @@ static PetscErrorCode MatDiagonalScale_SeqAIJHIP(Mat A, Vec ll, Vec rr) {
   PetscErrorCode ierr;
   HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
   const PetscScalar *l = NULL, *r = NULL;
-  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  CHK_ASSEMBLED(A);
   if (a->bs > 1) {   /* MatDiagonalScale_SeqBAIJ, baij2.c:2026-2084: blocks column-major, v[r + c bs] *= l[row bs + r], then *= r[col bs + c]; on the
                       * host copy (a set-up operation of this type); the wrapper's state bump sends the values to the device at the next use */
     const PetscInt bs = a->bs, bs2 = bs * bs, mbs = a->m;
@@ -1229,20 +1271,18 @@ static PetscErrorCode MatDiagonalScale_SeqAIJHIP(Mat A, Vec ll, Vec rr) {
       ierr = VecRestoreArrayRead(rr, &r);CHKERRQ(ierr);
       ierr = PetscLogFlops((PetscLogDouble)a->nz);CHKERRQ(ierr);
     }
-    d->uploaded_state = -1;
+    device_update_skipped(A);
     return 0;
   }
   if (ll && ll->map->n != a->m) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_SIZ, "Left scaling vector wrong length");
   if (rr && rr->map->n != a->n) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_SIZ, "Right scaling vector wrong length");
-  const PetscBool on_device = (PetscBool)(device_values_current(A) && !d->cprow);
-  if (on_device) {   /* device pointers first: fetching the host arrays below must not be what makes them stale */
+  if (updates_device(A, PETSC_FALSE, PETSC_TRUE)) {   /* device pointers first: fetching the host arrays below must not be what makes them stale */
     const PetscScalar *dl = NULL, *dr = NULL; PetscDeviceCtx *dc;
-    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
     if (ll) { ierr = VecHIPGetRead(ll, &dl);CHKERRQ(ierr); }
     if (rr) { ierr = VecHIPGetRead(rr, &dr);CHKERRQ(ierr); }
-    ierr = device_values_changed(A);CHKERRQ(ierr);
+    ierr = device_update_begin(A, &dc);CHKERRQ(ierr);
     CHKHIP(mi355x_csr_diagonal_scale(dc->h, a->m, d->mat.i, d->mat.j, d->mat.a, dl, dr));
-  }
+  } else device_update_skipped(A);
   if (ll) {
     ierr = VecGetArrayRead(ll, &l);CHKERRQ(ierr);
     for (PetscInt i = 0; i < a->m; i++) for (PetscInt k = a->i[i]; k < a->i[i + 1]; k++) a->a[k] *= l[i];
@@ -1262,11 +1302,6 @@ static PetscErrorCode MatDiagonalScale_SeqAIJHIP(Mat A, Vec ll, Vec rr) {
  * host copy by loops on host threads, and -- when the device copy is current -- the same update queued on the device, no host wait.
  * -mat_hipmi355x_update_on_device <1|0> (default 1; per matrix, for these three only): 0 updates the host copy alone and the values
  * travel at the next use, the route a program took before these slots existed.  BAIJ, compressed-row forms: host copy only. */
-static PetscBool update_on_device(Mat A) {
-  PetscInt v = 1;
-  if (hip_mat_option(A, HOPT_UPDATE_DEV, &v)) return PETSC_TRUE;
-  return (PetscBool)(v != 0);
-}
 /* the serial number of A's pattern upload while the host pattern still is that pattern (entries are never removed: same nz), else 0 */
 static unsigned long long host_pattern_gen(Mat A) {
   Mat_SeqAIJHIP *d = SD(A);
@@ -1282,7 +1317,7 @@ static PetscErrorCode value_op_view(Mat A) {   /* inside a PETSc tree the parent
 typedef struct { PetscScalar *a; const PetscInt *pos, *ai, *aj; const PetscScalar *x; PetscScalar alpha; PetscInt *out; } ValUpd;
 static void upd_find_diag(void *c_, PetscInt lo, PetscInt hi) {
   ValUpd *c = (ValUpd *)c_;
-  for (PetscInt r = lo; r < hi; r++) { PetscInt k = c->ai[r]; while (k < c->ai[r + 1] && c->aj[k] != r) k++; c->out[r] = k < c->ai[r + 1] ? k : -1; }
+  for (PetscInt r = lo; r < hi; r++) c->out[r] = diag_position(c->ai, c->aj, r);
 }
 static void upd_shift(void *c_, PetscInt lo, PetscInt hi) { ValUpd *c = (ValUpd *)c_; for (PetscInt r = lo; r < hi; r++) c->a[c->pos[r]] = c->a[c->pos[r]] + c->alpha; }
 static void upd_axpy(void *c_, PetscInt lo, PetscInt hi) { ValUpd *c = (ValUpd *)c_; for (PetscInt k = lo; k < hi; k++) c->a[k] = c->a[k] + c->alpha * c->x[k]; }
@@ -1317,20 +1352,15 @@ static PetscErrorCode MatShift_SeqAIJHIP(Mat A, PetscScalar alpha) {
   const PetscInt *pos; PetscBool full;
   ierr = value_op_view(A);CHKERRQ(ierr);
   a = SA(A);
-  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  CHK_ASSEMBLED(A);
   if (a->bs > 1) {   /* BAIJ: the diagonal of every diagonal block (column-major blocks), on the host copy; the values travel at the next use */
     const PetscInt bs = a->bs, bs2 = bs * bs;
+    for (PetscInt br = 0; br < a->m; br++) if (diag_position(a->i, a->j, br) < 0) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "block row %d has no diagonal block", br);
     for (PetscInt br = 0; br < a->m; br++) {
-      PetscInt k = a->i[br];
-      while (k < a->i[br + 1] && a->j[k] != br) k++;
-      if (k == a->i[br + 1]) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "block row %d has no diagonal block", br);
-    }
-    for (PetscInt br = 0; br < a->m; br++) {
-      PetscInt k = a->i[br];
-      while (a->j[k] != br) k++;
+      const PetscInt k = diag_position(a->i, a->j, br);
       for (PetscInt q = 0; q < bs; q++) a->a[(size_t)k * bs2 + q * bs + q] = a->a[(size_t)k * bs2 + q * bs + q] + alpha;
     }
-    d->uploaded_state = -1;
+    device_update_skipped(A);
     return PetscLogFlops((PetscLogDouble)a->m * bs);
   }
   ierr = shift_diag_positions(A, &pos, &full);CHKERRQ(ierr);
@@ -1341,15 +1371,14 @@ static PetscErrorCode MatShift_SeqAIJHIP(Mat A, PetscScalar alpha) {
     ierr = MatAssemblyEnd(A, MAT_FINAL_ASSEMBLY);CHKERRQ(ierr);
     return PetscLogFlops((PetscLogDouble)a->m);
   }
-  const PetscBool on_device = (PetscBool)(update_on_device(A) && device_values_current(A) && !d->cprow);
+  const PetscBool on_device = updates_device(A, PETSC_TRUE, PETSC_TRUE);
   { ValUpd u = {a->a, pos, NULL, NULL, NULL, alpha, NULL};
     HipParallelRanges(a->m, upd_shift, &u); }
   if (on_device) {
     PetscDeviceCtx *dc;
-    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-    ierr = device_values_changed(A);CHKERRQ(ierr);
+    ierr = device_update_begin(A, &dc);CHKERRQ(ierr);
     CHKHIP(mi355x_csr_shift(dc->h, a->m, d->mat.i, d->mat.j, alpha, d->mat.a, NULL));
-  } else d->uploaded_state = -1;
+  } else device_update_skipped(A);
 #if defined(PETSCHIPMI355X_WITH_PETSC)
   HipStateIncrease(A);   /* MatShift of 3.3 leaves the state to the assembly of its default loop: what device_values_changed stamped is this bump */
 #endif
@@ -1407,7 +1436,7 @@ static PetscErrorCode subset_map_get(Mat Y, Mat X, const PetscInt *xcols, const 
 }
 static PetscErrorCode value_op_pair(Mat Y, Mat X, PetscBool cols) {   /* what MatAXPY and MatCopy ask of their two matrices */
   PetscErrorCode ierr;
-  if (!X || !Y || X->ops->mult != MatMult_SeqAIJHIP || Y->ops->mult != MatMult_SeqAIJHIP) SETERRQ(Y ? HipObjComm(Y) : 0, PETSC_ERR_SUP, "both matrices must be sequential HIPMI355X matrices");
+  if (!is_seq_hip(X) || !is_seq_hip(Y)) SETERRQ(Y ? HipObjComm(Y) : 0, PETSC_ERR_SUP, "both matrices must be sequential HIPMI355X matrices");
   ierr = value_op_view(X);CHKERRQ(ierr);
   ierr = value_op_view(Y);CHKERRQ(ierr);
   HipAIJ *x = SA(X), *y = SA(Y);
@@ -1416,7 +1445,7 @@ static PetscErrorCode value_op_pair(Mat Y, Mat X, PetscBool cols) {   /* what Ma
   return 0;
 }
 /* Y's update by an AXPY (or a basic copy into it) runs on the device copy too */
-static PetscBool axpy_on_device(Mat Y) { return (PetscBool)(update_on_device(Y) && device_values_current(Y) && !SD(Y)->cprow); }
+static PetscBool axpy_on_device(Mat Y) { return updates_device(Y, PETSC_TRUE, PETSC_TRUE); }
 /* the errors MatAXPY (copy: MatCopy) of this pair would return, with nothing changed.  When Y's device copy will take the update, a source
  * that is not current is sent first (reading it is a use; its pattern upload keys the map); a map built here serves the call that follows
  * (its `checked` argument) */
@@ -1456,10 +1485,9 @@ static PetscErrorCode axpy_subset(Mat Y, PetscScalar alpha, Mat X, const PetscIn
     HipParallelRanges(x->nz, upd_axpy_map, &u); }
   if (on_device) {
     PetscDeviceCtx *dc;
-    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-    ierr = device_values_changed(Y);CHKERRQ(ierr);
+    ierr = device_update_begin(Y, &dc);CHKERRQ(ierr);
     CHKHIP(mi355x_csr_axpy_map(dc->h, x->nz, dy->xtoy_d, alpha, dx->mat.a, dy->mat.a));
-  } else dy->uploaded_state = -1;
+  } else device_update_skipped(Y);
   return 0;
 }
 PetscErrorCode MatAXPY_SeqAIJHIP_Cols(Mat Y, PetscScalar alpha, Mat X, MatStructure str, const PetscInt *xcols, const PetscInt *ycols, PetscBool checked) {
@@ -1467,25 +1495,24 @@ PetscErrorCode MatAXPY_SeqAIJHIP_Cols(Mat Y, PetscScalar alpha, Mat X, MatStruct
   if (!checked) { ierr = MatValueOpsCheck_SeqAIJHIP(Y, X, str, xcols, ycols, PETSC_FALSE);CHKERRQ(ierr); }
   HipAIJ *x = SA(X), *y = SA(Y); Mat_SeqAIJHIP *dx = SD(X), *dy = SD(Y);
   if (str == SAME_NONZERO_PATTERN) {   /* daxpy on the value arrays: alpha == 0 returns at once (so does mi355x_vec_axpy) */
-    const size_t vals = (size_t)y->nz * (size_t)(y->bs > 1 ? y->bs * y->bs : 1);
+    const size_t vals = value_count(y);
     const PetscBool on_device = axpy_on_device(Y);
-    if (alpha == 0.0) {   /* nothing changes on either copy: a current device copy stays current over the wrapper's state bump */
-      if (device_values_current(Y)) dy->uploaded_state = HipObjState(Y) + 1;
-      return PetscLogFlops(2.0 * (PetscLogDouble)x->nz * (x->bs > 1 ? x->bs * x->bs : 1));
+    if (alpha == 0.0) {
+      device_update_none(Y);
+      return PetscLogFlops(2.0 * (PetscLogDouble)value_count(x));
     }
     if (on_device && X != Y) { ierr = MatSeqAIJHIPUpload(X);CHKERRQ(ierr); }
     { ValUpd u = {y->a, NULL, NULL, NULL, x->a, alpha, NULL};
       HipParallelRanges((PetscInt)vals, upd_axpy, &u); }
     if (on_device) {
       PetscDeviceCtx *dc;
-      ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-      ierr = device_values_changed(Y);CHKERRQ(ierr);
+      ierr = device_update_begin(Y, &dc);CHKERRQ(ierr);
       CHKHIP(mi355x_vec_axpy(dc->h, vals, alpha, dx->mat.a, dy->mat.a));
-    } else dy->uploaded_state = -1;
+    } else device_update_skipped(Y);
   } else {
     ierr = axpy_subset(Y, alpha, X, xcols, ycols, PETSC_FALSE);CHKERRQ(ierr);
   }
-  return PetscLogFlops(2.0 * (PetscLogDouble)x->nz * (x->bs > 1 ? x->bs * x->bs : 1));
+  return PetscLogFlops(2.0 * (PetscLogDouble)value_count(x));
 }
 static PetscErrorCode MatAXPY_SeqAIJHIP(Mat Y, PetscScalar alpha, Mat X, MatStructure str) {
   PetscErrorCode ierr = MatAXPY_SeqAIJHIP_Cols(Y, alpha, X, str, NULL, NULL, PETSC_FALSE);CHKERRQ(ierr);
@@ -1502,7 +1529,7 @@ PetscErrorCode MatCopy_SeqAIJHIP_Cols(Mat A, Mat B, MatStructure str, const Pets
   HipAIJ *a = SA(A), *b = SA(B); Mat_SeqAIJHIP *da = SD(A), *db = SD(B);
   if (str == SAME_NONZERO_PATTERN) { ierr = same_pattern(B, A, acols, bcols, &same);CHKERRQ(ierr); }
   if (!same) return axpy_subset(B, 1.0, A, acols, bcols, PETSC_TRUE);   /* any other structure: MatCopy_Basic */
-  const size_t vals = (size_t)a->nz * (size_t)(a->bs > 1 ? a->bs * a->bs : 1);
+  const size_t vals = value_count(a);
   /* B's own values do not matter: its device arrays for this pattern do.  B becomes current when A is (A is sent first when it is not) */
   const PetscBool on_device = (PetscBool)(update_on_device(B) && b->bs <= 1 && !da->cprow && !db->cprow && db->mat.a && db->mat.plan && host_pattern_gen(B));
   if (on_device) { ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr); }
@@ -1510,10 +1537,9 @@ PetscErrorCode MatCopy_SeqAIJHIP_Cols(Mat A, Mat B, MatStructure str, const Pets
     HipParallelRanges((PetscInt)vals, upd_copy, &u); }
   if (on_device) {
     PetscDeviceCtx *dc;
-    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-    ierr = device_values_changed(B);CHKERRQ(ierr);
+    ierr = device_update_begin(B, &dc);CHKERRQ(ierr);
     CHKHIP(mi355x_memcpy_d2d(dc->h, db->mat.a, da->mat.a, sizeof(PetscScalar) * vals));
-  } else db->uploaded_state = -1;
+  } else device_update_skipped(B);
   return 0;
 }
 static PetscErrorCode MatCopy_SeqAIJHIP(Mat A, Mat B, MatStructure str) { return MatCopy_SeqAIJHIP_Cols(A, B, str, NULL, NULL, PETSC_FALSE); }
@@ -1574,7 +1600,7 @@ static PetscErrorCode zero_rows_list(Mat A, PetscInt n, const PetscInt rows[], P
 static PetscErrorCode zero_rows_check(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, PetscBool keep, PetscBool cols) {
   PetscErrorCode ierr;
   HipAIJ *a = SA(A);
-  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  CHK_ASSEMBLED(A);
   if (a->bs > 1) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "MatZeroRows / MatZeroRowsColumns on scalar rows of a block matrix");
   for (PetscInt q = 0; q < n; q++) if (rows[q] < 0 || rows[q] >= a->m) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_OUTOFRANGE, "row %d out of range [0,%d)", rows[q], a->m);
   if (cols && a->m != a->n) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_SIZ, "Only works for square matrices: %d x %d", a->m, a->n);
@@ -1594,11 +1620,8 @@ static PetscErrorCode zero_rows_keep_pattern(Mat A, PetscInt n, const PetscInt r
   ierr = value_op_view(A);CHKERRQ(ierr);
   a = SA(A);
   ierr = zero_rows_check(A, n, rows, diag, PETSC_TRUE, cols);CHKERRQ(ierr);
-  if (!n) {   /* nothing changes on either copy: a current device copy stays current over the wrapper's state bump */
-    if (device_values_current(A)) d->uploaded_state = HipObjState(A) + 1;
-    return 0;
-  }
-  const PetscBool on_device = (PetscBool)(update_on_device(A) && device_values_current(A) && !d->cprow);
+  if (!n) { device_update_none(A); return 0; }
+  const PetscBool on_device = updates_device(A, PETSC_TRUE, PETSC_TRUE);
   const PetscScalar *x = NULL, *dx = NULL; PetscScalar *b = NULL, *db = NULL;
   ierr = zero_rows_list(A, n, rows, on_device);CHKERRQ(ierr);
   if (xx && on_device) {   /* the vectors stay on the device: b is updated there */
@@ -1616,14 +1639,13 @@ static PetscErrorCode zero_rows_keep_pattern(Mat A, PetscInt n, const PetscInt r
   }
   if (on_device) {
     PetscDeviceCtx *dc;
-    ierr = PetscDeviceGet(&dc);CHKERRQ(ierr);
-    ierr = device_values_changed(A);CHKERRQ(ierr);
+    ierr = device_update_begin(A, &dc);CHKERRQ(ierr);
     /* the two kernels write disjoint entries and disjoint rows of b: the columns of the rows that are not listed, then the listed rows */
     if (cols) CHKHIP(mi355x_csr_zero_columns(dc->h, d->mat.plan, d->mat.i, d->mat.j, d->mat.a, d->zr_mask_d, dx, db));
     CHKHIP(mi355x_csr_zero_rows(dc->h, (int)n, d->zr_rows_d, d->mat.i, d->mat.j, d->mat.a, diag, dx, db));
     if (xx) { ierr = VecHIPRestoreWrite(bb);CHKERRQ(ierr); HipStateIncrease(bb); }   /* as the host route's VecRestoreArray does */
     d->zr_device_updates++;
-  } else d->uploaded_state = -1;
+  } else device_update_skipped(A);
   return 0;
 }
 static PetscErrorCode zero_rows_new_pattern(Mat A, PetscInt n, const PetscInt rows[], PetscScalar diag, Vec xx, Vec bb);   /* per flavour, below */
@@ -1637,7 +1659,7 @@ static PetscErrorCode MatZeroRowsColumns_SeqAIJHIP(Mat A, PetscInt n, const Pets
 }
 /* uploads of a row list to the device / updates that ran on the device copy so far (tests: the same list given again is not sent again) */
 PetscErrorCode MatHIPMI355XGetZeroRowsCounts(Mat A, PetscInt *list_uploads, PetscInt *device_updates) {
-  if (!A || A->ops->mult != MatMult_SeqAIJHIP) SETERRQ(A ? HipObjComm(A) : 0, PETSC_ERR_ARG_WRONG, "not a sequential HIPMI355X AIJ matrix");
+  { PetscErrorCode ierr = seq_hip_check(A, "not a sequential HIPMI355X AIJ matrix");CHKERRQ(ierr); }
   if (list_uploads) *list_uploads = SD(A)->zr_list_uploads;
   if (device_updates) *device_updates = SD(A)->zr_device_updates;
   return 0;
@@ -1662,10 +1684,7 @@ static PetscErrorCode zero_rows_new_pattern(Mat A, PetscInt n, const PetscInt ro
     ierr = VecRestoreArrayRead(xx, &x);CHKERRQ(ierr);
     ierr = VecRestoreArray(bb, &b);CHKERRQ(ierr);
   }
-  if (!n) {
-    if (device_values_current(A)) SD(A)->uploaded_state = HipObjState(A) + 1;
-    return 0;
-  }
+  if (!n) { device_update_none(A); return 0; }
   ierr = device_free(A);CHKERRQ(ierr);
   for (PetscInt q = 0; q < n; q++) {
     const PetscInt r = rows[q];
@@ -1684,8 +1703,8 @@ static PetscErrorCode zero_rows_new_pattern(Mat A, PetscInt n, const PetscInt ro
  * Device route: the matrix's own device arrays (sent first when the host copy is newer, as for a product), the vectors on the device, the
  * sweeps level by level (csrc/sor.hip); t, the two diagonals and the level plan stay with the matrix -- the plan for one pattern upload,
  * the diagonals for one upload state and one (omega, fshift).  No host wait per call.
- * Host route: the same loops on the host copy -- a compressed-row form, or -mat_hipmi355x_sor host (per matrix; a matrix never asked reads
- * the global database).  Same bits: one product and one difference per entry, in storage order, on both.
+ * Host route: the same loops on the host copy -- a compressed-row form, or -mat_hipmi355x_sor host (the route table).  Same bits: one
+ * product and one difference per entry, in storage order, on both.
  * Every error is raised before anything is written. */
 enum { SOR_FWD_BITS = SOR_FORWARD_SWEEP | SOR_LOCAL_FORWARD_SWEEP, SOR_BWD_BITS = SOR_BACKWARD_SWEEP | SOR_LOCAL_BACKWARD_SWEEP };
 #define SOR_MINUS_DOT(sum, k0, k1) do { for (PetscInt k_ = (k0); k_ < (k1); k_++) (sum) -= aa[k_] * x[aj[k_]]; } while (0)
@@ -1769,7 +1788,7 @@ static PetscErrorCode MatSOR_SeqAIJHIP(Mat A, Vec bb, PetscReal omega, MatSORTyp
   int route;
   ierr = value_op_view(A);CHKERRQ(ierr);
   a = SA(A);
-  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  CHK_ASSEMBLED(A);
   if (a->bs > 1) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "MatSOR on a block matrix");
   if (flag & SOR_EISENSTAT) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "No support yet for Eisenstat");
   if (flag & (SOR_APPLY_UPPER | SOR_APPLY_LOWER)) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "SOR_APPLY_UPPER or SOR_APPLY_LOWER is not implemented");
@@ -1777,11 +1796,7 @@ static PetscErrorCode MatSOR_SeqAIJHIP(Mat A, Vec bb, PetscReal omega, MatSORTyp
   if (its <= 0 || lits <= 0) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "Relaxation requires global its %d and local its %d both positive", its, lits);
   if (bb == xx) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_IDN, "b and x vector cannot be the same");
   its *= lits;
-  if (!d->sor.route) {                                          /* never asked under its prefix: the global database, once per matrix */
-    ierr = sor_route_option(A, NULL, &route);CHKERRQ(ierr);
-    d->sor.route = route ? route : 1;
-  }
-  route = d->sor.route;
+  ierr = route_resolve(A, HROUTE_SOR, &route);CHKERRQ(ierr);
   if (route != 2) {
     PetscDeviceCtx *dc;
     const PetscScalar *db; PetscScalar *dx;
@@ -1825,7 +1840,7 @@ static PetscErrorCode MatSOR_SeqAIJHIP(Mat A, Vec bb, PetscReal omega, MatSORTyp
   return PetscLogFlops(2.0 * (PetscLogDouble)a->nz * (PetscLogDouble)its);
 }
 PetscErrorCode MatHIPMI355XGetSORInfo(Mat A, PetscInt *levels, PetscInt *launches_per_sweep, PetscInt *idiag_builds, PetscInt *plan_builds, PetscInt *device_applications) {
-  if (!A || A->ops->mult != MatMult_SeqAIJHIP) SETERRQ(A ? HipObjComm(A) : 0, PETSC_ERR_ARG_WRONG, "not a sequential HIPMI355X AIJ matrix");
+  { PetscErrorCode ierr = seq_hip_check(A, "not a sequential HIPMI355X AIJ matrix");CHKERRQ(ierr); }
   int nlev = 0, launches = 0;
   if (SD(A)->sor.plan) CHKHIP(mi355x_sor_plan_info(SD(A)->sor.plan, &nlev, &launches, NULL));
   if (levels) *levels = nlev;
@@ -1844,26 +1859,9 @@ PetscErrorCode MatHIPMI355XGetSORInfo(Mat A, PetscInt *levels, PetscInt *launche
  * launches kernels only.  The operands' device values follow the ordinary upload rule -- an operand changed on the device by MatScale,
  * MatShift, MatAXPY is not sent again.  The result's host values are brought back with one copy, its device copy is stamped current and
  * its derived forms go stale through device_values_changed like after every other device-side value change.
- * -mat_hipmi355x_product <device|host> (default device; under A's prefix, else the global database, read at the symbolic phase and kept
- * with the result): the host route is the sequential loop over host threads followed by the ordinary upload at the result's next use.
+ * -mat_hipmi355x_product (the route table; A's, read at the symbolic phase and kept with the result): the host route is the sequential
+ * loop over host threads followed by the ordinary upload at the result's next use.
  * A product ends in the result's own state bump (the reference's numeric phases end in MatAssemblyEnd). */
-static PetscErrorCode product_route_option(Mat A, const char *prefix, int *route) {
-  PetscErrorCode ierr;
-  char kind[16] = ""; PetscBool set = PETSC_FALSE;
-  *route = 0;
-  ierr = PetscOptionsGetString(prefix, "-mat_hipmi355x_product", kind, sizeof(kind), &set);CHKERRQ(ierr);
-  if (!set) return 0;
-  if (strcmp(kind, "device") && strcmp(kind, "host")) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "-mat_hipmi355x_product <device|host>, got %s", kind);
-  *route = strcmp(kind, "host") ? 1 : 2;
-  return 0;
-}
-static PetscErrorCode product_route(Mat A, int *route) {
-  PetscErrorCode ierr;
-  *route = SD(A)->product_route;
-  if (!*route) { ierr = product_route_option(A, NULL, route);CHKERRQ(ierr); }
-  if (!*route) *route = 1;
-  return 0;
-}
 static void product_free(Mat C) {
   Mat_SeqAIJHIP *d = SD(C);
   HipMatProduct *p = d ? d->prod : NULL;
@@ -1877,10 +1875,10 @@ static void product_free(Mat C) {
 /* operands of a product: assembled sequential AIJ matrices of this type (BAIJ has the constructor in common) */
 static PetscErrorCode product_operand(Mat X) {
   PetscErrorCode ierr;
-  if (!X->spptr || X->ops->mult != MatMult_SeqAIJHIP) SETERRQ(HipObjComm(X), PETSC_ERR_SUP, "Matrix products of Mat type %s", HipObjTypeName(X));
+  if (!is_seq_hip(X)) SETERRQ(HipObjComm(X), PETSC_ERR_SUP, "Matrix products of Mat type %s", HipObjTypeName(X));
   ierr = value_op_view(X);CHKERRQ(ierr);
   if (SA(X)->bs > 1) SETERRQ(HipObjComm(X), PETSC_ERR_SUP, "Matrix products of block matrices (%s)", HipObjTypeName(X));
-  if (!SA(X)->compact) SETERRQ(HipObjComm(X), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  CHK_ASSEMBLED(X);
   return 0;
 }
 /* the device copies of the operands current; compressed rows (an off-diagonal block's form) are not the CSR the kernel reads: host route */
@@ -1900,7 +1898,7 @@ static PetscBool product_noted(const HipMatProduct *p, int k, Mat X) {
 static PetscErrorCode product_reuse_check(Mat C, int kind, Mat X, Mat Y, HipMatProduct **p_) {
   PetscErrorCode ierr;
   HipMatProduct *p;
-  if (!C->spptr || C->ops->mult != MatMult_SeqAIJHIP || !SD(C)->prod || SD(C)->prod->kind != kind)
+  if (!is_seq_hip(C) || !SD(C)->prod || SD(C)->prod->kind != kind)
     SETERRQ(HipObjComm(X), PETSC_ERR_ARG_WRONG, "MAT_REUSE_MATRIX: the matrix is not the result of this operation");
   p = SD(C)->prod;
   { int route = p->route; ierr = product_operands_up(X, Y, &route);CHKERRQ(ierr);
@@ -1910,7 +1908,8 @@ static PetscErrorCode product_reuse_check(Mat C, int kind, Mat X, Mat Y, HipMatP
   *p_ = p;
   return 0;
 }
-/* the result as a matrix of the operands' type with the given pattern and zero values; the type's options go along (as MatDuplicate) */
+/* the result as a matrix of the operands' type with the given pattern and zero values; the type's options go along (as MatDuplicate), and
+ * of the routes those the table marks inherited -- as they stand in A: asked under its prefix, or kept from its first use */
 static PetscErrorCode product_result(Mat A, PetscInt m, PetscInt n, const PetscInt *ci, const PetscInt *cj, int kind, int route, Mat *C_, HipMatProduct **p_) {
   PetscErrorCode ierr;
   Mat C; HipMatProduct *p; PetscScalar *ca;
@@ -1923,7 +1922,7 @@ static PetscErrorCode product_result(Mat A, PetscInt m, PetscInt n, const PetscI
   HipFree(ca);
   ierr = value_op_view(C);CHKERRQ(ierr);
   memcpy(SD(C)->opt, SD(A)->opt, sizeof(SD(A)->opt)); memcpy(SD(C)->opt_set, SD(A)->opt_set, sizeof(SD(A)->opt_set));
-  SD(C)->product_route = SD(A)->product_route; SD(C)->sor.route = SD(A)->sor.route; SD(C)->coarsen_route = SD(A)->coarsen_route;
+  for (int k = 0; k < HROUTE_N; k++) if (hroute[k].inherited) SD(C)->route[k] = SD(A)->route[k];
   ierr = PetscMalloc(sizeof(*p), &p);CHKERRQ(ierr);
   memset(p, 0, sizeof(*p));
   p->kind = kind; p->route = route; p->symbolic_builds = 1;
@@ -2048,7 +2047,7 @@ static PetscErrorCode MatMatMultSymbolic_SeqAIJHIP(Mat A, Mat B, PetscReal fill,
   ierr = product_operand(A);CHKERRQ(ierr);
   ierr = product_operand(B);CHKERRQ(ierr);
   if (SA(A)->n != SA(B)->m) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_SIZ, "Matrix dimensions are incompatible, %d != %d", SA(A)->n, SA(B)->m);
-  ierr = product_route(A, &route);CHKERRQ(ierr);
+  ierr = route_resolve(A, HROUTE_PRODUCT, &route);CHKERRQ(ierr);
   ierr = product_operands_up(A, B, &route);CHKERRQ(ierr);
   ierr = matmult_symbolic(A, B, route, C);CHKERRQ(ierr);      /* (the new matrix's first state is its constructor's: the device copy just made stays current) */
   return 0;
@@ -2072,7 +2071,7 @@ static PetscErrorCode MatTranspose_SeqAIJHIP(Mat A, MatReuse reuse, Mat *B) {
   ierr = product_operand(A);CHKERRQ(ierr);
   if (reuse == MAT_INITIAL_MATRIX || !*B) {
     int route;
-    ierr = product_route(A, &route);CHKERRQ(ierr);
+    ierr = route_resolve(A, HROUTE_PRODUCT, &route);CHKERRQ(ierr);
     ierr = product_operands_up(A, NULL, &route);CHKERRQ(ierr);
     ierr = transpose_symbolic(A, route, B);CHKERRQ(ierr);
   }
@@ -2089,7 +2088,7 @@ static PetscErrorCode MatPtAP_SeqAIJHIP(Mat A, Mat P, MatReuse scall, PetscReal 
   if (scall == MAT_INITIAL_MATRIX) {
     int route;
     Mat Pt = NULL, AP = NULL;
-    ierr = product_route(A, &route);CHKERRQ(ierr);
+    ierr = route_resolve(A, HROUTE_PRODUCT, &route);CHKERRQ(ierr);
     ierr = product_operands_up(A, P, &route);CHKERRQ(ierr);
     ierr = transpose_symbolic(P, route, &Pt);CHKERRQ(ierr);
     ierr = transpose_numeric(P, Pt);CHKERRQ(ierr);             /* (the symbolic phase of Pt (A P) reads patterns only; the inner results are complete matrices all the same) */
@@ -2111,7 +2110,7 @@ static PetscErrorCode MatPtAP_SeqAIJHIP(Mat A, Mat P, MatReuse scall, PetscReal 
   return matmult_numeric(p->Pt, p->AP, *C);
 }
 PetscErrorCode MatHIPMI355XGetProductCounts(Mat C, PetscInt *symbolic_builds, PetscInt *device_numerics, PetscInt *host_numerics) {
-  if (!C || !C->spptr || C->ops->mult != MatMult_SeqAIJHIP || !SD(C)->prod) SETERRQ(C ? HipObjComm(C) : 0, PETSC_ERR_ARG_WRONG, "not the result of MatMatMult, MatTranspose or MatPtAP");
+  if (!is_seq_hip(C) || !SD(C)->prod) SETERRQ(C ? HipObjComm(C) : 0, PETSC_ERR_ARG_WRONG, "not the result of MatMatMult, MatTranspose or MatPtAP");
   if (symbolic_builds) *symbolic_builds = SD(C)->prod->symbolic_builds;
   if (device_numerics) *device_numerics = SD(C)->prod->device_numerics;
   if (host_numerics) *host_numerics = SD(C)->prod->host_numerics;
@@ -2132,28 +2131,10 @@ PetscErrorCode MatHIPMI355XGetProductCounts(Mat C, PetscInt *symbolic_builds, Pe
  *   row max / min   a row with fewer stored entries than the matrix has columns starts at the implicit (0.0, its smallest missing
  *                   column), a full row at its first entry, a row without entries gives (0.0, 0); replaced on cur < a (a < cur) only
  *   column norms    NORM_1 / NORM_2 / NORM_INFINITY: the sums of |a|, the roots of the sums of a * a, the max-abs of the columns
- * -mat_hipmi355x_reductions <device|host> (default device; host when the process has no device): the device route runs the row
+ * -mat_hipmi355x_reductions (the route table): the device route runs the row
  * reductions of csrc/mat_reduce.hip over the plain device value array -- the one every device-side value update writes, current after
  * MatSeqAIJHIPUpload whatever form the products take -- and its transposed form; the host route is the loops below over the host
  * copy.  Except for NORM_FROBENIUS the two give the same bits. */
-static PetscErrorCode reductions_route_option(Mat A, const char *prefix, int *route) {
-  PetscErrorCode ierr;
-  char kind[16] = ""; PetscBool set = PETSC_FALSE;
-  *route = 0;
-  ierr = PetscOptionsGetString(prefix, "-mat_hipmi355x_reductions", kind, sizeof(kind), &set);CHKERRQ(ierr);
-  if (!set) return 0;
-  if (strcmp(kind, "device") && strcmp(kind, "host")) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "-mat_hipmi355x_reductions <device|host>, got %s", kind);
-  *route = strcmp(kind, "host") ? 1 : 2;
-  return 0;
-}
-static PetscErrorCode reductions_route(Mat A, int *route) {
-  PetscErrorCode ierr;
-  *route = SD(A)->reductions_route;
-  if (!*route) { ierr = reductions_route_option(A, NULL, route);CHKERRQ(ierr); }
-  if (!*route) { int n = 0; *route = (mi355x_device_count(&n) || n < 1) ? 2 : 1; }
-  SD(A)->reductions_route = *route;       /* resolved once per matrix; MatSetFromOptions reads the option again */
-  return 0;
-}
 /* entry j of point row I bs + r (block row I starts at block a0) and its scalar column */
 #define RED_VALUE(m_, bs_, a0_, r_, e_) ((m_)->a[(size_t)(a0_) * (size_t)((bs_) * (bs_)) + (size_t)(e_) * (size_t)(bs_) + (size_t)(r_)])
 #define RED_COLUMN(m_, bs_, a0_, e_) ((m_)->j[(a0_) + (e_) / (bs_)] * (bs_) + (e_) % (bs_))
@@ -2226,7 +2207,7 @@ static PetscErrorCode red_work_get(Mat A, size_t bytes, void **w) {
  * user holds, and its rows are not the matrix's */
 static PetscErrorCode red_device_copy(Mat A, PetscDeviceCtx **dc) {
   PetscErrorCode ierr;
-  if (!SA(A)->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  CHK_ASSEMBLED(A);
   ierr = PetscDeviceGet(dc);CHKERRQ(ierr);
   ierr = MatSeqAIJHIPUpload(A);CHKERRQ(ierr);
   if (SD(A)->cprow) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "reductions over a compressed-row device copy");
@@ -2245,12 +2226,12 @@ static PetscErrorCode MatNorm_SeqAIJHIP(Mat A, NormType type, PetscReal *nrm) {
   PetscErrorCode ierr;
   HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
   const PetscInt bs = a->bs > 1 ? a->bs : 1, mrows = a->m * bs;
-  const size_t nvals = (size_t)a->nz * (size_t)(bs * bs);
+  const size_t nvals = value_count(a);
   int route;
   if (type == NORM_2) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "No support for two norm");
   if (type != NORM_1 && type != NORM_FROBENIUS && type != NORM_INFINITY) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_OUTOFRANGE, "Unknown NormType %d", (int)type);
-  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
-  ierr = reductions_route(A, &route);CHKERRQ(ierr);
+  CHK_ASSEMBLED(A);
+  ierr = route_resolve(A, HROUTE_REDUCTIONS, &route);CHKERRQ(ierr);
   if (route == 2) {
     if (type == NORM_FROBENIUS) {
       PetscReal s = 0.0;
@@ -2286,16 +2267,15 @@ static PetscErrorCode MatNorm_SeqAIJHIP(Mat A, NormType type, PetscReal *nrm) {
   }
   return PetscLogFlops(type == NORM_FROBENIUS ? 2.0 * (double)nvals : (double)nvals);
 }
-static int red_is_hip_vec(Vec v) { return v && v->data && strstr(HipObjTypeName(v), "hipmi355x") != NULL; }
 static PetscErrorCode row_extremum(Mat A, int op, Vec v, PetscInt idx[]) {
   PetscErrorCode ierr;
   HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
   const PetscInt bs = a->bs > 1 ? a->bs : 1, mrows = a->m * bs;
   int route;
-  if (!red_is_hip_vec(v)) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "the result must be a HIPMI355X vector");
+  if (!vec_on_device(v)) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "the result must be a HIPMI355X vector");
   if (v->map->n != A->rmap->n) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_SIZ, "Nonconforming matrix and vector");
-  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
-  ierr = reductions_route(A, &route);CHKERRQ(ierr);
+  CHK_ASSEMBLED(A);
+  ierr = route_resolve(A, HROUTE_REDUCTIONS, &route);CHKERRQ(ierr);
   if (route == 2) {
     PetscScalar *h;
     ierr = VecGetArray(v, &h);CHKERRQ(ierr);
@@ -2323,8 +2303,8 @@ static PetscErrorCode MatGetColumnNorms_SeqAIJHIP(Mat A, NormType type, PetscRea
   int route;
   const int op = type == NORM_1 ? MI355X_ROW_ABSSUM : (type == NORM_2 ? MI355X_ROW_SQSUM : MI355X_ROW_MAXABS);
   if (type != NORM_1 && type != NORM_2 && type != NORM_INFINITY) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "Unknown NormType %d", (int)type);
-  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
-  ierr = reductions_route(A, &route);CHKERRQ(ierr);
+  CHK_ASSEMBLED(A);
+  ierr = route_resolve(A, HROUTE_REDUCTIONS, &route);CHKERRQ(ierr);
   if (route == 2) host_col_reduce(a, op, norms);
   else if (a->n > 0) {
     PetscDeviceCtx *dc; void *w;
@@ -2341,35 +2321,24 @@ static PetscErrorCode MatGetColumnNorms_SeqAIJHIP(Mat A, NormType type, PetscRea
 /* ---------------------------------------------------------------- Coarsening ("MatCoarsenAggregate_C", what PCGAMG asks of a level operator)
  * Aggregates of a square sequential AIJ matrix: d = its diagonal, the strength mask |a_ij| > threshold sqrt(|d_i| |d_j|), and the
  * distance-2 MIS aggregation of the strong graph (csrc/coarsen.hip; include/mi355x_kernels.h states the contract).  agg[i] in
- * [0, *nagg) for every row, a host array.  -mat_hipmi355x_coarsen <device|host> (default device; host when the process has no device;
- * read the way -mat_hipmi355x_product is): the device route works on the device copy of the pattern and the values, uploaded under
- * the ordinary rule, and brings back the m numbers; the host route is the host twins over the host copy.  The same integers. */
+ * [0, *nagg) for every row, a host array.  -mat_hipmi355x_coarsen (the route table): the device route works on the device copy of the
+ * pattern and the values, uploaded under the ordinary rule, and brings back the m numbers; the host route is the host twins over the
+ * host copy.  The same integers. */
 static PetscInt coarsen_total_device = 0, coarsen_total_host = 0, coarsen_total_rounds = 0;
-static PetscErrorCode coarsen_route_option(Mat A, const char *prefix, int *route) {
-  PetscErrorCode ierr;
-  char kind[16] = ""; PetscBool set = PETSC_FALSE;
-  *route = 0;
-  ierr = PetscOptionsGetString(prefix, "-mat_hipmi355x_coarsen", kind, sizeof(kind), &set);CHKERRQ(ierr);
-  if (!set) return 0;
-  if (strcmp(kind, "device") && strcmp(kind, "host")) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "-mat_hipmi355x_coarsen <device|host>, got %s", kind);
-  *route = strcmp(kind, "host") ? 1 : 2;
-  return 0;
-}
 static PetscErrorCode MatCoarsenAggregate_SeqAIJHIP(Mat A, PetscReal threshold, PetscInt *nagg, PetscInt agg[]) {
   PetscErrorCode ierr;
   HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
-  int route = d->coarsen_route, n = 0, rounds = 0;
+  int route, n = 0, rounds = 0;
   if (strcmp(HipObjTypeName(A), MATSEQAIJHIPMI355X) || a->bs > 1) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "MatCoarsenAggregate for Mat type %s", HipObjTypeName(A));
-  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  CHK_ASSEMBLED(A);
   if (a->m != a->n) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_SIZ, "Matrix must be square, %d != %d", (int)a->m, (int)a->n);
-  if (!route) { ierr = coarsen_route_option(A, NULL, &route);CHKERRQ(ierr); }
-  if (!route) { int ndev = 0; route = (mi355x_device_count(&ndev) || ndev < 1) ? 2 : 1; }
+  ierr = route_resolve(A, HROUTE_COARSEN, &route);CHKERRQ(ierr);
   *nagg = 0;
   if (route == 2) {
     PetscScalar *diag; unsigned char *strong;
     ierr = PetscMalloc(sizeof(PetscScalar) * (size_t)PetscMax(a->m, 1), &diag);CHKERRQ(ierr);
     ierr = PetscMalloc((size_t)PetscMax(a->nz, 1), &strong);CHKERRQ(ierr);
-    for (PetscInt r = 0; r < a->m; r++) { diag[r] = 0.0; for (PetscInt k = a->i[r]; k < a->i[r + 1]; k++) if (a->j[k] == r) { diag[r] = a->a[k]; break; } }
+    for (PetscInt r = 0; r < a->m; r++) { const PetscInt k = diag_position(a->i, a->j, r); diag[r] = k >= 0 ? a->a[k] : 0.0; }
     int rc = mi355x_csr_strength_host((int)a->m, a->i, a->j, a->a, diag, threshold, strong);
     if (!rc) rc = mi355x_coarsen_mis2_host((int)a->m, a->i, a->j, strong, agg, &n);
     HipFree(diag); HipFree(strong);
@@ -2397,7 +2366,7 @@ static PetscErrorCode MatCoarsenAggregate_SeqAIJHIP(Mat A, PetscReal threshold, 
   return 0;
 }
 PetscErrorCode MatHIPMI355XGetCoarsenCounts(Mat A, PetscInt *device, PetscInt *host, PetscInt *rounds) {
-  if (A && (!A->spptr || A->ops->mult != MatMult_SeqAIJHIP)) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONG, "not a sequential HIPMI355X AIJ matrix");
+  if (A) { PetscErrorCode ierr = seq_hip_check(A, "not a sequential HIPMI355X AIJ matrix");CHKERRQ(ierr); }   /* (NULL: the totals of the process) */
   if (device) *device = A ? SD(A)->coarsen_device : coarsen_total_device;
   if (host) *host = A ? SD(A)->coarsen_host : coarsen_total_host;
   if (rounds) *rounds = A ? SD(A)->coarsen_rounds : coarsen_total_rounds;
@@ -2408,11 +2377,11 @@ PetscErrorCode MatHIPMI355XGetCoarsenCounts(Mat A, PetscInt *device, PetscInt *h
  * Route 1: out / idx are device arrays of the block's rows; the off-diagonal block's compressed-row device copy is walked through
  * its plan's row list, and the rows it does not list keep what out / idx hold (add) or get (0.0, 0), an empty row's result.
  * Route 2: host arrays.  ncols: the columns of the matrix the block is a part of (a row is full only with that many entries). */
-PetscErrorCode MatReductionsRoute_SeqAIJHIP(Mat A, int *route) { return reductions_route(A, route); }
+PetscErrorCode MatReductionsRoute_SeqAIJHIP(Mat A, int *route) { return route_resolve(A, HROUTE_REDUCTIONS, route); }
 PetscErrorCode MatBlockRowReduce_SeqAIJHIP(Mat A, int route, int op, PetscInt ncols, PetscBool add, PetscScalar *out, PetscInt *idx) {
   PetscErrorCode ierr;
   HipAIJ *a = SA(A); Mat_SeqAIJHIP *d = SD(A);
-  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  CHK_ASSEMBLED(A);
   if (a->bs > 1) SETERRQ(HipObjComm(A), PETSC_ERR_SUP, "blocks of an MPIAIJ matrix are point matrices");
   if (route == 2) { host_row_reduce(a, op, ncols, add, out, idx); return 0; }
   PetscDeviceCtx *dc; const int *rows = NULL; int nrows = (int)a->m;
@@ -2432,7 +2401,7 @@ PetscErrorCode MatBlockRowReduce_SeqAIJHIP(Mat A, int route, int op, PetscInt nc
 PetscErrorCode MatBlockColReduce_SeqAIJHIP(Mat A, int route, int op, PetscScalar *out_host) {
   PetscErrorCode ierr;
   HipAIJ *a = SA(A);
-  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  CHK_ASSEMBLED(A);
   if (route == 2) { host_col_reduce(a, op, out_host); return 0; }
   if (a->n <= 0) return 0;
   PetscDeviceCtx *dc; void *w;
@@ -2449,7 +2418,7 @@ PetscErrorCode MatBlockSquareSum_SeqAIJHIP(Mat A, int route, PetscReal *s) {
   PetscErrorCode ierr;
   HipAIJ *a = SA(A);
   *s = 0.0;
-  if (!a->compact) SETERRQ(HipObjComm(A), PETSC_ERR_ARG_WRONGSTATE, "matrix must be assembled");
+  CHK_ASSEMBLED(A);
   if (route == 2) { for (PetscInt k = 0; k < a->nz; k++) *s = *s + a->a[k] * a->a[k]; return 0; }
   if (a->nz <= 0) return 0;
   PetscDeviceCtx *dc;
@@ -2589,10 +2558,9 @@ static PetscErrorCode MatDuplicate_SeqAIJHIP(Mat A, MatDuplicateOption op, Mat *
   ierr = MatSetSizes(B, A->rmap->n, A->cmap->n, A->rmap->n, A->cmap->n);CHKERRQ(ierr);
   ierr = MatSetType(B, HipObjTypeName(A));CHKERRQ(ierr);
   ierr = adopt_csr(B, a->m, a->bs > 1 ? a->bs : 1, a->i, a->j, a->a);CHKERRQ(ierr);
-  if (op != MAT_COPY_VALUES) memset(SA(B)->a, 0, sizeof(PetscScalar) * (size_t)a->nz * (size_t)(a->bs > 1 ? a->bs * a->bs : 1));
+  if (op != MAT_COPY_VALUES) memset(SA(B)->a, 0, sizeof(PetscScalar) * value_count(a));
   memcpy(SD(B)->opt, SD(A)->opt, sizeof(SD(A)->opt)); memcpy(SD(B)->opt_set, SD(A)->opt_set, sizeof(SD(A)->opt_set));
-  SD(B)->cprow = SD(A)->cprow; SD(B)->sor.route = SD(A)->sor.route; SD(B)->product_route = SD(A)->product_route;
-  SD(B)->reductions_route = SD(A)->reductions_route; SD(B)->residual_route = SD(A)->residual_route; SD(B)->coarsen_route = SD(A)->coarsen_route;
+  SD(B)->cprow = SD(A)->cprow; memcpy(SD(B)->route, SD(A)->route, sizeof(SD(A)->route));
   SA(B)->keepnonzeropattern = a->keepnonzeropattern;
   *M = B;
   return 0;
@@ -2660,7 +2628,7 @@ PetscErrorCode MatSeqAIJGetArrays(Mat A, PetscInt *m, const PetscInt **i, const 
 
 /* ---- per-launch device timing used by bench.py (hipEvent pairs on the compute stream) ---- */
 PetscErrorCode MatHIPMI355XSetTiming(Mat A, PetscBool on) {
-  if (!A || A->ops->mult != MatMult_SeqAIJHIP) SETERRQ(A ? HipObjComm(A) : 0, PETSC_ERR_ARG_WRONG, "sequential HIPMI355X matrix expected");
+  { PetscErrorCode ierr = seq_hip_check(A, "sequential HIPMI355X matrix expected");CHKERRQ(ierr); }
   Mat_SeqAIJHIP *d = SD(A);
   d->timing = on; d->time_n = 0;
   if (on && !d->time_ev) {
@@ -2681,7 +2649,7 @@ PetscErrorCode MatTimingEnd(Mat A, mi355x_handle_t h) {
   return 0;
 }
 PetscErrorCode MatHIPMI355XGetTiming(Mat A, PetscInt *nlaunches, PetscLogDouble *total_ms) {
-  if (!A || A->ops->mult != MatMult_SeqAIJHIP) SETERRQ(A ? HipObjComm(A) : 0, PETSC_ERR_ARG_WRONG, "sequential HIPMI355X matrix expected");
+  { PetscErrorCode ierr = seq_hip_check(A, "sequential HIPMI355X matrix expected");CHKERRQ(ierr); }
   Mat_SeqAIJHIP *d = SD(A);
   double tot = 0.0;
   for (PetscInt k = 0; k < d->time_n; k++) {

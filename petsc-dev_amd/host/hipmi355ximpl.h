@@ -276,6 +276,11 @@ typedef struct {
   PetscInt symbolic_builds, device_numerics, host_numerics;
 } HipMatProduct;
 
+/* the options of the sequential AIJ types (host/aijhip.c, "the type's options"): the integer ones, HOPT_*, index Mat_SeqAIJHIP.opt[] and
+ * opt_set[]; the route options, HROUTE_* -- one of two words each -- index route[] and the route table hroute[] */
+enum { HOPT_IC = 0, HOPT_RP, HOPT_VP, HOPT_TILED, HOPT_TILED_SMIN, HOPT_BLOCKED, HOPT_UPDATE_DEV, HOPT_PR, HOPT_N };
+enum { HROUTE_SOR = 0, HROUTE_PRODUCT, HROUTE_REDUCTIONS, HROUTE_RESIDUAL, HROUTE_COARSEN, HROUTE_N };
+
 /* device mirror */
 typedef struct {
   HipDevForm mat;           /* the device copy of the matrix (compressed rows: the rows with entries only) */
@@ -313,32 +318,28 @@ typedef struct {
   PetscInt zr_list_uploads, zr_device_updates;
   /* MatSOR (host/aijhip.c, "MatSOR"): the level plan of the pattern upload plan_gen (csrc/sor.hip), and with the matrix the work vector t
    * and the inverted / plain diagonal -- on the device as built for the values of upload state idiag_state with (omega, fshift), on the
-   * host (the host route) for the object state h_state.  route: -mat_hipmi355x_sor <device|host> as MatSetFromOptions read it, or as the first
-   * MatSOR found it in the global database (0: not looked up yet, 1 device, 2 host).  The counts outlive the arrays: diagonal builds (either route), plan builds, applications on the device */
+   * host (the host route) for the object state h_state.  The counts outlive the arrays: diagonal builds (either route), plan builds,
+   * applications on the device */
   struct {
     mi355x_sor_plan_t plan; unsigned long long plan_gen;
     PetscScalar *d_idiag, *d_mdiag, *d_t; int idiag_state; PetscReal omega, fshift; PetscBool have;
     PetscScalar *h_idiag, *h_mdiag, *h_t; int h_state; PetscReal h_omega, h_fshift; PetscBool h_have; PetscInt h_m;
-    int route;
     PetscInt idiag_builds, plan_builds, device_applications;
   } sor;
   HipMatProduct *prod;       /* the matrix is the result of a product (NULL: an ordinary matrix) */
-  int product_route;         /* -mat_hipmi355x_product <device|host> as MatSetFromOptions read it under the matrix's prefix (0: not given there) */
-  /* MatNorm / MatGetRowMaxAbs / Max / Min / MatGetColumnNorms (host/aijhip.c, "Norms and row / column reductions"): -mat_hipmi355x_reductions
-   * <device|host> as MatSetFromOptions read it under the matrix's prefix (0: not given there), and the device work array the row results
-   * and their locations go to before the finishing pass or the copy to the caller's host array (red_cap bytes; goes with the pattern) */
-  int reductions_route;
+  /* MatNorm / MatGetRowMaxAbs / Max / Min / MatGetColumnNorms (host/aijhip.c, "Norms and row / column reductions"): the device work array
+   * the row results and their locations go to before the finishing pass or the copy to the caller's host array (red_cap bytes; goes
+   * with the pattern) */
   void *red_work; size_t red_cap;
-  /* "MatResidual_C" (host/aijhip.c): -mat_hipmi355x_residual <fused|calls> as MatSetFromOptions read it under the matrix's prefix (1 fused,
-   * 2 calls, 0: not given there), the global answer as read when the device copy was built, and how many residuals took the fused kernel /
-   * the product and VecAYPX */
-  int residual_route, residual_global;
-  PetscInt residual_fused, residual_calls;
-  /* "MatCoarsenAggregate_C" (host/aijhip.c): -mat_hipmi355x_coarsen <device|host> as MatSetFromOptions read it under the matrix's prefix
-   * (1 device, 2 host, 0: not given there), coarsenings of this matrix per route so far and the rounds of the last one on the device */
-  int coarsen_route;
+  PetscInt residual_fused, residual_calls;   /* "MatResidual_C" (host/aijhip.c): residuals that took the fused kernel / the product and VecAYPX */
+  /* "MatCoarsenAggregate_C" (host/aijhip.c): coarsenings of this matrix per route so far and the rounds of the last one on the device */
   PetscInt coarsen_device, coarsen_host, coarsen_rounds;
-  PetscInt opt[8]; PetscBool opt_set[8];   /* the type's options as MatSetFromOptions read them under the matrix's prefix (host/aijhip.c) */
+  PetscInt opt[HOPT_N]; PetscBool opt_set[HOPT_N];   /* the integer options as MatSetFromOptions read them under the matrix's prefix */
+  /* the route options (the table hroute[] in host/aijhip.c states each one's rule): route[k] is 1 or 2 for the option's first or second
+   * word (device / host, fused / calls) as MatSetFromOptions read it under the matrix's prefix -- or, for an option whose global answer
+   * is kept (sor, reductions), as the matrix's first use resolved it -- and 0 while neither has happened.  residual_global: what the
+   * global database said to -mat_hipmi355x_residual when the device copy was last built for a new pattern (0: nothing) */
+  int route[HROUTE_N], residual_global;
   /* per-launch device timing for bench.py (hipEvent pairs on the compute stream) */
   PetscBool timing; PetscInt time_n, time_cap; mi355x_event_t *time_ev;
 #if defined(PETSCHIPMI355X_WITH_PETSC)

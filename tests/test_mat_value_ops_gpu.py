@@ -1,6 +1,8 @@
 """MatShift / MatAXPY / MatCopy on the device copy of AIJ matrices: host and device copies updated side by side, no
 re-upload, the derived forms following by a gather.  Expected values are computed in numpy (`cur[diag] += a` and
-`cur[xtoy] += a * xa` are separate ufuncs: two roundings); comparisons are bit for bit unless said otherwise."""
+`cur[xtoy] += a * xa` are separate ufuncs: two roundings); comparisons are bit for bit unless said otherwise.  The last grid runs
+every operator that updates values in place (MatScale, MatZeroEntries, MatDiagonalScale and the zero-rows pair included) through the
+three states of the device copy."""
 import ctypes as C
 
 import numpy as np
@@ -415,6 +417,94 @@ def test_mpiaij_two_staged_ranks(built):
         m = re.search(r"rank %d/2: MatShift, MatAXPY SAME / SUBSET, MatCopy of MPIAIJ then MatMult bitexact=True garray lengths X (\d+) Y (\d+)" % k, out)
         assert m, out[-3000:]
         assert 0 < int(m.group(1)) < int(m.group(2)), "the run wants X's garray shorter than Y's: %s" % m.group(0)
+
+
+class Tri70:
+    """a 70-row tridiagonal whose row 66 has only its diagonal: two row blocks of a 64-wide wavefront, the second partly idle"""
+    n, lone, listed = 70, 66, np.array([2, 63, 64, 66], np.int32)
+
+    def __init__(self):
+        cols = [[r] if r == self.lone else [c for c in (r - 1, r, r + 1) if 0 <= c < self.n] for r in range(self.n)]
+        self.ai = np.concatenate([[0], np.cumsum([len(q) for q in cols])]).astype(np.int32)
+        self.aj = np.concatenate(cols).astype(np.int32)
+        self.rows = np.repeat(np.arange(self.n), np.diff(self.ai))
+        self.diag = np.flatnonzero(self.rows == self.aj)
+        nz = self.aj.size
+        self.aa = 2.0 + np.sin(np.arange(nz))
+        self.za = np.cos(np.arange(nz)) - 0.3
+        self.xa = 0.5 + 0.01 * np.arange(self.n)                        # X: the diagonal alone, a subset of the pattern
+        self.x, self.l, self.r = np.cos(0.3 * np.arange(self.n)), 1.0 + 0.1 * np.cos(np.arange(self.n)), 1.0 + 0.1 * np.sin(np.arange(self.n))
+
+    def apply(self, P, op, Y, Z, X, cur):
+        """one update of Y through the library and of cur in numpy"""
+        L = P.lib()
+        cur = cur.copy()
+        in_list = np.isin(self.rows, self.listed)
+        if op == "scale":
+            L.MatScale(Y.h, -0.37); cur = -0.37 * cur
+        elif op == "zero_entries":
+            L.MatZeroEntries(Y.h); cur = np.zeros(cur.size)
+        elif op == "diagonal_scale":
+            vl, vr = V(P, self.l), V(P, self.r)
+            L.MatDiagonalScale(Y.h, vl.h, vr.h); cur = (cur * self.l[self.rows]) * self.r[self.aj]
+        elif op == "shift":
+            Y.shift(0.37); cur[self.diag] += 0.37
+        elif op == "axpy_same":
+            Y.axpy(-1.3, Z, P.SAME_NONZERO_PATTERN); cur = cur + (-1.3) * self.za
+        elif op == "axpy_subset":
+            Y.axpy(0.25, X, P.SUBSET_NONZERO_PATTERN); cur[self.diag] += 0.25 * self.xa
+        elif op == "copy":
+            Z.copy(Y, P.SAME_NONZERO_PATTERN); cur = self.za.copy()
+        elif op in ("zero_rows", "zero_rows_columns"):
+            if op == "zero_rows":
+                Y.zero_rows(self.listed, 2.0)
+            else:
+                Y.zero_rows_columns(self.listed, 2.0); cur[np.isin(self.aj, self.listed)] = 0.0
+            cur[in_list] = 0.0; cur[self.diag[self.listed]] = 2.0
+        else:
+            raise AssertionError(op)
+        return cur
+
+
+VALUE_UPDATES = ("scale", "zero_entries", "diagonal_scale", "shift", "axpy_same", "axpy_subset", "copy", "zero_rows", "zero_rows_columns")
+ASK_THE_OPTION = ("shift", "axpy_same", "axpy_subset", "copy", "zero_rows", "zero_rows_columns")
+
+
+@pytest.mark.parametrize("state", ["current", "host_newer", "option_0"])
+@pytest.mark.parametrize("op", VALUE_UPDATES)
+def test_the_device_step_of_every_value_update(P, op, state):
+    """8. every operator that updates the values in place, in three states of the device copy: current (the update runs on it: no
+    upload), the host copy newer (MatSetValues and an assembly since the last use: the host copy alone is updated and the next use
+    sends it -- but MatCopy, which asks for the target's device arrays, not for its values, overwrites them there), and
+    -mat_hipmi355x_update_on_device 0 under the matrix's prefix (the operators that ask the option update the host copy alone)"""
+    L = P.lib()
+    t = Tri70()
+    vx, vy = V(P, t.x), V(P, np.zeros(t.n))
+    L.PetscOptionsClear()
+    try:
+        Y, Z, X = P.Mat.from_csr(t.ai, t.aj, t.aa), P.Mat.from_csr(t.ai, t.aj, t.za), P.Mat.from_csr(np.arange(t.n + 1, dtype=np.int32), np.arange(t.n, dtype=np.int32), t.xa)
+        Y.set_option(P.MAT_KEEP_NONZERO_PATTERN)
+        if state == "option_0":
+            L.MatSetOptionsPrefix(Y.h, b"vu_")
+            L.PetscOptionsSetValue(b"-vu_mat_hipmi355x_update_on_device", b"0")
+            L.MatSetFromOptions(Y.h)
+        Y.mult(vx, vy)
+        cur = t.aa.copy()
+        if state == "host_newer":
+            i, v = np.array([3], np.int32), np.array([7.25])
+            L.MatSetValues(Y.h, 1, i.ctypes.data, 1, i.ctypes.data, v.ctypes.data, P.INSERT_VALUES)
+            L.MatAssemblyBegin(Y.h, P.MAT_FINAL_ASSEMBLY); L.MatAssemblyEnd(Y.h, P.MAT_FINAL_ASSEMBLY)
+            cur[t.diag[3]] = 7.25
+        assert uploads(P, Y) == 1
+        cur = t.apply(P, op, Y, Z, X, cur)
+        assert uploads(P, Y) == 1, "the update itself sends nothing"
+        assert np.array_equal(bits(host_values(P, Y, cur.size)), bits(cur)), "host copy"
+        Y.mult(vx, vy)
+        assert np.array_equal(bits(vy.array()), bits(orc.matmult(t.ai, t.aj, cur, t.x)[0]))
+        on_device = {"current": True, "host_newer": op == "copy", "option_0": op not in ASK_THE_OPTION}[state]
+        assert uploads(P, Y) == (1 if on_device else 2)
+    finally:
+        L.PetscOptionsClear()
 
 
 @pytest.mark.parametrize("tri", ["", "-pc_factor_hipmi355x_trisolve sweeps:3"])
